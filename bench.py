@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the `ris` hot path on MI355X (BASELINE.json metric: query RNAs/sec in `ris`).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1: one process per GPU.  Under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...
   bench.py --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) this process is one rank;
   started plainly with --gpus N it starts the N ranks itself (fresh child processes, before anything here has
@@ -13,7 +13,11 @@ characters), reference defaults (W=70, delta=5, hash 8, -l 20 -e -6 -f -4 -g -8 
 full 50k x 50k job cannot be run or its 3.7e10 result lines stored: as planned there, a
 contiguous sample of the 50,000 queries runs against the FULL database.  The database is built once,
 untimed, by the library's own `db` path (GPU Raccess + host suffix array) in the reference's file
-format and stays resident in HBM.
+format and stays resident in HBM.  It is an input, not a measurement: ~45 s to build and 1.3 GB to
+keep, so it is cached in the work directory (--workdir, BENCH_WORKDIR, else the user's cache
+directory), and build() makes it there already on a machine with a GPU (prepare_database()).  A stamp
+next to it (database_stamp()) names the library, parameters and generator that built it; another
+build of them builds it again.
 
 A "step" is one batch of `--queries` consecutive queries per GPU through the whole `ris` path, FASTA
 text in -> result lines out: encode + suffix arrays, Raccess, seed search, ungapped extension, sort +
@@ -27,17 +31,29 @@ submitted inside the timed region is finished inside it.  Weak scaling: every ra
 (prb_gather_hits, on a stream and a host thread of its own, behind the next batch's search) and rank 0
 writes all lines.
 
-One JSON line is printed by rank 0 (contract in the task description) with
+One JSON line is printed by rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = the wall time of
+one timed step) with
   roofline     : the gapped kernel that takes longest - k_gapped_front (every post-ungapped hit) or tier 0 of the LDS
                  cascade (the hits the front kernel hands on): algorithmic bytes = 600 B per post-ungapped hit
                  (DESIGN.md "Measurement") / device time from HIP events on the library's stream,
                  against the 8 TB/s HBM peak; traffic, VALU instructions per hit, active lanes and VALU issue share
                  from the committed PMC passes (profiles/r03_pmc_gapped_*.json); stage_roofline has both kernels, the
                  gapped stage as a whole, the pairs -> hits stage and Raccess;
-  cpu_baseline : the unmodified reference (oracle/_ref/pRIblast.shipped, OpenMP) on the same queries
-                 against the first 1/`--cpu-db-fraction` of the same database built as a database of its own
-                 (a full-database query costs the reference ~760 core-seconds), with the measured rate,
-                 the linear scale factor and the scaled estimate kept apart.
+  cpu_baseline : --full only (null otherwise): the unmodified reference (oracle/_ref/pRIblast.shipped, OpenMP)
+                 on the same queries against the first 1/`--cpu-db-fraction` of the same database built as a
+                 database of its own (a full-database query costs the reference ~760 core-seconds), with the
+                 measured rate, the linear scale factor and the scaled estimate kept apart, and the GPU command
+                 line's lines on that sample compared with both builds of the reference.
+A plain run does nothing but the timed path: the CPU baseline and its comparisons take runs of their own
+(~35 s) and come with --full.
+
+--dump-outputs DIR writes what the last timed step computed, as .npy files (float64) for comparing two builds
+output for output (the inputs are fixed by the arguments):
+  hits.npy               : the final hits of a fixed, seeded sample of the database sequences (1 in 128 of them,
+                           fewer if the files would exceed 64 MB), one row per hit with the columns HIT_COLUMNS,
+                           rows in lexicographic order
+  base_pairs.npy         : their base pairs [n, 2] (query position, database position), hit after hit in that order
+  hits_per_query.npy     : the number of final hits of every query of the step (all of them, not the sample)
 """
 import argparse
 import collections
@@ -49,6 +65,9 @@ import tempfile
 import threading
 import time
 
+import numpy as np
+
+T_START = time.time()  # (for the log line on the time spent outside the timed steps)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -66,7 +85,23 @@ PMC_FILES = {"k_gapped_front": os.path.join(ROOT, "profiles", "r03_pmc_gapped_fr
              "k_gapped_lds<0, Tier0, Rec32, true>": os.path.join(ROOT, "profiles", "r03_pmc_gapped_tier0.json")}
 
 
-def parse():
+HIT_COLUMNS = ("query", "db_id", "db_id_start", "q_sp", "db_sp", "q_len", "db_len", "e_acc", "e_hyb", "e_tot", "bp_count", "page")
+DUMP_DB_SAMPLE = 128             # --dump-outputs: the hits of one database sequence in this many (seeded choice) ...
+DUMP_MAX_BYTES = 64 * 2 ** 20    # ... or fewer, so that the files stay within this
+
+
+def default_workdir():
+    """where the generated databases are cached: the user's cache directory (build() fills it on a machine with a GPU),
+    the temporary directory where that cannot be made"""
+    d = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "priblast_amd", "bench")
+    try:
+        os.makedirs(d, exist_ok=True)
+        return d
+    except OSError:
+        return os.path.join(tempfile.gettempdir(), "priblast_bench")
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -80,8 +115,67 @@ def parse():
                     help="the CPU baseline runs against the first 1/F of the database (0: sized so that a query costs ~20 core-s)")
     ap.add_argument("--force-comm", action="store_true", help="run the N > 1 code path (RCCL communicator, final hit gather) with one rank")
     ap.add_argument("--no-overlap", action="store_true", help="accessibilities of a batch inside its own step (no second context)")
-    ap.add_argument("--workdir", default=os.environ.get("BENCH_WORKDIR", os.path.join(tempfile.gettempdir(), "priblast_bench")))
-    return ap.parse_args()
+    ap.add_argument("--workdir", default=os.environ.get("BENCH_WORKDIR") or default_workdir(), help="cache of the generated databases")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own (CPU baseline)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def database_stamp():
+    """what a cached database depends on: the library that builds it (its `db` path and file format), the energy
+    parameters and the sequence generator - a hash of the three files"""
+    import hashlib
+    from priblast_amd import capi
+    h = hashlib.sha256()
+    for path in (capi.LIB_PATH, capi.PARAMS, os.path.join(ROOT, "tools", "gen_synthetic.py")):
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def build_database(ctx, dbprefix, db_seqs, length, log):
+    """the synthetic database of the workload (seed 1), by the library's own `db` path, unless it is cached already with
+    the stamp of the current library, parameters and generator (dbprefix.stamp, written last)"""
+    import gen_synthetic
+    from priblast_amd import capi
+    exts = ("bas", "seq", "acc", "nam", "ind")
+    stamp = database_stamp()
+    if all(os.path.exists(f"{dbprefix}.{e}") for e in exts) and os.path.exists(f"{dbprefix}.stamp"):
+        with open(f"{dbprefix}.stamp") as f:
+            if f.read().strip() == stamp:
+                return
+        log("the cached database was built by another build of the library: building it again")
+    t0 = time.time()
+    drecs = gen_synthetic.gen_fixed(db_seqs, length, 1, "db")
+    t1 = time.time()
+    capi.db_build(ctx, dbprefix + ".tmp", [r[0] for r in drecs], [r[1] for r in drecs], 0, 8, 70, 5)
+    if os.path.exists(f"{dbprefix}.stamp"):
+        os.remove(f"{dbprefix}.stamp")
+    for e in exts:
+        os.replace(f"{dbprefix}.tmp.{e}", f"{dbprefix}.{e}")
+    with open(f"{dbprefix}.stamp", "w") as f:
+        f.write(stamp + "\n")
+    ms, _ = ctx.stage_ms("raccess")
+    log(f"database built in {time.time() - t1:.1f} s (Raccess on the GPU: {ms / 1e3:.1f} s for {db_seqs} x {length} nt; "
+        f"sequence generation {t1 - t0:.1f} s)")
+
+
+def prepare_database():
+    """build()'s step on a machine with a GPU: the database of the default workload into the default work directory, in a
+    process of its own (its GPU context and the 48 GB Raccess workspace of the `db` path end with it).  No GPU: nothing."""
+    import torch  # (first, as in main(): the library then runs on the HIP runtime torch loaded)
+    from priblast_amd import capi
+    if not torch.cuda.is_available():
+        print("bench.py: no GPU, the benchmark's database is left to the first benchmark run", file=sys.stderr)
+        return
+    a = parse([])
+    os.makedirs(a.workdir, exist_ok=True)
+    with capi.Context(0) as ctx:
+        build_database(ctx, os.path.join(a.workdir, f"db_s{a.db_seqs}x{a.length}"), a.db_seqs, a.length,
+                       lambda msg: print(f"[bench] {msg}", file=sys.stderr, flush=True))
 
 
 def pmc_of(kernel):
@@ -147,10 +241,45 @@ def result_rows(path):
     return rows, per_query
 
 
+def _runs(starts, counts):
+    """the indices of consecutive runs [starts[i], starts[i] + counts[i]), run after run"""
+    starts, counts = np.asarray(starts, np.int64), np.asarray(counts, np.int64)
+    return np.repeat(starts - np.cumsum(counts) + counts, counts) + np.arange(counts.sum(), dtype=np.int64)
+
+
+def dump_outputs(d, pages, nq, db_seqs, log):
+    """--dump-outputs: the final hits of the last timed step (pages = [(hits, bp)] per database page, `query` < nq) as
+    the .npy files the module docstring lists"""
+    os.makedirs(d, exist_ok=True)
+    per_query = np.zeros(nq)
+    for hits, _ in pages:
+        per_query += np.bincount(hits["query"], minlength=nq)
+    chosen = np.random.default_rng(1).permutation(db_seqs)[:max(1, db_seqs // DUMP_DB_SAMPLE)]
+    while True:
+        keep = np.zeros(db_seqs, bool)
+        keep[chosen] = True
+        rows, pairs = [], []
+        for p, (hits, bp) in enumerate(pages):
+            h = hits[keep[hits["db_id"]]]
+            rows.append(np.column_stack([h[c] for c in HIT_COLUMNS[:-1]] + [np.full(len(h), p)]).astype(np.float64))
+            pairs.append(bp[_runs(h["bp_offset"], h["bp_count"])])
+        rows, pairs = np.concatenate(rows), np.concatenate(pairs).astype(np.float64)
+        if rows.nbytes + pairs.nbytes <= DUMP_MAX_BYTES or len(chosen) == 1:
+            break
+        chosen = chosen[:len(chosen) // 2]
+    order = np.lexsort(rows.T[::-1])
+    cnt = rows[:, HIT_COLUMNS.index("bp_count")].astype(np.int64)
+    pairs = pairs[_runs((np.cumsum(cnt) - cnt)[order], cnt[order])]
+    out = {"hits": rows[order], "base_pairs": pairs, "hits_per_query": per_query}
+    for name, arr in out.items():
+        np.save(os.path.join(d, f"{name}.npy"), arr)
+    log(f"outputs of the last step in {d}: {len(rows)} hits of {len(chosen)} of the {db_seqs} database sequences, "
+        f"{len(pairs)} base pairs, {int(per_query.sum())} final hits in all")
+
+
 def cpu_baseline(a, ctx, workdir, qnames, qseqs, log):
     """Reference `ris` (shipped flags, OpenMP, one query per thread) against a fraction of the database."""
     import gen_synthetic
-    from priblast_amd import capi
     if a.cpu_queries == 0:
         return None
     ref = os.path.join(ROOT, "oracle", "_ref", "pRIblast.shipped")
@@ -171,11 +300,7 @@ def cpu_baseline(a, ctx, workdir, qnames, qseqs, log):
     nsub = max(1, a.db_seqs // frac)
     frac = a.db_seqs / nsub
     sub = os.path.join(workdir, f"dbfrac_s{nsub}x{a.length}")
-    if not all(os.path.exists(f"{sub}.{e}") for e in ("bas", "seq", "acc", "nam", "ind")):
-        drecs = gen_synthetic.gen_fixed(nsub, a.length, 1, "db")  # = the first nsub sequences of the full database
-        capi.db_build(ctx, sub + ".tmp", [r[0] for r in drecs], [r[1] for r in drecs], 0, 8, 70, 5)
-        for e in ("bas", "seq", "acc", "nam", "ind"):
-            os.replace(f"{sub}.tmp.{e}", f"{sub}.{e}")
+    build_database(ctx, sub, nsub, a.length, log)  # = the first nsub sequences of the full database
     sample = os.path.join(workdir, f"cpu_sample_{n}.fa")
     gen_synthetic.write_fasta(sample, zip(qnames[:n], qseqs[:n]))
     out = os.path.join(workdir, "cpu_sample.out")
@@ -292,7 +417,6 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
-    import numpy as np
     import torch
     import torch.distributed as dist
     import gen_synthetic
@@ -330,22 +454,13 @@ def main():
     tag = f"s{a.db_seqs}x{a.length}"
     dbprefix = os.path.join(a.workdir, f"db_{tag}")
     nq_total = (a.steps + a.warmup + 1) * a.queries * world
-    t0 = time.time()
     qrecs = gen_synthetic.gen_fixed(nq_total, a.length, 2, "q")  # = the first nq_total queries of the 50,000
     qnames, qseqs = [r[0] for r in qrecs], [r[1] for r in qrecs]
 
     ctx = capi.Context(local)
     ctx2 = None if a.no_overlap else capi.Context(local)  # accessibilities of the next batch, on its own stream
-    if rank == 0 and not all(os.path.exists(f"{dbprefix}.{e}") for e in ("bas", "seq", "acc", "nam", "ind")):
-        drecs = gen_synthetic.gen_fixed(a.db_seqs, a.length, 1, "db")
-        t1 = time.time()
-        capi.db_build(ctx, dbprefix + ".tmp", [r[0] for r in drecs], [r[1] for r in drecs], 0, 8, 70, 5)
-        for e in ("bas", "seq", "acc", "nam", "ind"):
-            os.replace(f"{dbprefix}.tmp.{e}", f"{dbprefix}.{e}")
-        ms, _ = ctx.stage_ms("raccess")
-        log(f"database built in {time.time() - t1:.1f} s (Raccess on the GPU: {ms / 1e3:.1f} s for {a.db_seqs} x {a.length} nt; "
-            f"sequence generation {t1 - t0:.1f} s)")
-        del drecs
+    if rank == 0:
+        build_database(ctx, dbprefix, a.db_seqs, a.length, log)
     barrier()
     t1 = time.time()
     db = capi.Db(ctx, dbprefix)
@@ -404,6 +519,8 @@ def main():
         del sets
         if rank != 0:
             return
+        if a.dump_outputs and k == a.warmup + a.steps - 1:
+            state["last"] = pages  # (the records of the last timed step, kept for --dump-outputs)
         t0 = time.perf_counter()
         lines, nbytes = capi.write_lines(db, names, qlen, pages, opts.output_style, state["id"], devnull)
         state["id"] += lines
@@ -456,6 +573,7 @@ def main():
         if state["prep"] is not None:
             state["prep"].join()
 
+    setup_s = time.time() - T_START
     for k in range(a.warmup):
         step(k)
     drain()
@@ -539,8 +657,12 @@ def main():
                     "achieved": ra_nt * RACCESS_BYTES_PER_NT / 1e9 / (ra_ms / 1e3) if ra_ms > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "logsumexp_per_s": ra_nt * RACCESS_LSE_PER_NT / (ra_ms / 1e3) if ra_ms > 0 else 0.0, "ms_per_step": ra_ms / a.steps}},
         }
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, state.pop("last"), a.queries * world, a.db_seqs, log)
         # (N > 1: the other ranks wait at the closing barrier meanwhile; the sample is bounded to ~20 s of wall time)
-        res["cpu_baseline"] = cpu_baseline(a, ctx, a.workdir, qnames, qseqs, log)
+        res["cpu_baseline"] = cpu_baseline(a, ctx, a.workdir, qnames, qseqs, log) if a.full else None
+        log(f"outside the steps: {setup_s:.1f} s before the first (imports, contexts, database), "
+            f"{time.perf_counter() - t - dt:.1f} s from the last to the result line")
         os.write(json_fd, (json.dumps(res) + "\n").encode())
     if state["prep"] is not None and state["prep"].qb is not None:
         state["prep"].qb.close()

@@ -305,3 +305,46 @@ def test_fast_generator_replays_the_seeded_python_stream():
         assert gen_synthetic.gen_fixed(n, L, seed, "x") == list(gen_synthetic.gen(n, L, seed, "x"))
     arr = gen_synthetic._fixed_fast(30, 500, 2, "ACGU")  # the fast path itself, not its fallback
     assert [r.tobytes().decode() for r in arr] == [s for _, s in gen_synthetic.gen(30, 500, 2, "q")]
+
+
+def test_bench_dump_outputs_sorted_sampled_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on synthetic hit records: the sampled hits come out in lexicographic order with their own
+    base pairs, every hit is counted per query, the files do not depend on the order the records arrive in, and the size
+    cap shrinks the sample of database sequences."""
+    import bench
+    rng = np.random.default_rng(0)
+
+    def page(n, ndb, nq):
+        h = np.zeros(n, capi.HIT_DTYPE)
+        h["query"], h["db_id"] = rng.integers(0, nq, n), rng.integers(0, ndb, n)
+        h["q_sp"], h["e_tot"], h["bp_count"] = rng.integers(0, 2000, n), rng.normal(size=n), rng.integers(1, 30, n)
+        h["bp_offset"] = np.cumsum(h["bp_count"]) - h["bp_count"]
+        bp = np.zeros((int(h["bp_count"].sum()), 2), np.int32)
+        for x in h:  # pair j of a hit: (its q_sp, j)
+            bp[x["bp_offset"]:x["bp_offset"] + x["bp_count"]] = np.stack([np.full(x["bp_count"], x["q_sp"]), np.arange(x["bp_count"])], 1)
+        return h[rng.permutation(n)], bp
+
+    pages = [page(20000, 1000, 16), page(5000, 1000, 16)]
+    bench.dump_outputs(str(tmp_path / "a"), pages, 16, 1000, lambda m: None)
+    hits, pairs = np.load(tmp_path / "a" / "hits.npy"), np.load(tmp_path / "a" / "base_pairs.npy")
+    assert hits.dtype == pairs.dtype == np.float64 and hits.shape[1] == len(bench.HIT_COLUMNS) and len(hits) > 0
+    assert (np.lexsort(hits.T[::-1]) == np.arange(len(hits))).all()
+    col = bench.HIT_COLUMNS.index
+    # the sample: every hit of the seeded choice of database sequences (1 in 128 of 1000: 7), and nothing else
+    chosen = np.random.default_rng(1).permutation(1000)[:1000 // bench.DUMP_DB_SAMPLE]
+    assert set(hits[:, col("db_id")].astype(int)) <= set(chosen.tolist())
+    assert len(hits) == sum(int(np.isin(h["db_id"], chosen).sum()) for h, _ in pages)
+    o = 0
+    for r in hits:
+        n = int(r[col("bp_count")])
+        assert (pairs[o:o + n, 0] == r[col("q_sp")]).all() and (pairs[o:o + n, 1] == np.arange(n)).all()
+        o += n
+    assert o == len(pairs)
+    assert np.load(tmp_path / "a" / "hits_per_query.npy").sum() == 25000
+    bench.dump_outputs(str(tmp_path / "b"), [(h[::-1].copy(), bp) for h, bp in pages], 16, 1000, lambda m: None)
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    bench.dump_outputs(str(tmp_path / "c"), pages, 16, 1000, lambda m: None)
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) < 20000 + 3 * 128
+    assert 0 < len(np.load(tmp_path / "c" / "hits.npy")) < len(hits)

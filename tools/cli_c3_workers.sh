@@ -5,9 +5,9 @@
 N=${1:-64}
 B=${2:-16}
 HERE=$(cd "$(dirname "$0")/.." && pwd)
-W=${BENCH_WORKDIR:-/tmp/priblast_bench}
+W=${BENCH_WORKDIR:-$(cd "$HERE" && python3 -c "import bench; print(bench.default_workdir())")}
 BIN=$HERE/priblast_amd/bin/pRIblast-hip
-[ -f "$W/db_s50000x2000.ind" ] || python3 "$HERE/bench.py" --cpu-queries 0 --steps 1 --warmup 0 > /dev/null 2> "$W.build.log" || exit 1
+(cd "$HERE" && BENCH_WORKDIR="$W" python3 -c "import bench; bench.prepare_database()") 2> "$W.build.log" || exit 1
 python3 "$HERE/tools/gen_synthetic.py" -n "$N" -L 2000 --seed 2 --prefix q -o "$W/cli_q.fa" || exit 1
 t() { local s=$(date +%s%N); "$@" || exit 1; local e=$(date +%s%N); echo "$(( (e - s) / 1000000 )) ms: $DESC"; }
 DESC="1 worker, batches of $B" PRB_BATCH=$B PRB_DEVICES=0 t "$BIN" ris -i "$W/cli_q.fa" -o "$W/cli_1.out" -d "$W/db_s50000x2000"

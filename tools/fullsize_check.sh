@@ -4,9 +4,9 @@
 # line, every result line compared (Id column aside).  usage: tools/fullsize_check.sh [N=4]
 N=${1:-4}
 HERE=$(cd "$(dirname "$0")/.." && pwd)
-W=${BENCH_WORKDIR:-/tmp/priblast_bench}
+W=${BENCH_WORKDIR:-$(cd "$HERE" && python3 -c "import bench; print(bench.default_workdir())")}
 mkdir -p "$W"
-[ -f "$W/db_s50000x2000.ind" ] || python3 "$HERE/bench.py" --cpu-queries 0 --steps 1 --warmup 0 > /dev/null 2> "$W.build.log" || exit 1
+(cd "$HERE" && BENCH_WORKDIR="$W" python3 -c "import bench; bench.prepare_database()") 2> "$W.build.log" || exit 1
 python3 "$HERE/tools/gen_synthetic.py" -n "$N" -L 2000 --seed 2 --prefix q -o "$W/full_q.fa" || exit 1
 s=$(date +%s)
 "$HERE/priblast_amd/bin/pRIblast-hip" ris -i "$W/full_q.fa" -o "$W/full_gpu.out" -d "$W/db_s50000x2000" || exit 1

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-round}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
 echo "bench done"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --cpu-queries 0 > $OUT/bench_prof.json 2> $OUT/bench_prof.err || { tail -5 $OUT/bench_prof.err; exit 1; }
 cp $(find $OUT/prof -name "*kernel_stats.csv" | head -1) $OUT/bench_default_kernel_stats.csv
