@@ -91,7 +91,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * ahead, beside the sub-batch before), "ungapped" (one-pass form: k_seed_extend, seeds found and extended), "sort",
  * "filter", "gapped_front" (the kernel in front of the gapped cascade: the hits whose two directions find nothing;
  * "gapped_front_hits": launches = hits it completed), "gapped" (LDS tier 0; "gapped_tier0_hits": launches = hits that entered it),
- * "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow" (wavefront-per-hit kernel), "traceback", "traceback_slow";
+ * "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow" (wavefront-per-hit kernel), "traceback", "traceback_slow",
+ * "summary" (prb_search_page_summary: pair heads, segment starts and the per-pair fold; launches = 3 per sub-batch);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -172,6 +173,32 @@ const int32_t *prb_hitset_basepairs(const prb_hitset *hs, int64_t *count);
 void prb_hitset_counts(const prb_hitset *hs, int64_t counts[3]);
 void prb_hitset_free(prb_hitset *hs);
 
+/* ---- per-pair summaries (`ris -t`): the final hits reduced on the device, one record per (query, database
+ * sequence) pair that has at least one final hit.  The hits are exactly those prb_search_page(..., 3, ...) returns
+ * with the same options (any output_style); their order there is the "output order" below.
+ *   hits      number of final hits of the pair
+ *   e_min     smallest e_tot; the best hit is the FIRST hit in output order with that e_tot
+ *   e_sum     sum of e_tot over the pair's hits, added left to right in output order, from 0.0
+ *   e_acc / e_hyb, bp_first / bp_last   the best hit's energies and its first and last base pair, as
+ *             prb_hitset_basepairs gives them with output_style 0 (the simplified form, SURVEY a17 quirk included)
+ * Records come query by query (ascending), and within a query in the order of the pairs' first hits.  The hit
+ * records and base pairs never leave the device.  Argument checks and option limits are those of prb_search_page;
+ * the device time of the reduction is the stage "summary" of prb_ctx_stage_ms. */
+typedef struct prb_pair_summary {
+  int32_t query, db_id;            /* index in the batch, sequence index in the page */
+  int64_t hits;
+  double e_min, e_sum, e_acc, e_hyb;
+  int32_t bp_first[2], bp_last[2]; /* (q, db) pairs; db in the page's reversed text, as in prb_hitset_basepairs */
+} prb_pair_summary;
+typedef struct prb_pairset prb_pairset;
+int prb_search_page_summary(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                            prb_pairset **out);
+int64_t prb_pairset_size(const prb_pairset *ps);
+const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps);
+/* the same stage counts as prb_hitset_counts: seeds, after ungapped+filter, final hits */
+void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]);
+void prb_pairset_free(prb_pairset *ps);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -187,6 +214,17 @@ typedef struct prb_page_hits {
 int prb_write_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                     const prb_page_hits *pages, int32_t npages, int32_t output_style, int64_t id0, int fd,
                     int64_t *lines, int64_t *bytes);
+/* The summary lines of one batch (`ris -t`), grouped and numbered as prb_write_lines groups and numbers result lines:
+ *   Id,qname,qlen,dbname,dblen,Hits,MinEnergy,SumEnergy,Eacc,Ehyb,(q0-qN:db0-dbN)
+ * energies in the result lines' form, the base-pair field the best hit's `-s 0` field.  pages[p] = the records of the
+ * batch against page p as prb_pairset_pairs returns them (ascending by `query`). */
+typedef struct prb_page_pairs {
+  const prb_pair_summary *pairs;
+  int64_t npairs;
+} prb_page_pairs;
+int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_page_pairs *pages, int32_t npages, int64_t id0, int fd, int64_t *lines,
+                            int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

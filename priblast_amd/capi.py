@@ -40,6 +40,15 @@ HIT_DTYPE = np.dtype([("q_sp", "<i4"), ("db_sp", "<i4"), ("q_len", "<i4"), ("db_
                       ("query", "<i4"), ("bp_count", "<i4"), ("bp_offset", "<i8")])
 assert HIT_DTYPE.itemsize == ctypes.sizeof(Hit)
 
+# prb_pair_summary: one (query, database sequence) pair of prb_search_page_summary
+PAIR_DTYPE = np.dtype([("query", "<i4"), ("db_id", "<i4"), ("hits", "<i8"), ("e_min", "<f8"), ("e_sum", "<f8"),
+                       ("e_acc", "<f8"), ("e_hyb", "<f8"), ("bp_first", "<i4", (2,)), ("bp_last", "<i4", (2,))])
+assert PAIR_DTYPE.itemsize == 64
+
+
+class PagePairs(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
+
 # every symbol include/priblast_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "prb_last_error": (ctypes.c_char_p, []),
@@ -84,6 +93,12 @@ SYMBOLS = {
     "prb_hitset_basepairs": (ctypes.c_void_p, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_free": (None, [ctypes.c_void_p]),
+    "prb_search_page_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts),
+                                               P(ctypes.c_void_p)]),
+    "prb_pairset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_pairset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_pairset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_pairset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -93,6 +108,8 @@ SYMBOLS = {
     "prb_ctx_keep_device_records": (None, [ctypes.c_void_p, c_i32]),
     "prb_write_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i32,
                                        c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_summary_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p,
+                                               c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
 }
 
 _lib = None
@@ -350,6 +367,26 @@ def search_page(ctx, qb, db, page, opts=None, last_stage=3):
     return hs.hits, hs.bp, hs.counts
 
 
+def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):
+    """prb_search_page_summary -> structured array PAIR_DTYPE (a copy): one record per (query, database sequence) pair
+    with final hits, in output order.  with_counts: -> (records, (seed, ungapped, final) counts)."""
+    o = opts or default_opts()
+    h = ctypes.c_void_p()
+    _check(lib().prb_search_page_summary(ctx.h, qb.h, db.h, page, ctypes.byref(o), ctypes.byref(h)))
+    try:
+        n = lib().prb_pairset_size(h)
+        if n:
+            buf = (ctypes.c_char * (n * PAIR_DTYPE.itemsize)).from_address(lib().prb_pairset_pairs(h))
+            pairs = np.frombuffer(buf, PAIR_DTYPE).copy()
+        else:
+            pairs = np.zeros(0, PAIR_DTYPE)
+        counts = (c_i64 * 3)()
+        lib().prb_pairset_counts(h, counts)
+    finally:
+        lib().prb_pairset_free(h)
+    return (pairs, tuple(counts)) if with_counts else pairs
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -404,4 +441,21 @@ def write_lines(db, qnames, qlen_unmasked, pages, output_style=0, id0=0, fd=-1):
     lines, nbytes = c_i64(), c_i64()
     _check(lib().prb_write_lines(db.h, len(qnames), names, ql.ctypes.data, arr, len(pages), output_style, id0, fd,
                                  ctypes.byref(lines), ctypes.byref(nbytes)))
+    return lines.value, nbytes.value
+
+
+def write_summary_lines(db, qnames, qlen_unmasked, pages, id0=0, fd=-1):
+    """Summary lines (`ris -t`) of one batch: pages = [records] per database page as search_page_summary returns
+    them.  -> (lines, bytes) written to the descriptor fd (-1: formatted and counted only)."""
+    arr = (PagePairs * len(pages))()
+    keep = []
+    for k, recs in enumerate(pages):
+        recs = np.ascontiguousarray(recs, PAIR_DTYPE)
+        keep.append(recs)
+        arr[k] = PagePairs(recs.ctypes.data if len(recs) else None, len(recs))
+    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
+    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
+    lines, nbytes = c_i64(), c_i64()
+    _check(lib().prb_write_summary_lines(db.h, len(qnames), names, ql.ctypes.data, arr, len(pages), id0, fd,
+                                         ctypes.byref(lines), ctypes.byref(nbytes)))
     return lines.value, nbytes.value

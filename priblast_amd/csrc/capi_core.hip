@@ -71,12 +71,12 @@ int prb_ctx::time_begin() {
   PRB_HIP(hipEventRecord(ev0, stream));
   return PRB_OK;
 }
-int prb_ctx::time_end(const char *stage, int64_t launches) {
+int prb_ctx::time_end(const char *stage, int64_t launches) { return time_end(timers[stage], launches); }
+int prb_ctx::time_end(prb::StageTimer &t, int64_t launches) {
   PRB_HIP(hipEventRecord(ev1, stream));
   PRB_HIP(hipEventSynchronize(ev1));
   float ms = 0;
   PRB_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-  auto &t = timers[stage];
   t.ms += ms;
   t.launches += launches;
   return PRB_OK;
@@ -214,6 +214,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->slow_hits;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "summary") == 0) {
+    if (ms) *ms = ctx->summary_timer.ms;
+    if (launches) *launches = ctx->summary_timer.launches;
+    return PRB_OK;
+  }
   auto it = ctx->timers.find(stage);
   if (ms) *ms = it == ctx->timers.end() ? 0.0 : it->second.ms;
   if (launches) *launches = it == ctx->timers.end() ? 0 : it->second.launches;
@@ -222,6 +227,7 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
 void prb_ctx_reset_timers(prb_ctx *ctx) {
   if (ctx) {
     ctx->timers.clear();
+    ctx->summary_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }
 }

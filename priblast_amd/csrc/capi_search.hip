@@ -48,7 +48,7 @@ struct PageMem {
 struct SearchWs {
   DevBuf cands, row_count, row_off, hitsA, hitsB, hitsC, hitsTmp, kE, kL, kQ, kP, kTmp, kTmp2, idxA, idxB, sortTmp, endKey, pmax,
       state, keep, pending, surv, count, first, gapScratch, overflow, subset, subset2, cidx, ntrace, bpCount, bpOff, bpOut, bpEnds, bpCount2, bpOff2,
-      scanTmp, tierOf, tierFin, listA, listB, trace, ntraceFin, packed, row_cand, seed_qacc, resumeSlot, resumePool, resumePool2, resumePool3, resumeCount, frontScratch, accScratch, listC, slowList, slowSlot, slowCnt, slowTrace, keptU, keptFirst, keptTier, keptNtrace, keptTrace;
+      scanTmp, tierOf, tierFin, listA, listB, trace, ntraceFin, packed, pairHead, pairStart, row_cand, seed_qacc, resumeSlot, resumePool, resumePool2, resumePool3, resumeCount, frontScratch, accScratch, listC, slowList, slowSlot, slowCnt, slowTrace, keptU, keptFirst, keptTier, keptNtrace, keptTrace;
   // The front of the one-pass seed path for a chunk of candidates - candidates and their pair offsets on the device,
   // query-side window sums, the pairs' keys and values, sorted - in buffers of its own, so that it can be issued for
   // the NEXT sub-batch, on a stream of its own, while this sub-batch is in its last, nearly idle stretch (search_range):
@@ -108,7 +108,7 @@ struct SearchWs {
     for (DevBuf *b : {&cands, &row_count, &row_off, &hitsA, &hitsB, &hitsC, &hitsTmp, &kE, &kL, &kQ, &kP, &kTmp, &kTmp2, &idxA, &idxB,
                       &sortTmp, &endKey, &pmax, &state, &keep, &surv, &first, &gapScratch, &overflow, &subset, &subset2, &cidx, &ntrace,
                       &bpCount, &bpOff, &bpOut, &bpEnds, &bpCount2, &bpOff2, &scanTmp, &tierOf, &tierFin, &listA, &listB, &trace, &ntraceFin,
-                      &row_cand, &seed_qacc, &resumePool, &resumePool2, &resumePool3, &frontScratch, &listC, &slowList, &slowSlot, &slowCnt, &slowTrace, &keptU, &keptFirst, &keptTier,
+                      &pairHead, &pairStart, &row_cand, &seed_qacc, &resumePool, &resumePool2, &resumePool3, &frontScratch, &listC, &slowList, &slowSlot, &slowCnt, &slowTrace, &keptU, &keptFirst, &keptTier,
                       &keptNtrace, &keptTrace})
       if (b->cap > ((size_t)256 << 20)) b->release();
     trim_next = false;
@@ -116,7 +116,7 @@ struct SearchWs {
   void release() {
     for (DevBuf *b : {&cands, &row_count, &row_off, &hitsA, &hitsB, &hitsC, &hitsTmp, &kE, &kL, &kQ, &kP, &kTmp, &kTmp2, &idxA, &idxB,
                       &sortTmp, &endKey, &pmax, &state, &keep, &pending, &surv, &count, &first, &gapScratch, &overflow,
-                      &subset, &subset2, &cidx, &ntrace, &bpCount, &bpOff, &bpOut, &bpEnds, &bpCount2, &bpOff2, &scanTmp, &tierOf, &tierFin, &listA, &listB, &trace, &ntraceFin, &packed, &row_cand, &seed_qacc, &resumeSlot, &resumePool, &resumePool2, &resumePool3, &resumeCount, &frontScratch, &accScratch, &listC, &slowList, &slowSlot, &slowCnt, &slowTrace, &keptU, &keptFirst, &keptTier, &keptNtrace, &keptTrace})
+                      &subset, &subset2, &cidx, &ntrace, &bpCount, &bpOff, &bpOut, &bpEnds, &bpCount2, &bpOff2, &scanTmp, &tierOf, &tierFin, &listA, &listB, &trace, &ntraceFin, &packed, &pairHead, &pairStart, &row_cand, &seed_qacc, &resumeSlot, &resumePool, &resumePool2, &resumePool3, &resumeCount, &frontScratch, &accScratch, &listC, &slowList, &slowSlot, &slowCnt, &slowTrace, &keptU, &keptFirst, &keptTier, &keptNtrace, &keptTrace})
       b->release();
     front.release();
     if (copy_stream) {
@@ -146,6 +146,7 @@ struct Drainer {
   };
   std::vector<prb_hit> *hits;
   std::vector<int32_t> *bp;
+  std::vector<prb_pair_summary> *pairs = nullptr; // summary searches: the slots hold pair records (Job::nhits of them)
   PinnedBuf *pin_hits, *pin_bp; // [2]
   hipEvent_t ev[2] = {nullptr, nullptr};
   std::thread th;
@@ -177,6 +178,16 @@ struct Drainer {
         jobs.pop_front();
       }
       if (hipEventSynchronize(ev[j.slot]) != hipSuccess) failed = true;
+      if (pairs) {
+        const prb_pair_summary *ps = static_cast<const prb_pair_summary *>(pin_hits[j.slot].p);
+        pairs->insert(pairs->end(), ps, ps + j.nhits);
+        {
+          std::lock_guard<std::mutex> lk(m);
+          busy[j.slot] = false;
+        }
+        cv.notify_all();
+        continue;
+      }
       const prb_hit *src = static_cast<const prb_hit *>(pin_hits[j.slot].p);
       if (hits->capacity() < hits->size() + (size_t)j.nhits)
         hits->reserve(std::max({2 * hits->capacity(), hits->size() + (size_t)j.nhits, hint_hits.load()}));
@@ -1843,6 +1854,46 @@ static int search_range(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int page, cons
     const int slot = hs->next_slot;
     hs->next_slot ^= 1;
     hs->drain->acquire(slot);
+    if (hs->summary) {
+      // per-pair summaries instead: the best hits' end pairs as the simplified output has them, then the pairs' runs of
+      // the list (contiguous: F is sorted by query, then db_sp, and a sub-batch is a range of whole queries) reduced
+      // on the device; only the records leave it
+      if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
+      PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+      if ((rc = ctx->time_end("traceback", 2))) return rc;
+      if ((rc = ctx->time_begin())) return rc;
+      const size_t NF = (size_t)nfin;
+      if ((rc = w.pairHead.ensure(NF)) || (rc = w.pairStart.ensure(NF * 4)) || (rc = w.count.ensure(16))) return rc;
+      PRB_HIP(launch_pair_heads(F.query, F.db_id, nfin, w.pairHead.as<uint8_t>(), ctx->stream));
+      size_t tmp = 0;
+      rocprim::counting_iterator<uint32_t> iota(0);
+      PRB_HIP(rocprim::select(nullptr, tmp, iota, w.pairHead.as<uint8_t>(), w.pairStart.as<uint32_t>(), w.count.as<size_t>(), NF,
+                              ctx->stream));
+      if ((rc = w.scanTmp.ensure(tmp))) return rc;
+      PRB_HIP(rocprim::select(w.scanTmp.p, tmp, iota, w.pairHead.as<uint8_t>(), w.pairStart.as<uint32_t>(), w.count.as<size_t>(), NF,
+                              ctx->stream));
+      size_t npairs = 0;
+      PRB_HIP(hipMemcpyAsync(&npairs, w.count.p, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+      if (npairs == 0 || npairs > NF) {
+        set_error("per-pair summary: " + std::to_string(npairs) + " pairs for " + std::to_string(nfin) + " hits");
+        return PRB_ERR_STATE;
+      }
+      const size_t rec_bytes = npairs * sizeof(prb_pair_summary);
+      if ((rc = w.packed.ensure(rec_bytes)) ||
+          (rc = w.pin_hits[slot].ensure(w.pin_hits[slot].cap >= rec_bytes ? rec_bytes : 2 * rec_bytes)))
+        return rc;
+      PRB_HIP(launch_pair_fold(F, nfin, w.pairStart.as<uint32_t>(), (int64_t)npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+      PRB_HIP(hipEventRecord(w.packed_ready, ctx->stream));
+      PRB_HIP(hipStreamWaitEvent(w.copy_stream, w.packed_ready, 0));
+      PRB_HIP(hipMemcpyAsync(w.pin_hits[slot].p, w.packed.p, rec_bytes, hipMemcpyDeviceToHost, w.copy_stream));
+      PRB_HIP(hipEventRecord(w.copy_done, w.copy_stream));
+      w.copy_pending = true;
+      PRB_HIP(hipEventRecord(hs->drain->ev[slot], w.copy_stream));
+      hs->drain->submit(Drainer::Job{slot, (int64_t)npairs, 0});
+      hs->hits_total += nfin;
+      return ctx->time_end(ctx->summary_timer, 3);
+    }
     const int64_t bp_base_pairs = hs->bp_ints_total / 2;
     const int64_t nbp_ints = opts.output_style == 0 ? nfin * 4 : total * 2;
     // (page-locking a fresh 50 MB block takes ~35 ms with the GPU idle: when a slot has to grow, to twice the need, so
@@ -1948,20 +1999,25 @@ int prb_qbatch_seed_search_begin(prb_ctx *ctx, prb_qbatch *qb, const prb_db *db,
   return PRB_OK;
 }
 
-int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                    prb_hitset **out) {
+} // extern "C"
+
+// prb_search_page, and with `summary` the search of prb_search_page_summary (final hits reduced to per-pair records,
+// prb_hitset::pairs)
+static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
+                       bool summary, prb_hitset **out) {
+  const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
   if (!ctx || !qb || !db || !opts || !out || qb->ctx->device != ctx->device || db->ctx->device != ctx->device || page < 0 ||
       page >= (int32_t)db->pages.size() || last_stage < 1 || last_stage > 3) {
-    set_error("prb_search_page: bad argument");
+    set_error(std::string(fn) + ": bad argument");
     return PRB_ERR_ARG;
   }
   *out = nullptr;
   if (!qb->have_acc || qb->W != db->hdr.maximal_span || qb->delta != db->hdr.min_accessible_length) {
-    set_error("prb_search_page: query accessibilities must be computed with the database's span / window parameters");
+    set_error(std::string(fn) + ": query accessibilities must be computed with the database's span / window parameters");
     return PRB_ERR_STATE;
   }
   if (qb->repeat_flag != db->hdr.repeat_flag) {
-    set_error("prb_search_page: query batch was encoded with a different repeat flag than the database");
+    set_error(std::string(fn) + ": query batch was encoded with a different repeat flag than the database");
     return PRB_ERR_STATE;
   }
   if (opts->drop_out_w_gap < 0 || opts->drop_out_w_gap > 30 || opts->drop_out_wo_gap < 1 || opts->drop_out_wo_gap > 15 ||
@@ -2004,15 +2060,17 @@ int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, cons
   std::thread &producer = plan.producer;
   auto *hs = new prb_hitset();
   hs->device = ctx->device;
-  hs->on_device = ctx->keep_device_records && last_stage == 3;
+  hs->summary = summary;
+  hs->on_device = ctx->keep_device_records && last_stage == 3 && !summary;
   hs->d_hits.hint = ctx->keep_hint_hits;
   hs->d_bp.hint = ctx->keep_hint_bp;
   SearchWs &wsp = ws_of(ctx);
   Drainer drain(&hs->hits, &hs->bp, wsp.pin_hits, wsp.pin_bp);
+  if (summary) drain.pairs = &hs->pairs;
   hs->drain = &drain;
   const char *env = getenv("PRB_SEARCH_PAIRS");
   const double budget = env ? atof(env) : 4.0e8;
-  if (last_stage == 3) { // a stream of similar batches: the last hit set's size, with a twentieth to spare, up front
+  if (last_stage == 3 && !summary) { // a stream of similar batches: the last hit set's size, with a twentieth to spare, up front
     drain.hint_hits = ctx->host_hint_hits + ctx->host_hint_hits / 20;
     drain.hint_bp = ctx->host_hint_bp + ctx->host_hint_bp / 20;
   }
@@ -2165,13 +2223,49 @@ int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, cons
     ctx->keep_hint_hits = hs->d_hits.used;
     ctx->keep_hint_bp = hs->d_bp.used;
   }
-  if (last_stage == 3) {
+  if (last_stage == 3 && !summary) {
     ctx->host_hint_hits = hs->hits.size();
     ctx->host_hint_bp = hs->bp.size();
   }
   *out = hs;
   return PRB_OK;
 }
+
+extern "C" {
+
+int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
+                    prb_hitset **out) {
+  return search_page(ctx, qb, db, page, opts, last_stage, false, out);
+}
+
+int prb_search_page_summary(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_pairset **out) {
+  if (!out) {
+    set_error("prb_search_page_summary: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  prb_hitset *hs = nullptr;
+  const int rc = search_page(ctx, qb, db, page, opts, 3, true, &hs);
+  if (rc != PRB_OK) return rc;
+  auto *ps = new (std::nothrow) prb_pairset();
+  if (!ps) {
+    delete hs;
+    set_error("prb_search_page_summary: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  ps->pairs.swap(hs->pairs);
+  for (int i = 0; i < 3; i++) ps->counts[i] = hs->counts[i];
+  delete hs;
+  *out = ps;
+  return PRB_OK;
+}
+
+int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }
+const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps) { return ps ? ps->pairs.data() : nullptr; }
+void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ps ? ps->counts[i] : 0;
+}
+void prb_pairset_free(prb_pairset *ps) { delete ps; }
 
 int64_t prb_hitset_size(const prb_hitset *hs) { return !hs ? -1 : hs->ext_hits ? hs->ext_nhits : (int64_t)hs->hits.size(); }
 const prb_hit *prb_hitset_hits(const prb_hitset *hs) { return !hs ? nullptr : hs->ext_hits ? hs->ext_hits : hs->hits.data(); }
@@ -2228,6 +2322,51 @@ int prb_write_lines(const prb_db *db, int32_t nq, const char *const *qnames, con
     }
   } catch (const std::exception &e) {
     set_error(std::string("prb_write_lines: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  return PRB_OK;
+}
+
+int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_page_pairs *pages, int32_t npages, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  if (!db || nq < 0 || (nq && (!qnames || !qlen_unmasked)) || !pages || npages != (int32_t)db->pages.size()) {
+    set_error("prb_write_summary_lines: bad argument");
+    return PRB_ERR_ARG;
+  }
+  try {
+    SummaryView v;
+    std::vector<std::string> names((size_t)nq);
+    for (int32_t q = 0; q < nq; q++) names[q] = qnames[q];
+    v.nq = (size_t)nq;
+    v.names = names.data();
+    v.qlen_unmasked = qlen_unmasked;
+    for (int32_t p = 0; p < npages; p++) {
+      const prb_page_pairs &pp = pages[p];
+      if (pp.npairs < 0 || (pp.npairs && !pp.pairs)) {
+        set_error("prb_write_summary_lines: bad page");
+        return PRB_ERR_ARG;
+      }
+      const int32_t nseq = db->pages[p].nseq;
+      for (int64_t i = 0; i < pp.npairs; i++) {
+        const prb_pair_summary &x = pp.pairs[i];
+        if (x.query < 0 || x.query >= nq || x.db_id < 0 || x.db_id >= nseq || x.hits < 1 || (i && x.query < pp.pairs[i - 1].query)) {
+          set_error("prb_write_summary_lines: pair record " + std::to_string(i) + " of page " + std::to_string(p) + " is inconsistent");
+          return PRB_ERR_ARG;
+        }
+      }
+      v.pages.push_back(PagePairs{pp.pairs, pp.npairs});
+    }
+    LineSink sink;
+    sink.fd = fd;
+    const int64_t next = format_summary_batch(v, db->tabs, id0, sink, format_threads());
+    if (lines) *lines = sink.lines;
+    if (bytes) *bytes = sink.bytes;
+    if (next < 0) {
+      set_error("prb_write_summary_lines: write failed");
+      return PRB_ERR_IO;
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_write_summary_lines: ") + e.what());
     return PRB_ERR_NOMEM;
   }
   return PRB_OK;

@@ -58,7 +58,11 @@ struct prb_ctx {
   prb::DevBuf ra_band, ra_vec, ra_codes, ra_desc, ra_acc, ra_cond;
   size_t ra_budget_bytes = 0;
   std::map<std::string, prb::StageTimer> timers;
+  // the per-pair reduction of prb_search_page_summary (stage "summary"): kept apart from the stages of the full-output
+  // search that `timers` holds and bench.py reports
+  prb::StageTimer summary_timer;
 
   int time_begin();
   int time_end(const char *stage, int64_t launches);
+  int time_end(prb::StageTimer &t, int64_t launches);
 };

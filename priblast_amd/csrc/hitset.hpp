@@ -105,5 +105,14 @@ struct prb_hitset {
   prb::Drainer *drain = nullptr;
   int64_t hits_total = 0, bp_ints_total = 0;
   int next_slot = 0;
+  // prb_search_page_summary: the search reduces its final hits to per-pair records on the device; `hits` / `bp` stay
+  // empty and the records arrive here
+  bool summary = false;
+  std::vector<prb_pair_summary> pairs;
+};
+
+struct prb_pairset {
+  std::vector<prb_pair_summary> pairs;
+  int64_t counts[3] = {0, 0, 0};
 };
 

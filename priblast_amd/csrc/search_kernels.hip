@@ -874,6 +874,48 @@ __global__ __launch_bounds__(kBlock) void k_pack_hits(HitSoA s, int64_t n, const
   out[i] = h;
 }
 
+// ---- per-pair summaries ----
+// The final list is sorted by query, then db_sp, and a database sequence is one contiguous range of the page text
+// (db_id = seq_of(db_sp)), so the hits of a (query, db_id) pair are one run of the list.
+__global__ __launch_bounds__(kBlock) void k_pair_heads(const int32_t *__restrict__ query, const int32_t *__restrict__ db_id,
+                                                       int64_t n, uint8_t *head) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  head[i] = i == 0 || query[i] != query[i - 1] || db_id[i] != db_id[i - 1];
+}
+
+// A lane walks its pair's run in list order: strict `<` keeps the first minimum, the sum is the left-to-right one.
+// (A lane per pair: the skew of the run lengths is in DESIGN.md §4.)
+__global__ __launch_bounds__(kBlock) void k_pair_fold(HitSoA h, int64_t n, const uint32_t *__restrict__ start, int64_t npairs,
+                                                      const int32_t *__restrict__ ends, prb_pair_summary *out) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= npairs) return;
+  const int64_t a = start[k], b = k + 1 < npairs ? (int64_t)start[k + 1] : n;
+  double sum = 0.0, mn = h.e_tot[a];
+  int64_t best = a;
+  for (int64_t i = a; i < b; i++) {
+    const double e = h.e_tot[i];
+    sum += e;
+    if (e < mn) {
+      mn = e;
+      best = i;
+    }
+  }
+  prb_pair_summary r;
+  r.query = h.query[a];
+  r.db_id = h.db_id[a];
+  r.hits = b - a;
+  r.e_min = mn;
+  r.e_sum = sum;
+  r.e_acc = h.e_acc[best];
+  r.e_hyb = h.e_hyb[best];
+  r.bp_first[0] = ends[4 * best];
+  r.bp_first[1] = ends[4 * best + 1];
+  r.bp_last[0] = ends[4 * best + 2];
+  r.bp_last[1] = ends[4 * best + 3];
+  out[k] = r;
+}
+
 // keep[i] = 1 unless E_i > threshold.  A hit above the threshold is flagged by CheckRedundancy
 // the moment the sweep reaches it and never flags anything else (as the contained hit of an
 // earlier scan it loses: E_a <= threshold < E_b), so it can be dropped BEFORE the sort.
@@ -1306,6 +1348,17 @@ hipError_t launch_pack_hits(const HitSoA &src, int64_t n, const int32_t *bp_coun
                             void *out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_pack_hits, grid_for(n), dim3(kBlock), 0, s, src, n, bp_count, bp_off, bp_base, static_cast<prb_hit *>(out));
+  return hipGetLastError();
+}
+hipError_t launch_pair_heads(const int32_t *query, const int32_t *db_id, int64_t n, uint8_t *head, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pair_heads, grid_for(n), dim3(kBlock), 0, s, query, db_id, n, head);
+  return hipGetLastError();
+}
+hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, void *out,
+                            hipStream_t s) {
+  if (npairs <= 0 || n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pair_fold, grid_for(npairs), dim3(kBlock), 0, s, h, n, start, npairs, ends, static_cast<prb_pair_summary *>(out));
   return hipGetLastError();
 }
 hipError_t launch_flag_not_above(const double *e_tot, int64_t n, double thr, uint8_t *keep, hipStream_t s) {

@@ -130,6 +130,14 @@ hipError_t launch_gather_u32(const uint32_t *src, const uint32_t *idx, uint32_t 
 // base-pair ranges (bp_count / bp_off per hit, or 2 pairs per hit when those are null)
 hipError_t launch_pack_hits(const HitSoA &src, int64_t n, const int32_t *bp_count, const int64_t *bp_off, int64_t bp_base,
                             void *out, hipStream_t s);
+// ---- per-pair summaries (prb_search_page_summary) over a final, sorted hit list ----
+// head[i] = 1 where (query, db_id) differs from hit i - 1 (and for i = 0): the first hit of every pair
+hipError_t launch_pair_heads(const int32_t *query, const int32_t *db_id, int64_t n, uint8_t *head, hipStream_t s);
+// one lane per pair k, hits [start[k], start[k + 1]) (the last one up to n), walked in order: count, first minimum of
+// e_tot, left-to-right sum; writes prb_pair_summary records with the best hit's e_acc / e_hyb and its two end pairs
+// from `ends` (4 ints per hit, launch_bp_ends)
+hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, void *out,
+                            hipStream_t s);
 hipError_t launch_gather_u8(const uint8_t *src, const uint32_t *idx, uint8_t *dst, int64_t n, hipStream_t s);
 hipError_t launch_iota_u32(uint32_t *dst, int64_t n, hipStream_t s); // dst[i] = i
 // flags[i] = marks[list[i]] & mask != 0

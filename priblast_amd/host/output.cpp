@@ -44,6 +44,42 @@ inline char *put_int(char *p, long long x) { return std::to_chars(p, p + 24, x).
 // format with precision 6 is specified as exactly that conversion (tests/test_host.py compares).
 inline char *put_g(char *p, double x) { return std::to_chars(p, p + 40, x, std::chars_format::general, 6).ptr; }
 
+// reversed page text -> forward coordinate of sequence `id` (:352-363)
+inline int32_t fwd_pos(const SeqTable &tab, int32_t id, int32_t dbpos) { return (tab.len[id] - 1) - (dbpos - tab.start_pos[id]); }
+
+// `-s 0` base-pair field "(q0-qN:db0-dbN) " from the first and the last pair of a hit
+inline char *put_ends(char *p, const SeqTable &tab, int32_t id, const int32_t first[2], const int32_t last[2]) {
+  *p++ = '(';
+  p = put_int(p, first[0]);
+  *p++ = '-';
+  p = put_int(p, last[0]);
+  *p++ = ':';
+  p = put_int(p, fwd_pos(tab, id, first[1]));
+  *p++ = '-';
+  p = put_int(p, fwd_pos(tab, id, last[1]));
+  *p++ = ')';
+  *p++ = ' ';
+  return p;
+}
+
+// "Id,qname,qlen,dbname,dblen," - the columns every line starts with
+inline char *put_names(char *p, int64_t id, const std::string &qname, int32_t qlen, const SeqTable &tab, int32_t db_id) {
+  const std::string &dname = tab.names[db_id];
+  p = put_int(p, id);
+  *p++ = ',';
+  std::memcpy(p, qname.data(), qname.size());
+  p += qname.size();
+  *p++ = ',';
+  p = put_int(p, qlen);
+  *p++ = ',';
+  std::memcpy(p, dname.data(), dname.size());
+  p += dname.size();
+  *p++ = ',';
+  p = put_int(p, tab.len_unmasked[db_id]);
+  *p++ = ',';
+  return p;
+}
+
 void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, Buf &b) {
   const PageHits &ph = v.pages[pc.p];
   const SeqTable &tab = tabs[pc.p];
@@ -52,23 +88,10 @@ void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTabl
   int64_t id = pc.id;
   for (int64_t i = pc.i0; i < pc.i1; i++) {
     const prb_hit &x = ph.h[i];
-    const std::string &dname = tab.names[x.db_id];
-    const int32_t len = tab.len[x.db_id], sp = tab.start_pos[x.db_id];
     const int32_t npairs = output_style == 1 ? x.bp_count : (x.bp_count > 0 ? 1 : 0);
-    char *p = b.room(qname.size() + dname.size() + 200 + (size_t)npairs * 48);
+    char *p = b.room(qname.size() + tab.names[x.db_id].size() + 200 + (size_t)npairs * 48);
     char *const p0 = p;
-    p = put_int(p, id++);
-    *p++ = ',';
-    std::memcpy(p, qname.data(), qname.size());
-    p += qname.size();
-    *p++ = ',';
-    p = put_int(p, qlen);
-    *p++ = ',';
-    std::memcpy(p, dname.data(), dname.size());
-    p += dname.size();
-    *p++ = ',';
-    p = put_int(p, tab.len_unmasked[x.db_id]);
-    *p++ = ',';
+    p = put_names(p, id++, qname, qlen, tab, x.db_id);
     p = put_g(p, x.e_acc);
     *p++ = ',';
     p = put_g(p, x.e_hyb);
@@ -76,28 +99,17 @@ void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTabl
     p = put_g(p, x.e_tot);
     *p++ = ',';
     const int32_t *pp = ph.bp + 2 * x.bp_offset;
-    auto fwd = [&](int32_t dbpos) { return (len - 1) - (dbpos - sp); }; // reversed page text -> forward coordinate
     if (output_style == 1) {
       for (int32_t j = 0; j < x.bp_count; j++) {
         *p++ = '(';
         p = put_int(p, pp[2 * j]);
         *p++ = ':';
-        p = put_int(p, fwd(pp[2 * j + 1]));
+        p = put_int(p, fwd_pos(tab, x.db_id, pp[2 * j + 1]));
         *p++ = ')';
         *p++ = ' ';
       }
     } else if (x.bp_count > 0) {
-      const int32_t l = x.bp_count - 1;
-      *p++ = '(';
-      p = put_int(p, pp[0]);
-      *p++ = '-';
-      p = put_int(p, pp[2 * l]);
-      *p++ = ':';
-      p = put_int(p, fwd(pp[1]));
-      *p++ = '-';
-      p = put_int(p, fwd(pp[2 * l + 1]));
-      *p++ = ')';
-      *p++ = ' ';
+      p = put_ends(p, tab, x.db_id, pp, pp + 2 * (x.bp_count - 1));
     }
     *p++ = '\n';
     b.n += (size_t)(p - p0);
@@ -114,18 +126,16 @@ bool write_all(int fd, const char *p, size_t n) {
   return true;
 }
 
-} // namespace
-
-int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
-                     int threads) {
-  const size_t nq = v.nq, np = v.pages.size();
-  std::vector<std::vector<int64_t>> first(np, std::vector<int64_t>(nq + 1, 0)); // first[p][q] = first hit of query q
+// Records of one batch (per page, ascending by query) as lines, query by query and page by page, numbered from id0 on:
+// n_of(p) = records of page p, query_of(p, i) = the query of record i, fmt(piece, buf) formats a piece.
+template <class NOf, class QueryOf, class Fmt>
+int64_t format_records(size_t nq, size_t np, NOf n_of, QueryOf query_of, Fmt fmt, int64_t id0, LineSink &sink, int threads) {
+  std::vector<std::vector<int64_t>> first(np, std::vector<int64_t>(nq + 1, 0)); // first[p][q] = first record of query q
   for (size_t p = 0; p < np; p++) {
-    const int64_t n = v.pages[p].n;
-    const prb_hit *h = v.pages[p].h;
+    const int64_t n = n_of(p);
     size_t q = 0;
     for (int64_t i = 0; i < n; i++)
-      while (q < nq && (int64_t)q <= h[i].query) first[p][q++] = i;
+      while (q < nq && (int64_t)q <= query_of(p, i)) first[p][q++] = i;
     while (q <= nq) first[p][q++] = n;
   }
   std::vector<Piece> pieces;
@@ -147,7 +157,7 @@ int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int 
     for (size_t k = r0; k < r1; k++) {
       Buf &b = bufs[k - r0];
       b.n = 0;
-      format_piece(pieces[k], v, tabs, output_style, b);
+      fmt(pieces[k], b);
     }
     for (size_t k = r0; k < r1 && ok; k++) {
       const Buf &b = bufs[k - r0];
@@ -157,6 +167,48 @@ int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int 
     }
   }
   return ok ? id : -1;
+}
+
+void format_summary_piece(const Piece &pc, const SummaryView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  const PagePairs &pp = v.pages[pc.p];
+  const SeqTable &tab = tabs[pc.p];
+  const std::string &qname = v.names[pc.q];
+  const int32_t qlen = v.qlen_unmasked[pc.q];
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_pair_summary &x = pp.r[i];
+    char *p = b.room(qname.size() + tab.names[x.db_id].size() + 320);
+    char *const p0 = p;
+    p = put_names(p, id++, qname, qlen, tab, x.db_id);
+    p = put_int(p, x.hits);
+    *p++ = ',';
+    p = put_g(p, x.e_min);
+    *p++ = ',';
+    p = put_g(p, x.e_sum);
+    *p++ = ',';
+    p = put_g(p, x.e_acc);
+    *p++ = ',';
+    p = put_g(p, x.e_hyb);
+    *p++ = ',';
+    p = put_ends(p, tab, x.db_id, x.bp_first, x.bp_last);
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
+} // namespace
+
+int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
+                     int threads) {
+  return format_records(
+      v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].h[i].query; },
+      [&](const Piece &pc, Buf &b) { format_piece(pc, v, tabs, output_style, b); }, id0, sink, threads);
+}
+
+int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  return format_records(
+      v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].r[i].query; },
+      [&](const Piece &pc, Buf &b) { format_summary_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 } // namespace prb

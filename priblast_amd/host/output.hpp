@@ -46,6 +46,21 @@ struct LineSink {
 int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
                      int threads);
 
+// Summary lines of `ris -t` (one per query-target pair, prb_search_page_summary), grouped and numbered the same way:
+//   Id,qname,qlen,dbname,dblen,Hits,MinE,SumE,Eacc,Ehyb,(q0-qN:db0-dbN)
+// energies and the best hit's base-pair field formatted exactly as in the result lines (-s 0 form).
+struct PagePairs {
+  const prb_pair_summary *r = nullptr;
+  int64_t n = 0;
+};
+struct SummaryView {
+  size_t nq = 0;
+  const std::string *names = nullptr; // [nq]
+  const int32_t *qlen_unmasked = nullptr;
+  std::vector<PagePairs> pages;
+};
+int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 int format_threads(); // PRB_HOST_THREADS, else min(32, hardware threads)
 
 } // namespace prb

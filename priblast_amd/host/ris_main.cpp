@@ -15,9 +15,12 @@
 //     replacement of the reference's MPI token ring (rna_interaction_search.cpp:426-487).  The 128-byte
 //     RCCL id travels through a file in the `-p` temporary directory (default: next to the output).
 //
-// Two additions to the reference's surface (the output path): `ris -b` writes
-// the hits as binary records instead of text (no number formatting on the search path), and the
-// `txt` sub-command turns such a file into exactly the text `ris` would have written.
+// Three additions to the reference's surface (the output path): `ris -b` writes
+// the hits as binary records instead of text (no number formatting on the search path), the
+// `txt` sub-command turns such a file into exactly the text `ris` would have written, and `ris -t`
+// writes one summary line per (query, target) pair instead of one line per hit: the final hits are
+// reduced on the GPU (prb_search_page_summary) and never leave it.  `-t` is refused with `-b` and in
+// rank mode (WORLD_SIZE > 1): the gather carries hit records only.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -79,6 +82,8 @@ void usage() {
             "    -a STR    accepted for compatibility (block, area, dynamic); ignored\n"
             "    -p STR    accepted for compatibility; ignored\n"
             "    -b        write binary hit records instead of text; `pRIblast-hip txt -i FILE -o TEXT` converts\n"
+            "    -t        one summary line per query-target pair: hit count, minimum and summed interaction energy,\n"
+            "              the best hit's energies and base-pair ends (-s has no effect; not with -b, nor with WORLD_SIZE > 1)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
@@ -88,6 +93,7 @@ struct Args {
   std::string in, out, db, tmp;
   prb_ris_opts o;
   bool binary = false;
+  bool summary = false; // -t
 };
 
 [[noreturn]] void die(const std::string &msg) {
@@ -105,6 +111,7 @@ struct Worker {
 struct BatchJob {
   size_t index = 0, nq = 0;
   std::vector<prb_hitset *> pages;
+  std::vector<prb_pairset *> pair_pages; // -t: the per-pair summaries instead
   std::vector<std::string> names; // of its queries, in the order of their indices in the hit records
   std::vector<int32_t> qlen_unmasked;
 };
@@ -288,9 +295,16 @@ Prepared prepare_batch(prb_ctx *c, const std::vector<std::string> &seqs, const s
   return p;
 }
 
-// the search stages of a prepared batch against every page; the hit sets go to the writer
-void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector<prb_hitset *> &pages) {
+// the search stages of a prepared batch against every page; the hit sets (with -t: the pair sets) go to the writer
+void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector<prb_hitset *> &pages,
+                  std::vector<prb_pairset *> &pair_pages) {
   for (int page = 0; page < npages; page++) {
+    if (a.summary) {
+      prb_pairset *ps = nullptr;
+      if (prb_search_page_summary(w.ctx, p.qb, w.db, page, &a.o, &ps)) die(prb_last_error());
+      pair_pages.push_back(ps);
+      continue;
+    }
     prb_hitset *hs = nullptr;
     if (prb_search_page(w.ctx, p.qb, w.db, page, &a.o, 3, &hs)) die(prb_last_error());
     pages.push_back(hs);
@@ -399,7 +413,7 @@ int ris_main(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:b")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:bt")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -414,6 +428,7 @@ int ris_main(int argc, char **argv) {
     case 'm': a.o.min_helix_length = std::atoi(optarg); break;
     case 'p': a.tmp = optarg; break;
     case 'b': a.binary = true; break;
+    case 't': a.summary = true; break;
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -421,6 +436,7 @@ int ris_main(int argc, char **argv) {
     default: die("Error: invalid argument");
     }
   }
+  if (a.summary && a.binary) die("Error: -t (per-pair summary lines) can't be combined with -b (binary hit records)");
   std::vector<std::string> names, seqs;
   std::string err = prb::read_fasta(a.in, names, seqs);
   if (!err.empty()) die(err);
@@ -443,6 +459,8 @@ int ris_main(int argc, char **argv) {
   const int rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
   const bool rank_mode = world > 1 || std::getenv("PRB_FORCE_COMM") != nullptr;
   if (rank < 0 || rank >= world) die("Error: RANK outside WORLD_SIZE");
+  if (rank_mode && a.summary)
+    die("Error: -t (per-pair summary lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
   if (rank_mode) {
     const int local = env_int("LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", rank);
     const int dev = devices.empty() ? local : devices[(size_t)local % devices.size()];
@@ -518,8 +536,12 @@ int ris_main(int argc, char **argv) {
                   a.o.final_threshold, a.o.drop_out_wo_gap, a.o.drop_out_w_gap);
     header += buf;
   }
-  header += "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
-            "Interaction Energy, BasePair\n";
+  if (a.summary)
+    header += "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+              "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
+  else
+    header += "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
+              "Interaction Energy, BasePair\n";
   if (a.binary) write_binary_head(out, a.o.output_style, header, tabs);
   else put(out, header.data(), header.size());
   if (std::fflush(out)) die("Error: can't write the output file");
@@ -557,6 +579,21 @@ int ris_main(int argc, char **argv) {
         job = std::move(done[b]);
         done.erase(b);
       }
+      if (a.summary) {
+        prb::SummaryView sv;
+        sv.nq = job.nq;
+        sv.names = job.names.data();
+        sv.qlen_unmasked = job.qlen_unmasked.data();
+        for (prb_pairset *ps : job.pair_pages) sv.pages.push_back(prb::PagePairs{prb_pairset_pairs(ps), prb_pairset_size(ps)});
+        if ((id = prb::format_summary_batch(sv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
+        for (prb_pairset *ps : job.pair_pages) prb_pairset_free(ps);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          written = b + 1;
+        }
+        cv.notify_all();
+        continue;
+      }
       BatchView v;
       v.nq = job.nq;
       v.names = job.names.data();
@@ -592,7 +629,8 @@ int ris_main(int argc, char **argv) {
   };
   // A worker: its batches one after the other; the accessibilities of the next one are computed by a
   // helper thread under the worker's second context while this one is searched.
-  auto work = [&](Worker &w, const std::function<bool(size_t &)> &next_batch, const std::function<void(size_t, Prepared *, std::vector<prb_hitset *> &)> &finish) {
+  using Finish = std::function<void(size_t, Prepared *, std::vector<prb_hitset *> &, std::vector<prb_pairset *> &)>;
+  auto work = [&](Worker &w, const std::function<bool(size_t &)> &next_batch, const Finish &finish) {
     size_t b = 0, bn = 0;
     bool have = next_batch(b);
     Prepared cur;
@@ -603,8 +641,9 @@ int ris_main(int argc, char **argv) {
       std::thread helper;
       if (more && w.prep_ctx) helper = std::thread([&] { nxt = prepare_batch(w.prep_ctx, seqs, batch_idx(bn), W, delta, repeat_flag, w.db, &a.o); });
       std::vector<prb_hitset *> pages;
-      search_batch(w, a, cur, npages, pages);
-      finish(b, &cur, pages);
+      std::vector<prb_pairset *> pair_pages;
+      search_batch(w, a, cur, npages, pages, pair_pages);
+      finish(b, &cur, pages, pair_pages);
       if (helper.joinable()) helper.join();
       else if (more) nxt = prepare_batch(w.ctx, seqs, batch_idx(bn), W, delta, repeat_flag, w.db, &a.o);
       cur = std::move(nxt);
@@ -622,7 +661,7 @@ int ris_main(int argc, char **argv) {
                b = next.fetch_add(1);
                return b < nb;
              },
-             [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages) {
+             [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages, std::vector<prb_pairset *> &pair_pages) {
                {
                  std::unique_lock<std::mutex> lk(mu); // bound the hit sets held in memory
                  cv.wait(lk, [&] { return b < written + 2 * workers.size() + 1; });
@@ -630,6 +669,7 @@ int ris_main(int argc, char **argv) {
                BatchJob job;
                job.index = b;
                job.pages = pages;
+               job.pair_pages = pair_pages;
                job.qlen_unmasked = p->qlen_unmasked;
                names_of(batch_idx(b), job.names);
                job.nq = job.names.size();
@@ -711,7 +751,9 @@ int ris_main(int argc, char **argv) {
            t_next++;
            return b < nb;
          },
-         [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages) { gather_round(b / (size_t)world, p, pages); });
+         [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages, std::vector<prb_pairset *> &) {
+           gather_round(b / (size_t)world, p, pages);
+         });
     // rounds in which this rank has no batch left (the last one, when nb is not a multiple of world)
     const size_t mine_rounds = nb > (size_t)rank ? (nb - (size_t)rank + (size_t)world - 1) / (size_t)world : 0;
     std::vector<prb_hitset *> none;
