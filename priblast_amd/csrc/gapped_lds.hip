@@ -39,7 +39,7 @@ namespace prb {
 // Developer-only cycle breakdown of the gapped kernel (make PROF=1 builds libpriblast_hip_prof.so;
 // tools/gapped_profile.py reads it).  Not part of the product build.
 #ifdef PRB_GAP_PROFILE
-constexpr int kProfSlots = 24;
+constexpr int kProfSlots = 26;
 __device__ unsigned long long g_gap_prof[10 * kProfSlots]; // [tier * 2 + (mode != 0)][region]
 struct GapProf {
   unsigned long long last, acc[kProfSlots];
@@ -187,7 +187,7 @@ template <class T, class Rec> struct LdsStore {
   using R = Rec;
   static constexpr bool kResumable = T::kResumable;
   static constexpr bool kAccGlobal = T::kAccGlobal;
-  static constexpr int kCapD = T::kCapD;
+  static constexpr int kCapD = T::kCapD, kCapR = T::kCapR;
   LdsLive<T, Rec> &s;
   double *acc; // kAccGlobal: eq[kCapD], ed[kCapD] of this group
   __device__ __forceinline__ int cap_d() const { return T::kCapD; }
@@ -516,6 +516,48 @@ __device__ __forceinline__ void stage_windows(const SeqBases &sb, const HitCtx &
   group_sync<kLds>();
 }
 
+// The candidate scan of a filled cell (ci, cj) in the LDS tiers with 8- and 16-lane groups: the best predecessor among the live
+// candidates [lo, dstart), lane `sub` of `stride` taking candidates lo + sub, lo + sub + stride, ...  Only a candidate with
+// ri < ci and rj < cj can close a loop on the cell, and the live list - in (anti-diagonal, i) order - holds those as one short
+// run per anti-diagonal (ri in (ci - (L - L'), ci) on anti-diagonal L' of a cell on L; none on L - 1): about half of the list
+// on the bench workload.  So the scan goes in two passes: the records alone, a few instructions per round, give each lane a bit
+// per round of its candidates that qualify; then the loop energies of those alone, a lane's in list order - each evaluation is
+// two thirds of a round's instructions, and its lanes are masked off for the candidates that do not qualify.  A lane takes its
+// candidates in ascending k with strict '<' as before: the (energy, index) reduction that follows still picks the first
+// candidate in list order.  v0: the record of candidate lo + sub (when there is one), fetched by the caller.
+template <class R, class Store, class Energy>
+__device__ __forceinline__ void scan_qualifying(const Store &S, int lo, int dstart, int sub, int stride, int ci, int cj,
+                                                typename R::word v0, const Energy &energy, double &bte, int &bkp, GapProf &prof) {
+  static_assert(Store::kCapR <= 32 * 4, "a bit per round of at least four lanes");
+  uint32_t mine = 0; // bit r: candidate lo + sub + r * stride qualifies
+  typename R::word vn = v0;
+  for (int k0 = lo, r = 0; k0 < dstart; k0 += stride, r++) {
+    GP_COUNT(25);
+    const int k = k0 + sub;
+    const auto v = vn;
+    if (k + stride < dstart) vn = S.info(k + stride);
+    const bool ok = k < dstart && R::i(v) < ci && R::j(v) < cj;
+#ifdef PRB_GAP_PROFILE
+    prof.acc[22] += (unsigned long long)__popcll(__ballot(k < dstart));
+    prof.acc[23] += (unsigned long long)__popcll(__ballot(ok));
+#endif
+    mine |= (uint32_t)ok << r;
+  }
+  GP_MARK(24);
+  while (mine) {
+    GP_COUNT(13);
+    const int k = lo + sub + __builtin_ctz(mine) * stride;
+    mine &= mine - 1;
+    const auto v = S.info(k);
+    double te = energy(v);
+    te += S.hyb(k);
+    if (te < bte) {
+      bte = te;
+      bkp = (k << 3) | R::type(v);
+    }
+  }
+}
+
 // GappedExtension::extension (gapped_extension.cpp:71-319) for one direction, by a group of G lanes,
 // in three pieces so that the groups of a wavefront can be at different points of different
 // hits: dir_init (state + everything the anti-diagonal loop touches staged on chip: the bases
@@ -604,11 +646,13 @@ __device__ __forceinline__ bool dir_step(const SearchConst &sc, const SeqBases &
   d.resume_i0 = 0;
 
   // the first G live candidates, for the first scan round of every filled cell of this anti-diagonal
+  // (two-pass scans, scan_qualifying: the records alone)
+  constexpr bool kQualScan = kLds && G <= 16;
   typename R::word v_first = 0;
   double h_first = 0;
   if (d.lo + gl < dstart) {
     v_first = S.info(d.lo + gl);
-    h_first = S.hyb(d.lo + gl);
+    if constexpr (!kQualScan) h_first = S.hyb(d.lo + gl);
   }
 
   // One filled cell (ci, d.length - ci) of pair type ctype: its best predecessor among the live
@@ -631,41 +675,44 @@ __device__ __forceinline__ bool dir_step(const SearchConst &sc, const SeqBases &
     const int fq = S.qb(ci + 1), fd = S.db(cj + 1);        // likewise: the new record's far-side bases
     double bte = 1000000.0;                                // INF
     int bkp = d.lo << 3; // candidate index << 3 | its type (0: none looked at), so the type comes out of the reduction
-    // (the records of the next round are fetched while this round's energies are looked up; those of
-    // the first round are the same for every cell of the anti-diagonal and were fetched at its start -
-    // with two cells, lanes 4-7 take theirs from lanes 0-3)
-    typename R::word vn = v_first;
-    double hn = h_first;
-    if constexpr (kTwoCells) {
-      if (pair_mode) {
-        const typename R::word v4 = (typename R::word)dpp_i32<0x114>((int)v_first); // row_shr:4
-        const double h4 = dpp_f64<0x114>(h_first);
-        vn = hi ? v4 : v_first;
-        hn = hi ? h4 : h_first;
-        if (sub + d.lo >= dstart) vn = 0; // (what the owner of this slot would hold)
+    // LoopEnergy between the new pair and candidate record v (:230-247); the loop lies between offsets (ri, rj) and (ci, cj)
+    // from the start.  (The groups of a wavefront are in different directions most of the time: the outer and the inner pair
+    // are put in place with selects, so there is one copy of the look-up, not one per direction.)
+    auto energy = [&](typename R::word v) -> double {
+      const int ri = R::i(v), rj = R::j(v);
+      const int rq = R::kBases ? R::qa(v) : (int)S.qb(ri + 1), rd = R::kBases ? R::da(v) : (int)S.db(rj + 1);
+      const bool f0 = flag == 0;
+      const int rt = R::type(v);
+      return loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd, f0 ? rq : nq,
+                              f0 ? rd : nd);
+    };
+    // (the records of the first round are the same for every cell of the anti-diagonal and were fetched at its start - with two
+    // cells, lanes 4-7 take theirs from lanes 0-3)
+    if constexpr (kQualScan) {
+      typename R::word v0 = v_first;
+      if constexpr (kTwoCells) {
+        if (pair_mode) {
+          // (the permute outside the select: every lane of the group takes part, or lanes 4-7 would read from inactive lanes)
+          const typename R::word v4 = (typename R::word)dpp_i32<0x114>((int)v_first); // row_shr:4
+          v0 = hi ? v4 : v_first;
+        }
       }
-    }
-    for (int k0 = d.lo; k0 < dstart; k0 += stride) {
-      GP_COUNT(13);
-      const int k = k0 + sub;
-      const auto v = vn;
-      const double hk = hn;
-      if (k + stride < dstart) {
-        vn = S.info(k + stride);
-        hn = S.hyb(k + stride);
-      }
-      if (k < dstart) {
-        const int ri = R::i(v), rj = R::j(v);
-        if (ri < ci && rj < cj) {
-          // LoopEnergy between the new pair and candidate k (:230-247); the loop lies between
-          // offsets (ri, rj) and (ci, cj) from the start
-          const int rq = R::kBases ? R::qa(v) : (int)S.qb(ri + 1), rd = R::kBases ? R::da(v) : (int)S.db(rj + 1);
-          // (the groups of a wavefront are in different directions most of the time: the outer and the
-          // inner pair are put in place with selects, so there is one copy of the look-up, not one per direction)
-          const bool f0 = flag == 0;
-          const int rt = R::type(v);
-          double te = loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd,
-                                       f0 ? rq : nq, f0 ? rd : nd);
+      scan_qualifying<R>(S, d.lo, dstart, sub, stride, ci, cj, v0, energy, bte, bkp, prof);
+    } else {
+      // (the records of the next round are fetched while this round's energies are looked up)
+      typename R::word vn = v_first;
+      double hn = h_first;
+      for (int k0 = d.lo; k0 < dstart; k0 += stride) {
+        GP_COUNT(13);
+        const int k = k0 + sub;
+        const auto v = vn;
+        const double hk = hn;
+        if (k + stride < dstart) {
+          vn = S.info(k + stride);
+          hn = S.hyb(k + stride);
+        }
+        if (k < dstart && R::i(v) < ci && R::j(v) < cj) {
+          double te = energy(v);
           te += hk;
           if (te < bte) {
             bte = te;
@@ -1073,44 +1120,18 @@ __device__ __forceinline__ bool dir_step_pair(const SearchConst &sc, const SeqBa
     int bkp = lo << 3;
     // (no records fetched ahead at the start of the step, nor the cell's own values ahead of the scan, as dir_step does:
     // the registers they occupy cost more here than the LDS latency they hide)
-    typename R::word vn = 0;
-    double hn = 0;
-    if (lo + sub < dstartA) {
-      vn = S.info(lo + sub);
-      hn = S.hyb(lo + sub);
-    }
-    for (int k0 = lo; k0 < dstartA; k0 += stride) {
-      GP_COUNT(13);
-      const int k = k0 + sub;
-      const auto v = vn;
-      const double hk = hn;
-      if (k + stride < dstartA) {
-        vn = S.info(k + stride);
-        hn = S.hyb(k + stride);
-      }
-#ifdef PRB_GAP_PROFILE
-      { // lanes with a candidate / with a qualifying candidate in this round (wave-level)
-        const bool has = k < dstartA, ok = has && R::i(v) < ci && R::j(v) < cj;
-        prof.acc[22] += (unsigned long long)__popcll(__ballot(has));
-        prof.acc[23] += (unsigned long long)__popcll(__ballot(ok));
-      }
-#endif
-      if (k < dstartA) {
-        const int ri = R::i(v), rj = R::j(v);
-        if (ri < ci && rj < cj) {
+    const typename R::word v0 = lo + sub < dstartA ? S.info(lo + sub) : 0;
+    scan_qualifying<R>(
+        S, lo, dstartA, sub, stride, ci, cj, v0,
+        [&](typename R::word v) -> double {
+          const int ri = R::i(v), rj = R::j(v);
           const int rq = R::qa(v), rd = R::da(v);
           const bool f0 = flag == 0;
           const int rt = R::type(v);
-          double te = loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd,
-                                       f0 ? rq : nq, f0 ? rd : nd);
-          te += hk;
-          if (te < bte) {
-            bte = te;
-            bkp = (k << 3) | R::type(v);
-          }
-        }
-      }
-    }
+          return loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd,
+                                  f0 ? rq : nq, f0 ? rd : nd);
+        },
+        bte, bkp, prof);
     GP_MARK(4);
     group_min_halves(bte, bkp, pair_mode);
     GP_MARK(5);

@@ -19,6 +19,8 @@ capi.LIB_PATH = os.path.join(ROOT, "priblast_amd", "lib", "libpriblast_hip_prof.
 REGIONS = ["dir setup (windows)", "acc staging", "ptab reset + prune", "cell check", "candidate scan",
            "group reduce", "cell update", "dir/hit epilogue", "hit prologue", "hit loop tail",
            "#anti-diagonal steps", "#chunks", "#fill iterations", "#scan rounds", "loop top", "boundary block (others)"]
+SLOTS = 26  # kProfSlots of gapped_lds.hip: 16..23 wave-level counts, 24 "candidate test" (cycles), 25 #test rounds
+REGION_IDX = list(range(10)) + [14, 15, 24]
 
 
 def main():
@@ -35,16 +37,16 @@ def main():
     qb = capi.QBatch(ctx, qs, db.repeat_flag)
     qb.accessibility(db.W, db.delta)
     L = capi.lib()
-    buf = (ctypes.c_ulonglong * 240)()
+    buf = (ctypes.c_ulonglong * (10 * SLOTS))()
     L.prb_debug_gap_profile(buf, 1)
     ctx.reset_timers()
     hits, bp, counts = capi.search_page(ctx, qb, db, 0, capi.default_opts(), 3)
     L.prb_debug_gap_profile(buf, 1)
-    allv = np.array(buf[:], dtype=np.float64).reshape(10, 24)
+    allv = np.array(buf[:], dtype=np.float64).reshape(10, SLOTS)
     print(f"hits: seed {counts[0]}, post-ungapped {counts[1]}, final {counts[2]}")
     for s in ("gapped", "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow", "traceback", "traceback_slow"):
         print(f"  {s}: {ctx.stage_ms(s)[0]:.1f} ms")
-    total = allv[:, :10].sum() + allv[:, 14:16].sum()
+    total = allv[:, REGION_IDX].sum()
     names = {0: "tier 0 extend", 1: "tier 0 trace", 2: "tier 1 extend", 3: "tier 1 trace", 4: "tier 2 extend", 5: "tier 2 trace",
              6: "tier 3 extend", 7: "tier 3 trace", 8: "wave extend", 9: "wave trace"}
     # NOTE: the accumulators live in lane 0 of each wavefront, so a region also collects the time
@@ -52,20 +54,26 @@ def main():
     # (e.g. "dir/hit epilogue" = waiting for the longest extension of the wavefront).
     for kind, name in names.items():
         v = allv[kind]
-        cyc = v[:10].sum() + v[14:16].sum()
+        cyc = v[REGION_IDX].sum()
         if cyc == 0:
             continue
         print(f"{name}: {cyc / total * 100:.1f} % of all gapped wave-cycles")
-        for i in list(range(10)) + [14, 15]:
-            print(f"  {REGIONS[i]:24s} {v[i] / cyc * 100:6.2f} %")
+        for i in REGION_IDX:
+            print(f"  {REGIONS[i] if i < len(REGIONS) else 'candidate test':24s} {v[i] / cyc * 100:6.2f} %")
         if v[21]:
             print(f"  wave-level, per lockstep step ({v[21]:.0f} steps): fill iterations {v[16] / v[21]:.3f} (two cells each), "
                   f"busiest group's cells {v[17] / v[21]:.3f}, cells per group {v[18] / v[21] / 8:.3f}; "
                   f"if two anti-diagonals shared a fill loop: {v[19] / max(v[20], 1):.3f} iterations per pair of steps "
                   f"(now {2 * v[16] / v[21]:.3f})")
         if v[22]:
-            print(f"  candidates looked at per scan round (as seen by lane 0's wavefront): {v[22] / max(v[13], 1):.1f} lanes, "
+            # (the two-pass scan: slot 25 counts the test rounds over the records, slot 13 the energy rounds behind them)
+            rounds = v[25] if v[25] else v[13]
+            print(f"  candidates looked at per test round (as seen by lane 0's wavefront): {v[22] / max(rounds, 1):.1f} lanes, "
                   f"of which qualify (ri < ci, rj < cj): {v[23] / v[22] * 100:.1f} %")
+        if v[25]:
+            print(f"  test rounds per fill iteration (lane 0's group): {v[25] / max(v[12], 1):.3f}")
+        if v[12]:
+            print(f"  {'energy' if v[25] else 'scan'} rounds per fill iteration (lane 0's group): {v[13] / v[12]:.3f}")
         print("  wave-level counts: " + ", ".join(f"{REGIONS[i]} {v[i]:.3g}" for i in range(10, 14)))
 
 
