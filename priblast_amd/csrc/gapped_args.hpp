@@ -74,6 +74,7 @@ struct GapArgs {
   double *acc_scratch = nullptr; // LDS tiers 1 and 2: 2 x capacity doubles per resident group (gapped_acc_scratch_bytes)
   int period = 0;   // LDS tiers: lockstep iterations between the boundaries at which groups change direction / hit (0: the drop-out length)
   int early = 0;    // LDS tiers: a boundary also as soon as this many groups of the wavefront have finished their direction (0: never)
+  int pool = 1;     // tier 0 with two anti-diagonals per step: the filled cells of a step pooled over the wavefront (0: each group its own)
   int handover = 0; // mode 0, LDS tiers and the wavefront-per-hit kernel: stop behind a first direction that this kernel ran (kHandoverMark)
 };
 

@@ -14,8 +14,8 @@
 // kept redundantly in every lane.  The reference's growing 100x100 Cell matrix never exists.
 // The groups of a wavefront run all of this in lockstep, so a loop costs what its busiest group
 // needs: the kernels are shaped to keep that maximum small (one loop over the filled cells of an
-// anti-diagonal - of two anti-diagonals in tier 0, dir_step_pair -, two cells at once on half a group each, one
-// instruction stream for both directions) rather than to keep every lane busy.
+// anti-diagonal, two cells at once on half a group each; in tier 0 the cells of two anti-diagonals, pooled over the
+// whole wavefront - pair_fill_pool -; one instruction stream for both directions) rather than to keep every lane busy.
 //
 // Two forms, a cascade of five kernels (a hit goes on to the next one when it outgrows the state a
 // kernel has room for; the LDS tiers hand their state over, so the next tier continues instead of
@@ -39,7 +39,8 @@ namespace prb {
 // Developer-only cycle breakdown of the gapped kernel (make PROF=1 builds libpriblast_hip_prof.so;
 // tools/gapped_profile.py reads it).  Not part of the product build.
 #ifdef PRB_GAP_PROFILE
-constexpr int kProfSlots = 26;
+// slots 16-23, 25, 30: counts; 29: marks whose clock went backwards (their delta is dropped, not booked as ~2^64 cycles)
+constexpr int kProfSlots = 31;
 __device__ unsigned long long g_gap_prof[10 * kProfSlots]; // [tier * 2 + (mode != 0)][region]
 struct GapProf {
   unsigned long long last, acc[kProfSlots];
@@ -50,7 +51,8 @@ struct GapProf {
   }
   __device__ __forceinline__ void mark(int r) {
     const unsigned long long t = __builtin_amdgcn_s_memtime();
-    acc[r] += t - last;
+    if (t >= last) acc[r] += t - last;
+    else acc[29] += 1;
     last = t;
   }
   __device__ __forceinline__ void count(int r) { acc[r] += 1; }
@@ -87,7 +89,7 @@ struct Tier0 { // 1,280 B per hit: 4 workgroups of 256 threads (32 hits) are exa
   static constexpr int kG = 8, kCapD = 32, kCapR = PRB_T0_CAPR, kGroups = 32, kWavesPerSimd = PRB_T0_WGCU, kWgPerCu = PRB_T0_WGCU;
   static constexpr bool kResumable = true; // a hit that outgrows it is continued, not redone, by the next tier
   static constexpr bool kResumes = false;
-  static constexpr bool kPairSteps = true; // two anti-diagonals per step where that is safe (dir_step_pair)
+  static constexpr bool kPairSteps = true; // two anti-diagonals per step where that is safe (pair_prep)
   static constexpr bool kAccGlobal = PRB_T0_ACC_GLOBAL;
 };
 #ifndef PRB_T12_ACC_GLOBAL
@@ -968,21 +970,57 @@ __device__ __forceinline__ bool dir_step(const SearchConst &sc, const SeqBases &
   return false;
 }
 
-// dir_step for eight-lane groups with at most 32 cells per anti-diagonal, TWO anti-diagonals per call where that
-// changes nothing.  The eight groups of a wavefront run their fill loops in lockstep, so a step costs what its busiest
-// group needs - 1.31 iterations per anti-diagonal where a group has 0.68 cells (PROF build, configs[2] shape).  Cells
-// of anti-diagonal L + 1 never take a cell of L as predecessor (ri < ci and rj < cj with ri + rj = L, ci + cj = L + 1
-// is impossible), and their helix check reads the types of L - 1: the two anti-diagonals only meet in the cell list
-// and in the running minimum, both of which take A's cells before B's.  One fill loop over both: 2.10 iterations
-// instead of 2.62, one pass through the prologue and the loop top instead of two.
+// The step of eight-lane groups with at most 32 cells per anti-diagonal, TWO anti-diagonals per step where that
+// changes nothing.  Cells of anti-diagonal L + 1 never take a cell of L as predecessor (ri < ci and rj < cj with
+// ri + rj = L, ci + cj = L + 1 is impossible), and their helix check reads the types of L - 1: the two anti-diagonals
+// only meet in the cell list and in the running minimum, both of which take A's cells before B's.  One fill over both,
+// one pass through the prologue and the loop top instead of two.
 // B is taken along only when A cannot be the last anti-diagonal (no improvement for `drop` lengths / both strands at
-// their ends), the state has room for both in full, and B's accessibility sums are staged; else the call is dir_step.
+// their ends), the state has room for both in full, and B's accessibility sums are staged; else the step is A alone.
 // The list as B's cells see it: live candidates [loB, dstartA) - A's cells lie behind and never qualify -, and the
 // default predecessor of a cell without candidates is entry loB, which is A's first cell when everything older has
 // been pruned (its type is known from the check, the record itself may not be written yet).
+// A step comes in three pieces so that its filled cells can be pooled over the wavefront: pair_prep (per group: prologue,
+// prune, the check of A and B), the fill (pair_fill_pool: all 64 lanes, the cells of every group of the wavefront;
+// pair_fill_group: each group its own, two at a time) and pair_close (per group: the running minimum, the end tests).
+// During the fill the list [lo, dstartA) is only read and records are only written at dstartA and behind it, so the cells
+// of a step - of any group - can be filled in any order and on any lanes.
+
+// What a group's step hands from its check to the fill and the end tests.  Bit b of cellsA / cellsB: cell i_loA + b of A / B is
+// filled - only as many as the cell list has room for -; their records go to nrec, nrec + 1, ... in the order A, B, ascending i.
+struct PairStep {
+  uint32_t cellsA, cellsB;
+  int LA, loA, loB, dstartA, i_loA, curA, typeA0, nrec;
+  bool paired;
+};
+
+// position of the r-th (from 0) set bit of m (r < popcount(m); else some position below 32)
+__device__ __forceinline__ int nth_bit(uint32_t m, int r) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 16; w >= 1; w >>= 1) {
+    const int c = __popc(m & ((1u << w) - 1));
+    if (r >= c) {
+      r -= c;
+      m >>= w;
+      pos += w;
+    }
+  }
+  return pos;
+}
+
+// pair type of the cell (i, j) whose bases pair, as dir_step's cell_type has it
+template <class Store> __device__ __forceinline__ int pair_type(const SearchConst &sc, const Store &S, int flag, int i, int j) {
+  const unsigned x0 = (unsigned)S.qb(i) * 5 + S.db(j);
+  int t = (int)((sc.bp_rows >> ((x0 * 3 - 15) & 63)) & 7);
+  if (flag == 1) t = ((t - 1) ^ 1) + 1;
+  return t;
+}
+
+// Prologue, prune and the check of a step; true when the direction has no room for another anti-diagonal (no cells then).
 template <class Store>
-__device__ __forceinline__ bool dir_step_pair(const SearchConst &sc, const SeqBases &sb, const ExtOpts &o, const HitCtx &c, int flag,
-                                              const Store &S, int gl, int gbase, DirState &d, GapProf &prof) {
+__device__ __forceinline__ bool pair_prep(const SearchConst &sc, const SeqBases &sb, const ExtOpts &o, const HitCtx &c, int flag,
+                                          const Store &S, int gl, int gbase, DirState &d, PairStep &p, GapProf &prof) {
   constexpr int G = 8;
   using R = typename Store::R;
   static_assert(Store::kCapD <= 32, "a 32-bit mask of cells per anti-diagonal");
@@ -1021,13 +1059,6 @@ __device__ __forceinline__ bool dir_step_pair(const SearchConst &sc, const SeqBa
   const int i_hiA = (LA < d.tq0 ? LA : d.tq0) - 1;
   d.resume_i0 = 0;
 
-  // pair type of the cell (i, j) whose bases pair, as dir_step's cell_type has it
-  auto pair_type = [&](int i, int j) -> int {
-    const unsigned x0 = (unsigned)S.qb(i) * 5 + S.db(j);
-    int t = (int)((sc.bp_rows >> ((x0 * 3 - 15) & 63)) & 7);
-    if (flag == 1) t = ((t - 1) ^ 1) + 1;
-    return t;
-  };
   // CheckHelixLength + GetBPType (see dir_step's cell_type) for cell (i, j): x0, x1, x2 = 5 * query base + database base
   // of the cell and of the two positions ahead of it on its diagonal, pt = Cell::type of its diagonal predecessor
   auto helix_ok = [&](unsigned x0, unsigned x1, unsigned x2, int pt, int i, int j) -> bool {
@@ -1040,7 +1071,7 @@ __device__ __forceinline__ bool dir_step_pair(const SearchConst &sc, const SeqBa
     return (p0 & (ahead | ~need) & 1) != 0;
   };
 
-  // ---- anti-diagonal B = LA + 1 in the same fill loop?  (LB mod 3 = (LA - 2) mod 3 = d2A; (LB - 2) mod 3 = d2B) ----
+  // ---- anti-diagonal B = LA + 1 in the same step?  (LB mod 3 = (LA - 2) mod 3 = d2A; (LB - 2) mod 3 = d2B) ----
   const int LB = LA + 1, d2B = curA == 0 ? 2 : curA - 1;
   const bool try_pair = !mid && openA && LA - (d.min_ci + d.min_cj) < drop && LA < S.cap_d() && LB <= d.staged;
   uint32_t cellsA = 0, cellsB = 0; // bit b: cell i = i_loA + b (both)
@@ -1100,112 +1131,194 @@ __device__ __forceinline__ bool dir_step_pair(const SearchConst &sc, const SeqBa
   int typeA0 = 0; // Stem::type of A's first cell as its record will hold it (0: A has no cell)
   if (paired && nA != 0) {
     const int iA0 = i_loA + __builtin_ctz(cellsA);
-    typeA0 = rtype_of(pair_type(iA0, LA - iA0));
+    typeA0 = rtype_of(pair_type(sc, S, flag, iA0, LA - iA0));
   }
 #ifdef PRB_GAP_PROFILE
   prof.cells_now = nA + __popc(cellsB);
 #endif
-  GP_MARK(3);
-
-  // one filled cell, or two at once on four lanes each (dir_step's fill_cell; a cell brings its anti-diagonal along)
-  auto fill_cell = [&](int ci, bool isB, bool two) -> int {
-    GP_COUNT(12);
-    const bool pair_mode = two, hi = pair_mode && gl >= G / 2;
-    const int sub = pair_mode ? (gl & (G / 2 - 1)) : gl, stride = pair_mode ? G / 2 : G;
-    const int L = LA + (isB ? 1 : 0), cur = isB ? (curA == 2 ? 0 : curA + 1) : curA, lo = isB ? loB : loA;
-    const int cj = L - ci;
-    const int ctype = pair_type(ci, cj);
-    const int nq = S.qb(ci - 1), nd = S.db(cj - 1);
-    double bte = 1000000.0; // INF
-    int bkp = lo << 3;
-    // (no records fetched ahead at the start of the step, nor the cell's own values ahead of the scan, as dir_step does:
-    // the registers they occupy cost more here than the LDS latency they hide)
-    const typename R::word v0 = lo + sub < dstartA ? S.info(lo + sub) : 0;
-    scan_qualifying<R>(
-        S, lo, dstartA, sub, stride, ci, cj, v0,
-        [&](typename R::word v) -> double {
-          const int ri = R::i(v), rj = R::j(v);
-          const int rq = R::qa(v), rd = R::da(v);
-          const bool f0 = flag == 0;
-          const int rt = R::type(v);
-          return loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd,
-                                  f0 ? rq : nq, f0 ? rd : nd);
-        },
-        bte, bkp, prof);
-    GP_MARK(4);
-    group_min_halves(bte, bkp, pair_mode);
-    GP_MARK(5);
-    if (d.nrec >= S.cap_r()) return -1;
-    int bk = bkp >> 3, ptype = bkp & 7;
-    // empty window - for a cell of B the list ends behind A's cells -: the reference reads stem_candidate[0] of an empty list
-    const bool a_first = isB && typeA0 != 0 && lo >= dstartA; // the default entry is A's first cell
-    if (lo >= dstartA && !a_first) bk = 0;
-    if (ptype == 0) ptype = a_first ? typeA0 : R::type(S.info(bk)); // no candidate qualified: the type of the default entry
-    const int rec = d.nrec + (hi ? 1 : 0);
-    if (sub == 0) {
-      S.hyb(rec) = bte;
-      S.info(rec) = R::pack(ci, cj, bk, rtype_of(ctype), S.qb(ci + 1), S.db(cj + 1));
-      S.ptab(cur, ci) = (uint8_t)ptype;
-    }
-    const double ie = S.eq(ci - 1) + S.ed(cj - 1) + bte;
-    // the first cell (lanes 0-3), then the second (lanes 4-7): each half gets the other's values from its mirror lane
-    const double ie_o = dpp_f64<0x141>(ie);
-    const int ci_o = dpp_i32<0x141>(ci), cj_o = dpp_i32<0x141>(cj);
-    const double ie_a = hi ? ie_o : ie, ie_b = hi ? ie : ie_o;
-    const int ci_a = hi ? ci_o : ci, ci_b = hi ? ci : ci_o, cj_a = hi ? cj_o : cj, cj_b = hi ? cj : cj_o;
-    if (ie_a < d.min_e) {
-      d.min_e = ie_a;
-      d.best = d.nrec;
-      d.min_ci = ci_a;
-      d.min_cj = cj_a;
-    }
-    if (pair_mode && ie_b < d.min_e) {
-      d.min_e = ie_b;
-      d.best = d.nrec + 1;
-      d.min_ci = ci_b;
-      d.min_cj = cj_b;
-    }
-    d.nrec += pair_mode ? 2 : 1;
-    GP_MARK(6);
-    return ptype;
-  };
-
-  unsigned long long cells = (unsigned long long)cellsA | ((unsigned long long)cellsB << 32);
-  while (cells) { // filled cells of A, then of B, ascending i, two at a time where there are two
-    const unsigned long long rest = cells & (cells - 1);
-    const bool two = rest != 0 && d.nrec + 2 <= S.cap_r();
-    const int b0 = __builtin_ctzll(cells);
-    if (Store::kResumable && d.nrec >= S.cap_r()) { // out of cells (never with B along): stop in front of this one
-      d.overflow = true;
-      d.resume_i0 = i_loA + b0;
+  // out of cells (never with B along): stop in front of the first cell that does not fit
+  const int room = S.cap_r() - d.nrec;
+  if (nA > room) {
+    const int keep = room > 0 ? room : 0, b = nth_bit(cellsA, keep);
+    cellsA &= (1u << b) - 1;
+    d.overflow = true;
+    if (Store::kResumable) {
+      d.resume_i0 = i_loA + b;
       d.resume_dstart = dstartA;
-      break;
     }
-    int b = b0;
-    if (two) {
-      if (gl >= G / 2) b = __builtin_ctzll(rest);
-      cells = rest & (rest - 1);
-    } else {
-      cells = rest;
+  }
+  p.cellsA = cellsA;
+  p.cellsB = cellsB;
+  p.LA = LA;
+  p.loA = loA;
+  p.loB = loB;
+  p.dstartA = dstartA;
+  p.i_loA = i_loA;
+  p.curA = curA;
+  p.typeA0 = typeA0;
+  p.nrec = d.nrec;
+  p.paired = paired;
+  GP_MARK(3);
+  return false;
+}
+
+// One filled cell of step p - i = p.i_loA + (b & 31), of A or (b >= 32) of B - on `stride` lanes (sub = 0..stride-1) of the
+// group whose state S is: its best predecessor among the live candidates, its record at `rec`, the predecessor's type in the
+// rotating row.  halves: the reduction stops at the quads (four-lane slots).  act = false: a slot without a cell, which takes
+// part in the reduction and writes nothing.
+template <class Store>
+__device__ __forceinline__ void pair_cell(const SearchConst &sc, const Store &S, int flag, const PairStep &p, int b, int rec, int sub,
+                                          int stride, bool halves, bool act, GapProf &prof) {
+  using R = typename Store::R;
+  GP_COUNT(12);
+  const bool isB = b >= 32;
+  const int cur = isB ? (p.curA == 2 ? 0 : p.curA + 1) : p.curA;
+  const int lo = act ? (isB ? p.loB : p.loA) : 0, dstart = act ? p.dstartA : 0;
+  const int ci = act ? p.i_loA + (b & 31) : 1, cj = act ? p.LA + (isB ? 1 : 0) - ci : 1;
+  const int ctype = pair_type(sc, S, flag, ci, cj);
+  const int nq = S.qb(ci - 1), nd = S.db(cj - 1);
+  double bte = 1000000.0; // INF
+  int bkp = lo << 3;
+  const typename R::word v0 = lo + sub < dstart ? S.info(lo + sub) : 0;
+  scan_qualifying<R>(
+      S, lo, dstart, sub, stride, ci, cj, v0,
+      [&](typename R::word v) -> double {
+        const int ri = R::i(v), rj = R::j(v);
+        const int rq = R::qa(v), rd = R::da(v);
+        const bool f0 = flag == 0;
+        const int rt = R::type(v);
+        return loop_energy_abcd(sc, f0 ? ctype : rt, f0 ? rt : ctype, ci - ri - 1, cj - rj - 1, f0 ? nq : rq, f0 ? nd : rd,
+                                f0 ? rq : nq, f0 ? rd : nd);
+      },
+      bte, bkp, prof);
+  GP_MARK(4);
+  group_min_halves(bte, bkp, halves);
+  GP_MARK(5);
+  int bk = bkp >> 3, ptype = bkp & 7;
+  // empty window - for a cell of B the list ends behind A's cells -: the reference reads stem_candidate[0] of an empty list
+  const bool a_first = isB && p.typeA0 != 0 && lo >= dstart; // the default entry is A's first cell
+  if (lo >= dstart && !a_first) bk = 0;
+  if (ptype == 0) ptype = a_first ? p.typeA0 : R::type(S.info(bk)); // no candidate qualified: the type of the default entry
+  if (act && sub == 0) {
+    S.hyb(rec) = bte;
+    S.info(rec) = R::pack(ci, cj, bk, rtype_of(ctype), S.qb(ci + 1), S.db(cj + 1));
+    S.ptab(cur, ci) = (uint8_t)ptype;
+  }
+  GP_MARK(6);
+}
+
+// The fill of a group's own cells, two at a time on four lanes each where there are two (PRB_GAPPED_POOL=0): the eight
+// groups of a wavefront run it in lockstep, so it costs what the busiest group needs.
+template <class Store>
+__device__ __forceinline__ void pair_fill_group(const SearchConst &sc, const Store &S, int flag, const PairStep &p, int gl, GapProf &prof) {
+  unsigned long long cells = (unsigned long long)p.cellsA | ((unsigned long long)p.cellsB << 32);
+  int rec = p.nrec;
+  while (cells) { // A, then B, ascending i
+    const unsigned long long rest = cells & (cells - 1);
+    const bool two = rest != 0, hi = two && gl >= 4;
+    const int b = hi ? __builtin_ctzll(rest) : __builtin_ctzll(cells);
+    pair_cell(sc, S, flag, p, b, rec + (hi ? 1 : 0), two ? (gl & 3) : gl, two ? 4 : 8, two, true, prof);
+    cells = two ? rest & (rest - 1) : rest;
+    rec += two ? 2 : 1;
+  }
+  GP_MARK(26); // (lane 0: the rest of the other groups' loops, once its own group is through)
+  group_sync<true>();
+}
+
+// The fill pooled over the wavefront: the (group, cell) items of its eight groups are numbered group after group - an
+// exclusive prefix over the groups' counts, in scalar registers - and dealt to 16 slots of four lanes per round, so the
+// wavefront runs ceil(cells / 16) rounds instead of the busiest group's ceil(cells / 2) iterations.  A slot takes its item's
+// step from the group's first lane (two packed words and the two cell masks, by ds_bpermute) and works on that group's state.
+// Every lane of the wavefront calls it, whatever its group is doing (a group without cells counts 0).
+template <class T, class Rec>
+__device__ __forceinline__ void pair_fill_pool(const SearchConst &sc, LdsLive<T, Rec> *wave_lds, int flag, const PairStep &p, int lane,
+                                               GapProf &prof) {
+  static_assert(T::kG == 8 && !T::kAccGlobal && T::kCapD < 255 && T::kCapR < 256, "eight groups per wavefront, state in LDS, 8-bit fields");
+  const int n = __popc(p.cellsA) + __popc(p.cellsB);
+  int incl[8]; // items of groups 0..g (wave-uniform)
+  int total = 0;
+#pragma unroll
+  for (int g = 0; g < 8; g++) {
+    total += __builtin_amdgcn_readlane(n, 8 * g);
+    incl[g] = total;
+  }
+  group_sync<true>(); // (the groups' row resets of pair_prep before any slot's type writes)
+  const uint32_t pk0 = (uint32_t)p.LA | ((uint32_t)p.loA << 8) | ((uint32_t)p.loB << 16) | ((uint32_t)p.dstartA << 24);
+  const uint32_t pk1 = (uint32_t)p.i_loA | ((uint32_t)p.curA << 8) | ((uint32_t)p.typeA0 << 10) | ((uint32_t)flag << 13) | ((uint32_t)p.nrec << 16);
+  const int slot = lane >> 2, sub = lane & 3;
+  for (int t0 = 0; t0 < total; t0 += 16) {
+    GP_COUNT(30);
+    const int t = t0 + slot;
+    int o = 0, ex = 0; // the item's group, and the items of the groups before it
+#pragma unroll
+    for (int g = 0; g < 7; g++) {
+      if (t >= incl[g]) {
+        o = g + 1;
+        ex = incl[g];
+      }
     }
-    const bool isB = b >= 32;
-    const int ptype = fill_cell(i_loA + (b & 31), isB, two);
-    if (ptype < 0) {
-      d.overflow = true;
-      break;
-    }
+    const int ob = 8 * o;
+    const uint32_t q0 = __shfl(pk0, ob), q1 = __shfl(pk1, ob), cA = __shfl(p.cellsA, ob), cB = __shfl(p.cellsB, ob);
+    PairStep po;
+    po.cellsA = cA;
+    po.cellsB = cB;
+    po.LA = q0 & 0xFF;
+    po.loA = (q0 >> 8) & 0xFF;
+    po.loB = (q0 >> 16) & 0xFF;
+    po.dstartA = q0 >> 24;
+    po.i_loA = q1 & 0xFF;
+    po.curA = (q1 >> 8) & 3;
+    po.typeA0 = (q1 >> 10) & 7;
+    po.nrec = q1 >> 16;
+    po.paired = false; // (not needed by the fill)
+    const int oflag = (q1 >> 13) & 1;
+    const int rank = t - ex, nA = __popc(cA);
+    const int b = rank < nA ? nth_bit(cA, rank) : 32 + nth_bit(cB, rank - nA);
+    GP_MARK(28);
+    const LdsStore<T, Rec> So{wave_lds[o], nullptr};
+    pair_cell(sc, So, oflag, po, b, po.nrec + rank, sub, 4, true, t < total, prof);
   }
   group_sync<true>();
-  GP_MARK(3);
-  if (d.overflow) return true;
-  if (paired) {
-    d.length = LA + 1;
-    d.lo = loB;
-    if (LB - (d.min_ci + d.min_cj) >= drop) return true;
-    return !(LB < d.tq0 || LB < d.td0);
+}
+
+// The end of a group's step: the running minimum (:260-278) over the step's records in their order with strict '<' - the
+// first record that holds the smallest ie, if that is below the minimum so far -, the cell count, the end tests.
+template <class Store>
+__device__ __forceinline__ bool pair_close(const ExtOpts &o, const Store &S, int gl, DirState &d, const PairStep &p, GapProf &prof) {
+  using R = typename Store::R;
+  const int drop = o.drop_w_gap;
+  const int n = __popc(p.cellsA) + __popc(p.cellsB);
+  if (n != 0) {
+    double m = __builtin_inf();
+    int key = 0x7fffffff;
+    for (int r = gl; r < n; r += 8) {
+      const auto v = S.info(p.nrec + r);
+      const double ie = S.eq(R::i(v) - 1) + S.ed(R::j(v) - 1) + S.hyb(p.nrec + r);
+      if (ie < m) {
+        m = ie;
+        key = r;
+      }
+    }
+    group_min<8>(m, key);
+    if (m < d.min_e) { // (everything else the reference notes down here follows from the cell)
+      const auto v = S.info(p.nrec + key);
+      d.min_e = m;
+      d.best = p.nrec + key;
+      d.min_ci = R::i(v);
+      d.min_cj = R::j(v);
+    }
+    d.nrec = p.nrec + n;
   }
-  if (LA - (d.min_ci + d.min_cj) >= drop) return true;
-  return !openA;
+  GP_MARK(6);
+  if (d.overflow) return true;
+  if (p.paired) {
+    d.length = p.LA + 1;
+    d.lo = p.loB;
+    if (p.LA + 1 - (d.min_ci + d.min_cj) >= drop) return true;
+    return !(p.LA + 1 < d.tq0 || p.LA + 1 < d.td0);
+  }
+  if (p.LA - (d.min_ci + d.min_cj) >= drop) return true;
+  return !(p.LA < d.tq0 || p.LA < d.td0);
 }
 
 // The hit after the direction (:300-318): grown by the cell of the minimum, if there is one.
@@ -1528,7 +1641,7 @@ __global__ __launch_bounds__(T::kG *T::kGroups) __attribute__((amdgpu_num_vgpr(1
 #else
 __global__ __launch_bounds__(T::kG *T::kGroups, T::kWavesPerSimd) void k_gapped_lds(GapArgs a) {
 #endif
-  static_assert(!kPair || (T::kPairSteps && T::kG == 8), "dir_step_pair");
+  static_assert(!kPair || (T::kPairSteps && T::kG == 8), "pair steps");
   __shared__ LdsLive<T, Rec> lds[T::kGroups];
   constexpr int G = T::kG;
   const int gl = threadIdx.x & (G - 1);
@@ -1602,7 +1715,17 @@ __global__ __launch_bounds__(T::kG *T::kGroups, T::kWavesPerSimd) void k_gapped_
     prof.cells_now = 0;
 #endif
     if constexpr (kPair) {
-      if (phase == kRun && dir_step_pair(a.sc, sb, a.o, c, flag, S, gl, gbase, d, prof)) phase = kFinished;
+      // the check per group, the fill pooled over the wavefront (a.pool; else per group), the end tests per group
+      const bool run = phase == kRun;
+      PairStep ps{0u, 0u, 0, 0, 0, 0, 0, 0, 0, 0, false};
+      bool fin = false;
+      if (run) fin = pair_prep(a.sc, sb, a.o, c, flag, S, gl, gbase, d, ps, prof);
+      GP_MARK(run ? 3 : 27);
+      if (a.pool) pair_fill_pool<T, Rec>(a.sc, &lds[gid & ~7], flag, ps, threadIdx.x & 63, prof);
+      else if (run) pair_fill_group(a.sc, S, flag, ps, gl, prof);
+      GP_MARK(run ? 26 : 27);
+      if (run && (fin || pair_close(a.o, S, gl, d, ps, prof))) phase = kFinished;
+      GP_MARK(run ? 6 : 27);
     } else {
       if (phase == kRun && dir_step<G, true>(a.sc, sb, a.o, c, flag, S, gl, gbase, d, prof)) phase = kFinished;
     }
@@ -1720,7 +1843,7 @@ size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec) {
 }
 
 namespace {
-template <class T, class Rec> hipError_t launch_tier(const GapArgs &a, int mode, hipStream_t s) {
+template <class T, class Rec> hipError_t launch_tier(GapArgs a, int mode, hipStream_t s) {
   const int64_t want = (a.n + T::kGroups - 1) / T::kGroups;
   const dim3 grid((unsigned)std::min<int64_t>(want, 256 * T::kWgPerCu)), blk(T::kG * T::kGroups);
   if (hipError_t e = hipMemsetAsync(a.next_work, 0, sizeof(unsigned long long), s); e != hipSuccess) return e;
@@ -1728,6 +1851,8 @@ template <class T, class Rec> hipError_t launch_tier(const GapArgs &a, int mode,
     const char *pe = getenv("PRB_GAPPED_PAIR"); // (read per launch: the tests switch it inside one process)
     const bool pair = !(pe && atoi(pe) == 0);
     if (pair) {
+      const char *pp = getenv("PRB_GAPPED_POOL"); // (likewise: 0 = each group fills its own cells)
+      a.pool = !(pp && atoi(pp) == 0);
       if (mode == 0) hipLaunchKernelGGL((k_gapped_lds<0, T, Rec, true>), grid, blk, 0, s, a);
       else hipLaunchKernelGGL((k_gapped_lds<2, T, Rec, true>), grid, blk, 0, s, a);
       return hipGetLastError();

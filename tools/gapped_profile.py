@@ -19,8 +19,11 @@ capi.LIB_PATH = os.path.join(ROOT, "priblast_amd", "lib", "libpriblast_hip_prof.
 REGIONS = ["dir setup (windows)", "acc staging", "ptab reset + prune", "cell check", "candidate scan",
            "group reduce", "cell update", "dir/hit epilogue", "hit prologue", "hit loop tail",
            "#anti-diagonal steps", "#chunks", "#fill iterations", "#scan rounds", "loop top", "boundary block (others)"]
-SLOTS = 26  # kProfSlots of gapped_lds.hip: 16..23 wave-level counts, 24 "candidate test" (cycles), 25 #test rounds
-REGION_IDX = list(range(10)) + [14, 15, 24]
+REGIONS += [""] * 8 + ["candidate test", "", "fill tail (other groups)", "waiting for a boundary", "pool: slot set-up"]
+# kProfSlots of gapped_lds.hip: 16..23 wave-level counts, 24 "candidate test" (cycles), 25 #test rounds, 26..28 cycles,
+# 29 marks whose clock went backwards (dropped), 30 wave-level rounds of the pooled fill
+SLOTS = 31
+REGION_IDX = list(range(10)) + [14, 15, 24, 26, 27, 28]
 
 
 def main():
@@ -59,12 +62,16 @@ def main():
             continue
         print(f"{name}: {cyc / total * 100:.1f} % of all gapped wave-cycles")
         for i in REGION_IDX:
-            print(f"  {REGIONS[i] if i < len(REGIONS) else 'candidate test':24s} {v[i] / cyc * 100:6.2f} %")
+            print(f"  {REGIONS[i]:24s} {v[i] / cyc * 100:6.2f} %")
+        if v[29]:
+            print(f"  ({v[29]:.0f} marks whose clock went backwards: their deltas are left out)")
         if v[21]:
             print(f"  wave-level, per lockstep step ({v[21]:.0f} steps): fill iterations {v[16] / v[21]:.3f} (two cells each), "
                   f"busiest group's cells {v[17] / v[21]:.3f}, cells per group {v[18] / v[21] / 8:.3f}; "
                   f"if two anti-diagonals shared a fill loop: {v[19] / max(v[20], 1):.3f} iterations per pair of steps "
                   f"(now {2 * v[16] / v[21]:.3f})")
+            if v[30]:
+                print(f"  pooled fill: {v[30] / v[21]:.3f} wave-level rounds per lockstep step (16 cells each)")
         if v[22]:
             # (the two-pass scan: slot 25 counts the test rounds over the records, slot 13 the energy rounds behind them)
             rounds = v[25] if v[25] else v[13]
