@@ -92,7 +92,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "filter", "gapped_front" (the kernel in front of the gapped cascade: the hits whose two directions find nothing;
  * "gapped_front_hits": launches = hits it completed), "gapped" (LDS tier 0; "gapped_tier0_hits": launches = hits that entered it),
  * "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow" (wavefront-per-hit kernel), "traceback", "traceback_slow",
- * "summary" (prb_search_page_summary: pair heads, segment starts and the per-pair fold; launches = 3 per sub-batch);
+ * "summary" (prb_search_page_summary: pair heads, segment starts and the per-pair fold; launches = 3 per sub-batch),
+ * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -199,6 +200,37 @@ const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps);
 void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]);
 void prb_pairset_free(prb_pairset *ps);
 
+/* ---- the N best pairs per query (`ris -t -n N`): a top-N table on the device ----
+ * A table holds, for each query of one batch, the N pairs with the lowest e_min among the per-pair summaries of the
+ * pages merged into it (fewer when the query has fewer pairs).  Pairs of a query are ranked by e_min ascending,
+ * compared as doubles (-0.0 == +0.0); equal values are ordered by the `-t` output order: page ascending, then the
+ * pair's position among that query's records of that page (prb_pairset_pairs order).  It is a total order, so the
+ * table does not depend on the order the pages are merged in, nor on how the batch is cut up.
+ *   prb_topset_create   an empty table for qb (1 <= n <= 1024; nq * n slots of about 72 B in HBM)
+ *   prb_search_page_top the search of prb_search_page_summary against `page`, its records merged into the table on
+ *                       the device (nothing is copied to the host).  Argument checks and option limits are those of
+ *                       prb_search_page_summary; the table must have been made with this context and this batch, and
+ *                       holds pages of one database, each merged once.  A call refused by these checks leaves the
+ *                       table as it was; a merge that fails part way leaves it unusable.
+ *   prb_topset_finish   copies the table to the host (one copy) and releases its device memory: prb_topset_pairs
+ *                       then returns the records by query ascending, then by rank; `rank` counts from 0 within the
+ *                       query.  No page can be merged after it (a second call does nothing)
+ *   prb_topset_counts   the stage counts of prb_pairset_counts, summed over the merged pages
+ * The device time of the merge is the stage "top" of prb_ctx_stage_ms. */
+typedef struct prb_top_pair {
+  prb_pair_summary s;
+  int32_t page, rank; /* the page the pair was found in; its rank within its query */
+} prb_top_pair;
+typedef struct prb_topset prb_topset;
+int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out);
+int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                        prb_topset *ts);
+int prb_topset_finish(prb_ctx *ctx, prb_topset *ts);
+int64_t prb_topset_size(const prb_topset *ts);
+const prb_top_pair *prb_topset_pairs(const prb_topset *ts);
+void prb_topset_counts(const prb_topset *ts, int64_t counts[3]);
+void prb_topset_free(prb_topset *ts);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -225,6 +257,10 @@ typedef struct prb_page_pairs {
 int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                             const prb_page_pairs *pages, int32_t npages, int64_t id0, int fd, int64_t *lines,
                             int64_t *bytes);
+/* The lines of `ris -t -n N` for one batch: pairs[0, n) as prb_topset_pairs returns them (ascending by query, then by
+ * rank), one line each in that order, numbered from id0 on; every line is the `-t` line of its pair. */
+int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                        const prb_top_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

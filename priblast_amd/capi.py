@@ -45,6 +45,10 @@ PAIR_DTYPE = np.dtype([("query", "<i4"), ("db_id", "<i4"), ("hits", "<i8"), ("e_
                        ("e_acc", "<f8"), ("e_hyb", "<f8"), ("bp_first", "<i4", (2,)), ("bp_last", "<i4", (2,))])
 assert PAIR_DTYPE.itemsize == 64
 
+# prb_top_pair: the embedded prb_pair_summary's fields, then the page it was found in and its rank within its query
+TOP_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
+assert TOP_DTYPE.itemsize == 72
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -99,6 +103,13 @@ SYMBOLS = {
     "prb_pairset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_pairset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_pairset_free": (None, [ctypes.c_void_p]),
+    "prb_topset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_top": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_topset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_topset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_topset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_topset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_topset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -110,6 +121,8 @@ SYMBOLS = {
                                        c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_summary_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p,
                                                c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_top_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                           c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
 }
 
 _lib = None
@@ -387,6 +400,56 @@ def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):
     return (pairs, tuple(counts)) if with_counts else pairs
 
 
+class TopSet:
+    """prb_topset: the N best pairs per query of one batch, in a table on the device that pages are merged into."""
+
+    def __init__(self, ctx, qb, n):
+        h = ctypes.c_void_p()
+        _check(lib().prb_topset_create(ctx.h, qb.h, n, ctypes.byref(h)))
+        self.h, self.ctx, self.qb = h, ctx, qb
+
+    def merge(self, db, page, opts=None):
+        """prb_search_page_top: searches the batch against `page` and merges its pairs into the table"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_top(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+
+    def finish(self):
+        """prb_topset_finish -> structured array TOP_DTYPE (a copy), by query, then rank"""
+        _check(lib().prb_topset_finish(self.ctx.h, self.h))
+        n = lib().prb_topset_size(self.h)
+        if not n:
+            return np.zeros(0, TOP_DTYPE)
+        buf = (ctypes.c_char * (n * TOP_DTYPE.itemsize)).from_address(lib().prb_topset_pairs(self.h))
+        return np.frombuffer(buf, TOP_DTYPE).copy()
+
+    def counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_topset_counts(self.h, c)
+        return tuple(c)
+
+    def close(self):
+        if self.h:
+            lib().prb_topset_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_top(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
+    """The n pairs of lowest e_min per query over the pages (all of them, in this order, by default) -> structured array
+    TOP_DTYPE, by query, then rank.  with_counts: -> (records, (seed, ungapped, final) counts summed over the pages)."""
+    with TopSet(ctx, qb, n) as ts:
+        for p in range(db.npages) if pages is None else pages:
+            ts.merge(db, p, opts)
+        recs = ts.finish()
+        counts = ts.counts()
+    return (recs, counts) if with_counts else recs
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -458,4 +521,16 @@ def write_summary_lines(db, qnames, qlen_unmasked, pages, id0=0, fd=-1):
     lines, nbytes = c_i64(), c_i64()
     _check(lib().prb_write_summary_lines(db.h, len(qnames), names, ql.ctypes.data, arr, len(pages), id0, fd,
                                          ctypes.byref(lines), ctypes.byref(nbytes)))
+    return lines.value, nbytes.value
+
+
+def write_top_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
+    """Lines of `ris -t -n N` for one batch: recs as search_top returns them.  -> (lines, bytes) written to fd
+    (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, TOP_DTYPE)
+    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
+    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
+    lines, nbytes = c_i64(), c_i64()
+    _check(lib().prb_write_top_lines(db.h, len(qnames), names, ql.ctypes.data, recs.ctypes.data if len(recs) else None,
+                                     len(recs), id0, fd, ctypes.byref(lines), ctypes.byref(nbytes)))
     return lines.value, nbytes.value

@@ -323,6 +323,25 @@ struct prb_qbatch {
   std::unique_ptr<SeedPlan> plan; // a seed search started ahead of prb_search_page, if any
 };
 
+// prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
+struct prb_topset {
+  prb_ctx *ctx = nullptr;
+  const prb_qbatch *qb = nullptr;
+  const prb_db *db = nullptr; // of the first merged page
+  int32_t nq = 0, n = 0;
+  DevBuf table;                 // prb_top_pair[nq * n] (`rank` = the pair's ordinal on the device), then int32_t fill[nq]
+  std::vector<uint8_t> merged;  // per page of db
+  bool broken = false;          // a merge failed part way
+  bool finished = false;        // prb_topset_finish: the records are in `pairs`, the device table is released
+  int64_t counts[3] = {0, 0, 0};
+  std::vector<prb_top_pair> pairs; // prb_topset_finish
+  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(prb_top_pair); }
+  ~prb_topset() { // (also on the error paths of prb_topset_create)
+    if (table.p) (void)hipSetDevice(ctx->device);
+    table.release();
+  }
+};
+
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS).  An explicit count,
 // because launchers such as torchrun export OMP_NUM_THREADS=1: PRB_HOST_THREADS, else
@@ -1852,8 +1871,10 @@ static int search_range(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int page, cons
     // results: records packed on the device (with their base-pair ranges), one asynchronous copy
     // each for hits and pairs into a pinned slot; the background thread appends them to the hit set
     const int slot = hs->next_slot;
-    hs->next_slot ^= 1;
-    hs->drain->acquire(slot);
+    if (!hs->top) { // (a top-N search copies nothing: no staging slot)
+      hs->next_slot ^= 1;
+      hs->drain->acquire(slot);
+    }
     if (hs->summary) {
       // per-pair summaries instead: the best hits' end pairs as the simplified output has them, then the pairs' runs of
       // the list (contiguous: F is sorted by query, then db_sp, and a sub-batch is a range of whole queries) reduced
@@ -1880,9 +1901,18 @@ static int search_range(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int page, cons
         return PRB_ERR_STATE;
       }
       const size_t rec_bytes = npairs * sizeof(prb_pair_summary);
-      if ((rc = w.packed.ensure(rec_bytes)) ||
-          (rc = w.pin_hits[slot].ensure(w.pin_hits[slot].cap >= rec_bytes ? rec_bytes : 2 * rec_bytes)))
-        return rc;
+      if ((rc = w.packed.ensure(rec_bytes))) return rc;
+      if (hs->top) { // top-N: the records are merged into the device table; nothing leaves the device
+        prb_topset *ts = hs->top;
+        PRB_HIP(launch_pair_fold(F, nfin, w.pairStart.as<uint32_t>(), (int64_t)npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+        if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
+        if ((rc = ctx->time_begin())) return rc;
+        PRB_HIP(launch_top_merge(w.packed.p, (int64_t)npairs, hs->sub_q0, hs->sub_q1, page, ts->n, ts->table.p,
+                                 reinterpret_cast<int32_t *>(ts->table.as<char>() + ts->slots_bytes()), ctx->stream));
+        hs->hits_total += nfin;
+        return ctx->time_end(ctx->top_timer, 1);
+      }
+      if ((rc = w.pin_hits[slot].ensure(w.pin_hits[slot].cap >= rec_bytes ? rec_bytes : 2 * rec_bytes))) return rc;
       PRB_HIP(launch_pair_fold(F, nfin, w.pairStart.as<uint32_t>(), (int64_t)npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
       PRB_HIP(hipEventRecord(w.packed_ready, ctx->stream));
       PRB_HIP(hipStreamWaitEvent(w.copy_stream, w.packed_ready, 0));
@@ -2002,16 +2032,15 @@ int prb_qbatch_seed_search_begin(prb_ctx *ctx, prb_qbatch *qb, const prb_db *db,
 } // extern "C"
 
 // prb_search_page, and with `summary` the search of prb_search_page_summary (final hits reduced to per-pair records,
-// prb_hitset::pairs)
-static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                       bool summary, prb_hitset **out) {
-  const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
-  if (!ctx || !qb || !db || !opts || !out || qb->ctx->device != ctx->device || db->ctx->device != ctx->device || page < 0 ||
+// prb_hitset::pairs; with `top` as well, those merged into the top-N table instead)
+// the argument checks and option limits of a search (`fn` names the entry point in the messages)
+static int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
+                             const prb_ris_opts *opts, int32_t last_stage) {
+  if (!ctx || !qb || !db || !opts || qb->ctx->device != ctx->device || db->ctx->device != ctx->device || page < 0 ||
       page >= (int32_t)db->pages.size() || last_stage < 1 || last_stage > 3) {
     set_error(std::string(fn) + ": bad argument");
     return PRB_ERR_ARG;
   }
-  *out = nullptr;
   if (!qb->have_acc || qb->W != db->hdr.maximal_span || qb->delta != db->hdr.min_accessible_length) {
     set_error(std::string(fn) + ": query accessibilities must be computed with the database's span / window parameters");
     return PRB_ERR_STATE;
@@ -2026,6 +2055,18 @@ static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, c
               "31-entry loop tables), 1 <= -m <= 16, 1 <= -l <= 63 (the seed search keeps a path of 64 characters)");
     return PRB_ERR_ARG;
   }
+  return PRB_OK;
+}
+
+static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
+                       bool summary, prb_hitset **out, prb_topset *top = nullptr) {
+  const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
+  if (!out) {
+    set_error(std::string(fn) + ": bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (int rc = check_search_args(fn, ctx, qb, db, page, opts, last_stage)) return rc;
+  *out = nullptr;
   PRB_HIP(hipSetDevice(ctx->device));
   {
     // the page on the device (uploaded now unless it is resident or was prefetched), then - while it is searched -
@@ -2061,6 +2102,7 @@ static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, c
   auto *hs = new prb_hitset();
   hs->device = ctx->device;
   hs->summary = summary;
+  hs->top = top;
   hs->on_device = ctx->keep_device_records && last_stage == 3 && !summary;
   hs->d_hits.hint = ctx->keep_hint_hits;
   hs->d_bp.hint = ctx->keep_hint_bp;
@@ -2183,6 +2225,8 @@ static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, c
     };
     {
       HostTimer ht(ctx, "host_search_range");
+      hs->sub_q0 = q0;
+      hs->sub_q1 = q1;
       rc = search_range(ctx, qb, db, page, *opts, last_stage, cd, ncand, nrows, nqent, hs, front_free);
       if (rc == PRB_ERR_NOMEM) // (the seed pools and the gapped stage's state are bounded by their chunk budgets; what grows with a
                                //  query is the list behind -f itself, ~200 B per hit with its sort keys)
@@ -2260,6 +2304,129 @@ int prb_search_page_summary(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
   return PRB_OK;
 }
 
+int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out) {
+  if (!ctx || !qb || !out) {
+    set_error("prb_topset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  if (n < 1 || n > kTopMaxN) {
+    set_error("prb_topset_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+    return PRB_ERR_ARG;
+  }
+  std::unique_ptr<prb_topset> ts(new (std::nothrow) prb_topset());
+  if (!ts) {
+    set_error("prb_topset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  ts->ctx = ctx;
+  ts->qb = qb;
+  ts->nq = qb->nq;
+  ts->n = n;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = ts->slots_bytes() + (size_t)qb->nq * sizeof(int32_t);
+  if (int rc = ts->table.ensure(std::max<size_t>(bytes, 1))) return rc;
+  PRB_HIP(hipMemsetAsync(ts->table.p, 0, std::max<size_t>(bytes, 1), ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ts.release();
+  return PRB_OK;
+}
+
+int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_topset *ts) {
+  if (!ts) {
+    set_error("prb_search_page_top: bad argument");
+    return PRB_ERR_ARG;
+  }
+  // (every check before the table is touched: a refused call leaves it as it was)
+  if (int rc = check_search_args("prb_search_page_top", ctx, qb, db, page, opts, 3)) return rc;
+  if (ts->ctx != ctx || ts->qb != qb || ts->nq != qb->nq) {
+    set_error("prb_search_page_top: the top-N table was made for another context or query batch (" + std::to_string(ts->nq) +
+              " queries; this batch has " + std::to_string(qb->nq) + ")");
+    return PRB_ERR_ARG;
+  }
+  if (ts->db && ts->db != db) {
+    set_error("prb_search_page_top: the top-N table holds pages of another database");
+    return PRB_ERR_ARG;
+  }
+  if (ts->broken) {
+    set_error("prb_search_page_top: an earlier merge into this top-N table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ts->finished) {
+    set_error("prb_search_page_top: the top-N table is finished (prb_topset_finish)");
+    return PRB_ERR_STATE;
+  }
+  if (!ts->db) {
+    ts->db = db;
+    ts->merged.assign(db->pages.size(), 0);
+  }
+  if (ts->merged[(size_t)page]) {
+    set_error("prb_search_page_top: page " + std::to_string(page) + " is already merged into this top-N table");
+    return PRB_ERR_ARG;
+  }
+  ts->merged[(size_t)page] = 1;
+  prb_hitset *hs = nullptr;
+  const int rc = search_page(ctx, qb, db, page, opts, 3, true, &hs, ts);
+  if (rc != PRB_OK) {
+    ts->broken = true;
+    return rc;
+  }
+  for (int i = 0; i < 3; i++) ts->counts[i] += hs->counts[i];
+  delete hs;
+  return PRB_OK;
+}
+
+int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
+  if (!ctx || !ts || ts->ctx != ctx) {
+    set_error("prb_topset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (ts->broken) {
+    set_error("prb_topset_finish: an earlier merge into this top-N table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ts->finished) return PRB_OK; // (the records are on the host already)
+  try {
+    std::vector<int32_t> fill((size_t)ts->nq);
+    // (slots and fill counts are one block: one copy)
+    std::vector<char> host(ts->slots_bytes() + fill.size() * sizeof(int32_t));
+    PRB_HIP(hipSetDevice(ctx->device));
+    if (!host.empty()) {
+      PRB_HIP(hipMemcpyAsync(host.data(), ts->table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    std::memcpy(fill.data(), host.data() + ts->slots_bytes(), fill.size() * sizeof(int32_t));
+    ts->pairs.clear();
+    for (int32_t q = 0; q < ts->nq; q++) {
+      if (fill[q] < 0 || fill[q] > ts->n) {
+        set_error("prb_topset_finish: query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
+        return PRB_ERR_STATE;
+      }
+      for (int32_t r = 0; r < fill[q]; r++) {
+        prb_top_pair p;
+        std::memcpy(&p, host.data() + ((size_t)q * ts->n + r) * sizeof(prb_top_pair), sizeof p);
+        p.rank = r;
+        ts->pairs.push_back(p);
+      }
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_topset_finish: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  ts->finished = true;
+  ts->table.release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_topset_size(const prb_topset *ts) { return ts ? (int64_t)ts->pairs.size() : -1; }
+const prb_top_pair *prb_topset_pairs(const prb_topset *ts) { return ts ? ts->pairs.data() : nullptr; }
+void prb_topset_counts(const prb_topset *ts, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ts ? ts->counts[i] : 0;
+}
+void prb_topset_free(prb_topset *ts) {
+  delete ts;
+}
+
 int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }
 const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps) { return ps ? ps->pairs.data() : nullptr; }
 void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]) {
@@ -2322,6 +2489,45 @@ int prb_write_lines(const prb_db *db, int32_t nq, const char *const *qnames, con
     }
   } catch (const std::exception &e) {
     set_error(std::string("prb_write_lines: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  return PRB_OK;
+}
+
+int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                        const prb_top_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  if (!db || nq < 0 || (nq && (!qnames || !qlen_unmasked)) || n < 0 || (n && !pairs)) {
+    set_error("prb_write_top_lines: bad argument");
+    return PRB_ERR_ARG;
+  }
+  try {
+    TopView v;
+    std::vector<std::string> names((size_t)nq);
+    for (int32_t q = 0; q < nq; q++) names[q] = qnames[q];
+    v.nq = (size_t)nq;
+    v.names = names.data();
+    v.qlen_unmasked = qlen_unmasked;
+    for (int64_t i = 0; i < n; i++) {
+      const prb_top_pair &x = pairs[i];
+      if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq || x.s.db_id < 0 ||
+          x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || (i && x.s.query < pairs[i - 1].s.query)) {
+        set_error("prb_write_top_lines: pair record " + std::to_string(i) + " is inconsistent");
+        return PRB_ERR_ARG;
+      }
+    }
+    v.r = pairs;
+    v.n = n;
+    LineSink sink;
+    sink.fd = fd;
+    const int64_t next = format_top_batch(v, db->tabs, id0, sink, format_threads());
+    if (lines) *lines = sink.lines;
+    if (bytes) *bytes = sink.bytes;
+    if (next < 0) {
+      set_error("prb_write_top_lines: write failed");
+      return PRB_ERR_IO;
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_write_top_lines: ") + e.what());
     return PRB_ERR_NOMEM;
   }
   return PRB_OK;

@@ -61,6 +61,7 @@ struct prb_ctx {
   // the per-pair reduction of prb_search_page_summary (stage "summary"): kept apart from the stages of the full-output
   // search that `timers` holds and bench.py reports
   prb::StageTimer summary_timer;
+  prb::StageTimer top_timer; // the merge of prb_search_page_top (stage "top"), kept apart for the same reason
 
   int time_begin();
   int time_end(const char *stage, int64_t launches);

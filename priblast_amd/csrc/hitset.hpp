@@ -109,6 +109,10 @@ struct prb_hitset {
   // empty and the records arrive here
   bool summary = false;
   std::vector<prb_pair_summary> pairs;
+  // prb_search_page_top: the records are merged into this table on the device instead (queries [sub_q0, sub_q1) are
+  // the sub-batch being searched)
+  prb_topset *top = nullptr;
+  int32_t sub_q0 = 0, sub_q1 = 0;
 };
 
 struct prb_pairset {

@@ -916,6 +916,230 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(HitSoA h, int64_t n, const
   out[k] = r;
 }
 
+// ---- top-N table (prb_search_page_top) ----
+// A pair's rank key is (energy key, tie key), compared as two u64 with the smaller one first.  The energy key maps
+// e_min to an unsigned integer of the same order (-0.0 becomes +0.0 first, so the two compare equal); the tie key is
+// (page << 32) | ordinal, the pair's position among its query's records of that page: the `-t` output order.  Within
+// one table no two pairs share a tie key (a page is merged once), so every merge below is one of distinct keys.
+constexpr int kTopBlock = 256;
+constexpr int kTopLoads = 4;                        // records per lane per step of the stream (loads in flight)
+constexpr int kTopTile = kTopBlock * kTopLoads;     // records per step
+constexpr int kTopCap = 2 * kTopMaxN;               // candidate buffer: room for at least one step beyond kTopMaxN
+constexpr int kTopPer = kTopMaxN / kTopBlock;       // set entries per lane in a merge
+constexpr int kTopCandPer = kTopCap / kTopBlock;    // candidate entries per lane in a merge
+static_assert(kTopPer * kTopBlock == kTopMaxN && kTopTile <= kTopCap - kTopMaxN, "top-N entries per lane");
+
+__device__ __forceinline__ uint64_t energy_key(double e) {
+  const uint64_t b = (uint64_t)__double_as_longlong(e + 0.0);
+  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ bool key_less(uint64_t a1, uint64_t a2, uint64_t b1, uint64_t b2) {
+  return a1 < b1 || (a1 == b1 && a2 < b2);
+}
+// entries of the sorted keys (k1, k2)[0, n) below (x1, x2)
+__device__ __forceinline__ int count_below(const uint64_t *k1, const uint64_t *k2, int n, uint64_t x1, uint64_t x2) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int m = (lo + hi) >> 1;
+    if (key_less(k1[m], k2[m], x1, x2)) lo = m + 1;
+    else hi = m;
+  }
+  return lo;
+}
+
+// One workgroup per query q = q0 + blockIdx.x of a sub-batch.  rec[0, nrec) are the sub-batch's pair records against
+// `page`, ascending by query, so q's records are one run [a, b).  The table keeps q's best pairs in slots
+// tab[q * n, q * n + fill[q]), in rank order; on the device a slot's `rank` holds its ordinal.
+// LDS (dynamic): the current set's keys and sources (n entries) and a candidate buffer of cap = kTopCap entries.  The
+// run streams through in steps of kTopTile records, kTopLoads per lane (one wavefront ballot per load): a record whose
+// key beats the set's n-th key (any key while the set is not full) is appended to the buffer, placed by the ballots
+// and the waves' counts.  When the next step might not fit, the buffer is bitonic-sorted and merged into the set (each entry's new place = its index + the entries of the
+// other list below it), the set is cut to n and the threshold drops.  At the end the set's records are gathered -
+// new ones from rec, kept ones from their old slots - and written in rank order.
+__global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary *__restrict__ rec, int64_t nrec, int32_t q0,
+                                                         int32_t page, int32_t n, int32_t cap, prb_top_pair *__restrict__ tab,
+                                                         int32_t *__restrict__ fill) {
+  extern __shared__ uint64_t top_lds[];
+  uint64_t *sk1 = top_lds, *sk2 = sk1 + n, *ck1 = sk2 + n, *ck2 = ck1 + cap;
+  uint32_t *ssrc = reinterpret_cast<uint32_t *>(ck2 + cap); // < 2^31: the old slot; else 2^31 | ordinal of a new record
+  __shared__ int64_t s_run[2];
+  __shared__ int s_wave[kTopBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t q = q0 + (int32_t)blockIdx.x;
+  if (tid < 2) { // lower bound of q (tid 0) and of q + 1 (tid 1) in rec
+    const int32_t want = q + tid;
+    int64_t lo = 0, hi = nrec;
+    while (lo < hi) {
+      const int64_t m = (lo + hi) >> 1;
+      if (rec[m].query < want) lo = m + 1;
+      else hi = m;
+    }
+    s_run[tid] = lo;
+  }
+  __syncthreads();
+  const int64_t a = s_run[0], b = s_run[1];
+  if (a >= b) return; // (uniform: no record of q against this page)
+  prb_top_pair *const slots = tab + (int64_t)q * n;
+  int cnt = fill[q];
+  for (int i = tid; i < cnt; i += kTopBlock) {
+    const prb_top_pair &t = slots[i];
+    sk1[i] = energy_key(t.s.e_min);
+    sk2[i] = ((uint64_t)(uint32_t)t.page << 32) | (uint32_t)t.rank;
+    ssrc[i] = (uint32_t)i;
+  }
+  __syncthreads();
+  uint64_t thr1 = ~0ull, thr2 = ~0ull;
+  if (cnt == n) {
+    thr1 = sk1[n - 1];
+    thr2 = sk2[n - 1];
+  }
+  int bcnt = 0;
+  bool changed = false;
+  auto flush = [&]() { // (uniform) sort the buffer, merge it into the set, cut to n
+    int P = 1;
+    while (P < bcnt) P <<= 1;
+    for (int i = bcnt + tid; i < P; i += kTopBlock) ck1[i] = ck2[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < P; i += kTopBlock) {
+          const int o = i ^ j;
+          if (o > i) {
+            const uint64_t x1 = ck1[i], x2 = ck2[i], y1 = ck1[o], y2 = ck2[o];
+            if (key_less(y1, y2, x1, x2) == ((i & k) == 0)) {
+              ck1[i] = y1;
+              ck2[i] = y2;
+              ck1[o] = x1;
+              ck2[o] = x2;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+    constexpr int kE = kTopPer + kTopCandPer;
+    uint64_t e1[kE], e2[kE];
+    uint32_t src[kE];
+    int pos[kE];
+#pragma unroll
+    for (int r = 0; r < kTopPer; r++) {
+      const int i = tid + r * kTopBlock;
+      pos[r] = n; // (not written)
+      if (i < cnt) {
+        e1[r] = sk1[i];
+        e2[r] = sk2[i];
+        src[r] = ssrc[i];
+        pos[r] = i + count_below(ck1, ck2, bcnt, e1[r], e2[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kTopCandPer; r++) {
+      const int i = tid + r * kTopBlock;
+      pos[kTopPer + r] = n;
+      if (i < bcnt) {
+        e1[kTopPer + r] = ck1[i];
+        e2[kTopPer + r] = ck2[i];
+        src[kTopPer + r] = 0x80000000u | (uint32_t)ck2[i];
+        pos[kTopPer + r] = i + count_below(sk1, sk2, cnt, ck1[i], ck2[i]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kE; r++) {
+      if (pos[r] < n) {
+        sk1[pos[r]] = e1[r];
+        sk2[pos[r]] = e2[r];
+        ssrc[pos[r]] = src[r];
+      }
+    }
+    __syncthreads();
+    cnt = min(n, cnt + bcnt);
+    bcnt = 0;
+    changed = true;
+    if (cnt == n) {
+      thr1 = sk1[n - 1];
+      thr2 = sk2[n - 1];
+    }
+  };
+  const uint64_t below = (1ull << lane) - 1;
+  for (int64_t base = a; base < b; base += kTopTile) {
+    if (bcnt + kTopTile > cap) flush();
+    double e[kTopLoads];
+#pragma unroll
+    for (int u = 0; u < kTopLoads; u++) { // (all loads issued before the first is used)
+      const int64_t i = base + u * kTopBlock + tid;
+      e[u] = i < b ? rec[i].e_min : 0.0;
+    }
+    uint64_t k1[kTopLoads], mask[kTopLoads];
+    bool take[kTopLoads];
+    int mine = 0;
+#pragma unroll
+    for (int u = 0; u < kTopLoads; u++) {
+      const int64_t i = base + u * kTopBlock + tid;
+      k1[u] = energy_key(e[u]);
+      take[u] = i < b && key_less(k1[u], ((uint64_t)(uint32_t)page << 32) | (uint32_t)(i - a), thr1, thr2);
+      mask[u] = __ballot(take[u]);
+      mine += __popcll(mask[u]);
+    }
+    if (lane == 0) s_wave[wave] = mine;
+    __syncthreads();
+    int off = bcnt, total = 0;
+#pragma unroll
+    for (int w = 0; w < kTopBlock / 64; w++) {
+      const int c = s_wave[w];
+      off += w < wave ? c : 0;
+      total += c;
+    }
+#pragma unroll
+    for (int u = 0; u < kTopLoads; u++) {
+      if (take[u]) {
+        const int64_t i = base + u * kTopBlock + tid;
+        const int at = off + __popcll(mask[u] & below);
+        ck1[at] = k1[u];
+        ck2[at] = ((uint64_t)(uint32_t)page << 32) | (uint32_t)(i - a);
+      }
+      off += __popcll(mask[u]);
+    }
+    bcnt += total;
+    __syncthreads(); // (the buffer is complete, s_wave free for the next step)
+  }
+  if (bcnt > 0) flush();
+  if (!changed) return;
+  // Write-back in rank order.  A kept pair moves from slot s to a place j >= s, so rounds of 256 places from the top
+  // down never read a slot an earlier round wrote; within a round every lane reads before any lane writes.
+  for (int r0 = ((cnt - 1) / kTopBlock) * kTopBlock; r0 >= 0; r0 -= kTopBlock) {
+    const int j = r0 + tid;
+    const prb_pair_summary *from = nullptr; // (the summary part, moved as 8 x 8 bytes: 8-byte aligned in both places)
+    int32_t pg = 0, rk = 0;
+    if (j < cnt) {
+      const uint32_t s = ssrc[j];
+      if (s & 0x80000000u) {
+        rk = (int32_t)(s & 0x7FFFFFFFu);
+        from = rec + a + rk;
+        pg = page;
+      } else if ((int)s != j) {
+        from = &slots[s].s;
+        pg = slots[s].page;
+        rk = slots[s].rank;
+      }
+    }
+    uint2 v[8];
+    if (from) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) v[k] = reinterpret_cast<const uint2 *>(from)[k];
+    }
+    __syncthreads();
+    if (from) {
+      uint2 *to = reinterpret_cast<uint2 *>(&slots[j].s);
+#pragma unroll
+      for (int k = 0; k < 8; k++) to[k] = v[k];
+      slots[j].page = pg;
+      slots[j].rank = rk;
+    }
+  }
+  if (tid == 0) fill[q] = cnt;
+}
+
 // keep[i] = 1 unless E_i > threshold.  A hit above the threshold is flagged by CheckRedundancy
 // the moment the sweep reaches it and never flags anything else (as the contained hit of an
 // earlier scan it loses: E_a <= threshold < E_b), so it can be dropped BEFORE the sort.
@@ -1359,6 +1583,16 @@ hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, i
                             hipStream_t s) {
   if (npairs <= 0 || n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_pair_fold, grid_for(npairs), dim3(kBlock), 0, s, h, n, start, npairs, ends, static_cast<prb_pair_summary *>(out));
+  return hipGetLastError();
+}
+hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
+                            hipStream_t s) {
+  if (nrec <= 0 || q1 <= q0) return hipSuccess;
+  if (n < 1 || n > kTopMaxN) return hipErrorInvalidValue;
+  const int cap = kTopCap;
+  const size_t lds = (size_t)n * (8 + 8 + 4) + (size_t)cap * 16; // at most 52 KB (n = 1024)
+  hipLaunchKernelGGL(k_top_merge, dim3((unsigned)(q1 - q0)), dim3(kTopBlock), lds, s, static_cast<const prb_pair_summary *>(rec), nrec,
+                     q0, page, n, cap, static_cast<prb_top_pair *>(tab), fill);
   return hipGetLastError();
 }
 hipError_t launch_flag_not_above(const double *e_tot, int64_t n, double thr, uint8_t *keep, hipStream_t s) {

@@ -138,6 +138,13 @@ hipError_t launch_pair_heads(const int32_t *query, const int32_t *db_id, int64_t
 // from `ends` (4 ints per hit, launch_bp_ends)
 hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, void *out,
                             hipStream_t s);
+// ---- top-N table (prb_search_page_top) ----
+constexpr int kTopMaxN = 1024; // the largest N: the set's keys and a candidate buffer of as many fit a workgroup's LDS
+// merges the pair records rec[0, nrec) (prb_pair_summary, launch_pair_fold's output for queries [q0, q1), ascending by
+// query) of `page` into the table: tab = prb_top_pair[nq * n] (slot `rank` = the pair's ordinal while on the device),
+// fill = int32_t[nq] (slots in use per query).  One workgroup per query; the page must not be in the table yet.
+hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
+                            hipStream_t s);
 hipError_t launch_gather_u8(const uint8_t *src, const uint32_t *idx, uint8_t *dst, int64_t n, hipStream_t s);
 hipError_t launch_iota_u32(uint32_t *dst, int64_t n, hipStream_t s); // dst[i] = i
 // flags[i] = marks[list[i]] & mask != 0

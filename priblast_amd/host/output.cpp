@@ -169,31 +169,36 @@ int64_t format_records(size_t nq, size_t np, NOf n_of, QueryOf query_of, Fmt fmt
   return ok ? id : -1;
 }
 
+// one summary line (`ris -t`) of pair x, found in the page whose table is `tab`
+void put_summary_line(Buf &b, int64_t id, const std::string &qname, int32_t qlen, const SeqTable &tab, const prb_pair_summary &x) {
+  char *p = b.room(qname.size() + tab.names[x.db_id].size() + 320);
+  char *const p0 = p;
+  p = put_names(p, id, qname, qlen, tab, x.db_id);
+  p = put_int(p, x.hits);
+  *p++ = ',';
+  p = put_g(p, x.e_min);
+  *p++ = ',';
+  p = put_g(p, x.e_sum);
+  *p++ = ',';
+  p = put_g(p, x.e_acc);
+  *p++ = ',';
+  p = put_g(p, x.e_hyb);
+  *p++ = ',';
+  p = put_ends(p, tab, x.db_id, x.bp_first, x.bp_last);
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
 void format_summary_piece(const Piece &pc, const SummaryView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   const PagePairs &pp = v.pages[pc.p];
-  const SeqTable &tab = tabs[pc.p];
-  const std::string &qname = v.names[pc.q];
-  const int32_t qlen = v.qlen_unmasked[pc.q];
   int64_t id = pc.id;
-  for (int64_t i = pc.i0; i < pc.i1; i++) {
-    const prb_pair_summary &x = pp.r[i];
-    char *p = b.room(qname.size() + tab.names[x.db_id].size() + 320);
-    char *const p0 = p;
-    p = put_names(p, id++, qname, qlen, tab, x.db_id);
-    p = put_int(p, x.hits);
-    *p++ = ',';
-    p = put_g(p, x.e_min);
-    *p++ = ',';
-    p = put_g(p, x.e_sum);
-    *p++ = ',';
-    p = put_g(p, x.e_acc);
-    *p++ = ',';
-    p = put_g(p, x.e_hyb);
-    *p++ = ',';
-    p = put_ends(p, tab, x.db_id, x.bp_first, x.bp_last);
-    *p++ = '\n';
-    b.n += (size_t)(p - p0);
-  }
+  for (int64_t i = pc.i0; i < pc.i1; i++) put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[pc.p], pp.r[i]);
+}
+
+void format_top_piece(const Piece &pc, const TopView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++)
+    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[v.r[i].page], v.r[i].s);
 }
 
 } // namespace
@@ -209,6 +214,13 @@ int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &
   return format_records(
       v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].r[i].query; },
       [&](const Piece &pc, Buf &b) { format_summary_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page": the records are in output order already, and each carries its own)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
+      [&](const Piece &pc, Buf &b) { format_top_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 } // namespace prb

@@ -61,6 +61,17 @@ struct SummaryView {
 };
 int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -t -n N` (prb_topset_pairs): the same lines, for ranked records that carry their page, in the records'
+// order (ascending by query, then by rank), numbered from id0 on.
+struct TopView {
+  size_t nq = 0;
+  const std::string *names = nullptr; // [nq]
+  const int32_t *qlen_unmasked = nullptr;
+  const prb_top_pair *r = nullptr;
+  int64_t n = 0;
+};
+int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 int format_threads(); // PRB_HOST_THREADS, else min(32, hardware threads)
 
 } // namespace prb

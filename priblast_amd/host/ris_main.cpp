@@ -20,7 +20,9 @@
 // `txt` sub-command turns such a file into exactly the text `ris` would have written, and `ris -t`
 // writes one summary line per (query, target) pair instead of one line per hit: the final hits are
 // reduced on the GPU (prb_search_page_summary) and never leave it.  `-t` is refused with `-b` and in
-// rank mode (WORLD_SIZE > 1): the gather carries hit records only.
+// rank mode (WORLD_SIZE > 1): the gather carries hit records only.  `-t -n N` keeps each query's N
+// pairs of lowest minimum energy: a table on the GPU (prb_search_page_top) takes every page of a
+// batch, and only its N records per query reach the host.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -84,6 +86,8 @@ void usage() {
             "    -b        write binary hit records instead of text; `pRIblast-hip txt -i FILE -o TEXT` converts\n"
             "    -t        one summary line per query-target pair: hit count, minimum and summed interaction energy,\n"
             "              the best hit's energies and base-pair ends (-s has no effect; not with -b, nor with WORLD_SIZE > 1)\n"
+            "    -n INT    with -t: only the INT pairs of lowest minimum interaction energy per query, best first\n"
+            "              (ties in -t order; 1 <= INT <= 1024)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
@@ -94,6 +98,8 @@ struct Args {
   prb_ris_opts o;
   bool binary = false;
   bool summary = false; // -t
+  int top = 0;          // -n (0: not given)
+  bool top_given = false;
 };
 
 [[noreturn]] void die(const std::string &msg) {
@@ -112,6 +118,7 @@ struct BatchJob {
   size_t index = 0, nq = 0;
   std::vector<prb_hitset *> pages;
   std::vector<prb_pairset *> pair_pages; // -t: the per-pair summaries instead
+  prb_topset *top = nullptr;             // -t -n: the batch's N best pairs per query instead
   std::vector<std::string> names; // of its queries, in the order of their indices in the hit records
   std::vector<int32_t> qlen_unmasked;
 };
@@ -120,6 +127,7 @@ struct BatchJob {
 struct Prepared {
   prb_qbatch *qb = nullptr;
   std::vector<int32_t> qlen_unmasked;
+  prb_topset *top = nullptr; // -t -n: filled by search_batch, handed to the writer
 };
 
 // ---- binary hit file (little-endian, the layouts of include/priblast_hip.h) ----------------------
@@ -298,6 +306,15 @@ Prepared prepare_batch(prb_ctx *c, const std::vector<std::string> &seqs, const s
 // the search stages of a prepared batch against every page; the hit sets (with -t: the pair sets) go to the writer
 void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector<prb_hitset *> &pages,
                   std::vector<prb_pairset *> &pair_pages) {
+  if (a.top) { // -t -n: every page merged into one table on the device, then one copy
+    if (prb_topset_create(w.ctx, p.qb, a.top, &p.top)) die(prb_last_error());
+    for (int page = 0; page < npages; page++)
+      if (prb_search_page_top(w.ctx, p.qb, w.db, page, &a.o, p.top)) die(prb_last_error());
+    if (prb_topset_finish(w.ctx, p.top)) die(prb_last_error());
+    prb_qbatch_destroy(p.qb);
+    p.qb = nullptr;
+    return;
+  }
   for (int page = 0; page < npages; page++) {
     if (a.summary) {
       prb_pairset *ps = nullptr;
@@ -413,7 +430,7 @@ int ris_main(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:bt")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -429,6 +446,13 @@ int ris_main(int argc, char **argv) {
     case 'p': a.tmp = optarg; break;
     case 'b': a.binary = true; break;
     case 't': a.summary = true; break;
+    case 'n': {
+      char *end = nullptr;
+      const long v = std::strtol(optarg, &end, 10);
+      a.top_given = true;
+      a.top = end != optarg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
+      break;
+    }
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -437,6 +461,8 @@ int ris_main(int argc, char **argv) {
     }
   }
   if (a.summary && a.binary) die("Error: -t (per-pair summary lines) can't be combined with -b (binary hit records)");
+  if (a.top_given && !a.summary) die("Error: -n (the N best pairs per query) needs -t (per-pair summary lines)");
+  if (a.top_given && (a.top < 1 || a.top > 1024)) die("Error: -n needs an integer between 1 and 1024 (this build's limit)");
   std::vector<std::string> names, seqs;
   std::string err = prb::read_fasta(a.in, names, seqs);
   if (!err.empty()) die(err);
@@ -579,6 +605,22 @@ int ris_main(int argc, char **argv) {
         job = std::move(done[b]);
         done.erase(b);
       }
+      if (job.top) {
+        prb::TopView tv;
+        tv.nq = job.nq;
+        tv.names = job.names.data();
+        tv.qlen_unmasked = job.qlen_unmasked.data();
+        tv.r = prb_topset_pairs(job.top);
+        tv.n = prb_topset_size(job.top);
+        if ((id = prb::format_top_batch(tv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
+        prb_topset_free(job.top);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          written = b + 1;
+        }
+        cv.notify_all();
+        continue;
+      }
       if (a.summary) {
         prb::SummaryView sv;
         sv.nq = job.nq;
@@ -670,6 +712,8 @@ int ris_main(int argc, char **argv) {
                job.index = b;
                job.pages = pages;
                job.pair_pages = pair_pages;
+               job.top = p->top;
+               p->top = nullptr;
                job.qlen_unmasked = p->qlen_unmasked;
                names_of(batch_idx(b), job.names);
                job.nq = job.names.size();
