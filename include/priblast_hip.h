@@ -93,7 +93,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "gapped_front_hits": launches = hits it completed), "gapped" (LDS tier 0; "gapped_tier0_hits": launches = hits that entered it),
  * "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow" (wavefront-per-hit kernel), "traceback", "traceback_slow",
  * "summary" (prb_search_page_summary: pair heads, segment starts and the per-pair fold; launches = 3 per sub-batch),
- * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch);
+ * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch),
+ * "profile" (prb_search_page_profile: the merge into the per-position table, launches = 8 per sub-batch; and
+ *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -231,6 +233,49 @@ const prb_top_pair *prb_topset_pairs(const prb_topset *ts);
 void prb_topset_counts(const prb_topset *ts, int64_t counts[3]);
 void prb_topset_free(prb_topset *ts);
 
+/* ---- per-position interaction profile (`ris -q`): a table of every query position on the device ----
+ * For each query of one batch and each of its positions covered by at least one final hit (the hits of
+ * prb_search_page(..., 3, ...) with the same options) of the pages merged in.  The span of a hit is the query positions
+ * q0..qN (inclusive, 0-based) of its first and last base pair in the `-s 0` form (prb_pair_summary's bp_first /
+ * bp_last); the reference sorts a hit's pairs, so q0 <= qN (the few unsorted ones, SURVEY a17, count as
+ * min(q0, qN)..max(q0, qN)).  Per covered position:
+ *   hits      the number of final hits whose span contains it
+ *   targets   the number of distinct database sequences (page, db_id) with such a hit: two hits of one pair count once
+ *   e_min     the smallest e_tot of those hits, compared as doubles (-0.0 == +0.0)
+ *   page, db_id, bp_first / bp_last   the best hit: the FIRST hit with e_min in output order (page ascending, then its
+ *             place in the page's result lines); its pairs as in prb_pair_summary
+ * Every column is a count or a minimum over a total order, so the table does not depend on the order the pages are
+ * merged in nor on how the batch is cut up.
+ *   prb_profset_create       an empty table for qb: one slot per query position plus one per query, about 68 B each in
+ *                            HBM (PRB_ERR_NOMEM when that cannot be allocated)
+ *   prb_search_page_profile  the search of prb_search_page_summary against `page`, its final hits merged into the table
+ *                            on the device.  Argument checks and option limits are those of prb_search_page_summary; the
+ *                            table must have been made with this context and this batch, and holds pages of one
+ *                            database, each merged once.  A call refused by these checks leaves the table as it was; a
+ *                            merge that fails part way leaves it unusable.
+ *   prb_profset_finish       the covered positions selected on the device and copied to the host (one copy); the device
+ *                            table is released.  prb_profset_rows then returns them by query ascending, then by
+ *                            position.  No page can be merged after it (a second call does nothing)
+ *   prb_profset_counts       the stage counts of prb_pairset_counts, summed over the merged pages
+ * The device time of the merge and of the finish is the stage "profile" of prb_ctx_stage_ms. */
+typedef struct prb_profile_pos {
+  int32_t query, pos;          /* index in the batch; 0-based position in the query (masked bases included) */
+  int64_t hits;
+  int32_t targets, page, db_id; /* page and sequence index in the page of the best hit */
+  int32_t reserved;            /* 0 */
+  double e_min;
+  int32_t bp_first[2], bp_last[2]; /* the best hit's (q, db) end pairs; db in the page's reversed text */
+} prb_profile_pos;
+typedef struct prb_profset prb_profset;
+int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out);
+int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                            prb_profset *ps);
+int prb_profset_finish(prb_ctx *ctx, prb_profset *ps);
+int64_t prb_profset_size(const prb_profset *ps);
+const prb_profile_pos *prb_profset_rows(const prb_profset *ps);
+void prb_profset_counts(const prb_profset *ps, int64_t counts[3]);
+void prb_profset_free(prb_profset *ps);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -261,6 +306,13 @@ int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qna
  * rank), one line each in that order, numbered from id0 on; every line is the `-t` line of its pair. */
 int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                         const prb_top_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
+/* The lines of `ris -q` for one batch: rows[0, n) as prb_profset_rows returns them (ascending by query, then by
+ * position), one line each in that order, numbered from id0 on:
+ *   Id,qname,qlen,Position,Hits,Targets,MinEnergy,dbname,dblen,(q0-qN:db0-dbN)
+ * qlen is the result lines' Query Length (the unmasked bases: with repeat masking a position can exceed it), the
+ * energy in the result lines' form, the last three fields those of the best hit's result line in the `-s 0` form. */
+int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_profile_pos *rows, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

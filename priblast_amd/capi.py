@@ -49,6 +49,12 @@ assert PAIR_DTYPE.itemsize == 64
 TOP_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
 assert TOP_DTYPE.itemsize == 72
 
+# prb_profile_pos: one covered query position of the per-position profile (`ris -q`)
+PROFILE_DTYPE = np.dtype([("query", "<i4"), ("pos", "<i4"), ("hits", "<i8"), ("targets", "<i4"), ("page", "<i4"),
+                          ("db_id", "<i4"), ("reserved", "<i4"), ("e_min", "<f8"), ("bp_first", "<i4", (2,)),
+                          ("bp_last", "<i4", (2,))])
+assert PROFILE_DTYPE.itemsize == 56
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -110,6 +116,13 @@ SYMBOLS = {
     "prb_topset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_topset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_topset_free": (None, [ctypes.c_void_p]),
+    "prb_profset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
+    "prb_search_page_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_profset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_profset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_profset_rows": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_profset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_profset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -123,6 +136,8 @@ SYMBOLS = {
                                                c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_top_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                            c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_profile_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                               c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
 }
 
 _lib = None
@@ -450,6 +465,56 @@ def search_top(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
     return (recs, counts) if with_counts else recs
 
 
+class ProfSet:
+    """prb_profset: the per-position profile of one batch, in a table on the device that pages are merged into."""
+
+    def __init__(self, ctx, qb):
+        h = ctypes.c_void_p()
+        _check(lib().prb_profset_create(ctx.h, qb.h, ctypes.byref(h)))
+        self.h, self.ctx, self.qb = h, ctx, qb
+
+    def merge(self, db, page, opts=None):
+        """prb_search_page_profile: searches the batch against `page` and merges its final hits into the table"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_profile(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+
+    def finish(self):
+        """prb_profset_finish -> structured array PROFILE_DTYPE (a copy), by query, then position"""
+        _check(lib().prb_profset_finish(self.ctx.h, self.h))
+        n = lib().prb_profset_size(self.h)
+        if not n:
+            return np.zeros(0, PROFILE_DTYPE)
+        buf = (ctypes.c_char * (n * PROFILE_DTYPE.itemsize)).from_address(lib().prb_profset_rows(self.h))
+        return np.frombuffer(buf, PROFILE_DTYPE).copy()
+
+    def counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_profset_counts(self.h, c)
+        return tuple(c)
+
+    def close(self):
+        if self.h:
+            lib().prb_profset_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_profile(ctx, qb, db, opts=None, pages=None, with_counts=False):
+    """The per-position profile over the pages (all of them, in this order, by default) -> structured array
+    PROFILE_DTYPE, by query, then position.  with_counts: -> (rows, (seed, ungapped, final) counts summed over the pages)."""
+    with ProfSet(ctx, qb) as ps:
+        for p in range(db.npages) if pages is None else pages:
+            ps.merge(db, p, opts)
+        rows = ps.finish()
+        counts = ps.counts()
+    return (rows, counts) if with_counts else rows
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -533,4 +598,16 @@ def write_top_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
     lines, nbytes = c_i64(), c_i64()
     _check(lib().prb_write_top_lines(db.h, len(qnames), names, ql.ctypes.data, recs.ctypes.data if len(recs) else None,
                                      len(recs), id0, fd, ctypes.byref(lines), ctypes.byref(nbytes)))
+    return lines.value, nbytes.value
+
+
+def write_profile_lines(db, qnames, qlen_unmasked, rows, id0=0, fd=-1):
+    """Lines of `ris -q` for one batch: rows as search_profile returns them.  -> (lines, bytes) written to fd
+    (-1: formatted and counted only)."""
+    rows = np.ascontiguousarray(rows, PROFILE_DTYPE)
+    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
+    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
+    lines, nbytes = c_i64(), c_i64()
+    _check(lib().prb_write_profile_lines(db.h, len(qnames), names, ql.ctypes.data, rows.ctypes.data if len(rows) else None,
+                                         len(rows), id0, fd, ctypes.byref(lines), ctypes.byref(nbytes)))
     return lines.value, nbytes.value

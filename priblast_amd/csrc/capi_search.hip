@@ -342,6 +342,53 @@ struct prb_topset {
   }
 };
 
+// prb_profset_create .. prb_profset_free: the per-position table of one batch, merged into sub-batch by sub-batch
+// (search_range), and the sort / scan buffers of those merges
+struct prb_profset {
+  prb_ctx *ctx = nullptr;
+  const prb_qbatch *qb = nullptr;
+  const prb_db *db = nullptr; // of the first merged page
+  int32_t nq = 0;
+  std::vector<int64_t> off;    // [nq + 1] the queries' first slots (ProfTab::off)
+  DevBuf table;                // ProfTab's arrays, one block (view())
+  DevBuf keyA, keyB, valA, valB, span, scan, sortTmp; // per sub-batch: the hits in (pair, first position) order
+  std::vector<uint8_t> merged; // per page of db
+  bool broken = false;         // a merge failed part way
+  bool finished = false;       // prb_profset_finish: the rows are in `rows`, the device memory is released
+  int64_t counts[3] = {0, 0, 0};
+  std::vector<prb_profile_pos> rows; // prb_profset_finish
+  int64_t slots() const { return off.empty() ? 0 : off.back(); }
+  // the block: off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie, db_id,
+  // bp (x4), bad
+  size_t bytes() const { return (off.size() + 5 * (size_t)slots()) * 8 + (7 * (size_t)slots() + 2) * 4; }
+  prb::ProfTab view() const {
+    prb::ProfTab t;
+    const size_t P = (size_t)slots();
+    char *b = table.as<char>();
+    t.off = reinterpret_cast<const int64_t *>(b);
+    b += off.size() * 8;
+    t.hdiff = reinterpret_cast<unsigned long long *>(b);
+    t.key = t.hdiff + P;
+    t.tie = t.key + P;
+    t.skey = t.tie + P;
+    t.e_min = reinterpret_cast<double *>(t.skey + P);
+    t.tdiff = reinterpret_cast<int32_t *>(t.e_min + P);
+    t.stie = reinterpret_cast<uint32_t *>(t.tdiff + P);
+    t.db_id = reinterpret_cast<int32_t *>(t.stie + P);
+    t.bp = t.db_id + P;
+    t.bad = reinterpret_cast<uint32_t *>(t.bp + 4 * P);
+    t.nq = nq;
+    return t;
+  }
+  void release() {
+    for (DevBuf *b : {&table, &keyA, &keyB, &valA, &valB, &span, &scan, &sortTmp}) b->release();
+  }
+  ~prb_profset() { // (also on the error paths of prb_profset_create)
+    if (table.p || keyA.p || sortTmp.p) (void)hipSetDevice(ctx->device);
+    release();
+  }
+};
+
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS).  An explicit count,
 // because launchers such as torchrun export OMP_NUM_THREADS=1: PRB_HOST_THREADS, else
@@ -932,6 +979,11 @@ struct ToI64 {
 };
 struct MaxOp {
   __host__ __device__ int64_t operator()(const int64_t &a, const int64_t &b) const { return a > b ? a : b; }
+};
+// a slot of the profile table that some final hit covers (prb_profset_finish: `hits` holds the scanned counts)
+struct ProfCovered {
+  const int64_t *hits;
+  __host__ __device__ bool operator()(const uint32_t &p) const { return hits[p] > 0; }
 };
 
 // CheckRedundancy on the sorted list `h`; writes the indices of the survivors (ascending) to
@@ -1871,7 +1923,7 @@ static int search_range(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int page, cons
     // results: records packed on the device (with their base-pair ranges), one asynchronous copy
     // each for hits and pairs into a pinned slot; the background thread appends them to the hit set
     const int slot = hs->next_slot;
-    if (!hs->top) { // (a top-N search copies nothing: no staging slot)
+    if (!hs->top && !hs->prof) { // (a top-N or profile search copies nothing: no staging slot)
       hs->next_slot ^= 1;
       hs->drain->acquire(slot);
     }
@@ -1899,6 +1951,35 @@ static int search_range(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int page, cons
       if (npairs == 0 || npairs > NF) {
         set_error("per-pair summary: " + std::to_string(npairs) + " pairs for " + std::to_string(nfin) + " hits");
         return PRB_ERR_STATE;
+      }
+      if (hs->prof) { // per-position profile: the hits merged into the device table; nothing leaves the device
+        prb_profset *ps = hs->prof;
+        if ((rc = ctx->time_end(ctx->summary_timer, 2))) return rc;
+        if ((rc = ctx->time_begin())) return rc;
+        if ((rc = ps->keyA.ensure(NF * 8)) || (rc = ps->keyB.ensure(NF * 8)) || (rc = ps->valA.ensure(NF * 4)) ||
+            (rc = ps->valB.ensure(NF * 4)) || (rc = ps->span.ensure(NF * 8)) || (rc = ps->scan.ensure(NF * 8)))
+          return rc;
+        const prb::ProfTab t = ps->view();
+        const int32_t *ends = w.bpEnds.as<int32_t>();
+        uint64_t *kA = ps->keyA.as<uint64_t>(), *kB = ps->keyB.as<uint64_t>(), *sp = ps->span.as<uint64_t>(), *sc = ps->scan.as<uint64_t>();
+        uint32_t *vA = ps->valA.as<uint32_t>(), *vB = ps->valB.as<uint32_t>();
+        // the hits by (pair, first position of the span): the pair index above bit 32, as many bits as it needs
+        int bits = 32;
+        while (bits < 64 && ((uint64_t)(npairs - 1) >> (bits - 32)) != 0) bits++;
+        size_t tmp_sort = 0, tmp_scan = 0;
+        PRB_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, kA, kB, vA, vB, NF, 0, bits, ctx->stream));
+        PRB_HIP(rocprim::inclusive_scan(nullptr, tmp_scan, sp, sc, NF, rocprim::maximum<uint64_t>(), ctx->stream));
+        if ((rc = ps->sortTmp.ensure(std::max<size_t>({tmp_sort, tmp_scan, 1})))) return rc;
+        PRB_HIP(launch_prof_keys(nfin, w.pairStart.as<uint32_t>(), (int64_t)npairs, ends, kA, vA, ctx->stream));
+        PRB_HIP(rocprim::radix_sort_pairs(ps->sortTmp.p, tmp_sort, kA, kB, vA, vB, NF, 0, bits, ctx->stream));
+        PRB_HIP(launch_prof_span(nfin, kB, vB, ends, sp, ctx->stream));
+        // (pair << 32 | 1 + last position: the running maximum of a pair never looks past the pair's own hits)
+        PRB_HIP(rocprim::inclusive_scan(ps->sortTmp.p, tmp_scan, sp, sc, NF, rocprim::maximum<uint64_t>(), ctx->stream));
+        PRB_HIP(launch_prof_add(F, nfin, kB, vB, sc, ends, t, ctx->stream));
+        PRB_HIP(launch_prof_min(F, nfin, vB, ends, t, ctx->stream));
+        PRB_HIP(launch_prof_merge(F, ends, t, ps->off[(size_t)hs->sub_q0], ps->off[(size_t)hs->sub_q1], page, ctx->stream));
+        hs->hits_total += nfin;
+        return ctx->time_end(ctx->profile_timer, 8);
       }
       const size_t rec_bytes = npairs * sizeof(prb_pair_summary);
       if ((rc = w.packed.ensure(rec_bytes))) return rc;
@@ -2059,7 +2140,7 @@ static int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatc
 }
 
 static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                       bool summary, prb_hitset **out, prb_topset *top = nullptr) {
+                       bool summary, prb_hitset **out, prb_topset *top = nullptr, prb_profset *prof = nullptr) {
   const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
   if (!out) {
     set_error(std::string(fn) + ": bad argument");
@@ -2103,6 +2184,7 @@ static int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, c
   hs->device = ctx->device;
   hs->summary = summary;
   hs->top = top;
+  hs->prof = prof;
   hs->on_device = ctx->keep_device_records && last_stage == 3 && !summary;
   hs->d_hits.hint = ctx->keep_hint_hits;
   hs->d_bp.hint = ctx->keep_hint_bp;
@@ -2427,6 +2509,154 @@ void prb_topset_free(prb_topset *ts) {
   delete ts;
 }
 
+int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
+  if (!ctx || !qb || !out) {
+    set_error("prb_profset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  std::unique_ptr<prb_profset> ps(new (std::nothrow) prb_profset());
+  if (!ps) {
+    set_error("prb_profset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  ps->ctx = ctx;
+  ps->qb = qb;
+  ps->nq = qb->nq;
+  ps->off.assign((size_t)qb->nq + 1, 0);
+  for (int32_t q = 0; q < qb->nq; q++) ps->off[(size_t)q + 1] = ps->off[(size_t)q] + qb->len[(size_t)q] + 1;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t P = (size_t)ps->slots();
+  if (ps->table.ensure(ps->bytes()) != PRB_OK) {
+    set_error("prb_profset_create: can't allocate the per-position table (" + std::to_string(ps->bytes() >> 20) + " MB of HBM for " +
+              std::to_string(P) + " query positions)");
+    return PRB_ERR_NOMEM;
+  }
+  const prb::ProfTab t = ps->view();
+  PRB_HIP(hipMemsetAsync(ps->table.p, 0, ps->bytes(), ctx->stream));
+  PRB_HIP(hipMemsetAsync(t.key, 0xFF, 3 * P * 8, ctx->stream)); // key, tie, skey: none yet
+  PRB_HIP(hipMemsetAsync(t.stie, 0xFF, P * 4, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(ps->table.p, ps->off.data(), ps->off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ps.release();
+  return PRB_OK;
+}
+
+int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_profset *ps) {
+  if (!ps) {
+    set_error("prb_search_page_profile: bad argument");
+    return PRB_ERR_ARG;
+  }
+  // (every check before the table is touched: a refused call leaves it as it was)
+  if (int rc = check_search_args("prb_search_page_profile", ctx, qb, db, page, opts, 3)) return rc;
+  if (ps->ctx != ctx || ps->qb != qb || ps->nq != qb->nq) {
+    set_error("prb_search_page_profile: the profile table was made for another context or query batch (" + std::to_string(ps->nq) +
+              " queries; this batch has " + std::to_string(qb->nq) + ")");
+    return PRB_ERR_ARG;
+  }
+  if (ps->db && ps->db != db) {
+    set_error("prb_search_page_profile: the profile table holds pages of another database");
+    return PRB_ERR_ARG;
+  }
+  if (ps->broken) {
+    set_error("prb_search_page_profile: an earlier merge into this profile table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ps->finished) {
+    set_error("prb_search_page_profile: the profile table is finished (prb_profset_finish)");
+    return PRB_ERR_STATE;
+  }
+  if (!ps->db) {
+    ps->db = db;
+    ps->merged.assign(db->pages.size(), 0);
+  }
+  if (ps->merged[(size_t)page]) {
+    set_error("prb_search_page_profile: page " + std::to_string(page) + " is already merged into this profile table");
+    return PRB_ERR_ARG;
+  }
+  ps->merged[(size_t)page] = 1;
+  prb_hitset *hs = nullptr;
+  const int rc = search_page(ctx, qb, db, page, opts, 3, true, &hs, nullptr, ps);
+  if (rc != PRB_OK) {
+    ps->broken = true;
+    return rc;
+  }
+  for (int i = 0; i < 3; i++) ps->counts[i] += hs->counts[i];
+  delete hs;
+  return PRB_OK;
+}
+
+// the covered positions selected on the device (Hits > 0 after the scans), their rows built there and copied once
+int prb_profset_finish(prb_ctx *ctx, prb_profset *ps) {
+  if (!ctx || !ps || ps->ctx != ctx) {
+    set_error("prb_profset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (ps->broken) {
+    set_error("prb_profset_finish: an earlier merge into this profile table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ps->finished) return PRB_OK; // (the rows are on the host already)
+  const size_t P = (size_t)ps->slots();
+  ps->rows.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (P > 0) {
+    int rc;
+    if ((rc = ctx->time_begin())) return rc;
+    const prb::ProfTab t = ps->view();
+    // counts: hits into skey's slots, targets into stie's (the scratch is free once every page is merged)
+    int64_t *hits = reinterpret_cast<int64_t *>(t.skey);
+    int32_t *targets = reinterpret_cast<int32_t *>(t.stie);
+    if ((rc = ps->valA.ensure(P * 4)) || (rc = ps->keyA.ensure(16))) return rc;
+    size_t tmp_h = 0, tmp_t = 0, tmp_s = 0;
+    const ProfCovered covered{hits};
+    rocprim::counting_iterator<uint32_t> iota(0);
+    PRB_HIP(rocprim::inclusive_scan(nullptr, tmp_h, reinterpret_cast<const int64_t *>(t.hdiff), hits, P, rocprim::plus<int64_t>(),
+                                    ctx->stream));
+    PRB_HIP(rocprim::inclusive_scan(nullptr, tmp_t, t.tdiff, targets, P, rocprim::plus<int32_t>(), ctx->stream));
+    PRB_HIP(rocprim::select(nullptr, tmp_s, iota, ps->valA.as<uint32_t>(), ps->keyA.as<size_t>(), P, covered, ctx->stream));
+    if ((rc = ps->sortTmp.ensure(std::max<size_t>({tmp_h, tmp_t, tmp_s, 1})))) return rc;
+    PRB_HIP(rocprim::inclusive_scan(ps->sortTmp.p, tmp_h, reinterpret_cast<const int64_t *>(t.hdiff), hits, P, rocprim::plus<int64_t>(),
+                                    ctx->stream));
+    PRB_HIP(rocprim::inclusive_scan(ps->sortTmp.p, tmp_t, t.tdiff, targets, P, rocprim::plus<int32_t>(), ctx->stream));
+    PRB_HIP(rocprim::select(ps->sortTmp.p, tmp_s, iota, ps->valA.as<uint32_t>(), ps->keyA.as<size_t>(), P, covered, ctx->stream));
+    size_t nsel = 0;
+    uint32_t bad = 0;
+    PRB_HIP(hipMemcpyAsync(&nsel, ps->keyA.p, sizeof nsel, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipMemcpyAsync(&bad, t.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad || nsel > P) {
+      set_error("prb_profset_finish: " + std::string(bad ? "a final hit's span lies outside its query" : "bad row count"));
+      return PRB_ERR_STATE;
+    }
+    if (nsel) {
+      try {
+        ps->rows.resize(nsel);
+      } catch (const std::exception &e) {
+        set_error(std::string("prb_profset_finish: ") + e.what());
+        return PRB_ERR_NOMEM;
+      }
+      if ((rc = ps->span.ensure(nsel * sizeof(prb_profile_pos)))) return rc;
+      PRB_HIP(launch_prof_rows(t, ps->valA.as<uint32_t>(), (int64_t)nsel, hits, targets, ps->span.p, ctx->stream));
+      PRB_HIP(hipMemcpyAsync(ps->rows.data(), ps->span.p, nsel * sizeof(prb_profile_pos), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = ctx->time_end(ctx->profile_timer, nsel ? 4 : 3))) return rc;
+  }
+  ps->finished = true;
+  ps->release(); // (only the host rows are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_profset_size(const prb_profset *ps) { return ps ? (int64_t)ps->rows.size() : -1; }
+const prb_profile_pos *prb_profset_rows(const prb_profset *ps) { return ps ? ps->rows.data() : nullptr; }
+void prb_profset_counts(const prb_profset *ps, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ps ? ps->counts[i] : 0;
+}
+void prb_profset_free(prb_profset *ps) {
+  delete ps;
+}
+
 int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }
 const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps) { return ps ? ps->pairs.data() : nullptr; }
 void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]) {
@@ -2528,6 +2758,46 @@ int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames,
     }
   } catch (const std::exception &e) {
     set_error(std::string("prb_write_top_lines: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  return PRB_OK;
+}
+
+int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_profile_pos *rows, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  if (!db || nq < 0 || (nq && (!qnames || !qlen_unmasked)) || n < 0 || (n && !rows)) {
+    set_error("prb_write_profile_lines: bad argument");
+    return PRB_ERR_ARG;
+  }
+  try {
+    ProfileView v;
+    std::vector<std::string> names((size_t)nq);
+    for (int32_t q = 0; q < nq; q++) names[q] = qnames[q];
+    v.nq = (size_t)nq;
+    v.names = names.data();
+    v.qlen_unmasked = qlen_unmasked;
+    for (int64_t i = 0; i < n; i++) {
+      const prb_profile_pos &x = rows[i];
+      if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.query < 0 || x.query >= nq || x.db_id < 0 ||
+          x.db_id >= db->pages[(size_t)x.page].nseq || x.hits < 1 || x.targets < 1 || x.pos < 0 ||
+          (i && (x.query < rows[i - 1].query || (x.query == rows[i - 1].query && x.pos <= rows[i - 1].pos)))) {
+        set_error("prb_write_profile_lines: row " + std::to_string(i) + " is inconsistent");
+        return PRB_ERR_ARG;
+      }
+    }
+    v.r = rows;
+    v.n = n;
+    LineSink sink;
+    sink.fd = fd;
+    const int64_t next = format_profile_batch(v, db->tabs, id0, sink, format_threads());
+    if (lines) *lines = sink.lines;
+    if (bytes) *bytes = sink.bytes;
+    if (next < 0) {
+      set_error("prb_write_profile_lines: write failed");
+      return PRB_ERR_IO;
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_write_profile_lines: ") + e.what());
     return PRB_ERR_NOMEM;
   }
   return PRB_OK;

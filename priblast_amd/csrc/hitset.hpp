@@ -112,6 +112,8 @@ struct prb_hitset {
   // prb_search_page_top: the records are merged into this table on the device instead (queries [sub_q0, sub_q1) are
   // the sub-batch being searched)
   prb_topset *top = nullptr;
+  // prb_search_page_profile: the final hits are merged into this per-position table on the device instead
+  prb_profset *prof = nullptr;
   int32_t sub_q0 = 0, sub_q1 = 0;
 };
 

@@ -145,6 +145,43 @@ constexpr int kTopMaxN = 1024; // the largest N: the set's keys and a candidate 
 // fill = int32_t[nq] (slots in use per query).  One workgroup per query; the page must not be in the table yet.
 hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
                             hipStream_t s);
+// ---- per-position profile (prb_search_page_profile) ----
+// The table of one batch in HBM.  Query q owns the slots [off[q], off[q + 1]) = its len + 1 positions (the last one
+// takes the -1 of a span that ends at the query's last base), so the difference arrays of all queries are one array
+// whose every query segment sums to zero.  Best-hit keys: key = energy key of e_tot, tie = page << 32 | the hit's place
+// in the page's final list; ~0 = none yet.  skey / stie: the (energy key, place) minima of the sub-batch being merged,
+// ~0 between sub-batches.  bad: set when a hit's span lies outside its query (never for a consistent search).
+struct ProfTab {
+  const int64_t *off;           // [nq + 1]
+  unsigned long long *hdiff;    // [P] hits: +1 at a span's first position, -1 behind its last (two's complement)
+  unsigned long long *key, *tie; // [P] the best hit so far
+  unsigned long long *skey;     // [P] sub-batch scratch
+  double *e_min;                // [P] the best hit's e_tot
+  int32_t *tdiff;               // [P] targets: the same over the union of each pair's spans
+  uint32_t *stie;               // [P] sub-batch scratch
+  int32_t *db_id;               // [P] the best hit's sequence
+  int32_t *bp;                  // [4 P] the best hit's first and last base pair (q, db, q, db)
+  uint32_t *bad;
+  int32_t nq;
+};
+// key[i] = pair << 32 | first query position of final hit i's span, val[i] = i (start = the pairs' first hits, as
+// launch_pair_fold takes them; ends = launch_bp_ends)
+hipError_t launch_prof_keys(int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, uint64_t *key, uint32_t *val,
+                            hipStream_t s);
+// v[i] = (key[i] with its position bits cleared) | (last position of hit val[i]'s span + 1): what the max-scan takes
+hipError_t launch_prof_span(int64_t n, const uint64_t *key, const uint32_t *val, const int32_t *ends, uint64_t *v, hipStream_t s);
+// the difference arrays: every hit's span into hdiff, and the part of it that no earlier hit of its pair (in key order)
+// covers into tdiff; m = the inclusive max-scan of launch_prof_span's v
+hipError_t launch_prof_add(const HitSoA &h, int64_t n, const uint64_t *key, const uint32_t *val, const uint64_t *m, const int32_t *ends,
+                           const ProfTab &t, hipStream_t s);
+// the sub-batch's minima: skey = smallest energy key over the covering hits, then stie = the first covering hit with it
+hipError_t launch_prof_min(const HitSoA &h, int64_t n, const uint32_t *val, const int32_t *ends, const ProfTab &t, hipStream_t s);
+// slots [p0, p1): the sub-batch's minima merged into the best hits (page `page`), the scratch reset
+hipError_t launch_prof_merge(const HitSoA &h, const int32_t *ends, const ProfTab &t, int64_t p0, int64_t p1, int32_t page,
+                             hipStream_t s);
+// rows[j] (prb_profile_pos) of the covered slot idx[j]; hits / targets = the scanned difference arrays
+hipError_t launch_prof_rows(const ProfTab &t, const uint32_t *idx, int64_t n, const int64_t *hits, const int32_t *targets, void *rows,
+                            hipStream_t s);
 hipError_t launch_gather_u8(const uint8_t *src, const uint32_t *idx, uint8_t *dst, int64_t n, hipStream_t s);
 hipError_t launch_iota_u32(uint32_t *dst, int64_t n, hipStream_t s); // dst[i] = i
 // flags[i] = marks[list[i]] & mask != 0

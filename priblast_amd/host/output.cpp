@@ -201,6 +201,41 @@ void format_top_piece(const Piece &pc, const TopView &v, const std::vector<SeqTa
     put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[v.r[i].page], v.r[i].s);
 }
 
+void format_profile_piece(const Piece &pc, const ProfileView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  const std::string &qname = v.names[pc.q];
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_profile_pos &x = v.r[i];
+    const SeqTable &tab = tabs[x.page];
+    const std::string &dname = tab.names[x.db_id];
+    char *p = b.room(qname.size() + dname.size() + 240);
+    char *const p0 = p;
+    p = put_int(p, id++);
+    *p++ = ',';
+    std::memcpy(p, qname.data(), qname.size());
+    p += qname.size();
+    *p++ = ',';
+    p = put_int(p, v.qlen_unmasked[pc.q]);
+    *p++ = ',';
+    p = put_int(p, x.pos);
+    *p++ = ',';
+    p = put_int(p, x.hits);
+    *p++ = ',';
+    p = put_int(p, x.targets);
+    *p++ = ',';
+    p = put_g(p, x.e_min);
+    *p++ = ',';
+    std::memcpy(p, dname.data(), dname.size());
+    p += dname.size();
+    *p++ = ',';
+    p = put_int(p, tab.len_unmasked[x.db_id]);
+    *p++ = ',';
+    p = put_ends(p, tab, x.db_id, x.bp_first, x.bp_last);
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
 } // namespace
 
 int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
@@ -214,6 +249,13 @@ int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &
   return format_records(
       v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].r[i].query; },
       [&](const Piece &pc, Buf &b) { format_summary_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_profile_batch(const ProfileView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page": the rows are in output order already, and each carries its best hit's page)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].query; },
+      [&](const Piece &pc, Buf &b) { format_profile_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

@@ -72,6 +72,19 @@ struct TopView {
 };
 int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -q` (prb_profset_rows), one per covered query position, in the rows' order (ascending by query, then by
+// position), numbered from id0 on:
+//   Id,qname,qlen,Position,Hits,Targets,MinE,dbname,dblen,(q0-qN:db0-dbN)
+// the energy and the best hit's base-pair field formatted as in the result lines (-s 0 form).
+struct ProfileView {
+  size_t nq = 0;
+  const std::string *names = nullptr; // [nq]
+  const int32_t *qlen_unmasked = nullptr;
+  const prb_profile_pos *r = nullptr;
+  int64_t n = 0;
+};
+int64_t format_profile_batch(const ProfileView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 int format_threads(); // PRB_HOST_THREADS, else min(32, hardware threads)
 
 } // namespace prb

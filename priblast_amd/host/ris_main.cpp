@@ -22,7 +22,10 @@
 // reduced on the GPU (prb_search_page_summary) and never leave it.  `-t` is refused with `-b` and in
 // rank mode (WORLD_SIZE > 1): the gather carries hit records only.  `-t -n N` keeps each query's N
 // pairs of lowest minimum energy: a table on the GPU (prb_search_page_top) takes every page of a
-// batch, and only its N records per query reach the host.
+// batch, and only its N records per query reach the host.  `ris -q` writes one line per query position
+// that a final hit covers (hits, distinct targets, minimum energy and its first hit): a per-position
+// table on the GPU (prb_search_page_profile) takes every page of a batch, and only its covered rows
+// reach the host.  `-q` is refused with -t, -n, -b and in rank mode, as -t is.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -88,6 +91,9 @@ void usage() {
             "              the best hit's energies and base-pair ends (-s has no effect; not with -b, nor with WORLD_SIZE > 1)\n"
             "    -n INT    with -t: only the INT pairs of lowest minimum interaction energy per query, best first\n"
             "              (ties in -t order; 1 <= INT <= 1024)\n"
+            "    -q        one line per query position covered by a final hit: hits and distinct targets covering it,\n"
+            "              their minimum interaction energy and its first hit (-s has no effect; not with -t, -n, -b,\n"
+            "              nor with WORLD_SIZE > 1)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
@@ -100,6 +106,7 @@ struct Args {
   bool summary = false; // -t
   int top = 0;          // -n (0: not given)
   bool top_given = false;
+  bool profile = false; // -q
 };
 
 [[noreturn]] void die(const std::string &msg) {
@@ -119,6 +126,7 @@ struct BatchJob {
   std::vector<prb_hitset *> pages;
   std::vector<prb_pairset *> pair_pages; // -t: the per-pair summaries instead
   prb_topset *top = nullptr;             // -t -n: the batch's N best pairs per query instead
+  prb_profset *prof = nullptr;           // -q: the batch's per-position profile instead
   std::vector<std::string> names; // of its queries, in the order of their indices in the hit records
   std::vector<int32_t> qlen_unmasked;
 };
@@ -128,6 +136,7 @@ struct Prepared {
   prb_qbatch *qb = nullptr;
   std::vector<int32_t> qlen_unmasked;
   prb_topset *top = nullptr; // -t -n: filled by search_batch, handed to the writer
+  prb_profset *prof = nullptr; // -q: likewise
 };
 
 // ---- binary hit file (little-endian, the layouts of include/priblast_hip.h) ----------------------
@@ -315,6 +324,15 @@ void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector
     p.qb = nullptr;
     return;
   }
+  if (a.profile) { // -q: every page merged into one per-position table on the device, then one copy of the covered rows
+    if (prb_profset_create(w.ctx, p.qb, &p.prof)) die(prb_last_error());
+    for (int page = 0; page < npages; page++)
+      if (prb_search_page_profile(w.ctx, p.qb, w.db, page, &a.o, p.prof)) die(prb_last_error());
+    if (prb_profset_finish(w.ctx, p.prof)) die(prb_last_error());
+    prb_qbatch_destroy(p.qb);
+    p.qb = nullptr;
+    return;
+  }
   for (int page = 0; page < npages; page++) {
     if (a.summary) {
       prb_pairset *ps = nullptr;
@@ -430,7 +448,7 @@ int ris_main(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:q")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -446,6 +464,7 @@ int ris_main(int argc, char **argv) {
     case 'p': a.tmp = optarg; break;
     case 'b': a.binary = true; break;
     case 't': a.summary = true; break;
+    case 'q': a.profile = true; break;
     case 'n': {
       char *end = nullptr;
       const long v = std::strtol(optarg, &end, 10);
@@ -460,6 +479,9 @@ int ris_main(int argc, char **argv) {
     default: die("Error: invalid argument");
     }
   }
+  if (a.profile && a.summary) die("Error: -q (per-position profile lines) can't be combined with -t (per-pair summary lines)");
+  if (a.profile && a.top_given) die("Error: -q (per-position profile lines) can't be combined with -n (the N best pairs per query)");
+  if (a.profile && a.binary) die("Error: -q (per-position profile lines) can't be combined with -b (binary hit records)");
   if (a.summary && a.binary) die("Error: -t (per-pair summary lines) can't be combined with -b (binary hit records)");
   if (a.top_given && !a.summary) die("Error: -n (the N best pairs per query) needs -t (per-pair summary lines)");
   if (a.top_given && (a.top < 1 || a.top > 1024)) die("Error: -n needs an integer between 1 and 1024 (this build's limit)");
@@ -485,6 +507,8 @@ int ris_main(int argc, char **argv) {
   const int rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
   const bool rank_mode = world > 1 || std::getenv("PRB_FORCE_COMM") != nullptr;
   if (rank < 0 || rank >= world) die("Error: RANK outside WORLD_SIZE");
+  if (rank_mode && a.profile)
+    die("Error: -q (per-position profile lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
   if (rank_mode && a.summary)
     die("Error: -t (per-pair summary lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
   if (rank_mode) {
@@ -562,7 +586,9 @@ int ris_main(int argc, char **argv) {
                   a.o.final_threshold, a.o.drop_out_wo_gap, a.o.drop_out_w_gap);
     header += buf;
   }
-  if (a.summary)
+  if (a.profile)
+    header += "Id,Query name,Query Length,Position,Hits,Targets,Minimum Interaction Energy,Target name,Target Length,BasePair\n";
+  else if (a.summary)
     header += "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
               "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
   else
@@ -604,6 +630,22 @@ int ris_main(int argc, char **argv) {
         cv.wait(lk, [&] { return done.count(b) != 0; });
         job = std::move(done[b]);
         done.erase(b);
+      }
+      if (job.prof) {
+        prb::ProfileView pv;
+        pv.nq = job.nq;
+        pv.names = job.names.data();
+        pv.qlen_unmasked = job.qlen_unmasked.data();
+        pv.r = prb_profset_rows(job.prof);
+        pv.n = prb_profset_size(job.prof);
+        if ((id = prb::format_profile_batch(pv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
+        prb_profset_free(job.prof);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          written = b + 1;
+        }
+        cv.notify_all();
+        continue;
       }
       if (job.top) {
         prb::TopView tv;
@@ -714,6 +756,8 @@ int ris_main(int argc, char **argv) {
                job.pair_pages = pair_pages;
                job.top = p->top;
                p->top = nullptr;
+               job.prof = p->prof;
+               p->prof = nullptr;
                job.qlen_unmasked = p->qlen_unmasked;
                names_of(batch_idx(b), job.names);
                job.nq = job.names.size();
