@@ -100,7 +100,7 @@ void prb_ris_opts_default(prb_ris_opts *o) {
   o->output_style = 0;
 }
 
-int prb_search_const_upload(prb_ctx *ctx); // capi_search.hip
+int prb_search_const_upload(prb_ctx *ctx); // capi_pages.hip
 void prb_search_const_free(prb_ctx *ctx);
 
 } // extern "C" (reopened below)

@@ -1,0 +1,136 @@
+// C ABI, part 5: result lines from records (prb_write_*_lines).  The records may come from another process - a
+// gathered hit set, a file read back - so every one is checked before anything is indexed with it.
+#include <string>
+#include <vector>
+
+#include "search_host.hpp"
+
+using namespace prb;
+
+namespace {
+// The body the four writers share.  `View` is the formatter's view of a batch (output.hpp); `kind_ok` = the checks of
+// the arguments only this kind has; `fill(v)` checks the records and puts them into the view (it sets the error text
+// and returns the code when one is inconsistent); `format(v, sink)` is the formatter's call, returning the next id or -1.
+template <class View, class Fill, class Format>
+int write_lines(const char *fn, bool kind_ok, const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                int64_t *lines, int64_t *bytes, int fd, Fill &&fill, Format &&format) {
+  if (!kind_ok || !db || nq < 0 || (nq && (!qnames || !qlen_unmasked))) {
+    set_error(std::string(fn) + ": bad argument");
+    return PRB_ERR_ARG;
+  }
+  try {
+    View v;
+    std::vector<std::string> names((size_t)nq);
+    for (int32_t q = 0; q < nq; q++) names[q] = qnames[q];
+    v.nq = (size_t)nq;
+    v.names = names.data();
+    v.qlen_unmasked = qlen_unmasked;
+    if (int rc = fill(v)) return rc;
+    LineSink sink;
+    sink.fd = fd;
+    const int64_t next = format(v, sink);
+    if (lines) *lines = sink.lines;
+    if (bytes) *bytes = sink.bytes;
+    if (next < 0) {
+      set_error(std::string(fn) + ": write failed");
+      return PRB_ERR_IO;
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string(fn) + ": " + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  return PRB_OK;
+}
+int bad_record(const std::string &msg) {
+  set_error(msg);
+  return PRB_ERR_ARG;
+}
+} // namespace
+
+extern "C" {
+
+int prb_write_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                    const prb_page_hits *pages, int32_t npages, int32_t output_style, int64_t id0, int fd, int64_t *lines,
+                    int64_t *bytes) {
+  const bool ok = db && pages && npages == (int32_t)db->pages.size() && output_style >= 0 && output_style <= 1;
+  return write_lines<BatchView>(
+      "prb_write_lines", ok, db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](BatchView &v) {
+        for (int32_t p = 0; p < npages; p++) {
+          const prb_page_hits &ph = pages[p];
+          if (ph.nhits < 0 || ph.npairs < 0 || (ph.nhits && !ph.hits)) return bad_record("prb_write_lines: bad page");
+          const int32_t nseq = db->pages[p].nseq;
+          for (int64_t i = 0; i < ph.nhits; i++) {
+            const prb_hit &x = ph.hits[i];
+            if (x.query < 0 || x.query >= nq || x.db_id < 0 || x.db_id >= nseq || x.bp_count < 0 || x.bp_offset < 0 ||
+                x.bp_offset + x.bp_count > ph.npairs || (i && x.query < ph.hits[i - 1].query))
+              return bad_record("prb_write_lines: hit record " + std::to_string(i) + " of page " + std::to_string(p) + " is inconsistent");
+          }
+          v.pages.push_back(PageHits{ph.hits, ph.nhits, ph.basepairs, ph.npairs});
+        }
+        return (int)PRB_OK;
+      },
+      [&](const BatchView &v, LineSink &sink) { return format_batch(v, db->tabs, output_style, id0, sink, format_threads()); });
+}
+
+int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_page_pairs *pages, int32_t npages, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  const bool ok = db && pages && npages == (int32_t)db->pages.size();
+  return write_lines<SummaryView>(
+      "prb_write_summary_lines", ok, db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](SummaryView &v) {
+        for (int32_t p = 0; p < npages; p++) {
+          const prb_page_pairs &pp = pages[p];
+          if (pp.npairs < 0 || (pp.npairs && !pp.pairs)) return bad_record("prb_write_summary_lines: bad page");
+          const int32_t nseq = db->pages[p].nseq;
+          for (int64_t i = 0; i < pp.npairs; i++) {
+            const prb_pair_summary &x = pp.pairs[i];
+            if (x.query < 0 || x.query >= nq || x.db_id < 0 || x.db_id >= nseq || x.hits < 1 || (i && x.query < pp.pairs[i - 1].query))
+              return bad_record("prb_write_summary_lines: pair record " + std::to_string(i) + " of page " + std::to_string(p) +
+                                " is inconsistent");
+          }
+          v.pages.push_back(PagePairs{pp.pairs, pp.npairs});
+        }
+        return (int)PRB_OK;
+      },
+      [&](const SummaryView &v, LineSink &sink) { return format_summary_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
+int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                        const prb_top_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<TopView>(
+      "prb_write_top_lines", n >= 0 && (!n || pairs), db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](TopView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_top_pair &x = pairs[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || (i && x.s.query < pairs[i - 1].s.query))
+            return bad_record("prb_write_top_lines: pair record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = pairs;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const TopView &v, LineSink &sink) { return format_top_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
+int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_profile_pos *rows, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<ProfileView>(
+      "prb_write_profile_lines", n >= 0 && (!n || rows), db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](ProfileView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_profile_pos &x = rows[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.query < 0 || x.query >= nq || x.db_id < 0 ||
+              x.db_id >= db->pages[(size_t)x.page].nseq || x.hits < 1 || x.targets < 1 || x.pos < 0 ||
+              (i && (x.query < rows[i - 1].query || (x.query == rows[i - 1].query && x.pos <= rows[i - 1].pos))))
+            return bad_record("prb_write_profile_lines: row " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = rows;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const ProfileView &v, LineSink &sink) { return format_profile_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
+} // extern "C"

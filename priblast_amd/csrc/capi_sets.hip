@@ -1,0 +1,285 @@
+// C ABI, part 4: the tables and record sets a search fills - the top-N table (prb_topset_*), the per-position
+// profile (prb_profset_*), per-pair records (prb_pairset_*), hit sets (prb_hitset_*).
+#include <algorithm>
+#include <cstring>
+
+#include "search_host.hpp"
+
+using namespace prb;
+
+namespace {
+// a slot of the profile table that some final hit covers (prb_profset_finish: `hits` holds the scanned counts)
+struct ProfCovered {
+  const int64_t *hits;
+  __host__ __device__ bool operator()(const uint32_t &p) const { return hits[p] > 0; }
+};
+} // namespace
+
+// prb_search_page_top / prb_search_page_profile: page `page` searched and merged into the table `t` - `what` in the
+// messages, finished by `finish_fn`.  Every check comes before the table is touched: a refused call leaves it as it was.
+static int merge_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, MergeTable *t, prb_ctx *ctx,
+                      prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts) {
+  const std::string fn = fn_name, table = std::string(what) + " table";
+  if (!t) {
+    set_error(fn + ": bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
+  if (t->ctx != ctx || t->qb != qb || t->nq != qb->nq) {
+    set_error(fn + ": the " + table + " was made for another context or query batch (" + std::to_string(t->nq) +
+              " queries; this batch has " + std::to_string(qb->nq) + ")");
+    return PRB_ERR_ARG;
+  }
+  if (t->db && t->db != db) {
+    set_error(fn + ": the " + table + " holds pages of another database");
+    return PRB_ERR_ARG;
+  }
+  if (t->broken) {
+    set_error(fn + ": an earlier merge into this " + table + " failed");
+    return PRB_ERR_STATE;
+  }
+  if (t->finished) {
+    set_error(fn + ": the " + table + " is finished (" + finish_fn + ")");
+    return PRB_ERR_STATE;
+  }
+  if (!t->db) {
+    t->db = db;
+    t->merged.assign(db->pages.size(), 0);
+  }
+  if (t->merged[(size_t)page]) {
+    set_error(fn + ": page " + std::to_string(page) + " is already merged into this " + table);
+    return PRB_ERR_ARG;
+  }
+  t->merged[(size_t)page] = 1;
+  prb_hitset *hs = nullptr;
+  const int rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t);
+  if (rc != PRB_OK) {
+    t->broken = true;
+    return rc;
+  }
+  for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
+  delete hs;
+  return PRB_OK;
+}
+
+extern "C" {
+
+int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out) {
+  if (!ctx || !qb || !out) {
+    set_error("prb_topset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  if (n < 1 || n > kTopMaxN) {
+    set_error("prb_topset_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+    return PRB_ERR_ARG;
+  }
+  std::unique_ptr<prb_topset> ts(new (std::nothrow) prb_topset());
+  if (!ts) {
+    set_error("prb_topset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  ts->ctx = ctx;
+  ts->qb = qb;
+  ts->nq = qb->nq;
+  ts->n = n;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = ts->slots_bytes() + (size_t)qb->nq * sizeof(int32_t);
+  if (int rc = ts->table.ensure(std::max<size_t>(bytes, 1))) return rc;
+  PRB_HIP(hipMemsetAsync(ts->table.p, 0, std::max<size_t>(bytes, 1), ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ts.release();
+  return PRB_OK;
+}
+
+int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_topset *ts) {
+  return merge_page("prb_search_page_top", "top-N", "prb_topset_finish", SearchMode::kTop, ts, ctx, qb, db, page, opts);
+}
+
+int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
+  if (!ctx || !ts || ts->ctx != ctx) {
+    set_error("prb_topset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (ts->broken) {
+    set_error("prb_topset_finish: an earlier merge into this top-N table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ts->finished) return PRB_OK; // (the records are on the host already)
+  try {
+    std::vector<int32_t> fill((size_t)ts->nq);
+    // (slots and fill counts are one block: one copy)
+    std::vector<char> host(ts->slots_bytes() + fill.size() * sizeof(int32_t));
+    PRB_HIP(hipSetDevice(ctx->device));
+    if (!host.empty()) {
+      PRB_HIP(hipMemcpyAsync(host.data(), ts->table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    std::memcpy(fill.data(), host.data() + ts->slots_bytes(), fill.size() * sizeof(int32_t));
+    ts->pairs.clear();
+    for (int32_t q = 0; q < ts->nq; q++) {
+      if (fill[q] < 0 || fill[q] > ts->n) {
+        set_error("prb_topset_finish: query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
+        return PRB_ERR_STATE;
+      }
+      for (int32_t r = 0; r < fill[q]; r++) {
+        prb_top_pair p;
+        std::memcpy(&p, host.data() + ((size_t)q * ts->n + r) * sizeof(prb_top_pair), sizeof p);
+        p.rank = r;
+        ts->pairs.push_back(p);
+      }
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_topset_finish: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  ts->finished = true;
+  ts->table.release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_topset_size(const prb_topset *ts) { return ts ? (int64_t)ts->pairs.size() : -1; }
+const prb_top_pair *prb_topset_pairs(const prb_topset *ts) { return ts ? ts->pairs.data() : nullptr; }
+void prb_topset_counts(const prb_topset *ts, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ts ? ts->counts[i] : 0;
+}
+void prb_topset_free(prb_topset *ts) {
+  delete ts;
+}
+
+int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
+  if (!ctx || !qb || !out) {
+    set_error("prb_profset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  std::unique_ptr<prb_profset> ps(new (std::nothrow) prb_profset());
+  if (!ps) {
+    set_error("prb_profset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  ps->ctx = ctx;
+  ps->qb = qb;
+  ps->nq = qb->nq;
+  ps->off.assign((size_t)qb->nq + 1, 0);
+  for (int32_t q = 0; q < qb->nq; q++) ps->off[(size_t)q + 1] = ps->off[(size_t)q] + qb->len[(size_t)q] + 1;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t P = (size_t)ps->slots();
+  if (ps->table.ensure(ps->bytes()) != PRB_OK) {
+    set_error("prb_profset_create: can't allocate the per-position table (" + std::to_string(ps->bytes() >> 20) + " MB of HBM for " +
+              std::to_string(P) + " query positions)");
+    return PRB_ERR_NOMEM;
+  }
+  const prb::ProfTab t = ps->view();
+  PRB_HIP(hipMemsetAsync(ps->table.p, 0, ps->bytes(), ctx->stream));
+  PRB_HIP(hipMemsetAsync(t.key, 0xFF, 3 * P * 8, ctx->stream)); // key, tie, skey: none yet
+  PRB_HIP(hipMemsetAsync(t.stie, 0xFF, P * 4, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(ps->table.p, ps->off.data(), ps->off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ps.release();
+  return PRB_OK;
+}
+
+int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_profset *ps) {
+  return merge_page("prb_search_page_profile", "profile", "prb_profset_finish", SearchMode::kProfile, ps, ctx, qb, db, page, opts);
+}
+
+// the covered positions selected on the device (Hits > 0 after the scans), their rows built there and copied once
+int prb_profset_finish(prb_ctx *ctx, prb_profset *ps) {
+  if (!ctx || !ps || ps->ctx != ctx) {
+    set_error("prb_profset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (ps->broken) {
+    set_error("prb_profset_finish: an earlier merge into this profile table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ps->finished) return PRB_OK; // (the rows are on the host already)
+  const size_t P = (size_t)ps->slots();
+  ps->rows.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (P > 0) {
+    int rc;
+    if ((rc = ctx->time_begin())) return rc;
+    const prb::ProfTab t = ps->view();
+    // counts: hits into skey's slots, targets into stie's (the scratch is free once every page is merged)
+    int64_t *hits = reinterpret_cast<int64_t *>(t.skey);
+    int32_t *targets = reinterpret_cast<int32_t *>(t.stie);
+    if ((rc = ps->valA.ensure(P * 4)) || (rc = ps->keyA.ensure(16))) return rc;
+    // (the three share ps->sortTmp: all are sized before the first is enqueued)
+    const ProfCovered covered{hits};
+    auto scan_hits = [&](void *tmp, size_t &bytes) {
+      return rocprim::inclusive_scan(tmp, bytes, reinterpret_cast<const int64_t *>(t.hdiff), hits, P, rocprim::plus<int64_t>(), ctx->stream);
+    };
+    auto scan_targets = [&](void *tmp, size_t &bytes) {
+      return rocprim::inclusive_scan(tmp, bytes, t.tdiff, targets, P, rocprim::plus<int32_t>(), ctx->stream);
+    };
+    auto select_covered = [&](void *tmp, size_t &bytes) {
+      return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint32_t>(0), ps->valA.as<uint32_t>(), ps->keyA.as<size_t>(), P, covered,
+                             ctx->stream);
+    };
+    size_t tmp_h = 0, tmp_t = 0, tmp_s = 0;
+    PRB_HIP(scan_hits(nullptr, tmp_h));
+    PRB_HIP(scan_targets(nullptr, tmp_t));
+    PRB_HIP(select_covered(nullptr, tmp_s));
+    if ((rc = ps->sortTmp.ensure(std::max<size_t>({tmp_h, tmp_t, tmp_s, 1})))) return rc;
+    PRB_HIP(scan_hits(ps->sortTmp.p, tmp_h));
+    PRB_HIP(scan_targets(ps->sortTmp.p, tmp_t));
+    PRB_HIP(select_covered(ps->sortTmp.p, tmp_s));
+    size_t nsel = 0;
+    uint32_t bad = 0;
+    PRB_HIP(hipMemcpyAsync(&nsel, ps->keyA.p, sizeof nsel, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipMemcpyAsync(&bad, t.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad || nsel > P) {
+      set_error("prb_profset_finish: " + std::string(bad ? "a final hit's span lies outside its query" : "bad row count"));
+      return PRB_ERR_STATE;
+    }
+    if (nsel) {
+      try {
+        ps->rows.resize(nsel);
+      } catch (const std::exception &e) {
+        set_error(std::string("prb_profset_finish: ") + e.what());
+        return PRB_ERR_NOMEM;
+      }
+      if ((rc = ps->span.ensure(nsel * sizeof(prb_profile_pos)))) return rc;
+      PRB_HIP(launch_prof_rows(t, ps->valA.as<uint32_t>(), (int64_t)nsel, hits, targets, ps->span.p, ctx->stream));
+      PRB_HIP(hipMemcpyAsync(ps->rows.data(), ps->span.p, nsel * sizeof(prb_profile_pos), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = ctx->time_end(ctx->profile_timer, nsel ? 4 : 3))) return rc;
+  }
+  ps->finished = true;
+  ps->release(); // (only the host rows are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_profset_size(const prb_profset *ps) { return ps ? (int64_t)ps->rows.size() : -1; }
+const prb_profile_pos *prb_profset_rows(const prb_profset *ps) { return ps ? ps->rows.data() : nullptr; }
+void prb_profset_counts(const prb_profset *ps, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ps ? ps->counts[i] : 0;
+}
+void prb_profset_free(prb_profset *ps) {
+  delete ps;
+}
+
+int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }
+const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps) { return ps ? ps->pairs.data() : nullptr; }
+void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ps ? ps->counts[i] : 0;
+}
+void prb_pairset_free(prb_pairset *ps) { delete ps; }
+
+int64_t prb_hitset_size(const prb_hitset *hs) { return !hs ? -1 : hs->ext_hits ? hs->ext_nhits : (int64_t)hs->hits.size(); }
+const prb_hit *prb_hitset_hits(const prb_hitset *hs) { return !hs ? nullptr : hs->ext_hits ? hs->ext_hits : hs->hits.data(); }
+const int32_t *prb_hitset_basepairs(const prb_hitset *hs, int64_t *count) {
+  if (!hs) return nullptr;
+  if (count) *count = (hs->ext_hits ? hs->ext_bp_ints : (int64_t)hs->bp.size()) / 2;
+  return hs->ext_hits ? hs->ext_bp : hs->bp.data();
+}
+void prb_hitset_counts(const prb_hitset *hs, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = hs ? hs->counts[i] : 0;
+}
+void prb_hitset_free(prb_hitset *hs) { delete hs; }
+
+} // extern "C"

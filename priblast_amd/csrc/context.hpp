@@ -47,7 +47,7 @@ struct prb_ctx {
   prb::RaConst ra_const{};
   // int tables for the search stages (search_kernels.hip)
   void *search_const = nullptr;
-  void *search_ws = nullptr;   // prb::SearchWs, capi_search.hip
+  void *search_ws = nullptr;   // prb::SearchWs, search_host.hpp
   int64_t slow_hits = 0;       // extensions that went through the HBM-scratch fallback kernel
   int max_gap_caps = 128;      // largest diagonal capacity any gapped extension has needed
   bool keep_device_records = false; // final hit sets also keep their packed records in HBM (for prb_gather_hits)

@@ -1,5 +1,5 @@
-// prb_hitset (include/priblast_hip.h): the result of prb_search_page / prb_gather_hits, shared by
-// capi_search.hip (which fills it) and capi_comm.hip (the final hit gather).
+// prb_hitset (include/priblast_hip.h): the result of prb_search_page / prb_gather_hits, shared by the search driver
+// (capi_search.hip, which fills it), capi_sets.hip (its accessors) and capi_comm.hip (the final hit gather).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,14 +107,7 @@ struct prb_hitset {
   int next_slot = 0;
   // prb_search_page_summary: the search reduces its final hits to per-pair records on the device; `hits` / `bp` stay
   // empty and the records arrive here
-  bool summary = false;
   std::vector<prb_pair_summary> pairs;
-  // prb_search_page_top: the records are merged into this table on the device instead (queries [sub_q0, sub_q1) are
-  // the sub-batch being searched)
-  prb_topset *top = nullptr;
-  // prb_search_page_profile: the final hits are merged into this per-position table on the device instead
-  prb_profset *prof = nullptr;
-  int32_t sub_q0 = 0, sub_q1 = 0;
 };
 
 struct prb_pairset {

@@ -1,0 +1,433 @@
+// What the host units of the search share (capi_pages.hip, capi_search.hip, capi_sets.hip, capi_lines.hip): the
+// objects behind the C ABI's handles, the workspace of the search stages, and the rocPRIM idioms they all use.
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include <rocprim/rocprim.hpp>
+
+#include "../../include/priblast_hip.h"
+#include "context.hpp"
+#include "db_format.hpp"
+#include "hitset.hpp"
+#include "output.hpp"
+#include "search_kernels.hpp"
+#include "seed_dfs.hpp"
+
+namespace prb {
+
+struct SearchConstMem {
+  DevBuf ints, bulge;
+  SearchConst view{};
+};
+
+struct PageMem {
+  DevBuf seqs, sa, sa_seq, blk_seq, start_pos, seq_length, acc, cond;
+  PageDev view{};
+};
+
+// The device buffers of the search stages, reused across prb_search_page calls: X(name, trimmable), the one list that
+// the members, trim() and release() come from.  Not trimmable (SearchWs::trim): `packed`, which may still be on its way to
+// the host, and the three 16-byte cells `pending`, `count`, `resumeCount`, which never reach the limit.  `resumeSlot`
+// (12 B per hit of a gapped chunk) and `accScratch` are spared as well, for no reason on record: they look like
+// omissions from the list, and stay spared here only because this list restates what was there.
+#define PRB_SEARCH_BUFFERS(X)                                                                                                   \
+  X(cands, 1) X(row_count, 1) X(row_off, 1) X(row_cand, 1) X(seed_qacc, 1)                             /* seeds */              \
+  X(hitsA, 1) X(hitsB, 1) X(hitsC, 1) X(hitsTmp, 1)                                                    /* hit lists */          \
+  X(kE, 1) X(kL, 1) X(kQ, 1) X(kP, 1) X(kTmp, 1) X(kTmp2, 1) X(idxA, 1) X(idxB, 1) X(sortTmp, 1)       /* sort */               \
+  X(endKey, 1) X(pmax, 1) X(state, 1) X(keep, 1) X(pending, 0) X(surv, 1) X(count, 0) X(scanTmp, 1)    /* filter, select */     \
+  X(first, 1) X(cidx, 1)                                                                                                        \
+  X(gapScratch, 1) X(overflow, 1) X(tierOf, 1) X(listA, 1) X(listB, 1) X(listC, 1) X(ntrace, 1) X(trace, 1) /* gapped */        \
+  X(frontScratch, 1) X(accScratch, 0)                                                                                           \
+  X(resumeSlot, 0) X(resumePool, 1) X(resumePool2, 1) X(resumePool3, 1) X(resumeCount, 0)                                       \
+  X(slowList, 1) X(slowSlot, 1) X(slowCnt, 1) X(slowTrace, 1)                                                                   \
+  X(keptU, 1) X(keptFirst, 1) X(keptTier, 1) X(keptNtrace, 1) X(keptTrace, 1)                          /* chunked gapped */     \
+  X(subset, 1) X(subset2, 1) X(tierFin, 1) X(ntraceFin, 1)                                             /* traceback */          \
+  X(bpCount, 1) X(bpOff, 1) X(bpOff2, 1) X(bpOut, 1) X(bpEnds, 1)                                                               \
+  X(packed, 0) X(pairHead, 1) X(pairStart, 1)                                                          /* results */
+
+struct SearchWs {
+#define X(name, trimmable) DevBuf name;
+  PRB_SEARCH_BUFFERS(X)
+#undef X
+  // The front of the one-pass seed path for a chunk of candidates - candidates and their pair offsets on the device,
+  // query-side window sums, the pairs' keys and values, sorted - in buffers of its own, so that it can be issued for
+  // the NEXT sub-batch, on a stream of its own, while this sub-batch is in its last, nearly idle stretch (search_range):
+  // ~7 ms of bandwidth-bound work per configs[2] query beside the ~2 ms that the ~150 longest extensions of a query run
+  // alone (twice) and the final sort / filter / copies, instead of standing in line behind them.
+  struct FrontStage {
+    DevBuf cands, seed_qacc, pair0, keyA, keyB, valA, valB, sortTmp;
+    PinnedBuf pair0_pin;
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    bool ahead = false;         // holds the first chunk of the sub-batch whose candidates are at `cd`, issued on `stream`
+    const CandDev *cd = nullptr;
+    int32_t nc = 0;
+    int64_t np = 0;
+    int init() {
+      if (stream) return PRB_OK;
+      int lo = 0, hi = 0;
+      (void)hipDeviceGetStreamPriorityRange(&lo, &hi); // (lo = the numerically largest = least urgent)
+      if (hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, lo) != hipSuccess ||
+          hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
+        set_error("hipStreamCreateWithPriority / hipEventCreate failed (seed front stage)");
+        return PRB_ERR_HIP;
+      }
+      return PRB_OK;
+    }
+    void release() {
+      if (stream) {
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamDestroy(stream);
+        (void)hipEventDestroy(done);
+        stream = nullptr;
+      }
+      for (DevBuf *b : {&cands, &seed_qacc, &pair0, &keyA, &keyB, &valA, &valB, &sortTmp}) b->release();
+      pair0_pin.release();
+      ahead = false;
+    }
+  } front;
+  // results leave on a stream of their own: the next sub-batch does not queue behind 60 MB over PCIe
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t packed_ready = nullptr, copy_done = nullptr;
+  bool copy_pending = false;
+  int copy_init() {
+    if (copy_stream) return PRB_OK;
+    if (hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&packed_ready, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&copy_done, hipEventDisableTiming) != hipSuccess) {
+      set_error("hipStreamCreate / hipEventCreate failed (result copies)");
+      return PRB_ERR_HIP;
+    }
+    return PRB_OK;
+  }
+  PinnedBuf pinned, cand_pinned[2], tb_pinned, pin_hits[2], pin_bp[2];
+  bool trim_next = false; // the last sub-batch had a giant list: its buffers are let go before the next one starts
+  // every trimmable stage buffer over 256 MB (the front stage's are not touched: they may hold the next sub-batch already)
+  void trim() {
+#define X(name, trimmable) \
+  if (trimmable && name.cap > ((size_t)256 << 20)) name.release();
+    PRB_SEARCH_BUFFERS(X)
+#undef X
+    trim_next = false;
+  }
+  void release() {
+#define X(name, trimmable) name.release();
+    PRB_SEARCH_BUFFERS(X)
+#undef X
+    front.release();
+    if (copy_stream) {
+      (void)hipStreamSynchronize(copy_stream);
+      (void)hipStreamDestroy(copy_stream);
+      (void)hipEventDestroy(packed_ready);
+      (void)hipEventDestroy(copy_done);
+      copy_stream = nullptr;
+    }
+    for (PinnedBuf *b : {&pinned, &cand_pinned[0], &cand_pinned[1], &tb_pinned, &pin_hits[0], &pin_hits[1], &pin_bp[0], &pin_bp[1]})
+      b->release();
+  }
+};
+
+inline SearchWs &ws_of(prb_ctx *ctx) {
+  if (!ctx->search_ws) ctx->search_ws = new SearchWs();
+  return *static_cast<SearchWs *>(ctx->search_ws);
+}
+
+// Appends the results of finished sub-batches (pinned staging slots filled by asynchronous
+// copies on the compute stream) to the hit set while the GPU already works on the next one.
+struct Drainer {
+  struct Job {
+    int slot;
+    int64_t nhits, nbp_ints;
+  };
+  std::vector<prb_hit> *hits;
+  std::vector<int32_t> *bp;
+  std::vector<prb_pair_summary> *pairs = nullptr; // summary searches: the slots hold pair records (Job::nhits of them)
+  PinnedBuf *pin_hits, *pin_bp; // [2]
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  std::thread th;
+  std::mutex m;
+  std::condition_variable cv;
+  std::deque<Job> jobs;
+  bool busy[2] = {false, false}, stop = false, failed = false;
+  // what the whole search is expected to deliver (extrapolated by the submitting thread from the queries done so far):
+  // the vectors then grow once instead of doubling five times - each doubling of a list of 1e7 hits is a fresh 1 GB
+  // mapping, page faults and a copy, on a thread the next staging slot waits for
+  std::atomic<size_t> hint_hits{0}, hint_bp{0};
+
+  Drainer(std::vector<prb_hit> *h, std::vector<int32_t> *b, PinnedBuf *ph, PinnedBuf *pb)
+      : hits(h), bp(b), pin_hits(ph), pin_bp(pb) {}
+  int start() {
+    for (int i = 0; i < 2; i++)
+      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return PRB_ERR_HIP;
+    th = std::thread([this] { run(); });
+    return PRB_OK;
+  }
+  void run() {
+    for (;;) {
+      Job j;
+      {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [this] { return stop || !jobs.empty(); });
+        if (jobs.empty()) return;
+        j = jobs.front();
+        jobs.pop_front();
+      }
+      if (hipEventSynchronize(ev[j.slot]) != hipSuccess) failed = true;
+      if (pairs) {
+        const prb_pair_summary *ps = static_cast<const prb_pair_summary *>(pin_hits[j.slot].p);
+        pairs->insert(pairs->end(), ps, ps + j.nhits);
+      } else {
+        const prb_hit *src = static_cast<const prb_hit *>(pin_hits[j.slot].p);
+        if (hits->capacity() < hits->size() + (size_t)j.nhits)
+          hits->reserve(std::max({2 * hits->capacity(), hits->size() + (size_t)j.nhits, hint_hits.load()}));
+        hits->insert(hits->end(), src, src + j.nhits);
+        const int32_t *bsrc = static_cast<const int32_t *>(pin_bp[j.slot].p);
+        if (bp->capacity() < bp->size() + (size_t)j.nbp_ints)
+          bp->reserve(std::max({2 * bp->capacity(), bp->size() + (size_t)j.nbp_ints, hint_bp.load()}));
+        bp->insert(bp->end(), bsrc, bsrc + j.nbp_ints);
+      }
+      { // slot done: the submitting thread may fill it again
+        std::lock_guard<std::mutex> lk(m);
+        busy[j.slot] = false;
+      }
+      cv.notify_all();
+    }
+  }
+  // blocks until the staging slot is no longer read by the background thread
+  void acquire(int slot) {
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [&] { return !busy[slot]; });
+    busy[slot] = true;
+  }
+  void submit(const Job &j) {
+    {
+      std::lock_guard<std::mutex> lk(m);
+      jobs.push_back(j);
+    }
+    cv.notify_all();
+  }
+  int finish() { // everything submitted is in the hit set afterwards
+    {
+      std::lock_guard<std::mutex> lk(m);
+      stop = true;
+    }
+    cv.notify_all();
+    if (th.joinable()) th.join();
+    for (int i = 0; i < 2; i++)
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+    return failed ? PRB_ERR_HIP : PRB_OK;
+  }
+};
+
+// wall-clock timer for host-side pieces, reported next to the device stage timers (pseudo-stage names "host_*")
+struct HostTimer {
+  prb_ctx *ctx;
+  const char *name;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  HostTimer(prb_ctx *c, const char *n) : ctx(c), name(n) {}
+  ~HostTimer() {
+    auto &t = ctx->timers[name];
+    t.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t.launches++;
+  }
+};
+
+// ---------------------------------------------------------------- rocPRIM idioms
+// rocPRIM's two calls: `call(nullptr, bytes)` asks for the size of the temporary storage, `tmp` grows to it,
+// `call(tmp.p, bytes)` does the work.  (Where several primitives share one temporary buffer within a stream sequence,
+// all are sized before the first is enqueued instead - a DevBuf that grows frees memory that work in flight still reads.)
+template <class Call> int with_temp(DevBuf &tmp, const char *what, Call &&call) {
+  size_t bytes = 0;
+  if (hipError_t e = call(nullptr, bytes); e != hipSuccess) return hip_fail(e, what);
+  if (int rc = tmp.ensure(bytes)) return rc;
+  if (hipError_t e = call(tmp.p, bytes); e != hipSuccess) return hip_fail(e, what);
+  return PRB_OK;
+}
+
+// one stable radix sort of (key, value) pairs by the low `bits` bits of the keys
+template <class K, class V>
+int sort_pairs(hipStream_t s, DevBuf &tmp, const K *kin, K *kout, const V *vin, V *vout, size_t n, unsigned bits) {
+  return with_temp(tmp, "rocprim::radix_sort_pairs",
+                   [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, n, 0, bits, s); });
+}
+
+// out <- the entries of `in` (a list, or nullptr: 0..n-1) whose flag is set, in order; *nsel = how many, copied back
+// through w.count (the caller has ensured it) - which synchronises the stream
+inline int select_flagged(prb_ctx *ctx, SearchWs &w, const uint32_t *in, const uint8_t *flags, uint32_t *out, size_t n, int64_t *nsel) {
+  int rc;
+  if (in)
+    rc = with_temp(w.scanTmp, "rocprim::select",
+                   [&](void *t, size_t &b) { return rocprim::select(t, b, in, flags, out, w.count.as<size_t>(), n, ctx->stream); });
+  else
+    rc = with_temp(w.scanTmp, "rocprim::select", [&](void *t, size_t &b) {
+      return rocprim::select(t, b, rocprim::counting_iterator<uint32_t>(0), flags, out, w.count.as<size_t>(), n, ctx->stream);
+    });
+  if (rc) return rc;
+  size_t cnt = 0;
+  PRB_HIP(hipMemcpyAsync(&cnt, w.count.p, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *nsel = (int64_t)cnt;
+  return PRB_OK;
+}
+
+} // namespace prb
+
+// ---------------------------------------------------------------- the objects behind the handles
+struct prb_db {
+  prb_ctx *ctx = nullptr;
+  prb::DbHeader hdr;
+  std::vector<prb::DbPage> pages;
+  // Device residency (DbReader::LoadDatabases loads every page eagerly, db_reader.cpp:29-59; here a database
+  // larger than HBM - or than the share of it one wants to give it - is streamed): `mem` are slots, at most
+  // max_resident of them; a page that is searched is uploaded into a slot if it is not there (the least recently
+  // used page makes room), and with two slots or more the NEXT page's upload runs on a copy stream of its own
+  // while this one is searched (the host copies are page-locked for that).
+  std::vector<prb::PageMem> mem;
+  std::vector<int> slot_of_page, page_in_slot;
+  std::vector<uint64_t> slot_used; // "time" of the last search that used the slot
+  std::vector<hipEvent_t> slot_ready;
+  uint64_t clock = 0;
+  hipStream_t copy_stream = nullptr;
+  bool pinned = false;
+  int64_t uploads = 0; // pages uploaded so far (tests)
+  std::vector<prb::SeqTable> tabs; // per page: what the result lines print about its sequences
+};
+
+namespace prb {
+// The seed search proper of a batch against one page (SeedSearch::Run's DFS, seed_search.cpp:153-295): per query,
+// on host threads, in the background; a consumer waits for query q with wait_for(q).  It needs the encoded queries,
+// their suffix arrays and the page's k-mer table only - not the accessibilities - so it can be started as soon as a
+// batch exists (prb_qbatch_seed_search_begin), long before the batch is searched.
+struct SeedPlan {
+  const prb_db *db = nullptr;
+  int32_t page = 0, nq = 0, max_seed_length = 0;
+  double hybrid_threshold = 0;
+  std::vector<std::vector<SeedCandidate>> per_q;
+  std::vector<double> qpairs;
+  std::vector<int64_t> qrows, qents;
+  std::unique_ptr<std::atomic<int>[]> done;
+  std::atomic<int32_t> next_query{0}; // queries are handed out strictly in order: the consumer needs the first ones first
+  std::thread producer;
+  double dfs_ms = 0;
+  ~SeedPlan() {
+    if (producer.joinable()) producer.join();
+  }
+  void wait_for(int32_t q) const {
+    while (!done[q].load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(50));
+  }
+};
+} // namespace prb
+
+struct prb_qbatch {
+  prb_ctx *ctx = nullptr;
+  int32_t nq = 0, repeat_flag = 0;
+  std::vector<int64_t> off; // nq + 1; query q occupies [off[q], off[q] + len[q] + 1)
+  std::vector<int32_t> len, len_unmasked;
+  std::vector<char> seqs;   // same offsets, NUL after each query
+  std::vector<uint8_t> enc;
+  std::vector<int32_t> sa;
+  prb::DevBuf d_enc, d_sa, d_acc, d_cond, d_off, d_len;
+  bool have_acc = false;
+  int32_t W = 0, delta = 0;
+  prb::QBatchDev view{};
+  std::unique_ptr<prb::SeedPlan> plan; // a seed search started ahead of prb_search_page, if any
+};
+
+namespace prb {
+// What the tables that a batch's pages are merged into one by one have in common (prb_topset, prb_profset), and
+// what prb_search_page_top / prb_search_page_profile check before a merge
+struct MergeTable {
+  prb_ctx *ctx = nullptr;
+  const prb_qbatch *qb = nullptr;
+  const prb_db *db = nullptr;  // of the first merged page
+  int32_t nq = 0;
+  std::vector<uint8_t> merged; // per page of db
+  bool broken = false;         // a merge failed part way
+  bool finished = false;       // prb_*set_finish: the records are on the host, the device memory is released
+  int64_t counts[3] = {0, 0, 0};
+};
+} // namespace prb
+
+// prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
+struct prb_topset : prb::MergeTable {
+  int32_t n = 0;
+  prb::DevBuf table;               // prb_top_pair[nq * n] (`rank` = the pair's ordinal on the device), then int32_t fill[nq]
+  std::vector<prb_top_pair> pairs; // prb_topset_finish
+  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(prb_top_pair); }
+  ~prb_topset() { // (also on the error paths of prb_topset_create)
+    if (table.p) (void)hipSetDevice(ctx->device);
+    table.release();
+  }
+};
+
+// prb_profset_create .. prb_profset_free: the per-position table of one batch, merged into sub-batch by sub-batch
+// (emit_profile, capi_search.hip), and the sort / scan buffers of those merges
+struct prb_profset : prb::MergeTable {
+  std::vector<int64_t> off;    // [nq + 1] the queries' first slots (ProfTab::off)
+  prb::DevBuf table;           // ProfTab's arrays, one block (view())
+  prb::DevBuf keyA, keyB, valA, valB, span, scan, sortTmp; // per sub-batch: the hits in (pair, first position) order
+  std::vector<prb_profile_pos> rows; // prb_profset_finish
+  int64_t slots() const { return off.empty() ? 0 : off.back(); }
+  // the block: off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie, db_id,
+  // bp (x4), bad
+  size_t bytes() const { return (off.size() + 5 * (size_t)slots()) * 8 + (7 * (size_t)slots() + 2) * 4; }
+  prb::ProfTab view() const {
+    prb::ProfTab t;
+    const size_t P = (size_t)slots();
+    char *b = table.as<char>();
+    t.off = reinterpret_cast<const int64_t *>(b);
+    b += off.size() * 8;
+    t.hdiff = reinterpret_cast<unsigned long long *>(b);
+    t.key = t.hdiff + P;
+    t.tie = t.key + P;
+    t.skey = t.tie + P;
+    t.e_min = reinterpret_cast<double *>(t.skey + P);
+    t.tdiff = reinterpret_cast<int32_t *>(t.e_min + P);
+    t.stie = reinterpret_cast<uint32_t *>(t.tdiff + P);
+    t.db_id = reinterpret_cast<int32_t *>(t.stie + P);
+    t.bp = t.db_id + P;
+    t.bad = reinterpret_cast<uint32_t *>(t.bp + 4 * P);
+    t.nq = nq;
+    return t;
+  }
+  void release() {
+    for (prb::DevBuf *b : {&table, &keyA, &keyB, &valA, &valB, &span, &scan, &sortTmp}) b->release();
+  }
+  ~prb_profset() { // (also on the error paths of prb_profset_create)
+    if (table.p || keyA.p || sortTmp.p) (void)hipSetDevice(ctx->device);
+    release();
+  }
+};
+
+namespace prb {
+// Host threads for the per-query host work (suffix arrays, seed DFS): PRB_HOST_THREADS, else half of the CPUs the
+// process may keep busy, at most 32 (capi_pages.hip)
+int host_threads(int work_items);
+
+// where the final hits of a search go
+enum class SearchMode {
+  kRecords, // prb_search_page: hit records and base pairs to the host
+  kSummary, // prb_search_page_summary: per-pair records to the host
+  kTop,     // prb_search_page_top: per-pair records merged into the top-N table on the device
+  kProfile, // prb_search_page_profile: the hits merged into the per-position table on the device
+};
+inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
+
+// capi_pages.hip
+int page_slot(prb_ctx *user, prb_db *db, int page, int keep, hipStream_t stream, int *slot_out);
+std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, int32_t max_seed_length,
+                                          double hybrid_threshold);
+// capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
+// the search of one page in `mode`; `table` = the prb_topset / prb_profset of kTop / kProfile
+int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
+                      const prb_ris_opts *opts, int32_t last_stage);
+int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
+                SearchMode mode, prb_hitset **out, MergeTable *table = nullptr);
+} // namespace prb

@@ -252,7 +252,7 @@ def test_gapped_stage_in_chunks(ctx, tmp_path, monkeypatch):
 
 def test_candidate_with_more_query_entries_than_a_pair_value_holds(ctx, oracle, golden_dir, monkeypatch):
     """A 5,000 nt poly-G query: its seed candidates have ~5,000 query suffix-array entries each, more than the 4,096 the
-    one-pass form's pair value has bits for, so those chunks take the list form (search_range's `fuse = false`); a
+    one-pass form's pair value has bits for, so those chunks take the list form (seeds_to_hits: issue_front reports no pairs, seed_chunk_lists takes the chunk); a
     mixed query in the same batch takes the one-pass form.  Both against the oracle, and the same with the list form
     forced for everything."""
     from priblast_amd import capi

@@ -200,10 +200,12 @@ def test_header_lists_every_stage_timer():
     bench.py reports all of them."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import glob
     src = ""
-    for name in ("capi_search.hip", "capi_core.hip"):
-        with open(os.path.join(root, "priblast_amd", "csrc", name)) as f:
-            src += f.read()
+    for pat in ("*.hip", "*.hpp"):
+        for path in sorted(glob.glob(os.path.join(root, "priblast_amd", "csrc", pat))):
+            with open(path) as f:
+                src += f.read()
     names = set(re.findall(r'time_end\("([a-z_0-9]+)"', src)) | set(re.findall(r'HostTimer \w+\(ctx, "([a-z_0-9]+)"\)', src))
     m = re.search(r'kTierTimer\[\d+\] = \{([^}]*)\}', src)
     names |= set(re.findall(r'"([a-z_0-9]+)"', m.group(1)))
