@@ -96,6 +96,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch),
  * "profile" (prb_search_page_profile: the merge into the per-position table, launches = 8 per sub-batch; and
  *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4);
+ * "tophits" (prb_search_page_tophits: the merge into the top-N hit table, the scan of the kept hits' pair counts and the
+ *   gather of their lists; launches = 4 per sub-batch);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -232,6 +234,46 @@ int64_t prb_topset_size(const prb_topset *ts);
 const prb_top_pair *prb_topset_pairs(const prb_topset *ts);
 void prb_topset_counts(const prb_topset *ts, int64_t counts[3]);
 void prb_topset_free(prb_topset *ts);
+
+/* ---- the N best interaction sites per query (`ris -k N`): a top-N table of hits, with their base pairs, on the device ----
+ * A table holds, for each query of one batch, the N final hits of lowest e_tot among the hits of the pages merged into
+ * it (fewer when the query has fewer hits).  The final hits are exactly those of prb_search_page(..., 3, ...) with the
+ * same options.  Hits of a query are ranked by e_tot ascending, compared as doubles (-0.0 == +0.0); equal values are
+ * ordered by the output order: page ascending, then the hit's place among that query's hits of that page as
+ * prb_search_page returns them.  It is a total order, so the table does not depend on the order the pages are merged
+ * in, on how the batch is cut up, on the chunks of the gapped stage, nor on page residency.
+ *   prb_tophits_create       an empty table for qb (1 <= n <= 1024; nq * n slots of 72 B in HBM, and a pool of the kept
+ *                            hits' base pairs that is sized by what is kept)
+ *   prb_search_page_tophits  the search of prb_search_page against `page`, its final hits merged into the table on the
+ *                            device, the base-pair lists of the kept ones gathered into the table's pool (nothing is
+ *                            copied to the host).  Argument checks and option limits are those of prb_search_page; the
+ *                            table must have been made with this context and this batch, and holds pages of one
+ *                            database, each merged once, all with the same opts->output_style.  A call refused by these
+ *                            checks leaves the table as it was; a merge that fails part way (PRB_ERR_NOMEM when the pool
+ *                            cannot be allocated) leaves it unusable.
+ *   prb_tophits_finish       copies the records and the pairs to the host (one copy each) and releases the device
+ *                            memory: prb_tophits_hits then returns the records by query ascending, then by rank; `rank`
+ *                            counts from 0 within the query.  No page can be merged after it (a second call does nothing)
+ *   prb_tophits_hits         `h` equals, field for field, the record prb_search_page returns for that hit with the same
+ *                            output_style - but for bp_offset, which indexes prb_tophits_basepairs: the kept hits' lists
+ *                            in record order, without gaps, each equal to the hit's pairs in prb_hitset_basepairs (with
+ *                            output_style 0 the two end pairs, SURVEY a17 quirk included; otherwise every pair)
+ *   prb_tophits_counts       the stage counts of prb_hitset_counts, summed over the merged pages
+ * The device time of the merge (selection, scan, gather) is the stage "tophits" of prb_ctx_stage_ms. */
+typedef struct prb_top_hit {
+  prb_hit h;
+  int32_t page, rank; /* the page the hit was found in; its rank within its query */
+} prb_top_hit;
+typedef struct prb_tophits prb_tophits;
+int prb_tophits_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_tophits **out);
+int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                            prb_tophits *th);
+int prb_tophits_finish(prb_ctx *ctx, prb_tophits *th);
+int64_t prb_tophits_size(const prb_tophits *th);
+const prb_top_hit *prb_tophits_hits(const prb_tophits *th);
+const int32_t *prb_tophits_basepairs(const prb_tophits *th, int64_t *npairs);
+void prb_tophits_counts(const prb_tophits *th, int64_t counts[3]);
+void prb_tophits_free(prb_tophits *th);
 
 /* ---- per-position interaction profile (`ris -q`): a table of every query position on the device ----
  * For each query of one batch and each of its positions covered by at least one final hit (the hits of

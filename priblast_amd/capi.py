@@ -49,6 +49,10 @@ assert PAIR_DTYPE.itemsize == 64
 TOP_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
 assert TOP_DTYPE.itemsize == 72
 
+# prb_top_hit: the embedded prb_hit's fields, then the page it was found in and its rank within its query
+TOPHIT_DTYPE = np.dtype(HIT_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
+assert TOPHIT_DTYPE.itemsize == 72
+
 # prb_profile_pos: one covered query position of the per-position profile (`ris -q`)
 PROFILE_DTYPE = np.dtype([("query", "<i4"), ("pos", "<i4"), ("hits", "<i8"), ("targets", "<i4"), ("page", "<i4"),
                           ("db_id", "<i4"), ("reserved", "<i4"), ("e_min", "<f8"), ("bp_first", "<i4", (2,)),
@@ -116,6 +120,14 @@ SYMBOLS = {
     "prb_topset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_topset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_topset_free": (None, [ctypes.c_void_p]),
+    "prb_tophits_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_tophits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_tophits_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_tophits_size": (c_i64, [ctypes.c_void_p]),
+    "prb_tophits_hits": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_tophits_basepairs": (ctypes.c_void_p, [ctypes.c_void_p, P(c_i64)]),
+    "prb_tophits_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_tophits_free": (None, [ctypes.c_void_p]),
     "prb_profset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
     "prb_search_page_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
     "prb_profset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -463,6 +475,65 @@ def search_top(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
         recs = ts.finish()
         counts = ts.counts()
     return (recs, counts) if with_counts else recs
+
+
+class TopHits:
+    """prb_tophits: the N best final hits per query of one batch, with their base pairs, in a table on the device that
+    pages are merged into."""
+
+    def __init__(self, ctx, qb, n):
+        h = ctypes.c_void_p()
+        _check(lib().prb_tophits_create(ctx.h, qb.h, n, ctypes.byref(h)))
+        self.h, self.ctx, self.qb = h, ctx, qb
+
+    def merge(self, db, page, opts=None):
+        """prb_search_page_tophits: searches the batch against `page` and merges its final hits into the table"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_tophits(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+
+    def finish(self):
+        """prb_tophits_finish -> (structured array TOPHIT_DTYPE by query, then rank; int32 [npairs, 2] that the records'
+        bp_offset / bp_count index), both copies"""
+        _check(lib().prb_tophits_finish(self.ctx.h, self.h))
+        n = lib().prb_tophits_size(self.h)
+        cnt = c_i64()
+        p = lib().prb_tophits_basepairs(self.h, ctypes.byref(cnt))
+        recs, bp = np.zeros(0, TOPHIT_DTYPE), np.zeros((0, 2), np.int32)
+        if n:
+            buf = (ctypes.c_char * (n * TOPHIT_DTYPE.itemsize)).from_address(lib().prb_tophits_hits(self.h))
+            recs = np.frombuffer(buf, TOPHIT_DTYPE).copy()
+        if cnt.value:
+            buf = (ctypes.c_char * (cnt.value * 8)).from_address(p)
+            bp = np.frombuffer(buf, np.int32).reshape(-1, 2).copy()
+        return recs, bp
+
+    def counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_tophits_counts(self.h, c)
+        return tuple(c)
+
+    def close(self):
+        if self.h:
+            lib().prb_tophits_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_tophits(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
+    """The n final hits of lowest e_tot per query over the pages (all of them, in this order, by default) ->
+    (records TOPHIT_DTYPE by query, then rank; base pairs int32 [npairs, 2]).  with_counts: -> (records, base pairs,
+    (seed, ungapped, final) counts summed over the pages)."""
+    with TopHits(ctx, qb, n) as th:
+        for p in range(db.npages) if pages is None else pages:
+            th.merge(db, p, opts)
+        recs, bp = th.finish()
+        counts = th.counts()
+    return (recs, bp, counts) if with_counts else (recs, bp)
 
 
 class ProfSet:

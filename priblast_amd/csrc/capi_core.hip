@@ -229,6 +229,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->profile_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "tophits") == 0) {
+    if (ms) *ms = ctx->tophits_timer.ms;
+    if (launches) *launches = ctx->tophits_timer.launches;
+    return PRB_OK;
+  }
   auto it = ctx->timers.find(stage);
   if (ms) *ms = it == ctx->timers.end() ? 0.0 : it->second.ms;
   if (launches) *launches = it == ctx->timers.end() ? 0 : it->second.launches;
@@ -240,6 +245,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
     ctx->summary_timer = prb::StageTimer{};
     ctx->top_timer = prb::StageTimer{};
     ctx->profile_timer = prb::StageTimer{};
+    ctx->tophits_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }
 }

@@ -98,6 +98,7 @@ struct PageSearch {
   const SearchMode mode;
   prb_topset *top;   // kTop
   prb_profset *prof; // kProfile
+  prb_tophits *tophits; // kTopHits
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
@@ -1307,12 +1308,65 @@ static int emit_profile(SubSearch &s) {
   return ctx->time_end(ctx->profile_timer, 8);
 }
 
+// prb_search_page_tophits: the hits' records (as emit_records packs them, their base-pair ranges counted from this
+// sub-batch's first pair) merged into the top-N hit table on the device, then the kept hits' base-pair lists gathered in
+// table order - survivors from the table's pool, newcomers from this sub-batch's pairs - into a second pool of exactly the
+// scanned size, which becomes the table's.  Nothing leaves the device.  Closes the "traceback" bracket.
+static int emit_tophits(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  prb_tophits *th = s.tophits;
+  const int64_t nfin = s.nfin;
+  int rc;
+  if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
+  const int32_t *fresh;
+  if (s.opts.output_style == 0) { // the two end pairs of every hit
+    if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
+    PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+    PRB_HIP(launch_pack_hits(s.F, nfin, nullptr, nullptr, 0, w.packed.p, ctx->stream));
+    fresh = w.bpEnds.as<int32_t>();
+  } else {
+    PRB_HIP(launch_pack_hits(s.F, nfin, w.bpCount.as<int32_t>(), w.bpOff.as<int64_t>(), 0, w.packed.p, ctx->stream));
+    fresh = w.bpOut.as<int32_t>();
+  }
+  if ((rc = ctx->time_end("traceback", 2))) return rc;
+  if ((rc = ctx->time_begin())) return rc;
+  const int64_t nslots = (int64_t)th->nq * th->n;
+  const size_t NS = (size_t)nslots + 1;
+  if ((rc = th->cnt.ensure(NS * 4)) || (rc = th->off.ensure(NS * 8))) return rc;
+  PRB_HIP(launch_tophits_merge(w.packed.p, nfin, s.b.q0, s.b.q1, s.page, th->n, th->table.p, th->fill(), ctx->stream));
+  PRB_HIP(launch_tophits_counts(th->table.p, th->fill(), th->n, nslots, th->cnt.as<int32_t>(), ctx->stream));
+  auto counts = rocprim::make_transform_iterator(th->cnt.as<int32_t>(), ToI64());
+  if ((rc = with_temp(th->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
+         return rocprim::exclusive_scan(t, b, counts, th->off.as<int64_t>(), (int64_t)0, NS, rocprim::plus<int64_t>(), ctx->stream);
+       })))
+    return rc;
+  int64_t total = 0;
+  PRB_HIP(hipMemcpyAsync(&total, th->off.as<int64_t>() + nslots, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  if (total < 0) {
+    set_error("top-N hit table: bad base-pair total");
+    return PRB_ERR_STATE;
+  }
+  if (th->pool2.ensure((size_t)std::max<int64_t>(total, 1) * 8) != PRB_OK) {
+    set_error("prb_search_page_tophits: can't allocate the pool of the kept hits' base pairs (" + std::to_string(total) + " pairs)");
+    return PRB_ERR_NOMEM;
+  }
+  PRB_HIP(launch_tophits_gather(th->table.p, th->fill(), th->n, nslots, th->off.as<int64_t>(), s.b.q0, s.b.q1, s.page,
+                                th->pool.as<int32_t>(), fresh, th->pool2.as<int32_t>(), ctx->stream));
+  std::swap(th->pool, th->pool2);
+  th->pool_pairs = total;
+  s.hs->hits_total += nfin;
+  return ctx->time_end(ctx->tophits_timer, 4);
+}
+
 static int emit_final(SubSearch &s) {
   switch (s.mode) {
   case SearchMode::kRecords: return emit_records(s);
   case SearchMode::kSummary: return emit_summary(s);
   case SearchMode::kTop: return emit_top(s);
   case SearchMode::kProfile: return emit_profile(s);
+  case SearchMode::kTopHits: return emit_tophits(s);
   }
   return PRB_ERR_STATE;
 }
@@ -1501,6 +1555,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
                 mode,
                 mode == SearchMode::kTop ? static_cast<prb_topset *>(table) : nullptr,
                 mode == SearchMode::kProfile ? static_cast<prb_profset *>(table) : nullptr,
+                mode == SearchMode::kTopHits ? static_cast<prb_tophits *>(table) : nullptr,
                 hs,
                 0,
                 0};

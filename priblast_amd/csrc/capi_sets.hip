@@ -1,5 +1,5 @@
-// C ABI, part 4: the tables and record sets a search fills - the top-N table (prb_topset_*), the per-position
-// profile (prb_profset_*), per-pair records (prb_pairset_*), hit sets (prb_hitset_*).
+// C ABI, part 4: the tables and record sets a search fills - the top-N table (prb_topset_*), the top-N hit table
+// (prb_tophits_*), the per-position profile (prb_profset_*), per-pair records (prb_pairset_*), hit sets (prb_hitset_*).
 #include <algorithm>
 #include <cstring>
 
@@ -15,7 +15,7 @@ struct ProfCovered {
 };
 } // namespace
 
-// prb_search_page_top / prb_search_page_profile: page `page` searched and merged into the table `t` - `what` in the
+// prb_search_page_top / prb_search_page_profile / prb_search_page_tophits: page `page` searched and merged into the table `t` - `what` in the
 // messages, finished by `finish_fn`.  Every check comes before the table is touched: a refused call leaves it as it was.
 static int merge_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, MergeTable *t, prb_ctx *ctx,
                       prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts) {
@@ -145,6 +145,112 @@ void prb_topset_counts(const prb_topset *ts, int64_t counts[3]) {
 }
 void prb_topset_free(prb_topset *ts) {
   delete ts;
+}
+
+int prb_tophits_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_tophits **out) {
+  if (!ctx || !qb || !out) {
+    set_error("prb_tophits_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  if (n < 1 || n > kTopMaxN) {
+    set_error("prb_tophits_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+    return PRB_ERR_ARG;
+  }
+  std::unique_ptr<prb_tophits> th(new (std::nothrow) prb_tophits());
+  if (!th) {
+    set_error("prb_tophits_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  th->ctx = ctx;
+  th->qb = qb;
+  th->nq = qb->nq;
+  th->n = n;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = std::max<size_t>(th->slots_bytes() + (size_t)qb->nq * sizeof(int32_t), 1);
+  if (int rc = th->table.ensure(bytes)) return rc;
+  PRB_HIP(hipMemsetAsync(th->table.p, 0, bytes, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = th.release();
+  return PRB_OK;
+}
+
+int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_tophits *th) {
+  // (with the other checks' guarantee: a refused call leaves the table as it was)
+  if (th && opts && th->style >= 0 && opts->output_style != th->style) {
+    set_error("prb_search_page_tophits: the top-N hit table holds pages searched with output_style " + std::to_string(th->style) +
+              " (this call: " + std::to_string(opts->output_style) + ")");
+    return PRB_ERR_ARG;
+  }
+  const int rc = merge_page("prb_search_page_tophits", "top-N hit", "prb_tophits_finish", SearchMode::kTopHits, th, ctx, qb, db, page, opts);
+  if (rc == PRB_OK) th->style = opts->output_style;
+  return rc;
+}
+
+// the table's slots and fill counts are one block, the pool another: one copy each
+int prb_tophits_finish(prb_ctx *ctx, prb_tophits *th) {
+  if (!ctx || !th || th->ctx != ctx) {
+    set_error("prb_tophits_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (th->broken) {
+    set_error("prb_tophits_finish: an earlier merge into this top-N hit table failed");
+    return PRB_ERR_STATE;
+  }
+  if (th->finished) return PRB_OK; // (the records are on the host already)
+  try {
+    std::vector<int32_t> fill((size_t)th->nq);
+    std::vector<char> host(th->slots_bytes() + fill.size() * sizeof(int32_t));
+    th->bp.assign((size_t)th->pool_pairs * 2, 0);
+    PRB_HIP(hipSetDevice(ctx->device));
+    if (!host.empty()) PRB_HIP(hipMemcpyAsync(host.data(), th->table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (!th->bp.empty()) PRB_HIP(hipMemcpyAsync(th->bp.data(), th->pool.p, th->bp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(fill.data(), host.data() + th->slots_bytes(), fill.size() * sizeof(int32_t));
+    th->hits.clear();
+    int64_t next = 0; // the lists lie in table order without gaps: in record order
+    for (int32_t q = 0; q < th->nq; q++) {
+      if (fill[q] < 0 || fill[q] > th->n) {
+        set_error("prb_tophits_finish: query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
+        return PRB_ERR_STATE;
+      }
+      for (int32_t r = 0; r < fill[q]; r++) {
+        prb_top_hit x;
+        std::memcpy(&x, host.data() + ((size_t)q * th->n + r) * sizeof(prb_top_hit), sizeof x);
+        if (x.h.bp_offset != next || x.h.bp_count < 0) {
+          set_error("prb_tophits_finish: the base pairs of query " + std::to_string(q) + ", rank " + std::to_string(r) + " are out of place");
+          return PRB_ERR_STATE;
+        }
+        next += x.h.bp_count;
+        x.rank = r;
+        th->hits.push_back(x);
+      }
+    }
+    if (next != th->pool_pairs) {
+      set_error("prb_tophits_finish: " + std::to_string(th->pool_pairs) + " base pairs in the pool, " + std::to_string(next) + " in the records");
+      return PRB_ERR_STATE;
+    }
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_tophits_finish: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  th->finished = true;
+  th->release(); // (only the host copies are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_tophits_size(const prb_tophits *th) { return th ? (int64_t)th->hits.size() : -1; }
+const prb_top_hit *prb_tophits_hits(const prb_tophits *th) { return th ? th->hits.data() : nullptr; }
+const int32_t *prb_tophits_basepairs(const prb_tophits *th, int64_t *npairs) {
+  if (!th) return nullptr;
+  if (npairs) *npairs = (int64_t)th->bp.size() / 2;
+  return th->bp.data();
+}
+void prb_tophits_counts(const prb_tophits *th, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = th ? th->counts[i] : 0;
+}
+void prb_tophits_free(prb_tophits *th) {
+  delete th;
 }
 
 int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {

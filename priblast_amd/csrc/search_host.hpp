@@ -341,8 +341,8 @@ struct prb_qbatch {
 };
 
 namespace prb {
-// What the tables that a batch's pages are merged into one by one have in common (prb_topset, prb_profset), and
-// what prb_search_page_top / prb_search_page_profile check before a merge
+// What the tables that a batch's pages are merged into one by one have in common (prb_topset, prb_profset,
+// prb_tophits), and what prb_search_page_top / prb_search_page_profile / prb_search_page_tophits check before a merge
 struct MergeTable {
   prb_ctx *ctx = nullptr;
   const prb_qbatch *qb = nullptr;
@@ -364,6 +364,28 @@ struct prb_topset : prb::MergeTable {
   ~prb_topset() { // (also on the error paths of prb_topset_create)
     if (table.p) (void)hipSetDevice(ctx->device);
     table.release();
+  }
+};
+
+// prb_tophits_create .. prb_tophits_free: the top-N hit table of one batch, merged into sub-batch by sub-batch
+// (emit_tophits, capi_search.hip), and the pool of the kept hits' base pairs
+struct prb_tophits : prb::MergeTable {
+  int32_t n = 0;
+  int32_t style = -1;              // opts->output_style of the merged pages (-1: none yet)
+  prb::DevBuf table;               // prb_top_hit[nq * n] (`rank` = the hit's place in its query's run on the device), then int32_t fill[nq]
+  prb::DevBuf pool, pool2;         // the kept hits' pairs in table order (h.bp_offset indexes `pool`); the gather's target
+  int64_t pool_pairs = 0;          // pairs in `pool`
+  prb::DevBuf cnt, off, scanTmp;   // per slot (+ 1): pair counts, their exclusive scan
+  std::vector<prb_top_hit> hits;   // prb_tophits_finish
+  std::vector<int32_t> bp;
+  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(prb_top_hit); }
+  int32_t *fill() const { return reinterpret_cast<int32_t *>(table.as<char>() + slots_bytes()); }
+  void release() {
+    for (prb::DevBuf *b : {&table, &pool, &pool2, &cnt, &off, &scanTmp}) b->release();
+  }
+  ~prb_tophits() { // (also on the error paths of prb_tophits_create)
+    if (table.p || pool.p || pool2.p || cnt.p) (void)hipSetDevice(ctx->device);
+    release();
   }
 };
 
@@ -417,7 +439,9 @@ enum class SearchMode {
   kSummary, // prb_search_page_summary: per-pair records to the host
   kTop,     // prb_search_page_top: per-pair records merged into the top-N table on the device
   kProfile, // prb_search_page_profile: the hits merged into the per-position table on the device
+  kTopHits, // prb_search_page_tophits: the hits and their base pairs merged into the top-N hit table on the device
 };
+// (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
 
 // capi_pages.hip
@@ -425,7 +449,7 @@ int page_slot(prb_ctx *user, prb_db *db, int page, int keep, hipStream_t stream,
 std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, int32_t max_seed_length,
                                           double hybrid_threshold);
 // capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
-// the search of one page in `mode`; `table` = the prb_topset / prb_profset of kTop / kProfile
+// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits of kTop / kProfile / kTopHits
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,

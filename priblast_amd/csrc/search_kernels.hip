@@ -916,9 +916,27 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(HitSoA h, int64_t n, const
   out[k] = r;
 }
 
-// ---- top-N table (prb_search_page_top) ----
-// A pair's rank key is (energy key, tie key), compared as two u64 with the smaller one first.  The energy key maps
-// e_min to an unsigned integer of the same order (-0.0 becomes +0.0 first, so the two compare equal); the tie key is
+// ---- top-N tables (prb_search_page_top, prb_search_page_tophits) ----
+// What k_top_merge ranks: the per-pair summaries by e_min into prb_top_pair slots, or the final hits by e_tot into
+// prb_top_hit slots.  Either record is 64 bytes with `query` in it, and either slot is the record, `page`, `rank`.
+struct TopPairs {
+  using Rec = prb_pair_summary;
+  using Slot = prb_top_pair;
+  static __device__ __forceinline__ double energy(const Rec &r) { return r.e_min; }
+  static __device__ __forceinline__ Rec &body(Slot &s) { return s.s; }
+  static __device__ __forceinline__ const Rec &body(const Slot &s) { return s.s; }
+};
+struct TopHits {
+  using Rec = prb_hit;
+  using Slot = prb_top_hit;
+  static __device__ __forceinline__ double energy(const Rec &r) { return r.e_tot; }
+  static __device__ __forceinline__ Rec &body(Slot &s) { return s.h; }
+  static __device__ __forceinline__ const Rec &body(const Slot &s) { return s.h; }
+};
+static_assert(sizeof(prb_pair_summary) == 64 && sizeof(prb_hit) == 64 && sizeof(prb_top_pair) == 72 && sizeof(prb_top_hit) == 72,
+              "k_top_merge moves a record as 8 x 8 bytes");
+// A record's rank key is (energy key, tie key), compared as two u64 with the smaller one first.  The energy key maps
+// the energy to an unsigned integer of the same order (-0.0 becomes +0.0 first, so the two compare equal); the tie key is
 // (page << 32) | ordinal, the pair's position among its query's records of that page: the `-t` output order.  Within
 // one table no two pairs share a tie key (a page is merged once), so every merge below is one of distinct keys.
 constexpr int kTopBlock = 256;
@@ -956,9 +974,12 @@ __device__ __forceinline__ int count_below(const uint64_t *k1, const uint64_t *k
 // and the waves' counts.  When the next step might not fit, the buffer is bitonic-sorted and merged into the set (each entry's new place = its index + the entries of the
 // other list below it), the set is cut to n and the threshold drops.  At the end the set's records are gathered -
 // new ones from rec, kept ones from their old slots - and written in rank order.
-__global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary *__restrict__ rec, int64_t nrec, int32_t q0,
-                                                         int32_t page, int32_t n, int32_t cap, prb_top_pair *__restrict__ tab,
+template <class R>
+__global__ __launch_bounds__(kTopBlock) void k_top_merge(const typename R::Rec *__restrict__ rec, int64_t nrec, int32_t q0,
+                                                         int32_t page, int32_t n, int32_t cap, typename R::Slot *__restrict__ tab,
                                                          int32_t *__restrict__ fill) {
+  using Rec = typename R::Rec;
+  using Slot = typename R::Slot;
   extern __shared__ uint64_t top_lds[];
   uint64_t *sk1 = top_lds, *sk2 = sk1 + n, *ck1 = sk2 + n, *ck2 = ck1 + cap;
   uint32_t *ssrc = reinterpret_cast<uint32_t *>(ck2 + cap); // < 2^31: the old slot; else 2^31 | ordinal of a new record
@@ -979,11 +1000,11 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
   __syncthreads();
   const int64_t a = s_run[0], b = s_run[1];
   if (a >= b) return; // (uniform: no record of q against this page)
-  prb_top_pair *const slots = tab + (int64_t)q * n;
+  Slot *const slots = tab + (int64_t)q * n;
   int cnt = fill[q];
   for (int i = tid; i < cnt; i += kTopBlock) {
-    const prb_top_pair &t = slots[i];
-    sk1[i] = energy_key(t.s.e_min);
+    const Slot &t = slots[i];
+    sk1[i] = energy_key(R::energy(R::body(t)));
     sk2[i] = ((uint64_t)(uint32_t)t.page << 32) | (uint32_t)t.rank;
     ssrc[i] = (uint32_t)i;
   }
@@ -1068,7 +1089,7 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
 #pragma unroll
     for (int u = 0; u < kTopLoads; u++) { // (all loads issued before the first is used)
       const int64_t i = base + u * kTopBlock + tid;
-      e[u] = i < b ? rec[i].e_min : 0.0;
+      e[u] = i < b ? R::energy(rec[i]) : 0.0;
     }
     uint64_t k1[kTopLoads], mask[kTopLoads];
     bool take[kTopLoads];
@@ -1109,7 +1130,7 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
   // down never read a slot an earlier round wrote; within a round every lane reads before any lane writes.
   for (int r0 = ((cnt - 1) / kTopBlock) * kTopBlock; r0 >= 0; r0 -= kTopBlock) {
     const int j = r0 + tid;
-    const prb_pair_summary *from = nullptr; // (the summary part, moved as 8 x 8 bytes: 8-byte aligned in both places)
+    const Rec *from = nullptr; // (the record, moved as 8 x 8 bytes: 8-byte aligned in both places)
     int32_t pg = 0, rk = 0;
     if (j < cnt) {
       const uint32_t s = ssrc[j];
@@ -1118,7 +1139,7 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
         from = rec + a + rk;
         pg = page;
       } else if ((int)s != j) {
-        from = &slots[s].s;
+        from = &R::body(slots[s]);
         pg = slots[s].page;
         rk = slots[s].rank;
       }
@@ -1130,7 +1151,7 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
     }
     __syncthreads();
     if (from) {
-      uint2 *to = reinterpret_cast<uint2 *>(&slots[j].s);
+      uint2 *to = reinterpret_cast<uint2 *>(&R::body(slots[j]));
 #pragma unroll
       for (int k = 0; k < 8; k++) to[k] = v[k];
       slots[j].page = pg;
@@ -1138,6 +1159,40 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const prb_pair_summary 
     }
   }
   if (tid == 0) fill[q] = cnt;
+}
+
+// ---- base pairs of the top-N hit table ----
+// The kept hits' lists lie in a pool in table order without gaps.  After a merge: the counts of the slots in use, their
+// exclusive scan (rocPRIM, on the host side), then every list gathered into a second pool at its scanned place.
+__global__ __launch_bounds__(kBlock) void k_tophits_counts(const prb_top_hit *__restrict__ tab, const int32_t *__restrict__ fill,
+                                                           int32_t n, int64_t nslots, int32_t *__restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i > nslots) return;
+  int32_t c = 0;
+  if (i < nslots && (int32_t)(i % n) < fill[i / n]) c = max(tab[i].h.bp_count, 0);
+  cnt[i] = c;
+}
+// kTopHitLanes lanes per slot, a pair (8 bytes) per lane and step.  A hit of queries [q0, q1) that was found in `page`
+// came with this merge - its offset indexes `fresh` -, every other one lies in the old pool.  (The lanes of a slot
+// have its old offset in a register before they copy, the first of them replaces it behind the copy.)
+constexpr int kTopHitLanes = 16;
+static_assert(kBlock % kTopHitLanes == 0, "whole slots per workgroup");
+__global__ __launch_bounds__(kBlock) void k_tophits_gather(prb_top_hit *__restrict__ tab, const int32_t *__restrict__ fill, int32_t n,
+                                                           int64_t nslots, const int64_t *__restrict__ off, int32_t q0, int32_t q1,
+                                                           int32_t page, const int2 *__restrict__ old_pool,
+                                                           const int2 *__restrict__ fresh, int2 *__restrict__ pool) {
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = t / kTopHitLanes;
+  const int sub = (int)(t % kTopHitLanes);
+  if (i >= nslots) return;
+  const int32_t q = (int32_t)(i / n);
+  if ((int32_t)(i % n) >= fill[q]) return;
+  prb_top_hit &slot = tab[i];
+  const int32_t c = max(slot.h.bp_count, 0);
+  const int64_t from = slot.h.bp_offset, to = off[i];
+  const int2 *src = (q >= q0 && q < q1 && slot.page == page ? fresh : old_pool) + from;
+  for (int32_t j = sub; j < c; j += kTopHitLanes) pool[to + j] = src[j];
+  if (sub == 0) slot.h.bp_offset = to;
 }
 
 // ---- per-position profile (prb_search_page_profile) ----
@@ -1728,14 +1783,37 @@ hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, i
   hipLaunchKernelGGL(k_pair_fold, grid_for(npairs), dim3(kBlock), 0, s, h, n, start, npairs, ends, static_cast<prb_pair_summary *>(out));
   return hipGetLastError();
 }
-hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
-                            hipStream_t s) {
+template <class R>
+static hipError_t launch_top_merge_of(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab,
+                                      int32_t *fill, hipStream_t s) {
   if (nrec <= 0 || q1 <= q0) return hipSuccess;
   if (n < 1 || n > kTopMaxN) return hipErrorInvalidValue;
   const int cap = kTopCap;
   const size_t lds = (size_t)n * (8 + 8 + 4) + (size_t)cap * 16; // at most 52 KB (n = 1024)
-  hipLaunchKernelGGL(k_top_merge, dim3((unsigned)(q1 - q0)), dim3(kTopBlock), lds, s, static_cast<const prb_pair_summary *>(rec), nrec,
-                     q0, page, n, cap, static_cast<prb_top_pair *>(tab), fill);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_top_merge<R>), dim3((unsigned)(q1 - q0)), dim3(kTopBlock), lds, s,
+                     static_cast<const typename R::Rec *>(rec), nrec, q0, page, n, cap, static_cast<typename R::Slot *>(tab), fill);
+  return hipGetLastError();
+}
+hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
+                            hipStream_t s) {
+  return launch_top_merge_of<TopPairs>(rec, nrec, q0, q1, page, n, tab, fill, s);
+}
+hipError_t launch_tophits_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
+                                hipStream_t s) {
+  return launch_top_merge_of<TopHits>(rec, nrec, q0, q1, page, n, tab, fill, s);
+}
+hipError_t launch_tophits_counts(const void *tab, const int32_t *fill, int32_t n, int64_t nslots, int32_t *cnt, hipStream_t s) {
+  if (nslots < 0 || n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tophits_counts, grid_for(nslots + 1), dim3(kBlock), 0, s, static_cast<const prb_top_hit *>(tab), fill, n, nslots, cnt);
+  return hipGetLastError();
+}
+hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int32_t q0, int32_t q1,
+                                 int32_t page, const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s) {
+  if (nslots <= 0) return hipSuccess;
+  if (n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tophits_gather, grid_for(nslots * kTopHitLanes), dim3(kBlock), 0, s, static_cast<prb_top_hit *>(tab), fill, n, nslots,
+                     off, q0, q1, page, reinterpret_cast<const int2 *>(old_pool), reinterpret_cast<const int2 *>(fresh),
+                     reinterpret_cast<int2 *>(pool));
   return hipGetLastError();
 }
 hipError_t launch_prof_keys(int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, uint64_t *key, uint32_t *val,

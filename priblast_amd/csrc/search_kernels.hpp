@@ -145,6 +145,19 @@ constexpr int kTopMaxN = 1024; // the largest N: the set's keys and a candidate 
 // fill = int32_t[nq] (slots in use per query).  One workgroup per query; the page must not be in the table yet.
 hipError_t launch_top_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
                             hipStream_t s);
+// ---- top-N hit table (prb_search_page_tophits) ----
+// the same merge for final hits: rec = prb_hit[nrec] (launch_pack_hits' output for queries [q0, q1), ascending by query),
+// ranked by e_tot, then page, then the hit's place among its query's hits of the page; tab = prb_top_hit[nq * n]
+hipError_t launch_tophits_merge(const void *rec, int64_t nrec, int32_t q0, int32_t q1, int32_t page, int32_t n, void *tab, int32_t *fill,
+                                hipStream_t s);
+// cnt[i] = the base pairs of slot i of the table (0 for a slot not in use), i < nslots = nq * n; cnt[nslots] = 0, so that
+// an exclusive scan over nslots + 1 values ends with the total
+hipError_t launch_tophits_counts(const void *tab, const int32_t *fill, int32_t n, int64_t nslots, int32_t *cnt, hipStream_t s);
+// The kept hits' base-pair lists gathered into `pool` in table order: slot i's list goes to pair off[i].  Its source is
+// `fresh` (this sub-batch's pairs, which launch_pack_hits' offsets index) for a hit of queries [q0, q1) found in `page`,
+// else `old_pool`; the slot's bp_offset becomes off[i].  All three arrays are (q, db) pairs of two int32.
+hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int32_t q0, int32_t q1,
+                                 int32_t page, const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s);
 // ---- per-position profile (prb_search_page_profile) ----
 // The table of one batch in HBM.  Query q owns the slots [off[q], off[q + 1]) = its len + 1 positions (the last one
 // takes the -1 of a span that ends at the query's last base), so the difference arrays of all queries are one array

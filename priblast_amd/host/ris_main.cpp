@@ -25,7 +25,10 @@
 // batch, and only its N records per query reach the host.  `ris -q` writes one line per query position
 // that a final hit covers (hits, distinct targets, minimum energy and its first hit): a per-position
 // table on the GPU (prb_search_page_profile) takes every page of a batch, and only its covered rows
-// reach the host.  `-q` is refused with -t, -n, -b and in rank mode, as -t is.
+// reach the host.  `-q` is refused with -t, -n, -b and in rank mode, as -t is.  `ris -k N` writes the normal result
+// lines (or, with -b, the normal binary records) of each query's N final hits of lowest interaction energy only, best
+// first: a table on the GPU (prb_search_page_tophits) takes every page of a batch and keeps those hits with their base
+// pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -94,6 +97,9 @@ void usage() {
             "    -q        one line per query position covered by a final hit: hits and distinct targets covering it,\n"
             "              their minimum interaction energy and its first hit (-s has no effect; not with -t, -n, -b,\n"
             "              nor with WORLD_SIZE > 1)\n"
+            "    -k INT    only the INT interaction sites of lowest interaction energy per query, best first, as normal\n"
+            "              result lines (-s and -b are honoured; ties in output order; 1 <= INT <= 1024; not with -t, -n, -q,\n"
+            "              nor with WORLD_SIZE > 1)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
@@ -107,6 +113,8 @@ struct Args {
   int top = 0;          // -n (0: not given)
   bool top_given = false;
   bool profile = false; // -q
+  int tophits = 0;      // -k (0: not given)
+  bool tophits_given = false;
 };
 
 [[noreturn]] void die(const std::string &msg) {
@@ -127,6 +135,7 @@ struct BatchJob {
   std::vector<prb_pairset *> pair_pages; // -t: the per-pair summaries instead
   prb_topset *top = nullptr;             // -t -n: the batch's N best pairs per query instead
   prb_profset *prof = nullptr;           // -q: the batch's per-position profile instead
+  prb_tophits *tophits = nullptr;        // -k: the batch's N best hits per query instead
   std::vector<std::string> names; // of its queries, in the order of their indices in the hit records
   std::vector<int32_t> qlen_unmasked;
 };
@@ -137,6 +146,7 @@ struct Prepared {
   std::vector<int32_t> qlen_unmasked;
   prb_topset *top = nullptr; // -t -n: filled by search_batch, handed to the writer
   prb_profset *prof = nullptr; // -q: likewise
+  prb_tophits *tophits = nullptr; // -k: likewise
 };
 
 // ---- binary hit file (little-endian, the layouts of include/priblast_hip.h) ----------------------
@@ -333,6 +343,15 @@ void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector
     p.qb = nullptr;
     return;
   }
+  if (a.tophits) { // -k: every page merged into one table of hits on the device, then one copy of records and pairs
+    if (prb_tophits_create(w.ctx, p.qb, a.tophits, &p.tophits)) die(prb_last_error());
+    for (int page = 0; page < npages; page++)
+      if (prb_search_page_tophits(w.ctx, p.qb, w.db, page, &a.o, p.tophits)) die(prb_last_error());
+    if (prb_tophits_finish(w.ctx, p.tophits)) die(prb_last_error());
+    prb_qbatch_destroy(p.qb);
+    p.qb = nullptr;
+    return;
+  }
   for (int page = 0; page < npages; page++) {
     if (a.summary) {
       prb_pairset *ps = nullptr;
@@ -448,7 +467,7 @@ int ris_main(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:q")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -472,6 +491,13 @@ int ris_main(int argc, char **argv) {
       a.top = end != optarg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
       break;
     }
+    case 'k': {
+      char *end = nullptr;
+      const long v = std::strtol(optarg, &end, 10);
+      a.tophits_given = true;
+      a.tophits = end != optarg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
+      break;
+    }
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -479,6 +505,10 @@ int ris_main(int argc, char **argv) {
     default: die("Error: invalid argument");
     }
   }
+  if (a.tophits_given && a.summary) die("Error: -k (the N best interaction sites per query) can't be combined with -t (per-pair summary lines)");
+  if (a.tophits_given && a.top_given) die("Error: -k (the N best interaction sites per query) can't be combined with -n (the N best pairs per query)");
+  if (a.tophits_given && a.profile) die("Error: -k (the N best interaction sites per query) can't be combined with -q (per-position profile lines)");
+  if (a.tophits_given && (a.tophits < 1 || a.tophits > 1024)) die("Error: -k needs an integer between 1 and 1024 (this build's limit)");
   if (a.profile && a.summary) die("Error: -q (per-position profile lines) can't be combined with -t (per-pair summary lines)");
   if (a.profile && a.top_given) die("Error: -q (per-position profile lines) can't be combined with -n (the N best pairs per query)");
   if (a.profile && a.binary) die("Error: -q (per-position profile lines) can't be combined with -b (binary hit records)");
@@ -507,6 +537,8 @@ int ris_main(int argc, char **argv) {
   const int rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
   const bool rank_mode = world > 1 || std::getenv("PRB_FORCE_COMM") != nullptr;
   if (rank < 0 || rank >= world) die("Error: RANK outside WORLD_SIZE");
+  if (rank_mode && a.tophits)
+    die("Error: -k (the N best interaction sites per query) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
   if (rank_mode && a.profile)
     die("Error: -q (per-position profile lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
   if (rank_mode && a.summary)
@@ -647,6 +679,60 @@ int ris_main(int argc, char **argv) {
         cv.notify_all();
         continue;
       }
+      if (job.tophits) {
+        // The kept hits come by query, then by rank, the pages mixed; the writers take hits page by page, ascending by
+        // query, and write a query's hits of one page in the order given.  So the records are cut where a query's next
+        // hit lies in a lower page, and every piece goes out as a batch of its own (one piece for a database of one page).
+        const prb_top_hit *r = prb_tophits_hits(job.tophits);
+        const int64_t n = prb_tophits_size(job.tophits);
+        int64_t nbp = 0;
+        const int32_t *bp = prb_tophits_basepairs(job.tophits, &nbp);
+        std::vector<std::vector<prb_hit>> hits((size_t)npages);
+        std::vector<std::vector<int32_t>> pairs((size_t)npages);
+        for (int64_t i0 = 0; i0 < n;) {
+          int64_t i1 = i0 + 1;
+          while (i1 < n && !(r[i1].h.query == r[i1 - 1].h.query && r[i1].page < r[i1 - 1].page)) i1++;
+          const int32_t qa = r[i0].h.query, qz = r[i1 - 1].h.query;
+          for (int p = 0; p < npages; p++) {
+            hits[(size_t)p].clear();
+            pairs[(size_t)p].clear();
+          }
+          for (int64_t i = i0; i < i1; i++) {
+            prb_hit x = r[i].h;
+            if (r[i].page < 0 || r[i].page >= npages || x.bp_count < 0 || x.bp_offset < 0 || x.bp_offset + x.bp_count > nbp)
+              die("Error: bad record in the table of the best hits");
+            std::vector<int32_t> &pp = pairs[(size_t)r[i].page];
+            const int64_t at = (int64_t)pp.size() / 2;
+            pp.insert(pp.end(), bp + 2 * x.bp_offset, bp + 2 * (x.bp_offset + x.bp_count));
+            x.bp_offset = at;
+            x.query -= qa;
+            hits[(size_t)r[i].page].push_back(x);
+          }
+          BatchView v;
+          v.nq = (size_t)(qz - qa + 1);
+          v.names = job.names.data() + qa;
+          v.qlen_unmasked = job.qlen_unmasked.data() + qa;
+          for (int p = 0; p < npages; p++) {
+            PageHits ph;
+            ph.n = (int64_t)hits[(size_t)p].size();
+            ph.h = hits[(size_t)p].data();
+            ph.bp = pairs[(size_t)p].data();
+            ph.nbp = (int64_t)pairs[(size_t)p].size() / 2;
+            v.pages.push_back(ph);
+          }
+          if (a.binary) id += write_binary_batch(v, out);
+          else if ((id = prb::format_batch(v, tabs, a.o.output_style, id, sink, prb::format_threads())) < 0)
+            die("Error: can't write the output file");
+          i0 = i1;
+        }
+        prb_tophits_free(job.tophits);
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          written = b + 1;
+        }
+        cv.notify_all();
+        continue;
+      }
       if (job.top) {
         prb::TopView tv;
         tv.nq = job.nq;
@@ -758,6 +844,8 @@ int ris_main(int argc, char **argv) {
                p->top = nullptr;
                job.prof = p->prof;
                p->prof = nullptr;
+               job.tophits = p->tophits;
+               p->tophits = nullptr;
                job.qlen_unmasked = p->qlen_unmasked;
                names_of(batch_idx(b), job.names);
                job.nq = job.names.size();
