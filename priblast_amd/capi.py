@@ -414,12 +414,7 @@ def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):
     h = ctypes.c_void_p()
     _check(lib().prb_search_page_summary(ctx.h, qb.h, db.h, page, ctypes.byref(o), ctypes.byref(h)))
     try:
-        n = lib().prb_pairset_size(h)
-        if n:
-            buf = (ctypes.c_char * (n * PAIR_DTYPE.itemsize)).from_address(lib().prb_pairset_pairs(h))
-            pairs = np.frombuffer(buf, PAIR_DTYPE).copy()
-        else:
-            pairs = np.zeros(0, PAIR_DTYPE)
+        pairs = _records(lib().prb_pairset_pairs(h), lib().prb_pairset_size(h), PAIR_DTYPE)
         counts = (c_i64 * 3)()
         lib().prb_pairset_counts(h, counts)
     finally:
@@ -427,36 +422,44 @@ def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):
     return (pairs, tuple(counts)) if with_counts else pairs
 
 
-class TopSet:
-    """prb_topset: the N best pairs per query of one batch, in a table on the device that pages are merged into."""
+def _records(ptr, n, dtype):
+    """n records of `dtype` at `ptr` in the library's memory -> structured array (a copy)"""
+    if not n:
+        return np.zeros(0, dtype)
+    return np.frombuffer((ctypes.c_char * (n * dtype.itemsize)).from_address(ptr), dtype).copy()
 
-    def __init__(self, ctx, qb, n):
+
+class _MergeTable:
+    """A table on the device that the pages of one batch are merged into: prb_<PREFIX>_create / _finish / _counts /
+    _free and prb_search_page_<MERGE>."""
+    PREFIX = MERGE = None
+
+    def __init__(self, ctx, qb, *create_args):
         h = ctypes.c_void_p()
-        _check(lib().prb_topset_create(ctx.h, qb.h, n, ctypes.byref(h)))
+        _check(self._fn("create")(ctx.h, qb.h, *create_args, ctypes.byref(h)))
         self.h, self.ctx, self.qb = h, ctx, qb
 
-    def merge(self, db, page, opts=None):
-        """prb_search_page_top: searches the batch against `page` and merges its pairs into the table"""
-        o = opts or default_opts()
-        _check(lib().prb_search_page_top(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+    def _fn(self, name):
+        return getattr(lib(), f"prb_{self.PREFIX}_{name}")
 
-    def finish(self):
-        """prb_topset_finish -> structured array TOP_DTYPE (a copy), by query, then rank"""
-        _check(lib().prb_topset_finish(self.ctx.h, self.h))
-        n = lib().prb_topset_size(self.h)
-        if not n:
-            return np.zeros(0, TOP_DTYPE)
-        buf = (ctypes.c_char * (n * TOP_DTYPE.itemsize)).from_address(lib().prb_topset_pairs(self.h))
-        return np.frombuffer(buf, TOP_DTYPE).copy()
+    def merge(self, db, page, opts=None):
+        """prb_search_page_<MERGE>: searches the batch against `page` and merges the result into the table"""
+        o = opts or default_opts()
+        _check(getattr(lib(), "prb_search_page_" + self.MERGE)(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+
+    def _finish(self, records, dtype):
+        """prb_<PREFIX>_finish -> the records that prb_<PREFIX>_<records> points to (a copy)"""
+        _check(self._fn("finish")(self.ctx.h, self.h))
+        return _records(self._fn(records)(self.h), self._fn("size")(self.h), dtype)
 
     def counts(self):
         c = (c_i64 * 3)()
-        lib().prb_topset_counts(self.h, c)
+        self._fn("counts")(self.h, c)
         return tuple(c)
 
     def close(self):
         if self.h:
-            lib().prb_topset_free(self.h)
+            self._fn("free")(self.h)
             self.h = None
 
     def __enter__(self):
@@ -464,64 +467,49 @@ class TopSet:
 
     def __exit__(self, *exc):
         self.close()
+
+    def search(self, db, opts, pages):
+        """every page (all of them, in this order, by default) merged, then finish() -> (what finish returns, counts)"""
+        for p in range(db.npages) if pages is None else pages:
+            self.merge(db, p, opts)
+        return self.finish(), self.counts()
+
+
+class TopSet(_MergeTable):
+    """prb_topset: the N best pairs per query of one batch, in a table on the device that pages are merged into."""
+    PREFIX, MERGE = "topset", "top"
+
+    def __init__(self, ctx, qb, n):
+        super().__init__(ctx, qb, n)
+
+    def finish(self):
+        """prb_topset_finish -> structured array TOP_DTYPE (a copy), by query, then rank"""
+        return self._finish("pairs", TOP_DTYPE)
 
 
 def search_top(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
     """The n pairs of lowest e_min per query over the pages (all of them, in this order, by default) -> structured array
     TOP_DTYPE, by query, then rank.  with_counts: -> (records, (seed, ungapped, final) counts summed over the pages)."""
     with TopSet(ctx, qb, n) as ts:
-        for p in range(db.npages) if pages is None else pages:
-            ts.merge(db, p, opts)
-        recs = ts.finish()
-        counts = ts.counts()
+        recs, counts = ts.search(db, opts, pages)
     return (recs, counts) if with_counts else recs
 
 
-class TopHits:
+class TopHits(_MergeTable):
     """prb_tophits: the N best final hits per query of one batch, with their base pairs, in a table on the device that
     pages are merged into."""
+    PREFIX, MERGE = "tophits", "tophits"
 
     def __init__(self, ctx, qb, n):
-        h = ctypes.c_void_p()
-        _check(lib().prb_tophits_create(ctx.h, qb.h, n, ctypes.byref(h)))
-        self.h, self.ctx, self.qb = h, ctx, qb
-
-    def merge(self, db, page, opts=None):
-        """prb_search_page_tophits: searches the batch against `page` and merges its final hits into the table"""
-        o = opts or default_opts()
-        _check(lib().prb_search_page_tophits(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+        super().__init__(ctx, qb, n)
 
     def finish(self):
         """prb_tophits_finish -> (structured array TOPHIT_DTYPE by query, then rank; int32 [npairs, 2] that the records'
         bp_offset / bp_count index), both copies"""
-        _check(lib().prb_tophits_finish(self.ctx.h, self.h))
-        n = lib().prb_tophits_size(self.h)
+        recs = self._finish("hits", TOPHIT_DTYPE)
         cnt = c_i64()
         p = lib().prb_tophits_basepairs(self.h, ctypes.byref(cnt))
-        recs, bp = np.zeros(0, TOPHIT_DTYPE), np.zeros((0, 2), np.int32)
-        if n:
-            buf = (ctypes.c_char * (n * TOPHIT_DTYPE.itemsize)).from_address(lib().prb_tophits_hits(self.h))
-            recs = np.frombuffer(buf, TOPHIT_DTYPE).copy()
-        if cnt.value:
-            buf = (ctypes.c_char * (cnt.value * 8)).from_address(p)
-            bp = np.frombuffer(buf, np.int32).reshape(-1, 2).copy()
-        return recs, bp
-
-    def counts(self):
-        c = (c_i64 * 3)()
-        lib().prb_tophits_counts(self.h, c)
-        return tuple(c)
-
-    def close(self):
-        if self.h:
-            lib().prb_tophits_free(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return recs, _records(p, cnt.value * 2, np.dtype(np.int32)).reshape(-1, 2)
 
 
 def search_tophits(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
@@ -529,60 +517,24 @@ def search_tophits(ctx, qb, db, n, opts=None, pages=None, with_counts=False):
     (records TOPHIT_DTYPE by query, then rank; base pairs int32 [npairs, 2]).  with_counts: -> (records, base pairs,
     (seed, ungapped, final) counts summed over the pages)."""
     with TopHits(ctx, qb, n) as th:
-        for p in range(db.npages) if pages is None else pages:
-            th.merge(db, p, opts)
-        recs, bp = th.finish()
-        counts = th.counts()
+        (recs, bp), counts = th.search(db, opts, pages)
     return (recs, bp, counts) if with_counts else (recs, bp)
 
 
-class ProfSet:
+class ProfSet(_MergeTable):
     """prb_profset: the per-position profile of one batch, in a table on the device that pages are merged into."""
-
-    def __init__(self, ctx, qb):
-        h = ctypes.c_void_p()
-        _check(lib().prb_profset_create(ctx.h, qb.h, ctypes.byref(h)))
-        self.h, self.ctx, self.qb = h, ctx, qb
-
-    def merge(self, db, page, opts=None):
-        """prb_search_page_profile: searches the batch against `page` and merges its final hits into the table"""
-        o = opts or default_opts()
-        _check(lib().prb_search_page_profile(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+    PREFIX, MERGE = "profset", "profile"
 
     def finish(self):
         """prb_profset_finish -> structured array PROFILE_DTYPE (a copy), by query, then position"""
-        _check(lib().prb_profset_finish(self.ctx.h, self.h))
-        n = lib().prb_profset_size(self.h)
-        if not n:
-            return np.zeros(0, PROFILE_DTYPE)
-        buf = (ctypes.c_char * (n * PROFILE_DTYPE.itemsize)).from_address(lib().prb_profset_rows(self.h))
-        return np.frombuffer(buf, PROFILE_DTYPE).copy()
-
-    def counts(self):
-        c = (c_i64 * 3)()
-        lib().prb_profset_counts(self.h, c)
-        return tuple(c)
-
-    def close(self):
-        if self.h:
-            lib().prb_profset_free(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._finish("rows", PROFILE_DTYPE)
 
 
 def search_profile(ctx, qb, db, opts=None, pages=None, with_counts=False):
     """The per-position profile over the pages (all of them, in this order, by default) -> structured array
     PROFILE_DTYPE, by query, then position.  with_counts: -> (rows, (seed, ungapped, final) counts summed over the pages)."""
     with ProfSet(ctx, qb) as ps:
-        for p in range(db.npages) if pages is None else pages:
-            ps.merge(db, p, opts)
-        rows = ps.finish()
-        counts = ps.counts()
+        rows, counts = ps.search(db, opts, pages)
     return (rows, counts) if with_counts else rows
 
 
@@ -625,6 +577,16 @@ class Comm:
         return g, nq_of, qall  #  order of destruction the plain one: hit sets first)
 
 
+def _write(fn, db, qnames, qlen_unmasked, *args):
+    """One of the prb_write_*lines: the queries' names and lengths marshalled, `args` between them and the output
+    counters -> (lines, bytes)"""
+    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
+    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
+    lines, nbytes = c_i64(), c_i64()
+    _check(fn(db.h, len(qnames), names, ql.ctypes.data, *args, ctypes.byref(lines), ctypes.byref(nbytes)))
+    return lines.value, nbytes.value
+
+
 def write_lines(db, qnames, qlen_unmasked, pages, output_style=0, id0=0, fd=-1):
     """Result lines (SaveMyResults) of one batch: pages = [(hits, bp)] per database page as search_page returns
     them.  -> (lines, bytes) written to the descriptor fd (-1: formatted and counted only)."""
@@ -635,12 +597,7 @@ def write_lines(db, qnames, qlen_unmasked, pages, output_style=0, id0=0, fd=-1):
         bp = np.ascontiguousarray(bp, np.int32)
         keep += [hits, bp]
         arr[k] = PageHits(hits.ctypes.data if len(hits) else None, len(hits), bp.ctypes.data if bp.size else None, bp.size // 2)
-    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
-    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
-    lines, nbytes = c_i64(), c_i64()
-    _check(lib().prb_write_lines(db.h, len(qnames), names, ql.ctypes.data, arr, len(pages), output_style, id0, fd,
-                                 ctypes.byref(lines), ctypes.byref(nbytes)))
-    return lines.value, nbytes.value
+    return _write(lib().prb_write_lines, db, qnames, qlen_unmasked, arr, len(pages), output_style, id0, fd)
 
 
 def write_summary_lines(db, qnames, qlen_unmasked, pages, id0=0, fd=-1):
@@ -652,33 +609,18 @@ def write_summary_lines(db, qnames, qlen_unmasked, pages, id0=0, fd=-1):
         recs = np.ascontiguousarray(recs, PAIR_DTYPE)
         keep.append(recs)
         arr[k] = PagePairs(recs.ctypes.data if len(recs) else None, len(recs))
-    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
-    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
-    lines, nbytes = c_i64(), c_i64()
-    _check(lib().prb_write_summary_lines(db.h, len(qnames), names, ql.ctypes.data, arr, len(pages), id0, fd,
-                                         ctypes.byref(lines), ctypes.byref(nbytes)))
-    return lines.value, nbytes.value
+    return _write(lib().prb_write_summary_lines, db, qnames, qlen_unmasked, arr, len(pages), id0, fd)
 
 
 def write_top_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
     """Lines of `ris -t -n N` for one batch: recs as search_top returns them.  -> (lines, bytes) written to fd
     (-1: formatted and counted only)."""
     recs = np.ascontiguousarray(recs, TOP_DTYPE)
-    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
-    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
-    lines, nbytes = c_i64(), c_i64()
-    _check(lib().prb_write_top_lines(db.h, len(qnames), names, ql.ctypes.data, recs.ctypes.data if len(recs) else None,
-                                     len(recs), id0, fd, ctypes.byref(lines), ctypes.byref(nbytes)))
-    return lines.value, nbytes.value
+    return _write(lib().prb_write_top_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
 
 
 def write_profile_lines(db, qnames, qlen_unmasked, rows, id0=0, fd=-1):
     """Lines of `ris -q` for one batch: rows as search_profile returns them.  -> (lines, bytes) written to fd
     (-1: formatted and counted only)."""
     rows = np.ascontiguousarray(rows, PROFILE_DTYPE)
-    names = (ctypes.c_char_p * len(qnames))(*[n.encode() for n in qnames])
-    ql = np.ascontiguousarray(qlen_unmasked, np.int32)
-    lines, nbytes = c_i64(), c_i64()
-    _check(lib().prb_write_profile_lines(db.h, len(qnames), names, ql.ctypes.data, rows.ctypes.data if len(rows) else None,
-                                         len(rows), id0, fd, ctypes.byref(lines), ctypes.byref(nbytes)))
-    return lines.value, nbytes.value
+    return _write(lib().prb_write_profile_lines, db, qnames, qlen_unmasked, rows.ctypes.data if len(rows) else None, len(rows), id0, fd)

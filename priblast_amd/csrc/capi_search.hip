@@ -1169,6 +1169,27 @@ static int copy_out(SubSearch &s, int slot, size_t bytes, const int32_t *bp_src,
 // that the larger sub-batches to come still fit)
 static int ensure_slot(PinnedBuf &b, size_t bytes) { return b.ensure(b.cap >= bytes ? bytes : 2 * bytes); }
 
+// The base pairs that go with a sub-batch's hit records, in ints: the simplified output prints only the first and the
+// last pair of a hit, so only those two are kept (w.bpEnds); the detailed output keeps every pair (w.bpOut)
+static int64_t record_bp_ints(const SubSearch &s) { return s.opts.output_style == 0 ? s.nfin * 4 : s.bp_total * 2; }
+// the final hits' records into w.packed (the caller has sized it), their base-pair ranges counted from pair `bp_base`
+// on; *bp_src = the record_bp_ints(s) ints that the ranges index
+static int pack_records(SubSearch &s, int64_t bp_base, const int32_t **bp_src) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  const int64_t nfin = s.nfin;
+  if (s.opts.output_style == 0) {
+    if (int rc = w.bpEnds.ensure((size_t)nfin * 16)) return rc;
+    PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+    PRB_HIP(launch_pack_hits(s.F, nfin, nullptr, nullptr, bp_base, w.packed.p, ctx->stream));
+    *bp_src = w.bpEnds.as<int32_t>();
+  } else {
+    PRB_HIP(launch_pack_hits(s.F, nfin, w.bpCount.as<int32_t>(), w.bpOff.as<int64_t>(), bp_base, w.packed.p, ctx->stream));
+    *bp_src = w.bpOut.as<int32_t>();
+  }
+  return PRB_OK;
+}
+
 // prb_search_page: records packed on the device (with their base-pair ranges), one asynchronous copy each for hits
 // and pairs into a pinned slot.  Closes the "traceback" bracket.
 static int emit_records(SubSearch &s) {
@@ -1179,21 +1200,12 @@ static int emit_records(SubSearch &s) {
   int rc;
   const int slot = acquire_slot(s);
   const int64_t bp_base_pairs = hs->bp_ints_total / 2;
-  const int64_t nbp_ints = s.opts.output_style == 0 ? nfin * 4 : s.bp_total * 2;
+  const int64_t nbp_ints = record_bp_ints(s);
   const size_t hit_bytes = (size_t)nfin * sizeof(prb_hit), bp_bytes = (size_t)std::max<int64_t>(nbp_ints, 1) * 4;
   if ((rc = w.packed.ensure(hit_bytes)) || (rc = ensure_slot(w.pin_hits[slot], hit_bytes)) || (rc = ensure_slot(w.pin_bp[slot], bp_bytes)))
     return rc;
   const int32_t *bp_src;
-  if (s.opts.output_style == 0) {
-    // simplified output: only the first and the last pair of a hit are ever printed
-    if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
-    PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
-    PRB_HIP(launch_pack_hits(s.F, nfin, nullptr, nullptr, bp_base_pairs, w.packed.p, ctx->stream));
-    bp_src = w.bpEnds.as<int32_t>();
-  } else {
-    PRB_HIP(launch_pack_hits(s.F, nfin, w.bpCount.as<int32_t>(), w.bpOff.as<int64_t>(), bp_base_pairs, w.packed.p, ctx->stream));
-    bp_src = w.bpOut.as<int32_t>();
-  }
+  if ((rc = pack_records(s, bp_base_pairs, &bp_src))) return rc;
   if ((rc = copy_out(s, slot, hit_bytes, bp_src, nbp_ints))) return rc;
   if (hs->on_device) { // device copies for the final hit gather (prb_gather_hits): no re-upload later
     if ((rc = hs->d_hits.append(w.packed.p, hit_bytes, ctx->stream)) || (rc = hs->d_bp.append(bp_src, (size_t)nbp_ints * 4, ctx->stream)))
@@ -1259,8 +1271,7 @@ static int emit_top(SubSearch &s) {
   PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
   if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
   if ((rc = ctx->time_begin())) return rc;
-  PRB_HIP(launch_top_merge(w.packed.p, npairs, s.b.q0, s.b.q1, s.page, ts->n, ts->table.p,
-                           reinterpret_cast<int32_t *>(ts->table.as<char>() + ts->slots_bytes()), ctx->stream));
+  PRB_HIP(launch_top_merge(w.packed.p, npairs, s.b.q0, s.b.q1, s.page, ts->n, ts->table.p, ts->fill(), ctx->stream));
   s.hs->hits_total += s.nfin;
   return ctx->time_end(ctx->top_timer, 1);
 }
@@ -1320,15 +1331,7 @@ static int emit_tophits(SubSearch &s) {
   int rc;
   if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
   const int32_t *fresh;
-  if (s.opts.output_style == 0) { // the two end pairs of every hit
-    if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
-    PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
-    PRB_HIP(launch_pack_hits(s.F, nfin, nullptr, nullptr, 0, w.packed.p, ctx->stream));
-    fresh = w.bpEnds.as<int32_t>();
-  } else {
-    PRB_HIP(launch_pack_hits(s.F, nfin, w.bpCount.as<int32_t>(), w.bpOff.as<int64_t>(), 0, w.packed.p, ctx->stream));
-    fresh = w.bpOut.as<int32_t>();
-  }
+  if ((rc = pack_records(s, 0, &fresh))) return rc;
   if ((rc = ctx->time_end("traceback", 2))) return rc;
   if ((rc = ctx->time_begin())) return rc;
   const int64_t nslots = (int64_t)th->nq * th->n;

@@ -62,34 +62,86 @@ static int merge_page(const char *fn_name, const char *what, const char *finish_
   return PRB_OK;
 }
 
-extern "C" {
-
-int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out) {
+// prb_topset_create / prb_tophits_create: an empty table of n slots per query of the batch
+template <class T> static int create_top_table(const char *fn_name, prb_ctx *ctx, const prb_qbatch *qb, int32_t n, T **out) {
+  const std::string fn = fn_name;
   if (!ctx || !qb || !out) {
-    set_error("prb_topset_create: bad argument");
+    set_error(fn + ": bad argument");
     return PRB_ERR_ARG;
   }
   *out = nullptr;
   if (n < 1 || n > kTopMaxN) {
-    set_error("prb_topset_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+    set_error(fn + ": need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
     return PRB_ERR_ARG;
   }
-  std::unique_ptr<prb_topset> ts(new (std::nothrow) prb_topset());
-  if (!ts) {
-    set_error("prb_topset_create: out of host memory");
+  std::unique_ptr<T> t(new (std::nothrow) T());
+  if (!t) {
+    set_error(fn + ": out of host memory");
     return PRB_ERR_NOMEM;
   }
-  ts->ctx = ctx;
-  ts->qb = qb;
-  ts->nq = qb->nq;
-  ts->n = n;
+  t->ctx = ctx;
+  t->qb = qb;
+  t->nq = qb->nq;
+  t->n = n;
   PRB_HIP(hipSetDevice(ctx->device));
-  const size_t bytes = ts->slots_bytes() + (size_t)qb->nq * sizeof(int32_t);
-  if (int rc = ts->table.ensure(std::max<size_t>(bytes, 1))) return rc;
-  PRB_HIP(hipMemsetAsync(ts->table.p, 0, std::max<size_t>(bytes, 1), ctx->stream));
+  const size_t bytes = std::max<size_t>(t->slots_bytes() + (size_t)qb->nq * sizeof(int32_t), 1);
+  if (int rc = t->table.ensure(bytes)) return rc;
+  PRB_HIP(hipMemsetAsync(t->table.p, 0, bytes, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream));
-  *out = ts.release();
+  *out = t.release();
   return PRB_OK;
+}
+
+// What every prb_*_finish starts with: the table `t` - `what` in the messages - belongs to ctx and no merge into it failed
+static int finish_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const MergeTable *t) {
+  if (!ctx || !t || t->ctx != ctx) {
+    set_error(std::string(fn_name) + ": bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (t->broken) {
+    set_error(std::string(fn_name) + ": an earlier merge into this " + what + " table failed");
+    return PRB_ERR_STATE;
+  }
+  return PRB_OK;
+}
+
+// prb_topset_finish / prb_tophits_finish: the slots and fill counts to the host (one block: one copy, enqueued after
+// `also_copy` has enqueued whatever else the table holds), then each(q, r, slot) for every slot in use, by query, then
+// rank - the order of the host records
+template <class Slot, class AlsoCopy, class Each>
+static int download_slots(const char *fn_name, prb_ctx *ctx, const TopTable<Slot> &t, AlsoCopy also_copy, Each each) {
+  const std::string fn = fn_name;
+  try {
+    std::vector<char> host(t.slots_bytes() + (size_t)t.nq * sizeof(int32_t));
+    PRB_HIP(hipSetDevice(ctx->device));
+    if (int rc = also_copy()) return rc;
+    if (!host.empty()) PRB_HIP(hipMemcpyAsync(host.data(), t.table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> fill((size_t)t.nq);
+    std::memcpy(fill.data(), host.data() + t.slots_bytes(), fill.size() * sizeof(int32_t));
+    for (int32_t q = 0; q < t.nq; q++) {
+      if (fill[q] < 0 || fill[q] > t.n) {
+        set_error(fn + ": query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
+        return PRB_ERR_STATE;
+      }
+      for (int32_t r = 0; r < fill[q]; r++) {
+        Slot x;
+        std::memcpy(&x, host.data() + ((size_t)q * t.n + r) * sizeof(Slot), sizeof x);
+        x.rank = r;
+        if (int rc = each(q, r, x)) return rc;
+      }
+    }
+  } catch (const std::exception &e) {
+    set_error(fn + ": " + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  return PRB_OK;
+}
+
+extern "C" {
+
+int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out) {
+  return create_top_table("prb_topset_create", ctx, qb, n, out);
 }
 
 int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_topset *ts) {
@@ -97,42 +149,16 @@ int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, 
 }
 
 int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
-  if (!ctx || !ts || ts->ctx != ctx) {
-    set_error("prb_topset_finish: bad argument (the table belongs to another context)");
-    return PRB_ERR_ARG;
-  }
-  if (ts->broken) {
-    set_error("prb_topset_finish: an earlier merge into this top-N table failed");
-    return PRB_ERR_STATE;
-  }
+  if (int rc = finish_guard("prb_topset_finish", "top-N", ctx, ts)) return rc;
   if (ts->finished) return PRB_OK; // (the records are on the host already)
-  try {
-    std::vector<int32_t> fill((size_t)ts->nq);
-    // (slots and fill counts are one block: one copy)
-    std::vector<char> host(ts->slots_bytes() + fill.size() * sizeof(int32_t));
-    PRB_HIP(hipSetDevice(ctx->device));
-    if (!host.empty()) {
-      PRB_HIP(hipMemcpyAsync(host.data(), ts->table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
-      PRB_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    std::memcpy(fill.data(), host.data() + ts->slots_bytes(), fill.size() * sizeof(int32_t));
-    ts->pairs.clear();
-    for (int32_t q = 0; q < ts->nq; q++) {
-      if (fill[q] < 0 || fill[q] > ts->n) {
-        set_error("prb_topset_finish: query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
-        return PRB_ERR_STATE;
-      }
-      for (int32_t r = 0; r < fill[q]; r++) {
-        prb_top_pair p;
-        std::memcpy(&p, host.data() + ((size_t)q * ts->n + r) * sizeof(prb_top_pair), sizeof p);
-        p.rank = r;
+  ts->pairs.clear();
+  const int rc = download_slots(
+      "prb_topset_finish", ctx, *ts, []() -> int { return PRB_OK; },
+      [&](int32_t, int32_t, const prb_top_pair &p) -> int {
         ts->pairs.push_back(p);
-      }
-    }
-  } catch (const std::exception &e) {
-    set_error(std::string("prb_topset_finish: ") + e.what());
-    return PRB_ERR_NOMEM;
-  }
+        return PRB_OK;
+      });
+  if (rc) return rc;
   ts->finished = true;
   ts->table.release(); // (only the host records are needed from here on)
   return PRB_OK;
@@ -148,31 +174,7 @@ void prb_topset_free(prb_topset *ts) {
 }
 
 int prb_tophits_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_tophits **out) {
-  if (!ctx || !qb || !out) {
-    set_error("prb_tophits_create: bad argument");
-    return PRB_ERR_ARG;
-  }
-  *out = nullptr;
-  if (n < 1 || n > kTopMaxN) {
-    set_error("prb_tophits_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
-    return PRB_ERR_ARG;
-  }
-  std::unique_ptr<prb_tophits> th(new (std::nothrow) prb_tophits());
-  if (!th) {
-    set_error("prb_tophits_create: out of host memory");
-    return PRB_ERR_NOMEM;
-  }
-  th->ctx = ctx;
-  th->qb = qb;
-  th->nq = qb->nq;
-  th->n = n;
-  PRB_HIP(hipSetDevice(ctx->device));
-  const size_t bytes = std::max<size_t>(th->slots_bytes() + (size_t)qb->nq * sizeof(int32_t), 1);
-  if (int rc = th->table.ensure(bytes)) return rc;
-  PRB_HIP(hipMemsetAsync(th->table.p, 0, bytes, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  *out = th.release();
-  return PRB_OK;
+  return create_top_table("prb_tophits_create", ctx, qb, n, out);
 }
 
 int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_tophits *th) {
@@ -189,50 +191,30 @@ int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
 
 // the table's slots and fill counts are one block, the pool another: one copy each
 int prb_tophits_finish(prb_ctx *ctx, prb_tophits *th) {
-  if (!ctx || !th || th->ctx != ctx) {
-    set_error("prb_tophits_finish: bad argument (the table belongs to another context)");
-    return PRB_ERR_ARG;
-  }
-  if (th->broken) {
-    set_error("prb_tophits_finish: an earlier merge into this top-N hit table failed");
-    return PRB_ERR_STATE;
-  }
+  if (int rc = finish_guard("prb_tophits_finish", "top-N hit", ctx, th)) return rc;
   if (th->finished) return PRB_OK; // (the records are on the host already)
-  try {
-    std::vector<int32_t> fill((size_t)th->nq);
-    std::vector<char> host(th->slots_bytes() + fill.size() * sizeof(int32_t));
-    th->bp.assign((size_t)th->pool_pairs * 2, 0);
-    PRB_HIP(hipSetDevice(ctx->device));
-    if (!host.empty()) PRB_HIP(hipMemcpyAsync(host.data(), th->table.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
-    if (!th->bp.empty()) PRB_HIP(hipMemcpyAsync(th->bp.data(), th->pool.p, th->bp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PRB_HIP(hipStreamSynchronize(ctx->stream));
-    std::memcpy(fill.data(), host.data() + th->slots_bytes(), fill.size() * sizeof(int32_t));
-    th->hits.clear();
-    int64_t next = 0; // the lists lie in table order without gaps: in record order
-    for (int32_t q = 0; q < th->nq; q++) {
-      if (fill[q] < 0 || fill[q] > th->n) {
-        set_error("prb_tophits_finish: query " + std::to_string(q) + " has " + std::to_string(fill[q]) + " slots in use");
-        return PRB_ERR_STATE;
-      }
-      for (int32_t r = 0; r < fill[q]; r++) {
-        prb_top_hit x;
-        std::memcpy(&x, host.data() + ((size_t)q * th->n + r) * sizeof(prb_top_hit), sizeof x);
+  th->hits.clear();
+  int64_t next = 0; // the lists lie in table order without gaps: in record order
+  const int rc = download_slots(
+      "prb_tophits_finish", ctx, *th,
+      [&]() -> int {
+        th->bp.assign((size_t)th->pool_pairs * 2, 0);
+        if (!th->bp.empty()) PRB_HIP(hipMemcpyAsync(th->bp.data(), th->pool.p, th->bp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return PRB_OK;
+      },
+      [&](int32_t q, int32_t r, const prb_top_hit &x) -> int {
         if (x.h.bp_offset != next || x.h.bp_count < 0) {
           set_error("prb_tophits_finish: the base pairs of query " + std::to_string(q) + ", rank " + std::to_string(r) + " are out of place");
           return PRB_ERR_STATE;
         }
         next += x.h.bp_count;
-        x.rank = r;
         th->hits.push_back(x);
-      }
-    }
-    if (next != th->pool_pairs) {
-      set_error("prb_tophits_finish: " + std::to_string(th->pool_pairs) + " base pairs in the pool, " + std::to_string(next) + " in the records");
-      return PRB_ERR_STATE;
-    }
-  } catch (const std::exception &e) {
-    set_error(std::string("prb_tophits_finish: ") + e.what());
-    return PRB_ERR_NOMEM;
+        return PRB_OK;
+      });
+  if (rc) return rc;
+  if (next != th->pool_pairs) {
+    set_error("prb_tophits_finish: " + std::to_string(th->pool_pairs) + " base pairs in the pool, " + std::to_string(next) + " in the records");
+    return PRB_ERR_STATE;
   }
   th->finished = true;
   th->release(); // (only the host copies are needed from here on)
@@ -292,14 +274,7 @@ int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
 
 // the covered positions selected on the device (Hits > 0 after the scans), their rows built there and copied once
 int prb_profset_finish(prb_ctx *ctx, prb_profset *ps) {
-  if (!ctx || !ps || ps->ctx != ctx) {
-    set_error("prb_profset_finish: bad argument (the table belongs to another context)");
-    return PRB_ERR_ARG;
-  }
-  if (ps->broken) {
-    set_error("prb_profset_finish: an earlier merge into this profile table failed");
-    return PRB_ERR_STATE;
-  }
+  if (int rc = finish_guard("prb_profset_finish", "profile", ctx, ps)) return rc;
   if (ps->finished) return PRB_OK; // (the rows are on the host already)
   const size_t P = (size_t)ps->slots();
   ps->rows.clear();

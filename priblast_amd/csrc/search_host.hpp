@@ -355,12 +355,20 @@ struct MergeTable {
 };
 } // namespace prb
 
-// prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
-struct prb_topset : prb::MergeTable {
+namespace prb {
+// What the two top-N tables have in common (prb_topset, prb_tophits): n slots of `Slot` per query and the queries' fill
+// counts, one block on the device
+template <class Slot> struct TopTable : MergeTable {
   int32_t n = 0;
-  prb::DevBuf table;               // prb_top_pair[nq * n] (`rank` = the pair's ordinal on the device), then int32_t fill[nq]
+  DevBuf table; // Slot[nq * n] (`rank` = the record's ordinal within its query's run on the device), then int32_t fill[nq]
+  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(Slot); }
+  int32_t *fill() const { return reinterpret_cast<int32_t *>(table.template as<char>() + slots_bytes()); }
+};
+} // namespace prb
+
+// prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
+struct prb_topset : prb::TopTable<prb_top_pair> {
   std::vector<prb_top_pair> pairs; // prb_topset_finish
-  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(prb_top_pair); }
   ~prb_topset() { // (also on the error paths of prb_topset_create)
     if (table.p) (void)hipSetDevice(ctx->device);
     table.release();
@@ -369,17 +377,13 @@ struct prb_topset : prb::MergeTable {
 
 // prb_tophits_create .. prb_tophits_free: the top-N hit table of one batch, merged into sub-batch by sub-batch
 // (emit_tophits, capi_search.hip), and the pool of the kept hits' base pairs
-struct prb_tophits : prb::MergeTable {
-  int32_t n = 0;
+struct prb_tophits : prb::TopTable<prb_top_hit> {
   int32_t style = -1;              // opts->output_style of the merged pages (-1: none yet)
-  prb::DevBuf table;               // prb_top_hit[nq * n] (`rank` = the hit's place in its query's run on the device), then int32_t fill[nq]
   prb::DevBuf pool, pool2;         // the kept hits' pairs in table order (h.bp_offset indexes `pool`); the gather's target
   int64_t pool_pairs = 0;          // pairs in `pool`
   prb::DevBuf cnt, off, scanTmp;   // per slot (+ 1): pair counts, their exclusive scan
   std::vector<prb_top_hit> hits;   // prb_tophits_finish
   std::vector<int32_t> bp;
-  size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(prb_top_hit); }
-  int32_t *fill() const { return reinterpret_cast<int32_t *>(table.as<char>() + slots_bytes()); }
   void release() {
     for (prb::DevBuf *b : {&table, &pool, &pool2, &cnt, &off, &scanTmp}) b->release();
   }

@@ -27,10 +27,13 @@ struct PageHits {
   const int32_t *bp = nullptr;
   int64_t nbp = 0; // pairs
 };
-struct BatchView {
+// The queries of a batch, which every view of its results starts with.
+struct QueryView {
   size_t nq = 0;
   const std::string *names = nullptr; // [nq]
   const int32_t *qlen_unmasked = nullptr;
+};
+struct BatchView : QueryView {
   std::vector<PageHits> pages;
 };
 
@@ -53,20 +56,14 @@ struct PagePairs {
   const prb_pair_summary *r = nullptr;
   int64_t n = 0;
 };
-struct SummaryView {
-  size_t nq = 0;
-  const std::string *names = nullptr; // [nq]
-  const int32_t *qlen_unmasked = nullptr;
+struct SummaryView : QueryView {
   std::vector<PagePairs> pages;
 };
 int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
 // Lines of `ris -t -n N` (prb_topset_pairs): the same lines, for ranked records that carry their page, in the records'
 // order (ascending by query, then by rank), numbered from id0 on.
-struct TopView {
-  size_t nq = 0;
-  const std::string *names = nullptr; // [nq]
-  const int32_t *qlen_unmasked = nullptr;
+struct TopView : QueryView {
   const prb_top_pair *r = nullptr;
   int64_t n = 0;
 };
@@ -76,10 +73,7 @@ int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, in
 // position), numbered from id0 on:
 //   Id,qname,qlen,Position,Hits,Targets,MinE,dbname,dblen,(q0-qN:db0-dbN)
 // the energy and the best hit's base-pair field formatted as in the result lines (-s 0 form).
-struct ProfileView {
-  size_t nq = 0;
-  const std::string *names = nullptr; // [nq]
-  const int32_t *qlen_unmasked = nullptr;
+struct ProfileView : QueryView {
   const prb_profile_pos *r = nullptr;
   int64_t n = 0;
 };

@@ -29,6 +29,12 @@
 // lines (or, with -b, the normal binary records) of each query's N final hits of lowest interaction energy only, best
 // first: a table on the GPU (prb_search_page_tophits) takes every page of a batch and keeps those hits with their base
 // pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.
+//
+// How the file is laid out.  The switches -t -n -q -k -b have one table (kSwitchTable) that every refusal is generated
+// from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
+// join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
+// (the Gatherer), and close_run.  Both producers drive run_batches, whose search_batch returns a BatchResult - the one
+// owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread calls write_job.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -40,6 +46,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <cctype>
 #include <cstdint>
 #include <cstdio>
@@ -105,22 +112,45 @@ void usage() {
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
 }
 
-struct Args {
-  std::string in, out, db, tmp;
-  prb_ris_opts o;
-  bool binary = false;
-  bool summary = false; // -t
-  int top = 0;          // -n (0: not given)
-  bool top_given = false;
-  bool profile = false; // -q
-  int tophits = 0;      // -k (0: not given)
-  bool tophits_given = false;
-};
-
 [[noreturn]] void die(const std::string &msg) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(1);
 }
+
+// What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
+// `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits };
+
+// The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
+// what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
+// are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
+// first, a row's partners from the first to the last.
+enum Switch { kT, kN, kQ, kK, kB, kSwitches };
+constexpr unsigned bit(Switch s) { return 1u << s; }
+struct SwitchRow {
+  char letter;
+  const char *what;
+  unsigned not_with; // bits of Switch
+  int needs;         // a Switch, or -1
+  bool not_in_rank_mode;
+};
+constexpr SwitchRow kSwitchTable[kSwitches] = {
+    {'t', "per-pair summary lines", bit(kB), -1, true},
+    {'n', "the N best pairs per query", 0, kT, false},
+    {'q', "per-position profile lines", bit(kT) | bit(kN) | bit(kB), -1, true},
+    {'k', "the N best interaction sites per query", bit(kT) | bit(kN) | bit(kQ), -1, true},
+    {'b', "binary hit records", 0, -1, false},
+};
+std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
+
+struct Args {
+  std::string in, out, db, tmp;
+  prb_ris_opts o;
+  bool given[kSwitches] = {};
+  int top = 0, tophits = 0; // the values of -n and -k (-1: not a count)
+  OutputMode mode = OutputMode::kHits;
+  bool binary() const { return given[kB]; }
+};
 
 struct Worker {
   int device;
@@ -128,14 +158,30 @@ struct Worker {
   prb_db *db = nullptr;
 };
 
-// The hit sets of one batch (one per database page), waiting to be written.
+// The one place where what a search returned is freed.
+struct Free {
+  void operator()(prb_hitset *p) const { prb_hitset_free(p); }
+  void operator()(prb_pairset *p) const { prb_pairset_free(p); }
+  void operator()(prb_topset *p) const { prb_topset_free(p); }
+  void operator()(prb_profset *p) const { prb_profset_free(p); }
+  void operator()(prb_tophits *p) const { prb_tophits_free(p); }
+};
+template <class T> using Handle = std::unique_ptr<T, Free>;
+
+// What a searched batch left, by mode: hit sets or pair sets (one per database page), or the one table that every page
+// was merged into on the device.
+struct BatchResult {
+  OutputMode mode = OutputMode::kHits;
+  std::vector<Handle<prb_hitset>> pages;       // kHits
+  std::vector<Handle<prb_pairset>> pair_pages; // kSummary
+  Handle<prb_topset> top;                      // kTop
+  Handle<prb_profset> prof;                    // kProfile
+  Handle<prb_tophits> tophits;                 // kTopHits
+};
+
+// The result of one batch (in rank mode: of one round of batches, gathered), waiting to be written.
 struct BatchJob {
-  size_t index = 0, nq = 0;
-  std::vector<prb_hitset *> pages;
-  std::vector<prb_pairset *> pair_pages; // -t: the per-pair summaries instead
-  prb_topset *top = nullptr;             // -t -n: the batch's N best pairs per query instead
-  prb_profset *prof = nullptr;           // -q: the batch's per-position profile instead
-  prb_tophits *tophits = nullptr;        // -k: the batch's N best hits per query instead
+  BatchResult res;
   std::vector<std::string> names; // of its queries, in the order of their indices in the hit records
   std::vector<int32_t> qlen_unmasked;
 };
@@ -144,9 +190,6 @@ struct BatchJob {
 struct Prepared {
   prb_qbatch *qb = nullptr;
   std::vector<int32_t> qlen_unmasked;
-  prb_topset *top = nullptr; // -t -n: filled by search_batch, handed to the writer
-  prb_profset *prof = nullptr; // -q: likewise
-  prb_tophits *tophits = nullptr; // -k: likewise
 };
 
 // ---- binary hit file (little-endian, the layouts of include/priblast_hip.h) ----------------------
@@ -302,71 +345,6 @@ int txt_main(int argc, char **argv) {
   return 0;
 }
 
-// encode + suffix arrays + accessibilities of the queries `idx` under context c
-Prepared prepare_batch(prb_ctx *c, const std::vector<std::string> &seqs, const std::vector<size_t> &idx, int W, int delta,
-                       int repeat_flag, const prb_db *db, const prb_ris_opts *opts) {
-  std::string cat;
-  std::vector<int64_t> off(idx.size() + 1, 0);
-  for (size_t k = 0; k < idx.size(); k++) {
-    cat += seqs[idx[k]];
-    off[k + 1] = (int64_t)cat.size();
-  }
-  Prepared p;
-  if (prb_qbatch_create(c, (int32_t)idx.size(), cat.data(), off.data(), repeat_flag, &p.qb)) die(prb_last_error());
-  // the seed DFS against the first page needs no GPU: it runs on host threads beside the accessibilities (and,
-  // for a batch prepared ahead, beside the previous batch's search)
-  if (db && prb_qbatch_seed_search_begin(c, p.qb, db, 0, opts)) die(prb_last_error());
-  if (prb_qbatch_accessibility(c, p.qb, W, delta)) die(prb_last_error());
-  p.qlen_unmasked.resize(idx.size());
-  for (size_t q = 0; q < idx.size(); q++) p.qlen_unmasked[q] = prb_qbatch_length_unmasked(p.qb, (int32_t)q);
-  return p;
-}
-
-// the search stages of a prepared batch against every page; the hit sets (with -t: the pair sets) go to the writer
-void search_batch(Worker &w, const Args &a, Prepared &p, int npages, std::vector<prb_hitset *> &pages,
-                  std::vector<prb_pairset *> &pair_pages) {
-  if (a.top) { // -t -n: every page merged into one table on the device, then one copy
-    if (prb_topset_create(w.ctx, p.qb, a.top, &p.top)) die(prb_last_error());
-    for (int page = 0; page < npages; page++)
-      if (prb_search_page_top(w.ctx, p.qb, w.db, page, &a.o, p.top)) die(prb_last_error());
-    if (prb_topset_finish(w.ctx, p.top)) die(prb_last_error());
-    prb_qbatch_destroy(p.qb);
-    p.qb = nullptr;
-    return;
-  }
-  if (a.profile) { // -q: every page merged into one per-position table on the device, then one copy of the covered rows
-    if (prb_profset_create(w.ctx, p.qb, &p.prof)) die(prb_last_error());
-    for (int page = 0; page < npages; page++)
-      if (prb_search_page_profile(w.ctx, p.qb, w.db, page, &a.o, p.prof)) die(prb_last_error());
-    if (prb_profset_finish(w.ctx, p.prof)) die(prb_last_error());
-    prb_qbatch_destroy(p.qb);
-    p.qb = nullptr;
-    return;
-  }
-  if (a.tophits) { // -k: every page merged into one table of hits on the device, then one copy of records and pairs
-    if (prb_tophits_create(w.ctx, p.qb, a.tophits, &p.tophits)) die(prb_last_error());
-    for (int page = 0; page < npages; page++)
-      if (prb_search_page_tophits(w.ctx, p.qb, w.db, page, &a.o, p.tophits)) die(prb_last_error());
-    if (prb_tophits_finish(w.ctx, p.tophits)) die(prb_last_error());
-    prb_qbatch_destroy(p.qb);
-    p.qb = nullptr;
-    return;
-  }
-  for (int page = 0; page < npages; page++) {
-    if (a.summary) {
-      prb_pairset *ps = nullptr;
-      if (prb_search_page_summary(w.ctx, p.qb, w.db, page, &a.o, &ps)) die(prb_last_error());
-      pair_pages.push_back(ps);
-      continue;
-    }
-    prb_hitset *hs = nullptr;
-    if (prb_search_page(w.ctx, p.qb, w.db, page, &a.o, 3, &hs)) die(prb_last_error());
-    pages.push_back(hs);
-  }
-  prb_qbatch_destroy(p.qb);
-  p.qb = nullptr;
-}
-
 // The RCCL id of a multi-process run travels through files in the `-p` directory.  A file left behind by a run that
 // died must never be taken for this run's (ncclCommInitRank would wait for ever on a stale id), and file times say
 // nothing reliable about that, so the exchange is a handshake: every other rank writes a random nonce to
@@ -463,7 +441,54 @@ struct Rendezvous {
   }
 };
 
-int ris_main(int argc, char **argv) {
+// ---- the run: what the steps of ris_main fill in, one after the other, and the workers read --------
+struct Run {
+  Args a;
+  std::vector<std::string> names, seqs; // the queries
+  int world = 1, rank = 0;              // one process per GPU?  (torchrun / mpirun style environment)
+  bool rank_mode = false;
+  prb_comm *comm = nullptr;
+  std::vector<Worker> workers;
+  int repeat_flag = 0, W = 0, delta = 0, npages = 0; // of the database
+  std::vector<SeqTable> tabs;                        // per page
+  std::FILE *out = nullptr;
+  // the batch plan: batch b = the queries order[b * batch ..), nb batches, njobs jobs for the writer
+  std::vector<size_t> order;
+  size_t batch = 1, nb = 0, njobs = 0;
+  std::vector<size_t> batch_idx(size_t b) const {
+    return std::vector<size_t>(order.begin() + b * batch, order.begin() + std::min(seqs.size(), (b + 1) * batch));
+  }
+  void names_of(size_t b, std::vector<std::string> &dst) const {
+    for (size_t i : batch_idx(b)) dst.push_back(names[i]);
+  }
+};
+
+// the value of -n / -k: a count, or -1
+int parse_count(const char *arg) {
+  char *end = nullptr;
+  const long v = std::strtol(arg, &end, 10);
+  return end != arg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
+}
+
+// the refusals that need the command line only, from the switch table
+void check_switches(const Args &a) {
+  for (int s = kSwitches - 1; s >= 0; s--) {
+    if (!a.given[s]) continue;
+    for (int p = 0; p < kSwitches; p++)
+      if (a.given[p] && (kSwitchTable[s].not_with & (1u << p))) die("Error: " + described(s) + " can't be combined with " + described(p));
+    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need]) die("Error: " + described(s) + " needs " + described(need));
+  }
+  for (Switch s : {kK, kN})
+    if (const int v = s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
+      die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
+}
+
+OutputMode output_mode(const Args &a) {
+  return a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
+         : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
+}
+
+Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
@@ -481,23 +506,11 @@ int ris_main(int argc, char **argv) {
     case 'y': a.o.drop_out_wo_gap = std::atoi(optarg); break;
     case 'm': a.o.min_helix_length = std::atoi(optarg); break;
     case 'p': a.tmp = optarg; break;
-    case 'b': a.binary = true; break;
-    case 't': a.summary = true; break;
-    case 'q': a.profile = true; break;
-    case 'n': {
-      char *end = nullptr;
-      const long v = std::strtol(optarg, &end, 10);
-      a.top_given = true;
-      a.top = end != optarg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
-      break;
-    }
-    case 'k': {
-      char *end = nullptr;
-      const long v = std::strtol(optarg, &end, 10);
-      a.tophits_given = true;
-      a.tophits = end != optarg && *end == '\0' && v >= 0 && v <= 1 << 20 ? (int)v : -1;
-      break;
-    }
+    case 'b': a.given[kB] = true; break;
+    case 't': a.given[kT] = true; break;
+    case 'q': a.given[kQ] = true; break;
+    case 'n': a.given[kN] = true, a.top = parse_count(optarg); break;
+    case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -505,20 +518,20 @@ int ris_main(int argc, char **argv) {
     default: die("Error: invalid argument");
     }
   }
-  if (a.tophits_given && a.summary) die("Error: -k (the N best interaction sites per query) can't be combined with -t (per-pair summary lines)");
-  if (a.tophits_given && a.top_given) die("Error: -k (the N best interaction sites per query) can't be combined with -n (the N best pairs per query)");
-  if (a.tophits_given && a.profile) die("Error: -k (the N best interaction sites per query) can't be combined with -q (per-position profile lines)");
-  if (a.tophits_given && (a.tophits < 1 || a.tophits > 1024)) die("Error: -k needs an integer between 1 and 1024 (this build's limit)");
-  if (a.profile && a.summary) die("Error: -q (per-position profile lines) can't be combined with -t (per-pair summary lines)");
-  if (a.profile && a.top_given) die("Error: -q (per-position profile lines) can't be combined with -n (the N best pairs per query)");
-  if (a.profile && a.binary) die("Error: -q (per-position profile lines) can't be combined with -b (binary hit records)");
-  if (a.summary && a.binary) die("Error: -t (per-pair summary lines) can't be combined with -b (binary hit records)");
-  if (a.top_given && !a.summary) die("Error: -n (the N best pairs per query) needs -t (per-pair summary lines)");
-  if (a.top_given && (a.top < 1 || a.top > 1024)) die("Error: -n needs an integer between 1 and 1024 (this build's limit)");
-  std::vector<std::string> names, seqs;
-  std::string err = prb::read_fasta(a.in, names, seqs);
-  if (!err.empty()) die(err);
+  check_switches(a);
+  a.mode = output_mode(a);
+  return a;
+}
 
+int env_int(const char *a, const char *b, int dflt) {
+  const char *e = std::getenv(a);
+  if (!e && b) e = std::getenv(b);
+  return e ? std::atoi(e) : dflt;
+}
+
+// WORLD_SIZE / RANK, the refusals of rank mode and its share of the CPUs; returns the devices of this process' workers
+std::vector<int> rank_setup(Run &r) {
+  const Args &a = r.a;
   std::vector<int> devices;
   if (const char *env = std::getenv("PRB_DEVICES")) {
     for (const char *p = env; *p;) {
@@ -527,135 +540,321 @@ int ris_main(int argc, char **argv) {
       if (*p == ',') p++;
     }
   }
-  // one process per GPU?  (torchrun / mpirun style environment)
-  auto env_int = [](const char *a, const char *b, int dflt) {
-    const char *e = std::getenv(a);
-    if (!e && b) e = std::getenv(b);
-    return e ? std::atoi(e) : dflt;
-  };
-  const int world = std::max(1, env_int("WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", 1));
-  const int rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
-  const bool rank_mode = world > 1 || std::getenv("PRB_FORCE_COMM") != nullptr;
-  if (rank < 0 || rank >= world) die("Error: RANK outside WORLD_SIZE");
-  if (rank_mode && a.tophits)
-    die("Error: -k (the N best interaction sites per query) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
-  if (rank_mode && a.profile)
-    die("Error: -q (per-position profile lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
-  if (rank_mode && a.summary)
-    die("Error: -t (per-pair summary lines) is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
-  if (rank_mode) {
-    const int local = env_int("LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", rank);
+  r.world = std::max(1, env_int("WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", 1));
+  r.rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
+  r.rank_mode = r.world > 1 || std::getenv("PRB_FORCE_COMM") != nullptr;
+  if (r.rank < 0 || r.rank >= r.world) die("Error: RANK outside WORLD_SIZE");
+  for (int s = kSwitches - 1; s >= 0 && r.rank_mode; s--)
+    if (a.given[s] && kSwitchTable[s].not_in_rank_mode)
+      die("Error: " + described(s) + " is not supported with one process per GPU (WORLD_SIZE > 1); use PRB_DEVICES=0,1,.. in one process");
+  if (r.rank_mode) {
+    const int local = env_int("LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", r.rank);
     const int dev = devices.empty() ? local : devices[(size_t)local % devices.size()];
     devices.assign(1, dev);
     // The ranks of a node share its CPUs: every rank runs suffix arrays + a seed DFS, rank 0 alone writes the lines of all
     // of them.  Unless the user says otherwise: half of the CPUs split over the ranks for the former, the other half for
     // rank 0's formatting (WORLD_SIZE counts ranks on other nodes too - then this errs on the small side).
     const int budget = prb_cpu_budget();
-    if (world > 1) {
-      setenv("PRB_HOST_THREADS", std::to_string(std::max(2, std::min(32, budget / (2 * world)))).c_str(), 0);
-      if (rank == 0) setenv("PRB_FORMAT_THREADS", std::to_string(std::max(2, std::min(32, budget / 2))).c_str(), 0);
+    if (r.world > 1) {
+      setenv("PRB_HOST_THREADS", std::to_string(std::max(2, std::min(32, budget / (2 * r.world)))).c_str(), 0);
+      if (r.rank == 0) setenv("PRB_FORMAT_THREADS", std::to_string(std::max(2, std::min(32, budget / 2))).c_str(), 0);
     }
   }
   if (devices.empty()) devices.push_back(0);
-  std::vector<Worker> workers(devices.size());
-  int hash_size = 0, repeat_flag = 0, W = 0, delta = 0, npages = 0;
+  return devices;
+}
+
+// a worker per device: its context, a second one for the batch prepared ahead, the database
+void open_workers(Run &r, const std::vector<int> &devices) {
+  r.workers.resize(devices.size());
   const bool prefetch = !std::getenv("PRB_NO_PREFETCH");
   for (size_t k = 0; k < devices.size(); k++) {
-    workers[k].device = devices[k];
-    if (prb_ctx_create(devices[k], nullptr, &workers[k].ctx)) die(std::string("Error: ") + prb_last_error());
-    if (prefetch && prb_ctx_create(devices[k], nullptr, &workers[k].prep_ctx)) die(std::string("Error: ") + prb_last_error());
-    if (prb_db_open(workers[k].ctx, a.db.c_str(), &workers[k].db)) die(prb_last_error());
+    Worker &w = r.workers[k];
+    w.device = devices[k];
+    if (prb_ctx_create(devices[k], nullptr, &w.ctx)) die(std::string("Error: ") + prb_last_error());
+    if (prefetch && prb_ctx_create(devices[k], nullptr, &w.prep_ctx)) die(std::string("Error: ") + prb_last_error());
+    if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
   }
-  prb_comm *comm = nullptr;
-  if (rank_mode) {
-    // one file name per launch where the launcher names the launch (torchrun: TORCHELASTIC_RUN_ID; Open MPI: its job id;
-    // or PRB_RUN_ID), else per MASTER_PORT
-    std::string token;
-    for (const char *k : {"PRB_RUN_ID", "TORCHELASTIC_RUN_ID", "OMPI_MCA_ess_base_jobid", "PMIX_NAMESPACE", "MASTER_PORT"})
-      if (const char *e = std::getenv(k); e && *e && std::strcmp(e, "none") != 0) {
-        token = e;
-        break;
-      }
-    for (char &ch : token)
-      if (!std::isalnum((unsigned char)ch) && ch != '-' && ch != '_') ch = '_';
-    const std::string path = (a.tmp.empty() ? a.out : a.tmp + "/prb") + ".rccl_id." + (token.empty() ? "0" : token);
-    Rendezvous rdv;
-    rdv.begin(path, world, rank);
-    if (prb_comm_create(workers[0].ctx, world, rank, rdv.id, &comm)) die(std::string("Error: ") + prb_last_error());
-    rdv.end();
-  }
-  const bool writer_rank = rank == 0;
-  prb_db_info(workers[0].db, &hash_size, &repeat_flag, &W, &delta, &npages);
+}
 
-  std::vector<SeqTable> tabs((size_t)npages);
-  for (int p = 0; p < npages; p++) {
+// the communicator of the ranks, its id exchanged through the rendezvous file
+prb_comm *join_ranks(const Run &r) {
+  // one file name per launch where the launcher names the launch (torchrun: TORCHELASTIC_RUN_ID; Open MPI: its job id;
+  // or PRB_RUN_ID), else per MASTER_PORT
+  std::string token;
+  for (const char *k : {"PRB_RUN_ID", "TORCHELASTIC_RUN_ID", "OMPI_MCA_ess_base_jobid", "PMIX_NAMESPACE", "MASTER_PORT"})
+    if (const char *e = std::getenv(k); e && *e && std::strcmp(e, "none") != 0) {
+      token = e;
+      break;
+    }
+  for (char &ch : token)
+    if (!std::isalnum((unsigned char)ch) && ch != '-' && ch != '_') ch = '_';
+  const std::string path = (r.a.tmp.empty() ? r.a.out : r.a.tmp + "/prb") + ".rccl_id." + (token.empty() ? "0" : token);
+  Rendezvous rdv;
+  rdv.begin(path, r.world, r.rank);
+  prb_comm *comm = nullptr;
+  if (prb_comm_create(r.workers[0].ctx, r.world, r.rank, rdv.id, &comm)) die(std::string("Error: ") + prb_last_error());
+  rdv.end();
+  return comm;
+}
+
+// what the output needs to know about the database: its parameters and the sequences of every page
+void read_seq_tables(Run &r) {
+  const prb_db *db = r.workers[0].db;
+  int hash_size = 0;
+  prb_db_info(db, &hash_size, &r.repeat_flag, &r.W, &r.delta, &r.npages);
+  r.tabs.resize((size_t)r.npages);
+  for (int p = 0; p < r.npages; p++) {
     int32_t nseq = 0;
     int64_t nchars = 0;
-    prb_db_page_info(workers[0].db, p, &nseq, &nchars);
-    SeqTable &t = tabs[p];
+    prb_db_page_info(db, p, &nseq, &nchars);
+    SeqTable &t = r.tabs[p];
     t.names.resize(nseq);
     t.len.resize(nseq);
     t.len_unmasked.resize(nseq);
     t.start_pos.resize(nseq);
     for (int32_t i = 0; i < nseq; i++) {
-      t.names[i] = prb_db_seq_name(workers[0].db, p, i);
-      prb_db_seq_lengths(workers[0].db, p, i, &t.len[i], &t.len_unmasked[i], &t.start_pos[i]);
+      t.names[i] = prb_db_seq_name(db, p, i);
+      prb_db_seq_lengths(db, p, i, &t.len[i], &t.len_unmasked[i], &t.start_pos[i]);
     }
   }
+}
 
-  std::FILE *out = std::fopen(writer_rank ? a.out.c_str() : "/dev/null", a.binary ? "wb" : "w");
-  if (!out) die("Error: can't open output_file: " + a.out);
-  // MergeOutput header, rna_interaction_search.cpp:445-463
+// MergeOutput header, rna_interaction_search.cpp:445-463
+std::string header_text(const Run &r) {
+  const Args &a = r.a;
   std::string header = "RIblast ris result\n";
-  {
-    char buf[256];
-    header += "input:" + a.in + ",database:" + a.db;
-    std::snprintf(buf, sizeof buf,
-                  ",RepeatFlag:%d,MaximalSpan:%d,MinAccessibleLength:%d,MaxSeedLength:%d,"
-                  "InteractionEnergyThreshold:%g,HybridEnergyThreshold:%g,FinalThreshold:%g,DropOutLengthWoGap:%d,"
-                  "DropOutLengthWGap:%d\n",
-                  repeat_flag, W, delta, a.o.max_seed_length, a.o.interaction_threshold, a.o.hybrid_threshold,
-                  a.o.final_threshold, a.o.drop_out_wo_gap, a.o.drop_out_w_gap);
-    header += buf;
+  char buf[256];
+  header += "input:" + a.in + ",database:" + a.db;
+  std::snprintf(buf, sizeof buf,
+                ",RepeatFlag:%d,MaximalSpan:%d,MinAccessibleLength:%d,MaxSeedLength:%d,"
+                "InteractionEnergyThreshold:%g,HybridEnergyThreshold:%g,FinalThreshold:%g,DropOutLengthWoGap:%d,"
+                "DropOutLengthWGap:%d\n",
+                r.repeat_flag, r.W, r.delta, a.o.max_seed_length, a.o.interaction_threshold, a.o.hybrid_threshold,
+                a.o.final_threshold, a.o.drop_out_wo_gap, a.o.drop_out_w_gap);
+  header += buf;
+  switch (a.mode) {
+  case OutputMode::kProfile:
+    return header + "Id,Query name,Query Length,Position,Hits,Targets,Minimum Interaction Energy,Target name,Target Length,BasePair\n";
+  case OutputMode::kSummary:
+  case OutputMode::kTop:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
+  case OutputMode::kHits:
+  case OutputMode::kTopHits: break;
   }
-  if (a.profile)
-    header += "Id,Query name,Query Length,Position,Hits,Targets,Minimum Interaction Energy,Target name,Target Length,BasePair\n";
-  else if (a.summary)
-    header += "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
-              "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
-  else
-    header += "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
-              "Interaction Energy, BasePair\n";
-  if (a.binary) write_binary_head(out, a.o.output_style, header, tabs);
-  else put(out, header.data(), header.size());
-  if (std::fflush(out)) die("Error: can't write the output file");
-  LineSink sink; // text lines go straight to the descriptor (nothing else is written through `out` meanwhile)
-  sink.fd = fileno(out);
+  return header + "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
+                  "Interaction Energy, BasePair\n";
+}
 
+// the output file (rank 0's; the other ranks write nowhere) with its header
+void open_output(Run &r) {
+  r.out = std::fopen(r.rank == 0 ? r.a.out.c_str() : "/dev/null", r.a.binary() ? "wb" : "w");
+  if (!r.out) die("Error: can't open output_file: " + r.a.out);
+  const std::string header = header_text(r);
+  if (r.a.binary()) write_binary_head(r.out, r.a.o.output_style, header, r.tabs);
+  else put(r.out, header.data(), header.size());
+  if (std::fflush(r.out)) die("Error: can't write the output file");
+}
+
+void plan_batches(Run &r) {
   // Queries per batch: PRB_BATCH, else large batches (full launches of the small-list kernels) but at least four per
   // worker / rank, so that every GPU has work and the last round is short (the reference deals single queries)
   const char *benv = std::getenv("PRB_BATCH");
-  const size_t consumers = rank_mode ? (size_t)world : devices.size();
-  const size_t batch = benv ? (size_t)std::max(1, std::atoi(benv))
-                            : std::max<size_t>(16, std::min<size_t>(2048, (seqs.size() + 4 * consumers - 1) / (4 * consumers)));
+  const size_t consumers = r.rank_mode ? (size_t)r.world : r.workers.size(), nseq = r.seqs.size();
+  r.batch = benv ? (size_t)std::max(1, std::atoi(benv))
+                 : std::max<size_t>(16, std::min<size_t>(2048, (nseq + 4 * consumers - 1) / (4 * consumers)));
   // longest first (stable: equal lengths keep their FASTA order), then batches in that order
-  std::vector<size_t> order(seqs.size());
-  std::iota(order.begin(), order.end(), (size_t)0);
-  std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return seqs[x].size() > seqs[y].size(); });
-  const size_t nb = (seqs.size() + batch - 1) / batch;
-  auto batch_idx = [&](size_t b) { return std::vector<size_t>(order.begin() + b * batch, order.begin() + std::min(seqs.size(), (b + 1) * batch)); };
-  // The writer thread turns finished jobs into text in job order while the GPUs already work on the
-  // next ones (a bounded number of finished jobs wait for it).  A job is a batch - or, with one process
-  // per GPU, a round of WORLD_SIZE batches gathered on rank 0.
-  const size_t njobs = rank_mode ? (nb + world - 1) / world : nb;
+  r.order.resize(nseq);
+  std::iota(r.order.begin(), r.order.end(), (size_t)0);
+  std::stable_sort(r.order.begin(), r.order.end(), [&](size_t x, size_t y) { return r.seqs[x].size() > r.seqs[y].size(); });
+  r.nb = (nseq + r.batch - 1) / r.batch;
+  // a job of the writer is a batch - or, with one process per GPU, a round of WORLD_SIZE batches gathered on rank 0
+  r.njobs = r.rank_mode ? (r.nb + r.world - 1) / r.world : r.nb;
+}
+
+// encode + suffix arrays + accessibilities of batch b under context c
+Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b) {
+  const std::vector<size_t> idx = r.batch_idx(b);
+  std::string cat;
+  std::vector<int64_t> off(idx.size() + 1, 0);
+  for (size_t k = 0; k < idx.size(); k++) {
+    cat += r.seqs[idx[k]];
+    off[k + 1] = (int64_t)cat.size();
+  }
+  Prepared p;
+  if (prb_qbatch_create(c, (int32_t)idx.size(), cat.data(), off.data(), r.repeat_flag, &p.qb)) die(prb_last_error());
+  // the seed DFS against the first page needs no GPU: it runs on host threads beside the accessibilities (and,
+  // for a batch prepared ahead, beside the previous batch's search)
+  if (db && prb_qbatch_seed_search_begin(c, p.qb, db, 0, &r.a.o)) die(prb_last_error());
+  if (prb_qbatch_accessibility(c, p.qb, r.W, r.delta)) die(prb_last_error());
+  p.qlen_unmasked.resize(idx.size());
+  for (size_t q = 0; q < idx.size(); q++) p.qlen_unmasked[q] = prb_qbatch_length_unmasked(p.qb, (int32_t)q);
+  return p;
+}
+
+// -t -n, -q, -k: a table made by `create`, every page searched and merged into it on the device by `merge`, then one copy
+// of its records to the host by `finish`
+template <class T, class Create>
+Handle<T> merged_table(const Run &r, Worker &w, prb_qbatch *qb, Create create,
+                       int (*merge)(prb_ctx *, prb_qbatch *, prb_db *, int32_t, const prb_ris_opts *, T *), int (*finish)(prb_ctx *, T *)) {
+  T *t = nullptr;
+  if (create(&t)) die(prb_last_error());
+  Handle<T> table(t);
+  for (int page = 0; page < r.npages; page++)
+    if (merge(w.ctx, qb, w.db, page, &r.a.o, t)) die(prb_last_error());
+  if (finish(w.ctx, t)) die(prb_last_error());
+  return table;
+}
+
+// the search stages of a prepared batch against every page
+BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
+  const Args &a = r.a;
+  BatchResult res;
+  res.mode = a.mode;
+  switch (a.mode) {
+  case OutputMode::kTop:
+    res.top = merged_table<prb_topset>(r, w, p.qb, [&](prb_topset **t) { return prb_topset_create(w.ctx, p.qb, a.top, t); },
+                                       prb_search_page_top, prb_topset_finish);
+    break;
+  case OutputMode::kProfile:
+    res.prof = merged_table<prb_profset>(r, w, p.qb, [&](prb_profset **t) { return prb_profset_create(w.ctx, p.qb, t); },
+                                         prb_search_page_profile, prb_profset_finish);
+    break;
+  case OutputMode::kTopHits:
+    res.tophits = merged_table<prb_tophits>(r, w, p.qb, [&](prb_tophits **t) { return prb_tophits_create(w.ctx, p.qb, a.tophits, t); },
+                                            prb_search_page_tophits, prb_tophits_finish);
+    break;
+  case OutputMode::kSummary:
+    for (int page = 0; page < r.npages; page++) {
+      prb_pairset *ps = nullptr;
+      if (prb_search_page_summary(w.ctx, p.qb, w.db, page, &a.o, &ps)) die(prb_last_error());
+      res.pair_pages.emplace_back(ps);
+    }
+    break;
+  case OutputMode::kHits:
+    for (int page = 0; page < r.npages; page++) {
+      prb_hitset *hs = nullptr;
+      if (prb_search_page(w.ctx, p.qb, w.db, page, &a.o, 3, &hs)) die(prb_last_error());
+      res.pages.emplace_back(hs);
+    }
+    break;
+  }
+  prb_qbatch_destroy(p.qb);
+  p.qb = nullptr;
+  return res;
+}
+
+// ---- the writer ----------------------------------------------------------------------------------
+void set_queries(prb::QueryView &v, const BatchJob &job) {
+  v.nq = job.names.size();
+  v.names = job.names.data();
+  v.qlen_unmasked = job.qlen_unmasked.data();
+}
+int64_t written_or_die(int64_t id) {
+  if (id < 0) die("Error: can't write the output file");
+  return id;
+}
+// the hits of a batch as binary records or as result lines; returns the next id
+int64_t write_hits(const Run &r, const BatchView &v, int64_t id, LineSink &sink) {
+  if (r.a.binary()) return id + write_binary_batch(v, r.out);
+  return written_or_die(prb::format_batch(v, r.tabs, r.a.o.output_style, id, sink, prb::format_threads()));
+}
+
+// The kept hits come by query, then by rank, the pages mixed; the writers take hits page by page, ascending by
+// query, and write a query's hits of one page in the order given.  So the records are cut where a query's next
+// hit lies in a lower page, and every piece goes out as a batch of its own (one piece for a database of one page).
+int64_t write_tophits(const Run &r, const BatchJob &job, int64_t id, LineSink &sink) {
+  const int npages = r.npages;
+  const prb_top_hit *rec = prb_tophits_hits(job.res.tophits.get());
+  const int64_t n = prb_tophits_size(job.res.tophits.get());
+  int64_t nbp = 0;
+  const int32_t *bp = prb_tophits_basepairs(job.res.tophits.get(), &nbp);
+  std::vector<std::vector<prb_hit>> hits((size_t)npages);
+  std::vector<std::vector<int32_t>> pairs((size_t)npages);
+  for (int64_t i0 = 0; i0 < n;) {
+    int64_t i1 = i0 + 1;
+    while (i1 < n && !(rec[i1].h.query == rec[i1 - 1].h.query && rec[i1].page < rec[i1 - 1].page)) i1++;
+    const int32_t qa = rec[i0].h.query, qz = rec[i1 - 1].h.query;
+    for (auto &h : hits) h.clear();
+    for (auto &p : pairs) p.clear();
+    for (int64_t i = i0; i < i1; i++) {
+      prb_hit x = rec[i].h;
+      if (rec[i].page < 0 || rec[i].page >= npages || x.bp_count < 0 || x.bp_offset < 0 || x.bp_offset + x.bp_count > nbp)
+        die("Error: bad record in the table of the best hits");
+      std::vector<int32_t> &pp = pairs[(size_t)rec[i].page];
+      const int64_t at = (int64_t)pp.size() / 2;
+      pp.insert(pp.end(), bp + 2 * x.bp_offset, bp + 2 * (x.bp_offset + x.bp_count));
+      x.bp_offset = at;
+      x.query -= qa;
+      hits[(size_t)rec[i].page].push_back(x);
+    }
+    BatchView v;
+    v.nq = (size_t)(qz - qa + 1);
+    v.names = job.names.data() + qa;
+    v.qlen_unmasked = job.qlen_unmasked.data() + qa;
+    for (size_t p = 0; p < hits.size(); p++)
+      v.pages.push_back(PageHits{hits[p].data(), (int64_t)hits[p].size(), pairs[p].data(), (int64_t)pairs[p].size() / 2});
+    id = write_hits(r, v, id, sink);
+    i0 = i1;
+  }
+  return id;
+}
+
+// one job to the output, numbered from `id` on; returns the next id.  The job's handles are freed on return.
+int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
+  const int threads = prb::format_threads();
+  switch (job.res.mode) {
+  case OutputMode::kProfile: {
+    prb::ProfileView v;
+    set_queries(v, job);
+    v.r = prb_profset_rows(job.res.prof.get());
+    v.n = prb_profset_size(job.res.prof.get());
+    return written_or_die(prb::format_profile_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kTopHits: return write_tophits(r, job, id, sink);
+  case OutputMode::kTop: {
+    prb::TopView v;
+    set_queries(v, job);
+    v.r = prb_topset_pairs(job.res.top.get());
+    v.n = prb_topset_size(job.res.top.get());
+    return written_or_die(prb::format_top_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kSummary: {
+    prb::SummaryView v;
+    set_queries(v, job);
+    for (const auto &ps : job.res.pair_pages) v.pages.push_back(prb::PagePairs{prb_pairset_pairs(ps.get()), prb_pairset_size(ps.get())});
+    return written_or_die(prb::format_summary_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kHits: break;
+  }
+  BatchView v;
+  set_queries(v, job);
+  for (const auto &hs : job.res.pages) {
+    PageHits ph{prb_hitset_hits(hs.get()), prb_hitset_size(hs.get())};
+    ph.bp = prb_hitset_basepairs(hs.get(), &ph.nbp);
+    v.pages.push_back(ph);
+  }
+  return write_hits(r, v, id, sink);
+}
+
+// The writer thread turns finished jobs into text in job order while the GPUs already work on the
+// next ones (a bounded number of finished jobs wait for it: wait_room).
+struct Writer {
+  const Run &r;
   std::mutex mu;
   std::condition_variable cv;
   std::map<size_t, BatchJob> done;
   size_t written = 0;
   int64_t total_hits = 0;
-  std::thread writer([&] {
+  std::thread th;
+
+  explicit Writer(const Run &run) : r(run), th([this] { loop(); }) {}
+  void loop() {
+    LineSink sink; // text lines go straight to the descriptor (nothing else is written through `out` meanwhile)
+    sink.fd = fileno(r.out);
     int64_t id = 0;
-    for (size_t b = 0; b < njobs && writer_rank; b++) {
+    for (size_t b = 0; b < r.njobs && r.rank == 0; b++) {
       BatchJob job;
       {
         std::unique_lock<std::mutex> lk(mu);
@@ -663,122 +862,7 @@ int ris_main(int argc, char **argv) {
         job = std::move(done[b]);
         done.erase(b);
       }
-      if (job.prof) {
-        prb::ProfileView pv;
-        pv.nq = job.nq;
-        pv.names = job.names.data();
-        pv.qlen_unmasked = job.qlen_unmasked.data();
-        pv.r = prb_profset_rows(job.prof);
-        pv.n = prb_profset_size(job.prof);
-        if ((id = prb::format_profile_batch(pv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
-        prb_profset_free(job.prof);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          written = b + 1;
-        }
-        cv.notify_all();
-        continue;
-      }
-      if (job.tophits) {
-        // The kept hits come by query, then by rank, the pages mixed; the writers take hits page by page, ascending by
-        // query, and write a query's hits of one page in the order given.  So the records are cut where a query's next
-        // hit lies in a lower page, and every piece goes out as a batch of its own (one piece for a database of one page).
-        const prb_top_hit *r = prb_tophits_hits(job.tophits);
-        const int64_t n = prb_tophits_size(job.tophits);
-        int64_t nbp = 0;
-        const int32_t *bp = prb_tophits_basepairs(job.tophits, &nbp);
-        std::vector<std::vector<prb_hit>> hits((size_t)npages);
-        std::vector<std::vector<int32_t>> pairs((size_t)npages);
-        for (int64_t i0 = 0; i0 < n;) {
-          int64_t i1 = i0 + 1;
-          while (i1 < n && !(r[i1].h.query == r[i1 - 1].h.query && r[i1].page < r[i1 - 1].page)) i1++;
-          const int32_t qa = r[i0].h.query, qz = r[i1 - 1].h.query;
-          for (int p = 0; p < npages; p++) {
-            hits[(size_t)p].clear();
-            pairs[(size_t)p].clear();
-          }
-          for (int64_t i = i0; i < i1; i++) {
-            prb_hit x = r[i].h;
-            if (r[i].page < 0 || r[i].page >= npages || x.bp_count < 0 || x.bp_offset < 0 || x.bp_offset + x.bp_count > nbp)
-              die("Error: bad record in the table of the best hits");
-            std::vector<int32_t> &pp = pairs[(size_t)r[i].page];
-            const int64_t at = (int64_t)pp.size() / 2;
-            pp.insert(pp.end(), bp + 2 * x.bp_offset, bp + 2 * (x.bp_offset + x.bp_count));
-            x.bp_offset = at;
-            x.query -= qa;
-            hits[(size_t)r[i].page].push_back(x);
-          }
-          BatchView v;
-          v.nq = (size_t)(qz - qa + 1);
-          v.names = job.names.data() + qa;
-          v.qlen_unmasked = job.qlen_unmasked.data() + qa;
-          for (int p = 0; p < npages; p++) {
-            PageHits ph;
-            ph.n = (int64_t)hits[(size_t)p].size();
-            ph.h = hits[(size_t)p].data();
-            ph.bp = pairs[(size_t)p].data();
-            ph.nbp = (int64_t)pairs[(size_t)p].size() / 2;
-            v.pages.push_back(ph);
-          }
-          if (a.binary) id += write_binary_batch(v, out);
-          else if ((id = prb::format_batch(v, tabs, a.o.output_style, id, sink, prb::format_threads())) < 0)
-            die("Error: can't write the output file");
-          i0 = i1;
-        }
-        prb_tophits_free(job.tophits);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          written = b + 1;
-        }
-        cv.notify_all();
-        continue;
-      }
-      if (job.top) {
-        prb::TopView tv;
-        tv.nq = job.nq;
-        tv.names = job.names.data();
-        tv.qlen_unmasked = job.qlen_unmasked.data();
-        tv.r = prb_topset_pairs(job.top);
-        tv.n = prb_topset_size(job.top);
-        if ((id = prb::format_top_batch(tv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
-        prb_topset_free(job.top);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          written = b + 1;
-        }
-        cv.notify_all();
-        continue;
-      }
-      if (a.summary) {
-        prb::SummaryView sv;
-        sv.nq = job.nq;
-        sv.names = job.names.data();
-        sv.qlen_unmasked = job.qlen_unmasked.data();
-        for (prb_pairset *ps : job.pair_pages) sv.pages.push_back(prb::PagePairs{prb_pairset_pairs(ps), prb_pairset_size(ps)});
-        if ((id = prb::format_summary_batch(sv, tabs, id, sink, prb::format_threads())) < 0) die("Error: can't write the output file");
-        for (prb_pairset *ps : job.pair_pages) prb_pairset_free(ps);
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          written = b + 1;
-        }
-        cv.notify_all();
-        continue;
-      }
-      BatchView v;
-      v.nq = job.nq;
-      v.names = job.names.data();
-      v.qlen_unmasked = job.qlen_unmasked.data();
-      for (prb_hitset *hs : job.pages) {
-        PageHits ph;
-        ph.n = prb_hitset_size(hs);
-        ph.h = prb_hitset_hits(hs);
-        ph.bp = prb_hitset_basepairs(hs, &ph.nbp);
-        v.pages.push_back(ph);
-      }
-      if (a.binary) id += write_binary_batch(v, out);
-      else if ((id = prb::format_batch(v, tabs, a.o.output_style, id, sink, prb::format_threads())) < 0)
-        die("Error: can't write the output file");
-      for (prb_hitset *hs : job.pages) prb_hitset_free(hs);
+      id = write_job(r, std::move(job), id, sink);
       {
         std::lock_guard<std::mutex> lk(mu);
         written = b + 1;
@@ -786,173 +870,196 @@ int ris_main(int argc, char **argv) {
       cv.notify_all();
     }
     total_hits = id;
-  });
-  auto submit = [&](size_t index, BatchJob &&job) {
+  }
+  // blocks while job `index` is `ahead` jobs or more past the last one written: bounds the results held in memory
+  void wait_room(size_t index, size_t ahead) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return index < written + ahead; });
+  }
+  void submit(size_t index, BatchJob &&job) {
     {
       std::lock_guard<std::mutex> lk(mu);
       done[index] = std::move(job);
     }
     cv.notify_all();
-  };
-  auto names_of = [&](const std::vector<size_t> &idx, std::vector<std::string> &dst) {
-    for (size_t i : idx) dst.push_back(names[i]);
-  };
-  // A worker: its batches one after the other; the accessibilities of the next one are computed by a
-  // helper thread under the worker's second context while this one is searched.
-  using Finish = std::function<void(size_t, Prepared *, std::vector<prb_hitset *> &, std::vector<prb_pairset *> &)>;
-  auto work = [&](Worker &w, const std::function<bool(size_t &)> &next_batch, const Finish &finish) {
-    size_t b = 0, bn = 0;
-    bool have = next_batch(b);
-    Prepared cur;
-    if (have) cur = prepare_batch(w.prep_ctx ? w.prep_ctx : w.ctx, seqs, batch_idx(b), W, delta, repeat_flag, w.db, &a.o);
-    while (have) {
-      const bool more = next_batch(bn);
-      Prepared nxt;
-      std::thread helper;
-      if (more && w.prep_ctx) helper = std::thread([&] { nxt = prepare_batch(w.prep_ctx, seqs, batch_idx(bn), W, delta, repeat_flag, w.db, &a.o); });
-      std::vector<prb_hitset *> pages;
-      std::vector<prb_pairset *> pair_pages;
-      search_batch(w, a, cur, npages, pages, pair_pages);
-      finish(b, &cur, pages, pair_pages);
-      if (helper.joinable()) helper.join();
-      else if (more) nxt = prepare_batch(w.ctx, seqs, batch_idx(bn), W, delta, repeat_flag, w.db, &a.o);
-      cur = std::move(nxt);
-      b = bn;
-      have = more;
-    }
-  };
-  if (!rank_mode) {
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> threads;
-    for (auto &w : workers)
-      threads.emplace_back([&, pw = &w] {
-        work(*pw,
-             [&](size_t &b) {
-               b = next.fetch_add(1);
-               return b < nb;
-             },
-             [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages, std::vector<prb_pairset *> &pair_pages) {
-               {
-                 std::unique_lock<std::mutex> lk(mu); // bound the hit sets held in memory
-                 cv.wait(lk, [&] { return b < written + 2 * workers.size() + 1; });
-               }
-               BatchJob job;
-               job.index = b;
-               job.pages = pages;
-               job.pair_pages = pair_pages;
-               job.top = p->top;
-               p->top = nullptr;
-               job.prof = p->prof;
-               p->prof = nullptr;
-               job.tophits = p->tophits;
-               p->tophits = nullptr;
-               job.qlen_unmasked = p->qlen_unmasked;
-               names_of(batch_idx(b), job.names);
-               job.nq = job.names.size();
-               submit(b, std::move(job));
-             });
+  }
+  int64_t join() { // -> the hits written
+    th.join();
+    return total_hits;
+  }
+};
+
+// ---- the producers -------------------------------------------------------------------------------
+// A worker: its batches one after the other, as next_batch names them; the accessibilities of the next one are computed
+// by a helper thread under the worker's second context while this one is searched.
+using Finish = std::function<void(size_t, const Prepared &, BatchResult &&)>;
+void run_batches(const Run &r, Worker &w, const std::function<bool(size_t &)> &next_batch, const Finish &finish) {
+  size_t b = 0, bn = 0;
+  bool have = next_batch(b);
+  Prepared cur;
+  if (have) cur = prepare_batch(r, w.prep_ctx ? w.prep_ctx : w.ctx, w.db, b);
+  while (have) {
+    const bool more = next_batch(bn);
+    Prepared nxt;
+    std::thread helper;
+    if (more && w.prep_ctx) helper = std::thread([&] { nxt = prepare_batch(r, w.prep_ctx, w.db, bn); });
+    finish(b, cur, search_batch(r, w, cur));
+    if (helper.joinable()) helper.join();
+    else if (more) nxt = prepare_batch(r, w.ctx, w.db, bn);
+    cur = std::move(nxt);
+    b = bn;
+    have = more;
+  }
+}
+
+// one process: the batches dealt from a counter to the workers, a host thread each
+void worker_main(const Run &r, Worker &w, std::atomic<size_t> &next, Writer &writer) {
+  run_batches(
+      r, w,
+      [&](size_t &b) {
+        b = next.fetch_add(1);
+        return b < r.nb;
+      },
+      [&](size_t b, const Prepared &p, BatchResult &&res) {
+        writer.wait_room(b, 2 * r.workers.size() + 1);
+        BatchJob job;
+        job.res = std::move(res);
+        job.qlen_unmasked = p.qlen_unmasked;
+        r.names_of(b, job.names);
+        writer.submit(b, std::move(job));
       });
-    for (auto &t : threads) t.join();
-  } else {
-    // round t: batch t * world + rank; every rank takes part in every round's gather, with or without a batch
-    size_t t_next = 0;
-    // The gathers run on a thread of their own, in round order, behind the search of the next batch (prb_gather_hits works
-    // on the communicator's own stream): rank 0, which receives everybody's records and copies them to the host, then takes no
-    // longer over a round than the others.  At most two rounds wait for it (their records stay in HBM until then).
-    struct GatherJob {
-      size_t t = 0;
-      bool has = false;
-      std::vector<int32_t> qlen;
-      std::vector<prb_hitset *> pages;
-    };
-    std::mutex gmu;
-    std::condition_variable gcv;
-    std::deque<GatherJob> gq;
-    bool gclosed = false;
-    auto gather_round_now = [&](GatherJob &gj) {
-      BatchJob job;
-      job.index = gj.t;
-      const size_t t = gj.t;
-      std::vector<prb_hitset *> &pages = gj.pages;
-      for (int page = 0; page < npages; page++) {
-        prb_hitset *mine = pages.empty() ? nullptr : pages[(size_t)page], *all = nullptr;
-        if (prb_gather_hits(comm, mine, gj.has ? (int32_t)gj.qlen.size() : 0, gj.has ? gj.qlen.data() : nullptr, 0, &all))
-          die(std::string("Error: ") + prb_last_error());
-        if (mine) prb_hitset_free(mine);
-        if (all) job.pages.push_back(all);
-      }
-      if (!writer_rank) return;
+}
+void run_workers(Run &r, Writer &writer) {
+  std::atomic<size_t> next{0};
+  std::vector<std::thread> threads;
+  for (Worker &w : r.workers) threads.emplace_back(worker_main, std::cref(r), std::ref(w), std::ref(next), std::ref(writer));
+  for (auto &t : threads) t.join();
+}
+
+// One process per GPU.  The gathers run on a thread of their own, in round order, behind the search of the next batch
+// (prb_gather_hits works on the communicator's own stream): rank 0, which receives everybody's records and copies them to
+// the host, then takes no longer over a round than the others.  At most two rounds wait for it (their records stay in HBM
+// until then).
+struct Gatherer {
+  struct Round {
+    size_t t = 0;
+    bool has = false; // this rank has a batch in the round
+    std::vector<int32_t> qlen;
+    BatchResult res;
+  };
+  const Run &r;
+  Writer &writer;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<Round> queue;
+  bool closed = false;
+  std::thread th;
+
+  Gatherer(const Run &run, Writer &wr) : r(run), writer(wr), th([this] { loop(); }) {}
+  void gather(Round &g) {
+    BatchJob job;
+    for (int page = 0; page < r.npages; page++) {
+      prb_hitset *mine = g.res.pages.empty() ? nullptr : g.res.pages[(size_t)page].get(), *all = nullptr;
+      if (prb_gather_hits(r.comm, mine, g.has ? (int32_t)g.qlen.size() : 0, g.has ? g.qlen.data() : nullptr, 0, &all))
+        die(std::string("Error: ") + prb_last_error());
+      if (mine) g.res.pages[(size_t)page].reset();
+      if (all) job.res.pages.emplace_back(all);
+    }
+    if (r.rank != 0) return;
+    writer.wait_room(g.t, 3);
+    int32_t nr = 0;
+    const int32_t *nq_of = nullptr, *ql = nullptr;
+    if (!job.res.pages.empty() && prb_hitset_gathered_queries(job.res.pages[0].get(), &nr, &nq_of, &ql)) die(std::string("Error: ") + prb_last_error());
+    for (int k = 0; k < nr; k++)
+      if (nq_of[k]) r.names_of(g.t * (size_t)r.world + (size_t)k, job.names);
+    job.qlen_unmasked.assign(ql, ql + job.names.size());
+    writer.submit(g.t, std::move(job));
+  }
+  void loop() {
+    for (;;) {
+      Round g;
       {
         std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return t < written + 3; });
+        cv.wait(lk, [&] { return !queue.empty() || closed; });
+        if (queue.empty()) return;
+        g = std::move(queue.front());
+        queue.pop_front();
       }
-      int32_t nr = 0;
-      const int32_t *nq_of = nullptr, *ql = nullptr;
-      if (!job.pages.empty() && prb_hitset_gathered_queries(job.pages[0], &nr, &nq_of, &ql)) die(std::string("Error: ") + prb_last_error());
-      for (int r = 0; r < nr; r++)
-        if (nq_of[r]) names_of(batch_idx(t * (size_t)world + (size_t)r), job.names);
-      job.nq = job.names.size();
-      job.qlen_unmasked.assign(ql, ql + job.nq);
-      submit(t, std::move(job));
-    };
-    std::thread gatherer([&] {
-      for (;;) {
-        GatherJob gj;
-        {
-          std::unique_lock<std::mutex> lk(gmu);
-          gcv.wait(lk, [&] { return !gq.empty() || gclosed; });
-          if (gq.empty()) return;
-          gj = std::move(gq.front());
-          gq.pop_front();
-        }
-        gcv.notify_all();
-        gather_round_now(gj);
-      }
-    });
-    auto gather_round = [&](size_t t, Prepared *p, std::vector<prb_hitset *> &pages) {
-      GatherJob gj;
-      gj.t = t;
-      gj.has = p != nullptr;
-      if (p) gj.qlen = p->qlen_unmasked;
-      gj.pages = pages;
-      std::unique_lock<std::mutex> lk(gmu);
-      gcv.wait(lk, [&] { return gq.size() < 2; });
-      gq.push_back(std::move(gj));
-      lk.unlock();
-      gcv.notify_all();
-    };
-    work(workers[0],
-         [&](size_t &b) {
-           b = t_next * (size_t)world + (size_t)rank;
-           t_next++;
-           return b < nb;
-         },
-         [&](size_t b, Prepared *p, std::vector<prb_hitset *> &pages, std::vector<prb_pairset *> &) {
-           gather_round(b / (size_t)world, p, pages);
-         });
-    // rounds in which this rank has no batch left (the last one, when nb is not a multiple of world)
-    const size_t mine_rounds = nb > (size_t)rank ? (nb - (size_t)rank + (size_t)world - 1) / (size_t)world : 0;
-    std::vector<prb_hitset *> none;
-    for (size_t t = mine_rounds; t < njobs; t++) gather_round(t, nullptr, none);
-    {
-      std::lock_guard<std::mutex> lk(gmu);
-      gclosed = true;
+      cv.notify_all();
+      gather(g);
     }
-    gcv.notify_all();
-    gatherer.join();
   }
-  writer.join();
-  if (a.binary) {
-    put<int64_t>(out, kEnd);
-    put<int64_t>(out, total_hits);
+  // round t: with this rank's batch (p, res), or without one
+  void push(size_t t, const Prepared *p, BatchResult &&res) {
+    Round g;
+    g.t = t;
+    g.has = p != nullptr;
+    if (p) g.qlen = p->qlen_unmasked;
+    g.res = std::move(res);
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return queue.size() < 2; });
+    queue.push_back(std::move(g));
+    lk.unlock();
+    cv.notify_all();
   }
-  if (std::fclose(out)) die("Error: can't write the output file");
-  if (comm) prb_comm_destroy(comm);
-  for (auto &w : workers) {
+  void close() {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      closed = true;
+    }
+    cv.notify_all();
+    th.join();
+  }
+};
+
+// round t: batch t * world + rank; every rank takes part in every round's gather, with or without a batch
+void run_ranks(Run &r, Writer &writer) {
+  const size_t world = (size_t)r.world, rank = (size_t)r.rank;
+  Gatherer gatherer(r, writer);
+  size_t t_next = 0;
+  run_batches(
+      r, r.workers[0],
+      [&](size_t &b) {
+        b = t_next * world + rank;
+        t_next++;
+        return b < r.nb;
+      },
+      [&](size_t b, const Prepared &p, BatchResult &&res) { gatherer.push(b / world, &p, std::move(res)); });
+  // rounds in which this rank has no batch left (the last one, when nb is not a multiple of world)
+  const size_t mine_rounds = r.nb > rank ? (r.nb - rank + world - 1) / world : 0;
+  for (size_t t = mine_rounds; t < r.njobs; t++) gatherer.push(t, nullptr, BatchResult());
+  gatherer.close();
+}
+
+void close_run(Run &r, int64_t total_hits) {
+  if (r.a.binary()) {
+    put<int64_t>(r.out, kEnd);
+    put<int64_t>(r.out, total_hits);
+  }
+  if (std::fclose(r.out)) die("Error: can't write the output file");
+  if (r.comm) prb_comm_destroy(r.comm);
+  for (auto &w : r.workers) {
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
     prb_ctx_destroy(w.ctx);
   }
+}
+
+int ris_main(int argc, char **argv) {
+  Run r;
+  r.a = parse_args(argc, argv);
+  const std::string err = prb::read_fasta(r.a.in, r.names, r.seqs);
+  if (!err.empty()) die(err);
+  const std::vector<int> devices = rank_setup(r);
+  open_workers(r, devices);
+  if (r.rank_mode) r.comm = join_ranks(r);
+  read_seq_tables(r);
+  open_output(r);
+  plan_batches(r);
+  Writer writer(r);
+  if (r.rank_mode) run_ranks(r, writer);
+  else run_workers(r, writer);
+  close_run(r, writer.join());
   return 0;
 }
 
