@@ -93,11 +93,11 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "gapped_front_hits": launches = hits it completed), "gapped" (LDS tier 0; "gapped_tier0_hits": launches = hits that entered it),
  * "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow" (wavefront-per-hit kernel), "traceback", "traceback_slow",
  * "summary" (prb_search_page_summary: pair heads, segment starts and the per-pair fold; launches = 3 per sub-batch),
- * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch),
+ * "top" (prb_search_page_top: the merge into the top-N table; launches = 1 per sub-batch; prb_topset_merge: 1),
  * "profile" (prb_search_page_profile: the merge into the per-position table, launches = 8 per sub-batch; and
- *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4);
+ *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4; prb_profset_merge: 1);
  * "tophits" (prb_search_page_tophits: the merge into the top-N hit table, the scan of the kept hits' pair counts and the
- *   gather of their lists; launches = 4 per sub-batch);
+ *   gather of their lists; launches = 4 per sub-batch, and per prb_tophits_merge);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -220,7 +220,17 @@ void prb_pairset_free(prb_pairset *ps);
  *                       then returns the records by query ascending, then by rank; `rank` counts from 0 within the
  *                       query.  No page can be merged after it (a second call does nothing)
  *   prb_topset_counts   the stage counts of prb_pairset_counts, summed over the merged pages
- * The device time of the merge is the stage "top" of prb_ctx_stage_ms. */
+ *   prb_topset_merge    two unfinished tables into one, on the device: dst (of ctx) then holds exactly - bit for bit -
+ *                       the table that the union of the two page sets merged into one table gives, its counts are the
+ *                       sums and its page set is the union; src is left empty but valid (it can be freed, or finished to
+ *                       zero records).  src may belong to another context, on the same or on another device: its records
+ *                       are then copied to dst's device first (a peer copy where hipDeviceCanAccessPeer allows it, else
+ *                       through pinned host memory), and the caller's current device is restored.  Both tables were made
+ *                       with the same n for batches of the same number of queries of the same lengths, and no page is
+ *                       merged into both: anything else returns PRB_ERR_ARG and leaves both tables as they were.  This is
+ *                       what lets several contexts share the pages of ONE batch (`ris` with PRB_SPLIT).  A dst that had
+ *                       merged no page takes over src's database: pages of no other one can be searched into it.
+ * The device time of the merges is the stage "top" of prb_ctx_stage_ms (prb_topset_merge: launches = 1). */
 typedef struct prb_top_pair {
   prb_pair_summary s;
   int32_t page, rank; /* the page the pair was found in; its rank within its query */
@@ -229,6 +239,7 @@ typedef struct prb_topset prb_topset;
 int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out);
 int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
                         prb_topset *ts);
+int prb_topset_merge(prb_ctx *ctx, prb_topset *dst, prb_topset *src);
 int prb_topset_finish(prb_ctx *ctx, prb_topset *ts);
 int64_t prb_topset_size(const prb_topset *ts);
 const prb_top_pair *prb_topset_pairs(const prb_topset *ts);
@@ -259,7 +270,12 @@ void prb_topset_free(prb_topset *ts);
  *                            in record order, without gaps, each equal to the hit's pairs in prb_hitset_basepairs (with
  *                            output_style 0 the two end pairs, SURVEY a17 quirk included; otherwise every pair)
  *   prb_tophits_counts       the stage counts of prb_hitset_counts, summed over the merged pages
- * The device time of the merge (selection, scan, gather) is the stage "tophits" of prb_ctx_stage_ms. */
+ *   prb_tophits_merge        prb_topset_merge for two unfinished top-N hit tables, same contract; the kept hits' base-pair
+ *                            lists are gathered from the two pools into a pool of exactly their size (the scan and the
+ *                            gather of prb_search_page_tophits).  The two tables hold pages searched with the same
+ *                            output_style, unless one of them has merged no page yet (else PRB_ERR_ARG, both untouched)
+ * The device time of the merges (selection, scan, gather) is the stage "tophits" of prb_ctx_stage_ms (prb_tophits_merge:
+ * launches = 4). */
 typedef struct prb_top_hit {
   prb_hit h;
   int32_t page, rank; /* the page the hit was found in; its rank within its query */
@@ -268,6 +284,7 @@ typedef struct prb_tophits prb_tophits;
 int prb_tophits_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_tophits **out);
 int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
                             prb_tophits *th);
+int prb_tophits_merge(prb_ctx *ctx, prb_tophits *dst, prb_tophits *src);
 int prb_tophits_finish(prb_ctx *ctx, prb_tophits *th);
 int64_t prb_tophits_size(const prb_tophits *th);
 const prb_top_hit *prb_tophits_hits(const prb_tophits *th);
@@ -299,7 +316,11 @@ void prb_tophits_free(prb_tophits *th);
  *                            table is released.  prb_profset_rows then returns them by query ascending, then by
  *                            position.  No page can be merged after it (a second call does nothing)
  *   prb_profset_counts       the stage counts of prb_pairset_counts, summed over the merged pages
- * The device time of the merge and of the finish is the stage "profile" of prb_ctx_stage_ms. */
+ *   prb_profset_merge        prb_topset_merge for two unfinished profile tables, same contract (there is no n): per slot
+ *                            the hits add, the targets add - no page is in both tables, so no (page, db_id) is counted
+ *                            twice -, and the best hit is the one of lower e_min, equal values decided by (page, place)
+ * The device time of the merges and of the finish is the stage "profile" of prb_ctx_stage_ms (prb_profset_merge:
+ * launches = 1). */
 typedef struct prb_profile_pos {
   int32_t query, pos;          /* index in the batch; 0-based position in the query (masked bases included) */
   int64_t hits;
@@ -312,6 +333,7 @@ typedef struct prb_profset prb_profset;
 int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out);
 int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
                             prb_profset *ps);
+int prb_profset_merge(prb_ctx *ctx, prb_profset *dst, prb_profset *src);
 int prb_profset_finish(prb_ctx *ctx, prb_profset *ps);
 int64_t prb_profset_size(const prb_profset *ps);
 const prb_profile_pos *prb_profset_rows(const prb_profset *ps);

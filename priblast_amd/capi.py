@@ -115,6 +115,7 @@ SYMBOLS = {
     "prb_pairset_free": (None, [ctypes.c_void_p]),
     "prb_topset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
     "prb_search_page_top": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_topset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "prb_topset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "prb_topset_size": (c_i64, [ctypes.c_void_p]),
     "prb_topset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -122,6 +123,7 @@ SYMBOLS = {
     "prb_topset_free": (None, [ctypes.c_void_p]),
     "prb_tophits_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
     "prb_search_page_tophits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_tophits_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "prb_tophits_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "prb_tophits_size": (c_i64, [ctypes.c_void_p]),
     "prb_tophits_hits": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -130,6 +132,7 @@ SYMBOLS = {
     "prb_tophits_free": (None, [ctypes.c_void_p]),
     "prb_profset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
     "prb_search_page_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_profset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "prb_profset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "prb_profset_size": (c_i64, [ctypes.c_void_p]),
     "prb_profset_rows": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -446,6 +449,11 @@ class _MergeTable:
         """prb_search_page_<MERGE>: searches the batch against `page` and merges the result into the table"""
         o = opts or default_opts()
         _check(getattr(lib(), "prb_search_page_" + self.MERGE)(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
+
+    def absorb(self, other):
+        """prb_<PREFIX>_merge: the unfinished table `other` (over other pages of the same queries; of any context) merged
+        into this one on the device; `other` is left empty"""
+        _check(self._fn("merge")(self.ctx.h, self.h, other.h))
 
     def _finish(self, records, dtype):
         """prb_<PREFIX>_finish -> the records that prb_<PREFIX>_<records> points to (a copy)"""

@@ -1319,25 +1319,15 @@ static int emit_profile(SubSearch &s) {
   return ctx->time_end(ctx->profile_timer, 8);
 }
 
-// prb_search_page_tophits: the hits' records (as emit_records packs them, their base-pair ranges counted from this
-// sub-batch's first pair) merged into the top-N hit table on the device, then the kept hits' base-pair lists gathered in
-// table order - survivors from the table's pool, newcomers from this sub-batch's pairs - into a second pool of exactly the
-// scanned size, which becomes the table's.  Nothing leaves the device.  Closes the "traceback" bracket.
-static int emit_tophits(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  prb_tophits *th = s.tophits;
-  const int64_t nfin = s.nfin;
+// What follows a merge into the top-N hit table, of a sub-batch (emit_tophits) or of another table (prb_tophits_merge):
+// the pair counts of the slots in use, their exclusive scan, and the kept hits' base-pair lists gathered in table order
+// into a second pool of exactly the scanned size, which becomes the table's.  A newcomer's bp_offset is `split` (the
+// table's pool_pairs) + the place of its list in `fresh`.  `fn` names the entry point in the messages.  Synchronises.
+int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh) {
   int rc;
-  if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
-  const int32_t *fresh;
-  if ((rc = pack_records(s, 0, &fresh))) return rc;
-  if ((rc = ctx->time_end("traceback", 2))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
   const int64_t nslots = (int64_t)th->nq * th->n;
   const size_t NS = (size_t)nslots + 1;
   if ((rc = th->cnt.ensure(NS * 4)) || (rc = th->off.ensure(NS * 8))) return rc;
-  PRB_HIP(launch_tophits_merge(w.packed.p, nfin, s.b.q0, s.b.q1, s.page, th->n, th->table.p, th->fill(), ctx->stream));
   PRB_HIP(launch_tophits_counts(th->table.p, th->fill(), th->n, nslots, th->cnt.as<int32_t>(), ctx->stream));
   auto counts = rocprim::make_transform_iterator(th->cnt.as<int32_t>(), ToI64());
   if ((rc = with_temp(th->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
@@ -1352,13 +1342,33 @@ static int emit_tophits(SubSearch &s) {
     return PRB_ERR_STATE;
   }
   if (th->pool2.ensure((size_t)std::max<int64_t>(total, 1) * 8) != PRB_OK) {
-    set_error("prb_search_page_tophits: can't allocate the pool of the kept hits' base pairs (" + std::to_string(total) + " pairs)");
+    set_error(std::string(fn) + ": can't allocate the pool of the kept hits' base pairs (" + std::to_string(total) + " pairs)");
     return PRB_ERR_NOMEM;
   }
-  PRB_HIP(launch_tophits_gather(th->table.p, th->fill(), th->n, nslots, th->off.as<int64_t>(), s.b.q0, s.b.q1, s.page,
-                                th->pool.as<int32_t>(), fresh, th->pool2.as<int32_t>(), ctx->stream));
+  PRB_HIP(launch_tophits_gather(th->table.p, th->fill(), th->n, nslots, th->off.as<int64_t>(), th->pool_pairs, th->pool.as<int32_t>(), fresh,
+                                th->pool2.as<int32_t>(), ctx->stream));
   std::swap(th->pool, th->pool2);
   th->pool_pairs = total;
+  return PRB_OK;
+}
+
+// prb_search_page_tophits: the hits' records (as emit_records packs them, their base-pair ranges counted from the end of
+// the table's pool on) merged into the top-N hit table on the device, then the kept hits' base-pair lists gathered in
+// table order - survivors from the table's pool, newcomers from this sub-batch's pairs (regather_tophits).  Nothing
+// leaves the device.  Closes the "traceback" bracket.
+static int emit_tophits(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  prb_tophits *th = s.tophits;
+  const int64_t nfin = s.nfin;
+  int rc;
+  if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
+  const int32_t *fresh;
+  if ((rc = pack_records(s, th->pool_pairs, &fresh))) return rc;
+  if ((rc = ctx->time_end("traceback", 2))) return rc;
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_tophits_merge(w.packed.p, nfin, s.b.q0, s.b.q1, s.page, th->n, th->table.p, th->fill(), ctx->stream));
+  if ((rc = regather_tophits("prb_search_page_tophits", ctx, th, fresh))) return rc;
   s.hs->hits_total += nfin;
   return ctx->time_end(ctx->tophits_timer, 4);
 }

@@ -13,6 +13,23 @@ struct ProfCovered {
   const int64_t *hits;
   __host__ __device__ bool operator()(const uint32_t &p) const { return hits[p] > 0; }
 };
+// the caller's current device, put back on every way out of a call that visits another table's device
+struct DeviceScope {
+  int prev = -1;
+  DeviceScope() {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  }
+  ~DeviceScope() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+// device / pinned memory that lives as long as one call
+struct ScratchBuf : DevBuf {
+  ~ScratchBuf() { release(); }
+};
+struct ScratchPin : PinnedBuf {
+  ~ScratchPin() { release(); }
+};
 } // namespace
 
 // prb_search_page_top / prb_search_page_profile / prb_search_page_tophits: page `page` searched and merged into the table `t` - `what` in the
@@ -82,6 +99,7 @@ template <class T> static int create_top_table(const char *fn_name, prb_ctx *ctx
   t->ctx = ctx;
   t->qb = qb;
   t->nq = qb->nq;
+  t->qlen = qb->len;
   t->n = n;
   PRB_HIP(hipSetDevice(ctx->device));
   const size_t bytes = std::max<size_t>(t->slots_bytes() + (size_t)qb->nq * sizeof(int32_t), 1);
@@ -103,6 +121,112 @@ static int finish_guard(const char *fn_name, const char *what, const prb_ctx *ct
     return PRB_ERR_STATE;
   }
   return PRB_OK;
+}
+
+// ---- prb_topset_merge / prb_tophits_merge / prb_profset_merge: two unfinished tables over disjoint page sets into one
+// What the three check before either table is touched: `dst` - `what` in the messages - belongs to ctx, both are
+// unfinished and whole, made for the same queries, and no page is in both.
+static int merge_tables_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const MergeTable *dst, const MergeTable *src) {
+  const std::string fn = fn_name, tables = std::string(what) + " tables";
+  auto refuse = [&](const std::string &why) {
+    set_error(fn + ": " + why);
+    return PRB_ERR_ARG;
+  };
+  if (!ctx || !dst || !src || dst == src) return refuse("bad argument");
+  if (dst->ctx != ctx) return refuse("the table to merge into belongs to another context");
+  if (dst->broken || src->broken) return refuse("an earlier merge into one of the " + tables + " failed");
+  if (dst->finished || src->finished) return refuse("one of the " + tables + " is finished");
+  if (dst->nq != src->nq) return refuse("the " + tables + " were made for " + std::to_string(dst->nq) + " and " + std::to_string(src->nq) + " queries");
+  if (dst->qlen != src->qlen) return refuse("the " + tables + " were made for queries of different lengths");
+  if (dst->db && src->db) {
+    if (dst->merged.size() != src->merged.size())
+      return refuse("the " + tables + " hold pages of databases of " + std::to_string(dst->merged.size()) + " and " +
+                    std::to_string(src->merged.size()) + " pages");
+    for (size_t p = 0; p < dst->merged.size(); p++)
+      if (dst->merged[p] && src->merged[p]) return refuse("page " + std::to_string(p) + " is merged into both " + tables);
+  }
+  return PRB_OK;
+}
+// after the merge: dst's page set is the union and its counts the sums; src has merged nothing
+static void move_pages(MergeTable *dst, MergeTable *src) {
+  if (src->db) {
+    if (!dst->db) {
+      dst->db = src->db;
+      dst->merged = src->merged;
+    } else {
+      for (size_t p = 0; p < dst->merged.size(); p++) dst->merged[p] |= src->merged[p];
+    }
+  }
+  for (int i = 0; i < 3; i++) {
+    dst->counts[i] += src->counts[i];
+    src->counts[i] = 0;
+  }
+  src->db = nullptr;
+  src->merged.clear();
+}
+// `bytes` at p on device `from` into `scratch` on ctx's device (the current one), complete on return or in order on
+// ctx's stream: a peer copy where the devices allow it, else through pinned host memory
+static int fetch_remote(prb_ctx *ctx, int from, const void *p, size_t bytes, DevBuf &scratch) {
+  if (int rc = scratch.ensure(std::max<size_t>(bytes, 1))) return rc;
+  if (!bytes) return PRB_OK;
+  int peer = 0;
+  if (hipDeviceCanAccessPeer(&peer, ctx->device, from) != hipSuccess) {
+    (void)hipGetLastError();
+    peer = 0;
+  }
+  if (peer) {
+    PRB_HIP(hipMemcpyPeerAsync(scratch.p, ctx->device, p, from, bytes, ctx->stream));
+    return PRB_OK;
+  }
+  ScratchPin pin;
+  if (int rc = pin.ensure(bytes)) return rc;
+  PRB_HIP(hipSetDevice(from));
+  PRB_HIP(hipMemcpy(pin.p, p, bytes, hipMemcpyDeviceToHost));
+  PRB_HIP(hipSetDevice(ctx->device));
+  PRB_HIP(hipMemcpy(scratch.p, pin.p, bytes, hipMemcpyHostToDevice));
+  return PRB_OK;
+}
+// `bytes` at p of a table of context `owner`, once that context's work is done, where ctx's device reads them: in place,
+// or a copy in `scratch`
+static int on_device_of(prb_ctx *ctx, const prb_ctx *owner, void *p, size_t bytes, DevBuf &scratch, void **out) {
+  PRB_HIP(hipStreamSynchronize(owner->stream));
+  *out = p;
+  if (owner->device == ctx->device || !p) return PRB_OK;
+  if (int rc = fetch_remote(ctx, owner->device, p, bytes, scratch)) return rc;
+  *out = scratch.p;
+  return PRB_OK;
+}
+// a top table back to empty, on its own device and stream
+template <class Slot> static int clear_top_table(TopTable<Slot> &t) {
+  PRB_HIP(hipSetDevice(t.ctx->device));
+  PRB_HIP(hipMemsetAsync(t.table.p, 0, std::max<size_t>(t.slots_bytes() + (size_t)t.nq * sizeof(int32_t), 1), t.ctx->stream));
+  PRB_HIP(hipStreamSynchronize(t.ctx->stream));
+  return PRB_OK;
+}
+// The two top tables: src's slots (and what `more` fetches) where dst's device reads them, join(slots, fill) enqueued
+// in the bracket of `timer`, then src emptied.  A failure from the first launch on leaves dst unusable.
+template <class T, class More, class Join>
+static int merge_top_tables(const char *fn_name, const char *what, StageTimer prb_ctx::*timer, int64_t launches, prb_ctx *ctx, T *dst, T *src,
+                            More more, Join join) {
+  if (int rc = merge_tables_guard(fn_name, what, ctx, dst, src)) return rc;
+  if (dst->n != src->n) {
+    set_error(std::string(fn_name) + ": the " + what + " tables keep " + std::to_string(dst->n) + " and " + std::to_string(src->n) + " records per query");
+    return PRB_ERR_ARG;
+  }
+  DeviceScope restore;
+  ScratchBuf copy;
+  PRB_HIP(hipSetDevice(ctx->device));
+  void *slots = nullptr;
+  int rc;
+  if ((rc = on_device_of(ctx, src->ctx, src->table.p, src->slots_bytes() + (size_t)src->nq * sizeof(int32_t), copy, &slots))) return rc;
+  if ((rc = more())) return rc;
+  dst->broken = true; // (until the merge is whole)
+  if ((rc = ctx->time_begin())) return rc;
+  if ((rc = join(slots, reinterpret_cast<const int32_t *>(static_cast<char *>(slots) + src->slots_bytes())))) return rc;
+  if ((rc = ctx->time_end(ctx->*timer, launches))) return rc; // (synchronises: src is read no more)
+  dst->broken = false;
+  move_pages(dst, src);
+  return clear_top_table(*src);
 }
 
 // prb_topset_finish / prb_tophits_finish: the slots and fill counts to the host (one block: one copy, enqueued after
@@ -164,6 +288,15 @@ int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
   return PRB_OK;
 }
 
+int prb_topset_merge(prb_ctx *ctx, prb_topset *dst, prb_topset *src) {
+  return merge_top_tables(
+      "prb_topset_merge", "top-N", &prb_ctx::top_timer, 1, ctx, dst, src, []() -> int { return PRB_OK; },
+      [&](const void *slots, const int32_t *fill) -> int {
+        PRB_HIP(launch_top_join(dst->table.p, dst->fill(), slots, fill, dst->nq, dst->n, ctx->stream));
+        return PRB_OK;
+      });
+}
+
 int64_t prb_topset_size(const prb_topset *ts) { return ts ? (int64_t)ts->pairs.size() : -1; }
 const prb_top_pair *prb_topset_pairs(const prb_topset *ts) { return ts ? ts->pairs.data() : nullptr; }
 void prb_topset_counts(const prb_topset *ts, int64_t counts[3]) {
@@ -221,6 +354,30 @@ int prb_tophits_finish(prb_ctx *ctx, prb_tophits *th) {
   return PRB_OK;
 }
 
+// the records as prb_topset_merge merges them, src's lists addressed behind dst's pool; then the scan and the gather of
+// prb_search_page_tophits with src's pool as the newcomers' source
+int prb_tophits_merge(prb_ctx *ctx, prb_tophits *dst, prb_tophits *src) {
+  if (dst && src && dst->style >= 0 && src->style >= 0 && dst->style != src->style) {
+    set_error("prb_tophits_merge: the top-N hit tables hold pages searched with output_style " + std::to_string(dst->style) + " and " +
+              std::to_string(src->style));
+    return PRB_ERR_ARG;
+  }
+  ScratchBuf pool_copy;
+  void *pool = nullptr;
+  const int rc = merge_top_tables(
+      "prb_tophits_merge", "top-N hit", &prb_ctx::tophits_timer, 4, ctx, dst, src,
+      [&]() -> int { return on_device_of(ctx, src->ctx, src->pool.p, (size_t)src->pool_pairs * 8, pool_copy, &pool); },
+      [&](const void *slots, const int32_t *fill) -> int {
+        PRB_HIP(launch_tophits_join(dst->table.p, dst->fill(), slots, fill, dst->nq, dst->n, dst->pool_pairs, ctx->stream));
+        return regather_tophits("prb_tophits_merge", ctx, dst, static_cast<const int32_t *>(pool));
+      });
+  if (rc) return rc;
+  if (dst->style < 0) dst->style = src->style;
+  src->style = -1;
+  src->pool_pairs = 0;
+  return PRB_OK;
+}
+
 int64_t prb_tophits_size(const prb_tophits *th) { return th ? (int64_t)th->hits.size() : -1; }
 const prb_top_hit *prb_tophits_hits(const prb_tophits *th) { return th ? th->hits.data() : nullptr; }
 const int32_t *prb_tophits_basepairs(const prb_tophits *th, int64_t *npairs) {
@@ -233,6 +390,19 @@ void prb_tophits_counts(const prb_tophits *th, int64_t counts[3]) {
 }
 void prb_tophits_free(prb_tophits *th) {
   delete th;
+}
+
+// every slot of the table back to "no hit" (the current device is the table's); its stream is idle on return
+static int clear_profile_table(prb_profset &ps) {
+  hipStream_t stream = ps.ctx->stream;
+  const size_t P = (size_t)ps.slots();
+  const prb::ProfTab t = ps.view();
+  PRB_HIP(hipMemsetAsync(ps.table.p, 0, ps.bytes(), stream));
+  PRB_HIP(hipMemsetAsync(t.key, 0xFF, 3 * P * 8, stream)); // key, tie, skey: none yet
+  PRB_HIP(hipMemsetAsync(t.stie, 0xFF, P * 4, stream));
+  PRB_HIP(hipMemcpyAsync(ps.table.p, ps.off.data(), ps.off.size() * 8, hipMemcpyHostToDevice, stream));
+  PRB_HIP(hipStreamSynchronize(stream));
+  return PRB_OK;
 }
 
 int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
@@ -249,6 +419,7 @@ int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
   ps->ctx = ctx;
   ps->qb = qb;
   ps->nq = qb->nq;
+  ps->qlen = qb->len;
   ps->off.assign((size_t)qb->nq + 1, 0);
   for (int32_t q = 0; q < qb->nq; q++) ps->off[(size_t)q + 1] = ps->off[(size_t)q] + qb->len[(size_t)q] + 1;
   PRB_HIP(hipSetDevice(ctx->device));
@@ -258,14 +429,27 @@ int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
               std::to_string(P) + " query positions)");
     return PRB_ERR_NOMEM;
   }
-  const prb::ProfTab t = ps->view();
-  PRB_HIP(hipMemsetAsync(ps->table.p, 0, ps->bytes(), ctx->stream));
-  PRB_HIP(hipMemsetAsync(t.key, 0xFF, 3 * P * 8, ctx->stream)); // key, tie, skey: none yet
-  PRB_HIP(hipMemsetAsync(t.stie, 0xFF, P * 4, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(ps->table.p, ps->off.data(), ps->off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  if (int rc = clear_profile_table(*ps)) return rc;
   *out = ps.release();
   return PRB_OK;
+}
+
+int prb_profset_merge(prb_ctx *ctx, prb_profset *dst, prb_profset *src) {
+  if (int rc = merge_tables_guard("prb_profset_merge", "profile", ctx, dst, src)) return rc;
+  DeviceScope restore;
+  ScratchBuf copy;
+  PRB_HIP(hipSetDevice(ctx->device));
+  void *block = nullptr;
+  int rc;
+  if ((rc = on_device_of(ctx, src->ctx, src->table.p, src->bytes(), copy, &block))) return rc;
+  dst->broken = true; // (until the merge is whole)
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_prof_join(dst->view(), dst->view_of(static_cast<char *>(block)), dst->slots(), ctx->stream));
+  if ((rc = ctx->time_end(ctx->profile_timer, 1))) return rc; // (synchronises: src is read no more)
+  dst->broken = false;
+  move_pages(dst, src);
+  PRB_HIP(hipSetDevice(src->ctx->device));
+  return clear_profile_table(*src);
 }
 
 int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_profset *ps) {

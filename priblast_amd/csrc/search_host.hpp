@@ -348,6 +348,7 @@ struct MergeTable {
   const prb_qbatch *qb = nullptr;
   const prb_db *db = nullptr;  // of the first merged page
   int32_t nq = 0;
+  std::vector<int32_t> qlen;   // the queries' lengths (what two tables must share to be merged, prb_*_merge)
   std::vector<uint8_t> merged; // per page of db
   bool broken = false;         // a merge failed part way
   bool finished = false;       // prb_*set_finish: the records are on the host, the device memory is released
@@ -404,10 +405,11 @@ struct prb_profset : prb::MergeTable {
   // the block: off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie, db_id,
   // bp (x4), bad
   size_t bytes() const { return (off.size() + 5 * (size_t)slots()) * 8 + (7 * (size_t)slots() + 2) * 4; }
-  prb::ProfTab view() const {
+  prb::ProfTab view() const { return view_of(table.as<char>()); }
+  // the arrays of a block at b (the table's own, or a copy of another table's)
+  prb::ProfTab view_of(char *b) const {
     prb::ProfTab t;
     const size_t P = (size_t)slots();
-    char *b = table.as<char>();
     t.off = reinterpret_cast<const int64_t *>(b);
     b += off.size() * 8;
     t.hdiff = reinterpret_cast<unsigned long long *>(b);
@@ -458,4 +460,6 @@ int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, 
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
                 SearchMode mode, prb_hitset **out, MergeTable *table = nullptr);
+// capi_search.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
+int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh);
 } // namespace prb

@@ -1161,6 +1161,80 @@ __global__ __launch_bounds__(kTopBlock) void k_top_merge(const typename R::Rec *
   if (tid == 0) fill[q] = cnt;
 }
 
+// ---- two tables of one kind into one (prb_topset_merge, prb_tophits_merge) ----
+// One workgroup per query.  The query's slots in use are two ranked lists - tab's and src's - over disjoint page sets, so
+// no two of their (energy key, tie key) pairs are equal, and an entry's place in the union is its index plus the entries
+// of the other list below it (binary-search rank: no re-sort).  LDS (dynamic): the two lists' keys (n entries each) and
+// the sources of the n places kept - < 2^31: tab's slot, else 2^31 | src's slot.  A record from src keeps its page and
+// ordinal; shift = what is added to its bp_offset (the top-N hit table: its list lies behind tab's pool, see
+// k_tophits_gather).  The write-back is k_top_merge's: in rank order, from the top down.
+template <class R> struct TopRebase;
+template <> struct TopRebase<TopPairs> {
+  static __device__ __forceinline__ void apply(prb_top_pair &, int64_t) {}
+};
+template <> struct TopRebase<TopHits> {
+  static __device__ __forceinline__ void apply(prb_top_hit &s, int64_t shift) { s.h.bp_offset += shift; }
+};
+template <class R>
+__global__ __launch_bounds__(kTopBlock) void k_table_merge(typename R::Slot *__restrict__ tab, int32_t *__restrict__ fill,
+                                                           const typename R::Slot *__restrict__ src, const int32_t *__restrict__ src_fill,
+                                                           int32_t n, int64_t shift) {
+  using Slot = typename R::Slot;
+  extern __shared__ uint64_t top_lds[];
+  uint64_t *dk1 = top_lds, *dk2 = dk1 + n, *sk1 = dk2 + n, *sk2 = sk1 + n;
+  uint32_t *from = reinterpret_cast<uint32_t *>(sk2 + n);
+  const int tid = threadIdx.x;
+  const int32_t q = (int32_t)blockIdx.x;
+  const int cs = min(max(src_fill[q], 0), n);
+  if (cs == 0) return; // (uniform: src has nothing of q)
+  const int cd = min(max(fill[q], 0), n);
+  Slot *const slots = tab + (int64_t)q * n;
+  const Slot *const other = src + (int64_t)q * n;
+  for (int i = tid; i < cd; i += kTopBlock) {
+    const Slot &t = slots[i];
+    dk1[i] = energy_key(R::energy(R::body(t)));
+    dk2[i] = ((uint64_t)(uint32_t)t.page << 32) | (uint32_t)t.rank;
+  }
+  for (int i = tid; i < cs; i += kTopBlock) {
+    const Slot &t = other[i];
+    sk1[i] = energy_key(R::energy(R::body(t)));
+    sk2[i] = ((uint64_t)(uint32_t)t.page << 32) | (uint32_t)t.rank;
+  }
+  for (int i = tid; i < n; i += kTopBlock) from[i] = (uint32_t)i; // (every place has a source inside the table, whatever the keys)
+  __syncthreads();
+  for (int i = tid; i < cd; i += kTopBlock) {
+    const int pos = i + count_below(sk1, sk2, cs, dk1[i], dk2[i]);
+    if (pos < n) from[pos] = (uint32_t)i;
+  }
+  for (int i = tid; i < cs; i += kTopBlock) {
+    const int pos = i + count_below(dk1, dk2, cd, sk1[i], sk2[i]);
+    if (pos < n) from[pos] = 0x80000000u | (uint32_t)i;
+  }
+  __syncthreads();
+  const int cnt = min(n, cd + cs);
+  // A kept record of tab moves from slot s to a place j >= s, so rounds of 256 places from the top down never read a
+  // slot an earlier round wrote; within a round every lane reads before any lane writes.
+  for (int r0 = ((cnt - 1) / kTopBlock) * kTopBlock; r0 >= 0; r0 -= kTopBlock) {
+    const int j = r0 + tid;
+    bool move = false;
+    Slot v;
+    if (j < cnt) {
+      const uint32_t s = from[j];
+      if (s & 0x80000000u) {
+        v = other[s & 0x7FFFFFFFu];
+        TopRebase<R>::apply(v, shift);
+        move = true;
+      } else if ((int)s != j) {
+        v = slots[s];
+        move = true;
+      }
+    }
+    __syncthreads();
+    if (move) slots[j] = v;
+  }
+  if (tid == 0) fill[q] = cnt;
+}
+
 // ---- base pairs of the top-N hit table ----
 // The kept hits' lists lie in a pool in table order without gaps.  After a merge: the counts of the slots in use, their
 // exclusive scan (rocPRIM, on the host side), then every list gathered into a second pool at its scanned place.
@@ -1172,15 +1246,16 @@ __global__ __launch_bounds__(kBlock) void k_tophits_counts(const prb_top_hit *__
   if (i < nslots && (int32_t)(i % n) < fill[i / n]) c = max(tab[i].h.bp_count, 0);
   cnt[i] = c;
 }
-// kTopHitLanes lanes per slot, a pair (8 bytes) per lane and step.  A hit of queries [q0, q1) that was found in `page`
-// came with this merge - its offset indexes `fresh` -, every other one lies in the old pool.  (The lanes of a slot
-// have its old offset in a register before they copy, the first of them replaces it behind the copy.)
+// kTopHitLanes lanes per slot, a pair (8 bytes) per lane and step.  A hit that came with this merge has an offset at
+// or beyond `split`, the old pool's size in pairs - its list lies in `fresh` at that offset less `split` -, every other
+// one lies in the old pool.  (The lanes of a slot have its old offset in a register before they copy, the first of them
+// replaces it behind the copy.)
 constexpr int kTopHitLanes = 16;
 static_assert(kBlock % kTopHitLanes == 0, "whole slots per workgroup");
 __global__ __launch_bounds__(kBlock) void k_tophits_gather(prb_top_hit *__restrict__ tab, const int32_t *__restrict__ fill, int32_t n,
-                                                           int64_t nslots, const int64_t *__restrict__ off, int32_t q0, int32_t q1,
-                                                           int32_t page, const int2 *__restrict__ old_pool,
-                                                           const int2 *__restrict__ fresh, int2 *__restrict__ pool) {
+                                                           int64_t nslots, const int64_t *__restrict__ off, int64_t split,
+                                                           const int2 *__restrict__ old_pool, const int2 *__restrict__ fresh,
+                                                           int2 *__restrict__ pool) {
   const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t i = t / kTopHitLanes;
   const int sub = (int)(t % kTopHitLanes);
@@ -1190,7 +1265,7 @@ __global__ __launch_bounds__(kBlock) void k_tophits_gather(prb_top_hit *__restri
   prb_top_hit &slot = tab[i];
   const int32_t c = max(slot.h.bp_count, 0);
   const int64_t from = slot.h.bp_offset, to = off[i];
-  const int2 *src = (q >= q0 && q < q1 && slot.page == page ? fresh : old_pool) + from;
+  const int2 *src = from >= split ? fresh + (from - split) : old_pool + from;
   for (int32_t j = sub; j < c; j += kTopHitLanes) pool[to + j] = src[j];
   if (sub == 0) slot.h.bp_offset = to;
 }
@@ -1309,6 +1384,26 @@ __global__ __launch_bounds__(kBlock) void k_prof_merge(HitSoA h, const int32_t *
   }
   t.skey[p] = ~0ull;
   t.stie[p] = ~0u;
+}
+
+// prb_profset_merge: the table s, over other pages of the same batch, into t, a lane per slot.  The difference arrays
+// add (no page is in both, so no (page, db_id) is counted twice among the targets); the best hit is the lower of the two
+// (key, tie) pairs.
+__global__ __launch_bounds__(kBlock) void k_prof_join(ProfTab t, ProfTab s, int64_t P) {
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p == 0 && *s.bad) *t.bad = 1u;
+  if (p >= P) return;
+  t.hdiff[p] += s.hdiff[p];
+  t.tdiff[p] += s.tdiff[p];
+  const unsigned long long sk = s.key[p], st = s.tie[p], k = t.key[p];
+  if (sk < k || (sk == k && st < t.tie[p])) {
+    t.key[p] = sk;
+    t.tie[p] = st;
+    t.e_min[p] = s.e_min[p];
+    t.db_id[p] = s.db_id[p];
+#pragma unroll
+    for (int c = 0; c < 4; c++) t.bp[4 * p + c] = s.bp[4 * p + c];
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void k_prof_rows(ProfTab t, const uint32_t *__restrict__ idx, int64_t n, const int64_t *__restrict__ hits,
@@ -1807,13 +1902,35 @@ hipError_t launch_tophits_counts(const void *tab, const int32_t *fill, int32_t n
   hipLaunchKernelGGL(k_tophits_counts, grid_for(nslots + 1), dim3(kBlock), 0, s, static_cast<const prb_top_hit *>(tab), fill, n, nslots, cnt);
   return hipGetLastError();
 }
-hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int32_t q0, int32_t q1,
-                                 int32_t page, const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s) {
+hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int64_t split,
+                                 const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s) {
   if (nslots <= 0) return hipSuccess;
-  if (n < 1) return hipErrorInvalidValue;
+  if (n < 1 || split < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_tophits_gather, grid_for(nslots * kTopHitLanes), dim3(kBlock), 0, s, static_cast<prb_top_hit *>(tab), fill, n, nslots,
-                     off, q0, q1, page, reinterpret_cast<const int2 *>(old_pool), reinterpret_cast<const int2 *>(fresh),
+                     off, split, reinterpret_cast<const int2 *>(old_pool), reinterpret_cast<const int2 *>(fresh),
                      reinterpret_cast<int2 *>(pool));
+  return hipGetLastError();
+}
+template <class R>
+static hipError_t launch_table_merge_of(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n,
+                                        int64_t shift, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  if (n < 1 || n > kTopMaxN) return hipErrorInvalidValue;
+  const size_t lds = (size_t)n * (4 * 8 + 4); // at most 36 KB (n = 1024)
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_table_merge<R>), dim3((unsigned)nq), dim3(kTopBlock), lds, s, static_cast<typename R::Slot *>(tab),
+                     fill, static_cast<const typename R::Slot *>(src), src_fill, n, shift);
+  return hipGetLastError();
+}
+hipError_t launch_top_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, hipStream_t s) {
+  return launch_table_merge_of<TopPairs>(tab, fill, src, src_fill, nq, n, 0, s);
+}
+hipError_t launch_tophits_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, int64_t shift,
+                               hipStream_t s) {
+  return launch_table_merge_of<TopHits>(tab, fill, src, src_fill, nq, n, shift, s);
+}
+hipError_t launch_prof_join(const ProfTab &t, const ProfTab &src, int64_t P, hipStream_t s) {
+  if (P <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_prof_join, grid_for(P), dim3(kBlock), 0, s, t, src, P);
   return hipGetLastError();
 }
 hipError_t launch_prof_keys(int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, uint64_t *key, uint32_t *val,

@@ -154,10 +154,19 @@ hipError_t launch_tophits_merge(const void *rec, int64_t nrec, int32_t q0, int32
 // an exclusive scan over nslots + 1 values ends with the total
 hipError_t launch_tophits_counts(const void *tab, const int32_t *fill, int32_t n, int64_t nslots, int32_t *cnt, hipStream_t s);
 // The kept hits' base-pair lists gathered into `pool` in table order: slot i's list goes to pair off[i].  Its source is
-// `fresh` (this sub-batch's pairs, which launch_pack_hits' offsets index) for a hit of queries [q0, q1) found in `page`,
-// else `old_pool`; the slot's bp_offset becomes off[i].  All three arrays are (q, db) pairs of two int32.
-hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int32_t q0, int32_t q1,
-                                 int32_t page, const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s);
+// `old_pool` at the slot's bp_offset when that is below `split` (the old pool's pairs), else `fresh` at bp_offset - split:
+// the newcomers' lists (this sub-batch's pairs, with launch_pack_hits' offsets counted from `split` on; or the pool of the
+// table that launch_tophits_join took them from); the slot's bp_offset becomes off[i].  All three arrays are (q, db) pairs
+// of two int32.
+hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int64_t nslots, const int64_t *off, int64_t split,
+                                 const int32_t *old_pool, const int32_t *fresh, int32_t *pool, hipStream_t s);
+// ---- two tables over disjoint page sets into one (prb_topset_merge, prb_tophits_merge) ----
+// per query, tab's and src's ranked slots in use merged under the tables' order, the first n kept, in tab (src is only
+// read); one workgroup per query, nq of them.  launch_tophits_join adds `shift` to the bp_offset of every record it
+// takes from src.
+hipError_t launch_top_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, hipStream_t s);
+hipError_t launch_tophits_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, int64_t shift,
+                               hipStream_t s);
 // ---- per-position profile (prb_search_page_profile) ----
 // The table of one batch in HBM.  Query q owns the slots [off[q], off[q + 1]) = its len + 1 positions (the last one
 // takes the -1 of a span that ends at the query's last base), so the difference arrays of all queries are one array
@@ -192,6 +201,8 @@ hipError_t launch_prof_min(const HitSoA &h, int64_t n, const uint32_t *val, cons
 // slots [p0, p1): the sub-batch's minima merged into the best hits (page `page`), the scratch reset
 hipError_t launch_prof_merge(const HitSoA &h, const int32_t *ends, const ProfTab &t, int64_t p0, int64_t p1, int32_t page,
                              hipStream_t s);
+// prb_profset_merge: slots [0, P) of src (same queries, other pages) into t: counts added, the lower best hit kept
+hipError_t launch_prof_join(const ProfTab &t, const ProfTab &src, int64_t P, hipStream_t s);
 // rows[j] (prb_profile_pos) of the covered slot idx[j]; hits / targets = the scanned difference arrays
 hipError_t launch_prof_rows(const ProfTab &t, const uint32_t *idx, int64_t n, const int64_t *hits, const int32_t *targets, void *rows,
                             hipStream_t s);

@@ -9,6 +9,9 @@
 //   * one process: dealt from a counter to the workers named by PRB_DEVICES (default: device 0), one
 //     host thread each; a worker computes the accessibilities of its next batch under a second
 //     context while the current batch is searched; one writer thread prints finished batches in order;
+//     With fewer batches than workers (one lncRNA against a transcriptome) and a database of several pages
+//     (`db -c`), the workers share each batch instead (PRB_SPLIT): everyone takes pages of it from a counter, and
+//     the first worker merges the others' tables into its own on the device (prb_*_merge) - run_team;
 //   * one process per GPU (WORLD_SIZE / RANK / LOCAL_RANK in the environment, as torchrun or mpirun
 //     set them): batch b goes to rank b mod WORLD_SIZE, and after every round of batches the final
 //     hits are gathered on rank 0 over RCCL (prb_gather_hits), which writes the lines - the
@@ -33,7 +36,7 @@
 // How the file is laid out.  The switches -t -n -q -k -b have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
 // join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
-// (the Gatherer), and close_run.  Both producers drive run_batches, whose search_batch returns a BatchResult - the one
+// (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
 // owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread calls write_job.
 #include <getopt.h>
 #include <sys/stat.h>
@@ -109,10 +112,20 @@ void usage() {
             "              nor with WORLD_SIZE > 1)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
+            "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
+            "               every batch (a database built with `db -c`); auto [default]: pages when there are fewer batches\n"
+            "               than workers; the output is the same; ignored with WORLD_SIZE > 1;\n"
             "               WORLD_SIZE / RANK / LOCAL_RANK  one process per GPU, final hits gathered on rank 0 over RCCL");
 }
 
+// An error ends the run: at once - except in a thread of a team (run_team), which hands the message to the main thread
+// instead (an exit under the feet of the other workers of a batch would leave their GPUs mid-kernel).
+struct TeamError {
+  std::string msg;
+};
+thread_local bool t_team_thread = false;
 [[noreturn]] void die(const std::string &msg) {
+  if (t_team_thread) throw TeamError{msg};
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(1);
 }
@@ -455,6 +468,10 @@ struct Run {
   // the batch plan: batch b = the queries order[b * batch ..), nb batches, njobs jobs for the writer
   std::vector<size_t> order;
   size_t batch = 1, nb = 0, njobs = 0;
+  // PRB_SPLIT: what the workers of one process share out (plan_split)
+  int split_knob = 0;       // index in kSplitNames
+  bool split_given = false; // PRB_SPLIT is set
+  bool split_pages = false; // this run: the pages of every batch
   std::vector<size_t> batch_idx(size_t b) const {
     return std::vector<size_t>(order.begin() + b * batch, order.begin() + std::min(seqs.size(), (b + 1) * batch));
   }
@@ -562,6 +579,24 @@ std::vector<int> rank_setup(Run &r) {
   }
   if (devices.empty()) devices.push_back(0);
   return devices;
+}
+
+// PRB_SPLIT: one of kSplitNames; anything else is refused here, before any GPU work, the message from the same list
+enum SplitKnob { kSplitAuto, kSplitQueries, kSplitPages, kSplitKnobs };
+constexpr const char *kSplitNames[kSplitKnobs] = {"auto", "queries", "pages"};
+void split_setup(Run &r) {
+  const char *e = std::getenv("PRB_SPLIT");
+  r.split_given = e != nullptr;
+  r.split_knob = kSplitAuto;
+  if (!e) return;
+  for (int k = 0; k < kSplitKnobs; k++)
+    if (std::strcmp(e, kSplitNames[k]) == 0) {
+      r.split_knob = k;
+      return;
+    }
+  std::string names;
+  for (int k = 0; k < kSplitKnobs; k++) names += std::string(k ? (k + 1 < kSplitKnobs ? ", " : " or ") : "") + kSplitNames[k];
+  die("Error: PRB_SPLIT needs one of " + names + " (got \"" + e + "\")");
 }
 
 // a worker per device: its context, a second one for the batch prepared ahead, the database
@@ -673,8 +708,16 @@ void plan_batches(Run &r) {
   r.njobs = r.rank_mode ? (r.nb + r.world - 1) / r.world : r.nb;
 }
 
-// encode + suffix arrays + accessibilities of batch b under context c
-Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b) {
+// Whole batches to the workers, or the pages of every batch?  Pages only in one process with two workers or more and
+// a database of two pages or more: when asked for, or - auto - when there are fewer batches than workers.
+void plan_split(Run &r) {
+  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2;
+  r.split_pages = can && (r.split_knob == kSplitPages || (r.split_knob == kSplitAuto && r.nb < r.workers.size()));
+}
+
+// encode + suffix arrays + accessibilities of batch b under context c; the seed search against seed_page is begun
+// beside them (none if it is negative)
+Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b, int seed_page = 0) {
   const std::vector<size_t> idx = r.batch_idx(b);
   std::string cat;
   std::vector<int64_t> off(idx.size() + 1, 0);
@@ -686,60 +729,108 @@ Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b) {
   if (prb_qbatch_create(c, (int32_t)idx.size(), cat.data(), off.data(), r.repeat_flag, &p.qb)) die(prb_last_error());
   // the seed DFS against the first page needs no GPU: it runs on host threads beside the accessibilities (and,
   // for a batch prepared ahead, beside the previous batch's search)
-  if (db && prb_qbatch_seed_search_begin(c, p.qb, db, 0, &r.a.o)) die(prb_last_error());
+  if (db && seed_page >= 0 && prb_qbatch_seed_search_begin(c, p.qb, db, seed_page, &r.a.o)) die(prb_last_error());
   if (prb_qbatch_accessibility(c, p.qb, r.W, r.delta)) die(prb_last_error());
   p.qlen_unmasked.resize(idx.size());
   for (size_t q = 0; q < idx.size(); q++) p.qlen_unmasked[q] = prb_qbatch_length_unmasked(p.qb, (int32_t)q);
   return p;
 }
 
-// -t -n, -q, -k: a table made by `create`, every page searched and merged into it on the device by `merge`, then one copy
+// -t -n, -q, -k: a table per batch; every page is searched and merged into it on the device by `search`, then one copy
 // of its records to the host by `finish`
-template <class T, class Create>
-Handle<T> merged_table(const Run &r, Worker &w, prb_qbatch *qb, Create create,
-                       int (*merge)(prb_ctx *, prb_qbatch *, prb_db *, int32_t, const prb_ris_opts *, T *), int (*finish)(prb_ctx *, T *)) {
-  T *t = nullptr;
-  if (create(&t)) die(prb_last_error());
-  Handle<T> table(t);
-  for (int page = 0; page < r.npages; page++)
-    if (merge(w.ctx, qb, w.db, page, &r.a.o, t)) die(prb_last_error());
-  if (finish(w.ctx, t)) die(prb_last_error());
-  return table;
+template <class T> struct TableOps {
+  int (*search)(prb_ctx *, prb_qbatch *, prb_db *, int32_t, const prb_ris_opts *, T *);
+  int (*merge)(prb_ctx *, T *, T *); // another worker's table of the same batch into this one (a team, run_team)
+  int (*finish)(prb_ctx *, T *);
+};
+const TableOps<prb_topset> kTopOps = {prb_search_page_top, prb_topset_merge, prb_topset_finish};
+const TableOps<prb_profset> kProfOps = {prb_search_page_profile, prb_profset_merge, prb_profset_finish};
+const TableOps<prb_tophits> kTopHitsOps = {prb_search_page_tophits, prb_tophits_merge, prb_tophits_finish};
+
+// the empty table of a batch, by mode (nothing for the modes that have none), in res
+void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
+  const Args &a = r.a;
+  int rc = 0;
+  switch (a.mode) {
+  case OutputMode::kTop: {
+    prb_topset *t = nullptr;
+    rc = prb_topset_create(w.ctx, qb, a.top, &t);
+    res.top.reset(t);
+    break;
+  }
+  case OutputMode::kProfile: {
+    prb_profset *t = nullptr;
+    rc = prb_profset_create(w.ctx, qb, &t);
+    res.prof.reset(t);
+    break;
+  }
+  case OutputMode::kTopHits: {
+    prb_tophits *t = nullptr;
+    rc = prb_tophits_create(w.ctx, qb, a.tophits, &t);
+    res.tophits.reset(t);
+    break;
+  }
+  case OutputMode::kSummary:
+  case OutputMode::kHits: break;
+  }
+  if (rc) die(prb_last_error());
+}
+
+// one page of a prepared batch searched: into the table of `mine`, or - a hit set or a pair set - into slot `page` of `out`
+void search_one_page(const Run &r, Worker &w, prb_qbatch *qb, int page, BatchResult &mine, BatchResult &out) {
+  const Args &a = r.a;
+  int rc = 0;
+  switch (a.mode) {
+  case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &a.o, mine.top.get()); break;
+  case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &a.o, mine.prof.get()); break;
+  case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &a.o, mine.tophits.get()); break;
+  case OutputMode::kSummary: {
+    prb_pairset *ps = nullptr;
+    rc = prb_search_page_summary(w.ctx, qb, w.db, page, &a.o, &ps);
+    out.pair_pages[(size_t)page].reset(ps);
+    break;
+  }
+  case OutputMode::kHits: {
+    prb_hitset *hs = nullptr;
+    rc = prb_search_page(w.ctx, qb, w.db, page, &a.o, 3, &hs);
+    out.pages[(size_t)page].reset(hs);
+    break;
+  }
+  }
+  if (rc) die(prb_last_error());
+}
+
+// the table of `mine` - with the tables of `others` merged into it first - to the host: one copy of its records
+void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<BatchResult *> &others = {}) {
+  auto run = [&](auto ops, auto member) {
+    for (BatchResult *o : others)
+      if (ops.merge(w.ctx, (mine.*member).get(), (o->*member).get())) die(prb_last_error());
+    if (ops.finish(w.ctx, (mine.*member).get())) die(prb_last_error());
+  };
+  switch (r.a.mode) {
+  case OutputMode::kTop: run(kTopOps, &BatchResult::top); break;
+  case OutputMode::kProfile: run(kProfOps, &BatchResult::prof); break;
+  case OutputMode::kTopHits: run(kTopHitsOps, &BatchResult::tophits); break;
+  case OutputMode::kSummary:
+  case OutputMode::kHits: break;
+  }
+}
+
+// a result with a slot per page for the modes that keep the pages apart
+BatchResult empty_result(const Run &r) {
+  BatchResult res;
+  res.mode = r.a.mode;
+  if (r.a.mode == OutputMode::kHits) res.pages.resize((size_t)r.npages);
+  if (r.a.mode == OutputMode::kSummary) res.pair_pages.resize((size_t)r.npages);
+  return res;
 }
 
 // the search stages of a prepared batch against every page
 BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
-  const Args &a = r.a;
-  BatchResult res;
-  res.mode = a.mode;
-  switch (a.mode) {
-  case OutputMode::kTop:
-    res.top = merged_table<prb_topset>(r, w, p.qb, [&](prb_topset **t) { return prb_topset_create(w.ctx, p.qb, a.top, t); },
-                                       prb_search_page_top, prb_topset_finish);
-    break;
-  case OutputMode::kProfile:
-    res.prof = merged_table<prb_profset>(r, w, p.qb, [&](prb_profset **t) { return prb_profset_create(w.ctx, p.qb, t); },
-                                         prb_search_page_profile, prb_profset_finish);
-    break;
-  case OutputMode::kTopHits:
-    res.tophits = merged_table<prb_tophits>(r, w, p.qb, [&](prb_tophits **t) { return prb_tophits_create(w.ctx, p.qb, a.tophits, t); },
-                                            prb_search_page_tophits, prb_tophits_finish);
-    break;
-  case OutputMode::kSummary:
-    for (int page = 0; page < r.npages; page++) {
-      prb_pairset *ps = nullptr;
-      if (prb_search_page_summary(w.ctx, p.qb, w.db, page, &a.o, &ps)) die(prb_last_error());
-      res.pair_pages.emplace_back(ps);
-    }
-    break;
-  case OutputMode::kHits:
-    for (int page = 0; page < r.npages; page++) {
-      prb_hitset *hs = nullptr;
-      if (prb_search_page(w.ctx, p.qb, w.db, page, &a.o, 3, &hs)) die(prb_last_error());
-      res.pages.emplace_back(hs);
-    }
-    break;
-  }
+  BatchResult res = empty_result(r);
+  create_table(r, w, p.qb, res);
+  for (int page = 0; page < r.npages; page++) search_one_page(r, w, p.qb, page, res, res);
+  finish_table(r, w, res);
   prb_qbatch_destroy(p.qb);
   p.qb = nullptr;
   return res;
@@ -891,21 +982,41 @@ struct Writer {
 
 // ---- the producers -------------------------------------------------------------------------------
 // A worker: its batches one after the other, as next_batch names them; the accessibilities of the next one are computed
-// by a helper thread under the worker's second context while this one is searched.
+// by a helper thread under the worker's second context while this one is searched.  `search` = search_batch, or a team's
+// share of it; seed_page: prepare_batch.
 using Finish = std::function<void(size_t, const Prepared &, BatchResult &&)>;
-void run_batches(const Run &r, Worker &w, const std::function<bool(size_t &)> &next_batch, const Finish &finish) {
+using Search = std::function<BatchResult(size_t, Worker &, Prepared &)>;
+void run_batches(const Run &r, Worker &w, const std::function<bool(size_t &)> &next_batch, const Finish &finish, const Search &search = {},
+                 int seed_page = 0) {
   size_t b = 0, bn = 0;
   bool have = next_batch(b);
   Prepared cur;
-  if (have) cur = prepare_batch(r, w.prep_ctx ? w.prep_ctx : w.ctx, w.db, b);
+  if (have) cur = prepare_batch(r, w.prep_ctx ? w.prep_ctx : w.ctx, w.db, b, seed_page);
   while (have) {
     const bool more = next_batch(bn);
     Prepared nxt;
     std::thread helper;
-    if (more && w.prep_ctx) helper = std::thread([&] { nxt = prepare_batch(r, w.prep_ctx, w.db, bn); });
-    finish(b, cur, search_batch(r, w, cur));
+    std::string helper_error; // (of a team's helper: it ends like its worker)
+    bool helper_failed = false;
+    if (more && w.prep_ctx)
+      helper = std::thread([&, team = t_team_thread] {
+        t_team_thread = team;
+        try {
+          nxt = prepare_batch(r, w.prep_ctx, w.db, bn, seed_page);
+        } catch (const TeamError &e) {
+          helper_error = e.msg;
+          helper_failed = true;
+        }
+      });
+    try {
+      finish(b, cur, search ? search(b, w, cur) : search_batch(r, w, cur));
+    } catch (...) {
+      if (helper.joinable()) helper.join();
+      throw;
+    }
     if (helper.joinable()) helper.join();
-    else if (more) nxt = prepare_batch(r, w.ctx, w.db, bn);
+    else if (more) nxt = prepare_batch(r, w.ctx, w.db, bn, seed_page);
+    if (helper_failed) die(helper_error);
     cur = std::move(nxt);
     b = bn;
     have = more;
@@ -913,6 +1024,14 @@ void run_batches(const Run &r, Worker &w, const std::function<bool(size_t &)> &n
 }
 
 // one process: the batches dealt from a counter to the workers, a host thread each
+void submit_batch(const Run &r, Writer &writer, size_t b, const Prepared &p, BatchResult &&res) {
+  writer.wait_room(b, 2 * r.workers.size() + 1);
+  BatchJob job;
+  job.res = std::move(res);
+  job.qlen_unmasked = p.qlen_unmasked;
+  r.names_of(b, job.names);
+  writer.submit(b, std::move(job));
+}
 void worker_main(const Run &r, Worker &w, std::atomic<size_t> &next, Writer &writer) {
   run_batches(
       r, w,
@@ -920,20 +1039,146 @@ void worker_main(const Run &r, Worker &w, std::atomic<size_t> &next, Writer &wri
         b = next.fetch_add(1);
         return b < r.nb;
       },
-      [&](size_t b, const Prepared &p, BatchResult &&res) {
-        writer.wait_room(b, 2 * r.workers.size() + 1);
-        BatchJob job;
-        job.res = std::move(res);
-        job.qlen_unmasked = p.qlen_unmasked;
-        r.names_of(b, job.names);
-        writer.submit(b, std::move(job));
-      });
+      [&](size_t b, const Prepared &p, BatchResult &&res) { submit_batch(r, writer, b, p, std::move(res)); });
 }
+
+// The same with the pages of every batch shared out (PRB_SPLIT): the workers are a team that takes the batches one after
+// the other, all of them each batch - everyone with a prb_qbatch of its own, made and given its accessibilities as ever.
+// Worker k begins with page k (its seed search started beside the accessibilities), then takes pages from the batch's
+// counter until none are left.  A page's hit set or pair set goes into slot p of the batch's one result, whoever searched
+// it; in the table modes everyone fills a table of its own, and when all have arrived the first worker merges the others'
+// into its own on the device and finishes it.  It hands the result to the writer - one BatchResult per batch, as ever -
+// and only then do the others go on (their contexts are not theirs while their tables are merged from).
+// A worker that fails raises `failed` with its message and ends; the others end at their next look, the main thread exits.
+struct Team {
+  struct Batch {
+    std::atomic<int> next_page{0};
+    BatchResult res;                // what the writer gets: the page slots, or the first worker's table
+    std::vector<BatchResult> table; // per worker: its own table (the table modes)
+    size_t arrived = 0, left = 0;
+    bool taken = false;             // the first worker has merged and handed on
+  };
+  const Run &r;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::map<size_t, std::shared_ptr<Batch>> batches;
+  bool failed = false;
+  std::string error;
+  std::vector<int64_t> pages_of_worker;
+
+  explicit Team(const Run &run) : r(run), pages_of_worker(run.workers.size(), 0) {}
+  std::shared_ptr<Batch> join(size_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::shared_ptr<Batch> &tb = batches[b];
+    if (!tb) {
+      tb = std::make_shared<Batch>();
+      tb->res = empty_result(r);
+      tb->table.resize(r.workers.size());
+      tb->next_page = (int)std::min<size_t>(r.workers.size(), (size_t)r.npages);
+    }
+    return tb;
+  }
+  void leave(size_t b, Batch &tb) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (++tb.left == r.workers.size()) batches.erase(b);
+  }
+  void fail(const std::string &msg) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      if (!failed) error = msg;
+      failed = true;
+    }
+    cv.notify_all();
+  }
+  bool has_failed() {
+    std::lock_guard<std::mutex> lk(mu);
+    return failed;
+  }
+  // blocks until `ready` holds (under the lock) - or somebody failed, which ends this worker too
+  template <class Ready> void wait(Ready ready) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return failed || ready(); });
+    if (failed) throw TeamError{""};
+  }
+  void signal(const std::function<void()> &change) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      change();
+    }
+    cv.notify_all();
+  }
+
+  // worker k's share of batch b; the first worker returns the batch's result, the others an empty one
+  BatchResult search(size_t b, size_t k, Worker &w, Prepared &p) {
+    const std::shared_ptr<Batch> tb = join(b);
+    BatchResult &mine = tb->table[k];
+    mine.mode = r.a.mode;
+    create_table(r, w, p.qb, mine);
+    for (int page = k < (size_t)r.npages ? (int)k : tb->next_page.fetch_add(1); page < r.npages; page = tb->next_page.fetch_add(1)) {
+      if (has_failed()) throw TeamError{""};
+      search_one_page(r, w, p.qb, page, mine, tb->res);
+      pages_of_worker[k]++;
+    }
+    signal([&] { tb->arrived++; });
+    BatchResult res;
+    if (k == 0) {
+      wait([&] { return tb->arrived == r.workers.size(); });
+      std::vector<BatchResult *> others;
+      for (size_t j = 1; j < tb->table.size(); j++) others.push_back(&tb->table[j]);
+      finish_table(r, w, mine, others);
+      res = std::move(tb->res);
+      res.top = std::move(mine.top);
+      res.prof = std::move(mine.prof);
+      res.tophits = std::move(mine.tophits);
+      signal([&] { tb->taken = true; });
+    } else {
+      wait([&] { return tb->taken; });
+      mine = BatchResult(); // (its table, empty by now, freed by its own worker)
+    }
+    prb_qbatch_destroy(p.qb);
+    p.qb = nullptr;
+    leave(b, *tb);
+    return res;
+  }
+};
+
+void team_main(const Run &r, size_t k, Team &team, Writer &writer) {
+  Worker &w = const_cast<Run &>(r).workers[k];
+  t_team_thread = true;
+  size_t next = 0;
+  try {
+    run_batches(
+        r, w,
+        [&](size_t &b) {
+          b = next++;
+          return b < r.nb;
+        },
+        [&](size_t b, const Prepared &p, BatchResult &&res) {
+          if (k == 0) submit_batch(r, writer, b, p, std::move(res));
+        },
+        [&](size_t b, Worker &me, Prepared &p) { return team.search(b, k, me, p); }, k < (size_t)r.npages ? (int)k : -1);
+  } catch (const TeamError &e) {
+    team.fail(e.msg);
+  }
+}
+
 void run_workers(Run &r, Writer &writer) {
-  std::atomic<size_t> next{0};
   std::vector<std::thread> threads;
-  for (Worker &w : r.workers) threads.emplace_back(worker_main, std::cref(r), std::ref(w), std::ref(next), std::ref(writer));
+  if (!r.split_pages) {
+    std::atomic<size_t> next{0};
+    for (Worker &w : r.workers) threads.emplace_back(worker_main, std::cref(r), std::ref(w), std::ref(next), std::ref(writer));
+    for (auto &t : threads) t.join();
+    return;
+  }
+  Team team(r);
+  for (size_t k = 0; k < r.workers.size(); k++) threads.emplace_back(team_main, std::cref(r), k, std::ref(team), std::ref(writer));
   for (auto &t : threads) t.join();
+  if (team.failed) die(team.error);
+  if (r.split_given && r.split_knob == kSplitPages) {
+    std::string per;
+    for (size_t k = 0; k < team.pages_of_worker.size(); k++) per += (k ? "," : "") + std::to_string(team.pages_of_worker[k]);
+    std::fprintf(stderr, "page split: %zu batch(es), pages per worker: %s\n", r.nb, per.c_str());
+  }
 }
 
 // One process per GPU.  The gathers run on a thread of their own, in round order, behind the search of the next batch
@@ -1051,11 +1296,13 @@ int ris_main(int argc, char **argv) {
   const std::string err = prb::read_fasta(r.a.in, r.names, r.seqs);
   if (!err.empty()) die(err);
   const std::vector<int> devices = rank_setup(r);
+  split_setup(r);
   open_workers(r, devices);
   if (r.rank_mode) r.comm = join_ranks(r);
   read_seq_tables(r);
   open_output(r);
   plan_batches(r);
+  plan_split(r);
   Writer writer(r);
   if (r.rank_mode) run_ranks(r, writer);
   else run_workers(r, writer);
