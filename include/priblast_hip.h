@@ -58,9 +58,38 @@ typedef struct prb_ris_opts {
   int32_t drop_out_w_gap;     /* -x 16 */
   int32_t min_helix_length;   /* -m 3  */
   int32_t output_style;       /* -s 0  */
+  int32_t distinct_sites;     /* -u: 0 = every final hit (the default), 1 = the distinct sites of each pair only, see below;
+                               * anything else is PRB_ERR_ARG.  Ignored for last_stage 1 and 2 */
 } prb_ris_opts;
+#ifdef __cplusplus
+static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: nine fields, distinct_sites the last one");
+#endif
 
 /* POD form of hit.hpp:38-118 (`Hit`) */
+/* ---- distinct interaction sites (opts->distinct_sites = 1, `ris -u`) ----
+ * CheckRedundancy (rna_interaction_search.cpp:387-424) removes a final hit only when another one contains it; hits that
+ * merely overlap all survive, so a binding site comes out as a dozen hits shifted by a few bases.  With distinct_sites
+ * the final hits of every pair are thinned by greedy non-maximum suppression on the device, between the final filter and
+ * the traceback:
+ *   extent     of a final hit: the rectangle [q_sp, q_sp + q_len - 1] x [db_sp, db_sp + db_len - 1] of its record,
+ *              inclusive ends (the coordinates CheckRedundancy compares).  Two hits INTERSECT when their query intervals
+ *              and their target intervals each share at least one position
+ *   pair       the final hits of one query with one db_id of one page
+ *   order      within a pair: e_tot ascending, compared as doubles (-0.0 == +0.0); equal values in output order (the
+ *              hit's place in the list prb_search_page returns)
+ *   selection  the pair's hits are walked in that order; a hit is kept if and only if it intersects no hit kept before
+ *              it.  Dropped hits suppress nothing.  Kept hits stay in output order
+ * The order is total, a pair lies within one page and a sub-batch is a range of whole queries, so the result depends
+ * neither on how the batch is cut up, nor on PRB_SEARCH_PAIRS / PRB_GAPPED_CHUNK_HITS / page residency, nor on PRB_SPLIT
+ * or the order of the pages.  A kept hit is, field for field and base pair for base pair (SURVEY a17 quirk included), the
+ * hit that the search without the option returns; only bp_offset may differ.  Every mode takes the thinned list:
+ * prb_search_page, _summary, _top, _tophits, _profile.  The stage counts keep their meaning - counts[2] = the final hits
+ * after the redundancy filter, BEFORE the selection - so counts[2] minus the number of hits returned (prb_hitset_size;
+ * the sum of prb_pair_summary.hits) is the number of hits the selection dropped.
+ * A top-N pair table, a top-N hit table and a profile table each hold pages searched with one value of distinct_sites:
+ * prb_search_page_top / _tophits / _profile refuse a second value (PRB_ERR_ARG, the table untouched), and the three
+ * prb_*_merge refuse two tables of different values unless one of them has merged no page. */
+
 typedef struct prb_hit {
   int32_t q_sp, db_sp;          /* start in the query / in the page's reversed db text */
   int32_t q_len, db_len;
@@ -98,6 +127,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4; prb_profset_merge: 1);
  * "tophits" (prb_search_page_tophits: the merge into the top-N hit table, the scan of the kept hits' pair counts and the
  *   gather of their lists; launches = 4 per sub-batch, and per prb_tophits_merge);
+ * "distinct" (opts->distinct_sites: the pairs' head flags, the two selection kernels and the selection of the kept hits,
+ *   launches = 4 per sub-batch with final hits, and 2 more - the gathers of the records and of their pre-gapped
+ *   indices - when a hit is dropped; nothing when the option is off; prb_distinct_sites: launches = 3);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -177,6 +209,12 @@ const int32_t *prb_hitset_basepairs(const prb_hitset *hs, int64_t *count);
 /* number of hits per stage for the whole call: seeds, after ungapped+filter, final */
 void prb_hitset_counts(const prb_hitset *hs, int64_t counts[3]);
 void prb_hitset_free(prb_hitset *hs);
+
+/* The selection of opts->distinct_sites for a caller's own list of final hits in host memory (hit sets gathered from
+ * several ranks, the records of a `ris -b` file ...), by the same kernels: keep[i] = 1 for the hits kept, else 0.  A pair
+ * is a maximal run of consecutive records with equal (query, db_id); the order inside a run is e_tot, then the index.
+ * The runs need not be sorted by db_sp.  n <= 2^31 - 1; n = 0 does nothing. */
+int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep);
 
 /* ---- per-pair summaries (`ris -t`): the final hits reduced on the device, one record per (query, database
  * sequence) pair that has at least one final hit.  The hits are exactly those prb_search_page(..., 3, ...) returns

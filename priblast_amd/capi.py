@@ -22,7 +22,7 @@ P = ctypes.POINTER
 class RisOpts(ctypes.Structure):
     _fields_ = [("max_seed_length", c_i32), ("hybrid_threshold", c_dbl), ("interaction_threshold", c_dbl),
                 ("final_threshold", c_dbl), ("drop_out_wo_gap", c_i32), ("drop_out_w_gap", c_i32),
-                ("min_helix_length", c_i32), ("output_style", c_i32)]
+                ("min_helix_length", c_i32), ("output_style", c_i32), ("distinct_sites", c_i32)]
 
 
 class Hit(ctypes.Structure):
@@ -107,6 +107,7 @@ SYMBOLS = {
     "prb_hitset_basepairs": (ctypes.c_void_p, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_free": (None, [ctypes.c_void_p]),
+    "prb_distinct_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "prb_search_page_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts),
                                                P(ctypes.c_void_p)]),
     "prb_pairset_size": (c_i64, [ctypes.c_void_p]),
@@ -408,6 +409,16 @@ def search_page(ctx, qb, db, page, opts=None, last_stage=3):
     The arrays are views of the hit set (freed when the last of them goes away)."""
     hs = search_page_hs(ctx, qb, db, page, opts, last_stage)
     return hs.hits, hs.bp, hs.counts
+
+
+def distinct_sites(ctx, hits):
+    """prb_distinct_sites: hits = structured array HIT_DTYPE (a caller's list of final hits) -> uint8 [n], 1 for the hits
+    that the selection of opts.distinct_sites keeps within their run of equal (query, db_id)"""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    keep = np.zeros(len(hits), np.uint8)
+    _check(lib().prb_distinct_sites(ctx.h, hits.ctypes.data if len(hits) else None, len(hits),
+                                    keep.ctypes.data if len(hits) else None))
+    return keep
 
 
 def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):

@@ -98,6 +98,7 @@ void prb_ris_opts_default(prb_ris_opts *o) {
   o->drop_out_w_gap = 16;
   o->min_helix_length = 3;
   o->output_style = 0;
+  o->distinct_sites = 0;
 }
 
 int prb_search_const_upload(prb_ctx *ctx); // capi_pages.hip
@@ -234,6 +235,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->tophits_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "distinct") == 0) {
+    if (ms) *ms = ctx->distinct_timer.ms;
+    if (launches) *launches = ctx->distinct_timer.launches;
+    return PRB_OK;
+  }
   auto it = ctx->timers.find(stage);
   if (ms) *ms = it == ctx->timers.end() ? 0.0 : it->second.ms;
   if (launches) *launches = it == ctx->timers.end() ? 0 : it->second.launches;
@@ -246,6 +252,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
     ctx->top_timer = prb::StageTimer{};
     ctx->profile_timer = prb::StageTimer{};
     ctx->tophits_timer = prb::StageTimer{};
+    ctx->distinct_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }
 }

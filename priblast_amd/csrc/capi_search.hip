@@ -34,6 +34,7 @@ struct SearchKnobs {
   int skip_tiers;      // experiment: bit t set = LDS tier t is left out behind the front kernel
   bool trace_no_long, trace_no_slots; // testing: no long traces; re-extend every final hit as well
   int trace_long_cap, trace_slot_cap; // testing: pretend the slots are shorter
+  int distinct_lds_hits; // testing: the LDS capacity of the distinct-sites selection (runs beyond it keep their state in HBM)
   bool debug_rows, debug_mem;
 };
 static bool env_off(const char *e) { return e && atoi(e) == 0; }
@@ -71,6 +72,8 @@ static SearchKnobs read_search_knobs() {
   k.trace_no_slots = getenv("PRB_TRACE_NO_SLOTS") != nullptr;
   e = getenv("PRB_TRACE_SLOT_CAP");
   k.trace_slot_cap = e ? std::min(kTraceCap, atoi(e)) : kTraceCap;
+  e = getenv("PRB_DISTINCT_LDS_HITS");
+  k.distinct_lds_hits = e ? atoi(e) : kSiteLdsHits;
   k.debug_rows = getenv("PRB_DEBUG_ROWS") != nullptr;
   k.debug_mem = getenv("PRB_DEBUG_MEM") != nullptr;
   return k;
@@ -156,9 +159,8 @@ static void call_front_free(SubSearch &s) {
 }
 
 // ------------------------------------------------------------------------- lists of hits
-static HitSoA carve_hits(DevBuf &b, int64_t n) {
+static HitSoA carve_hits(uint8_t *p, int64_t n) {
   HitSoA h;
-  uint8_t *p = b.as<uint8_t>();
   const size_t n8 = ((size_t)n + 1) & ~(size_t)1; // keep the double arrays 8-byte aligned
   h.e_acc = reinterpret_cast<double *>(p);
   h.e_hyb = h.e_acc + n8;
@@ -173,6 +175,7 @@ static HitSoA carve_hits(DevBuf &b, int64_t n) {
   h.query = ip + 6 * n8;
   return h;
 }
+static HitSoA carve_hits(DevBuf &b, int64_t n) { return carve_hits(b.as<uint8_t>(), n); }
 static size_t hits_bytes(int64_t n) { return (((size_t)n + 1) & ~(size_t)1) * kHitBytes + 64; }
 // the hits from `first` on, as a list of their own
 static HitSoA offset_hits(const HitSoA &h, int64_t first) {
@@ -1059,6 +1062,53 @@ static int final_sort_filter(SubSearch &s) {
   return PRB_OK;
 }
 
+// ------------------------------------------------------------------------- distinct sites
+// The selection of opts.distinct_sites over the n hits of `h` (sorted, or a caller's list): keep flags in w.keep.  The
+// scratch is what the redundancy filter has left behind (w.endKey, w.pmax, w.state) and a list of the gapped cascade.
+static int select_sites(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, int lds_hits) {
+  const size_t N = (size_t)n;
+  int rc;
+  if (n > INT32_MAX) {
+    set_error("distinct sites: more than 2^31 - 1 final hits in one list");
+    return PRB_ERR_ARG;
+  }
+  if ((rc = w.pairHead.ensure(N)) || (rc = w.keep.ensure(N)) || (rc = w.state.ensure(N)) || (rc = w.endKey.ensure(N * 4)) ||
+      (rc = w.pmax.ensure(N * 4)) || (rc = w.listA.ensure((size_t)site_long_runs_max(n) * 4)) || (rc = w.pending.ensure(16)))
+    return rc;
+  PRB_HIP(launch_pair_heads(h.query, h.db_id, n, w.pairHead.as<uint8_t>(), ctx->stream));
+  const SiteScratch scratch{w.listA.as<uint32_t>(), w.pending.as<uint32_t>(), w.endKey.as<int32_t>(), w.pmax.as<int32_t>(), w.state.as<uint8_t>()};
+  PRB_HIP(launch_site_select(h, n, w.pairHead.as<uint8_t>(), lds_hits, scratch, w.keep.as<uint8_t>(), ctx->stream));
+  return PRB_OK;
+}
+
+// opts.distinct_sites: the final hits F thinned to the distinct sites of each pair (include/priblast_hip.h), before the
+// traceback - the last stage that touches every final hit - so that a dropped hit costs no traceback, no copy and no
+// formatting.  F and w.subset (the pre-gapped indices the traceback and the `first` flags go by) are compacted alike, s.nfin
+// becomes the number kept; everything behind works on that list unchanged.  (counts[2] was taken before.)
+static int distinct_sites(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  if ((rc = select_sites(ctx, w, s.F, s.nfin, s.k.distinct_lds_hits))) return rc;
+  int64_t nkeep = 0;
+  if ((rc = w.surv.ensure((size_t)s.nfin * 4)) || (rc = w.count.ensure(16))) return rc;
+  if ((rc = select_flagged(ctx, w, nullptr, w.keep.as<uint8_t>(), w.surv.as<uint32_t>(), (size_t)s.nfin, &nkeep))) return rc;
+  if (nkeep <= 0 || nkeep > s.nfin) { // (the best hit of every pair is kept)
+    set_error("distinct sites: " + std::to_string(nkeep) + " of " + std::to_string(s.nfin) + " final hits kept");
+    return PRB_ERR_STATE;
+  }
+  if (nkeep == s.nfin) return ctx->time_end(ctx->distinct_timer, 4);
+  if ((rc = w.hitsTmp.ensure(hits_bytes(nkeep))) || (rc = w.subset2.ensure((size_t)nkeep * 4))) return rc;
+  const HitSoA kept = carve_hits(w.hitsTmp, nkeep);
+  PRB_HIP(launch_gather_hits(s.F, w.surv.as<uint32_t>(), kept, nkeep, ctx->stream));
+  PRB_HIP(launch_gather_u32(w.subset.as<uint32_t>(), w.surv.as<uint32_t>(), w.subset2.as<uint32_t>(), nkeep, ctx->stream));
+  std::swap(w.subset, w.subset2);
+  s.F = kept;
+  s.nfin = nkeep;
+  return ctx->time_end(ctx->distinct_timer, 6);
+}
+
 // ------------------------------------------------------------------------- traceback
 // Base pairs of the final hits: from the trace slots of the extension pass; the few hits the slots cannot describe
 // (wave-kernel hits, chains longer than a slot) are extended again.  Leaves the "traceback" bracket open: what an
@@ -1422,6 +1472,7 @@ static int search_range(const PageSearch &p, const CandBatch &b, const std::func
   call_front_free(s);
   if ((rc = final_sort_filter(s))) return rc;
   if (s.nfin == 0) return PRB_OK;
+  if (s.opts.distinct_sites && (rc = distinct_sites(s))) return rc;
   if ((rc = traceback(s))) return rc;
   return emit_final(s);
 }
@@ -1446,6 +1497,10 @@ int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, 
       opts->min_helix_length < 1 || opts->min_helix_length > 16 || opts->max_seed_length < 1 || opts->max_seed_length > 63) {
     set_error("unsupported option: need 0 <= -x <= 30, 1 <= -y <= 15 (beyond that the reference reads outside its "
               "31-entry loop tables), 1 <= -m <= 16, 1 <= -l <= 63 (the seed search keeps a path of 64 characters)");
+    return PRB_ERR_ARG;
+  }
+  if (opts->distinct_sites != 0 && opts->distinct_sites != 1) {
+    set_error(std::string(fn) + ": distinct_sites must be 0 or 1 (got " + std::to_string(opts->distinct_sites) + ")");
     return PRB_ERR_ARG;
   }
   return PRB_OK;
@@ -1672,6 +1727,49 @@ extern "C" {
 int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
                     prb_hitset **out) {
   return search_page(ctx, qb, db, page, opts, last_stage, SearchMode::kRecords, out);
+}
+
+// the caller's records as a list of the search's own layout (the fields the selection reads; the others stay zero), one
+// upload; the flags come back in one copy
+int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep) {
+  if (!ctx || n < 0 || (n > 0 && (!hits || !keep))) {
+    set_error("prb_distinct_sites: bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (n == 0) return PRB_OK;
+  if (n > INT32_MAX) {
+    set_error("prb_distinct_sites: more than 2^31 - 1 hits");
+    return PRB_ERR_ARG;
+  }
+  PRB_HIP(hipSetDevice(ctx->device));
+  SearchWs &w = ws_of(ctx);
+  const SearchKnobs knobs = read_search_knobs();
+  int rc;
+  if ((rc = w.hitsTmp.ensure(hits_bytes(n)))) return rc;
+  try {
+    std::vector<uint8_t> host(hits_bytes(n), 0);
+    const HitSoA hh = carve_hits(host.data(), n);
+    for (int64_t i = 0; i < n; i++) {
+      hh.q_sp[i] = hits[i].q_sp;
+      hh.db_sp[i] = hits[i].db_sp;
+      hh.q_len[i] = hits[i].q_len;
+      hh.db_len[i] = hits[i].db_len;
+      hh.db_id[i] = hits[i].db_id;
+      hh.query[i] = hits[i].query;
+      hh.e_tot[i] = hits[i].e_tot;
+    }
+    PRB_HIP(hipMemcpyAsync(w.hitsTmp.p, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the copy is staged, `host` may go)
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_distinct_sites: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  if ((rc = ctx->time_begin())) return rc;
+  if ((rc = select_sites(ctx, w, carve_hits(w.hitsTmp, n), n, knobs.distinct_lds_hits))) return rc;
+  if ((rc = ctx->time_end(ctx->distinct_timer, 3))) return rc;
+  PRB_HIP(hipMemcpyAsync(keep, w.keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  return PRB_OK;
 }
 
 int prb_search_page_summary(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_pairset **out) {

@@ -59,6 +59,11 @@ static int merge_page(const char *fn_name, const char *what, const char *finish_
     set_error(fn + ": the " + table + " is finished (" + finish_fn + ")");
     return PRB_ERR_STATE;
   }
+  if (t->distinct >= 0 && opts->distinct_sites != t->distinct) {
+    set_error(fn + ": the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
+              std::to_string(opts->distinct_sites) + ")");
+    return PRB_ERR_ARG;
+  }
   if (!t->db) {
     t->db = db;
     t->merged.assign(db->pages.size(), 0);
@@ -75,6 +80,7 @@ static int merge_page(const char *fn_name, const char *what, const char *finish_
     return rc;
   }
   for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
+  t->distinct = opts->distinct_sites;
   delete hs;
   return PRB_OK;
 }
@@ -138,6 +144,9 @@ static int merge_tables_guard(const char *fn_name, const char *what, const prb_c
   if (dst->finished || src->finished) return refuse("one of the " + tables + " is finished");
   if (dst->nq != src->nq) return refuse("the " + tables + " were made for " + std::to_string(dst->nq) + " and " + std::to_string(src->nq) + " queries");
   if (dst->qlen != src->qlen) return refuse("the " + tables + " were made for queries of different lengths");
+  if (dst->distinct >= 0 && src->distinct >= 0 && dst->distinct != src->distinct)
+    return refuse("the " + tables + " hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
+                  std::to_string(src->distinct));
   if (dst->db && src->db) {
     if (dst->merged.size() != src->merged.size())
       return refuse("the " + tables + " hold pages of databases of " + std::to_string(dst->merged.size()) + " and " +
@@ -161,6 +170,8 @@ static void move_pages(MergeTable *dst, MergeTable *src) {
     dst->counts[i] += src->counts[i];
     src->counts[i] = 0;
   }
+  if (dst->distinct < 0) dst->distinct = src->distinct;
+  src->distinct = -1;
   src->db = nullptr;
   src->merged.clear();
 }

@@ -352,6 +352,7 @@ struct MergeTable {
   std::vector<uint8_t> merged; // per page of db
   bool broken = false;         // a merge failed part way
   bool finished = false;       // prb_*set_finish: the records are on the host, the device memory is released
+  int32_t distinct = -1;       // opts->distinct_sites of the merged pages (-1: none yet)
   int64_t counts[3] = {0, 0, 0};
 };
 } // namespace prb

@@ -138,6 +138,24 @@ hipError_t launch_pair_heads(const int32_t *query, const int32_t *db_id, int64_t
 // from `ends` (4 ints per hit, launch_bp_ends)
 hipError_t launch_pair_fold(const HitSoA &h, int64_t n, const uint32_t *start, int64_t npairs, const int32_t *ends, void *out,
                             hipStream_t s);
+// ---- distinct interaction sites (prb_ris_opts::distinct_sites) over a final, sorted hit list ----
+// keep[i] = 1 for the hits that the greedy selection of include/priblast_hip.h keeps within their run, 0 for the others;
+// head = launch_pair_heads' flags (a caller's list: any flags that start a run at hit 0).  Two launches: runs of up to
+// 64 hits several per wavefront, state in registers; the longer ones, which the first launch lists in w.long_list, a
+// workgroup each - with rectangles and state in LDS up to lds_hits hits (clamped to 1 .. kSiteLdsHits; below 64 it
+// also lowers the first launch's limit, so that tests reach the other paths with short runs), beyond that read from
+// the list with the state in w.lo / w.hi / w.state.  Nothing comes back to the host.  n <= INT32_MAX.
+constexpr int kSiteLdsHits = 2048; // 31 bytes of LDS per hit
+constexpr int kSiteLongGrid = 1024;
+inline int64_t site_long_runs_max(int64_t n) { return n / 2 + 1; } // a listed run has two hits at least
+struct SiteScratch {
+  uint32_t *long_list; // site_long_runs_max(n) entries
+  uint32_t *nlong;     // one counter
+  int32_t *lo, *hi;    // n entries each
+  uint8_t *state;      // n entries
+};
+hipError_t launch_site_select(const HitSoA &h, int64_t n, const uint8_t *head, int lds_hits, const SiteScratch &w, uint8_t *keep,
+                              hipStream_t s);
 // ---- top-N table (prb_search_page_top) ----
 constexpr int kTopMaxN = 1024; // the largest N: the set's keys and a candidate buffer of as many fit a workgroup's LDS
 // merges the pair records rec[0, nrec) (prb_pair_summary, launch_pair_fold's output for queries [q0, q1), ascending by

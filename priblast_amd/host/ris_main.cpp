@@ -31,9 +31,11 @@
 // reach the host.  `-q` is refused with -t, -n, -b and in rank mode, as -t is.  `ris -k N` writes the normal result
 // lines (or, with -b, the normal binary records) of each query's N final hits of lowest interaction energy only, best
 // first: a table on the GPU (prb_search_page_tophits) takes every page of a batch and keeps those hits with their base
-// pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.
+// pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.  `ris -u` keeps only the distinct
+// interaction sites of each (query, target) pair - greedy non-maximum suppression on the GPU, before the traceback
+// (prb_ris_opts::distinct_sites) - and combines with every mode: each of them takes the thinned list.
 //
-// How the file is laid out.  The switches -t -n -q -k -b have one table (kSwitchTable) that every refusal is generated
+// How the file is laid out.  The switches -t -n -q -k -b -u have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
 // join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
 // (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
@@ -110,6 +112,10 @@ void usage() {
             "    -k INT    only the INT interaction sites of lowest interaction energy per query, best first, as normal\n"
             "              result lines (-s and -b are honoured; ties in output order; 1 <= INT <= 1024; not with -t, -n, -q,\n"
             "              nor with WORLD_SIZE > 1)\n"
+            "    -u        only the distinct interaction sites of each query-target pair: a pair's hits are taken best\n"
+            "              first (interaction energy, ties in output order), and a hit is kept only if its query range and\n"
+            "              its target range do not both overlap those of a hit kept before it; the lines are lines of the\n"
+            "              run without -u (with every other switch; -t, -n, -q and -k then count and rank the kept hits)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -138,7 +144,7 @@ enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits };
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -153,6 +159,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'q', "per-position profile lines", bit(kT) | bit(kN) | bit(kB), -1, true},
     {'k', "the N best interaction sites per query", bit(kT) | bit(kN) | bit(kQ), -1, true},
     {'b', "binary hit records", 0, -1, false},
+    {'u', "the distinct interaction sites of each pair", 0, -1, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -509,7 +516,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:u")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -526,6 +533,7 @@ Args parse_args(int argc, char **argv) {
     case 'b': a.given[kB] = true; break;
     case 't': a.given[kT] = true; break;
     case 'q': a.given[kQ] = true; break;
+    case 'u': a.given[kU] = true, a.o.distinct_sites = 1; break;
     case 'n': a.given[kN] = true, a.top = parse_count(optarg); break;
     case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
     case 'a':
