@@ -30,6 +30,8 @@ struct SearchKnobs {
   int64_t gapped_chunk_hits;
   int first_tier;      // the cascade starts at this kernel (4 = the wave-per-hit kernel alone), so the rarely taken kernels see every hit
   bool wave_hbm, no_resume, front_paired, front, handover;
+  GapTierKnobs tiers;  // the experiments inside the LDS tiers (search_kernels.hpp)
+  bool filter_tiles;   // the redundancy filter scans windows of the list in LDS (0: the plain kernels)
   int resume_cap;      // > 0, testing: pools that run out (those hits are redone instead)
   int skip_tiers;      // experiment: bit t set = LDS tier t is left out behind the front kernel
   bool trace_no_long, trace_no_slots; // testing: no long traces; re-extend every final hit as well
@@ -66,6 +68,16 @@ static SearchKnobs read_search_knobs() {
   k.skip_tiers = e ? atoi(e) : 0;
   k.front = !env_off(getenv("PRB_GAPPED_FRONT"));
   k.handover = !env_off(getenv("PRB_GAPPED_HANDOVER"));
+  k.tiers.pair = !env_off(getenv("PRB_GAPPED_PAIR"));
+  k.tiers.pool = !env_off(getenv("PRB_GAPPED_POOL"));
+  GapTierKnobs &t = k.tiers;
+  if ((e = getenv("PRB_GAPPED_LDS_PAD"))) sscanf(e, "%d,%d,%d", &t.pad[1], &t.pad[2], &t.pad[3]);
+  t.pad_set = e != nullptr;
+  if ((e = getenv("PRB_GAPPED_PERIOD"))) sscanf(e, "%d,%d,%d,%d", &t.period[0], &t.period[1], &t.period[2], &t.period[3]);
+  t.period_set = e != nullptr;
+  if ((e = getenv("PRB_GAPPED_EARLY"))) sscanf(e, "%d,%d,%d,%d", &t.early[0], &t.early[1], &t.early[2], &t.early[3]);
+  t.early_set = e != nullptr;
+  k.filter_tiles = !env_off(getenv("PRB_FILTER_TILES"));
   k.trace_no_long = getenv("PRB_TRACE_NO_LONG") != nullptr;
   e = getenv("PRB_TRACE_LONG_CAP");
   k.trace_long_cap = e ? std::max(1, atoi(e)) : 1024;
@@ -276,7 +288,7 @@ struct MaxOp {
 
 // CheckRedundancy on the sorted list `h`; writes the indices of the survivors (ascending) to
 // w.surv and returns their number.
-static int filter_hits(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, double thr, int64_t *nsurv) {
+static int filter_hits(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, double thr, bool tiles, int64_t *nsurv) {
   int rc;
   const size_t N = (size_t)n;
   *nsurv = 0;
@@ -291,7 +303,7 @@ static int filter_hits(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, do
     return rc;
   for (int round = 0;; round++) {
     PRB_HIP(hipMemsetAsync(w.pending.p, 0, 4, ctx->stream));
-    PRB_HIP(launch_filter_round(h, n, w.pmax.as<int64_t>(), w.state.as<uint8_t>(), w.pending.as<int32_t>(), ctx->stream));
+    PRB_HIP(launch_filter_round(h, n, w.pmax.as<int64_t>(), w.state.as<uint8_t>(), w.pending.as<int32_t>(), tiles, ctx->stream));
     int32_t pend = 0;
     PRB_HIP(hipMemcpyAsync(&pend, w.pending.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     PRB_HIP(hipStreamSynchronize(ctx->stream));
@@ -301,7 +313,7 @@ static int filter_hits(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, do
       return PRB_ERR_STATE;
     }
   }
-  PRB_HIP(launch_filter_final(h, n, w.pmax.as<int64_t>(), w.state.as<uint8_t>(), w.keep.as<uint8_t>(), ctx->stream));
+  PRB_HIP(launch_filter_final(h, n, w.pmax.as<int64_t>(), w.state.as<uint8_t>(), w.keep.as<uint8_t>(), tiles, ctx->stream));
   return select_flagged(ctx, w, nullptr, w.keep.as<uint8_t>(), w.surv.as<uint32_t>(), N, nsurv);
 }
 
@@ -641,7 +653,7 @@ static int sort_filter_ungapped(SubSearch &s) {
     for (DevBuf *b : {&w.hitsB, &w.kE, &w.kL, &w.kQ, &w.kP, &w.kTmp, &w.kTmp2, &w.idxA, &w.idxB, &w.sortTmp}) b->release();
   mem_note("sorted", w);
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = filter_hits(ctx, w, B, s.nf, s.opts.interaction_threshold, &s.nung))) return rc;
+  if ((rc = filter_hits(ctx, w, B, s.nf, s.opts.interaction_threshold, s.k.filter_tiles, &s.nung))) return rc;
   if ((rc = ctx->time_end("filter", 3))) return rc;
   s.hs->counts[1] += s.nung;
   if (s.nung == 0) return PRB_OK;
@@ -840,7 +852,7 @@ static int run_cascade(SubSearch &s, Cascade &c, int handover, bool hold_wave) {
     PRB_HIP(launch_gapped_lds(s.U, s.G, l.m, l.cur, s.qb->view, s.pd, s.sc, s.eo, 0, tier, w.overflow.as<uint8_t>(), w.tierOf.as<uint8_t>(),
                               s.first, w.ntrace.as<int32_t>(), w.trace.as<uint16_t>(), nullptr, nullptr,
                               w.count.as<unsigned long long>() + 1, tier >= 1 ? c.rs[tier - 1] : kNoResume,
-                              tier < kLdsTiers - 1 ? c.rs[tier] : kNoResume, ctx->stream, handover, w.accScratch.as<double>()));
+                              tier < kLdsTiers - 1 ? c.rs[tier] : kNoResume, s.k.tiers, ctx->stream, handover, w.accScratch.as<double>()));
     int64_t rest = 0;
     if ((rc = advance(s, l, &rest))) return rc;
     if (s.k.debug_rows)
@@ -1047,7 +1059,7 @@ static int final_sort_filter(SubSearch &s) {
   if ((rc = sort_hits(s, w.hitsB.as<HitRec>(), S, s.ngap, s.sb, &perm))) return rc;
   if ((rc = ctx->time_end("sort", 9))) return rc;
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = filter_hits(ctx, w, S, s.ngap, s.opts.final_threshold, &s.nfin))) return rc;
+  if ((rc = filter_hits(ctx, w, S, s.ngap, s.opts.final_threshold, s.k.filter_tiles, &s.nfin))) return rc;
   if ((rc = ctx->time_end("filter", 3))) return rc;
   s.hs->counts[2] += s.nfin;
   if (s.nfin == 0) return PRB_OK;
@@ -1183,7 +1195,7 @@ static int traceback(SubSearch &s) {
     } else {
       PRB_HIP(launch_gapped_lds(s.U, s.G, m, w.subset2.as<uint32_t>(), s.qb->view, s.pd, s.sc, s.eo, 2, t, nullptr, nullptr, s.first, nullptr,
                                 nullptr, w.bpOff2.as<int64_t>(), w.bpOut.as<int32_t>(), w.count.as<unsigned long long>() + 1, kNoResume,
-                                kNoResume, ctx->stream, 0, w.accScratch.as<double>()));
+                                kNoResume, s.k.tiers, ctx->stream, 0, w.accScratch.as<double>()));
     }
     PRB_HIP(hipStreamSynchronize(ctx->stream)); // the staging buffers are reused by the next tier
   }

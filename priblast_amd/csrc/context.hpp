@@ -45,7 +45,7 @@ struct prb_ctx {
   prb::RaccessTables ra_tables;
   prb::FmathTables fm_tables;
   prb::RaConst ra_const{};
-  // int tables for the search stages (search_kernels.hip)
+  // int tables for the search stages (SearchConst, search_kernels.hpp)
   void *search_const = nullptr;
   void *search_ws = nullptr;   // prb::SearchWs, search_host.hpp
   int64_t slow_hits = 0;       // extensions that went through the HBM-scratch fallback kernel

@@ -1610,22 +1610,6 @@ __device__ __forceinline__ void hit_handover(const GapArgs &a, int64_t w, const 
   a.tier_out[x] = (uint8_t)(kHandoverMark | (a.tier_id & kMarkTier));
 }
 
-// total base pairs of list entry w = complementary positions of the ungapped diagonal
-// (GetBasePair, rna_interaction_search.cpp:371-385) + the pairs traced by the two extensions
-__global__ __launch_bounds__(256) void k_bp_count(HitSoA in, int64_t n, const uint32_t *__restrict__ subset, QBatchDev qb,
-                                                  PageDev pg, SearchConst sc, const int32_t *__restrict__ ntrace,
-                                                  int32_t *bp_count) {
-  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (w >= n) return;
-  const int64_t x = subset ? (int64_t)subset[w] : w;
-  const uint8_t *qs = qb.enc + qb.off[in.query[x]] + in.q_sp[x];
-  const uint8_t *ds = pg.seqs + in.db_sp[x];
-  const int len = US(in.q_len[x]);
-  int c = 0;
-  for (int t = 0; t < len; t++) c += diag_pairs(sc, qs[t], ds[t]);
-  bp_count[w] = c + (ntrace[x] & 0xFFFF) + (int)((uint32_t)ntrace[x] >> 16);
-}
-
 // LDS form.  The grid is what is resident at once; every group takes hits from a global work
 // counter.  The groups of a wavefront share one loop whose body is "one anti-diagonal of whatever
 // hit / direction the group is at", and they change direction / hit only at the iterations that
@@ -1843,27 +1827,20 @@ size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec) {
 }
 
 namespace {
-template <class T, class Rec> hipError_t launch_tier(GapArgs a, int mode, hipStream_t s) {
+template <class T, class Rec> hipError_t launch_tier(GapArgs a, int mode, const GapTierKnobs &k, hipStream_t s) {
   const int64_t want = (a.n + T::kGroups - 1) / T::kGroups;
   const dim3 grid((unsigned)std::min<int64_t>(want, 256 * T::kWgPerCu)), blk(T::kG * T::kGroups);
   if (hipError_t e = hipMemsetAsync(a.next_work, 0, sizeof(unsigned long long), s); e != hipSuccess) return e;
   if constexpr (T::kPairSteps) {
-    const char *pe = getenv("PRB_GAPPED_PAIR"); // (read per launch: the tests switch it inside one process)
-    const bool pair = !(pe && atoi(pe) == 0);
-    if (pair) {
-      const char *pp = getenv("PRB_GAPPED_POOL"); // (likewise: 0 = each group fills its own cells)
-      a.pool = !(pp && atoi(pp) == 0);
+    if (k.pair) {
+      a.pool = k.pool;
       if (mode == 0) hipLaunchKernelGGL((k_gapped_lds<0, T, Rec, true>), grid, blk, 0, s, a);
       else hipLaunchKernelGGL((k_gapped_lds<2, T, Rec, true>), grid, blk, 0, s, a);
       return hipGetLastError();
     }
   }
-  size_t pad = 0; // experiment (PRB_GAPPED_LDS_PAD="b1,b2,b3"): unused dynamic LDS per workgroup of tiers 1 - 3, i.e. fewer wavefronts per compute unit
-  if (const char *pe = getenv("PRB_GAPPED_LDS_PAD")) {
-    int b[4] = {0, 0, 0, 0};
-    sscanf(pe, "%d,%d,%d", &b[1], &b[2], &b[3]);
-    pad = (size_t)b[a.tier_id < 4 ? a.tier_id : 0];
-  }
+  // experiment (GapTierKnobs::pad): unused dynamic LDS per workgroup of tiers 1 - 3, i.e. fewer wavefronts per compute unit
+  const size_t pad = k.pad_set ? (size_t)k.pad[a.tier_id < kLdsTiers ? a.tier_id : 0] : 0;
   if (mode == 0) hipLaunchKernelGGL((k_gapped_lds<0, T, Rec, false>), grid, blk, pad, s, a);
   else hipLaunchKernelGGL((k_gapped_lds<2, T, Rec, false>), grid, blk, 0, s, a);
   return hipGetLastError();
@@ -1874,31 +1851,25 @@ hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint
                              const PageDev &pg, const SearchConst &sc, ExtOpts o, int mode, int tier, uint8_t *overflow,
                              uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count, uint16_t *trace,
                              const int64_t *bp_off, int32_t *bp_out, unsigned long long *next_work, const GapResume &rin,
-                             const GapResume &rout, hipStream_t s, int handover, double *acc_scratch) {
+                             const GapResume &rout, const GapTierKnobs &knobs, hipStream_t s, int handover, double *acc_scratch) {
   if (n <= 0) return hipSuccess;
   GapArgs a{in,      out,   n,      subset, qb,        pg,         sc, o, overflow, tier_out, tier, first_flag, bp_count,
             trace,   bp_off, bp_out, next_work, rin,     rout};
   a.handover = mode == 0 ? handover : 0;
   a.acc_scratch = acc_scratch;
   if (((tier == 1 || tier == 2) && Tier1::kAccGlobal || tier == 0 && Tier0::kAccGlobal) && !acc_scratch) return hipErrorInvalidValue;
-  if (const char *pe = getenv("PRB_GAPPED_PERIOD")) { // experiment: "p0,p1,p2,p3" lockstep iterations between boundaries, per tier (0: default)
-    int p[4] = {0, 0, 0, 0};
-    sscanf(pe, "%d,%d,%d,%d", &p[0], &p[1], &p[2], &p[3]);
-    a.period = mode == 0 && tier >= 0 && tier < 4 ? p[tier] : 0;
-  }
+  const bool lds_tier = tier >= 0 && tier < kLdsTiers;
+  // experiment (GapTierKnobs::period): lockstep iterations between boundaries (0: default)
+  if (knobs.period_set) a.period = mode == 0 && lds_tier ? knobs.period[tier] : 0;
   // Tier 2's four groups per wavefront hold hits that arrive in the middle of a direction and end anywhere: a boundary as soon as
   // two of them wait costs it 220 ms per configs[2] step instead of 238 (tiers 0 and 1, eight groups: 2 - 4 waiting groups cost
   // more in transitions than they save in waiting; tier 3 has one group per wavefront and waits for nobody).
   a.early = tier == 2 ? 2 : 0;
-  if (const char *ee = getenv("PRB_GAPPED_EARLY")) { // experiment: "k0,k1,k2,k3" groups waiting that make a boundary, per tier
-    int k[4] = {0, 0, 0, 0};
-    sscanf(ee, "%d,%d,%d,%d", &k[0], &k[1], &k[2], &k[3]);
-    a.early = tier >= 0 && tier < 4 ? k[tier] : 0;
-  }
-  if (tier == 0) return launch_tier<Tier0, Rec32>(a, mode, s);
-  if (tier == 1) return launch_tier<Tier1, Rec32>(a, mode, s);
-  if (tier == 2) return launch_tier<Tier2, Rec32>(a, mode, s);
-  return launch_tier<Tier3, Rec32W>(a, mode, s);
+  if (knobs.early_set) a.early = lds_tier ? knobs.early[tier] : 0; // experiment (GapTierKnobs::early)
+  if (tier == 0) return launch_tier<Tier0, Rec32>(a, mode, knobs, s);
+  if (tier == 1) return launch_tier<Tier1, Rec32>(a, mode, knobs, s);
+  if (tier == 2) return launch_tier<Tier2, Rec32>(a, mode, knobs, s);
+  return launch_tier<Tier3, Rec32W>(a, mode, knobs, s);
 }
 
 hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
@@ -1919,100 +1890,6 @@ hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uin
     if (mode == 0) hipLaunchKernelGGL((k_gapped_wave<0, false>), dim3(blocks), dim3(64), 0, s, a, scratch);
     else hipLaunchKernelGGL((k_gapped_wave<2, false>), dim3(blocks), dim3(64), 0, s, a, scratch);
   }
-  return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void k_assign_slots(const uint32_t *__restrict__ list, int64_t n, int32_t base, int32_t *slot) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) slot[list[p]] = base + (int32_t)p;
-}
-hipError_t launch_assign_slots(const uint32_t *list, int64_t n, int32_t base, int32_t *slot, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_assign_slots, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, base, slot);
-  return hipGetLastError();
-}
-
-// Base pairs of final hit w from the trace slot its extension pass left (same layout as mode 2
-// of the gapped kernels writes).  Hits completed by the wave kernel (tier 3) or with a chain
-// longer than the slot are left to the mode-2 pass.
-__global__ __launch_bounds__(256) void k_bp_expand(HitSoA in, int64_t n, const uint32_t *__restrict__ subset, QBatchDev qb,
-                                                   PageDev pg, SearchConst sc, const uint8_t *__restrict__ first_flag,
-                                                   const int32_t *__restrict__ ntrace, const uint8_t *__restrict__ tier_of,
-                                                   const uint16_t *__restrict__ trace, LongTrace lt, const int64_t *__restrict__ bp_off,
-                                                   int32_t *bp_out) {
-  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (w >= n) return;
-  const int64_t x = subset[w];
-  const int nleft = ntrace[x] & 0xFFFF, nright = (int)((uint32_t)ntrace[x] >> 16);
-  // a hit of the wavefront-per-hit kernel with its chains on record (kLongTraceTier): the second direction from its long
-  // trace, the first one from there too unless an LDS tier ran it (then from that tier's trace slot)
-  const int ls = (tier_of[x] == kLongTraceTier && lt.slot) ? lt.slot[x] : -1;
-  if (ls < 0 && (tier_of[x] >= kWaveTier || nleft > kTraceCap || nright > kTraceCap)) return;
-  const uint32_t *lt_left = ls >= 0 && lt.count[ls * 2] >= 0 ? lt.trace + ((int64_t)ls * 2) * lt.cap : nullptr;
-  const uint32_t *lt_right = ls >= 0 ? lt.trace + ((int64_t)ls * 2 + 1) * lt.cap : nullptr;
-  const int q_sp = in.q_sp[x], db_sp = in.db_sp[x], len = US(in.q_len[x]);
-  const uint8_t *qs = qb.enc + qb.off[in.query[x]] + q_sp;
-  const uint8_t *ds = pg.seqs + db_sp;
-  const bool unsorted = first_flag[x] != 0; // hit 0 of a query keeps the raw pair order
-  const int64_t out0 = bp_off[w];
-  int ndiag = 0;
-  const int64_t d0 = unsorted ? out0 : out0 + nleft;
-  for (int t = 0; t < len; t++)
-    if (diag_pairs(sc, qs[t], ds[t])) {
-      bp_out[2 * (d0 + ndiag)] = q_sp + t;
-      bp_out[2 * (d0 + ndiag) + 1] = db_sp + t;
-      ndiag++;
-    }
-  const uint16_t *sl = trace + x * 2 * kTraceCap;
-  for (int t = 0; t < nleft; t++) {
-    const int ci = lt_left ? (int)(lt_left[t] & 0xFFFF) : (sl[t] & 0xFF), cj = lt_left ? (int)(lt_left[t] >> 16) : (sl[t] >> 8);
-    const int64_t pos = unsorted ? out0 + ndiag + t : out0 + t;
-    bp_out[2 * pos] = q_sp - ci;
-    bp_out[2 * pos + 1] = db_sp - cj;
-  }
-  const int q_end = q_sp + in.q_len[x] - 1, db_end = db_sp + in.db_len[x] - 1;
-  for (int t = 0; t < nright; t++) {
-    const int ci = lt_right ? (int)(lt_right[t] & 0xFFFF) : (sl[kTraceCap + t] & 0xFF),
-              cj = lt_right ? (int)(lt_right[t] >> 16) : (sl[kTraceCap + t] >> 8);
-    const int64_t pos = unsorted ? out0 + ndiag + nleft + t : out0 + nleft + ndiag + (nright - 1 - t);
-    bp_out[2 * pos] = q_end + ci;
-    bp_out[2 * pos + 1] = db_end + cj;
-  }
-}
-
-hipError_t launch_bp_expand(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                            const SearchConst &sc, const uint8_t *first_flag, const int32_t *ntrace, const uint8_t *tier_of,
-                            const uint16_t *trace, const LongTrace &lt, const int64_t *bp_off, int32_t *bp_out, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bp_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, n, subset, qb, pg, sc, first_flag,
-                     ntrace, tier_of, trace, lt, bp_off, bp_out);
-  return hipGetLastError();
-}
-
-// first and last pair of every list entry (all the simplified output prints,
-// rna_interaction_search.cpp:355-363): ends[4w..4w+3] = (q0, db0, qN, dbN)
-__global__ __launch_bounds__(256) void k_bp_ends(const int64_t *__restrict__ bp_off, int64_t n, const int32_t *__restrict__ bp,
-                                                 int32_t *ends) {
-  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (w >= n) return;
-  const int64_t a = bp_off[w], b = bp_off[w + 1] - 1;
-  ends[4 * w] = bp[2 * a];
-  ends[4 * w + 1] = bp[2 * a + 1];
-  ends[4 * w + 2] = bp[2 * b];
-  ends[4 * w + 3] = bp[2 * b + 1];
-}
-
-hipError_t launch_bp_ends(const int64_t *bp_off, int64_t n, const int32_t *bp, int32_t *ends, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bp_ends, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bp_off, n, bp, ends);
-  return hipGetLastError();
-}
-
-hipError_t launch_bp_count(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                           const SearchConst &sc, const int32_t *ntrace, int32_t *bp_count, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bp_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, n, subset, qb, pg, sc, ntrace,
-                     bp_count);
   return hipGetLastError();
 }
 

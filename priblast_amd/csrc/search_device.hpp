@@ -1,4 +1,5 @@
-// Device helpers shared by the interaction-search kernels (search_kernels.hip, gapped_lds.hip).
+// Device helpers that more than one file of interaction-search kernels uses (the *_kernels.hip of search_kernels.hpp,
+// gapped_lds.hip, gapped_front.hip).  What one file alone uses is in that file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +9,34 @@
 
 namespace prb {
 
+constexpr int kBlock = 256; // threads per workgroup of the one-thread-per-element kernels
+
 #define US(x) ((int)(uint16_t)(x)) // Hit::GetQLength/GetDbLength are unsigned short (hit.hpp:62-64)
+
+// id with start_pos[id] <= sp < start_pos[id+1]  (GetSeqIdAndStart, seed_search.cpp:101-141)
+__device__ __forceinline__ int seq_of(const PageDev &pg, int sp) {
+  int lo = 0, hi = pg.nseq - 1;
+  while (lo < hi) {
+    int m = (lo + hi + 1) >> 1;
+    if (pg.start_pos[m] <= sp) lo = m;
+    else hi = m - 1;
+  }
+  return lo;
+}
+
+// SeedSearch::CalcAccessibility, seed_search.cpp:143-151
+__device__ __forceinline__ double window_acc(const float *acc, const float *cond, int64_t sp, int length, int delta) {
+  double t = acc[sp];
+  for (int i = delta; i < length; i++) t += cond[sp + i];
+  return t;
+}
+
+// The rank key of an energy in the top-N tables and the profile: an unsigned integer of the same order (-0.0 becomes
+// +0.0 first, so the two compare equal)
+__device__ __forceinline__ uint64_t energy_key(double e) {
+  const uint64_t b = (uint64_t)__double_as_longlong(e + 0.0);
+  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
 
 __device__ __forceinline__ int base_of(unsigned c) { return c <= 5 ? (int)c - 1 : (int)c - 5; } // codes 6..9 = soft-masked
 __device__ __forceinline__ int get_char(const uint8_t *s, int64_t i) {                          // GetChar, gapped_extension.cpp:401-407
@@ -36,7 +64,6 @@ __device__ __forceinline__ double div100(const SearchConst &, int z) {
   const double r = fma(-q0, 100.0, zd);
   return fma(r, r100, q0);
 }
-
 
 // GappedExtension::LoopEnergy, gapped_extension.cpp:426-473.  Every branch sums integers
 // (units of 0.01 kcal/mol) and divides by 100.0 once.
@@ -140,7 +167,6 @@ __device__ __forceinline__ double dangle_energy_gapped(const SearchConst &sc, in
   }
   return div100(sc, x);
 }
-
 
 struct HitState {
   int q_sp, db_sp, q_len, db_len, id_start;

@@ -1,5 +1,6 @@
-// Host-visible interface of the interaction-search kernels (search_kernels.hip):
-// seed expansion, ungapped extension, sort + redundancy filter, gapped extension, traceback.
+// Host-visible interface of the interaction-search kernels: the structs the device sees, then one section per kernel
+// file in the order of the pipeline - seed expansion, ungapped extension, sort, redundancy filter, gapped extension,
+// traceback - and behind it the output modes' own stages (pair summaries and distinct sites, top-N tables, profile).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 
 namespace prb {
 
+// ============================================================================ device-visible structs
 // Integer Turner tables (0.01 kcal/mol) as used by the extension stages
 // (ungapped_extension.cpp:157-186, gapped_extension.cpp:366-399, 426-473).
 // layout of the concatenated integer table `SearchConst::tab`
@@ -87,30 +89,59 @@ struct ExtOpts {
   int32_t min_helix;   // -m
 };
 
-// ---- seeds ----
-// blk_seq for a page (PageDev::blk_seq, blk_seq_entries(nchars) values)
-inline int64_t blk_seq_entries(int64_t nchars) { return (nchars >> 5) + 1; }
-hipError_t launch_blk_seq(const PageDev &pg, int32_t *blk_seq, hipStream_t s);
+// The hits between a threshold compaction and the sort behind it, one 64-byte record each: the sort
+// ends in a gather in random order, which then costs one cache line per hit instead of one per field.
+struct alignas(16) HitRec {
+  int32_t q_sp, db_sp, q_len, db_len, db_id, db_id_start, query, pad0;
+  double e_acc, e_hyb, e_tot;
+  int64_t pad1;
+};
+static_assert(sizeof(HitRec) == 64, "one cache line half, two per 128-byte line");
+
+// ============================================================================ seed_kernels.hip: seed expansion
 // sa_seq[k] for every SA entry of a page
 hipError_t launch_sa_seq(const PageDev &pg, int32_t *sa_seq, hipStream_t s);
 // qacc[c.qoff + t] = accessibility energy of the query window of candidate c at its SA entry sp_q + t
 hipError_t launch_seed_qacc(const CandDev *cands, int32_t ncand, int64_t nq_entries, const QBatchDev &qb, int delta, double *qacc,
                             hipStream_t s);
-// row_perm (optional, both passes alike): the order in which the rows are taken - launch_row_keys gives every row its
-// candidate (row_cand) and the key ((query - qmin) << dbits | position in the page text >> shift; 64-bit keys if `wide`,
-// else 32-bit) to sort the rows by, val = the row
+// every row its candidate (row_cand) and the key to sort the rows by: (query - qmin) << dbits | position in the page
+// text >> shift; 64-bit keys if `wide`, else 32-bit; val = the row
 hipError_t launch_row_keys(const CandDev *cands, int32_t ncand, int64_t nrows, const PageDev &pg, int qmin, int shift, int dbits,
                            bool wide, int32_t *row_cand, void *key, uint32_t *val, hipStream_t s);
+// the two passes over the rows: seeds per row, then the seeds themselves at the scanned offsets.  row_perm (optional,
+// both passes alike): the order in which the rows are taken, launch_row_keys' rows sorted by key
 hipError_t launch_seed_count(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
                              int delta, const double *qacc, int32_t *row_count, int32_t *row_cand, const uint32_t *row_perm,
                              hipStream_t s);
 hipError_t launch_seed_emit(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
                             int delta, const double *qacc, const int32_t *row_cand, const int64_t *row_off, HitSoA hits,
                             const uint32_t *row_perm, hipStream_t s);
-// ---- ungapped ----
+
+// ============================================================================ ungapped_kernels.hip: ungapped extension
+// the walk on a list of seed hits, in place
 hipError_t launch_ungapped(HitSoA hits, int64_t n, const QBatchDev &qb, const PageDev &pg, const SearchConst &sc,
                            ExtOpts o, int max_query_len, hipStream_t s);
-// ---- sort keys / gather ----
+// blk_seq for a page (PageDev::blk_seq, blk_seq_entries(nchars) values)
+inline int64_t blk_seq_entries(int64_t nchars) { return (nchars >> 5) + 1; }
+hipError_t launch_blk_seq(const PageDev &pg, int32_t *blk_seq, hipStream_t s);
+// Seeds to extended hits in one pass over the (query SA entry, database SA entry) pairs of a chunk of candidates
+// (ungapped_kernels.hip, "seeds -> extended hits in one pass").  pair0[c] = first pair of candidate c; at most
+// kMaxFusedCands candidates of at most kMaxFusedEntries query entries each.
+constexpr int64_t kMaxFusedCands = 1 << 20, kMaxFusedEntries = 1 << 12;
+hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t ncand, int64_t npairs, const PageDev &pg, int qmin,
+                            int shift, int dbits, bool wide, void *key, uint64_t *val, hipStream_t s);
+// A workgroup takes kFusePairs pairs and keeps what survives in its slice of `slices` (kFusePairs records of
+// kSliceRecBytes each), slice_count[b] of them; nseed[0] += seeds, nseed[1] = max(nseed[1], length of the longest hit
+// kept).  launch_collect_slices packs the slices into `out` (slice b at slice_off[b] = the exclusive scan of the counts).
+constexpr int kFusePairs = 2048, kSliceRecBytes = 48;
+inline int64_t fused_slices(int64_t npairs) { return (npairs + kFusePairs - 1) / kFusePairs; }
+hipError_t launch_seed_extend(const CandDev *cands, const uint64_t *vals, int64_t npairs, const QBatchDev &qb, const PageDev &pg,
+                              const SearchConst &sc, ExtOpts o, const double *qacc, double thr, int max_query_len, void *slices,
+                              int32_t *slice_count, uint64_t *nseed, hipStream_t s);
+hipError_t launch_collect_slices(const void *slices, const int32_t *slice_count, const int64_t *slice_off, int64_t nslices, HitRec *out,
+                                 hipStream_t s);
+
+// ============================================================================ sort_kernels.hip: sort keys, gathers, flags
 // One-key form of the sort (when the fields fit 64 bits): field widths and the offsets
 struct PackedKeyInfo {
   int32_t qmin, lmax; // first query of the sub-batch; upper bound of q_len / db_len
@@ -119,17 +150,156 @@ struct PackedKeyInfo {
 };
 hipError_t launch_make_packed_keys(const HitSoA &hits, int64_t n, const PackedKeyInfo &f, uint64_t *key, uint64_t *k_energy,
                                    uint32_t *idx, hipStream_t s);
-// after the stable sort by the packed key: runs of equal keys -> (energy, input index) order; *too_long is
-// set if a run is longer than the kernel handles (the caller then sorts by the four keys instead)
-hipError_t launch_order_keys(const double *v, int64_t n, uint64_t *key, hipStream_t s); // monotone u64 image of doubles
+hipError_t launch_make_packed_keys_recs(const HitRec *hits, int64_t n, const PackedKeyInfo &f, uint64_t *key, uint64_t *k_energy,
+                                        uint32_t *idx, hipStream_t s);
+// after the stable sort by the packed key: perm_out = perm with every run of equal keys put in (energy, its parts,
+// input index) order; *too_long is set if a run is longer than the kernel handles (the caller then sorts by the four
+// keys instead)
+hipError_t launch_fix_ties(const uint64_t *key_sorted, const uint64_t *e_sorted, const uint32_t *perm, int64_t n, const HitRec *recs,
+                           uint32_t *perm_out, int32_t *too_long, hipStream_t s);
+// the four keys of that sort
 hipError_t launch_make_keys(const HitSoA &hits, int64_t n, uint64_t *k_energy, uint32_t *k_len, uint32_t *k_qsp,
                             uint64_t *k_pos, uint32_t *idx, hipStream_t s);
+hipError_t launch_order_keys(const double *v, int64_t n, uint64_t *key, hipStream_t s); // monotone u64 image of doubles
 hipError_t launch_gather_u64(const uint64_t *src, const uint32_t *idx, uint64_t *dst, int64_t n, hipStream_t s);
 hipError_t launch_gather_u32(const uint32_t *src, const uint32_t *idx, uint32_t *dst, int64_t n, hipStream_t s);
+hipError_t launch_gather_u8(const uint8_t *src, const uint32_t *idx, uint8_t *dst, int64_t n, hipStream_t s);
+hipError_t launch_iota_u32(uint32_t *dst, int64_t n, hipStream_t s); // dst[i] = i
+// dst row r = src row idx[r], rows of row_bytes (a multiple of 16) bytes
+hipError_t launch_gather_rows(const void *src, const uint32_t *idx, void *dst, int64_t n, int row_bytes, hipStream_t s);
+hipError_t launch_gather_hits(const HitSoA &src, const uint32_t *idx, HitSoA dst, int64_t n, hipStream_t s);
+hipError_t launch_gather_hits_to_recs(const HitSoA &src, const uint32_t *idx, HitRec *dst, int64_t n, hipStream_t s);
+// idx == nullptr: in order
+hipError_t launch_gather_recs_to_hits(const HitRec *src, const uint32_t *idx, HitSoA dst, int64_t n, hipStream_t s);
+// flags[i] = marks[list[i]] & mask != 0
+hipError_t launch_flag_marked(const uint8_t *marks, const uint32_t *list, int64_t n, uint8_t mask, uint8_t *flags, hipStream_t s);
+// keep[i] = 1 unless e_tot[i] > thr
+hipError_t launch_flag_not_above(const double *e_tot, int64_t n, double thr, uint8_t *keep, hipStream_t s);
+// first[i] = 1 for the first hit of every query of a query-sorted list
+hipError_t launch_mark_first(const int32_t *query, int64_t n, uint8_t *first, hipStream_t s);
 // out: n records of prb_hit (include/priblast_hip.h) in device memory; bp_base >= 0 also fills their
 // base-pair ranges (bp_count / bp_off per hit, or 2 pairs per hit when those are null)
 hipError_t launch_pack_hits(const HitSoA &src, int64_t n, const int32_t *bp_count, const int64_t *bp_off, int64_t bp_base,
                             void *out, hipStream_t s);
+
+// ============================================================================ filter_kernels.hip: redundancy filter
+// On a sorted list.  state: 0 unknown, 1 active, 2 inactive; keep[i] = 1 for survivors.  tiles: the forms that scan a
+// window of the list in LDS (the default; PRB_FILTER_TILES=0 selects the plain ones)
+hipError_t launch_filter_init(const HitSoA &h, int64_t n, double thr, int64_t *db_end_key, uint8_t *state, hipStream_t s);
+hipError_t launch_filter_round(const HitSoA &h, int64_t n, const int64_t *pmax, uint8_t *state, int32_t *pending, bool tiles,
+                               hipStream_t s);
+hipError_t launch_filter_final(const HitSoA &h, int64_t n, const int64_t *pmax, const uint8_t *state, uint8_t *keep, bool tiles,
+                               hipStream_t s);
+
+// ============================================================================ gapped_lds.hip: gapped extension
+constexpr size_t kGapWaveLdsBytes = 64 * 1024; // a state block up to this size can live in the workgroup's LDS
+struct GapScratch {
+  uint8_t *base;           // one block per wavefront; nullptr = in the wavefront's (dynamic) LDS
+  size_t bytes_per_thread; // bytes per block
+  int32_t cap_rec, cap_diag;
+  int32_t nthreads;        // number of wavefronts (= grid size)
+};
+size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec);
+// State dumps of the hits that outgrow LDS tier 0 / tier 1 (mode 0): the next tier continues from
+// them instead of starting over.  slot[x] = -1 or the hit's dump; pool = cap dumps of
+// gapped_resume_bytes(tier that writes them) each; *count = dumps taken so far (zero it together
+// with the slots).  All null / 0: no dumps.  A launch gets the pool it may continue (rin: tier 1
+// <- tier 0's, tier 2 <- tier 1's) and the pool it fills (rout: tiers 0 and 1).
+struct GapResume {
+  int32_t *slot;
+  uint8_t *pool;
+  uint32_t *count;
+  int32_t cap;
+};
+size_t gapped_resume_bytes(int tier);
+// ids of the gapped kernels a hit can be completed by (tier_out): LDS tiers 0..3, then the
+// wavefront-per-hit kernel with its state in HBM scratch
+constexpr int kLdsTiers = 4, kWaveTier = 4;
+// The experiments of the LDS tiers, as the driver read them from the environment (read_search_knobs, capi_search.hip;
+// INTEGRATION.md has the table).  The per-tier lists count only where their variable is set.
+struct GapTierKnobs {
+  bool pair = true; // PRB_GAPPED_PAIR: tier 0 takes two anti-diagonals per step (0: one)
+  bool pool = true; // PRB_GAPPED_POOL: the filled cells of such a step pooled over the wavefront (0: each group its own)
+  bool pad_set = false, period_set = false, early_set = false;
+  int pad[kLdsTiers] = {};    // PRB_GAPPED_LDS_PAD "b1,b2,b3": unused dynamic LDS per workgroup of tiers 1 - 3 (mode 0, not tier 0's paired form)
+  int period[kLdsTiers] = {}; // PRB_GAPPED_PERIOD "p0,p1,p2,p3": GapArgs::period per tier (mode 0)
+  int early[kLdsTiers] = {};  // PRB_GAPPED_EARLY "k0,k1,k2,k3": GapArgs::early per tier, in place of the default 0,0,2,0
+};
+// Trace slots: the extension pass (mode 0, LDS tiers) leaves the first kTraceCap cells (i | j << 8)
+// of each direction's traceback chain of hit x at trace[(2x + direction) * kTraceCap ...];
+// launch_bp_expand writes the base pairs of the final hits from them (hits of the wave kernel or
+// with longer chains are skipped: they are traced by a mode-2 pass).
+constexpr int kTraceCap = 32;
+// Long traces: the wavefront-per-hit kernel (mode 0) leaves the whole traceback chain of a direction it ran - cells as
+// i | j << 16 - in a pool of its own, trace[(2 * slot[x] + direction) * cap ...], and count[2 * slot[x] + direction] = its
+// length (-1: the direction was not run by this kernel - an LDS tier's trace slot has it -, -2: longer than cap).  A hit
+// whose two chains are all there is reported as kLongTraceTier instead of kWaveTier, and launch_bp_expand writes its pairs
+// from them: no second extension of the ~150 longest hits of a query (2 - 3 ms on an otherwise idle GPU).
+constexpr int kLongTraceTier = 5;
+struct LongTrace {
+  uint32_t *trace = nullptr;
+  int32_t *count = nullptr;
+  const int32_t *slot = nullptr; // per hit x; -1: none
+  int32_t cap = 0;
+};
+// tier_out[x] of a hit whose first direction is done and whose second one is somebody else's business: out.*[x] and
+// bp_count[x] hold its state after direction 0.  kResumeMark: the next kernel of the cascade extends the other
+// direction (a hit that outgrew a kernel in direction 1, or that the front kernel handed on with a first direction that
+// finds nothing).  kHandoverMark: an LDS tier stopped behind direction 0 on purpose (GapArgs::handover): the second
+// direction goes to the front kernel first - it finds nothing nine times in ten, which that kernel proves at a fraction of
+// a tier's cost.  The low three bits are the LDS tier that has room for the first direction: a hit is reported as the
+// larger of the tiers its two directions needed (the tier that would have to extend it again for its pairs).
+constexpr uint8_t kResumeMark = 0x40, kHandoverMark = 0x80, kMarkTier = 0x07;
+__host__ __device__ inline bool is_resumed(uint8_t t) { return (t & (kResumeMark | kHandoverMark)) != 0; }
+// Gapped extension.  mode 0: extend hits (coords + energies) into `out`,
+// overflow[i] = 1 if the state capacity was too small, bp_count[x] = pairs traced back by the
+// two extensions of hit x; mode 2: write the base pairs of list entry i at bp_off[i] (hits
+// beyond the capacity are skipped).
+// launch_gapped_lds: a group of lanes per hit, state in LDS with fixed capacities: tiers 0 and 1 = 8 lanes (32 and 40
+// anti-diagonals), tier 2 = 16 lanes, 64 anti-diagonals; tier 3 = a wavefront, 128 anti-diagonals.
+hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
+                             const PageDev &pg, const SearchConst &sc, ExtOpts o, int mode, int tier, uint8_t *overflow,
+                             uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count, uint16_t *trace,
+                             const int64_t *bp_off, int32_t *bp_out, unsigned long long *next_work /* 8 bytes of scratch */,
+                             const GapResume &rin, const GapResume &rout, const GapTierKnobs &knobs, hipStream_t s,
+                             int handover = 0 /* GapArgs::handover */,
+                             double *acc_scratch = nullptr /* gapped_acc_scratch_bytes() of device memory */);
+size_t gapped_acc_scratch_bytes();
+// launch_gapped_wave: one wavefront per hit, state in the HBM scratch (`scratch.nthreads`
+// wavefronts, `bytes_per_thread` bytes each = gapped_wave_scratch_bytes(cap_diag, cap_rec)).
+hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
+                              const PageDev &pg, const SearchConst &sc, ExtOpts o, GapScratch scratch, int mode,
+                              uint8_t *overflow, uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count,
+                              const int64_t *bp_off, int32_t *bp_out, hipStream_t s, int handover = 0,
+                              const LongTrace &lt = LongTrace{});
+
+// ============================================================================ gapped_front.hip: in front of the cascade
+// launch_gapped_front proves that a direction finds nothing within its `-x` anti-diagonals (phases that are dense over
+// directions / filled cells / (cell, candidate) pairs of 64 directions at a time) and completes the hits whose two directions both find nothing; the others are flagged in
+// overflow[] (with direction 0 handed over when it found nothing) and go on to the LDS tiers.  Completed hits are
+// reported as `tier_id`.  Takes -x <= kFrontMaxDrop.
+constexpr int kFrontMaxDrop = 16;
+bool gapped_front_supported(const SearchConst &sc, const ExtOpts &o);
+size_t gapped_front_scratch_bytes(); // HBM scratch of a launch (accessibility sums of the resident wavefronts; stays in L2)
+hipError_t launch_gapped_front(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
+                               const SearchConst &sc, ExtOpts o, int tier_id, uint8_t *overflow, uint8_t *tier_out, int32_t *bp_count,
+                               unsigned long long *next_work, void *scratch, hipStream_t s,
+                               bool second_only = false /* every hit of the list has its first direction done (a resume / hand-over mark) */);
+
+// ============================================================================ traceback_kernels.hip: base pairs
+// slot[list[p]] = base + p (the long-trace slots of the hits that go to the wavefront-per-hit kernel)
+hipError_t launch_assign_slots(const uint32_t *list, int64_t n, int32_t base, int32_t *slot, hipStream_t s);
+// bp_count[w] = total pairs of list entry w: its ungapped diagonal's plus what the two extensions traced (ntrace)
+hipError_t launch_bp_count(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
+                           const SearchConst &sc, const int32_t *ntrace, int32_t *bp_count, hipStream_t s);
+// the pairs of list entry w at bp_off[w], from the trace slots and long traces of the extension pass
+hipError_t launch_bp_expand(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
+                            const SearchConst &sc, const uint8_t *first_flag, const int32_t *ntrace, const uint8_t *tier_of,
+                            const uint16_t *trace, const LongTrace &lt, const int64_t *bp_off, int32_t *bp_out, hipStream_t s);
+// ends[4w .. 4w + 3] = first and last pair (q0, db0, qN, dbN) of list entry w
+hipError_t launch_bp_ends(const int64_t *bp_off, int64_t n, const int32_t *bp, int32_t *ends, hipStream_t s);
+
+// ============================================================================ site_kernels.hip: (query, db_id) runs
 // ---- per-pair summaries (prb_search_page_summary) over a final, sorted hit list ----
 // head[i] = 1 where (query, db_id) differs from hit i - 1 (and for i = 0): the first hit of every pair
 hipError_t launch_pair_heads(const int32_t *query, const int32_t *db_id, int64_t n, uint8_t *head, hipStream_t s);
@@ -156,6 +326,8 @@ struct SiteScratch {
 };
 hipError_t launch_site_select(const HitSoA &h, int64_t n, const uint8_t *head, int lds_hits, const SiteScratch &w, uint8_t *keep,
                               hipStream_t s);
+
+// ============================================================================ table_kernels.hip: top-N tables
 // ---- top-N table (prb_search_page_top) ----
 constexpr int kTopMaxN = 1024; // the largest N: the set's keys and a candidate buffer of as many fit a workgroup's LDS
 // merges the pair records rec[0, nrec) (prb_pair_summary, launch_pair_fold's output for queries [q0, q1), ascending by
@@ -185,7 +357,9 @@ hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int6
 hipError_t launch_top_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, hipStream_t s);
 hipError_t launch_tophits_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, int64_t shift,
                                hipStream_t s);
-// ---- per-position profile (prb_search_page_profile) ----
+
+// ============================================================================ profile_kernels.hip: per-position profile
+// (prb_search_page_profile)
 // The table of one batch in HBM.  Query q owns the slots [off[q], off[q + 1]) = its len + 1 positions (the last one
 // takes the -1 of a span that ends at the query's last base), so the difference arrays of all queries are one array
 // whose every query segment sums to zero.  Best-hit keys: key = energy key of e_tot, tie = page << 32 | the hit's place
@@ -224,143 +398,5 @@ hipError_t launch_prof_join(const ProfTab &t, const ProfTab &src, int64_t P, hip
 // rows[j] (prb_profile_pos) of the covered slot idx[j]; hits / targets = the scanned difference arrays
 hipError_t launch_prof_rows(const ProfTab &t, const uint32_t *idx, int64_t n, const int64_t *hits, const int32_t *targets, void *rows,
                             hipStream_t s);
-hipError_t launch_gather_u8(const uint8_t *src, const uint32_t *idx, uint8_t *dst, int64_t n, hipStream_t s);
-hipError_t launch_iota_u32(uint32_t *dst, int64_t n, hipStream_t s); // dst[i] = i
-// flags[i] = marks[list[i]] & mask != 0
-hipError_t launch_flag_marked(const uint8_t *marks, const uint32_t *list, int64_t n, uint8_t mask, uint8_t *flags, hipStream_t s);
-// dst row r = src row idx[r], rows of row_bytes (a multiple of 16) bytes
-hipError_t launch_gather_rows(const void *src, const uint32_t *idx, void *dst, int64_t n, int row_bytes, hipStream_t s);
-hipError_t launch_gather_hits(const HitSoA &src, const uint32_t *idx, HitSoA dst, int64_t n, hipStream_t s);
-// The hits between a threshold compaction and the sort behind it, one 64-byte record each: the sort
-// ends in a gather in random order, which then costs one cache line per hit instead of one per field.
-struct alignas(16) HitRec {
-  int32_t q_sp, db_sp, q_len, db_len, db_id, db_id_start, query, pad0;
-  double e_acc, e_hyb, e_tot;
-  int64_t pad1;
-};
-static_assert(sizeof(HitRec) == 64, "one cache line half, two per 128-byte line");
-// Seeds to extended hits in one pass over the (query SA entry, database SA entry) pairs of a chunk of candidates
-// (search_kernels.hip, "seeds -> extended hits in one pass").  pair0[c] = first pair of candidate c; at most
-// kMaxFusedCands candidates of at most kMaxFusedEntries query entries each.
-constexpr int64_t kMaxFusedCands = 1 << 20, kMaxFusedEntries = 1 << 12;
-hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t ncand, int64_t npairs, const PageDev &pg, int qmin,
-                            int shift, int dbits, bool wide, void *key, uint64_t *val, hipStream_t s);
-// A workgroup takes kFusePairs pairs and keeps what survives in its slice of `slices` (kFusePairs records of
-// kSliceRecBytes each), slice_count[b] of them; nseed[0] += seeds, nseed[1] = max(nseed[1], length of the longest hit kept).  launch_collect_slices packs the slices into `out`
-// (slice b at slice_off[b] = the exclusive scan of the counts).
-constexpr int kFusePairs = 2048, kSliceRecBytes = 48;
-inline int64_t fused_slices(int64_t npairs) { return (npairs + kFusePairs - 1) / kFusePairs; }
-hipError_t launch_seed_extend(const CandDev *cands, const uint64_t *vals, int64_t npairs, const QBatchDev &qb, const PageDev &pg,
-                              const SearchConst &sc, ExtOpts o, const double *qacc, double thr, int max_query_len, void *slices,
-                              int32_t *slice_count, uint64_t *nseed, hipStream_t s);
-hipError_t launch_collect_slices(const void *slices, const int32_t *slice_count, const int64_t *slice_off, int64_t nslices, HitRec *out,
-                                 hipStream_t s);
-// perm_out = perm with every run of equal keys put in (energy, its parts, input index) order
-hipError_t launch_fix_ties(const uint64_t *key_sorted, const uint64_t *e_sorted, const uint32_t *perm, int64_t n, const HitRec *recs,
-                           uint32_t *perm_out, int32_t *too_long, hipStream_t s);
-hipError_t launch_gather_hits_to_recs(const HitSoA &src, const uint32_t *idx, HitRec *dst, int64_t n, hipStream_t s);
-// idx == nullptr: in order
-hipError_t launch_gather_recs_to_hits(const HitRec *src, const uint32_t *idx, HitSoA dst, int64_t n, hipStream_t s);
-hipError_t launch_make_packed_keys_recs(const HitRec *hits, int64_t n, const PackedKeyInfo &f, uint64_t *key, uint64_t *k_energy,
-                                        uint32_t *idx, hipStream_t s);
-hipError_t launch_flag_not_above(const double *e_tot, int64_t n, double thr, uint8_t *keep, hipStream_t s);
-hipError_t launch_mark_first(const int32_t *query, int64_t n, uint8_t *first, hipStream_t s);
-// ---- redundancy filter on a sorted list ----
-// state: 0 unknown, 1 active, 2 inactive; keep[i] = 1 for survivors
-hipError_t launch_filter_init(const HitSoA &h, int64_t n, double thr, int64_t *db_end_key, uint8_t *state, hipStream_t s);
-hipError_t launch_filter_round(const HitSoA &h, int64_t n, const int64_t *pmax, uint8_t *state, int32_t *pending,
-                               hipStream_t s);
-hipError_t launch_filter_final(const HitSoA &h, int64_t n, const int64_t *pmax, const uint8_t *state, uint8_t *keep,
-                               hipStream_t s);
-// ---- gapped ----
-constexpr size_t kGapWaveLdsBytes = 64 * 1024; // a state block up to this size can live in the workgroup's LDS
-struct GapScratch {
-  uint8_t *base;           // one block per wavefront; nullptr = in the wavefront's (dynamic) LDS
-  size_t bytes_per_thread; // bytes per block
-  int32_t cap_rec, cap_diag;
-  int32_t nthreads;        // number of wavefronts (= grid size)
-};
-size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec);
-// State dumps of the hits that outgrow LDS tier 0 / tier 1 (mode 0): the next tier continues from
-// them instead of starting over.  slot[x] = -1 or the hit's dump; pool = cap dumps of
-// gapped_resume_bytes(tier that writes them) each; *count = dumps taken so far (zero it together
-// with the slots).  All null / 0: no dumps.  A launch gets the pool it may continue (rin: tier 1
-// <- tier 0's, tier 2 <- tier 1's) and the pool it fills (rout: tiers 0 and 1).
-struct GapResume {
-  int32_t *slot;
-  uint8_t *pool;
-  uint32_t *count;
-  int32_t cap;
-};
-size_t gapped_resume_bytes(int tier);
-// Gapped extension (gapped_lds.hip).  mode 0: extend hits (coords + energies) into `out`,
-// overflow[i] = 1 if the state capacity was too small, bp_count[x] = pairs traced back by the
-// two extensions of hit x; mode 2: write the base pairs of list entry i at bp_off[i] (hits
-// beyond the capacity are skipped).  launch_bp_count: total pairs per list entry.
-// launch_gapped_lds: a group of lanes per hit, state in LDS with fixed capacities: tier 0 = 8 lanes,
-// 32 anti-diagonals; tier 1 = 16 lanes, 64 anti-diagonals; tier 2 = 64 lanes, 128 anti-diagonals.
-// launch_gapped_wave: one wavefront per hit, state in the HBM scratch (`scratch.nthreads`
-// wavefronts, `bytes_per_thread` bytes each = gapped_wave_scratch_bytes(cap_diag, cap_rec)).
-hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                             const PageDev &pg, const SearchConst &sc, ExtOpts o, int mode, int tier, uint8_t *overflow,
-                             uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count, uint16_t *trace,
-                             const int64_t *bp_off, int32_t *bp_out, unsigned long long *next_work /* 8 bytes of scratch */,
-                             const GapResume &rin, const GapResume &rout, hipStream_t s, int handover = 0 /* GapArgs::handover */,
-                             double *acc_scratch = nullptr /* gapped_acc_scratch_bytes() of device memory */);
-size_t gapped_acc_scratch_bytes();
-// Trace slots: the extension pass (mode 0, LDS tiers) leaves the first kTraceCap cells (i | j << 8)
-// of each direction's traceback chain of hit x at trace[(2x + direction) * kTraceCap ...];
-// launch_bp_expand writes the base pairs of the final hits from them (hits of the wave kernel or
-// with longer chains are skipped: they are traced by a mode-2 pass).
-constexpr int kTraceCap = 32;
-// ids of the gapped kernels a hit can be completed by (tier_out): LDS tiers 0..3, then the
-// wavefront-per-hit kernel with its state in HBM scratch
-constexpr int kLdsTiers = 4, kWaveTier = 4;
-// Long traces: the wavefront-per-hit kernel (mode 0) leaves the whole traceback chain of a direction it ran - cells as
-// i | j << 16 - in a pool of its own, trace[(2 * slot[x] + direction) * cap ...], and count[2 * slot[x] + direction] = its
-// length (-1: the direction was not run by this kernel - an LDS tier's trace slot has it -, -2: longer than cap).  A hit
-// whose two chains are all there is reported as kLongTraceTier instead of kWaveTier, and launch_bp_expand writes its pairs
-// from them: no second extension of the ~150 longest hits of a query (2 - 3 ms on an otherwise idle GPU).
-constexpr int kLongTraceTier = 5;
-struct LongTrace {
-  uint32_t *trace = nullptr;
-  int32_t *count = nullptr;
-  const int32_t *slot = nullptr; // per hit x; -1: none
-  int32_t cap = 0;
-};
-// tier_out[x] of a hit whose first direction is done and whose second one is somebody else's business: out.*[x] and
-// bp_count[x] hold its state after direction 0.  kResumeMark: the next kernel of the cascade extends the other
-// direction (a hit that outgrew a kernel in direction 1, or that the front kernel handed on with a first direction that
-// finds nothing).  kHandoverMark: an LDS tier stopped behind direction 0 on purpose (GapArgs::handover): the second
-// direction goes to the front kernel first - it finds nothing nine times in ten, which that kernel proves at a fraction of
-// a tier's cost.  The low three bits are the LDS tier that has room for the first direction: a hit is reported as the
-// larger of the tiers its two directions needed (the tier that would have to extend it again for its pairs).
-constexpr uint8_t kResumeMark = 0x40, kHandoverMark = 0x80, kMarkTier = 0x07;
-__host__ __device__ inline bool is_resumed(uint8_t t) { return (t & (kResumeMark | kHandoverMark)) != 0; }
-
-// launch_gapped_front (gapped_front.hip): the kernel in front of the cascade.  It proves that a direction finds nothing
-// within its `-x` anti-diagonals (phases that are dense over directions / filled cells / (cell, candidate) pairs of 64
-// directions at a time) and completes the hits whose two directions both find nothing; the others are flagged in
-// overflow[] (with direction 0 handed over when it found nothing) and go on to the LDS tiers.  Completed hits are
-// reported as `tier_id`.  Takes -x <= kFrontMaxDrop.
-constexpr int kFrontMaxDrop = 16;
-bool gapped_front_supported(const SearchConst &sc, const ExtOpts &o);
-size_t gapped_front_scratch_bytes(); // HBM scratch of a launch (accessibility sums of the resident wavefronts; stays in L2)
-hipError_t launch_gapped_front(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                               const SearchConst &sc, ExtOpts o, int tier_id, uint8_t *overflow, uint8_t *tier_out, int32_t *bp_count,
-                               unsigned long long *next_work, void *scratch, hipStream_t s,
-                               bool second_only = false /* every hit of the list has its first direction done (a resume / hand-over mark) */);
-hipError_t launch_bp_expand(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                            const SearchConst &sc, const uint8_t *first_flag, const int32_t *ntrace, const uint8_t *tier_of,
-                            const uint16_t *trace, const LongTrace &lt, const int64_t *bp_off, int32_t *bp_out, hipStream_t s);
-hipError_t launch_bp_count(const HitSoA &in, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                           const SearchConst &sc, const int32_t *ntrace, int32_t *bp_count, hipStream_t s);
-hipError_t launch_bp_ends(const int64_t *bp_off, int64_t n, const int32_t *bp, int32_t *ends, hipStream_t s);
-hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                              const PageDev &pg, const SearchConst &sc, ExtOpts o, GapScratch scratch, int mode,
-                              uint8_t *overflow, uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count,
-                              const int64_t *bp_off, int32_t *bp_out, hipStream_t s, int handover = 0,
-                              const LongTrace &lt = LongTrace{});
-hipError_t launch_assign_slots(const uint32_t *list, int64_t n, int32_t base, int32_t *slot, hipStream_t s); // slot[list[p]] = base + p
 
 } // namespace prb

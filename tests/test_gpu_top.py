@@ -65,7 +65,7 @@ def assert_bytes(got, want, what):
             assert got[k].tobytes() == want[k].tobytes(), (what, k, got[k], want[k])
 
 
-K_TOP_TILE = 1024  # records a k_top_merge workgroup streams per step (search_kernels.hip, kTopTile)
+K_TOP_TILE = 1024  # records a k_top_merge workgroup streams per step (table_kernels.hip, kTopTile)
 
 
 def random_seq(rng, n):

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
 OPTS = [{}, OPTION_SETS[1], OPTION_SETS[5]]  # defaults; -f -2 -g -5; -m 2
 
-K_TOP_TILE = 1024  # records a k_top_merge workgroup streams per step (search_kernels.hip, kTopTile)
+K_TOP_TILE = 1024  # records a k_top_merge workgroup streams per step (table_kernels.hip, kTopTile)
 
 
 @pytest.fixture(scope="module")

@@ -11,8 +11,10 @@ if [ "$1" = build ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -fopenmp -ffp-contract=off -Wall -Wno-unused-function \
       -I$HERE/priblast_amd/csrc -I$HERE/priblast_amd/host -I$HERE/include -DPRB_T1_CAPD=$d -DPRB_T1_CAPR=$r -DPRB_T1_GROUPS=$g -DPRB_T1_WGCU=$w \
       -c $HERE/priblast_amd/csrc/gapped_lds.hip -o /tmp/gapped_lds_$tag.o || exit 1
+    # the objects of the present sources only: lib/obj may still hold those of files that no longer exist
+    others=$(for f in $HERE/priblast_amd/csrc/*.hip; do echo $LIB/obj/$(basename $f).o; done | grep -v gapped_lds.hip.o)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $LIB/alt_$tag.so /tmp/gapped_lds_$tag.o \
-      $(ls $LIB/obj/*.o | grep -v gapped_lds.hip.o) -fopenmp -ldl -lpthread || exit 1
+      $others $(ls $LIB/obj/*.o | grep -v '\.hip\.o$') -fopenmp -ldl -lpthread || exit 1
     echo "built alt_$tag.so"
   done
 else
