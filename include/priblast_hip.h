@@ -127,6 +127,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   prb_profset_finish: the scans, the selection and the rows, launches = 3 or 4; prb_profset_merge: 1);
  * "tophits" (prb_search_page_tophits: the merge into the top-N hit table, the scan of the kept hits' pair counts and the
  *   gather of their lists; launches = 4 per sub-batch, and per prb_tophits_merge);
+ * "targets" (prb_search_page_targets: the merge into the per-target table - the records' query identifiers and sort keys,
+ *   the stable sort by target, the runs' keys and head flags, the selection of the heads and the merge; launches = 5 per
+ *   sub-batch; prb_targetset_merge: 1);
  * "distinct" (opts->distinct_sites: the pairs' head flags, the two selection kernels and the selection of the kept hits,
  *   launches = 4 per sub-batch with final hits, and 2 more - the gathers of the records and of their pre-gapped
  *   indices - when a hit is dropped; nothing when the option is off; prb_distinct_sites: launches = 3);
@@ -378,6 +381,60 @@ const prb_profile_pos *prb_profset_rows(const prb_profset *ps);
 void prb_profset_counts(const prb_profset *ps, int64_t counts[3]);
 void prb_profset_free(prb_profset *ps);
 
+/* ---- the N best queries per target (`ris -r N`): a top-N table per database sequence on the device ----
+ * A target is a (page, db_id) of one database.  A table holds, for every target, the N pairs with the lowest e_min among
+ * the per-pair summaries (exactly the records prb_search_page_summary returns) of all the calls merged into it, over
+ * all their queries (fewer when the target has fewer pairs).  It lives as long as the caller likes - a whole run -, not
+ * one batch: every call names its queries by caller-given identifiers, int32 >= 0, one per query of the batch (the
+ * command line: the 0-based position in the input FASTA), and `s.query` of a record holds that identifier.  Pairs of a
+ * target are ranked by e_min ascending, compared as doubles (-0.0 == +0.0); equal values are ordered by the query's
+ * identifier ascending.  A (query id, page, db_id) triple occurs at most once - a (query id, page) is merged once -, so
+ * it is a total order, and the table depends - bit for bit - neither on how the queries are cut into batches or
+ * sub-batches, nor on the order of the batches or of the pages, nor on which context (worker) took what, nor on page
+ * residency.
+ *   prb_targetset_create     an empty table for db (1 <= n <= 1024): n slots of 72 B and n keys of 16 B per sequence of
+ *                            every page of db, plus a fill count per target, in HBM; PRB_ERR_NOMEM when that cannot be
+ *                            allocated
+ *   prb_search_page_targets  the search of prb_search_page_summary of qb against `page`, its records merged into the
+ *                            table on the device (nothing is copied to the host); query_ids[q] = the identifier of query q
+ *                            of qb (qb's number of queries).  Argument checks and option limits are those of
+ *                            prb_search_page_summary.  PRB_ERR_ARG, the table untouched: a table made with another
+ *                            context or for another database; an identifier below 0, given twice in the call, or already
+ *                            merged for this page; opts->distinct_sites other than that of the pages merged so far.  A
+ *                            merge that fails part way leaves the table unusable.
+ *   prb_targetset_merge      two unfinished tables into one, on the device: dst (of ctx) then holds exactly - bit for bit
+ *                            - the table that all that was merged into either, merged into one table, gives; its counts
+ *                            are the sums; src is left empty but valid (it can be freed, or finished to zero records).
+ *                            src may belong to another context, on the same or on another device: its table is then
+ *                            copied to dst's device first (a peer copy where hipDeviceCanAccessPeer allows it, else through
+ *                            pinned host memory), and the caller's current device is restored.  Both were made with the
+ *                            same n for the same database - the handles may differ (every context opens its own): the
+ *                            same pages of the same numbers of sequences -, hold the same distinct_sites unless one is
+ *                            empty, and no (query id, page) is merged into both: anything else returns PRB_ERR_ARG and
+ *                            leaves both tables as they were.
+ *   prb_targetset_finish     the filled slots compacted on the device (a scan over the fills, a gather in rank order)
+ *                            and copied to the host in one copy; the device memory is released.  prb_targetset_pairs then
+ *                            returns the records by page, then db_id, then rank; `rank` counts from 0 within the target.
+ *                            Nothing can be merged after it (a second call does nothing)
+ *   prb_targetset_counts     the stage counts of prb_pairset_counts, summed over the merged calls
+ * The device time of the merges is the stage "targets" of prb_ctx_stage_ms (launches = 5 per sub-batch: identifiers and
+ * sort keys, the stable sort by target, the runs' keys and heads, the selection of the heads, the merge;
+ * prb_targetset_merge: 1). */
+typedef struct prb_target_pair {
+  prb_pair_summary s; /* s.query = the query's identifier */
+  int32_t page, rank; /* the target's page; the pair's rank within its target */
+} prb_target_pair;
+typedef struct prb_targetset prb_targetset;
+int prb_targetset_create(prb_ctx *ctx, prb_db *db, int32_t n, prb_targetset **out);
+int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                            const int32_t *query_ids, prb_targetset *ts);
+int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src);
+int prb_targetset_finish(prb_ctx *ctx, prb_targetset *ts);
+int64_t prb_targetset_size(const prb_targetset *ts);
+const prb_target_pair *prb_targetset_pairs(const prb_targetset *ts);
+void prb_targetset_counts(const prb_targetset *ts, int64_t counts[3]);
+void prb_targetset_free(prb_targetset *ts);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -408,6 +465,11 @@ int prb_write_summary_lines(const prb_db *db, int32_t nq, const char *const *qna
  * rank), one line each in that order, numbered from id0 on; every line is the `-t` line of its pair. */
 int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                         const prb_top_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
+/* The lines of `ris -r N`: pairs[0, n) as prb_targetset_pairs returns them (by page, then db_id, then rank), one line
+ * each in that order, numbered from id0 on; every line is the `-t` line of its pair.  qnames and qlen_unmasked are indexed
+ * by the query's identifier (nq_total of them: every s.query lies below it). */
+int prb_write_target_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                           const prb_target_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
 /* The lines of `ris -q` for one batch: rows[0, n) as prb_profset_rows returns them (ascending by query, then by
  * position), one line each in that order, numbered from id0 on:
  *   Id,qname,qlen,Position,Hits,Targets,MinEnergy,dbname,dblen,(q0-qN:db0-dbN)

@@ -53,6 +53,11 @@ assert TOP_DTYPE.itemsize == 72
 TOPHIT_DTYPE = np.dtype(HIT_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
 assert TOPHIT_DTYPE.itemsize == 72
 
+# prb_target_pair: the embedded prb_pair_summary's fields (`query` = the query's identifier), then the target's page and the
+# pair's rank within its target
+TARGET_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("rank", "<i4")])
+assert TARGET_DTYPE.itemsize == 72
+
 # prb_profile_pos: one covered query position of the per-position profile (`ris -q`)
 PROFILE_DTYPE = np.dtype([("query", "<i4"), ("pos", "<i4"), ("hits", "<i8"), ("targets", "<i4"), ("page", "<i4"),
                           ("db_id", "<i4"), ("reserved", "<i4"), ("e_min", "<f8"), ("bp_first", "<i4", (2,)),
@@ -139,6 +144,15 @@ SYMBOLS = {
     "prb_profset_rows": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_profset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_profset_free": (None, [ctypes.c_void_p]),
+    "prb_targetset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_targets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "prb_targetset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_targetset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_targetset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_targetset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_targetset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_targetset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -152,6 +166,8 @@ SYMBOLS = {
                                                c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_top_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                            c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_target_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                              c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_profile_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                                c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
 }
@@ -557,6 +573,62 @@ def search_profile(ctx, qb, db, opts=None, pages=None, with_counts=False):
     return (rows, counts) if with_counts else rows
 
 
+class TargetSet:
+    """prb_targetset: the N best queries per target (page, db_id) of one database, in a table on the device that any
+    number of batches is merged into, page by page; every batch names its queries by identifiers of the caller's."""
+
+    def __init__(self, ctx, db, n):
+        h = ctypes.c_void_p()
+        _check(lib().prb_targetset_create(ctx.h, db.h, n, ctypes.byref(h)))
+        self.h, self.ctx, self.db = h, ctx, db
+
+    def merge(self, qb, page, ids, opts=None, db=None):
+        """prb_search_page_targets: searches the batch against `page` and merges its pair records into the table;
+        ids[q] = the identifier of query q of the batch"""
+        o = opts or default_opts()
+        ids = np.ascontiguousarray(ids, np.int32)
+        assert len(ids) == len(qb.lens)
+        _check(lib().prb_search_page_targets(self.ctx.h, qb.h, (db or self.db).h, page, ctypes.byref(o), ids.ctypes.data, self.h))
+
+    def absorb(self, other):
+        """prb_targetset_merge: the unfinished table `other` (over other (identifier, page) sets; of any context) merged
+        into this one on the device; `other` is left empty"""
+        _check(lib().prb_targetset_merge(self.ctx.h, self.h, other.h))
+
+    def finish(self):
+        """prb_targetset_finish -> structured array TARGET_DTYPE (a copy), by page, then db_id, then rank"""
+        _check(lib().prb_targetset_finish(self.ctx.h, self.h))
+        return _records(lib().prb_targetset_pairs(self.h), lib().prb_targetset_size(self.h), TARGET_DTYPE)
+
+    def counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_targetset_counts(self.h, c)
+        return tuple(c)
+
+    def close(self):
+        if self.h:
+            lib().prb_targetset_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_targets(ctx, db, n, batches, opts=None, pages=None, with_counts=False):
+    """The n pairs of lowest e_min per target over batches = [(QBatch, ids)], every batch against the pages (all of them,
+    in this order, by default) -> structured array TARGET_DTYPE, by page, db_id and rank.  with_counts: -> (records,
+    (seed, ungapped, final) counts summed over the calls)."""
+    with TargetSet(ctx, db, n) as ts:
+        for qb, ids in batches:
+            for p in range(db.npages) if pages is None else pages:
+                ts.merge(qb, p, ids, opts)
+        recs, counts = ts.finish(), ts.counts()
+    return (recs, counts) if with_counts else recs
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -636,6 +708,13 @@ def write_top_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
     (-1: formatted and counted only)."""
     recs = np.ascontiguousarray(recs, TOP_DTYPE)
     return _write(lib().prb_write_top_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
+
+
+def write_target_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
+    """Lines of `ris -r N`: recs as search_targets returns them; qnames / qlen_unmasked indexed by query identifier.
+    -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, TARGET_DTYPE)
+    return _write(lib().prb_write_target_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
 
 
 def write_profile_lines(db, qnames, qlen_unmasked, rows, id0=0, fd=-1):

@@ -235,6 +235,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->tophits_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "targets") == 0) {
+    if (ms) *ms = ctx->targets_timer.ms;
+    if (launches) *launches = ctx->targets_timer.launches;
+    return PRB_OK;
+  }
   if (std::strcmp(stage, "distinct") == 0) {
     if (ms) *ms = ctx->distinct_timer.ms;
     if (launches) *launches = ctx->distinct_timer.launches;
@@ -252,6 +257,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
     ctx->top_timer = prb::StageTimer{};
     ctx->profile_timer = prb::StageTimer{};
     ctx->tophits_timer = prb::StageTimer{};
+    ctx->targets_timer = prb::StageTimer{};
     ctx->distinct_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }

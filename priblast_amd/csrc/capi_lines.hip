@@ -8,7 +8,7 @@
 using namespace prb;
 
 namespace {
-// The body the four writers share.  `View` is the formatter's view of a batch (output.hpp); `kind_ok` = the checks of
+// The body the five writers share.  `View` is the formatter's view of a batch (output.hpp); `kind_ok` = the checks of
 // the arguments only this kind has; `fill(v)` checks the records and puts them into the view (it sets the error text
 // and returns the code when one is inconsistent); `format(v, sink)` is the formatter's call, returning the next id or -1.
 template <class View, class Fill, class Format>
@@ -112,6 +112,24 @@ int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames,
         return (int)PRB_OK;
       },
       [&](const TopView &v, LineSink &sink) { return format_top_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
+int prb_write_target_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                           const prb_target_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<TargetView>(
+      "prb_write_target_lines", n >= 0 && (!n || pairs), db, nq_total, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](TargetView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_target_pair &x = pairs[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq_total || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1)
+            return bad_record("prb_write_target_lines: pair record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = pairs;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const TargetView &v, LineSink &sink) { return format_target_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
 int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,

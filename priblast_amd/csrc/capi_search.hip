@@ -114,6 +114,7 @@ struct PageSearch {
   prb_topset *top;   // kTop
   prb_profset *prof; // kProfile
   prb_tophits *tophits; // kTopHits
+  prb_targetset *targets; // kTargets
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
@@ -1435,6 +1436,44 @@ static int emit_tophits(SubSearch &s) {
   return ctx->time_end(ctx->tophits_timer, 4);
 }
 
+// prb_search_page_targets: the pairs' records - their `query` turned into the caller's identifier - grouped by target (a
+// stable sort by db_id: a target's records stay in query order; always, whatever the sub-batch holds) and every
+// target's run merged into the per-target table by a wavefront; nothing leaves the device
+static int emit_targets(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  prb_targetset *ts = s.targets;
+  int rc;
+  int64_t npairs = 0;
+  if ((rc = pair_runs(s, &npairs))) return rc;
+  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
+  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
+  if ((rc = ctx->time_begin())) return rc;
+  const size_t NP = (size_t)npairs;
+  if ((rc = ts->key.ensure(NP * 4)) || (rc = ts->keyS.ensure(NP * 4)) || (rc = ts->val.ensure(NP * 4)) || (rc = ts->valS.ensure(NP * 4)) ||
+      (rc = ts->rkey.ensure(NP * sizeof(TargetKey))) || (rc = ts->head.ensure(NP)) || (rc = ts->start.ensure(NP * 4)))
+    return rc;
+  const int32_t nseq = s.pg.nseq;
+  PRB_HIP(launch_target_ids(w.packed.p, npairs, ts->ids.as<int32_t>(), s.qb->nq, ts->key.as<uint32_t>(), ts->val.as<uint32_t>(), ctx->stream));
+  if ((rc = sort_pairs(ctx->stream, ts->sortTmp, ts->key.as<uint32_t>(), ts->keyS.as<uint32_t>(), ts->val.as<uint32_t>(), ts->valS.as<uint32_t>(), NP,
+                       (unsigned)bits_for(std::max(nseq - 1, 1)))))
+    return rc;
+  PRB_HIP(launch_target_runs(w.packed.p, npairs, ts->keyS.as<uint32_t>(), ts->valS.as<uint32_t>(), ts->rkey.as<TargetKey>(), ts->head.as<uint8_t>(),
+                             ctx->stream));
+  int64_t nruns = 0;
+  if ((rc = select_flagged(ctx, w, nullptr, ts->head.as<uint8_t>(), ts->start.as<uint32_t>(), NP, &nruns))) return rc;
+  if (nruns <= 0 || nruns > npairs || nruns > nseq) {
+    set_error("per-target table: " + std::to_string(nruns) + " targets for " + std::to_string(npairs) + " pairs");
+    return PRB_ERR_STATE;
+  }
+  PRB_HIP(launch_target_merge(w.packed.p, ts->rkey.as<TargetKey>(), ts->keyS.as<uint32_t>(), ts->start.as<uint32_t>(), nruns, npairs, s.page,
+                              ts->tbase[(size_t)s.page], nseq, ts->n, ts->keys_of(ts->table.p), ts->slots_of(ts->table.p),
+                              ts->fill_of(ts->table.p), ctx->stream));
+  s.hs->hits_total += s.nfin;
+  return ctx->time_end(ctx->targets_timer, 5);
+}
+
 static int emit_final(SubSearch &s) {
   switch (s.mode) {
   case SearchMode::kRecords: return emit_records(s);
@@ -1442,6 +1481,7 @@ static int emit_final(SubSearch &s) {
   case SearchMode::kTop: return emit_top(s);
   case SearchMode::kProfile: return emit_profile(s);
   case SearchMode::kTopHits: return emit_tophits(s);
+  case SearchMode::kTargets: return emit_targets(s);
   }
   return PRB_ERR_STATE;
 }
@@ -1568,7 +1608,7 @@ static bool take_queries(SeedPlan &plan, int32_t q0, double budget, bool wait, i
 }
 
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                SearchMode mode, prb_hitset **out, MergeTable *table) {
+                SearchMode mode, prb_hitset **out, void *table) {
   const bool summary = reduces_to_pairs(mode);
   const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
   if (!out) {
@@ -1636,6 +1676,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
                 mode == SearchMode::kTop ? static_cast<prb_topset *>(table) : nullptr,
                 mode == SearchMode::kProfile ? static_cast<prb_profset *>(table) : nullptr,
                 mode == SearchMode::kTopHits ? static_cast<prb_tophits *>(table) : nullptr,
+                mode == SearchMode::kTargets ? static_cast<prb_targetset *>(table) : nullptr,
                 hs,
                 0,
                 0};

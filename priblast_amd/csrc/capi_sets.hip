@@ -1,5 +1,6 @@
 // C ABI, part 4: the tables and record sets a search fills - the top-N table (prb_topset_*), the top-N hit table
-// (prb_tophits_*), the per-position profile (prb_profset_*), per-pair records (prb_pairset_*), hit sets (prb_hitset_*).
+// (prb_tophits_*), the per-position profile (prb_profset_*), the per-target table (prb_targetset_*), per-pair records
+// (prb_pairset_*), hit sets (prb_hitset_*).
 #include <algorithm>
 #include <cstring>
 
@@ -12,6 +13,10 @@ namespace {
 struct ProfCovered {
   const int64_t *hits;
   __host__ __device__ bool operator()(const uint32_t &p) const { return hits[p] > 0; }
+};
+// a fill count as what the scan of prb_targetset_finish adds up
+struct FillToI64 {
+  __host__ __device__ int64_t operator()(const int32_t &x) const { return (int64_t)x; }
 };
 // the caller's current device, put back on every way out of a call that visits another table's device
 struct DeviceScope {
@@ -537,6 +542,200 @@ void prb_profset_counts(const prb_profset *ps, int64_t counts[3]) {
 }
 void prb_profset_free(prb_profset *ps) {
   delete ps;
+}
+
+// ---- the per-target table (prb_targetset_*) ----
+// every key, payload slot and fill count of the table back to "nothing", on its own device and stream
+static int clear_target_table(prb_targetset &t) {
+  PRB_HIP(hipSetDevice(t.ctx->device));
+  PRB_HIP(hipMemsetAsync(t.table.p, 0, t.bytes(), t.ctx->stream));
+  PRB_HIP(hipStreamSynchronize(t.ctx->stream));
+  return PRB_OK;
+}
+
+int prb_targetset_create(prb_ctx *ctx, prb_db *db, int32_t n, prb_targetset **out) {
+  if (!ctx || !db || !out || db->ctx->device != ctx->device) {
+    set_error("prb_targetset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  if (n < 1 || n > kTopMaxN) {
+    set_error("prb_targetset_create: need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+    return PRB_ERR_ARG;
+  }
+  std::unique_ptr<prb_targetset> t(new (std::nothrow) prb_targetset());
+  if (!t) {
+    set_error("prb_targetset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  t->ctx = ctx;
+  t->db = db;
+  t->n = n;
+  t->tbase.assign(db->pages.size() + 1, 0);
+  for (size_t p = 0; p < db->pages.size(); p++) t->tbase[p + 1] = t->tbase[p] + db->pages[p].nseq;
+  t->merged.resize(db->pages.size());
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (t->table.ensure(t->bytes()) != PRB_OK) {
+    set_error("prb_targetset_create: can't allocate the per-target table (" + std::to_string(t->bytes() >> 20) + " MB of HBM for " +
+              std::to_string(t->targets()) + " targets of " + std::to_string(n) + " slots)");
+    return PRB_ERR_NOMEM;
+  }
+  if (int rc = clear_target_table(*t)) return rc;
+  *out = t.release();
+  return PRB_OK;
+}
+
+// Every check comes before the table is touched: a refused call leaves it as it was.
+int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
+                            prb_targetset *ts) {
+  const std::string fn = "prb_search_page_targets";
+  auto refuse = [&](const std::string &why, int code = PRB_ERR_ARG) {
+    set_error(fn + ": " + why);
+    return code;
+  };
+  if (!ts || !query_ids) return refuse("bad argument");
+  if (int rc = check_search_args(fn.c_str(), ctx, qb, db, page, opts, 3)) return rc;
+  if (ts->ctx != ctx || ts->db != db) return refuse("the per-target table was made with another context or for another database");
+  if (ts->broken) return refuse("an earlier merge into this per-target table failed", PRB_ERR_STATE);
+  if (ts->finished) return refuse("the per-target table is finished (prb_targetset_finish)", PRB_ERR_STATE);
+  if (ts->distinct >= 0 && opts->distinct_sites != ts->distinct)
+    return refuse("the per-target table holds pages searched with distinct_sites " + std::to_string(ts->distinct) + " (this call: " +
+                  std::to_string(opts->distinct_sites) + ")");
+  try {
+    std::vector<int32_t> sorted(query_ids, query_ids + qb->nq);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < sorted.size(); i++) {
+      if (sorted[i] < 0) return refuse("query identifier " + std::to_string(sorted[i]) + " is below 0");
+      if (i && sorted[i] == sorted[i - 1]) return refuse("query identifier " + std::to_string(sorted[i]) + " is given twice");
+      if (ts->has((size_t)page, sorted[i]))
+        return refuse("query identifier " + std::to_string(sorted[i]) + " is already merged for page " + std::to_string(page));
+    }
+    for (int32_t id : sorted) ts->set((size_t)page, id);
+  } catch (const std::exception &e) {
+    return refuse(e.what(), PRB_ERR_NOMEM);
+  }
+  PRB_HIP(hipSetDevice(ctx->device));
+  ts->broken = true; // (until the merge is whole)
+  int rc;
+  if ((rc = ts->ids.ensure(std::max<size_t>((size_t)qb->nq * 4, 4)))) return rc;
+  PRB_HIP(hipMemcpyAsync(ts->ids.p, query_ids, (size_t)qb->nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  prb_hitset *hs = nullptr;
+  if ((rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kTargets, &hs, ts))) return rc;
+  for (int i = 0; i < 3; i++) ts->counts[i] += hs->counts[i];
+  ts->distinct = opts->distinct_sites;
+  ts->broken = false;
+  delete hs;
+  return PRB_OK;
+}
+
+int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
+  auto refuse = [&](const std::string &why) {
+    set_error("prb_targetset_merge: " + why);
+    return PRB_ERR_ARG;
+  };
+  if (!ctx || !dst || !src || dst == src) return refuse("bad argument");
+  if (dst->ctx != ctx) return refuse("the table to merge into belongs to another context");
+  if (dst->broken || src->broken) return refuse("an earlier merge into one of the per-target tables failed");
+  if (dst->finished || src->finished) return refuse("one of the per-target tables is finished");
+  if (dst->n != src->n) return refuse("the per-target tables keep " + std::to_string(dst->n) + " and " + std::to_string(src->n) + " records per target");
+  if (dst->tbase != src->tbase) return refuse("the per-target tables were made for different databases");
+  if (dst->distinct >= 0 && src->distinct >= 0 && dst->distinct != src->distinct)
+    return refuse("the per-target tables hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
+                  std::to_string(src->distinct));
+  for (size_t p = 0; p < dst->merged.size(); p++) {
+    const std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
+    for (size_t k = 0; k < std::min(a.size(), b.size()); k++)
+      if (a[k] & b[k]) return refuse("a query identifier is merged for page " + std::to_string(p) + " into both per-target tables");
+  }
+  DeviceScope restore;
+  ScratchBuf copy;
+  PRB_HIP(hipSetDevice(ctx->device));
+  void *block = nullptr;
+  int rc;
+  if ((rc = on_device_of(ctx, src->ctx, src->table.p, src->bytes(), copy, &block))) return rc;
+  dst->broken = true; // (until the merge is whole)
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_target_join(dst->keys_of(dst->table.p), dst->slots_of(dst->table.p), dst->fill_of(dst->table.p), dst->keys_of(block),
+                             dst->slots_of(block), dst->fill_of(block), dst->targets(), dst->n, ctx->stream));
+  if ((rc = ctx->time_end(ctx->targets_timer, 1))) return rc; // (synchronises: src is read no more)
+  dst->broken = false;
+  try {
+    for (size_t p = 0; p < dst->merged.size(); p++) {
+      std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
+      if (a.size() < b.size()) a.resize(b.size(), 0);
+      for (size_t k = 0; k < b.size(); k++) a[k] |= b[k];
+      b.clear();
+    }
+  } catch (const std::exception &e) {
+    dst->broken = true;
+    set_error(std::string("prb_targetset_merge: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  for (int i = 0; i < 3; i++) {
+    dst->counts[i] += src->counts[i];
+    src->counts[i] = 0;
+  }
+  if (dst->distinct < 0) dst->distinct = src->distinct;
+  src->distinct = -1;
+  return clear_target_table(*src);
+}
+
+// the fills scanned, the filled slots gathered by target and rank on the device, one copy
+int prb_targetset_finish(prb_ctx *ctx, prb_targetset *ts) {
+  if (!ctx || !ts || ts->ctx != ctx) {
+    set_error("prb_targetset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (ts->broken) {
+    set_error("prb_targetset_finish: an earlier merge into this per-target table failed");
+    return PRB_ERR_STATE;
+  }
+  if (ts->finished) return PRB_OK; // (the records are on the host already)
+  ts->pairs.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  const int64_t T = ts->targets();
+  if (T > 0) {
+    int rc;
+    ScratchBuf off, out, tmp;
+    if ((rc = off.ensure(((size_t)T + 1) * 8))) return rc;
+    auto fills = rocprim::make_transform_iterator(ts->fill_of(ts->table.p), FillToI64());
+    if ((rc = with_temp(tmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
+           return rocprim::exclusive_scan(t, b, fills, off.as<int64_t>(), (int64_t)0, (size_t)T + 1, rocprim::plus<int64_t>(), ctx->stream);
+         })))
+      return rc;
+    int64_t total = 0;
+    PRB_HIP(hipMemcpyAsync(&total, off.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (total < 0 || (uint64_t)total > (uint64_t)ts->entries()) {
+      set_error("prb_targetset_finish: bad record count " + std::to_string(total));
+      return PRB_ERR_STATE;
+    }
+    if (total) {
+      try {
+        ts->pairs.resize((size_t)total);
+      } catch (const std::exception &e) {
+        set_error(std::string("prb_targetset_finish: ") + e.what());
+        return PRB_ERR_NOMEM;
+      }
+      if ((rc = out.ensure((size_t)total * sizeof(prb_target_pair)))) return rc;
+      PRB_HIP(launch_target_gather(ts->keys_of(ts->table.p), ts->slots_of(ts->table.p), off.as<int64_t>(), T, ts->n, total, out.p, ctx->stream));
+      PRB_HIP(hipMemcpyAsync(ts->pairs.data(), out.p, (size_t)total * sizeof(prb_target_pair), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+    }
+  }
+  ts->finished = true;
+  ts->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_targetset_size(const prb_targetset *ts) { return ts ? (int64_t)ts->pairs.size() : -1; }
+const prb_target_pair *prb_targetset_pairs(const prb_targetset *ts) { return ts ? ts->pairs.data() : nullptr; }
+void prb_targetset_counts(const prb_targetset *ts, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ts ? ts->counts[i] : 0;
+}
+void prb_targetset_free(prb_targetset *ts) {
+  delete ts;
 }
 
 int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }

@@ -64,6 +64,7 @@ struct prb_ctx {
   prb::StageTimer top_timer; // the merge of prb_search_page_top (stage "top"), kept apart for the same reason
   prb::StageTimer profile_timer; // prb_search_page_profile and prb_profset_finish (stage "profile"), likewise
   prb::StageTimer tophits_timer; // the merge of prb_search_page_tophits (stage "tophits"), likewise
+  prb::StageTimer targets_timer; // the merges of prb_search_page_targets and prb_targetset_merge (stage "targets"), likewise
   prb::StageTimer distinct_timer; // the selection of opts->distinct_sites (stage "distinct"), likewise
 
   int time_begin();

@@ -435,6 +435,49 @@ struct prb_profset : prb::MergeTable {
   }
 };
 
+// prb_targetset_create .. prb_targetset_free: the per-target table of one database, merged into sub-batch by sub-batch
+// (emit_targets, capi_search.hip) for as many batches as the caller likes, and the sort buffers of those merges.  It is
+// keyed by (page, db_id), not by a batch's queries, so it shares nothing with MergeTable but the flags.
+struct prb_targetset {
+  prb_ctx *ctx = nullptr;
+  const prb_db *db = nullptr;
+  int32_t n = 0;
+  std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
+  std::vector<std::vector<uint64_t>> merged;  // per page: a bit per query identifier merged, grown on demand
+  bool broken = false, finished = false;
+  int32_t distinct = -1;                      // opts->distinct_sites of the merged calls (-1: none yet)
+  int64_t counts[3] = {0, 0, 0};
+  prb::DevBuf table;                          // TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
+  prb::DevBuf ids;                            // the identifiers of the batch being merged
+  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
+  std::vector<prb_target_pair> pairs;         // prb_targetset_finish
+  int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
+  size_t entries() const { return (size_t)targets() * (size_t)n; }
+  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)) + ((size_t)targets() + 1) * sizeof(int32_t); }
+  // the three arrays of a block at b (the table's own, or a copy of another table's)
+  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
+  prb_target_pair *slots_of(void *b) const { return reinterpret_cast<prb_target_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
+  int32_t *fill_of(void *b) const {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)));
+  }
+  bool has(size_t page, int32_t id) const {
+    const std::vector<uint64_t> &m = merged[page];
+    return ((size_t)id >> 6) < m.size() && (m[(size_t)id >> 6] >> (id & 63) & 1);
+  }
+  void set(size_t page, int32_t id) {
+    std::vector<uint64_t> &m = merged[page];
+    if (((size_t)id >> 6) >= m.size()) m.resize(((size_t)id >> 6) + 1, 0);
+    m[(size_t)id >> 6] |= 1ull << (id & 63);
+  }
+  void release() {
+    for (prb::DevBuf *b : {&table, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp}) b->release();
+  }
+  ~prb_targetset() { // (also on the error paths of prb_targetset_create)
+    if (table.p || ids.p || key.p) (void)hipSetDevice(ctx->device);
+    release();
+  }
+};
+
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS): PRB_HOST_THREADS, else half of the CPUs the
 // process may keep busy, at most 32 (capi_pages.hip)
@@ -447,6 +490,7 @@ enum class SearchMode {
   kTop,     // prb_search_page_top: per-pair records merged into the top-N table on the device
   kProfile, // prb_search_page_profile: the hits merged into the per-position table on the device
   kTopHits, // prb_search_page_tophits: the hits and their base pairs merged into the top-N hit table on the device
+  kTargets, // prb_search_page_targets: per-pair records merged into the per-target table on the device
 };
 // (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
@@ -456,11 +500,12 @@ int page_slot(prb_ctx *user, prb_db *db, int page, int keep, hipStream_t stream,
 std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, int32_t max_seed_length,
                                           double hybrid_threshold);
 // capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
-// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits of kTop / kProfile / kTopHits
+// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits / prb_targetset of kTop /
+// kProfile / kTopHits / kTargets
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                SearchMode mode, prb_hitset **out, MergeTable *table = nullptr);
+                SearchMode mode, prb_hitset **out, void *table = nullptr);
 // capi_search.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
 int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh);
 } // namespace prb

@@ -1,6 +1,7 @@
 // Host-visible interface of the interaction-search kernels: the structs the device sees, then one section per kernel
 // file in the order of the pipeline - seed expansion, ungapped extension, sort, redundancy filter, gapped extension,
-// traceback - and behind it the output modes' own stages (pair summaries and distinct sites, top-N tables, profile).
+// traceback - and behind it the output modes' own stages (pair summaries and distinct sites, top-N tables, per-target
+// table, profile).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -357,6 +358,35 @@ hipError_t launch_tophits_gather(void *tab, const int32_t *fill, int32_t n, int6
 hipError_t launch_top_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, hipStream_t s);
 hipError_t launch_tophits_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, int64_t shift,
                                hipStream_t s);
+
+// ============================================================================ target_kernels.hip: per-target table
+// (prb_search_page_targets)  A target = (page, db_id), numbered page by page; per target n ranked keys, n payload slots
+// (prb_target_pair) and a fill count.  A key: the order-preserving image of e_min, the query's identifier, and `at` - in
+// the table the payload slot of the entry (payloads never move), in a sub-batch's run the record's index.
+struct alignas(16) TargetKey {
+  uint64_t e;
+  uint32_t id, at;
+};
+// rec[0, nrec) = launch_pair_fold's records of a sub-batch: `query` (index in the batch, < nq) becomes ids[query];
+// key[i] = db_id, val[i] = i - what the stable sort by target takes
+hipError_t launch_target_ids(void *rec, int64_t nrec, const int32_t *ids, int32_t nq, uint32_t *key, uint32_t *val, hipStream_t s);
+// behind that sort (key, val sorted): rkey[i] = the rank key of record val[i] (`at` = val[i]), head[i] = 1 where key
+// changes (and for i = 0): the first record of every target's run
+hipError_t launch_target_runs(const void *rec, int64_t nrec, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head,
+                              hipStream_t s);
+// the runs [start[r], start[r + 1]) (the last one up to nrec) of rkey - run r is target tbase + db_of[start[r]] of
+// `page` (nseq sequences) - merged into the table, a wavefront per run; no (query id, page) may be in the table yet
+hipError_t launch_target_merge(const void *rec, const TargetKey *rkey, const uint32_t *db_of, const uint32_t *start, int64_t nruns,
+                               int64_t nrec, int32_t page, int64_t tbase, int32_t nseq, int32_t n, TargetKey *keys, void *slots, int32_t *fill,
+                               hipStream_t s);
+// prb_targetset_merge: per target, the table's and src's ranked entries merged under the table's order, the first n kept,
+// in the table (src is only read); a wavefront per target
+hipError_t launch_target_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
+                              int64_t ntargets, int32_t n, hipStream_t s);
+// prb_targetset_finish: out[0, total) = the filled slots by target, then rank (`rank` set); off = the exclusive scan of
+// fill over ntargets + 1 values
+hipError_t launch_target_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t ntargets, int32_t n, int64_t total,
+                                void *out, hipStream_t s);
 
 // ============================================================================ profile_kernels.hip: per-position profile
 // (prb_search_page_profile)

@@ -126,6 +126,29 @@ bool write_all(int fd, const char *p, size_t n) {
   return true;
 }
 
+// rounds of pieces: formatted in parallel, then written in order; false when a write failed
+template <class Fmt> bool write_pieces(const std::vector<Piece> &pieces, Fmt fmt, LineSink &sink, int threads) {
+  const size_t per_round = (size_t)std::max(1, threads) * 4;
+  std::vector<Buf> bufs(std::min(per_round, std::max<size_t>(pieces.size(), 1)));
+  bool ok = true;
+  for (size_t r0 = 0; r0 < pieces.size() && ok; r0 += per_round) {
+    const size_t r1 = std::min(pieces.size(), r0 + per_round);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, threads))
+    for (size_t k = r0; k < r1; k++) {
+      Buf &b = bufs[k - r0];
+      b.n = 0;
+      fmt(pieces[k], b);
+    }
+    for (size_t k = r0; k < r1 && ok; k++) {
+      const Buf &b = bufs[k - r0];
+      if (sink.fd >= 0 && b.n) ok = write_all(sink.fd, b.v.data(), b.n);
+      sink.bytes += (int64_t)b.n;
+      sink.lines += pieces[k].i1 - pieces[k].i0;
+    }
+  }
+  return ok;
+}
+
 // Records of one batch (per page, ascending by query) as lines, query by query and page by page, numbered from id0 on:
 // n_of(p) = records of page p, query_of(p, i) = the query of record i, fmt(piece, buf) formats a piece.
 template <class NOf, class QueryOf, class Fmt>
@@ -147,26 +170,7 @@ int64_t format_records(size_t nq, size_t np, NOf n_of, QueryOf query_of, Fmt fmt
         pieces.push_back(Piece{(uint32_t)q, (uint32_t)p, i, e, id});
         id += e - i;
       }
-  // rounds of pieces: formatted in parallel, then written in order
-  const size_t per_round = (size_t)std::max(1, threads) * 4;
-  std::vector<Buf> bufs(std::min(per_round, std::max<size_t>(pieces.size(), 1)));
-  bool ok = true;
-  for (size_t r0 = 0; r0 < pieces.size() && ok; r0 += per_round) {
-    const size_t r1 = std::min(pieces.size(), r0 + per_round);
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, threads))
-    for (size_t k = r0; k < r1; k++) {
-      Buf &b = bufs[k - r0];
-      b.n = 0;
-      fmt(pieces[k], b);
-    }
-    for (size_t k = r0; k < r1 && ok; k++) {
-      const Buf &b = bufs[k - r0];
-      if (sink.fd >= 0 && b.n) ok = write_all(sink.fd, b.v.data(), b.n);
-      sink.bytes += (int64_t)b.n;
-      sink.lines += pieces[k].i1 - pieces[k].i0;
-    }
-  }
-  return ok ? id : -1;
+  return write_pieces(pieces, fmt, sink, threads) ? id : -1;
 }
 
 // one summary line (`ris -t`) of pair x, found in the page whose table is `tab`
@@ -199,6 +203,12 @@ void format_top_piece(const Piece &pc, const TopView &v, const std::vector<SeqTa
   int64_t id = pc.id;
   for (int64_t i = pc.i0; i < pc.i1; i++)
     put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[v.r[i].page], v.r[i].s);
+}
+
+void format_target_piece(const Piece &pc, const TargetView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++)
+    put_summary_line(b, id++, v.names[v.r[i].s.query], v.qlen_unmasked[v.r[i].s.query], tabs[v.r[i].page], v.r[i].s);
 }
 
 void format_profile_piece(const Piece &pc, const ProfileView &v, const std::vector<SeqTable> &tabs, Buf &b) {
@@ -263,6 +273,13 @@ int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, in
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_top_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (the records are in output order, and not grouped by query: pieces of consecutive records)
+  std::vector<Piece> pieces;
+  for (int64_t i = 0; i < v.n; i += kPieceLines) pieces.push_back(Piece{0, 0, i, std::min(v.n, i + kPieceLines), id0 + i});
+  return write_pieces(pieces, [&](const Piece &pc, Buf &b) { format_target_piece(pc, v, tabs, b); }, sink, threads) ? id0 + v.n : -1;
 }
 
 } // namespace prb

@@ -69,6 +69,15 @@ struct TopView : QueryView {
 };
 int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -r N` (prb_targetset_pairs): the same lines again, in the records' order (by page, target and rank),
+// numbered from id0 on.  The queries are those of the whole run: `names` and `qlen_unmasked` are indexed by the
+// records' query identifiers.
+struct TargetView : QueryView {
+  const prb_target_pair *r = nullptr;
+  int64_t n = 0;
+};
+int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 // Lines of `ris -q` (prb_profset_rows), one per covered query position, in the rows' order (ascending by query, then by
 // position), numbered from id0 on:
 //   Id,qname,qlen,Position,Hits,Targets,MinE,dbname,dblen,(q0-qN:db0-dbN)

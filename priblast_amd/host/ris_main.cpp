@@ -33,9 +33,13 @@
 // first: a table on the GPU (prb_search_page_tophits) takes every page of a batch and keeps those hits with their base
 // pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.  `ris -u` keeps only the distinct
 // interaction sites of each (query, target) pair - greedy non-maximum suppression on the GPU, before the traceback
-// (prb_ris_opts::distinct_sites) - and combines with every mode: each of them takes the thinned list.
+// (prb_ris_opts::distinct_sites) - and combines with every mode: each of them takes the thinned list.  `ris -r N` turns
+// `-t -n` round: the `-t` lines of each TARGET's N pairs of lowest minimum energy over all the queries of the run.  Every
+// worker owns one table on its GPU for the whole run (prb_search_page_targets takes every page of every batch it
+// searches); at the end the first worker merges the others' into its own (prb_targetset_merge), and only N records per
+// target reach the host, written by page, target and rank.  `-r` is refused with -t, -n, -q, -k, -b and in rank mode.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u have one table (kSwitchTable) that every refusal is generated
+// How the file is laid out.  The switches -t -n -q -k -b -u -r have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
 // join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
 // (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
@@ -116,6 +120,10 @@ void usage() {
             "              first (interaction energy, ties in output order), and a hit is kept only if its query range and\n"
             "              its target range do not both overlap those of a hit kept before it; the lines are lines of the\n"
             "              run without -u (with every other switch; -t, -n, -q and -k then count and rank the kept hits)\n"
+            "    -r INT    the -t lines of only the INT queries of lowest minimum interaction energy per target (database\n"
+            "              sequence) over all the queries, written at the end of the run by page, target and rank (ties by\n"
+            "              the query's place in the input file; 1 <= INT <= 1024; not with -t, -n, -q, -k, -b, nor with\n"
+            "              WORLD_SIZE > 1; -u combines)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -137,14 +145,15 @@ thread_local bool t_team_thread = false;
 }
 
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
-// `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits };
+// `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
+// N best pairs per target.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kR, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -160,6 +169,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'k', "the N best interaction sites per query", bit(kT) | bit(kN) | bit(kQ), -1, true},
     {'b', "binary hit records", 0, -1, false},
     {'u', "the distinct interaction sites of each pair", 0, -1, false},
+    {'r', "the N best queries per target", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB), -1, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -167,7 +177,7 @@ struct Args {
   std::string in, out, db, tmp;
   prb_ris_opts o;
   bool given[kSwitches] = {};
-  int top = 0, tophits = 0; // the values of -n and -k (-1: not a count)
+  int top = 0, tophits = 0, targets = 0; // the values of -n, -k and -r (-1: not a count)
   OutputMode mode = OutputMode::kHits;
   bool binary() const { return given[kB]; }
 };
@@ -176,6 +186,8 @@ struct Worker {
   int device;
   prb_ctx *ctx = nullptr, *prep_ctx = nullptr; // prep_ctx: accessibilities of the next batch, on a stream of its own
   prb_db *db = nullptr;
+  prb_targetset *targets = nullptr;                   // -r: this worker's table, for the whole run
+  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r: (input position, unmasked length) of the queries it prepared
 };
 
 // The one place where what a search returned is freed.
@@ -210,6 +222,7 @@ struct BatchJob {
 struct Prepared {
   prb_qbatch *qb = nullptr;
   std::vector<int32_t> qlen_unmasked;
+  std::vector<int32_t> ids; // its queries' positions in the input file (-r: their identifiers in the table)
 };
 
 // ---- binary hit file (little-endian, the layouts of include/priblast_hip.h) ----------------------
@@ -487,7 +500,7 @@ struct Run {
   }
 };
 
-// the value of -n / -k: a count, or -1
+// the value of -n / -k / -r: a count, or -1
 int parse_count(const char *arg) {
   char *end = nullptr;
   const long v = std::strtol(arg, &end, 10);
@@ -502,13 +515,13 @@ void check_switches(const Args &a) {
       if (a.given[p] && (kSwitchTable[s].not_with & (1u << p))) die("Error: " + described(s) + " can't be combined with " + described(p));
     if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need]) die("Error: " + described(s) + " needs " + described(need));
   }
-  for (Switch s : {kK, kN})
-    if (const int v = s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
+  for (Switch s : {kR, kK, kN})
+    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
 }
 
 OutputMode output_mode(const Args &a) {
-  return a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
+  return a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
 }
 
@@ -516,7 +529,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:u")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ur:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -536,6 +549,7 @@ Args parse_args(int argc, char **argv) {
     case 'u': a.given[kU] = true, a.o.distinct_sites = 1; break;
     case 'n': a.given[kN] = true, a.top = parse_count(optarg); break;
     case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
+    case 'r': a.given[kR] = true, a.targets = parse_count(optarg); break;
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -617,6 +631,7 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prb_ctx_create(devices[k], nullptr, &w.ctx)) die(std::string("Error: ") + prb_last_error());
     if (prefetch && prb_ctx_create(devices[k], nullptr, &w.prep_ctx)) die(std::string("Error: ") + prb_last_error());
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
+    if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
   }
 }
 
@@ -681,6 +696,7 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name,Query Length,Position,Hits,Targets,Minimum Interaction Energy,Target name,Target Length,BasePair\n";
   case OutputMode::kSummary:
   case OutputMode::kTop:
+  case OutputMode::kTargets:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
   case OutputMode::kHits:
@@ -741,6 +757,7 @@ Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b, int
   if (prb_qbatch_accessibility(c, p.qb, r.W, r.delta)) die(prb_last_error());
   p.qlen_unmasked.resize(idx.size());
   for (size_t q = 0; q < idx.size(); q++) p.qlen_unmasked[q] = prb_qbatch_length_unmasked(p.qb, (int32_t)q);
+  p.ids.assign(idx.begin(), idx.end());
   return p;
 }
 
@@ -778,17 +795,21 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
+  case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
   if (rc) die(prb_last_error());
 }
 
-// one page of a prepared batch searched: into the table of `mine`, or - a hit set or a pair set - into slot `page` of `out`
-void search_one_page(const Run &r, Worker &w, prb_qbatch *qb, int page, BatchResult &mine, BatchResult &out) {
+// one page of a prepared batch searched: into the table of `mine` (-r: into the worker's), or - a hit set or a pair set -
+// into slot `page` of `out`
+void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, BatchResult &mine, BatchResult &out) {
   const Args &a = r.a;
+  prb_qbatch *qb = p.qb;
   int rc = 0;
   switch (a.mode) {
+  case OutputMode::kTargets: rc = prb_search_page_targets(w.ctx, qb, w.db, page, &a.o, p.ids.data(), w.targets); break;
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &a.o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &a.o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &a.o, mine.tophits.get()); break;
@@ -819,6 +840,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kTop: run(kTopOps, &BatchResult::top); break;
   case OutputMode::kProfile: run(kProfOps, &BatchResult::prof); break;
   case OutputMode::kTopHits: run(kTopHitsOps, &BatchResult::tophits); break;
+  case OutputMode::kTargets:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -833,12 +855,19 @@ BatchResult empty_result(const Run &r) {
   return res;
 }
 
+// -r: the lines are written at the end of the run, with every query's unmasked length by its place in the input
+void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
+  if (r.a.mode != OutputMode::kTargets) return;
+  for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
+}
+
 // the search stages of a prepared batch against every page
 BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
   create_table(r, w, p.qb, res);
-  for (int page = 0; page < r.npages; page++) search_one_page(r, w, p.qb, page, res, res);
+  for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
   finish_table(r, w, res);
+  note_target_queries(r, w, p);
   prb_qbatch_destroy(p.qb);
   p.qb = nullptr;
   return res;
@@ -919,6 +948,7 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.n = prb_topset_size(job.res.top.get());
     return written_or_die(prb::format_top_batch(v, r.tabs, id, sink, threads));
   }
+  case OutputMode::kTargets: return id; // (nothing but progress: the table is written at the end of the run, close_run)
   case OutputMode::kSummary: {
     prb::SummaryView v;
     set_queries(v, job);
@@ -1124,9 +1154,10 @@ struct Team {
     create_table(r, w, p.qb, mine);
     for (int page = k < (size_t)r.npages ? (int)k : tb->next_page.fetch_add(1); page < r.npages; page = tb->next_page.fetch_add(1)) {
       if (has_failed()) throw TeamError{""};
-      search_one_page(r, w, p.qb, page, mine, tb->res);
+      search_one_page(r, w, p, page, mine, tb->res);
       pages_of_worker[k]++;
     }
+    note_target_queries(r, w, p);
     signal([&] { tb->arrived++; });
     BatchResult res;
     if (k == 0) {
@@ -1284,7 +1315,32 @@ void run_ranks(Run &r, Writer &writer) {
   gatherer.close();
 }
 
+// -r: the first worker merges the others' tables into its own on the device and finishes it; the lines by page, target
+// and rank, numbered from 0
+void write_targets(Run &r) {
+  Worker &w0 = r.workers[0];
+  std::vector<int32_t> qlen(r.seqs.size(), 0);
+  for (Worker &w : r.workers) {
+    for (const auto &[id, len] : w.target_qlen) qlen[(size_t)id] = len;
+    if (&w != &w0 && prb_targetset_merge(w0.ctx, w0.targets, w.targets)) die(prb_last_error());
+  }
+  if (prb_targetset_finish(w0.ctx, w0.targets)) die(prb_last_error());
+  prb::TargetView v;
+  v.nq = r.names.size();
+  v.names = r.names.data();
+  v.qlen_unmasked = qlen.data();
+  v.r = prb_targetset_pairs(w0.targets);
+  v.n = prb_targetset_size(w0.targets);
+  for (int64_t i = 0; i < v.n; i++)
+    if (v.r[i].s.query < 0 || (size_t)v.r[i].s.query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages)
+      die("Error: bad record in the table of the best queries per target");
+  LineSink sink;
+  sink.fd = fileno(r.out);
+  written_or_die(prb::format_target_batch(v, r.tabs, 0, sink, prb::format_threads()));
+}
+
 void close_run(Run &r, int64_t total_hits) {
+  if (r.a.mode == OutputMode::kTargets && r.rank == 0) write_targets(r);
   if (r.a.binary()) {
     put<int64_t>(r.out, kEnd);
     put<int64_t>(r.out, total_hits);
@@ -1292,6 +1348,7 @@ void close_run(Run &r, int64_t total_hits) {
   if (std::fclose(r.out)) die("Error: can't write the output file");
   if (r.comm) prb_comm_destroy(r.comm);
   for (auto &w : r.workers) {
+    prb_targetset_free(w.targets);
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
     prb_ctx_destroy(w.ctx);
