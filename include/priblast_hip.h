@@ -219,6 +219,24 @@ void prb_hitset_free(prb_hitset *hs);
  * The runs need not be sorted by db_sp.  n <= 2^31 - 1; n = 0 does nothing. */
 int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep);
 
+/* Diagnostics: a caller's list of hit records, in any order, through the sort and the redundancy filter that every
+ * search runs behind its ungapped and its gapped stage (the same code, with the PRB_SORT_* / PRB_FILTER_TILES switches
+ * of the environment).  sorted[n]: the records in the stages' order (query, db_sp, q_sp, db_len and q_len descending,
+ * e_tot, e_hyb, e_acc, place in the input), bp_count and bp_offset zero; keep[n]: 1 for the hits at those sorted places
+ * that the filter leaves with `threshold`; *form: the form of the sort that gave the order.  The bounds of the one-key
+ * sort come from the list itself (the one-length key: every hit has q_len == db_len).  query, q_sp and db_sp must not be
+ * negative, q_sp + q_len and db_sp + db_len at most 2^31 - 1 (lengths count modulo 2^16, as in the search);
+ * n <= 2^31 - 1; n = 0 does nothing. */
+enum {
+  PRB_SORT_PACKED_TWO_LENGTHS = 0, /* one packed key with both lengths */
+  PRB_SORT_PACKED_ONE_LENGTH = 1,  /* one packed key with the length once */
+  PRB_SORT_GENERAL_WIDTH = 2,      /* the sort field by field: the packed key needs more than 64 bits */
+  PRB_SORT_GENERAL_TIE_RUN = 3,    /* ... : more hits with identical coordinates than the tie pass takes */
+  PRB_SORT_GENERAL_FORCED = 4      /* ... : PRB_SORT_FOUR_KEYS is set */
+};
+int prb_sort_filter(prb_ctx *ctx, const prb_hit *hits, int64_t n, double threshold, prb_hit *sorted, uint8_t *keep,
+                    int32_t *form);
+
 /* ---- per-pair summaries (`ris -t`): the final hits reduced on the device, one record per (query, database
  * sequence) pair that has at least one final hit.  The hits are exactly those prb_search_page(..., 3, ...) returns
  * with the same options (any output_style); their order there is the "output order" below.

@@ -132,6 +132,12 @@ void orc_extend_ungapped(const orc_db *db, int page, const orc_ris_opts *o, cons
 void orc_extend_gapped(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc,
                        int qn, const float *qacc, const float *qcond, orc_hits *hits);
 
+/* The stages' sort (the reference's compare made total: energy, its hybridization part, its accessibility part, input
+ * order) and CheckRedundancy's sweep on a caller's list of ONE query, for the tests of the sort and filter kernels:
+ * order[i] = index in `in` of the hit at sorted position i, keep[i] = 1 if the sweep leaves that hit.  `in` is only
+ * read (flag and bp are ignored). */
+void orc_sort_filter(const orc_hit *in, size_t n, double thr, uint32_t *order, uint8_t *keep);
+
 /* whole `ris` (rna_interaction_search.cpp:61-92), single thread unless nthreads>1
  * (queries are independent; output order = query order, page order, hit order).
  * Returns the number of hits written, <0 on error. */

@@ -320,8 +320,8 @@ static void sort_hits(orc_hits *v) {
   free(r);
 }
 
-/* CheckRedundancy, rna_interaction_search.cpp:387-424 */
-static void check_redundancy(orc_hits *v, double thr) {
+/* CheckRedundancy, rna_interaction_search.cpp:387-424: the sweep that sets the flags ... */
+static void sweep_redundancy(orc_hits *v, double thr) {
   for (size_t i = 0; i < v->n; i++) {
     orc_hit *a = &v->h[i];
     if (a->e_tot > thr) a->flag = 1;
@@ -341,12 +341,35 @@ static void check_redundancy(orc_hits *v, double thr) {
       }
     }
   }
+}
+
+/* ... and the removal of the flagged hits */
+static void check_redundancy(orc_hits *v, double thr) {
+  sweep_redundancy(v, thr);
   size_t w = 0;
   for (size_t i = 0; i < v->n; i++) {
     if (v->h[i].flag) free(v->h[i].bp);
     else v->h[w++] = v->h[i];
   }
   v->n = w;
+}
+
+/* The sort and the sweep above on a caller's list of ONE query (oracle.h) */
+void orc_sort_filter(const orc_hit *in, size_t n, double thr, uint32_t *order, uint8_t *keep) {
+  sort_rec *r = malloc(sizeof(sort_rec) * (n ? n : 1));
+  orc_hits v = {n, n, malloc(sizeof(orc_hit) * (n ? n : 1))};
+  for (size_t i = 0; i < n; i++) { r[i].h = in[i]; r[i].ord = i; }
+  qsort(r, n, sizeof(sort_rec), hit_cmp);
+  for (size_t i = 0; i < n; i++) {
+    v.h[i] = r[i].h;
+    v.h[i].flag = 0;
+    v.h[i].bp = NULL; /* (the caller's: nothing of it is freed) */
+    order[i] = (uint32_t)r[i].ord;
+  }
+  sweep_redundancy(&v, thr);
+  for (size_t i = 0; i < n; i++) keep[i] = v.h[i].flag ? 0 : 1;
+  free(v.h);
+  free(r);
 }
 
 void orc_extend_ungapped(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc, int qn,

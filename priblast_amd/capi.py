@@ -113,6 +113,8 @@ SYMBOLS = {
     "prb_hitset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_free": (None, [ctypes.c_void_p]),
     "prb_distinct_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "prb_sort_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_dbl, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
     "prb_search_page_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts),
                                                P(ctypes.c_void_p)]),
     "prb_pairset_size": (c_i64, [ctypes.c_void_p]),
@@ -435,6 +437,23 @@ def distinct_sites(ctx, hits):
     _check(lib().prb_distinct_sites(ctx.h, hits.ctypes.data if len(hits) else None, len(hits),
                                     keep.ctypes.data if len(hits) else None))
     return keep
+
+
+# prb_sort_filter's *form (include/priblast_hip.h)
+SORT_PACKED_TWO_LENGTHS, SORT_PACKED_ONE_LENGTH, SORT_GENERAL_WIDTH, SORT_GENERAL_TIE_RUN, SORT_GENERAL_FORCED = range(5)
+
+
+def sort_filter(ctx, hits, threshold):
+    """prb_sort_filter: hits = structured array HIT_DTYPE in any order -> (the records in the stages' sorted order, uint8
+    [n] keep flags of the redundancy filter by sorted position, the SORT_* form of the sort that ran; None for no hits)"""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    n = len(hits)
+    out = np.zeros(n, HIT_DTYPE)
+    keep = np.zeros(n, np.uint8)
+    form = np.full(1, -1, np.int32)
+    _check(lib().prb_sort_filter(ctx.h, hits.ctypes.data if n else None, n, float(threshold), out.ctypes.data if n else None,
+                                 keep.ctypes.data if n else None, form.ctypes.data))
+    return out, keep, int(form[0]) if n else None
 
 
 def search_page_summary(ctx, qb, db, page, opts=None, with_counts=False):

@@ -203,11 +203,12 @@ static int bits_for(int64_t max_value) {
 
 // Sorts the records `recs` (n hits) into `out` by the reference's comparator made total:
 // (query, db_sp asc, q_sp asc, db_len desc, q_len desc, energy asc, hybridization part asc, accessibility part asc,
-// input order).  perm_out[i] = index in `recs`.
-static int sort_hits(SubSearch &s, const HitRec *recs, HitSoA out, int64_t n, const SortBounds &sb, uint32_t **perm_out) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
+// input order).  perm_out[i] = index in `recs`.  form (optional): which form of the sort gave the order, a PRB_SORT_* of
+// include/priblast_hip.h.
+static int sort_hits(prb_ctx *ctx, SearchWs &w, const SearchKnobs &k, const HitRec *recs, HitSoA out, int64_t n, const SortBounds &sb,
+                     uint32_t **perm_out, int32_t *form = nullptr) {
   int rc;
+  int32_t why = PRB_SORT_GENERAL_FORCED;
   const size_t N = (size_t)n;
   {
     // one stable radix sort over a packed key + a pass over the runs of identical coordinates
@@ -219,7 +220,8 @@ static int sort_hits(SubSearch &s, const HitRec *recs, HitSoA out, int64_t n, co
     f.bq = bits_for(sb.max_qlen);
     f.bd = bits_for(sb.nchars);
     const int total = (f.one_len ? 1 : 2) * f.bl + f.bq + f.bd + bits_for(sb.qspan - 1);
-    if (total <= 64 && f.lmax <= 65535 && !s.k.sort_four_keys) {
+    if (!k.sort_four_keys) why = PRB_SORT_GENERAL_WIDTH;
+    if (total <= 64 && f.lmax <= 65535 && !k.sort_four_keys) {
       if ((rc = w.kP.ensure(N * 8)) || (rc = w.kTmp2.ensure(N * 8)) || (rc = w.kE.ensure(N * 8)) || (rc = w.kTmp.ensure(N * 8)) ||
           (rc = w.idxA.ensure(N * 4)) || (rc = w.idxB.ensure(N * 4)) || (rc = w.pending.ensure(16)))
         return rc;
@@ -237,12 +239,15 @@ static int sort_hits(SubSearch &s, const HitRec *recs, HitSoA out, int64_t n, co
       if (!too_long) {
         PRB_HIP(launch_gather_recs_to_hits(recs, w.idxA.as<uint32_t>(), out, n, ctx->stream));
         *perm_out = w.idxA.as<uint32_t>();
+        if (form) *form = f.one_len ? PRB_SORT_PACKED_ONE_LENGTH : PRB_SORT_PACKED_TWO_LENGTHS;
         return PRB_OK;
       }
+      why = PRB_SORT_GENERAL_TIE_RUN;
     }
   }
+  if (form) *form = why;
   // The general form works on the fields as arrays.  LSD: one stable radix sort per key, least significant first.
-  if (s.k.debug_mem) fprintf(stderr, "[mem] sort: the general form (%lld hits)\n", (long long)n);
+  if (k.debug_mem) fprintf(stderr, "[mem] sort: the general form (%lld hits)\n", (long long)n);
   if ((rc = w.hitsTmp.ensure(hits_bytes(n)))) return rc;
   const HitSoA in = carve_hits(w.hitsTmp, n);
   PRB_HIP(launch_gather_recs_to_hits(recs, nullptr, in, n, ctx->stream));
@@ -273,7 +278,7 @@ static int sort_hits(SubSearch &s, const HitRec *recs, HitSoA out, int64_t n, co
   if ((rc = sort_step(w.kTmp.as<uint32_t>(), 32))) return rc;
   PRB_HIP(launch_gather_u64(w.kP.as<uint64_t>(), ia, w.kTmp.as<uint64_t>(), n, ctx->stream));
   unsigned qbits = 1;
-  while ((1 << qbits) < s.qb->nq && qbits < 31) qbits++;
+  while ((int64_t(1) << qbits) < (int64_t)sb.qmin + sb.qspan && qbits < 31) qbits++; // (the queries of the list are below that)
   if ((rc = sort_step(w.kTmp.as<uint64_t>(), 32 + qbits))) return rc;
   PRB_HIP(launch_gather_hits(in, ia, out, n, ctx->stream));
   *perm_out = ia;
@@ -648,7 +653,7 @@ static int sort_filter_ungapped(SubSearch &s) {
   if ((rc = ctx->time_begin())) return rc;
   SortBounds sb1 = s.sb; // hits extended without gaps have one length: the key is 11 + (11 - bits of the longest) bits shorter
   if (s.all_one_pass && s.one_pass_maxlen > 0 && !s.k.sort_two_lengths) sb1.eq_len_max = (int32_t)s.one_pass_maxlen;
-  if ((rc = sort_hits(s, w.hitsB.as<HitRec>(), B, s.nf, sb1, &perm))) return rc;
+  if ((rc = sort_hits(ctx, w, s.k, w.hitsB.as<HitRec>(), B, s.nf, sb1, &perm))) return rc;
   if ((rc = ctx->time_end("sort", 9))) return rc;
   if (big_list) // (the records and the sort's keys are dead)
     for (DevBuf *b : {&w.hitsB, &w.kE, &w.kL, &w.kQ, &w.kP, &w.kTmp, &w.kTmp2, &w.idxA, &w.idxB, &w.sortTmp}) b->release();
@@ -1057,7 +1062,7 @@ static int final_sort_filter(SubSearch &s) {
   HitSoA S = carve_hits(w.hitsC, s.ngap); // G is dead after the compaction
   uint32_t *perm = nullptr;
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = sort_hits(s, w.hitsB.as<HitRec>(), S, s.ngap, s.sb, &perm))) return rc;
+  if ((rc = sort_hits(ctx, w, s.k, w.hitsB.as<HitRec>(), S, s.ngap, s.sb, &perm))) return rc;
   if ((rc = ctx->time_end("sort", 9))) return rc;
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = filter_hits(ctx, w, S, s.ngap, s.opts.final_threshold, s.k.filter_tiles, &s.nfin))) return rc;
@@ -1821,6 +1826,71 @@ int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *ke
   if ((rc = select_sites(ctx, w, carve_hits(w.hitsTmp, n), n, knobs.distinct_lds_hits))) return rc;
   if ((rc = ctx->time_end(ctx->distinct_timer, 3))) return rc;
   PRB_HIP(hipMemcpyAsync(keep, w.keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  return PRB_OK;
+}
+
+// A caller's records through the search's own sort and redundancy filter (sort_hits, filter_hits: what
+// sort_filter_ungapped and final_sort_filter call), with the field bounds of the one-key sort taken from the list itself.
+int prb_sort_filter(prb_ctx *ctx, const prb_hit *hits, int64_t n, double threshold, prb_hit *sorted, uint8_t *keep, int32_t *form) {
+  if (!ctx || n < 0 || (n > 0 && (!hits || !sorted || !keep || !form))) {
+    set_error("prb_sort_filter: bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (n == 0) return PRB_OK;
+  if (n > INT32_MAX) {
+    set_error("prb_sort_filter: more than 2^31 - 1 hits");
+    return PRB_ERR_ARG;
+  }
+  const SearchKnobs knobs = read_search_knobs();
+  SortBounds sb;
+  int32_t qlo = INT32_MAX, qhi = 0, eq_len = 0;
+  bool one_len = !knobs.sort_two_lengths;
+  auto len16 = [](int32_t v) { return (int32_t)(uint16_t)v; }; // (the search's lengths are unsigned short, search_device.hpp)
+  for (int64_t i = 0; i < n; i++) {
+    const prb_hit &h = hits[i];
+    const int64_t qend = (int64_t)h.q_sp + len16(h.q_len), dend = (int64_t)h.db_sp + len16(h.db_len);
+    if (h.query < 0 || h.q_sp < 0 || h.db_sp < 0 || qend > INT32_MAX || dend > INT32_MAX) {
+      set_error("prb_sort_filter: hit " + std::to_string(i) + " has a negative query or a coordinate outside 0 .. 2^31 - 1");
+      return PRB_ERR_ARG;
+    }
+    qlo = std::min(qlo, h.query);
+    qhi = std::max(qhi, h.query);
+    sb.max_qlen = std::max(sb.max_qlen, (int32_t)qend);
+    sb.max_dblen = std::max(sb.max_dblen, len16(h.db_len));
+    sb.nchars = std::max(sb.nchars, (int32_t)dend);
+    one_len = one_len && len16(h.q_len) == len16(h.db_len);
+    eq_len = std::max(eq_len, len16(h.db_len));
+  }
+  sb.qmin = qlo;
+  sb.qspan = qhi - qlo + 1;
+  sb.eq_len_max = one_len ? eq_len : 0;
+  PRB_HIP(hipSetDevice(ctx->device));
+  SearchWs &w = ws_of(ctx);
+  int rc;
+  const size_t N = (size_t)n;
+  if ((rc = w.hitsB.ensure(N * sizeof(HitRec))) || (rc = w.hitsC.ensure(hits_bytes(n))) || (rc = w.packed.ensure(N * sizeof(prb_hit))))
+    return rc;
+  try {
+    std::vector<HitRec> host(N);
+    for (int64_t i = 0; i < n; i++) {
+      const prb_hit &h = hits[i];
+      host[(size_t)i] = HitRec{h.q_sp, h.db_sp, h.q_len, h.db_len, h.db_id, h.db_id_start, h.query, 0, h.e_acc, h.e_hyb, h.e_tot, 0};
+    }
+    PRB_HIP(hipMemcpyAsync(w.hitsB.p, host.data(), N * sizeof(HitRec), hipMemcpyHostToDevice, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the copy is staged, `host` may go)
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_sort_filter: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  const HitSoA S = carve_hits(w.hitsC, n);
+  uint32_t *perm = nullptr;
+  int64_t nsurv = 0;
+  if ((rc = sort_hits(ctx, w, knobs, w.hitsB.as<HitRec>(), S, n, sb, &perm, form))) return rc;
+  if ((rc = filter_hits(ctx, w, S, n, threshold, knobs.filter_tiles, &nsurv))) return rc;
+  PRB_HIP(launch_pack_hits(S, n, nullptr, nullptr, -1, w.packed.p, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(sorted, w.packed.p, N * sizeof(prb_hit), hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(keep, w.keep.p, N, hipMemcpyDeviceToHost, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream));
   return PRB_OK;
 }

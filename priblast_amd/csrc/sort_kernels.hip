@@ -15,14 +15,21 @@ namespace prb {
 
 namespace {
 
+// Monotone map of a double onto unsigned integers, for the energies of the sort keys.  -0.0 maps as +0.0: the
+// comparator these keys restate compares with != and <, for which the zeros are equal, so the next field decides
+// between them (the hits keep their energies as they are; only the keys are made alike).
+__device__ __forceinline__ uint64_t order_bits(double v) {
+  const uint64_t b = v == 0.0 ? 0ull : (uint64_t)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
 __global__ __launch_bounds__(kBlock) void k_make_keys(HitSoA h, int64_t n, uint64_t *k_energy, uint32_t *k_len,
                                                       uint32_t *k_qsp, uint64_t *k_pos, uint32_t *idx) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   // compare(): db_sp asc, q_sp asc, db_len desc, q_len desc (rna_interaction_search.cpp:45-55);
   // ties are then broken by energy asc, its two parts and input order (DESIGN.md "total order")
-  const uint64_t eb = (uint64_t)__double_as_longlong(h.e_tot[i]);
-  k_energy[i] = (eb >> 63) ? ~eb : (eb | 0x8000000000000000ull);
+  k_energy[i] = order_bits(h.e_tot[i]);
   k_len[i] = ((uint32_t)(0xFFFF - US(h.db_len[i])) << 16) | (uint32_t)(0xFFFF - US(h.q_len[i]));
   k_qsp[i] = (uint32_t)h.q_sp[i];
   k_pos[i] = ((uint64_t)(uint32_t)h.query[i] << 32) | (uint32_t)h.db_sp[i];
@@ -38,8 +45,7 @@ __global__ __launch_bounds__(kBlock) void k_make_packed_keys(HitSoA h, int64_t n
                                                              uint64_t *k_energy, uint32_t *idx) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  const uint64_t eb = (uint64_t)__double_as_longlong(h.e_tot[i]);
-  k_energy[i] = (eb >> 63) ? ~eb : (eb | 0x8000000000000000ull);
+  k_energy[i] = order_bits(h.e_tot[i]);
   uint64_t k = (uint64_t)(uint32_t)(h.query[i] - f.qmin);
   k = (k << f.bd) | (uint32_t)h.db_sp[i];
   k = (k << f.bq) | (uint32_t)h.q_sp[i];
@@ -54,8 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_make_packed_keys_recs(const HitRec *
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const HitRec r = h[i];
-  const uint64_t eb = (uint64_t)__double_as_longlong(r.e_tot);
-  k_energy[i] = (eb >> 63) ? ~eb : (eb | 0x8000000000000000ull);
+  k_energy[i] = order_bits(r.e_tot);
   uint64_t k = (uint64_t)(uint32_t)(r.query - f.qmin);
   k = (k << f.bd) | (uint32_t)r.db_sp;
   k = (k << f.bq) | (uint32_t)r.q_sp;
@@ -66,11 +71,6 @@ __global__ __launch_bounds__(kBlock) void k_make_packed_keys_recs(const HitRec *
 }
 
 constexpr int kMaxTieRun = 4096;
-// monotone map of a double onto unsigned integers
-__device__ __forceinline__ uint64_t order_bits(double v) {
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 // Runs of identical coordinates are put in (energy, hybridization part, accessibility part, input index) order: two
 // hits still tied after the three energies are identical records, so the result does not depend on the order in which
 // the seeds were produced (chunks of candidates, pairs sorted by database position).  Every element of a run finds its

@@ -27,6 +27,13 @@ class Hit(ctypes.Structure):
                 ("bp", ctypes.POINTER(ctypes.c_int32))]
 
 
+# orc_hit as a numpy record (the pointer as an integer)
+ORC_HIT_DTYPE = np.dtype([(n, "<i4") for n in ("q_sp", "db_sp", "q_len", "db_len", "db_id", "db_id_start")] +
+                         [(n, "<f8") for n in ("e_acc", "e_hyb", "e_tot")] +
+                         [("flag", "<i4"), ("nbp", "<i4"), ("bp_cap", "<i4"), ("pad", "<i4"), ("bp", "<u8")])
+assert ORC_HIT_DTYPE.itemsize == ctypes.sizeof(Hit)
+
+
 class Hits(ctypes.Structure):
     _fields_ = [("n", ctypes.c_size_t), ("cap", ctypes.c_size_t), ("h", ctypes.POINTER(Hit))]
 
@@ -75,6 +82,8 @@ def lib():
     L.orc_seed_search.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RisOpts), ctypes.c_void_p,
                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.POINTER(Hits)]
+    L.orc_sort_filter.restype = None
+    L.orc_sort_filter.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
     L.orc_ris.restype = ctypes.c_long
     L.orc_ris.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(RisOpts), ctypes.c_int]
     _lib = L
@@ -168,6 +177,31 @@ class Db:
         gap = hits_to_list(hs)
         L.orc_hits_free(ctypes.byref(hs))
         return seed, ung, gap
+
+
+def sort_filter(hits, thr):
+    """orc_sort_filter (the stages' own comparator and sweep) on a list of several queries: hits = structured array with
+    priblast_amd.capi.HIT_DTYPE's fields, in any order -> (the records by query, then in sorted order, base-pair fields
+    zero; uint8 keep flags by sorted position).  The oracle works on one query at a time: the list is split by `query`,
+    every part keeps its input order (which only decides between identical records)."""
+    hits = np.asarray(hits)
+    out = hits.copy()
+    keep = np.zeros(len(hits), np.uint8)
+    at = 0
+    for q in np.unique(hits["query"]):
+        idx = np.flatnonzero(hits["query"] == q)
+        rec = np.zeros(len(idx), ORC_HIT_DTYPE)
+        for f in ("q_sp", "db_sp", "q_len", "db_len", "db_id", "db_id_start", "e_acc", "e_hyb", "e_tot"):
+            rec[f] = hits[f][idx]
+        order = np.zeros(len(idx), np.uint32)
+        k = np.zeros(len(idx), np.uint8)
+        lib().orc_sort_filter(rec.ctypes.data, len(idx), float(thr), order.ctypes.data, k.ctypes.data)
+        out[at:at + len(idx)] = hits[idx[order]]
+        keep[at:at + len(idx)] = k
+        at += len(idx)
+    out["bp_count"] = 0
+    out["bp_offset"] = 0
+    return out, keep
 
 
 def ris(fasta, dbprefix, out, nthreads=1, **kw):
