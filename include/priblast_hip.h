@@ -133,6 +133,11 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "distinct" (opts->distinct_sites: the pairs' head flags, the two selection kernels and the selection of the kept hits,
  *   launches = 4 per sub-batch with final hits, and 2 more - the gathers of the records and of their pre-gapped
  *   indices - when a hit is dropped; nothing when the option is off; prb_distinct_sites: launches = 3);
+ * "coverage" (prb_search_page_coverage and prb_covset_add_hits: the merge into the per-target coverage table - keys and
+ *   places, the sort by (query, span start), the spans' ends, their running maximum, the difference arrays, and four
+ *   launches for the best hits: minimum energy, minimum tie, take-over, scratch reset; launches = 9 per sub-batch with
+ *   final hits and per prb_covset_add_hits; prb_covset_finish: the two scans, the selection of the regions' heads and the
+ *   region kernel, launches = 4, or 3 when there is no region; prb_covset_merge: 1);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -453,6 +458,92 @@ const prb_target_pair *prb_targetset_pairs(const prb_targetset *ts);
 void prb_targetset_counts(const prb_targetset *ts, int64_t counts[3]);
 void prb_targetset_free(prb_targetset *ts);
 
+/* ---- the regions of each target bound by at least D queries (`ris -c D`): a per-position table of the database on the
+ * device ----
+ * A target is a (page, db_id) of one database.  The span of a final hit (the hits of prb_search_page(..., 3, ...) with the
+ * same options; with distinct_sites the kept ones) on its target is [min(db0, dbN), max(db0, dbN)]: db0 and dbN are the
+ * database coordinates of its first and last base pair in the `-s 0` form (prb_pair_summary's bp_first[1] / bp_last[1]),
+ * positions in the page's text, which holds the sequences reversed.  A span that leaves its sequence [start_pos,
+ * start_pos + length) raises the table's `bad` flag, is counted nowhere, and fails the call that sees it with
+ * PRB_ERR_STATE: prb_covset_add_hits, which checks its list first and leaves the table untouched, or prb_covset_finish
+ * (never for a consistent search).  Per position of a target, over everything merged into the table:
+ *   hits      the number of final hits whose span contains it
+ *   starts    the number of final hits whose span begins at it: at min(db0, dbN), a position of the page's text
+ *   queries   the number of distinct query identifiers with such a hit: the union of each (query id, target)'s spans, two
+ *             hits of one query count once
+ *   e_min     the smallest e_tot of those hits, compared as doubles (-0.0 == +0.0), and the best hit: among the hits with
+ *             e_min the one of the lowest (query id, place).  `place` is the hit's index among that query's hits against
+ *             that page in output order (the list prb_search_page returns), not its index in a sub-batch's list
+ * Query identifiers are the caller's, int32 >= 0, as in prb_search_page_targets; a (query id, page) is merged at most
+ * once.  Every column is a sum, a maximum, a minimum or a lexicographic minimum of integers over a total order, so the
+ * table depends - bit for bit - neither on how the queries are cut into batches or sub-batches, nor on the order of the
+ * batches or of the pages, nor on which context (worker) took what, nor on page residency.
+ * A REGION at depth D is a maximal run of consecutive positions of ONE sequence with queries >= D: two neighbouring
+ * sequences that are both covered from end to end are two regions.  Its record:
+ *   page, db_id   the target
+ *   start, end    inclusive, start <= end, in the sequence's FORWARD coordinates - the numbers that the base-pair field of
+ *                 a result line prints: length - 1 - (text position - start_pos)
+ *   hits          the sum of `starts` over the region: for D = 1 every hit that touches it
+ *   max_hits, max_queries   the maxima of the two per-position columns over the region
+ *   peak          the lowest forward position with queries == max_queries
+ *   e_min, query, bp_first / bp_last   the best hit over the region - the lowest (e_min, query id, place) of its positions
+ *                 -: its e_tot, its query's identifier and its end pairs as in prb_pair_summary
+ *   reserved      0 (the record has no uninitialised byte)
+ * Records come by page, then db_id, then start.
+ *   prb_covset_create         an empty table for db: a slot per character of every page's text, which holds a separator
+ *                             behind every sequence - one slot per base plus one per sequence -, 72 B each in HBM (64 B
+ *                             of columns and 8 B of scratch; 1e8 characters: 7.2 GB), plus 8 B per sequence.  PRB_ERR_NOMEM
+ *                             when that cannot be allocated; PRB_ERR_ARG for a database of 2^32 slots or more
+ *   prb_search_page_coverage  the search of prb_search_page_summary of qb against `page`, its final hits merged into the
+ *                             table on the device (nothing is copied to the host); query_ids[q] = the identifier of query
+ *                             q of qb.  Argument checks and option limits are those of prb_search_page_summary, the
+ *                             refusals those of prb_search_page_targets (PRB_ERR_ARG, the table untouched): a table made
+ *                             with another context or for another database; an identifier below 0, given twice in the
+ *                             call, or already merged for this page; opts->distinct_sites other than that of the pages
+ *                             merged so far.  A merge that fails part way leaves the table unusable.
+ *   prb_covset_add_hits       the same merge for a caller's list of final hits of one page in host memory: prb_hit
+ *                             records with their pair array as prb_hitset_hits / prb_hitset_basepairs or a `ris -b` file
+ *                             hold them, ascending by `query` (0 <= query < nq), every hit with at least one pair (the
+ *                             first and the last are its ends); query_ids[nq] as above.  Stage counts are not touched.
+ *                             The refusals of prb_search_page_coverage but for the options; n = 0 only marks the
+ *                             identifiers as merged
+ *   prb_covset_merge          two unfinished tables into one, on the device, with the contract of prb_targetset_merge:
+ *                             the difference and start arrays add, the best hit is the lower (e_min, query id, place); src
+ *                             may live on another device (a peer copy, else through pinned host memory); both were made
+ *                             for the same database (the handles may differ), hold the same distinct_sites unless one is
+ *                             empty, and no (query id, page) is merged into both: anything else returns PRB_ERR_ARG and
+ *                             leaves both tables as they were.  src is left empty but valid
+ *   prb_covset_finish         1 <= min_queries <= 1000000: the scans of the difference arrays, the regions' first
+ *                             positions and the reduction of every region to its record, all on the device; one copy to
+ *                             the host, and the device memory is released.  Nothing can be merged after it (a second call
+ *                             does nothing, whatever its min_queries)
+ *   prb_covset_counts         the stage counts of prb_pairset_counts, summed over the merged searches
+ * The device time of all this is the stage "coverage" of prb_ctx_stage_ms. */
+typedef struct prb_target_region {
+  int32_t page, db_id;
+  int32_t start, end;
+  int64_t hits, max_hits;
+  int32_t max_queries, peak;
+  double e_min;
+  int32_t query, reserved;
+  int32_t bp_first[2], bp_last[2]; /* the best hit's (q, db) end pairs; db in the page's reversed text */
+} prb_target_region;
+#ifdef __cplusplus
+static_assert(sizeof(prb_target_region) == 72, "prb_target_region: no padding");
+#endif
+typedef struct prb_covset prb_covset;
+int prb_covset_create(prb_ctx *ctx, prb_db *db, prb_covset **out);
+int prb_search_page_coverage(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts,
+                             const int32_t *query_ids, prb_covset *cs);
+int prb_covset_add_hits(prb_ctx *ctx, prb_covset *cs, int32_t page, const int32_t *query_ids, int32_t nq, const prb_hit *hits,
+                        int64_t nhits, const int32_t *basepairs, int64_t npairs);
+int prb_covset_merge(prb_ctx *ctx, prb_covset *dst, prb_covset *src);
+int prb_covset_finish(prb_ctx *ctx, prb_covset *cs, int32_t min_queries);
+int64_t prb_covset_size(const prb_covset *cs);
+const prb_target_region *prb_covset_regions(const prb_covset *cs);
+void prb_covset_counts(const prb_covset *cs, int64_t counts[3]);
+void prb_covset_free(prb_covset *cs);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -495,6 +586,13 @@ int prb_write_target_lines(const prb_db *db, int32_t nq_total, const char *const
  * energy in the result lines' form, the last three fields those of the best hit's result line in the `-s 0` form. */
 int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                             const prb_profile_pos *rows, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
+/* The lines of `ris -c D`: regions[0, n) as prb_covset_regions returns them (by page, then db_id, then start), one line
+ * each in that order, numbered from id0 on:
+ *   Id,dbname,dblen,Start,End,Hits,MaxHits,MaxQueries,Peak,MinEnergy,qname,qlen,(q0-qN:db0-dbN)
+ * the energy and the best hit's base-pair field in the result lines' form.  qnames and qlen_unmasked are indexed by the
+ * query's identifier (nq_total of them: every `query` lies below it). */
+int prb_write_region_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                           const prb_target_region *regions, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

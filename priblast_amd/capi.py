@@ -64,6 +64,12 @@ PROFILE_DTYPE = np.dtype([("query", "<i4"), ("pos", "<i4"), ("hits", "<i8"), ("t
                           ("bp_last", "<i4", (2,))])
 assert PROFILE_DTYPE.itemsize == 56
 
+# prb_target_region: one region of a target covered by at least D queries (`ris -c D`)
+REGION_DTYPE = np.dtype([("page", "<i4"), ("db_id", "<i4"), ("start", "<i4"), ("end", "<i4"), ("hits", "<i8"),
+                         ("max_hits", "<i8"), ("max_queries", "<i4"), ("peak", "<i4"), ("e_min", "<f8"), ("query", "<i4"),
+                         ("reserved", "<i4"), ("bp_first", "<i4", (2,)), ("bp_last", "<i4", (2,))])
+assert REGION_DTYPE.itemsize == 72
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -155,6 +161,17 @@ SYMBOLS = {
     "prb_targetset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_targetset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_targetset_free": (None, [ctypes.c_void_p]),
+    "prb_covset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
+    "prb_search_page_coverage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "prb_covset_add_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64,
+                                           ctypes.c_void_p, c_i64]),
+    "prb_covset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_covset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32]),
+    "prb_covset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_covset_regions": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_covset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_covset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -172,6 +189,8 @@ SYMBOLS = {
                                               c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_profile_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                                c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_region_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                              c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
 }
 
 _lib = None
@@ -648,6 +667,73 @@ def search_targets(ctx, db, n, batches, opts=None, pages=None, with_counts=False
     return (recs, counts) if with_counts else recs
 
 
+class CovSet:
+    """prb_covset: the per-position coverage of every target (page, db_id) of one database, in a table on the device that
+    any number of batches - or of hit lists - is merged into, page by page; every batch names its queries by identifiers
+    of the caller's."""
+
+    def __init__(self, ctx, db):
+        h = ctypes.c_void_p()
+        _check(lib().prb_covset_create(ctx.h, db.h, ctypes.byref(h)))
+        self.h, self.ctx, self.db = h, ctx, db
+
+    def merge(self, qb, page, ids, opts=None, db=None):
+        """prb_search_page_coverage: searches the batch against `page` and merges its final hits into the table;
+        ids[q] = the identifier of query q of the batch"""
+        o = opts or default_opts()
+        ids = np.ascontiguousarray(ids, np.int32)
+        assert len(ids) == len(qb.lens)
+        _check(lib().prb_search_page_coverage(self.ctx.h, qb.h, (db or self.db).h, page, ctypes.byref(o), ids.ctypes.data, self.h))
+
+    def add_hits(self, page, ids, hits, bp):
+        """prb_covset_add_hits: a list of final hits of `page` (HIT_DTYPE records ascending by `query`, with the int32 [n, 2]
+        pairs their bp_offset / bp_count index) merged into the table; ids[q] = the identifier of the list's query q"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        hits = np.ascontiguousarray(hits, HIT_DTYPE)
+        bp = np.ascontiguousarray(bp, np.int32)
+        _check(lib().prb_covset_add_hits(self.ctx.h, self.h, page, ids.ctypes.data if len(ids) else None, len(ids),
+                                         hits.ctypes.data if len(hits) else None, len(hits), bp.ctypes.data if bp.size else None,
+                                         bp.size // 2))
+
+    def absorb(self, other):
+        """prb_covset_merge: the unfinished table `other` (over other (identifier, page) sets; of any context) merged into
+        this one on the device; `other` is left empty"""
+        _check(lib().prb_covset_merge(self.ctx.h, self.h, other.h))
+
+    def finish(self, d):
+        """prb_covset_finish -> structured array REGION_DTYPE (a copy): the regions of depth d by page, db_id and start"""
+        _check(lib().prb_covset_finish(self.ctx.h, self.h, d))
+        return _records(lib().prb_covset_regions(self.h), lib().prb_covset_size(self.h), REGION_DTYPE)
+
+    def counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_covset_counts(self.h, c)
+        return tuple(c)
+
+    def close(self):
+        if self.h:
+            lib().prb_covset_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_coverage(ctx, db, d, batches, opts=None, pages=None, with_counts=False):
+    """The regions of every target that at least d queries bind, over batches = [(QBatch, ids)], every batch against the
+    pages (all of them, in this order, by default) -> structured array REGION_DTYPE, by page, db_id and start.
+    with_counts: -> (records, (seed, ungapped, final) counts summed over the calls)."""
+    with CovSet(ctx, db) as cs:
+        for qb, ids in batches:
+            for p in range(db.npages) if pages is None else pages:
+                cs.merge(qb, p, ids, opts)
+        recs, counts = cs.finish(d), cs.counts()
+    return (recs, counts) if with_counts else recs
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -741,3 +827,10 @@ def write_profile_lines(db, qnames, qlen_unmasked, rows, id0=0, fd=-1):
     (-1: formatted and counted only)."""
     rows = np.ascontiguousarray(rows, PROFILE_DTYPE)
     return _write(lib().prb_write_profile_lines, db, qnames, qlen_unmasked, rows.ctypes.data if len(rows) else None, len(rows), id0, fd)
+
+
+def write_region_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
+    """Lines of `ris -c D`: recs as search_coverage returns them; qnames / qlen_unmasked indexed by query identifier.
+    -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, REGION_DTYPE)
+    return _write(lib().prb_write_region_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)

@@ -8,7 +8,7 @@
 using namespace prb;
 
 namespace {
-// The body the five writers share.  `View` is the formatter's view of a batch (output.hpp); `kind_ok` = the checks of
+// The body the six writers share.  `View` is the formatter's view of a batch (output.hpp); `kind_ok` = the checks of
 // the arguments only this kind has; `fill(v)` checks the records and puts them into the view (it sets the error text
 // and returns the code when one is inconsistent); `format(v, sink)` is the formatter's call, returning the next id or -1.
 template <class View, class Fill, class Format>
@@ -149,6 +149,24 @@ int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qna
         return (int)PRB_OK;
       },
       [&](const ProfileView &v, LineSink &sink) { return format_profile_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
+int prb_write_region_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                           const prb_target_region *regions, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<RegionView>(
+      "prb_write_region_lines", n >= 0 && (!n || regions), db, nq_total, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](RegionView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_target_region &x = regions[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.query < 0 || x.query >= nq_total || x.db_id < 0 ||
+              x.db_id >= db->pages[(size_t)x.page].nseq || x.start < 0 || x.end < x.start || x.hits < 0 || x.max_hits < 1 || x.max_queries < 1)
+            return bad_record("prb_write_region_lines: region record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = regions;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const RegionView &v, LineSink &sink) { return format_region_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
 } // extern "C"

@@ -115,6 +115,7 @@ struct PageSearch {
   prb_profset *prof; // kProfile
   prb_tophits *tophits; // kTopHits
   prb_targetset *targets; // kTargets
+  prb_covset *cov;   // kCoverage
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
@@ -1479,6 +1480,55 @@ static int emit_targets(SubSearch &s) {
   return ctx->time_end(ctx->targets_timer, 5);
 }
 
+// What prb_search_page_coverage and prb_covset_add_hits share: the list by (query, first position of the span) - a
+// sequence's positions are contiguous in the page's text, so that is by (query, target, first position) -, the running
+// maximum of the spans' ends per query, the difference arrays, and the four passes of the best hits.  In the bracket of
+// the "coverage" timer.
+int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq) {
+  const size_t NF = (size_t)h.n;
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  if ((rc = cs->keyA.ensure(NF * 8)) || (rc = cs->keyB.ensure(NF * 8)) || (rc = cs->valA.ensure(NF * 4)) || (rc = cs->valB.ensure(NF * 4)) ||
+      (rc = cs->place.ensure(NF * 4)) || (rc = cs->span.ensure(NF * 8)) || (rc = cs->scan.ensure(NF * 8)))
+    return rc;
+  const CovTab t = cs->view();
+  const CovPage pg = cs->page_view((size_t)page);
+  uint64_t *kA = cs->keyA.as<uint64_t>(), *kB = cs->keyB.as<uint64_t>(), *span = cs->span.as<uint64_t>(), *run_max = cs->scan.as<uint64_t>();
+  uint32_t *vA = cs->valA.as<uint32_t>(), *vB = cs->valB.as<uint32_t>(), *place = cs->place.as<uint32_t>();
+  const int bits = 32 + bits_for(std::max(nq - 1, 1)); // the position, and above it the query
+  auto sort_by_query = [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, kA, kB, vA, vB, NF, 0, bits, ctx->stream); };
+  auto scan_spans = [&](void *tmp, size_t &bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, span, run_max, NF, rocprim::maximum<uint64_t>(), ctx->stream);
+  };
+  // (the two share cs->sortTmp: both are sized before anything is enqueued)
+  size_t tmp_sort = 0, tmp_scan = 0;
+  PRB_HIP(sort_by_query(nullptr, tmp_sort));
+  PRB_HIP(scan_spans(nullptr, tmp_scan));
+  if ((rc = cs->sortTmp.ensure(std::max<size_t>({tmp_sort, tmp_scan, 1})))) return rc;
+  PRB_HIP(launch_cov_keys(h, t, pg, kA, vA, place, ctx->stream));
+  PRB_HIP(sort_by_query(cs->sortTmp.p, tmp_sort));
+  PRB_HIP(launch_cov_span(h, kB, vB, t, pg, span, ctx->stream));
+  PRB_HIP(scan_spans(cs->sortTmp.p, tmp_scan));
+  PRB_HIP(launch_cov_add(h, kB, vB, run_max, t, pg, ctx->stream));
+  PRB_HIP(launch_cov_min(h, vB, place, cs->ids.as<int32_t>(), t, pg, ctx->stream));
+  return ctx->time_end(ctx->coverage_timer, 9);
+}
+
+// prb_search_page_coverage: the hits merged into the per-target coverage table on the device; nothing leaves it.  Closes
+// the "traceback" bracket.
+static int emit_coverage(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  const int64_t nfin = s.nfin;
+  int rc;
+  if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
+  PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+  if ((rc = ctx->time_end("traceback", 2))) return rc;
+  if ((rc = merge_coverage(ctx, s.cov, s.page, CovHits{nfin, s.F.query, s.F.db_id, s.F.e_tot, w.bpEnds.as<int32_t>()}, s.qb->nq))) return rc;
+  s.hs->hits_total += nfin;
+  return PRB_OK;
+}
+
 static int emit_final(SubSearch &s) {
   switch (s.mode) {
   case SearchMode::kRecords: return emit_records(s);
@@ -1487,6 +1537,7 @@ static int emit_final(SubSearch &s) {
   case SearchMode::kProfile: return emit_profile(s);
   case SearchMode::kTopHits: return emit_tophits(s);
   case SearchMode::kTargets: return emit_targets(s);
+  case SearchMode::kCoverage: return emit_coverage(s);
   }
   return PRB_ERR_STATE;
 }
@@ -1682,6 +1733,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
                 mode == SearchMode::kProfile ? static_cast<prb_profset *>(table) : nullptr,
                 mode == SearchMode::kTopHits ? static_cast<prb_tophits *>(table) : nullptr,
                 mode == SearchMode::kTargets ? static_cast<prb_targetset *>(table) : nullptr,
+                mode == SearchMode::kCoverage ? static_cast<prb_covset *>(table) : nullptr,
                 hs,
                 0,
                 0};

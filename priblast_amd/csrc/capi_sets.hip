@@ -1,8 +1,9 @@
 // C ABI, part 4: the tables and record sets a search fills - the top-N table (prb_topset_*), the top-N hit table
-// (prb_tophits_*), the per-position profile (prb_profset_*), the per-target table (prb_targetset_*), per-pair records
-// (prb_pairset_*), hit sets (prb_hitset_*).
+// (prb_tophits_*), the per-position profile (prb_profset_*), the per-target table (prb_targetset_*), the per-target
+// coverage table (prb_covset_*), per-pair records (prb_pairset_*), hit sets (prb_hitset_*).
 #include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "search_host.hpp"
 
@@ -17,6 +18,13 @@ struct ProfCovered {
 // a fill count as what the scan of prb_targetset_finish adds up
 struct FillToI64 {
   __host__ __device__ int64_t operator()(const int32_t &x) const { return (int64_t)x; }
+};
+// the first slot of a region of the coverage table at depth D (prb_covset_finish: `queries` holds the scanned counts; a
+// sequence's separator slot has none, so the slot in front of a sequence's first one is always below D)
+struct CovHead {
+  const int32_t *queries;
+  int32_t D;
+  __host__ __device__ bool operator()(const uint32_t &p) const { return queries[p] >= D && (p == 0 || queries[p - 1] < D); }
 };
 // the caller's current device, put back on every way out of a call that visits another table's device
 struct DeviceScope {
@@ -585,41 +593,59 @@ int prb_targetset_create(prb_ctx *ctx, prb_db *db, int32_t n, prb_targetset **ou
   return PRB_OK;
 }
 
-// Every check comes before the table is touched: a refused call leaves it as it was.
-int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
-                            prb_targetset *ts) {
-  const std::string fn = "prb_search_page_targets";
+// prb_search_page_targets / prb_search_page_coverage / prb_covset_add_hits: what is checked of the run table `t` - `what`
+// in the messages, finished by `finish_fn` - before a batch of nq queries named query_ids is merged into it for `page`
+// (distinct < 0: the call has no options).  Every check comes before the table is touched: a refused call leaves it as
+// it was; a call that passes has its identifiers marked as merged.
+static int run_table_guard(const std::string &fn, const char *what, const char *finish_fn, RunTable *t, const prb_ctx *ctx, const prb_db *db,
+                           int32_t page, int32_t distinct, const int32_t *query_ids, int32_t nq) {
+  const std::string table = std::string(what) + " table";
   auto refuse = [&](const std::string &why, int code = PRB_ERR_ARG) {
     set_error(fn + ": " + why);
     return code;
   };
-  if (!ts || !query_ids) return refuse("bad argument");
-  if (int rc = check_search_args(fn.c_str(), ctx, qb, db, page, opts, 3)) return rc;
-  if (ts->ctx != ctx || ts->db != db) return refuse("the per-target table was made with another context or for another database");
-  if (ts->broken) return refuse("an earlier merge into this per-target table failed", PRB_ERR_STATE);
-  if (ts->finished) return refuse("the per-target table is finished (prb_targetset_finish)", PRB_ERR_STATE);
-  if (ts->distinct >= 0 && opts->distinct_sites != ts->distinct)
-    return refuse("the per-target table holds pages searched with distinct_sites " + std::to_string(ts->distinct) + " (this call: " +
-                  std::to_string(opts->distinct_sites) + ")");
+  if (t->ctx != ctx || t->db != db) return refuse("the " + table + " was made with another context or for another database");
+  if (t->broken) return refuse("an earlier merge into this " + table + " failed", PRB_ERR_STATE);
+  if (t->finished) return refuse("the " + table + " is finished (" + finish_fn + ")", PRB_ERR_STATE);
+  if (t->distinct >= 0 && distinct >= 0 && distinct != t->distinct)
+    return refuse("the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
+                  std::to_string(distinct) + ")");
   try {
-    std::vector<int32_t> sorted(query_ids, query_ids + qb->nq);
+    std::vector<int32_t> sorted(query_ids, query_ids + nq);
     std::sort(sorted.begin(), sorted.end());
     for (size_t i = 0; i < sorted.size(); i++) {
       if (sorted[i] < 0) return refuse("query identifier " + std::to_string(sorted[i]) + " is below 0");
       if (i && sorted[i] == sorted[i - 1]) return refuse("query identifier " + std::to_string(sorted[i]) + " is given twice");
-      if (ts->has((size_t)page, sorted[i]))
+      if (t->has((size_t)page, sorted[i]))
         return refuse("query identifier " + std::to_string(sorted[i]) + " is already merged for page " + std::to_string(page));
     }
-    for (int32_t id : sorted) ts->set((size_t)page, id);
+    for (int32_t id : sorted) t->set((size_t)page, id);
   } catch (const std::exception &e) {
     return refuse(e.what(), PRB_ERR_NOMEM);
   }
+  return PRB_OK;
+}
+// the identifiers of the batch being merged into t, on the device (the current one)
+static int upload_ids(prb_ctx *ctx, RunTable *t, const int32_t *query_ids, int32_t nq) {
+  if (int rc = t->ids.ensure(std::max<size_t>((size_t)nq * 4, 4))) return rc;
+  PRB_HIP(hipMemcpyAsync(t->ids.p, query_ids, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  return PRB_OK;
+}
+
+int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
+                            prb_targetset *ts) {
+  const std::string fn = "prb_search_page_targets";
+  if (!ts || !query_ids) {
+    set_error(fn + ": bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (int rc = check_search_args(fn.c_str(), ctx, qb, db, page, opts, 3)) return rc;
+  if (int rc = run_table_guard(fn, "per-target", "prb_targetset_finish", ts, ctx, db, page, opts->distinct_sites, query_ids, qb->nq)) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
   ts->broken = true; // (until the merge is whole)
   int rc;
-  if ((rc = ts->ids.ensure(std::max<size_t>((size_t)qb->nq * 4, 4)))) return rc;
-  PRB_HIP(hipMemcpyAsync(ts->ids.p, query_ids, (size_t)qb->nq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  if ((rc = upload_ids(ctx, ts, query_ids, qb->nq))) return rc;
   prb_hitset *hs = nullptr;
   if ((rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kTargets, &hs, ts))) return rc;
   for (int i = 0; i < 3; i++) ts->counts[i] += hs->counts[i];
@@ -629,25 +655,61 @@ int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
   return PRB_OK;
 }
 
-int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
+// prb_targetset_merge / prb_covset_merge: what is checked before either run table - `what` in the messages - is touched;
+// `more` (may be empty) = a refusal of the caller's own, or "", asked once both are known to be whole and unfinished
+static int run_tables_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const RunTable *dst, const RunTable *src,
+                            const std::function<std::string()> &more) {
+  const std::string tables = std::string(what) + " tables";
   auto refuse = [&](const std::string &why) {
-    set_error("prb_targetset_merge: " + why);
+    set_error(std::string(fn_name) + ": " + why);
     return PRB_ERR_ARG;
   };
   if (!ctx || !dst || !src || dst == src) return refuse("bad argument");
   if (dst->ctx != ctx) return refuse("the table to merge into belongs to another context");
-  if (dst->broken || src->broken) return refuse("an earlier merge into one of the per-target tables failed");
-  if (dst->finished || src->finished) return refuse("one of the per-target tables is finished");
-  if (dst->n != src->n) return refuse("the per-target tables keep " + std::to_string(dst->n) + " and " + std::to_string(src->n) + " records per target");
-  if (dst->tbase != src->tbase) return refuse("the per-target tables were made for different databases");
+  if (dst->broken || src->broken) return refuse("an earlier merge into one of the " + tables + " failed");
+  if (dst->finished || src->finished) return refuse("one of the " + tables + " is finished");
+  if (more)
+    if (const std::string why = more(); !why.empty()) return refuse(why);
+  if (dst->tbase != src->tbase) return refuse("the " + tables + " were made for different databases");
   if (dst->distinct >= 0 && src->distinct >= 0 && dst->distinct != src->distinct)
-    return refuse("the per-target tables hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
+    return refuse("the " + tables + " hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
                   std::to_string(src->distinct));
   for (size_t p = 0; p < dst->merged.size(); p++) {
     const std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
     for (size_t k = 0; k < std::min(a.size(), b.size()); k++)
-      if (a[k] & b[k]) return refuse("a query identifier is merged for page " + std::to_string(p) + " into both per-target tables");
+      if (a[k] & b[k]) return refuse("a query identifier is merged for page " + std::to_string(p) + " into both " + tables);
   }
+  return PRB_OK;
+}
+// after the merge: dst's identifier sets are the unions and its counts the sums; src has merged nothing
+static int move_ids(const char *fn_name, RunTable *dst, RunTable *src) {
+  try {
+    for (size_t p = 0; p < dst->merged.size(); p++) {
+      std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
+      if (a.size() < b.size()) a.resize(b.size(), 0);
+      for (size_t k = 0; k < b.size(); k++) a[k] |= b[k];
+      b.clear();
+    }
+  } catch (const std::exception &e) {
+    dst->broken = true;
+    set_error(std::string(fn_name) + ": " + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  for (int i = 0; i < 3; i++) {
+    dst->counts[i] += src->counts[i];
+    src->counts[i] = 0;
+  }
+  if (dst->distinct < 0) dst->distinct = src->distinct;
+  src->distinct = -1;
+  return PRB_OK;
+}
+
+int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
+  if (int rc = run_tables_guard("prb_targetset_merge", "per-target", ctx, dst, src, [&]() -> std::string {
+        if (dst->n == src->n) return "";
+        return "the per-target tables keep " + std::to_string(dst->n) + " and " + std::to_string(src->n) + " records per target";
+      }))
+    return rc;
   DeviceScope restore;
   ScratchBuf copy;
   PRB_HIP(hipSetDevice(ctx->device));
@@ -660,24 +722,7 @@ int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
                              dst->slots_of(block), dst->fill_of(block), dst->targets(), dst->n, ctx->stream));
   if ((rc = ctx->time_end(ctx->targets_timer, 1))) return rc; // (synchronises: src is read no more)
   dst->broken = false;
-  try {
-    for (size_t p = 0; p < dst->merged.size(); p++) {
-      std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
-      if (a.size() < b.size()) a.resize(b.size(), 0);
-      for (size_t k = 0; k < b.size(); k++) a[k] |= b[k];
-      b.clear();
-    }
-  } catch (const std::exception &e) {
-    dst->broken = true;
-    set_error(std::string("prb_targetset_merge: ") + e.what());
-    return PRB_ERR_NOMEM;
-  }
-  for (int i = 0; i < 3; i++) {
-    dst->counts[i] += src->counts[i];
-    src->counts[i] = 0;
-  }
-  if (dst->distinct < 0) dst->distinct = src->distinct;
-  src->distinct = -1;
+  if ((rc = move_ids("prb_targetset_merge", dst, src))) return rc;
   return clear_target_table(*src);
 }
 
@@ -736,6 +781,257 @@ void prb_targetset_counts(const prb_targetset *ts, int64_t counts[3]) {
 }
 void prb_targetset_free(prb_targetset *ts) {
   delete ts;
+}
+
+// ---- the per-target coverage table (prb_covset_*) ----
+// every slot of the table back to "no hit", on its own device and stream; its stream is idle on return
+static int clear_coverage_table(prb_covset &cs) {
+  hipStream_t stream = cs.ctx->stream;
+  const size_t P = (size_t)cs.slots();
+  const prb::CovTab t = cs.view();
+  PRB_HIP(hipSetDevice(cs.ctx->device));
+  PRB_HIP(hipMemsetAsync(cs.table.p, 0, cs.bytes(), stream));
+  if (P) PRB_HIP(hipMemsetAsync(t.key, 0xFF, 4 * P * 8, stream)); // key, tie, skey, stie: none yet
+  PRB_HIP(hipMemcpyAsync(cs.table.p, cs.seq_lo.data(), cs.seq_lo.size() * 8, hipMemcpyHostToDevice, stream));
+  PRB_HIP(hipMemcpyAsync(cs.table.as<int64_t>() + cs.seq_lo.size(), cs.tbase.data(), cs.tbase.size() * 8, hipMemcpyHostToDevice, stream));
+  PRB_HIP(hipStreamSynchronize(stream));
+  return PRB_OK;
+}
+
+int prb_covset_create(prb_ctx *ctx, prb_db *db, prb_covset **out) {
+  if (!ctx || !db || !out || db->ctx->device != ctx->device) {
+    set_error("prb_covset_create: bad argument");
+    return PRB_ERR_ARG;
+  }
+  *out = nullptr;
+  std::unique_ptr<prb_covset> cs(new (std::nothrow) prb_covset());
+  if (!cs) {
+    set_error("prb_covset_create: out of host memory");
+    return PRB_ERR_NOMEM;
+  }
+  cs->ctx = ctx;
+  cs->db = db;
+  try {
+    cs->tbase.assign(db->pages.size() + 1, 0);
+    cs->slot0.assign(db->pages.size() + 1, 0);
+    for (size_t p = 0; p < db->pages.size(); p++) {
+      const DbPage &pg = db->pages[p];
+      cs->tbase[p + 1] = cs->tbase[p] + pg.nseq;
+      for (int32_t i = 0; i < pg.nseq; i++) cs->seq_lo.push_back(cs->slot0[p] + pg.start_pos[(size_t)i]);
+      cs->slot0[p + 1] = cs->slot0[p] + (int64_t)pg.seqs.size(); // (the text: every sequence and the separator behind it)
+    }
+    cs->seq_lo.push_back(cs->slot0.back());
+    cs->merged.resize(db->pages.size());
+  } catch (const std::exception &e) {
+    set_error(std::string("prb_covset_create: ") + e.what());
+    return PRB_ERR_NOMEM;
+  }
+  if (cs->slots() > (int64_t)UINT32_MAX) {
+    set_error("prb_covset_create: the database has " + std::to_string(cs->slots()) + " positions (at most 2^32 - 1)");
+    return PRB_ERR_ARG;
+  }
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (cs->table.ensure(cs->bytes()) != PRB_OK) {
+    set_error("prb_covset_create: can't allocate the coverage table (" + std::to_string(cs->bytes() >> 20) + " MB of HBM for " +
+              std::to_string(cs->slots()) + " positions of " + std::to_string(cs->targets()) + " targets)");
+    return PRB_ERR_NOMEM;
+  }
+  if (int rc = clear_coverage_table(*cs)) return rc;
+  *out = cs.release();
+  return PRB_OK;
+}
+
+int prb_search_page_coverage(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
+                             prb_covset *cs) {
+  const std::string fn = "prb_search_page_coverage";
+  if (!cs || !query_ids) {
+    set_error(fn + ": bad argument");
+    return PRB_ERR_ARG;
+  }
+  if (int rc = check_search_args(fn.c_str(), ctx, qb, db, page, opts, 3)) return rc;
+  if (int rc = run_table_guard(fn, "coverage", "prb_covset_finish", cs, ctx, db, page, opts->distinct_sites, query_ids, qb->nq)) return rc;
+  PRB_HIP(hipSetDevice(ctx->device));
+  cs->broken = true; // (until the merge is whole)
+  int rc;
+  if ((rc = upload_ids(ctx, cs, query_ids, qb->nq))) return rc;
+  prb_hitset *hs = nullptr;
+  if ((rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kCoverage, &hs, cs))) return rc;
+  for (int i = 0; i < 3; i++) cs->counts[i] += hs->counts[i];
+  cs->distinct = opts->distinct_sites;
+  cs->broken = false;
+  delete hs;
+  return PRB_OK;
+}
+
+// the caller's list checked on the host - a refused call leaves the table as it was -, then as columns to the device and
+// through the merge of a sub-batch
+int prb_covset_add_hits(prb_ctx *ctx, prb_covset *cs, int32_t page, const int32_t *query_ids, int32_t nq, const prb_hit *hits, int64_t nhits,
+                        const int32_t *basepairs, int64_t npairs) {
+  const std::string fn = "prb_covset_add_hits";
+  auto refuse = [&](const std::string &why, int code = PRB_ERR_ARG) {
+    set_error(fn + ": " + why);
+    return code;
+  };
+  if (!ctx || !cs || nq < 0 || (nq && !query_ids) || nhits < 0 || nhits > INT32_MAX || npairs < 0 || (nhits && (!hits || !basepairs)))
+    return refuse("bad argument");
+  if (page < 0 || (size_t)page >= cs->merged.size()) return refuse("page " + std::to_string(page) + " out of range");
+  const prb::CovPage pg = cs->page_view((size_t)page);
+  std::vector<int32_t> query, db_id, ends;
+  std::vector<double> e_tot;
+  try {
+    query.resize((size_t)nhits);
+    db_id.resize((size_t)nhits);
+    e_tot.resize((size_t)nhits);
+    ends.resize((size_t)nhits * 4);
+  } catch (const std::exception &e) {
+    return refuse(e.what(), PRB_ERR_NOMEM);
+  }
+  for (int64_t i = 0; i < nhits; i++) {
+    const prb_hit &x = hits[i];
+    if (x.query < 0 || x.query >= nq || (i && x.query < hits[i - 1].query) || x.db_id < 0 || x.db_id >= pg.nseq || x.bp_count < 1 ||
+        x.bp_offset < 0 || x.bp_offset + x.bp_count > npairs)
+      return refuse("hit record " + std::to_string(i) + " is inconsistent");
+    const int32_t *first = basepairs + 2 * x.bp_offset, *last = basepairs + 2 * (x.bp_offset + x.bp_count - 1);
+    const int64_t lo = std::min(first[1], last[1]), hi = std::max(first[1], last[1]);
+    const int64_t s0 = cs->seq_lo[(size_t)(pg.target0 + x.db_id)] - pg.slot0, sep = cs->seq_lo[(size_t)(pg.target0 + x.db_id) + 1] - pg.slot0 - 1;
+    if (lo < s0 || hi >= sep) return refuse("the span of hit record " + std::to_string(i) + " leaves its sequence", PRB_ERR_STATE);
+    query[(size_t)i] = x.query;
+    db_id[(size_t)i] = x.db_id;
+    e_tot[(size_t)i] = x.e_tot;
+    ends[4 * (size_t)i] = first[0], ends[4 * (size_t)i + 1] = first[1], ends[4 * (size_t)i + 2] = last[0], ends[4 * (size_t)i + 3] = last[1];
+  }
+  if (int rc = run_table_guard(fn, "coverage", "prb_covset_finish", cs, ctx, cs->db, page, -1, query_ids, nq)) return rc;
+  if (!nhits) return PRB_OK;
+  DeviceScope restore;
+  PRB_HIP(hipSetDevice(ctx->device));
+  cs->broken = true; // (until the merge is whole)
+  int rc;
+  const size_t N = (size_t)nhits;
+  if ((rc = upload_ids(ctx, cs, query_ids, nq))) return rc;
+  if ((rc = cs->h_query.ensure(N * 4)) || (rc = cs->h_db_id.ensure(N * 4)) || (rc = cs->h_e_tot.ensure(N * 8)) || (rc = cs->h_ends.ensure(N * 16)))
+    return rc;
+  PRB_HIP(hipMemcpyAsync(cs->h_query.p, query.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(cs->h_db_id.p, db_id.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(cs->h_e_tot.p, e_tot.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(cs->h_ends.p, ends.data(), N * 16, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the vectors go)
+  if ((rc = merge_coverage(ctx, cs, page, prb::CovHits{nhits, cs->h_query.as<int32_t>(), cs->h_db_id.as<int32_t>(), cs->h_e_tot.as<double>(),
+                                                      cs->h_ends.as<int32_t>()},
+                           nq)))
+    return rc;
+  cs->broken = false;
+  return PRB_OK;
+}
+
+int prb_covset_merge(prb_ctx *ctx, prb_covset *dst, prb_covset *src) {
+  if (int rc = run_tables_guard("prb_covset_merge", "coverage", ctx, dst, src, [&]() -> std::string {
+        return dst->seq_lo == src->seq_lo ? "" : "the coverage tables were made for different databases";
+      }))
+    return rc;
+  DeviceScope restore;
+  ScratchBuf copy;
+  PRB_HIP(hipSetDevice(ctx->device));
+  void *block = nullptr;
+  int rc;
+  if ((rc = on_device_of(ctx, src->ctx, src->table.p, src->bytes(), copy, &block))) return rc;
+  dst->broken = true; // (until the merge is whole)
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_cov_join(dst->view(), dst->view_of(static_cast<char *>(block)), dst->slots(), ctx->stream));
+  if ((rc = ctx->time_end(ctx->coverage_timer, 1))) return rc; // (synchronises: src is read no more)
+  dst->broken = false;
+  if ((rc = move_ids("prb_covset_merge", dst, src))) return rc;
+  return clear_coverage_table(*src);
+}
+
+// the counts scanned into the scratch columns, the regions' first slots selected, a wavefront per region, one copy
+int prb_covset_finish(prb_ctx *ctx, prb_covset *cs, int32_t min_queries) {
+  if (!ctx || !cs || cs->ctx != ctx) {
+    set_error("prb_covset_finish: bad argument (the table belongs to another context)");
+    return PRB_ERR_ARG;
+  }
+  if (cs->broken) {
+    set_error("prb_covset_finish: an earlier merge into this coverage table failed");
+    return PRB_ERR_STATE;
+  }
+  if (cs->finished) return PRB_OK; // (the records are on the host already)
+  if (min_queries < 1 || min_queries > 1000000) {
+    set_error("prb_covset_finish: need 1 <= min_queries <= 1000000 (got " + std::to_string(min_queries) + ")");
+    return PRB_ERR_ARG;
+  }
+  const size_t P = (size_t)cs->slots();
+  cs->regions.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (P > 0) {
+    int rc;
+    if ((rc = ctx->time_begin())) return rc;
+    const prb::CovTab t = cs->view();
+    // the scratch is free once everything is merged: hits into skey's slots, queries into the first half of stie's, the
+    // regions' first slots (at most one for two slots) into the second half
+    int64_t *hits = reinterpret_cast<int64_t *>(t.skey);
+    int32_t *queries = reinterpret_cast<int32_t *>(t.stie);
+    uint32_t *first = reinterpret_cast<uint32_t *>(t.stie) + P;
+    if ((rc = cs->keyA.ensure(16))) return rc;
+    // (the three share cs->sortTmp: all are sized before the first is enqueued)
+    const CovHead head{queries, min_queries};
+    auto scan_hits = [&](void *tmp, size_t &bytes) {
+      return rocprim::inclusive_scan(tmp, bytes, reinterpret_cast<const int64_t *>(t.hdiff), hits, P, rocprim::plus<int64_t>(), ctx->stream);
+    };
+    auto scan_queries = [&](void *tmp, size_t &bytes) {
+      return rocprim::inclusive_scan(tmp, bytes, t.qdiff, queries, P, rocprim::plus<int32_t>(), ctx->stream);
+    };
+    auto select_heads = [&](void *tmp, size_t &bytes) {
+      return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint32_t>(0), first, cs->keyA.as<size_t>(), P, head, ctx->stream);
+    };
+    size_t tmp_h = 0, tmp_q = 0, tmp_s = 0;
+    PRB_HIP(scan_hits(nullptr, tmp_h));
+    PRB_HIP(scan_queries(nullptr, tmp_q));
+    PRB_HIP(select_heads(nullptr, tmp_s));
+    if ((rc = cs->sortTmp.ensure(std::max<size_t>({tmp_h, tmp_q, tmp_s, 1})))) return rc;
+    PRB_HIP(scan_hits(cs->sortTmp.p, tmp_h));
+    PRB_HIP(scan_queries(cs->sortTmp.p, tmp_q));
+    PRB_HIP(select_heads(cs->sortTmp.p, tmp_s));
+    size_t nreg = 0;
+    uint32_t bad = 0;
+    PRB_HIP(hipMemcpyAsync(&nreg, cs->keyA.p, sizeof nreg, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipMemcpyAsync(&bad, t.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (bad || nreg > (P + 1) / 2) {
+      set_error("prb_covset_finish: " + std::string(bad ? "a final hit's span leaves its sequence" : "bad region count"));
+      return PRB_ERR_STATE;
+    }
+    if (nreg) {
+      try {
+        cs->regions.resize(nreg);
+      } catch (const std::exception &e) {
+        set_error(std::string("prb_covset_finish: ") + e.what());
+        return PRB_ERR_NOMEM;
+      }
+      if ((rc = cs->span.ensure(nreg * sizeof(prb_target_region)))) return rc;
+      PRB_HIP(launch_cov_regions(t, cs->tbase_dev(), (int32_t)cs->merged.size(), cs->targets(), first, (int64_t)nreg, hits, queries, min_queries,
+                                 cs->span.p, ctx->stream));
+      PRB_HIP(hipMemcpyAsync(cs->regions.data(), cs->span.p, nreg * sizeof(prb_target_region), hipMemcpyDeviceToHost, ctx->stream));
+      PRB_HIP(hipStreamSynchronize(ctx->stream));
+      // (the slots run along the page's text, which holds the sequences reversed: a target's regions arrive by start
+      // descending)
+      for (size_t i = 0, j; i < nreg; i = j) {
+        for (j = i + 1; j < nreg && cs->regions[j].page == cs->regions[i].page && cs->regions[j].db_id == cs->regions[i].db_id;) j++;
+        std::reverse(cs->regions.begin() + (ptrdiff_t)i, cs->regions.begin() + (ptrdiff_t)j);
+      }
+    }
+    if ((rc = ctx->time_end(ctx->coverage_timer, nreg ? 4 : 3))) return rc;
+  }
+  cs->finished = true;
+  cs->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_covset_size(const prb_covset *cs) { return cs ? (int64_t)cs->regions.size() : -1; }
+const prb_target_region *prb_covset_regions(const prb_covset *cs) { return cs ? cs->regions.data() : nullptr; }
+void prb_covset_counts(const prb_covset *cs, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = cs ? cs->counts[i] : 0;
+}
+void prb_covset_free(prb_covset *cs) {
+  delete cs;
 }
 
 int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }

@@ -435,31 +435,20 @@ struct prb_profset : prb::MergeTable {
   }
 };
 
-// prb_targetset_create .. prb_targetset_free: the per-target table of one database, merged into sub-batch by sub-batch
-// (emit_targets, capi_search.hip) for as many batches as the caller likes, and the sort buffers of those merges.  It is
-// keyed by (page, db_id), not by a batch's queries, so it shares nothing with MergeTable but the flags.
-struct prb_targetset {
+namespace prb {
+// What the tables that live for a whole run and are keyed by the database's targets (page, db_id) have in common
+// (prb_targetset, prb_covset), and what prb_search_page_targets / prb_search_page_coverage check before a merge.  Such a
+// table takes any number of batches, so it shares nothing with MergeTable but the flags.
+struct RunTable {
   prb_ctx *ctx = nullptr;
   const prb_db *db = nullptr;
-  int32_t n = 0;
   std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
   std::vector<std::vector<uint64_t>> merged;  // per page: a bit per query identifier merged, grown on demand
   bool broken = false, finished = false;
   int32_t distinct = -1;                      // opts->distinct_sites of the merged calls (-1: none yet)
   int64_t counts[3] = {0, 0, 0};
-  prb::DevBuf table;                          // TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
   prb::DevBuf ids;                            // the identifiers of the batch being merged
-  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
-  std::vector<prb_target_pair> pairs;         // prb_targetset_finish
   int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
-  size_t entries() const { return (size_t)targets() * (size_t)n; }
-  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)) + ((size_t)targets() + 1) * sizeof(int32_t); }
-  // the three arrays of a block at b (the table's own, or a copy of another table's)
-  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
-  prb_target_pair *slots_of(void *b) const { return reinterpret_cast<prb_target_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
-  int32_t *fill_of(void *b) const {
-    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)));
-  }
   bool has(size_t page, int32_t id) const {
     const std::vector<uint64_t> &m = merged[page];
     return ((size_t)id >> 6) < m.size() && (m[(size_t)id >> 6] >> (id & 63) & 1);
@@ -469,11 +458,77 @@ struct prb_targetset {
     if (((size_t)id >> 6) >= m.size()) m.resize(((size_t)id >> 6) + 1, 0);
     m[(size_t)id >> 6] |= 1ull << (id & 63);
   }
+};
+} // namespace prb
+
+// prb_targetset_create .. prb_targetset_free: the per-target table of one database, merged into sub-batch by sub-batch
+// (emit_targets, capi_search.hip) for as many batches as the caller likes, and the sort buffers of those merges.
+struct prb_targetset : prb::RunTable {
+  int32_t n = 0;
+  prb::DevBuf table;                          // TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
+  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
+  std::vector<prb_target_pair> pairs;         // prb_targetset_finish
+  size_t entries() const { return (size_t)targets() * (size_t)n; }
+  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)) + ((size_t)targets() + 1) * sizeof(int32_t); }
+  // the three arrays of a block at b (the table's own, or a copy of another table's)
+  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
+  prb_target_pair *slots_of(void *b) const { return reinterpret_cast<prb_target_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
+  int32_t *fill_of(void *b) const {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)));
+  }
   void release() {
     for (prb::DevBuf *b : {&table, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp}) b->release();
   }
   ~prb_targetset() { // (also on the error paths of prb_targetset_create)
     if (table.p || ids.p || key.p) (void)hipSetDevice(ctx->device);
+    release();
+  }
+};
+
+// prb_covset_create .. prb_covset_free: the per-position coverage table of one database, merged into sub-batch by
+// sub-batch (emit_coverage, capi_search.hip) or list by list (prb_covset_add_hits) for as many batches as the caller
+// likes, and the sort / scan buffers of those merges
+struct prb_covset : prb::RunTable {
+  std::vector<int64_t> seq_lo;  // [T + 1] the first slot of every target (CovTab::seq_lo); back() = the slots
+  std::vector<int64_t> slot0;   // [npages + 1] the first slot of every page
+  prb::DevBuf table;            // seq_lo, tbase, then CovTab's arrays, one block (view())
+  prb::DevBuf keyA, keyB, valA, valB, place, span, scan, sortTmp; // per merge: the hits in (query, first position) order
+  prb::DevBuf h_query, h_db_id, h_e_tot, h_ends;                  // prb_covset_add_hits: the caller's list as columns
+  std::vector<prb_target_region> regions; // prb_covset_finish
+  int64_t slots() const { return seq_lo.empty() ? 0 : seq_lo.back(); }
+  size_t head_bytes() const { return (seq_lo.size() + tbase.size()) * 8; }
+  // the block: seq_lo and tbase, then the 8-byte arrays hdiff, key, tie, skey, stie, e_min, then the 4-byte arrays qdiff,
+  // starts, bp (x4), bad
+  size_t bytes() const { return head_bytes() + 6 * (size_t)slots() * 8 + (6 * (size_t)slots() + 2) * 4; }
+  prb::CovTab view() const { return view_of(table.as<char>()); }
+  const int64_t *tbase_dev() const { return table.as<int64_t>() + seq_lo.size(); }
+  // the arrays of a block at b (the table's own, or a copy of another table's)
+  prb::CovTab view_of(char *b) const {
+    prb::CovTab t;
+    const size_t P = (size_t)slots();
+    t.seq_lo = reinterpret_cast<const int64_t *>(b);
+    b += head_bytes();
+    t.hdiff = reinterpret_cast<unsigned long long *>(b);
+    t.key = t.hdiff + P;
+    t.tie = t.key + P;
+    t.skey = t.tie + P;
+    t.stie = t.skey + P;
+    t.e_min = reinterpret_cast<double *>(t.stie + P);
+    t.qdiff = reinterpret_cast<int32_t *>(t.e_min + P);
+    t.starts = reinterpret_cast<uint32_t *>(t.qdiff + P);
+    t.bp = reinterpret_cast<int32_t *>(t.starts + P);
+    t.bad = reinterpret_cast<uint32_t *>(t.bp + 4 * P);
+    return t;
+  }
+  prb::CovPage page_view(size_t page) const {
+    return prb::CovPage{slot0[page], tbase[page], (int32_t)(tbase[page + 1] - tbase[page])};
+  }
+  void release() {
+    for (prb::DevBuf *b : {&table, &ids, &keyA, &keyB, &valA, &valB, &place, &span, &scan, &sortTmp, &h_query, &h_db_id, &h_e_tot, &h_ends})
+      b->release();
+  }
+  ~prb_covset() { // (also on the error paths of prb_covset_create)
+    if (table.p || ids.p || keyA.p || h_query.p) (void)hipSetDevice(ctx->device);
     release();
   }
 };
@@ -491,6 +546,7 @@ enum class SearchMode {
   kProfile, // prb_search_page_profile: the hits merged into the per-position table on the device
   kTopHits, // prb_search_page_tophits: the hits and their base pairs merged into the top-N hit table on the device
   kTargets, // prb_search_page_targets: per-pair records merged into the per-target table on the device
+  kCoverage, // prb_search_page_coverage: the hits merged into the per-target coverage table on the device
 };
 // (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
@@ -500,12 +556,15 @@ int page_slot(prb_ctx *user, prb_db *db, int page, int keep, hipStream_t stream,
 std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, int32_t max_seed_length,
                                           double hybrid_threshold);
 // capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
-// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits / prb_targetset of kTop /
-// kProfile / kTopHits / kTargets
+// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits / prb_targetset / prb_covset of
+// kTop / kProfile / kTopHits / kTargets / kCoverage
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
                 SearchMode mode, prb_hitset **out, void *table = nullptr);
 // capi_search.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
 int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh);
+// capi_search.hip: a list of final hits of `page` (of a sub-batch, or a caller's: prb_covset_add_hits) merged into the
+// coverage table, in the bracket of the "coverage" timer; cs->ids holds the identifiers of the list's nq queries
+int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq);
 } // namespace prb

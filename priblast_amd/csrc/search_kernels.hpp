@@ -1,7 +1,7 @@
 // Host-visible interface of the interaction-search kernels: the structs the device sees, then one section per kernel
 // file in the order of the pipeline - seed expansion, ungapped extension, sort, redundancy filter, gapped extension,
 // traceback - and behind it the output modes' own stages (pair summaries and distinct sites, top-N tables, per-target
-// table, profile).
+// table, profile, coverage).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -428,5 +428,56 @@ hipError_t launch_prof_join(const ProfTab &t, const ProfTab &src, int64_t P, hip
 // rows[j] (prb_profile_pos) of the covered slot idx[j]; hits / targets = the scanned difference arrays
 hipError_t launch_prof_rows(const ProfTab &t, const uint32_t *idx, int64_t n, const int64_t *hits, const int32_t *targets, void *rows,
                             hipStream_t s);
+
+// ============================================================================ coverage_kernels.hip: per-target coverage
+// (prb_search_page_coverage, prb_covset_add_hits)
+// The table of one database in HBM, a slot per character of every page's text: page after page, and within a page the
+// text position itself - so every sequence is followed by its separator's slot, which takes the -1 of a span that ends
+// at the sequence's last character and keeps two neighbouring sequences' regions apart (its counts stay 0).  seq_lo[t] =
+// the first slot of target t (targets numbered page by page), seq_lo[ntargets] = the number of slots.  Best-hit keys:
+// key = energy key of e_tot, tie = query identifier << 32 | the hit's place among that query's hits of the page; ~0 = none
+// yet.  skey / stie: the (energy key, tie) minima of the list being merged, ~0 between merges.  bad: set when a hit's
+// span leaves its sequence.
+struct CovTab {
+  const int64_t *seq_lo;           // [ntargets + 1]
+  unsigned long long *hdiff;       // [P] hits: +1 at a span's first position, -1 behind its last (two's complement)
+  unsigned long long *key, *tie;   // [P] the best hit so far
+  unsigned long long *skey, *stie; // [P] scratch of a merge; prb_covset_finish: the scanned hits, the scanned queries and the heads
+  double *e_min;                   // [P] the best hit's e_tot
+  int32_t *qdiff;                  // [P] queries: the same as hdiff over the union of each (identifier, target)'s spans
+  uint32_t *starts;                // [P] hits whose span begins here
+  int32_t *bp;                     // [4 P] the best hit's first and last base pair (q, db, q, db)
+  uint32_t *bad;
+};
+struct CovPage {
+  int64_t slot0, target0; // the page's first slot and first target
+  int32_t nseq;
+};
+// a list of final hits of one page, ascending by `query` (index in the call's batch): SoA columns in device memory
+struct CovHits {
+  int64_t n;
+  const int32_t *query, *db_id;
+  const double *e_tot;
+  const int32_t *ends; // launch_bp_ends' four ints per hit
+};
+// key[i] = query << 32 | first text position of hit i's span, val[i] = i, place[i] = i's index among its query's hits
+hipError_t launch_cov_keys(const CovHits &h, const CovTab &t, const CovPage &pg, uint64_t *key, uint32_t *val, uint32_t *place, hipStream_t s);
+// v[i] = (key[i] with its position bits cleared) | (last position of hit val[i]'s span + 1): what the max-scan takes
+hipError_t launch_cov_span(const CovHits &h, const uint64_t *key, const uint32_t *val, const CovTab &t, const CovPage &pg, uint64_t *v,
+                           hipStream_t s);
+// the difference arrays: every hit's span into hdiff and starts, and the part of it that no earlier hit of its query (in
+// key order) covers into qdiff; m = the inclusive max-scan of launch_cov_span's v
+hipError_t launch_cov_add(const CovHits &h, const uint64_t *key, const uint32_t *val, const uint64_t *m, const CovTab &t, const CovPage &pg,
+                          hipStream_t s);
+// four launches: the list's minima per covered slot (energy key, then (ids[query], place)), the take-over of the slots
+// where that hit is below the table's best, the scratch reset
+hipError_t launch_cov_min(const CovHits &h, const uint32_t *val, const uint32_t *place, const int32_t *ids, const CovTab &t, const CovPage &pg,
+                          hipStream_t s);
+// prb_covset_merge: slots [0, P) of src (same database) into t: counts added, the lower best hit kept
+hipError_t launch_cov_join(const CovTab &t, const CovTab &src, int64_t P, hipStream_t s);
+// prb_covset_finish: out[r] (prb_target_region) of the region that begins at slot first[r], a wavefront each; hits /
+// queries = the scanned difference arrays, D = the depth, tbase[npages + 1] = the pages' first targets
+hipError_t launch_cov_regions(const CovTab &t, const int64_t *tbase, int32_t npages, int64_t ntargets, const uint32_t *first, int64_t nregions,
+                              const int64_t *hits, const int32_t *queries, int32_t D, void *out, hipStream_t s);
 
 } // namespace prb

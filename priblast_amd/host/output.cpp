@@ -246,6 +246,38 @@ void format_profile_piece(const Piece &pc, const ProfileView &v, const std::vect
   }
 }
 
+void format_region_piece(const Piece &pc, const RegionView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_target_region &x = v.r[i];
+    const SeqTable &tab = tabs[x.page];
+    const std::string &dname = tab.names[x.db_id], &qname = v.names[x.query];
+    char *p = b.room(qname.size() + dname.size() + 400);
+    char *const p0 = p;
+    p = put_int(p, id++);
+    *p++ = ',';
+    std::memcpy(p, dname.data(), dname.size());
+    p += dname.size();
+    *p++ = ',';
+    p = put_int(p, tab.len_unmasked[x.db_id]);
+    for (long long f : {(long long)x.start, (long long)x.end, (long long)x.hits, (long long)x.max_hits, (long long)x.max_queries, (long long)x.peak}) {
+      *p++ = ',';
+      p = put_int(p, f);
+    }
+    *p++ = ',';
+    p = put_g(p, x.e_min);
+    *p++ = ',';
+    std::memcpy(p, qname.data(), qname.size());
+    p += qname.size();
+    *p++ = ',';
+    p = put_int(p, v.qlen_unmasked[x.query]);
+    *p++ = ',';
+    p = put_ends(p, tab, x.db_id, x.bp_first, x.bp_last);
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
 } // namespace
 
 int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
@@ -280,6 +312,13 @@ int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &ta
   std::vector<Piece> pieces;
   for (int64_t i = 0; i < v.n; i += kPieceLines) pieces.push_back(Piece{0, 0, i, std::min(v.n, i + kPieceLines), id0 + i});
   return write_pieces(pieces, [&](const Piece &pc, Buf &b) { format_target_piece(pc, v, tabs, b); }, sink, threads) ? id0 + v.n : -1;
+}
+
+int64_t format_region_batch(const RegionView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (as the per-target records: in output order, not grouped by query)
+  std::vector<Piece> pieces;
+  for (int64_t i = 0; i < v.n; i += kPieceLines) pieces.push_back(Piece{0, 0, i, std::min(v.n, i + kPieceLines), id0 + i});
+  return write_pieces(pieces, [&](const Piece &pc, Buf &b) { format_region_piece(pc, v, tabs, b); }, sink, threads) ? id0 + v.n : -1;
 }
 
 } // namespace prb

@@ -88,6 +88,15 @@ struct ProfileView : QueryView {
 };
 int64_t format_profile_batch(const ProfileView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -c D` (prb_covset_regions), one per region, in the records' order (by page, db_id, start), numbered from
+// id0 on; names / qlen_unmasked are indexed by the query's identifier:
+//   Id,dbname,dblen,Start,End,Hits,MaxHits,MaxQueries,Peak,MinEnergy,qname,qlen,(q0-qN:db0-dbN)
+struct RegionView : QueryView {
+  const prb_target_region *r = nullptr;
+  int64_t n = 0;
+};
+int64_t format_region_batch(const RegionView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 int format_threads(); // PRB_HOST_THREADS, else min(32, hardware threads)
 
 } // namespace prb

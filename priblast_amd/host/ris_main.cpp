@@ -38,8 +38,14 @@
 // worker owns one table on its GPU for the whole run (prb_search_page_targets takes every page of every batch it
 // searches); at the end the first worker merges the others' into its own (prb_targetset_merge), and only N records per
 // target reach the host, written by page, target and rank.  `-r` is refused with -t, -n, -q, -k, -b and in rank mode.
+// `ris -c D` says where on a target the queries bind: one line per region - a maximal run of positions of one database
+// sequence, each covered by final hits of at least D distinct queries.  Every worker owns one per-position table of the
+// database on its GPU for the whole run (prb_search_page_coverage takes every page of every batch it searches); at the
+// end the first worker merges the others' into its own (prb_covset_merge), the regions are reduced on the device
+// (prb_covset_finish) and only their records reach the host, written by page, target and start.  `-c` is refused with
+// -t, -n, -q, -k, -b, -r and in rank mode; -u combines.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -r have one table (kSwitchTable) that every refusal is generated
+// How the file is laid out.  The switches -t -n -q -k -b -u -r -c have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
 // join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
 // (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
@@ -124,6 +130,11 @@ void usage() {
             "              sequence) over all the queries, written at the end of the run by page, target and rank (ties by\n"
             "              the query's place in the input file; 1 <= INT <= 1024; not with -t, -n, -q, -k, -b, nor with\n"
             "              WORLD_SIZE > 1; -u combines)\n"
+            "    -c INT    one line per region of a target (database sequence): a maximal run of its positions that final\n"
+            "              hits of at least INT distinct queries cover, with the hits that begin in it, the deepest\n"
+            "              coverage and where it peaks, the minimum interaction energy and its hit, written at the end of\n"
+            "              the run by page, target and start (1 <= INT <= 1000000; not with -t, -n, -q, -k, -b, -r, nor with\n"
+            "              WORLD_SIZE > 1; -u combines)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -146,14 +157,14 @@ thread_local bool t_team_thread = false;
 
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
-// N best pairs per target.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets };
+// N best pairs per target, `-c` the regions of each target that enough queries cover.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kR, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kR, kC, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -170,6 +181,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'b', "binary hit records", 0, -1, false},
     {'u', "the distinct interaction sites of each pair", 0, -1, false},
     {'r', "the N best queries per target", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB), -1, true},
+    {'c', "the regions of each target bound by at least D queries", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR), -1, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -177,7 +189,7 @@ struct Args {
   std::string in, out, db, tmp;
   prb_ris_opts o;
   bool given[kSwitches] = {};
-  int top = 0, tophits = 0, targets = 0; // the values of -n, -k and -r (-1: not a count)
+  int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
   OutputMode mode = OutputMode::kHits;
   bool binary() const { return given[kB]; }
 };
@@ -187,7 +199,8 @@ struct Worker {
   prb_ctx *ctx = nullptr, *prep_ctx = nullptr; // prep_ctx: accessibilities of the next batch, on a stream of its own
   prb_db *db = nullptr;
   prb_targetset *targets = nullptr;                   // -r: this worker's table, for the whole run
-  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r: (input position, unmasked length) of the queries it prepared
+  prb_covset *coverage = nullptr;                     // -c: this worker's table, for the whole run
+  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c: (input position, unmasked length) of the queries it prepared
 };
 
 // The one place where what a search returned is freed.
@@ -500,7 +513,7 @@ struct Run {
   }
 };
 
-// the value of -n / -k / -r: a count, or -1
+// the value of -n / -k / -r / -c: a count, or -1
 int parse_count(const char *arg) {
   char *end = nullptr;
   const long v = std::strtol(arg, &end, 10);
@@ -518,10 +531,11 @@ void check_switches(const Args &a) {
   for (Switch s : {kR, kK, kN})
     if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
+  if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
 }
 
 OutputMode output_mode(const Args &a) {
-  return a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
+  return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
 }
 
@@ -529,7 +543,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ur:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ur:c:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -550,6 +564,7 @@ Args parse_args(int argc, char **argv) {
     case 'n': a.given[kN] = true, a.top = parse_count(optarg); break;
     case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
     case 'r': a.given[kR] = true, a.targets = parse_count(optarg); break;
+    case 'c': a.given[kC] = true, a.depth = parse_count(optarg); break;
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -632,6 +647,7 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prefetch && prb_ctx_create(devices[k], nullptr, &w.prep_ctx)) die(std::string("Error: ") + prb_last_error());
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
     if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
+    if (r.a.mode == OutputMode::kCoverage && prb_covset_create(w.ctx, w.db, &w.coverage)) die(prb_last_error());
   }
 }
 
@@ -692,6 +708,9 @@ std::string header_text(const Run &r) {
                 a.o.final_threshold, a.o.drop_out_wo_gap, a.o.drop_out_w_gap);
   header += buf;
   switch (a.mode) {
+  case OutputMode::kCoverage:
+    return header + "Id,Target name,Target Length,Start,End,Hits,Max Hits,Max Queries,Peak,Minimum Interaction Energy,Query name,"
+                    "Query Length,BasePair\n";
   case OutputMode::kProfile:
     return header + "Id,Query name,Query Length,Position,Hits,Targets,Minimum Interaction Energy,Target name,Target Length,BasePair\n";
   case OutputMode::kSummary:
@@ -796,6 +815,7 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     break;
   }
   case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
+  case OutputMode::kCoverage:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -810,6 +830,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   int rc = 0;
   switch (a.mode) {
   case OutputMode::kTargets: rc = prb_search_page_targets(w.ctx, qb, w.db, page, &a.o, p.ids.data(), w.targets); break;
+  case OutputMode::kCoverage: rc = prb_search_page_coverage(w.ctx, qb, w.db, page, &a.o, p.ids.data(), w.coverage); break;
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &a.o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &a.o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &a.o, mine.tophits.get()); break;
@@ -841,6 +862,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kProfile: run(kProfOps, &BatchResult::prof); break;
   case OutputMode::kTopHits: run(kTopHitsOps, &BatchResult::tophits); break;
   case OutputMode::kTargets:
+  case OutputMode::kCoverage:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -855,9 +877,9 @@ BatchResult empty_result(const Run &r) {
   return res;
 }
 
-// -r: the lines are written at the end of the run, with every query's unmasked length by its place in the input
+// -r, -c: the lines are written at the end of the run, with every query's unmasked length by its place in the input
 void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
-  if (r.a.mode != OutputMode::kTargets) return;
+  if (r.a.mode != OutputMode::kTargets && r.a.mode != OutputMode::kCoverage) return;
   for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
 }
 
@@ -948,7 +970,8 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.n = prb_topset_size(job.res.top.get());
     return written_or_die(prb::format_top_batch(v, r.tabs, id, sink, threads));
   }
-  case OutputMode::kTargets: return id; // (nothing but progress: the table is written at the end of the run, close_run)
+  case OutputMode::kTargets:
+  case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
   case OutputMode::kSummary: {
     prb::SummaryView v;
     set_queries(v, job);
@@ -1339,8 +1362,34 @@ void write_targets(Run &r) {
   written_or_die(prb::format_target_batch(v, r.tabs, 0, sink, prb::format_threads()));
 }
 
+// -c: the first worker merges the others' tables into its own on the device and reduces it to the regions of depth D;
+// the lines by page, target and start, numbered from 0
+void write_regions(Run &r) {
+  Worker &w0 = r.workers[0];
+  std::vector<int32_t> qlen(r.seqs.size(), 0);
+  for (Worker &w : r.workers) {
+    for (const auto &[id, len] : w.target_qlen) qlen[(size_t)id] = len;
+    if (&w != &w0 && prb_covset_merge(w0.ctx, w0.coverage, w.coverage)) die(prb_last_error());
+  }
+  if (prb_covset_finish(w0.ctx, w0.coverage, r.a.depth)) die(prb_last_error());
+  prb::RegionView v;
+  v.nq = r.names.size();
+  v.names = r.names.data();
+  v.qlen_unmasked = qlen.data();
+  v.r = prb_covset_regions(w0.coverage);
+  v.n = prb_covset_size(w0.coverage);
+  for (int64_t i = 0; i < v.n; i++)
+    if (v.r[i].query < 0 || (size_t)v.r[i].query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages || v.r[i].db_id < 0 ||
+        (size_t)v.r[i].db_id >= r.tabs[(size_t)v.r[i].page].names.size())
+      die("Error: bad record in the table of the targets' regions");
+  LineSink sink;
+  sink.fd = fileno(r.out);
+  written_or_die(prb::format_region_batch(v, r.tabs, 0, sink, prb::format_threads()));
+}
+
 void close_run(Run &r, int64_t total_hits) {
   if (r.a.mode == OutputMode::kTargets && r.rank == 0) write_targets(r);
+  if (r.a.mode == OutputMode::kCoverage && r.rank == 0) write_regions(r);
   if (r.a.binary()) {
     put<int64_t>(r.out, kEnd);
     put<int64_t>(r.out, total_hits);
@@ -1349,6 +1398,7 @@ void close_run(Run &r, int64_t total_hits) {
   if (r.comm) prb_comm_destroy(r.comm);
   for (auto &w : r.workers) {
     prb_targetset_free(w.targets);
+    prb_covset_free(w.coverage);
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
     prb_ctx_destroy(w.ctx);
