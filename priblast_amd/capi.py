@@ -497,32 +497,21 @@ def _records(ptr, n, dtype):
     return np.frombuffer((ctypes.c_char * (n * dtype.itemsize)).from_address(ptr), dtype).copy()
 
 
-class _MergeTable:
-    """A table on the device that the pages of one batch are merged into: prb_<PREFIX>_create / _finish / _counts /
-    _free and prb_search_page_<MERGE>."""
-    PREFIX = MERGE = None
-
-    def __init__(self, ctx, qb, *create_args):
-        h = ctypes.c_void_p()
-        _check(self._fn("create")(ctx.h, qb.h, *create_args, ctypes.byref(h)))
-        self.h, self.ctx, self.qb = h, ctx, qb
+class _Table:
+    """A result table on the device, whichever it is made for: prb_<PREFIX>_merge / _finish / _counts / _free."""
+    PREFIX = None
 
     def _fn(self, name):
         return getattr(lib(), f"prb_{self.PREFIX}_{name}")
 
-    def merge(self, db, page, opts=None):
-        """prb_search_page_<MERGE>: searches the batch against `page` and merges the result into the table"""
-        o = opts or default_opts()
-        _check(getattr(lib(), "prb_search_page_" + self.MERGE)(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
-
     def absorb(self, other):
-        """prb_<PREFIX>_merge: the unfinished table `other` (over other pages of the same queries; of any context) merged
-        into this one on the device; `other` is left empty"""
+        """prb_<PREFIX>_merge: the unfinished table `other` (over other pages - or other (identifier, page) sets - of the
+        same queries or database; of any context) merged into this one on the device; `other` is left empty"""
         _check(self._fn("merge")(self.ctx.h, self.h, other.h))
 
-    def _finish(self, records, dtype):
+    def _finish(self, records, dtype, *finish_args):
         """prb_<PREFIX>_finish -> the records that prb_<PREFIX>_<records> points to (a copy)"""
-        _check(self._fn("finish")(self.ctx.h, self.h))
+        _check(self._fn("finish")(self.ctx.h, self.h, *finish_args))
         return _records(self._fn(records)(self.h), self._fn("size")(self.h), dtype)
 
     def counts(self):
@@ -540,6 +529,22 @@ class _MergeTable:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class _MergeTable(_Table):
+    """A table on the device that the pages of one batch are merged into: prb_<PREFIX>_create and
+    prb_search_page_<MERGE>."""
+    MERGE = None
+
+    def __init__(self, ctx, qb, *create_args):
+        h = ctypes.c_void_p()
+        _check(self._fn("create")(ctx.h, qb.h, *create_args, ctypes.byref(h)))
+        self.h, self.ctx, self.qb = h, ctx, qb
+
+    def merge(self, db, page, opts=None):
+        """prb_search_page_<MERGE>: searches the batch against `page` and merges the result into the table"""
+        o = opts or default_opts()
+        _check(getattr(lib(), "prb_search_page_" + self.MERGE)(self.ctx.h, self.qb.h, db.h, page, ctypes.byref(o), self.h))
 
     def search(self, db, opts, pages):
         """every page (all of them, in this order, by default) merged, then finish() -> (what finish returns, counts)"""
@@ -611,48 +616,36 @@ def search_profile(ctx, qb, db, opts=None, pages=None, with_counts=False):
     return (rows, counts) if with_counts else rows
 
 
-class TargetSet:
-    """prb_targetset: the N best queries per target (page, db_id) of one database, in a table on the device that any
-    number of batches is merged into, page by page; every batch names its queries by identifiers of the caller's."""
+class _RunTable(_Table):
+    """A table on the device, made for one database, that any number of batches is merged into, page by page; every
+    batch names its queries by identifiers of the caller's: prb_<PREFIX>_create and prb_search_page_<MERGE>."""
+    MERGE = None
 
-    def __init__(self, ctx, db, n):
+    def __init__(self, ctx, db, *create_args):
         h = ctypes.c_void_p()
-        _check(lib().prb_targetset_create(ctx.h, db.h, n, ctypes.byref(h)))
+        _check(self._fn("create")(ctx.h, db.h, *create_args, ctypes.byref(h)))
         self.h, self.ctx, self.db = h, ctx, db
 
     def merge(self, qb, page, ids, opts=None, db=None):
-        """prb_search_page_targets: searches the batch against `page` and merges its pair records into the table;
+        """prb_search_page_<MERGE>: searches the batch against `page` and merges the result into the table;
         ids[q] = the identifier of query q of the batch"""
         o = opts or default_opts()
         ids = np.ascontiguousarray(ids, np.int32)
         assert len(ids) == len(qb.lens)
-        _check(lib().prb_search_page_targets(self.ctx.h, qb.h, (db or self.db).h, page, ctypes.byref(o), ids.ctypes.data, self.h))
+        _check(getattr(lib(), "prb_search_page_" + self.MERGE)(self.ctx.h, qb.h, (db or self.db).h, page, ctypes.byref(o), ids.ctypes.data, self.h))
 
-    def absorb(self, other):
-        """prb_targetset_merge: the unfinished table `other` (over other (identifier, page) sets; of any context) merged
-        into this one on the device; `other` is left empty"""
-        _check(lib().prb_targetset_merge(self.ctx.h, self.h, other.h))
+
+class TargetSet(_RunTable):
+    """prb_targetset: the N best queries per target (page, db_id) of one database, in a table on the device that any
+    number of batches is merged into, page by page; every batch names its queries by identifiers of the caller's."""
+    PREFIX, MERGE = "targetset", "targets"
+
+    def __init__(self, ctx, db, n):
+        super().__init__(ctx, db, n)
 
     def finish(self):
         """prb_targetset_finish -> structured array TARGET_DTYPE (a copy), by page, then db_id, then rank"""
-        _check(lib().prb_targetset_finish(self.ctx.h, self.h))
-        return _records(lib().prb_targetset_pairs(self.h), lib().prb_targetset_size(self.h), TARGET_DTYPE)
-
-    def counts(self):
-        c = (c_i64 * 3)()
-        lib().prb_targetset_counts(self.h, c)
-        return tuple(c)
-
-    def close(self):
-        if self.h:
-            lib().prb_targetset_free(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._finish("pairs", TARGET_DTYPE)
 
 
 def search_targets(ctx, db, n, batches, opts=None, pages=None, with_counts=False):
@@ -667,23 +660,14 @@ def search_targets(ctx, db, n, batches, opts=None, pages=None, with_counts=False
     return (recs, counts) if with_counts else recs
 
 
-class CovSet:
+class CovSet(_RunTable):
     """prb_covset: the per-position coverage of every target (page, db_id) of one database, in a table on the device that
     any number of batches - or of hit lists - is merged into, page by page; every batch names its queries by identifiers
     of the caller's."""
+    PREFIX, MERGE = "covset", "coverage"
 
     def __init__(self, ctx, db):
-        h = ctypes.c_void_p()
-        _check(lib().prb_covset_create(ctx.h, db.h, ctypes.byref(h)))
-        self.h, self.ctx, self.db = h, ctx, db
-
-    def merge(self, qb, page, ids, opts=None, db=None):
-        """prb_search_page_coverage: searches the batch against `page` and merges its final hits into the table;
-        ids[q] = the identifier of query q of the batch"""
-        o = opts or default_opts()
-        ids = np.ascontiguousarray(ids, np.int32)
-        assert len(ids) == len(qb.lens)
-        _check(lib().prb_search_page_coverage(self.ctx.h, qb.h, (db or self.db).h, page, ctypes.byref(o), ids.ctypes.data, self.h))
+        super().__init__(ctx, db)
 
     def add_hits(self, page, ids, hits, bp):
         """prb_covset_add_hits: a list of final hits of `page` (HIT_DTYPE records ascending by `query`, with the int32 [n, 2]
@@ -695,31 +679,9 @@ class CovSet:
                                          hits.ctypes.data if len(hits) else None, len(hits), bp.ctypes.data if bp.size else None,
                                          bp.size // 2))
 
-    def absorb(self, other):
-        """prb_covset_merge: the unfinished table `other` (over other (identifier, page) sets; of any context) merged into
-        this one on the device; `other` is left empty"""
-        _check(lib().prb_covset_merge(self.ctx.h, self.h, other.h))
-
     def finish(self, d):
         """prb_covset_finish -> structured array REGION_DTYPE (a copy): the regions of depth d by page, db_id and start"""
-        _check(lib().prb_covset_finish(self.ctx.h, self.h, d))
-        return _records(lib().prb_covset_regions(self.h), lib().prb_covset_size(self.h), REGION_DTYPE)
-
-    def counts(self):
-        c = (c_i64 * 3)()
-        lib().prb_covset_counts(self.h, c)
-        return tuple(c)
-
-    def close(self):
-        if self.h:
-            lib().prb_covset_free(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._finish("regions", REGION_DTYPE, d)
 
 
 def search_coverage(ctx, db, d, batches, opts=None, pages=None, with_counts=False):

@@ -111,11 +111,7 @@ struct PageSearch {
   const SearchKnobs &k;
   const int page, last_stage;
   const SearchMode mode;
-  prb_topset *top;   // kTop
-  prb_profset *prof; // kProfile
-  prb_tophits *tophits; // kTopHits
-  prb_targetset *targets; // kTargets
-  prb_covset *cov;   // kCoverage
+  TableState *table; // the table of the mode, if it has one: each emit_* knows which
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
@@ -196,10 +192,13 @@ static HitSoA offset_hits(const HitSoA &h, int64_t first) {
   return HitSoA{h.q_sp + first, h.db_sp + first, h.q_len + first, h.db_len + first, h.db_id + first, h.db_id_start + first,
                 h.query + first, h.e_acc + first, h.e_hyb + first, h.e_tot + first};
 }
-static int bits_for(int64_t max_value) {
-  int b = 1;
-  while (b < 40 && (int64_t(1) << b) <= max_value) b++;
-  return b;
+
+// the radix sorts of the tables' merges (search_host.hpp)
+int sort_target_keys(hipStream_t s, DevBuf &tmp, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits) {
+  return sort_pairs(s, tmp, kin, kout, vin, vout, n, bits);
+}
+hipError_t sort_span_keys(void *tmp, size_t &bytes, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, size_t n, int bits, hipStream_t s) {
+  return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, 0, bits, s);
 }
 
 // Sorts the records `recs` (n hits) into `out` by the reference's comparator made total:
@@ -286,9 +285,6 @@ static int sort_hits(prb_ctx *ctx, SearchWs &w, const SearchKnobs &k, const HitR
   return PRB_OK;
 }
 
-struct ToI64 {
-  __host__ __device__ int64_t operator()(const int32_t &v) const { return (int64_t)v; }
-};
 struct MaxOp {
   __host__ __device__ int64_t operator()(const int64_t &a, const int64_t &b) const { return a > b ? a : b; }
 };
@@ -1332,7 +1328,7 @@ static int emit_summary(SubSearch &s) {
 static int emit_top(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  prb_topset *ts = s.top;
+  prb_topset *ts = static_cast<prb_topset *>(s.table);
   int rc;
   int64_t npairs = 0;
   if ((rc = pair_runs(s, &npairs))) return rc;
@@ -1349,75 +1345,14 @@ static int emit_top(SubSearch &s) {
 static int emit_profile(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  prb_profset *ps = s.prof;
-  const int64_t nfin = s.nfin;
-  const size_t NF = (size_t)nfin;
   int rc;
   int64_t npairs = 0;
   if ((rc = pair_runs(s, &npairs))) return rc;
   if ((rc = ctx->time_end(ctx->summary_timer, 2))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
-  if ((rc = ps->keyA.ensure(NF * 8)) || (rc = ps->keyB.ensure(NF * 8)) || (rc = ps->valA.ensure(NF * 4)) ||
-      (rc = ps->valB.ensure(NF * 4)) || (rc = ps->span.ensure(NF * 8)) || (rc = ps->scan.ensure(NF * 8)))
+  if ((rc = merge_profile(ctx, static_cast<prb_profset *>(s.table), s.page, s.b.q0, s.b.q1, s.F, s.nfin, w.bpEnds.as<int32_t>(),
+                          w.pairStart.as<uint32_t>(), npairs)))
     return rc;
-  const ProfTab t = ps->view();
-  const int32_t *ends = w.bpEnds.as<int32_t>();
-  uint64_t *kA = ps->keyA.as<uint64_t>(), *kB = ps->keyB.as<uint64_t>(), *span = ps->span.as<uint64_t>(), *run_max = ps->scan.as<uint64_t>();
-  uint32_t *vA = ps->valA.as<uint32_t>(), *vB = ps->valB.as<uint32_t>();
-  // the hits by (pair, first position of the span): the pair index above bit 32, as many bits as it needs
-  int bits = 32;
-  while (bits < 64 && ((uint64_t)(npairs - 1) >> (bits - 32)) != 0) bits++;
-  // (pair << 32 | 1 + last position: the running maximum of a pair never looks past the pair's own hits)
-  auto sort_by_pair = [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, kA, kB, vA, vB, NF, 0, bits, ctx->stream); };
-  auto scan_spans = [&](void *tmp, size_t &bytes) {
-    return rocprim::inclusive_scan(tmp, bytes, span, run_max, NF, rocprim::maximum<uint64_t>(), ctx->stream);
-  };
-  // (the two share ps->sortTmp: both are sized before anything is enqueued)
-  size_t tmp_sort = 0, tmp_scan = 0;
-  PRB_HIP(sort_by_pair(nullptr, tmp_sort));
-  PRB_HIP(scan_spans(nullptr, tmp_scan));
-  if ((rc = ps->sortTmp.ensure(std::max<size_t>({tmp_sort, tmp_scan, 1})))) return rc;
-  PRB_HIP(launch_prof_keys(nfin, w.pairStart.as<uint32_t>(), npairs, ends, kA, vA, ctx->stream));
-  PRB_HIP(sort_by_pair(ps->sortTmp.p, tmp_sort));
-  PRB_HIP(launch_prof_span(nfin, kB, vB, ends, span, ctx->stream));
-  PRB_HIP(scan_spans(ps->sortTmp.p, tmp_scan));
-  PRB_HIP(launch_prof_add(s.F, nfin, kB, vB, run_max, ends, t, ctx->stream));
-  PRB_HIP(launch_prof_min(s.F, nfin, vB, ends, t, ctx->stream));
-  PRB_HIP(launch_prof_merge(s.F, ends, t, ps->off[(size_t)s.b.q0], ps->off[(size_t)s.b.q1], s.page, ctx->stream));
-  s.hs->hits_total += nfin;
-  return ctx->time_end(ctx->profile_timer, 8);
-}
-
-// What follows a merge into the top-N hit table, of a sub-batch (emit_tophits) or of another table (prb_tophits_merge):
-// the pair counts of the slots in use, their exclusive scan, and the kept hits' base-pair lists gathered in table order
-// into a second pool of exactly the scanned size, which becomes the table's.  A newcomer's bp_offset is `split` (the
-// table's pool_pairs) + the place of its list in `fresh`.  `fn` names the entry point in the messages.  Synchronises.
-int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh) {
-  int rc;
-  const int64_t nslots = (int64_t)th->nq * th->n;
-  const size_t NS = (size_t)nslots + 1;
-  if ((rc = th->cnt.ensure(NS * 4)) || (rc = th->off.ensure(NS * 8))) return rc;
-  PRB_HIP(launch_tophits_counts(th->table.p, th->fill(), th->n, nslots, th->cnt.as<int32_t>(), ctx->stream));
-  auto counts = rocprim::make_transform_iterator(th->cnt.as<int32_t>(), ToI64());
-  if ((rc = with_temp(th->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
-         return rocprim::exclusive_scan(t, b, counts, th->off.as<int64_t>(), (int64_t)0, NS, rocprim::plus<int64_t>(), ctx->stream);
-       })))
-    return rc;
-  int64_t total = 0;
-  PRB_HIP(hipMemcpyAsync(&total, th->off.as<int64_t>() + nslots, 8, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  if (total < 0) {
-    set_error("top-N hit table: bad base-pair total");
-    return PRB_ERR_STATE;
-  }
-  if (th->pool2.ensure((size_t)std::max<int64_t>(total, 1) * 8) != PRB_OK) {
-    set_error(std::string(fn) + ": can't allocate the pool of the kept hits' base pairs (" + std::to_string(total) + " pairs)");
-    return PRB_ERR_NOMEM;
-  }
-  PRB_HIP(launch_tophits_gather(th->table.p, th->fill(), th->n, nslots, th->off.as<int64_t>(), th->pool_pairs, th->pool.as<int32_t>(), fresh,
-                                th->pool2.as<int32_t>(), ctx->stream));
-  std::swap(th->pool, th->pool2);
-  th->pool_pairs = total;
+  s.hs->hits_total += s.nfin;
   return PRB_OK;
 }
 
@@ -1428,7 +1363,7 @@ int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_
 static int emit_tophits(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  prb_tophits *th = s.tophits;
+  prb_tophits *th = static_cast<prb_tophits *>(s.table);
   const int64_t nfin = s.nfin;
   int rc;
   if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
@@ -1442,76 +1377,19 @@ static int emit_tophits(SubSearch &s) {
   return ctx->time_end(ctx->tophits_timer, 4);
 }
 
-// prb_search_page_targets: the pairs' records - their `query` turned into the caller's identifier - grouped by target (a
-// stable sort by db_id: a target's records stay in query order; always, whatever the sub-batch holds) and every
-// target's run merged into the per-target table by a wavefront; nothing leaves the device
+// prb_search_page_targets: the pairs' records merged into the per-target table on the device; nothing leaves it
 static int emit_targets(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  prb_targetset *ts = s.targets;
   int rc;
   int64_t npairs = 0;
   if ((rc = pair_runs(s, &npairs))) return rc;
   if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
   PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
   if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
-  const size_t NP = (size_t)npairs;
-  if ((rc = ts->key.ensure(NP * 4)) || (rc = ts->keyS.ensure(NP * 4)) || (rc = ts->val.ensure(NP * 4)) || (rc = ts->valS.ensure(NP * 4)) ||
-      (rc = ts->rkey.ensure(NP * sizeof(TargetKey))) || (rc = ts->head.ensure(NP)) || (rc = ts->start.ensure(NP * 4)))
-    return rc;
-  const int32_t nseq = s.pg.nseq;
-  PRB_HIP(launch_target_ids(w.packed.p, npairs, ts->ids.as<int32_t>(), s.qb->nq, ts->key.as<uint32_t>(), ts->val.as<uint32_t>(), ctx->stream));
-  if ((rc = sort_pairs(ctx->stream, ts->sortTmp, ts->key.as<uint32_t>(), ts->keyS.as<uint32_t>(), ts->val.as<uint32_t>(), ts->valS.as<uint32_t>(), NP,
-                       (unsigned)bits_for(std::max(nseq - 1, 1)))))
-    return rc;
-  PRB_HIP(launch_target_runs(w.packed.p, npairs, ts->keyS.as<uint32_t>(), ts->valS.as<uint32_t>(), ts->rkey.as<TargetKey>(), ts->head.as<uint8_t>(),
-                             ctx->stream));
-  int64_t nruns = 0;
-  if ((rc = select_flagged(ctx, w, nullptr, ts->head.as<uint8_t>(), ts->start.as<uint32_t>(), NP, &nruns))) return rc;
-  if (nruns <= 0 || nruns > npairs || nruns > nseq) {
-    set_error("per-target table: " + std::to_string(nruns) + " targets for " + std::to_string(npairs) + " pairs");
-    return PRB_ERR_STATE;
-  }
-  PRB_HIP(launch_target_merge(w.packed.p, ts->rkey.as<TargetKey>(), ts->keyS.as<uint32_t>(), ts->start.as<uint32_t>(), nruns, npairs, s.page,
-                              ts->tbase[(size_t)s.page], nseq, ts->n, ts->keys_of(ts->table.p), ts->slots_of(ts->table.p),
-                              ts->fill_of(ts->table.p), ctx->stream));
+  if ((rc = merge_targets(ctx, w, static_cast<prb_targetset *>(s.table), s.page, s.pg.nseq, s.qb->nq, w.packed.p, npairs))) return rc;
   s.hs->hits_total += s.nfin;
-  return ctx->time_end(ctx->targets_timer, 5);
-}
-
-// What prb_search_page_coverage and prb_covset_add_hits share: the list by (query, first position of the span) - a
-// sequence's positions are contiguous in the page's text, so that is by (query, target, first position) -, the running
-// maximum of the spans' ends per query, the difference arrays, and the four passes of the best hits.  In the bracket of
-// the "coverage" timer.
-int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq) {
-  const size_t NF = (size_t)h.n;
-  int rc;
-  if ((rc = ctx->time_begin())) return rc;
-  if ((rc = cs->keyA.ensure(NF * 8)) || (rc = cs->keyB.ensure(NF * 8)) || (rc = cs->valA.ensure(NF * 4)) || (rc = cs->valB.ensure(NF * 4)) ||
-      (rc = cs->place.ensure(NF * 4)) || (rc = cs->span.ensure(NF * 8)) || (rc = cs->scan.ensure(NF * 8)))
-    return rc;
-  const CovTab t = cs->view();
-  const CovPage pg = cs->page_view((size_t)page);
-  uint64_t *kA = cs->keyA.as<uint64_t>(), *kB = cs->keyB.as<uint64_t>(), *span = cs->span.as<uint64_t>(), *run_max = cs->scan.as<uint64_t>();
-  uint32_t *vA = cs->valA.as<uint32_t>(), *vB = cs->valB.as<uint32_t>(), *place = cs->place.as<uint32_t>();
-  const int bits = 32 + bits_for(std::max(nq - 1, 1)); // the position, and above it the query
-  auto sort_by_query = [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, kA, kB, vA, vB, NF, 0, bits, ctx->stream); };
-  auto scan_spans = [&](void *tmp, size_t &bytes) {
-    return rocprim::inclusive_scan(tmp, bytes, span, run_max, NF, rocprim::maximum<uint64_t>(), ctx->stream);
-  };
-  // (the two share cs->sortTmp: both are sized before anything is enqueued)
-  size_t tmp_sort = 0, tmp_scan = 0;
-  PRB_HIP(sort_by_query(nullptr, tmp_sort));
-  PRB_HIP(scan_spans(nullptr, tmp_scan));
-  if ((rc = cs->sortTmp.ensure(std::max<size_t>({tmp_sort, tmp_scan, 1})))) return rc;
-  PRB_HIP(launch_cov_keys(h, t, pg, kA, vA, place, ctx->stream));
-  PRB_HIP(sort_by_query(cs->sortTmp.p, tmp_sort));
-  PRB_HIP(launch_cov_span(h, kB, vB, t, pg, span, ctx->stream));
-  PRB_HIP(scan_spans(cs->sortTmp.p, tmp_scan));
-  PRB_HIP(launch_cov_add(h, kB, vB, run_max, t, pg, ctx->stream));
-  PRB_HIP(launch_cov_min(h, vB, place, cs->ids.as<int32_t>(), t, pg, ctx->stream));
-  return ctx->time_end(ctx->coverage_timer, 9);
+  return PRB_OK;
 }
 
 // prb_search_page_coverage: the hits merged into the per-target coverage table on the device; nothing leaves it.  Closes
@@ -1524,7 +1402,7 @@ static int emit_coverage(SubSearch &s) {
   if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
   PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
   if ((rc = ctx->time_end("traceback", 2))) return rc;
-  if ((rc = merge_coverage(ctx, s.cov, s.page, CovHits{nfin, s.F.query, s.F.db_id, s.F.e_tot, w.bpEnds.as<int32_t>()}, s.qb->nq))) return rc;
+  if ((rc = merge_coverage(ctx, static_cast<prb_covset *>(s.table), s.page, CovHits{nfin, s.F.query, s.F.db_id, s.F.e_tot, w.bpEnds.as<int32_t>()}, s.qb->nq))) return rc;
   s.hs->hits_total += nfin;
   return PRB_OK;
 }
@@ -1664,7 +1542,7 @@ static bool take_queries(SeedPlan &plan, int32_t q0, double budget, bool wait, i
 }
 
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                SearchMode mode, prb_hitset **out, void *table) {
+                SearchMode mode, prb_hitset **out, TableState *table) {
   const bool summary = reduces_to_pairs(mode);
   const char *fn = summary ? "prb_search_page_summary" : "prb_search_page";
   if (!out) {
@@ -1729,11 +1607,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
                 page,
                 last_stage,
                 mode,
-                mode == SearchMode::kTop ? static_cast<prb_topset *>(table) : nullptr,
-                mode == SearchMode::kProfile ? static_cast<prb_profset *>(table) : nullptr,
-                mode == SearchMode::kTopHits ? static_cast<prb_tophits *>(table) : nullptr,
-                mode == SearchMode::kTargets ? static_cast<prb_targetset *>(table) : nullptr,
-                mode == SearchMode::kCoverage ? static_cast<prb_covset *>(table) : nullptr,
+                table,
                 hs,
                 0,
                 0};
@@ -1968,5 +1842,24 @@ int prb_search_page_summary(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
   *out = ps;
   return PRB_OK;
 }
+
+int64_t prb_pairset_size(const prb_pairset *ps) { return ps ? (int64_t)ps->pairs.size() : -1; }
+const prb_pair_summary *prb_pairset_pairs(const prb_pairset *ps) { return ps ? ps->pairs.data() : nullptr; }
+void prb_pairset_counts(const prb_pairset *ps, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ps ? ps->counts[i] : 0;
+}
+void prb_pairset_free(prb_pairset *ps) { delete ps; }
+
+int64_t prb_hitset_size(const prb_hitset *hs) { return !hs ? -1 : hs->ext_hits ? hs->ext_nhits : (int64_t)hs->hits.size(); }
+const prb_hit *prb_hitset_hits(const prb_hitset *hs) { return !hs ? nullptr : hs->ext_hits ? hs->ext_hits : hs->hits.data(); }
+const int32_t *prb_hitset_basepairs(const prb_hitset *hs, int64_t *count) {
+  if (!hs) return nullptr;
+  if (count) *count = (hs->ext_hits ? hs->ext_bp_ints : (int64_t)hs->bp.size()) / 2;
+  return hs->ext_hits ? hs->ext_bp : hs->bp.data();
+}
+void prb_hitset_counts(const prb_hitset *hs, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = hs ? hs->counts[i] : 0;
+}
+void prb_hitset_free(prb_hitset *hs) { delete hs; }
 
 } // extern "C"

@@ -1,0 +1,295 @@
+// The protocol of the five result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip): what a
+// prb_*_create starts with, what is checked before a page or another table is merged, the merge of one table into
+// another across contexts and devices, and what every prb_*_finish starts with.  `fn_name` is the entry point and `what`
+// the table's noun in the messages.  Every check comes before a table is touched: a refused call leaves it as it was.
+#pragma once
+#include <algorithm>
+#include <string>
+
+#include "search_host.hpp"
+
+namespace prb {
+
+// the caller's current device, put back on every way out of a call that visits another table's device
+struct DeviceScope {
+  int prev = -1;
+  DeviceScope() {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  }
+  ~DeviceScope() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+// device / pinned memory that lives as long as one call
+struct ScratchBuf : DevBuf {
+  ~ScratchBuf() { release(); }
+};
+struct ScratchPin : PinnedBuf {
+  ~ScratchPin() { release(); }
+};
+
+inline int refuse(const std::string &fn, const std::string &why, int code = PRB_ERR_ARG) {
+  set_error(fn + ": " + why);
+  return code;
+}
+
+// ---- prb_*_create
+// What the five create functions start with (args_ok: the caller's test of its other arguments): *out = nullptr, the
+// caller's own refusal if it has one (bad_n), and an empty table in `t`
+template <class T> int new_table(const char *fn_name, bool args_ok, T **out, std::unique_ptr<T> &t, const std::string &why = "") {
+  if (!args_ok || !out) return refuse(fn_name, "bad argument");
+  *out = nullptr;
+  if (!why.empty()) return refuse(fn_name, why);
+  t.reset(new (std::nothrow) T());
+  if (!t) return refuse(fn_name, "out of host memory", PRB_ERR_NOMEM);
+  return PRB_OK;
+}
+// the refusal of a number of slots per query or target that no table takes ("": n is fine)
+inline std::string bad_n(int32_t n) {
+  return n < 1 || n > kTopMaxN ? "need 1 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")" : "";
+}
+
+// ---- prb_*_finish
+// What every prb_*_finish starts with: the table belongs to ctx and no merge into it failed
+inline int finish_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *t) {
+  if (!ctx || !t || t->ctx != ctx) return refuse(fn_name, "bad argument (the table belongs to another context)");
+  if (t->broken) return refuse(fn_name, std::string("an earlier merge into this ") + what + " table failed", PRB_ERR_STATE);
+  return PRB_OK;
+}
+
+// ---- prb_search_page_top / _profile / _tophits: a page searched and merged into a batch table
+// Page `page` searched in `mode` and merged into the table `t`, finished by `finish_fn`
+inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb,
+                      prb_db *db, int32_t page, const prb_ris_opts *opts) {
+  const std::string fn = fn_name, table = std::string(what) + " table";
+  if (!t) return refuse(fn, "bad argument");
+  if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
+  if (t->ctx != ctx || t->qb != qb || t->nq != qb->nq)
+    return refuse(fn, "the " + table + " was made for another context or query batch (" + std::to_string(t->nq) + " queries; this batch has " +
+                          std::to_string(qb->nq) + ")");
+  if (t->db && t->db != db) return refuse(fn, "the " + table + " holds pages of another database");
+  if (t->broken) return refuse(fn, "an earlier merge into this " + table + " failed", PRB_ERR_STATE);
+  if (t->finished) return refuse(fn, "the " + table + " is finished (" + finish_fn + ")", PRB_ERR_STATE);
+  if (t->distinct >= 0 && opts->distinct_sites != t->distinct)
+    return refuse(fn, "the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
+                          std::to_string(opts->distinct_sites) + ")");
+  if (!t->db) {
+    t->db = db;
+    t->merged.assign(db->pages.size(), 0);
+  }
+  if (t->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this " + table);
+  t->merged[(size_t)page] = 1;
+  prb_hitset *hs = nullptr;
+  const int rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t);
+  if (rc != PRB_OK) {
+    t->broken = true;
+    return rc;
+  }
+  for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
+  t->distinct = opts->distinct_sites;
+  delete hs;
+  return PRB_OK;
+}
+
+// ---- prb_search_page_targets / _coverage / prb_covset_add_hits: a batch merged into a run table
+// What is checked of the run table `t`, finished by `finish_fn`, before a batch of nq queries named query_ids is merged
+// into it for `page` (distinct < 0: the call has no options).  A call that passes has its identifiers marked as merged.
+inline int run_table_guard(const std::string &fn, const char *what, const char *finish_fn, RunTable *t, const prb_ctx *ctx, const prb_db *db,
+                           int32_t page, int32_t distinct, const int32_t *query_ids, int32_t nq) {
+  const std::string table = std::string(what) + " table";
+  if (t->ctx != ctx || t->db != db) return refuse(fn, "the " + table + " was made with another context or for another database");
+  if (t->broken) return refuse(fn, "an earlier merge into this " + table + " failed", PRB_ERR_STATE);
+  if (t->finished) return refuse(fn, "the " + table + " is finished (" + finish_fn + ")", PRB_ERR_STATE);
+  if (t->distinct >= 0 && distinct >= 0 && distinct != t->distinct)
+    return refuse(fn, "the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
+                          std::to_string(distinct) + ")");
+  try {
+    std::vector<int32_t> sorted(query_ids, query_ids + nq);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < sorted.size(); i++) {
+      if (sorted[i] < 0) return refuse(fn, "query identifier " + std::to_string(sorted[i]) + " is below 0");
+      if (i && sorted[i] == sorted[i - 1]) return refuse(fn, "query identifier " + std::to_string(sorted[i]) + " is given twice");
+      if (t->has((size_t)page, sorted[i]))
+        return refuse(fn, "query identifier " + std::to_string(sorted[i]) + " is already merged for page " + std::to_string(page));
+    }
+    for (int32_t id : sorted) t->set((size_t)page, id);
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  return PRB_OK;
+}
+// the identifiers of the batch being merged into t, on the device (the current one)
+inline int upload_ids(prb_ctx *ctx, RunTable *t, const int32_t *query_ids, int32_t nq) {
+  if (int rc = t->ids.ensure(std::max<size_t>((size_t)nq * 4, 4))) return rc;
+  PRB_HIP(hipMemcpyAsync(t->ids.p, query_ids, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  return PRB_OK;
+}
+// Page `page` searched in `mode` and merged into the run table `t` under the caller's identifiers.  A failure from the
+// upload on leaves the table unusable.
+inline int merge_run_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, RunTable *t, prb_ctx *ctx,
+                          prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids) {
+  if (!t || !query_ids) return refuse(fn_name, "bad argument");
+  if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
+  if (int rc = run_table_guard(fn_name, what, finish_fn, t, ctx, db, page, opts->distinct_sites, query_ids, qb->nq)) return rc;
+  PRB_HIP(hipSetDevice(ctx->device));
+  t->broken = true; // (until the merge is whole)
+  int rc;
+  if ((rc = upload_ids(ctx, t, query_ids, qb->nq))) return rc;
+  prb_hitset *hs = nullptr;
+  if ((rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t))) return rc;
+  for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
+  t->distinct = opts->distinct_sites;
+  t->broken = false;
+  delete hs;
+  return PRB_OK;
+}
+
+// ---- prb_*_merge: two unfinished tables over disjoint page or (page, identifier) sets into one
+// What all five check first: `dst` belongs to ctx, both are unfinished and whole, own() has no refusal of the table's
+// own ("" = none; asked once both are known to be whole and unfinished), and both were searched with one distinct_sites
+template <class Own>
+int merge_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *dst, const TableState *src, Own own) {
+  const std::string tables = std::string(what) + " tables";
+  if (!ctx || !dst || !src || dst == src) return refuse(fn_name, "bad argument");
+  if (dst->ctx != ctx) return refuse(fn_name, "the table to merge into belongs to another context");
+  if (dst->broken || src->broken) return refuse(fn_name, "an earlier merge into one of the " + tables + " failed");
+  if (dst->finished || src->finished) return refuse(fn_name, "one of the " + tables + " is finished");
+  if (const std::string why = own(); !why.empty()) return refuse(fn_name, why);
+  if (dst->distinct >= 0 && src->distinct >= 0 && dst->distinct != src->distinct)
+    return refuse(fn_name, "the " + tables + " hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
+                               std::to_string(src->distinct));
+  return PRB_OK;
+}
+// ... of two batch tables: made for the same queries, and no page is in both
+inline int merge_tables_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const MergeTable *dst, const MergeTable *src) {
+  const std::string tables = std::string(what) + " tables";
+  if (int rc = merge_guard(fn_name, what, ctx, dst, src, [&]() -> std::string {
+        if (dst->nq != src->nq) return "the " + tables + " were made for " + std::to_string(dst->nq) + " and " + std::to_string(src->nq) + " queries";
+        if (dst->qlen != src->qlen) return "the " + tables + " were made for queries of different lengths";
+        return "";
+      }))
+    return rc;
+  if (dst->db && src->db) {
+    if (dst->merged.size() != src->merged.size())
+      return refuse(fn_name, "the " + tables + " hold pages of databases of " + std::to_string(dst->merged.size()) + " and " +
+                                 std::to_string(src->merged.size()) + " pages");
+    for (size_t p = 0; p < dst->merged.size(); p++)
+      if (dst->merged[p] && src->merged[p]) return refuse(fn_name, "page " + std::to_string(p) + " is merged into both " + tables);
+  }
+  return PRB_OK;
+}
+// ... of two run tables: more() has no refusal of the table's own, they were made for databases of one shape, and no
+// (page, identifier) is in both
+template <class More>
+int run_tables_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const RunTable *dst, const RunTable *src, More more) {
+  const std::string tables = std::string(what) + " tables";
+  if (int rc = merge_guard(fn_name, what, ctx, dst, src, [&]() -> std::string {
+        if (const std::string why = more(); !why.empty()) return why;
+        return dst->tbase != src->tbase ? "the " + tables + " were made for different databases" : "";
+      }))
+    return rc;
+  for (size_t p = 0; p < dst->merged.size(); p++) {
+    const std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
+    for (size_t k = 0; k < std::min(a.size(), b.size()); k++)
+      if (a[k] & b[k]) return refuse(fn_name, "a query identifier is merged for page " + std::to_string(p) + " into both " + tables);
+  }
+  return PRB_OK;
+}
+
+// after the merge: dst's counts are the sums and its distinct_sites the merged pages'; src has merged nothing
+inline void move_counts(TableState *dst, TableState *src) {
+  for (int i = 0; i < 3; i++) {
+    dst->counts[i] += src->counts[i];
+    src->counts[i] = 0;
+  }
+  if (dst->distinct < 0) dst->distinct = src->distinct;
+  src->distinct = -1;
+}
+// ... and dst's page set is the union
+inline void move_merged(MergeTable *dst, MergeTable *src) {
+  if (src->db) {
+    if (!dst->db) {
+      dst->db = src->db;
+      dst->merged = src->merged;
+    } else {
+      for (size_t p = 0; p < dst->merged.size(); p++) dst->merged[p] |= src->merged[p];
+    }
+  }
+  move_counts(dst, src);
+  src->db = nullptr;
+  src->merged.clear();
+}
+// ... and dst's identifier sets are the unions
+inline void move_merged(RunTable *dst, RunTable *src) {
+  for (size_t p = 0; p < dst->merged.size(); p++) {
+    std::vector<uint64_t> &a = dst->merged[p], &b = src->merged[p];
+    if (a.size() < b.size()) a.resize(b.size(), 0);
+    for (size_t k = 0; k < b.size(); k++) a[k] |= b[k];
+    b.clear();
+  }
+  move_counts(dst, src);
+}
+
+// `bytes` at p on device `from` into `scratch` on ctx's device (the current one), complete on return or in order on
+// ctx's stream: a peer copy where the devices allow it, else through pinned host memory
+inline int fetch_remote(prb_ctx *ctx, int from, const void *p, size_t bytes, DevBuf &scratch) {
+  if (int rc = scratch.ensure(std::max<size_t>(bytes, 1))) return rc;
+  if (!bytes) return PRB_OK;
+  int peer = 0;
+  if (hipDeviceCanAccessPeer(&peer, ctx->device, from) != hipSuccess) {
+    (void)hipGetLastError();
+    peer = 0;
+  }
+  if (peer) {
+    PRB_HIP(hipMemcpyPeerAsync(scratch.p, ctx->device, p, from, bytes, ctx->stream));
+    return PRB_OK;
+  }
+  ScratchPin pin;
+  if (int rc = pin.ensure(bytes)) return rc;
+  PRB_HIP(hipSetDevice(from));
+  PRB_HIP(hipMemcpy(pin.p, p, bytes, hipMemcpyDeviceToHost));
+  PRB_HIP(hipSetDevice(ctx->device));
+  PRB_HIP(hipMemcpy(scratch.p, pin.p, bytes, hipMemcpyHostToDevice));
+  return PRB_OK;
+}
+// `bytes` at p of a table of context `owner`, once that context's work is done, where ctx's device reads them: in place,
+// or a copy in `scratch`
+inline int on_device_of(prb_ctx *ctx, const prb_ctx *owner, void *p, size_t bytes, DevBuf &scratch, void **out) {
+  PRB_HIP(hipStreamSynchronize(owner->stream));
+  *out = p;
+  if (owner->device == ctx->device || !p) return PRB_OK;
+  if (int rc = fetch_remote(ctx, owner->device, p, bytes, scratch)) return rc;
+  *out = scratch.p;
+  return PRB_OK;
+}
+
+// The merge proper, behind the table's guard: src's block of `bytes` (and what `more` fetches) where dst's device reads
+// it, join(block) enqueued in the bracket of `timer` with its `launches`, dst's book-keeping, then src emptied on its
+// own device by `clear`.  A failure from the first launch on leaves dst unusable.
+template <class T, class More, class Join, class Clear>
+int join_tables(const char *fn_name, StageTimer prb_ctx::*timer, int64_t launches, prb_ctx *ctx, T *dst, T *src, size_t bytes, More more,
+                Join join, Clear clear) {
+  DeviceScope restore;
+  ScratchBuf copy;
+  PRB_HIP(hipSetDevice(ctx->device));
+  void *block = nullptr;
+  int rc;
+  if ((rc = on_device_of(ctx, src->ctx, src->table.p, bytes, copy, &block))) return rc;
+  if ((rc = more())) return rc;
+  dst->broken = true; // (until the merge is whole)
+  if ((rc = ctx->time_begin())) return rc;
+  if ((rc = join(block))) return rc;
+  if ((rc = ctx->time_end(ctx->*timer, launches))) return rc; // (synchronises: src is read no more)
+  dst->broken = false;
+  try {
+    move_merged(dst, src);
+  } catch (const std::exception &e) { // (a page set that could not grow)
+    dst->broken = true;
+    return refuse(fn_name, e.what(), PRB_ERR_NOMEM);
+  }
+  return clear(*src);
+}
+inline int nothing_more() { return PRB_OK; }
+
+} // namespace prb

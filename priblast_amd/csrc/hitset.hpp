@@ -1,5 +1,5 @@
 // prb_hitset (include/priblast_hip.h): the result of prb_search_page / prb_gather_hits, shared by the search driver
-// (capi_search.hip, which fills it), capi_sets.hip (its accessors) and capi_comm.hip (the final hit gather).
+// (capi_search.hip, which fills it and has its accessors) and capi_comm.hip (the final hit gather).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
-// What the host units of the search share (capi_pages.hip, capi_search.hip, capi_sets.hip, capi_lines.hip): the
-// objects behind the C ABI's handles, the workspace of the search stages, and the rocPRIM idioms they all use.
+// What the host units of the search share (capi_pages.hip, capi_search.hip, capi_top.hip, capi_targets.hip,
+// capi_spans.hip, capi_lines.hip): the objects behind the C ABI's handles, the workspace of the search stages, and the
+// rocPRIM idioms they all use.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -240,6 +241,17 @@ struct HostTimer {
 };
 
 // ---------------------------------------------------------------- rocPRIM idioms
+// a 32-bit count as what a 64-bit scan adds up
+struct ToI64 {
+  __host__ __device__ int64_t operator()(const int32_t &v) const { return (int64_t)v; }
+};
+// the bits of a sort key's field whose largest value is max_value
+inline int bits_for(int64_t max_value) {
+  int b = 1;
+  while (b < 40 && (int64_t(1) << b) <= max_value) b++;
+  return b;
+}
+
 // rocPRIM's two calls: `call(nullptr, bytes)` asks for the size of the temporary storage, `tmp` grows to it,
 // `call(tmp.p, bytes)` does the work.  (Where several primitives share one temporary buffer within a stream sequence,
 // all are sized before the first is enqueued instead - a DevBuf that grows frees memory that work in flight still reads.)
@@ -341,29 +353,62 @@ struct prb_qbatch {
 };
 
 namespace prb {
-// What the tables that a batch's pages are merged into one by one have in common (prb_topset, prb_profset,
-// prb_tophits), and what prb_search_page_top / prb_search_page_profile / prb_search_page_tophits check before a merge
-struct MergeTable {
+// What the five result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset): whose
+// they are, whether they can still be merged into, and the block on the device that the merges work on.  What every
+// prb_*_merge and prb_*_finish checks (capi_tables.hpp) and what search_page hands to the emit_* of its mode.
+struct TableState {
   prb_ctx *ctx = nullptr;
+  const prb_db *db = nullptr;  // batch tables: of the first merged page; run tables: the one they were made for
+  bool broken = false;         // a merge failed part way
+  bool finished = false;       // prb_*_finish: the records are on the host, the device memory is released
+  int32_t distinct = -1;       // opts->distinct_sites of the merged pages (-1: none yet)
+  int64_t counts[3] = {0, 0, 0};
+  DevBuf table;                // the table proper, one block (every table says what it holds)
+};
+
+// The tables that a batch's pages are merged into one by one (prb_topset, prb_profset, prb_tophits): a byte per page
+struct MergeTable : TableState {
   const prb_qbatch *qb = nullptr;
-  const prb_db *db = nullptr;  // of the first merged page
   int32_t nq = 0;
   std::vector<int32_t> qlen;   // the queries' lengths (what two tables must share to be merged, prb_*_merge)
   std::vector<uint8_t> merged; // per page of db
-  bool broken = false;         // a merge failed part way
-  bool finished = false;       // prb_*set_finish: the records are on the host, the device memory is released
-  int32_t distinct = -1;       // opts->distinct_sites of the merged pages (-1: none yet)
-  int64_t counts[3] = {0, 0, 0};
 };
-} // namespace prb
 
-namespace prb {
+// The tables that live for a whole run and are keyed by the database's targets (page, db_id) (prb_targetset, prb_covset):
+// such a table takes any number of batches, so it keeps a bit per (page, query identifier)
+struct RunTable : TableState {
+  std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
+  std::vector<std::vector<uint64_t>> merged;  // per page: a bit per query identifier merged, grown on demand
+  DevBuf ids;                                 // the identifiers of the batch being merged
+  int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
+  bool has(size_t page, int32_t id) const {
+    const std::vector<uint64_t> &m = merged[page];
+    return ((size_t)id >> 6) < m.size() && (m[(size_t)id >> 6] >> (id & 63) & 1);
+  }
+  void set(size_t page, int32_t id) {
+    std::vector<uint64_t> &m = merged[page];
+    if (((size_t)id >> 6) >= m.size()) m.resize(((size_t)id >> 6) + 1, 0);
+    m[(size_t)id >> 6] |= 1ull << (id & 63);
+  }
+};
+
+// What the two span tables own beside their block (prb_profset, prb_covset; capi_spans.hip): per merge the hits in
+// (owner, first position) order - keys and values before and behind the sort, the spans' ends and their running
+// maximum - and the temporary storage of the sorts, scans and selects
+struct SpanBufs {
+  DevBuf keyA, keyB, valA, valB, span, scan, sortTmp;
+  void release() {
+    for (DevBuf *b : {&keyA, &keyB, &valA, &valB, &span, &scan, &sortTmp}) b->release();
+  }
+};
+
 // What the two top-N tables have in common (prb_topset, prb_tophits): n slots of `Slot` per query and the queries' fill
-// counts, one block on the device
+// counts, one block on the device: Slot[nq * n] (`rank` = the record's ordinal within its query's run on the device),
+// then int32_t fill[nq]
 template <class Slot> struct TopTable : MergeTable {
   int32_t n = 0;
-  DevBuf table; // Slot[nq * n] (`rank` = the record's ordinal within its query's run on the device), then int32_t fill[nq]
   size_t slots_bytes() const { return (size_t)nq * (size_t)n * sizeof(Slot); }
+  size_t bytes() const { return slots_bytes() + (size_t)nq * sizeof(int32_t); }
   int32_t *fill() const { return reinterpret_cast<int32_t *>(table.template as<char>() + slots_bytes()); }
 };
 } // namespace prb
@@ -396,15 +441,14 @@ struct prb_tophits : prb::TopTable<prb_top_hit> {
 };
 
 // prb_profset_create .. prb_profset_free: the per-position table of one batch, merged into sub-batch by sub-batch
-// (emit_profile, capi_search.hip), and the sort / scan buffers of those merges
-struct prb_profset : prb::MergeTable {
+// (merge_profile, capi_spans.hip), and the sort / scan buffers of those merges (per sub-batch: the hits in (pair, first
+// position) order)
+struct prb_profset : prb::MergeTable, prb::SpanBufs {
   std::vector<int64_t> off;    // [nq + 1] the queries' first slots (ProfTab::off)
-  prb::DevBuf table;           // ProfTab's arrays, one block (view())
-  prb::DevBuf keyA, keyB, valA, valB, span, scan, sortTmp; // per sub-batch: the hits in (pair, first position) order
   std::vector<prb_profile_pos> rows; // prb_profset_finish
   int64_t slots() const { return off.empty() ? 0 : off.back(); }
-  // the block: off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie, db_id,
-  // bp (x4), bad
+  // the block (view()): off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie,
+  // db_id, bp (x4), bad
   size_t bytes() const { return (off.size() + 5 * (size_t)slots()) * 8 + (7 * (size_t)slots() + 2) * 4; }
   prb::ProfTab view() const { return view_of(table.as<char>()); }
   // the arrays of a block at b (the table's own, or a copy of another table's)
@@ -427,7 +471,8 @@ struct prb_profset : prb::MergeTable {
     return t;
   }
   void release() {
-    for (prb::DevBuf *b : {&table, &keyA, &keyB, &valA, &valB, &span, &scan, &sortTmp}) b->release();
+    table.release();
+    SpanBufs::release();
   }
   ~prb_profset() { // (also on the error paths of prb_profset_create)
     if (table.p || keyA.p || sortTmp.p) (void)hipSetDevice(ctx->device);
@@ -435,37 +480,11 @@ struct prb_profset : prb::MergeTable {
   }
 };
 
-namespace prb {
-// What the tables that live for a whole run and are keyed by the database's targets (page, db_id) have in common
-// (prb_targetset, prb_covset), and what prb_search_page_targets / prb_search_page_coverage check before a merge.  Such a
-// table takes any number of batches, so it shares nothing with MergeTable but the flags.
-struct RunTable {
-  prb_ctx *ctx = nullptr;
-  const prb_db *db = nullptr;
-  std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
-  std::vector<std::vector<uint64_t>> merged;  // per page: a bit per query identifier merged, grown on demand
-  bool broken = false, finished = false;
-  int32_t distinct = -1;                      // opts->distinct_sites of the merged calls (-1: none yet)
-  int64_t counts[3] = {0, 0, 0};
-  prb::DevBuf ids;                            // the identifiers of the batch being merged
-  int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
-  bool has(size_t page, int32_t id) const {
-    const std::vector<uint64_t> &m = merged[page];
-    return ((size_t)id >> 6) < m.size() && (m[(size_t)id >> 6] >> (id & 63) & 1);
-  }
-  void set(size_t page, int32_t id) {
-    std::vector<uint64_t> &m = merged[page];
-    if (((size_t)id >> 6) >= m.size()) m.resize(((size_t)id >> 6) + 1, 0);
-    m[(size_t)id >> 6] |= 1ull << (id & 63);
-  }
-};
-} // namespace prb
-
 // prb_targetset_create .. prb_targetset_free: the per-target table of one database, merged into sub-batch by sub-batch
-// (emit_targets, capi_search.hip) for as many batches as the caller likes, and the sort buffers of those merges.
+// (merge_targets, capi_targets.hip) for as many batches as the caller likes, and the sort buffers of those merges.
+// The block: TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
 struct prb_targetset : prb::RunTable {
   int32_t n = 0;
-  prb::DevBuf table;                          // TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
   prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
   std::vector<prb_target_pair> pairs;         // prb_targetset_finish
   size_t entries() const { return (size_t)targets() * (size_t)n; }
@@ -486,19 +505,19 @@ struct prb_targetset : prb::RunTable {
 };
 
 // prb_covset_create .. prb_covset_free: the per-position coverage table of one database, merged into sub-batch by
-// sub-batch (emit_coverage, capi_search.hip) or list by list (prb_covset_add_hits) for as many batches as the caller
-// likes, and the sort / scan buffers of those merges
-struct prb_covset : prb::RunTable {
+// sub-batch (prb_search_page_coverage) or list by list (prb_covset_add_hits) for as many batches as the caller likes
+// (merge_coverage, capi_spans.hip), and the sort / scan buffers of those merges (per merge: the hits in (query, first
+// position) order)
+struct prb_covset : prb::RunTable, prb::SpanBufs {
   std::vector<int64_t> seq_lo;  // [T + 1] the first slot of every target (CovTab::seq_lo); back() = the slots
   std::vector<int64_t> slot0;   // [npages + 1] the first slot of every page
-  prb::DevBuf table;            // seq_lo, tbase, then CovTab's arrays, one block (view())
-  prb::DevBuf keyA, keyB, valA, valB, place, span, scan, sortTmp; // per merge: the hits in (query, first position) order
-  prb::DevBuf h_query, h_db_id, h_e_tot, h_ends;                  // prb_covset_add_hits: the caller's list as columns
+  prb::DevBuf place;                              // per merge: every hit's place in its list
+  prb::DevBuf h_query, h_db_id, h_e_tot, h_ends;  // prb_covset_add_hits: the caller's list as columns
   std::vector<prb_target_region> regions; // prb_covset_finish
   int64_t slots() const { return seq_lo.empty() ? 0 : seq_lo.back(); }
   size_t head_bytes() const { return (seq_lo.size() + tbase.size()) * 8; }
-  // the block: seq_lo and tbase, then the 8-byte arrays hdiff, key, tie, skey, stie, e_min, then the 4-byte arrays qdiff,
-  // starts, bp (x4), bad
+  // the block (view()): seq_lo and tbase, then the 8-byte arrays hdiff, key, tie, skey, stie, e_min, then the 4-byte
+  // arrays qdiff, starts, bp (x4), bad
   size_t bytes() const { return head_bytes() + 6 * (size_t)slots() * 8 + (6 * (size_t)slots() + 2) * 4; }
   prb::CovTab view() const { return view_of(table.as<char>()); }
   const int64_t *tbase_dev() const { return table.as<int64_t>() + seq_lo.size(); }
@@ -524,8 +543,8 @@ struct prb_covset : prb::RunTable {
     return prb::CovPage{slot0[page], tbase[page], (int32_t)(tbase[page + 1] - tbase[page])};
   }
   void release() {
-    for (prb::DevBuf *b : {&table, &ids, &keyA, &keyB, &valA, &valB, &place, &span, &scan, &sortTmp, &h_query, &h_db_id, &h_e_tot, &h_ends})
-      b->release();
+    for (prb::DevBuf *b : {&table, &ids, &place, &h_query, &h_db_id, &h_e_tot, &h_ends}) b->release();
+    SpanBufs::release();
   }
   ~prb_covset() { // (also on the error paths of prb_covset_create)
     if (table.p || ids.p || keyA.p || h_query.p) (void)hipSetDevice(ctx->device);
@@ -561,10 +580,26 @@ std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, co
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
-                SearchMode mode, prb_hitset **out, void *table = nullptr);
-// capi_search.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
+                SearchMode mode, prb_hitset **out, TableState *table = nullptr);
+// capi_search.hip: the two radix sorts of the tables' merges - by the low `bits` bits of 32-bit keys, through `tmp`
+// (capi_targets.hip), and rocPRIM's two calls for 64-bit keys (capi_spans.hip).  Every radix sort of the search is
+// instantiated in that one unit: the register count and the code the compiler gives a rocPRIM sort kernel depend on
+// which other sorts the unit instantiates.  With these two in the tables' units, five kernels came out otherwise: the
+// block sort of (u32, u32), the block sort of (u64, u32) in both its `const *` and plain-pointer forms (52 VGPRs against
+// 48, the former without having left this unit), and the two onesweep iterations of (u64, u32).
+int sort_target_keys(hipStream_t s, DevBuf &tmp, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits);
+hipError_t sort_span_keys(void *tmp, size_t &bytes, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, size_t n, int bits, hipStream_t s);
+
+// What a sub-batch's emit_* (capi_search.hip) hands to its table, each in a bracket of the table's stage timer that it
+// opens and closes; nothing leaves the device.  `page`, [q0, q1) = the sub-batch's page and queries.
+// capi_top.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
 int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh);
-// capi_search.hip: a list of final hits of `page` (of a sub-batch, or a caller's: prb_covset_add_hits) merged into the
-// coverage table, in the bracket of the "coverage" timer; cs->ids holds the identifiers of the list's nq queries
+// capi_targets.hip: the npairs pair records at `packed` (of a batch of nq queries against a page of nseq sequences)
+int merge_targets(prb_ctx *ctx, SearchWs &w, prb_targetset *ts, int32_t page, int32_t nseq, int32_t nq, void *packed, int64_t npairs);
+// capi_spans.hip: the nfin final hits F with their end pairs `ends`, in npairs pair runs that start at pair_start
+int merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, int32_t q1, const HitSoA &F, int64_t nfin, const int32_t *ends,
+                  const uint32_t *pair_start, int64_t npairs);
+// capi_spans.hip: a list of final hits of `page` (of a sub-batch, or a caller's: prb_covset_add_hits); cs->ids holds the
+// identifiers of the list's nq queries
 int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq);
 } // namespace prb
