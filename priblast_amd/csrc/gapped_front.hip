@@ -76,6 +76,7 @@ constexpr int kFCells = 192;      // filled cells of a wavefront's directions in
 #define PRB_FRONT_PAIRS 256
 #endif
 constexpr int kFPairs = PRB_FRONT_PAIRS;      // (cell, candidate) pairs in one round of at most 64 cells
+constexpr int kFScan = 8;         // records of a direction's list a cell looks at per turn of its candidate scan
 
 // the part of SearchTab every loop class but the 1x1 / 1x2 / 2x1 / 2x2 interior loops reads from, staged in LDS
 struct FrontTab {
@@ -281,9 +282,7 @@ __global__ __launch_bounds__(64 * kFWaves) void k_gapped_front(GapArgs a, FrontA
   while (tile < ntiles) {
     FP_MARK(0);
     FP_COUNT(16, 1);
-    // the next tile: one atomic per wavefront, asked for now and looked at when this tile is done
-    unsigned long long nt = 0;
-    if (lane == 0) nt = atomicAdd(a.next_work, 1ull);
+    unsigned long long nt = 0; // the next tile: asked for behind the accessibility terms, looked at when this tile is done
     // ---- the hit, the direction's origin (:88-128) ----
     const int64_t w = tile * kTileHits + (kOneDir ? lane : lane >> 1);
     const bool live = isdir && w < a.n;
@@ -359,15 +358,31 @@ __global__ __launch_bounds__(64 * kFWaves) void k_gapped_front(GapArgs a, FrontA
       const int p0 = f0 ? q_start : id_start;
       const int t3 = f0 ? tq0 : td0, t1 = f0 ? td0 : tq0;
       double s3 = 0, s1 = 0;
-      // all the terms first (their loads in flight together): a3[p0 - len] of one length is a3[p0 - len + 1] of the next
+      // all the terms first, their loads in flight together: a term that is not there is read from a place that always can be
+      // (the first query's first value) and left aside - a load under its own condition is waited for before the next one is
+      // asked for, 46 round trips one behind the other.  a3[p0 - len] of one length is a3[p0 - len + 1] of the next
+      // (qb.acc holds L values and one 0 per query, so its first entry is there whenever a hit is.  That the loads below stay
+      // unconditional is the compiler's choice: DESIGN.md, "The front kernel", says how to check it)
+      const float *const nowhere = a.qb.acc;
       float ta[kFD + 1], tz[kFD], tw[kFD];
-      ta[0] = (live && 1 < t3 && 1 <= lend) ? a3[p0] : 0.0f;
+      const bool v0 = live && 1 < t3 && 1 <= lend;
+      ta[0] = *(v0 ? a3 + p0 : nowhere);
 #pragma unroll
       for (int len = 1; len <= kFD; len++) {
         const bool v3 = live && len < t3 && len <= lend, v1 = live && len < t1 && len <= lend;
-        ta[len] = v3 ? a3[p0 - len] : 0.0f;
-        tz[len - 1] = v3 ? c3[p0 - len + delta] : 0.0f;
-        tw[len - 1] = v1 ? c1[len] : 0.0f;
+        ta[len] = *(v3 ? a3 + (p0 - len) : nowhere);
+        tz[len - 1] = *(v3 ? c3 + (p0 - len + delta) : nowhere);
+        tw[len - 1] = *(v1 ? c1 + len : nowhere);
+      }
+      // the next tile: one atomic per wavefront.  Its answer is waited for on the spot (the compiler's doing), so it
+      // is asked for here, where that wait is the wait for the terms
+      if (lane == 0) nt = atomicAdd(a.next_work, 1ull);
+      if (!v0) ta[0] = 0.0f;
+#pragma unroll
+      for (int len = 1; len <= kFD; len++) {
+        const bool v3 = live && len < t3 && len <= lend, v1 = live && len < t1 && len <= lend;
+        if (!v3) ta[len] = tz[len - 1] = 0.0f;
+        if (!v1) tw[len - 1] = 0.0f;
       }
 #pragma unroll
       for (int len = 1; len <= kFD; len++) {
@@ -429,6 +444,7 @@ __global__ __launch_bounds__(64 * kFWaves) void k_gapped_front(GapArgs a, FrontA
       }
       int total;
       int base = wave_excl_scan(cnt, lane, total);
+      FP_COUNT(31, total > kFCells || pool_used + total > kFPool); // steps that outgrow the cell list or the pool
       if (total > kFCells || pool_used + total > kFPool) { // (next to never: 64 directions with 4+ cells each on two anti-diagonals, or 13+ each so far)
         if (base + cnt > kFCells || pool_used + base + cnt > kFPool) {
           dead = true;
@@ -478,10 +494,16 @@ __global__ __launch_bounds__(64 * kFWaves) void k_gapped_front(GapArgs a, FrontA
           edc = A.ed[cj - 1][dl];
         }
         const int nscan = has ? nrecb : 0;
-        for (int k = 0; __ballot(k < nscan) != 0; k += 2) { // (two records per turn: their reads are in flight together)
-          const uint32_t v0 = S.info[k][dl], v1 = S.info[k + 1 < kFR ? k + 1 : k][dl];
-          if (k < nscan && FRec::i(v0) < ci && FRec::j(v0) < cj) qmask |= 1u << k;
-          if (k + 1 < nscan && FRec::i(v1) < ci && FRec::j(v1) < cj) qmask |= 2u << k;
+        FP_COUNT(27, __popcll(__ballot(nscan > kFScan)));     // cells whose scan takes a second batch
+        FP_COUNT(28, __popcll(__ballot(nscan > 2 * kFScan))); // ... a third one
+        FP_COUNT(29, __popcll(__ballot(nscan == kFR - 1)));   // ... of a direction with one record's room left
+        for (int k = 0; __ballot(k < nscan) != 0; k += kFScan) { // (a batch of records per turn: their reads are in flight together)
+          uint32_t v[kFScan];
+#pragma unroll
+          for (int u = 0; u < kFScan; u++) v[u] = S.info[k + u < kFR ? k + u : kFR - 1][dl];
+#pragma unroll
+          for (int u = 0; u < kFScan; u++)
+            if (k + u < nscan && FRec::i(v[u]) < ci && FRec::j(v[u]) < cj) qmask |= 1u << (k + u);
         }
         const uint32_t cdw = (uint32_t)ci | ((uint32_t)cj << 5) | ((uint32_t)ctype << 10) | ((uint32_t)nq << 13) | ((uint32_t)nd << 16) |
                              ((uint32_t)dl << 19);
@@ -537,6 +559,7 @@ __global__ __launch_bounds__(64 * kFWaves) void k_gapped_front(GapArgs a, FrontA
           // (the start cell is a candidate of every cell, so there is a best one; its type is what the cell stores)
           const int ptype = FRec::type(S.info[bk][dl]);
           S.hyb[pool] = bte;
+          FP_COUNT(30, __popcll(__ballot(wobble(ptype)))); // cells behind a wobble pair
           if (ptype != 0) atomicOr(&S.wfp[isB][dl], (wobble(ptype) ? 0x10001u : 1u) << (ci - 1)); // (a cell has 1 <= i <= 16)
           const double ie = eqc + edc + bte;
           const double min_e = S.hyb[dl]; // the hit's energy (the start cell's entry): nothing has improved on it so far
