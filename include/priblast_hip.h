@@ -60,9 +60,12 @@ typedef struct prb_ris_opts {
   int32_t output_style;       /* -s 0  */
   int32_t distinct_sites;     /* -u: 0 = every final hit (the default), 1 = the distinct sites of each pair only, see below;
                                * anything else is PRB_ERR_ARG.  Ignored for last_stage 1 and 2 */
+  int32_t chain_sites;        /* -j: 0 = every final hit (the default), 1 = each pair's best co-linear chain of sites only, see
+                               * below; anything else, and 1 together with distinct_sites = 1, is PRB_ERR_ARG.  Ignored for
+                               * last_stage 1 and 2.  (It takes what used to be the struct's tail padding.) */
 } prb_ris_opts;
 #ifdef __cplusplus
-static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: nine fields, distinct_sites the last one");
+static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: ten fields, chain_sites the last one, no tail padding");
 #endif
 
 /* POD form of hit.hpp:38-118 (`Hit`) */
@@ -89,6 +92,30 @@ static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: nine fields, distinct_s
  * A top-N pair table, a top-N hit table and a profile table each hold pages searched with one value of distinct_sites:
  * prb_search_page_top / _tophits / _profile refuse a second value (PRB_ERR_ARG, the table untouched), and the three
  * prb_*_merge refuse two tables of different values unless one of them has merged no page. */
+/* ---- best co-linear chain of sites (opts->chain_sites = 1, `ris -j`) ----
+ * Neither the plain list nor the distinct sites say which sites of a pair can bind AT THE SAME TIME: the former holds
+ * copies shifted by a few bases, the latter keeps sites that cross - two duplexes in an order that no single
+ * arrangement of the two strands allows.  With chain_sites the final hits of every pair are thinned, at the same point
+ * as for distinct_sites, to the set of sites that increases in both coordinates and has the lowest summed energy:
+ *   pair, extent, output order   as above.  db_sp is a coordinate of the page's reversed text, so both coordinates grow
+ *              along a duplex
+ *   precedes   hit i PRECEDES hit j when q_sp[i] + q_len[i] - 1 < q_sp[j] and db_sp[i] + db_len[i] - 1 < db_sp[j]: both
+ *              gaps are strict, the two extents share no row and no column
+ *   score      S(j) = P(j) + e_tot[j], in double.  P(j) = S(i*) of the chosen predecessor, or 0.0 when none is taken.
+ *              i* is the hit of lowest S among the hits that precede j, doubles compared with -0.0 == +0.0, equal
+ *              values going to the lowest place in the list; it is taken only if S(i*) < 0.0
+ *   chain      ends at the hit of lowest S (equal values: the lowest place); its members are found by following the
+ *              chosen predecessors back.  They are kept, every other hit of the pair is dropped.  Kept hits stay in
+ *              output order
+ * The search's list is sorted by db_sp inside a pair, so a hit's predecessors come before it and the chain's order is the
+ * output order: over the kept hits, prb_pair_summary.e_sum (the left-to-right sum) is bit for bit the chain's score S,
+ * and .hits its length.  Every pair keeps at least one hit; a hit with e_tot >= 0 is never chained onto and never
+ * extended - it is kept only as the one hit of its pair's chain.  As for distinct_sites: a kept hit is the plain search's hit field
+ * for field and base pair for base pair (only bp_offset may differ), the result depends neither on PRB_BATCH,
+ * PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS, PRB_SPLIT, PRB_DEVICES nor on page residency, every mode takes the thinned
+ * list, counts[2] stays the number of final hits BEFORE the selection, and each of the five result tables holds pages of
+ * one value of chain_sites (a second one is PRB_ERR_ARG with the field's name, the table untouched; prb_*_merge refuse
+ * two tables of different values unless one has merged no page). */
 
 typedef struct prb_hit {
   int32_t q_sp, db_sp;          /* start in the query / in the page's reversed db text */
@@ -133,6 +160,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "distinct" (opts->distinct_sites: the pairs' head flags, the two selection kernels and the selection of the kept hits,
  *   launches = 4 per sub-batch with final hits, and 2 more - the gathers of the records and of their pre-gapped
  *   indices - when a hit is dropped; nothing when the option is off; prb_distinct_sites: launches = 3);
+ * "chain" (opts->chain_sites: the same count of launches for the chain selection - head flags, its two kernels, the
+ *   selection of the kept hits, and the two gathers when a hit is dropped; prb_chain_sites: launches = 3);
  * "coverage" (prb_search_page_coverage and prb_covset_add_hits: the merge into the per-target coverage table - keys and
  *   places, the sort by (query, span start), the spans' ends, their running maximum, the difference arrays, and four
  *   launches for the best hits: minimum energy, minimum tie, take-over, scratch reset; launches = 9 per sub-batch with
@@ -223,6 +252,11 @@ void prb_hitset_free(prb_hitset *hs);
  * is a maximal run of consecutive records with equal (query, db_id); the order inside a run is e_tot, then the index.
  * The runs need not be sorted by db_sp.  n <= 2^31 - 1; n = 0 does nothing. */
 int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep);
+/* The selection of opts->chain_sites for a caller's own list, likewise: keep[i] = 1 for the members of their pair's best
+ * chain, else 0.  A pair is a maximal run of consecutive records with equal (query, db_id).  Inside a run db_sp must not
+ * decrease (the search's order: a hit's predecessors then come before it); a record that breaks this is PRB_ERR_ARG
+ * with its index in the message, and nothing is computed.  n <= 2^31 - 1; n = 0 does nothing. */
+int prb_chain_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep);
 
 /* Diagnostics: a caller's list of hit records, in any order, through the sort and the redundancy filter that every
  * search runs behind its ungapped and its gapped stage (the same code, with the PRB_SORT_* / PRB_FILTER_TILES switches

@@ -22,7 +22,7 @@ P = ctypes.POINTER
 class RisOpts(ctypes.Structure):
     _fields_ = [("max_seed_length", c_i32), ("hybrid_threshold", c_dbl), ("interaction_threshold", c_dbl),
                 ("final_threshold", c_dbl), ("drop_out_wo_gap", c_i32), ("drop_out_w_gap", c_i32),
-                ("min_helix_length", c_i32), ("output_style", c_i32), ("distinct_sites", c_i32)]
+                ("min_helix_length", c_i32), ("output_style", c_i32), ("distinct_sites", c_i32), ("chain_sites", c_i32)]
 
 
 class Hit(ctypes.Structure):
@@ -119,6 +119,7 @@ SYMBOLS = {
     "prb_hitset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_hitset_free": (None, [ctypes.c_void_p]),
     "prb_distinct_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "prb_chain_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "prb_sort_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_dbl, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p]),
     "prb_search_page_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts),
@@ -455,6 +456,16 @@ def distinct_sites(ctx, hits):
     keep = np.zeros(len(hits), np.uint8)
     _check(lib().prb_distinct_sites(ctx.h, hits.ctypes.data if len(hits) else None, len(hits),
                                     keep.ctypes.data if len(hits) else None))
+    return keep
+
+
+def chain_sites(ctx, hits):
+    """prb_chain_sites: hits = structured array HIT_DTYPE (a caller's list of final hits, db_sp not decreasing inside a run
+    of equal (query, db_id)) -> uint8 [n], 1 for the hits of their run's best co-linear chain (opts.chain_sites)"""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    keep = np.zeros(len(hits), np.uint8)
+    _check(lib().prb_chain_sites(ctx.h, hits.ctypes.data if len(hits) else None, len(hits),
+                                 keep.ctypes.data if len(hits) else None))
     return keep
 
 

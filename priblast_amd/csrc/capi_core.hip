@@ -99,6 +99,7 @@ void prb_ris_opts_default(prb_ris_opts *o) {
   o->min_helix_length = 3;
   o->output_style = 0;
   o->distinct_sites = 0;
+  o->chain_sites = 0;
 }
 
 int prb_search_const_upload(prb_ctx *ctx); // capi_pages.hip
@@ -245,6 +246,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->distinct_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "chain") == 0) {
+    if (ms) *ms = ctx->chain_timer.ms;
+    if (launches) *launches = ctx->chain_timer.launches;
+    return PRB_OK;
+  }
   if (std::strcmp(stage, "coverage") == 0) {
     if (ms) *ms = ctx->coverage_timer.ms;
     if (launches) *launches = ctx->coverage_timer.launches;
@@ -264,6 +270,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
     ctx->tophits_timer = prb::StageTimer{};
     ctx->targets_timer = prb::StageTimer{};
     ctx->distinct_timer = prb::StageTimer{};
+    ctx->chain_timer = prb::StageTimer{};
     ctx->coverage_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }

@@ -37,6 +37,7 @@ struct SearchKnobs {
   bool trace_no_long, trace_no_slots; // testing: no long traces; re-extend every final hit as well
   int trace_long_cap, trace_slot_cap; // testing: pretend the slots are shorter
   int distinct_lds_hits; // testing: the LDS capacity of the distinct-sites selection (runs beyond it keep their state in HBM)
+  int chain_lds_hits;    // testing: the same for the chain selection (PRB_CHAIN_LDS_HITS)
   bool debug_rows, debug_mem;
 };
 static bool env_off(const char *e) { return e && atoi(e) == 0; }
@@ -86,6 +87,8 @@ static SearchKnobs read_search_knobs() {
   k.trace_slot_cap = e ? std::min(kTraceCap, atoi(e)) : kTraceCap;
   e = getenv("PRB_DISTINCT_LDS_HITS");
   k.distinct_lds_hits = e ? atoi(e) : kSiteLdsHits;
+  e = getenv("PRB_CHAIN_LDS_HITS");
+  k.chain_lds_hits = e ? atoi(e) : kChainLdsHits;
   k.debug_rows = getenv("PRB_DEBUG_ROWS") != nullptr;
   k.debug_mem = getenv("PRB_DEBUG_MEM") != nullptr;
   return k;
@@ -1077,43 +1080,57 @@ static int final_sort_filter(SubSearch &s) {
   return PRB_OK;
 }
 
-// ------------------------------------------------------------------------- distinct sites
-// The selection of opts.distinct_sites over the n hits of `h` (sorted, or a caller's list): keep flags in w.keep.  The
-// scratch is what the redundancy filter has left behind (w.endKey, w.pmax, w.state) and a list of the gapped cascade.
-static int select_sites(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, int lds_hits) {
+// ------------------------------------------------------------------------- distinct sites, best chain
+// The two selections inside the (query, db_id) runs of a final list (include/priblast_hip.h): what tells them apart
+enum class SiteRule { kDistinct, kChain };
+static const char *rule_name(SiteRule rule) { return rule == SiteRule::kChain ? "chain sites" : "distinct sites"; }
+static StageTimer &rule_timer(prb_ctx *ctx, SiteRule rule) { return rule == SiteRule::kChain ? ctx->chain_timer : ctx->distinct_timer; }
+
+// The selection of opts.distinct_sites / opts.chain_sites over the n hits of `h` (sorted, or a caller's list): keep flags
+// in w.keep.  The scratch is what the redundancy filter has left behind (w.endKey, w.pmax, w.state) and a list of the
+// gapped cascade.
+static int select_sites(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, SiteRule rule, const SearchKnobs &k) {
   const size_t N = (size_t)n;
+  const bool chain = rule == SiteRule::kChain;
   int rc;
   if (n > INT32_MAX) {
-    set_error("distinct sites: more than 2^31 - 1 final hits in one list");
+    set_error(std::string(rule_name(rule)) + ": more than 2^31 - 1 final hits in one list");
     return PRB_ERR_ARG;
   }
-  if ((rc = w.pairHead.ensure(N)) || (rc = w.keep.ensure(N)) || (rc = w.state.ensure(N)) || (rc = w.endKey.ensure(N * 4)) ||
+  if ((rc = w.pairHead.ensure(N)) || (rc = w.keep.ensure(N)) || (rc = w.state.ensure(N)) || (rc = w.endKey.ensure(N * (chain ? 8 : 4))) ||
       (rc = w.pmax.ensure(N * 4)) || (rc = w.listA.ensure((size_t)site_long_runs_max(n) * 4)) || (rc = w.pending.ensure(16)))
     return rc;
   PRB_HIP(launch_pair_heads(h.query, h.db_id, n, w.pairHead.as<uint8_t>(), ctx->stream));
-  const SiteScratch scratch{w.listA.as<uint32_t>(), w.pending.as<uint32_t>(), w.endKey.as<int32_t>(), w.pmax.as<int32_t>(), w.state.as<uint8_t>()};
-  PRB_HIP(launch_site_select(h, n, w.pairHead.as<uint8_t>(), lds_hits, scratch, w.keep.as<uint8_t>(), ctx->stream));
+  if (chain) {
+    const ChainScratch scratch{w.listA.as<uint32_t>(), w.pending.as<uint32_t>(), w.endKey.as<double>(), w.pmax.as<int32_t>()};
+    PRB_HIP(launch_chain_select(h, n, w.pairHead.as<uint8_t>(), k.chain_lds_hits, scratch, w.keep.as<uint8_t>(), ctx->stream));
+  } else {
+    const SiteScratch scratch{w.listA.as<uint32_t>(), w.pending.as<uint32_t>(), w.endKey.as<int32_t>(), w.pmax.as<int32_t>(), w.state.as<uint8_t>()};
+    PRB_HIP(launch_site_select(h, n, w.pairHead.as<uint8_t>(), k.distinct_lds_hits, scratch, w.keep.as<uint8_t>(), ctx->stream));
+  }
   return PRB_OK;
 }
 
-// opts.distinct_sites: the final hits F thinned to the distinct sites of each pair (include/priblast_hip.h), before the
-// traceback - the last stage that touches every final hit - so that a dropped hit costs no traceback, no copy and no
-// formatting.  F and w.subset (the pre-gapped indices the traceback and the `first` flags go by) are compacted alike, s.nfin
-// becomes the number kept; everything behind works on that list unchanged.  (counts[2] was taken before.)
-static int distinct_sites(SubSearch &s) {
+// opts.distinct_sites / opts.chain_sites: the final hits F thinned to what the rule keeps of each pair
+// (include/priblast_hip.h), before the traceback - the last stage that touches every final hit - so that a dropped hit
+// costs no traceback, no copy and no formatting.  F and w.subset (the pre-gapped indices the traceback and the `first`
+// flags go by) are compacted alike, s.nfin becomes the number kept; everything behind works on that list unchanged.
+// (counts[2] was taken before.)
+static int thin_sites(SubSearch &s, SiteRule rule) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
+  StageTimer &timer = rule_timer(ctx, rule);
   int rc;
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = select_sites(ctx, w, s.F, s.nfin, s.k.distinct_lds_hits))) return rc;
+  if ((rc = select_sites(ctx, w, s.F, s.nfin, rule, s.k))) return rc;
   int64_t nkeep = 0;
   if ((rc = w.surv.ensure((size_t)s.nfin * 4)) || (rc = w.count.ensure(16))) return rc;
   if ((rc = select_flagged(ctx, w, nullptr, w.keep.as<uint8_t>(), w.surv.as<uint32_t>(), (size_t)s.nfin, &nkeep))) return rc;
-  if (nkeep <= 0 || nkeep > s.nfin) { // (the best hit of every pair is kept)
-    set_error("distinct sites: " + std::to_string(nkeep) + " of " + std::to_string(s.nfin) + " final hits kept");
+  if (nkeep <= 0 || nkeep > s.nfin) { // (every pair keeps a hit)
+    set_error(std::string(rule_name(rule)) + ": " + std::to_string(nkeep) + " of " + std::to_string(s.nfin) + " final hits kept");
     return PRB_ERR_STATE;
   }
-  if (nkeep == s.nfin) return ctx->time_end(ctx->distinct_timer, 4);
+  if (nkeep == s.nfin) return ctx->time_end(timer, 4);
   if ((rc = w.hitsTmp.ensure(hits_bytes(nkeep))) || (rc = w.subset2.ensure((size_t)nkeep * 4))) return rc;
   const HitSoA kept = carve_hits(w.hitsTmp, nkeep);
   PRB_HIP(launch_gather_hits(s.F, w.surv.as<uint32_t>(), kept, nkeep, ctx->stream));
@@ -1121,8 +1138,10 @@ static int distinct_sites(SubSearch &s) {
   std::swap(w.subset, w.subset2);
   s.F = kept;
   s.nfin = nkeep;
-  return ctx->time_end(ctx->distinct_timer, 6);
+  return ctx->time_end(timer, 6);
 }
+static int distinct_sites(SubSearch &s) { return thin_sites(s, SiteRule::kDistinct); }
+static int chain_sites(SubSearch &s) { return thin_sites(s, SiteRule::kChain); }
 
 // ------------------------------------------------------------------------- traceback
 // Base pairs of the final hits: from the trace slots of the extension pass; the few hits the slots cannot describe
@@ -1459,6 +1478,7 @@ static int search_range(const PageSearch &p, const CandBatch &b, const std::func
   if ((rc = final_sort_filter(s))) return rc;
   if (s.nfin == 0) return PRB_OK;
   if (s.opts.distinct_sites && (rc = distinct_sites(s))) return rc;
+  if (s.opts.chain_sites && (rc = chain_sites(s))) return rc;
   if ((rc = traceback(s))) return rc;
   return emit_final(s);
 }
@@ -1487,6 +1507,14 @@ int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, 
   }
   if (opts->distinct_sites != 0 && opts->distinct_sites != 1) {
     set_error(std::string(fn) + ": distinct_sites must be 0 or 1 (got " + std::to_string(opts->distinct_sites) + ")");
+    return PRB_ERR_ARG;
+  }
+  if (opts->chain_sites != 0 && opts->chain_sites != 1) {
+    set_error(std::string(fn) + ": chain_sites must be 0 or 1 (got " + std::to_string(opts->chain_sites) + ")");
+    return PRB_ERR_ARG;
+  }
+  if (opts->chain_sites && opts->distinct_sites) {
+    set_error(std::string(fn) + ": chain_sites and distinct_sites can't both be 1 (each of them selects among every final hit of a pair)");
     return PRB_ERR_ARG;
   }
   return PRB_OK;
@@ -1713,18 +1741,25 @@ int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, cons
   return search_page(ctx, qb, db, page, opts, last_stage, SearchMode::kRecords, out);
 }
 
-// the caller's records as a list of the search's own layout (the fields the selection reads; the others stay zero), one
-// upload; the flags come back in one copy
-int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep) {
+// prb_distinct_sites / prb_chain_sites: the caller's records as a list of the search's own layout (the fields the
+// selections read; the others stay zero), one upload; the flags come back in one copy
+static int select_callers_sites(const char *fn_name, prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep, prb::SiteRule rule) {
+  const std::string fn = fn_name;
   if (!ctx || n < 0 || (n > 0 && (!hits || !keep))) {
-    set_error("prb_distinct_sites: bad argument");
+    set_error(fn + ": bad argument");
     return PRB_ERR_ARG;
   }
   if (n == 0) return PRB_OK;
   if (n > INT32_MAX) {
-    set_error("prb_distinct_sites: more than 2^31 - 1 hits");
+    set_error(fn + ": more than 2^31 - 1 hits");
     return PRB_ERR_ARG;
   }
+  if (rule == prb::SiteRule::kChain) // the pass in list order needs every predecessor before its successors
+    for (int64_t i = 1; i < n; i++)
+      if (hits[i].query == hits[i - 1].query && hits[i].db_id == hits[i - 1].db_id && hits[i].db_sp < hits[i - 1].db_sp) {
+        set_error(fn + ": hit " + std::to_string(i) + " has a lower db_sp than the hit before it in its run of equal (query, db_id)");
+        return PRB_ERR_ARG;
+      }
   PRB_HIP(hipSetDevice(ctx->device));
   SearchWs &w = ws_of(ctx);
   const SearchKnobs knobs = read_search_knobs();
@@ -1745,15 +1780,21 @@ int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *ke
     PRB_HIP(hipMemcpyAsync(w.hitsTmp.p, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
     PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the copy is staged, `host` may go)
   } catch (const std::exception &e) {
-    set_error(std::string("prb_distinct_sites: ") + e.what());
+    set_error(fn + ": " + e.what());
     return PRB_ERR_NOMEM;
   }
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = select_sites(ctx, w, carve_hits(w.hitsTmp, n), n, knobs.distinct_lds_hits))) return rc;
-  if ((rc = ctx->time_end(ctx->distinct_timer, 3))) return rc;
+  if ((rc = select_sites(ctx, w, carve_hits(w.hitsTmp, n), n, rule, knobs))) return rc;
+  if ((rc = ctx->time_end(rule_timer(ctx, rule), 3))) return rc;
   PRB_HIP(hipMemcpyAsync(keep, w.keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream));
   return PRB_OK;
+}
+int prb_distinct_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep) {
+  return select_callers_sites("prb_distinct_sites", ctx, hits, n, keep, prb::SiteRule::kDistinct);
+}
+int prb_chain_sites(prb_ctx *ctx, const prb_hit *hits, int64_t n, uint8_t *keep) {
+  return select_callers_sites("prb_chain_sites", ctx, hits, n, keep, prb::SiteRule::kChain);
 }
 
 // A caller's records through the search's own sort and redundancy filter (sort_hits, filter_hits: what

@@ -322,7 +322,7 @@ int prb_covset_add_hits(prb_ctx *ctx, prb_covset *cs, int32_t page, const int32_
     e_tot[(size_t)i] = x.e_tot;
     ends[4 * (size_t)i] = first[0], ends[4 * (size_t)i + 1] = first[1], ends[4 * (size_t)i + 2] = last[0], ends[4 * (size_t)i + 3] = last[1];
   }
-  if (int rc = run_table_guard(fn, "coverage", "prb_covset_finish", cs, ctx, cs->db, page, -1, query_ids, nq)) return rc;
+  if (int rc = run_table_guard(fn, "coverage", "prb_covset_finish", cs, ctx, cs->db, page, -1, -1, query_ids, nq)) return rc;
   if (!nhits) return PRB_OK;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));

@@ -57,6 +57,21 @@ inline int finish_guard(const char *fn_name, const char *what, const prb_ctx *ct
   return PRB_OK;
 }
 
+// ---- one selection per table
+// A table holds pages of one selection: why pages searched with (distinct_sites, chain_sites) = (distinct, chain) do
+// not go with the ones `t` holds, or "" (a value below 0: none yet, or the call has no options).  The message names the
+// field; `holds` = "holds" or "hold", other_open / other_close = what stands around the second value.
+inline std::string selection_clash(const std::string &tables, const char *holds, const TableState *t, int32_t distinct, int32_t chain,
+                                   const char *other_open, const char *other_close) {
+  if (t->distinct >= 0 && distinct >= 0 && distinct != t->distinct)
+    return "the " + tables + " " + holds + " pages searched with distinct_sites " + std::to_string(t->distinct) + other_open +
+           std::to_string(distinct) + other_close;
+  if (t->chain >= 0 && chain >= 0 && chain != t->chain)
+    return "the " + tables + " " + holds + " pages searched with chain_sites " + std::to_string(t->chain) + other_open + std::to_string(chain) +
+           other_close;
+  return "";
+}
+
 // ---- prb_search_page_top / _profile / _tophits: a page searched and merged into a batch table
 // Page `page` searched in `mode` and merged into the table `t`, finished by `finish_fn`
 inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb,
@@ -70,9 +85,8 @@ inline int merge_page(const char *fn_name, const char *what, const char *finish_
   if (t->db && t->db != db) return refuse(fn, "the " + table + " holds pages of another database");
   if (t->broken) return refuse(fn, "an earlier merge into this " + table + " failed", PRB_ERR_STATE);
   if (t->finished) return refuse(fn, "the " + table + " is finished (" + finish_fn + ")", PRB_ERR_STATE);
-  if (t->distinct >= 0 && opts->distinct_sites != t->distinct)
-    return refuse(fn, "the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
-                          std::to_string(opts->distinct_sites) + ")");
+  if (const std::string why = selection_clash(table, "holds", t, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
+    return refuse(fn, why);
   if (!t->db) {
     t->db = db;
     t->merged.assign(db->pages.size(), 0);
@@ -87,22 +101,21 @@ inline int merge_page(const char *fn_name, const char *what, const char *finish_
   }
   for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
   t->distinct = opts->distinct_sites;
+  t->chain = opts->chain_sites;
   delete hs;
   return PRB_OK;
 }
 
 // ---- prb_search_page_targets / _coverage / prb_covset_add_hits: a batch merged into a run table
 // What is checked of the run table `t`, finished by `finish_fn`, before a batch of nq queries named query_ids is merged
-// into it for `page` (distinct < 0: the call has no options).  A call that passes has its identifiers marked as merged.
+// into it for `page` (distinct, chain < 0: the call has no options).  A call that passes has its identifiers marked as merged.
 inline int run_table_guard(const std::string &fn, const char *what, const char *finish_fn, RunTable *t, const prb_ctx *ctx, const prb_db *db,
-                           int32_t page, int32_t distinct, const int32_t *query_ids, int32_t nq) {
+                           int32_t page, int32_t distinct, int32_t chain, const int32_t *query_ids, int32_t nq) {
   const std::string table = std::string(what) + " table";
   if (t->ctx != ctx || t->db != db) return refuse(fn, "the " + table + " was made with another context or for another database");
   if (t->broken) return refuse(fn, "an earlier merge into this " + table + " failed", PRB_ERR_STATE);
   if (t->finished) return refuse(fn, "the " + table + " is finished (" + finish_fn + ")", PRB_ERR_STATE);
-  if (t->distinct >= 0 && distinct >= 0 && distinct != t->distinct)
-    return refuse(fn, "the " + table + " holds pages searched with distinct_sites " + std::to_string(t->distinct) + " (this call: " +
-                          std::to_string(distinct) + ")");
+  if (const std::string why = selection_clash(table, "holds", t, distinct, chain, " (this call: ", ")"); !why.empty()) return refuse(fn, why);
   try {
     std::vector<int32_t> sorted(query_ids, query_ids + nq);
     std::sort(sorted.begin(), sorted.end());
@@ -131,7 +144,7 @@ inline int merge_run_page(const char *fn_name, const char *what, const char *fin
                           prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids) {
   if (!t || !query_ids) return refuse(fn_name, "bad argument");
   if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
-  if (int rc = run_table_guard(fn_name, what, finish_fn, t, ctx, db, page, opts->distinct_sites, query_ids, qb->nq)) return rc;
+  if (int rc = run_table_guard(fn_name, what, finish_fn, t, ctx, db, page, opts->distinct_sites, opts->chain_sites, query_ids, qb->nq)) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
   t->broken = true; // (until the merge is whole)
   int rc;
@@ -140,6 +153,7 @@ inline int merge_run_page(const char *fn_name, const char *what, const char *fin
   if ((rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t))) return rc;
   for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
   t->distinct = opts->distinct_sites;
+  t->chain = opts->chain_sites;
   t->broken = false;
   delete hs;
   return PRB_OK;
@@ -147,7 +161,7 @@ inline int merge_run_page(const char *fn_name, const char *what, const char *fin
 
 // ---- prb_*_merge: two unfinished tables over disjoint page or (page, identifier) sets into one
 // What all five check first: `dst` belongs to ctx, both are unfinished and whole, own() has no refusal of the table's
-// own ("" = none; asked once both are known to be whole and unfinished), and both were searched with one distinct_sites
+// own ("" = none; asked once both are known to be whole and unfinished), and both were searched with one distinct_sites and one chain_sites
 template <class Own>
 int merge_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *dst, const TableState *src, Own own) {
   const std::string tables = std::string(what) + " tables";
@@ -156,9 +170,8 @@ int merge_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const
   if (dst->broken || src->broken) return refuse(fn_name, "an earlier merge into one of the " + tables + " failed");
   if (dst->finished || src->finished) return refuse(fn_name, "one of the " + tables + " is finished");
   if (const std::string why = own(); !why.empty()) return refuse(fn_name, why);
-  if (dst->distinct >= 0 && src->distinct >= 0 && dst->distinct != src->distinct)
-    return refuse(fn_name, "the " + tables + " hold pages searched with distinct_sites " + std::to_string(dst->distinct) + " and " +
-                               std::to_string(src->distinct));
+  if (const std::string why = selection_clash(tables, "hold", dst, src->distinct, src->chain, " and ", ""); !why.empty())
+    return refuse(fn_name, why);
   return PRB_OK;
 }
 // ... of two batch tables: made for the same queries, and no page is in both
@@ -197,14 +210,15 @@ int run_tables_guard(const char *fn_name, const char *what, const prb_ctx *ctx, 
   return PRB_OK;
 }
 
-// after the merge: dst's counts are the sums and its distinct_sites the merged pages'; src has merged nothing
+// after the merge: dst's counts are the sums and its distinct_sites / chain_sites the merged pages'; src has merged nothing
 inline void move_counts(TableState *dst, TableState *src) {
   for (int i = 0; i < 3; i++) {
     dst->counts[i] += src->counts[i];
     src->counts[i] = 0;
   }
   if (dst->distinct < 0) dst->distinct = src->distinct;
-  src->distinct = -1;
+  if (dst->chain < 0) dst->chain = src->chain;
+  src->distinct = src->chain = -1;
 }
 // ... and dst's page set is the union
 inline void move_merged(MergeTable *dst, MergeTable *src) {

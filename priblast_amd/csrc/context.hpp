@@ -66,6 +66,7 @@ struct prb_ctx {
   prb::StageTimer tophits_timer; // the merge of prb_search_page_tophits (stage "tophits"), likewise
   prb::StageTimer targets_timer; // the merges of prb_search_page_targets and prb_targetset_merge (stage "targets"), likewise
   prb::StageTimer distinct_timer; // the selection of opts->distinct_sites (stage "distinct"), likewise
+  prb::StageTimer chain_timer; // the selection of opts->chain_sites (stage "chain"), likewise
   prb::StageTimer coverage_timer; // the merges, the join and the finish of the coverage table (stage "coverage"), likewise
 
   int time_begin();

@@ -362,6 +362,7 @@ struct TableState {
   bool broken = false;         // a merge failed part way
   bool finished = false;       // prb_*_finish: the records are on the host, the device memory is released
   int32_t distinct = -1;       // opts->distinct_sites of the merged pages (-1: none yet)
+  int32_t chain = -1;          // opts->chain_sites of the merged pages, likewise
   int64_t counts[3] = {0, 0, 0};
   DevBuf table;                // the table proper, one block (every table says what it holds)
 };

@@ -327,6 +327,22 @@ struct SiteScratch {
 };
 hipError_t launch_site_select(const HitSoA &h, int64_t n, const uint8_t *head, int lds_hits, const SiteScratch &w, uint8_t *keep,
                               hipStream_t s);
+// ---- best co-linear chain of sites (prb_ris_opts::chain_sites) over a final hit list sorted by db_sp inside its runs ----
+// keep[i] = 1 for the hits of their run's best chain (the dynamic programme of include/priblast_hip.h), 0 for the
+// others; head as above.  Two launches of the same shape as launch_site_select's: runs of up to 64 hits several per
+// wavefront, scores and predecessors in registers; the longer ones, listed in w.long_list, a workgroup each in tiles
+// of 64 hits - with rectangles, energies, scores and predecessors in LDS up to lds_hits hits (clamped to
+// 1 .. kChainLdsHits; below 64 it also lowers the first launch's limit), beyond that read from the list with scores and
+// predecessors in w.score / w.prev.  Nothing comes back to the host.  n <= INT32_MAX.
+constexpr int kChainLdsHits = 1536; // 36 bytes of LDS per hit
+struct ChainScratch {
+  uint32_t *long_list; // site_long_runs_max(n) entries
+  uint32_t *nlong;     // one counter
+  double *score;       // n entries
+  int32_t *prev;       // n entries
+};
+hipError_t launch_chain_select(const HitSoA &h, int64_t n, const uint8_t *head, int lds_hits, const ChainScratch &w, uint8_t *keep,
+                               hipStream_t s);
 
 // ============================================================================ table_kernels.hip: top-N tables
 // ---- top-N table (prb_search_page_top) ----

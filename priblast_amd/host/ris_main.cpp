@@ -33,7 +33,9 @@
 // first: a table on the GPU (prb_search_page_tophits) takes every page of a batch and keeps those hits with their base
 // pairs, and only they reach the host.  `-k` is refused with -t, -n, -q and in rank mode.  `ris -u` keeps only the distinct
 // interaction sites of each (query, target) pair - greedy non-maximum suppression on the GPU, before the traceback
-// (prb_ris_opts::distinct_sites) - and combines with every mode: each of them takes the thinned list.  `ris -r N` turns
+// (prb_ris_opts::distinct_sites) - and combines with every mode: each of them takes the thinned list.  `ris -j` keeps each
+// pair's best co-linear chain of sites instead - the sites that can bind at the same time, by a dynamic programme on the
+// GPU at the same point (prb_ris_opts::chain_sites); it combines like -u and is refused with it.  `ris -r N` turns
 // `-t -n` round: the `-t` lines of each TARGET's N pairs of lowest minimum energy over all the queries of the run.  Every
 // worker owns one table on its GPU for the whole run (prb_search_page_targets takes every page of every batch it
 // searches); at the end the first worker merges the others' into its own (prb_targetset_merge), and only N records per
@@ -43,9 +45,9 @@
 // database on its GPU for the whole run (prb_search_page_coverage takes every page of every batch it searches); at the
 // end the first worker merges the others' into its own (prb_covset_merge), the regions are reduced on the device
 // (prb_covset_finish) and only their records reach the host, written by page, target and start.  `-c` is refused with
-// -t, -n, -q, -k, -b, -r and in rank mode; -u combines.
+// -t, -n, -q, -k, -b, -r and in rank mode; -u and -j combine.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -r -c have one table (kSwitchTable) that every refusal is generated
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
 // join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
 // (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
@@ -126,15 +128,20 @@ void usage() {
             "              first (interaction energy, ties in output order), and a hit is kept only if its query range and\n"
             "              its target range do not both overlap those of a hit kept before it; the lines are lines of the\n"
             "              run without -u (with every other switch; -t, -n, -q and -k then count and rank the kept hits)\n"
+            "    -j        only the best co-linear chain of sites of each query-target pair: the hits that follow one\n"
+            "              another in the query and in the target without sharing a position of either, chosen for the lowest\n"
+            "              summed interaction energy (ties to the earlier hit in output order) - the sites that can bind at\n"
+            "              the same time; the lines are lines of the run without -j, and -t's hit count and summed energy are\n"
+            "              the chain's (with every switch that -u goes with; not with -u)\n"
             "    -r INT    the -t lines of only the INT queries of lowest minimum interaction energy per target (database\n"
             "              sequence) over all the queries, written at the end of the run by page, target and rank (ties by\n"
             "              the query's place in the input file; 1 <= INT <= 1024; not with -t, -n, -q, -k, -b, nor with\n"
-            "              WORLD_SIZE > 1; -u combines)\n"
+            "              WORLD_SIZE > 1; -u and -j combine)\n"
             "    -c INT    one line per region of a target (database sequence): a maximal run of its positions that final\n"
             "              hits of at least INT distinct queries cover, with the hits that begin in it, the deepest\n"
             "              coverage and where it peaks, the minimum interaction energy and its hit, written at the end of\n"
             "              the run by page, target and start (1 <= INT <= 1000000; not with -t, -n, -q, -k, -b, -r, nor with\n"
-            "              WORLD_SIZE > 1; -u combines)\n"
+            "              WORLD_SIZE > 1; -u and -j combine)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -164,7 +171,7 @@ enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCo
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kR, kC, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -180,6 +187,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'k', "the N best interaction sites per query", bit(kT) | bit(kN) | bit(kQ), -1, true},
     {'b', "binary hit records", 0, -1, false},
     {'u', "the distinct interaction sites of each pair", 0, -1, false},
+    {'j', "the best co-linear chain of sites of each pair", bit(kU), -1, false},
     {'r', "the N best queries per target", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB), -1, true},
     {'c', "the regions of each target bound by at least D queries", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR), -1, true},
 };
@@ -543,7 +551,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ur:c:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -561,6 +569,7 @@ Args parse_args(int argc, char **argv) {
     case 't': a.given[kT] = true; break;
     case 'q': a.given[kQ] = true; break;
     case 'u': a.given[kU] = true, a.o.distinct_sites = 1; break;
+    case 'j': a.given[kJ] = true, a.o.chain_sites = 1; break;
     case 'n': a.given[kN] = true, a.top = parse_count(optarg); break;
     case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
     case 'r': a.given[kR] = true, a.targets = parse_count(optarg); break;
