@@ -1,45 +1,21 @@
 // C ABI, part 3: the search of one page (SearchSeed / ExtendWithoutGap / ExtendWithGap,
 // rna_interaction_search.cpp:264-320).  search_page cuts a batch into sub-batches of queries; search_range takes one
-// sub-batch through the stages of DESIGN.md section 1, one function per stage over the sub-batch's state (SubSearch).
+// sub-batch through the stages of DESIGN.md section 1, one function per stage over the sub-batch's state (SubSearch,
+// search_stages.hpp).  The gapped stage's is in capi_gapped.hip.
 #include <omp.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 
-#include "search_host.hpp"
+#include "search_stages.hpp"
 
 using namespace prb;
 
 namespace prb {
 
 // ------------------------------------------------------------------------- knobs
-// The environment of a search, read once per prb_search_page* call (INTEGRATION.md has the table; most exist for the
-// tests, which compare the default path against the paths these select).  Not cached beyond the call: a process may
-// change its environment between two searches.
-struct SearchKnobs {
-  double budget;       // pairs per sub-batch
-  double chunk_pairs;  // pairs per chunk of candidates
-  int row_shift;       // rows / pairs in (query, database position >> row_shift) order, see k_row_key; -1 keeps suffix-array order
-  bool fused;          // seeds -> hits under -f in one pass (0: written as a list, extended and thinned in separate passes)
-  bool front_ahead;    // the front of the next sub-batch's seed path is issued while this one is extended
-  bool sort_four_keys, sort_two_lengths;
-  size_t big_list_bytes;  // a list behind -f beyond this takes the memory of stages already over (tests: every list)
-  int64_t gapped_chunk_hits;
-  int first_tier;      // the cascade starts at this kernel (4 = the wave-per-hit kernel alone), so the rarely taken kernels see every hit
-  bool wave_hbm, no_resume, front_paired, front, handover;
-  GapTierKnobs tiers;  // the experiments inside the LDS tiers (search_kernels.hpp)
-  bool filter_tiles;   // the redundancy filter scans windows of the list in LDS (0: the plain kernels)
-  int resume_cap;      // > 0, testing: pools that run out (those hits are redone instead)
-  int skip_tiers;      // experiment: bit t set = LDS tier t is left out behind the front kernel
-  bool trace_no_long, trace_no_slots; // testing: no long traces; re-extend every final hit as well
-  int trace_long_cap, trace_slot_cap; // testing: pretend the slots are shorter
-  int distinct_lds_hits; // testing: the LDS capacity of the distinct-sites selection (runs beyond it keep their state in HBM)
-  int chain_lds_hits;    // testing: the same for the chain selection (PRB_CHAIN_LDS_HITS)
-  bool debug_rows, debug_mem;
-};
 static bool env_off(const char *e) { return e && atoi(e) == 0; }
 static SearchKnobs read_search_knobs() {
   SearchKnobs k;
@@ -94,85 +70,8 @@ static SearchKnobs read_search_knobs() {
   return k;
 }
 
-// ------------------------------------------------------------------------- state
-// Field bounds of the hits of one sub-batch, for the one-key sort
-struct SortBounds {
-  int32_t qmin = 0, qspan = 1, max_qlen = 0, max_dblen = 0, nchars = 0;
-  int32_t eq_len_max = 0; // > 0: every hit of the list has q_len = db_len <= this (the one-pass seed path reports it)
-};
-
-// What the search of a page is given: the same for all its sub-batches
-struct PageSearch {
-  prb_ctx *ctx;
-  SearchWs &w;
-  const prb_qbatch *qb;
-  const DbPage &pg;
-  const PageDev &pd;
-  const SearchConst &sc;
-  const ExtOpts eo;
-  const prb_ris_opts &opts;
-  const SearchKnobs &k;
-  const int page, last_stage;
-  const SearchMode mode;
-  TableState *table; // the table of the mode, if it has one: each emit_* knows which
-  prb_hitset *hs;
-  int max_qlen;
-  int32_t max_dblen;
-};
-
-// the candidates of a sub-batch: queries [q0, q1), in page-locked memory, rows and query entries numbered from 0
-struct CandBatch {
-  int32_t q0 = 0, q1 = 0;
-  CandDev *cd = nullptr; // in query order, row0 / qoff filled in (each is rebased once, for its chunk)
-  int64_t ncand = 0, nrows = 0, nqent = 0;
-};
-
-// One sub-batch on its way through the stages: what it is given, then what each stage hands to the ones behind it.
-// (The lists themselves are in the workspace's buffers; the HitSoA views here say which.)
-struct SubSearch : PageSearch {
-  const CandBatch &b;
-  // called at most once, behind the LDS tiers of the gapped cascade (the front stage's buffers are long free by then): the
-  // caller's chance to issue the front of the NEXT sub-batch ahead (call_front_free)
-  const std::function<void()> &front_free;
-  bool front_called = false;
-  int32_t ncand = 0;
-  SortBounds sb;
-  // seeds_to_hits: nf hits under the -f threshold, as records in w.hitsB
-  int64_t nf = 0, one_pass_maxlen = 0;
-  bool all_one_pass = true; // every chunk through k_seed_extend: lengths known, q_len = db_len
-  // sort_filter_ungapped: the nung survivors
-  int64_t nung = 0;
-  // The gapped stage's view of the list: hits U -> G, `first` = their first-of-query flags, per-hit arrays indexed from
-  // 0.  That is the whole list (U in w.hitsA) - or, while the stage runs in chunks, the chunk at hand, and behind it the
-  // kept lists.  The traceback re-extends final hits through the same view.
-  HitSoA U, G;
-  const uint8_t *first = nullptr;
-  int64_t nch = 0;        // hits in the view while the cascade runs
-  bool chunked = false;
-  int64_t nmax = 0;       // what the per-hit buffers of the stage hold
-  int64_t ngap = 0;       // hits not above -g behind the stage, as records in w.hitsB (w.cidx: their indices in U)
-  LongTrace lt{};         // long traces of wave-kernel hits (search_kernels.hpp)
-  int32_t lt_used = 0;
-  // what the traceback reads per hit of U: the stage's own arrays, or the kept lists when it ran in chunks
-  const uint8_t *tier_all = nullptr;
-  const int32_t *ntrace_all = nullptr;
-  const uint16_t *trace_all = nullptr;
-  // final_sort_filter: the nfin final hits F (w.hitsB), w.subset = the index of each one's pre-gapped state in U
-  HitSoA F;
-  int64_t nfin = 0;
-  // traceback: base pairs in all (w.bpCount / w.bpOff / w.bpOut hold them per hit)
-  int64_t bp_total = 0;
-};
-
-static void call_front_free(SubSearch &s) {
-  if (s.front_free && !s.front_called) {
-    s.front_free();
-    s.front_called = true;
-  }
-}
-
-// ------------------------------------------------------------------------- lists of hits
-static HitSoA carve_hits(uint8_t *p, int64_t n) {
+// ------------------------------------------------------------------------- lists of hits (search_stages.hpp)
+HitSoA carve_hits(uint8_t *p, int64_t n) {
   HitSoA h;
   const size_t n8 = ((size_t)n + 1) & ~(size_t)1; // keep the double arrays 8-byte aligned
   h.e_acc = reinterpret_cast<double *>(p);
@@ -187,13 +86,6 @@ static HitSoA carve_hits(uint8_t *p, int64_t n) {
   h.db_id_start = ip + 5 * n8;
   h.query = ip + 6 * n8;
   return h;
-}
-static HitSoA carve_hits(DevBuf &b, int64_t n) { return carve_hits(b.as<uint8_t>(), n); }
-static size_t hits_bytes(int64_t n) { return (((size_t)n + 1) & ~(size_t)1) * kHitBytes + 64; }
-// the hits from `first` on, as a list of their own
-static HitSoA offset_hits(const HitSoA &h, int64_t first) {
-  return HitSoA{h.q_sp + first, h.db_sp + first, h.q_len + first, h.db_len + first, h.db_id + first, h.db_id_start + first,
-                h.query + first, h.e_acc + first, h.e_hyb + first, h.e_tot + first};
 }
 
 // the radix sorts of the tables' merges (search_host.hpp)
@@ -336,7 +228,7 @@ static void mem_note(const char *where, const SearchWs &w) {
 // `need` bytes in a buffer whose first `have` bytes are kept.  (Grown with room to spare while memory allows: every
 // growth is a copy of everything, and a list of 1e9 records - 64 GB - must still be able to grow next to its old copy.
 // `spare_limit`: beyond that only a sixth - what is spare here is missing in whatever comes behind.)
-static int grow_keep(prb_ctx *ctx, DevBuf &buf, size_t have, size_t need, size_t spare_limit = SIZE_MAX) {
+int grow_keep(prb_ctx *ctx, DevBuf &buf, size_t have, size_t need, size_t spare_limit) {
   int rc;
   if (have > 0 && need > buf.cap) {
     DevBuf bigger;
@@ -361,8 +253,8 @@ static int reserve_recs(prb_ctx *ctx, DevBuf &recbuf, int64_t have, int64_t more
 // it, see k_flag_not_above): recbuf <- the kept hits of `in`, in order, as records for the sort that
 // follows; idxbuf[i] = index in `in`.
 // `have` records already in recbuf are kept (the new ones are appended behind them).
-static int compact_below(prb_ctx *ctx, SearchWs &w, const HitSoA &in, int64_t n, double thr, DevBuf &idxbuf, DevBuf &recbuf,
-                         int64_t *m, int64_t have = 0) {
+int compact_below(prb_ctx *ctx, SearchWs &w, const HitSoA &in, int64_t n, double thr, DevBuf &idxbuf, DevBuf &recbuf, int64_t *m,
+                  int64_t have) {
   int rc;
   *m = 0;
   if (n == 0) return PRB_OK;
@@ -639,9 +531,9 @@ static int sort_filter_ungapped(SubSearch &s) {
     w.trim_next = true;
     PRB_HIP(hipStreamSynchronize(ctx->stream));
     w.front.release();
-    for (DevBuf *b : {&w.hitsA, &w.hitsTmp, &w.row_count, &w.row_off, &w.row_cand, &w.seed_qacc, &w.cands, &w.trace, &w.resumePool,
-                      &w.resumePool2, &w.resumePool3, &w.keptU, &w.keptTrace})
+    for (DevBuf *b : {&w.hitsA, &w.hitsTmp, &w.row_count, &w.row_off, &w.row_cand, &w.seed_qacc, &w.cands, &w.trace, &w.keptU, &w.keptTrace})
       b->release();
+    for (DevBuf &b : w.resumePool) b.release();
     // (and this context's Raccess workspace, up to 48 GB when it last took a large batch: its launches are over)
     for (DevBuf *b : {&ctx->ra_band, &ctx->ra_vec, &ctx->ra_codes, &ctx->ra_desc}) b->release();
     if ((rc = w.front.init())) return rc;
@@ -693,356 +585,6 @@ static int emit_ungapped(SubSearch &s) {
         h.bp_count++;
       }
   }
-  return PRB_OK;
-}
-
-// ------------------------------------------------------------------------- gapped extension
-// The cascade of kernels a hit goes through until one has the capacity for it: the front kernel (gapped_front.hip),
-// LDS tiers 0 and 1 (8 lanes per hit), tier 2 (16 lanes), tier 3 (a wavefront per hit), then the wave-per-hit kernel
-// with HBM scratch of any size.
-static const char *const kTierTimer[5] = {"gapped", "gapped_t1", "gapped_t2", "gapped_t3", "gapped_slow"};
-static const GapResume kNoResume{nullptr, nullptr, nullptr, 0};
-
-// The hits of the view that no kernel has completed yet, on their way down the cascade
-struct WorkList {
-  const uint32_t *cur = nullptr; // indices into U (nullptr: all of 0..m-1)
-  int64_t m = 0;
-  uint32_t *bufs[2];             // where the next, shorter list is written, in turns
-  int nb = 0;
-  uint32_t *spare() const { return bufs[nb]; }
-};
-// and what the cascade of one chunk carries along
-struct Cascade {
-  WorkList l;
-  GapResume rs[kLdsTiers - 1] = {kNoResume, kNoResume, kNoResume}; // rs[t] = the state dumps of the hits that outgrow tier t
-  int skip_mask = 0;
-};
-static_assert(kLdsTiers == 4, "one pool of state dumps per LDS tier but the last");
-
-static int scratch_for(SubSearch &s, int64_t n, int cap_diag, int cap_rec, GapScratch &gs) {
-  gs.cap_diag = cap_diag;
-  gs.cap_rec = cap_rec;
-  gs.bytes_per_thread = gapped_wave_scratch_bytes(cap_diag, cap_rec);
-  if (gs.bytes_per_thread <= kGapWaveLdsBytes && !s.k.wave_hbm) { // the state fits the LDS of a workgroup
-    gs.base = nullptr;
-    gs.nthreads = (int32_t)std::min<int64_t>(n, 4096);
-    return PRB_OK;
-  }
-  int64_t nw = std::min<int64_t>(n, 4096);
-  while (nw > 64 && (size_t)nw * gs.bytes_per_thread > ((size_t)4 << 30)) nw /= 2;
-  gs.nthreads = (int32_t)nw;
-  int r = s.w.gapScratch.ensure((size_t)nw * gs.bytes_per_thread);
-  gs.base = s.w.gapScratch.as<uint8_t>();
-  return r;
-}
-
-// next = the entries of the work list `cur` (nullptr: 0..m-1) whose overflow flag is set
-static int select_overflow(SubSearch &s, const uint32_t *cur, int64_t m, uint32_t *next, int64_t *mout) {
-  return select_flagged(s.ctx, s.w, cur, s.w.overflow.as<uint8_t>(), next, (size_t)m, mout);
-}
-// the same for the list of a cascade, which the selection then is
-static int advance(SubSearch &s, WorkList &l, int64_t *rest) {
-  if (int rc = select_overflow(s, l.cur, l.m, l.spare(), rest)) return rc;
-  l.cur = l.spare();
-  l.nb ^= 1;
-  return PRB_OK;
-}
-
-// Wave-per-hit kernel with its state in HBM scratch, for the device list `cur` (indices into U;
-// nullptr = all) of m hits.  mode 0 writes G and retries hits that still overflow with a 4x
-// larger scratch; mode 2 writes base pairs at off_dev (indexed by list position).
-// (long traces, search_kernels.hpp: not when the stage runs in chunks - the kept lists renumber the hits -, not for a
-// list that is every hit - PRB_GAPPED_FIRST_TIER=4 -; PRB_TRACE_NO_LONG / PRB_TRACE_LONG_CAP are for the tests)
-static int run_wave(SubSearch &s, int mode, const uint32_t *cur, int64_t m, uint32_t *spare, const int64_t *off_dev, int handover = 0) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  int rc;
-  const bool long_traces = mode == 0 && !s.chunked && m <= 65536 && !s.k.trace_no_long;
-  if (long_traces && cur == nullptr) { // (every hit, as a list)
-    if ((rc = w.slowList.ensure((size_t)m * 4))) return rc;
-    PRB_HIP(launch_iota_u32(w.slowList.as<uint32_t>(), m, ctx->stream));
-    cur = w.slowList.as<uint32_t>();
-  }
-  if (long_traces) {
-    const int32_t cap = s.k.trace_long_cap;
-    if (s.lt_used == 0) {
-      if ((rc = w.slowSlot.ensure((size_t)s.nmax * 4))) return rc;
-      PRB_HIP(hipMemsetAsync(w.slowSlot.p, 0xFF, (size_t)s.nmax * 4, ctx->stream));
-    }
-    const size_t have = (size_t)s.lt_used, need = have + (size_t)m;
-    if ((rc = grow_keep(ctx, w.slowCnt, have * 8, need * 8)) || (rc = grow_keep(ctx, w.slowTrace, have * 8 * cap, need * 8 * cap))) return rc;
-    PRB_HIP(hipMemsetAsync(w.slowCnt.as<int32_t>() + have * 2, 0xFF, (size_t)m * 8, ctx->stream));
-    PRB_HIP(launch_assign_slots(cur, m, s.lt_used, w.slowSlot.as<int32_t>(), ctx->stream));
-    s.lt_used += (int32_t)m;
-    s.lt = LongTrace{w.slowTrace.as<uint32_t>(), w.slowCnt.as<int32_t>(), w.slowSlot.as<int32_t>(), cap};
-  }
-  int cap_diag = 512, cap_rec = 2048;
-  if (mode != 0) { // caps known to suffice for every hit seen so far
-    cap_diag = std::max(512, ctx->max_gap_caps);
-    cap_rec = cap_diag * 4;
-  }
-  uint32_t *other = spare;
-  while (m > 0) {
-    GapScratch gs;
-    if ((rc = scratch_for(s, m, cap_diag, cap_rec, gs))) return rc;
-    PRB_HIP(launch_gapped_wave(s.U, s.G, m, cur, s.qb->view, s.pd, s.sc, s.eo, gs, mode, mode == 0 ? w.overflow.as<uint8_t>() : nullptr,
-                               mode == 0 ? w.tierOf.as<uint8_t>() : nullptr, s.first,
-                               mode == 0 ? w.ntrace.as<int32_t>() : nullptr, off_dev, w.bpOut.as<int32_t>(), ctx->stream, handover,
-                               mode == 0 ? s.lt : LongTrace{}));
-    if (mode != 0) break;
-    int64_t again = 0;
-    if ((rc = select_overflow(s, cur, m, other, &again))) return rc;
-    uint32_t *done_list = const_cast<uint32_t *>(cur);
-    cur = other;
-    other = done_list ? done_list : (other == w.listA.as<uint32_t>() ? w.listB.as<uint32_t>() : w.listA.as<uint32_t>());
-    m = again;
-    if (m == 0) break;
-    cap_diag *= 4;
-    cap_rec *= 4;
-    if (cap_diag > 32768) {
-      set_error("gapped extension exceeds the supported extension length (32768)");
-      return PRB_ERR_STATE;
-    }
-    ctx->max_gap_caps = std::max(ctx->max_gap_caps, cap_diag);
-  }
-  return PRB_OK;
-}
-// the whole list `l` through it, as the cascade's last kernel (the next sub-batch's front goes out first: these few,
-// longest extensions run nearly alone)
-static int run_slow(SubSearch &s, WorkList &l, int handover) {
-  int rc;
-  if (!handover) call_front_free(s);
-  if ((rc = s.ctx->time_begin())) return rc;
-  s.hs->slow_hits += l.m;
-  s.ctx->slow_hits += l.m;
-  if ((rc = run_wave(s, 0, l.cur, l.m, l.spare(), nullptr, handover))) return rc;
-  l.m = 0;
-  return s.ctx->time_end(kTierTimer[kWaveTier], 1);
-}
-
-// the front kernel on the list: what it completes leaves the list
-static int run_front(SubSearch &s, Cascade &c, bool second_only = false) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  WorkList &l = c.l;
-  int rc;
-  if ((rc = w.frontScratch.ensure(gapped_front_scratch_bytes()))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
-  PRB_HIP(launch_gapped_front(s.U, s.G, l.m, l.cur, s.qb->view, s.pd, s.sc, s.eo, 0, w.overflow.as<uint8_t>(), w.tierOf.as<uint8_t>(),
-                              w.ntrace.as<int32_t>(), w.count.as<unsigned long long>() + 1, w.frontScratch.p, ctx->stream,
-                              second_only && !s.k.front_paired));
-  int64_t rest = 0;
-  if ((rc = advance(s, l, &rest))) return rc;
-  if (s.k.debug_rows) fprintf(stderr, "[front] hits %lld, go on %lld\n", (long long)l.m, (long long)rest);
-  ctx->timers["gapped_front_hits"].launches += l.m - rest; // (a counter, not a time: hits completed by the front kernel)
-  l.m = rest;
-  return ctx->time_end("gapped_front", 1);
-}
-
-// the LDS tiers and the wavefront-per-hit kernel on the list, each taking what the one before it could not hold
-// (hold_wave: the list is handed back before the wavefront-per-hit kernel instead)
-static int run_cascade(SubSearch &s, Cascade &c, int handover, bool hold_wave) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  WorkList &l = c.l;
-  int rc;
-  for (int tier = s.k.first_tier; tier <= kWaveTier && l.m > 0; tier++) {
-    if (tier < kLdsTiers - 1 && ((c.skip_mask >> tier) & 1)) continue;
-    if (tier == kWaveTier) {
-      if (hold_wave) break;
-      if ((rc = run_slow(s, l, handover))) return rc;
-      continue;
-    }
-    if ((rc = ctx->time_begin())) return rc;
-    if (tier == 0) ctx->timers["gapped_tier0_hits"].launches += l.m; // (a counter, not a time: hits that entered tier 0)
-    PRB_HIP(launch_gapped_lds(s.U, s.G, l.m, l.cur, s.qb->view, s.pd, s.sc, s.eo, 0, tier, w.overflow.as<uint8_t>(), w.tierOf.as<uint8_t>(),
-                              s.first, w.ntrace.as<int32_t>(), w.trace.as<uint16_t>(), nullptr, nullptr,
-                              w.count.as<unsigned long long>() + 1, tier >= 1 ? c.rs[tier - 1] : kNoResume,
-                              tier < kLdsTiers - 1 ? c.rs[tier] : kNoResume, s.k.tiers, ctx->stream, handover, w.accScratch.as<double>()));
-    int64_t rest = 0;
-    if ((rc = advance(s, l, &rest))) return rc;
-    if (s.k.debug_rows)
-      fprintf(stderr, "[tier %d%s] hits %lld, go on %lld\n", tier, handover ? ", first direction" : "", (long long)l.m, (long long)rest);
-    l.m = rest;
-    if ((rc = ctx->time_end(kTierTimer[tier], 1))) return rc;
-  }
-  return PRB_OK;
-}
-
-// state dumps for the hits that outgrow tier 0 (~15 %: room for one hit in four, at most 4 M), tier 1
-// (~4 %: one in eight, at most 2 M) and tier 2 (~0.7 %: one in 32, at most 1 M)
-static int prepare_resume(SubSearch &s, Cascade &c) {
-  SearchWs &w = s.w;
-  int rc;
-  c.rs[0].cap = (int32_t)std::min<int64_t>(s.nch / 4 + 1024, 4 << 20);
-  c.rs[1].cap = (int32_t)std::min<int64_t>(s.nch / 8 + 1024, 2 << 20);
-  c.rs[2].cap = (int32_t)std::min<int64_t>(s.nch / 32 + 1024, 1 << 20);
-  if (s.k.resume_cap > 0) c.rs[0].cap = c.rs[1].cap = c.rs[2].cap = s.k.resume_cap;
-  DevBuf *pools[3] = {&w.resumePool, &w.resumePool2, &w.resumePool3};
-  if ((rc = w.resumeSlot.ensure((size_t)s.nch * 4 * 3)) || (rc = w.resumeCount.ensure(16))) return rc;
-  for (int t = 0; t < 3; t++) {
-    if ((rc = pools[t]->ensure((size_t)c.rs[t].cap * gapped_resume_bytes(t)))) return rc;
-    c.rs[t].slot = w.resumeSlot.as<int32_t>() + (size_t)t * s.nch;
-    c.rs[t].pool = pools[t]->as<uint8_t>();
-    c.rs[t].count = w.resumeCount.as<uint32_t>() + t;
-  }
-  return PRB_OK;
-}
-static int clear_resume(SubSearch &s) {
-  PRB_HIP(hipMemsetAsync(s.w.resumeCount.p, 0, 16, s.ctx->stream));
-  PRB_HIP(hipMemsetAsync(s.w.resumeSlot.p, 0xFF, (size_t)s.nch * 4 * 3, s.ctx->stream));
-  return PRB_OK;
-}
-
-// The hits that the front kernel leaves have a direction that finds something - or had too many cells for it.  Nine
-// SECOND directions in ten still find nothing, and a tier pays for proving that what it pays for 16 anti-diagonals of
-// any extension (8 - 40 ns per hit, against the front kernel's 0.6 per direction).  So the cascade first runs FIRST
-// directions only (GapArgs::handover; a hit whose first direction the front kernel completed runs its second one, as
-// ever), the front kernel then looks at the second directions of what the tiers stopped behind, and only the hits
-// whose second direction finds something too come back to the cascade, for that direction.
-static int run_handover(SubSearch &s, Cascade &c) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  WorkList &l = c.l;
-  int rc;
-  const int64_t m_first = l.m;
-  if ((rc = w.listC.ensure((size_t)m_first * 4))) return rc;
-  PRB_HIP(hipMemcpyAsync(w.listC.p, l.cur, (size_t)m_first * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  if ((rc = run_cascade(s, c, 1, true))) return rc;
-  // What outgrew the last LDS tier - ~150 extensions per configs[2] query, a wavefront each for 2 ms on a GPU that is
-  // otherwise idle - waits for the second pass's: ONE launch of the wavefront-per-hit kernel for both (a launch lasts
-  // as long as its longest extension; these hits run both their directions there).
-  const int64_t n_slow = l.m;
-  if (n_slow > 0) {
-    if ((rc = w.slowList.ensure((size_t)n_slow * 4))) return rc;
-    PRB_HIP(hipMemcpyAsync(w.slowList.p, l.cur, (size_t)n_slow * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  // the hits an LDS tier stopped behind their first direction
-  PRB_HIP(launch_flag_marked(w.tierOf.as<uint8_t>(), w.listC.as<uint32_t>(), m_first, kHandoverMark, w.overflow.as<uint8_t>(), ctx->stream));
-  l.cur = w.listC.as<uint32_t>();
-  l.m = m_first;
-  int64_t mh = 0;
-  if ((rc = advance(s, l, &mh))) return rc;
-  l.m = mh;
-  if (l.m > 0) {
-    if (c.rs[0].slot && (rc = clear_resume(s))) return rc; // (the hand-over slots of the first pass are not to be taken for this pass's)
-    if ((rc = run_front(s, c, true))) return rc; // (all of them stopped behind their first direction: a lane per hit)
-    if ((rc = run_cascade(s, c, 0, true))) return rc;
-  }
-  if (n_slow + l.m == 0) return PRB_OK;
-  if (l.m > 0) { // both passes' lists as one
-    if ((rc = grow_keep(ctx, w.slowList, (size_t)n_slow * 4, (size_t)(n_slow + l.m) * 4))) return rc;
-    PRB_HIP(hipMemcpyAsync(w.slowList.as<uint32_t>() + n_slow, l.cur, (size_t)l.m * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  l.cur = w.slowList.as<uint32_t>();
-  l.m += n_slow;
-  return run_slow(s, l, 0);
-}
-
-// the cascade for the view (s.U, s.G, s.nch, s.first)
-static int extend_chunk(SubSearch &s) {
-  SearchWs &w = s.w;
-  int rc;
-  Cascade c;
-  if ((rc = w.accScratch.ensure(std::max<size_t>(gapped_acc_scratch_bytes(), 8)))) return rc;
-  PRB_HIP(hipMemsetAsync(w.tierOf.p, 0, (size_t)s.nch, s.ctx->stream)); // no hit carries a resume mark yet
-  if (!s.k.no_resume) {
-    if ((rc = prepare_resume(s, c)) || (rc = clear_resume(s))) return rc;
-  }
-  c.l.m = s.nch; // all of U
-  c.l.bufs[0] = w.listA.as<uint32_t>();
-  c.l.bufs[1] = w.listB.as<uint32_t>();
-  // In front of the cascade (gapped_front.hip; PRB_GAPPED_FRONT=0 leaves it out): the hits neither direction of which
-  // finds anything - four in five - are completed by a kernel that only has to prove that.
-  const bool front_on = s.k.first_tier == 0 && s.k.front && gapped_front_supported(s.sc, s.eo);
-  if (front_on) {
-    if ((rc = run_front(s, c))) return rc;
-    c.skip_mask = s.k.skip_tiers;
-  }
-  if (!(front_on && s.k.handover)) return run_cascade(s, c, 0, false);
-  return c.l.m > 0 ? run_handover(s, c) : PRB_OK;
-}
-
-// Of the chunk just extended, what is not above the -g threshold is appended to the kept lists: the extended hits as
-// records in hitsB (what the final sort takes), the hits they came from, their first-of-query flags, tiers, chain lengths
-// and trace slots - everything the traceback of the final hits reads, indexed by position in the kept lists from now on
-static int keep_chunk(SubSearch &s, int64_t c0) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  const size_t trace_row = 2 * kTraceCap * sizeof(uint16_t);
-  int rc;
-  int64_t mc = 0;
-  if ((rc = ctx->time_begin())) return rc;
-  if ((rc = compact_below(ctx, w, s.G, s.nch, s.opts.final_threshold, w.cidx, w.hitsB, &mc, s.ngap))) return rc;
-  if (mc > 0) {
-    const size_t have = (size_t)s.ngap, need = have + (size_t)mc;
-    if ((rc = grow_keep(ctx, w.keptU, have * sizeof(HitRec), need * sizeof(HitRec))) || (rc = grow_keep(ctx, w.keptFirst, have, need)) ||
-        (rc = grow_keep(ctx, w.keptTier, have, need)) || (rc = grow_keep(ctx, w.keptNtrace, have * 4, need * 4)) ||
-        (rc = grow_keep(ctx, w.keptTrace, have * trace_row, need * trace_row)))
-      return rc;
-    const uint32_t *idx = w.cidx.as<uint32_t>();
-    PRB_HIP(launch_gather_hits_to_recs(s.U, idx, w.keptU.as<HitRec>() + have, mc, ctx->stream));
-    PRB_HIP(launch_gather_u8(s.first, idx, w.keptFirst.as<uint8_t>() + have, mc, ctx->stream));
-    PRB_HIP(launch_gather_u8(w.tierOf.as<uint8_t>(), idx, w.keptTier.as<uint8_t>() + have, mc, ctx->stream));
-    PRB_HIP(launch_gather_u32(w.ntrace.as<uint32_t>(), idx, w.keptNtrace.as<uint32_t>() + have, mc, ctx->stream));
-    PRB_HIP(launch_gather_rows(w.trace.p, idx, static_cast<uint8_t *>(w.keptTrace.p) + have * trace_row, mc, (int)trace_row, ctx->stream));
-  }
-  if ((rc = ctx->time_end("filter", 2))) return rc;
-  if (s.k.debug_rows)
-    fprintf(stderr, "[gapped chunk] hits %lld at %lld of %lld, kept %lld\n", (long long)s.nch, (long long)c0, (long long)s.nung, (long long)mc);
-  s.ngap += mc;
-  if (s.ngap > (int64_t)UINT32_MAX - 16) {
-    set_error("more than 4e9 hits under the -g threshold in one sub-batch: build the database in smaller pages (db -c)");
-    return PRB_ERR_NOMEM;
-  }
-  return PRB_OK;
-}
-
-// The state of this stage is ~350 B per hit (the extended hit, work lists, trace slots, hand-over slots): a list
-// longer than PRB_GAPPED_CHUNK_HITS (a 45 kb query against a 100 M character page leaves 5e8 hits behind -f) goes through
-// it in chunks of that many - the list is sorted and filtered already, the extension of a hit depends on nothing but the
-// hit -, and only what is not above the -g threshold is kept of a chunk.  The final sort + filter then run over the
-// union, as the reference's do over the whole list (rna_interaction_search.cpp:302-320).
-static int gapped_stage(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  int rc;
-  s.chunked = s.nung > s.k.gapped_chunk_hits;
-  s.nmax = s.chunked ? s.k.gapped_chunk_hits : s.nung;
-  const size_t NM = (size_t)s.nmax;
-  if ((rc = w.hitsC.ensure(hits_bytes(s.nmax)))) return rc;
-  if ((rc = w.overflow.ensure(NM)) || (rc = w.subset.ensure(NM * 4)) || (rc = w.ntrace.ensure(NM * 4)) || (rc = w.tierOf.ensure(NM)) ||
-      (rc = w.listA.ensure(NM * 4)) || (rc = w.listB.ensure(NM * 4)) || (rc = w.count.ensure(16)) ||
-      (rc = w.trace.ensure(NM * 2 * kTraceCap * sizeof(uint16_t))))
-    return rc;
-  s.G = carve_hits(w.hitsC, s.nmax);
-  s.nch = s.nmax;
-  if (!s.chunked) {
-    if ((rc = extend_chunk(s))) return rc;
-    s.tier_all = w.tierOf.as<uint8_t>();
-    s.ntrace_all = w.ntrace.as<int32_t>();
-    s.trace_all = w.trace.as<uint16_t>();
-    return PRB_OK;
-  }
-  const HitSoA Uall = s.U;
-  for (int64_t c0 = 0; c0 < s.nung; c0 += s.k.gapped_chunk_hits) {
-    s.nch = std::min<int64_t>(s.k.gapped_chunk_hits, s.nung - c0);
-    s.U = offset_hits(Uall, c0);
-    s.G = carve_hits(w.hitsC, s.nch);
-    s.first = w.first.as<uint8_t>() + c0;
-    if ((rc = extend_chunk(s)) || (rc = keep_chunk(s, c0))) return rc;
-  }
-  // from here on "the hits before the gapped stage" are the kept ones, in the order they were kept
-  if (s.ngap > 0) {
-    if ((rc = w.hitsA.ensure(hits_bytes(s.ngap))) || (rc = w.cidx.ensure((size_t)s.ngap * 4))) return rc;
-    s.U = carve_hits(w.hitsA, s.ngap);
-    PRB_HIP(launch_iota_u32(w.cidx.as<uint32_t>(), s.ngap, ctx->stream));
-    PRB_HIP(launch_gather_recs_to_hits(w.keptU.as<HitRec>(), w.cidx.as<uint32_t>(), s.U, s.ngap, ctx->stream));
-  }
-  s.first = w.keptFirst.as<uint8_t>();
-  s.tier_all = w.keptTier.as<uint8_t>();
-  s.ntrace_all = w.keptNtrace.as<int32_t>();
-  s.trace_all = w.keptTrace.as<uint16_t>();
   return PRB_OK;
 }
 
@@ -1212,13 +754,7 @@ static int traceback(SubSearch &s) {
     if ((rc = w.bpOff2.ensure((size_t)m * 8)) || (rc = w.subset2.ensure((size_t)m * 4))) return rc;
     PRB_HIP(hipMemcpyAsync(w.bpOff2.p, toff[t].data(), (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
     PRB_HIP(hipMemcpyAsync(w.subset2.p, tlist[t].data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (t == kWaveTier) {
-      if ((rc = run_wave(s, 2, w.subset2.as<uint32_t>(), m, nullptr, w.bpOff2.as<int64_t>()))) return rc;
-    } else {
-      PRB_HIP(launch_gapped_lds(s.U, s.G, m, w.subset2.as<uint32_t>(), s.qb->view, s.pd, s.sc, s.eo, 2, t, nullptr, nullptr, s.first, nullptr,
-                                nullptr, w.bpOff2.as<int64_t>(), w.bpOut.as<int32_t>(), w.count.as<unsigned long long>() + 1, kNoResume,
-                                kNoResume, s.k.tiers, ctx->stream, 0, w.accScratch.as<double>()));
-    }
+    if ((rc = retrace_tier(s, t, w.subset2.as<uint32_t>(), w.bpOff2.as<int64_t>(), m))) return rc;
     PRB_HIP(hipStreamSynchronize(ctx->stream)); // the staging buffers are reused by the next tier
   }
   if (any_rerun) {

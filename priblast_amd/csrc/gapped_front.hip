@@ -687,13 +687,16 @@ static int front_blocks_per_cu() {
 }
 size_t gapped_front_scratch_bytes() { return (size_t)256 * front_blocks_per_cu() * kFWaves * sizeof(FrontAcc); }
 
-hipError_t launch_gapped_front(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                               const SearchConst &sc, ExtOpts o, int tier_id, uint8_t *overflow, uint8_t *tier_out, int32_t *bp_count,
-                               unsigned long long *next_work, void *scratch, hipStream_t s, bool second_only) {
+hipError_t launch_gapped_front(const GapArgs &args, void *scratch, bool second_only, hipStream_t s) {
+  const int64_t n = args.n;
   if (n <= 0) return hipSuccess;
-  GapArgs a{in,      out,     n,       subset,    qb, pg, sc, o, overflow, tier_out, tier_id, nullptr, bp_count,
-            nullptr, nullptr, nullptr, next_work, GapResume{nullptr, nullptr, nullptr, 0}, GapResume{nullptr, nullptr, nullptr, 0}};
-  if (hipError_t e = hipMemsetAsync(next_work, 0, sizeof(unsigned long long), s); e != hipSuccess) return e;
+  GapArgs a = args;
+  a.first_flag = nullptr;
+  a.trace = nullptr;
+  a.bp_off = nullptr;
+  a.bp_out = nullptr;
+  a.rin = a.rout = GapResume{};
+  if (hipError_t e = hipMemsetAsync(a.next_work, 0, sizeof(unsigned long long), s); e != hipSuccess) return e;
   const int per_tile = second_only ? kFDirs : kFDirs / 2;
   const int64_t tiles = (n + per_tile - 1) / per_tile, want_blocks = (tiles + kFWaves - 1) / kFWaves;
   const dim3 grid((unsigned)std::min<int64_t>(want_blocks, 256 * front_blocks_per_cu())), blk(64 * kFWaves);

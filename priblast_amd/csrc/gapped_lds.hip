@@ -1752,7 +1752,7 @@ __global__ __launch_bounds__(T::kG *T::kGroups, T::kWavesPerSimd) void k_gapped_
 template <int kMode, bool kInLds> __global__ __launch_bounds__(64) void k_gapped_wave(GapArgs a, GapScratch scratch) {
   extern __shared__ __align__(16) uint8_t wave_smem[];
   const int gl = threadIdx.x;
-  uint8_t *mine = kInLds ? wave_smem : scratch.base + (size_t)blockIdx.x * scratch.bytes_per_thread; // one block per wavefront
+  uint8_t *mine = kInLds ? wave_smem : scratch.base + (size_t)blockIdx.x * scratch.bytes_per_wave; // one block per wavefront
   HbmStore S;
   S.capd = scratch.cap_diag;
   S.capr = scratch.cap_rec;
@@ -1847,20 +1847,17 @@ template <class T, class Rec> hipError_t launch_tier(GapArgs a, int mode, const 
 }
 } // namespace
 
-hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                             const PageDev &pg, const SearchConst &sc, ExtOpts o, int mode, int tier, uint8_t *overflow,
-                             uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count, uint16_t *trace,
-                             const int64_t *bp_off, int32_t *bp_out, unsigned long long *next_work, const GapResume &rin,
-                             const GapResume &rout, const GapTierKnobs &knobs, hipStream_t s, int handover, double *acc_scratch) {
-  if (n <= 0) return hipSuccess;
-  GapArgs a{in,      out,   n,      subset, qb,        pg,         sc, o, overflow, tier_out, tier, first_flag, bp_count,
-            trace,   bp_off, bp_out, next_work, rin,     rout};
-  a.handover = mode == 0 ? handover : 0;
-  a.acc_scratch = acc_scratch;
-  if (((tier == 1 || tier == 2) && Tier1::kAccGlobal || tier == 0 && Tier0::kAccGlobal) && !acc_scratch) return hipErrorInvalidValue;
+hipError_t launch_gapped_lds(const GapArgs &args, int mode, int tier, const GapTierKnobs &knobs, hipStream_t s) {
+  if (args.n <= 0) return hipSuccess;
+  GapArgs a = args;
+  a.tier_id = tier;
+  a.lt = LongTrace{};
+  if (mode != 0) a.handover = 0;
+  if (((tier == 1 || tier == 2) && Tier1::kAccGlobal || tier == 0 && Tier0::kAccGlobal) && !a.acc_scratch) return hipErrorInvalidValue;
   const bool lds_tier = tier >= 0 && tier < kLdsTiers;
   // experiment (GapTierKnobs::period): lockstep iterations between boundaries (0: default)
-  if (knobs.period_set) a.period = mode == 0 && lds_tier ? knobs.period[tier] : 0;
+  a.period = knobs.period_set && mode == 0 && lds_tier ? knobs.period[tier] : 0;
+  a.pool = 1; // (launch_tier: GapTierKnobs::pool for tier 0's paired form)
   // Tier 2's four groups per wavefront hold hits that arrive in the middle of a direction and end anywhere: a boundary as soon as
   // two of them wait costs it 220 ms per configs[2] step instead of 238 (tiers 0 and 1, eight groups: 2 - 4 waiting groups cost
   // more in transitions than they save in waiting; tier 3 has one group per wavefront and waits for nobody).
@@ -1872,18 +1869,20 @@ hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint
   return launch_tier<Tier3, Rec32W>(a, mode, knobs, s);
 }
 
-hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                              const PageDev &pg, const SearchConst &sc, ExtOpts o, GapScratch scratch, int mode,
-                              uint8_t *overflow, uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count,
-                              const int64_t *bp_off, int32_t *bp_out, hipStream_t s, int handover, const LongTrace &lt) {
-  if (n <= 0) return hipSuccess;
-  GapArgs a{in,      out,    n,      subset,  qb,      pg,      sc,      o, overflow, tier_out, kWaveTier, first_flag, bp_count,
-            nullptr, bp_off, bp_out, nullptr, GapResume{nullptr, nullptr, nullptr, 0}, GapResume{nullptr, nullptr, nullptr, 0}};
-  a.handover = mode == 0 ? handover : 0;
-  if (mode == 0) a.lt = lt;
-  const int blocks = scratch.nthreads; // here: number of wavefronts that own a state block
+hipError_t launch_gapped_wave(const GapArgs &args, GapScratch scratch, int mode, hipStream_t s) {
+  if (args.n <= 0) return hipSuccess;
+  GapArgs a = args;
+  a.tier_id = kWaveTier;
+  a.trace = nullptr;
+  a.next_work = nullptr;
+  a.rin = a.rout = GapResume{};
+  if (mode != 0) {
+    a.lt = LongTrace{};
+    a.handover = 0;
+  }
+  const int blocks = scratch.nwaves;
   if (scratch.base == nullptr) { // state in LDS
-    const size_t lds = scratch.bytes_per_thread;
+    const size_t lds = scratch.bytes_per_wave;
     if (mode == 0) hipLaunchKernelGGL((k_gapped_wave<0, true>), dim3(blocks), dim3(64), lds, s, a, scratch);
     else hipLaunchKernelGGL((k_gapped_wave<2, true>), dim3(blocks), dim3(64), lds, s, a, scratch);
   } else {

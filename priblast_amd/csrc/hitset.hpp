@@ -1,5 +1,6 @@
 // prb_hitset (include/priblast_hip.h): the result of prb_search_page / prb_gather_hits, shared by the search driver
-// (capi_search.hip, which fills it and has its accessors) and capi_comm.hip (the final hit gather).
+// (capi_search.hip, which fills it and has its accessors; capi_gapped.hip, which counts the hits of its slow path) and
+// capi_comm.hip (the final hit gather).
 #pragma once
 #include <hip/hip_runtime.h>
 

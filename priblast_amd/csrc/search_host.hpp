@@ -1,5 +1,5 @@
-// What the host units of the search share (capi_pages.hip, capi_search.hip, capi_top.hip, capi_targets.hip,
-// capi_spans.hip, capi_lines.hip): the objects behind the C ABI's handles, the workspace of the search stages, and the
+// What the host units of the search share (capi_pages.hip, capi_search.hip, capi_gapped.hip, capi_top.hip,
+// capi_targets.hip, capi_spans.hip, capi_lines.hip): the objects behind the C ABI's handles, the workspace of the search stages, and the
 // rocPRIM idioms they all use.
 #pragma once
 #include <atomic>
@@ -46,7 +46,7 @@ struct PageMem {
   X(first, 1) X(cidx, 1)                                                                                                        \
   X(gapScratch, 1) X(overflow, 1) X(tierOf, 1) X(listA, 1) X(listB, 1) X(listC, 1) X(ntrace, 1) X(trace, 1) /* gapped */        \
   X(frontScratch, 1) X(accScratch, 0)                                                                                           \
-  X(resumeSlot, 0) X(resumePool, 1) X(resumePool2, 1) X(resumePool3, 1) X(resumeCount, 0)                                       \
+  X(resumeSlot, 0) X(resumeCount, 0)                                                                                            \
   X(slowList, 1) X(slowSlot, 1) X(slowCnt, 1) X(slowTrace, 1)                                                                   \
   X(keptU, 1) X(keptFirst, 1) X(keptTier, 1) X(keptNtrace, 1) X(keptTrace, 1)                          /* chunked gapped */     \
   X(subset, 1) X(subset2, 1) X(tierFin, 1) X(ntraceFin, 1)                                             /* traceback */          \
@@ -57,6 +57,7 @@ struct SearchWs {
 #define X(name, trimmable) DevBuf name;
   PRB_SEARCH_BUFFERS(X)
 #undef X
+  DevBuf resumePool[kLdsTiers - 1]; // resumePool[t]: the state dumps of the hits that outgrow LDS tier t (trimmable)
   // The front of the one-pass seed path for a chunk of candidates - candidates and their pair offsets on the device,
   // query-side window sums, the pairs' keys and values, sorted - in buffers of its own, so that it can be issued for
   // the NEXT sub-batch, on a stream of its own, while this sub-batch is in its last, nearly idle stretch (search_range):
@@ -116,12 +117,15 @@ struct SearchWs {
   if (trimmable && name.cap > ((size_t)256 << 20)) name.release();
     PRB_SEARCH_BUFFERS(X)
 #undef X
+    for (DevBuf &b : resumePool)
+      if (b.cap > ((size_t)256 << 20)) b.release();
     trim_next = false;
   }
   void release() {
 #define X(name, trimmable) name.release();
     PRB_SEARCH_BUFFERS(X)
 #undef X
+    for (DevBuf &b : resumePool) b.release();
     front.release();
     if (copy_stream) {
       (void)hipStreamSynchronize(copy_stream);

@@ -195,10 +195,10 @@ hipError_t launch_filter_final(const HitSoA &h, int64_t n, const int64_t *pmax, 
 // ============================================================================ gapped_lds.hip: gapped extension
 constexpr size_t kGapWaveLdsBytes = 64 * 1024; // a state block up to this size can live in the workgroup's LDS
 struct GapScratch {
-  uint8_t *base;           // one block per wavefront; nullptr = in the wavefront's (dynamic) LDS
-  size_t bytes_per_thread; // bytes per block
+  uint8_t *base;         // one block per wavefront; nullptr = in the wavefront's (dynamic) LDS
+  size_t bytes_per_wave; // bytes per block = gapped_wave_scratch_bytes(cap_diag, cap_rec)
   int32_t cap_rec, cap_diag;
-  int32_t nthreads;        // number of wavefronts (= grid size)
+  int32_t nwaves;        // wavefronts that own a state block (= grid size)
 };
 size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec);
 // State dumps of the hits that outgrow LDS tier 0 / tier 1 (mode 0): the next tier continues from
@@ -207,16 +207,17 @@ size_t gapped_wave_scratch_bytes(int cap_diag, int cap_rec);
 // with the slots).  All null / 0: no dumps.  A launch gets the pool it may continue (rin: tier 1
 // <- tier 0's, tier 2 <- tier 1's) and the pool it fills (rout: tiers 0 and 1).
 struct GapResume {
-  int32_t *slot;
-  uint8_t *pool;
-  uint32_t *count;
-  int32_t cap;
+  int32_t *slot = nullptr;
+  uint8_t *pool = nullptr;
+  uint32_t *count = nullptr;
+  int32_t cap = 0;
 };
 size_t gapped_resume_bytes(int tier);
 // ids of the gapped kernels a hit can be completed by (tier_out): LDS tiers 0..3, then the
 // wavefront-per-hit kernel with its state in HBM scratch
 constexpr int kLdsTiers = 4, kWaveTier = 4;
-// The experiments of the LDS tiers, as the driver read them from the environment (read_search_knobs, capi_search.hip;
+// The experiments of the LDS tiers, as the driver read them from the environment (read_search_knobs, capi_search.hip -
+// SearchKnobs::tiers, search_stages.hpp;
 // INTEGRATION.md has the table).  The per-tier lists count only where their variable is set.
 struct GapTierKnobs {
   bool pair = true; // PRB_GAPPED_PAIR: tier 0 takes two anti-diagonals per step (0: one)
@@ -252,40 +253,58 @@ struct LongTrace {
 // larger of the tiers its two directions needed (the tier that would have to extend it again for its pairs).
 constexpr uint8_t kResumeMark = 0x40, kHandoverMark = 0x80, kMarkTier = 0x07;
 __host__ __device__ inline bool is_resumed(uint8_t t) { return (t & (kResumeMark | kHandoverMark)) != 0; }
-// Gapped extension.  mode 0: extend hits (coords + energies) into `out`,
-// overflow[i] = 1 if the state capacity was too small, bp_count[x] = pairs traced back by the
-// two extensions of hit x; mode 2: write the base pairs of list entry i at bp_off[i] (hits
-// beyond the capacity are skipped).
+// What a gapped kernel is launched with: the driver (capi_gapped.hip) fills it by name, the launchers below take it and
+// set what is their kernel's own business.  Passed to the kernels by value.  mode 0: extend the n hits of the list
+// `subset` (indices into in / out and the per-hit arrays; nullptr: 0..n-1) into `out`; mode 2: write the base pairs of
+// list entry w at bp_off[w] (hits beyond the kernel's capacity are skipped).  A field that names a mode or a kernel is
+// read by no other.
+struct GapArgs {
+  HitSoA in{}, out{}; // coordinates and energies before / behind the extension
+  int64_t n = 0;
+  const uint32_t *subset = nullptr;
+  QBatchDev qb{};
+  PageDev pg{};
+  SearchConst sc{};
+  ExtOpts o{};
+  uint8_t *overflow = nullptr; // mode 0: overflow[w] = 1 if the capacities of this kernel did not suffice
+  uint8_t *tier_out = nullptr; // mode 0: tier_out[x] = tier_id when hit x was completed here (the front kernel: its `tier_id`, 0)
+  int tier_id = 0;             // set by launch_gapped_lds (its tier) and launch_gapped_wave (kWaveTier)
+  const uint8_t *first_flag = nullptr; // mode 2: first_flag[x] = 1 for the first hit of a query, whose pairs keep the order they were found in
+  int32_t *bp_count = nullptr; // mode 0: traced pairs of hit x, left | right << 16
+  uint16_t *trace = nullptr;   // mode 0 (LDS tiers): the first kTraceCap traced cells (i | j << 8) per direction of hit x
+  const int64_t *bp_off = nullptr; // mode 2: where the pairs of list entry w go in bp_out
+  int32_t *bp_out = nullptr;   // mode 2: the pairs, (q, db) each
+  unsigned long long *next_work = nullptr; // LDS and front kernels: 8 bytes of scratch, the work counter (zeroed by the launcher) behind the statically assigned first hits
+  // mode 0: state dumps of hits that outgrow an LDS tier, for the next one to continue from
+  // (slot[x] = -1: none): `rin` = what this kernel may continue, `rout` = where it leaves its own
+  GapResume rin{}, rout{};
+  LongTrace lt{};   // mode 0, the wavefront-per-hit kernel: where it leaves whole traceback chains
+  double *acc_scratch = nullptr; // LDS tiers: gapped_acc_scratch_bytes() of device memory, 2 x capacity doubles per resident group
+  // set by launch_gapped_lds from GapTierKnobs:
+  int period = 0;   // LDS tiers: lockstep iterations between the boundaries at which groups change direction / hit (0: the drop-out length)
+  int early = 0;    // LDS tiers: a boundary also as soon as this many groups of the wavefront have finished their direction (0: never)
+  int pool = 1;     // tier 0 with two anti-diagonals per step: the filled cells of a step pooled over the wavefront (0: each group its own)
+  int handover = 0; // mode 0, LDS tiers and the wavefront-per-hit kernel: stop behind a first direction that this kernel ran (kHandoverMark)
+};
 // launch_gapped_lds: a group of lanes per hit, state in LDS with fixed capacities: tiers 0 and 1 = 8 lanes (32 and 40
-// anti-diagonals), tier 2 = 16 lanes, 64 anti-diagonals; tier 3 = a wavefront, 128 anti-diagonals.
-hipError_t launch_gapped_lds(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                             const PageDev &pg, const SearchConst &sc, ExtOpts o, int mode, int tier, uint8_t *overflow,
-                             uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count, uint16_t *trace,
-                             const int64_t *bp_off, int32_t *bp_out, unsigned long long *next_work /* 8 bytes of scratch */,
-                             const GapResume &rin, const GapResume &rout, const GapTierKnobs &knobs, hipStream_t s,
-                             int handover = 0 /* GapArgs::handover */,
-                             double *acc_scratch = nullptr /* gapped_acc_scratch_bytes() of device memory */);
+// anti-diagonals), tier 2 = 16 lanes, 64 anti-diagonals; tier 3 = a wavefront, 128 anti-diagonals.  Passes `handover`
+// on only in mode 0, and no `lt`.
+hipError_t launch_gapped_lds(const GapArgs &a, int mode, int tier, const GapTierKnobs &knobs, hipStream_t s);
 size_t gapped_acc_scratch_bytes();
-// launch_gapped_wave: one wavefront per hit, state in the HBM scratch (`scratch.nthreads`
-// wavefronts, `bytes_per_thread` bytes each = gapped_wave_scratch_bytes(cap_diag, cap_rec)).
-hipError_t launch_gapped_wave(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb,
-                              const PageDev &pg, const SearchConst &sc, ExtOpts o, GapScratch scratch, int mode,
-                              uint8_t *overflow, uint8_t *tier_out, const uint8_t *first_flag, int32_t *bp_count,
-                              const int64_t *bp_off, int32_t *bp_out, hipStream_t s, int handover = 0,
-                              const LongTrace &lt = LongTrace{});
+// launch_gapped_wave: one wavefront per hit, state in the scratch (`scratch.nwaves` wavefronts).  Passes `lt` and
+// `handover` on only in mode 0, and no `trace`, `next_work`, `rin` or `rout`.
+hipError_t launch_gapped_wave(const GapArgs &a, GapScratch scratch, int mode, hipStream_t s);
 
 // ============================================================================ gapped_front.hip: in front of the cascade
 // launch_gapped_front proves that a direction finds nothing within its `-x` anti-diagonals (phases that are dense over
 // directions / filled cells / (cell, candidate) pairs of 64 directions at a time) and completes the hits whose two directions both find nothing; the others are flagged in
 // overflow[] (with direction 0 handed over when it found nothing) and go on to the LDS tiers.  Completed hits are
-// reported as `tier_id`.  Takes -x <= kFrontMaxDrop.
+// reported as `tier_id`.  Takes -x <= kFrontMaxDrop.  Mode 0 only; passes no `first_flag`, `trace`, `bp_off`, `bp_out`,
+// `rin` or `rout` on.  second_only: every hit of the list has its first direction done (a resume / hand-over mark).
 constexpr int kFrontMaxDrop = 16;
 bool gapped_front_supported(const SearchConst &sc, const ExtOpts &o);
 size_t gapped_front_scratch_bytes(); // HBM scratch of a launch (accessibility sums of the resident wavefronts; stays in L2)
-hipError_t launch_gapped_front(const HitSoA &in, HitSoA out, int64_t n, const uint32_t *subset, const QBatchDev &qb, const PageDev &pg,
-                               const SearchConst &sc, ExtOpts o, int tier_id, uint8_t *overflow, uint8_t *tier_out, int32_t *bp_count,
-                               unsigned long long *next_work, void *scratch, hipStream_t s,
-                               bool second_only = false /* every hit of the list has its first direction done (a resume / hand-over mark) */);
+hipError_t launch_gapped_front(const GapArgs &a, void *scratch, bool second_only, hipStream_t s);
 
 // ============================================================================ traceback_kernels.hip: base pairs
 // slot[list[p]] = base + p (the long-trace slots of the hits that go to the wavefront-per-hit kernel)
