@@ -47,6 +47,7 @@ typedef struct prb_ctx prb_ctx;       /* one GPU: stream, parameter tables, work
 typedef struct prb_db prb_db;         /* database pages resident in HBM */
 typedef struct prb_qbatch prb_qbatch; /* a batch of queries: enc + SA + accessibilities */
 typedef struct prb_hitset prb_hitset; /* result of prb_search_page, host side */
+typedef struct prb_pairmask prb_pairmask; /* the (query, target) pairs a search is restricted to, see below */
 
 /* `ris` options, defaults of rna_interaction_search_parameters.hpp:54-62 */
 typedef struct prb_ris_opts {
@@ -63,9 +64,11 @@ typedef struct prb_ris_opts {
   int32_t chain_sites;        /* -j: 0 = every final hit (the default), 1 = each pair's best co-linear chain of sites only, see
                                * below; anything else, and 1 together with distinct_sites = 1, is PRB_ERR_ARG.  Ignored for
                                * last_stage 1 and 2.  (It takes what used to be the struct's tail padding.) */
+  const prb_pairmask *allowed_pairs; /* -L: NULL = every pair (the default); else only the pairs the mask allows are searched,
+                               * see below.  A mask made for another batch or database is PRB_ERR_ARG */
 } prb_ris_opts;
 #ifdef __cplusplus
-static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: ten fields, chain_sites the last one, no tail padding");
+static_assert(sizeof(prb_ris_opts) == 64, "prb_ris_opts: eleven fields, allowed_pairs the last one, no tail padding");
 #endif
 
 /* POD form of hit.hpp:38-118 (`Hit`) */
@@ -116,6 +119,33 @@ static_assert(sizeof(prb_ris_opts) == 56, "prb_ris_opts: ten fields, chain_sites
  * list, counts[2] stays the number of final hits BEFORE the selection, and each of the five result tables holds pages of
  * one value of chain_sites (a second one is PRB_ERR_ARG with the field's name, the table untouched; prb_*_merge refuse
  * two tables of different values unless one has merged no page). */
+
+/* ---- searching only listed pairs (opts->allowed_pairs, `ris -L`) ----
+ * A prb_pairmask holds one bit per (query of a batch, target of a database), targets numbered page by page as
+ * prb_targetset numbers them; on the device a bit matrix in HBM, its rows padded to whole 32-bit words, uploaded once - at
+ * the first search that uses it - and independent of which pages are resident.  The seeds of pairs that are not allowed
+ * are dropped right behind the seed expansion (one-pass form: the (query entry, database entry) pairs are compacted in
+ * front of their sort; list form: a row of a disallowed pair counts no seed), so the sort, both redundancy filters, the
+ * gapped stage and the traceback see the allowed pairs' hits only, and counts[0] counts their seeds only.  Nothing behind
+ * the seeds mixes hits of two pairs, so the hits are, field for field, the hits of the unrestricted search for the allowed
+ * pairs - with one exception: the base pairs of the FIRST hit of a query's list stay in found order, and
+ * under a mask that is the first hit of the restricted list; the pairs are the same set.  With allowed_pairs = NULL
+ * nothing is launched or branched on that was not before.
+ *   prb_pairmask_create   no pair allowed
+ *   prb_pairmask_allow    allows n pairs (query[i], page[i], db_id[i]); query[i] == -1: every query of the batch.  Only
+ *                         before the first search that uses the mask (afterwards PRB_ERR_STATE); an index out of range is
+ *                         PRB_ERR_ARG with the entry named, and nothing of the call is applied
+ *   prb_pairmask_count    the allowed pairs (-1 for NULL)
+ * A mask belongs to the batch and the database it was made for and must be freed before either: a search tells them by
+ * their handles (and the batch's size and the database's page count), so a mask that outlives its batch may be taken
+ * for the mask of a later batch of equal size at the same address.  Searches of several threads (contexts) may share a
+ * mask - its first use is guarded -, prb_pairmask_allow may not run beside a search or another prb_pairmask_allow.
+ * Stage timer "allow": the bit test and the compaction of the one-pass form's pairs (launches = 3 per chunk: test,
+ * scan, scatter), for the chunks that are not issued ahead. */
+int prb_pairmask_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, prb_pairmask **out);
+int prb_pairmask_allow(prb_pairmask *pm, int64_t n, const int32_t *query, const int32_t *page, const int32_t *db_id);
+int64_t prb_pairmask_count(const prb_pairmask *pm);
+void prb_pairmask_free(prb_pairmask *pm);
 
 typedef struct prb_hit {
   int32_t q_sp, db_sp;          /* start in the query / in the page's reversed db text */

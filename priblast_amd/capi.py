@@ -22,7 +22,8 @@ P = ctypes.POINTER
 class RisOpts(ctypes.Structure):
     _fields_ = [("max_seed_length", c_i32), ("hybrid_threshold", c_dbl), ("interaction_threshold", c_dbl),
                 ("final_threshold", c_dbl), ("drop_out_wo_gap", c_i32), ("drop_out_w_gap", c_i32),
-                ("min_helix_length", c_i32), ("output_style", c_i32), ("distinct_sites", c_i32), ("chain_sites", c_i32)]
+                ("min_helix_length", c_i32), ("output_style", c_i32), ("distinct_sites", c_i32), ("chain_sites", c_i32),
+                ("allowed_pairs", ctypes.c_void_p)]  # a prb_pairmask (PairMask.h), or None: every pair
 
 
 class Hit(ctypes.Structure):
@@ -113,6 +114,10 @@ SYMBOLS = {
     "prb_qbatch_seed_search_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts)]),
     "prb_search_page": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), c_i32,
                                        P(ctypes.c_void_p)]),
+    "prb_pairmask_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
+    "prb_pairmask_allow": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_pairmask_count": (c_i64, [ctypes.c_void_p]),
+    "prb_pairmask_free": (None, [ctypes.c_void_p]),
     "prb_hitset_size": (c_i64, [ctypes.c_void_p]),
     "prb_hitset_hits": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_hitset_basepairs": (ctypes.c_void_p, [ctypes.c_void_p, P(c_i64)]),
@@ -390,6 +395,38 @@ class QBatch:
         """starts the seed DFS against `page` in the background; a later search_page with the same options uses it"""
         o = opts or default_opts()
         _check(lib().prb_qbatch_seed_search_begin(self.ctx.h, self.h, db.h, page, ctypes.byref(o)))
+
+
+class PairMask:
+    """A prb_pairmask: the (query, target) pairs a search of `qb` against `db` is restricted to.  Give it to a search as
+    default_opts(allowed_pairs=mask.h); it must outlive the searches that use it."""
+
+    def __init__(self, ctx, qb, db):
+        h = ctypes.c_void_p()
+        _check(lib().prb_pairmask_create(ctx.h, qb.h, db.h, ctypes.byref(h)))
+        self.h = h
+
+    def allow(self, query, page, db_id):
+        """arrays of equal length; query -1 = every query of the batch"""
+        q, p, d = (np.ascontiguousarray(np.atleast_1d(x), np.int32) for x in (query, page, db_id))
+        assert len(q) == len(p) == len(d)
+        _check(lib().prb_pairmask_allow(self.h, len(q), q.ctypes.data, p.ctypes.data, d.ctypes.data))
+        return self
+
+    @property
+    def count(self):
+        return lib().prb_pairmask_count(self.h)
+
+    def close(self):
+        if self.h:
+            lib().prb_pairmask_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class _HitSetOwner:

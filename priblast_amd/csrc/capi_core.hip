@@ -100,6 +100,7 @@ void prb_ris_opts_default(prb_ris_opts *o) {
   o->output_style = 0;
   o->distinct_sites = 0;
   o->chain_sites = 0;
+  o->allowed_pairs = nullptr;
 }
 
 int prb_search_const_upload(prb_ctx *ctx); // capi_pages.hip
@@ -251,6 +252,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->chain_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "allow") == 0) {
+    if (ms) *ms = ctx->allow_timer.ms;
+    if (launches) *launches = ctx->allow_timer.launches;
+    return PRB_OK;
+  }
   if (std::strcmp(stage, "coverage") == 0) {
     if (ms) *ms = ctx->coverage_timer.ms;
     if (launches) *launches = ctx->coverage_timer.launches;
@@ -265,6 +271,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
   if (ctx) {
     ctx->timers.clear();
     ctx->summary_timer = prb::StageTimer{};
+    ctx->allow_timer = prb::StageTimer{};
     ctx->top_timer = prb::StageTimer{};
     ctx->profile_timer = prb::StageTimer{};
     ctx->tophits_timer = prb::StageTimer{};

@@ -326,8 +326,11 @@ static int scan_row_counts(prb_ctx *ctx, SearchWs &w, int64_t n) {
 // The front of the one-pass seed path (SearchWs::FrontStage) for the chunk whose candidates - row0 / qoff relative to
 // the chunk - are the nc entries at cd (page-locked): everything is issued on `s`.  *np_out = its pairs, or -1 when a
 // candidate has more query entries than a pair's value has bits for (nothing is issued then: the list form takes it).
+// Under a pair mask (`allow`) the pairs that are not allowed are dropped behind their keys: a test, a scan over one count
+// per 64 pairs and a scatter, in a bracket of the "allow" timer when the caller has the "seed" bracket open on `s`
+// (`timed`).  The sort needs the number of pairs left, which is on its way to the host: finish_front does it.
 static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int delta, int row_shift, const CandDev *cd, int32_t nc,
-                       int64_t cents, hipStream_t s, int64_t *np_out) {
+                       int64_t cents, hipStream_t s, int64_t *np_out, const AllowDev *allow, prb_ctx *timed) {
   SearchWs::FrontStage &F = w.front;
   int rc;
   *np_out = -1;
@@ -352,8 +355,56 @@ static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int
   PRB_HIP(launch_seed_qacc(F.cands.as<CandDev>(), nc, cents, qb->view, delta, F.seed_qacc.as<double>(), s));
   PRB_HIP(launch_pair_keys(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), nc, np, pd, cd[0].query, row_shift, kb.dbits, kb.wide(), F.keyA.p,
                            F.valA.as<uint64_t>(), s));
+  F.unsorted = false;
+  F.np_all = np;
+  F.vals = F.valB.as<uint64_t>();
+  if (allow) {
+    const int64_t nw = allow_words(np);
+    if ((rc = F.ballot.ensure((size_t)nw * 8)) || (rc = F.wcount.ensure((size_t)(nw + 1) * 4)) || (rc = F.woff.ensure((size_t)(nw + 1) * 8)) ||
+        (rc = F.kept_pin.ensure(8)))
+      return rc;
+    if (timed && ((rc = timed->time_end("seed", 1)) || (rc = timed->time_begin()))) return rc; // (the keys; the sort is counted where it runs)
+    PRB_HIP(hipMemsetAsync(F.wcount.as<int32_t>() + nw, 0, 4, s)); // (the scan over nw + 1 counts ends with the total)
+    PRB_HIP(launch_allow_test(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), F.valA.as<uint64_t>(), np, pd, *allow, F.ballot.as<uint64_t>(),
+                              F.wcount.as<int32_t>(), s));
+    auto counts = rocprim::make_transform_iterator(F.wcount.as<int32_t>(), ToI64());
+    if ((rc = with_temp(F.scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
+           return rocprim::exclusive_scan(t, b, counts, F.woff.as<int64_t>(), (int64_t)0, (size_t)nw + 1, rocprim::plus<int64_t>(), s);
+         })))
+      return rc;
+    PRB_HIP(launch_allow_scatter(F.keyA.p, F.valA.as<uint64_t>(), np, kb.wide(), F.ballot.as<uint64_t>(), F.woff.as<int64_t>(), F.keyB.p,
+                                 F.valB.as<uint64_t>(), s));
+    PRB_HIP(hipMemcpyAsync(F.kept_pin.p, F.woff.as<int64_t>() + nw, 8, hipMemcpyDeviceToHost, s));
+    if (timed && ((rc = timed->time_end(timed->allow_timer, 3)) || (rc = timed->time_begin()))) return rc;
+    F.unsorted = true;
+    F.key_bits = kb.kbits;
+    *np_out = np;
+    return PRB_OK;
+  }
   if ((rc = sort_by_row_key(s, F.sortTmp, kb, F.keyA, F.keyB, F.valA.as<uint64_t>(), F.valB.as<uint64_t>(), NP))) return rc;
   *np_out = np;
+  return PRB_OK;
+}
+
+// Under a pair mask: the front stage's pairs were compacted (issue_front, on the context's stream or waited for by it);
+// *np = how many are left, sorted now - none: nothing is launched
+static int finish_front(prb_ctx *ctx, SearchWs &w, const SearchKnobs &k, int32_t nc, int64_t *np) {
+  SearchWs::FrontStage &F = w.front;
+  int rc;
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  F.unsorted = false;
+  const int64_t kept = *static_cast<const int64_t *>(F.kept_pin.p);
+  if (kept < 0 || kept > F.np_all) {
+    set_error("pair mask: " + std::to_string(kept) + " of " + std::to_string(F.np_all) + " pairs kept");
+    return PRB_ERR_STATE;
+  }
+  if (k.debug_rows) fprintf(stderr, "[allow] cands %d pairs %lld allowed %lld\n", nc, (long long)F.np_all, (long long)kept);
+  *np = kept;
+  if (kept == 0) return PRB_OK;
+  if ((rc = sort_by_row_key(ctx->stream, F.sortTmp, RowKeyBits{0, F.key_bits}, F.keyB, F.keyA, F.valB.as<uint64_t>(), F.valA.as<uint64_t>(),
+                            (size_t)kept)))
+    return rc;
+  F.vals = F.valA.as<uint64_t>();
   return PRB_OK;
 }
 
@@ -381,7 +432,7 @@ static int seed_chunk_one_pass(SubSearch &s, const SeedChunk &c, int64_t np) {
   SearchWs::FrontStage &F = w.front;
   int rc;
   if ((rc = w.count.ensure(16))) return rc;
-  if ((rc = ctx->time_end("seed", 2))) return rc;
+  if ((rc = ctx->time_end("seed", s.allow ? 1 : 2))) return rc; // (under a pair mask the keys were counted in front of "allow")
   if ((rc = ctx->time_begin())) return rc;
   const int64_t nsl = fused_slices(np);
   if ((rc = w.hitsA.ensure((size_t)nsl * kFusePairs * kSliceRecBytes)) || (rc = w.row_count.ensure((size_t)(nsl + 1) * 4)) ||
@@ -389,7 +440,7 @@ static int seed_chunk_one_pass(SubSearch &s, const SeedChunk &c, int64_t np) {
     return rc;
   PRB_HIP(hipMemsetAsync(w.count.p, 0, 16, ctx->stream));
   PRB_HIP(hipMemsetAsync(w.row_count.as<int32_t>() + nsl, 0, 4, ctx->stream));
-  PRB_HIP(launch_seed_extend(F.cands.as<CandDev>(), F.valB.as<uint64_t>(), np, s.qb->view, s.pd, s.sc, s.eo, F.seed_qacc.as<double>(),
+  PRB_HIP(launch_seed_extend(F.cands.as<CandDev>(), F.vals, np, s.qb->view, s.pd, s.sc, s.eo, F.seed_qacc.as<double>(),
                              s.opts.interaction_threshold, s.max_qlen, w.hitsA.p, w.row_count.as<int32_t>(), w.count.as<uint64_t>(),
                              ctx->stream));
   if ((rc = scan_row_counts(ctx, w, nsl))) return rc;
@@ -442,8 +493,12 @@ static int seed_chunk_lists(SubSearch &s, const SeedChunk &c) {
     if ((rc = sort_by_row_key(ctx->stream, w.sortTmp, kb, w.kP, w.kTmp2, w.idxA.as<uint32_t>(), w.idxB.as<uint32_t>(), NR))) return rc;
     row_perm = w.idxB.as<uint32_t>();
   }
-  PRB_HIP(launch_seed_count(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
-                            w.row_count.as<int32_t>(), w.row_cand.as<int32_t>(), row_perm, ctx->stream));
+  if (s.allow)
+    PRB_HIP(launch_seed_count_allowed(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
+                                      w.row_count.as<int32_t>(), w.row_cand.as<int32_t>(), row_perm, *s.allow, ctx->stream));
+  else
+    PRB_HIP(launch_seed_count(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
+                              w.row_count.as<int32_t>(), w.row_cand.as<int32_t>(), row_perm, ctx->stream));
   if ((rc = scan_row_counts(ctx, w, crows))) return rc;
   int64_t nseed = 0;
   PRB_HIP(hipMemcpyAsync(&nseed, w.row_off.as<int64_t>() + crows, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -459,8 +514,12 @@ static int seed_chunk_lists(SubSearch &s, const SeedChunk &c) {
   }
   if ((rc = w.hitsA.ensure(hits_bytes(nseed)))) return rc;
   HitSoA A = carve_hits(w.hitsA, nseed);
-  PRB_HIP(launch_seed_emit(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
-                           w.row_cand.as<int32_t>(), w.row_off.as<int64_t>(), A, row_perm, ctx->stream));
+  if (s.allow)
+    PRB_HIP(launch_seed_emit_allowed(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
+                                     w.row_cand.as<int32_t>(), w.row_off.as<int64_t>(), A, row_perm, *s.allow, ctx->stream));
+  else
+    PRB_HIP(launch_seed_emit(w.cands.as<CandDev>(), nc, crows, s.qb->view, s.pd, delta, w.seed_qacc.as<double>(),
+                             w.row_cand.as<int32_t>(), w.row_off.as<int64_t>(), A, row_perm, ctx->stream));
   if ((rc = ctx->time_end("seed", 2))) return rc;
   if (s.last_stage == 1) return download_hits(ctx, w, A, nseed, s.hs->hits);
   // ---- ungapped extension; hits above the -f threshold are dropped before the sort (they cannot survive the filter) ----
@@ -506,9 +565,17 @@ static int seeds_to_hits(SubSearch &s) {
         PRB_HIP(hipStreamWaitEvent(s.ctx->stream, F.done, 0));
       } else {
         if (F.ahead) PRB_HIP(hipStreamSynchronize(F.stream)); // (not what was expected: its buffers are taken over)
-        if ((rc = issue_front(w, s.qb, s.pd, s.eo.delta, s.k.row_shift, cd + c0, c.nc, c.cents, s.ctx->stream, &np))) return rc;
+        if ((rc = issue_front(w, s.qb, s.pd, s.eo.delta, s.k.row_shift, cd + c0, c.nc, c.cents, s.ctx->stream, &np, s.allow, s.ctx))) return rc;
       }
       F.ahead = false;
+      if (np >= 0 && F.unsorted) {
+        if ((rc = finish_front(s.ctx, w, s.k, c.nc, &np))) return rc;
+        if (np == 0) { // the mask leaves nothing of the chunk: no sort, no extension
+          if ((rc = s.ctx->time_end("seed", 0))) return rc;
+          c0 = c.c1;
+          continue;
+        }
+      }
     }
     if ((rc = np >= 0 ? seed_chunk_one_pass(s, c, np) : seed_chunk_lists(s, c))) return rc;
     c0 = c.c1;
@@ -1116,6 +1183,9 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
   if (int rc = check_search_args(fn, ctx, qb, db, page, opts, last_stage)) return rc;
   *out = nullptr;
   PRB_HIP(hipSetDevice(ctx->device));
+  AllowDev allow{};
+  if (opts->allowed_pairs)
+    if (int rc = use_pairmask(fn, ctx, qb, db, page, opts->allowed_pairs, &allow)) return rc;
   {
     // the page on the device (uploaded now unless it is resident or was prefetched), then - while it is searched -
     // the next page on the copy stream
@@ -1175,6 +1245,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
                 hs,
                 0,
                 0};
+  if (opts->allowed_pairs) ps.allow = &allow;
   for (int32_t q = 0; q < nq; q++) ps.max_qlen = std::max(ps.max_qlen, qb->len[q]);
   for (int32_t L : ps.pg.seq_length) ps.max_dblen = std::max(ps.max_dblen, L);
   CandBatch next; // the sub-batch behind the current one, when it has been prepared ahead (next.q1 > next.q0)
@@ -1208,7 +1279,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
       const int64_t cents = (c1 < nb.ncand ? nb.cd[c1].qoff : nb.nqent) - nb.cd[0].qoff;
       SearchWs::FrontStage &F = wsp.front;
       int64_t np = -1;
-      if (issue_front(wsp, qb, ps.pd, delta, knobs.row_shift, nb.cd, c1, cents, F.stream, &np) != PRB_OK || np < 0 ||
+      if (issue_front(wsp, qb, ps.pd, delta, knobs.row_shift, nb.cd, c1, cents, F.stream, &np, ps.allow, nullptr) != PRB_OK || np < 0 ||
           hipEventRecord(F.done, F.stream) != hipSuccess) {
         (void)hipStreamSynchronize(F.stream); // (whatever part of it was issued is not used)
         return;

@@ -67,6 +67,7 @@ struct prb_ctx {
   prb::StageTimer targets_timer; // the merges of prb_search_page_targets and prb_targetset_merge (stage "targets"), likewise
   prb::StageTimer distinct_timer; // the selection of opts->distinct_sites (stage "distinct"), likewise
   prb::StageTimer chain_timer; // the selection of opts->chain_sites (stage "chain"), likewise
+  prb::StageTimer allow_timer; // the test and compaction of the pairs under opts->allowed_pairs (stage "allow"), likewise
   prb::StageTimer coverage_timer; // the merges, the join and the finish of the coverage table (stage "coverage"), likewise
 
   int time_begin();

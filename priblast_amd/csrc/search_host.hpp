@@ -72,6 +72,15 @@ struct SearchWs {
     const CandDev *cd = nullptr;
     int32_t nc = 0;
     int64_t np = 0;
+    const uint64_t *vals = nullptr; // the sorted values (valB; under a pair mask valA: the compaction writes valB)
+    // Under a pair mask (issue_front): a ballot word, a count and its scanned offset per 64 pairs, and the number of
+    // allowed pairs on its way to the host.  The sort takes that number, so a front issued ahead stops behind the
+    // compaction; finish_front sorts what is left when the chunk is taken up.
+    DevBuf ballot, wcount, woff, scanTmp;
+    PinnedBuf kept_pin;
+    bool unsorted = false;      // the compacted pairs are still to be sorted
+    int key_bits = 0;           // ... by keys of this many bits
+    int64_t np_all = 0;         // the chunk's pairs before the compaction
     int init() {
       if (stream) return PRB_OK;
       int lo = 0, hi = 0;
@@ -90,8 +99,9 @@ struct SearchWs {
         (void)hipEventDestroy(done);
         stream = nullptr;
       }
-      for (DevBuf *b : {&cands, &seed_qacc, &pair0, &keyA, &keyB, &valA, &valB, &sortTmp}) b->release();
+      for (DevBuf *b : {&cands, &seed_qacc, &pair0, &keyA, &keyB, &valA, &valB, &sortTmp, &ballot, &wcount, &woff, &scanTmp}) b->release();
       pair0_pin.release();
+      kept_pin.release();
       ahead = false;
     }
   } front;
@@ -356,7 +366,31 @@ struct prb_qbatch {
   std::unique_ptr<prb::SeedPlan> plan; // a seed search started ahead of prb_search_page, if any
 };
 
+// prb_pairmask_create .. prb_pairmask_free (capi_pairmask.hip): the pairs a search of `qb` against `db` is restricted to.
+// The bits are set on the host; the first search that uses the mask uploads them (use_pairmask) and closes it to changes.
+struct prb_pairmask {
+  prb_ctx *ctx = nullptr;
+  const prb_qbatch *qb = nullptr;
+  const prb_db *db = nullptr;
+  int32_t nq = 0;
+  std::vector<int64_t> tbase; // [npages + 1] the first target of every page; back() = the targets
+  int64_t row_words = 0;      // 32-bit words per query
+  std::vector<uint32_t> bits; // [nq * row_words]
+  int64_t count = 0;          // bits set
+  bool used = false;
+  std::mutex first_use;       // the upload, whoever comes first
+  prb::DevBuf dev;
+  ~prb_pairmask() {
+    if (dev.p) (void)hipSetDevice(ctx->device);
+    dev.release();
+  }
+};
+
 namespace prb {
+// capi_pairmask.hip: opts->allowed_pairs checked against the search it is given to (PRB_ERR_ARG with `fn` in the message)
+// and, at its first use, uploaded; *view = the mask as the kernels take it for `page`.  Not called for NULL.
+int use_pairmask(const char *fn, prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, const prb_pairmask *pm, AllowDev *view);
+
 // What the five result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset): whose
 // they are, whether they can still be merged into, and the block on the device that the merges work on.  What every
 // prb_*_merge and prb_*_finish checks (capi_tables.hpp) and what search_page hands to the emit_* of its mode.

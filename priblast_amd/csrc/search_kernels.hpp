@@ -76,6 +76,17 @@ struct CandDev { // SeedCandidate + first row of the candidate (one row per db S
   int64_t qoff; // first of the candidate's ep_q - sp_q + 1 entries in the query-side window sums
 };
 
+// The pairs a search is restricted to (prb_pairmask, include/priblast_hip.h): a bit per (query of the batch, target of
+// the database), row q at bits + q * row_words; tbase = the number of the first target of the page being searched
+struct AllowDev {
+  const uint32_t *bits;
+  int64_t row_words, tbase;
+};
+__host__ __device__ inline bool pair_allowed(const AllowDev &a, int query, int db_id) {
+  const int64_t t = a.tbase + db_id;
+  return (a.bits[(int64_t)query * a.row_words + (t >> 5)] >> (t & 31)) & 1u;
+}
+
 struct HitSoA {
   int32_t *q_sp, *db_sp, *q_len, *db_len, *db_id, *db_id_start, *query;
   double *e_acc, *e_hyb, *e_tot;
@@ -117,6 +128,15 @@ hipError_t launch_seed_count(const CandDev *cands, int32_t ncand, int64_t nrows,
 hipError_t launch_seed_emit(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
                             int delta, const double *qacc, const int32_t *row_cand, const int64_t *row_off, HitSoA hits,
                             const uint32_t *row_perm, hipStream_t s);
+// The same two passes under a pair mask: a row - one (candidate, database entry), so one (query, target) pair - that is
+// not allowed counts no seed, and the emit pass skips the rows that counted none.  (Kernels of their own: the passes
+// above are what they were.)
+hipError_t launch_seed_count_allowed(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
+                                     int delta, const double *qacc, int32_t *row_count, int32_t *row_cand, const uint32_t *row_perm,
+                                     const AllowDev &allow, hipStream_t s);
+hipError_t launch_seed_emit_allowed(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
+                                    int delta, const double *qacc, const int32_t *row_cand, const int64_t *row_off, HitSoA hits,
+                                    const uint32_t *row_perm, const AllowDev &allow, hipStream_t s);
 
 // ============================================================================ ungapped_kernels.hip: ungapped extension
 // the walk on a list of seed hits, in place
@@ -131,6 +151,15 @@ hipError_t launch_blk_seq(const PageDev &pg, int32_t *blk_seq, hipStream_t s);
 constexpr int64_t kMaxFusedCands = 1 << 20, kMaxFusedEntries = 1 << 12;
 hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t ncand, int64_t npairs, const PageDev &pg, int qmin,
                             int shift, int dbits, bool wide, void *key, uint64_t *val, hipStream_t s);
+// Under a pair mask, between launch_pair_keys and the sort: the pairs whose (query, target) is allowed, compacted in
+// order.  launch_allow_test: pair p's bit - the query of its candidate, the sequence of its database entry (sa_seq) - as
+// one ballot word and one count per 64 pairs (allow_words(npairs) of each, and one more count, a zero, for the scan);
+// launch_allow_scatter: behind the exclusive scan `off` of the counts, the allowed pairs' keys and values to their places.
+inline int64_t allow_words(int64_t npairs) { return (npairs + 63) / 64; }
+hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const uint64_t *val, int64_t npairs, const PageDev &pg,
+                             const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s);
+hipError_t launch_allow_scatter(const void *key_in, const uint64_t *val_in, int64_t npairs, bool wide, const uint64_t *ballot,
+                                const int64_t *off, void *key_out, uint64_t *val_out, hipStream_t s);
 // A workgroup takes kFusePairs pairs and keeps what survives in its slice of `slices` (kFusePairs records of
 // kSliceRecBytes each), slice_count[b] of them; nseed[0] += seeds, nseed[1] = max(nseed[1], length of the longest hit
 // kept).  launch_collect_slices packs the slices into `out` (slice b at slice_off[b] = the exclusive scan of the counts).

@@ -58,6 +58,7 @@ struct PageSearch {
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
+  const AllowDev *allow = nullptr; // opts.allowed_pairs on the device, for this page; nullptr: every pair
 };
 
 // the candidates of a sub-batch: queries [q0, q1), in page-locked memory, rows and query entries numbered from 0

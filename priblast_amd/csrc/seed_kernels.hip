@@ -54,12 +54,15 @@ __global__ __launch_bounds__(kBlock) void k_seed_qacc(const CandDev *__restrict_
 // With `row_perm` the threads take the rows in that order (rows sorted by query and database position, see
 // k_row_key): thread t works on row row_perm[t], whose candidate k_row_key has left in row_cand; counts and offsets
 // are indexed by t.
-template <bool kEmit>
+// `allow` (none, or one AllowDev - the instantiations without one are the kernels they were): a row whose (query, target)
+// is not allowed counts no seed; the emit pass leaves out the rows that counted none.
+template <bool kEmit, class... Allow>
 __global__ __launch_bounds__(kBlock) void k_seed(const CandDev *__restrict__ cands, int ncand, int64_t nrows, QBatchDev qb,
                                                  PageDev pg, int delta, const double *__restrict__ qacc,
                                                  int32_t *__restrict__ row_count, int32_t *__restrict__ row_cand,
                                                  const int64_t *__restrict__ row_off, HitSoA hits,
-                                                 const uint32_t *__restrict__ row_perm) {
+                                                 const uint32_t *__restrict__ row_perm, Allow... allow) {
+  static_assert(sizeof...(Allow) <= 1, "at most one mask");
   __shared__ int64_t s_row0[kBlock + 1];
   __shared__ int s_c0;
   const int64_t slot = (int64_t)blockIdx.x * kBlock + threadIdx.x; // index of the row's count / offset
@@ -89,6 +92,14 @@ __global__ __launch_bounds__(kBlock) void k_seed(const CandDev *__restrict__ can
   const int k = c.sp_db + (int)(row - c.row0);
   const int db_sp = pg.sa[k];
   const int id = pg.sa_seq[k];
+  if constexpr (sizeof...(Allow) > 0) {
+    if (kEmit) {
+      if (row_off[slot + 1] == row_off[slot]) return; // (row_off has a total behind the last row)
+    } else if (!(pair_allowed(allow, c.query, id) && ...)) {
+      row_count[slot] = 0;
+      return;
+    }
+  }
   const int st = pg.seq_length[id] - (db_sp - pg.start_pos[id]) - c.length;
   const int64_t base = (int64_t)pg.start_pos[id] - id;
   const double dba = window_acc(pg.acc + base, pg.cond + base, st, c.length, delta);
@@ -181,6 +192,18 @@ hipError_t launch_seed_emit(const CandDev *cands, int32_t ncand, int64_t nrows, 
                             const uint32_t *row_perm, hipStream_t s) {
   return launch_1d(k_seed<true>, nrows, kBlock, 0, s, cands, ncand, nrows, qb, pg, delta, qacc, (int32_t *)nullptr,
                    const_cast<int32_t *>(row_cand), row_off, hits, row_perm);
+}
+hipError_t launch_seed_count_allowed(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
+                                     int delta, const double *qacc, int32_t *row_count, int32_t *row_cand, const uint32_t *row_perm,
+                                     const AllowDev &allow, hipStream_t s) {
+  return launch_1d(k_seed<false, AllowDev>, nrows, kBlock, 0, s, cands, ncand, nrows, qb, pg, delta, qacc, row_count, row_cand,
+                   (const int64_t *)nullptr, HitSoA{}, row_perm, allow);
+}
+hipError_t launch_seed_emit_allowed(const CandDev *cands, int32_t ncand, int64_t nrows, const QBatchDev &qb, const PageDev &pg,
+                                    int delta, const double *qacc, const int32_t *row_cand, const int64_t *row_off, HitSoA hits,
+                                    const uint32_t *row_perm, const AllowDev &allow, hipStream_t s) {
+  return launch_1d(k_seed<true, AllowDev>, nrows, kBlock, 0, s, cands, ncand, nrows, qb, pg, delta, qacc, (int32_t *)nullptr,
+                   const_cast<int32_t *>(row_cand), row_off, hits, row_perm, allow);
 }
 
 } // namespace prb

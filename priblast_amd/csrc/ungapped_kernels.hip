@@ -342,6 +342,44 @@ __global__ __launch_bounds__(kBlock) void k_pair_key(const CandDev *__restrict__
   val[p] = (uint64_t)db_sp | ((uint64_t)(uint32_t)ci << 32) | ((uint64_t)jrel << (32 + kPairCandBits));
 }
 
+__device__ __forceinline__ int pair_cand(uint64_t v) { return (int)((v >> 32) & ((1u << kPairCandBits) - 1)); }
+
+// Under a pair mask (AllowDev): which of the chunk's pairs are searched at all.  Pair p's query is its candidate's, its
+// target the sequence of its database SA entry (sa_seq; the entry from p's place among its candidate's pairs, as
+// k_pair_key numbers them).  A wavefront's 64 answers are one ballot: the word and its population count are all that is
+// written, so the scatter behind the scan of the counts reads no candidate and no bit of the mask again, the order of
+// the pairs is kept and the result does not depend on how the wavefronts are scheduled.
+__global__ __launch_bounds__(kBlock) void k_allow_test(const CandDev *__restrict__ cands, const int64_t *__restrict__ pair0,
+                                                       const uint64_t *__restrict__ val, int64_t npairs, PageDev pg, AllowDev allow,
+                                                       uint64_t *__restrict__ ballot, int32_t *__restrict__ count) {
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  bool ok = false;
+  if (p < npairs) {
+    const int ci = pair_cand(val[p]);
+    const CandDev c = cands[ci];
+    const uint32_t pl = (uint32_t)(p - pair0[ci]), qw = (uint32_t)(c.ep_q - c.sp_q + 1);
+    ok = pair_allowed(allow, c.query, pg.sa_seq[c.sp_db + (int)(pl / qw)]);
+  }
+  const unsigned long long m = __ballot(ok);
+  if ((threadIdx.x & 63) == 0 && p < npairs) {
+    ballot[p >> 6] = m;
+    count[p >> 6] = __popcll(m);
+  }
+}
+template <class Key>
+__global__ __launch_bounds__(kBlock) void k_allow_scatter(const Key *__restrict__ key_in, const uint64_t *__restrict__ val_in, int64_t npairs,
+                                                          const uint64_t *__restrict__ ballot, const int64_t *__restrict__ off,
+                                                          Key *__restrict__ key_out, uint64_t *__restrict__ val_out) {
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= npairs) return;
+  const uint64_t m = ballot[p >> 6];
+  const int lane = (int)(p & 63);
+  if (!(m >> lane & 1)) return;
+  const int64_t at = off[p >> 6] + __popcll(m & ((1ull << lane) - 1));
+  key_out[at] = key_in[p];
+  val_out[at] = val_in[p];
+}
+
 // What a workgroup keeps goes to ITS slice of a sparse list (kFusePairs records, one per pair it takes: no bound to
 // check), the position from a counter in LDS; k_collect_slices then packs the used part of every slice into the list
 // proper.  (One global counter for all wavefronts - an atomic add with return per 64 pairs - serialised the whole
@@ -363,8 +401,6 @@ struct FuseArgs {
   unsigned long long *nseed; // [0] += seeds, [1] = max(., length of the longest hit kept)
   int qcap;
 };
-
-__device__ __forceinline__ int pair_cand(uint64_t v) { return (int)((v >> 32) & ((1u << kPairCandBits) - 1)); }
 
 constexpr int kFusePer = kFusePairs / kBlock;
 static_assert(kFusePer * kBlock == kFusePairs, "pairs per workgroup");
@@ -524,6 +560,18 @@ hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t 
   if (wide)
     return launch_1d(k_pair_key<uint64_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, shift, dbits, (uint64_t *)key, val);
   return launch_1d(k_pair_key<uint32_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, shift, dbits, (uint32_t *)key, val);
+}
+hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const uint64_t *val, int64_t npairs, const PageDev &pg,
+                             const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s) {
+  return launch_1d(k_allow_test, npairs, kBlock, 0, s, cands, pair0, val, npairs, pg, allow, ballot, count);
+}
+hipError_t launch_allow_scatter(const void *key_in, const uint64_t *val_in, int64_t npairs, bool wide, const uint64_t *ballot,
+                                const int64_t *off, void *key_out, uint64_t *val_out, hipStream_t s) {
+  if (wide)
+    return launch_1d(k_allow_scatter<uint64_t>, npairs, kBlock, 0, s, (const uint64_t *)key_in, val_in, npairs, ballot, off, (uint64_t *)key_out,
+                     val_out);
+  return launch_1d(k_allow_scatter<uint32_t>, npairs, kBlock, 0, s, (const uint32_t *)key_in, val_in, npairs, ballot, off, (uint32_t *)key_out,
+                   val_out);
 }
 hipError_t launch_seed_extend(const CandDev *cands, const uint64_t *vals, int64_t npairs, const QBatchDev &qb, const PageDev &pg,
                               const SearchConst &sc, ExtOpts o, const double *qacc, double thr, int max_query_len, void *slices,

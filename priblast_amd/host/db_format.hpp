@@ -37,6 +37,10 @@ struct DbHeader {
 // returns "" or an error message
 std::string read_db(const std::string &prefix, DbHeader &hdr, std::vector<DbPage> &pages);
 
+// Only the names of the sequences, page by page (names[page][id]): the page sizes from .seq, whose texts are skipped,
+// and the lines of .nam; nothing else is read.  Returns "" or an error message.
+std::string read_db_names(const std::string &prefix, std::vector<std::vector<std::string>> &names);
+
 // k-mer lookup table of a page (db_construction.cpp:337-369): SA interval of every string of
 // length <= hash_size over {A,C,G,U}; absent k-mers are stored as (1, 0).
 void build_kmer_table(const std::vector<uint8_t> &text, const std::vector<int32_t> &sa, int hash_size,

@@ -77,6 +77,7 @@
 #include <vector>
 
 #include "../../include/priblast_hip.h"
+#include "db_format.hpp"
 #include "fasta.hpp"
 #include "output.hpp"
 
@@ -142,6 +143,11 @@ void usage() {
             "              coverage and where it peaks, the minimum interaction energy and its hit, written at the end of\n"
             "              the run by page, target and start (1 <= INT <= 1000000; not with -t, -n, -q, -k, -b, -r, nor with\n"
             "              WORLD_SIZE > 1; -u and -j combine)\n"
+            "    -L STR    search only the query-target pairs listed in the file STR: one pair per line, query name, a tab,\n"
+            "              target name, as the result lines print them; `*` as the query name means every query; empty lines\n"
+            "              and lines that begin with # are skipped.  The seeds of all other pairs are dropped on the GPU, so\n"
+            "              the stages behind cost what the listed pairs cost; the lines are lines of the run without -L (a\n"
+            "              query's first line may list its base pairs in another order).  With every other switch\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -195,6 +201,8 @@ std::string described(int s) { return std::string("-") + kSwitchTable[s].letter 
 
 struct Args {
   std::string in, out, db, tmp;
+  std::string pairlist; // -L
+  bool have_pairlist = false;
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
@@ -242,6 +250,7 @@ struct BatchJob {
 // A batch with its accessibilities computed, ready to be searched.
 struct Prepared {
   prb_qbatch *qb = nullptr;
+  prb_pairmask *mask = nullptr; // -L: the listed pairs of its queries
   std::vector<int32_t> qlen_unmasked;
   std::vector<int32_t> ids; // its queries' positions in the input file (-r: their identifiers in the table)
 };
@@ -496,8 +505,17 @@ struct Rendezvous {
 };
 
 // ---- the run: what the steps of ris_main fill in, one after the other, and the workers read --------
+// -L: the listed pairs, by the query's place in the input file (`of_query`) and for every query (`every`: the `*`
+// lines), as targets numbered page by page; page_first[p] = the first target of page p
+struct PairList {
+  std::vector<std::vector<int64_t>> of_query;
+  std::vector<int64_t> every;
+  std::vector<int64_t> page_first; // [npages + 1]
+};
+
 struct Run {
   Args a;
+  PairList list;
   std::vector<std::string> names, seqs; // the queries
   int world = 1, rank = 0;              // one process per GPU?  (torchrun / mpirun style environment)
   bool rank_mode = false;
@@ -551,7 +569,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -574,6 +592,7 @@ Args parse_args(int argc, char **argv) {
     case 'k': a.given[kK] = true, a.tophits = parse_count(optarg); break;
     case 'r': a.given[kR] = true, a.targets = parse_count(optarg); break;
     case 'c': a.given[kC] = true, a.depth = parse_count(optarg); break;
+    case 'L': a.have_pairlist = true, a.pairlist = optarg; break;
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -584,6 +603,78 @@ Args parse_args(int argc, char **argv) {
   check_switches(a);
   a.mode = output_mode(a);
   return a;
+}
+
+// -L FILE: every line checked and turned into targets per query; any fault ends the run here, before any GPU work
+void load_pairlist(Run &r) {
+  if (!r.a.have_pairlist) return;
+  std::FILE *f = std::fopen(r.a.pairlist.c_str(), "r");
+  if (!f) die("Error: can't open the pair list (-L): " + r.a.pairlist);
+  std::string text;
+  char buf[1 << 16];
+  size_t got;
+  while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  const bool bad = std::ferror(f) != 0;
+  std::fclose(f);
+  if (bad) die("Error: can't read the pair list (-L): " + r.a.pairlist);
+  std::vector<std::vector<std::string>> pages;
+  if (const std::string err = prb::read_db_names(r.a.db, pages); !err.empty()) die(err); // (no GPU is needed to refuse a list)
+  PairList &pl = r.list;
+  std::multimap<std::string, int64_t> target_of, query_of; // a name that occurs several times matches all of them
+  pl.page_first.assign(1, 0);
+  for (const auto &pg : pages) {
+    for (const std::string &n : pg) target_of.emplace(n, pl.page_first.back() + (int64_t)(&n - pg.data()));
+    pl.page_first.push_back(pl.page_first.back() + (int64_t)pg.size());
+  }
+  for (size_t q = 0; q < r.names.size(); q++) query_of.emplace(r.names[q], (int64_t)q);
+  pl.of_query.resize(r.names.size());
+  int64_t allowed = 0;
+  size_t lineno = 0;
+  for (size_t at = 0; at < text.size();) {
+    size_t end = text.find('\n', at);
+    if (end == std::string::npos) end = text.size();
+    std::string line = text.substr(at, end - at);
+    at = end + 1;
+    lineno++;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    const size_t tab = line.find('\t');
+    if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos)
+      die("Error: pair list line " + std::to_string(lineno) + ": expected query name, one tab, target name");
+    const std::string qn = line.substr(0, tab), tn = line.substr(tab + 1);
+    const auto tr = target_of.equal_range(tn);
+    if (qn != "*" && query_of.find(qn) == query_of.end()) die("Error: pair list line " + std::to_string(lineno) + ": no query is named \"" + qn + "\"");
+    if (tr.first == tr.second) die("Error: pair list line " + std::to_string(lineno) + ": no database sequence is named \"" + tn + "\"");
+    for (auto t = tr.first; t != tr.second; ++t) {
+      if (qn == "*") {
+        pl.every.push_back(t->second);
+      } else {
+        const auto qr = query_of.equal_range(qn);
+        for (auto q = qr.first; q != qr.second; ++q) pl.of_query[(size_t)q->second].push_back(t->second);
+      }
+      allowed++;
+    }
+  }
+  if (allowed == 0) die("Error: the pair list (-L) allows no pair: " + r.a.pairlist);
+}
+
+// -L: the mask of a prepared batch's queries (input positions `ids`)
+prb_pairmask *batch_mask(const Run &r, prb_ctx *c, const prb_qbatch *qb, const prb_db *db, const std::vector<int32_t> &ids) {
+  const PairList &pl = r.list;
+  std::vector<int32_t> query, page, db_id;
+  auto add = [&](int32_t q, int64_t t) {
+    const size_t p = (size_t)(std::upper_bound(pl.page_first.begin(), pl.page_first.end(), t) - pl.page_first.begin()) - 1;
+    query.push_back(q);
+    page.push_back((int32_t)p);
+    db_id.push_back((int32_t)(t - pl.page_first[p]));
+  };
+  for (int64_t t : pl.every) add(-1, t);
+  for (size_t k = 0; k < ids.size(); k++)
+    for (int64_t t : pl.of_query[(size_t)ids[k]]) add((int32_t)k, t);
+  prb_pairmask *m = nullptr;
+  if (prb_pairmask_create(c, qb, db, &m) || prb_pairmask_allow(m, (int64_t)query.size(), query.data(), page.data(), db_id.data()))
+    die(std::string("Error: ") + prb_last_error());
+  return m;
 }
 
 int env_int(const char *a, const char *b, int dflt) {
@@ -786,7 +877,15 @@ Prepared prepare_batch(const Run &r, prb_ctx *c, const prb_db *db, size_t b, int
   p.qlen_unmasked.resize(idx.size());
   for (size_t q = 0; q < idx.size(); q++) p.qlen_unmasked[q] = prb_qbatch_length_unmasked(p.qb, (int32_t)q);
   p.ids.assign(idx.begin(), idx.end());
+  if (r.a.have_pairlist) p.mask = batch_mask(r, c, p.qb, db, p.ids);
   return p;
+}
+// a searched batch's queries and mask let go
+void release_batch(Prepared &p) {
+  prb_qbatch_destroy(p.qb);
+  prb_pairmask_free(p.mask);
+  p.qb = nullptr;
+  p.mask = nullptr;
 }
 
 // -t -n, -q, -k: a table per batch; every page is searched and merged into it on the device by `search`, then one copy
@@ -834,24 +933,25 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
 // one page of a prepared batch searched: into the table of `mine` (-r: into the worker's), or - a hit set or a pair set -
 // into slot `page` of `out`
 void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, BatchResult &mine, BatchResult &out) {
-  const Args &a = r.a;
   prb_qbatch *qb = p.qb;
+  prb_ris_opts o = r.a.o; // the run's options with the batch's own mask (-L)
+  o.allowed_pairs = p.mask;
   int rc = 0;
-  switch (a.mode) {
-  case OutputMode::kTargets: rc = prb_search_page_targets(w.ctx, qb, w.db, page, &a.o, p.ids.data(), w.targets); break;
-  case OutputMode::kCoverage: rc = prb_search_page_coverage(w.ctx, qb, w.db, page, &a.o, p.ids.data(), w.coverage); break;
-  case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &a.o, mine.top.get()); break;
-  case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &a.o, mine.prof.get()); break;
-  case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &a.o, mine.tophits.get()); break;
+  switch (r.a.mode) {
+  case OutputMode::kTargets: rc = prb_search_page_targets(w.ctx, qb, w.db, page, &o, p.ids.data(), w.targets); break;
+  case OutputMode::kCoverage: rc = prb_search_page_coverage(w.ctx, qb, w.db, page, &o, p.ids.data(), w.coverage); break;
+  case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &o, mine.top.get()); break;
+  case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &o, mine.prof.get()); break;
+  case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &o, mine.tophits.get()); break;
   case OutputMode::kSummary: {
     prb_pairset *ps = nullptr;
-    rc = prb_search_page_summary(w.ctx, qb, w.db, page, &a.o, &ps);
+    rc = prb_search_page_summary(w.ctx, qb, w.db, page, &o, &ps);
     out.pair_pages[(size_t)page].reset(ps);
     break;
   }
   case OutputMode::kHits: {
     prb_hitset *hs = nullptr;
-    rc = prb_search_page(w.ctx, qb, w.db, page, &a.o, 3, &hs);
+    rc = prb_search_page(w.ctx, qb, w.db, page, &o, 3, &hs);
     out.pages[(size_t)page].reset(hs);
     break;
   }
@@ -899,8 +999,7 @@ BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
   for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
   finish_table(r, w, res);
   note_target_queries(r, w, p);
-  prb_qbatch_destroy(p.qb);
-  p.qb = nullptr;
+  release_batch(p);
   return res;
 }
 
@@ -1206,8 +1305,7 @@ struct Team {
       wait([&] { return tb->taken; });
       mine = BatchResult(); // (its table, empty by now, freed by its own worker)
     }
-    prb_qbatch_destroy(p.qb);
-    p.qb = nullptr;
+    release_batch(p);
     leave(b, *tb);
     return res;
   }
@@ -1419,6 +1517,7 @@ int ris_main(int argc, char **argv) {
   r.a = parse_args(argc, argv);
   const std::string err = prb::read_fasta(r.a.in, r.names, r.seqs);
   if (!err.empty()) die(err);
+  load_pairlist(r);
   const std::vector<int> devices = rank_setup(r);
   split_setup(r);
   open_workers(r, devices);
