@@ -221,6 +221,25 @@ int prb_accessibility_tables(prb_ctx *ctx, const char *seq, int32_t len, int32_t
 /* ---- host helpers that are part of the seam (stage 2: encode + suffix array) ---- */
 int prb_encode_query(const char *seq, int32_t len, int32_t repeat_flag, uint8_t *enc /* len+1 */);
 int prb_suffix_array(const uint8_t *text, int32_t n, int32_t *sa);
+/* A decoy of a query, for an empirical null of its interaction energies (no GPU): decoy `decoy` of the sequence
+ * seq[0, len) that stands at place file_pos of its input file.  An Altschul-Erikson shuffle over the bytes as read - a
+ * lower-case, soft-masked letter is a symbol of its own - that keeps the first byte, the last byte and the count of every
+ * pair of adjacent bytes; out[0, len) (no NUL is added; `out` must not overlap `seq`).  len < 3 copies the input.
+ *   successors   per symbol, the bytes that follow its occurrences, in order of occurrence
+ *   last edges   for each symbol that occurs among seq[0, len - 1), other than seq[len - 1], in ascending byte value: one
+ *                entry of its list, drawn uniformly; all are drawn again until every such symbol reaches seq[len - 1]
+ *                through last edges
+ *   lists        per symbol: the LAST occurrence of the chosen edge is taken out, the rest shuffled (Fisher-Yates: for
+ *                i = k - 1 down to 1, j = draw(i + 1), swap i and j), the chosen edge put at the end; the symbol of
+ *                seq[len - 1] shuffles its whole list; symbols in ascending byte value
+ *   walk         from seq[0], every symbol's list consumed front to back
+ * Draws: splitmix64 (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31), draw(k) = next() % k.  The state starts at
+ * mix(mix(mix(seed) ^ (uint64_t)file_pos) ^ (uint64_t)decoy), mix(x) = the splitmix64 output for state x (the increment
+ * included): a decoy depends on the seed, its query and the query's place in its file only - not on how the queries are
+ * cut into batches.  tests/shuffle_ref.py restates all of it.  PRB_ERR_ARG: a NULL pointer with len > 0; len, file_pos
+ * or decoy below 0. */
+int prb_shuffle_sequence(const char *seq, int32_t len, uint64_t seed, int64_t file_pos, int32_t decoy, char *out);
 
 /* ---- database ---- */
 int prb_db_open(prb_ctx *ctx, const char *prefix, prb_db **out);

@@ -191,6 +191,7 @@ SYMBOLS = {
                                                c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_top_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                            c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_shuffle_sequence": (ctypes.c_int, [ctypes.c_char_p, c_i32, ctypes.c_uint64, c_i64, c_i32, ctypes.c_char_p]),
     "prb_write_target_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                               c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_write_profile_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
@@ -251,6 +252,15 @@ def suffix_array(text):
     sa = np.zeros(len(text), np.int32)
     _check(lib().prb_suffix_array(text.ctypes.data, len(text), sa.ctypes.data))
     return sa
+
+
+def shuffle_sequence(seq, seed=1, file_pos=0, decoy=0):
+    """prb_shuffle_sequence: the dinucleotide-preserving decoy of seq (str or bytes) -> the same type"""
+    raw = seq.encode("latin-1") if isinstance(seq, str) else bytes(seq)
+    out = ctypes.create_string_buffer(max(len(raw), 1))
+    _check(lib().prb_shuffle_sequence(raw, len(raw), seed, file_pos, decoy, out))
+    res = out.raw[:len(raw)]
+    return res.decode("latin-1") if isinstance(seq, str) else res
 
 
 def default_opts(**kw):

@@ -1,7 +1,8 @@
-// C ABI, host-only entry points (stage 2 of the seam: encode + suffix array; the CPU budget of the host thread pools).
+// C ABI, host-only entry points (stage 2 of the seam: encode + suffix array; dinucleotide-preserving decoys; the CPU budget of the host thread pools).
 #include "../../include/priblast_hip.h"
 #include "cpu_budget.hpp"
 #include "encoder.hpp"
+#include "shuffle.hpp"
 #include "suffix_array.hpp"
 
 extern "C" {
@@ -15,6 +16,16 @@ int prb_encode_query(const char *seq, int32_t len, int32_t repeat_flag, uint8_t 
 int prb_suffix_array(const uint8_t *text, int32_t n, int32_t *sa) {
   if (!text || !sa || n < 0) return PRB_ERR_ARG;
   prb::suffix_array(text, n, sa);
+  return PRB_OK;
+}
+
+int prb_shuffle_sequence(const char *seq, int32_t len, uint64_t seed, int64_t file_pos, int32_t decoy, char *out) {
+  if (len < 0 || file_pos < 0 || decoy < 0 || (len > 0 && (!seq || !out))) return PRB_ERR_ARG;
+  try {
+    prb::shuffle_sequence(seq, len, seed, file_pos, decoy, out);
+  } catch (...) { // (no exception leaves the C ABI)
+    return PRB_ERR_NOMEM;
+  }
   return PRB_OK;
 }
 
