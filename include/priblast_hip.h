@@ -197,6 +197,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   launches for the best hits: minimum energy, minimum tie, take-over, scratch reset; launches = 9 per sub-batch with
  *   final hits and per prb_covset_add_hits; prb_covset_finish: the two scans, the selection of the regions' heads and the
  *   region kernel, launches = 4, or 3 when there is no region; prb_covset_merge: 1);
+ * "null" (prb_search_page_observed / _decoys, prb_nullset_observe / _add_pairs: the scatter or the fold into the null
+ *   table, launches = 1 per sub-batch with final hits; prb_nullset_finish: the selection and the gather, launches = 2);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -627,6 +629,82 @@ const prb_target_region *prb_covset_regions(const prb_covset *cs);
 void prb_covset_counts(const prb_covset *cs, int64_t counts[3]);
 void prb_covset_free(prb_covset *cs);
 
+/* ---- an empirical p-value per pair from shuffled decoys (`ris -t -z N`): a null table on the device ----
+ * Raw energies are not comparable across queries - a long GC-rich query gets a low e_min against everything.  For one batch
+ * of real queries, one database and N decoys per query, the decoys of a query are
+ *     prb_shuffle_sequence(seq, len, seed, file_pos, decoy, out)   for decoy = 0 .. N - 1
+ * and the table holds, over everything merged into it:
+ *   observed   a pair (query q, target (page, db_id)) is OBSERVED when q has at least one final hit against the target; its
+ *              record `s` is the prb_pair_summary that prb_search_page_summary returns for it, field for field
+ *   null_hits  the number of decoys of q that have at least one final hit against the target
+ *   null_le    the number of those decoys whose e_min against the target is <= the observed e_min, compared as doubles
+ *              (-0.0 == +0.0); a decoy without a hit counts as +infinity, that is, nowhere
+ *   null_min   the smallest decoy e_min against the target (of -0.0 and +0.0 the latter is reported); +infinity when
+ *              null_hits == 0.  An integer atomic minimum over the order-preserving 64-bit key of the energy
+ *   decoys     N; the p-value is p = (null_le + 1) / (N + 1), computed in double on the host (prb_write_null_lines)
+ * Decoy pairs whose (owner, target) is not observed are counted nowhere.  Records come by query, then page, then db_id: an
+ * order of this mode's own, not the `-t` order.  Every column is an integer sum or a minimum over a total order, so the
+ * table is - bit for bit - independent of how the decoys are cut into batches and sub-batches, of the order of the pages
+ * and of the decoy batches, of PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS and page residency, and of whether the decoys were
+ * searched under a pair mask that allows (at least) the observed targets of their owners.
+ *   prb_nullset_create        an empty table for qb and db, 1 <= ndecoys <= 100000 (else PRB_ERR_ARG): one dense slot per
+ *                             (query, target of every page) of 96 B - the 64 B record, three 8 B counters, a flag - and
+ *                             1 B of selection flag, in HBM; PRB_ERR_NOMEM when that cannot be allocated, PRB_ERR_ARG for
+ *                             2^32 slots or more.  The table owns all its device memory and must be freed before its
+ *                             context, its batch and its database
+ *   prb_search_page_observed  the search of prb_search_page_summary of the real batch against `page`, its records
+ *                             scattered into the table on the device (nothing is copied to the host).  Argument checks and
+ *                             option limits are those of prb_search_page_summary.  The table was made with this context
+ *                             for this batch and this database; a page is observed once (else PRB_ERR_ARG)
+ *   prb_search_page_decoys    the same search of a batch dqb of decoys, its records folded into the counters on the
+ *                             device, one thread per record, integer atomics: owner[q] = the real query's index in the
+ *                             table's batch, decoy[q] = the decoy's number, 0 <= decoy[q] < ndecoys, for every query q of
+ *                             dqb.  The page must be observed first (else PRB_ERR_STATE); a (owner, decoy, page) triple is
+ *                             merged once, and an (owner, decoy) comes once per call (else PRB_ERR_ARG).  It honours
+ *                             opts->allowed_pairs (a mask made for dqb) like every search entry
+ *   prb_nullset_observe       the scatter of prb_search_page_observed for a caller's records of `page` in host memory
+ *   prb_nullset_add_pairs     the fold of prb_search_page_decoys for a caller's records (their `query` indexes owner[nq]
+ *                             and decoy[nq]); n = 0 only marks the decoys as merged.  Both take the refusals of the two
+ *                             search entries but for the options, and refuse (PRB_ERR_ARG) a record whose query or db_id is
+ *                             out of range, whose hits are below 1, or whose (query, db_id) comes twice in the list
+ *   prb_nullset_finish        PRB_ERR_STATE unless every (query, decoy, page) has been merged - a p-value never rests on
+ *                             fewer decoys than it says.  The observed slots are selected on the device, their records
+ *                             gathered there and copied to the host in one copy; the device memory is released.  Nothing
+ *                             can be merged after it (a second call does nothing)
+ *   prb_nullset_counts        the stage counts of prb_pairset_counts, summed over the observed pages;
+ *   prb_nullset_decoy_counts  the same over the decoy searches (under a pair mask counts[0] counts the allowed pairs' seeds)
+ * Every check of a call - owners, decoy numbers, the page, what is merged already - is made on the host before anything
+ * is enqueued: a refused call leaves the table untouched; a merge that fails part way leaves it unusable.  On the device
+ * every kernel checks its slot and each record's query, db_id, owner and decoy number against the table's ranges again;
+ * a violation raises the table's `bad` flag and writes nothing, and the next call on the table returns PRB_ERR_STATE.
+ * A table holds pages searched with one value of distinct_sites and of chain_sites (a second one is PRB_ERR_ARG).  There is
+ * no prb_nullset_merge: a batch belongs to one worker.  Stage timer "null": the scatter or the fold (launches = 1 per
+ * sub-batch with final hits, and per prb_nullset_observe / _add_pairs with records), and prb_nullset_finish: the selection
+ * and the gather (launches = 2, or 1 when no pair is observed). */
+typedef struct prb_null_pair {
+  prb_pair_summary s;   /* the observed pair */
+  int32_t page, decoys; /* the target's page; N */
+  int64_t null_hits, null_le;
+  double null_min;
+} prb_null_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_null_pair) == 96, "prb_null_pair: no padding");
+#endif
+typedef struct prb_nullset prb_nullset;
+int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t ndecoys, prb_nullset **out);
+int prb_search_page_observed(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_nullset *ns);
+int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *owner,
+                           const int32_t *decoy, prb_nullset *ns);
+int prb_nullset_observe(prb_ctx *ctx, prb_nullset *ns, int32_t page, const prb_pair_summary *pairs, int64_t n);
+int prb_nullset_add_pairs(prb_ctx *ctx, prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t nq,
+                          const prb_pair_summary *pairs, int64_t n);
+int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns);
+int64_t prb_nullset_size(const prb_nullset *ns);
+const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns);
+void prb_nullset_counts(const prb_nullset *ns, int64_t counts[3]);
+void prb_nullset_decoy_counts(const prb_nullset *ns, int64_t counts[3]);
+void prb_nullset_free(prb_nullset *ns);
+
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered
  * from id0 on (the `Id` column; MergeOutput, rna_interaction_search.cpp:464-476), written to the file
@@ -676,6 +754,13 @@ int prb_write_profile_lines(const prb_db *db, int32_t nq, const char *const *qna
  * query's identifier (nq_total of them: every `query` lies below it). */
 int prb_write_region_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
                            const prb_target_region *regions, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
+/* The lines of `ris -t -z N` for one batch: recs[0, n) as prb_nullset_pairs returns them (by query, then page, then
+ * db_id), one line each in that order, numbered from id0 on: the `-t` line of the observed pair, and behind it
+ *   ,Decoys,NullHits,NullLE,NullMin,PValue
+ * NullMin in the result lines' energy form, or NA when NullHits is 0; PValue = (NullLE + 1) / (Decoys + 1) in double,
+ * printed as %.6g. */
+int prb_write_null_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_null_pair *recs,
+                         int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

@@ -71,6 +71,12 @@ REGION_DTYPE = np.dtype([("page", "<i4"), ("db_id", "<i4"), ("start", "<i4"), ("
                          ("reserved", "<i4"), ("bp_first", "<i4", (2,)), ("bp_last", "<i4", (2,))])
 assert REGION_DTYPE.itemsize == 72
 
+# prb_null_pair: the embedded prb_pair_summary's fields (the observed pair), then its page, the decoys per query and the
+# null counters (`ris -t -z N`)
+NULL_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("decoys", "<i4"), ("null_hits", "<i8"), ("null_le", "<i8"),
+                                          ("null_min", "<f8")])
+assert NULL_DTYPE.itemsize == 96
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -178,6 +184,21 @@ SYMBOLS = {
     "prb_covset_regions": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_covset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_covset_free": (None, [ctypes.c_void_p]),
+    "prb_nullset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_observed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_search_page_decoys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_nullset_observe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64]),
+    "prb_nullset_add_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, ctypes.c_void_p, c_i32,
+                                             ctypes.c_void_p, c_i64]),
+    "prb_nullset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_nullset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_nullset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_nullset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_nullset_decoy_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_nullset_free": (None, [ctypes.c_void_p]),
+    "prb_write_null_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                            c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -754,6 +775,116 @@ def search_coverage(ctx, db, d, batches, opts=None, pages=None, with_counts=Fals
     return (recs, counts) if with_counts else recs
 
 
+class NullSet(_Table):
+    """prb_nullset: per observed (query, target) pair of one batch, how the query's decoys fare against the target, in a
+    table on the device: the real batch is observed page by page, then its decoys are merged batch by batch.  Close it
+    before its context."""
+    PREFIX = "nullset"
+
+    def __init__(self, ctx, qb, db, ndecoys):
+        h = ctypes.c_void_p()
+        _check(lib().prb_nullset_create(ctx.h, qb.h, db.h, ndecoys, ctypes.byref(h)))
+        self.h, self.ctx, self.qb, self.db = h, ctx, qb, db
+
+    def observed(self, page, opts=None):
+        """prb_search_page_observed: the real batch against `page`"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_observed(self.ctx.h, self.qb.h, self.db.h, page, ctypes.byref(o), self.h))
+
+    def decoys(self, dqb, page, owner, decoy, opts=None):
+        """prb_search_page_decoys: the batch dqb of decoys against `page`; owner[q] / decoy[q] = the real query and the decoy
+        number of its query q"""
+        o = opts or default_opts()
+        owner, decoy = np.ascontiguousarray(owner, np.int32), np.ascontiguousarray(decoy, np.int32)
+        assert len(owner) == len(decoy) == len(dqb.lens)
+        _check(lib().prb_search_page_decoys(self.ctx.h, dqb.h, self.db.h, page, ctypes.byref(o), owner.ctypes.data, decoy.ctypes.data,
+                                            self.h))
+
+    def observe(self, page, pairs):
+        """prb_nullset_observe: a caller's PAIR_DTYPE records of the real batch against `page`"""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        _check(lib().prb_nullset_observe(self.ctx.h, self.h, page, pairs.ctypes.data if len(pairs) else None, len(pairs)))
+
+    def add_pairs(self, page, owner, decoy, pairs):
+        """prb_nullset_add_pairs: a caller's PAIR_DTYPE records of a batch of decoys against `page`; their `query` indexes
+        owner / decoy"""
+        owner, decoy = np.ascontiguousarray(owner, np.int32), np.ascontiguousarray(decoy, np.int32)
+        assert len(owner) == len(decoy)
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        _check(lib().prb_nullset_add_pairs(self.ctx.h, self.h, page, owner.ctypes.data if len(owner) else None,
+                                           decoy.ctypes.data if len(owner) else None, len(owner),
+                                           pairs.ctypes.data if len(pairs) else None, len(pairs)))
+
+    def finish(self):
+        """prb_nullset_finish -> structured array NULL_DTYPE (a copy), by query, then page, then db_id"""
+        return self._finish("pairs", NULL_DTYPE)
+
+    def decoy_counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_nullset_decoy_counts(self.h, c)
+        return tuple(c)
+
+
+def null_decoys(seqs, ndecoys, seed=1, file_pos0=0):
+    """the decoys of a batch as search_null searches them -> (sequences, owner, decoy), query by query, decoy by decoy"""
+    dseqs, owner, decoy = [], [], []
+    for q, s in enumerate(seqs):
+        for d in range(ndecoys):
+            dseqs.append(shuffle_sequence(s, seed, file_pos0 + q, d))
+            owner.append(q)
+            decoy.append(d)
+    return dseqs, np.array(owner, np.int32), np.array(decoy, np.int32)
+
+
+def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None,
+                with_counts=False):
+    """The null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its file)
+    against db with ndecoys decoys per query -> structured array NULL_DTYPE, by query, then page, then db_id.  mask: every
+    decoy batch is searched under a pair mask that allows its owners' observed targets only (the same records either way).
+    decoy_batch: decoys per batch (all at once by default); pages: their order.  with_counts: -> (records, counts of the
+    real batch's searches, counts of the decoys')."""
+    o = opts or default_opts()
+    pages = list(range(db.npages)) if pages is None else list(pages)
+    dseqs, owner, decoy = null_decoys(seqs, ndecoys, seed, file_pos0)
+    step = decoy_batch or len(dseqs)
+    with NullSet(ctx, qb, db, ndecoys) as ns:
+        observed, counts = [], np.zeros(3, np.int64)
+        for p in pages:
+            if mask:  # (as the command line: the mask needs the observed triples on the host, the table takes them from there)
+                recs, c = search_page_summary(ctx, qb, db, p, o, with_counts=True)
+                observed.append((p, recs["query"].copy(), recs["db_id"].copy()))
+                counts += np.array(c, np.int64)
+                ns.observe(p, recs)
+            else:
+                ns.observed(p, o)
+        for i0 in range(0, len(dseqs), step):
+            own, dec = owner[i0:i0 + step], decoy[i0:i0 + step]
+            dqb = QBatch(ctx, dseqs[i0:i0 + step], db.repeat_flag)
+            pm = None
+            try:
+                dqb.accessibility(db.W, db.delta)
+                od = RisOpts.from_buffer_copy(o)
+                od.allowed_pairs = None  # (a caller's mask is for the real batch; what it allows is all that is observed)
+                if mask:
+                    pm = PairMask(ctx, dqb, db)
+                    for p, rq, rd in observed:
+                        for k in range(len(own)):
+                            sel = rd[rq == own[k]]
+                            if len(sel):
+                                pm.allow(np.full(len(sel), k, np.int32), np.full(len(sel), p, np.int32), sel)
+                    od.allowed_pairs = pm.h.value
+                for p in pages:
+                    ns.decoys(dqb, p, own, dec, od)
+            finally:
+                if pm is not None:
+                    pm.close()
+                dqb.close()
+        recs = ns.finish()
+        counts = tuple(int(x) for x in counts) if mask else ns.counts()
+        dcounts = ns.decoy_counts()
+    return (recs, counts, dcounts) if with_counts else recs
+
+
 class Comm:
     """prb_comm: the RCCL communicator of the final hit gather (one process per GPU)."""
 
@@ -833,6 +964,13 @@ def write_top_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
     (-1: formatted and counted only)."""
     recs = np.ascontiguousarray(recs, TOP_DTYPE)
     return _write(lib().prb_write_top_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
+
+
+def write_null_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
+    """Lines of `ris -t -z N` for one batch: recs as search_null returns them.  -> (lines, bytes) written to fd
+    (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, NULL_DTYPE)
+    return _write(lib().prb_write_null_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
 
 
 def write_target_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):

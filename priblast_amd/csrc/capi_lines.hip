@@ -114,6 +114,25 @@ int prb_write_top_lines(const prb_db *db, int32_t nq, const char *const *qnames,
       [&](const TopView &v, LineSink &sink) { return format_top_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
+int prb_write_null_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_null_pair *recs,
+                         int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<NullView>(
+      "prb_write_null_lines", n >= 0 && (!n || recs), db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](NullView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_null_pair &x = recs[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || x.decoys < 1 || x.null_hits < 0 || x.null_hits > x.decoys ||
+              x.null_le < 0 || x.null_le > x.null_hits || (i && x.s.query < recs[i - 1].s.query))
+            return bad_record("prb_write_null_lines: record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = recs;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const NullView &v, LineSink &sink) { return format_null_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
 int prb_write_target_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
                            const prb_target_pair *pairs, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
   return write_lines<TargetView>(

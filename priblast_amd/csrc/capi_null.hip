@@ -1,0 +1,329 @@
+// C ABI, part 10: the null table of one batch - per observed (query, target) pair, how the query's decoys fare against
+// the same target (prb_nullset_*, `ris -t -z N`).  The kernels are in null_kernels.hip.  Every check of a call is made on
+// the host before anything is enqueued: a refused call leaves the table as it was.
+#include "capi_tables.hpp"
+
+using namespace prb;
+
+namespace {
+
+const char *const kFinishFn = "prb_nullset_finish";
+
+// What every call that merges into the table checks of it first
+int null_guard(const std::string &fn, const prb_ctx *ctx, const prb_nullset *ns, int32_t page) {
+  if (!ctx || !ns) return refuse(fn, "bad argument");
+  if (ns->ctx != ctx) return refuse(fn, "the null table was made with another context");
+  if (ns->broken) return refuse(fn, "an earlier merge into this null table failed", PRB_ERR_STATE);
+  if (ns->bad) return refuse(fn, "a record merged into this null table named a query, a sequence, an owner or a decoy outside it", PRB_ERR_STATE);
+  if (ns->finished) return refuse(fn, std::string("the null table is finished (") + kFinishFn + ")", PRB_ERR_STATE);
+  if (page < 0 || (size_t)page >= ns->observed.size())
+    return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(ns->observed.size()) + ")");
+  return PRB_OK;
+}
+
+// the real batch's page: observed once
+int observed_guard(const std::string &fn, const prb_nullset *ns, int32_t page) {
+  if (ns->observed[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already observed in this null table");
+  return PRB_OK;
+}
+
+// A batch of ndq decoys for `page`: the page is observed, every owner and decoy number lies in its range, and no (owner,
+// decoy) comes twice - in the call, or with this page before
+int decoys_guard(const std::string &fn, const prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+  if (!ns->observed[(size_t)page])
+    return refuse(fn, "page " + std::to_string(page) + " is not observed yet (the real batch's search comes first)", PRB_ERR_STATE);
+  try {
+    std::vector<int64_t> bits((size_t)ndq);
+    for (int32_t i = 0; i < ndq; i++) {
+      if (owner[i] < 0 || owner[i] >= ns->nq)
+        return refuse(fn, "owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is out of range (the batch has " +
+                              std::to_string(ns->nq) + " queries)");
+      if (decoy[i] < 0 || decoy[i] >= ns->ndecoys)
+        return refuse(fn, "decoy[" + std::to_string(i) + "] = " + std::to_string(decoy[i]) + " is out of range (the table has " +
+                              std::to_string(ns->ndecoys) + " decoys per query)");
+      bits[(size_t)i] = ns->bit_of(page, owner[i], decoy[i]);
+      if ((ns->merged[(size_t)(bits[(size_t)i] >> 6)] >> (bits[(size_t)i] & 63)) & 1)
+        return refuse(fn, "decoy " + std::to_string(decoy[i]) + " of query " + std::to_string(owner[i]) + " is already merged for page " +
+                              std::to_string(page));
+    }
+    std::sort(bits.begin(), bits.end());
+    for (size_t i = 1; i < bits.size(); i++)
+      if (bits[i] == bits[i - 1]) {
+        const int64_t od = bits[i] - (int64_t)page * ns->nq * (int64_t)ns->ndecoys;
+        return refuse(fn, "decoy " + std::to_string(od % ns->ndecoys) + " of query " + std::to_string(od / ns->ndecoys) + " is given twice");
+      }
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  return PRB_OK;
+}
+void mark_decoys(prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+  for (int32_t i = 0; i < ndq; i++) {
+    const int64_t b = ns->bit_of(page, owner[i], decoy[i]);
+    ns->merged[(size_t)(b >> 6)] |= 1ull << (b & 63);
+  }
+  ns->nmerged += ndq;
+}
+
+// A caller's list of pair records of `page` (its queries below nq_list): every record within the table's ranges, and no
+// (query, db_id) twice
+int records_guard(const std::string &fn, const prb_nullset *ns, int32_t page, int32_t nq_list, const prb_pair_summary *pairs, int64_t n) {
+  const int64_t nseq = ns->tbase[(size_t)page + 1] - ns->tbase[(size_t)page];
+  try {
+    std::vector<int64_t> keys((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+      const prb_pair_summary &r = pairs[i];
+      if (r.query < 0 || r.query >= nq_list || r.db_id < 0 || r.db_id >= nseq || r.hits < 1)
+        return refuse(fn, "pair record " + std::to_string(i) + " is out of range (query " + std::to_string(r.query) + " of " + std::to_string(nq_list) +
+                              ", db_id " + std::to_string(r.db_id) + " of " + std::to_string(nseq) + ", hits " + std::to_string(r.hits) + ")");
+      keys[(size_t)i] = (int64_t)r.query * nseq + r.db_id;
+    }
+    std::sort(keys.begin(), keys.end());
+    for (size_t i = 1; i < keys.size(); i++)
+      if (keys[i] == keys[i - 1])
+        return refuse(fn, "the pair (query " + std::to_string(keys[i] / nseq) + ", db_id " + std::to_string(keys[i] % nseq) + ") has two records");
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  return PRB_OK;
+}
+
+// the options' selection against the table's (one value of distinct_sites / chain_sites per table)
+int selection_guard(const std::string &fn, const prb_nullset *ns, const prb_ris_opts *opts) {
+  if (const std::string why = selection_clash("null table", "holds", ns, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
+    return refuse(fn, why);
+  return PRB_OK;
+}
+
+// opts->allowed_pairs belongs to this search (what search_page would refuse only once the call is under way)
+int mask_guard(const std::string &fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const prb_ris_opts *opts) {
+  const prb_pairmask *pm = opts->allowed_pairs;
+  if (pm && (pm->qb != qb || pm->db != db || pm->nq != qb->nq || pm->tbase.size() != db->pages.size() + 1 || pm->ctx->device != ctx->device))
+    return refuse(fn, "allowed_pairs was made for another query batch, another database or on another device");
+  return PRB_OK;
+}
+
+// the device's `bad` flag to the host (the stream is drained: every merge ends with this)
+int fetch_bad(prb_ctx *ctx, prb_nullset *ns) {
+  uint32_t flag = 0;
+  PRB_HIP(hipMemcpyAsync(&flag, ns->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  ns->bad = flag != 0;
+  return PRB_OK;
+}
+
+// the owners and the decoy numbers of the batch being merged, on the device
+int upload_owners(prb_ctx *ctx, prb_nullset *ns, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+  if (int rc = ns->own.ensure(std::max<size_t>((size_t)ndq * 8, 8))) return rc;
+  ns->ndq = ndq;
+  if (!ndq) return PRB_OK;
+  PRB_HIP(hipMemcpyAsync(ns->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(ns->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
+  return PRB_OK;
+}
+// a caller's records on the device
+int upload_records(prb_ctx *ctx, prb_nullset *ns, const prb_pair_summary *pairs, int64_t n) {
+  const size_t bytes = (size_t)n * sizeof(prb_pair_summary);
+  if (int rc = ns->h_rec.ensure(std::max<size_t>(bytes, 8))) return rc;
+  if (!n) return PRB_OK;
+  PRB_HIP(hipMemcpyAsync(ns->h_rec.p, pairs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  return PRB_OK;
+}
+
+} // namespace
+
+// prb_search_page_observed (per sub-batch) and prb_nullset_observe: the records into their slots, in a bracket of the
+// "null" timer
+int prb::merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_null_observe(packed, npairs, ns->view(), ns->page_view((size_t)page), ctx->stream));
+  if ((rc = ctx->time_end(ctx->null_timer, 1))) return rc;
+  return fetch_bad(ctx, ns);
+}
+// prb_search_page_decoys (per sub-batch) and prb_nullset_add_pairs: the records folded into the counters, likewise
+int prb::merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_null_count(packed, npairs, ns->own.as<int32_t>(), ns->own.as<int32_t>() + ns->ndq, ns->ndq, ns->view(),
+                            ns->page_view((size_t)page), ctx->stream));
+  if ((rc = ctx->time_end(ctx->null_timer, 1))) return rc;
+  return fetch_bad(ctx, ns);
+}
+
+extern "C" {
+
+int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t ndecoys, prb_nullset **out) {
+  const char *fn = "prb_nullset_create";
+  std::unique_ptr<prb_nullset> ns;
+  const bool args_ok = ctx && qb && db && qb->ctx->device == ctx->device && db->ctx->device == ctx->device;
+  if (int rc = new_table(fn, args_ok, out, ns,
+                         ndecoys < 1 || ndecoys > 100000 ? "need 1 <= ndecoys <= 100000 (got " + std::to_string(ndecoys) + ")" : ""))
+    return rc;
+  try {
+    ns->tbase.assign(db->pages.size() + 1, 0);
+    for (size_t p = 0; p < db->pages.size(); p++) ns->tbase[p + 1] = ns->tbase[p] + db->pages[p].nseq;
+    ns->observed.assign(db->pages.size(), 0);
+    ns->nq = qb->nq;
+    ns->ndecoys = ndecoys;
+    ns->merged.assign((size_t)((ns->triples() + 63) / 64), 0);
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  if (ns->slots() > (int64_t)UINT32_MAX)
+    return refuse(fn, "the batch and the database have " + std::to_string(ns->slots()) + " (query, target) pairs (at most 2^32 - 1)");
+  ns->ctx = ctx; // (from here on the destructor has a device and a stream to release under)
+  ns->db = db;
+  ns->qb = qb;
+  PRB_HIP(hipSetDevice(ctx->device));
+  const size_t S = (size_t)ns->slots();
+  if (ns->table.ensure(std::max<size_t>(S * sizeof(NullSlot), 16)) != PRB_OK || ns->obs.ensure(std::max<size_t>(S, 16)) != PRB_OK ||
+      ns->badflag.ensure(16) != PRB_OK || ns->tbase_dev.ensure(ns->tbase.size() * 8) != PRB_OK)
+    return refuse(fn, "can't allocate the null table (" + std::to_string((S * (sizeof(NullSlot) + 1)) >> 20) + " MB of HBM for " + std::to_string(ns->nq) +
+                          " queries x " + std::to_string(ns->targets()) + " targets)",
+                  PRB_ERR_NOMEM);
+  PRB_HIP(hipMemsetAsync(ns->badflag.p, 0, 16, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(ns->tbase_dev.p, ns->tbase.data(), ns->tbase.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(launch_null_clear(ns->view(), ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ns.release();
+  return PRB_OK;
+}
+
+int prb_search_page_observed(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_nullset *ns) {
+  const char *fn = "prb_search_page_observed";
+  if (!ns) return refuse(fn, "bad argument");
+  if (int rc = check_search_args(fn, ctx, qb, db, page, opts, 3)) return rc;
+  if (ns->qb != qb || ns->nq != qb->nq || ns->db != db) return refuse(fn, "the null table was made for another query batch or another database");
+  if (int rc = null_guard(fn, ctx, ns, page)) return rc;
+  if (int rc = selection_guard(fn, ns, opts)) return rc;
+  if (int rc = mask_guard(fn, ctx, qb, db, opts)) return rc;
+  if (int rc = observed_guard(fn, ns, page)) return rc;
+  PRB_HIP(hipSetDevice(ctx->device));
+  ns->observed[(size_t)page] = 1;
+  ns->broken = true; // (until the merge is whole)
+  prb_hitset *hs = nullptr;
+  if (int rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kNullObserved, &hs, ns)) return rc;
+  for (int i = 0; i < 3; i++) ns->counts[i] += hs->counts[i];
+  ns->distinct = opts->distinct_sites;
+  ns->chain = opts->chain_sites;
+  ns->broken = false;
+  delete hs;
+  return PRB_OK;
+}
+
+int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *owner,
+                           const int32_t *decoy, prb_nullset *ns) {
+  const char *fn = "prb_search_page_decoys";
+  if (!ns || !owner || !decoy) return refuse(fn, "bad argument");
+  if (int rc = check_search_args(fn, ctx, dqb, db, page, opts, 3)) return rc;
+  if (ns->db != db) return refuse(fn, "the null table was made for another database");
+  if (int rc = null_guard(fn, ctx, ns, page)) return rc;
+  if (int rc = selection_guard(fn, ns, opts)) return rc;
+  if (int rc = mask_guard(fn, ctx, dqb, db, opts)) return rc;
+  if (int rc = decoys_guard(fn, ns, page, owner, decoy, dqb->nq)) return rc;
+  PRB_HIP(hipSetDevice(ctx->device));
+  ns->broken = true; // (until the merge is whole)
+  mark_decoys(ns, page, owner, decoy, dqb->nq);
+  if (int rc = upload_owners(ctx, ns, owner, decoy, dqb->nq)) return rc;
+  prb_hitset *hs = nullptr;
+  if (int rc = search_page(ctx, dqb, db, page, opts, 3, SearchMode::kNullDecoys, &hs, ns)) return rc;
+  for (int i = 0; i < 3; i++) ns->decoy_counts[i] += hs->counts[i];
+  ns->broken = false;
+  delete hs;
+  return PRB_OK;
+}
+
+int prb_nullset_observe(prb_ctx *ctx, prb_nullset *ns, int32_t page, const prb_pair_summary *pairs, int64_t n) {
+  const char *fn = "prb_nullset_observe";
+  if (n < 0 || n > INT32_MAX || (n && !pairs)) return refuse(fn, "bad argument");
+  if (int rc = null_guard(fn, ctx, ns, page)) return rc;
+  if (int rc = observed_guard(fn, ns, page)) return rc;
+  if (int rc = records_guard(fn, ns, page, ns->nq, pairs, n)) return rc;
+  DeviceScope restore;
+  PRB_HIP(hipSetDevice(ctx->device));
+  ns->observed[(size_t)page] = 1;
+  if (!n) return PRB_OK;
+  ns->broken = true; // (until the merge is whole)
+  if (int rc = upload_records(ctx, ns, pairs, n)) return rc;
+  if (int rc = merge_null_observed(ctx, ns, page, ns->h_rec.p, n)) return rc;
+  ns->broken = false;
+  return PRB_OK;
+}
+
+int prb_nullset_add_pairs(prb_ctx *ctx, prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t nq,
+                          const prb_pair_summary *pairs, int64_t n) {
+  const char *fn = "prb_nullset_add_pairs";
+  if (nq < 0 || (nq && (!owner || !decoy)) || n < 0 || n > INT32_MAX || (n && !pairs)) return refuse(fn, "bad argument");
+  if (int rc = null_guard(fn, ctx, ns, page)) return rc;
+  if (int rc = decoys_guard(fn, ns, page, owner, decoy, nq)) return rc;
+  if (int rc = records_guard(fn, ns, page, nq, pairs, n)) return rc;
+  DeviceScope restore;
+  PRB_HIP(hipSetDevice(ctx->device));
+  mark_decoys(ns, page, owner, decoy, nq);
+  if (!n) return PRB_OK; // (decoys without a hit: they are merged)
+  ns->broken = true; // (until the merge is whole)
+  if (int rc = upload_owners(ctx, ns, owner, decoy, nq)) return rc;
+  if (int rc = upload_records(ctx, ns, pairs, n)) return rc;
+  if (int rc = merge_null_decoys(ctx, ns, page, ns->h_rec.p, n)) return rc;
+  ns->broken = false;
+  return PRB_OK;
+}
+
+// the observed slots selected on the device, their records gathered there and copied once
+int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
+  const char *fn = kFinishFn;
+  if (int rc = finish_guard(fn, "null", ctx, ns)) return rc;
+  if (ns->finished) return PRB_OK; // (the records are on the host already)
+  if (ns->bad) return refuse(fn, "a record merged into this null table named a query, a sequence, an owner or a decoy outside it", PRB_ERR_STATE);
+  if (ns->nmerged != ns->triples())
+    return refuse(fn, std::to_string(ns->nmerged) + " of " + std::to_string(ns->triples()) + " (query, decoy, page) searches are merged: every decoy of every query against every page comes first",
+                  PRB_ERR_STATE);
+  ns->pairs.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  const int64_t S = ns->slots();
+  if (S > 0) {
+    int rc;
+    SearchWs &w = ws_of(ctx);
+    if ((rc = ns->sel.ensure((size_t)S * 4)) || (rc = w.count.ensure(16))) return rc;
+    if ((rc = ctx->time_begin())) return rc;
+    int64_t nsel = 0;
+    if ((rc = select_flagged(ctx, w, nullptr, ns->obs.as<uint8_t>(), ns->sel.as<uint32_t>(), (size_t)S, &nsel))) return rc;
+    if (nsel < 0 || nsel > S) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
+    if (nsel) {
+      try {
+        ns->pairs.resize((size_t)nsel);
+      } catch (const std::exception &e) {
+        return refuse(fn, e.what(), PRB_ERR_NOMEM);
+      }
+      const size_t bytes = (size_t)nsel * sizeof(prb_null_pair);
+      if ((rc = ns->out.ensure(bytes))) return rc;
+      PRB_HIP(launch_null_gather(ns->view(), ns->sel.as<uint32_t>(), nsel, ns->tbase_dev.as<int64_t>(), (int32_t)ns->observed.size(), ns->out.p,
+                                 ctx->stream));
+      PRB_HIP(hipMemcpyAsync(ns->pairs.data(), ns->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if ((rc = ctx->time_end(ctx->null_timer, nsel ? 2 : 1))) return rc; // (synchronises: the copy is over)
+    if ((rc = fetch_bad(ctx, ns))) return rc;
+    if (ns->bad) {
+      ns->pairs.clear();
+      return refuse(fn, "a selected slot lies outside the null table", PRB_ERR_STATE);
+    }
+  }
+  ns->finished = true;
+  ns->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_nullset_size(const prb_nullset *ns) { return ns ? (int64_t)ns->pairs.size() : -1; }
+const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns) { return ns ? ns->pairs.data() : nullptr; }
+void prb_nullset_counts(const prb_nullset *ns, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ns ? ns->counts[i] : 0;
+}
+void prb_nullset_decoy_counts(const prb_nullset *ns, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = ns ? ns->decoy_counts[i] : 0;
+}
+void prb_nullset_free(prb_nullset *ns) { delete ns; }
+
+} // extern "C"

@@ -1029,6 +1029,23 @@ static int emit_coverage(SubSearch &s) {
   return PRB_OK;
 }
 
+// prb_search_page_observed / prb_search_page_decoys: the pairs' records into the null table on the device - the real
+// batch's scattered into their slots, a decoy batch's folded into the counters; nothing leaves it
+static int emit_null(SubSearch &s, bool decoys) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  prb_nullset *ns = static_cast<prb_nullset *>(s.table);
+  int rc;
+  int64_t npairs = 0;
+  if ((rc = pair_runs(s, &npairs))) return rc;
+  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
+  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
+  if ((rc = decoys ? merge_null_decoys(ctx, ns, s.page, w.packed.p, npairs) : merge_null_observed(ctx, ns, s.page, w.packed.p, npairs))) return rc;
+  s.hs->hits_total += s.nfin;
+  return PRB_OK;
+}
+
 static int emit_final(SubSearch &s) {
   switch (s.mode) {
   case SearchMode::kRecords: return emit_records(s);
@@ -1038,6 +1055,8 @@ static int emit_final(SubSearch &s) {
   case SearchMode::kTopHits: return emit_tophits(s);
   case SearchMode::kTargets: return emit_targets(s);
   case SearchMode::kCoverage: return emit_coverage(s);
+  case SearchMode::kNullObserved: return emit_null(s, false);
+  case SearchMode::kNullDecoys: return emit_null(s, true);
   }
   return PRB_ERR_STATE;
 }

@@ -73,4 +73,6 @@ struct prb_ctx {
   int time_begin();
   int time_end(const char *stage, int64_t launches);
   int time_end(prb::StageTimer &t, int64_t launches);
+
+  prb::StageTimer null_timer; // the scatter, the fold and the finish of the null table (stage "null"), kept apart like the others
 };

@@ -591,6 +591,42 @@ struct prb_covset : prb::RunTable, prb::SpanBufs {
   }
 };
 
+// prb_nullset_create .. prb_nullset_free: the null table of one batch against one database (capi_null.hip), merged into
+// sub-batch by sub-batch - the real batch's pairs page by page first (merge_null_observed), then the pairs of its decoys
+// (merge_null_decoys).  It owns all its device memory; `table` = NullSlot[nq * targets]
+struct prb_nullset : prb::TableState {
+  const prb_qbatch *qb = nullptr;
+  int32_t nq = 0, ndecoys = 0;
+  std::vector<int64_t> tbase;        // [npages + 1] the first target of every page; back() = the targets
+  std::vector<uint8_t> observed;     // per page: the real batch's search is merged
+  std::vector<uint64_t> merged;      // a bit per (page, query, decoy): that decoy's search of the page is merged
+  int64_t nmerged = 0;               // bits set in `merged`
+  int64_t decoy_counts[3] = {0, 0, 0}; // the stage counts of the decoy searches (`counts`: of the real batch's)
+  bool bad = false;                  // the device's `bad` flag, as the last merge left it
+  prb::DevBuf obs, badflag, tbase_dev; // the selection's flags, the kernels' flag, tbase on the device
+  prb::DevBuf own;                   // the decoy batch being merged: owner[ndq], then decoy[ndq]
+  int32_t ndq = 0;                   // ... its number of decoys
+  prb::DevBuf h_rec;                 // prb_nullset_observe / _add_pairs: the caller's records
+  prb::DevBuf sel, out;              // prb_nullset_finish: the observed slots, their records
+  std::vector<prb_null_pair> pairs;  // prb_nullset_finish
+  int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
+  int64_t slots() const { return (int64_t)nq * targets(); }
+  int64_t triples() const { return (int64_t)observed.size() * (int64_t)nq * (int64_t)ndecoys; }
+  int64_t bit_of(int32_t page, int32_t q, int32_t d) const { return ((int64_t)page * nq + q) * (int64_t)ndecoys + d; }
+  prb::NullTab view() const {
+    return prb::NullTab{table.as<prb::NullSlot>(), obs.as<uint8_t>(), badflag.as<uint32_t>(), slots(), targets(), nq, ndecoys};
+  }
+  prb::NullPage page_view(size_t page) const { return prb::NullPage{tbase[page], (int32_t)(tbase[page + 1] - tbase[page])}; }
+  // nothing of the table is released while work on it may still be queued on its context's stream
+  void release() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (prb::DevBuf *b : {&table, &obs, &badflag, &tbase_dev, &own, &h_rec, &sel, &out}) b->release();
+  }
+  ~prb_nullset() { release(); } // (also on the error paths of prb_nullset_create)
+};
+
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS): PRB_HOST_THREADS, else half of the CPUs the
 // process may keep busy, at most 32 (capi_pages.hip)
@@ -605,6 +641,8 @@ enum class SearchMode {
   kTopHits, // prb_search_page_tophits: the hits and their base pairs merged into the top-N hit table on the device
   kTargets, // prb_search_page_targets: per-pair records merged into the per-target table on the device
   kCoverage, // prb_search_page_coverage: the hits merged into the per-target coverage table on the device
+  kNullObserved, // prb_search_page_observed: per-pair records of the real batch scattered into the null table on the device
+  kNullDecoys,   // prb_search_page_decoys: per-pair records of a batch of decoys folded into the null table's counters
 };
 // (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
@@ -641,4 +679,8 @@ int merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, int32
 // capi_spans.hip: a list of final hits of `page` (of a sub-batch, or a caller's: prb_covset_add_hits); cs->ids holds the
 // identifiers of the list's nq queries
 int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq);
+// capi_null.hip: the npairs pair records at `packed` (device) of `page` - of the real batch, or of the decoy batch whose
+// owners and decoy numbers ns->own holds - into the null table
+int merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
+int merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
 } // namespace prb

@@ -544,4 +544,39 @@ hipError_t launch_cov_join(const CovTab &t, const CovTab &src, int64_t P, hipStr
 hipError_t launch_cov_regions(const CovTab &t, const int64_t *tbase, int32_t npages, int64_t ntargets, const uint32_t *first, int64_t nregions,
                               const int64_t *hits, const int32_t *queries, int32_t D, void *out, hipStream_t s);
 
+// ============================================================================ null_kernels.hip: the null table
+// (prb_nullset_*)  The table of one batch against one database in HBM: a slot per (query q, target t), slot
+// q * ntargets + t, targets numbered page by page.  A slot: the observed pair's summary record, the number of decoys
+// with a hit against the target, the number of those whose e_min is not above the observed one, and the smallest decoy
+// e_min as its energy key (the key of +infinity: none).  obs[slot] = the slot's `observed` as the flag the selection of
+// prb_nullset_finish takes.  bad: set when a record names a query, a sequence, an owner or a decoy outside the table.
+struct NullSlot {
+  uint64_t s[8];                                 // the observed pair's prb_pair_summary
+  unsigned long long null_hits, null_le, null_min;
+  uint32_t observed, reserved;
+};
+static_assert(sizeof(NullSlot) == 96, "NullSlot: 64 B of record, three counters, the flag");
+struct NullTab {
+  NullSlot *slot;    // [nslots]
+  uint8_t *obs;      // [nslots]
+  uint32_t *bad;
+  int64_t nslots, ntargets; // nslots = nq * ntargets
+  int32_t nq, ndecoys;
+};
+struct NullPage {
+  int64_t target0; // the page's first target
+  int32_t nseq;
+};
+// every slot back to "not observed"
+hipError_t launch_null_clear(const NullTab &t, hipStream_t s);
+// rec[0, nrec) = launch_pair_fold's records (prb_pair_summary) of the real batch against the page, or a caller's: each
+// into the slot of its (query, db_id), a lane per record; a (query, page) comes once
+hipError_t launch_null_observe(const void *rec, int64_t nrec, const NullTab &t, const NullPage &pg, hipStream_t s);
+// rec[0, nrec) = the records of a batch of ndq decoys against the page: record i is decoy decoy[query] of the real query
+// owner[query]; folded into the counters of the observed slots with integer atomics, a lane per record
+hipError_t launch_null_count(const void *rec, int64_t nrec, const int32_t *owner, const int32_t *decoy, int32_t ndq, const NullTab &t,
+                             const NullPage &pg, hipStream_t s);
+// prb_nullset_finish: out[j] (prb_null_pair) of the observed slot idx[j]; tbase[npages + 1] = the pages' first targets
+hipError_t launch_null_gather(const NullTab &t, const uint32_t *idx, int64_t n, const int64_t *tbase, int32_t npages, void *out, hipStream_t s);
+
 } // namespace prb

@@ -211,6 +211,33 @@ void format_target_piece(const Piece &pc, const TargetView &v, const std::vector
     put_summary_line(b, id++, v.names[v.r[i].s.query], v.qlen_unmasked[v.r[i].s.query], tabs[v.r[i].page], v.r[i].s);
 }
 
+// the `-t` line of the observed pair, then - in place of its newline - the null columns
+void format_null_piece(const Piece &pc, const NullView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_null_pair &x = v.r[i];
+    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
+    b.n--; // (the newline)
+    char *p = b.room(200);
+    char *const p0 = p;
+    for (long long f : {(long long)x.decoys, (long long)x.null_hits, (long long)x.null_le}) {
+      *p++ = ',';
+      p = put_int(p, f);
+    }
+    *p++ = ',';
+    if (x.null_hits > 0) {
+      p = put_g(p, x.null_min);
+    } else {
+      *p++ = 'N';
+      *p++ = 'A';
+    }
+    *p++ = ',';
+    p = put_g(p, ((double)x.null_le + 1.0) / ((double)x.decoys + 1.0));
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
 void format_profile_piece(const Piece &pc, const ProfileView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   const std::string &qname = v.names[pc.q];
   int64_t id = pc.id;
@@ -305,6 +332,13 @@ int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, in
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_top_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the top-N records: in output order already, each with its own page)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
+      [&](const Piece &pc, Buf &b) { format_null_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

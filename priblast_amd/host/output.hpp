@@ -69,6 +69,16 @@ struct TopView : QueryView {
 };
 int64_t format_top_batch(const TopView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -t -z N` (prb_nullset_pairs): the `-t` line of every observed pair with the null columns behind it, in
+// the records' order (by query, then page, then db_id), numbered from id0 on:
+//   Id,qname,qlen,dbname,dblen,Hits,MinE,SumE,Eacc,Ehyb,(q0-qN:db0-dbN) ,Decoys,NullHits,NullLE,NullMin,PValue
+// NullMin in the energies' form, or NA when no decoy has a hit; PValue = (NullLE + 1) / (Decoys + 1), six significant digits.
+struct NullView : QueryView {
+  const prb_null_pair *r = nullptr;
+  int64_t n = 0;
+};
+int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 // Lines of `ris -r N` (prb_targetset_pairs): the same lines again, in the records' order (by page, target and rank),
 // numbered from id0 on.  The queries are those of the whole run: `names` and `qlen_unmasked` are indexed by the
 // records' query identifiers.

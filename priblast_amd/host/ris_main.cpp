@@ -40,6 +40,9 @@
 // worker owns one table on its GPU for the whole run (prb_search_page_targets takes every page of every batch it
 // searches); at the end the first worker merges the others' into its own (prb_targetset_merge), and only N records per
 // target reach the host, written by page, target and rank.  `-r` is refused with -t, -n, -q, -k, -b and in rank mode.
+// `ris -t -z N` adds an empirical p-value to every `-t` line: N shuffled decoys of each query (prb_shuffle_sequence) are
+// searched like the query, and a null table on the GPU (prb_nullset_*) counts, per observed pair, the decoys that reach
+// its minimum energy; only the table's records reach the host.  `-z` needs -t and is refused with -n, -k, -q, -r, -c, -b.
 // `ris -c D` says where on a target the queries bind: one line per region - a maximal run of positions of one database
 // sequence, each covered by final hits of at least D distinct queries.  Every worker owns one per-position table of the
 // database on its GPU for the whole run (prb_search_page_coverage takes every page of every batch it searches); at the
@@ -65,6 +68,7 @@
 #include <map>
 #include <memory>
 #include <cctype>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -148,6 +152,14 @@ void usage() {
             "              and lines that begin with # are skipped.  The seeds of all other pairs are dropped on the GPU, so\n"
             "              the stages behind cost what the listed pairs cost; the lines are lines of the run without -L (a\n"
             "              query's first line may list its base pairs in another order).  With every other switch\n"
+            "    -z INT    with -t: an empirical p-value per query-target pair from INT dinucleotide-preserving shuffles\n"
+            "              (decoys) of each query, searched like the query: behind every -t line the decoys per query, how\n"
+            "              many of them have a hit against the target (NullHits), how many of those reach the pair's minimum\n"
+            "              interaction energy or below (NullLE), the lowest decoy minimum (NullMin, NA without one) and\n"
+            "              PValue = (NullLE + 1) / (INT + 1); lines by query, then page, then target (1 <= INT <= 100000;\n"
+            "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
+            "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
+            "    -Z INT    with -z: the seed of the shuffles [default:1]\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -171,13 +183,13 @@ thread_local bool t_team_thread = false;
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage };
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -196,6 +208,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'j', "the best co-linear chain of sites of each pair", bit(kU), -1, false},
     {'r', "the N best queries per target", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB), -1, true},
     {'c', "the regions of each target bound by at least D queries", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR), -1, true},
+    {'z', "an empirical p-value per pair from N shuffled decoys", bit(kN) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
+    {'Z', "the seed of the decoys' shuffles", 0, kZ, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -206,6 +220,9 @@ struct Args {
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
+  int decoys = 0;                                   // -z, likewise
+  uint64_t shuffle_seed = 1;                        // -Z
+  bool seed_ok = true;                              // -Z's value is a non-negative integer
   OutputMode mode = OutputMode::kHits;
   bool binary() const { return given[kB]; }
 };
@@ -226,6 +243,7 @@ struct Free {
   void operator()(prb_topset *p) const { prb_topset_free(p); }
   void operator()(prb_profset *p) const { prb_profset_free(p); }
   void operator()(prb_tophits *p) const { prb_tophits_free(p); }
+  void operator()(prb_nullset *p) const { prb_nullset_free(p); }
 };
 template <class T> using Handle = std::unique_ptr<T, Free>;
 
@@ -238,6 +256,7 @@ struct BatchResult {
   Handle<prb_topset> top;                      // kTop
   Handle<prb_profset> prof;                    // kProfile
   Handle<prb_tophits> tophits;                 // kTopHits
+  Handle<prb_nullset> null;                    // kNull
 };
 
 // The result of one batch (in rank mode: of one round of batches, gathered), waiting to be written.
@@ -558,9 +577,12 @@ void check_switches(const Args &a) {
     if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
+  if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
+  if (a.given[kZSeed] && !a.seed_ok) die("Error: -Z needs a non-negative integer");
 }
 
 OutputMode output_mode(const Args &a) {
+  if (a.given[kZ]) return OutputMode::kNull;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
 }
@@ -569,7 +591,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -593,6 +615,15 @@ Args parse_args(int argc, char **argv) {
     case 'r': a.given[kR] = true, a.targets = parse_count(optarg); break;
     case 'c': a.given[kC] = true, a.depth = parse_count(optarg); break;
     case 'L': a.have_pairlist = true, a.pairlist = optarg; break;
+    case 'z': a.given[kZ] = true, a.decoys = parse_count(optarg); break;
+    case 'Z': {
+      char *end = nullptr;
+      errno = 0;
+      a.given[kZSeed] = true;
+      a.shuffle_seed = std::strtoull(optarg, &end, 10);
+      a.seed_ok = end != optarg && *end == '\0' && errno == 0 && optarg[0] != '-';
+      break;
+    }
     case 'a':
       if (std::strcmp(optarg, "block") && std::strcmp(optarg, "area") && std::strcmp(optarg, "dynamic"))
         die("Error: parallel algorithm not supported.");
@@ -818,6 +849,10 @@ std::string header_text(const Run &r) {
   case OutputMode::kTargets:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
+  case OutputMode::kNull:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Decoys, Null Hits, Null LE, "
+                    "Null Minimum Energy, P Value\n";
   case OutputMode::kHits:
   case OutputMode::kTopHits: break;
   }
@@ -854,7 +889,8 @@ void plan_batches(Run &r) {
 // Whole batches to the workers, or the pages of every batch?  Pages only in one process with two workers or more and
 // a database of two pages or more: when asked for, or - auto - when there are fewer batches than workers.
 void plan_split(Run &r) {
-  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2;
+  // (-z: a batch and its decoys belong to one worker - there is no merge of two null tables)
+  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull;
   r.split_pages = can && (r.split_knob == kSplitPages || (r.split_knob == kSplitAuto && r.nb < r.workers.size()));
 }
 
@@ -924,6 +960,7 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
   }
   case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
   case OutputMode::kCoverage:
+  case OutputMode::kNull: // (search_null_batch makes its own)
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -955,6 +992,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
     out.pages[(size_t)page].reset(hs);
     break;
   }
+  case OutputMode::kNull: break; // (search_null_batch)
   }
   if (rc) die(prb_last_error());
 }
@@ -972,6 +1010,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kTopHits: run(kTopHitsOps, &BatchResult::tophits); break;
   case OutputMode::kTargets:
   case OutputMode::kCoverage:
+  case OutputMode::kNull:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -992,8 +1031,92 @@ void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
   for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
 }
 
+// -t -z N: the real batch against every page into a null table of its own, then its decoys - N shuffles of every query,
+// made on host threads, file_pos = the query's place in the input file - in batches of at most the batch size, each with
+// its suffix arrays and accessibilities, against every page.  Unless PRB_NULL_MASK=0, a decoy batch is searched under a
+// pair mask that allows each decoy the observed targets of its owner only (under -L those are listed pairs already): the
+// real batch's records come to the host for that (prb_search_page_summary) and go into the table from there
+// (prb_nullset_observe); without the mask they never leave the device (prb_search_page_observed).
+BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
+  BatchResult res = empty_result(r);
+  const Args &a = r.a;
+  const char *menv = std::getenv("PRB_NULL_MASK");
+  const bool masked = !(menv && std::atoi(menv) == 0);
+  const size_t nq = p.ids.size();
+  prb_nullset *ns = nullptr;
+  if (prb_nullset_create(w.ctx, p.qb, w.db, a.decoys, &ns)) die(prb_last_error());
+  res.null.reset(ns);
+  prb_ris_opts o = a.o;
+  o.allowed_pairs = p.mask;
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> observed(nq); // per query: its (page, db_id)
+  for (int page = 0; page < r.npages; page++) {
+    if (!masked) {
+      if (prb_search_page_observed(w.ctx, p.qb, w.db, page, &o, ns)) die(prb_last_error());
+      continue;
+    }
+    prb_pairset *raw = nullptr;
+    if (prb_search_page_summary(w.ctx, p.qb, w.db, page, &o, &raw)) die(prb_last_error());
+    const Handle<prb_pairset> ps(raw);
+    const prb_pair_summary *rec = prb_pairset_pairs(raw);
+    const int64_t n = prb_pairset_size(raw);
+    for (int64_t i = 0; i < n; i++) {
+      if (rec[i].query < 0 || (size_t)rec[i].query >= nq) die("Error: bad record in a batch's pair summaries");
+      observed[(size_t)rec[i].query].emplace_back((int32_t)page, rec[i].db_id);
+    }
+    if (prb_nullset_observe(w.ctx, ns, page, rec, n)) die(prb_last_error());
+  }
+  // the decoys, query by query and decoy by decoy
+  const size_t nd = (size_t)a.decoys, total = nq * nd;
+  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
+    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
+    std::vector<int64_t> off(m + 1, 0);
+    std::vector<int32_t> owner(m), decoy(m);
+    for (size_t k = 0; k < m; k++) {
+      owner[k] = (int32_t)((d0 + k) / nd);
+      decoy[k] = (int32_t)((d0 + k) % nd);
+      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)p.ids[(size_t)owner[k]]].size();
+    }
+    std::string cat((size_t)off[m], '\0');
+    bool shuffled = true;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
+    for (size_t k = 0; k < m; k++) {
+      const std::string &seq = r.seqs[(size_t)p.ids[(size_t)owner[k]]];
+      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)p.ids[(size_t)owner[k]], decoy[k], &cat[(size_t)off[k]])) {
+#pragma omp atomic write
+        shuffled = false;
+      }
+    }
+    if (!shuffled) die(std::string("Error: ") + prb_last_error());
+    prb_qbatch *dqb = nullptr;
+    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
+    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
+    prb_ris_opts od = a.o;
+    prb_pairmask *dmask = nullptr;
+    if (masked) {
+      std::vector<int32_t> mq, mp, md;
+      for (size_t k = 0; k < m; k++)
+        for (const auto &[page, db_id] : observed[(size_t)owner[k]]) {
+          mq.push_back((int32_t)k);
+          mp.push_back(page);
+          md.push_back(db_id);
+        }
+      if (prb_pairmask_create(w.ctx, dqb, w.db, &dmask) || prb_pairmask_allow(dmask, (int64_t)mq.size(), mq.data(), mp.data(), md.data()))
+        die(std::string("Error: ") + prb_last_error());
+      od.allowed_pairs = dmask;
+    }
+    for (int page = 0; page < r.npages; page++)
+      if (prb_search_page_decoys(w.ctx, dqb, w.db, page, &od, owner.data(), decoy.data(), ns)) die(prb_last_error());
+    prb_pairmask_free(dmask);
+    prb_qbatch_destroy(dqb);
+  }
+  if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
+  release_batch(p);
+  return res;
+}
+
 // the search stages of a prepared batch against every page
 BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
+  if (r.a.mode == OutputMode::kNull) return search_null_batch(r, w, p);
   BatchResult res = empty_result(r);
   create_table(r, w, p.qb, res);
   for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
@@ -1077,6 +1200,17 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.r = prb_topset_pairs(job.res.top.get());
     v.n = prb_topset_size(job.res.top.get());
     return written_or_die(prb::format_top_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kNull: {
+    prb::NullView v;
+    set_queries(v, job);
+    v.r = prb_nullset_pairs(job.res.null.get());
+    v.n = prb_nullset_size(job.res.null.get());
+    for (int64_t i = 0; i < v.n; i++)
+      if (v.r[i].s.query < 0 || (size_t)v.r[i].s.query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages || v.r[i].s.db_id < 0 ||
+          (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size())
+        die("Error: bad record in the null table");
+    return written_or_die(prb::format_null_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kTargets:
   case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
