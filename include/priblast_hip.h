@@ -165,6 +165,15 @@ const char *prb_version(void);
 int prb_cpu_budget(void);
 int prb_host_threads_default(void);
 void prb_ris_opts_default(prb_ris_opts *o);
+/* How the one-pass seed path holds and sorts the (query SA entry, database SA entry) pairs of a chunk: the choice the
+ * search makes for a page of `nchars` characters, a chunk whose queries span `query_span` (last - first) and the knobs
+ * PRB_SEED_ROW_SHIFT, PRB_SEED_SORT_BITS, PRB_SEED_LOCAL_ORDER (0 / 1) and PRB_SEED_PAIR_WIDE (0 / 1), given as arguments,
+ * not read from the environment.  No GPU is touched.  out[0] = 1: narrow pairs (32-bit key {query, position}, 32-bit
+ * value), 0: wide ones; out[1] = bits of the key's position part, out[2] = bits of the whole key (0: row_shift < 0, no
+ * pair sort), out[3] = the lowest key bit the radix sort covers, out[4] = the key bits below it that each 2048-pair tile
+ * orders for itself, out[5] = 1: 64-bit keys. */
+int prb_seed_pair_layout(int64_t nchars, int64_t query_span, int32_t row_shift, int32_t sort_bits, int32_t local_order,
+                         int32_t pair_wide, int32_t out[6]);
 
 /* ---- context ---- */
 /* param_file: nearest-neighbour parameter data (priblast_amd/params/rna_andronescu2007.par);

@@ -87,6 +87,7 @@ SYMBOLS = {
     "prb_version": (ctypes.c_char_p, []),
     "prb_cpu_budget": (ctypes.c_int, []),
     "prb_host_threads_default": (ctypes.c_int, []),
+    "prb_seed_pair_layout": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, P(c_i32)]),
     "prb_ris_opts_default": (None, [P(RisOpts)]),
     "prb_ctx_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_ctx_destroy": (None, [ctypes.c_void_p]),
@@ -282,6 +283,13 @@ def shuffle_sequence(seq, seed=1, file_pos=0, decoy=0):
     _check(lib().prb_shuffle_sequence(raw, len(raw), seed, file_pos, decoy, out))
     res = out.raw[:len(raw)]
     return res.decode("latin-1") if isinstance(seq, str) else res
+
+
+def seed_pair_layout(nchars, query_span, row_shift=7, sort_bits=16, local_order=True, pair_wide=False):
+    """prb_seed_pair_layout -> dict(narrow, pbits, kbits, begin, local_bits, wide_key)"""
+    out = (c_i32 * 6)()
+    _check(lib().prb_seed_pair_layout(nchars, query_span, row_shift, sort_bits, int(local_order), int(pair_wide), out))
+    return dict(narrow=bool(out[0]), pbits=out[1], kbits=out[2], begin=out[3], local_bits=out[4], wide_key=bool(out[5]))
 
 
 def default_opts(**kw):

@@ -26,6 +26,11 @@ static SearchKnobs read_search_knobs() {
   if ((e = getenv("PRB_SEARCH_CHUNK_PAIRS"))) k.chunk_pairs = atof(e);
   e = getenv("PRB_SEED_ROW_SHIFT");
   k.row_shift = e ? std::min(atoi(e), 30) : 7;
+  e = getenv("PRB_SEED_SORT_BITS");
+  k.sort_bits = e ? std::max(atoi(e), 1) : 16;
+  k.local_order = !env_off(getenv("PRB_SEED_LOCAL_ORDER"));
+  e = getenv("PRB_SEED_PAIR_WIDE");
+  k.pair_wide = e && atoi(e) != 0;
   k.fused = !env_off(getenv("PRB_SEED_FUSED"));
   k.front_ahead = !getenv("PRB_NO_FRONT_AHEAD");
   k.sort_four_keys = getenv("PRB_SORT_FOUR_KEYS") != nullptr;
@@ -299,9 +304,10 @@ static int32_t chunk_end(const CandDev *cd, int32_t ncand, int32_t c0, double ch
 }
 
 // (query, database position >> row_shift) keys of a chunk's rows or pairs (k_row_key): the bits of the position part
-// and of the whole key
+// and of the whole key, and the lowest bit that the sort looks at (above 0 in the narrow layout of the pairs only)
 struct RowKeyBits {
   int dbits, kbits;
+  int begin = 0;
   bool wide() const { return kbits > 32; }
 };
 static RowKeyBits row_key_bits(const PageDev &pd, int row_shift, const CandDev *cd, int32_t nc) {
@@ -311,8 +317,14 @@ static RowKeyBits row_key_bits(const PageDev &pd, int row_shift, const CandDev *
 // the sort by those keys, which are 32 bits wide unless they need more
 template <class V>
 static int sort_by_row_key(hipStream_t s, DevBuf &tmp, const RowKeyBits &kb, DevBuf &kin, DevBuf &kout, const V *vin, V *vout, size_t n) {
-  return kb.wide() ? sort_pairs(s, tmp, kin.as<uint64_t>(), kout.as<uint64_t>(), vin, vout, n, (unsigned)kb.kbits)
-                   : sort_pairs(s, tmp, kin.as<uint32_t>(), kout.as<uint32_t>(), vin, vout, n, (unsigned)kb.kbits);
+  return kb.wide() ? sort_pairs(s, tmp, kin.as<uint64_t>(), kout.as<uint64_t>(), vin, vout, n, (unsigned)kb.begin, (unsigned)kb.kbits)
+                   : sort_pairs(s, tmp, kin.as<uint32_t>(), kout.as<uint32_t>(), vin, vout, n, (unsigned)kb.begin, (unsigned)kb.kbits);
+}
+// a chunk's pairs in the layout `lay`, from (kin, vin) to (kout, vout)
+static int sort_chunk_pairs(hipStream_t s, DevBuf &tmp, const PairLayout &lay, DevBuf &kin, DevBuf &kout, DevBuf &vin, DevBuf &vout, size_t n) {
+  const RowKeyBits kb{lay.pbits, lay.kbits, lay.begin};
+  return lay.narrow ? sort_by_row_key(s, tmp, kb, kin, kout, vin.as<uint32_t>(), vout.as<uint32_t>(), n)
+                    : sort_by_row_key(s, tmp, kb, kin, kout, vin.as<uint64_t>(), vout.as<uint64_t>(), n);
 }
 
 // w.row_off[0..n] <- the exclusive scan of the counts w.row_count[0..n] (the last one a zero: row_off[n] is the total)
@@ -329,7 +341,7 @@ static int scan_row_counts(prb_ctx *ctx, SearchWs &w, int64_t n) {
 // Under a pair mask (`allow`) the pairs that are not allowed are dropped behind their keys: a test, a scan over one count
 // per 64 pairs and a scatter, in a bracket of the "allow" timer when the caller has the "seed" bracket open on `s`
 // (`timed`).  The sort needs the number of pairs left, which is on its way to the host: finish_front does it.
-static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int delta, int row_shift, const CandDev *cd, int32_t nc,
+static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int delta, const SearchKnobs &k, const CandDev *cd, int32_t nc,
                        int64_t cents, hipStream_t s, int64_t *np_out, const AllowDev *allow, prb_ctx *timed) {
   SearchWs::FrontStage &F = w.front;
   int rc;
@@ -345,19 +357,20 @@ static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int
   }
   pair0[nc] = np;
   const size_t NP = (size_t)np;
-  const RowKeyBits kb = row_key_bits(pd, row_shift, cd, nc);
+  const PairLayout lay = pair_layout(pd.nchars, (int64_t)cd[nc - 1].query - cd[0].query, k.row_shift, k.sort_bits, k.local_order, k.pair_wide);
   if ((rc = F.cands.ensure((size_t)nc * sizeof(CandDev))) || (rc = F.seed_qacc.ensure((size_t)std::max<int64_t>(cents, 1) * 8)) ||
-      (rc = F.pair0.ensure(((size_t)nc + 1) * 8)) || (rc = F.keyA.ensure(NP * (kb.wide() ? 8 : 4))) ||
-      (rc = F.keyB.ensure(NP * (kb.wide() ? 8 : 4))) || (rc = F.valA.ensure(NP * 8)) || (rc = F.valB.ensure(NP * 8)))
+      (rc = F.pair0.ensure(((size_t)nc + 1) * 8)) || (rc = F.keyA.ensure(NP * lay.key_bytes())) || (rc = F.keyB.ensure(NP * lay.key_bytes())) ||
+      (rc = F.valA.ensure(NP * lay.val_bytes())) || (rc = F.valB.ensure(NP * lay.val_bytes())))
     return rc;
   PRB_HIP(hipMemcpyAsync(F.cands.p, cd, (size_t)nc * sizeof(CandDev), hipMemcpyHostToDevice, s));
   PRB_HIP(hipMemcpyAsync(F.pair0.p, pair0, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
   PRB_HIP(launch_seed_qacc(F.cands.as<CandDev>(), nc, cents, qb->view, delta, F.seed_qacc.as<double>(), s));
-  PRB_HIP(launch_pair_keys(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), nc, np, pd, cd[0].query, row_shift, kb.dbits, kb.wide(), F.keyA.p,
-                           F.valA.as<uint64_t>(), s));
+  PRB_HIP(launch_pair_keys(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), nc, np, pd, cd[0].query, lay, F.keyA.p, F.valA.p, s));
   F.unsorted = false;
   F.np_all = np;
-  F.vals = F.valB.as<uint64_t>();
+  F.lay = lay;
+  F.keys = F.keyB.p;
+  F.vals = F.valB.p;
   if (allow) {
     const int64_t nw = allow_words(np);
     if ((rc = F.ballot.ensure((size_t)nw * 8)) || (rc = F.wcount.ensure((size_t)(nw + 1) * 4)) || (rc = F.woff.ensure((size_t)(nw + 1) * 8)) ||
@@ -365,23 +378,21 @@ static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int
       return rc;
     if (timed && ((rc = timed->time_end("seed", 1)) || (rc = timed->time_begin()))) return rc; // (the keys; the sort is counted where it runs)
     PRB_HIP(hipMemsetAsync(F.wcount.as<int32_t>() + nw, 0, 4, s)); // (the scan over nw + 1 counts ends with the total)
-    PRB_HIP(launch_allow_test(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), F.valA.as<uint64_t>(), np, pd, *allow, F.ballot.as<uint64_t>(),
+    PRB_HIP(launch_allow_test(F.cands.as<CandDev>(), F.pair0.as<int64_t>(), F.valA.p, lay, np, pd, *allow, F.ballot.as<uint64_t>(),
                               F.wcount.as<int32_t>(), s));
     auto counts = rocprim::make_transform_iterator(F.wcount.as<int32_t>(), ToI64());
     if ((rc = with_temp(F.scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
            return rocprim::exclusive_scan(t, b, counts, F.woff.as<int64_t>(), (int64_t)0, (size_t)nw + 1, rocprim::plus<int64_t>(), s);
          })))
       return rc;
-    PRB_HIP(launch_allow_scatter(F.keyA.p, F.valA.as<uint64_t>(), np, kb.wide(), F.ballot.as<uint64_t>(), F.woff.as<int64_t>(), F.keyB.p,
-                                 F.valB.as<uint64_t>(), s));
+    PRB_HIP(launch_allow_scatter(F.keyA.p, F.valA.p, np, lay, F.ballot.as<uint64_t>(), F.woff.as<int64_t>(), F.keyB.p, F.valB.p, s));
     PRB_HIP(hipMemcpyAsync(F.kept_pin.p, F.woff.as<int64_t>() + nw, 8, hipMemcpyDeviceToHost, s));
     if (timed && ((rc = timed->time_end(timed->allow_timer, 3)) || (rc = timed->time_begin()))) return rc;
     F.unsorted = true;
-    F.key_bits = kb.kbits;
     *np_out = np;
     return PRB_OK;
   }
-  if ((rc = sort_by_row_key(s, F.sortTmp, kb, F.keyA, F.keyB, F.valA.as<uint64_t>(), F.valB.as<uint64_t>(), NP))) return rc;
+  if ((rc = sort_chunk_pairs(s, F.sortTmp, lay, F.keyA, F.keyB, F.valA, F.valB, NP))) return rc;
   *np_out = np;
   return PRB_OK;
 }
@@ -401,10 +412,9 @@ static int finish_front(prb_ctx *ctx, SearchWs &w, const SearchKnobs &k, int32_t
   if (k.debug_rows) fprintf(stderr, "[allow] cands %d pairs %lld allowed %lld\n", nc, (long long)F.np_all, (long long)kept);
   *np = kept;
   if (kept == 0) return PRB_OK;
-  if ((rc = sort_by_row_key(ctx->stream, F.sortTmp, RowKeyBits{0, F.key_bits}, F.keyB, F.keyA, F.valB.as<uint64_t>(), F.valA.as<uint64_t>(),
-                            (size_t)kept)))
-    return rc;
-  F.vals = F.valA.as<uint64_t>();
+  if ((rc = sort_chunk_pairs(ctx->stream, F.sortTmp, F.lay, F.keyB, F.keyA, F.valB, F.valA, (size_t)kept))) return rc;
+  F.keys = F.keyA.p;
+  F.vals = F.valA.p;
   return PRB_OK;
 }
 
@@ -440,7 +450,7 @@ static int seed_chunk_one_pass(SubSearch &s, const SeedChunk &c, int64_t np) {
     return rc;
   PRB_HIP(hipMemsetAsync(w.count.p, 0, 16, ctx->stream));
   PRB_HIP(hipMemsetAsync(w.row_count.as<int32_t>() + nsl, 0, 4, ctx->stream));
-  PRB_HIP(launch_seed_extend(F.cands.as<CandDev>(), F.vals, np, s.qb->view, s.pd, s.sc, s.eo, F.seed_qacc.as<double>(),
+  PRB_HIP(launch_seed_extend(F.cands.as<CandDev>(), F.keys, F.vals, F.lay, np, s.qb->view, s.pd, s.sc, s.eo, F.seed_qacc.as<double>(),
                              s.opts.interaction_threshold, s.max_qlen, w.hitsA.p, w.row_count.as<int32_t>(), w.count.as<uint64_t>(),
                              ctx->stream));
   if ((rc = scan_row_counts(ctx, w, nsl))) return rc;
@@ -565,7 +575,7 @@ static int seeds_to_hits(SubSearch &s) {
         PRB_HIP(hipStreamWaitEvent(s.ctx->stream, F.done, 0));
       } else {
         if (F.ahead) PRB_HIP(hipStreamSynchronize(F.stream)); // (not what was expected: its buffers are taken over)
-        if ((rc = issue_front(w, s.qb, s.pd, s.eo.delta, s.k.row_shift, cd + c0, c.nc, c.cents, s.ctx->stream, &np, s.allow, s.ctx))) return rc;
+        if ((rc = issue_front(w, s.qb, s.pd, s.eo.delta, s.k, cd + c0, c.nc, c.cents, s.ctx->stream, &np, s.allow, s.ctx))) return rc;
       }
       F.ahead = false;
       if (np >= 0 && F.unsorted) {
@@ -1298,7 +1308,7 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
       const int64_t cents = (c1 < nb.ncand ? nb.cd[c1].qoff : nb.nqent) - nb.cd[0].qoff;
       SearchWs::FrontStage &F = wsp.front;
       int64_t np = -1;
-      if (issue_front(wsp, qb, ps.pd, delta, knobs.row_shift, nb.cd, c1, cents, F.stream, &np, ps.allow, nullptr) != PRB_OK || np < 0 ||
+      if (issue_front(wsp, qb, ps.pd, delta, knobs, nb.cd, c1, cents, F.stream, &np, ps.allow, nullptr) != PRB_OK || np < 0 ||
           hipEventRecord(F.done, F.stream) != hipSuccess) {
         (void)hipStreamSynchronize(F.stream); // (whatever part of it was issued is not used)
         return;
@@ -1365,6 +1375,18 @@ extern "C" {
 int prb_search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
                     prb_hitset **out) {
   return search_page(ctx, qb, db, page, opts, last_stage, SearchMode::kRecords, out);
+}
+
+int prb_seed_pair_layout(int64_t nchars, int64_t query_span, int32_t row_shift, int32_t sort_bits, int32_t local_order, int32_t pair_wide,
+                         int32_t out[6]) {
+  if (!out || nchars < 1 || query_span < 0) {
+    set_error("prb_seed_pair_layout: bad argument");
+    return PRB_ERR_ARG;
+  }
+  const PairLayout L = pair_layout(nchars, query_span, std::min(row_shift, 30), std::max(sort_bits, 1), local_order != 0, pair_wide != 0);
+  const int32_t v[6] = {L.narrow, L.pbits, L.kbits, L.begin, L.local_bits, L.wide_key()};
+  std::copy(v, v + 6, out);
+  return PRB_OK;
 }
 
 // prb_distinct_sites / prb_chain_sites: the caller's records as a list of the search's own layout (the fields the

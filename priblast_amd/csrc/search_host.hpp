@@ -59,7 +59,8 @@ struct SearchWs {
 #undef X
   DevBuf resumePool[kLdsTiers - 1]; // resumePool[t]: the state dumps of the hits that outgrow LDS tier t (trimmable)
   // The front of the one-pass seed path for a chunk of candidates - candidates and their pair offsets on the device,
-  // query-side window sums, the pairs' keys and values, sorted - in buffers of its own, so that it can be issued for
+  // query-side window sums, the pairs' keys and values in the chunk's layout (`lay`: 4 + 4 bytes per pair and buffer in
+  // the narrow one, up to 8 + 8 in the wide one), sorted - in buffers of its own, so that it can be issued for
   // the NEXT sub-batch, on a stream of its own, while this sub-batch is in its last, nearly idle stretch (search_range):
   // ~7 ms of bandwidth-bound work per configs[2] query beside the ~2 ms that the ~150 longest extensions of a query run
   // alone (twice) and the final sort / filter / copies, instead of standing in line behind them.
@@ -72,14 +73,14 @@ struct SearchWs {
     const CandDev *cd = nullptr;
     int32_t nc = 0;
     int64_t np = 0;
-    const uint64_t *vals = nullptr; // the sorted values (valB; under a pair mask valA: the compaction writes valB)
+    PairLayout lay;             // how keyA / keyB / valA / valB hold the chunk's pairs
+    const void *keys = nullptr, *vals = nullptr; // the sorted pairs (keyB, valB; under a pair mask keyA, valA: the compaction writes the B's)
     // Under a pair mask (issue_front): a ballot word, a count and its scanned offset per 64 pairs, and the number of
     // allowed pairs on its way to the host.  The sort takes that number, so a front issued ahead stops behind the
     // compaction; finish_front sorts what is left when the chunk is taken up.
     DevBuf ballot, wcount, woff, scanTmp;
     PinnedBuf kept_pin;
-    bool unsorted = false;      // the compacted pairs are still to be sorted
-    int key_bits = 0;           // ... by keys of this many bits
+    bool unsorted = false;      // the compacted pairs are still to be sorted (by `lay`)
     int64_t np_all = 0;         // the chunk's pairs before the compaction
     int init() {
       if (stream) return PRB_OK;
@@ -277,11 +278,44 @@ template <class Call> int with_temp(DevBuf &tmp, const char *what, Call &&call) 
   return PRB_OK;
 }
 
-// one stable radix sort of (key, value) pairs by the low `bits` bits of the keys
+// one stable radix sort of (key, value) pairs by the bits [begin, end) of the keys
+template <class K, class V>
+int sort_pairs(hipStream_t s, DevBuf &tmp, const K *kin, K *kout, const V *vin, V *vout, size_t n, unsigned begin, unsigned end) {
+  return with_temp(tmp, "rocprim::radix_sort_pairs",
+                   [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, n, begin, end, s); });
+}
+// ... by the low `bits` bits of the keys
 template <class K, class V>
 int sort_pairs(hipStream_t s, DevBuf &tmp, const K *kin, K *kout, const V *vin, V *vout, size_t n, unsigned bits) {
-  return with_temp(tmp, "rocprim::radix_sort_pairs",
-                   [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, n, 0, bits, s); });
+  return sort_pairs(s, tmp, kin, kout, vin, vout, n, 0u, bits);
+}
+
+// The layout of a chunk's pairs (PairLayout, search_kernels.hpp) for a page of `nchars` characters, queries that span
+// `qspan` (last - first of the chunk) and the knobs PRB_SEED_ROW_SHIFT, PRB_SEED_SORT_BITS, PRB_SEED_LOCAL_ORDER and
+// PRB_SEED_PAIR_WIDE.  Narrow when position and query fit 32 bits together.  The radix sort then covers at most
+// `sort_bits` bits from the top - two passes of 8 bits by default - and leaves up to kPairLocalBits bits above the row
+// shift to the tiles of k_seed_extend: begin = max(shift, kbits - sort_bits), but no more than shift + kPairLocalBits
+// (pairs further apart than that within a tile gain nothing from the tile's order: the sort takes those bits, in a
+// pass more).  A row shift beyond the position bits sorts by query alone.  row_shift < 0 (suffix-array order: the list
+// form takes every chunk): no layout, kbits = 0.
+inline PairLayout pair_layout(int64_t nchars, int64_t qspan, int row_shift, int sort_bits, bool local_order, bool force_wide) {
+  PairLayout L;
+  if (row_shift < 0) return L;
+  const int qbits = bits_for(std::max<int64_t>(1, qspan)), pbits = bits_for(std::max<int64_t>(1, nchars - 1));
+  if (!force_wide && pbits + qbits <= 32) {
+    L.narrow = true;
+    L.pbits = pbits;
+    L.kbits = pbits + qbits;
+    const int shift = std::min(row_shift, pbits);
+    L.begin = shift;
+    if (local_order) L.begin = std::min(std::max(shift, L.kbits - std::max(sort_bits, 1)), shift + kPairLocalBits);
+    L.local_bits = L.begin - shift;
+    return L;
+  }
+  L.shift = row_shift;
+  L.pbits = bits_for(std::max<int64_t>(1, (nchars - 1) >> row_shift));
+  L.kbits = L.pbits + qbits;
+  return L;
 }
 
 // out <- the entries of `in` (a list, or nullptr: 0..n-1) whose flag is set, in order; *nsel = how many, copied back

@@ -149,25 +149,44 @@ hipError_t launch_blk_seq(const PageDev &pg, int32_t *blk_seq, hipStream_t s);
 // (ungapped_kernels.hip, "seeds -> extended hits in one pass").  pair0[c] = first pair of candidate c; at most
 // kMaxFusedCands candidates of at most kMaxFusedEntries query entries each.
 constexpr int64_t kMaxFusedCands = 1 << 20, kMaxFusedEntries = 1 << 12;
+// How the pairs of a chunk are held between launch_pair_keys, the radix sort and launch_seed_extend (chosen by
+// pair_layout, search_host.hpp).  The order wanted is (query, database position >> row shift), for locality only.
+//   narrow  key   u32 (query - first query) << pbits | database position; sorted on its bits [begin, kbits) alone,
+//           value u32 candidate : 20 | query entry within the candidate : 12
+//   wide    key   u32 or u64 (query - first query) << pbits | database position >> shift; sorted on all kbits bits,
+//           value u64 database position : 32 | candidate : 20 | query entry : 12
+struct PairLayout {
+  bool narrow = false;
+  int shift = 0;      // wide: the key holds the position >> shift (narrow: 0, the key holds the position itself)
+  int pbits = 0;      // bits of the key's position part
+  int kbits = 0;      // bits of the whole key: the end bit of the sort (0: no pair sort at all, suffix-array order)
+  int begin = 0;      // the begin bit of the sort
+  int local_bits = 0; // narrow: key bits [begin - local_bits, begin) are put in order tile by tile in launch_seed_extend
+  bool wide_key() const { return !narrow && kbits > 32; }
+  size_t key_bytes() const { return wide_key() ? 8 : 4; }
+  size_t val_bytes() const { return narrow ? 4 : 8; }
+};
+constexpr int kPairLocalBits = 5; // a tile is ordered on at most as many bits (32 buckets of ~64 pairs, a wavefront each)
 hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t ncand, int64_t npairs, const PageDev &pg, int qmin,
-                            int shift, int dbits, bool wide, void *key, uint64_t *val, hipStream_t s);
+                            const PairLayout &lay, void *key, void *val, hipStream_t s);
 // Under a pair mask, between launch_pair_keys and the sort: the pairs whose (query, target) is allowed, compacted in
 // order.  launch_allow_test: pair p's bit - the query of its candidate, the sequence of its database entry (sa_seq) - as
 // one ballot word and one count per 64 pairs (allow_words(npairs) of each, and one more count, a zero, for the scan);
 // launch_allow_scatter: behind the exclusive scan `off` of the counts, the allowed pairs' keys and values to their places.
 inline int64_t allow_words(int64_t npairs) { return (npairs + 63) / 64; }
-hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const uint64_t *val, int64_t npairs, const PageDev &pg,
-                             const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s);
-hipError_t launch_allow_scatter(const void *key_in, const uint64_t *val_in, int64_t npairs, bool wide, const uint64_t *ballot,
-                                const int64_t *off, void *key_out, uint64_t *val_out, hipStream_t s);
+hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const void *val, const PairLayout &lay, int64_t npairs,
+                             const PageDev &pg, const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s);
+hipError_t launch_allow_scatter(const void *key_in, const void *val_in, int64_t npairs, const PairLayout &lay, const uint64_t *ballot,
+                                const int64_t *off, void *key_out, void *val_out, hipStream_t s);
 // A workgroup takes kFusePairs pairs and keeps what survives in its slice of `slices` (kFusePairs records of
 // kSliceRecBytes each), slice_count[b] of them; nseed[0] += seeds, nseed[1] = max(nseed[1], length of the longest hit
-// kept).  launch_collect_slices packs the slices into `out` (slice b at slice_off[b] = the exclusive scan of the counts).
+// kept).  keys, vals = the sorted pairs in the layout `lay` (the wide one reads no keys).  launch_collect_slices packs the
+// slices into `out` (slice b at slice_off[b] = the exclusive scan of the counts).
 constexpr int kFusePairs = 2048, kSliceRecBytes = 48;
 inline int64_t fused_slices(int64_t npairs) { return (npairs + kFusePairs - 1) / kFusePairs; }
-hipError_t launch_seed_extend(const CandDev *cands, const uint64_t *vals, int64_t npairs, const QBatchDev &qb, const PageDev &pg,
-                              const SearchConst &sc, ExtOpts o, const double *qacc, double thr, int max_query_len, void *slices,
-                              int32_t *slice_count, uint64_t *nseed, hipStream_t s);
+hipError_t launch_seed_extend(const CandDev *cands, const void *keys, const void *vals, const PairLayout &lay, int64_t npairs,
+                              const QBatchDev &qb, const PageDev &pg, const SearchConst &sc, ExtOpts o, const double *qacc, double thr,
+                              int max_query_len, void *slices, int32_t *slice_count, uint64_t *nseed, hipStream_t s);
 hipError_t launch_collect_slices(const void *slices, const int32_t *slice_count, const int64_t *slice_off, int64_t nslices, HitRec *out,
                                  hipStream_t s);
 

@@ -16,6 +16,9 @@ struct SearchKnobs { // (read_search_knobs, capi_search.hip)
   double budget;       // pairs per sub-batch
   double chunk_pairs;  // pairs per chunk of candidates
   int row_shift;       // rows / pairs in (query, database position >> row_shift) order, see k_row_key; -1 keeps suffix-array order
+  int sort_bits;       // the one-pass form's radix sort covers at most this many key bits from the top (pair_layout, search_host.hpp)
+  bool local_order;    // ... and the tiles of k_seed_extend order the bits it leaves above the row shift (0: the sort takes them all)
+  bool pair_wide;      // testing: the wide pair layout for every chunk
   bool fused;          // seeds -> hits under -f in one pass (0: written as a list, extended and thinned in separate passes)
   bool front_ahead;    // the front of the next sub-batch's seed path is issued while this one is extended
   bool sort_four_keys, sort_two_lengths;

@@ -285,11 +285,20 @@ __global__ __launch_bounds__(kBlock) void k_ungapped(HitSoA h, int64_t n, QBatch
 
 // ---------------------------------------------------------------------------- seeds -> extended hits in one pass
 // Every (query SA entry, database SA entry) PAIR of a chunk of candidates is one unit of work:
-//   k_pair_key    pair p -> sort key (query, database position >> shift) and a 64-bit value
-//                 {database position : 32, candidate : 20, query entry within the candidate : 12}
-//   (radix sort of the pairs by key)
+//   k_pair_key    pair p -> a sort key and a value, in one of two layouts (PairLayout, pair_layout in search_host.hpp):
+//                 narrow  key {query - first query : qbits, database position : pbits} in 32 bits,
+//                         value {candidate : 20, query entry within the candidate : 12} in 32 bits
+//                 wide    key (query - first query, database position >> shift) in 32 or 64 bits,
+//                         value {database position : 32, candidate : 20, query entry : 12} in 64 bits
+//                         (pages or sub-batches whose narrow key would need more than 32 bits; PRB_SEED_PAIR_WIDE=1)
+//   (radix sort of the pairs by key.  The order is there for locality only - (query, position >> shift) - so the narrow
+//   layout sorts on the key's bits [g, qbits + pbits) alone, g >= shift: 8 B per pair and pass instead of 12 B, and with
+//   g = qbits + pbits - 16 two passes of the radix sort instead of three)
 //   k_seed_extend pair -> SeedSearch::CalcInteractionEnergy's test (seed_search.cpp:47-99); a seed is walked at once
-//                 (UngappedExtension::Run) and, if it is not above the -f threshold, kept (see SliceRec)
+//                 (UngappedExtension::Run) and, if it is not above the -f threshold, kept (see SliceRec).  Where g > shift a
+//                 workgroup first buckets its tile's pairs on the key bits [shift, g) the sort left out - a counting sort
+//                 in LDS, at most 32 buckets - and takes them in bucket order: a wavefront's 64 pairs then come from about
+//                 as narrow a span of the database as behind a sort on all the bits
 //   k_collect_slices  what the workgroups kept -> the list of 64-byte records
 // Against k_seed (count) / scan / k_seed (emit) / k_ungapped / threshold compaction this never writes the seeds
 // (3.3e9 x 48 B per configs[2] step, written once, read and written by the walk, read by the compaction), and
@@ -305,10 +314,11 @@ __global__ __launch_bounds__(kBlock) void k_blk_seq(PageDev pg, int32_t *blk_seq
   if (b < nblk) blk_seq[b] = seq_of(pg, (int)(b << kSeqBlkShift));
 }
 
-template <class Key>
+// (Val = uint32_t: the narrow layout, shift = 0 and dbits = pbits; uint64_t: the wide one)
+template <class Key, class Val>
 __global__ __launch_bounds__(kBlock) void k_pair_key(const CandDev *__restrict__ cands, const int64_t *__restrict__ pair0, int ncand,
                                                      int64_t npairs, PageDev pg, int qmin, int shift, int dbits,
-                                                     Key *__restrict__ key, uint64_t *__restrict__ val) {
+                                                     Key *__restrict__ key, Val *__restrict__ val) {
   __shared__ int64_t s_p0[kBlock + 1];
   __shared__ int s_c0;
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -339,18 +349,21 @@ __global__ __launch_bounds__(kBlock) void k_pair_key(const CandDev *__restrict__
   const uint32_t rowl = pl / qw, jrel = pl - rowl * qw;
   const uint32_t db_sp = (uint32_t)pg.sa[c.sp_db + (int)rowl];
   key[p] = ((Key)(uint32_t)(c.query - qmin) << dbits) | (Key)(db_sp >> shift);
-  val[p] = (uint64_t)db_sp | ((uint64_t)(uint32_t)ci << 32) | ((uint64_t)jrel << (32 + kPairCandBits));
+  if constexpr (sizeof(Val) == 4) val[p] = (uint32_t)ci | (jrel << kPairCandBits);
+  else val[p] = (uint64_t)db_sp | ((uint64_t)(uint32_t)ci << 32) | ((uint64_t)jrel << (32 + kPairCandBits));
 }
 
 __device__ __forceinline__ int pair_cand(uint64_t v) { return (int)((v >> 32) & ((1u << kPairCandBits) - 1)); }
+__device__ __forceinline__ int pair_cand(uint32_t v) { return (int)(v & ((1u << kPairCandBits) - 1)); }
 
 // Under a pair mask (AllowDev): which of the chunk's pairs are searched at all.  Pair p's query is its candidate's, its
 // target the sequence of its database SA entry (sa_seq; the entry from p's place among its candidate's pairs, as
 // k_pair_key numbers them).  A wavefront's 64 answers are one ballot: the word and its population count are all that is
 // written, so the scatter behind the scan of the counts reads no candidate and no bit of the mask again, the order of
 // the pairs is kept and the result does not depend on how the wavefronts are scheduled.
+template <class Val>
 __global__ __launch_bounds__(kBlock) void k_allow_test(const CandDev *__restrict__ cands, const int64_t *__restrict__ pair0,
-                                                       const uint64_t *__restrict__ val, int64_t npairs, PageDev pg, AllowDev allow,
+                                                       const Val *__restrict__ val, int64_t npairs, PageDev pg, AllowDev allow,
                                                        uint64_t *__restrict__ ballot, int32_t *__restrict__ count) {
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   bool ok = false;
@@ -366,10 +379,10 @@ __global__ __launch_bounds__(kBlock) void k_allow_test(const CandDev *__restrict
     count[p >> 6] = __popcll(m);
   }
 }
-template <class Key>
-__global__ __launch_bounds__(kBlock) void k_allow_scatter(const Key *__restrict__ key_in, const uint64_t *__restrict__ val_in, int64_t npairs,
+template <class Key, class Val>
+__global__ __launch_bounds__(kBlock) void k_allow_scatter(const Key *__restrict__ key_in, const Val *__restrict__ val_in, int64_t npairs,
                                                           const uint64_t *__restrict__ ballot, const int64_t *__restrict__ off,
-                                                          Key *__restrict__ key_out, uint64_t *__restrict__ val_out) {
+                                                          Key *__restrict__ key_out, Val *__restrict__ val_out) {
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (p >= npairs) return;
   const uint64_t m = ballot[p >> 6];
@@ -392,7 +405,10 @@ static_assert(sizeof(SliceRec) == kSliceRecBytes, "three 16-byte stores");
 
 struct FuseArgs {
   const CandDev *cands;
-  const uint64_t *vals;
+  const uint32_t *keys; // narrow layout: the sorted keys, the database position in their low `pbits` bits
+  const void *vals;     // the sorted values: uint32_t (narrow layout) or uint64_t each
+  int pbits;
+  int lshift, lbits;    // narrow layout: a tile is taken in the order of its key bits [lshift, lshift + lbits) (0 bits: as it is)
   int64_t npairs;
   const double *qacc;
   double thr;
@@ -404,11 +420,22 @@ struct FuseArgs {
 
 constexpr int kFusePer = kFusePairs / kBlock;
 static_assert(kFusePer * kBlock == kFusePairs, "pairs per workgroup");
-template <int kAhead>
+static_assert(kFusePairs <= 65536 && kPairLocalBits <= 5, "a tile's order: 16-bit places, the buckets scanned by half a wavefront");
+// the candidate of sorted pair x
+template <bool kNarrow> __device__ __forceinline__ int sorted_pair_cand(const FuseArgs &f, int64_t x) {
+  if constexpr (kNarrow) return pair_cand(static_cast<const uint32_t *>(f.vals)[x]);
+  else return pair_cand(static_cast<const uint64_t *>(f.vals)[x]);
+}
+// The order of a tile lives in LDS as 2048 16-bit places (4 KB), not as the pairs themselves (16 KB): with the tables
+// and a 2 kb query a workgroup holds 25.5 KB, five workgroups per CU is what the registers allow, and 41.5 KB would
+// leave three.  The pairs are read again through the places; the tile's 16 KB were read a moment before.
+template <int kAhead, bool kNarrow>
 __global__ __launch_bounds__(kBlock) void k_seed_extend(FuseArgs f, QBatchDev qb, PageDev pg, SearchConst sc, ExtOpts o) {
   extern __shared__ __align__(16) uint8_t ungapped_smem[];
   __shared__ int32_t s_tab[kUtTotal];
   __shared__ unsigned s_kept, s_seeds, s_maxlen;
+  __shared__ uint16_t s_place[kNarrow ? kFusePairs : 1];
+  __shared__ unsigned s_bucket[kNarrow ? 1 << kPairLocalBits : 1];
   const int64_t b0 = (int64_t)blockIdx.x * kFusePairs;
   if (b0 >= f.npairs) return;
   const int64_t b1 = (b0 + kFusePairs < f.npairs ? b0 + kFusePairs : f.npairs) - 1;
@@ -417,16 +444,19 @@ __global__ __launch_bounds__(kBlock) void k_seed_extend(FuseArgs f, QBatchDev qb
     s_seeds = 0;
     s_maxlen = 0;
   }
+  if constexpr (kNarrow)
+    if (f.lbits > 0 && threadIdx.x < (1 << kPairLocalBits)) s_bucket[threadIdx.x] = 0;
   for (int t = threadIdx.x; t < kUtTotal; t += kBlock)
     s_tab[t] = t < kUtInternal   ? sc.stack37[t]
                : t < kUtMismatch ? sc.internal37[t - kUtInternal]
                : t < kUtInt11    ? sc.mismatchI37[t - kUtMismatch]
                                  : sc.int11[t - kUtInt11];
   const UngappedTabs tabs{s_tab + kUtStack, s_tab + kUtInternal, s_tab + kUtMismatch, s_tab + kUtInt11, sc.int22};
-  // the pairs are sorted by query first: one query for the whole workgroup unless it sits on a boundary
-  const int q0 = f.cands[pair_cand(f.vals[b0])].query;
+  // the pairs are sorted by query first: one query for the whole workgroup unless it sits on a boundary (the first and
+  // the last pair as the sort left them: behind the tile's own ordering the queries of such a tile interleave)
+  const int q0 = f.cands[sorted_pair_cand<kNarrow>(f, b0)].query;
   const int nslots = qb.len[q0] + 1;
-  const bool staged = q0 == f.cands[pair_cand(f.vals[b1])].query && nslots <= f.qcap; // uniform over the workgroup
+  const bool staged = q0 == f.cands[sorted_pair_cand<kNarrow>(f, b1)].query && nslots <= f.qcap; // uniform over the workgroup
   float *s_acc = reinterpret_cast<float *>(ungapped_smem), *s_cond = s_acc + f.qcap;
   uint8_t *s_enc = reinterpret_cast<uint8_t *>(s_cond + f.qcap);
   if (staged) {
@@ -439,17 +469,64 @@ __global__ __launch_bounds__(kBlock) void k_seed_extend(FuseArgs f, QBatchDev qb
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
+  const int ntile = (int)(b1 - b0) + 1;
+  bool placed = false; // s_place[0 .. ntile) = the tile's pairs in bucket order (uniform over the workgroup)
+  if constexpr (kNarrow) {
+    placed = f.lbits > 0;
+    if (placed) { // a counting sort of the tile on key bits [lshift, lshift + lbits): count, scan, place
+      const unsigned bmask = (1u << f.lbits) - 1;
+      unsigned bucket[kFusePer];
+#pragma unroll
+      for (int it = 0; it < kFusePer; it++) {
+        const int i = it * kBlock + threadIdx.x;
+        bucket[it] = 0;
+        if (i < ntile) {
+          bucket[it] = (f.keys[b0 + i] >> f.lshift) & bmask;
+          atomicAdd(&s_bucket[bucket[it]], 1u);
+        }
+      }
+      __syncthreads();
+      if (threadIdx.x < 64) { // exclusive scan of the counts
+        const unsigned cnt = lane < (1 << kPairLocalBits) ? s_bucket[lane] : 0;
+        unsigned incl = cnt;
+        for (int d = 1; d < (1 << kPairLocalBits); d <<= 1) {
+          const unsigned up = (unsigned)__shfl_up((int)incl, d);
+          if (lane >= d) incl += up;
+        }
+        if (lane < (1 << kPairLocalBits)) s_bucket[lane] = incl - cnt;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int it = 0; it < kFusePer; it++) {
+        const int i = it * kBlock + threadIdx.x;
+        if (i < ntile) s_place[atomicAdd(&s_bucket[bucket[it]], 1u)] = (uint16_t)i;
+      }
+      __syncthreads();
+    }
+  }
   SliceRec *slice = f.slices + b0;
   unsigned nseed = 0, maxlen = 0; // (the longest hit kept: the sort behind this packs the lengths into as many bits)
   for (int it = 0; it < kFusePer; it++) {
-    const int64_t x = b0 + (int64_t)it * kBlock + threadIdx.x;
+    const int i = it * kBlock + threadIdx.x; // (places beyond the tile's pairs are not filled: i < ntile comes first)
     bool keep = false;
     WalkHit w{};
     int query = 0;
-    if (x <= b1) {
-      const uint64_t v = f.vals[x];
-      const int db_sp = (int)(uint32_t)v, jrel = (int)(v >> (32 + kPairCandBits));
-      const CandDev c = f.cands[pair_cand(v)];
+    if (i < ntile) {
+      int64_t x = b0 + i;
+      int db_sp, jrel, ci;
+      if constexpr (kNarrow) {
+        if (placed) x = b0 + s_place[i];
+        const uint32_t v = static_cast<const uint32_t *>(f.vals)[x];
+        db_sp = (int)(f.keys[x] & ((1u << f.pbits) - 1));
+        jrel = (int)(v >> kPairCandBits);
+        ci = pair_cand(v);
+      } else {
+        const uint64_t v = static_cast<const uint64_t *>(f.vals)[x];
+        db_sp = (int)(uint32_t)v;
+        jrel = (int)(v >> (32 + kPairCandBits));
+        ci = pair_cand(v);
+      }
+      const CandDev c = f.cands[ci];
       int id = pg.blk_seq[db_sp >> kSeqBlkShift];
       while (id + 1 < pg.nseq && pg.start_pos[id + 1] <= db_sp) id++;
       const int sp0 = pg.start_pos[id];
@@ -556,32 +633,45 @@ hipError_t launch_blk_seq(const PageDev &pg, int32_t *blk_seq, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_pair_keys(const CandDev *cands, const int64_t *pair0, int32_t ncand, int64_t npairs, const PageDev &pg, int qmin,
-                            int shift, int dbits, bool wide, void *key, uint64_t *val, hipStream_t s) {
-  if (wide)
-    return launch_1d(k_pair_key<uint64_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, shift, dbits, (uint64_t *)key, val);
-  return launch_1d(k_pair_key<uint32_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, shift, dbits, (uint32_t *)key, val);
+                            const PairLayout &lay, void *key, void *val, hipStream_t s) {
+  if (lay.narrow)
+    return launch_1d(k_pair_key<uint32_t, uint32_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, 0, lay.pbits, (uint32_t *)key,
+                     (uint32_t *)val);
+  if (lay.wide_key())
+    return launch_1d(k_pair_key<uint64_t, uint64_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, lay.shift, lay.pbits,
+                     (uint64_t *)key, (uint64_t *)val);
+  return launch_1d(k_pair_key<uint32_t, uint64_t>, npairs, kBlock, 0, s, cands, pair0, ncand, npairs, pg, qmin, lay.shift, lay.pbits,
+                   (uint32_t *)key, (uint64_t *)val);
 }
-hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const uint64_t *val, int64_t npairs, const PageDev &pg,
-                             const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s) {
-  return launch_1d(k_allow_test, npairs, kBlock, 0, s, cands, pair0, val, npairs, pg, allow, ballot, count);
+hipError_t launch_allow_test(const CandDev *cands, const int64_t *pair0, const void *val, const PairLayout &lay, int64_t npairs,
+                             const PageDev &pg, const AllowDev &allow, uint64_t *ballot, int32_t *count, hipStream_t s) {
+  if (lay.narrow) return launch_1d(k_allow_test<uint32_t>, npairs, kBlock, 0, s, cands, pair0, (const uint32_t *)val, npairs, pg, allow, ballot, count);
+  return launch_1d(k_allow_test<uint64_t>, npairs, kBlock, 0, s, cands, pair0, (const uint64_t *)val, npairs, pg, allow, ballot, count);
 }
-hipError_t launch_allow_scatter(const void *key_in, const uint64_t *val_in, int64_t npairs, bool wide, const uint64_t *ballot,
-                                const int64_t *off, void *key_out, uint64_t *val_out, hipStream_t s) {
-  if (wide)
-    return launch_1d(k_allow_scatter<uint64_t>, npairs, kBlock, 0, s, (const uint64_t *)key_in, val_in, npairs, ballot, off, (uint64_t *)key_out,
-                     val_out);
-  return launch_1d(k_allow_scatter<uint32_t>, npairs, kBlock, 0, s, (const uint32_t *)key_in, val_in, npairs, ballot, off, (uint32_t *)key_out,
-                   val_out);
+hipError_t launch_allow_scatter(const void *key_in, const void *val_in, int64_t npairs, const PairLayout &lay, const uint64_t *ballot,
+                                const int64_t *off, void *key_out, void *val_out, hipStream_t s) {
+  if (lay.narrow)
+    return launch_1d(k_allow_scatter<uint32_t, uint32_t>, npairs, kBlock, 0, s, (const uint32_t *)key_in, (const uint32_t *)val_in, npairs, ballot,
+                     off, (uint32_t *)key_out, (uint32_t *)val_out);
+  if (lay.wide_key())
+    return launch_1d(k_allow_scatter<uint64_t, uint64_t>, npairs, kBlock, 0, s, (const uint64_t *)key_in, (const uint64_t *)val_in, npairs, ballot,
+                     off, (uint64_t *)key_out, (uint64_t *)val_out);
+  return launch_1d(k_allow_scatter<uint32_t, uint64_t>, npairs, kBlock, 0, s, (const uint32_t *)key_in, (const uint64_t *)val_in, npairs, ballot, off,
+                   (uint32_t *)key_out, (uint64_t *)val_out);
 }
-hipError_t launch_seed_extend(const CandDev *cands, const uint64_t *vals, int64_t npairs, const QBatchDev &qb, const PageDev &pg,
-                              const SearchConst &sc, ExtOpts o, const double *qacc, double thr, int max_query_len, void *slices,
-                              int32_t *slice_count, uint64_t *nseed, hipStream_t s) {
+hipError_t launch_seed_extend(const CandDev *cands, const void *keys, const void *vals, const PairLayout &lay, int64_t npairs,
+                              const QBatchDev &qb, const PageDev &pg, const SearchConst &sc, ExtOpts o, const double *qacc, double thr,
+                              int max_query_len, void *slices, int32_t *slice_count, uint64_t *nseed, hipStream_t s) {
   if (npairs <= 0) return hipSuccess;
   const int qcap = query_lds_slots(max_query_len);
-  FuseArgs f{cands, vals, npairs, qacc, thr, static_cast<SliceRec *>(slices), slice_count, reinterpret_cast<unsigned long long *>(nseed),
-             qcap};
+  const int lbits = lay.narrow ? std::min(lay.local_bits, kPairLocalBits) : 0;
+  FuseArgs f{cands, lay.narrow ? static_cast<const uint32_t *>(keys) : nullptr, vals, lay.pbits, lay.begin - lbits, lbits, npairs, qacc, thr,
+             static_cast<SliceRec *>(slices), slice_count, reinterpret_cast<unsigned long long *>(nseed), qcap};
   // (4, 5 or 6 positions fetched ahead instead of 8: the same 273-290 ms per configs[2] step)
-  hipLaunchKernelGGL(k_seed_extend<8>, dim3((unsigned)fused_slices(npairs)), dim3(kBlock), (size_t)qcap * 9, s, f, qb, pg, sc, o);
+  if (lay.narrow)
+    hipLaunchKernelGGL((k_seed_extend<8, true>), dim3((unsigned)fused_slices(npairs)), dim3(kBlock), (size_t)qcap * 9, s, f, qb, pg, sc, o);
+  else
+    hipLaunchKernelGGL((k_seed_extend<8, false>), dim3((unsigned)fused_slices(npairs)), dim3(kBlock), (size_t)qcap * 9, s, f, qb, pg, sc, o);
   return hipGetLastError();
 }
 hipError_t launch_collect_slices(const void *slices, const int32_t *slice_count, const int64_t *slice_off, int64_t nslices, HitRec *out,
