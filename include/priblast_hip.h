@@ -208,6 +208,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   region kernel, launches = 4, or 3 when there is no region; prb_covset_merge: 1);
  * "null" (prb_search_page_observed / _decoys, prb_nullset_observe / _add_pairs: the scatter or the fold into the null
  *   table, launches = 1 per sub-batch with final hits; prb_nullset_finish: the selection and the gather, launches = 2);
+ * "group" (prb_search_page_groups / prb_groupset_add_pairs: the fold into the group table, launches = 3 per sub-batch with
+ *   final hits; prb_groupset_merge: 1; prb_groupset_finish: the flags, the selections and the gather, launches = 2 to 5);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -713,6 +715,83 @@ const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns);
 void prb_nullset_counts(const prb_nullset *ns, int64_t counts[3]);
 void prb_nullset_decoy_counts(const prb_nullset *ns, int64_t counts[3]);
 void prb_nullset_free(prb_nullset *ns);
+
+/* ---- one record per (query, group of targets) (`ris -t -G FILE`): a group table on the device ----
+ * A transcriptome lists isoforms that share most of their exons, so a strong interaction comes back once per isoform.  A
+ * GROUP MAP gives every database sequence (page, db_id) a group index g in [0, G), 1 <= G <= the number of sequences (a
+ * gene, say).  For one batch of queries and one database the table holds, over everything merged into it, one record per
+ * (query, group) that has at least one member pair with a final hit:
+ *   s         the group's BEST member pair: field for field the prb_pair_summary that prb_search_page_summary returns for
+ *             it.  Best = the lowest e_min, compared as doubles (-0.0 == +0.0; the stored record keeps the bits it came
+ *             with); ties go to the lower page, then the lower db_id.  This is a total order that the record itself
+ *             carries.  It is NOT the tie rule of the top-N table (prb_topset), which orders equal energies by the pair's
+ *             position in its page's list: a dense fold has no such position
+ *   page      the best member's page;  group: g
+ *   members   the member targets with at least one final hit
+ *   hits      the sum of the members' s.hits.  No energy is summed across members: isoforms share exons, so such a sum
+ *             would count one site several times, and a floating-point sum would depend on the merge order.  s.e_sum and
+ *             s.hits are the best member's own
+ *   rank      the record's rank within its query under a top-N selection, else 0
+ * Every column is an integer sum or a minimum over a total order, so the table is - bit for bit - independent of the
+ * order of the pages, of how a batch is cut into sub-batches and chunks (PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS, page
+ * residency) and of how the pages are shared between tables that are merged later.
+ *   prb_groupset_create     an empty table for qb and db; group_of_page[p][db_id] = the group of sequence db_id of page p,
+ *                           every value in [0, ngroups) (checked on the host, else PRB_ERR_ARG; uploaded once per page).
+ *                           The table is dense: one slot of 96 B per (query, group) - the 64 B record, its two 8 B keys,
+ *                           the two counters - in HBM, plus 4 B per database sequence for the map; PRB_ERR_ARG for 2^32
+ *                           slots or more, PRB_ERR_NOMEM when the table cannot be allocated.  It owns all its device
+ *                           memory and must be freed before its context, its batch and its database
+ *   prb_search_page_groups  the search of prb_search_page_summary against `page`, its records folded into the table on the
+ *                           device (nothing is copied to the host): integer atomics for the counters, staged 64-bit atomic
+ *                           minima for the best member (energy key, then page << 32 | db_id among the records that hold the
+ *                           slot's energy; the one winner writes its record).  Argument checks and option limits are those
+ *                           of prb_search_page_summary; it honours distinct_sites, chain_sites and allowed_pairs.  The
+ *                           table was made with this context for this batch and this database; a page is merged once
+ *   prb_groupset_add_pairs  the same fold for a caller's records of `page` in host memory.  PRB_ERR_ARG, table untouched,
+ *                           for a record whose query or db_id is out of range or whose hits are below 1, a (query, db_id)
+ *                           that comes twice in the list, and a page already merged
+ *   prb_groupset_merge      two unfinished tables over disjoint page sets into one, on the device, under the rules of
+ *                           prb_topset_merge; the two maps must be equal.  dst then holds - bit for bit - the table of the
+ *                           union; src is left empty: it can be freed, or finished to zero records
+ *   prb_groupset_finish     n = 0: the occupied slots are selected on the device, their records gathered there and copied
+ *                           to the host in one copy: by query ascending, then group ascending, rank = 0.  1 <= n <= 1024:
+ *                           only each query's n groups of lowest s.e_min, ties by (page, s.db_id) of the best member, by
+ *                           query, then rank (a workgroup per query selects in LDS).  Any other n is PRB_ERR_ARG.  The
+ *                           device memory is released; nothing can be merged after it (a second call does nothing)
+ *   prb_groupset_counts     the stage counts of prb_pairset_counts, summed over the searched pages
+ * A call refused by its checks leaves the table as it was; a merge that fails part way leaves it unusable.  On the device
+ * every kernel checks query, db_id, page and group against the table's ranges again; a violation raises the table's `bad`
+ * flag and writes nothing, and the next call on the table returns PRB_ERR_STATE.  A table holds pages searched with one
+ * value of distinct_sites and of chain_sites.  Stage timer "group": the fold (launches = 3 per sub-batch with final hits
+ * and per prb_groupset_add_pairs with records), prb_groupset_merge (1), and prb_groupset_finish: the flags, the selection
+ * and the gather (launches = 3, or 2 when the table is empty; with n > 0 two more, the per-query selection and the
+ * selection of the kept ranks). */
+typedef struct prb_group_pair {
+  prb_pair_summary s;    /* the group's best member pair */
+  int32_t page, group;   /* the best member's page; the group index */
+  int32_t members, rank; /* member targets with >= 1 final hit; rank within the query (0 without a top-N selection) */
+  int64_t hits;          /* sum of the members' s.hits */
+} prb_group_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_group_pair) == 88, "prb_group_pair: no padding");
+#endif
+typedef struct prb_groupset prb_groupset;
+int prb_groupset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const int32_t *const *group_of_page, int32_t ngroups,
+                        prb_groupset **out);
+int prb_search_page_groups(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_groupset *gs);
+int prb_groupset_add_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const prb_pair_summary *pairs, int64_t n);
+int prb_groupset_merge(prb_ctx *ctx, prb_groupset *dst, prb_groupset *src);
+int prb_groupset_finish(prb_ctx *ctx, prb_groupset *gs, int32_t n);
+int64_t prb_groupset_size(const prb_groupset *gs);
+const prb_group_pair *prb_groupset_pairs(const prb_groupset *gs);
+void prb_groupset_counts(const prb_groupset *gs, int64_t counts[3]);
+void prb_groupset_free(prb_groupset *gs);
+/* The lines of `ris -t -G FILE` for one batch: per record the `-t` line of the best member (prb_write_summary_lines'
+ * columns, numbered from id0 on) followed by ",<group name>,<members>,<targets in the group>,<hits>"; group_names[g] and
+ * group_sizes[g] for every group of the table.  Arguments and results as prb_write_top_lines. */
+int prb_write_group_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_group_pair *recs,
+                          int64_t nrecs, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
+                          int64_t *nlines, int64_t *nbytes);
 
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered

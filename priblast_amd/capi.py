@@ -77,6 +77,11 @@ NULL_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("decoys", "<i4"), ("
                                           ("null_min", "<f8")])
 assert NULL_DTYPE.itemsize == 96
 
+# prb_group_pair: the embedded prb_pair_summary's fields (the group's best member pair), then that pair's page, the group,
+# the members with a hit, the rank within the query and the members' hits (`ris -t -G FILE`)
+GROUP_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("group", "<i4"), ("members", "<i4"), ("rank", "<i4"), ("group_hits", "<i8")])
+assert GROUP_DTYPE.itemsize == 88
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -200,6 +205,17 @@ SYMBOLS = {
     "prb_nullset_free": (None, [ctypes.c_void_p]),
     "prb_write_null_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                             c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_groupset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p), c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_groupset_add_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64]),
+    "prb_groupset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_groupset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32]),
+    "prb_groupset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_groupset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_groupset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_groupset_free": (None, [ctypes.c_void_p]),
+    "prb_write_group_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                             P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -833,6 +849,45 @@ class NullSet(_Table):
         return tuple(c)
 
 
+class GroupSet(_Table):
+    """prb_groupset: per (query, group of database sequences) of one batch, the group's best member pair and the integer
+    sums over its members, in a dense table on the device that pages are folded into.  group_of_page[p][db_id] = the group
+    of sequence db_id of page p, in [0, ngroups).  Close it before its context."""
+    PREFIX = "groupset"
+
+    def __init__(self, ctx, qb, db, group_of_page, ngroups):
+        maps = [np.ascontiguousarray(m, np.int32) for m in group_of_page]
+        ptrs = (ctypes.c_void_p * max(len(maps), 1))(*[m.ctypes.data if len(m) else None for m in maps])
+        h = ctypes.c_void_p()
+        _check(lib().prb_groupset_create(ctx.h, qb.h, db.h, ptrs, ngroups, ctypes.byref(h)))
+        self.h, self.ctx, self.qb, self.db = h, ctx, qb, db
+
+    def merge(self, page, opts=None):
+        """prb_search_page_groups: searches the batch against `page` and folds the pairs' records into the table"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_groups(self.ctx.h, self.qb.h, self.db.h, page, ctypes.byref(o), self.h))
+
+    def add_pairs(self, page, pairs):
+        """prb_groupset_add_pairs: a caller's PAIR_DTYPE records of the batch against `page`"""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        _check(lib().prb_groupset_add_pairs(self.ctx.h, self.h, page, pairs.ctypes.data if len(pairs) else None, len(pairs)))
+
+    def finish(self, n=0):
+        """prb_groupset_finish -> structured array GROUP_DTYPE (a copy): by query, then group (n = 0), or each query's n
+        best groups by query, then rank"""
+        return self._finish("pairs", GROUP_DTYPE, n)
+
+
+def search_groups(ctx, qb, db, group_of_page, ngroups, n=0, opts=None, pages=None, with_counts=False):
+    """The group table of the batch over the pages (all of them, in this order, by default) -> structured array
+    GROUP_DTYPE.  with_counts: -> (records, (seed, ungapped, final) counts summed over the pages)."""
+    with GroupSet(ctx, qb, db, group_of_page, ngroups) as gs:
+        for p in range(db.npages) if pages is None else pages:
+            gs.merge(p, opts)
+        recs, counts = gs.finish(n), gs.counts()
+    return (recs, counts) if with_counts else recs
+
+
 def null_decoys(seqs, ndecoys, seed=1, file_pos0=0):
     """the decoys of a batch as search_null searches them -> (sequences, owner, decoy), query by query, decoy by decoy"""
     dseqs, owner, decoy = [], [], []
@@ -979,6 +1034,16 @@ def write_null_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):
     (-1: formatted and counted only)."""
     recs = np.ascontiguousarray(recs, NULL_DTYPE)
     return _write(lib().prb_write_null_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), id0, fd)
+
+
+def write_group_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes, id0=0, fd=-1):
+    """Lines of `ris -t -G FILE` for one batch: recs as GroupSet.finish returns them; group_names / group_sizes indexed by
+    group.  -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, GROUP_DTYPE)
+    gn = (ctypes.c_char_p * max(len(group_names), 1))(*[g.encode() for g in group_names])
+    gsz = np.ascontiguousarray(group_sizes, np.int32)
+    return _write(lib().prb_write_group_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
+                  gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
 
 
 def write_target_lines(db, qnames, qlen_unmasked, recs, id0=0, fd=-1):

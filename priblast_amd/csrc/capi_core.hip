@@ -267,6 +267,11 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->null_timer.launches;
     return PRB_OK;
   }
+  if (std::strcmp(stage, "group") == 0) {
+    if (ms) *ms = ctx->group_timer.ms;
+    if (launches) *launches = ctx->group_timer.launches;
+    return PRB_OK;
+  }
   auto it = ctx->timers.find(stage);
   if (ms) *ms = it == ctx->timers.end() ? 0.0 : it->second.ms;
   if (launches) *launches = it == ctx->timers.end() ? 0 : it->second.launches;
@@ -285,6 +290,7 @@ void prb_ctx_reset_timers(prb_ctx *ctx) {
     ctx->chain_timer = prb::StageTimer{};
     ctx->coverage_timer = prb::StageTimer{};
     ctx->null_timer = prb::StageTimer{};
+    ctx->group_timer = prb::StageTimer{};
     ctx->slow_hits = 0;
   }
 }

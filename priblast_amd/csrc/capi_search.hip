@@ -1056,6 +1056,21 @@ static int emit_null(SubSearch &s, bool decoys) {
   return PRB_OK;
 }
 
+// prb_search_page_groups: the pairs' records folded into the group table on the device; nothing leaves it
+static int emit_groups(SubSearch &s) {
+  prb_ctx *ctx = s.ctx;
+  SearchWs &w = s.w;
+  int rc;
+  int64_t npairs = 0;
+  if ((rc = pair_runs(s, &npairs))) return rc;
+  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
+  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
+  if ((rc = merge_group_pairs(ctx, static_cast<prb_groupset *>(s.table), s.page, w.packed.p, npairs))) return rc;
+  s.hs->hits_total += s.nfin;
+  return PRB_OK;
+}
+
 static int emit_final(SubSearch &s) {
   switch (s.mode) {
   case SearchMode::kRecords: return emit_records(s);
@@ -1067,6 +1082,7 @@ static int emit_final(SubSearch &s) {
   case SearchMode::kCoverage: return emit_coverage(s);
   case SearchMode::kNullObserved: return emit_null(s, false);
   case SearchMode::kNullDecoys: return emit_null(s, true);
+  case SearchMode::kGroups: return emit_groups(s);
   }
   return PRB_ERR_STATE;
 }

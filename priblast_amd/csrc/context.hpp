@@ -75,4 +75,5 @@ struct prb_ctx {
   int time_end(prb::StageTimer &t, int64_t launches);
 
   prb::StageTimer null_timer; // the scatter, the fold and the finish of the null table (stage "null"), kept apart like the others
+  prb::StageTimer group_timer; // the fold, the merge and the finish of the group table (stage "group"), likewise
 };

@@ -661,6 +661,35 @@ struct prb_nullset : prb::TableState {
   ~prb_nullset() { release(); } // (also on the error paths of prb_nullset_create)
 };
 
+// prb_groupset_create .. prb_groupset_free: the group table of one batch against one database (capi_groups.hip), folded
+// into sub-batch by sub-batch (merge_group_pairs).  It owns all its device memory; `table` = GroupSlot[nq * ngroups],
+// the one block that prb_groupset_merge reads of another table
+struct prb_groupset : prb::MergeTable {
+  int32_t ngroups = 0;
+  std::vector<std::vector<int32_t>> map; // per page: the groups of its sequences (what two tables must share to be merged)
+  std::vector<prb::DevBuf> map_dev;      // ... on the device
+  bool bad = false;                      // the device's `bad` flag, as the last call left it
+  prb::DevBuf badflag;
+  prb::DevBuf h_rec;                     // prb_groupset_add_pairs: the caller's records
+  prb::DevBuf occ, sel, top, keep, out;  // prb_groupset_finish: flags and lists of the selection, the records
+  std::vector<prb_group_pair> pairs;     // prb_groupset_finish
+  int64_t slots() const { return (int64_t)nq * ngroups; }
+  size_t bytes() const { return (size_t)slots() * sizeof(prb::GroupSlot); }
+  prb::GroupTab view() const {
+    return prb::GroupTab{table.as<prb::GroupSlot>(), badflag.as<uint32_t>(), slots(), nq, ngroups, (int32_t)map.size()};
+  }
+  prb::GroupPage page_view(size_t page) const { return prb::GroupPage{map_dev[page].as<int32_t>(), (int32_t)page, (int32_t)map[page].size()}; }
+  // nothing of the table is released while work on it may still be queued on its context's stream
+  void release() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (prb::DevBuf *b : {&table, &badflag, &h_rec, &occ, &sel, &top, &keep, &out}) b->release();
+    for (prb::DevBuf &b : map_dev) b.release();
+  }
+  ~prb_groupset() { release(); } // (also on the error paths of prb_groupset_create)
+};
+
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS): PRB_HOST_THREADS, else half of the CPUs the
 // process may keep busy, at most 32 (capi_pages.hip)
@@ -677,6 +706,7 @@ enum class SearchMode {
   kCoverage, // prb_search_page_coverage: the hits merged into the per-target coverage table on the device
   kNullObserved, // prb_search_page_observed: per-pair records of the real batch scattered into the null table on the device
   kNullDecoys,   // prb_search_page_decoys: per-pair records of a batch of decoys folded into the null table's counters
+  kGroups,       // prb_search_page_groups: per-pair records folded into the group table on the device
 };
 // (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
@@ -687,7 +717,7 @@ std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, co
                                           double hybrid_threshold);
 // capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
 // the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits / prb_targetset / prb_covset of
-// kTop / kProfile / kTopHits / kTargets / kCoverage
+// kTop / kProfile / kTopHits / kTargets / kCoverage (and the prb_nullset / prb_groupset of kNull* / kGroups)
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
@@ -717,4 +747,6 @@ int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h,
 // owners and decoy numbers ns->own holds - into the null table
 int merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
 int merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
+// capi_groups.hip: the npairs pair records at `packed` (device) of `page` into the group table
+int merge_group_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const void *packed, int64_t npairs);
 } // namespace prb

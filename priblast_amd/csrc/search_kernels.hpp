@@ -598,4 +598,44 @@ hipError_t launch_null_count(const void *rec, int64_t nrec, const int32_t *owner
 // prb_nullset_finish: out[j] (prb_null_pair) of the observed slot idx[j]; tbase[npages + 1] = the pages' first targets
 hipError_t launch_null_gather(const NullTab &t, const uint32_t *idx, int64_t n, const int64_t *tbase, int32_t npages, void *out, hipStream_t s);
 
+// ============================================================================ group_kernels.hip: the group table
+// (prb_groupset_*)  The table of one batch against one database in HBM: a slot per (query q, group g), slot
+// q * ngroups + g.  A slot: the best member pair's summary record, the 128-bit key it won with - the energy key of its
+// e_min, then page << 32 | db_id - and the integer sums over the members.  An empty slot has members == 0 and both keys
+// all ones.  bad: set when a record or a slot names a query, a sequence, a page or a group outside the table.
+struct GroupSlot {
+  uint64_t s[8];                  // the best member's prb_pair_summary
+  unsigned long long ekey, tie;   // the key of that record
+  unsigned long long hits;        // sum of the members' hits
+  uint32_t members, reserved;     // member pairs merged
+};
+static_assert(sizeof(GroupSlot) == 96, "GroupSlot: 64 B of record, two keys, two counters");
+struct GroupTab {
+  GroupSlot *slot;  // [nslots]
+  uint32_t *bad;
+  int64_t nslots;   // nq * ngroups
+  int32_t nq, ngroups, npages;
+};
+struct GroupPage {
+  const int32_t *group_of; // [nseq] the groups of the page's sequences
+  int32_t page, nseq;
+};
+inline constexpr int kGroupSelect = 2048; // the entries a workgroup of launch_group_select sorts at a time
+// every slot back to empty
+hipError_t launch_group_clear(const GroupTab &t, hipStream_t s);
+// rec[0, nrec) = launch_pair_fold's records (prb_pair_summary) of the batch against the page, or a caller's, folded into
+// the slots of their (query, group of db_id), a lane per record, in three launches: the counters and the minimum energy
+// key per slot (a slot whose key drops forgets its tie key), the minimum tie key among the records that hold their
+// slot's energy key, and the one record that holds both keys into its slot.  A (query, page) comes once.
+hipError_t launch_group_fold(const void *rec, int64_t nrec, const GroupTab &t, const GroupPage &pg, hipStream_t s);
+// prb_groupset_merge: slot by slot of src (a table of the same shape) into t: counters added, the lower key's record kept
+hipError_t launch_group_join(const GroupTab &t, const GroupSlot *src, hipStream_t s);
+// prb_groupset_finish: occ[i] = slot i has members
+hipError_t launch_group_flags(const GroupTab &t, uint8_t *occ, hipStream_t s);
+// ... with n > 0: occ[0, nocc) = the occupied slots, ascending; a workgroup per query sorts its slots by key, kGroupSelect
+// entries in LDS at a time, and leaves the n lowest: top[q * n + r] = the slot of rank r, keep[q * n + r] = there is one
+hipError_t launch_group_select(const GroupTab &t, const uint32_t *occ, int64_t nocc, int32_t n, uint32_t *top, uint8_t *keep, hipStream_t s);
+// ... out[j] (prb_group_pair) of the slot idx[j] (top == nullptr, rank 0), or of the slot top[idx[j]] with rank idx[j] % n
+hipError_t launch_group_gather(const GroupTab &t, const uint32_t *idx, int64_t nrec, const uint32_t *top, int32_t n, void *out, hipStream_t s);
+
 } // namespace prb

@@ -238,6 +238,28 @@ void format_null_piece(const Piece &pc, const NullView &v, const std::vector<Seq
   }
 }
 
+// the `-t` line of the group's best member, then - in place of its newline - the group columns
+void format_group_piece(const Piece &pc, const GroupView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_group_pair &x = v.r[i];
+    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
+    b.n--; // (the newline)
+    const size_t len = std::strlen(v.group_names[x.group]);
+    char *p = b.room(len + 100);
+    char *const p0 = p;
+    *p++ = ',';
+    std::memcpy(p, v.group_names[x.group], len);
+    p += len;
+    for (long long f : {(long long)x.members, (long long)v.group_sizes[x.group], (long long)x.hits}) {
+      *p++ = ',';
+      p = put_int(p, f);
+    }
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
 void format_profile_piece(const Piece &pc, const ProfileView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   const std::string &qname = v.names[pc.q];
   int64_t id = pc.id;
@@ -339,6 +361,13 @@ int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, 
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_null_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the top-N records: in output order already, each with its own page)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
+      [&](const Piece &pc, Buf &b) { format_group_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

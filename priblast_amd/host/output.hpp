@@ -79,6 +79,18 @@ struct NullView : QueryView {
 };
 int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -t -G FILE` (prb_groupset_pairs): the `-t` line of every group's best member with the group columns behind
+// it, in the records' order (by query, then group or rank), numbered from id0 on:
+//   Id,qname,qlen,dbname,dblen,Hits,MinE,SumE,Eacc,Ehyb,(q0-qN:db0-dbN) ,Group,Members,GroupSize,GroupHits
+// group_names / group_sizes are indexed by the records' group.
+struct GroupView : QueryView {
+  const prb_group_pair *r = nullptr;
+  int64_t n = 0;
+  const char *const *group_names = nullptr;
+  const int32_t *group_sizes = nullptr;
+};
+int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 // Lines of `ris -r N` (prb_targetset_pairs): the same lines again, in the records' order (by page, target and rank),
 // numbered from id0 on.  The queries are those of the whole run: `names` and `qlen_unmasked` are indexed by the
 // records' query identifiers.

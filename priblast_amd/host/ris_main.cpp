@@ -160,6 +160,14 @@ void usage() {
             "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
             "    -Z INT    with -z: the seed of the shuffles [default:1]\n"
+            "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
+            "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
+            "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
+            "              is the -t line of the group's best member (lowest minimum interaction energy; ties: the earlier\n"
+            "              target of the database), and behind it the group's name, its members with a hit, its targets and\n"
+            "              the members' hits; lines by query, then group in database order; with -n N the N best groups of\n"
+            "              each query, by rank (with -n, -u, -j, -L and the search options; not with -z, -k, -q, -r, -c, -b,\n"
+            "              nor with WORLD_SIZE > 1: p-values per group and the best queries per group are not implemented)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -182,14 +190,14 @@ thread_local bool t_team_thread = false;
 
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
-// N best pairs per target, `-c` the regions of each target that enough queries cover.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull };
+// N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -210,6 +218,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'c', "the regions of each target bound by at least D queries", bit(kT) | bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR), -1, true},
     {'z', "an empirical p-value per pair from N shuffled decoys", bit(kN) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
     {'Z', "the seed of the decoys' shuffles", 0, kZ, false},
+    {'G', "one line per query-group pair", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -217,6 +226,7 @@ struct Args {
   std::string in, out, db, tmp;
   std::string pairlist; // -L
   bool have_pairlist = false;
+  std::string groupfile; // -G
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
@@ -244,6 +254,7 @@ struct Free {
   void operator()(prb_profset *p) const { prb_profset_free(p); }
   void operator()(prb_tophits *p) const { prb_tophits_free(p); }
   void operator()(prb_nullset *p) const { prb_nullset_free(p); }
+  void operator()(prb_groupset *p) const { prb_groupset_free(p); }
 };
 template <class T> using Handle = std::unique_ptr<T, Free>;
 
@@ -257,6 +268,7 @@ struct BatchResult {
   Handle<prb_profset> prof;                    // kProfile
   Handle<prb_tophits> tophits;                 // kTopHits
   Handle<prb_nullset> null;                    // kNull
+  Handle<prb_groupset> groups;                 // kGroups
 };
 
 // The result of one batch (in rank mode: of one round of batches, gathered), waiting to be written.
@@ -532,9 +544,17 @@ struct PairList {
   std::vector<int64_t> page_first; // [npages + 1]
 };
 
+// -G: the group of every database sequence, per page; the groups numbered by their first member in database order
+struct GroupMap {
+  std::vector<std::vector<int32_t>> of_page;
+  std::vector<std::string> names;
+  std::vector<int32_t> sizes; // targets per group
+};
+
 struct Run {
   Args a;
   PairList list;
+  GroupMap groups;
   std::vector<std::string> names, seqs; // the queries
   int world = 1, rank = 0;              // one process per GPU?  (torchrun / mpirun style environment)
   bool rank_mode = false;
@@ -583,6 +603,7 @@ void check_switches(const Args &a) {
 
 OutputMode output_mode(const Args &a) {
   if (a.given[kZ]) return OutputMode::kNull;
+  if (a.given[kG]) return OutputMode::kGroups;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
 }
@@ -591,7 +612,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -616,6 +637,7 @@ Args parse_args(int argc, char **argv) {
     case 'c': a.given[kC] = true, a.depth = parse_count(optarg); break;
     case 'L': a.have_pairlist = true, a.pairlist = optarg; break;
     case 'z': a.given[kZ] = true, a.decoys = parse_count(optarg); break;
+    case 'G': a.given[kG] = true, a.groupfile = optarg; break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -636,18 +658,24 @@ Args parse_args(int argc, char **argv) {
   return a;
 }
 
-// -L FILE: every line checked and turned into targets per query; any fault ends the run here, before any GPU work
-void load_pairlist(Run &r) {
-  if (!r.a.have_pairlist) return;
-  std::FILE *f = std::fopen(r.a.pairlist.c_str(), "r");
-  if (!f) die("Error: can't open the pair list (-L): " + r.a.pairlist);
+// the text of the file `path` that a switch names (`what`: "the pair list (-L)")
+std::string read_list_file(const std::string &path, const char *what) {
+  std::FILE *f = std::fopen(path.c_str(), "r");
+  if (!f) die(std::string("Error: can't open ") + what + ": " + path);
   std::string text;
   char buf[1 << 16];
   size_t got;
   while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
   const bool bad = std::ferror(f) != 0;
   std::fclose(f);
-  if (bad) die("Error: can't read the pair list (-L): " + r.a.pairlist);
+  if (bad) die(std::string("Error: can't read ") + what + ": " + path);
+  return text;
+}
+
+// -L FILE: every line checked and turned into targets per query; any fault ends the run here, before any GPU work
+void load_pairlist(Run &r) {
+  if (!r.a.have_pairlist) return;
+  const std::string text = read_list_file(r.a.pairlist, "the pair list (-L)");
   std::vector<std::vector<std::string>> pages;
   if (const std::string err = prb::read_db_names(r.a.db, pages); !err.empty()) die(err); // (no GPU is needed to refuse a list)
   PairList &pl = r.list;
@@ -687,6 +715,53 @@ void load_pairlist(Run &r) {
     }
   }
   if (allowed == 0) die("Error: the pair list (-L) allows no pair: " + r.a.pairlist);
+}
+
+// -G FILE: every line checked, then every database sequence given its group; any fault ends the run here, before any GPU
+// work.  Groups are identified by name; a sequence that the file does not list is in the group named by its own name.
+void load_groups(Run &r) {
+  if (!r.a.given[kG]) return;
+  const std::string text = read_list_file(r.a.groupfile, "the group file (-G)");
+  std::vector<std::vector<std::string>> pages;
+  if (const std::string err = prb::read_db_names(r.a.db, pages); !err.empty()) die(err); // (no GPU is needed to refuse a file)
+  std::map<std::string, bool> in_db;
+  for (const auto &pg : pages)
+    for (const std::string &n : pg) in_db[n] = true;
+  std::map<std::string, std::string> group_of_target;
+  size_t lineno = 0;
+  for (size_t at = 0; at < text.size();) {
+    size_t end = text.find('\n', at);
+    if (end == std::string::npos) end = text.size();
+    std::string line = text.substr(at, end - at);
+    at = end + 1;
+    lineno++;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    const std::string where = "Error: group file line " + std::to_string(lineno) + ": ";
+    const size_t tab = line.find('\t');
+    if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos) die(where + "expected target name, one tab, group name");
+    const std::string tn = line.substr(0, tab), gn = line.substr(tab + 1);
+    if (gn.empty()) die(where + "the group name is empty");
+    if (!in_db.count(tn)) die(where + "no database sequence is named \"" + tn + "\"");
+    const auto ins = group_of_target.emplace(tn, gn);
+    if (!ins.second && ins.first->second != gn)
+      die(where + "\"" + tn + "\" is listed with the groups \"" + ins.first->second + "\" and \"" + gn + "\"");
+  }
+  GroupMap &gm = r.groups;
+  std::map<std::string, int32_t> index_of; // groups numbered by their first member in database order
+  gm.of_page.resize(pages.size());
+  for (size_t p = 0; p < pages.size(); p++)
+    for (const std::string &n : pages[p]) {
+      const auto listed = group_of_target.find(n);
+      const std::string &gn = listed == group_of_target.end() ? n : listed->second;
+      const auto ins = index_of.emplace(gn, (int32_t)gm.names.size());
+      if (ins.second) {
+        gm.names.push_back(gn);
+        gm.sizes.push_back(0);
+      }
+      gm.of_page[p].push_back(ins.first->second);
+      gm.sizes[(size_t)ins.first->second]++;
+    }
 }
 
 // -L: the mask of a prepared batch's queries (input positions `ids`)
@@ -849,6 +924,10 @@ std::string header_text(const Run &r) {
   case OutputMode::kTargets:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
+  case OutputMode::kGroups:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
+                    "Group Hits\n";
   case OutputMode::kNull:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Decoys, Null Hits, Null LE, "
@@ -958,6 +1037,16 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
+  case OutputMode::kGroups: {
+    std::vector<const int32_t *> maps;
+    for (const auto &m : r.groups.of_page) maps.push_back(m.data());
+    prb_groupset *t = nullptr;
+    rc = prb_groupset_create(w.ctx, qb, w.db, maps.data(), (int32_t)r.groups.names.size(), &t);
+    res.groups.reset(t);
+    if (rc == PRB_ERR_NOMEM)
+      die(std::string("Error: ") + prb_last_error() + "; lower PRB_BATCH (queries per batch: " + std::to_string(r.batch) + ")");
+    break;
+  }
   case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
   case OutputMode::kCoverage:
   case OutputMode::kNull: // (search_null_batch makes its own)
@@ -980,6 +1069,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &o, mine.tophits.get()); break;
+  case OutputMode::kGroups: rc = prb_search_page_groups(w.ctx, qb, w.db, page, &o, mine.groups.get()); break;
   case OutputMode::kSummary: {
     prb_pairset *ps = nullptr;
     rc = prb_search_page_summary(w.ctx, qb, w.db, page, &o, &ps);
@@ -1008,6 +1098,11 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kTop: run(kTopOps, &BatchResult::top); break;
   case OutputMode::kProfile: run(kProfOps, &BatchResult::prof); break;
   case OutputMode::kTopHits: run(kTopHitsOps, &BatchResult::tophits); break;
+  case OutputMode::kGroups: // (its finish takes the -n of the run: 0 without one)
+    for (BatchResult *o : others)
+      if (prb_groupset_merge(w.ctx, mine.groups.get(), o->groups.get())) die(prb_last_error());
+    if (prb_groupset_finish(w.ctx, mine.groups.get(), r.a.given[kN] ? r.a.top : 0)) die(prb_last_error());
+    break;
   case OutputMode::kTargets:
   case OutputMode::kCoverage:
   case OutputMode::kNull:
@@ -1211,6 +1306,21 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
           (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size())
         die("Error: bad record in the null table");
     return written_or_die(prb::format_null_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kGroups: {
+    prb::GroupView v;
+    set_queries(v, job);
+    v.r = prb_groupset_pairs(job.res.groups.get());
+    v.n = prb_groupset_size(job.res.groups.get());
+    std::vector<const char *> gnames;
+    for (const std::string &g : r.groups.names) gnames.push_back(g.c_str());
+    v.group_names = gnames.data();
+    v.group_sizes = r.groups.sizes.data();
+    for (int64_t i = 0; i < v.n; i++)
+      if (v.r[i].s.query < 0 || (size_t)v.r[i].s.query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages || v.r[i].s.db_id < 0 ||
+          (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size() || v.r[i].group < 0 || (size_t)v.r[i].group >= gnames.size())
+        die("Error: bad record in the group table");
+    return written_or_die(prb::format_group_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kTargets:
   case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
@@ -1434,6 +1544,7 @@ struct Team {
       res.top = std::move(mine.top);
       res.prof = std::move(mine.prof);
       res.tophits = std::move(mine.tophits);
+      res.groups = std::move(mine.groups);
       signal([&] { tb->taken = true; });
     } else {
       wait([&] { return tb->taken; });
@@ -1652,6 +1763,7 @@ int ris_main(int argc, char **argv) {
   const std::string err = prb::read_fasta(r.a.in, r.names, r.seqs);
   if (!err.empty()) die(err);
   load_pairlist(r);
+  load_groups(r);
   const std::vector<int> devices = rank_setup(r);
   split_setup(r);
   open_workers(r, devices);
