@@ -116,7 +116,7 @@ static_assert(sizeof(prb_ris_opts) == 64, "prb_ris_opts: eleven fields, allowed_
  * extended - it is kept only as the one hit of its pair's chain.  As for distinct_sites: a kept hit is the plain search's hit field
  * for field and base pair for base pair (only bp_offset may differ), the result depends neither on PRB_BATCH,
  * PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS, PRB_SPLIT, PRB_DEVICES nor on page residency, every mode takes the thinned
- * list, counts[2] stays the number of final hits BEFORE the selection, and each of the five result tables holds pages of
+ * list, counts[2] stays the number of final hits BEFORE the selection, and each of the result tables holds pages of
  * one value of chain_sites (a second one is PRB_ERR_ARG with the field's name, the table untouched; prb_*_merge refuse
  * two tables of different values unless one has merged no page). */
 

@@ -217,80 +217,21 @@ int prb_ctx_stage_ms(prb_ctx *ctx, const char *stage, double *ms, int64_t *launc
     if (launches) *launches = ctx->slow_hits;
     return PRB_OK;
   }
-  if (std::strcmp(stage, "summary") == 0) {
-    if (ms) *ms = ctx->summary_timer.ms;
-    if (launches) *launches = ctx->summary_timer.launches;
-    return PRB_OK;
+  const prb::StageTimer *t = nullptr;
+  for (int i = 0; i < (int)prb::ModeTimer::kCount && !t; i++)
+    if (std::strcmp(stage, prb::kModeTimerName[i]) == 0) t = &ctx->mode_timers[i];
+  if (!t) {
+    auto it = ctx->timers.find(stage);
+    if (it != ctx->timers.end()) t = &it->second;
   }
-  if (std::strcmp(stage, "top") == 0) {
-    if (ms) *ms = ctx->top_timer.ms;
-    if (launches) *launches = ctx->top_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "profile") == 0) {
-    if (ms) *ms = ctx->profile_timer.ms;
-    if (launches) *launches = ctx->profile_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "tophits") == 0) {
-    if (ms) *ms = ctx->tophits_timer.ms;
-    if (launches) *launches = ctx->tophits_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "targets") == 0) {
-    if (ms) *ms = ctx->targets_timer.ms;
-    if (launches) *launches = ctx->targets_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "distinct") == 0) {
-    if (ms) *ms = ctx->distinct_timer.ms;
-    if (launches) *launches = ctx->distinct_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "chain") == 0) {
-    if (ms) *ms = ctx->chain_timer.ms;
-    if (launches) *launches = ctx->chain_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "allow") == 0) {
-    if (ms) *ms = ctx->allow_timer.ms;
-    if (launches) *launches = ctx->allow_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "coverage") == 0) {
-    if (ms) *ms = ctx->coverage_timer.ms;
-    if (launches) *launches = ctx->coverage_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "null") == 0) {
-    if (ms) *ms = ctx->null_timer.ms;
-    if (launches) *launches = ctx->null_timer.launches;
-    return PRB_OK;
-  }
-  if (std::strcmp(stage, "group") == 0) {
-    if (ms) *ms = ctx->group_timer.ms;
-    if (launches) *launches = ctx->group_timer.launches;
-    return PRB_OK;
-  }
-  auto it = ctx->timers.find(stage);
-  if (ms) *ms = it == ctx->timers.end() ? 0.0 : it->second.ms;
-  if (launches) *launches = it == ctx->timers.end() ? 0 : it->second.launches;
+  if (ms) *ms = t ? t->ms : 0.0;
+  if (launches) *launches = t ? t->launches : 0;
   return PRB_OK;
 }
 void prb_ctx_reset_timers(prb_ctx *ctx) {
   if (ctx) {
     ctx->timers.clear();
-    ctx->summary_timer = prb::StageTimer{};
-    ctx->allow_timer = prb::StageTimer{};
-    ctx->top_timer = prb::StageTimer{};
-    ctx->profile_timer = prb::StageTimer{};
-    ctx->tophits_timer = prb::StageTimer{};
-    ctx->targets_timer = prb::StageTimer{};
-    ctx->distinct_timer = prb::StageTimer{};
-    ctx->chain_timer = prb::StageTimer{};
-    ctx->coverage_timer = prb::StageTimer{};
-    ctx->null_timer = prb::StageTimer{};
-    ctx->group_timer = prb::StageTimer{};
+    for (prb::StageTimer &t : ctx->mode_timers) t = prb::StageTimer{};
     ctx->slow_hits = 0;
   }
 }

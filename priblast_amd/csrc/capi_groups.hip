@@ -53,16 +53,17 @@ int clear_group_table(prb_groupset &gs) {
 
 // prb_search_page_groups (per sub-batch) and prb_groupset_add_pairs: the records folded into their slots, in a bracket of
 // the "group" timer
-int prb::merge_group_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const void *packed, int64_t npairs) {
+static int merge_group_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const void *packed, int64_t npairs) {
   int rc;
   if (page < 0 || (size_t)page >= gs->map_dev.size()) return refuse("prb_search_page_groups", "page out of range", PRB_ERR_STATE);
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_group_fold(packed, npairs, gs->view(), gs->page_view((size_t)page), ctx->stream));
-  if ((rc = ctx->time_end(ctx->group_timer, 3))) return rc;
+  if ((rc = ctx->time_end(ModeTimer::kGroup, 3))) return rc;
   if ((rc = fetch_bad(ctx, gs))) return rc;
   if (gs->bad) return refuse("prb_search_page_groups", kBadRecord, PRB_ERR_STATE);
   return PRB_OK;
 }
+int prb_groupset::take(const SubBatch &b) { return merge_group_pairs(ctx, this, b.page, b.records, b.npairs); }
 
 extern "C" {
 
@@ -123,7 +124,7 @@ int prb_groupset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, co
 int prb_search_page_groups(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_groupset *gs) {
   const char *fn = "prb_search_page_groups";
   if (gs && gs->bad) return refuse(fn, kBadRecord, PRB_ERR_STATE);
-  return merge_page(fn, "group", kFinishFn, SearchMode::kGroups, gs, ctx, qb, db, page, opts);
+  return merge_page(fn, "group", kFinishFn, gs, ctx, qb, db, page, opts);
 }
 
 int prb_groupset_add_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const prb_pair_summary *pairs, int64_t n) {
@@ -159,7 +160,7 @@ int prb_groupset_merge(prb_ctx *ctx, prb_groupset *dst, prb_groupset *src) {
   const prb_db *db = src->db;
   const size_t npages = src->merged.size();
   const int rc = join_tables(
-      fn, &prb_ctx::group_timer, 1, ctx, dst, src, src->bytes(), nothing_more,
+      fn, ModeTimer::kGroup, 1, ctx, dst, src, src->bytes(), nothing_more,
       [&](void *slots) -> int {
         PRB_HIP(launch_group_join(dst->view(), static_cast<const GroupSlot *>(slots), ctx->stream));
         return PRB_OK;
@@ -216,7 +217,7 @@ int prb_groupset_finish(prb_ctx *ctx, prb_groupset *gs, int32_t n) {
       PRB_HIP(hipMemcpyAsync(gs->pairs.data(), gs->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
       launches++;
     }
-    if ((rc = ctx->time_end(ctx->group_timer, launches))) return rc; // (synchronises: the copy is over)
+    if ((rc = ctx->time_end(ModeTimer::kGroup, launches))) return rc; // (synchronises: the copy is over)
     if ((rc = fetch_bad(ctx, gs))) return rc;
     if (gs->bad) {
       gs->pairs.clear();

@@ -136,21 +136,25 @@ int upload_records(prb_ctx *ctx, prb_nullset *ns, const prb_pair_summary *pairs,
 
 // prb_search_page_observed (per sub-batch) and prb_nullset_observe: the records into their slots, in a bracket of the
 // "null" timer
-int prb::merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
+static int merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
   int rc;
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_null_observe(packed, npairs, ns->view(), ns->page_view((size_t)page), ctx->stream));
-  if ((rc = ctx->time_end(ctx->null_timer, 1))) return rc;
+  if ((rc = ctx->time_end(ModeTimer::kNull, 1))) return rc;
   return fetch_bad(ctx, ns);
 }
 // prb_search_page_decoys (per sub-batch) and prb_nullset_add_pairs: the records folded into the counters, likewise
-int prb::merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
+static int merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs) {
   int rc;
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_null_count(packed, npairs, ns->own.as<int32_t>(), ns->own.as<int32_t>() + ns->ndq, ns->ndq, ns->view(),
                             ns->page_view((size_t)page), ctx->stream));
-  if ((rc = ctx->time_end(ctx->null_timer, 1))) return rc;
+  if ((rc = ctx->time_end(ModeTimer::kNull, 1))) return rc;
   return fetch_bad(ctx, ns);
+}
+// a sub-batch of the batch being searched: a decoy batch's while prb_search_page_decoys says so, else the real one's
+int prb_nullset::take(const SubBatch &b) {
+  return decoy_phase ? merge_null_decoys(ctx, this, b.page, b.records, b.npairs) : merge_null_observed(ctx, this, b.page, b.records, b.npairs);
 }
 
 extern "C" {
@@ -204,13 +208,8 @@ int prb_search_page_observed(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t p
   PRB_HIP(hipSetDevice(ctx->device));
   ns->observed[(size_t)page] = 1;
   ns->broken = true; // (until the merge is whole)
-  prb_hitset *hs = nullptr;
-  if (int rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kNullObserved, &hs, ns)) return rc;
-  for (int i = 0; i < 3; i++) ns->counts[i] += hs->counts[i];
-  ns->distinct = opts->distinct_sites;
-  ns->chain = opts->chain_sites;
+  if (int rc = search_into_table(ns, ctx, qb, db, page, opts, ns->counts)) return rc;
   ns->broken = false;
-  delete hs;
   return PRB_OK;
 }
 
@@ -228,11 +227,11 @@ int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t pa
   ns->broken = true; // (until the merge is whole)
   mark_decoys(ns, page, owner, decoy, dqb->nq);
   if (int rc = upload_owners(ctx, ns, owner, decoy, dqb->nq)) return rc;
-  prb_hitset *hs = nullptr;
-  if (int rc = search_page(ctx, dqb, db, page, opts, 3, SearchMode::kNullDecoys, &hs, ns)) return rc;
-  for (int i = 0; i < 3; i++) ns->decoy_counts[i] += hs->counts[i];
+  ns->decoy_phase = true;
+  const int rc = search_into_table(ns, ctx, dqb, db, page, opts, ns->decoy_counts, false);
+  ns->decoy_phase = false;
+  if (rc) return rc;
   ns->broken = false;
-  delete hs;
   return PRB_OK;
 }
 
@@ -304,7 +303,7 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
                                  ctx->stream));
       PRB_HIP(hipMemcpyAsync(ns->pairs.data(), ns->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if ((rc = ctx->time_end(ctx->null_timer, nsel ? 2 : 1))) return rc; // (synchronises: the copy is over)
+    if ((rc = ctx->time_end(ModeTimer::kNull, nsel ? 2 : 1))) return rc; // (synchronises: the copy is over)
     if ((rc = fetch_bad(ctx, ns))) return rc;
     if (ns->bad) {
       ns->pairs.clear();

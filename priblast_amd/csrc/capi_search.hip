@@ -387,7 +387,7 @@ static int issue_front(SearchWs &w, const prb_qbatch *qb, const PageDev &pd, int
       return rc;
     PRB_HIP(launch_allow_scatter(F.keyA.p, F.valA.p, np, lay, F.ballot.as<uint64_t>(), F.woff.as<int64_t>(), F.keyB.p, F.valB.p, s));
     PRB_HIP(hipMemcpyAsync(F.kept_pin.p, F.woff.as<int64_t>() + nw, 8, hipMemcpyDeviceToHost, s));
-    if (timed && ((rc = timed->time_end(timed->allow_timer, 3)) || (rc = timed->time_begin()))) return rc;
+    if (timed && ((rc = timed->time_end(ModeTimer::kAllow, 3)) || (rc = timed->time_begin()))) return rc;
     F.unsorted = true;
     *np_out = np;
     return PRB_OK;
@@ -703,7 +703,7 @@ static int final_sort_filter(SubSearch &s) {
 // The two selections inside the (query, db_id) runs of a final list (include/priblast_hip.h): what tells them apart
 enum class SiteRule { kDistinct, kChain };
 static const char *rule_name(SiteRule rule) { return rule == SiteRule::kChain ? "chain sites" : "distinct sites"; }
-static StageTimer &rule_timer(prb_ctx *ctx, SiteRule rule) { return rule == SiteRule::kChain ? ctx->chain_timer : ctx->distinct_timer; }
+static ModeTimer rule_timer(SiteRule rule) { return rule == SiteRule::kChain ? ModeTimer::kChain : ModeTimer::kDistinct; }
 
 // The selection of opts.distinct_sites / opts.chain_sites over the n hits of `h` (sorted, or a caller's list): keep flags
 // in w.keep.  The scratch is what the redundancy filter has left behind (w.endKey, w.pmax, w.state) and a list of the
@@ -738,7 +738,7 @@ static int select_sites(prb_ctx *ctx, SearchWs &w, const HitSoA &h, int64_t n, S
 static int thin_sites(SubSearch &s, SiteRule rule) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  StageTimer &timer = rule_timer(ctx, rule);
+  const ModeTimer timer = rule_timer(rule);
   int rc;
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = select_sites(ctx, w, s.F, s.nfin, rule, s.k))) return rc;
@@ -764,8 +764,8 @@ static int chain_sites(SubSearch &s) { return thin_sites(s, SiteRule::kChain); }
 
 // ------------------------------------------------------------------------- traceback
 // Base pairs of the final hits: from the trace slots of the extension pass; the few hits the slots cannot describe
-// (wave-kernel hits, chains longer than a slot) are extended again.  Leaves the "traceback" bracket open: what an
-// emit_* function does before it closes it still counts there.
+// (wave-kernel hits, chains longer than a slot) are extended again.  Leaves the "traceback" bracket open: what the
+// emit path does before it closes it still counts there.
 static int traceback(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
@@ -869,6 +869,13 @@ static int ensure_slot(PinnedBuf &b, size_t bytes) { return b.ensure(b.cap >= by
 // The base pairs that go with a sub-batch's hit records, in ints: the simplified output prints only the first and the
 // last pair of a hit, so only those two are kept (w.bpEnds); the detailed output keeps every pair (w.bpOut)
 static int64_t record_bp_ints(const SubSearch &s) { return s.opts.output_style == 0 ? s.nfin * 4 : s.bp_total * 2; }
+// the final hits' end pairs, as the simplified output has them: w.bpEnds
+static int bp_ends(SubSearch &s) {
+  SearchWs &w = s.w;
+  if (int rc = w.bpEnds.ensure((size_t)s.nfin * 16)) return rc;
+  PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), s.nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), s.ctx->stream));
+  return PRB_OK;
+}
 // the final hits' records into w.packed (the caller has sized it), their base-pair ranges counted from pair `bp_base`
 // on; *bp_src = the record_bp_ints(s) ints that the ranges index
 static int pack_records(SubSearch &s, int64_t bp_base, const int32_t **bp_src) {
@@ -876,8 +883,7 @@ static int pack_records(SubSearch &s, int64_t bp_base, const int32_t **bp_src) {
   SearchWs &w = s.w;
   const int64_t nfin = s.nfin;
   if (s.opts.output_style == 0) {
-    if (int rc = w.bpEnds.ensure((size_t)nfin * 16)) return rc;
-    PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+    if (int rc = bp_ends(s)) return rc;
     PRB_HIP(launch_pack_hits(s.F, nfin, nullptr, nullptr, bp_base, w.packed.p, ctx->stream));
     *bp_src = w.bpEnds.as<int32_t>();
   } else {
@@ -915,18 +921,16 @@ static int emit_records(SubSearch &s) {
   return ctx->time_end("traceback", 2);
 }
 
-// What the three per-pair modes start with: the final hits' end pairs as the simplified output has them (w.bpEnds),
-// which closes the "traceback" bracket, then - in the bracket of the summary timer, left open - the pairs' runs of the
-// list (contiguous: F is sorted by query, then db_sp, and a sub-batch is a range of whole queries): w.pairStart = the
-// first hit of each of the *npairs pairs
+// What everything per pair starts with: the final hits' end pairs (bp_ends), which closes the "traceback" bracket, then
+// - in the bracket of the summary timer, left open - the pairs' runs of the list (contiguous: F is sorted by query, then
+// db_sp, and a sub-batch is a range of whole queries): w.pairStart = the first hit of each of the *npairs pairs
 static int pair_runs(SubSearch &s, int64_t *npairs) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
   const int64_t nfin = s.nfin;
   const size_t NF = (size_t)nfin;
   int rc;
-  if ((rc = w.bpEnds.ensure(NF * 16))) return rc;
-  PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
+  if ((rc = bp_ends(s))) return rc;
   if ((rc = ctx->time_end("traceback", 2))) return rc;
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = w.pairHead.ensure(NF)) || (rc = w.pairStart.ensure(NF * 4)) || (rc = w.count.ensure(16))) return rc;
@@ -938,6 +942,14 @@ static int pair_runs(SubSearch &s, int64_t *npairs) {
   }
   return PRB_OK;
 }
+// ... and the runs folded into the pairs' records: prb_pair_summary[npairs] in w.packed
+static int fold_pairs(SubSearch &s, int64_t npairs) {
+  SearchWs &w = s.w;
+  if (int rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary))) return rc;
+  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, s.ctx->stream));
+  return PRB_OK;
+}
+
 // prb_search_page_summary: the pairs' records reduced on the device; only they leave it
 static int emit_summary(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
@@ -947,144 +959,44 @@ static int emit_summary(SubSearch &s) {
   int64_t npairs = 0;
   if ((rc = pair_runs(s, &npairs))) return rc;
   const size_t rec_bytes = (size_t)npairs * sizeof(prb_pair_summary);
-  if ((rc = w.packed.ensure(rec_bytes)) || (rc = ensure_slot(w.pin_hits[slot], rec_bytes))) return rc;
-  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
+  if ((rc = ensure_slot(w.pin_hits[slot], rec_bytes)) || (rc = fold_pairs(s, npairs))) return rc;
   if ((rc = copy_out(s, slot, rec_bytes, nullptr, 0))) return rc;
   PRB_HIP(hipEventRecord(s.hs->drain->ev[slot], w.copy_stream));
   s.hs->drain->submit(Drainer::Job{slot, npairs, 0});
   s.hs->hits_total += s.nfin;
-  return ctx->time_end(ctx->summary_timer, 3);
+  return ctx->time_end(ModeTimer::kSummary, 3);
 }
 
-// prb_search_page_top: the pairs' records merged into the top-N table on the device; nothing leaves it
-static int emit_top(SubSearch &s) {
+// Every prb_search_page_* of a result table: what the table's feed asks for (TableFeed, search_host.hpp) prepared in
+// the brackets that are the driver's - "traceback" closed with the end pairs or the records, the summary timer's with
+// the pairs' runs and their fold -, then the table takes the sub-batch in a bracket of its own.  Nothing leaves the device.
+static int emit_to_table(SubSearch &s) {
   prb_ctx *ctx = s.ctx;
   SearchWs &w = s.w;
-  prb_topset *ts = static_cast<prb_topset *>(s.table);
+  const TableFeed feed = s.table->feed();
+  SubBatch b{s.page, s.b.q0, s.b.q1, s.qb->nq, s.pg.nseq, s.F, s.nfin};
   int rc;
-  int64_t npairs = 0;
-  if ((rc = pair_runs(s, &npairs))) return rc;
-  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
-  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
-  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
-  PRB_HIP(launch_top_merge(w.packed.p, npairs, s.b.q0, s.b.q1, s.page, ts->n, ts->table.p, ts->fill(), ctx->stream));
-  s.hs->hits_total += s.nfin;
-  return ctx->time_end(ctx->top_timer, 1);
-}
-
-// prb_search_page_profile: the hits merged into the per-position table on the device; nothing leaves it
-static int emit_profile(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  int rc;
-  int64_t npairs = 0;
-  if ((rc = pair_runs(s, &npairs))) return rc;
-  if ((rc = ctx->time_end(ctx->summary_timer, 2))) return rc;
-  if ((rc = merge_profile(ctx, static_cast<prb_profset *>(s.table), s.page, s.b.q0, s.b.q1, s.F, s.nfin, w.bpEnds.as<int32_t>(),
-                          w.pairStart.as<uint32_t>(), npairs)))
-    return rc;
-  s.hs->hits_total += s.nfin;
-  return PRB_OK;
-}
-
-// prb_search_page_tophits: the hits' records (as emit_records packs them, their base-pair ranges counted from the end of
-// the table's pool on) merged into the top-N hit table on the device, then the kept hits' base-pair lists gathered in
-// table order - survivors from the table's pool, newcomers from this sub-batch's pairs (regather_tophits).  Nothing
-// leaves the device.  Closes the "traceback" bracket.
-static int emit_tophits(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  prb_tophits *th = static_cast<prb_tophits *>(s.table);
-  const int64_t nfin = s.nfin;
-  int rc;
-  if ((rc = w.packed.ensure((size_t)nfin * sizeof(prb_hit)))) return rc;
-  const int32_t *fresh;
-  if ((rc = pack_records(s, th->pool_pairs, &fresh))) return rc;
-  if ((rc = ctx->time_end("traceback", 2))) return rc;
-  if ((rc = ctx->time_begin())) return rc;
-  PRB_HIP(launch_tophits_merge(w.packed.p, nfin, s.b.q0, s.b.q1, s.page, th->n, th->table.p, th->fill(), ctx->stream));
-  if ((rc = regather_tophits("prb_search_page_tophits", ctx, th, fresh))) return rc;
-  s.hs->hits_total += nfin;
-  return ctx->time_end(ctx->tophits_timer, 4);
-}
-
-// prb_search_page_targets: the pairs' records merged into the per-target table on the device; nothing leaves it
-static int emit_targets(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  int rc;
-  int64_t npairs = 0;
-  if ((rc = pair_runs(s, &npairs))) return rc;
-  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
-  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
-  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
-  if ((rc = merge_targets(ctx, w, static_cast<prb_targetset *>(s.table), s.page, s.pg.nseq, s.qb->nq, w.packed.p, npairs))) return rc;
-  s.hs->hits_total += s.nfin;
-  return PRB_OK;
-}
-
-// prb_search_page_coverage: the hits merged into the per-target coverage table on the device; nothing leaves it.  Closes
-// the "traceback" bracket.
-static int emit_coverage(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  const int64_t nfin = s.nfin;
-  int rc;
-  if ((rc = w.bpEnds.ensure((size_t)nfin * 16))) return rc;
-  PRB_HIP(launch_bp_ends(w.bpOff.as<int64_t>(), nfin, w.bpOut.as<int32_t>(), w.bpEnds.as<int32_t>(), ctx->stream));
-  if ((rc = ctx->time_end("traceback", 2))) return rc;
-  if ((rc = merge_coverage(ctx, static_cast<prb_covset *>(s.table), s.page, CovHits{nfin, s.F.query, s.F.db_id, s.F.e_tot, w.bpEnds.as<int32_t>()}, s.qb->nq))) return rc;
-  s.hs->hits_total += nfin;
-  return PRB_OK;
-}
-
-// prb_search_page_observed / prb_search_page_decoys: the pairs' records into the null table on the device - the real
-// batch's scattered into their slots, a decoy batch's folded into the counters; nothing leaves it
-static int emit_null(SubSearch &s, bool decoys) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  prb_nullset *ns = static_cast<prb_nullset *>(s.table);
-  int rc;
-  int64_t npairs = 0;
-  if ((rc = pair_runs(s, &npairs))) return rc;
-  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
-  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
-  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
-  if ((rc = decoys ? merge_null_decoys(ctx, ns, s.page, w.packed.p, npairs) : merge_null_observed(ctx, ns, s.page, w.packed.p, npairs))) return rc;
-  s.hs->hits_total += s.nfin;
-  return PRB_OK;
-}
-
-// prb_search_page_groups: the pairs' records folded into the group table on the device; nothing leaves it
-static int emit_groups(SubSearch &s) {
-  prb_ctx *ctx = s.ctx;
-  SearchWs &w = s.w;
-  int rc;
-  int64_t npairs = 0;
-  if ((rc = pair_runs(s, &npairs))) return rc;
-  if ((rc = w.packed.ensure((size_t)npairs * sizeof(prb_pair_summary)))) return rc;
-  PRB_HIP(launch_pair_fold(s.F, s.nfin, w.pairStart.as<uint32_t>(), npairs, w.bpEnds.as<int32_t>(), w.packed.p, ctx->stream));
-  if ((rc = ctx->time_end(ctx->summary_timer, 3))) return rc;
-  if ((rc = merge_group_pairs(ctx, static_cast<prb_groupset *>(s.table), s.page, w.packed.p, npairs))) return rc;
-  s.hs->hits_total += s.nfin;
-  return PRB_OK;
-}
-
-static int emit_final(SubSearch &s) {
-  switch (s.mode) {
-  case SearchMode::kRecords: return emit_records(s);
-  case SearchMode::kSummary: return emit_summary(s);
-  case SearchMode::kTop: return emit_top(s);
-  case SearchMode::kProfile: return emit_profile(s);
-  case SearchMode::kTopHits: return emit_tophits(s);
-  case SearchMode::kTargets: return emit_targets(s);
-  case SearchMode::kCoverage: return emit_coverage(s);
-  case SearchMode::kNullObserved: return emit_null(s, false);
-  case SearchMode::kNullDecoys: return emit_null(s, true);
-  case SearchMode::kGroups: return emit_groups(s);
+  if (feed == TableFeed::kHitRecords) {
+    if ((rc = w.packed.ensure((size_t)s.nfin * sizeof(prb_hit)))) return rc;
+    if ((rc = pack_records(s, s.table->bp_base(), &b.fresh_bp))) return rc;
+    if ((rc = ctx->time_end("traceback", 2))) return rc;
+    b.records = w.packed.p;
+  } else if (feed == TableFeed::kHits) {
+    if ((rc = bp_ends(s))) return rc;
+    if ((rc = ctx->time_end("traceback", 2))) return rc;
+    b.ends = w.bpEnds.as<int32_t>();
+  } else {
+    const bool fold = feed == TableFeed::kPairRecords;
+    if ((rc = pair_runs(s, &b.npairs))) return rc;
+    if (fold && (rc = fold_pairs(s, b.npairs))) return rc;
+    if ((rc = ctx->time_end(ModeTimer::kSummary, fold ? 3 : 2))) return rc;
+    b.ends = w.bpEnds.as<int32_t>();
+    b.pair_start = w.pairStart.as<uint32_t>();
+    if (fold) b.records = w.packed.p;
   }
-  return PRB_ERR_STATE;
+  if ((rc = s.table->take(b))) return rc;
+  s.hs->hits_total += s.nfin;
+  return PRB_OK;
 }
 
 // ------------------------------------------------------------------------- one sub-batch
@@ -1128,7 +1040,7 @@ static int search_range(const PageSearch &p, const CandBatch &b, const std::func
   if (s.opts.distinct_sites && (rc = distinct_sites(s))) return rc;
   if (s.opts.chain_sites && (rc = chain_sites(s))) return rc;
   if ((rc = traceback(s))) return rc;
-  return emit_final(s);
+  return s.mode == SearchMode::kRecords ? emit_records(s) : s.mode == SearchMode::kSummary ? emit_summary(s) : emit_to_table(s);
 }
 
 // ------------------------------------------------------------------------- one page
@@ -1449,7 +1361,7 @@ static int select_callers_sites(const char *fn_name, prb_ctx *ctx, const prb_hit
   }
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = select_sites(ctx, w, carve_hits(w.hitsTmp, n), n, rule, knobs))) return rc;
-  if ((rc = ctx->time_end(rule_timer(ctx, rule), 3))) return rc;
+  if ((rc = ctx->time_end(rule_timer(rule), 3))) return rc;
   PRB_HIP(hipMemcpyAsync(keep, w.keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream));
   return PRB_OK;

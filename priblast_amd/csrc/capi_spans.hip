@@ -125,7 +125,7 @@ static int clear_profile_table(prb_profset &ps) {
 // prb_search_page_profile, per sub-batch: the hits by (pair, first position of the span), the running maximum of the
 // spans' ends per pair, the difference arrays, the sub-batch's best hit per position and its merge into the table's, in
 // a bracket of the "profile" timer
-int prb::merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, int32_t q1, const HitSoA &F, int64_t nfin, const int32_t *ends,
+static int merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, int32_t q1, const HitSoA &F, int64_t nfin, const int32_t *ends,
                        const uint32_t *pair_start, int64_t npairs) {
   int rc;
   if ((rc = ctx->time_begin())) return rc;
@@ -142,8 +142,9 @@ int prb::merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, 
   PRB_HIP(launch_prof_add(F, nfin, ps->keyB.as<uint64_t>(), ps->valB.as<uint32_t>(), ps->scan.as<uint64_t>(), ends, t, ctx->stream));
   PRB_HIP(launch_prof_min(F, nfin, ps->valB.as<uint32_t>(), ends, t, ctx->stream));
   PRB_HIP(launch_prof_merge(F, ends, t, ps->off[(size_t)q0], ps->off[(size_t)q1], page, ctx->stream));
-  return ctx->time_end(ctx->profile_timer, 8);
+  return ctx->time_end(ModeTimer::kProfile, 8);
 }
+int prb_profset::take(const SubBatch &b) { return merge_profile(ctx, this, b.page, b.q0, b.q1, b.F, b.nfin, b.ends, b.pair_start, b.npairs); }
 
 // ---- the per-target coverage (prb_covset_*) ----
 // every slot of the table back to "no hit", on its own device and stream; its stream is idle on return
@@ -164,7 +165,7 @@ static int clear_coverage_table(prb_covset &cs) {
 // sequence's positions are contiguous in the page's text, so that is by (query, target, first position) -, the running
 // maximum of the spans' ends per query, the difference arrays, and the four passes of the best hits.  In a bracket of
 // the "coverage" timer.
-int prb::merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq) {
+static int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq) {
   int rc;
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = cs->place.ensure((size_t)h.n * 4))) return rc;
@@ -178,7 +179,10 @@ int prb::merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHit
     return rc;
   PRB_HIP(launch_cov_add(h, cs->keyB.as<uint64_t>(), cs->valB.as<uint32_t>(), cs->scan.as<uint64_t>(), t, pg, ctx->stream));
   PRB_HIP(launch_cov_min(h, cs->valB.as<uint32_t>(), place, cs->ids.as<int32_t>(), t, pg, ctx->stream));
-  return ctx->time_end(ctx->coverage_timer, 9);
+  return ctx->time_end(ModeTimer::kCoverage, 9);
+}
+int prb_covset::take(const SubBatch &b) {
+  return merge_coverage(ctx, this, b.page, CovHits{b.nfin, b.F.query, b.F.db_id, b.F.e_tot, b.ends}, b.nq);
 }
 
 extern "C" {
@@ -205,7 +209,7 @@ int prb_profset_create(prb_ctx *ctx, const prb_qbatch *qb, prb_profset **out) {
 int prb_profset_merge(prb_ctx *ctx, prb_profset *dst, prb_profset *src) {
   if (int rc = merge_tables_guard("prb_profset_merge", "profile", ctx, dst, src)) return rc;
   return join_tables(
-      "prb_profset_merge", &prb_ctx::profile_timer, 1, ctx, dst, src, src->bytes(), nothing_more,
+      "prb_profset_merge", ModeTimer::kProfile, 1, ctx, dst, src, src->bytes(), nothing_more,
       [&](void *block) -> int {
         PRB_HIP(launch_prof_join(dst->view(), dst->view_of(static_cast<char *>(block)), dst->slots(), ctx->stream));
         return PRB_OK;
@@ -214,7 +218,7 @@ int prb_profset_merge(prb_ctx *ctx, prb_profset *dst, prb_profset *src) {
 }
 
 int prb_search_page_profile(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_profset *ps) {
-  return merge_page("prb_search_page_profile", "profile", "prb_profset_finish", SearchMode::kProfile, ps, ctx, qb, db, page, opts);
+  return merge_page("prb_search_page_profile", "profile", "prb_profset_finish", ps, ctx, qb, db, page, opts);
 }
 
 // the covered positions selected on the device (Hits > 0 after the scans), their rows built there and copied once
@@ -237,7 +241,7 @@ int prb_profset_finish(prb_ctx *ctx, prb_profset *ps) {
            return launch_prof_rows(t, f.selected, nsel, hits, targets, rows, ctx->stream);
          })))
       return rc;
-    if ((rc = ctx->time_end(ctx->profile_timer, ps->rows.empty() ? 3 : 4))) return rc;
+    if ((rc = ctx->time_end(ModeTimer::kProfile, ps->rows.empty() ? 3 : 4))) return rc;
   }
   ps->finished = true;
   ps->release(); // (only the host rows are needed from here on)
@@ -286,7 +290,7 @@ int prb_covset_create(prb_ctx *ctx, prb_db *db, prb_covset **out) {
 
 int prb_search_page_coverage(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
                              prb_covset *cs) {
-  return merge_run_page("prb_search_page_coverage", "coverage", "prb_covset_finish", SearchMode::kCoverage, cs, ctx, qb, db, page, opts, query_ids);
+  return merge_run_page("prb_search_page_coverage", "coverage", "prb_covset_finish", cs, ctx, qb, db, page, opts, query_ids);
 }
 
 // the caller's list checked on the host - a refused call leaves the table as it was -, then as columns to the device and
@@ -351,7 +355,7 @@ int prb_covset_merge(prb_ctx *ctx, prb_covset *dst, prb_covset *src) {
       }))
     return rc;
   return join_tables(
-      "prb_covset_merge", &prb_ctx::coverage_timer, 1, ctx, dst, src, src->bytes(), nothing_more,
+      "prb_covset_merge", ModeTimer::kCoverage, 1, ctx, dst, src, src->bytes(), nothing_more,
       [&](void *block) -> int {
         PRB_HIP(launch_cov_join(dst->view(), dst->view_of(static_cast<char *>(block)), dst->slots(), ctx->stream));
         return PRB_OK;
@@ -390,7 +394,7 @@ int prb_covset_finish(prb_ctx *ctx, prb_covset *cs, int32_t min_queries) {
       for (j = i + 1; j < nreg && cs->regions[j].page == cs->regions[i].page && cs->regions[j].db_id == cs->regions[i].db_id;) j++;
       std::reverse(cs->regions.begin() + (ptrdiff_t)i, cs->regions.begin() + (ptrdiff_t)j);
     }
-    if ((rc = ctx->time_end(ctx->coverage_timer, nreg ? 4 : 3))) return rc;
+    if ((rc = ctx->time_end(ModeTimer::kCoverage, nreg ? 4 : 3))) return rc;
   }
   cs->finished = true;
   cs->release(); // (only the host records are needed from here on)

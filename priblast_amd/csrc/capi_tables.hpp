@@ -1,7 +1,8 @@
-// The protocol of the five result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip): what a
-// prb_*_create starts with, what is checked before a page or another table is merged, the merge of one table into
-// another across contexts and devices, and what every prb_*_finish starts with.  `fn_name` is the entry point and `what`
-// the table's noun in the messages.  Every check comes before a table is touched: a refused call leaves it as it was.
+// The protocol of the seven result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
+// search of a page into a table, the merge of one table into another across contexts and devices, and what every
+// prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check comes
+// before a table is touched: a refused call leaves it as it was.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -34,7 +35,7 @@ inline int refuse(const std::string &fn, const std::string &why, int code = PRB_
 }
 
 // ---- prb_*_create
-// What the five create functions start with (args_ok: the caller's test of its other arguments): *out = nullptr, the
+// What the create functions start with (args_ok: the caller's test of its other arguments): *out = nullptr, the
 // caller's own refusal if it has one (bad_n), and an empty table in `t`
 template <class T> int new_table(const char *fn_name, bool args_ok, T **out, std::unique_ptr<T> &t, const std::string &why = "") {
   if (!args_ok || !out) return refuse(fn_name, "bad argument");
@@ -72,10 +73,27 @@ inline std::string selection_clash(const std::string &tables, const char *holds,
   return "";
 }
 
-// ---- prb_search_page_top / _profile / _tophits: a page searched and merged into a batch table
-// Page `page` searched in `mode` and merged into the table `t`, finished by `finish_fn`
-inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb,
-                      prb_db *db, int32_t page, const prb_ris_opts *opts) {
+// ---- every prb_search_page_* of a table, behind its guards
+// Page `page` searched with every sub-batch's final hits taken by `t` (TableState::take), the three stage counts of the
+// search added to `counts` (t->counts, or the table's other set), and - unless the batch is not the table's own
+// (record_selection = false: the null table's decoys) - the options' selection recorded as the table's
+inline int search_into_table(TableState *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int64_t counts[3],
+                             bool record_selection = true) {
+  prb_hitset *hs = nullptr;
+  if (int rc = search_page(ctx, qb, db, page, opts, 3, SearchMode::kTable, &hs, t)) return rc;
+  for (int i = 0; i < 3; i++) counts[i] += hs->counts[i];
+  if (record_selection) {
+    t->distinct = opts->distinct_sites;
+    t->chain = opts->chain_sites;
+  }
+  delete hs;
+  return PRB_OK;
+}
+
+// ---- prb_search_page_top / _profile / _tophits / _groups: a page searched and merged into a batch table
+// Page `page` searched and merged into the table `t`, finished by `finish_fn`
+inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db,
+                      int32_t page, const prb_ris_opts *opts) {
   const std::string fn = fn_name, table = std::string(what) + " table";
   if (!t) return refuse(fn, "bad argument");
   if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
@@ -93,17 +111,9 @@ inline int merge_page(const char *fn_name, const char *what, const char *finish_
   }
   if (t->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this " + table);
   t->merged[(size_t)page] = 1;
-  prb_hitset *hs = nullptr;
-  const int rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t);
-  if (rc != PRB_OK) {
-    t->broken = true;
-    return rc;
-  }
-  for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
-  t->distinct = opts->distinct_sites;
-  t->chain = opts->chain_sites;
-  delete hs;
-  return PRB_OK;
+  const int rc = search_into_table(t, ctx, qb, db, page, opts, t->counts);
+  if (rc != PRB_OK) t->broken = true;
+  return rc;
 }
 
 // ---- prb_search_page_targets / _coverage / prb_covset_add_hits: a batch merged into a run table
@@ -138,10 +148,10 @@ inline int upload_ids(prb_ctx *ctx, RunTable *t, const int32_t *query_ids, int32
   PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
   return PRB_OK;
 }
-// Page `page` searched in `mode` and merged into the run table `t` under the caller's identifiers.  A failure from the
-// upload on leaves the table unusable.
-inline int merge_run_page(const char *fn_name, const char *what, const char *finish_fn, SearchMode mode, RunTable *t, prb_ctx *ctx,
-                          prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids) {
+// Page `page` searched and merged into the run table `t` under the caller's identifiers.  A failure from the upload on
+// leaves the table unusable.
+inline int merge_run_page(const char *fn_name, const char *what, const char *finish_fn, RunTable *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db,
+                          int32_t page, const prb_ris_opts *opts, const int32_t *query_ids) {
   if (!t || !query_ids) return refuse(fn_name, "bad argument");
   if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
   if (int rc = run_table_guard(fn_name, what, finish_fn, t, ctx, db, page, opts->distinct_sites, opts->chain_sites, query_ids, qb->nq)) return rc;
@@ -149,18 +159,13 @@ inline int merge_run_page(const char *fn_name, const char *what, const char *fin
   t->broken = true; // (until the merge is whole)
   int rc;
   if ((rc = upload_ids(ctx, t, query_ids, qb->nq))) return rc;
-  prb_hitset *hs = nullptr;
-  if ((rc = search_page(ctx, qb, db, page, opts, 3, mode, &hs, t))) return rc;
-  for (int i = 0; i < 3; i++) t->counts[i] += hs->counts[i];
-  t->distinct = opts->distinct_sites;
-  t->chain = opts->chain_sites;
+  if ((rc = search_into_table(t, ctx, qb, db, page, opts, t->counts))) return rc;
   t->broken = false;
-  delete hs;
   return PRB_OK;
 }
 
 // ---- prb_*_merge: two unfinished tables over disjoint page or (page, identifier) sets into one
-// What all five check first: `dst` belongs to ctx, both are unfinished and whole, own() has no refusal of the table's
+// What they all check first: `dst` belongs to ctx, both are unfinished and whole, own() has no refusal of the table's
 // own ("" = none; asked once both are known to be whole and unfinished), and both were searched with one distinct_sites and one chain_sites
 template <class Own>
 int merge_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *dst, const TableState *src, Own own) {
@@ -282,7 +287,7 @@ inline int on_device_of(prb_ctx *ctx, const prb_ctx *owner, void *p, size_t byte
 // it, join(block) enqueued in the bracket of `timer` with its `launches`, dst's book-keeping, then src emptied on its
 // own device by `clear`.  A failure from the first launch on leaves dst unusable.
 template <class T, class More, class Join, class Clear>
-int join_tables(const char *fn_name, StageTimer prb_ctx::*timer, int64_t launches, prb_ctx *ctx, T *dst, T *src, size_t bytes, More more,
+int join_tables(const char *fn_name, ModeTimer timer, int64_t launches, prb_ctx *ctx, T *dst, T *src, size_t bytes, More more,
                 Join join, Clear clear) {
   DeviceScope restore;
   ScratchBuf copy;
@@ -294,7 +299,7 @@ int join_tables(const char *fn_name, StageTimer prb_ctx::*timer, int64_t launche
   dst->broken = true; // (until the merge is whole)
   if ((rc = ctx->time_begin())) return rc;
   if ((rc = join(block))) return rc;
-  if ((rc = ctx->time_end(ctx->*timer, launches))) return rc; // (synchronises: src is read no more)
+  if ((rc = ctx->time_end(timer, launches))) return rc; // (synchronises: src is read no more)
   dst->broken = false;
   try {
     move_merged(dst, src);

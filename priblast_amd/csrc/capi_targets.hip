@@ -22,7 +22,7 @@ static int clear_target_table(prb_targetset &t) {
 // prb_search_page_targets, per sub-batch: the pairs' records - their `query` turned into the caller's identifier -
 // grouped by target (a stable sort by db_id: a target's records stay in query order; always, whatever the sub-batch
 // holds) and every target's run merged into the per-target table by a wavefront, in a bracket of the "targets" timer
-int prb::merge_targets(prb_ctx *ctx, SearchWs &w, prb_targetset *ts, int32_t page, int32_t nseq, int32_t nq, void *packed, int64_t npairs) {
+static int merge_targets(prb_ctx *ctx, SearchWs &w, prb_targetset *ts, int32_t page, int32_t nseq, int32_t nq, void *packed, int64_t npairs) {
   int rc;
   if ((rc = ctx->time_begin())) return rc;
   const size_t NP = (size_t)npairs;
@@ -44,8 +44,9 @@ int prb::merge_targets(prb_ctx *ctx, SearchWs &w, prb_targetset *ts, int32_t pag
   PRB_HIP(launch_target_merge(packed, ts->rkey.as<TargetKey>(), ts->keyS.as<uint32_t>(), ts->start.as<uint32_t>(), nruns, npairs, page,
                               ts->tbase[(size_t)page], nseq, ts->n, ts->keys_of(ts->table.p), ts->slots_of(ts->table.p), ts->fill_of(ts->table.p),
                               ctx->stream));
-  return ctx->time_end(ctx->targets_timer, 5);
+  return ctx->time_end(ModeTimer::kTargets, 5);
 }
+int prb_targetset::take(const SubBatch &b) { return merge_targets(ctx, ws_of(ctx), this, b.page, b.nseq, b.nq, b.records, b.npairs); }
 
 extern "C" {
 
@@ -70,7 +71,7 @@ int prb_targetset_create(prb_ctx *ctx, prb_db *db, int32_t n, prb_targetset **ou
 
 int prb_search_page_targets(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *query_ids,
                             prb_targetset *ts) {
-  return merge_run_page("prb_search_page_targets", "per-target", "prb_targetset_finish", SearchMode::kTargets, ts, ctx, qb, db, page, opts,
+  return merge_run_page("prb_search_page_targets", "per-target", "prb_targetset_finish", ts, ctx, qb, db, page, opts,
                         query_ids);
 }
 
@@ -81,7 +82,7 @@ int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
       }))
     return rc;
   return join_tables(
-      "prb_targetset_merge", &prb_ctx::targets_timer, 1, ctx, dst, src, src->bytes(), nothing_more,
+      "prb_targetset_merge", ModeTimer::kTargets, 1, ctx, dst, src, src->bytes(), nothing_more,
       [&](void *block) -> int {
         PRB_HIP(launch_target_join(dst->keys_of(dst->table.p), dst->slots_of(dst->table.p), dst->fill_of(dst->table.p), dst->keys_of(block),
                                    dst->slots_of(block), dst->fill_of(block), dst->targets(), dst->n, ctx->stream));

@@ -67,11 +67,11 @@ static int download_slots(const char *fn_name, prb_ctx *ctx, const TopTable<Slot
   return PRB_OK;
 }
 
-// What follows a merge into the top-N hit table, of a sub-batch (emit_tophits) or of another table (prb_tophits_merge):
+// What follows a merge into the top-N hit table, of a sub-batch (prb_tophits::take) or of another table (prb_tophits_merge):
 // the pair counts of the slots in use, their exclusive scan, and the kept hits' base-pair lists gathered in table order
 // into a second pool of exactly the scanned size, which becomes the table's.  A newcomer's bp_offset is `split` (the
 // table's pool_pairs) + the place of its list in `fresh`.  `fn` names the entry point in the messages.  Synchronises.
-int prb::regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh) {
+static int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh) {
   int rc;
   const int64_t nslots = (int64_t)th->nq * th->n;
   const size_t NS = (size_t)nslots + 1;
@@ -98,6 +98,27 @@ int prb::regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const i
   return PRB_OK;
 }
 
+// prb_search_page_top, per sub-batch: the npairs pair records at `packed` (of the queries [q0, q1) against `page`) merged
+// into the top-N table, in a bracket of the "top" timer
+static int merge_top(prb_ctx *ctx, prb_topset *ts, int32_t page, int32_t q0, int32_t q1, const void *packed, int64_t npairs) {
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_top_merge(packed, npairs, q0, q1, page, ts->n, ts->table.p, ts->fill(), ctx->stream));
+  return ctx->time_end(ModeTimer::kTop, 1);
+}
+int prb_topset::take(const SubBatch &b) { return merge_top(ctx, this, b.page, b.q0, b.q1, b.records, b.npairs); }
+
+// prb_search_page_tophits, per sub-batch: the hits' records merged into the top-N hit table, then the kept hits'
+// base-pair lists gathered in table order - survivors from the table's pool, newcomers from this sub-batch's pairs
+// (regather_tophits) -, in a bracket of the "tophits" timer
+int prb_tophits::take(const SubBatch &b) {
+  int rc;
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(launch_tophits_merge(b.records, b.nfin, b.q0, b.q1, b.page, n, table.p, fill(), ctx->stream));
+  if ((rc = regather_tophits("prb_search_page_tophits", ctx, this, b.fresh_bp))) return rc;
+  return ctx->time_end(ModeTimer::kTopHits, 4);
+}
+
 extern "C" {
 
 int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset **out) {
@@ -105,7 +126,7 @@ int prb_topset_create(prb_ctx *ctx, const prb_qbatch *qb, int32_t n, prb_topset 
 }
 
 int prb_search_page_top(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_topset *ts) {
-  return merge_page("prb_search_page_top", "top-N", "prb_topset_finish", SearchMode::kTop, ts, ctx, qb, db, page, opts);
+  return merge_page("prb_search_page_top", "top-N", "prb_topset_finish", ts, ctx, qb, db, page, opts);
 }
 
 int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
@@ -125,7 +146,7 @@ int prb_topset_finish(prb_ctx *ctx, prb_topset *ts) {
 int prb_topset_merge(prb_ctx *ctx, prb_topset *dst, prb_topset *src) {
   if (int rc = top_tables_guard("prb_topset_merge", "top-N", ctx, dst, src)) return rc;
   return join_tables(
-      "prb_topset_merge", &prb_ctx::top_timer, 1, ctx, dst, src, src->bytes(), nothing_more,
+      "prb_topset_merge", ModeTimer::kTop, 1, ctx, dst, src, src->bytes(), nothing_more,
       [&](void *slots) -> int {
         PRB_HIP(launch_top_join(dst->table.p, dst->fill(), slots, reinterpret_cast<const int32_t *>(static_cast<char *>(slots) + src->slots_bytes()),
                                 dst->nq, dst->n, ctx->stream));
@@ -152,7 +173,7 @@ int prb_search_page_tophits(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pa
   if (th && opts && th->style >= 0 && opts->output_style != th->style)
     return refuse("prb_search_page_tophits", "the top-N hit table holds pages searched with output_style " + std::to_string(th->style) +
                                                  " (this call: " + std::to_string(opts->output_style) + ")");
-  const int rc = merge_page("prb_search_page_tophits", "top-N hit", "prb_tophits_finish", SearchMode::kTopHits, th, ctx, qb, db, page, opts);
+  const int rc = merge_page("prb_search_page_tophits", "top-N hit", "prb_tophits_finish", th, ctx, qb, db, page, opts);
   if (rc == PRB_OK) th->style = opts->output_style;
   return rc;
 }
@@ -197,7 +218,7 @@ int prb_tophits_merge(prb_ctx *ctx, prb_tophits *dst, prb_tophits *src) {
   ScratchBuf pool_copy;
   void *pool = nullptr;
   const int rc = join_tables(
-      "prb_tophits_merge", &prb_ctx::tophits_timer, 4, ctx, dst, src, src->bytes(),
+      "prb_tophits_merge", ModeTimer::kTopHits, 4, ctx, dst, src, src->bytes(),
       [&]() -> int { return on_device_of(ctx, src->ctx, src->pool.p, (size_t)src->pool_pairs * 8, pool_copy, &pool); },
       [&](void *slots) -> int {
         PRB_HIP(launch_tophits_join(dst->table.p, dst->fill(), slots, reinterpret_cast<const int32_t *>(static_cast<char *>(slots) + src->slots_bytes()),

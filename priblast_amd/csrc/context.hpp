@@ -35,6 +35,12 @@ struct StageTimer {
   int64_t launches = 0;
 };
 
+// The stages outside the full-output search (prb_ctx::mode_timers): one row each, the value and - in the same order -
+// the name that prb_ctx_stage_ms answers to
+enum class ModeTimer { kSummary, kTop, kProfile, kTopHits, kTargets, kDistinct, kChain, kAllow, kCoverage, kNull, kGroup, kCount };
+inline constexpr const char *kModeTimerName[(int)ModeTimer::kCount] = {"summary", "top",   "profile",  "tophits", "targets", "distinct",
+                                                                       "chain",   "allow", "coverage", "null",    "group"};
+
 } // namespace prb
 
 struct prb_ctx {
@@ -58,22 +64,15 @@ struct prb_ctx {
   prb::DevBuf ra_band, ra_vec, ra_codes, ra_desc, ra_acc, ra_cond;
   size_t ra_budget_bytes = 0;
   std::map<std::string, prb::StageTimer> timers;
-  // the per-pair reduction of prb_search_page_summary (stage "summary"): kept apart from the stages of the full-output
-  // search that `timers` holds and bench.py reports
-  prb::StageTimer summary_timer;
-  prb::StageTimer top_timer; // the merge of prb_search_page_top (stage "top"), kept apart for the same reason
-  prb::StageTimer profile_timer; // prb_search_page_profile and prb_profset_finish (stage "profile"), likewise
-  prb::StageTimer tophits_timer; // the merge of prb_search_page_tophits (stage "tophits"), likewise
-  prb::StageTimer targets_timer; // the merges of prb_search_page_targets and prb_targetset_merge (stage "targets"), likewise
-  prb::StageTimer distinct_timer; // the selection of opts->distinct_sites (stage "distinct"), likewise
-  prb::StageTimer chain_timer; // the selection of opts->chain_sites (stage "chain"), likewise
-  prb::StageTimer allow_timer; // the test and compaction of the pairs under opts->allowed_pairs (stage "allow"), likewise
-  prb::StageTimer coverage_timer; // the merges, the join and the finish of the coverage table (stage "coverage"), likewise
+  // What is not a stage of the full-output search - the per-pair reduction ("summary"), the merges, joins and finishes of
+  // the result tables (a stage per table), the selections of opts->distinct_sites / chain_sites and the pairs' test under
+  // opts->allowed_pairs - is kept apart from `timers`: every name that is written as time_end("...", n), HostTimer x(ctx,
+  // "...") or timers["..."] has to be a stage that bench.py reports (tests/test_host.py), and these are not.  So they are passed as
+  // prb::ModeTimer values and never spelled in one of those three forms; prb::kModeTimerName has their names.
+  prb::StageTimer mode_timers[(int)prb::ModeTimer::kCount];
 
   int time_begin();
   int time_end(const char *stage, int64_t launches);
+  int time_end(prb::ModeTimer t, int64_t launches) { return time_end(mode_timers[(int)t], launches); }
   int time_end(prb::StageTimer &t, int64_t launches);
-
-  prb::StageTimer null_timer; // the scatter, the fold and the finish of the null table (stage "null"), kept apart like the others
-  prb::StageTimer group_timer; // the fold, the merge and the finish of the group table (stage "group"), likewise
 };

@@ -425,10 +425,38 @@ namespace prb {
 // and, at its first use, uploaded; *view = the mask as the kernels take it for `page`.  Not called for NULL.
 int use_pairmask(const char *fn, prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, const prb_pairmask *pm, AllowDev *view);
 
-// What the five result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset): whose
-// they are, whether they can still be merged into, and the block on the device that the merges work on.  What every
-// prb_*_merge and prb_*_finish checks (capi_tables.hpp) and what search_page hands to the emit_* of its mode.
+// What a result table takes from every sub-batch of a page search - what the search driver (emit_to_table,
+// capi_search.hip) prepares before it calls TableState::take; each of the first three has all that the one above it has:
+enum class TableFeed {
+  kHits,        // the final hits F with their end pairs, as the simplified output has them (SubBatch::ends)
+  kPairRuns,    // ... and the runs of equal (query, db_id) in F: pair_start, npairs
+  kPairRecords, // ... and the runs folded into records: prb_pair_summary[npairs]
+  kHitRecords,  // F and its records: prb_hit[nfin] as prb_search_page packs them, their base-pair ranges counted from pair
+                // TableState::bp_base() on; fresh_bp = the ints that the ranges index (none of the three above)
+};
+// One sub-batch as a table takes it: the queries [q0, q1) of a batch of nq against `page` (of nseq sequences).  What
+// the table's feed does not include is null; everything is on the device, and nothing of it outlives the call.
+struct SubBatch {
+  int32_t page, q0, q1, nq, nseq;
+  HitSoA F;
+  int64_t nfin;
+  const int32_t *ends = nullptr;
+  const uint32_t *pair_start = nullptr;
+  int64_t npairs = 0;
+  void *records = nullptr;
+  const int32_t *fresh_bp = nullptr;
+};
+
+// What the seven result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset): whose they are, whether they can still be merged into, and the block on the device that
+// the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
+// its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
+// own file; nothing leaves the device.
 struct TableState {
+  virtual ~TableState() = default;
+  virtual TableFeed feed() const = 0;
+  virtual int64_t bp_base() const { return 0; } // (kHitRecords)
+  virtual int take(const SubBatch &b) = 0;
   prb_ctx *ctx = nullptr;
   const prb_db *db = nullptr;  // batch tables: of the first merged page; run tables: the one they were made for
   bool broken = false;         // a merge failed part way
@@ -489,6 +517,8 @@ template <class Slot> struct TopTable : MergeTable {
 // prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
 struct prb_topset : prb::TopTable<prb_top_pair> {
   std::vector<prb_top_pair> pairs; // prb_topset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &b) override;
   ~prb_topset() { // (also on the error paths of prb_topset_create)
     if (table.p) (void)hipSetDevice(ctx->device);
     table.release();
@@ -496,7 +526,7 @@ struct prb_topset : prb::TopTable<prb_top_pair> {
 };
 
 // prb_tophits_create .. prb_tophits_free: the top-N hit table of one batch, merged into sub-batch by sub-batch
-// (emit_tophits, capi_search.hip), and the pool of the kept hits' base pairs
+// (capi_top.hip), and the pool of the kept hits' base pairs
 struct prb_tophits : prb::TopTable<prb_top_hit> {
   int32_t style = -1;              // opts->output_style of the merged pages (-1: none yet)
   prb::DevBuf pool, pool2;         // the kept hits' pairs in table order (h.bp_offset indexes `pool`); the gather's target
@@ -504,6 +534,9 @@ struct prb_tophits : prb::TopTable<prb_top_hit> {
   prb::DevBuf cnt, off, scanTmp;   // per slot (+ 1): pair counts, their exclusive scan
   std::vector<prb_top_hit> hits;   // prb_tophits_finish
   std::vector<int32_t> bp;
+  prb::TableFeed feed() const override { return prb::TableFeed::kHitRecords; }
+  int64_t bp_base() const override { return pool_pairs; } // (a newcomer's pairs lie behind the pool's until the gather)
+  int take(const prb::SubBatch &b) override;
   void release() {
     for (prb::DevBuf *b : {&table, &pool, &pool2, &cnt, &off, &scanTmp}) b->release();
   }
@@ -519,6 +552,8 @@ struct prb_tophits : prb::TopTable<prb_top_hit> {
 struct prb_profset : prb::MergeTable, prb::SpanBufs {
   std::vector<int64_t> off;    // [nq + 1] the queries' first slots (ProfTab::off)
   std::vector<prb_profile_pos> rows; // prb_profset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRuns; }
+  int take(const prb::SubBatch &b) override;
   int64_t slots() const { return off.empty() ? 0 : off.back(); }
   // the block (view()): off, then the 8-byte arrays hdiff, key, tie, skey, e_min, then the 4-byte arrays tdiff, stie,
   // db_id, bp (x4), bad
@@ -560,6 +595,8 @@ struct prb_targetset : prb::RunTable {
   int32_t n = 0;
   prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
   std::vector<prb_target_pair> pairs;         // prb_targetset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &b) override;
   size_t entries() const { return (size_t)targets() * (size_t)n; }
   size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)) + ((size_t)targets() + 1) * sizeof(int32_t); }
   // the three arrays of a block at b (the table's own, or a copy of another table's)
@@ -587,6 +624,8 @@ struct prb_covset : prb::RunTable, prb::SpanBufs {
   prb::DevBuf place;                              // per merge: every hit's place in its list
   prb::DevBuf h_query, h_db_id, h_e_tot, h_ends;  // prb_covset_add_hits: the caller's list as columns
   std::vector<prb_target_region> regions; // prb_covset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kHits; }
+  int take(const prb::SubBatch &b) override;
   int64_t slots() const { return seq_lo.empty() ? 0 : seq_lo.back(); }
   size_t head_bytes() const { return (seq_lo.size() + tbase.size()) * 8; }
   // the block (view()): seq_lo and tbase, then the 8-byte arrays hdiff, key, tie, skey, stie, e_min, then the 4-byte
@@ -640,9 +679,12 @@ struct prb_nullset : prb::TableState {
   prb::DevBuf obs, badflag, tbase_dev; // the selection's flags, the kernels' flag, tbase on the device
   prb::DevBuf own;                   // the decoy batch being merged: owner[ndq], then decoy[ndq]
   int32_t ndq = 0;                   // ... its number of decoys
+  bool decoy_phase = false;          // ... and that it is one: what take() merges (else the real batch), prb_search_page_decoys
   prb::DevBuf h_rec;                 // prb_nullset_observe / _add_pairs: the caller's records
   prb::DevBuf sel, out;              // prb_nullset_finish: the observed slots, their records
   std::vector<prb_null_pair> pairs;  // prb_nullset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &b) override;
   int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
   int64_t slots() const { return (int64_t)nq * targets(); }
   int64_t triples() const { return (int64_t)observed.size() * (int64_t)nq * (int64_t)ndecoys; }
@@ -673,6 +715,8 @@ struct prb_groupset : prb::MergeTable {
   prb::DevBuf h_rec;                     // prb_groupset_add_pairs: the caller's records
   prb::DevBuf occ, sel, top, keep, out;  // prb_groupset_finish: flags and lists of the selection, the records
   std::vector<prb_group_pair> pairs;     // prb_groupset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &b) override;
   int64_t slots() const { return (int64_t)nq * ngroups; }
   size_t bytes() const { return (size_t)slots() * sizeof(prb::GroupSlot); }
   prb::GroupTab view() const {
@@ -699,16 +743,9 @@ int host_threads(int work_items);
 enum class SearchMode {
   kRecords, // prb_search_page: hit records and base pairs to the host
   kSummary, // prb_search_page_summary: per-pair records to the host
-  kTop,     // prb_search_page_top: per-pair records merged into the top-N table on the device
-  kProfile, // prb_search_page_profile: the hits merged into the per-position table on the device
-  kTopHits, // prb_search_page_tophits: the hits and their base pairs merged into the top-N hit table on the device
-  kTargets, // prb_search_page_targets: per-pair records merged into the per-target table on the device
-  kCoverage, // prb_search_page_coverage: the hits merged into the per-target coverage table on the device
-  kNullObserved, // prb_search_page_observed: per-pair records of the real batch scattered into the null table on the device
-  kNullDecoys,   // prb_search_page_decoys: per-pair records of a batch of decoys folded into the null table's counters
-  kGroups,       // prb_search_page_groups: per-pair records folded into the group table on the device
+  kTable,   // every prb_search_page_* of a result table: into the table on the device, by the table's feed
 };
-// (every mode but the first: no hit records for the host; kTopHits keeps hit records, in its table)
+// (every mode but the first: no hit records for the host; a table that takes hit records keeps them itself)
 inline bool reduces_to_pairs(SearchMode m) { return m != SearchMode::kRecords; }
 
 // capi_pages.hip
@@ -716,8 +753,7 @@ int page_slot(prb_ctx *user, prb_db *db, int page, int keep, hipStream_t stream,
 std::unique_ptr<SeedPlan> start_seed_plan(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page, int32_t max_seed_length,
                                           double hybrid_threshold);
 // capi_search.hip: the argument checks and option limits of a search (`fn` names the entry point in the messages), and
-// the search of one page in `mode`; `table` = the prb_topset / prb_profset / prb_tophits / prb_targetset / prb_covset of
-// kTop / kProfile / kTopHits / kTargets / kCoverage (and the prb_nullset / prb_groupset of kNull* / kGroups)
+// the search of one page in `mode`; `table` = the table of kTable (search_into_table, capi_tables.hpp)
 int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t page,
                       const prb_ris_opts *opts, int32_t last_stage);
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
@@ -730,23 +766,6 @@ int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const pr
 // 48, the former without having left this unit), and the two onesweep iterations of (u64, u32).
 int sort_target_keys(hipStream_t s, DevBuf &tmp, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits);
 hipError_t sort_span_keys(void *tmp, size_t &bytes, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, size_t n, int bits, hipStream_t s);
-
-// What a sub-batch's emit_* (capi_search.hip) hands to its table, each in a bracket of the table's stage timer that it
-// opens and closes; nothing leaves the device.  `page`, [q0, q1) = the sub-batch's page and queries.
-// capi_top.hip: the scan and the gather behind a merge into the top-N hit table (of a sub-batch, or of another table)
-int regather_tophits(const char *fn, prb_ctx *ctx, prb_tophits *th, const int32_t *fresh);
-// capi_targets.hip: the npairs pair records at `packed` (of a batch of nq queries against a page of nseq sequences)
-int merge_targets(prb_ctx *ctx, SearchWs &w, prb_targetset *ts, int32_t page, int32_t nseq, int32_t nq, void *packed, int64_t npairs);
-// capi_spans.hip: the nfin final hits F with their end pairs `ends`, in npairs pair runs that start at pair_start
-int merge_profile(prb_ctx *ctx, prb_profset *ps, int32_t page, int32_t q0, int32_t q1, const HitSoA &F, int64_t nfin, const int32_t *ends,
-                  const uint32_t *pair_start, int64_t npairs);
-// capi_spans.hip: a list of final hits of `page` (of a sub-batch, or a caller's: prb_covset_add_hits); cs->ids holds the
-// identifiers of the list's nq queries
-int merge_coverage(prb_ctx *ctx, prb_covset *cs, int32_t page, const CovHits &h, int32_t nq);
-// capi_null.hip: the npairs pair records at `packed` (device) of `page` - of the real batch, or of the decoy batch whose
-// owners and decoy numbers ns->own holds - into the null table
-int merge_null_observed(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
-int merge_null_decoys(prb_ctx *ctx, prb_nullset *ns, int32_t page, const void *packed, int64_t npairs);
-// capi_groups.hip: the npairs pair records at `packed` (device) of `page` into the group table
-int merge_group_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const void *packed, int64_t npairs);
+// (What a table does with a sub-batch - its merge_* - is called from its own file alone: by its take() and by the entry
+// points that merge a caller's list.)
 } // namespace prb

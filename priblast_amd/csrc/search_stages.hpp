@@ -57,7 +57,7 @@ struct PageSearch {
   const SearchKnobs &k;
   const int page, last_stage;
   const SearchMode mode;
-  TableState *table; // the table of the mode, if it has one: each emit_* knows which
+  TableState *table; // SearchMode::kTable: where the final hits go
   prb_hitset *hs;
   int max_qlen;
   int32_t max_dblen;
