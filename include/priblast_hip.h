@@ -210,6 +210,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   table, launches = 1 per sub-batch with final hits; prb_nullset_finish: the selection and the gather, launches = 2);
  * "group" (prb_search_page_groups / prb_groupset_add_pairs: the fold into the group table, launches = 3 per sub-batch with
  *   final hits; prb_groupset_merge: 1; prb_groupset_finish: the flags, the selections and the gather, launches = 2 to 5);
+ * "gnull" (prb_gnullset_create: the kept records into the lookup, launches = 1; prb_search_page_gnull / prb_gnullset_add_pairs:
+ *   the fold into the scratch, launches = 1 per sub-batch with final hits; prb_gnullset_end: the close, 1; prb_gnullset_finish:
+ *   the gather, 1);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -790,6 +793,83 @@ void prb_groupset_free(prb_groupset *gs);
  * columns, numbered from id0 on) followed by ",<group name>,<members>,<targets in the group>,<hits>"; group_names[g] and
  * group_sizes[g] for every group of the table.  Arguments and results as prb_write_top_lines. */
 int prb_write_group_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_group_pair *recs,
+                          int64_t nrecs, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
+                          int64_t *nlines, int64_t *nbytes);
+
+/* ---- an empirical p-value per (query, group) from shuffled decoys (`ris -t -G FILE -P N`): a group null table ----
+ * A group's record reports the minimum e_min over its members, so its null is the distribution of the DECOYS' minimum over
+ * the same members - members the real query never hit included, and a decoy that beats the observed energy on two isoforms
+ * counting once.  No fold of the per-pair columns of prb_nullset yields that count, and the best member's pair-level p-value
+ * is anti-conservative, more so the more members a group has.  For one batch of real queries, one database, a group map as
+ * prb_groupset_create takes it and N decoys per query - prb_shuffle_sequence(seq, len, seed, file_pos, decoy, out) for
+ * decoy = 0 .. N - 1, as for prb_nullset -:
+ *   kept       the KEPT groups of query q are the records prb_groupset_finish(gs, n) returns for it: every occupied (q, group)
+ *              for n = 0, else its n best.  g = such a record, field for field; e_obs = g.s.e_min
+ *   m(q, d, g) for a kept (q, g) and decoy d of q: the minimum of the decoy's pair e_min over all targets of group g, of every
+ *              page, whether or not q itself has a hit against the target; +infinity when the decoy has no final hit in g
+ *   null_hits  the number of decoys d with m < +infinity
+ *   null_le    the number of decoys d with m <= e_obs, compared as doubles (-0.0 == +0.0)
+ *   null_min   the minimum of m over d (of -0.0 and +0.0 the latter is reported); +infinity when null_hits == 0
+ *   decoys     N; the p-value is p = (null_le + 1) / (N + 1), computed in double on the host (prb_write_gnull_lines)
+ * Decoy pairs of a group that is not kept for their owner are counted nowhere.  Every column is an integer sum or a minimum
+ * over a total order, so the table is - bit for bit - independent of how the decoys are cut into batches and sub-batches, of
+ * the order of the pages and of the decoy batches, of PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS and page residency, and of
+ * whether the decoys were searched under a pair mask that allows (at least) the members of their owners' kept groups.
+ *   prb_gnullset_create      finishes gs exactly as prb_groupset_finish(ctx, gs, n) does - the records are then to be had
+ *                            from prb_groupset_pairs(gs) - and keeps on the device what the decoys need: the kept records,
+ *                            a dense lookup of 4 B per (query, group), 32 B of key and counters per record, the page maps.
+ *                            PRB_ERR_STATE unless every page is merged into gs (and for a finished, broken or bad gs);
+ *                            PRB_ERR_ARG unless 1 <= ndecoys <= 100000, and for any n that prb_groupset_finish refuses.  The
+ *                            table owns all its device memory and must be freed before its context
+ *   prb_gnullset_begin       opens a batch of ndq >= 1 decoys: owner[k] = the real query's index in the group table's batch,
+ *                            decoy[k] = the decoy's number.  PRB_ERR_ARG when an (owner, decoy) is out of range, comes twice
+ *                            or belongs to a batch closed before; PRB_ERR_STATE when a batch is open; PRB_ERR_NOMEM, with the
+ *                            size in the message, when the scratch of 8 B x ndq x groups cannot be had
+ *   prb_search_page_gnull    the search of prb_search_page_summary of the batch dqb of decoys (dqb's queries are the open
+ *                            batch's, in its order: else PRB_ERR_ARG) against `page`, its records folded on the device into
+ *                            the scratch: an atomic minimum of the energy key per (decoy, group), a thread per record.  A page
+ *                            comes once per open batch.  It honours allowed_pairs (a mask made for dqb), distinct_sites and
+ *                            chain_sites; of the latter two a table takes one value, the one gs was searched with
+ *   prb_gnullset_add_pairs   the same fold for a caller's records of `page` in host memory (their `query` indexes the open
+ *                            batch); n = 0 only marks the page as merged.  PRB_ERR_ARG for a record whose query or db_id is
+ *                            out of range, whose hits are below 1, or whose (query, db_id) comes twice in the list
+ *   prb_gnullset_end         PRB_ERR_STATE unless every page is merged in the open batch.  Every scratch cell that holds a
+ *                            minimum is counted into its record and emptied, a thread per cell; the batch's (owner, decoy)
+ *                            pairs are closed
+ *   prb_gnullset_finish      PRB_ERR_STATE unless every (query, decoy) is closed and no batch is open - a p-value never rests
+ *                            on fewer decoys than it says.  The records are gathered on the device and copied to the host in
+ *                            one copy; the device memory is released (a second call does nothing)
+ *   prb_gnullset_pairs       the records, in the order and number of prb_groupset_pairs(gs)
+ *   prb_gnullset_decoy_counts  the stage counts of prb_pairset_counts, summed over the decoy searches
+ * Every check of a call is made on the host before anything is enqueued: a refused call leaves the table untouched; a merge
+ * that fails part way leaves it unusable.  On the device every kernel checks query, db_id, page, group, owner and decoy
+ * against the table's ranges again; a violation raises the table's `bad` flag and writes nothing, and the next call on the
+ * table returns PRB_ERR_STATE.  There is no prb_gnullset_merge: a batch belongs to one worker.  Stage timer "gnull":
+ * launches = 1 for prb_gnullset_create with records to keep, 1 per sub-batch with final hits and per prb_gnullset_add_pairs
+ * with records (the fold), 1 per prb_gnullset_end (the close), 1 for prb_gnullset_finish with records (the gather). */
+typedef struct prb_gnull_pair {
+  prb_group_pair g;      /* the kept (query, group) record */
+  int32_t decoys, pad;   /* N; 0 */
+  int64_t null_hits, null_le;
+  double null_min;
+} prb_gnull_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_gnull_pair) == 120, "prb_gnull_pair: no padding");
+#endif
+typedef struct prb_gnullset prb_gnullset;
+int prb_gnullset_create(prb_ctx *ctx, prb_groupset *gs, int32_t n, int32_t ndecoys, prb_gnullset **out);
+int prb_gnullset_begin(prb_ctx *ctx, prb_gnullset *gn, const int32_t *owner, const int32_t *decoy, int32_t ndq);
+int prb_search_page_gnull(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_gnullset *gn);
+int prb_gnullset_add_pairs(prb_ctx *ctx, prb_gnullset *gn, int32_t page, const prb_pair_summary *pairs, int64_t n);
+int prb_gnullset_end(prb_ctx *ctx, prb_gnullset *gn);
+int prb_gnullset_finish(prb_ctx *ctx, prb_gnullset *gn);
+int64_t prb_gnullset_size(const prb_gnullset *gn);
+const prb_gnull_pair *prb_gnullset_pairs(const prb_gnullset *gn);
+void prb_gnullset_decoy_counts(const prb_gnullset *gn, int64_t counts[3]);
+void prb_gnullset_free(prb_gnullset *gn);
+/* The lines of `ris -t -G FILE -P N` for one batch: per record the line of prb_write_group_lines, and behind it the five
+ * columns that prb_write_null_lines puts behind a `-t` line: ,Decoys,NullHits,NullLE,NullMin,PValue - in the same forms. */
+int prb_write_gnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_gnull_pair *recs,
                           int64_t nrecs, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
                           int64_t *nlines, int64_t *nbytes);
 

@@ -82,6 +82,12 @@ assert NULL_DTYPE.itemsize == 96
 GROUP_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("group", "<i4"), ("members", "<i4"), ("rank", "<i4"), ("group_hits", "<i8")])
 assert GROUP_DTYPE.itemsize == 88
 
+# prb_gnull_pair: the embedded prb_group_pair's fields (the kept record), then the decoys per query and the null counters of
+# the group (`ris -t -G FILE -P N`)
+GNULL_DTYPE = np.dtype(GROUP_DTYPE.descr + [("decoys", "<i4"), ("pad", "<i4"), ("null_hits", "<i8"), ("null_le", "<i8"),
+                                            ("null_min", "<f8")])
+assert GNULL_DTYPE.itemsize == 120
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -215,6 +221,18 @@ SYMBOLS = {
     "prb_groupset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_groupset_free": (None, [ctypes.c_void_p]),
     "prb_write_group_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                             P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_gnullset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, c_i32, P(ctypes.c_void_p)]),
+    "prb_gnullset_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32]),
+    "prb_search_page_gnull": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_gnullset_add_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64]),
+    "prb_gnullset_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_gnullset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_gnullset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_gnullset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_gnullset_decoy_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_gnullset_free": (None, [ctypes.c_void_p]),
+    "prb_write_gnull_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                              P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
@@ -888,6 +906,101 @@ def search_groups(ctx, qb, db, group_of_page, ngroups, n=0, opts=None, pages=Non
     return (recs, counts) if with_counts else recs
 
 
+class GNullSet(_Table):
+    """prb_gnullset: per kept (query, group) record of a group table, how the query's decoys fare against the group's
+    members.  Made from a GroupSet with every page merged, which it finishes (gs.records() are then its records); the decoys
+    come in batches between begin() and end().  Close it before its context."""
+    PREFIX = "gnullset"
+
+    def __init__(self, ctx, gs, n, ndecoys):
+        h = ctypes.c_void_p()
+        _check(lib().prb_gnullset_create(ctx.h, gs.h, n, ndecoys, ctypes.byref(h)))
+        self.h, self.ctx, self.db = h, ctx, gs.db
+
+    def begin(self, owner, decoy):
+        """prb_gnullset_begin: opens the batch of the decoys decoy[k] of the real queries owner[k]"""
+        owner, decoy = np.ascontiguousarray(owner, np.int32), np.ascontiguousarray(decoy, np.int32)
+        assert len(owner) == len(decoy)
+        _check(lib().prb_gnullset_begin(self.ctx.h, self.h, owner.ctypes.data if len(owner) else None,
+                                        decoy.ctypes.data if len(owner) else None, len(owner)))
+
+    def merge(self, dqb, page, opts=None):
+        """prb_search_page_gnull: the open batch's decoys dqb against `page`"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_gnull(self.ctx.h, dqb.h, self.db.h, page, ctypes.byref(o), self.h))
+
+    def add_pairs(self, page, pairs):
+        """prb_gnullset_add_pairs: a caller's PAIR_DTYPE records of the open batch against `page`; their `query` indexes
+        the batch"""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        _check(lib().prb_gnullset_add_pairs(self.ctx.h, self.h, page, pairs.ctypes.data if len(pairs) else None, len(pairs)))
+
+    def end(self):
+        """prb_gnullset_end: the open batch counted and closed"""
+        _check(lib().prb_gnullset_end(self.ctx.h, self.h))
+
+    def finish(self):
+        """prb_gnullset_finish -> structured array GNULL_DTYPE (a copy), in the group table's order"""
+        return self._finish("pairs", GNULL_DTYPE)
+
+    def counts(self):
+        """the stage counts of the decoy searches"""
+        c = (c_i64 * 3)()
+        lib().prb_gnullset_decoy_counts(self.h, c)
+        return tuple(c)
+
+
+def group_records(gs):
+    """prb_groupset_pairs of a finished group table (a GNullSet finishes the one it is made from) -> GROUP_DTYPE (a copy)"""
+    return _records(lib().prb_groupset_pairs(gs.h), lib().prb_groupset_size(gs.h), GROUP_DTYPE)
+
+
+def search_gnull(ctx, qb, seqs, db, group_of_page, ngroups, ndecoys, n=0, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None,
+                 pages=None):
+    """The group null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its
+    file) against db -> structured array GNULL_DTYPE, in the order of GroupSet.finish(n).  mask: every decoy batch is
+    searched under a pair mask that allows each decoy the members of its owner's kept groups only (the same records either
+    way).  decoy_batch: decoys per batch (all at once by default); pages: their order."""
+    o = opts or default_opts()
+    pages = list(range(db.npages)) if pages is None else list(pages)
+    dseqs, owner, decoy = null_decoys(seqs, ndecoys, seed, file_pos0)
+    step = decoy_batch or len(dseqs)
+    with GroupSet(ctx, qb, db, group_of_page, ngroups) as gs:
+        for p in pages:
+            gs.merge(p, o)
+        with GNullSet(ctx, gs, n, ndecoys) as gn:
+            kept = group_records(gs)
+            members = {}  # group -> [(page, db_id)]
+            for p, m in enumerate(group_of_page):
+                for i, g in enumerate(m):
+                    members.setdefault(int(g), []).append((p, i))
+            for i0 in range(0, len(dseqs), step):
+                own, dec = owner[i0:i0 + step], decoy[i0:i0 + step]
+                dqb = QBatch(ctx, dseqs[i0:i0 + step], db.repeat_flag)
+                pm = None
+                try:
+                    dqb.accessibility(db.W, db.delta)
+                    od = RisOpts.from_buffer_copy(o)
+                    od.allowed_pairs = None  # (a caller's mask is for the real batch)
+                    if mask:
+                        pm = PairMask(ctx, dqb, db)
+                        for k in range(len(own)):
+                            tgt = [t for g in kept["group"][kept["query"] == own[k]] for t in members[int(g)]]
+                            if tgt:
+                                pm.allow(np.full(len(tgt), k, np.int32), np.array([t[0] for t in tgt], np.int32),
+                                         np.array([t[1] for t in tgt], np.int32))
+                        od.allowed_pairs = pm.h.value
+                    gn.begin(own, dec)
+                    for p in pages:
+                        gn.merge(dqb, p, od)
+                    gn.end()
+                finally:
+                    if pm is not None:
+                        pm.close()
+                    dqb.close()
+            return gn.finish()
+
+
 def null_decoys(seqs, ndecoys, seed=1, file_pos0=0):
     """the decoys of a batch as search_null searches them -> (sequences, owner, decoy), query by query, decoy by decoy"""
     dseqs, owner, decoy = [], [], []
@@ -1043,6 +1156,16 @@ def write_group_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes,
     gn = (ctypes.c_char_p * max(len(group_names), 1))(*[g.encode() for g in group_names])
     gsz = np.ascontiguousarray(group_sizes, np.int32)
     return _write(lib().prb_write_group_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
+                  gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
+
+
+def write_gnull_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes, id0=0, fd=-1):
+    """Lines of `ris -t -G FILE -P N` for one batch: recs as GNullSet.finish returns them; group_names / group_sizes indexed
+    by group.  -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, GNULL_DTYPE)
+    gn = (ctypes.c_char_p * max(len(group_names), 1))(*[g.encode() for g in group_names])
+    gsz = np.ascontiguousarray(group_sizes, np.int32)
+    return _write(lib().prb_write_gnull_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
                   gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
 
 

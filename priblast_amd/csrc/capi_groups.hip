@@ -65,6 +65,64 @@ static int merge_group_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const
 }
 int prb_groupset::take(const SubBatch &b) { return merge_group_pairs(ctx, this, b.page, b.records, b.npairs); }
 
+// prb_groupset_finish (and prb_gnullset_create, which keeps the records on the device): the occupied slots selected on the
+// device - with n > 0 each query's n lowest keys among them -, their records gathered there and copied once
+int prb::finish_groupset(const char *fn, prb_ctx *ctx, prb_groupset *gs, int32_t n, prb_gnullset *keep) {
+  if (int rc = finish_guard(fn, "group", ctx, gs)) return rc;
+  if (gs->finished) return PRB_OK; // (the records are on the host already)
+  if (gs->bad) return refuse(fn, kBadRecord, PRB_ERR_STATE);
+  if (n < 0 || n > kTopMaxN) return refuse(fn, "need 0 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
+  gs->pairs.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  const int64_t S = gs->slots();
+  if (S > 0) {
+    int rc;
+    SearchWs &w = ws_of(ctx);
+    if ((rc = gs->occ.ensure((size_t)S)) || (rc = gs->sel.ensure((size_t)S * 4)) || (rc = w.count.ensure(16))) return rc;
+    if ((rc = ctx->time_begin())) return rc;
+    int64_t launches = 2, nsel = 0;
+    PRB_HIP(launch_group_flags(gs->view(), gs->occ.as<uint8_t>(), ctx->stream));
+    if ((rc = select_flagged(ctx, w, nullptr, gs->occ.as<uint8_t>(), gs->sel.as<uint32_t>(), (size_t)S, &nsel))) return rc;
+    if (nsel < 0 || nsel > S) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
+    const uint32_t *idx = gs->sel.as<uint32_t>(), *top = nullptr;
+    if (nsel && n > 0) {
+      // each query's n lowest keys: top[q * n + r]; the ranks in use selected in (query, rank) order into occ's place
+      const size_t T = (size_t)gs->nq * (size_t)n;
+      if ((rc = gs->top.ensure(T * 4)) || (rc = gs->keep.ensure(T)) || (rc = gs->out.ensure(T * 4))) return rc;
+      PRB_HIP(launch_group_select(gs->view(), gs->sel.as<uint32_t>(), nsel, n, gs->top.as<uint32_t>(), gs->keep.as<uint8_t>(), ctx->stream));
+      if ((rc = select_flagged(ctx, w, nullptr, gs->keep.as<uint8_t>(), gs->out.as<uint32_t>(), T, &nsel))) return rc;
+      if (nsel < 0 || nsel > (int64_t)T) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
+      std::swap(gs->sel, gs->out); // (sel = the kept ranks; out is free for the records)
+      idx = gs->sel.as<uint32_t>();
+      top = gs->top.as<uint32_t>();
+      launches += 2;
+    }
+    if (nsel) {
+      try {
+        gs->pairs.resize((size_t)nsel);
+      } catch (const std::exception &e) {
+        return refuse(fn, e.what(), PRB_ERR_NOMEM);
+      }
+      const size_t bytes = (size_t)nsel * sizeof(prb_group_pair);
+      if ((rc = gs->out.ensure(bytes))) return rc;
+      PRB_HIP(launch_group_gather(gs->view(), idx, nsel, top, n, gs->out.p, ctx->stream));
+      PRB_HIP(hipMemcpyAsync(gs->pairs.data(), gs->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      launches++;
+    }
+    if ((rc = ctx->time_end(ModeTimer::kGroup, launches))) return rc; // (synchronises: the copy is over)
+    if ((rc = fetch_bad(ctx, gs))) return rc;
+    if (gs->bad) {
+      gs->pairs.clear();
+      return refuse(fn, "a selected slot lies outside the group table", PRB_ERR_STATE);
+    }
+  }
+  if (keep)
+    if (int rc = keep_group_records(ctx, keep, gs, gs->pairs.empty() ? nullptr : gs->out.p, (int64_t)gs->pairs.size())) return rc;
+  gs->finished = true;
+  gs->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
 extern "C" {
 
 int prb_groupset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const int32_t *const *group_of_page, int32_t ngroups,
@@ -172,62 +230,7 @@ int prb_groupset_merge(prb_ctx *ctx, prb_groupset *dst, prb_groupset *src) {
   return rc;
 }
 
-// the occupied slots selected on the device - with n > 0 each query's n lowest keys among them -, their records gathered
-// there and copied once
-int prb_groupset_finish(prb_ctx *ctx, prb_groupset *gs, int32_t n) {
-  const char *fn = kFinishFn;
-  if (int rc = finish_guard(fn, "group", ctx, gs)) return rc;
-  if (gs->finished) return PRB_OK; // (the records are on the host already)
-  if (gs->bad) return refuse(fn, kBadRecord, PRB_ERR_STATE);
-  if (n < 0 || n > kTopMaxN) return refuse(fn, "need 0 <= n <= " + std::to_string(kTopMaxN) + " (got " + std::to_string(n) + ")");
-  gs->pairs.clear();
-  PRB_HIP(hipSetDevice(ctx->device));
-  const int64_t S = gs->slots();
-  if (S > 0) {
-    int rc;
-    SearchWs &w = ws_of(ctx);
-    if ((rc = gs->occ.ensure((size_t)S)) || (rc = gs->sel.ensure((size_t)S * 4)) || (rc = w.count.ensure(16))) return rc;
-    if ((rc = ctx->time_begin())) return rc;
-    int64_t launches = 2, nsel = 0;
-    PRB_HIP(launch_group_flags(gs->view(), gs->occ.as<uint8_t>(), ctx->stream));
-    if ((rc = select_flagged(ctx, w, nullptr, gs->occ.as<uint8_t>(), gs->sel.as<uint32_t>(), (size_t)S, &nsel))) return rc;
-    if (nsel < 0 || nsel > S) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
-    const uint32_t *idx = gs->sel.as<uint32_t>(), *top = nullptr;
-    if (nsel && n > 0) {
-      // each query's n lowest keys: top[q * n + r]; the ranks in use selected in (query, rank) order into occ's place
-      const size_t T = (size_t)gs->nq * (size_t)n;
-      if ((rc = gs->top.ensure(T * 4)) || (rc = gs->keep.ensure(T)) || (rc = gs->out.ensure(T * 4))) return rc;
-      PRB_HIP(launch_group_select(gs->view(), gs->sel.as<uint32_t>(), nsel, n, gs->top.as<uint32_t>(), gs->keep.as<uint8_t>(), ctx->stream));
-      if ((rc = select_flagged(ctx, w, nullptr, gs->keep.as<uint8_t>(), gs->out.as<uint32_t>(), T, &nsel))) return rc;
-      if (nsel < 0 || nsel > (int64_t)T) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
-      std::swap(gs->sel, gs->out); // (sel = the kept ranks; out is free for the records)
-      idx = gs->sel.as<uint32_t>();
-      top = gs->top.as<uint32_t>();
-      launches += 2;
-    }
-    if (nsel) {
-      try {
-        gs->pairs.resize((size_t)nsel);
-      } catch (const std::exception &e) {
-        return refuse(fn, e.what(), PRB_ERR_NOMEM);
-      }
-      const size_t bytes = (size_t)nsel * sizeof(prb_group_pair);
-      if ((rc = gs->out.ensure(bytes))) return rc;
-      PRB_HIP(launch_group_gather(gs->view(), idx, nsel, top, n, gs->out.p, ctx->stream));
-      PRB_HIP(hipMemcpyAsync(gs->pairs.data(), gs->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-      launches++;
-    }
-    if ((rc = ctx->time_end(ModeTimer::kGroup, launches))) return rc; // (synchronises: the copy is over)
-    if ((rc = fetch_bad(ctx, gs))) return rc;
-    if (gs->bad) {
-      gs->pairs.clear();
-      return refuse(fn, "a selected slot lies outside the group table", PRB_ERR_STATE);
-    }
-  }
-  gs->finished = true;
-  gs->release(); // (only the host records are needed from here on)
-  return PRB_OK;
-}
+int prb_groupset_finish(prb_ctx *ctx, prb_groupset *gs, int32_t n) { return finish_groupset(kFinishFn, ctx, gs, n, nullptr); }
 
 int64_t prb_groupset_size(const prb_groupset *gs) { return gs ? (int64_t)gs->pairs.size() : -1; }
 const prb_group_pair *prb_groupset_pairs(const prb_groupset *gs) { return gs ? gs->pairs.data() : nullptr; }

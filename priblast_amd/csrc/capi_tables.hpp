@@ -1,5 +1,5 @@
-// The protocol of the seven result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
+// The protocol of the eight result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip, capi_gnull.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
 // search of a page into a table, the merge of one table into another across contexts and devices, and what every
 // prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check comes
 // before a table is touched: a refused call leaves it as it was.

@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the seven result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset): whose they are, whether they can still be merged into, and the block on the device that
+// What the eight result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_gnullset): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -733,6 +733,55 @@ struct prb_groupset : prb::MergeTable {
   }
   ~prb_groupset() { release(); } // (also on the error paths of prb_groupset_create)
 };
+
+// prb_gnullset_create .. prb_gnullset_free: the group null table of one batch (capi_gnull.hip): the records that a group
+// table was finished into, kept on the device with a lookup from (query, group), and their decoy counters.  Decoys come
+// in batches between prb_gnullset_begin and prb_gnullset_end; the pages of the open batch are folded into `cell`
+// sub-batch by sub-batch (merge_gnull_pairs).  It owns all its device memory - the page maps are the group table's,
+// taken over when that is finished.  `table` = GNullCount[nkept]
+struct prb_gnullset : prb::TableState {
+  int32_t nq = 0, ngroups = 0, ndecoys = 0;
+  int64_t nkept = 0;
+  std::vector<std::vector<int32_t>> map; // per page: the groups of its sequences
+  std::vector<prb::DevBuf> map_dev;      // ... on the device
+  std::vector<uint64_t> closed;          // a bit per (query, decoy): its batch is closed (prb_gnullset_end)
+  int64_t nclosed = 0;                   // bits set in `closed`
+  bool open = false;                     // between prb_gnullset_begin and prb_gnullset_end
+  std::vector<int32_t> owner, decoy;     // the open batch
+  std::vector<uint8_t> merged;           // per page: merged in the open batch
+  bool bad = false;                      // the device's `bad` flag, as the last call left it
+  prb::DevBuf lookup, kept, cell, own, badflag;
+  prb::DevBuf h_rec;                     // prb_gnullset_add_pairs: the caller's records
+  prb::DevBuf out;                       // prb_gnullset_finish: the records
+  std::vector<prb_gnull_pair> pairs;     // prb_gnullset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &b) override;
+  int64_t slots() const { return (int64_t)nq * ngroups; }
+  int64_t decoys_all() const { return (int64_t)nq * ndecoys; }
+  prb::GNullTab view() const {
+    const int32_t ndq = (int32_t)owner.size();
+    return prb::GNullTab{lookup.as<uint32_t>(), table.as<prb::GNullCount>(), cell.as<unsigned long long>(), own.as<int32_t>(),
+                         own.as<int32_t>() + ndq, badflag.as<uint32_t>(), nkept, nq, ngroups, ndecoys, (int32_t)map.size(), ndq};
+  }
+  prb::GroupPage page_view(size_t page) const { return prb::GroupPage{map_dev[page].as<int32_t>(), (int32_t)page, (int32_t)map[page].size()}; }
+  // nothing of the table is released while work on it may still be queued on its context's stream
+  void release() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (prb::DevBuf *b : {&table, &lookup, &kept, &cell, &own, &badflag, &h_rec, &out}) b->release();
+    for (prb::DevBuf &b : map_dev) b.release();
+  }
+  ~prb_gnullset() { release(); } // (also on the error paths of prb_gnullset_create)
+};
+
+namespace prb {
+// capi_groups.hip: prb_groupset_finish proper, for `fn_name`.  keep != nullptr (prb_gnullset_create): before the group
+// table's device memory is released, the gathered records - still on the device - go to keep_group_records
+// (capi_gnull.hip), which also takes the page maps over.
+int finish_groupset(const char *fn_name, prb_ctx *ctx, prb_groupset *gs, int32_t n, prb_gnullset *keep);
+int keep_group_records(prb_ctx *ctx, prb_gnullset *gn, prb_groupset *gs, const void *recs_dev, int64_t nrec);
+} // namespace prb
 
 namespace prb {
 // Host threads for the per-query host work (suffix arrays, seed DFS): PRB_HOST_THREADS, else half of the CPUs the

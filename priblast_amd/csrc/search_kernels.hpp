@@ -638,4 +638,35 @@ hipError_t launch_group_select(const GroupTab &t, const uint32_t *occ, int64_t n
 // ... out[j] (prb_group_pair) of the slot idx[j] (top == nullptr, rank 0), or of the slot top[idx[j]] with rank idx[j] % n
 hipError_t launch_group_gather(const GroupTab &t, const uint32_t *idx, int64_t nrec, const uint32_t *top, int32_t n, void *out, hipStream_t s);
 
+// ============================================================================ gnull_kernels.hip: the group null table
+// (prb_gnullset_*)  The kept (query, group) records of a finished group table, and per record how the query's decoys
+// fare against the group.  lookup[q * ngroups + g] = the record of (q, g), all ones: not kept.  A record's counters: the
+// energy key of its e_min, the decoys with a hit in the group, those whose minimum over the group is not above e_min,
+// and the smallest such minimum as its energy key (the key of +infinity: none).  cell[d * ngroups + g] = the minimum
+// energy key of decoy d of the OPEN batch (owner[d], decoy[d]; ndq of them) over the members of g, all ones: no hit yet.
+// bad: set when a record names a query, a sequence, a page, a group, an owner or a decoy outside the table.
+struct GNullCount {
+  unsigned long long ekey, null_hits, null_le, null_min;
+};
+struct GNullTab {
+  uint32_t *lookup;         // [nq * ngroups]
+  GNullCount *cnt;          // [nkept]
+  unsigned long long *cell; // [ndq * ngroups] (more is allocated when an earlier batch was larger)
+  const int32_t *owner, *decoy; // [ndq]
+  uint32_t *bad;
+  int64_t nkept;
+  int32_t nq, ngroups, ndecoys, npages, ndq;
+};
+// prb_gnullset_create: rec[0, nkept) (prb_group_pair, on the device) copied to kept[], each into the lookup (all ones
+// before), with its energy key and empty counters; a lane per record
+hipError_t launch_gnull_keep(const void *rec, const GNullTab &t, void *kept, hipStream_t s);
+// rec[0, nrec) = launch_pair_fold's records (prb_pair_summary) of the open decoy batch against the page, or a caller's:
+// an atomic minimum of each record's energy key into the cell of (its decoy, the group of its db_id) when that group is
+// kept for the decoy's owner; a lane per record
+hipError_t launch_gnull_fold(const void *rec, int64_t nrec, const GNullTab &t, const GroupPage &pg, hipStream_t s);
+// prb_gnullset_end: every cell of the open batch that holds a key counted into its record and emptied; a lane per cell
+hipError_t launch_gnull_close(const GNullTab &t, hipStream_t s);
+// prb_gnullset_finish: out[k] (prb_gnull_pair) = kept[k] with its counters
+hipError_t launch_gnull_gather(const GNullTab &t, const void *kept, void *out, hipStream_t s);
+
 } // namespace prb

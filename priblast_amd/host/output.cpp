@@ -211,52 +211,69 @@ void format_target_piece(const Piece &pc, const TargetView &v, const std::vector
     put_summary_line(b, id++, v.names[v.r[i].s.query], v.qlen_unmasked[v.r[i].s.query], tabs[v.r[i].page], v.r[i].s);
 }
 
-// the `-t` line of the observed pair, then - in place of its newline - the null columns
+// in place of a line's newline: the null columns and the newline
+void put_null_columns(Buf &b, int32_t decoys, int64_t null_hits, int64_t null_le, double null_min) {
+  b.n--; // (the newline)
+  char *p = b.room(200);
+  char *const p0 = p;
+  for (long long f : {(long long)decoys, (long long)null_hits, (long long)null_le}) {
+    *p++ = ',';
+    p = put_int(p, f);
+  }
+  *p++ = ',';
+  if (null_hits > 0) {
+    p = put_g(p, null_min);
+  } else {
+    *p++ = 'N';
+    *p++ = 'A';
+  }
+  *p++ = ',';
+  p = put_g(p, ((double)null_le + 1.0) / ((double)decoys + 1.0));
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
+// the `-t` line of the observed pair, then the null columns
 void format_null_piece(const Piece &pc, const NullView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   int64_t id = pc.id;
   for (int64_t i = pc.i0; i < pc.i1; i++) {
     const prb_null_pair &x = v.r[i];
     put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
-    b.n--; // (the newline)
-    char *p = b.room(200);
-    char *const p0 = p;
-    for (long long f : {(long long)x.decoys, (long long)x.null_hits, (long long)x.null_le}) {
-      *p++ = ',';
-      p = put_int(p, f);
-    }
-    *p++ = ',';
-    if (x.null_hits > 0) {
-      p = put_g(p, x.null_min);
-    } else {
-      *p++ = 'N';
-      *p++ = 'A';
-    }
-    *p++ = ',';
-    p = put_g(p, ((double)x.null_le + 1.0) / ((double)x.decoys + 1.0));
-    *p++ = '\n';
-    b.n += (size_t)(p - p0);
+    put_null_columns(b, x.decoys, x.null_hits, x.null_le, x.null_min);
   }
 }
 
-// the `-t` line of the group's best member, then - in place of its newline - the group columns
+// the `-t` line of the group's best member x, then - in place of its newline - the group columns
+void put_group_line(Buf &b, int64_t id, const std::string &qname, int32_t qlen, const std::vector<SeqTable> &tabs, const prb_group_pair &x,
+                    const char *const *group_names, const int32_t *group_sizes) {
+  put_summary_line(b, id, qname, qlen, tabs[x.page], x.s);
+  b.n--; // (the newline)
+  const size_t len = std::strlen(group_names[x.group]);
+  char *p = b.room(len + 100);
+  char *const p0 = p;
+  *p++ = ',';
+  std::memcpy(p, group_names[x.group], len);
+  p += len;
+  for (long long f : {(long long)x.members, (long long)group_sizes[x.group], (long long)x.hits}) {
+    *p++ = ',';
+    p = put_int(p, f);
+  }
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
 void format_group_piece(const Piece &pc, const GroupView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) put_group_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs, v.r[i], v.group_names, v.group_sizes);
+}
+
+// the group line, then the null columns
+void format_gnull_piece(const Piece &pc, const GNullView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
   for (int64_t i = pc.i0; i < pc.i1; i++) {
-    const prb_group_pair &x = v.r[i];
-    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
-    b.n--; // (the newline)
-    const size_t len = std::strlen(v.group_names[x.group]);
-    char *p = b.room(len + 100);
-    char *const p0 = p;
-    *p++ = ',';
-    std::memcpy(p, v.group_names[x.group], len);
-    p += len;
-    for (long long f : {(long long)x.members, (long long)v.group_sizes[x.group], (long long)x.hits}) {
-      *p++ = ',';
-      p = put_int(p, f);
-    }
-    *p++ = '\n';
-    b.n += (size_t)(p - p0);
+    const prb_gnull_pair &x = v.r[i];
+    put_group_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs, x.g, v.group_names, v.group_sizes);
+    put_null_columns(b, x.decoys, x.null_hits, x.null_le, x.null_min);
   }
 }
 
@@ -368,6 +385,13 @@ int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_group_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_gnull_batch(const GNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the group records)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].g.s.query; },
+      [&](const Piece &pc, Buf &b) { format_gnull_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_target_batch(const TargetView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

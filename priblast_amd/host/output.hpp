@@ -91,6 +91,17 @@ struct GroupView : QueryView {
 };
 int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -t -G FILE -P N` (prb_gnullset_pairs): the line of `-t -G` for every kept record, in the records' order,
+// with the null columns of `-t -z` behind it:
+//   ... ,Group,Members,GroupSize,GroupHits ,Decoys,NullHits,NullLE,NullMin,PValue
+struct GNullView : QueryView {
+  const prb_gnull_pair *r = nullptr;
+  int64_t n = 0;
+  const char *const *group_names = nullptr;
+  const int32_t *group_sizes = nullptr;
+};
+int64_t format_gnull_batch(const GNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 // Lines of `ris -r N` (prb_targetset_pairs): the same lines again, in the records' order (by page, target and rank),
 // numbered from id0 on.  The queries are those of the whole run: `names` and `qlen_unmasked` are indexed by the
 // records' query identifiers.

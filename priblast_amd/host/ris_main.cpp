@@ -49,6 +49,10 @@
 // end the first worker merges the others' into its own (prb_covset_merge), the regions are reduced on the device
 // (prb_covset_finish) and only their records reach the host, written by page, target and start.  `-c` is refused with
 // -t, -n, -q, -k, -b, -r and in rank mode; -u and -j combine.
+// `ris -t -G FILE -P N` adds an empirical p-value to every `-t -G [-n K]` line: the decoys of `-z`, but counted per group -
+// a decoy's minimum over all members of the group against the group's minimum - in a group null table on the GPU
+// (prb_gnullset_*), the decoys searched against the members of each query's kept groups only.  `-P` needs -G and is
+// refused with -z, -k, -q, -r, -c, -b and in rank mode.
 //
 // How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
@@ -159,7 +163,7 @@ void usage() {
             "              PValue = (NullLE + 1) / (INT + 1); lines by query, then page, then target (1 <= INT <= 100000;\n"
             "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
-            "    -Z INT    with -z: the seed of the shuffles [default:1]\n"
+            "    -Z INT    with -z or -P: the seed of the shuffles [default:1]\n"
             "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
             "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
             "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
@@ -167,7 +171,16 @@ void usage() {
             "              target of the database), and behind it the group's name, its members with a hit, its targets and\n"
             "              the members' hits; lines by query, then group in database order; with -n N the N best groups of\n"
             "              each query, by rank (with -n, -u, -j, -L and the search options; not with -z, -k, -q, -r, -c, -b,\n"
-            "              nor with WORLD_SIZE > 1: p-values per group and the best queries per group are not implemented)\n"
+            "              nor with WORLD_SIZE > 1: the best queries per group are not implemented)\n"
+            "    -P INT    with -t -G: an empirical p-value per query-group pair from INT shuffled decoys of each query, as -z\n"
+            "              makes them: behind every -t -G line the decoys per query, how many of them have a hit against a\n"
+            "              target of the group (NullHits), how many of those reach the group's minimum interaction energy or\n"
+            "              below on any of its targets - whether or not the query itself hits that target - (NullLE; a decoy\n"
+            "              counts once), the lowest decoy minimum (NullMin, NA without one) and PValue = (NullLE + 1) /\n"
+            "              (INT + 1); with -n N only the N kept groups of each query get decoys searched against them\n"
+            "              (1 <= INT <= 100000; with -n, -u, -j, -L and the search options; not with -z, -k, -q, -r, -c, -b, nor\n"
+            "              with WORLD_SIZE > 1; PRB_SPLIT has no effect; PRB_NULL_MASK=0: the decoys are searched against every\n"
+            "              target - every listed one under -L -, the output is the same)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -190,14 +203,15 @@ thread_local bool t_team_thread = false;
 
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
-// N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups };
+// N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
+// `-t -G -P` the same with the group's null columns.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -219,6 +233,7 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'z', "an empirical p-value per pair from N shuffled decoys", bit(kN) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
     {'Z', "the seed of the decoys' shuffles", 0, kZ, false},
     {'G', "one line per query-group pair", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
+    {'P', "an empirical p-value per query-group pair from N shuffled decoys", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kG, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -230,7 +245,7 @@ struct Args {
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
-  int decoys = 0;                                   // -z, likewise
+  int decoys = 0;                                   // -z or -P, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
   OutputMode mode = OutputMode::kHits;
@@ -255,6 +270,7 @@ struct Free {
   void operator()(prb_tophits *p) const { prb_tophits_free(p); }
   void operator()(prb_nullset *p) const { prb_nullset_free(p); }
   void operator()(prb_groupset *p) const { prb_groupset_free(p); }
+  void operator()(prb_gnullset *p) const { prb_gnullset_free(p); }
 };
 template <class T> using Handle = std::unique_ptr<T, Free>;
 
@@ -269,6 +285,7 @@ struct BatchResult {
   Handle<prb_tophits> tophits;                 // kTopHits
   Handle<prb_nullset> null;                    // kNull
   Handle<prb_groupset> groups;                 // kGroups
+  Handle<prb_gnullset> gnull;                  // kGroupNull
 };
 
 // The result of one batch (in rank mode: of one round of batches, gathered), waiting to be written.
@@ -549,6 +566,7 @@ struct GroupMap {
   std::vector<std::vector<int32_t>> of_page;
   std::vector<std::string> names;
   std::vector<int32_t> sizes; // targets per group
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> members; // -P: per group its targets (page, db_id), in database order
 };
 
 struct Run {
@@ -591,18 +609,21 @@ void check_switches(const Args &a) {
     if (!a.given[s]) continue;
     for (int p = 0; p < kSwitches; p++)
       if (a.given[p] && (kSwitchTable[s].not_with & (1u << p))) die("Error: " + described(s) + " can't be combined with " + described(p));
-    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need]) die("Error: " + described(s) + " needs " + described(need));
+    // (-Z goes with either switch that makes decoys)
+    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && a.given[kP])) die("Error: " + described(s) + " needs " + described(need));
   }
   for (Switch s : {kR, kK, kN})
     if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
+  if (a.given[kP] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -P needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kZSeed] && !a.seed_ok) die("Error: -Z needs a non-negative integer");
 }
 
 OutputMode output_mode(const Args &a) {
   if (a.given[kZ]) return OutputMode::kNull;
+  if (a.given[kP]) return OutputMode::kGroupNull;
   if (a.given[kG]) return OutputMode::kGroups;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
@@ -612,7 +633,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -638,6 +659,7 @@ Args parse_args(int argc, char **argv) {
     case 'L': a.have_pairlist = true, a.pairlist = optarg; break;
     case 'z': a.given[kZ] = true, a.decoys = parse_count(optarg); break;
     case 'G': a.given[kG] = true, a.groupfile = optarg; break;
+    case 'P': a.given[kP] = true, a.decoys = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -762,6 +784,10 @@ void load_groups(Run &r) {
       gm.of_page[p].push_back(ins.first->second);
       gm.sizes[(size_t)ins.first->second]++;
     }
+  if (!r.a.given[kP]) return;
+  gm.members.resize(gm.names.size());
+  for (size_t p = 0; p < gm.of_page.size(); p++)
+    for (size_t i = 0; i < gm.of_page[p].size(); i++) gm.members[(size_t)gm.of_page[p][i]].emplace_back((int32_t)p, (int32_t)i);
 }
 
 // -L: the mask of a prepared batch's queries (input positions `ids`)
@@ -928,6 +954,10 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
                     "Group Hits\n";
+  case OutputMode::kGroupNull:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
+                    "Group Hits, Decoys, Null Hits, Null LE, Null Minimum Energy, P Value\n";
   case OutputMode::kNull:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Decoys, Null Hits, Null LE, "
@@ -968,8 +998,8 @@ void plan_batches(Run &r) {
 // Whole batches to the workers, or the pages of every batch?  Pages only in one process with two workers or more and
 // a database of two pages or more: when asked for, or - auto - when there are fewer batches than workers.
 void plan_split(Run &r) {
-  // (-z: a batch and its decoys belong to one worker - there is no merge of two null tables)
-  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull;
+  // (-z, -P: a batch and its decoys belong to one worker - there is no merge of two null tables)
+  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull && r.a.mode != OutputMode::kGroupNull;
   r.split_pages = can && (r.split_knob == kSplitPages || (r.split_knob == kSplitAuto && r.nb < r.workers.size()));
 }
 
@@ -1050,6 +1080,7 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
   case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
   case OutputMode::kCoverage:
   case OutputMode::kNull: // (search_null_batch makes its own)
+  case OutputMode::kGroupNull: // (search_gnull_batch)
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -1083,6 +1114,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
     break;
   }
   case OutputMode::kNull: break; // (search_null_batch)
+  case OutputMode::kGroupNull: break; // (search_gnull_batch)
   }
   if (rc) die(prb_last_error());
 }
@@ -1106,6 +1138,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kTargets:
   case OutputMode::kCoverage:
   case OutputMode::kNull:
+  case OutputMode::kGroupNull:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -1209,9 +1242,120 @@ BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
   return res;
 }
 
+// -t -G FILE -P N: the real batch against every page into a group table, which is finished - under the run's -n - into a
+// group null table: nothing comes to the host but the kept records.  Then the decoys as -z makes them, in batches of at
+// most the batch size, each against every page between prb_gnullset_begin and prb_gnullset_end.  Unless PRB_NULL_MASK=0,
+// a decoy batch is searched under a pair mask that allows each decoy the members of its owner's kept groups only - under
+// -L those of them that are listed for the owner; with PRB_NULL_MASK=0, under -L, every pair listed for the owner (the
+// statistic runs over the listed targets either way).
+BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
+  BatchResult res = empty_result(r);
+  const Args &a = r.a;
+  const char *menv = std::getenv("PRB_NULL_MASK");
+  const bool masked = !(menv && std::atoi(menv) == 0);
+  const size_t nq = p.ids.size();
+  Handle<prb_groupset> real;
+  {
+    std::vector<const int32_t *> maps;
+    for (const auto &m : r.groups.of_page) maps.push_back(m.data());
+    prb_groupset *t = nullptr;
+    const int rc = prb_groupset_create(w.ctx, p.qb, w.db, maps.data(), (int32_t)r.groups.names.size(), &t);
+    real.reset(t);
+    if (rc == PRB_ERR_NOMEM)
+      die(std::string("Error: ") + prb_last_error() + "; lower PRB_BATCH (queries per batch: " + std::to_string(r.batch) + ")");
+    if (rc) die(prb_last_error());
+  }
+  prb_ris_opts o = a.o;
+  o.allowed_pairs = p.mask;
+  for (int page = 0; page < r.npages; page++)
+    if (prb_search_page_groups(w.ctx, p.qb, w.db, page, &o, real.get())) die(prb_last_error());
+  prb_gnullset *gn = nullptr;
+  if (prb_gnullset_create(w.ctx, real.get(), a.given[kN] ? a.top : 0, a.decoys, &gn)) die(prb_last_error());
+  res.gnull.reset(gn);
+  // per query its kept groups, and - under -L - its listed targets, numbered page by page, ascending
+  std::vector<std::vector<int32_t>> kept(nq);
+  {
+    const prb_group_pair *rec = prb_groupset_pairs(real.get());
+    const int64_t n = prb_groupset_size(real.get());
+    for (int64_t i = 0; i < n; i++) {
+      if (rec[i].s.query < 0 || (size_t)rec[i].s.query >= nq || rec[i].group < 0 || (size_t)rec[i].group >= r.groups.members.size())
+        die("Error: bad record in the group table");
+      kept[(size_t)rec[i].s.query].push_back(rec[i].group);
+    }
+  }
+  real.reset();
+  std::vector<int64_t> page_first(1, 0);
+  for (const auto &m : r.groups.of_page) page_first.push_back(page_first.back() + (int64_t)m.size());
+  std::vector<std::vector<int64_t>> listed(a.have_pairlist && masked ? nq : 0);
+  for (size_t q = 0; q < listed.size(); q++) {
+    listed[q] = r.list.every;
+    const std::vector<int64_t> &own = r.list.of_query[(size_t)p.ids[q]];
+    listed[q].insert(listed[q].end(), own.begin(), own.end());
+    std::sort(listed[q].begin(), listed[q].end());
+  }
+  // the decoys, query by query and decoy by decoy
+  const size_t nd = (size_t)a.decoys, total = nq * nd;
+  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
+    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
+    std::vector<int64_t> off(m + 1, 0);
+    std::vector<int32_t> owner(m), decoy(m), dids(m);
+    for (size_t k = 0; k < m; k++) {
+      owner[k] = (int32_t)((d0 + k) / nd);
+      decoy[k] = (int32_t)((d0 + k) % nd);
+      dids[k] = p.ids[(size_t)owner[k]];
+      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dids[k]].size();
+    }
+    std::string cat((size_t)off[m], '\0');
+    bool shuffled = true;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
+    for (size_t k = 0; k < m; k++) {
+      const std::string &seq = r.seqs[(size_t)dids[k]];
+      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)dids[k], decoy[k], &cat[(size_t)off[k]])) {
+#pragma omp atomic write
+        shuffled = false;
+      }
+    }
+    if (!shuffled) die(std::string("Error: ") + prb_last_error());
+    prb_qbatch *dqb = nullptr;
+    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
+    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
+    prb_ris_opts od = a.o;
+    prb_pairmask *dmask = nullptr;
+    if (masked) {
+      std::vector<int32_t> mq, mp, md;
+      for (size_t k = 0; k < m; k++)
+        for (int32_t g : kept[(size_t)owner[k]])
+          for (const auto &[page, db_id] : r.groups.members[(size_t)g]) {
+            if (a.have_pairlist) {
+              const std::vector<int64_t> &l = listed[(size_t)owner[k]];
+              if (!std::binary_search(l.begin(), l.end(), page_first[(size_t)page] + db_id)) continue;
+            }
+            mq.push_back((int32_t)k);
+            mp.push_back(page);
+            md.push_back(db_id);
+          }
+      if (prb_pairmask_create(w.ctx, dqb, w.db, &dmask) || prb_pairmask_allow(dmask, (int64_t)mq.size(), mq.data(), mp.data(), md.data()))
+        die(std::string("Error: ") + prb_last_error());
+    } else if (a.have_pairlist) {
+      dmask = batch_mask(r, w.ctx, dqb, w.db, dids);
+    }
+    od.allowed_pairs = dmask;
+    if (prb_gnullset_begin(w.ctx, gn, owner.data(), decoy.data(), (int32_t)m)) die(std::string("Error: ") + prb_last_error());
+    for (int page = 0; page < r.npages; page++)
+      if (prb_search_page_gnull(w.ctx, dqb, w.db, page, &od, gn)) die(prb_last_error());
+    if (prb_gnullset_end(w.ctx, gn)) die(prb_last_error());
+    prb_pairmask_free(dmask);
+    prb_qbatch_destroy(dqb);
+  }
+  if (prb_gnullset_finish(w.ctx, gn)) die(prb_last_error());
+  release_batch(p);
+  return res;
+}
+
 // the search stages of a prepared batch against every page
 BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
   if (r.a.mode == OutputMode::kNull) return search_null_batch(r, w, p);
+  if (r.a.mode == OutputMode::kGroupNull) return search_gnull_batch(r, w, p);
   BatchResult res = empty_result(r);
   create_table(r, w, p.qb, res);
   for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
@@ -1321,6 +1465,23 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
           (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size() || v.r[i].group < 0 || (size_t)v.r[i].group >= gnames.size())
         die("Error: bad record in the group table");
     return written_or_die(prb::format_group_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kGroupNull: {
+    prb::GNullView v;
+    set_queries(v, job);
+    v.r = prb_gnullset_pairs(job.res.gnull.get());
+    v.n = prb_gnullset_size(job.res.gnull.get());
+    std::vector<const char *> gnames;
+    for (const std::string &g : r.groups.names) gnames.push_back(g.c_str());
+    v.group_names = gnames.data();
+    v.group_sizes = r.groups.sizes.data();
+    for (int64_t i = 0; i < v.n; i++) {
+      const prb_group_pair &x = v.r[i].g;
+      if (x.s.query < 0 || (size_t)x.s.query >= v.nq || x.page < 0 || x.page >= r.npages || x.s.db_id < 0 ||
+          (size_t)x.s.db_id >= r.tabs[(size_t)x.page].names.size() || x.group < 0 || (size_t)x.group >= gnames.size())
+        die("Error: bad record in the group null table");
+    }
+    return written_or_die(prb::format_gnull_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kTargets:
   case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
