@@ -213,6 +213,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "gnull" (prb_gnullset_create: the kept records into the lookup, launches = 1; prb_search_page_gnull / prb_gnullset_add_pairs:
  *   the fold into the scratch, launches = 1 per sub-batch with final hits; prb_gnullset_end: the close, 1; prb_gnullset_finish:
  *   the gather, 1);
+ * "eval" (prb_search_page_scored / _null_hits, prb_evalset_add_keys: the append of the keys, launches = 1 per sub-batch with
+ *   final hits; prb_evalset_close: per list the sorts and gathers and the count, then the ranks and the suffix minima;
+ *   prb_evalset_score: the look-up, 1);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -872,6 +875,76 @@ void prb_gnullset_free(prb_gnullset *gn);
 int prb_write_gnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_gnull_pair *recs,
                           int64_t nrecs, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
                           int64_t *nlines, int64_t *nbytes);
+
+/* ---- an E-value and an FDR q-value per interaction site from pooled decoys (`ris -k N -E M`): an evalset on the device ----
+ * The null tables above score a PAIR and resolve no p-value below 1 / (N + 1).  Here the decoys' hits against the WHOLE
+ * database are pooled into one null distribution of hit energies per query, and every real hit is placed in it.  For one
+ * batch of real queries, one database and M decoys per query - made as for the null table, prb_shuffle_sequence with decoy =
+ * 0 .. M - 1 - the table holds two lists of (query, energy key): the final hits (after distinct_sites / chain_sites) of the
+ * real batch, and those of the decoys under their owners.  The key is the order-preserving 64-bit key of the hit's e_tot
+ * (-0.0 == +0.0).  For a real hit h of query q, all in integers:
+ *   rank      the number of real hits of q with key <= key(h) (h included; equal energies share the value)
+ *   null_le   the number of hits of q's M decoys with key <= key(h)
+ *   EValue    null_le / M: the decoy hits this good that one search yields by chance
+ *   FDR_g     null_le_g / (M * rank_g)
+ *   QValue    min(1, the minimum of FDR_g over the real hits g of q with key(g) >= key(h)), kept as the minimising g's pair
+ *             (q_num, q_den) = (null_le_g, rank_g) - among equal fractions that of the g of lowest key; (M, 1) when the minimum
+ *             exceeds 1.  The host prints q_num / (M * q_den)
+ * Fractions are compared exactly by cross-multiplication: a list holds at most 2^32 - 1 keys (more is refused), so every
+ * product fits 64 bits; no floating point takes part on the device.  Every figure is a count over a total order: the table
+ * is - bit for bit - independent of how the batches are cut, of the order of pages and decoy batches and of the order of
+ * the lists.
+ *   prb_evalset_create          an empty table for qb and db, 1 <= ndecoys <= 100000 (else PRB_ERR_ARG).  It owns all its
+ *                               device memory - 12 B per real hit and per decoy hit while the lists grow - and must be
+ *                               freed before its context, its batch and its database
+ *   prb_search_page_scored      the real batch's search of `page`, once: the final hits' keys appended to the real list
+ *                               (nothing leaves the device).  With tophits != NULL the same sub-batches are handed on to
+ *                               that top-N hit table, which ends up byte for byte as prb_search_page_tophits fills it, and
+ *                               takes all its refusals (its context, batch, pages, output_style and selection); a page is
+ *                               searched once (else PRB_ERR_ARG)
+ *   prb_search_page_null_hits   the same search of a batch dqb of decoys, its final hits' keys appended to the decoy list
+ *                               under owner[q], for every query q of dqb: no hit records are packed and no base pairs
+ *                               gathered.  owner / decoy as for prb_search_page_decoys; an (owner, decoy, page) is accepted
+ *                               once, an (owner, decoy) once per call (else PRB_ERR_ARG).  It honours opts->allowed_pairs
+ *   prb_evalset_add_keys        the append for a caller's list: energy[i] under query_or_owner[i], into the real list
+ *                               (is_decoy == 0) or the decoy list
+ *   prb_evalset_close           PRB_ERR_STATE unless - when anything was merged by a search - every page of the real batch and
+ *                               every (query, decoy, page) is merged; lists given through prb_evalset_add_keys alone close
+ *                               as they are.  Both lists are sorted by (query, key), every real hit gets its rank, null_le
+ *                               and the pair of its q-value.  Nothing can be merged after it (a second call does nothing)
+ *   prb_evalset_score           after the close: out[i] for the real hit (query[i], energy[i]), looked up by its key on the
+ *                               device, one copy back.  A key that the query's real list does not hold is an error
+ *   prb_evalset_sizes           the keys in the real and in the decoy list
+ *   prb_evalset_counts          the stage counts of prb_hitset_counts summed over the real batch's pages;
+ *   prb_evalset_decoy_counts    the same over the decoy searches
+ * Every check of a call is made on the host before anything is enqueued: a refused call leaves the table untouched; a merge
+ * that fails part way leaves it unusable.  On the device every kernel checks each record's query, owner and decoy number
+ * against the table's ranges again; a violation - and a looked-up key that is not there - raises the table's `bad` flag,
+ * writes nothing, and this and every later call on the table returns PRB_ERR_STATE.  A table holds pages searched with one
+ * value of distinct_sites and of chain_sites (a second one is PRB_ERR_ARG).  There is no merge of two evalsets: a batch
+ * belongs to one worker.  Stage timer "eval": the appends (launches = 1 per sub-batch with final hits and per
+ * prb_evalset_add_keys with keys), the close (sorts, counts, ranks, suffix minima) and the look-ups. */
+typedef struct prb_eval_score {
+  int32_t decoys, reserved; /* M; 0 */
+  int64_t null_le, rank;
+  uint32_t q_num, q_den;
+} prb_eval_score;
+#ifdef __cplusplus
+static_assert(sizeof(prb_eval_score) == 32, "prb_eval_score: no padding");
+#endif
+typedef struct prb_evalset prb_evalset;
+int prb_evalset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t ndecoys, prb_evalset **out);
+int prb_search_page_scored(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_tophits *tophits,
+                           prb_evalset *es);
+int prb_search_page_null_hits(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *owner,
+                              const int32_t *decoy, prb_evalset *es);
+int prb_evalset_add_keys(prb_ctx *ctx, prb_evalset *es, int32_t is_decoy, const int32_t *query_or_owner, const double *energy, int64_t n);
+int prb_evalset_close(prb_ctx *ctx, prb_evalset *es);
+int prb_evalset_score(prb_ctx *ctx, prb_evalset *es, const int32_t *query, const double *energy, int64_t n, prb_eval_score *out);
+void prb_evalset_sizes(const prb_evalset *es, int64_t *nreal, int64_t *ndecoy);
+void prb_evalset_counts(const prb_evalset *es, int64_t counts[3]);
+void prb_evalset_decoy_counts(const prb_evalset *es, int64_t counts[3]);
+void prb_evalset_free(prb_evalset *es);
 
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered

@@ -88,6 +88,10 @@ GNULL_DTYPE = np.dtype(GROUP_DTYPE.descr + [("decoys", "<i4"), ("pad", "<i4"), (
                                             ("null_min", "<f8")])
 assert GNULL_DTYPE.itemsize == 120
 
+# prb_eval_score: a real hit's place among its query's real hits and among the pooled hits of its decoys (`ris -k N -E M`)
+EVAL_DTYPE = np.dtype([("decoys", "<i4"), ("reserved", "<i4"), ("null_le", "<i8"), ("rank", "<i8"), ("q_num", "<u4"), ("q_den", "<u4")])
+assert EVAL_DTYPE.itemsize == 32
+
 
 class PagePairs(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_void_p), ("npairs", c_i64)]
@@ -234,6 +238,18 @@ SYMBOLS = {
     "prb_gnullset_free": (None, [ctypes.c_void_p]),
     "prb_write_gnull_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                              P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_evalset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_search_page_scored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "prb_search_page_null_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_evalset_add_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, ctypes.c_void_p, c_i64]),
+    "prb_evalset_close": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_evalset_score": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "prb_evalset_sizes": (None, [ctypes.c_void_p, P(c_i64), P(c_i64)]),
+    "prb_evalset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_evalset_decoy_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_evalset_free": (None, [ctypes.c_void_p]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -947,6 +963,63 @@ class GNullSet(_Table):
         """the stage counts of the decoy searches"""
         c = (c_i64 * 3)()
         lib().prb_gnullset_decoy_counts(self.h, c)
+        return tuple(c)
+
+
+class EvalSet(_Table):
+    """prb_evalset: the energy keys of one batch's final hits and of its decoys', pooled per query over the whole database,
+    and per real hit its rank, the decoy hits at or below it and the pair of its FDR q-value.  The real batch is searched
+    page by page (with a TopHits table beside it, if wanted), then its decoys batch by batch; close(); then score().  Close
+    it before its context."""
+    PREFIX = "evalset"
+
+    def __init__(self, ctx, qb, db, ndecoys):
+        h = ctypes.c_void_p()
+        _check(lib().prb_evalset_create(ctx.h, qb.h, db.h, ndecoys, ctypes.byref(h)))
+        self.h, self.ctx, self.qb, self.db = h, ctx, qb, db
+
+    def scored(self, page, opts=None, tophits=None):
+        """prb_search_page_scored: the real batch against `page`, once; tophits: a TopHits table that takes the same hits"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_scored(self.ctx.h, self.qb.h, self.db.h, page, ctypes.byref(o), tophits.h if tophits else None, self.h))
+
+    def null_hits(self, dqb, page, owner, decoy, opts=None):
+        """prb_search_page_null_hits: the batch dqb of decoys against `page`; owner[q] / decoy[q] = the real query and the
+        decoy number of its query q"""
+        o = opts or default_opts()
+        owner, decoy = np.ascontiguousarray(owner, np.int32), np.ascontiguousarray(decoy, np.int32)
+        assert len(owner) == len(decoy) == len(dqb.lens)
+        _check(lib().prb_search_page_null_hits(self.ctx.h, dqb.h, self.db.h, page, ctypes.byref(o), owner.ctypes.data, decoy.ctypes.data,
+                                               self.h))
+
+    def add_keys(self, is_decoy, query_or_owner, energy):
+        """prb_evalset_add_keys: a caller's energies under their queries (real list) or owners (decoy list)"""
+        ids, energy = np.ascontiguousarray(query_or_owner, np.int32), np.ascontiguousarray(energy, np.float64)
+        assert len(ids) == len(energy)
+        _check(lib().prb_evalset_add_keys(self.ctx.h, self.h, int(bool(is_decoy)), ids.ctypes.data if len(ids) else None,
+                                          energy.ctypes.data if len(ids) else None, len(ids)))
+
+    def finish(self):
+        """prb_evalset_close: the lists sorted, every real hit's figures computed; nothing is merged after it"""
+        _check(lib().prb_evalset_close(self.ctx.h, self.h))
+
+    def score(self, query, energy):
+        """prb_evalset_score -> structured array EVAL_DTYPE, one record per (query[i], energy[i])"""
+        query, energy = np.ascontiguousarray(query, np.int32), np.ascontiguousarray(energy, np.float64)
+        assert len(query) == len(energy)
+        out = np.zeros(len(query), EVAL_DTYPE)
+        _check(lib().prb_evalset_score(self.ctx.h, self.h, query.ctypes.data if len(query) else None, energy.ctypes.data if len(query) else None,
+                                       len(query), out.ctypes.data if len(query) else None))
+        return out
+
+    def sizes(self):
+        a, b = c_i64(), c_i64()
+        lib().prb_evalset_sizes(self.h, ctypes.byref(a), ctypes.byref(b))
+        return a.value, b.value
+
+    def decoy_counts(self):
+        c = (c_i64 * 3)()
+        lib().prb_evalset_decoy_counts(self.h, c)
         return tuple(c)
 
 

@@ -1,5 +1,5 @@
-// The protocol of the eight result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip, capi_gnull.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
+// The protocol of the nine result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip, capi_gnull.hip, capi_eval.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
 // search of a page into a table, the merge of one table into another across contexts and devices, and what every
 // prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check comes
 // before a table is touched: a refused call leaves it as it was.
@@ -91,9 +91,11 @@ inline int search_into_table(TableState *t, prb_ctx *ctx, prb_qbatch *qb, prb_db
 }
 
 // ---- prb_search_page_top / _profile / _tophits / _groups: a page searched and merged into a batch table
-// Page `page` searched and merged into the table `t`, finished by `finish_fn`
-inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db,
-                      int32_t page, const prb_ris_opts *opts) {
+// What is checked of the table `t`, finished by `finish_fn`, before `page` is searched and merged into it; a call that
+// passes has the page marked as merged (also prb_search_page_scored, which searches the page into its evalset and hands
+// the sub-batches on to `t`)
+inline int merge_page_guard(const char *fn_name, const char *what, const char *finish_fn, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db,
+                            int32_t page, const prb_ris_opts *opts) {
   const std::string fn = fn_name, table = std::string(what) + " table";
   if (!t) return refuse(fn, "bad argument");
   if (int rc = check_search_args(fn_name, ctx, qb, db, page, opts, 3)) return rc;
@@ -111,6 +113,12 @@ inline int merge_page(const char *fn_name, const char *what, const char *finish_
   }
   if (t->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this " + table);
   t->merged[(size_t)page] = 1;
+  return PRB_OK;
+}
+// Page `page` searched and merged into the table `t`, finished by `finish_fn`
+inline int merge_page(const char *fn_name, const char *what, const char *finish_fn, MergeTable *t, prb_ctx *ctx, prb_qbatch *qb, prb_db *db,
+                      int32_t page, const prb_ris_opts *opts) {
+  if (int rc = merge_page_guard(fn_name, what, finish_fn, t, ctx, qb, db, page, opts)) return rc;
   const int rc = search_into_table(t, ctx, qb, db, page, opts, t->counts);
   if (rc != PRB_OK) t->broken = true;
   return rc;

@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the eight result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset, prb_gnullset): whose they are, whether they can still be merged into, and the block on the device that
+// What the nine result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_gnullset, prb_evalset): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -773,6 +773,61 @@ struct prb_gnullset : prb::TableState {
     for (prb::DevBuf &b : map_dev) b.release();
   }
   ~prb_gnullset() { release(); } // (also on the error paths of prb_gnullset_create)
+};
+
+// prb_evalset_create .. prb_evalset_free: the evalset of one batch against one database (capi_eval.hip): the energy keys
+// of the real batch's final hits and of its decoys', appended sub-batch by sub-batch (append_eval_keys) and closed into
+// sorted segments with every real hit's figures.  It owns all its device memory; `table` is not used.
+struct prb_evalset : prb::TableState {
+  // a list of (key, owner) that grows on the host's side between launches and keeps what it holds; a buffer that is
+  // outgrown is retired, not freed, until the close (hipFree waits for the whole device)
+  struct List {
+    prb::DevBuf key, own; // unsigned long long [cap], uint32_t [cap]
+    int64_t n = 0, cap = 0;
+    std::vector<prb::DevBuf> retired;
+  };
+  const prb_qbatch *qb = nullptr;
+  int32_t nq = 0, ndecoys = 0, npages = 0;
+  List real, dec;
+  std::vector<uint8_t> real_merged;  // per page: the real batch's search is merged
+  std::vector<uint64_t> merged;      // a bit per (page, query, decoy): that decoy's search of the page is merged
+  int64_t nreal_merged = 0, nmerged = 0; // bytes / bits set
+  bool searched = false;             // something came by a search: the close asks for all of it
+  int64_t decoy_counts[3] = {0, 0, 0}; // the stage counts of the decoy searches (`counts`: of the real batch's)
+  bool bad = false;                  // the device's `bad` flag, as the last call left it
+  prb::DevBuf badflag;
+  prb::DevBuf own_map;               // the decoy batch being merged: owner[ndq], then decoy[ndq]
+  int32_t ndq = 0;
+  bool decoy_phase = false;          // ... and that it is one: what take() appends to (prb_search_page_null_hits)
+  prb_tophits *tee = nullptr;        // prb_search_page_scored: the table that the sub-batch is handed on to
+  prb::DevBuf h_ids, h_energy;       // prb_evalset_add_keys / _score: the caller's list
+  prb::DevBuf off, null_le, rank, qnum, qden, out; // the close: roff, doff [nq + 1] each; per real entry; the look-up's records
+  prb::TableFeed feed() const override { return tee && !decoy_phase ? prb::TableFeed::kHitRecords : prb::TableFeed::kHits; }
+  int64_t bp_base() const override { return tee && !decoy_phase ? tee->bp_base() : 0; }
+  int take(const prb::SubBatch &b) override;
+  int64_t triples() const { return (int64_t)npages * (int64_t)nq * (int64_t)ndecoys; }
+  int64_t bit_of(int32_t page, int32_t q, int32_t d) const { return ((int64_t)page * nq + q) * (int64_t)ndecoys + d; }
+  prb::EvalTab view() const {
+    return prb::EvalTab{real.key.as<unsigned long long>(), dec.key.as<unsigned long long>(), off.as<int64_t>(), off.as<int64_t>() + (nq + 1),
+                        null_le.as<uint32_t>(), rank.as<uint32_t>(), qnum.as<uint32_t>(), qden.as<uint32_t>(), badflag.as<uint32_t>(),
+                        real.n, dec.n, nq, ndecoys};
+  }
+  void drop_retired() {
+    for (List *l : {&real, &dec}) {
+      for (prb::DevBuf &b : l->retired) b.release();
+      l->retired.clear();
+    }
+  }
+  // nothing of the table is released while work on it may still be queued on its context's stream
+  void release() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    drop_retired();
+    for (prb::DevBuf *b : {&real.key, &real.own, &dec.key, &dec.own, &badflag, &own_map, &h_ids, &h_energy, &off, &null_le, &rank, &qnum, &qden, &out})
+      b->release();
+  }
+  ~prb_evalset() { release(); } // (also on the error paths of prb_evalset_create)
 };
 
 namespace prb {

@@ -669,4 +669,39 @@ hipError_t launch_gnull_close(const GNullTab &t, hipStream_t s);
 // prb_gnullset_finish: out[k] (prb_gnull_pair) = kept[k] with its counters
 hipError_t launch_gnull_gather(const GNullTab &t, const void *kept, void *out, hipStream_t s);
 
+// ============================================================================ eval_kernels.hip: the evalset
+// (prb_evalset_*)  Two lists of (owner query, energy key) in HBM, the real batch's final hits and its decoys'.  After the
+// close both are sorted by (query, key): rkey / dkey with the queries' segments roff / doff [nq + 1], and per real entry
+// null_le (the decoy keys of its query that are <= its key), rank (the real ones, itself included) and the pair
+// (qnum, qden) of its q-value.  bad: set when a record names a query, an owner or a decoy outside the table, an index of
+// the close lies outside its list, or a looked-up key is not in its query's segment.
+struct EvalTab {
+  const unsigned long long *rkey, *dkey;
+  const int64_t *roff, *doff;
+  uint32_t *null_le, *rank, *qnum, *qden;
+  uint32_t *bad;
+  int64_t nreal, ndecoy;
+  int32_t nq, ndecoys;
+};
+inline constexpr int kEvalChunk = 256; // the entries of a segment that the workgroup of launch_eval_qmin scans at a time
+// energy[i] under ids[i], i < n, appended at key / own (the list's end: the host has made room), a lane per hit.  owner ==
+// nullptr: ids[i] is the owner itself, in [0, nq).  Else ids[i] is a query of a batch of ndq decoys: the owner is
+// owner[ids[i]], and decoy[ids[i]] lies in [0, ndecoys).
+hipError_t launch_eval_append(const int32_t *ids, const double *energy, int64_t n, const int32_t *owner, const int32_t *decoy, int32_t ndq,
+                              int32_t nq, int32_t ndecoys, unsigned long long *key, uint32_t *own, uint32_t *bad, hipStream_t s);
+// prb_evalset_close: v[i] = i;
+hipError_t launch_eval_iota(uint32_t *v, int64_t n, hipStream_t s);
+// ... dst[i] = src[idx[i]] for 4-byte and for 8-byte entries (an index outside [0, n) raises bad);
+hipError_t launch_eval_gather32(const uint32_t *src, const uint32_t *idx, uint32_t *dst, int64_t n, uint32_t *bad, hipStream_t s);
+hipError_t launch_eval_gather64(const unsigned long long *src, const uint32_t *idx, unsigned long long *dst, int64_t n, uint32_t *bad, hipStream_t s);
+// ... cnt[own[i]] += 1 (cnt zeroed by the caller): the queries' segment sizes by counting;
+hipError_t launch_eval_count(const uint32_t *own, int64_t n, int32_t nq, uint32_t *cnt, uint32_t *bad, hipStream_t s);
+// ... rank and null_le of every real entry, a lane each: upper bounds in its own and in its owner's decoy segment;
+hipError_t launch_eval_rank(const EvalTab &t, hipStream_t s);
+// ... the suffix minimum of null_le / rank within every query's segment, from the highest key down, a workgroup per query
+// walking its segment in chunks of kEvalChunk with a wave-level scan and a carry between the chunks
+hipError_t launch_eval_qmin(const EvalTab &t, hipStream_t s);
+// prb_evalset_score: out[i] (prb_eval_score) of the real hit (query[i], energy[i]), a lane each
+hipError_t launch_eval_lookup(const EvalTab &t, const int32_t *query, const double *energy, int64_t n, void *out, hipStream_t s);
+
 } // namespace prb

@@ -80,7 +80,26 @@ inline char *put_names(char *p, int64_t id, const std::string &qname, int32_t ql
   return p;
 }
 
-void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, Buf &b) {
+// in place of a line's newline: ,Decoys,NullLE,Rank,EValue,QValue and the newline (`ris -k N -E M`)
+void put_eval_columns(Buf &b, const prb_eval_score &x) {
+  b.n--; // (the newline)
+  char *p = b.room(200);
+  char *const p0 = p;
+  for (long long f : {(long long)x.decoys, (long long)x.null_le, (long long)x.rank}) {
+    *p++ = ',';
+    p = put_int(p, f);
+  }
+  *p++ = ',';
+  p = put_g(p, (double)x.null_le / (double)x.decoys);
+  *p++ = ',';
+  p = put_g(p, (double)x.q_num / ((double)x.decoys * (double)x.q_den));
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
+// scores (may be null): per page, the score of every hit, printed behind its line
+void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, Buf &b,
+                  const std::vector<const prb_eval_score *> *scores = nullptr) {
   const PageHits &ph = v.pages[pc.p];
   const SeqTable &tab = tabs[pc.p];
   const std::string &qname = v.names[pc.q];
@@ -113,6 +132,7 @@ void format_piece(const Piece &pc, const BatchView &v, const std::vector<SeqTabl
     }
     *p++ = '\n';
     b.n += (size_t)(p - p0);
+    if (scores) put_eval_columns(b, (*scores)[pc.p][i]);
   }
 }
 
@@ -351,6 +371,13 @@ int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int 
   return format_records(
       v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].h[i].query; },
       [&](const Piece &pc, Buf &b) { format_piece(pc, v, tabs, output_style, b); }, id0, sink, threads);
+}
+
+int64_t format_scored_batch(const ScoredView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
+                            int threads) {
+  return format_records(
+      v.nq, v.pages.size(), [&](size_t p) { return v.pages[p].n; }, [&](size_t p, int64_t i) { return v.pages[p].h[i].query; },
+      [&](const Piece &pc, Buf &b) { format_piece(pc, v, tabs, output_style, b, &v.scores); }, id0, sink, threads);
 }
 
 int64_t format_summary_batch(const SummaryView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

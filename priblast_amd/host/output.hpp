@@ -49,6 +49,16 @@ struct LineSink {
 int64_t format_batch(const BatchView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
                      int threads);
 
+// Lines of `ris -k N -E M`: the lines of format_batch, and behind each one the five columns of its hit's score
+// (prb_evalset_score; scores[p][i] belongs to pages[p].h[i]):
+//   ... ,Decoys,NullLE,Rank,EValue,QValue
+// EValue = NullLE / Decoys and QValue = q_num / (Decoys * q_den), in double, six significant digits.
+struct ScoredView : BatchView {
+  std::vector<const prb_eval_score *> scores;
+};
+int64_t format_scored_batch(const ScoredView &v, const std::vector<SeqTable> &tabs, int output_style, int64_t id0, LineSink &sink,
+                            int threads);
+
 // Summary lines of `ris -t` (one per query-target pair, prb_search_page_summary), grouped and numbered the same way:
 //   Id,qname,qlen,dbname,dblen,Hits,MinE,SumE,Eacc,Ehyb,(q0-qN:db0-dbN)
 // energies and the best hit's base-pair field formatted exactly as in the result lines (-s 0 form).

@@ -53,6 +53,10 @@
 // a decoy's minimum over all members of the group against the group's minimum - in a group null table on the GPU
 // (prb_gnullset_*), the decoys searched against the members of each query's kept groups only.  `-P` needs -G and is
 // refused with -z, -k, -q, -r, -c, -b and in rank mode.
+// `ris -k K -E M` scores every `-k` line: the real batch is searched once into the top-N hit table and - the same
+// sub-batches - into an evalset on the GPU (prb_search_page_scored), then M shuffled decoys of each query against the whole
+// database (prb_search_page_null_hits: only their hits' energy keys are kept); the evalset is closed and the kept hits
+// looked up in it (prb_evalset_score).  `-E` needs -k and is refused with -b, -t, -n, -q, -r, -c, -z, -G, -P and in rank mode.
 //
 // How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c have one table (kSwitchTable) that every refusal is generated
 // from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
@@ -163,7 +167,7 @@ void usage() {
             "              PValue = (NullLE + 1) / (INT + 1); lines by query, then page, then target (1 <= INT <= 100000;\n"
             "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
-            "    -Z INT    with -z or -P: the seed of the shuffles [default:1]\n"
+            "    -Z INT    with -z or -P, or with -E: the seed of the shuffles [default:1]\n"
             "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
             "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
             "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
@@ -181,6 +185,15 @@ void usage() {
             "              (1 <= INT <= 100000; with -n, -u, -j, -L and the search options; not with -z, -k, -q, -r, -c, -b, nor\n"
             "              with WORLD_SIZE > 1; PRB_SPLIT has no effect; PRB_NULL_MASK=0: the decoys are searched against every\n"
             "              target - every listed one under -L -, the output is the same)\n"
+            "    -E INT    with -k: an E-value and an FDR q-value per interaction site from INT shuffled decoys of each query, as\n"
+            "              -z makes them, searched against the whole database (under -L: against the query's listed targets)\n"
+            "              and pooled into one null distribution of hit energies per query: behind every -k line the decoys per\n"
+            "              query, the decoy hits at or below the line's interaction energy (NullLE), the query's hits at or\n"
+            "              below it (Rank), EValue = NullLE / INT and QValue = the lowest NullLE / (INT * Rank) over the query's\n"
+            "              hits of this energy or above, at most 1.  There is no decoy mask: -E INT costs about INT + 1\n"
+            "              searches per query, and the pooled null has millions of energies with INT = 5 to 10 - keep INT small\n"
+            "              (1 <= INT <= 100000; with -u, -j, -L, -s and the search options; not with -b, -t, -n, -q, -r, -c, -z,\n"
+            "              -G, -P, nor with WORLD_SIZE > 1; PRB_SPLIT has no effect)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -204,14 +217,14 @@ thread_local bool t_team_thread = false;
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
-// `-t -G -P` the same with the group's null columns.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull };
+// `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored };
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -234,6 +247,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'Z', "the seed of the decoys' shuffles", 0, kZ, false},
     {'G', "one line per query-group pair", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kT, true},
     {'P', "an empirical p-value per query-group pair from N shuffled decoys", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kG, true},
+    {'E', "an E-value and a q-value per interaction site from N pooled decoys per query",
+     bit(kB) | bit(kT) | bit(kN) | bit(kQ) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP), kK, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -245,7 +260,7 @@ struct Args {
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
-  int decoys = 0;                                   // -z or -P, likewise
+  int decoys = 0;                                   // -z, -P or -E, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
   OutputMode mode = OutputMode::kHits;
@@ -271,6 +286,7 @@ struct Free {
   void operator()(prb_nullset *p) const { prb_nullset_free(p); }
   void operator()(prb_groupset *p) const { prb_groupset_free(p); }
   void operator()(prb_gnullset *p) const { prb_gnullset_free(p); }
+  void operator()(prb_evalset *p) const { prb_evalset_free(p); }
 };
 template <class T> using Handle = std::unique_ptr<T, Free>;
 
@@ -286,6 +302,7 @@ struct BatchResult {
   Handle<prb_nullset> null;                    // kNull
   Handle<prb_groupset> groups;                 // kGroups
   Handle<prb_gnullset> gnull;                  // kGroupNull
+  std::vector<prb_eval_score> scores;          // kScored: of the records of `tophits`, in their order
 };
 
 // The result of one batch (in rank mode: of one round of batches, gathered), waiting to be written.
@@ -610,7 +627,7 @@ void check_switches(const Args &a) {
     for (int p = 0; p < kSwitches; p++)
       if (a.given[p] && (kSwitchTable[s].not_with & (1u << p))) die("Error: " + described(s) + " can't be combined with " + described(p));
     // (-Z goes with either switch that makes decoys)
-    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && a.given[kP])) die("Error: " + described(s) + " needs " + described(need));
+    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE]))) die("Error: " + described(s) + " needs " + described(need));
   }
   for (Switch s : {kR, kK, kN})
     if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
@@ -618,10 +635,12 @@ void check_switches(const Args &a) {
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kP] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -P needs an integer between 1 and 100000 (this build's limit)");
+  if (a.given[kE] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -E needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kZSeed] && !a.seed_ok) die("Error: -Z needs a non-negative integer");
 }
 
 OutputMode output_mode(const Args &a) {
+  if (a.given[kE]) return OutputMode::kScored;
   if (a.given[kZ]) return OutputMode::kNull;
   if (a.given[kP]) return OutputMode::kGroupNull;
   if (a.given[kG]) return OutputMode::kGroups;
@@ -633,7 +652,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -660,6 +679,7 @@ Args parse_args(int argc, char **argv) {
     case 'z': a.given[kZ] = true, a.decoys = parse_count(optarg); break;
     case 'G': a.given[kG] = true, a.groupfile = optarg; break;
     case 'P': a.given[kP] = true, a.decoys = parse_count(optarg); break;
+    case 'E': a.given[kE] = true, a.decoys = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -962,6 +982,9 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Decoys, Null Hits, Null LE, "
                     "Null Minimum Energy, P Value\n";
+  case OutputMode::kScored:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
+                    "Interaction Energy, BasePair, Decoys, Null LE, Rank, E Value, Q Value\n";
   case OutputMode::kHits:
   case OutputMode::kTopHits: break;
   }
@@ -998,8 +1021,9 @@ void plan_batches(Run &r) {
 // Whole batches to the workers, or the pages of every batch?  Pages only in one process with two workers or more and
 // a database of two pages or more: when asked for, or - auto - when there are fewer batches than workers.
 void plan_split(Run &r) {
-  // (-z, -P: a batch and its decoys belong to one worker - there is no merge of two null tables)
-  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull && r.a.mode != OutputMode::kGroupNull;
+  // (-z, -P, -E: a batch and its decoys belong to one worker - there is no merge of two null tables or evalsets)
+  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull && r.a.mode != OutputMode::kGroupNull &&
+                   r.a.mode != OutputMode::kScored;
   r.split_pages = can && (r.split_knob == kSplitPages || (r.split_knob == kSplitAuto && r.nb < r.workers.size()));
 }
 
@@ -1081,6 +1105,7 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
   case OutputMode::kCoverage:
   case OutputMode::kNull: // (search_null_batch makes its own)
   case OutputMode::kGroupNull: // (search_gnull_batch)
+  case OutputMode::kScored: // (search_scored_batch)
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -1115,6 +1140,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   }
   case OutputMode::kNull: break; // (search_null_batch)
   case OutputMode::kGroupNull: break; // (search_gnull_batch)
+  case OutputMode::kScored: break; // (search_scored_batch)
   }
   if (rc) die(prb_last_error());
 }
@@ -1139,6 +1165,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
   case OutputMode::kCoverage:
   case OutputMode::kNull:
   case OutputMode::kGroupNull:
+  case OutputMode::kScored:
   case OutputMode::kSummary:
   case OutputMode::kHits: break;
   }
@@ -1352,8 +1379,77 @@ BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
   return res;
 }
 
+// -k K -E M: the real batch against every page, once, into the top-N hit table and an evalset beside it; then its decoys
+// - M shuffles of every query, as -z makes and cuts them - against every page into the evalset's decoy list.  There is no
+// decoy mask: the null is pooled over every target (under -L: over the owner's listed targets, the query's own search
+// space).  The evalset is closed, the table finished, and the kept hits looked up on the device.
+BatchResult search_scored_batch(const Run &r, Worker &w, Prepared &p) {
+  BatchResult res = empty_result(r);
+  const Args &a = r.a;
+  const size_t nq = p.ids.size();
+  prb_tophits *th = nullptr;
+  if (prb_tophits_create(w.ctx, p.qb, a.tophits, &th)) die(prb_last_error());
+  res.tophits.reset(th);
+  prb_evalset *raw = nullptr;
+  if (prb_evalset_create(w.ctx, p.qb, w.db, a.decoys, &raw)) die(prb_last_error());
+  const Handle<prb_evalset> es(raw);
+  prb_ris_opts o = a.o;
+  o.allowed_pairs = p.mask;
+  for (int page = 0; page < r.npages; page++)
+    if (prb_search_page_scored(w.ctx, p.qb, w.db, page, &o, th, es.get())) die(prb_last_error());
+  // the decoys, query by query and decoy by decoy
+  const size_t nd = (size_t)a.decoys, total = nq * nd;
+  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
+    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
+    std::vector<int64_t> off(m + 1, 0);
+    std::vector<int32_t> owner(m), decoy(m), dids(m);
+    for (size_t k = 0; k < m; k++) {
+      owner[k] = (int32_t)((d0 + k) / nd);
+      decoy[k] = (int32_t)((d0 + k) % nd);
+      dids[k] = p.ids[(size_t)owner[k]];
+      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dids[k]].size();
+    }
+    std::string cat((size_t)off[m], '\0');
+    bool shuffled = true;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
+    for (size_t k = 0; k < m; k++) {
+      const std::string &seq = r.seqs[(size_t)dids[k]];
+      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)dids[k], decoy[k], &cat[(size_t)off[k]])) {
+#pragma omp atomic write
+        shuffled = false;
+      }
+    }
+    if (!shuffled) die(std::string("Error: ") + prb_last_error());
+    prb_qbatch *dqb = nullptr;
+    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
+    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
+    prb_ris_opts od = a.o;
+    prb_pairmask *dmask = a.have_pairlist ? batch_mask(r, w.ctx, dqb, w.db, dids) : nullptr;
+    od.allowed_pairs = dmask;
+    for (int page = 0; page < r.npages; page++)
+      if (prb_search_page_null_hits(w.ctx, dqb, w.db, page, &od, owner.data(), decoy.data(), es.get())) die(prb_last_error());
+    prb_pairmask_free(dmask);
+    prb_qbatch_destroy(dqb);
+  }
+  if (prb_evalset_close(w.ctx, es.get())) die(prb_last_error());
+  if (prb_tophits_finish(w.ctx, th)) die(prb_last_error());
+  const prb_top_hit *rec = prb_tophits_hits(th);
+  const int64_t n = prb_tophits_size(th);
+  std::vector<int32_t> lq((size_t)n);
+  std::vector<double> le((size_t)n);
+  for (int64_t i = 0; i < n; i++) {
+    lq[(size_t)i] = rec[i].h.query;
+    le[(size_t)i] = rec[i].h.e_tot;
+  }
+  res.scores.resize((size_t)n);
+  if (prb_evalset_score(w.ctx, es.get(), lq.data(), le.data(), n, res.scores.data())) die(prb_last_error());
+  release_batch(p);
+  return res;
+}
+
 // the search stages of a prepared batch against every page
 BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
+  if (r.a.mode == OutputMode::kScored) return search_scored_batch(r, w, p);
   if (r.a.mode == OutputMode::kNull) return search_null_batch(r, w, p);
   if (r.a.mode == OutputMode::kGroupNull) return search_gnull_batch(r, w, p);
   BatchResult res = empty_result(r);
@@ -1384,7 +1480,9 @@ int64_t write_hits(const Run &r, const BatchView &v, int64_t id, LineSink &sink)
 // The kept hits come by query, then by rank, the pages mixed; the writers take hits page by page, ascending by
 // query, and write a query's hits of one page in the order given.  So the records are cut where a query's next
 // hit lies in a lower page, and every piece goes out as a batch of its own (one piece for a database of one page).
+// -k -E: every record's score (job.res.scores, in the records' order) goes with it, behind its line.
 int64_t write_tophits(const Run &r, const BatchJob &job, int64_t id, LineSink &sink) {
+  const bool scored = job.res.mode == OutputMode::kScored;
   const int npages = r.npages;
   const prb_top_hit *rec = prb_tophits_hits(job.res.tophits.get());
   const int64_t n = prb_tophits_size(job.res.tophits.get());
@@ -1392,12 +1490,15 @@ int64_t write_tophits(const Run &r, const BatchJob &job, int64_t id, LineSink &s
   const int32_t *bp = prb_tophits_basepairs(job.res.tophits.get(), &nbp);
   std::vector<std::vector<prb_hit>> hits((size_t)npages);
   std::vector<std::vector<int32_t>> pairs((size_t)npages);
+  std::vector<std::vector<prb_eval_score>> scores(scored ? (size_t)npages : 0);
+  if (scored && (int64_t)job.res.scores.size() != n) die("Error: the scores of the best hits do not match their records");
   for (int64_t i0 = 0; i0 < n;) {
     int64_t i1 = i0 + 1;
     while (i1 < n && !(rec[i1].h.query == rec[i1 - 1].h.query && rec[i1].page < rec[i1 - 1].page)) i1++;
     const int32_t qa = rec[i0].h.query, qz = rec[i1 - 1].h.query;
     for (auto &h : hits) h.clear();
     for (auto &p : pairs) p.clear();
+    for (auto &s : scores) s.clear();
     for (int64_t i = i0; i < i1; i++) {
       prb_hit x = rec[i].h;
       if (rec[i].page < 0 || rec[i].page >= npages || x.bp_count < 0 || x.bp_offset < 0 || x.bp_offset + x.bp_count > nbp)
@@ -1408,14 +1509,16 @@ int64_t write_tophits(const Run &r, const BatchJob &job, int64_t id, LineSink &s
       x.bp_offset = at;
       x.query -= qa;
       hits[(size_t)rec[i].page].push_back(x);
+      if (scored) scores[(size_t)rec[i].page].push_back(job.res.scores[(size_t)i]);
     }
-    BatchView v;
+    prb::ScoredView v;
     v.nq = (size_t)(qz - qa + 1);
     v.names = job.names.data() + qa;
     v.qlen_unmasked = job.qlen_unmasked.data() + qa;
     for (size_t p = 0; p < hits.size(); p++)
       v.pages.push_back(PageHits{hits[p].data(), (int64_t)hits[p].size(), pairs[p].data(), (int64_t)pairs[p].size() / 2});
-    id = write_hits(r, v, id, sink);
+    for (const auto &s : scores) v.scores.push_back(s.data());
+    id = scored ? written_or_die(prb::format_scored_batch(v, r.tabs, r.a.o.output_style, id, sink, prb::format_threads())) : write_hits(r, v, id, sink);
     i0 = i1;
   }
   return id;
@@ -1432,6 +1535,7 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.n = prb_profset_size(job.res.prof.get());
     return written_or_die(prb::format_profile_batch(v, r.tabs, id, sink, threads));
   }
+  case OutputMode::kScored:
   case OutputMode::kTopHits: return write_tophits(r, job, id, sink);
   case OutputMode::kTop: {
     prb::TopView v;
