@@ -4,6 +4,7 @@ This is plumbing for tests and bench.py; the product is the shared library and t
 `pRIblast-hip` command line.  There is no CPU fallback: if the library is missing it raises,
 and on a machine without a GPU `Context()` raises with the library's error text.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -1036,8 +1037,6 @@ def search_gnull(ctx, qb, seqs, db, group_of_page, ngroups, ndecoys, n=0, seed=1
     way).  decoy_batch: decoys per batch (all at once by default); pages: their order."""
     o = opts or default_opts()
     pages = list(range(db.npages)) if pages is None else list(pages)
-    dseqs, owner, decoy = null_decoys(seqs, ndecoys, seed, file_pos0)
-    step = decoy_batch or len(dseqs)
     with GroupSet(ctx, qb, db, group_of_page, ngroups) as gs:
         for p in pages:
             gs.merge(p, o)
@@ -1047,30 +1046,17 @@ def search_gnull(ctx, qb, seqs, db, group_of_page, ngroups, ndecoys, n=0, seed=1
             for p, m in enumerate(group_of_page):
                 for i, g in enumerate(m):
                     members.setdefault(int(g), []).append((p, i))
-            for i0 in range(0, len(dseqs), step):
-                own, dec = owner[i0:i0 + step], decoy[i0:i0 + step]
-                dqb = QBatch(ctx, dseqs[i0:i0 + step], db.repeat_flag)
-                pm = None
-                try:
-                    dqb.accessibility(db.W, db.delta)
-                    od = RisOpts.from_buffer_copy(o)
-                    od.allowed_pairs = None  # (a caller's mask is for the real batch)
-                    if mask:
-                        pm = PairMask(ctx, dqb, db)
-                        for k in range(len(own)):
-                            tgt = [t for g in kept["group"][kept["query"] == own[k]] for t in members[int(g)]]
-                            if tgt:
-                                pm.allow(np.full(len(tgt), k, np.int32), np.array([t[0] for t in tgt], np.int32),
-                                         np.array([t[1] for t in tgt], np.int32))
-                        od.allowed_pairs = pm.h.value
+
+            def targets(q):
+                tgt = [t for g in kept["group"][kept["query"] == q] for t in members[int(g)]]
+                return np.array([t[0] for t in tgt], np.int32), np.array([t[1] for t in tgt], np.int32)
+
+            with contextlib.closing(_decoy_batches(ctx, seqs, db, ndecoys, seed, file_pos0, o, decoy_batch, targets if mask else None)) as batches:
+                for dqb, own, dec, od in batches:
                     gn.begin(own, dec)
                     for p in pages:
                         gn.merge(dqb, p, od)
                     gn.end()
-                finally:
-                    if pm is not None:
-                        pm.close()
-                    dqb.close()
             return gn.finish()
 
 
@@ -1085,6 +1071,36 @@ def null_decoys(seqs, ndecoys, seed=1, file_pos0=0):
     return dseqs, np.array(owner, np.int32), np.array(decoy, np.int32)
 
 
+def _decoy_batches(ctx, seqs, db, ndecoys, seed, file_pos0, opts, decoy_batch, targets):
+    """The decoys of a batch in batches of decoy_batch (all at once by default): for each, yields the decoy QBatch with its
+    accessibilities computed, its owner and decoy slices, and the options for its searches - opts without the caller's
+    mask, which is for the real batch, and, with targets(q) -> (pages, db_ids), under a PairMask that allows every decoy
+    of query q those targets.  What was made for a batch is closed when the caller comes back for the next one, or closes
+    the generator."""
+    dseqs, owner, decoy = null_decoys(seqs, ndecoys, seed, file_pos0)
+    step = decoy_batch or len(dseqs)
+    for i0 in range(0, len(dseqs), step):
+        own, dec = owner[i0:i0 + step], decoy[i0:i0 + step]
+        dqb = QBatch(ctx, dseqs[i0:i0 + step], db.repeat_flag)
+        pm = None
+        try:
+            dqb.accessibility(db.W, db.delta)
+            od = RisOpts.from_buffer_copy(opts)
+            od.allowed_pairs = None
+            if targets is not None:
+                pm = PairMask(ctx, dqb, db)
+                for k in range(len(own)):
+                    tp, td = targets(own[k])
+                    if len(td):
+                        pm.allow(np.full(len(td), k, np.int32), tp, td)
+                od.allowed_pairs = pm.h.value
+            yield dqb, own, dec, od
+        finally:
+            if pm is not None:
+                pm.close()
+            dqb.close()
+
+
 def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None,
                 with_counts=False):
     """The null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its file)
@@ -1094,40 +1110,26 @@ def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask
     real batch's searches, counts of the decoys')."""
     o = opts or default_opts()
     pages = list(range(db.npages)) if pages is None else list(pages)
-    dseqs, owner, decoy = null_decoys(seqs, ndecoys, seed, file_pos0)
-    step = decoy_batch or len(dseqs)
     with NullSet(ctx, qb, db, ndecoys) as ns:
         observed, counts = [], np.zeros(3, np.int64)
         for p in pages:
             if mask:  # (as the command line: the mask needs the observed triples on the host, the table takes them from there)
                 recs, c = search_page_summary(ctx, qb, db, p, o, with_counts=True)
-                observed.append((p, recs["query"].copy(), recs["db_id"].copy()))
+                observed.append((recs["query"].copy(), np.full(len(recs), p, np.int32), recs["db_id"].copy()))
                 counts += np.array(c, np.int64)
                 ns.observe(p, recs)
             else:
                 ns.observed(p, o)
-        for i0 in range(0, len(dseqs), step):
-            own, dec = owner[i0:i0 + step], decoy[i0:i0 + step]
-            dqb = QBatch(ctx, dseqs[i0:i0 + step], db.repeat_flag)
-            pm = None
-            try:
-                dqb.accessibility(db.W, db.delta)
-                od = RisOpts.from_buffer_copy(o)
-                od.allowed_pairs = None  # (a caller's mask is for the real batch; what it allows is all that is observed)
-                if mask:
-                    pm = PairMask(ctx, dqb, db)
-                    for p, rq, rd in observed:
-                        for k in range(len(own)):
-                            sel = rd[rq == own[k]]
-                            if len(sel):
-                                pm.allow(np.full(len(sel), k, np.int32), np.full(len(sel), p, np.int32), sel)
-                    od.allowed_pairs = pm.h.value
+
+        obs_q, obs_p, obs_d = (np.concatenate([np.zeros(0, np.int32)] + [x[i] for x in observed]) for i in range(3))
+
+        def targets(q):  # (what the real batch's mask allows is all that is observed)
+            return obs_p[obs_q == q], obs_d[obs_q == q]
+
+        with contextlib.closing(_decoy_batches(ctx, seqs, db, ndecoys, seed, file_pos0, o, decoy_batch, targets if mask else None)) as batches:
+            for dqb, own, dec, od in batches:
                 for p in pages:
                     ns.decoys(dqb, p, own, dec, od)
-            finally:
-                if pm is not None:
-                    pm.close()
-                dqb.close()
         recs = ns.finish()
         counts = tuple(int(x) for x in counts) if mask else ns.counts()
         dcounts = ns.decoy_counts()

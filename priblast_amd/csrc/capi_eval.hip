@@ -32,57 +32,6 @@ int page_guard(const std::string &fn, const prb_evalset *es, int32_t page) {
   return PRB_OK;
 }
 
-// A batch of ndq decoys for `page`: every owner and decoy number lies in its range, and no (owner, decoy) comes twice -
-// in the call, or with this page before
-int decoys_guard(const std::string &fn, const prb_evalset *es, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
-  try {
-    std::vector<int64_t> bits((size_t)ndq);
-    for (int32_t i = 0; i < ndq; i++) {
-      if (owner[i] < 0 || owner[i] >= es->nq)
-        return refuse(fn, "owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is out of range (the batch has " +
-                              std::to_string(es->nq) + " queries)");
-      if (decoy[i] < 0 || decoy[i] >= es->ndecoys)
-        return refuse(fn, "decoy[" + std::to_string(i) + "] = " + std::to_string(decoy[i]) + " is out of range (the table has " +
-                              std::to_string(es->ndecoys) + " decoys per query)");
-      bits[(size_t)i] = es->bit_of(page, owner[i], decoy[i]);
-      if ((es->merged[(size_t)(bits[(size_t)i] >> 6)] >> (bits[(size_t)i] & 63)) & 1)
-        return refuse(fn, "decoy " + std::to_string(decoy[i]) + " of query " + std::to_string(owner[i]) + " is already merged for page " +
-                              std::to_string(page));
-    }
-    std::sort(bits.begin(), bits.end());
-    for (size_t i = 1; i < bits.size(); i++)
-      if (bits[i] == bits[i - 1]) {
-        const int64_t od = bits[i] - (int64_t)page * es->nq * (int64_t)es->ndecoys;
-        return refuse(fn, "decoy " + std::to_string(od % es->ndecoys) + " of query " + std::to_string(od / es->ndecoys) + " is given twice");
-      }
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  return PRB_OK;
-}
-
-int selection_guard(const std::string &fn, const prb_evalset *es, const prb_ris_opts *opts) {
-  if (const std::string why = selection_clash("evalset", "holds", es, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
-    return refuse(fn, why);
-  return PRB_OK;
-}
-// opts->allowed_pairs belongs to this search (what search_page would refuse only once the call is under way)
-int mask_guard(const std::string &fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const prb_ris_opts *opts) {
-  const prb_pairmask *pm = opts->allowed_pairs;
-  if (pm && (pm->qb != qb || pm->db != db || pm->nq != qb->nq || pm->tbase.size() != db->pages.size() + 1 || pm->ctx->device != ctx->device))
-    return refuse(fn, "allowed_pairs was made for another query batch, another database or on another device");
-  return PRB_OK;
-}
-
-// the device's `bad` flag to the host (the stream is drained: every call ends with this)
-int fetch_bad(prb_ctx *ctx, prb_evalset *es) {
-  uint32_t flag = 0;
-  PRB_HIP(hipMemcpyAsync(&flag, es->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  es->bad = flag != 0;
-  return PRB_OK;
-}
-
 // room for `more` entries behind the list's end; what it holds moves along.  `fn` names the entry point.
 int reserve(const char *fn, prb_ctx *ctx, prb_evalset::List &l, int64_t more) {
   if (more > kEvalMaxKeys - l.n)
@@ -113,16 +62,6 @@ int reserve(const char *fn, prb_ctx *ctx, prb_evalset::List &l, int64_t more) {
   return PRB_OK;
 }
 
-// the owners and the decoy numbers of the batch being merged, on the device
-int upload_owners(prb_ctx *ctx, prb_evalset *es, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
-  if (int rc = es->own_map.ensure(std::max<size_t>((size_t)ndq * 8, 8))) return rc;
-  es->ndq = ndq;
-  if (!ndq) return PRB_OK;
-  PRB_HIP(hipMemcpyAsync(es->own_map.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(es->own_map.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
-  return PRB_OK;
-}
 // a caller's (identifier, energy) list on the device
 int upload_list(prb_ctx *ctx, prb_evalset *es, const int32_t *ids, const double *energy, int64_t n) {
   int rc;
@@ -145,7 +84,7 @@ static int append_eval_keys(const char *fn, prb_ctx *ctx, prb_evalset *es, bool 
   int rc;
   if ((rc = reserve(fn, ctx, l, n))) return rc;
   if ((rc = ctx->time_begin())) return rc;
-  PRB_HIP(launch_eval_append(ids, energy, n, mapped ? es->own_map.as<int32_t>() : nullptr, mapped ? es->own_map.as<int32_t>() + es->ndq : nullptr,
+  PRB_HIP(launch_eval_append(ids, energy, n, mapped ? es->own.as<int32_t>() : nullptr, mapped ? es->own.as<int32_t>() + es->ndq : nullptr,
                              es->ndq, es->nq, es->ndecoys, l.key.as<unsigned long long>() + l.n, l.own.as<uint32_t>() + l.n,
                              es->badflag.as<uint32_t>(), ctx->stream));
   l.n += n;
@@ -224,7 +163,7 @@ int prb_search_page_scored(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t pag
   if (es->qb != qb || es->nq != qb->nq || es->db != db) return refuse(fn, "the evalset was made for another query batch or another database");
   if (int rc = open_guard(fn, ctx, es)) return rc;
   if (int rc = page_guard(fn, es, page)) return rc;
-  if (int rc = selection_guard(fn, es, opts)) return rc;
+  if (int rc = selection_guard(fn, "evalset", es, opts)) return rc;
   if (int rc = mask_guard(fn, ctx, qb, db, opts)) return rc;
   if (es->real_merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this evalset");
   if (th) { // (its own refusals last: the guard marks the page as merged)
@@ -264,17 +203,13 @@ int prb_search_page_null_hits(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t
   if (es->db != db) return refuse(fn, "the evalset was made for another database");
   if (int rc = open_guard(fn, ctx, es)) return rc;
   if (int rc = page_guard(fn, es, page)) return rc;
-  if (int rc = selection_guard(fn, es, opts)) return rc;
+  if (int rc = selection_guard(fn, "evalset", es, opts)) return rc;
   if (int rc = mask_guard(fn, ctx, dqb, db, opts)) return rc;
-  if (int rc = decoys_guard(fn, es, page, owner, decoy, dqb->nq)) return rc;
+  if (int rc = decoys_guard(fn, es, es->bit0(page), owner, decoy, dqb->nq, " is already merged for page " + std::to_string(page))) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
   es->broken = true; // (until the merge is whole)
   es->searched = true;
-  for (int32_t i = 0; i < dqb->nq; i++) {
-    const int64_t b = es->bit_of(page, owner[i], decoy[i]);
-    es->merged[(size_t)(b >> 6)] |= 1ull << (b & 63);
-  }
-  es->nmerged += dqb->nq;
+  mark_decoys(es, es->bit0(page), owner, decoy, dqb->nq);
   if (int rc = upload_owners(ctx, es, owner, decoy, dqb->nq)) return rc;
   es->decoy_phase = true;
   const int rc = search_into_table(es, ctx, dqb, db, page, opts, es->decoy_counts, false);
@@ -347,7 +282,7 @@ int prb_evalset_close(prb_ctx *ctx, prb_evalset *es) {
   if (es->bad) return refuse(fn, "an index of the close lies outside its list", PRB_ERR_STATE);
   // (only the sorted keys and the real entries' figures are needed from here on)
   es->drop_retired();
-  for (DevBuf *b : {&es->real.own, &es->dec.own, &es->own_map}) b->release();
+  for (DevBuf *b : {&es->real.own, &es->dec.own, &es->own}) b->release();
   es->broken = false;
   es->finished = true;
   return PRB_OK;

@@ -23,41 +23,15 @@ int gnull_guard(const std::string &fn, const prb_ctx *ctx, const prb_gnullset *g
 // ... and a call that merges a page into the open batch
 int page_guard(const std::string &fn, const prb_gnullset *gn, int32_t page) {
   if (!gn->open) return refuse(fn, "no decoy batch is open (prb_gnullset_begin comes first)", PRB_ERR_STATE);
-  if (page < 0 || (size_t)page >= gn->merged.size())
-    return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(gn->merged.size()) + ")");
-  if (gn->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged in the open decoy batch");
+  if (page < 0 || (size_t)page >= gn->page_merged.size())
+    return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(gn->page_merged.size()) + ")");
+  if (gn->page_merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged in the open decoy batch");
   return PRB_OK;
 }
 
-// A caller's list of pair records of `page` (its queries are the open batch's): every record within the table's ranges,
-// and no (query, db_id) twice
-int records_guard(const std::string &fn, const prb_gnullset *gn, int32_t page, const prb_pair_summary *pairs, int64_t n) {
-  const int64_t nseq = (int64_t)gn->map[(size_t)page].size(), ndq = (int64_t)gn->owner.size();
-  try {
-    std::vector<int64_t> keys((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-      const prb_pair_summary &r = pairs[i];
-      if (r.query < 0 || r.query >= ndq || r.db_id < 0 || r.db_id >= nseq || r.hits < 1)
-        return refuse(fn, "pair record " + std::to_string(i) + " is out of range (query " + std::to_string(r.query) + " of " + std::to_string(ndq) +
-                              ", db_id " + std::to_string(r.db_id) + " of " + std::to_string(nseq) + ", hits " + std::to_string(r.hits) + ")");
-      keys[(size_t)i] = (int64_t)r.query * nseq + r.db_id;
-    }
-    std::sort(keys.begin(), keys.end());
-    for (size_t i = 1; i < keys.size(); i++)
-      if (keys[i] == keys[i - 1])
-        return refuse(fn, "the pair (query " + std::to_string(keys[i] / nseq) + ", db_id " + std::to_string(keys[i] % nseq) + ") has two records");
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  return PRB_OK;
-}
-
-// the device's `bad` flag to the host (the stream is drained: every merge ends with this)
-int fetch_bad(prb_ctx *ctx, prb_gnullset *gn, const char *fn) {
-  uint32_t flag = 0;
-  PRB_HIP(hipMemcpyAsync(&flag, gn->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  gn->bad = flag != 0;
+// the device's `bad` flag to the host: raised = the call is refused
+int refuse_if_bad(prb_ctx *ctx, prb_gnullset *gn, const char *fn) {
+  if (int rc = fetch_bad(ctx, gn)) return rc;
   if (gn->bad) return refuse(fn, kBadRecord, PRB_ERR_STATE);
   return PRB_OK;
 }
@@ -72,7 +46,7 @@ static int merge_gnull_pairs(prb_ctx *ctx, prb_gnullset *gn, int32_t page, const
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_gnull_fold(packed, npairs, gn->view(), gn->page_view((size_t)page), ctx->stream));
   if ((rc = ctx->time_end(ModeTimer::kGnull, 1))) return rc;
-  return fetch_bad(ctx, gn, "prb_search_page_gnull");
+  return refuse_if_bad(ctx, gn, "prb_search_page_gnull");
 }
 int prb_gnullset::take(const SubBatch &b) { return merge_gnull_pairs(ctx, this, b.page, b.records, b.npairs); }
 
@@ -93,7 +67,7 @@ int prb::keep_group_records(prb_ctx *ctx, prb_gnullset *gn, prb_groupset *gs, co
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_gnull_keep(recs_dev, gn->view(), gn->kept.p, ctx->stream));
   if ((rc = ctx->time_end(ModeTimer::kGnull, nrec ? 1 : 0))) return rc;
-  if ((rc = fetch_bad(ctx, gn, fn))) return rc;
+  if ((rc = refuse_if_bad(ctx, gn, fn))) return rc;
   gn->map_dev = std::move(gs->map_dev);
   gs->map_dev.clear();
   return PRB_OK;
@@ -117,8 +91,8 @@ int prb_gnullset_create(prb_ctx *ctx, prb_groupset *gs, int32_t n, int32_t ndeco
       return refuse(fn, "page " + std::to_string(p) + " is not merged into the group table: the real batch against every page comes first", PRB_ERR_STATE);
   try {
     gn->map = gs->map;
-    gn->merged.assign(gs->map.size(), 0);
-    gn->closed.assign((size_t)(((int64_t)gs->nq * ndecoys + 63) / 64), 0);
+    gn->page_merged.assign(gs->map.size(), 0);
+    gn->merged.assign((size_t)(((int64_t)gs->nq * ndecoys + 63) / 64), 0);
   } catch (const std::exception &e) {
     return refuse(fn, e.what(), PRB_ERR_NOMEM);
   }
@@ -139,26 +113,7 @@ int prb_gnullset_begin(prb_ctx *ctx, prb_gnullset *gn, const int32_t *owner, con
   if (int rc = gnull_guard(fn, ctx, gn)) return rc;
   if (ndq < 1 || !owner || !decoy) return refuse(fn, "bad argument (a batch has one decoy at least)");
   if (gn->open) return refuse(fn, "a decoy batch is open (prb_gnullset_end comes first)", PRB_ERR_STATE);
-  try {
-    std::vector<int64_t> bits((size_t)ndq);
-    for (int32_t i = 0; i < ndq; i++) {
-      if (owner[i] < 0 || owner[i] >= gn->nq)
-        return refuse(fn, "owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is out of range (the batch has " +
-                              std::to_string(gn->nq) + " queries)");
-      if (decoy[i] < 0 || decoy[i] >= gn->ndecoys)
-        return refuse(fn, "decoy[" + std::to_string(i) + "] = " + std::to_string(decoy[i]) + " is out of range (the table has " +
-                              std::to_string(gn->ndecoys) + " decoys per query)");
-      bits[(size_t)i] = (int64_t)owner[i] * gn->ndecoys + decoy[i];
-      if ((gn->closed[(size_t)(bits[(size_t)i] >> 6)] >> (bits[(size_t)i] & 63)) & 1)
-        return refuse(fn, "decoy " + std::to_string(decoy[i]) + " of query " + std::to_string(owner[i]) + " belongs to a batch closed before");
-    }
-    std::sort(bits.begin(), bits.end());
-    for (size_t i = 1; i < bits.size(); i++)
-      if (bits[i] == bits[i - 1])
-        return refuse(fn, "decoy " + std::to_string(bits[i] % gn->ndecoys) + " of query " + std::to_string(bits[i] / gn->ndecoys) + " is given twice");
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
+  if (int rc = decoys_guard(fn, gn, 0, owner, decoy, ndq, " belongs to a batch closed before")) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
   // the scratch: every cell is empty between two batches (the close empties what it counts), so only new memory is filled
@@ -170,9 +125,7 @@ int prb_gnullset_begin(prb_ctx *ctx, prb_gnullset *gn, const int32_t *owner, con
     return refuse(fn, "can't allocate the scratch of the decoy batch (" + std::to_string(bytes >> 20) + " MB of HBM for " + std::to_string(ndq) +
                           " decoys x " + std::to_string(gn->ngroups) + " groups); open smaller batches",
                   PRB_ERR_NOMEM);
-  PRB_HIP(hipMemcpyAsync(gn->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(gn->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
+  if (int rc = upload_owners(ctx, gn, owner, decoy, ndq)) return rc; // (the room is there)
   try {
     gn->owner.assign(owner, owner + ndq);
     gn->decoy.assign(decoy, decoy + ndq);
@@ -181,7 +134,7 @@ int prb_gnullset_begin(prb_ctx *ctx, prb_gnullset *gn, const int32_t *owner, con
     gn->decoy.clear();
     return refuse(fn, e.what(), PRB_ERR_NOMEM);
   }
-  std::fill(gn->merged.begin(), gn->merged.end(), 0);
+  std::fill(gn->page_merged.begin(), gn->page_merged.end(), 0);
   gn->open = true;
   return PRB_OK;
 }
@@ -195,13 +148,10 @@ int prb_search_page_gnull(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t pag
   if (int rc = page_guard(fn, gn, page)) return rc;
   if ((size_t)dqb->nq != gn->owner.size())
     return refuse(fn, "the open decoy batch has " + std::to_string(gn->owner.size()) + " decoys; this query batch has " + std::to_string(dqb->nq));
-  if (const std::string why = selection_clash("group null table", "holds", gn, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
-    return refuse(fn, why);
-  if (const prb_pairmask *pm = opts->allowed_pairs;
-      pm && (pm->qb != dqb || pm->db != db || pm->nq != dqb->nq || pm->tbase.size() != db->pages.size() + 1 || pm->ctx->device != ctx->device))
-    return refuse(fn, "allowed_pairs was made for another query batch, another database or on another device");
+  if (int rc = selection_guard(fn, "group null table", gn, opts)) return rc;
+  if (int rc = mask_guard(fn, ctx, dqb, db, opts)) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
-  gn->merged[(size_t)page] = 1;
+  gn->page_merged[(size_t)page] = 1;
   gn->broken = true; // (until the merge is whole)
   if (int rc = search_into_table(gn, ctx, dqb, db, page, opts, gn->counts)) return rc;
   gn->broken = false;
@@ -213,16 +163,13 @@ int prb_gnullset_add_pairs(prb_ctx *ctx, prb_gnullset *gn, int32_t page, const p
   if (n < 0 || n > INT32_MAX || (n && !pairs)) return refuse(fn, "bad argument");
   if (int rc = gnull_guard(fn, ctx, gn)) return rc;
   if (int rc = page_guard(fn, gn, page)) return rc;
-  if (int rc = records_guard(fn, gn, page, pairs, n)) return rc;
+  if (int rc = records_guard(fn, (int64_t)gn->map[(size_t)page].size(), (int64_t)gn->owner.size(), pairs, n)) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
-  gn->merged[(size_t)page] = 1;
+  gn->page_merged[(size_t)page] = 1;
   if (!n) return PRB_OK; // (decoys without a hit in the page: it is merged)
   gn->broken = true; // (until the merge is whole)
-  const size_t bytes = (size_t)n * sizeof(prb_pair_summary);
-  if (int rc = gn->h_rec.ensure(bytes)) return rc;
-  PRB_HIP(hipMemcpyAsync(gn->h_rec.p, pairs, bytes, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  if (int rc = upload_records(ctx, gn->h_rec, pairs, n)) return rc;
   if (int rc = merge_gnull_pairs(ctx, gn, page, gn->h_rec.p, n)) return rc;
   gn->broken = false;
   return PRB_OK;
@@ -232,8 +179,8 @@ int prb_gnullset_end(prb_ctx *ctx, prb_gnullset *gn) {
   const char *fn = "prb_gnullset_end";
   if (int rc = gnull_guard(fn, ctx, gn)) return rc;
   if (!gn->open) return refuse(fn, "no decoy batch is open", PRB_ERR_STATE);
-  for (size_t p = 0; p < gn->merged.size(); p++)
-    if (!gn->merged[p])
+  for (size_t p = 0; p < gn->page_merged.size(); p++)
+    if (!gn->page_merged[p])
       return refuse(fn, "page " + std::to_string(p) + " is not merged in the open decoy batch: every page comes first", PRB_ERR_STATE);
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
@@ -242,13 +189,9 @@ int prb_gnullset_end(prb_ctx *ctx, prb_gnullset *gn) {
   if ((rc = ctx->time_begin())) return rc;
   PRB_HIP(launch_gnull_close(gn->view(), ctx->stream));
   if ((rc = ctx->time_end(ModeTimer::kGnull, 1))) return rc;
-  if ((rc = fetch_bad(ctx, gn, fn))) return rc;
+  if ((rc = refuse_if_bad(ctx, gn, fn))) return rc;
   gn->broken = false;
-  for (size_t i = 0; i < gn->owner.size(); i++) {
-    const int64_t b = (int64_t)gn->owner[i] * gn->ndecoys + gn->decoy[i];
-    gn->closed[(size_t)(b >> 6)] |= 1ull << (b & 63);
-  }
-  gn->nclosed += (int64_t)gn->owner.size();
+  mark_decoys(gn, 0, gn->owner.data(), gn->decoy.data(), (int32_t)gn->owner.size());
   gn->owner.clear();
   gn->decoy.clear();
   gn->open = false;
@@ -262,8 +205,8 @@ int prb_gnullset_finish(prb_ctx *ctx, prb_gnullset *gn) {
   if (gn->finished) return PRB_OK; // (the records are on the host already)
   if (gn->bad) return refuse(fn, kBadRecord, PRB_ERR_STATE);
   if (gn->open) return refuse(fn, "a decoy batch is open (prb_gnullset_end comes first)", PRB_ERR_STATE);
-  if (gn->nclosed != gn->decoys_all())
-    return refuse(fn, std::to_string(gn->nclosed) + " of " + std::to_string(gn->decoys_all()) + " (query, decoy) pairs are closed: every decoy of every query comes first",
+  if (gn->nmerged != gn->decoys_all())
+    return refuse(fn, std::to_string(gn->nmerged) + " of " + std::to_string(gn->decoys_all()) + " (query, decoy) pairs are closed: every decoy of every query comes first",
                   PRB_ERR_STATE);
   gn->pairs.clear();
   PRB_HIP(hipSetDevice(ctx->device));

@@ -10,37 +10,6 @@ namespace {
 const char *const kFinishFn = "prb_groupset_finish";
 const char *const kBadRecord = "a record merged into this group table named a query, a sequence, a page or a group outside it";
 
-// the device's `bad` flag to the host (the stream is drained: every merge ends with this)
-int fetch_bad(prb_ctx *ctx, prb_groupset *gs) {
-  uint32_t flag = 0;
-  PRB_HIP(hipMemcpyAsync(&flag, gs->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  gs->bad = flag != 0;
-  return PRB_OK;
-}
-
-// A caller's list of pair records of `page`: every record within the table's ranges, and no (query, db_id) twice
-int records_guard(const std::string &fn, const prb_groupset *gs, int32_t page, const prb_pair_summary *pairs, int64_t n) {
-  const int64_t nseq = (int64_t)gs->map[(size_t)page].size();
-  try {
-    std::vector<int64_t> keys((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-      const prb_pair_summary &r = pairs[i];
-      if (r.query < 0 || r.query >= gs->nq || r.db_id < 0 || r.db_id >= nseq || r.hits < 1)
-        return refuse(fn, "pair record " + std::to_string(i) + " is out of range (query " + std::to_string(r.query) + " of " + std::to_string(gs->nq) +
-                              ", db_id " + std::to_string(r.db_id) + " of " + std::to_string(nseq) + ", hits " + std::to_string(r.hits) + ")");
-      keys[(size_t)i] = (int64_t)r.query * nseq + r.db_id;
-    }
-    std::sort(keys.begin(), keys.end());
-    for (size_t i = 1; i < keys.size(); i++)
-      if (keys[i] == keys[i - 1])
-        return refuse(fn, "the pair (query " + std::to_string(keys[i] / nseq) + ", db_id " + std::to_string(keys[i] % nseq) + ") has two records");
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  return PRB_OK;
-}
-
 // a group table back to empty, on its own device and stream
 int clear_group_table(prb_groupset &gs) {
   PRB_HIP(hipSetDevice(gs.ctx->device));
@@ -195,16 +164,13 @@ int prb_groupset_add_pairs(prb_ctx *ctx, prb_groupset *gs, int32_t page, const p
   if (page < 0 || (size_t)page >= gs->merged.size())
     return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(gs->merged.size()) + ")");
   if (gs->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this group table");
-  if (int rc = records_guard(fn, gs, page, pairs, n)) return rc;
+  if (int rc = records_guard(fn, (int64_t)gs->map[(size_t)page].size(), gs->nq, pairs, n)) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
   gs->merged[(size_t)page] = 1;
   if (!n) return PRB_OK;
   gs->broken = true; // (until the merge is whole)
-  const size_t bytes = (size_t)n * sizeof(prb_pair_summary);
-  if (int rc = gs->h_rec.ensure(bytes)) return rc;
-  PRB_HIP(hipMemcpyAsync(gs->h_rec.p, pairs, bytes, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  if (int rc = upload_records(ctx, gs->h_rec, pairs, n)) return rc;
   if (int rc = merge_group_pairs(ctx, gs, page, gs->h_rec.p, n)) return rc;
   gs->broken = false;
   return PRB_OK;

@@ -27,109 +27,16 @@ int observed_guard(const std::string &fn, const prb_nullset *ns, int32_t page) {
   return PRB_OK;
 }
 
-// A batch of ndq decoys for `page`: the page is observed, every owner and decoy number lies in its range, and no (owner,
-// decoy) comes twice - in the call, or with this page before
-int decoys_guard(const std::string &fn, const prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+// A batch of ndq decoys for `page`: the page is observed, and the batch is new to the page (decoys_guard over the page's bits)
+int decoy_batch_guard(const std::string &fn, const prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
   if (!ns->observed[(size_t)page])
     return refuse(fn, "page " + std::to_string(page) + " is not observed yet (the real batch's search comes first)", PRB_ERR_STATE);
-  try {
-    std::vector<int64_t> bits((size_t)ndq);
-    for (int32_t i = 0; i < ndq; i++) {
-      if (owner[i] < 0 || owner[i] >= ns->nq)
-        return refuse(fn, "owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is out of range (the batch has " +
-                              std::to_string(ns->nq) + " queries)");
-      if (decoy[i] < 0 || decoy[i] >= ns->ndecoys)
-        return refuse(fn, "decoy[" + std::to_string(i) + "] = " + std::to_string(decoy[i]) + " is out of range (the table has " +
-                              std::to_string(ns->ndecoys) + " decoys per query)");
-      bits[(size_t)i] = ns->bit_of(page, owner[i], decoy[i]);
-      if ((ns->merged[(size_t)(bits[(size_t)i] >> 6)] >> (bits[(size_t)i] & 63)) & 1)
-        return refuse(fn, "decoy " + std::to_string(decoy[i]) + " of query " + std::to_string(owner[i]) + " is already merged for page " +
-                              std::to_string(page));
-    }
-    std::sort(bits.begin(), bits.end());
-    for (size_t i = 1; i < bits.size(); i++)
-      if (bits[i] == bits[i - 1]) {
-        const int64_t od = bits[i] - (int64_t)page * ns->nq * (int64_t)ns->ndecoys;
-        return refuse(fn, "decoy " + std::to_string(od % ns->ndecoys) + " of query " + std::to_string(od / ns->ndecoys) + " is given twice");
-      }
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  return PRB_OK;
-}
-void mark_decoys(prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
-  for (int32_t i = 0; i < ndq; i++) {
-    const int64_t b = ns->bit_of(page, owner[i], decoy[i]);
-    ns->merged[(size_t)(b >> 6)] |= 1ull << (b & 63);
-  }
-  ns->nmerged += ndq;
+  return decoys_guard(fn, ns, ns->bit0(page), owner, decoy, ndq, " is already merged for page " + std::to_string(page));
 }
 
-// A caller's list of pair records of `page` (its queries below nq_list): every record within the table's ranges, and no
-// (query, db_id) twice
-int records_guard(const std::string &fn, const prb_nullset *ns, int32_t page, int32_t nq_list, const prb_pair_summary *pairs, int64_t n) {
-  const int64_t nseq = ns->tbase[(size_t)page + 1] - ns->tbase[(size_t)page];
-  try {
-    std::vector<int64_t> keys((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-      const prb_pair_summary &r = pairs[i];
-      if (r.query < 0 || r.query >= nq_list || r.db_id < 0 || r.db_id >= nseq || r.hits < 1)
-        return refuse(fn, "pair record " + std::to_string(i) + " is out of range (query " + std::to_string(r.query) + " of " + std::to_string(nq_list) +
-                              ", db_id " + std::to_string(r.db_id) + " of " + std::to_string(nseq) + ", hits " + std::to_string(r.hits) + ")");
-      keys[(size_t)i] = (int64_t)r.query * nseq + r.db_id;
-    }
-    std::sort(keys.begin(), keys.end());
-    for (size_t i = 1; i < keys.size(); i++)
-      if (keys[i] == keys[i - 1])
-        return refuse(fn, "the pair (query " + std::to_string(keys[i] / nseq) + ", db_id " + std::to_string(keys[i] % nseq) + ") has two records");
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  return PRB_OK;
-}
-
-// the options' selection against the table's (one value of distinct_sites / chain_sites per table)
-int selection_guard(const std::string &fn, const prb_nullset *ns, const prb_ris_opts *opts) {
-  if (const std::string why = selection_clash("null table", "holds", ns, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
-    return refuse(fn, why);
-  return PRB_OK;
-}
-
-// opts->allowed_pairs belongs to this search (what search_page would refuse only once the call is under way)
-int mask_guard(const std::string &fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const prb_ris_opts *opts) {
-  const prb_pairmask *pm = opts->allowed_pairs;
-  if (pm && (pm->qb != qb || pm->db != db || pm->nq != qb->nq || pm->tbase.size() != db->pages.size() + 1 || pm->ctx->device != ctx->device))
-    return refuse(fn, "allowed_pairs was made for another query batch, another database or on another device");
-  return PRB_OK;
-}
-
-// the device's `bad` flag to the host (the stream is drained: every merge ends with this)
-int fetch_bad(prb_ctx *ctx, prb_nullset *ns) {
-  uint32_t flag = 0;
-  PRB_HIP(hipMemcpyAsync(&flag, ns->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  ns->bad = flag != 0;
-  return PRB_OK;
-}
-
-// the owners and the decoy numbers of the batch being merged, on the device
-int upload_owners(prb_ctx *ctx, prb_nullset *ns, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
-  if (int rc = ns->own.ensure(std::max<size_t>((size_t)ndq * 8, 8))) return rc;
-  ns->ndq = ndq;
-  if (!ndq) return PRB_OK;
-  PRB_HIP(hipMemcpyAsync(ns->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(ns->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
-  return PRB_OK;
-}
-// a caller's records on the device
-int upload_records(prb_ctx *ctx, prb_nullset *ns, const prb_pair_summary *pairs, int64_t n) {
-  const size_t bytes = (size_t)n * sizeof(prb_pair_summary);
-  if (int rc = ns->h_rec.ensure(std::max<size_t>(bytes, 8))) return rc;
-  if (!n) return PRB_OK;
-  PRB_HIP(hipMemcpyAsync(ns->h_rec.p, pairs, bytes, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
-  return PRB_OK;
+// A caller's list of pair records of `page` (its queries below nq_list)
+int page_list_guard(const std::string &fn, const prb_nullset *ns, int32_t page, int32_t nq_list, const prb_pair_summary *pairs, int64_t n) {
+  return records_guard(fn, ns->tbase[(size_t)page + 1] - ns->tbase[(size_t)page], nq_list, pairs, n);
 }
 
 } // namespace
@@ -170,6 +77,7 @@ int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int
     ns->tbase.assign(db->pages.size() + 1, 0);
     for (size_t p = 0; p < db->pages.size(); p++) ns->tbase[p + 1] = ns->tbase[p] + db->pages[p].nseq;
     ns->observed.assign(db->pages.size(), 0);
+    ns->npages = (int32_t)db->pages.size();
     ns->nq = qb->nq;
     ns->ndecoys = ndecoys;
     ns->merged.assign((size_t)((ns->triples() + 63) / 64), 0);
@@ -202,7 +110,7 @@ int prb_search_page_observed(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t p
   if (int rc = check_search_args(fn, ctx, qb, db, page, opts, 3)) return rc;
   if (ns->qb != qb || ns->nq != qb->nq || ns->db != db) return refuse(fn, "the null table was made for another query batch or another database");
   if (int rc = null_guard(fn, ctx, ns, page)) return rc;
-  if (int rc = selection_guard(fn, ns, opts)) return rc;
+  if (int rc = selection_guard(fn, "null table", ns, opts)) return rc;
   if (int rc = mask_guard(fn, ctx, qb, db, opts)) return rc;
   if (int rc = observed_guard(fn, ns, page)) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
@@ -220,12 +128,12 @@ int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t pa
   if (int rc = check_search_args(fn, ctx, dqb, db, page, opts, 3)) return rc;
   if (ns->db != db) return refuse(fn, "the null table was made for another database");
   if (int rc = null_guard(fn, ctx, ns, page)) return rc;
-  if (int rc = selection_guard(fn, ns, opts)) return rc;
+  if (int rc = selection_guard(fn, "null table", ns, opts)) return rc;
   if (int rc = mask_guard(fn, ctx, dqb, db, opts)) return rc;
-  if (int rc = decoys_guard(fn, ns, page, owner, decoy, dqb->nq)) return rc;
+  if (int rc = decoy_batch_guard(fn, ns, page, owner, decoy, dqb->nq)) return rc;
   PRB_HIP(hipSetDevice(ctx->device));
   ns->broken = true; // (until the merge is whole)
-  mark_decoys(ns, page, owner, decoy, dqb->nq);
+  mark_decoys(ns, ns->bit0(page), owner, decoy, dqb->nq);
   if (int rc = upload_owners(ctx, ns, owner, decoy, dqb->nq)) return rc;
   ns->decoy_phase = true;
   const int rc = search_into_table(ns, ctx, dqb, db, page, opts, ns->decoy_counts, false);
@@ -240,13 +148,13 @@ int prb_nullset_observe(prb_ctx *ctx, prb_nullset *ns, int32_t page, const prb_p
   if (n < 0 || n > INT32_MAX || (n && !pairs)) return refuse(fn, "bad argument");
   if (int rc = null_guard(fn, ctx, ns, page)) return rc;
   if (int rc = observed_guard(fn, ns, page)) return rc;
-  if (int rc = records_guard(fn, ns, page, ns->nq, pairs, n)) return rc;
+  if (int rc = page_list_guard(fn, ns, page, ns->nq, pairs, n)) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
   ns->observed[(size_t)page] = 1;
   if (!n) return PRB_OK;
   ns->broken = true; // (until the merge is whole)
-  if (int rc = upload_records(ctx, ns, pairs, n)) return rc;
+  if (int rc = upload_records(ctx, ns->h_rec, pairs, n)) return rc;
   if (int rc = merge_null_observed(ctx, ns, page, ns->h_rec.p, n)) return rc;
   ns->broken = false;
   return PRB_OK;
@@ -257,15 +165,15 @@ int prb_nullset_add_pairs(prb_ctx *ctx, prb_nullset *ns, int32_t page, const int
   const char *fn = "prb_nullset_add_pairs";
   if (nq < 0 || (nq && (!owner || !decoy)) || n < 0 || n > INT32_MAX || (n && !pairs)) return refuse(fn, "bad argument");
   if (int rc = null_guard(fn, ctx, ns, page)) return rc;
-  if (int rc = decoys_guard(fn, ns, page, owner, decoy, nq)) return rc;
-  if (int rc = records_guard(fn, ns, page, nq, pairs, n)) return rc;
+  if (int rc = decoy_batch_guard(fn, ns, page, owner, decoy, nq)) return rc;
+  if (int rc = page_list_guard(fn, ns, page, nq, pairs, n)) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
-  mark_decoys(ns, page, owner, decoy, nq);
+  mark_decoys(ns, ns->bit0(page), owner, decoy, nq);
   if (!n) return PRB_OK; // (decoys without a hit: they are merged)
   ns->broken = true; // (until the merge is whole)
   if (int rc = upload_owners(ctx, ns, owner, decoy, nq)) return rc;
-  if (int rc = upload_records(ctx, ns, pairs, n)) return rc;
+  if (int rc = upload_records(ctx, ns->h_rec, pairs, n)) return rc;
   if (int rc = merge_null_decoys(ctx, ns, page, ns->h_rec.p, n)) return rc;
   ns->broken = false;
   return PRB_OK;

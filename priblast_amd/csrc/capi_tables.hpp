@@ -1,8 +1,10 @@
 // The protocol of the nine result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip, capi_gnull.hip, capi_eval.hip): what a prb_*_create starts with, what is checked before a page or another table is merged, the
-// search of a page into a table, the merge of one table into another across contexts and devices, and what every
-// prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check comes
-// before a table is touched: a refused call leaves it as it was.
+// capi_groups.hip, capi_gnull.hip, capi_eval.hip): what a prb_*_create starts with, what is checked before a page, a
+// caller's list, a batch of decoys or another table is merged, the search of a page into a table, the uploads of a
+// caller's arrays, the device's `bad` flag, the merge of one table into another across contexts and devices, and what
+// every prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check
+// comes before a table is touched: a refused call leaves it as it was.  The per-table files keep what is theirs alone:
+// their own state checks, their kernels' launches and their create and finish.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -71,6 +73,20 @@ inline std::string selection_clash(const std::string &tables, const char *holds,
     return "the " + tables + " " + holds + " pages searched with chain_sites " + std::to_string(t->chain) + other_open + std::to_string(chain) +
            other_close;
   return "";
+}
+
+// the options of a page search against the selection of the table it goes into (`table`: "null table", "evalset", ...)
+inline int selection_guard(const std::string &fn, const char *table, const TableState *t, const prb_ris_opts *opts) {
+  if (const std::string why = selection_clash(table, "holds", t, opts->distinct_sites, opts->chain_sites, " (this call: ", ")"); !why.empty())
+    return refuse(fn, why);
+  return PRB_OK;
+}
+// opts->allowed_pairs belongs to this search (what search_page would refuse only once the call is under way)
+inline int mask_guard(const std::string &fn, const prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, const prb_ris_opts *opts) {
+  const prb_pairmask *pm = opts->allowed_pairs;
+  if (pm && (pm->qb != qb || pm->db != db || pm->nq != qb->nq || pm->tbase.size() != db->pages.size() + 1 || pm->ctx->device != ctx->device))
+    return refuse(fn, "allowed_pairs was made for another query batch, another database or on another device");
+  return PRB_OK;
 }
 
 // ---- every prb_search_page_* of a table, behind its guards
@@ -169,6 +185,94 @@ inline int merge_run_page(const char *fn_name, const char *what, const char *fin
   if ((rc = upload_ids(ctx, t, query_ids, qb->nq))) return rc;
   if ((rc = search_into_table(t, ctx, qb, db, page, opts, t->counts))) return rc;
   t->broken = false;
+  return PRB_OK;
+}
+
+// ---- prb_*_add_pairs / prb_nullset_observe: a caller's list of pair records merged like a page's
+// The list against a page of nseq sequences and a batch of nq queries: every record within those ranges and with a hit,
+// and no (query, db_id) twice
+inline int records_guard(const std::string &fn, int64_t nseq, int64_t nq, const prb_pair_summary *pairs, int64_t n) {
+  try {
+    std::vector<int64_t> keys((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+      const prb_pair_summary &r = pairs[i];
+      if (r.query < 0 || r.query >= nq || r.db_id < 0 || r.db_id >= nseq || r.hits < 1)
+        return refuse(fn, "pair record " + std::to_string(i) + " is out of range (query " + std::to_string(r.query) + " of " + std::to_string(nq) +
+                              ", db_id " + std::to_string(r.db_id) + " of " + std::to_string(nseq) + ", hits " + std::to_string(r.hits) + ")");
+      keys[(size_t)i] = (int64_t)r.query * nseq + r.db_id;
+    }
+    std::sort(keys.begin(), keys.end());
+    for (size_t i = 1; i < keys.size(); i++)
+      if (keys[i] == keys[i - 1])
+        return refuse(fn, "the pair (query " + std::to_string(keys[i] / nseq) + ", db_id " + std::to_string(keys[i] % nseq) + ") has two records");
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  return PRB_OK;
+}
+// ... and on the device (the current one), in the table's `h_rec`
+inline int upload_records(prb_ctx *ctx, DevBuf &h_rec, const prb_pair_summary *pairs, int64_t n) {
+  const size_t bytes = (size_t)n * sizeof(prb_pair_summary);
+  if (int rc = h_rec.ensure(std::max<size_t>(bytes, 8))) return rc;
+  if (!n) return PRB_OK;
+  PRB_HIP(hipMemcpyAsync(h_rec.p, pairs, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
+  return PRB_OK;
+}
+
+// ---- a batch of decoys merged into a table that keeps a bit per decoy (DecoySet, search_host.hpp)
+// The ndq decoys decoy[i] of the queries owner[i], their bits counted from bit0 on: every owner and decoy number lies in
+// its range, and no (owner, decoy) comes twice - before (`already`: how that message ends), or in the call
+inline int decoys_guard(const std::string &fn, const DecoySet *t, int64_t bit0, const int32_t *owner, const int32_t *decoy, int32_t ndq,
+                        const std::string &already) {
+  try {
+    std::vector<int64_t> bits((size_t)ndq);
+    for (int32_t i = 0; i < ndq; i++) {
+      if (owner[i] < 0 || owner[i] >= t->nq)
+        return refuse(fn, "owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is out of range (the batch has " +
+                              std::to_string(t->nq) + " queries)");
+      if (decoy[i] < 0 || decoy[i] >= t->ndecoys)
+        return refuse(fn, "decoy[" + std::to_string(i) + "] = " + std::to_string(decoy[i]) + " is out of range (the table has " +
+                              std::to_string(t->ndecoys) + " decoys per query)");
+      bits[(size_t)i] = t->bit_of(bit0, owner[i], decoy[i]);
+      if ((t->merged[(size_t)(bits[(size_t)i] >> 6)] >> (bits[(size_t)i] & 63)) & 1)
+        return refuse(fn, "decoy " + std::to_string(decoy[i]) + " of query " + std::to_string(owner[i]) + already);
+    }
+    std::sort(bits.begin(), bits.end());
+    for (size_t i = 1; i < bits.size(); i++)
+      if (bits[i] == bits[i - 1])
+        return refuse(fn, "decoy " + std::to_string((bits[i] - bit0) % t->ndecoys) + " of query " + std::to_string((bits[i] - bit0) / t->ndecoys) +
+                              " is given twice");
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  return PRB_OK;
+}
+// ... behind the guard: their bits set
+inline void mark_decoys(DecoySet *t, int64_t bit0, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+  for (int32_t i = 0; i < ndq; i++) {
+    const int64_t b = t->bit_of(bit0, owner[i], decoy[i]);
+    t->merged[(size_t)(b >> 6)] |= 1ull << (b & 63);
+  }
+  t->nmerged += ndq;
+}
+// ... and their owners and decoy numbers on the device (the current one)
+inline int upload_owners(prb_ctx *ctx, DecoySet *t, const int32_t *owner, const int32_t *decoy, int32_t ndq) {
+  if (int rc = t->own.ensure(std::max<size_t>((size_t)ndq * 8, 8))) return rc;
+  t->ndq = ndq;
+  if (!ndq) return PRB_OK;
+  PRB_HIP(hipMemcpyAsync(t->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(t->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
+  return PRB_OK;
+}
+
+// ---- the device's `bad` flag to the host, in t->bad (the stream is drained: every merge of such a table ends with this)
+inline int fetch_bad(prb_ctx *ctx, TableState *t) {
+  uint32_t flag = 0;
+  PRB_HIP(hipMemcpyAsync(&flag, t->badflag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  t->bad = flag != 0;
   return PRB_OK;
 }
 

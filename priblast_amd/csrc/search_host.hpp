@@ -465,6 +465,16 @@ struct TableState {
   int32_t chain = -1;          // opts->chain_sites of the merged pages, likewise
   int64_t counts[3] = {0, 0, 0};
   DevBuf table;                // the table proper, one block (every table says what it holds)
+  bool bad = false;            // the device's `bad` flag, as the last call left it (fetch_bad, capi_tables.hpp) - of the
+  DevBuf badflag;              // tables that keep one of their own: prb_nullset, prb_groupset, prb_gnullset, prb_evalset
+  // What their release() starts with - nothing of such a table is released while work on it may still be queued on its
+  // context's stream: false = there is no context yet, and so nothing to release
+  bool quiesce() const {
+    if (!ctx) return false;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    return true;
+  }
 };
 
 // The tables that a batch's pages are merged into one by one (prb_topset, prb_profset, prb_tophits): a byte per page
@@ -491,6 +501,29 @@ struct RunTable : TableState {
     if (((size_t)id >> 6) >= m.size()) m.resize(((size_t)id >> 6) + 1, 0);
     m[(size_t)id >> 6] |= 1ull << (id & 63);
   }
+};
+
+// What the tables that take a batch's decoys keep of them (prb_nullset, prb_evalset, prb_gnullset): a bit per (query,
+// decoy) that is merged - a row of them per page, where the table keeps the pages apart: `bit0` = the bit of (0, 0) in
+// the row - and the batch of decoys being merged, on the device (decoys_guard, mark_decoys, upload_owners, capi_tables.hpp)
+struct DecoySet {
+  int32_t nq = 0, ndecoys = 0;
+  std::vector<uint64_t> merged; // the bits
+  int64_t nmerged = 0;          // ... that are set
+  DevBuf own;                   // the decoy batch being merged: owner[ndq], then decoy[ndq]
+  int32_t ndq = 0;              // ... its number of decoys
+  int64_t decoys_all() const { return (int64_t)nq * ndecoys; }
+  int64_t bit_of(int64_t bit0, int32_t q, int32_t d) const { return bit0 + (int64_t)q * ndecoys + d; }
+};
+// The tables that a batch's decoys are searched into page by page, batch by batch, behind the real batch (prb_nullset,
+// prb_evalset): a bit per (page, query, decoy)
+struct DecoyTable : TableState, DecoySet {
+  const prb_qbatch *qb = nullptr;
+  int32_t npages = 0;
+  int64_t decoy_counts[3] = {0, 0, 0}; // the stage counts of the decoy searches (`counts`: of the real batch's)
+  bool decoy_phase = false;            // the batch being searched is one of decoys: what take() merges (else the real batch)
+  int64_t triples() const { return (int64_t)npages * decoys_all(); }
+  int64_t bit0(int32_t page) const { return (int64_t)page * decoys_all(); }
 };
 
 // What the two span tables own beside their block (prb_profset, prb_covset; capi_spans.hip): per merge the hits in
@@ -667,19 +700,10 @@ struct prb_covset : prb::RunTable, prb::SpanBufs {
 // prb_nullset_create .. prb_nullset_free: the null table of one batch against one database (capi_null.hip), merged into
 // sub-batch by sub-batch - the real batch's pairs page by page first (merge_null_observed), then the pairs of its decoys
 // (merge_null_decoys).  It owns all its device memory; `table` = NullSlot[nq * targets]
-struct prb_nullset : prb::TableState {
-  const prb_qbatch *qb = nullptr;
-  int32_t nq = 0, ndecoys = 0;
+struct prb_nullset : prb::DecoyTable {
   std::vector<int64_t> tbase;        // [npages + 1] the first target of every page; back() = the targets
   std::vector<uint8_t> observed;     // per page: the real batch's search is merged
-  std::vector<uint64_t> merged;      // a bit per (page, query, decoy): that decoy's search of the page is merged
-  int64_t nmerged = 0;               // bits set in `merged`
-  int64_t decoy_counts[3] = {0, 0, 0}; // the stage counts of the decoy searches (`counts`: of the real batch's)
-  bool bad = false;                  // the device's `bad` flag, as the last merge left it
-  prb::DevBuf obs, badflag, tbase_dev; // the selection's flags, the kernels' flag, tbase on the device
-  prb::DevBuf own;                   // the decoy batch being merged: owner[ndq], then decoy[ndq]
-  int32_t ndq = 0;                   // ... its number of decoys
-  bool decoy_phase = false;          // ... and that it is one: what take() merges (else the real batch), prb_search_page_decoys
+  prb::DevBuf obs, tbase_dev;        // the selection's flags, tbase on the device
   prb::DevBuf h_rec;                 // prb_nullset_observe / _add_pairs: the caller's records
   prb::DevBuf sel, out;              // prb_nullset_finish: the observed slots, their records
   std::vector<prb_null_pair> pairs;  // prb_nullset_finish
@@ -687,17 +711,12 @@ struct prb_nullset : prb::TableState {
   int take(const prb::SubBatch &b) override;
   int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
   int64_t slots() const { return (int64_t)nq * targets(); }
-  int64_t triples() const { return (int64_t)observed.size() * (int64_t)nq * (int64_t)ndecoys; }
-  int64_t bit_of(int32_t page, int32_t q, int32_t d) const { return ((int64_t)page * nq + q) * (int64_t)ndecoys + d; }
   prb::NullTab view() const {
     return prb::NullTab{table.as<prb::NullSlot>(), obs.as<uint8_t>(), badflag.as<uint32_t>(), slots(), targets(), nq, ndecoys};
   }
   prb::NullPage page_view(size_t page) const { return prb::NullPage{tbase[page], (int32_t)(tbase[page + 1] - tbase[page])}; }
-  // nothing of the table is released while work on it may still be queued on its context's stream
   void release() {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    if (!quiesce()) return;
     for (prb::DevBuf *b : {&table, &obs, &badflag, &tbase_dev, &own, &h_rec, &sel, &out}) b->release();
   }
   ~prb_nullset() { release(); } // (also on the error paths of prb_nullset_create)
@@ -710,8 +729,6 @@ struct prb_groupset : prb::MergeTable {
   int32_t ngroups = 0;
   std::vector<std::vector<int32_t>> map; // per page: the groups of its sequences (what two tables must share to be merged)
   std::vector<prb::DevBuf> map_dev;      // ... on the device
-  bool bad = false;                      // the device's `bad` flag, as the last call left it
-  prb::DevBuf badflag;
   prb::DevBuf h_rec;                     // prb_groupset_add_pairs: the caller's records
   prb::DevBuf occ, sel, top, keep, out;  // prb_groupset_finish: flags and lists of the selection, the records
   std::vector<prb_group_pair> pairs;     // prb_groupset_finish
@@ -723,11 +740,8 @@ struct prb_groupset : prb::MergeTable {
     return prb::GroupTab{table.as<prb::GroupSlot>(), badflag.as<uint32_t>(), slots(), nq, ngroups, (int32_t)map.size()};
   }
   prb::GroupPage page_view(size_t page) const { return prb::GroupPage{map_dev[page].as<int32_t>(), (int32_t)page, (int32_t)map[page].size()}; }
-  // nothing of the table is released while work on it may still be queued on its context's stream
   void release() {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    if (!quiesce()) return;
     for (prb::DevBuf *b : {&table, &badflag, &h_rec, &occ, &sel, &top, &keep, &out}) b->release();
     for (prb::DevBuf &b : map_dev) b.release();
   }
@@ -739,36 +753,29 @@ struct prb_groupset : prb::MergeTable {
 // in batches between prb_gnullset_begin and prb_gnullset_end; the pages of the open batch are folded into `cell`
 // sub-batch by sub-batch (merge_gnull_pairs).  It owns all its device memory - the page maps are the group table's,
 // taken over when that is finished.  `table` = GNullCount[nkept]
-struct prb_gnullset : prb::TableState {
-  int32_t nq = 0, ngroups = 0, ndecoys = 0;
+struct prb_gnullset : prb::TableState, prb::DecoySet { // (`merged`: a bit per (query, decoy) whose batch is closed, prb_gnullset_end)
+  int32_t ngroups = 0;
   int64_t nkept = 0;
   std::vector<std::vector<int32_t>> map; // per page: the groups of its sequences
   std::vector<prb::DevBuf> map_dev;      // ... on the device
-  std::vector<uint64_t> closed;          // a bit per (query, decoy): its batch is closed (prb_gnullset_end)
-  int64_t nclosed = 0;                   // bits set in `closed`
   bool open = false;                     // between prb_gnullset_begin and prb_gnullset_end
   std::vector<int32_t> owner, decoy;     // the open batch
-  std::vector<uint8_t> merged;           // per page: merged in the open batch
-  bool bad = false;                      // the device's `bad` flag, as the last call left it
-  prb::DevBuf lookup, kept, cell, own, badflag;
+  std::vector<uint8_t> page_merged;      // per page: merged in the open batch
+  prb::DevBuf lookup, kept, cell;
   prb::DevBuf h_rec;                     // prb_gnullset_add_pairs: the caller's records
   prb::DevBuf out;                       // prb_gnullset_finish: the records
   std::vector<prb_gnull_pair> pairs;     // prb_gnullset_finish
   prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
   int take(const prb::SubBatch &b) override;
   int64_t slots() const { return (int64_t)nq * ngroups; }
-  int64_t decoys_all() const { return (int64_t)nq * ndecoys; }
   prb::GNullTab view() const {
     const int32_t ndq = (int32_t)owner.size();
     return prb::GNullTab{lookup.as<uint32_t>(), table.as<prb::GNullCount>(), cell.as<unsigned long long>(), own.as<int32_t>(),
                          own.as<int32_t>() + ndq, badflag.as<uint32_t>(), nkept, nq, ngroups, ndecoys, (int32_t)map.size(), ndq};
   }
   prb::GroupPage page_view(size_t page) const { return prb::GroupPage{map_dev[page].as<int32_t>(), (int32_t)page, (int32_t)map[page].size()}; }
-  // nothing of the table is released while work on it may still be queued on its context's stream
   void release() {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    if (!quiesce()) return;
     for (prb::DevBuf *b : {&table, &lookup, &kept, &cell, &own, &badflag, &h_rec, &out}) b->release();
     for (prb::DevBuf &b : map_dev) b.release();
   }
@@ -778,7 +785,7 @@ struct prb_gnullset : prb::TableState {
 // prb_evalset_create .. prb_evalset_free: the evalset of one batch against one database (capi_eval.hip): the energy keys
 // of the real batch's final hits and of its decoys', appended sub-batch by sub-batch (append_eval_keys) and closed into
 // sorted segments with every real hit's figures.  It owns all its device memory; `table` is not used.
-struct prb_evalset : prb::TableState {
+struct prb_evalset : prb::DecoyTable {
   // a list of (key, owner) that grows on the host's side between launches and keeps what it holds; a buffer that is
   // outgrown is retired, not freed, until the close (hipFree waits for the whole device)
   struct List {
@@ -786,27 +793,16 @@ struct prb_evalset : prb::TableState {
     int64_t n = 0, cap = 0;
     std::vector<prb::DevBuf> retired;
   };
-  const prb_qbatch *qb = nullptr;
-  int32_t nq = 0, ndecoys = 0, npages = 0;
   List real, dec;
   std::vector<uint8_t> real_merged;  // per page: the real batch's search is merged
-  std::vector<uint64_t> merged;      // a bit per (page, query, decoy): that decoy's search of the page is merged
-  int64_t nreal_merged = 0, nmerged = 0; // bytes / bits set
+  int64_t nreal_merged = 0;          // ... bytes set
   bool searched = false;             // something came by a search: the close asks for all of it
-  int64_t decoy_counts[3] = {0, 0, 0}; // the stage counts of the decoy searches (`counts`: of the real batch's)
-  bool bad = false;                  // the device's `bad` flag, as the last call left it
-  prb::DevBuf badflag;
-  prb::DevBuf own_map;               // the decoy batch being merged: owner[ndq], then decoy[ndq]
-  int32_t ndq = 0;
-  bool decoy_phase = false;          // ... and that it is one: what take() appends to (prb_search_page_null_hits)
   prb_tophits *tee = nullptr;        // prb_search_page_scored: the table that the sub-batch is handed on to
   prb::DevBuf h_ids, h_energy;       // prb_evalset_add_keys / _score: the caller's list
   prb::DevBuf off, null_le, rank, qnum, qden, out; // the close: roff, doff [nq + 1] each; per real entry; the look-up's records
   prb::TableFeed feed() const override { return tee && !decoy_phase ? prb::TableFeed::kHitRecords : prb::TableFeed::kHits; }
   int64_t bp_base() const override { return tee && !decoy_phase ? tee->bp_base() : 0; }
   int take(const prb::SubBatch &b) override;
-  int64_t triples() const { return (int64_t)npages * (int64_t)nq * (int64_t)ndecoys; }
-  int64_t bit_of(int32_t page, int32_t q, int32_t d) const { return ((int64_t)page * nq + q) * (int64_t)ndecoys + d; }
   prb::EvalTab view() const {
     return prb::EvalTab{real.key.as<unsigned long long>(), dec.key.as<unsigned long long>(), off.as<int64_t>(), off.as<int64_t>() + (nq + 1),
                         null_le.as<uint32_t>(), rank.as<uint32_t>(), qnum.as<uint32_t>(), qden.as<uint32_t>(), badflag.as<uint32_t>(),
@@ -818,13 +814,10 @@ struct prb_evalset : prb::TableState {
       l->retired.clear();
     }
   }
-  // nothing of the table is released while work on it may still be queued on its context's stream
   void release() {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    if (!quiesce()) return;
     drop_retired();
-    for (prb::DevBuf *b : {&real.key, &real.own, &dec.key, &dec.own, &badflag, &own_map, &h_ids, &h_energy, &off, &null_le, &rank, &qnum, &qden, &out})
+    for (prb::DevBuf *b : {&real.key, &real.own, &dec.key, &dec.own, &badflag, &own, &h_ids, &h_energy, &off, &null_le, &rank, &qnum, &qden, &out})
       b->release();
   }
   ~prb_evalset() { release(); } // (also on the error paths of prb_evalset_create)

@@ -58,11 +58,18 @@
 // database (prb_search_page_null_hits: only their hits' energy keys are kept); the evalset is closed and the kept hits
 // looked up in it (prb_evalset_score).  `-E` needs -k and is refused with -b, -t, -n, -q, -r, -c, -z, -G, -P and in rank mode.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c have one table (kSwitchTable) that every refusal is generated
-// from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args, rank_setup, open_workers,
-// join_ranks (the Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks
-// (the Gatherer), and close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a BatchResult - the one
-// owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread calls write_job.
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E have one table (kSwitchTable) that every
+// refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
+// load_pairlist and load_groups, which read the files of -L and -G), rank_setup, open_workers, join_ranks (the
+// Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
+// close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a
+// BatchResult - the one owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread
+// calls write_job.  search_batch has two shapes.  Most modes: create_table, search_one_page for every page, finish_table
+// - the three steps that a team of workers shares out (Team::search).  The modes with decoys (runs_decoys: -z, -P, -E)
+// have a function each that makes, fills and finishes its own tables around one loop, for_decoy_pieces: it cuts the
+// batch's decoys into pieces, shuffles them, makes each piece's query batch and hands it as a DecoyPiece to the mode's
+// body, which decides the piece's mask (mask_piece, mask_piece_by_list) and searches the pages.  Free has a deleter for
+// every handle of the C ABI that this file keeps in a Handle.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -219,6 +226,9 @@ thread_local bool t_team_thread = false;
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
 // `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score.
 enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored };
+// -z, -P, -E: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
+// (search_null_batch, search_gnull_batch, search_scored_batch) - and by one worker: there is no merge of two of them
+constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m == OutputMode::kGroupNull || m == OutputMode::kScored; }
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
@@ -287,6 +297,8 @@ struct Free {
   void operator()(prb_groupset *p) const { prb_groupset_free(p); }
   void operator()(prb_gnullset *p) const { prb_gnullset_free(p); }
   void operator()(prb_evalset *p) const { prb_evalset_free(p); }
+  void operator()(prb_qbatch *p) const { prb_qbatch_destroy(p); }
+  void operator()(prb_pairmask *p) const { prb_pairmask_free(p); }
 };
 template <class T> using Handle = std::unique_ptr<T, Free>;
 
@@ -1021,9 +1033,7 @@ void plan_batches(Run &r) {
 // Whole batches to the workers, or the pages of every batch?  Pages only in one process with two workers or more and
 // a database of two pages or more: when asked for, or - auto - when there are fewer batches than workers.
 void plan_split(Run &r) {
-  // (-z, -P, -E: a batch and its decoys belong to one worker - there is no merge of two null tables or evalsets)
-  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && r.a.mode != OutputMode::kNull && r.a.mode != OutputMode::kGroupNull &&
-                   r.a.mode != OutputMode::kScored;
+  const bool can = !r.rank_mode && r.workers.size() >= 2 && r.npages >= 2 && !runs_decoys(r.a.mode);
   r.split_pages = can && (r.split_knob == kSplitPages || (r.split_knob == kSplitAuto && r.nb < r.workers.size()));
 }
 
@@ -1068,7 +1078,28 @@ const TableOps<prb_topset> kTopOps = {prb_search_page_top, prb_topset_merge, prb
 const TableOps<prb_profset> kProfOps = {prb_search_page_profile, prb_profset_merge, prb_profset_finish};
 const TableOps<prb_tophits> kTopHitsOps = {prb_search_page_tophits, prb_tophits_merge, prb_tophits_finish};
 
-// the empty table of a batch, by mode (nothing for the modes that have none), in res
+// the run's options with a batch's own mask (-L; a decoy piece's)
+prb_ris_opts opts_with(const Run &r, const prb_pairmask *mask) {
+  prb_ris_opts o = r.a.o;
+  o.allowed_pairs = mask;
+  return o;
+}
+
+// -t -G: the empty group table of a batch
+Handle<prb_groupset> create_groupset(const Run &r, Worker &w, prb_qbatch *qb) {
+  std::vector<const int32_t *> maps;
+  for (const auto &m : r.groups.of_page) maps.push_back(m.data());
+  prb_groupset *t = nullptr;
+  const int rc = prb_groupset_create(w.ctx, qb, w.db, maps.data(), (int32_t)r.groups.names.size(), &t);
+  Handle<prb_groupset> gs(t);
+  if (rc == PRB_ERR_NOMEM)
+    die(std::string("Error: ") + prb_last_error() + "; lower PRB_BATCH (queries per batch: " + std::to_string(r.batch) + ")");
+  if (rc) die(prb_last_error());
+  return gs;
+}
+
+// the empty table of a batch, by mode (nothing for the modes that have none: the run's tables, the page sets - and
+// runs_decoys, which never come here), in res
 void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
   const Args &a = r.a;
   int rc = 0;
@@ -1091,23 +1122,8 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
-  case OutputMode::kGroups: {
-    std::vector<const int32_t *> maps;
-    for (const auto &m : r.groups.of_page) maps.push_back(m.data());
-    prb_groupset *t = nullptr;
-    rc = prb_groupset_create(w.ctx, qb, w.db, maps.data(), (int32_t)r.groups.names.size(), &t);
-    res.groups.reset(t);
-    if (rc == PRB_ERR_NOMEM)
-      die(std::string("Error: ") + prb_last_error() + "; lower PRB_BATCH (queries per batch: " + std::to_string(r.batch) + ")");
-    break;
-  }
-  case OutputMode::kTargets: // (the worker's own table, for the whole run: open_workers)
-  case OutputMode::kCoverage:
-  case OutputMode::kNull: // (search_null_batch makes its own)
-  case OutputMode::kGroupNull: // (search_gnull_batch)
-  case OutputMode::kScored: // (search_scored_batch)
-  case OutputMode::kSummary:
-  case OutputMode::kHits: break;
+  case OutputMode::kGroups: res.groups = create_groupset(r, w, qb); break;
+  default: break; // (kTargets, kCoverage: the worker's own table, for the whole run - open_workers)
   }
   if (rc) die(prb_last_error());
 }
@@ -1116,8 +1132,7 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
 // into slot `page` of `out`
 void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, BatchResult &mine, BatchResult &out) {
   prb_qbatch *qb = p.qb;
-  prb_ris_opts o = r.a.o; // the run's options with the batch's own mask (-L)
-  o.allowed_pairs = p.mask;
+  const prb_ris_opts o = opts_with(r, p.mask);
   int rc = 0;
   switch (r.a.mode) {
   case OutputMode::kTargets: rc = prb_search_page_targets(w.ctx, qb, w.db, page, &o, p.ids.data(), w.targets); break;
@@ -1138,9 +1153,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
     out.pages[(size_t)page].reset(hs);
     break;
   }
-  case OutputMode::kNull: break; // (search_null_batch)
-  case OutputMode::kGroupNull: break; // (search_gnull_batch)
-  case OutputMode::kScored: break; // (search_scored_batch)
+  default: break; // (runs_decoys: never here)
   }
   if (rc) die(prb_last_error());
 }
@@ -1161,13 +1174,7 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
       if (prb_groupset_merge(w.ctx, mine.groups.get(), o->groups.get())) die(prb_last_error());
     if (prb_groupset_finish(w.ctx, mine.groups.get(), r.a.given[kN] ? r.a.top : 0)) die(prb_last_error());
     break;
-  case OutputMode::kTargets:
-  case OutputMode::kCoverage:
-  case OutputMode::kNull:
-  case OutputMode::kGroupNull:
-  case OutputMode::kScored:
-  case OutputMode::kSummary:
-  case OutputMode::kHits: break;
+  default: break; // (no table of the batch's own to finish: create_table)
   }
 }
 
@@ -1186,23 +1193,89 @@ void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
   for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
 }
 
-// -t -z N: the real batch against every page into a null table of its own, then its decoys - N shuffles of every query,
-// made on host threads, file_pos = the query's place in the input file - in batches of at most the batch size, each with
-// its suffix arrays and accessibilities, against every page.  Unless PRB_NULL_MASK=0, a decoy batch is searched under a
-// pair mask that allows each decoy the observed targets of its owner only (under -L those are listed pairs already): the
-// real batch's records come to the host for that (prb_search_page_summary) and go into the table from there
-// (prb_nullset_observe); without the mask they never leave the device (prb_search_page_observed).
+// ---- -z, -P, -E: a batch and its decoys (runs_decoys) ------------------------------------------------
+// One piece of a batch's decoys, ready to be searched: at most the batch size of them
+struct DecoyPiece {
+  std::vector<int32_t> owner, decoy, ids; // per decoy: its query's place in the batch, its number, its query's place in the input file
+  Handle<prb_qbatch> qb;                  // the shuffles, with their suffix arrays and accessibilities
+  Handle<prb_pairmask> mask;              // what the mode's body restricts their search to, if anything
+};
+
+// The decoys of a prepared batch - N shuffles of every query (prb_shuffle_sequence under the run's seed, the query's place
+// in the input file and the decoy's number), made on host threads -, query by query and decoy by decoy, in pieces of at
+// most the batch size: each piece gets its suffix arrays and accessibilities, goes to the mode's `body` - which makes
+// the piece's mask, if it wants one, and searches the piece against every page -, and is let go of with its mask.
+template <class Body> void for_decoy_pieces(const Run &r, Worker &w, const Prepared &p, Body body) {
+  const size_t nd = (size_t)r.a.decoys, total = p.ids.size() * nd;
+  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
+    const size_t m = std::min(total, d0 + r.batch) - d0;
+    DecoyPiece dp;
+    dp.owner.resize(m);
+    dp.decoy.resize(m);
+    dp.ids.resize(m);
+    std::vector<int64_t> off(m + 1, 0);
+    for (size_t k = 0; k < m; k++) {
+      dp.owner[k] = (int32_t)((d0 + k) / nd);
+      dp.decoy[k] = (int32_t)((d0 + k) % nd);
+      dp.ids[k] = p.ids[(size_t)dp.owner[k]];
+      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dp.ids[k]].size();
+    }
+    std::string cat((size_t)off[m], '\0');
+    bool shuffled = true;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
+    for (size_t k = 0; k < m; k++) {
+      const std::string &seq = r.seqs[(size_t)dp.ids[k]];
+      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), r.a.shuffle_seed, (int64_t)dp.ids[k], dp.decoy[k], &cat[(size_t)off[k]])) {
+#pragma omp atomic write
+        shuffled = false;
+      }
+    }
+    if (!shuffled) die(std::string("Error: ") + prb_last_error());
+    prb_qbatch *dqb = nullptr;
+    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
+    dp.qb.reset(dqb);
+    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
+    body(dp);
+  }
+}
+
+// PRB_NULL_MASK=0: -z and -P search their decoys without a mask of the mode's own
+bool null_mask_wanted() {
+  const char *menv = std::getenv("PRB_NULL_MASK");
+  return !(menv && std::atoi(menv) == 0);
+}
+// A piece's masks: the one of the targets that each_target(k, add) names for decoy k with add(page, db_id), and - under
+// -L - the one of its owners' listed pairs
+template <class EachTarget> void mask_piece(Worker &w, DecoyPiece &dp, EachTarget each_target) {
+  std::vector<int32_t> mq, mp, md;
+  for (size_t k = 0; k < dp.owner.size(); k++)
+    each_target(k, [&](int32_t page, int32_t db_id) {
+      mq.push_back((int32_t)k);
+      mp.push_back(page);
+      md.push_back(db_id);
+    });
+  prb_pairmask *m = nullptr;
+  const int rc = prb_pairmask_create(w.ctx, dp.qb.get(), w.db, &m);
+  dp.mask.reset(m);
+  if (rc || prb_pairmask_allow(m, (int64_t)mq.size(), mq.data(), mp.data(), md.data())) die(std::string("Error: ") + prb_last_error());
+}
+void mask_piece_by_list(const Run &r, Worker &w, DecoyPiece &dp) {
+  if (r.a.have_pairlist) dp.mask.reset(batch_mask(r, w.ctx, dp.qb.get(), w.db, dp.ids));
+}
+
+// -t -z N: the real batch against every page into a null table of its own, then its decoys against every page.  Unless
+// PRB_NULL_MASK=0, a piece is searched under a pair mask that allows each decoy the observed targets of its owner only
+// (under -L those are listed pairs already): the real batch's records come to the host for that
+// (prb_search_page_summary) and go into the table from there (prb_nullset_observe); without the mask - none at all, also
+// under -L - they never leave the device (prb_search_page_observed).
 BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
-  const Args &a = r.a;
-  const char *menv = std::getenv("PRB_NULL_MASK");
-  const bool masked = !(menv && std::atoi(menv) == 0);
+  const bool masked = null_mask_wanted();
   const size_t nq = p.ids.size();
   prb_nullset *ns = nullptr;
-  if (prb_nullset_create(w.ctx, p.qb, w.db, a.decoys, &ns)) die(prb_last_error());
+  if (prb_nullset_create(w.ctx, p.qb, w.db, r.a.decoys, &ns)) die(prb_last_error());
   res.null.reset(ns);
-  prb_ris_opts o = a.o;
-  o.allowed_pairs = p.mask;
+  const prb_ris_opts o = opts_with(r, p.mask);
   std::vector<std::vector<std::pair<int32_t, int32_t>>> observed(nq); // per query: its (page, db_id)
   for (int page = 0; page < r.npages; page++) {
     if (!masked) {
@@ -1220,80 +1293,32 @@ BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
     }
     if (prb_nullset_observe(w.ctx, ns, page, rec, n)) die(prb_last_error());
   }
-  // the decoys, query by query and decoy by decoy
-  const size_t nd = (size_t)a.decoys, total = nq * nd;
-  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
-    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
-    std::vector<int64_t> off(m + 1, 0);
-    std::vector<int32_t> owner(m), decoy(m);
-    for (size_t k = 0; k < m; k++) {
-      owner[k] = (int32_t)((d0 + k) / nd);
-      decoy[k] = (int32_t)((d0 + k) % nd);
-      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)p.ids[(size_t)owner[k]]].size();
-    }
-    std::string cat((size_t)off[m], '\0');
-    bool shuffled = true;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
-    for (size_t k = 0; k < m; k++) {
-      const std::string &seq = r.seqs[(size_t)p.ids[(size_t)owner[k]]];
-      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)p.ids[(size_t)owner[k]], decoy[k], &cat[(size_t)off[k]])) {
-#pragma omp atomic write
-        shuffled = false;
-      }
-    }
-    if (!shuffled) die(std::string("Error: ") + prb_last_error());
-    prb_qbatch *dqb = nullptr;
-    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
-    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
-    prb_ris_opts od = a.o;
-    prb_pairmask *dmask = nullptr;
-    if (masked) {
-      std::vector<int32_t> mq, mp, md;
-      for (size_t k = 0; k < m; k++)
-        for (const auto &[page, db_id] : observed[(size_t)owner[k]]) {
-          mq.push_back((int32_t)k);
-          mp.push_back(page);
-          md.push_back(db_id);
-        }
-      if (prb_pairmask_create(w.ctx, dqb, w.db, &dmask) || prb_pairmask_allow(dmask, (int64_t)mq.size(), mq.data(), mp.data(), md.data()))
-        die(std::string("Error: ") + prb_last_error());
-      od.allowed_pairs = dmask;
-    }
+  for_decoy_pieces(r, w, p, [&](DecoyPiece &dp) {
+    if (masked)
+      mask_piece(w, dp, [&](size_t k, auto add) {
+        for (const auto &[page, db_id] : observed[(size_t)dp.owner[k]]) add(page, db_id);
+      });
+    const prb_ris_opts od = opts_with(r, dp.mask.get());
     for (int page = 0; page < r.npages; page++)
-      if (prb_search_page_decoys(w.ctx, dqb, w.db, page, &od, owner.data(), decoy.data(), ns)) die(prb_last_error());
-    prb_pairmask_free(dmask);
-    prb_qbatch_destroy(dqb);
-  }
+      if (prb_search_page_decoys(w.ctx, dp.qb.get(), w.db, page, &od, dp.owner.data(), dp.decoy.data(), ns)) die(prb_last_error());
+  });
   if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
   release_batch(p);
   return res;
 }
 
 // -t -G FILE -P N: the real batch against every page into a group table, which is finished - under the run's -n - into a
-// group null table: nothing comes to the host but the kept records.  Then the decoys as -z makes them, in batches of at
-// most the batch size, each against every page between prb_gnullset_begin and prb_gnullset_end.  Unless PRB_NULL_MASK=0,
-// a decoy batch is searched under a pair mask that allows each decoy the members of its owner's kept groups only - under
-// -L those of them that are listed for the owner; with PRB_NULL_MASK=0, under -L, every pair listed for the owner (the
-// statistic runs over the listed targets either way).
+// group null table: nothing comes to the host but the kept records.  Then the decoys, each piece against every page
+// between prb_gnullset_begin and prb_gnullset_end.  Unless PRB_NULL_MASK=0, a piece is searched under a pair mask that
+// allows each decoy the members of its owner's kept groups only - under -L those of them that are listed for the owner;
+// with PRB_NULL_MASK=0, under -L, every pair listed for the owner (the statistic runs over the listed targets either way).
 BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
   const Args &a = r.a;
-  const char *menv = std::getenv("PRB_NULL_MASK");
-  const bool masked = !(menv && std::atoi(menv) == 0);
+  const bool masked = null_mask_wanted();
   const size_t nq = p.ids.size();
-  Handle<prb_groupset> real;
-  {
-    std::vector<const int32_t *> maps;
-    for (const auto &m : r.groups.of_page) maps.push_back(m.data());
-    prb_groupset *t = nullptr;
-    const int rc = prb_groupset_create(w.ctx, p.qb, w.db, maps.data(), (int32_t)r.groups.names.size(), &t);
-    real.reset(t);
-    if (rc == PRB_ERR_NOMEM)
-      die(std::string("Error: ") + prb_last_error() + "; lower PRB_BATCH (queries per batch: " + std::to_string(r.batch) + ")");
-    if (rc) die(prb_last_error());
-  }
-  prb_ris_opts o = a.o;
-  o.allowed_pairs = p.mask;
+  Handle<prb_groupset> real = create_groupset(r, w, p.qb);
+  const prb_ris_opts o = opts_with(r, p.mask);
   for (int page = 0; page < r.npages; page++)
     if (prb_search_page_groups(w.ctx, p.qb, w.db, page, &o, real.get())) die(prb_last_error());
   prb_gnullset *gn = nullptr;
@@ -1320,117 +1345,53 @@ BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
     listed[q].insert(listed[q].end(), own.begin(), own.end());
     std::sort(listed[q].begin(), listed[q].end());
   }
-  // the decoys, query by query and decoy by decoy
-  const size_t nd = (size_t)a.decoys, total = nq * nd;
-  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
-    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
-    std::vector<int64_t> off(m + 1, 0);
-    std::vector<int32_t> owner(m), decoy(m), dids(m);
-    for (size_t k = 0; k < m; k++) {
-      owner[k] = (int32_t)((d0 + k) / nd);
-      decoy[k] = (int32_t)((d0 + k) % nd);
-      dids[k] = p.ids[(size_t)owner[k]];
-      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dids[k]].size();
-    }
-    std::string cat((size_t)off[m], '\0');
-    bool shuffled = true;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
-    for (size_t k = 0; k < m; k++) {
-      const std::string &seq = r.seqs[(size_t)dids[k]];
-      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)dids[k], decoy[k], &cat[(size_t)off[k]])) {
-#pragma omp atomic write
-        shuffled = false;
-      }
-    }
-    if (!shuffled) die(std::string("Error: ") + prb_last_error());
-    prb_qbatch *dqb = nullptr;
-    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
-    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
-    prb_ris_opts od = a.o;
-    prb_pairmask *dmask = nullptr;
-    if (masked) {
-      std::vector<int32_t> mq, mp, md;
-      for (size_t k = 0; k < m; k++)
-        for (int32_t g : kept[(size_t)owner[k]])
+  for_decoy_pieces(r, w, p, [&](DecoyPiece &dp) {
+    if (masked)
+      mask_piece(w, dp, [&](size_t k, auto add) {
+        for (int32_t g : kept[(size_t)dp.owner[k]])
           for (const auto &[page, db_id] : r.groups.members[(size_t)g]) {
             if (a.have_pairlist) {
-              const std::vector<int64_t> &l = listed[(size_t)owner[k]];
+              const std::vector<int64_t> &l = listed[(size_t)dp.owner[k]];
               if (!std::binary_search(l.begin(), l.end(), page_first[(size_t)page] + db_id)) continue;
             }
-            mq.push_back((int32_t)k);
-            mp.push_back(page);
-            md.push_back(db_id);
+            add(page, db_id);
           }
-      if (prb_pairmask_create(w.ctx, dqb, w.db, &dmask) || prb_pairmask_allow(dmask, (int64_t)mq.size(), mq.data(), mp.data(), md.data()))
-        die(std::string("Error: ") + prb_last_error());
-    } else if (a.have_pairlist) {
-      dmask = batch_mask(r, w.ctx, dqb, w.db, dids);
-    }
-    od.allowed_pairs = dmask;
-    if (prb_gnullset_begin(w.ctx, gn, owner.data(), decoy.data(), (int32_t)m)) die(std::string("Error: ") + prb_last_error());
+      });
+    else
+      mask_piece_by_list(r, w, dp);
+    const prb_ris_opts od = opts_with(r, dp.mask.get());
+    if (prb_gnullset_begin(w.ctx, gn, dp.owner.data(), dp.decoy.data(), (int32_t)dp.owner.size())) die(std::string("Error: ") + prb_last_error());
     for (int page = 0; page < r.npages; page++)
-      if (prb_search_page_gnull(w.ctx, dqb, w.db, page, &od, gn)) die(prb_last_error());
+      if (prb_search_page_gnull(w.ctx, dp.qb.get(), w.db, page, &od, gn)) die(prb_last_error());
     if (prb_gnullset_end(w.ctx, gn)) die(prb_last_error());
-    prb_pairmask_free(dmask);
-    prb_qbatch_destroy(dqb);
-  }
+  });
   if (prb_gnullset_finish(w.ctx, gn)) die(prb_last_error());
   release_batch(p);
   return res;
 }
 
 // -k K -E M: the real batch against every page, once, into the top-N hit table and an evalset beside it; then its decoys
-// - M shuffles of every query, as -z makes and cuts them - against every page into the evalset's decoy list.  There is no
-// decoy mask: the null is pooled over every target (under -L: over the owner's listed targets, the query's own search
-// space).  The evalset is closed, the table finished, and the kept hits looked up on the device.
+// against every page into the evalset's decoy list.  There is no decoy mask, whatever PRB_NULL_MASK says: the null is
+// pooled over every target (under -L: over the owner's listed targets, the query's own search space).  The evalset is
+// closed, the table finished, and the kept hits looked up on the device.
 BatchResult search_scored_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
   const Args &a = r.a;
-  const size_t nq = p.ids.size();
   prb_tophits *th = nullptr;
   if (prb_tophits_create(w.ctx, p.qb, a.tophits, &th)) die(prb_last_error());
   res.tophits.reset(th);
   prb_evalset *raw = nullptr;
   if (prb_evalset_create(w.ctx, p.qb, w.db, a.decoys, &raw)) die(prb_last_error());
   const Handle<prb_evalset> es(raw);
-  prb_ris_opts o = a.o;
-  o.allowed_pairs = p.mask;
+  const prb_ris_opts o = opts_with(r, p.mask);
   for (int page = 0; page < r.npages; page++)
     if (prb_search_page_scored(w.ctx, p.qb, w.db, page, &o, th, es.get())) die(prb_last_error());
-  // the decoys, query by query and decoy by decoy
-  const size_t nd = (size_t)a.decoys, total = nq * nd;
-  for (size_t d0 = 0; d0 < total; d0 += r.batch) {
-    const size_t d1 = std::min(total, d0 + r.batch), m = d1 - d0;
-    std::vector<int64_t> off(m + 1, 0);
-    std::vector<int32_t> owner(m), decoy(m), dids(m);
-    for (size_t k = 0; k < m; k++) {
-      owner[k] = (int32_t)((d0 + k) / nd);
-      decoy[k] = (int32_t)((d0 + k) % nd);
-      dids[k] = p.ids[(size_t)owner[k]];
-      off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dids[k]].size();
-    }
-    std::string cat((size_t)off[m], '\0');
-    bool shuffled = true;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(std::max(1, prb_host_threads_default()))
-    for (size_t k = 0; k < m; k++) {
-      const std::string &seq = r.seqs[(size_t)dids[k]];
-      if (prb_shuffle_sequence(seq.data(), (int32_t)seq.size(), a.shuffle_seed, (int64_t)dids[k], decoy[k], &cat[(size_t)off[k]])) {
-#pragma omp atomic write
-        shuffled = false;
-      }
-    }
-    if (!shuffled) die(std::string("Error: ") + prb_last_error());
-    prb_qbatch *dqb = nullptr;
-    if (prb_qbatch_create(w.ctx, (int32_t)m, cat.data(), off.data(), r.repeat_flag, &dqb)) die(prb_last_error());
-    if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
-    prb_ris_opts od = a.o;
-    prb_pairmask *dmask = a.have_pairlist ? batch_mask(r, w.ctx, dqb, w.db, dids) : nullptr;
-    od.allowed_pairs = dmask;
+  for_decoy_pieces(r, w, p, [&](DecoyPiece &dp) {
+    mask_piece_by_list(r, w, dp);
+    const prb_ris_opts od = opts_with(r, dp.mask.get());
     for (int page = 0; page < r.npages; page++)
-      if (prb_search_page_null_hits(w.ctx, dqb, w.db, page, &od, owner.data(), decoy.data(), es.get())) die(prb_last_error());
-    prb_pairmask_free(dmask);
-    prb_qbatch_destroy(dqb);
-  }
+      if (prb_search_page_null_hits(w.ctx, dp.qb.get(), w.db, page, &od, dp.owner.data(), dp.decoy.data(), es.get())) die(prb_last_error());
+  });
   if (prb_evalset_close(w.ctx, es.get())) die(prb_last_error());
   if (prb_tophits_finish(w.ctx, th)) die(prb_last_error());
   const prb_top_hit *rec = prb_tophits_hits(th);
@@ -1524,6 +1485,20 @@ int64_t write_tophits(const Run &r, const BatchJob &job, int64_t id, LineSink &s
   return id;
 }
 
+// a table's record names a query of the job and a sequence of the database - and, a group record, a group of the run
+bool in_range(const Run &r, size_t nq, const prb_pair_summary &s, int32_t page) {
+  return s.query >= 0 && (size_t)s.query < nq && page >= 0 && page < r.npages && s.db_id >= 0 && (size_t)s.db_id < r.tabs[(size_t)page].names.size();
+}
+bool in_range(const Run &r, size_t nq, const prb_group_pair &x) {
+  return in_range(r, nq, x.s, x.page) && x.group >= 0 && (size_t)x.group < r.groups.names.size();
+}
+// -G: the groups' names and sizes as the formatters take them (`names` keeps the pointers)
+template <class View> void set_groups(View &v, const Run &r, std::vector<const char *> &names) {
+  for (const std::string &g : r.groups.names) names.push_back(g.c_str());
+  v.group_names = names.data();
+  v.group_sizes = r.groups.sizes.data();
+}
+
 // one job to the output, numbered from `id` on; returns the next id.  The job's handles are freed on return.
 int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
   const int threads = prb::format_threads();
@@ -1550,9 +1525,7 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.r = prb_nullset_pairs(job.res.null.get());
     v.n = prb_nullset_size(job.res.null.get());
     for (int64_t i = 0; i < v.n; i++)
-      if (v.r[i].s.query < 0 || (size_t)v.r[i].s.query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages || v.r[i].s.db_id < 0 ||
-          (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size())
-        die("Error: bad record in the null table");
+      if (!in_range(r, v.nq, v.r[i].s, v.r[i].page)) die("Error: bad record in the null table");
     return written_or_die(prb::format_null_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kGroups: {
@@ -1561,13 +1534,9 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.r = prb_groupset_pairs(job.res.groups.get());
     v.n = prb_groupset_size(job.res.groups.get());
     std::vector<const char *> gnames;
-    for (const std::string &g : r.groups.names) gnames.push_back(g.c_str());
-    v.group_names = gnames.data();
-    v.group_sizes = r.groups.sizes.data();
+    set_groups(v, r, gnames);
     for (int64_t i = 0; i < v.n; i++)
-      if (v.r[i].s.query < 0 || (size_t)v.r[i].s.query >= v.nq || v.r[i].page < 0 || v.r[i].page >= r.npages || v.r[i].s.db_id < 0 ||
-          (size_t)v.r[i].s.db_id >= r.tabs[(size_t)v.r[i].page].names.size() || v.r[i].group < 0 || (size_t)v.r[i].group >= gnames.size())
-        die("Error: bad record in the group table");
+      if (!in_range(r, v.nq, v.r[i])) die("Error: bad record in the group table");
     return written_or_die(prb::format_group_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kGroupNull: {
@@ -1576,15 +1545,9 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.r = prb_gnullset_pairs(job.res.gnull.get());
     v.n = prb_gnullset_size(job.res.gnull.get());
     std::vector<const char *> gnames;
-    for (const std::string &g : r.groups.names) gnames.push_back(g.c_str());
-    v.group_names = gnames.data();
-    v.group_sizes = r.groups.sizes.data();
-    for (int64_t i = 0; i < v.n; i++) {
-      const prb_group_pair &x = v.r[i].g;
-      if (x.s.query < 0 || (size_t)x.s.query >= v.nq || x.page < 0 || x.page >= r.npages || x.s.db_id < 0 ||
-          (size_t)x.s.db_id >= r.tabs[(size_t)x.page].names.size() || x.group < 0 || (size_t)x.group >= gnames.size())
-        die("Error: bad record in the group null table");
-    }
+    set_groups(v, r, gnames);
+    for (int64_t i = 0; i < v.n; i++)
+      if (!in_range(r, v.nq, v.r[i].g)) die("Error: bad record in the group null table");
     return written_or_die(prb::format_gnull_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kTargets:
