@@ -21,6 +21,11 @@ compiled reference produced for them (strict build: -ffp-contract=off, SURVEY.md
                         designed duplexes with a bulge next to the seed: the FIRST post-ungapped hit of a
                         query is gapped-extended and survives the final filter, so it keeps the unsorted
                         base-pair order of rna_interaction_search.cpp:314-317; 5 DB pages
+  edge_*.fa, edgedb.*.gz, edge_ris_s{0,1}.out, edge.stg.gz
+                        the database side at its edges (edge_inputs): targets of 4 to 33 nt next to each other,
+                        targets that are nothing but a site, trap neighbours behind the separators, sites at text
+                        position 0 and nchars - 1, a page of one sequence; 5 DB pages (-c 8).
+                        `make_golden.py edge` regenerates this case alone
 """
 import gzip
 import os
@@ -151,6 +156,78 @@ def quirk_inputs():
     return q, db
 
 
+# (no 1, 2 or 3 nt: `db` stores L - 4 as a target's count of accessibilities, and the reference's `ris` aborts on a
+# negative count when it loads the database - DESIGN.md 2)
+EDGE_TINY = (4, 5, 7, 8, 9, 20, 31, 32, 33)
+EDGE_PAGE = 8  # `db -c`: sequences per page
+
+
+def edge_inputs():
+    """Database side at its edges (33 targets, pages of 8: 5 pages, the last of one sequence).  The page text holds the
+    targets reversed and 0-terminated in file order, so file neighbours are text neighbours.
+
+      page 0  site-only targets (nothing but rc(a query stretch): the hit spans the sequence) as the first and the last
+              sequence of the page, and two more between TRAP neighbours - tiny targets whose bases continue the
+              complement behind the separator, once on the diagonal (one query base skipped: a 1x1 loop for an
+              extension that steps over the separator), once next to it (a 1-nt bulge)
+      page 1  quirk-style designs rc(Y)+bulge+rc(X) with the poly-C flank on one side only (one per side), two
+              identical targets next to each other, an all-N and an all-lower-case target, a 20-nt site-only target
+      page 2  only targets too short to be hit: eight of 4 nt - seven starts in the first 32-character block
+      page 3  5, 7, 8, 9, 31, 32, 33 nt and a site-only target
+      page 4  one site-only target: text position 0 and nchars - 1 belong to the same hit
+    Queries: stretches at position 0 and at the last base, a query that is only a site (shorter than the
+    accessibility span, and the second query on that target), a random 150-mer, three degenerate strings."""
+    comp = {"A": "U", "C": "G", "G": "C", "U": "A"}
+
+    def rc(x):
+        return "".join(comp[c] for c in reversed(x))
+    rng = random.Random(2024)
+
+    def rnd(n, alphabet="ACGU"):
+        return "".join(rng.choice(alphabet) for _ in range(n))
+
+    def site(n):
+        return "".join(rng.choice("GC" if rng.random() < 0.65 else "AU") for _ in range(n))
+    A, Z, B, C, E, F, G20 = site(16), site(15), site(14), site(18), site(12), site(17), site(20)
+    p1, n1, p2, n2 = site(5), site(7), site(4), site(5)
+    p1, n1, p2, n2 = "GC" + p1[2:], n1[:-2] + "CG", "CG" + p2[2:], n2[:-2] + "GC"
+    q, db = [], []
+    q.append(("eq_ends", A + rnd(20, "AU") + G20 + rnd(20, "AU") + Z))        # sites at position 0 and at the last base
+    q.append(("eq_trap1", rnd(12, "AU") + p1 + "A" + B + "A" + n1 + rnd(12, "AU")))  # traps on the diagonal
+    q.append(("eq_trap2", rnd(12, "AU") + p2 + C + n2 + rnd(9, "AU") + E + rnd(7, "AU") + F))  # traps beside it
+    q.append(("eq_site", B))                                                   # nothing but a site
+    rnd150 = rnd(150)
+    kq, kdb = [], []
+    for k, (seed, end) in enumerate(((1, "l"), (2, "r"), (5, "l"))):
+        r2 = random.Random(seed)
+        X = "".join(r2.choice("GC" if r2.random() < 0.6 else "AU") for _ in range(r2.randint(8, 12)))
+        Y = "".join(r2.choice("GC" if r2.random() < 0.6 else "AU") for _ in range(r2.randint(5, 9)))
+        bulge = "".join(r2.choice("AC") for _ in range(r2.randint(1, 2)))
+        side = r2.random() < 0.5
+        kq.append((f"eq_k{k}", "A" * 25 + (X + Y if side else Y + X) + "A" * 25))
+        core = rc(Y) + bulge + rc(X) if side else rc(X) + bulge + rc(Y)
+        kdb.append((f"ed_k{k}{end}", core + "C" * 20 if end == "l" else "C" * 20 + core))
+    q += kq
+    q.append(("eq_random", rnd150))
+    q += [("eq_deg_n", "N" * 40), ("eq_deg_gc", "GC" * 40), ("eq_deg_acgu", "ACGU")]
+    # page 0
+    db += [("ed_first", rc(A)), ("ed_p1", rc(p1)), ("ed_trap1", rc(B)), ("ed_n1", rc(n1)),
+           ("ed_p2", rc(p2)), ("ed_trap2", rc(C)), ("ed_n2", rc(n2)), ("ed_last", rc(Z))]
+    # page 1
+    twin = rnd(9) + rc(rnd150[40:58]) + rnd(6)
+    db += kdb[:2] + [("ed_twin_a", twin), ("ed_twin_b", twin), ("ed_alln", "N" * 7),
+                     ("ed_lower", (rnd(5) + rc(Z) + rnd(4)).lower()), ("ed_site20", rc(G20)), kdb[2]]
+    # page 2: too short for a seed
+    db += [(f"ed_tiny{k}", rnd(4)) for k in range(EDGE_PAGE)]
+    # page 3
+    db += [(f"ed_len{n}", rnd(n)) for n in (5, 7, 8, 9, 31, 32, 33)] + [("ed_site12", rc(E))]
+    # page 4
+    db.append(("ed_alone", rc(F)))
+    assert len(db) == 4 * EDGE_PAGE + 1 and sum(len(s) for _, s in db) < 2000
+    assert set(EDGE_TINY) <= {len(s) for _, s in db}
+    return q, db
+
+
 def main():
     assert os.path.exists(os.path.join(REF, "ref_harness")), "run `make -C oracle ref` first"
     strict = os.path.join(REF, "pRIblast.strict")
@@ -176,7 +253,8 @@ def main():
             run(harness, "raccess", os.path.join(HERE, "widew.fa"), str(W), str(delta),
                 os.path.join(HERE, f"widew_w{W}d{delta}.racc"))
     cases = [("c1", "c1_q.fa", "c1_db.fa", []), ("mix", "mix_q.fa", "mix_db.fa", ["-c", "10"]),
-             ("quirk", "quirk_q.fa", "quirk_db.fa", ["-c", "2"])]
+             ("quirk", "quirk_q.fa", "quirk_db.fa", ["-c", "2"]),
+             ("edge", "edge_q.fa", "edge_db.fa", ["-c", str(EDGE_PAGE)])]
     if only:
         cases = [c for c in cases if c[0] in only]
     mq, mdb = mix_inputs()
@@ -185,6 +263,9 @@ def main():
     kq, kdb = quirk_inputs()
     gen_synthetic.write_fasta(os.path.join(HERE, "quirk_q.fa"), kq)
     gen_synthetic.write_fasta(os.path.join(HERE, "quirk_db.fa"), kdb)
+    eq, edb = edge_inputs()
+    gen_synthetic.write_fasta(os.path.join(HERE, "edge_q.fa"), eq)
+    gen_synthetic.write_fasta(os.path.join(HERE, "edge_db.fa"), edb)
     for tag, qfa, dbfa, dbopts in cases:
         dbp = os.path.join(tmp, tag + "db")
         run(strict, "db", "-i", os.path.join(HERE, dbfa), "-o", dbp, *dbopts, cwd=tmp)

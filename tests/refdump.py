@@ -120,6 +120,46 @@ def read_stages(path):
     return out
 
 
+def unpack_case(golden, tag, dst):
+    """Unpacks one golden case's gzip'd database files and stage dump (<tag>db.*.gz, <tag>.stg.gz) into dst."""
+    import gzip
+    import os
+    import shutil
+    for name in [f"{tag}db.{ext}" for ext in ("bas", "seq", "acc", "nam", "ind")] + [f"{tag}.stg"]:
+        with gzip.open(os.path.join(golden, name + ".gz"), "rb") as f, open(os.path.join(dst, name), "wb") as g:
+            shutil.copyfileobj(f, g)
+
+
+def read_seq_pages(path):
+    """The pages of a .seq file: per page {"len": int32[nseq], "start": int32[nseq] (text position of each sequence's
+    first character), "text": uint8[nchars] (the sequences reversed, each followed by a 0)}."""
+    r = _Reader(path)
+    pages = []
+    while not r.done():
+        nseq = r.take("i")
+        lens = r.arr("<i4", nseq)
+        nchars = r.take("i")
+        text = r.arr("u1", nchars)
+        start = np.concatenate([[0], np.cumsum(lens + 1)[:-1]]).astype(np.int32)
+        assert nchars == int(lens.sum()) + nseq
+        pages.append({"len": lens, "start": start, "text": text})
+    return pages
+
+
+def read_acc(path, nseq):
+    """The .acc file: per sequence (int32 n, float32 acc[n], int32 m, float32 cond[m]); n = L - delta + 1, m = L."""
+    r = _Reader(path)
+    out = []
+    for _ in range(nseq):
+        n = r.take("i")
+        acc = r.arr("<f4", max(n, 0))
+        m = r.take("i")
+        cond = r.arr("<f4", max(m, 0))
+        out.append((n, acc, m, cond))
+    assert r.done()
+    return out
+
+
 def read_fasta(path):
     names, seqs = [], []
     with open(path) as f:
