@@ -196,7 +196,7 @@ void prb_ctx_destroy(prb_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   prb_search_const_free(ctx);
   for (DevBuf *b : {&ctx->d_expd, &ctx->d_log, &ctx->d_small, &ctx->d_big, &ctx->ra_band, &ctx->ra_vec,
-                    &ctx->ra_codes, &ctx->ra_desc, &ctx->ra_acc, &ctx->ra_cond})
+                    &ctx->ra_codes, &ctx->ra_desc, &ctx->ra_watchdog, &ctx->ra_acc, &ctx->ra_cond})
     b->release();
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -277,7 +277,7 @@ int run_accessibility(prb_ctx *ctx, int32_t nseq, const char *seqs, const int64_
     while (end < nseq) {
       const int64_t L = len(order[end]);
       const size_t need = (size_t)(band + ra_band_elems((int)L, W) + vec + ra_vec_elems((int)L)) * sizeof(double);
-      if (end > pos && need > ctx->ra_budget_bytes) break;
+      if (end > pos && (need > ctx->ra_budget_bytes || end - pos >= kRaMaxChunk)) break;
       RaSeqDesc d;
       d.band_off = band;
       d.vec_off = vec;
@@ -300,6 +300,7 @@ int run_accessibility(prb_ctx *ctx, int32_t nseq, const char *seqs, const int64_
     if ((rc = ctx->ra_vec.ensure((size_t)vec * sizeof(double)))) return rc;
     if ((rc = ctx->ra_codes.ensure(codes.size()))) return rc;
     if ((rc = ctx->ra_desc.ensure(desc.size() * sizeof(RaSeqDesc)))) return rc;
+    if ((rc = ctx->ra_watchdog.ensure(sizeof(int)))) return rc;
     PRB_HIP(hipMemcpyAsync(ctx->ra_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
     PRB_HIP(hipMemcpyAsync(ctx->ra_desc.p, desc.data(), desc.size() * sizeof(RaSeqDesc), hipMemcpyHostToDevice,
                            ctx->stream));
@@ -314,6 +315,7 @@ int run_accessibility(prb_ctx *ctx, int32_t nseq, const char *seqs, const int64_
     b.codes = ctx->ra_codes.as<unsigned char>();
     b.acc = d_acc;
     b.cond = d_cond;
+    b.watchdog = ctx->ra_watchdog.as<int>();
     {
       // the LOGSUM branch of the bulge / interior sums by windows of 64 positions (which sequences take it is only known on
       // the device, after the inside pass: the grid covers every sequence, the others' workgroups leave at once)
@@ -327,12 +329,13 @@ int run_accessibility(prb_ctx *ctx, int32_t nseq, const char *seqs, const int64_
       const char *wa = std::getenv("PRB_RACCESS_WINDOWS_ALL"); // (tests: 0 / 1 whatever the size of the launch)
       b.windows_all = wa ? (std::atoi(wa) != 0) : (n <= 512);
     }
+    if (b.helpers == 3) PRB_HIP(hipMemsetAsync(b.watchdog, 0, sizeof(int), ctx->stream));
     if ((rc = ctx->time_begin())) return rc;
     PRB_HIP(ra_launch(b, ctx->ra_const, band, vec, ctx->stream));
     if ((rc = ctx->time_end("raccess", 1))) return rc; // synchronises: host staging vectors may be reused
     if (b.helpers == 3) {
-      int tripped = 0;
-      PRB_HIP(ra_watchdog_tripped(&tripped, ctx->stream));
+      int tripped = 0; // (the launch has completed)
+      PRB_HIP(hipMemcpy(&tripped, b.watchdog, sizeof(int), hipMemcpyDeviceToHost));
       if (tripped) {
         set_error("Raccess: a wavefront gave up waiting for its workgroup (PRB_RACCESS_HELPERS=2 avoids that form of the passes)");
         return PRB_ERR_STATE;

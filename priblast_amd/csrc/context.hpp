@@ -63,6 +63,7 @@ struct prb_ctx {
   prb::DevBuf d_expd, d_log, d_small, d_big;
   // Raccess workspaces
   prb::DevBuf ra_band, ra_vec, ra_codes, ra_desc, ra_acc, ra_cond;
+  prb::DevBuf ra_watchdog; // one int: RaBatch::watchdog of this context's launches
   size_t ra_budget_bytes = 0;
   std::map<std::string, prb::StageTimer> timers;
   // What is not a stage of the full-output search - the per-pair reduction ("summary"), the merges, joins and finishes of

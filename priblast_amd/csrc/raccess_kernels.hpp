@@ -1,4 +1,4 @@
-// Host-visible interface of the Raccess kernels (raccess_kernels.hip).
+// Host-visible interface of the Raccess kernels (raccess_inside/outside/biloop/access.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +20,8 @@ struct RaSeqDesc {
 
 constexpr int kRaBands = 13;
 constexpr int kRaVecs = 8;
-constexpr int kRaMaxSpan = 255; // cells of a column / positions of a window: at most four passes of 64 lanes (raccess_kernels.hip)
+constexpr int kRaMaxChunk = 65535; // sequences of a launch: k_access and k_biloop_win put the sequence on grid.y
+constexpr int kRaMaxSpan = 255; // cells of a column / positions of a window: at most four passes of 64 lanes (raccess_common.hpp)
 
 struct RaBatch {
   const RaSeqDesc *desc;
@@ -42,13 +43,23 @@ struct RaBatch {
   // that folds, beside the sequence's own, which keeps the other phases): a workgroup per sequence
   // instead of a wavefront - for the few sequences of a query batch, whose time is the latency of one wavefront's chain
   int32_t helpers = 0;
+  // helpers == 3: set to 1 by a wavefront that gave up waiting for its workgroup (a device int of the context, zeroed before the launch)
+  int *watchdog = nullptr;
 };
 
 // Enqueue fill + inside + outside + biloop + accessibility for a batch on `stream`.
 hipError_t ra_launch(const RaBatch &b, const RaConst &c, int64_t band_elems, int64_t vec_elems,
                      hipStream_t stream);
 
-hipError_t ra_watchdog_tripped(int *tripped, hipStream_t stream);
+// What ra_launch is made of: each kernel file enqueues its own kernels (the instantiation and grid a batch takes).
+void ra_launch_inside(const RaBatch &b, const RaConst &c, hipStream_t stream);  // raccess_inside.hip
+void ra_launch_outside(const RaBatch &b, const RaConst &c, hipStream_t stream); // raccess_outside.hip
+void ra_launch_biloop(const RaBatch &b, const RaConst &c, hipStream_t stream);  // raccess_biloop.hip: k_biloop, k_biloop_win
+#ifdef PRB_GAP_PROFILE
+// developer build: add the file's cycle counters to out[32]
+int ra_inside_profile(unsigned long long *out, int reset);
+int ra_outside_profile(unsigned long long *out, int reset);
+#endif
 
 // doubles / bytes needed for a sequence of length L
 inline int64_t ra_band_elems(int L, int W) { return (int64_t)kRaBands * (L + 2) * (W + 2); }

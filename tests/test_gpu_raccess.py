@@ -26,7 +26,7 @@ def ctx():
 @pytest.mark.parametrize("W,delta", [(70, 5), (100, 5), (127, 3), (128, 5), (150, 5), (255, 2)])
 def test_dp_tables_match_oracle(ctx, oracle, W, delta):
     """Every DP table of one sequence, cell by cell (diagnostics entry point).  Maximal spans beyond 96 leave the
-    row-mask form of the two big folds (raccess_kernels.hip: use_masks), beyond 127 the two-pass cell mapping."""
+    row-mask form of the two big folds (raccess_inside.hip / raccess_outside.hip: use_masks), beyond 127 the two-pass cell mapping."""
     names, seqs = refdump.read_fasta(os.path.join(GOLDEN, "c1_q.fa"))
     cases = (seqs[0][:40], seqs[1], "GGGGGCCAAAAGGCCCCCAUAU" * 6)
     if W > 70:
@@ -81,7 +81,7 @@ def test_batch_order_and_chunking_do_not_matter(ctx, oracle):
 
 def test_lengths_around_the_overflow_classification(ctx, oracle):
     """The bulge/interior sums of long sequences are classified (overflow / zero) instead of summed
-    (raccess_kernels.hip: biloop_classify) once log Z >= 120; below that, and whenever some position
+    (raccess_biloop.hip: biloop_classify) once log Z >= 120; below that, and whenever some position
     cannot be decided that way, the ordered sums are used.  Lengths on both sides of the switch,
     AU-rich (small log Z per nucleotide) and GC-rich (large), against the oracle."""
     rng = np.random.default_rng(11)
@@ -157,3 +157,19 @@ def test_bulge_interior_sums_by_windows(ctx, oracle, monkeypatch, windows_all):
         assert np.array_equal(bits(acc), bits(oa)), (windows_all, len(s))
         assert np.array_equal(bits(cond), bits(oc)), (windows_all, len(s))
     monkeypatch.delenv("PRB_RACCESS_WINDOWS_ALL", raising=False)
+
+
+def test_a_chunk_never_exceeds_the_grid_limit(ctx, oracle):
+    """k_access and k_biloop_win put the sequence on grid.y, which ends at 65,535: 66,000 tiny sequences (four distinct
+    8-nt strings; their workspace, about 5 GB, fits one chunk's byte budget) must be cut into chunks by count as well,
+    every result bit-equal to the oracle's for its string."""
+    four = ["GGGAAACC", "GCGAAAGC", "ACGUACGU", "GGCAAGCC"]
+    want = [oracle.raccess(s, 70, 5) for s in four]
+    n = 66000
+    res = ctx.accessibility([four[k & 3] for k in range(n)], 70, 5)
+    assert len(res) == n
+    acc = np.stack([bits(a) for a, _ in res]).reshape(n // 4, 4, -1)
+    cond = np.stack([bits(c) for _, c in res]).reshape(n // 4, 4, -1)
+    for k in range(4):
+        assert np.array_equal(acc[:, k], np.broadcast_to(bits(want[k][0]), acc[:, k].shape)), four[k]
+        assert np.array_equal(cond[:, k], np.broadcast_to(bits(want[k][1]), cond[:, k].shape)), four[k]
