@@ -210,6 +210,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   table, launches = 1 per sub-batch with final hits; prb_nullset_finish: the selection and the gather, launches = 2);
  * "group" (prb_search_page_groups / prb_groupset_add_pairs: the fold into the group table, launches = 3 per sub-batch with
  *   final hits; prb_groupset_merge: 1; prb_groupset_finish: the flags, the selections and the gather, launches = 2 to 5);
+ * "grouprank" (prb_grouprank_add_groupset: the group table's occupied slots merged into the group ranking table - flags,
+ *   compaction, sort keys, the stable sort by group, rank keys and heads, the selection of the heads, the merge; launches = 7,
+ *   or 2 when the group table is empty; prb_grouprank_add_records: 5; prb_grouprank_merge: 1);
  * "gnull" (prb_gnullset_create: the kept records into the lookup, launches = 1; prb_search_page_gnull / prb_gnullset_add_pairs:
  *   the fold into the scratch, launches = 1 per sub-batch with final hits; prb_gnullset_end: the close, 1; prb_gnullset_finish:
  *   the gather, 1);
@@ -798,6 +801,71 @@ void prb_groupset_free(prb_groupset *gs);
 int prb_write_group_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_group_pair *recs,
                           int64_t nrecs, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
                           int64_t *nlines, int64_t *nbytes);
+
+/* ---- the N best queries per group (`ris -t -G FILE -R N`): a group ranking table on the device ----
+ * prb_targetset ranks the queries of a run per database sequence, and so returns a gene once per isoform; a group table
+ * lives for one batch.  A group ranking table holds, for every group g in [0, ngroups), the N records of lowest s.e_min
+ * among all the (query, group) records merged into it over a whole run (fewer when the group has fewer).  A record is a
+ * prb_group_pair exactly as prb_groupset_finish(gs, 0) returns it, but `s.query` holds a caller-given identifier, int32
+ * >= 0, as in prb_search_page_targets (the command line: the 0-based position in the input FASTA), and `rank` the rank
+ * within the group.  Records of a group are ranked by s.e_min ascending, compared as doubles (-0.0 == +0.0; the stored
+ * record keeps the bits it came with); equal values are ordered by the identifier ascending.  An (identifier, group)
+ * occurs at most once, so it is a total order, and the finished table depends - bit for bit - neither on how the queries
+ * are cut into batches or sub-batches, nor on the order of the batches, nor on which context (worker) took what.
+ *   prb_grouprank_create        an empty table (1 <= n <= 1024, ngroups >= 1, else PRB_ERR_ARG): n slots of 88 B and n
+ *                               keys of 16 B per group, plus a fill count per group, in HBM; PRB_ERR_NOMEM when that
+ *                               cannot be allocated
+ *   prb_grouprank_add_groupset  every occupied slot of the UNFINISHED group table gs merged into the table, on the
+ *                               device: nothing is copied to the host, and gs is left untouched - it can still be
+ *                               finished or merged.  query_ids[q] = the identifier of query q of gs's batch.  Refused,
+ *                               the table untouched: gs or the table made with another context, a gs with another
+ *                               number of groups, an identifier below 0, given twice in the call or already merged into
+ *                               the table, distinct_sites or chain_sites other than those the table holds (PRB_ERR_ARG);
+ *                               a gs that is finished, broken or bad, and a gs that has NOT had every page of its
+ *                               database merged - a group's minimum over some of its members is never ranked -
+ *                               (PRB_ERR_STATE).  The stage counts of gs are added to the table's
+ *   prb_grouprank_add_records   the same merge for a caller's records in host memory whose s.query holds the identifier
+ *                               already (tests; callers with a fold of their own).  PRB_ERR_ARG, table untouched: a group
+ *                               outside the table, an identifier below 0, an (identifier, group) given twice in the call,
+ *                               an identifier merged by an earlier call - every identifier of a call is marked as merged,
+ *                               so all the records of one identifier come in one call.  n = 0 does nothing
+ *   prb_grouprank_merge         two unfinished tables into one, on the device, under the contract of prb_targetset_merge:
+ *                               src may live on another device; both have the same n and ngroups, hold the same
+ *                               distinct_sites and chain_sites unless one is empty, and no identifier is merged into
+ *                               both: anything else returns PRB_ERR_ARG and leaves both tables as they were.  dst then
+ *                               holds - bit for bit - the table of all that was merged into either; src is left empty but
+ *                               valid
+ *   prb_grouprank_finish        the filled slots compacted on the device (a scan over the fills, a gather in rank order)
+ *                               and copied to the host in one copy; the device memory is released.  prb_grouprank_pairs
+ *                               then returns the records by group ascending, then rank; `rank` counts from 0 within the
+ *                               group.  Nothing can be merged after it (a second call does nothing)
+ *   prb_grouprank_counts        the stage counts of prb_groupset_counts, summed over the group tables merged
+ * A merge works in one linear pass over the group table's dense slots - the flags of the occupied ones and their
+ * compaction - plus work in proportion to the occupied ones: their groups as sort keys, a stable sort by group, the rank
+ * keys (the monotone 64-bit key of e_min, the identifier) and the heads of the groups' runs, and a wavefront per run that
+ * merges it into the group's ranked list in LDS - the lists, the merge and the gather of the per-target table.  No
+ * floating-point atomics, and nothing depends on the order in which threads arrive.  On the device every kernel checks
+ * slot, group, query and identifier against the tables' ranges again; a violation raises the table's `bad` flag and
+ * writes nothing, and this and every later call on the table returns PRB_ERR_STATE.  A merge that fails part way leaves
+ * the table unusable.  Stage timer "grouprank": prb_grouprank_add_groupset (launches = 7: flags, compaction, sort keys,
+ * sort, rank keys and heads, selection of the heads, merge; 2 when the group table is empty), prb_grouprank_add_records
+ * (5), prb_grouprank_merge (1); the launches booked to "group" are those of the group table's own calls, as ever. */
+typedef struct prb_grouprank prb_grouprank;
+int prb_grouprank_create(prb_ctx *ctx, int32_t ngroups, int32_t n, prb_grouprank **out);
+int prb_grouprank_add_groupset(prb_ctx *ctx, prb_grouprank *gr, const prb_groupset *gs, const int32_t *query_ids);
+int prb_grouprank_add_records(prb_ctx *ctx, prb_grouprank *gr, const prb_group_pair *recs, int64_t n);
+int prb_grouprank_merge(prb_ctx *ctx, prb_grouprank *dst, prb_grouprank *src);
+int prb_grouprank_finish(prb_ctx *ctx, prb_grouprank *gr);
+int64_t prb_grouprank_size(const prb_grouprank *gr);
+const prb_group_pair *prb_grouprank_pairs(const prb_grouprank *gr);
+void prb_grouprank_counts(const prb_grouprank *gr, int64_t counts[3]);
+void prb_grouprank_free(prb_grouprank *gr);
+/* The lines of `ris -t -G FILE -R N`: recs[0, nrecs) as prb_grouprank_pairs returns them (by group, then rank), one line
+ * each in that order, numbered from id0 on; every line is the prb_write_group_lines line of its record.  qnames and
+ * qlen_unmasked are indexed by the query's identifier (nq_total of them: every s.query lies below it). */
+int prb_write_grouprank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                              const prb_group_pair *recs, int64_t nrecs, const char *const *group_names, const int32_t *group_sizes,
+                              int32_t ngroups, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
 
 /* ---- an empirical p-value per (query, group) from shuffled decoys (`ris -t -G FILE -P N`): a group null table ----
  * A group's record reports the minimum e_min over its members, so its null is the distribution of the DECOYS' minimum over

@@ -227,6 +227,17 @@ SYMBOLS = {
     "prb_groupset_free": (None, [ctypes.c_void_p]),
     "prb_write_group_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                              P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_grouprank_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, P(ctypes.c_void_p)]),
+    "prb_grouprank_add_groupset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_grouprank_add_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64]),
+    "prb_grouprank_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_grouprank_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_grouprank_size": (c_i64, [ctypes.c_void_p]),
+    "prb_grouprank_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_grouprank_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_grouprank_free": (None, [ctypes.c_void_p]),
+    "prb_write_grouprank_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                                 P(ctypes.c_char_p), ctypes.c_void_p, c_i32, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_gnullset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, c_i32, P(ctypes.c_void_p)]),
     "prb_gnullset_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32]),
     "prb_search_page_gnull": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
@@ -923,6 +934,49 @@ def search_groups(ctx, qb, db, group_of_page, ngroups, n=0, opts=None, pages=Non
     return (recs, counts) if with_counts else recs
 
 
+class GroupRank(_Table):
+    """prb_grouprank: the N best queries per group of database sequences, in a table on the device that any number of
+    batches is merged into - each as its complete, unfinished GroupSet, or as GROUP_DTYPE records -; every batch names its
+    queries by identifiers of the caller's.  Close it before its context."""
+    PREFIX = "grouprank"
+
+    def __init__(self, ctx, ngroups, n):
+        h = ctypes.c_void_p()
+        _check(lib().prb_grouprank_create(ctx.h, ngroups, n, ctypes.byref(h)))
+        self.h, self.ctx = h, ctx
+
+    def add_groupset(self, gs, ids):
+        """prb_grouprank_add_groupset: every occupied slot of the unfinished GroupSet `gs` (every page merged), on the
+        device; ids[q] = the identifier of query q of its batch.  gs is left as it was"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        assert len(ids) == len(gs.qb.lens)
+        _check(lib().prb_grouprank_add_groupset(self.ctx.h, self.h, gs.h, ids.ctypes.data))
+
+    def add_records(self, recs):
+        """prb_grouprank_add_records: a caller's GROUP_DTYPE records whose s.query is the identifier already"""
+        recs = np.ascontiguousarray(recs, GROUP_DTYPE)
+        _check(lib().prb_grouprank_add_records(self.ctx.h, self.h, recs.ctypes.data if len(recs) else None, len(recs)))
+
+    def finish(self):
+        """prb_grouprank_finish -> structured array GROUP_DTYPE (a copy), by group, then rank"""
+        return self._finish("pairs", GROUP_DTYPE)
+
+
+def search_grouprank(ctx, db, group_of_page, ngroups, n, batches, opts=None, pages=None, with_counts=False):
+    """The n (query, group) records of lowest e_min per group over batches = [(QBatch, ids)], every batch against every
+    page (in this order, if given) into a group table of its own, which is merged into the ranking on the device and
+    dropped -> structured array GROUP_DTYPE, by group and rank.  with_counts: -> (records, (seed, ungapped, final) counts
+    summed over the batches)."""
+    with GroupRank(ctx, ngroups, n) as gr:
+        for qb, ids in batches:
+            with GroupSet(ctx, qb, db, group_of_page, ngroups) as gs:
+                for p in range(db.npages) if pages is None else pages:
+                    gs.merge(p, opts)
+                gr.add_groupset(gs, ids)
+        recs, counts = gr.finish(), gr.counts()
+    return (recs, counts) if with_counts else recs
+
+
 class GNullSet(_Table):
     """prb_gnullset: per kept (query, group) record of a group table, how the query's decoys fare against the group's
     members.  Made from a GroupSet with every page merged, which it finishes (gs.records() are then its records); the decoys
@@ -1231,6 +1285,16 @@ def write_group_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes,
     gn = (ctypes.c_char_p * max(len(group_names), 1))(*[g.encode() for g in group_names])
     gsz = np.ascontiguousarray(group_sizes, np.int32)
     return _write(lib().prb_write_group_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
+                  gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
+
+
+def write_grouprank_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes, id0=0, fd=-1):
+    """Lines of `ris -t -G FILE -R N`: recs as GroupRank.finish returns them; qnames / qlen_unmasked indexed by query
+    identifier, group_names / group_sizes by group.  -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, GROUP_DTYPE)
+    gn = (ctypes.c_char_p * max(len(group_names), 1))(*[g.encode() for g in group_names])
+    gsz = np.ascontiguousarray(group_sizes, np.int32)
+    return _write(lib().prb_write_grouprank_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
                   gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
 
 

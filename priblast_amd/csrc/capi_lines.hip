@@ -156,6 +156,29 @@ int prb_write_group_lines(const prb_db *db, int32_t nq, const char *const *qname
       [&](const GroupView &v, LineSink &sink) { return format_group_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
+int prb_write_grouprank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                              const prb_group_pair *recs, int64_t n, const char *const *group_names, const int32_t *group_sizes,
+                              int32_t ngroups, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<GroupView>(
+      "prb_write_grouprank_lines", n >= 0 && (!n || recs) && ngroups >= 0 && (!ngroups || (group_names && group_sizes)), db, nq_total, qnames,
+      qlen_unmasked, lines, bytes, fd,
+      [&](GroupView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_group_pair &x = recs[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq_total || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || x.group < 0 || x.group >= ngroups || !group_names[x.group] ||
+              x.members < 1 || x.hits < x.s.hits)
+            return bad_record("prb_write_grouprank_lines: record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = recs;
+        v.n = n;
+        v.group_names = group_names;
+        v.group_sizes = group_sizes;
+        return (int)PRB_OK;
+      },
+      [&](const GroupView &v, LineSink &sink) { return format_grouprank_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
 int prb_write_gnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_gnull_pair *recs,
                           int64_t n, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
                           int64_t *lines, int64_t *bytes) {

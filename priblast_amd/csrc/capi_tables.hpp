@@ -1,5 +1,5 @@
-// The protocol of the nine result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip, capi_gnull.hip, capi_eval.hip): what a prb_*_create starts with, what is checked before a page, a
+// The protocol of the ten result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip, capi_grouprank.hip, capi_gnull.hip, capi_eval.hip): what a prb_*_create starts with, what is checked before a page, a
 // caller's list, a batch of decoys or another table is merged, the search of a page into a table, the uploads of a
 // caller's arrays, the device's `bad` flag, the merge of one table into another across contexts and devices, and what
 // every prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check
@@ -57,6 +57,38 @@ inline std::string bad_n(int32_t n) {
 inline int finish_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *t) {
   if (!ctx || !t || t->ctx != ctx) return refuse(fn_name, "bad argument (the table belongs to another context)");
   if (t->broken) return refuse(fn_name, std::string("an earlier merge into this ") + what + " table failed", PRB_ERR_STATE);
+  return PRB_OK;
+}
+
+// ---- prb_targetset_finish / prb_grouprank_finish: the ranked lists of a run table (rank_kernels.hpp) to the host
+// fill[0, nlists] (the last one 0) scanned, the filled slots - at most `entries` - gathered by list and rank on the
+// device by gather(off, total, out), and copied to `recs` in one copy
+template <class Rec, class Gather>
+int finish_ranked(const char *fn_name, prb_ctx *ctx, const int32_t *fill, int64_t nlists, size_t entries, std::vector<Rec> &recs, Gather gather) {
+  recs.clear();
+  if (nlists <= 0) return PRB_OK;
+  int rc;
+  ScratchBuf off, out, tmp;
+  if ((rc = off.ensure(((size_t)nlists + 1) * 8))) return rc;
+  auto fills = rocprim::make_transform_iterator(fill, ToI64());
+  if ((rc = with_temp(tmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
+         return rocprim::exclusive_scan(t, b, fills, off.as<int64_t>(), (int64_t)0, (size_t)nlists + 1, rocprim::plus<int64_t>(), ctx->stream);
+       })))
+    return rc;
+  int64_t total = 0;
+  PRB_HIP(hipMemcpyAsync(&total, off.as<int64_t>() + nlists, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  if (total < 0 || (uint64_t)total > (uint64_t)entries) return refuse(fn_name, "bad record count " + std::to_string(total), PRB_ERR_STATE);
+  if (!total) return PRB_OK;
+  try {
+    recs.resize((size_t)total);
+  } catch (const std::exception &e) {
+    return refuse(fn_name, e.what(), PRB_ERR_NOMEM);
+  }
+  if ((rc = out.ensure((size_t)total * sizeof(Rec)))) return rc;
+  PRB_HIP(gather(off.as<int64_t>(), total, out.p));
+  PRB_HIP(hipMemcpyAsync(recs.data(), out.p, (size_t)total * sizeof(Rec), hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
   return PRB_OK;
 }
 

@@ -4,13 +4,6 @@
 
 using namespace prb;
 
-namespace {
-// a fill count as what the scan of prb_targetset_finish adds up
-struct FillToI64 {
-  __host__ __device__ int64_t operator()(const int32_t &x) const { return (int64_t)x; }
-};
-} // namespace
-
 // every key, payload slot and fill count of the table back to "nothing", on its own device and stream
 static int clear_target_table(prb_targetset &t) {
   PRB_HIP(hipSetDevice(t.ctx->device));
@@ -95,35 +88,13 @@ int prb_targetset_merge(prb_ctx *ctx, prb_targetset *dst, prb_targetset *src) {
 int prb_targetset_finish(prb_ctx *ctx, prb_targetset *ts) {
   if (int rc = finish_guard("prb_targetset_finish", "per-target", ctx, ts)) return rc;
   if (ts->finished) return PRB_OK; // (the records are on the host already)
-  ts->pairs.clear();
   PRB_HIP(hipSetDevice(ctx->device));
-  const int64_t T = ts->targets();
-  if (T > 0) {
-    int rc;
-    ScratchBuf off, out, tmp;
-    if ((rc = off.ensure(((size_t)T + 1) * 8))) return rc;
-    auto fills = rocprim::make_transform_iterator(ts->fill_of(ts->table.p), FillToI64());
-    if ((rc = with_temp(tmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
-           return rocprim::exclusive_scan(t, b, fills, off.as<int64_t>(), (int64_t)0, (size_t)T + 1, rocprim::plus<int64_t>(), ctx->stream);
-         })))
-      return rc;
-    int64_t total = 0;
-    PRB_HIP(hipMemcpyAsync(&total, off.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PRB_HIP(hipStreamSynchronize(ctx->stream));
-    if (total < 0 || (uint64_t)total > (uint64_t)ts->entries())
-      return refuse("prb_targetset_finish", "bad record count " + std::to_string(total), PRB_ERR_STATE);
-    if (total) {
-      try {
-        ts->pairs.resize((size_t)total);
-      } catch (const std::exception &e) {
-        return refuse("prb_targetset_finish", e.what(), PRB_ERR_NOMEM);
-      }
-      if ((rc = out.ensure((size_t)total * sizeof(prb_target_pair)))) return rc;
-      PRB_HIP(launch_target_gather(ts->keys_of(ts->table.p), ts->slots_of(ts->table.p), off.as<int64_t>(), T, ts->n, total, out.p, ctx->stream));
-      PRB_HIP(hipMemcpyAsync(ts->pairs.data(), out.p, (size_t)total * sizeof(prb_target_pair), hipMemcpyDeviceToHost, ctx->stream));
-      PRB_HIP(hipStreamSynchronize(ctx->stream));
-    }
-  }
+  if (int rc = finish_ranked("prb_targetset_finish", ctx, ts->fill_of(ts->table.p), ts->targets(), ts->entries(), ts->pairs,
+                             [&](const int64_t *off, int64_t total, void *out) {
+                               return launch_target_gather(ts->keys_of(ts->table.p), ts->slots_of(ts->table.p), off, ts->targets(), ts->n, total, out,
+                                                           ctx->stream);
+                             }))
+    return rc;
   ts->finished = true;
   ts->release(); // (only the host records are needed from here on)
   return PRB_OK;

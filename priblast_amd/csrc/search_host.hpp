@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the nine result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset, prb_gnullset, prb_evalset): whose they are, whether they can still be merged into, and the block on the device that
+// What the ten result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -466,7 +466,7 @@ struct TableState {
   int64_t counts[3] = {0, 0, 0};
   DevBuf table;                // the table proper, one block (every table says what it holds)
   bool bad = false;            // the device's `bad` flag, as the last call left it (fetch_bad, capi_tables.hpp) - of the
-  DevBuf badflag;              // tables that keep one of their own: prb_nullset, prb_groupset, prb_gnullset, prb_evalset
+  DevBuf badflag;              // tables that keep one of their own: prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset
   // What their release() starts with - nothing of such a table is released while work on it may still be queued on its
   // context's stream: false = there is no context yet, and so nothing to release
   bool quiesce() const {
@@ -485,8 +485,9 @@ struct MergeTable : TableState {
   std::vector<uint8_t> merged; // per page of db
 };
 
-// The tables that live for a whole run and are keyed by the database's targets (page, db_id) (prb_targetset, prb_covset):
-// such a table takes any number of batches, so it keeps a bit per (page, query identifier)
+// The tables that live for a whole run and are keyed by the database's targets (page, db_id) (prb_targetset, prb_covset)
+// or by its groups (prb_grouprank: one "page", its "targets" the groups): such a table takes any number of batches, so
+// it keeps a bit per (page, query identifier)
 struct RunTable : TableState {
   std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
   std::vector<std::vector<uint64_t>> merged;  // per page: a bit per query identifier merged, grown on demand
@@ -746,6 +747,34 @@ struct prb_groupset : prb::MergeTable {
     for (prb::DevBuf &b : map_dev) b.release();
   }
   ~prb_groupset() { release(); } // (also on the error paths of prb_groupset_create)
+};
+
+// prb_grouprank_create .. prb_grouprank_free: the group ranking table of a run (capi_grouprank.hip): per group its n best
+// queries over as many batches as the caller likes, fed from each batch's complete group table or from a caller's
+// records (merge_group_candidates) - never by a search itself.  A run table with one "page": `merged` keeps a bit per
+// query identifier, tbase = {0, ngroups}.  It owns all its device memory.
+// The block: TargetKey[G * n], prb_group_pair[G * n], int32_t fill[G + 1] (the last one 0)
+struct prb_grouprank : prb::RunTable {
+  int32_t n = 0, ngroups = 0;
+  prb::DevBuf occ, sel;                                         // per merge: the group table's occupied slots
+  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // ... and the candidates in group order
+  prb::DevBuf h_rec;                                            // prb_grouprank_add_records: the caller's records
+  std::vector<prb_group_pair> pairs;                            // prb_grouprank_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &) override { return PRB_ERR_STATE; } // (no search feeds it)
+  size_t entries() const { return (size_t)ngroups * (size_t)n; }
+  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_group_pair)) + ((size_t)ngroups + 1) * sizeof(int32_t); }
+  // the three arrays of a block at b (the table's own, or a copy of another table's)
+  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
+  prb_group_pair *slots_of(void *b) const { return reinterpret_cast<prb_group_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
+  int32_t *fill_of(void *b) const {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_group_pair)));
+  }
+  void release() {
+    if (!quiesce()) return;
+    for (prb::DevBuf *b : {&table, &badflag, &ids, &occ, &sel, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp, &h_rec}) b->release();
+  }
+  ~prb_grouprank() { release(); } // (also on the error paths of prb_grouprank_create)
 };
 
 // prb_gnullset_create .. prb_gnullset_free: the group null table of one batch (capi_gnull.hip): the records that a group

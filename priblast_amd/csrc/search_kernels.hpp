@@ -638,6 +638,43 @@ hipError_t launch_group_select(const GroupTab &t, const uint32_t *occ, int64_t n
 // ... out[j] (prb_group_pair) of the slot idx[j] (top == nullptr, rank 0), or of the slot top[idx[j]] with rank idx[j] % n
 hipError_t launch_group_gather(const GroupTab &t, const uint32_t *idx, int64_t nrec, const uint32_t *top, int32_t n, void *out, hipStream_t s);
 
+// ============================================================================ grouprank_kernels.hip: group ranking table
+// (prb_grouprank_*)  Per group n ranked keys (TargetKey: `id` = the query's identifier), n payload slots (prb_group_pair)
+// and a fill count, the lists of rank_kernels.hpp as the per-target table keeps them.  The candidates of one merge come
+// from a batch's group table - its occupied slots cand[0, ncand), ascending; ids[q] = the identifier of query q - or
+// from a caller's records (prb_group_pair, s.query = the identifier).  bad: set when a candidate names a slot, a group, a
+// query or an identifier outside its table; such a candidate is skipped.
+// key[c] = the group of candidate c, val[c] = its slot / its index: what the stable sort by group takes
+hipError_t launch_grouprank_slot_groups(const GroupTab &t, const uint32_t *cand, int64_t ncand, uint32_t *key, uint32_t *val, uint32_t *bad,
+                                        hipStream_t s);
+hipError_t launch_grouprank_record_groups(const void *rec, int64_t nrec, int32_t ngroups, uint32_t *key, uint32_t *val, uint32_t *bad,
+                                          hipStream_t s);
+// behind that sort (key, val sorted): rkey[i] = (the energy key of candidate val[i], its identifier, val[i]), head[i] = 1
+// where key changes (and for i = 0): the first candidate of every group's run
+hipError_t launch_grouprank_slot_runs(const GroupTab &t, const int32_t *ids, int64_t ncand, const uint32_t *key, const uint32_t *val,
+                                      TargetKey *rkey, uint8_t *head, uint32_t *bad, hipStream_t s);
+hipError_t launch_grouprank_record_runs(const void *rec, int64_t nrec, int32_t ngroups, const uint32_t *key, const uint32_t *val, TargetKey *rkey,
+                                        uint8_t *head, uint32_t *bad, hipStream_t s);
+// the runs [start[r], start[r + 1]) (the last one up to ncand) of rkey - run r is group group_of[start[r]] - merged into
+// the table, a wavefront per run; no (identifier, group) may be in the table yet
+struct GroupRankRuns {
+  const TargetKey *rkey;
+  const uint32_t *group_of, *start;
+  int64_t nruns, ncand;
+};
+hipError_t launch_grouprank_slot_merge(const GroupTab &t, const int32_t *ids, const GroupRankRuns &r, int32_t n, TargetKey *keys, void *slots,
+                                       int32_t *fill, hipStream_t s);
+hipError_t launch_grouprank_record_merge(const void *rec, int64_t nrec, const GroupRankRuns &r, int32_t ngroups, int32_t n, TargetKey *keys,
+                                         void *slots, int32_t *fill, hipStream_t s);
+// prb_grouprank_merge: per group, the table's and src's ranked entries merged under the table's order, the first n kept,
+// in the table (src is only read); a wavefront per group
+hipError_t launch_grouprank_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
+                                 int64_t ngroups, int32_t n, hipStream_t s);
+// prb_grouprank_finish: out[0, total) = the filled slots by group, then rank (`rank` set); off = the exclusive scan of
+// fill over ngroups + 1 values
+hipError_t launch_grouprank_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t ngroups, int32_t n, int64_t total,
+                                   void *out, hipStream_t s);
+
 // ============================================================================ gnull_kernels.hip: the group null table
 // (prb_gnullset_*)  The kept (query, group) records of a finished group table, and per record how the query's decoys
 // fare against the group.  lookup[q * ngroups + g] = the record of (q, g), all ones: not kept.  A record's counters: the

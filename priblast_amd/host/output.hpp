@@ -100,6 +100,9 @@ struct GroupView : QueryView {
   const int32_t *group_sizes = nullptr;
 };
 int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+// Lines of `ris -t -G FILE -R N` (prb_grouprank_pairs): the same line for every record, in the records' order (by group,
+// then by rank - not grouped by query): names and qlen_unmasked are indexed by the records' s.query, an identifier.
+int64_t format_grouprank_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
 // Lines of `ris -t -G FILE -P N` (prb_gnullset_pairs): the line of `-t -G` for every kept record, in the records' order,
 // with the null columns of `-t -z` behind it:

@@ -57,8 +57,15 @@
 // sub-batches - into an evalset on the GPU (prb_search_page_scored), then M shuffled decoys of each query against the whole
 // database (prb_search_page_null_hits: only their hits' energy keys are kept); the evalset is closed and the kept hits
 // looked up in it (prb_evalset_score).  `-E` needs -k and is refused with -b, -t, -n, -q, -r, -c, -z, -G, -P and in rank mode.
+// `ris -t -G FILE -R N` is `-r` at the level of the groups: the `-t -G` lines of each GROUP's N queries of lowest minimum
+// energy over all the queries of the run.  A group's members may lie on any page, so a batch is searched against every
+// page into its group table as for `-t -G` (with PRB_SPLIT the workers' tables merged), and that table - complete, never
+// copied to the host - is merged on the device into the group ranking table that the worker owns for the whole run
+// (prb_grouprank_add_groupset, under the queries' input positions); at the end the first worker merges the others' into
+// its own (prb_grouprank_merge), and only N records per group reach the host, written by group and rank.  `-R` needs -G
+// and is refused with -n and -P; everything else is refused through -G.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E have one table (kSwitchTable) that every
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist and load_groups, which read the files of -L and -G), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
@@ -182,7 +189,7 @@ void usage() {
             "              target of the database), and behind it the group's name, its members with a hit, its targets and\n"
             "              the members' hits; lines by query, then group in database order; with -n N the N best groups of\n"
             "              each query, by rank (with -n, -u, -j, -L and the search options; not with -z, -k, -q, -r, -c, -b,\n"
-            "              nor with WORLD_SIZE > 1: the best queries per group are not implemented)\n"
+            "              nor with WORLD_SIZE > 1; the best queries per group: -R)\n"
             "    -P INT    with -t -G: an empirical p-value per query-group pair from INT shuffled decoys of each query, as -z\n"
             "              makes them: behind every -t -G line the decoys per query, how many of them have a hit against a\n"
             "              target of the group (NullHits), how many of those reach the group's minimum interaction energy or\n"
@@ -201,6 +208,11 @@ void usage() {
             "              searches per query, and the pooled null has millions of energies with INT = 5 to 10 - keep INT small\n"
             "              (1 <= INT <= 100000; with -u, -j, -L, -s and the search options; not with -b, -t, -n, -q, -r, -c, -z,\n"
             "              -G, -P, nor with WORLD_SIZE > 1; PRB_SPLIT has no effect)\n"
+            "    -R INT    with -t -G: the -t -G lines of only the INT queries of lowest minimum interaction energy per group\n"
+            "              over all the queries, written at the end of the run by group in database order, then rank (ties by\n"
+            "              the query's place in the input file; 1 <= INT <= 1024; with -u, -j, -L and the search options; not\n"
+            "              with -n, -P, nor with what -G can't be combined with; with one process per GPU, WORLD_SIZE > 1,\n"
+            "              it is not implemented; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -224,8 +236,9 @@ thread_local bool t_team_thread = false;
 // What a run writes, decided once after parsing (output_mode): a line or record per hit, `-t` a line per pair,
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
-// `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored };
+// `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score, `-t -G -R` the N best
+// query-group pairs per group.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank };
 // -z, -P, -E: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
 // (search_null_batch, search_gnull_batch, search_scored_batch) - and by one worker: there is no merge of two of them
 constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m == OutputMode::kGroupNull || m == OutputMode::kScored; }
@@ -234,7 +247,7 @@ constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m ==
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -259,6 +272,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'P', "an empirical p-value per query-group pair from N shuffled decoys", bit(kZ) | bit(kK) | bit(kQ) | bit(kR) | bit(kC) | bit(kB), kG, true},
     {'E', "an E-value and a q-value per interaction site from N pooled decoys per query",
      bit(kB) | bit(kT) | bit(kN) | bit(kQ) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP), kK, true},
+    // (what -G can't be combined with, and one process per GPU, are refused through -G's row, in its words)
+    {'R', "the N best queries per group", bit(kN) | bit(kP), kG, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -270,6 +285,7 @@ struct Args {
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
+  int grouprank = 0;                                // -R, likewise
   int decoys = 0;                                   // -z, -P or -E, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
@@ -283,7 +299,8 @@ struct Worker {
   prb_db *db = nullptr;
   prb_targetset *targets = nullptr;                   // -r: this worker's table, for the whole run
   prb_covset *coverage = nullptr;                     // -c: this worker's table, for the whole run
-  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c: (input position, unmasked length) of the queries it prepared
+  prb_grouprank *grouprank = nullptr;                 // -R: this worker's table, for the whole run
+  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c, -R: (input position, unmasked length) of the queries it prepared
 };
 
 // The one place where what a search returned is freed.
@@ -312,7 +329,7 @@ struct BatchResult {
   Handle<prb_profset> prof;                    // kProfile
   Handle<prb_tophits> tophits;                 // kTopHits
   Handle<prb_nullset> null;                    // kNull
-  Handle<prb_groupset> groups;                 // kGroups
+  Handle<prb_groupset> groups;                 // kGroups; kGroupRank: until it is merged into the worker's table
   Handle<prb_gnullset> gnull;                  // kGroupNull
   std::vector<prb_eval_score> scores;          // kScored: of the records of `tophits`, in their order
 };
@@ -641,8 +658,8 @@ void check_switches(const Args &a) {
     // (-Z goes with either switch that makes decoys)
     if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE]))) die("Error: " + described(s) + " needs " + described(need));
   }
-  for (Switch s : {kR, kK, kN})
-    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : a.top; a.given[s] && (v < 1 || v > 1024))
+  for (Switch s : {kR, kK, kN, kGR})
+    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
@@ -655,6 +672,7 @@ OutputMode output_mode(const Args &a) {
   if (a.given[kE]) return OutputMode::kScored;
   if (a.given[kZ]) return OutputMode::kNull;
   if (a.given[kP]) return OutputMode::kGroupNull;
+  if (a.given[kGR]) return OutputMode::kGroupRank;
   if (a.given[kG]) return OutputMode::kGroups;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
@@ -664,7 +682,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -692,6 +710,7 @@ Args parse_args(int argc, char **argv) {
     case 'G': a.given[kG] = true, a.groupfile = optarg; break;
     case 'P': a.given[kP] = true, a.decoys = parse_count(optarg); break;
     case 'E': a.given[kE] = true, a.decoys = parse_count(optarg); break;
+    case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -912,6 +931,8 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
     if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
     if (r.a.mode == OutputMode::kCoverage && prb_covset_create(w.ctx, w.db, &w.coverage)) die(prb_last_error());
+    if (r.a.mode == OutputMode::kGroupRank && prb_grouprank_create(w.ctx, (int32_t)r.groups.names.size(), r.a.grouprank, &w.grouprank))
+      die(prb_last_error());
   }
 }
 
@@ -983,6 +1004,7 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair\n";
   case OutputMode::kGroups:
+  case OutputMode::kGroupRank:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
                     "Group Hits\n";
@@ -1122,7 +1144,8 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
-  case OutputMode::kGroups: res.groups = create_groupset(r, w, qb); break;
+  case OutputMode::kGroups:
+  case OutputMode::kGroupRank: res.groups = create_groupset(r, w, qb); break; // (-R: the batch's group table, merged into the worker's)
   default: break; // (kTargets, kCoverage: the worker's own table, for the whole run - open_workers)
   }
   if (rc) die(prb_last_error());
@@ -1140,7 +1163,8 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &o, mine.tophits.get()); break;
-  case OutputMode::kGroups: rc = prb_search_page_groups(w.ctx, qb, w.db, page, &o, mine.groups.get()); break;
+  case OutputMode::kGroups:
+  case OutputMode::kGroupRank: rc = prb_search_page_groups(w.ctx, qb, w.db, page, &o, mine.groups.get()); break;
   case OutputMode::kSummary: {
     prb_pairset *ps = nullptr;
     rc = prb_search_page_summary(w.ctx, qb, w.db, page, &o, &ps);
@@ -1158,8 +1182,9 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   if (rc) die(prb_last_error());
 }
 
-// the table of `mine` - with the tables of `others` merged into it first - to the host: one copy of its records
-void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<BatchResult *> &others = {}) {
+// the table of `mine` - with the tables of `others` merged into it first - to the host: one copy of its records; -R: into
+// the worker's table of the run under the input positions of the batch `p`, on the device, and dropped
+void finish_table(const Run &r, Worker &w, const Prepared &p, BatchResult &mine, const std::vector<BatchResult *> &others = {}) {
   auto run = [&](auto ops, auto member) {
     for (BatchResult *o : others)
       if (ops.merge(w.ctx, (mine.*member).get(), (o->*member).get())) die(prb_last_error());
@@ -1174,6 +1199,12 @@ void finish_table(const Run &r, Worker &w, BatchResult &mine, const std::vector<
       if (prb_groupset_merge(w.ctx, mine.groups.get(), o->groups.get())) die(prb_last_error());
     if (prb_groupset_finish(w.ctx, mine.groups.get(), r.a.given[kN] ? r.a.top : 0)) die(prb_last_error());
     break;
+  case OutputMode::kGroupRank: // (a group's members may lie on any page: only the batch's whole group table is ranked)
+    for (BatchResult *o : others)
+      if (prb_groupset_merge(w.ctx, mine.groups.get(), o->groups.get())) die(prb_last_error());
+    if (prb_grouprank_add_groupset(w.ctx, w.grouprank, mine.groups.get(), p.ids.data())) die(prb_last_error());
+    mine.groups.reset();
+    break;
   default: break; // (no table of the batch's own to finish: create_table)
   }
 }
@@ -1187,9 +1218,9 @@ BatchResult empty_result(const Run &r) {
   return res;
 }
 
-// -r, -c: the lines are written at the end of the run, with every query's unmasked length by its place in the input
+// -r, -c, -R: the lines are written at the end of the run, with every query's unmasked length by its place in the input
 void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
-  if (r.a.mode != OutputMode::kTargets && r.a.mode != OutputMode::kCoverage) return;
+  if (r.a.mode != OutputMode::kTargets && r.a.mode != OutputMode::kCoverage && r.a.mode != OutputMode::kGroupRank) return;
   for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
 }
 
@@ -1416,7 +1447,7 @@ BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
   create_table(r, w, p.qb, res);
   for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
-  finish_table(r, w, res);
+  finish_table(r, w, p, res);
   note_target_queries(r, w, p);
   release_batch(p);
   return res;
@@ -1551,6 +1582,7 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     return written_or_die(prb::format_gnull_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kTargets:
+  case OutputMode::kGroupRank:
   case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
   case OutputMode::kSummary: {
     prb::SummaryView v;
@@ -1767,7 +1799,7 @@ struct Team {
       wait([&] { return tb->arrived == r.workers.size(); });
       std::vector<BatchResult *> others;
       for (size_t j = 1; j < tb->table.size(); j++) others.push_back(&tb->table[j]);
-      finish_table(r, w, mine, others);
+      finish_table(r, w, p, mine, others);
       res = std::move(tb->res);
       res.top = std::move(mine.top);
       res.prof = std::move(mine.prof);
@@ -1967,8 +1999,34 @@ void write_regions(Run &r) {
   written_or_die(prb::format_region_batch(v, r.tabs, 0, sink, prb::format_threads()));
 }
 
+// -R: the first worker merges the others' tables into its own on the device and finishes it; the lines by group and rank,
+// numbered from 0
+void write_grouprank(Run &r) {
+  Worker &w0 = r.workers[0];
+  std::vector<int32_t> qlen(r.seqs.size(), 0);
+  for (Worker &w : r.workers) {
+    for (const auto &[id, len] : w.target_qlen) qlen[(size_t)id] = len;
+    if (&w != &w0 && prb_grouprank_merge(w0.ctx, w0.grouprank, w.grouprank)) die(prb_last_error());
+  }
+  if (prb_grouprank_finish(w0.ctx, w0.grouprank)) die(prb_last_error());
+  prb::GroupView v;
+  v.nq = r.names.size();
+  v.names = r.names.data();
+  v.qlen_unmasked = qlen.data();
+  v.r = prb_grouprank_pairs(w0.grouprank);
+  v.n = prb_grouprank_size(w0.grouprank);
+  std::vector<const char *> gnames;
+  set_groups(v, r, gnames);
+  for (int64_t i = 0; i < v.n; i++)
+    if (!in_range(r, v.nq, v.r[i])) die("Error: bad record in the table of the best queries per group");
+  LineSink sink;
+  sink.fd = fileno(r.out);
+  written_or_die(prb::format_grouprank_batch(v, r.tabs, 0, sink, prb::format_threads()));
+}
+
 void close_run(Run &r, int64_t total_hits) {
   if (r.a.mode == OutputMode::kTargets && r.rank == 0) write_targets(r);
+  if (r.a.mode == OutputMode::kGroupRank && r.rank == 0) write_grouprank(r);
   if (r.a.mode == OutputMode::kCoverage && r.rank == 0) write_regions(r);
   if (r.a.binary()) {
     put<int64_t>(r.out, kEnd);
@@ -1979,6 +2037,7 @@ void close_run(Run &r, int64_t total_hits) {
   for (auto &w : r.workers) {
     prb_targetset_free(w.targets);
     prb_covset_free(w.coverage);
+    prb_grouprank_free(w.grouprank);
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
     prb_ctx_destroy(w.ctx);
