@@ -219,6 +219,12 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  * "eval" (prb_search_page_scored / _null_hits, prb_evalset_add_keys: the append of the keys, launches = 1 per sub-batch with
  *   final hits; prb_evalset_close: per list the sorts and gathers and the count, then the ranks and the suffix minima;
  *   prb_evalset_score: the look-up, 1);
+ * "feature" (prb_search_page_features / prb_featset_add_hits: the fold into the feature table - the items per pair, their
+ *   scan, the item kernel, its long-run form, the unassigned count, the selection of the items with a hit and the append;
+ *   launches = 7 per sub-batch with final hits, or 3 - the counts, their scan and the unassigned count - when its targets
+ *   have no feature, and 2 more - head flags and the selection of the runs' first hits - in front per prb_featset_add_hits
+ *   with hits; prb_featset_merge: 1; prb_featset_finish: the cells' record counts, their scan and the gather, launches = 3,
+ *   or none for a table without records);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -1013,6 +1019,97 @@ void prb_evalset_sizes(const prb_evalset *es, int64_t *nreal, int64_t *ndecoy);
 void prb_evalset_counts(const prb_evalset *es, int64_t counts[3]);
 void prb_evalset_decoy_counts(const prb_evalset *es, int64_t counts[3]);
 void prb_evalset_free(prb_evalset *es);
+
+/* ---- one record per (query, annotated feature of a target) (`ris -t -A FILE`): a feature table on the device ----
+ * `-t` answers "which targets", `-G` folds targets into genes; this table looks one level below the target: WHERE on a
+ * transcript a query binds, in the terms transcripts are annotated with (5'UTR, CDS, 3'UTR, an exon, a motif).
+ * An ANNOTATION is a list of features; feature i is (page, db_id, start, end): start <= end, inclusive, in the target's
+ * FORWARD coordinates - the numbers that the base-pair field of a result line prints, the convention of
+ * prb_target_region.start / end: length - 1 - (text position - start_pos).  Features of one target may overlap, nest or
+ * repeat; a target may have none.
+ * The SPAN of a final hit on its target is prb_covset's: [min(db0, dbN), max(db0, dbN)] of its first and last base pair in
+ * the `-s 0` form, in forward coordinates.  A hit BELONGS to every feature of its target that its span shares at least
+ * one position with; it is INSIDE a feature when its span lies wholly within it.  A hit that belongs to no feature is
+ * UNASSIGNED: it is counted (prb_featset_unassigned) and appears in no record.
+ * One record per (query, feature) with at least one hit:
+ *   s         a prb_pair_summary over the feature's hits under exactly the rules of prb_search_page_summary: hits; e_min
+ *             with strict `<`, so the first hit in output order with that e_tot is the best hit; e_sum added left to right
+ *             in output order from 0.0; the best hit's e_acc, e_hyb, bp_first, bp_last; s.db_id = the target
+ *   page      the target's page;  feature: the caller's index i
+ *   inside    the hits among s.hits whose span lies wholly within the feature
+ * The finished records come by query ascending, then page, then - within a page - in the order of the (query, target)
+ * runs of the merged lists, which for a search is db_id ascending; a target's features come by (start, end, index).
+ * A feature lies in one page, a (query, target) run lies in one sub-batch, and every column is a count or a left-to-right
+ * fold in output order: the records depend - bit for bit - neither on how the batch is cut into sub-batches and chunks
+ * (PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS), nor on page residency, nor on the order of the pages, nor on how the pages
+ * are shared between tables that are merged later.
+ *   prb_annot_create           n >= 0 features of db checked one by one - page and db_id in range, 0 <= start <= end <
+ *                              the target's length; the first bad entry is PRB_ERR_ARG with its index in the message, and
+ *                              nothing is made -, sorted by (page, db_id, start, end, index) on the host and uploaded as
+ *                              one CSR per page: the first feature of every sequence, then the features' two ends - as
+ *                              positions of the page's text - and their indices, beside the sequences' start positions
+ *                              and lengths.  It belongs to `db` (as a prb_pairmask does) and must be freed before it,
+ *                              and after every table made with it
+ *   prb_featset_create         an empty table for qb and the annotation (of a database on ctx's device)
+ *   prb_search_page_features   the search of prb_search_page_summary against `page`, every sub-batch's final hits folded
+ *                              on the device; nothing leaves it.  Argument checks and option limits are those of
+ *                              prb_search_page_summary; it honours distinct_sites, chain_sites (the kept hits are folded)
+ *                              and allowed_pairs.  Refusals (PRB_ERR_ARG, or PRB_ERR_STATE for a finished or broken table;
+ *                              the table untouched) as prb_search_page_groups: another context, batch or database, a
+ *                              page merged twice, a second value of distinct_sites or chain_sites
+ *   prb_featset_add_hits       the same fold for a caller's list of final hits of one page in host memory: prb_hit records
+ *                              with their pair array as prb_covset_add_hits takes them, ascending by `query` (0 <= query <
+ *                              the batch's queries); the (query, db_id) runs are the maximal runs of consecutive records.
+ *                              The list is checked on the host first (PRB_ERR_ARG for an inconsistent record); a span that
+ *                              leaves its sequence fails with PRB_ERR_STATE - before anything is merged here; the kernels
+ *                              check again and raise the table's `bad` flag.  Stage counts are not touched
+ *   prb_featset_merge          two unfinished tables over disjoint page sets into one, on the device, with the contract of
+ *                              prb_topset_merge: src may live on another device (a peer copy, else through pinned host
+ *                              memory; the caller's device is restored); both were made for the same queries and for equal
+ *                              annotations (the handles may differ).  src is left empty but valid
+ *   prb_featset_finish         the per-(page, query) record counts scanned by query, then page, the records gathered in
+ *                              that order on the device and copied to the host in one copy; the device memory is released,
+ *                              and nothing can be merged after it (a second call does nothing)
+ *   prb_featset_unassigned     the final hits merged so far that belong to no feature
+ *   prb_featset_counts         the stage counts of prb_pairset_counts, summed over the searched pages
+ * On the device a sub-batch's work items are (pair run, feature of its target): a count per run from the CSR, an exclusive
+ * scan, and an item kernel - a lane per item, which finds its run by binary search and walks it in list order; items of
+ * runs longer than 128 hits go to a wavefront each, which tests 64 hits at a time and adds the members' energies one by
+ * one in list order (the same sum, bit for bit).  Items without a hit are compacted out; the survivors are appended to the
+ * table's block, which grows geometrically.  Stage timer "feature" (launch counts: prb_ctx_stage_ms). */
+typedef struct prb_feature_pair {
+  prb_pair_summary s;     /* over the feature's hits; s.db_id = the target */
+  int32_t page, feature;  /* the target's page; the feature's index in the caller's list */
+  int64_t inside;         /* hits whose span lies wholly within the feature */
+} prb_feature_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_feature_pair) == 80, "prb_feature_pair: no padding");
+#endif
+typedef struct prb_annot prb_annot;
+typedef struct prb_featset prb_featset;
+int prb_annot_create(prb_ctx *ctx, const prb_db *db, int64_t n, const int32_t *page, const int32_t *db_id, const int32_t *start,
+                     const int32_t *end, prb_annot **out);
+int64_t prb_annot_count(const prb_annot *an);
+void prb_annot_free(prb_annot *an);
+int prb_featset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_annot *an, prb_featset **out);
+int prb_search_page_features(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_featset *fs);
+int prb_featset_add_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,
+                         int64_t npairs);
+int prb_featset_merge(prb_ctx *ctx, prb_featset *dst, prb_featset *src);
+int prb_featset_finish(prb_ctx *ctx, prb_featset *fs);
+int64_t prb_featset_size(const prb_featset *fs);
+const prb_feature_pair *prb_featset_records(const prb_featset *fs);
+void prb_featset_counts(const prb_featset *fs, int64_t counts[3]);
+int64_t prb_featset_unassigned(const prb_featset *fs);
+void prb_featset_free(prb_featset *fs);
+/* The lines of `ris -t -A FILE` for one batch: recs[0, nrecs) as prb_featset_records returns them, one line each in that
+ * order, numbered from id0 on: the `-t` line of s (prb_write_summary_lines' columns), and behind it
+ *   ,<feature name>,<start>-<end>,<inside>
+ * feat_names[i], feat_start[i], feat_end[i] for every feature i of the annotation (nfeat of them).  Arguments and results
+ * as prb_write_top_lines. */
+int prb_write_feature_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                            const prb_feature_pair *recs, int64_t nrecs, const char *const *feat_names, const int32_t *feat_start,
+                            const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
 
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered

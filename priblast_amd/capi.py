@@ -89,6 +89,11 @@ GNULL_DTYPE = np.dtype(GROUP_DTYPE.descr + [("decoys", "<i4"), ("pad", "<i4"), (
                                             ("null_min", "<f8")])
 assert GNULL_DTYPE.itemsize == 120
 
+# prb_feature_pair: the embedded prb_pair_summary's fields (over the feature's hits), then the target's page, the feature's
+# index in the annotation and the hits wholly inside the feature (`ris -t -A FILE`)
+FEATURE_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("feature", "<i4"), ("inside", "<i8")])
+assert FEATURE_DTYPE.itemsize == 80
+
 # prb_eval_score: a real hit's place among its query's real hits and among the pooled hits of its decoys (`ris -k N -E M`)
 EVAL_DTYPE = np.dtype([("decoys", "<i4"), ("reserved", "<i4"), ("null_le", "<i8"), ("rank", "<i8"), ("q_num", "<u4"), ("q_den", "<u4")])
 assert EVAL_DTYPE.itemsize == 32
@@ -262,6 +267,23 @@ SYMBOLS = {
     "prb_evalset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_evalset_decoy_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_evalset_free": (None, [ctypes.c_void_p]),
+    "prb_annot_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, P(ctypes.c_void_p)]),
+    "prb_annot_count": (c_i64, [ctypes.c_void_p]),
+    "prb_annot_free": (None, [ctypes.c_void_p]),
+    "prb_featset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
+    "prb_search_page_features": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_featset_add_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64]),
+    "prb_featset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_featset_records": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_featset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_featset_unassigned": (c_i64, [ctypes.c_void_p]),
+    "prb_featset_free": (None, [ctypes.c_void_p]),
+    "prb_write_feature_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                               P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, ctypes.c_int, P(c_i64),
+                                               P(c_i64)]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -934,6 +956,74 @@ def search_groups(ctx, qb, db, group_of_page, ngroups, n=0, opts=None, pages=Non
     return (recs, counts) if with_counts else recs
 
 
+class Annotation:
+    """prb_annot: the annotated features of one database on the device.  features = [(page, db_id, start, end)], start <= end
+    inclusive, in the target's forward coordinates (what the result lines print).  Close it after every FeatSet made with
+    it, and before its database."""
+
+    def __init__(self, ctx, db, features):
+        f = np.ascontiguousarray(np.asarray(features, np.int32).reshape(-1, 4).T)
+        h = ctypes.c_void_p()
+        n = f.shape[1]
+        _check(lib().prb_annot_create(ctx.h, db.h, n, *[f[k].ctypes.data if n else None for k in range(4)], ctypes.byref(h)))
+        self.h, self.ctx, self.db = h, ctx, db
+
+    def count(self):
+        return lib().prb_annot_count(self.h)
+
+    def close(self):
+        if self.h:
+            lib().prb_annot_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class FeatSet(_Table):
+    """prb_featset: per (query, annotated feature of a target) of one batch, the `-t` summary over the final hits whose span
+    meets the feature, in a table on the device that pages are folded into.  Close it before its annotation."""
+    PREFIX = "featset"
+
+    def __init__(self, ctx, qb, annot):
+        h = ctypes.c_void_p()
+        _check(lib().prb_featset_create(ctx.h, qb.h, annot.h, ctypes.byref(h)))
+        self.h, self.ctx, self.qb, self.annot = h, ctx, qb, annot
+
+    def merge(self, db, page, opts=None, qb=None):
+        """prb_search_page_features: searches the batch against `page` and folds its final hits into the table"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_features(self.ctx.h, (qb or self.qb).h, db.h, page, ctypes.byref(o), self.h))
+
+    def add_hits(self, page, hits, bp):
+        """prb_featset_add_hits: a list of final hits of `page` (HIT_DTYPE records ascending by `query`, with the int32 [n, 2]
+        pairs their bp_offset / bp_count index) folded into the table"""
+        hits = np.ascontiguousarray(hits, HIT_DTYPE)
+        bp = np.ascontiguousarray(bp, np.int32)
+        _check(lib().prb_featset_add_hits(self.ctx.h, self.h, page, hits.ctypes.data if len(hits) else None, len(hits),
+                                          bp.ctypes.data if bp.size else None, bp.size // 2))
+
+    def finish(self):
+        """prb_featset_finish -> structured array FEATURE_DTYPE (a copy): by query, page, target and feature"""
+        return self._finish("records", FEATURE_DTYPE)
+
+    def unassigned(self):
+        return lib().prb_featset_unassigned(self.h)
+
+
+def search_features(ctx, qb, db, annot, opts=None, pages=None, with_counts=False):
+    """The feature table of the batch over the pages (all of them, in this order, by default) -> (structured array
+    FEATURE_DTYPE, unassigned hits).  with_counts: -> (records, unassigned, (seed, ungapped, final) counts)."""
+    with FeatSet(ctx, qb, annot) as fs:
+        for p in range(db.npages) if pages is None else pages:
+            fs.merge(db, p, opts)
+        recs, un, counts = fs.finish(), fs.unassigned(), fs.counts()
+    return (recs, un, counts) if with_counts else (recs, un)
+
+
 class GroupRank(_Table):
     """prb_grouprank: the N best queries per group of database sequences, in a table on the device that any number of
     batches is merged into - each as its complete, unfinished GroupSet, or as GROUP_DTYPE records -; every batch names its
@@ -1286,6 +1376,15 @@ def write_group_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes,
     gsz = np.ascontiguousarray(group_sizes, np.int32)
     return _write(lib().prb_write_group_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
                   gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
+
+
+def write_feature_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start, feat_end, id0=0, fd=-1):
+    """prb_write_feature_lines over FEATURE_DTYPE records; feat_names / feat_start / feat_end are indexed by their `feature`"""
+    recs = np.ascontiguousarray(recs, FEATURE_DTYPE)
+    names = (ctypes.c_char_p * max(len(feat_names), 1))(*[n.encode() for n in feat_names])
+    fs, fe = np.ascontiguousarray(feat_start, np.int32), np.ascontiguousarray(feat_end, np.int32)
+    return _write(lib().prb_write_feature_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), names,
+                  fs.ctypes.data, fe.ctypes.data, len(feat_names), id0, fd)
 
 
 def write_grouprank_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes, id0=0, fd=-1):

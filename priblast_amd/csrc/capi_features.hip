@@ -1,0 +1,399 @@
+// C ABI, part 15: the annotation of a database and the feature table of one batch - per (query, annotated feature of a
+// target), the `-t` summary over the final hits whose span meets the feature (prb_annot_*, prb_featset_*, `ris -t -A
+// FILE`).  The kernels are in feature_kernels.hip.  Every check of a call is made on the host before anything is
+// enqueued: a refused call leaves the table as it was.
+#include <numeric>
+
+#include "capi_tables.hpp"
+
+using namespace prb;
+
+namespace {
+
+const char *const kFinishFn = "prb_featset_finish";
+const char *const kBadHit = "a hit merged into this feature table named a query or a sequence outside it, or its span left its sequence";
+constexpr int64_t kFirstRoom = 4096; // records a new table has room for
+
+// the block with room for `need` records (at least twice what it had), what it holds kept; on the table's device
+int grow_block(prb_ctx *ctx, prb_featset *fs, int64_t need) {
+  if (need <= fs->cap) return PRB_OK;
+  const int64_t cap = std::max({need, 2 * fs->cap, kFirstRoom});
+  ScratchBuf wider;
+  if (wider.ensure(fs->head_bytes() + (size_t)cap * sizeof(prb_feature_pair)) != PRB_OK)
+    return refuse("prb_featset", "can't allocate the feature table's records (" + std::to_string(cap) + " of them)", PRB_ERR_NOMEM);
+  PRB_HIP(hipMemcpyAsync(wider.p, fs->table.p, fs->bytes(), hipMemcpyDeviceToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  std::swap(static_cast<DevBuf &>(wider), fs->table); // (the scratch buffer lets the old block go)
+  fs->cap = cap;
+  return PRB_OK;
+}
+
+// a feature table back to empty, on its own device and stream
+int clear_feature_table(prb_featset &fs) {
+  PRB_HIP(hipSetDevice(fs.ctx->device));
+  PRB_HIP(hipMemsetAsync(fs.table.p, 0, fs.head_bytes(), fs.ctx->stream));
+  PRB_HIP(hipStreamSynchronize(fs.ctx->stream));
+  fs.nrec = 0;
+  fs.unassigned = 0;
+  return PRB_OK;
+}
+
+FeatWork work_of(const prb_featset *fs) {
+  uint32_t *flags = fs->badflag.as<uint32_t>(); // bad, nlong, the 64-bit count of unassigned hits
+  return FeatWork{fs->cnt.as<int32_t>(), fs->ioff.as<int64_t>(), fs->tmp.p, fs->flag.as<uint8_t>(), fs->long_list.as<uint32_t>(), flags + 1, flags};
+}
+
+} // namespace
+
+// prb_search_page_features (per sub-batch) and prb_featset_add_hits: the list's items folded and the ones with a hit
+// appended to the block, in a bracket of the "feature" timer.  start == nullptr: the runs of the list - head flags and
+// their selection - are made here first.
+static int merge_feature_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const FeatHits &h, const uint32_t *start, int64_t npairs) {
+  const char *fn = "prb_search_page_features";
+  int rc;
+  if (page < 0 || (size_t)page >= fs->annot->pages.size()) return refuse(fn, "page out of range", PRB_ERR_STATE);
+  if (h.n <= 0) return PRB_OK;
+  if (h.n > (int64_t)UINT32_MAX) return refuse(fn, "a list of " + std::to_string(h.n) + " hits (at most 2^32 - 1)");
+  SearchWs &ws = ws_of(ctx);
+  const FeatPage pg = fs->annot->page_view((size_t)page);
+  if ((rc = ws.count.ensure(16))) return rc;
+  if ((rc = ctx->time_begin())) return rc;
+  int64_t launches = 0;
+  if (!start) {
+    if ((rc = fs->head.ensure((size_t)h.n)) || (rc = fs->start.ensure((size_t)h.n * 4))) return rc;
+    PRB_HIP(launch_pair_heads(h.query, h.db_id, h.n, fs->head.as<uint8_t>(), ctx->stream));
+    if ((rc = select_flagged(ctx, ws, nullptr, fs->head.as<uint8_t>(), fs->start.as<uint32_t>(), (size_t)h.n, &npairs))) return rc;
+    start = fs->start.as<uint32_t>();
+    launches += 2;
+  }
+  if (npairs <= 0 || npairs > h.n) return refuse(fn, std::to_string(npairs) + " pair runs for " + std::to_string(h.n) + " hits", PRB_ERR_STATE);
+  const size_t N = (size_t)npairs + 1;
+  if ((rc = fs->cnt.ensure(N * 4)) || (rc = fs->ioff.ensure(N * 8))) return rc;
+  PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
+  FeatWork w = work_of(fs);
+  PRB_HIP(launch_feat_count(h, start, npairs, pg, fs->nq, w, ctx->stream));
+  auto counts = rocprim::make_transform_iterator(fs->cnt.as<int32_t>(), ToI64());
+  if ((rc = with_temp(fs->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
+         return rocprim::exclusive_scan(t, b, counts, fs->ioff.as<int64_t>(), (int64_t)0, N, rocprim::plus<int64_t>(), ctx->stream);
+       })))
+    return rc;
+  PRB_HIP(launch_feat_unassigned(h, pg, fs->nq, w, ctx->stream));
+  launches += 3;
+  int64_t nitems = 0;
+  PRB_HIP(hipMemcpyAsync(&nitems, fs->ioff.as<int64_t>() + npairs, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  if (nitems < 0 || nitems > (int64_t)UINT32_MAX)
+    return refuse(fn, std::to_string(nitems) + " (pair, feature) items in one sub-batch (at most 2^32 - 1): lower PRB_SEARCH_PAIRS", PRB_ERR_STATE);
+  if (nitems > 0) {
+    const size_t I = (size_t)nitems;
+    if ((rc = fs->tmp.ensure(I * sizeof(prb_feature_pair))) || (rc = fs->flag.ensure(I)) || (rc = fs->long_list.ensure(I * 4)) ||
+        (rc = fs->sel.ensure(I * 4)))
+      return rc;
+    w = work_of(fs);
+    PRB_HIP(launch_feat_items(h, start, npairs, nitems, pg, w, ctx->stream));
+    PRB_HIP(launch_feat_items_long(h, start, npairs, nitems, pg, w, ctx->stream));
+    int64_t nsel = 0;
+    if ((rc = select_flagged(ctx, ws, nullptr, fs->flag.as<uint8_t>(), fs->sel.as<uint32_t>(), I, &nsel))) return rc;
+    if (nsel < 0 || nsel > nitems) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
+    if (nsel) {
+      if ((rc = grow_block(ctx, fs, fs->nrec + nsel))) return rc;
+      void *b = fs->table.p;
+      PRB_HIP(launch_feat_append(fs->tmp.p, fs->sel.as<uint32_t>(), nsel, fs->recs_of(b), fs->nrec, fs->first_of(b), fs->end_of(b), page, fs->nq,
+                                 ctx->stream));
+      fs->nrec += nsel;
+    }
+    launches += 4;
+  }
+  if ((rc = ctx->time_end(ModeTimer::kFeature, launches))) return rc;
+  uint64_t flags[2] = {0, 0};
+  PRB_HIP(hipMemcpyAsync(flags, fs->badflag.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  if ((uint32_t)flags[0]) {
+    fs->bad = true;
+    return refuse(fn, kBadHit, PRB_ERR_STATE);
+  }
+  fs->unassigned += (int64_t)flags[1];
+  return PRB_OK;
+}
+int prb_featset::take(const SubBatch &b) {
+  return merge_feature_hits(ctx, this, b.page, FeatHits{b.nfin, b.F.query, b.F.db_id, b.F.e_tot, b.F.e_acc, b.F.e_hyb, b.ends}, b.pair_start, b.npairs);
+}
+
+extern "C" {
+
+int prb_annot_create(prb_ctx *ctx, const prb_db *db, int64_t n, const int32_t *page, const int32_t *db_id, const int32_t *start,
+                     const int32_t *end, prb_annot **out) {
+  const char *fn = "prb_annot_create";
+  if (!ctx || !db || !out || n < 0 || n > INT32_MAX || (n && (!page || !db_id || !start || !end)) || db->ctx->device != ctx->device)
+    return refuse(fn, "bad argument");
+  *out = nullptr;
+  const int32_t npages = (int32_t)db->pages.size();
+  for (int64_t i = 0; i < n; i++) {
+    const std::string entry = "feature " + std::to_string(i);
+    if (page[i] < 0 || page[i] >= npages)
+      return refuse(fn, entry + ": page " + std::to_string(page[i]) + " out of range (the database has " + std::to_string(npages) + ")");
+    const DbPage &pg = db->pages[(size_t)page[i]];
+    if (db_id[i] < 0 || db_id[i] >= pg.nseq)
+      return refuse(fn, entry + ": db_id " + std::to_string(db_id[i]) + " out of range (page " + std::to_string(page[i]) + " has " +
+                            std::to_string(pg.nseq) + " sequences)");
+    const int32_t len = pg.seq_length[(size_t)db_id[i]];
+    if (start[i] < 0 || start[i] > end[i] || end[i] >= len)
+      return refuse(fn, entry + ": need 0 <= start <= end < " + std::to_string(len) + ", the target's length (got " + std::to_string(start[i]) +
+                            " and " + std::to_string(end[i]) + ")");
+  }
+  std::unique_ptr<prb_annot> an(new (std::nothrow) prb_annot());
+  if (!an) return refuse(fn, "out of host memory", PRB_ERR_NOMEM);
+  std::vector<std::vector<int32_t>> dev((size_t)npages);
+  try {
+    std::vector<int32_t> order((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+      if (page[a] != page[b]) return page[a] < page[b];
+      if (db_id[a] != db_id[b]) return db_id[a] < db_id[b];
+      if (start[a] != start[b]) return start[a] < start[b];
+      if (end[a] != end[b]) return end[a] < end[b];
+      return a < b;
+    });
+    an->pages.resize((size_t)npages);
+    for (int32_t p = 0; p < npages; p++) {
+      const DbPage &pg = db->pages[(size_t)p];
+      prb_annot::Page &g = an->pages[(size_t)p];
+      g.off.assign((size_t)pg.nseq + 1, 0);
+      g.slo.assign(pg.start_pos.begin(), pg.start_pos.begin() + pg.nseq);
+      g.slen.assign(pg.seq_length.begin(), pg.seq_length.begin() + pg.nseq);
+    }
+    for (int32_t i : order) {
+      prb_annot::Page &g = an->pages[(size_t)page[i]];
+      g.off[(size_t)db_id[i] + 1]++;
+      g.start.push_back(start[i]);
+      g.end.push_back(end[i]);
+      g.idx.push_back(i);
+    }
+    for (int32_t p = 0; p < npages; p++) {
+      prb_annot::Page &g = an->pages[(size_t)p];
+      for (size_t d = 0; d + 1 < g.off.size(); d++) g.off[d + 1] += g.off[d];
+      // what the device reads: off, slo, slen, then the features' ends in the page's text (which holds the sequences
+      // reversed) and their indices
+      std::vector<int32_t> &v = dev[(size_t)p];
+      v.insert(v.end(), g.off.begin(), g.off.end());
+      v.insert(v.end(), g.slo.begin(), g.slo.end());
+      v.insert(v.end(), g.slen.begin(), g.slen.end());
+      const size_t nf = g.idx.size();
+      std::vector<int32_t> tlo(nf), thi(nf);
+      for (size_t d = 0; d + 1 < g.off.size(); d++)
+        for (int32_t f = g.off[d]; f < g.off[d + 1]; f++) {
+          tlo[(size_t)f] = g.slo[d] + g.slen[d] - 1 - g.end[(size_t)f];
+          thi[(size_t)f] = g.slo[d] + g.slen[d] - 1 - g.start[(size_t)f];
+        }
+      v.insert(v.end(), tlo.begin(), tlo.end());
+      v.insert(v.end(), thi.begin(), thi.end());
+      v.insert(v.end(), g.idx.begin(), g.idx.end());
+    }
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  an->n = n;
+  an->db = db;
+  an->ctx = ctx; // (from here on the destructor has a device and a stream to release under)
+  PRB_HIP(hipSetDevice(ctx->device));
+  for (int32_t p = 0; p < npages; p++) {
+    const std::vector<int32_t> &v = dev[(size_t)p];
+    if (an->pages[(size_t)p].dev.ensure(std::max<size_t>(v.size() * 4, 16)) != PRB_OK)
+      return refuse(fn, "can't allocate the annotation of page " + std::to_string(p), PRB_ERR_NOMEM);
+    PRB_HIP(hipMemcpyAsync(an->pages[(size_t)p].dev.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the vectors go)
+  *out = an.release();
+  return PRB_OK;
+}
+
+int64_t prb_annot_count(const prb_annot *an) { return an ? an->n : -1; }
+void prb_annot_free(prb_annot *an) { delete an; }
+
+int prb_featset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_annot *an, prb_featset **out) {
+  const char *fn = "prb_featset_create";
+  std::unique_ptr<prb_featset> fs;
+  const bool args_ok = ctx && qb && an && qb->ctx->device == ctx->device && an->ctx->device == ctx->device;
+  if (int rc = new_table(fn, args_ok, out, fs)) return rc;
+  try {
+    fs->merged.assign(an->pages.size(), 0);
+    fs->qlen = qb->len;
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  fs->nq = qb->nq;
+  fs->annot = an;
+  fs->ctx = ctx; // (from here on the destructor has a device and a stream to release under)
+  fs->db = an->db;
+  fs->qb = qb;
+  fs->cap = kFirstRoom;
+  PRB_HIP(hipSetDevice(ctx->device));
+  if (fs->table.ensure(std::max<size_t>(fs->head_bytes() + (size_t)fs->cap * sizeof(prb_feature_pair), 16)) != PRB_OK ||
+      fs->badflag.ensure(16) != PRB_OK)
+    return refuse(fn, "can't allocate the feature table (" + std::to_string(fs->cells()) + " (page, query) cells)", PRB_ERR_NOMEM);
+  PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
+  if (int rc = clear_feature_table(*fs)) return rc;
+  *out = fs.release();
+  return PRB_OK;
+}
+
+int prb_search_page_features(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_featset *fs) {
+  const char *fn = "prb_search_page_features";
+  if (fs && fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
+  return merge_page(fn, "feature", kFinishFn, fs, ctx, qb, db, page, opts);
+}
+
+// the caller's list checked on the host - a refused call leaves the table as it was -, then as columns to the device and
+// through the fold of a sub-batch
+int prb_featset_add_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,
+                         int64_t npairs) {
+  const std::string fn = "prb_featset_add_hits";
+  if (!ctx || !fs || nhits < 0 || nhits > INT32_MAX || npairs < 0 || (nhits && (!hits || !basepairs))) return refuse(fn, "bad argument");
+  if (fs->ctx != ctx) return refuse(fn, "the feature table was made with another context");
+  if (fs->broken) return refuse(fn, "an earlier merge into this feature table failed", PRB_ERR_STATE);
+  if (fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
+  if (fs->finished) return refuse(fn, std::string("the feature table is finished (") + kFinishFn + ")", PRB_ERR_STATE);
+  if (page < 0 || (size_t)page >= fs->merged.size())
+    return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(fs->merged.size()) + ")");
+  if (fs->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this feature table");
+  const prb_annot::Page &g = fs->annot->pages[(size_t)page];
+  const int32_t nseq = (int32_t)g.slo.size();
+  std::vector<int32_t> query, db_id, ends;
+  std::vector<double> e_tot, e_acc, e_hyb;
+  try {
+    query.resize((size_t)nhits);
+    db_id.resize((size_t)nhits);
+    e_tot.resize((size_t)nhits);
+    e_acc.resize((size_t)nhits);
+    e_hyb.resize((size_t)nhits);
+    ends.resize((size_t)nhits * 4);
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  for (int64_t i = 0; i < nhits; i++) {
+    const prb_hit &x = hits[i];
+    if (x.query < 0 || x.query >= fs->nq || (i && x.query < hits[i - 1].query) || x.db_id < 0 || x.db_id >= nseq || x.bp_count < 1 ||
+        x.bp_offset < 0 || x.bp_offset + x.bp_count > npairs)
+      return refuse(fn, "hit record " + std::to_string(i) + " is inconsistent");
+    const int32_t *first = basepairs + 2 * x.bp_offset, *last = basepairs + 2 * (x.bp_offset + x.bp_count - 1);
+    const int64_t lo = std::min(first[1], last[1]), hi = std::max(first[1], last[1]);
+    const int64_t s0 = g.slo[(size_t)x.db_id];
+    if (lo < s0 || hi >= s0 + g.slen[(size_t)x.db_id])
+      return refuse(fn, "the span of hit record " + std::to_string(i) + " leaves its sequence", PRB_ERR_STATE);
+    query[(size_t)i] = x.query;
+    db_id[(size_t)i] = x.db_id;
+    e_tot[(size_t)i] = x.e_tot;
+    e_acc[(size_t)i] = x.e_acc;
+    e_hyb[(size_t)i] = x.e_hyb;
+    ends[4 * (size_t)i] = first[0], ends[4 * (size_t)i + 1] = first[1], ends[4 * (size_t)i + 2] = last[0], ends[4 * (size_t)i + 3] = last[1];
+  }
+  DeviceScope restore;
+  PRB_HIP(hipSetDevice(ctx->device));
+  fs->merged[(size_t)page] = 1;
+  if (!nhits) return PRB_OK;
+  fs->broken = true; // (until the merge is whole)
+  int rc;
+  const size_t N = (size_t)nhits;
+  if ((rc = fs->h_query.ensure(N * 4)) || (rc = fs->h_db_id.ensure(N * 4)) || (rc = fs->h_e_tot.ensure(N * 8)) || (rc = fs->h_e_acc.ensure(N * 8)) ||
+      (rc = fs->h_e_hyb.ensure(N * 8)) || (rc = fs->h_ends.ensure(N * 16)))
+    return rc;
+  PRB_HIP(hipMemcpyAsync(fs->h_query.p, query.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(fs->h_db_id.p, db_id.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(fs->h_e_tot.p, e_tot.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(fs->h_e_acc.p, e_acc.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(fs->h_e_hyb.p, e_hyb.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(fs->h_ends.p, ends.data(), N * 16, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the vectors go)
+  const FeatHits h{nhits,           fs->h_query.as<int32_t>(), fs->h_db_id.as<int32_t>(), fs->h_e_tot.as<double>(), fs->h_e_acc.as<double>(),
+                   fs->h_e_hyb.as<double>(), fs->h_ends.as<int32_t>()};
+  if ((rc = merge_feature_hits(ctx, fs, page, h, nullptr, 0))) return rc;
+  fs->broken = false;
+  return PRB_OK;
+}
+
+int prb_featset_merge(prb_ctx *ctx, prb_featset *dst, prb_featset *src) {
+  const char *fn = "prb_featset_merge";
+  if (int rc = merge_tables_guard(fn, "feature", ctx, dst, src)) return rc;
+  if (dst->bad || src->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
+  if (dst->annot != src->annot && !(dst->annot->pages == src->annot->pages))
+    return refuse(fn, "the feature tables were made with different annotations");
+  const prb_db *db = src->db;
+  const size_t npages = src->merged.size();
+  const int64_t nsrc = src->nrec, src_unassigned = src->unassigned;
+  const int rc = join_tables(
+      fn, ModeTimer::kFeature, 1, ctx, dst, src, src->bytes(), [&]() -> int { return grow_block(ctx, dst, dst->nrec + nsrc); },
+      [&](void *block) -> int {
+        void *b = dst->table.p;
+        PRB_HIP(launch_feat_join(dst->recs_of(b), dst->nrec, dst->first_of(b), dst->end_of(b), src->recs_of(block), nsrc, src->first_of(block),
+                                 src->end_of(block), dst->cells(), ctx->stream));
+        dst->nrec += nsrc;
+        dst->unassigned += src_unassigned;
+        return PRB_OK;
+      },
+      clear_feature_table);
+  // (src stays a table of its database, with no page merged: it can be finished to zero records)
+  src->db = db;
+  src->merged.assign(npages, 0);
+  return rc;
+}
+
+// the record counts of the (page, query) cells scanned by query, then page, the records gathered in that order, one copy
+int prb_featset_finish(prb_ctx *ctx, prb_featset *fs) {
+  const char *fn = kFinishFn;
+  if (int rc = finish_guard(fn, "feature", ctx, fs)) return rc;
+  if (fs->finished) return PRB_OK; // (the records are on the host already)
+  if (fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
+  fs->recs.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  const int64_t C = fs->cells();
+  if (C > 0 && fs->nrec > 0) {
+    int rc;
+    const int32_t npages = (int32_t)fs->merged.size();
+    if ((rc = fs->tmp.ensure(((size_t)C + 1) * 8)) || (rc = fs->ioff.ensure(((size_t)C + 1) * 8)) ||
+        (rc = fs->out.ensure((size_t)fs->nrec * sizeof(prb_feature_pair))))
+      return rc;
+    try {
+      fs->recs.resize((size_t)fs->nrec);
+    } catch (const std::exception &e) {
+      return refuse(fn, e.what(), PRB_ERR_NOMEM);
+    }
+    if ((rc = ctx->time_begin())) return rc;
+    void *b = fs->table.p;
+    PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
+    PRB_HIP(launch_feat_cell_counts(fs->first_of(b), fs->end_of(b), npages, fs->nq, fs->tmp.as<int64_t>(), ctx->stream));
+    if ((rc = with_temp(fs->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &bytes) {
+           return rocprim::exclusive_scan(t, bytes, fs->tmp.as<int64_t>(), fs->ioff.as<int64_t>(), (int64_t)0, (size_t)C + 1, rocprim::plus<int64_t>(),
+                                          ctx->stream);
+         })))
+      return rc;
+    int64_t total = 0;
+    PRB_HIP(hipMemcpyAsync(&total, fs->ioff.as<int64_t>() + C, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (total != fs->nrec) {
+      fs->recs.clear();
+      return refuse(fn, "bad record count " + std::to_string(total) + " (the table holds " + std::to_string(fs->nrec) + ")", PRB_ERR_STATE);
+    }
+    PRB_HIP(launch_feat_gather(fs->recs_of(b), fs->nrec, fs->first_of(b), fs->ioff.as<int64_t>(), npages, fs->nq, total, fs->out.p,
+                               fs->badflag.as<uint32_t>(), ctx->stream));
+    PRB_HIP(hipMemcpyAsync(fs->recs.data(), fs->out.p, (size_t)total * sizeof(prb_feature_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->time_end(ModeTimer::kFeature, 3))) return rc; // (synchronises: the copy is over)
+    if ((rc = fetch_bad(ctx, fs))) return rc;
+    if (fs->bad) {
+      fs->recs.clear();
+      return refuse(fn, "a record lies outside the feature table", PRB_ERR_STATE);
+    }
+  }
+  fs->finished = true;
+  fs->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+int64_t prb_featset_size(const prb_featset *fs) { return fs ? (int64_t)fs->recs.size() : -1; }
+const prb_feature_pair *prb_featset_records(const prb_featset *fs) { return fs ? fs->recs.data() : nullptr; }
+void prb_featset_counts(const prb_featset *fs, int64_t counts[3]) {
+  for (int i = 0; i < 3; i++) counts[i] = fs ? fs->counts[i] : 0;
+}
+int64_t prb_featset_unassigned(const prb_featset *fs) { return fs ? fs->unassigned : -1; }
+void prb_featset_free(prb_featset *fs) { delete fs; }
+
+} // extern "C"

@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the ten result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset): whose they are, whether they can still be merged into, and the block on the device that
+// What the eleven result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featset): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -850,6 +850,63 @@ struct prb_evalset : prb::DecoyTable {
       b->release();
   }
   ~prb_evalset() { release(); } // (also on the error paths of prb_evalset_create)
+};
+
+// prb_annot_create .. prb_annot_free (capi_features.hip): the annotation of one database, sorted by (page, db_id, start,
+// end, index), on the host - what two feature tables must share to be merged - and as one CSR per page on the device
+struct prb_annot {
+  prb_ctx *ctx = nullptr;
+  const prb_db *db = nullptr;
+  int64_t n = 0;
+  struct Page {
+    std::vector<int32_t> off, slo, slen; // [nseq + 1], [nseq], [nseq]
+    std::vector<int32_t> start, end, idx; // the features in order: forward coordinates, the caller's index
+    prb::DevBuf dev;                      // off, slo, slen, tlo, thi, idx
+    bool operator==(const Page &o) const { return off == o.off && slen == o.slen && start == o.start && end == o.end && idx == o.idx; }
+  };
+  std::vector<Page> pages;
+  prb::FeatPage page_view(size_t p) const {
+    const Page &g = pages[p];
+    const int32_t *b = g.dev.as<int32_t>();
+    const size_t ns = g.slo.size(), nf = g.idx.size();
+    return prb::FeatPage{b, b + ns + 1, b + 2 * ns + 1, b + 3 * ns + 1, b + 3 * ns + 1 + nf, b + 3 * ns + 1 + 2 * nf, (int32_t)p, (int32_t)ns};
+  }
+  ~prb_annot() {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (Page &g : pages) g.dev.release();
+  }
+};
+
+// prb_featset_create .. prb_featset_free: the feature table of one batch against one annotated database
+// (capi_features.hip), folded into sub-batch by sub-batch (merge_feature_hits).  It owns all its device memory; `table` =
+// int64_t first[cells], end[cells] (cells = pages x queries: the places of a (page, query)'s records), then
+// prb_feature_pair[cap], of which nrec are in use - the one block that prb_featset_merge reads of another table
+struct prb_featset : prb::MergeTable {
+  const prb_annot *annot = nullptr;
+  int64_t nrec = 0, cap = 0;       // records in the block, and its room
+  int64_t unassigned = 0;          // final hits that belong to no feature
+  prb::DevBuf cnt, ioff, tmp, flag, long_list, sel, scanTmp, count; // per fold: FeatWork, the selected items
+  prb::DevBuf head, start;                                          // prb_featset_add_hits: the runs of the caller's list
+  prb::DevBuf h_query, h_db_id, h_e_tot, h_e_acc, h_e_hyb, h_ends;  // ... and the list as columns
+  prb::DevBuf out;                                                  // prb_featset_finish: the records in order
+  std::vector<prb_feature_pair> recs;                               // prb_featset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRuns; }
+  int take(const prb::SubBatch &b) override;
+  int64_t cells() const { return (int64_t)merged.size() * nq; }
+  size_t head_bytes() const { return (size_t)cells() * 16; }
+  size_t bytes() const { return head_bytes() + (size_t)nrec * sizeof(prb_feature_pair); } // (what is in use)
+  int64_t *first_of(void *b) const { return static_cast<int64_t *>(b); }
+  int64_t *end_of(void *b) const { return static_cast<int64_t *>(b) + cells(); }
+  prb_feature_pair *recs_of(void *b) const { return reinterpret_cast<prb_feature_pair *>(static_cast<char *>(b) + head_bytes()); }
+  void release() {
+    if (!quiesce()) return;
+    for (prb::DevBuf *b : {&table, &badflag, &cnt, &ioff, &tmp, &flag, &long_list, &sel, &scanTmp, &count, &head, &start, &h_query, &h_db_id,
+                           &h_e_tot, &h_e_acc, &h_e_hyb, &h_ends, &out})
+      b->release();
+  }
+  ~prb_featset() { release(); } // (also on the error paths of prb_featset_create)
 };
 
 namespace prb {

@@ -741,4 +741,63 @@ hipError_t launch_eval_qmin(const EvalTab &t, hipStream_t s);
 // prb_evalset_score: out[i] (prb_eval_score) of the real hit (query[i], energy[i]), a lane each
 hipError_t launch_eval_lookup(const EvalTab &t, const int32_t *query, const double *energy, int64_t n, void *out, hipStream_t s);
 
+// ============================================================================ feature_kernels.hip: the feature table
+// (prb_featset_*)  The annotation of one page as the kernels read it: a CSR over the page's sequences - off[d] = the
+// first feature of sequence d - and per feature its two ends as positions of the page's text (which holds the sequences
+// reversed: tlo = start_pos + length - 1 - end, thi = start_pos + length - 1 - start) and its index in the caller's list;
+// a target's features stand by (start, end, index) of their forward coordinates.  slo / slen: the sequences' first text
+// position and length, what a span is checked against.
+struct FeatPage {
+  const int32_t *off;              // [nseq + 1]
+  const int32_t *slo, *slen;       // [nseq]
+  const int32_t *tlo, *thi, *idx;  // [off[nseq]]
+  int32_t page, nseq;
+};
+// a list of final hits of one page in output order, as columns (a sub-batch's F, or a caller's list)
+struct FeatHits {
+  int64_t n;
+  const int32_t *query, *db_id;
+  const double *e_tot, *e_acc, *e_hyb;
+  const int32_t *ends; // launch_bp_ends' four ints per hit
+};
+// What a fold works in: cnt / ioff [npairs + 1] the items per pair run and their exclusive scan, tmp [nitems] the items'
+// records (prb_feature_pair; written where flag is set), flag [nitems], long_list [nitems] and nlong: the items that the
+// lane form left to the wavefront form.  bad[0]: a hit or a run names a query or a sequence outside the page, or a span
+// leaves its sequence (such a hit is counted nowhere); the 64-bit word at bad + 2: the unassigned hits.
+struct FeatWork {
+  int32_t *cnt;
+  int64_t *ioff;
+  void *tmp;
+  uint8_t *flag;
+  uint32_t *long_list, *nlong;
+  uint32_t *bad;
+};
+inline constexpr int kFeatLongRun = 128; // a run of more hits goes to a wavefront per item
+// cnt[k] = the features of the target of run k (start[k] = its first hit), cnt[npairs] = 0
+hipError_t launch_feat_count(const FeatHits &h, const uint32_t *start, int64_t npairs, const FeatPage &pg, int32_t nq, const FeatWork &w,
+                             hipStream_t s);
+// The items (run k, feature f of its target), item x = ioff[k] + (f - off[d]): a lane per item finds its run by binary
+// search in ioff and walks it in list order - count, inside, strict-`<` minimum, left-to-right sum - over the hits whose
+// span meets the feature; items of runs longer than kFeatLongRun are listed for launch_feat_items_long, which gives each
+// a wavefront: 64 hits tested at a time, the members' energies added one by one in list order.  Both write tmp and flag.
+hipError_t launch_feat_items(const FeatHits &h, const uint32_t *start, int64_t npairs, int64_t nitems, const FeatPage &pg, const FeatWork &w,
+                             hipStream_t s);
+hipError_t launch_feat_items_long(const FeatHits &h, const uint32_t *start, int64_t npairs, int64_t nitems, const FeatPage &pg,
+                                  const FeatWork &w, hipStream_t s);
+// the hits whose span meets no feature of their target, added to the 64-bit word at w.bad + 2 (a lane per hit, one
+// integer atomic per wavefront)
+hipError_t launch_feat_unassigned(const FeatHits &h, const FeatPage &pg, int32_t nq, const FeatWork &w, hipStream_t s);
+// sel[0, nsel) = the items with a hit, ascending: their records to rec[base + j] (prb_feature_pair), and per query of
+// the list the place of its first record and the place behind its last: first / end [page * nq + query]
+hipError_t launch_feat_append(const void *tmp, const uint32_t *sel, int64_t nsel, void *rec, int64_t base, int64_t *first, int64_t *end,
+                              int32_t page, int32_t nq, hipStream_t s);
+// prb_featset_merge: src's nsrc records behind dst's `base`, and the cells of src that hold records moved by `base`
+hipError_t launch_feat_join(void *rec, int64_t base, int64_t *first, int64_t *end, const void *src_rec, int64_t nsrc, const int64_t *src_first,
+                            const int64_t *src_end, int64_t ncells, hipStream_t s);
+// prb_featset_finish: cnt[c'] for the cells in (query, page) order, c' = q * npages + p of the cell p * nq + q ...
+hipError_t launch_feat_cell_counts(const int64_t *first, const int64_t *end, int32_t npages, int32_t nq, int64_t *cnt, hipStream_t s);
+// ... and out[o] = the record at first[cell] + (o - off[c']) of the cell whose scanned range [off[c'], off[c' + 1]) holds o
+hipError_t launch_feat_gather(const void *rec, int64_t nrec, const int64_t *first, const int64_t *off, int32_t npages, int32_t nq, int64_t total,
+                              void *out, uint32_t *bad, hipStream_t s);
+
 } // namespace prb

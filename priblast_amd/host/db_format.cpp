@@ -22,17 +22,23 @@ struct File {
 } // namespace
 
 // (the .seq layout as read_db below reads it: nseq, the lengths, nchars, the text)
-std::string read_db_names(const std::string &prefix, std::vector<std::vector<std::string>> &names) {
+std::string read_db_names(const std::string &prefix, std::vector<std::vector<std::string>> &names, std::vector<std::vector<int32_t>> *lengths) {
   File seq;
   std::ifstream nam(prefix + ".nam");
   if (!seq.open(prefix + ".seq", "rb") || !nam) return "Error: can't open db_file";
   names.clear();
+  if (lengths) lengths->clear();
   for (;;) {
     int32_t nseq, nchars;
     if (!seq.rd(&nseq, 4)) break; // EOF on .seq ends the database
     if (nseq < 0 || nseq > (1 << 28)) return "Error: corrupt " + prefix + ".seq (sequence count)";
-    if (fseek(seq.f, 4 * (long)nseq, SEEK_CUR) || !seq.rd(&nchars, 4) || nchars < 0 || fseek(seq.f, (long)nchars, SEEK_CUR))
+    if (lengths) {
+      lengths->emplace_back((size_t)nseq);
+      if (nseq && !seq.rd(lengths->back().data(), 4 * (size_t)nseq)) return "Error: truncated " + prefix + ".seq";
+    } else if (fseek(seq.f, 4 * (long)nseq, SEEK_CUR)) {
       return "Error: truncated " + prefix + ".seq";
+    }
+    if (!seq.rd(&nchars, 4) || nchars < 0 || fseek(seq.f, (long)nchars, SEEK_CUR)) return "Error: truncated " + prefix + ".seq";
     names.emplace_back((size_t)nseq);
     for (int i = 0; i < nseq; i++) std::getline(nam, names.back()[(size_t)i]);
   }

@@ -39,7 +39,9 @@ std::string read_db(const std::string &prefix, DbHeader &hdr, std::vector<DbPage
 
 // Only the names of the sequences, page by page (names[page][id]): the page sizes from .seq, whose texts are skipped,
 // and the lines of .nam; nothing else is read.  Returns "" or an error message.
-std::string read_db_names(const std::string &prefix, std::vector<std::vector<std::string>> &names);
+// lengths (optional): the sequences' lengths as stored, likewise.
+std::string read_db_names(const std::string &prefix, std::vector<std::vector<std::string>> &names,
+                          std::vector<std::vector<int32_t>> *lengths = nullptr);
 
 // k-mer lookup table of a page (db_construction.cpp:337-369): SA interval of every string of
 // length <= hash_size over {A,C,G,U}; absent k-mers are stored as (1, 0).

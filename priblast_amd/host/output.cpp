@@ -287,6 +287,30 @@ void format_group_piece(const Piece &pc, const GroupView &v, const std::vector<S
   for (int64_t i = pc.i0; i < pc.i1; i++) put_group_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs, v.r[i], v.group_names, v.group_sizes);
 }
 
+// the `-t` line of the record's s, then - in place of its newline - the feature columns
+void format_feature_piece(const Piece &pc, const FeatureView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_feature_pair &x = v.r[i];
+    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
+    b.n--; // (the newline)
+    const size_t len = std::strlen(v.feat_names[x.feature]);
+    char *p = b.room(len + 100);
+    char *const p0 = p;
+    *p++ = ',';
+    std::memcpy(p, v.feat_names[x.feature], len);
+    p += len;
+    *p++ = ',';
+    p = put_int(p, (long long)v.feat_start[x.feature]);
+    *p++ = '-';
+    p = put_int(p, (long long)v.feat_end[x.feature]);
+    *p++ = ',';
+    p = put_int(p, (long long)x.inside);
+    *p++ = '\n';
+    b.n += (size_t)(p - p0);
+  }
+}
+
 // ... of records that are not grouped by query: s.query is the query's identifier
 void format_grouprank_piece(const Piece &pc, const GroupView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   int64_t id = pc.id;
@@ -419,6 +443,13 @@ int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_group_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_feature_batch(const FeatureView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the top-N records: in output order already, each with its own page)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
+      [&](const Piece &pc, Buf &b) { format_feature_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_gnull_batch(const GNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

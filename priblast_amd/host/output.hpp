@@ -100,6 +100,17 @@ struct GroupView : QueryView {
   const int32_t *group_sizes = nullptr;
 };
 int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+// Lines of `ris -t -A FILE` (prb_featset_records): the `-t` line of every record's s with the feature columns behind it, in
+// the records' order, numbered from id0 on:
+//   Id,qname,qlen,dbname,dblen,Hits,MinE,SumE,Eacc,Ehyb,(q0-qN:db0-dbN) ,Feature,Start-End,Inside
+// feat_names / feat_start / feat_end are indexed by the records' feature.
+struct FeatureView : QueryView {
+  const prb_feature_pair *r = nullptr;
+  int64_t n = 0;
+  const char *const *feat_names = nullptr;
+  const int32_t *feat_start = nullptr, *feat_end = nullptr;
+};
+int64_t format_feature_batch(const FeatureView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 // Lines of `ris -t -G FILE -R N` (prb_grouprank_pairs): the same line for every record, in the records' order (by group,
 // then by rank - not grouped by query): names and qlen_unmasked are indexed by the records' s.query, an identifier.
 int64_t format_grouprank_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);

@@ -65,9 +65,14 @@
 // its own (prb_grouprank_merge), and only N records per group reach the host, written by group and rank.  `-R` needs -G
 // and is refused with -n and -P; everything else is refused through -G.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R have one table (kSwitchTable) that every
+// `ris -t -A FILE` is `-t` one level below the target: a line per (query, annotated feature of a target) over the final
+// hits whose span meets the feature.  The annotation is read and checked before any GPU work (load_features), uploaded
+// once per worker (prb_annot_create, open_workers), and a batch's pages are folded into its feature table on the device
+// (prb_search_page_features; with PRB_SPLIT the workers' tables merged, prb_featset_merge): only the records reach the host.
+//
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
-// load_pairlist and load_groups, which read the files of -L and -G), rank_setup, open_workers, join_ranks (the
+// load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
 // close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a
 // BatchResult - the one owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread
@@ -213,6 +218,16 @@ void usage() {
             "              the query's place in the input file; 1 <= INT <= 1024; with -u, -j, -L and the search options; not\n"
             "              with -n, -P, nor with what -G can't be combined with; with one process per GPU, WORLD_SIZE > 1,\n"
             "              it is not implemented; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
+            "    -A STR    with -t: one line per query-feature pair, folded on the GPU.  The file STR annotates the targets: one\n"
+            "              feature per line, target name, a tab, start, a tab, end, a tab, feature name; the coordinates are those\n"
+            "              the result lines print (0-based, inclusive); empty lines and lines that begin with # are skipped; a\n"
+            "              target's features may overlap, nest or repeat, and a target the file does not list has none.  A\n"
+            "              final hit belongs to every feature of its target that its span on the target - from the first to\n"
+            "              the last base pair - shares a position with.  Every line is the -t line over the feature's hits,\n"
+            "              and behind it the feature's name, its start-end and the hits that lie wholly inside it; lines by\n"
+            "              query, then target in database order, then the target's features by start, end and line (with\n"
+            "              -u, -j, -L and the search options; -s has no effect; not with -n, -z, -k, -q, -r, -c, -b, -G, -P, -E,\n"
+            "              -R, nor with WORLD_SIZE > 1; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -237,8 +252,8 @@ thread_local bool t_team_thread = false;
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
 // `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score, `-t -G -R` the N best
-// query-group pairs per group.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank };
+// query-group pairs per group, `-t -A` a line per query-feature pair.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures };
 // -z, -P, -E: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
 // (search_null_batch, search_gnull_batch, search_scored_batch) - and by one worker: there is no merge of two of them
 constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m == OutputMode::kGroupNull || m == OutputMode::kScored; }
@@ -247,7 +262,7 @@ constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m ==
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -274,6 +289,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
      bit(kB) | bit(kT) | bit(kN) | bit(kQ) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP), kK, true},
     // (what -G can't be combined with, and one process per GPU, are refused through -G's row, in its words)
     {'R', "the N best queries per group", bit(kN) | bit(kP), kG, false},
+    {'A', "one line per query-feature pair",
+     bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kT, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -282,6 +299,7 @@ struct Args {
   std::string pairlist; // -L
   bool have_pairlist = false;
   std::string groupfile; // -G
+  std::string annotfile; // -A
   prb_ris_opts o;
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
@@ -300,6 +318,7 @@ struct Worker {
   prb_targetset *targets = nullptr;                   // -r: this worker's table, for the whole run
   prb_covset *coverage = nullptr;                     // -c: this worker's table, for the whole run
   prb_grouprank *grouprank = nullptr;                 // -R: this worker's table, for the whole run
+  prb_annot *annot = nullptr;                         // -A: the annotation on this worker's device, for the whole run
   std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c, -R: (input position, unmasked length) of the queries it prepared
 };
 
@@ -313,6 +332,7 @@ struct Free {
   void operator()(prb_nullset *p) const { prb_nullset_free(p); }
   void operator()(prb_groupset *p) const { prb_groupset_free(p); }
   void operator()(prb_gnullset *p) const { prb_gnullset_free(p); }
+  void operator()(prb_featset *p) const { prb_featset_free(p); }
   void operator()(prb_evalset *p) const { prb_evalset_free(p); }
   void operator()(prb_qbatch *p) const { prb_qbatch_destroy(p); }
   void operator()(prb_pairmask *p) const { prb_pairmask_free(p); }
@@ -331,6 +351,7 @@ struct BatchResult {
   Handle<prb_nullset> null;                    // kNull
   Handle<prb_groupset> groups;                 // kGroups; kGroupRank: until it is merged into the worker's table
   Handle<prb_gnullset> gnull;                  // kGroupNull
+  Handle<prb_featset> features;                // kFeatures
   std::vector<prb_eval_score> scores;          // kScored: of the records of `tophits`, in their order
 };
 
@@ -615,10 +636,17 @@ struct GroupMap {
   std::vector<std::vector<std::pair<int32_t, int32_t>>> members; // -P: per group its targets (page, db_id), in database order
 };
 
+// -A: the features of the database's sequences in the file's order, as prb_annot_create takes them, and their names
+struct Annotation {
+  std::vector<int32_t> page, db_id, start, end;
+  std::vector<std::string> names;
+};
+
 struct Run {
   Args a;
   PairList list;
   GroupMap groups;
+  Annotation annot;
   std::vector<std::string> names, seqs; // the queries
   int world = 1, rank = 0;              // one process per GPU?  (torchrun / mpirun style environment)
   bool rank_mode = false;
@@ -673,6 +701,7 @@ OutputMode output_mode(const Args &a) {
   if (a.given[kZ]) return OutputMode::kNull;
   if (a.given[kP]) return OutputMode::kGroupNull;
   if (a.given[kGR]) return OutputMode::kGroupRank;
+  if (a.given[kA]) return OutputMode::kFeatures;
   if (a.given[kG]) return OutputMode::kGroups;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
          : a.given[kT] ? OutputMode::kSummary : OutputMode::kHits;
@@ -682,7 +711,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -708,6 +737,7 @@ Args parse_args(int argc, char **argv) {
     case 'L': a.have_pairlist = true, a.pairlist = optarg; break;
     case 'z': a.given[kZ] = true, a.decoys = parse_count(optarg); break;
     case 'G': a.given[kG] = true, a.groupfile = optarg; break;
+    case 'A': a.given[kA] = true, a.annotfile = optarg; break;
     case 'P': a.given[kP] = true, a.decoys = parse_count(optarg); break;
     case 'E': a.given[kE] = true, a.decoys = parse_count(optarg); break;
     case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
@@ -841,6 +871,63 @@ void load_groups(Run &r) {
     for (size_t i = 0; i < gm.of_page[p].size(); i++) gm.members[(size_t)gm.of_page[p][i]].emplace_back((int32_t)p, (int32_t)i);
 }
 
+// -A FILE: every line checked and turned into a feature of every database sequence of that name; any fault ends the run
+// here, before any GPU work, with the file's name and the line's number.  A sequence that the file does not list has no feature.
+void load_features(Run &r) {
+  if (!r.a.given[kA]) return;
+  const std::string text = read_list_file(r.a.annotfile, "the annotation file (-A)");
+  std::vector<std::vector<std::string>> pages;
+  std::vector<std::vector<int32_t>> lengths;
+  if (const std::string err = prb::read_db_names(r.a.db, pages, &lengths); !err.empty()) die(err); // (no GPU is needed to refuse a file)
+  std::multimap<std::string, std::pair<int32_t, int32_t>> target_of; // a name that occurs several times matches all of them
+  for (size_t p = 0; p < pages.size(); p++)
+    for (size_t i = 0; i < pages[p].size(); i++) target_of.emplace(pages[p][i], std::make_pair((int32_t)p, (int32_t)i));
+  Annotation &an = r.annot;
+  // a coordinate: digits only, within int32
+  auto coordinate = [](const std::string &f, int64_t *v) {
+    if (f.empty() || f.size() > 10) return false;
+    *v = 0;
+    for (char ch : f) {
+      if (ch < '0' || ch > '9') return false;
+      *v = *v * 10 + (ch - '0');
+    }
+    return *v <= INT32_MAX;
+  };
+  size_t lineno = 0;
+  for (size_t at = 0; at < text.size();) {
+    size_t end = text.find('\n', at);
+    if (end == std::string::npos) end = text.size();
+    std::string line = text.substr(at, end - at);
+    at = end + 1;
+    lineno++;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    const std::string where = "Error: annotation file " + r.a.annotfile + " line " + std::to_string(lineno) + ": ";
+    std::vector<std::string> f;
+    for (size_t a0 = 0;;) {
+      const size_t tab = line.find('\t', a0);
+      f.push_back(line.substr(a0, tab == std::string::npos ? std::string::npos : tab - a0));
+      if (tab == std::string::npos) break;
+      a0 = tab + 1;
+    }
+    int64_t s = 0, e = 0;
+    if (f.size() != 4 || f[0].empty() || f[3].empty() || !coordinate(f[1], &s) || !coordinate(f[2], &e))
+      die(where + "expected target name, start, end and feature name, separated by tabs (0-based, inclusive coordinates)");
+    const auto tr = target_of.equal_range(f[0]);
+    if (tr.first == tr.second) die(where + "no database sequence is named \"" + f[0] + "\"");
+    if (s > e) die(where + "start " + std::to_string(s) + " is behind end " + std::to_string(e));
+    for (auto t = tr.first; t != tr.second; ++t) {
+      const int32_t len = lengths[(size_t)t->second.first][(size_t)t->second.second];
+      if (e >= len) die(where + "end " + std::to_string(e) + " is outside \"" + f[0] + "\" (length " + std::to_string(len) + ")");
+      an.page.push_back(t->second.first);
+      an.db_id.push_back(t->second.second);
+      an.start.push_back((int32_t)s);
+      an.end.push_back((int32_t)e);
+      an.names.push_back(f[3]);
+    }
+  }
+}
+
 // -L: the mask of a prepared batch's queries (input positions `ids`)
 prb_pairmask *batch_mask(const Run &r, prb_ctx *c, const prb_qbatch *qb, const prb_db *db, const std::vector<int32_t> &ids) {
   const PairList &pl = r.list;
@@ -931,6 +1018,10 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
     if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
     if (r.a.mode == OutputMode::kCoverage && prb_covset_create(w.ctx, w.db, &w.coverage)) die(prb_last_error());
+    if (r.a.mode == OutputMode::kFeatures &&
+        prb_annot_create(w.ctx, w.db, (int64_t)r.annot.page.size(), r.annot.page.data(), r.annot.db_id.data(), r.annot.start.data(),
+                         r.annot.end.data(), &w.annot))
+      die(std::string("Error: ") + prb_last_error());
     if (r.a.mode == OutputMode::kGroupRank && prb_grouprank_create(w.ctx, (int32_t)r.groups.names.size(), r.a.grouprank, &w.grouprank))
       die(prb_last_error());
   }
@@ -1008,6 +1099,10 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
                     "Group Hits\n";
+  case OutputMode::kFeatures:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Feature, Feature Range, "
+                    "Inside\n";
   case OutputMode::kGroupNull:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
@@ -1144,6 +1239,12 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
+  case OutputMode::kFeatures: {
+    prb_featset *t = nullptr;
+    rc = prb_featset_create(w.ctx, qb, w.annot, &t);
+    res.features.reset(t);
+    break;
+  }
   case OutputMode::kGroups:
   case OutputMode::kGroupRank: res.groups = create_groupset(r, w, qb); break; // (-R: the batch's group table, merged into the worker's)
   default: break; // (kTargets, kCoverage: the worker's own table, for the whole run - open_workers)
@@ -1163,6 +1264,7 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &o, mine.tophits.get()); break;
+  case OutputMode::kFeatures: rc = prb_search_page_features(w.ctx, qb, w.db, page, &o, mine.features.get()); break;
   case OutputMode::kGroups:
   case OutputMode::kGroupRank: rc = prb_search_page_groups(w.ctx, qb, w.db, page, &o, mine.groups.get()); break;
   case OutputMode::kSummary: {
@@ -1198,6 +1300,11 @@ void finish_table(const Run &r, Worker &w, const Prepared &p, BatchResult &mine,
     for (BatchResult *o : others)
       if (prb_groupset_merge(w.ctx, mine.groups.get(), o->groups.get())) die(prb_last_error());
     if (prb_groupset_finish(w.ctx, mine.groups.get(), r.a.given[kN] ? r.a.top : 0)) die(prb_last_error());
+    break;
+  case OutputMode::kFeatures:
+    for (BatchResult *o : others)
+      if (prb_featset_merge(w.ctx, mine.features.get(), o->features.get())) die(prb_last_error());
+    if (prb_featset_finish(w.ctx, mine.features.get())) die(prb_last_error());
     break;
   case OutputMode::kGroupRank: // (a group's members may lie on any page: only the batch's whole group table is ranked)
     for (BatchResult *o : others)
@@ -1570,6 +1677,21 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
       if (!in_range(r, v.nq, v.r[i])) die("Error: bad record in the group table");
     return written_or_die(prb::format_group_batch(v, r.tabs, id, sink, threads));
   }
+  case OutputMode::kFeatures: {
+    prb::FeatureView v;
+    set_queries(v, job);
+    v.r = prb_featset_records(job.res.features.get());
+    v.n = prb_featset_size(job.res.features.get());
+    std::vector<const char *> fnames;
+    for (const std::string &f : r.annot.names) fnames.push_back(f.c_str());
+    v.feat_names = fnames.data();
+    v.feat_start = r.annot.start.data();
+    v.feat_end = r.annot.end.data();
+    for (int64_t i = 0; i < v.n; i++)
+      if (!in_range(r, v.nq, v.r[i].s, v.r[i].page) || v.r[i].feature < 0 || (size_t)v.r[i].feature >= r.annot.names.size())
+        die("Error: bad record in the feature table");
+    return written_or_die(prb::format_feature_batch(v, r.tabs, id, sink, threads));
+  }
   case OutputMode::kGroupNull: {
     prb::GNullView v;
     set_queries(v, job);
@@ -1805,6 +1927,7 @@ struct Team {
       res.prof = std::move(mine.prof);
       res.tophits = std::move(mine.tophits);
       res.groups = std::move(mine.groups);
+      res.features = std::move(mine.features);
       signal([&] { tb->taken = true; });
     } else {
       wait([&] { return tb->taken; });
@@ -2038,6 +2161,7 @@ void close_run(Run &r, int64_t total_hits) {
     prb_targetset_free(w.targets);
     prb_covset_free(w.coverage);
     prb_grouprank_free(w.grouprank);
+    prb_annot_free(w.annot);
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
     prb_ctx_destroy(w.ctx);
@@ -2051,6 +2175,7 @@ int ris_main(int argc, char **argv) {
   if (!err.empty()) die(err);
   load_pairlist(r);
   load_groups(r);
+  load_features(r);
   const std::vector<int> devices = rank_setup(r);
   split_setup(r);
   open_workers(r, devices);
