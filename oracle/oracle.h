@@ -131,6 +131,13 @@ void orc_extend_ungapped(const orc_db *db, int page, const orc_ris_opts *o, cons
                          int qn, const float *qacc, const float *qcond, orc_hits *hits);
 void orc_extend_gapped(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc,
                        int qn, const float *qacc, const float *qcond, orc_hits *hits);
+/* orc_extend_gapped that also appends to `extended` (initialised by the caller, freed with orc_hits_free) a copy of
+ * every extended hit as it stands BEFORE the final sort and redundancy filter: energies with the dangles, base pairs
+ * as stored.  Two of them with the same coordinates and bit-identical e_tot are a tie of the reference's comparator:
+ * its std::sort leaves their order open, and CheckRedundancy keeps whichever comes first (deviation 1).
+ * The tests prove a tie with this list before they excuse a difference from the reference. */
+void orc_extend_gapped_keep(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc,
+                            int qn, const float *qacc, const float *qcond, orc_hits *hits, orc_hits *extended);
 
 /* The stages' sort (the reference's compare made total: energy, its hybridization part, its accessibility part, input
  * order) and CheckRedundancy's sweep on a caller's list of ONE query, for the tests of the sort and filter kernels:

@@ -632,8 +632,8 @@ static int bp_cmp(const void *a, const void *b) {
   return x < y ? -1 : (x > y ? 1 : 0);
 }
 
-void orc_extend_gapped(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc, int qn,
-                       const float *qacc, const float *qcond, orc_hits *hits) {
+void orc_extend_gapped_keep(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc, int qn,
+                            const float *qacc, const float *qcond, orc_hits *hits, orc_hits *extended) {
   const orc_page *pg = &db->pages[page];
   const int delta = db->min_accessible_length;
   /* CheckHelixLength looks up to min_helix - 1 positions past a cell (GetBPType -> GetChar, gapped_extension.cpp:
@@ -660,9 +660,23 @@ void orc_extend_gapped(const orc_db *db, int page, const orc_ris_opts *o, const 
   }
   /* rna_interaction_search.cpp:314-319: SortBasePair for hits 1..n-1 only */
   for (size_t x = 1; x < hits->n; x++) qsort(hits->h[x].bp, hits->h[x].nbp, 2 * sizeof(int32_t), bp_cmp);
+  if (extended) { /* the list as the sort is about to see it (oracle.h) */
+    for (size_t x = 0; x < hits->n; x++) {
+      orc_hit *c = hits_push(extended);
+      *c = hits->h[x];
+      c->bp_cap = c->nbp;
+      c->bp = malloc((size_t)(c->nbp ? c->nbp : 1) * 2 * sizeof(int32_t));
+      memcpy(c->bp, hits->h[x].bp, (size_t)c->nbp * 2 * sizeof(int32_t));
+    }
+  }
   sort_hits(hits);
   check_redundancy(hits, o->final_thr);
   free(qpad);
+}
+
+void orc_extend_gapped(const orc_db *db, int page, const orc_ris_opts *o, const uint8_t *qenc, int qn,
+                       const float *qacc, const float *qcond, orc_hits *hits) {
+  orc_extend_gapped_keep(db, page, o, qenc, qn, qacc, qcond, hits, NULL);
 }
 
 /* ------------------------------------------------------------------- whole `ris` */

@@ -26,11 +26,16 @@ compiled reference produced for them (strict build: -ffp-contract=off, SURVEY.md
                         targets that are nothing but a site, trap neighbours behind the separators, sites at text
                         position 0 and nchars - 1, a page of one sequence; 5 DB pages (-c 8).
                         `make_golden.py edge` regenerates this case alone
+  mix_opt<k>.stg.gz     the `mix` case's stage dumps under the non-default `ris` options of tests/option_sets.py
+                        (OPTION_SETS[k]); a set that changes neither -l nor -e has the seed lists of mix.stg - checked
+                        here, record for record - and is stored with empty seed lists.  `make_golden.py mixopt`
+  widew_short.fa        the sequences of widew.fa of at most 700 nt, for the span 255 (widew_w255d2.racc)
 """
 import gzip
 import os
 import random
 import shutil
+import struct
 import subprocess
 import sys
 import tempfile
@@ -39,7 +44,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.path.join(ROOT, "oracle", "_ref")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gen_synthetic  # noqa: E402
+import option_sets  # noqa: E402
 
 
 def run(*cmd, cwd=None):
@@ -88,6 +95,11 @@ def corpus():
 
 
 WIDE_W = [(100, 5), (129, 5), (129, 2), (150, 5), (200, 4)]
+# the spans at which the HIP kernels change form: 64 / 65 cells per pass, 96 / 97 for the row masks, 127 / 128 for the
+# two-pass mapping, and the limit 255 - the last on the sequences of at most WIDE_SHORT nt (widew_short.fa)
+EDGE_W = [(64, 5), (65, 5), (96, 5), (97, 5), (128, 5)]
+LIMIT_W = (255, 2)
+WIDE_SHORT = 700
 
 
 def widew_corpus():
@@ -249,9 +261,12 @@ def main():
         run(harness, "sa", os.path.join(HERE, "c1_q.fa"), "0", os.path.join(HERE, "c1_q.sa"))
     if not only or "widew" in only:
         gen_synthetic.write_fasta(os.path.join(HERE, "widew.fa"), widew_corpus())
-        for W, delta in WIDE_W:
+        for W, delta in WIDE_W + EDGE_W:
             run(harness, "raccess", os.path.join(HERE, "widew.fa"), str(W), str(delta),
                 os.path.join(HERE, f"widew_w{W}d{delta}.racc"))
+        gen_synthetic.write_fasta(os.path.join(HERE, "widew_short.fa"), [r for r in widew_corpus() if len(r[1]) <= WIDE_SHORT])
+        run(harness, "raccess", os.path.join(HERE, "widew_short.fa"), str(LIMIT_W[0]), str(LIMIT_W[1]),
+            os.path.join(HERE, "widew_w%dd%d.racc" % LIMIT_W))
     cases = [("c1", "c1_q.fa", "c1_db.fa", []), ("mix", "mix_q.fa", "mix_db.fa", ["-c", "10"]),
              ("quirk", "quirk_q.fa", "quirk_db.fa", ["-c", "2"]),
              ("edge", "edge_q.fa", "edge_db.fa", ["-c", str(EDGE_PAGE)])]
@@ -280,7 +295,41 @@ def main():
         stg = os.path.join(tmp, tag + ".stg")
         run(harness, "stages", os.path.join(HERE, qfa), dbp, stg)
         gz(stg, os.path.join(HERE, tag + ".stg.gz"))
+    if not only or "mixopt" in only:
+        mixopt(strict, harness, tmp)
     shutil.rmtree(tmp)
+
+
+def mixopt(strict, harness, tmp):
+    """mix_opt<k>.stg.gz for every set of option_sets.OPTION_SETS."""
+    import refdump
+    dbp = os.path.join(tmp, "mixdb")
+    if not os.path.exists(dbp + ".bas"):
+        run(strict, "db", "-i", os.path.join(HERE, "mix_db.fa"), "-o", dbp, "-c", "10", cwd=tmp)
+    nq = len(mix_inputs()[0])
+    base = os.path.join(tmp, "mix_default.stg")
+    run(harness, "stages", os.path.join(HERE, "mix_q.fa"), dbp, base)
+    with gzip.open(os.path.join(HERE, "mix.stg.gz"), "rb") as f, open(base, "rb") as g:
+        assert f.read() == g.read(), "mix.stg.gz is stale: regenerate the mix case first"
+    default = refdump.read_stages(base)
+
+    def flat(h):
+        return tuple(h[k] for k in ("q_sp", "db_sp", "q_len", "db_len", "db_id", "db_id_start")) + tuple(
+            struct.pack("<d", h[k]) for k in ("e_acc", "e_hyb", "e_tot")) + (h["bp"].tobytes(),)
+    for k, kw in enumerate(option_sets.OPTION_SETS):
+        stg = os.path.join(tmp, f"mix_opt{k}.stg")
+        run(harness, "stages", os.path.join(HERE, "mix_q.fa"), dbp, stg, *option_sets.switches(kw))
+        recs = refdump.read_stages(stg)
+        assert len(recs) == len(default) and len(recs) % nq == 0
+        if not option_sets.holds_seeds(k):
+            for a, b in zip(recs, default):
+                assert (a["q"], a["page"]) == (b["q"], b["page"])
+                assert [flat(h) for h in a["seed"]] == [flat(h) for h in b["seed"]], (k, a["q"], a["page"])
+            refdump.write_stages(stg, nq, len(recs) // nq, recs, keep_seeds=False)
+        gz(stg, os.path.join(HERE, option_sets.fixture(k)))
+        n = [sum(len(r[s]) for r in recs) for s in ("seed", "ungapped", "gapped")]
+        print(f"mix_opt{k} {kw}: seed {n[0]} ungapped {n[1]} gapped {n[2]}, "
+              f"{os.path.getsize(os.path.join(HERE, option_sets.fixture(k)))} bytes")
 
 
 if __name__ == "__main__":

@@ -79,6 +79,7 @@ def lib():
     for fn in (L.orc_extend_ungapped, L.orc_extend_gapped):
         fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RisOpts), ctypes.c_void_p, ctypes.c_int,
                        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Hits)]
+    L.orc_extend_gapped_keep.argtypes = L.orc_extend_gapped.argtypes + [ctypes.POINTER(Hits)]
     L.orc_seed_search.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RisOpts), ctypes.c_void_p,
                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.POINTER(Hits)]
@@ -156,8 +157,9 @@ class Db:
             lib().orc_db_close(self.h)
             self.h = None
 
-    def stages(self, seq, page, opts=None):
-        """seed -> ungapped -> gapped for one query against one page; returns 3 hit lists."""
+    def stages(self, seq, page, opts=None, extended=False):
+        """seed -> ungapped -> gapped for one query against one page; returns 3 hit lists - and, with `extended`, as a
+        fourth the gapped-extended hits before the final sort and redundancy filter (orc_extend_gapped_keep)."""
         L = lib()
         o = opts or default_opts()
         acc, cond = raccess(seq, self.W, self.delta)
@@ -172,10 +174,16 @@ class Db:
         L.orc_extend_ungapped(self.h, page, ctypes.byref(o), enc.ctypes.data, len(enc), acc.ctypes.data,
                               cond.ctypes.data, ctypes.byref(hs))
         ung = hits_to_list(hs)
-        L.orc_extend_gapped(self.h, page, ctypes.byref(o), enc.ctypes.data, len(enc), acc.ctypes.data,
-                            cond.ctypes.data, ctypes.byref(hs))
+        ext = Hits()
+        L.orc_hits_init(ctypes.byref(ext))
+        L.orc_extend_gapped_keep(self.h, page, ctypes.byref(o), enc.ctypes.data, len(enc), acc.ctypes.data,
+                                 cond.ctypes.data, ctypes.byref(hs), ctypes.byref(ext) if extended else None)
         gap = hits_to_list(hs)
         L.orc_hits_free(ctypes.byref(hs))
+        if extended:
+            raw = hits_to_list(ext)
+            L.orc_hits_free(ctypes.byref(ext))
+            return seed, ung, gap, raw
         return seed, ung, gap
 
 

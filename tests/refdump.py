@@ -120,6 +120,23 @@ def read_stages(path):
     return out
 
 
+def write_stages(path, nq, npages, recs, keep_seeds=True):
+    """Writes read_stages' records back in the same layout; without keep_seeds every seed list is written empty
+    (n = 0), which read_stages reads as such."""
+    out = [struct.pack("<I2i", 0x53544731, nq, npages)]
+    for rec in recs:
+        out.append(struct.pack("<2i", rec["q"], rec["page"]))
+        for name in ("seed", "ungapped", "gapped"):
+            hits = rec[name] if keep_seeds or name != "seed" else []
+            out.append(struct.pack("<i", len(hits)))
+            for h in hits:
+                out.append(struct.pack("<6i3di", h["q_sp"], h["db_sp"], h["q_len"], h["db_len"], h["db_id"], h["db_id_start"],
+                                       h["e_acc"], h["e_hyb"], h["e_tot"], len(h["bp"])))
+                out.append(np.ascontiguousarray(h["bp"], "<i4").tobytes())
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
+
+
 def unpack_case(golden, tag, dst):
     """Unpacks one golden case's gzip'd database files and stage dump (<tag>db.*.gz, <tag>.stg.gz) into dst."""
     import gzip

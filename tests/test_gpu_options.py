@@ -1,7 +1,8 @@
 """GPU parity under non-default `ris` options and on a larger case.
 
-* option sweeps (-l -e -f -g -x -y -m) are checked against the oracle's C restatement, which is
-  itself pinned to the reference on the default options (tests/test_oracle.py);
+* option sweeps (-l -e -f -g -x -y -m, tests/option_sets.py) are checked against the UNMODIFIED reference's stage dumps
+  for them (tests/golden/mix_opt<k>.stg.gz), and against the oracle's C restatement, which is pinned to the same dumps
+  (tests/test_oracle_options.py) and to the reference on the default options (tests/test_oracle.py);
 * a 1 kb x 200 kb case is checked against the UNMODIFIED reference binary run on the box
   (oracle/_ref, strict build) when it is present: sorted result lines, Id stripped."""
 import os
@@ -10,7 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import option_sets
 import refdump
+import tiecheck
+from option_sets import OPTION_SETS, ORACLE_NAMES
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,25 +28,6 @@ def ctx():
     c = capi.Context(0)
     yield c
     c.close()
-
-
-OPTION_SETS = [
-    dict(max_seed_length=8, hybrid_threshold=-4.0),
-    dict(interaction_threshold=-2.0, final_threshold=-5.0),
-    dict(drop_out_w_gap=4, drop_out_wo_gap=2),
-    dict(drop_out_w_gap=30, drop_out_wo_gap=12, min_helix_length=1),
-    dict(min_helix_length=5, final_threshold=-6.0),
-    dict(min_helix_length=2),
-    dict(min_helix_length=9, interaction_threshold=-2.0, final_threshold=-4.0, drop_out_w_gap=24),
-    # odd and tiny -x: tier 0 takes two anti-diagonals per step, a direction without improvement (x + 1) / 2 steps
-    dict(drop_out_w_gap=5, final_threshold=-6.0),
-    dict(drop_out_w_gap=7, min_helix_length=4, final_threshold=-5.0),
-    dict(drop_out_w_gap=1, final_threshold=-5.0),
-    dict(drop_out_w_gap=19, drop_out_wo_gap=7),
-]
-ORACLE_NAMES = dict(max_seed_length="max_seed_length", hybrid_threshold="hybrid_thr", interaction_threshold="interaction_thr",
-                    final_threshold="final_thr", drop_out_w_gap="drop_w_gap", drop_out_wo_gap="drop_wo_gap",
-                    min_helix_length="min_helix")
 
 
 @pytest.mark.parametrize("kw", OPTION_SETS)
@@ -74,6 +59,76 @@ def test_option_sweep_matches_oracle(ctx, oracle, golden_dir, kw):
         qb.close()
         db.close()
         odb.close()
+
+
+@pytest.fixture(scope="module")
+def mix(ctx, golden_dir):
+    """The `mix` case loaded once for the reference sweep: (query sequences, Db, QBatch with accessibilities)."""
+    from priblast_amd import capi
+    names, seqs = refdump.read_fasta(os.path.join(GOLDEN, "mix_q.fa"))
+    db = capi.Db(ctx, os.path.join(golden_dir, "mixdb"))
+    qb = capi.QBatch(ctx, seqs, db.repeat_flag)
+    qb.accessibility(db.W, db.delta)
+    yield seqs, db, qb
+    qb.close()
+    db.close()
+
+
+@pytest.mark.parametrize("k", range(len(OPTION_SETS)))
+def test_option_sweep_matches_reference(ctx, oracle, golden_dir, tmp_path, mix, k):
+    """The HIP path against the reference itself under OPTION_SETS[k]: the final hits of every (query, page) list as a
+    multiset - coordinates, the three energies and the base pairs exact - but for proven ties of the reference's
+    comparator (tiecheck.py), which must be exactly the ones recorded in option_sets.EXCUSED, and at which the HIP
+    path keeps the same twin as the restatement (both sort by one total order).  For the sets of
+    option_sets.STAGE_SETS the ungapped lists too (multisets, the acc/hyb split to 1e-12, as test_stage_dumps), and
+    the seed list in the reference's emission order where the fixture holds it ({-l 8, -e -4})."""
+    from priblast_amd import capi
+    from test_gpu_search import as_dicts, key, same
+    kw = OPTION_SETS[k]
+    seqs, db, qb = mix
+    stg = refdump.read_stages(option_sets.unpack(GOLDEN, k, str(tmp_path)))
+    stages = [3] + ([2] if k in option_sets.STAGE_SETS else []) + ([1] if k in option_sets.STAGE_SETS and option_sets.holds_seeds(k) else [])
+    excused = set()
+    total = 0
+    for page in range(db.npages):
+        per_stage = {}
+        for stage in stages:
+            hits, bp, counts = capi.search_page(ctx, qb, db, page, capi.default_opts(output_style=1, **kw), last_stage=stage)
+            per_stage[stage] = as_dicts(hits, bp)
+        for rec in stg:
+            if rec["page"] != page:
+                continue
+            q = rec["q"]
+            where = (k, q, page)
+            mine = {s: [h for h in per_stage[s] if h["query"] == q] for s in stages}
+            if 1 in stages:
+                assert len(mine[1]) == len(rec["seed"]) > 0, where
+                for a, b in zip(mine[1], rec["seed"]):
+                    assert same(a, b, with_bp=False), (where, a, b)
+            if 2 in stages:
+                assert len(mine[2]) == len(rec["ungapped"]), where
+                for a, b in zip(sorted(mine[2], key=key), sorted(rec["ungapped"], key=key)):
+                    assert same(a, b, 1e-12), (where, a, b)
+            assert len(mine[3]) == len(rec["gapped"]), where
+            total += len(mine[3])
+            pairs = tiecheck.pair_twins(*tiecheck.unmatched(mine[3], rec["gapped"]))
+            assert len(pairs) <= option_sets.MAX_EXCUSED_PER_LIST, (where, pairs)
+            if not pairs:
+                continue
+            # the proof needs the extended hits before the final sort and filter: the restatement's, for this list only
+            odb = oracle.Db(os.path.join(golden_dir, "mixdb"))
+            try:
+                oopts = oracle.default_opts(**{ORACLE_NAMES[o]: v for o, v in kw.items()})
+                _, _, ogap, ext = odb.stages(seqs[q], page, oopts, extended=True)
+            finally:
+                odb.close()
+            for ours, theirs in pairs:
+                tiecheck.prove_tie(ours, theirs, ext)
+                twin = [h for h in ogap if tiecheck.tie_key(h) == tiecheck.tie_key(ours)]
+                assert len(twin) == 1 and tiecheck.identity(twin[0]) == tiecheck.identity(ours), (where, ours, twin)
+                excused.add(where + tiecheck.coords(ours))
+    assert total == sum(len(rec["gapped"]) for rec in stg) > 0
+    assert excused == {e for e in option_sets.EXCUSED if e[0] == k}
 
 
 def test_unsupported_options_fail_loudly(ctx, golden_dir):
@@ -287,6 +342,12 @@ def test_nondefault_db_and_ris_options_through_the_command_lines(tmp_path):
     (ha, a), (hb, b) = read(str(tmp_path / "gpu.out")), read(str(tmp_path / "ref.out"))
     assert ha == hb  # the option echo of the header line (after input: and database:)
     assert len(b) > 20
+    # `==` on -s 1 lines holds because these inputs happen to hold no tie of the reference's comparator (DESIGN.md 2,
+    # deviation 1): two gapped extensions with the same coordinates and bit-identical total energy but different base
+    # pairs, of which the reference keeps whichever its std::sort put first and we the one with the lower hybridization
+    # energy.  That is luck of the inputs, not a guarantee - test_option_sweep_matches_reference meets such a pair on
+    # the `mix` case under {-f -2, -g -5} and excuses it on proof.  Should new inputs here bring one, prove it the same
+    # way; the comparison itself stays this strict.
     assert a == b
 
 

@@ -48,6 +48,9 @@ def test_dp_tables_match_oracle(ctx, oracle, W, delta):
 
 
 WIDE = [("widew.fa", f"widew_w{W}d{d}.racc") for W, d in ((100, 5), (129, 5), (129, 2), (150, 5), (200, 4))]
+# the spans the HIP kernels change form at (64 / 65 cells per pass, 96 / 97 for the row masks, 127 / 128 for the two-pass
+# mapping) and the limit 255, the last on the sequences of at most 700 nt
+WIDE += [("widew.fa", f"widew_w{W}d5.racc") for W in (64, 65, 96, 97, 128)] + [("widew_short.fa", "widew_w255d2.racc")]
 
 
 @pytest.mark.parametrize("fa,racc", [("corpus.fa", "corpus.racc"), ("c1_q.fa", "c1_q_w40d7.racc")] + WIDE)
@@ -119,20 +122,27 @@ def test_logsum_windows_match_the_ordered_pass(ctx, oracle, monkeypatch):
     monkeypatch.delenv("PRB_RACCESS_LOGSUM_WINDOWS", raising=False)
 
 
+_HELPER_WANT = {}
+
+
 @pytest.mark.parametrize("helpers", ["0", "1", "2", "3"])
 def test_helper_wavefronts_do_not_change_a_bit(ctx, oracle, monkeypatch, helpers):
     """PRB_RACCESS_HELPERS: the big folds of the inside / outside passes with 0, 1 or 2 helper wavefronts per sequence, or
     (3, the default for batches of up to 512 sequences) two helpers and a wavefront that folds beside the sequence's own,
     which runs the other phases meanwhile (a workgroup per sequence) - ragged batch, both passes over the
-    cells of a column (W = 70: 69 cells), a span that leaves the row masks (W = 100: helpers do not apply) - bit-identical
-    to the oracle."""
+    cells of a column (W = 70: 69 cells), a span that leaves the row masks (W = 100: helpers do not apply), and the spans
+    on both sides of one pass of 64 cells (W = 64, 65) and the last one with row masks (W = 96), where the helper forms
+    still apply (test_oracle.py pins the oracle to the reference at these: widew_w64d5 ... widew_w96d5) - bit-identical to
+    the oracle."""
     monkeypatch.setenv("PRB_RACCESS_HELPERS", helpers)
     rng = np.random.default_rng(31)
     seqs = ["".join(rng.choice(list("ACGU"), n)) for n in (5, 64, 71, 300, 777)] + ["GGGGGCCAAAAGGCCCCCAUAU" * 9, ""]
-    for W, delta in ((70, 5), (40, 7), (100, 5)):
+    for W, delta in ((70, 5), (40, 7), (100, 5), (64, 5), (65, 5), (96, 5)):
         res = ctx.accessibility(seqs, W, delta)
-        for s, (acc, cond) in zip(seqs, res):
-            oa, oc = oracle.raccess(s, W, delta) if len(s) else (np.zeros(0, np.float32), np.zeros(0, np.float32))
+        if (W, delta) not in _HELPER_WANT:  # the same for every `helpers`: computed once
+            _HELPER_WANT[W, delta] = [oracle.raccess(s, W, delta) if len(s) else (np.zeros(0, np.float32), np.zeros(0, np.float32))
+                                      for s in seqs]
+        for s, (acc, cond), (oa, oc) in zip(seqs, res, _HELPER_WANT[W, delta]):
             assert np.array_equal(bits(acc), bits(oa)), (helpers, W, len(s))
             assert np.array_equal(bits(cond), bits(oc)), (helpers, W, len(s))
     monkeypatch.delenv("PRB_RACCESS_HELPERS", raising=False)

@@ -36,6 +36,9 @@ def test_fmath_tables_and_probes(oracle):
 
 
 WIDE = [("widew.fa", f"widew_w{W}d{d}.racc") for W, d in ((100, 5), (129, 5), (129, 2), (150, 5), (200, 4))]
+# the spans the HIP kernels change form at (64 / 65 cells per pass, 96 / 97 for the row masks, 127 / 128 for the two-pass
+# mapping) and the limit 255, the last on the sequences of at most 700 nt
+WIDE += [("widew.fa", f"widew_w{W}d5.racc") for W in (64, 65, 96, 97, 128)] + [("widew_short.fa", "widew_w255d2.racc")]
 
 
 @pytest.mark.parametrize("fa,racc", [("corpus.fa", "corpus.racc"), ("c1_q.fa", "c1_q_w40d7.racc")] + WIDE)
@@ -94,8 +97,9 @@ def _same_hit(a, b, split_tol=0.0):
     acc/hyb split: after the ungapped stage two different seeds can extend to the same
     region with bit-identical total energy but hybridization sums that differ in the last
     bit (sums of 0.01 multiples in a different order); which of the two survives the
-    redundancy filter depends on the reference's unspecified std::sort tie order, and the
-    split is recomputed by the gapped stage anyway (gapped_extension.cpp:317-318)."""
+    redundancy filter depends on the reference's unspecified std::sort tie order.  (After
+    the gapped stage the comparison is exact; twins that survive it with different base
+    pairs are excused only on proof, tests/tiecheck.py and DESIGN.md 2, deviation 1.)"""
     for k in ("q_sp", "db_sp", "q_len", "db_len", "db_id", "db_id_start"):
         if a[k] != b[k]:
             return False
