@@ -225,6 +225,12 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   have no feature, and 2 more - head flags and the selection of the runs' first hits - in front per prb_featset_add_hits
  *   with hits; prb_featset_merge: 1; prb_featset_finish: the cells' record counts, their scan and the gather, launches = 3,
  *   or none for a table without records);
+ * "fnull" (prb_fnullset_create: the kept records with their lookup keys, the sort of the keys and the check of their order,
+ *   launches = 3, or none without records; prb_search_page_fnull / prb_fnullset_add_hits: the fold into the scratch - the
+ *   items per pair, their scan, the item kernel and its long-run form; launches = 4 per sub-batch with final hits, or 2 -
+ *   the counts and their scan - when its targets have no feature, and 2 more - head flags and the selection of the runs'
+ *   first hits - in front per prb_fnullset_add_hits with hits; prb_fnullset_end: the close, 1, or none for a batch without
+ *   cells; prb_fnullset_finish: the gather, 1, or none without records);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -1110,6 +1116,79 @@ void prb_featset_free(prb_featset *fs);
 int prb_write_feature_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                             const prb_feature_pair *recs, int64_t nrecs, const char *const *feat_names, const int32_t *feat_start,
                             const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
+
+/* ---- the feature null table: an empirical p-value per (query, feature) record (`ris -t -A FILE -F N`) ----
+ * For one batch of real queries, one annotation and N decoys per query, made by prb_shuffle_sequence exactly as for
+ * prb_nullset.  No fold of the columns of the other tables yields the counts (as for prb_gnullset): a decoy's hits have
+ * to be looked at feature by feature.
+ *   kept       the records prb_featset_finish returns for the real batch, field for field and in that order; e_obs = f.s.e_min
+ *   m(q, d, f) for a kept (q, f) and decoy d of q: the minimum e_tot over decoy d's final hits against f's target whose
+ *              span - prb_featset's: min / max of the first and the last base pair - shares a position with f; +infinity
+ *              without such a hit.  It is the s.e_min of the record that a prb_search_page_features run of the decoy
+ *              gives for f.
+ *   null_hits  the decoys d with m < +infinity
+ *   null_le    the decoys d with m <= e_obs, compared as doubles (-0.0 == +0.0)
+ *   null_min   the minimum of m over d (+0.0 for +-0.0); +infinity when null_hits == 0
+ *   decoys     N; the p-value is p = (null_le + 1) / (N + 1), computed in double on the host (prb_write_fnull_lines)
+ * A decoy hit that touches two overlapping features counts once in each; one that touches only features without a kept
+ * record for its owner, or no feature, counts nowhere.  The table is bit for bit independent of how the decoys are cut
+ * into batches, sub-batches and chunks (PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS), of the order of the pages and of the
+ * decoy batches, of page residency, and of whether the decoys ran under a pair mask that allows at least the targets of
+ * their owners' kept records: every column is an integer count or a minimum over a total order.
+ *   prb_fnullset_create      finishes fs exactly as prb_featset_finish does - the records are then to be had from
+ *                            prb_featset_records(fs) - and keeps on the device the kept records, a lookup (the records'
+ *                            keys (query << 32 | feature) sorted once, 12 B per record, searched by bisection: a dense
+ *                            queries x features array is not affordable) and 32 B of key and counters per record.
+ *                            PRB_ERR_STATE unless every page is merged into fs, and for a finished, broken or bad fs;
+ *                            PRB_ERR_ARG unless 1 <= ndecoys <= 100000.
+ *   prb_fnullset_begin       opens a batch of ndq >= 1 decoys: owner[k] = the real query's index in the feature table's
+ *                            batch, decoy[k] in [0, ndecoys); the checks of prb_gnullset_begin.  The scratch is 8 B per
+ *                            (decoy of the batch, kept record of its owner), addressed through a prefix sum over the
+ *                            batch's decoys - not a dense decoy x feature array; PRB_ERR_NOMEM with the size in the message.
+ *   prb_search_page_fnull    the search of prb_search_page_features of the batch dqb of decoys (dqb's queries are the open
+ *                            batch's decoys, in its order), every sub-batch's final hits folded on the device.  It honours
+ *                            allowed_pairs, distinct_sites and chain_sites - of the latter two only the value fs was
+ *                            searched with.  A page comes once per open batch.
+ *   prb_fnullset_add_hits    the same fold for a caller's list of decoy hits of `page` in host memory (their `query` = the
+ *                            place in the open batch), with the host checks of prb_featset_add_hits; nhits = 0 only marks
+ *                            the page as merged.
+ *   prb_fnullset_end         PRB_ERR_STATE unless every page is merged in the open batch.  Every scratch cell that holds a
+ *                            minimum is counted into its record, once, and emptied.
+ *   prb_fnullset_finish      PRB_ERR_STATE unless every (query, decoy) is closed and no batch is open.  The records are
+ *                            gathered on the device with their counters, and copied once.
+ *   prb_fnullset_records     the records, in the order and number of prb_featset_records(fs)
+ *   prb_fnullset_decoy_counts  the stage counts of prb_pairset_counts, summed over the decoy searches
+ * Every check of a call is made on the host before anything is enqueued: a refused call leaves the table as it was.  The
+ * kernels check their ranges again and raise a flag; a table whose flag is raised returns PRB_ERR_STATE.  There is no
+ * prb_fnullset_merge: a batch belongs to one worker.  Stage timer "fnull" (launch counts: prb_ctx_stage_ms). */
+typedef struct prb_fnull_pair {
+  prb_feature_pair f; /* the kept record */
+  int32_t decoys, pad;
+  int64_t null_hits, null_le;
+  double null_min;
+} prb_fnull_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_fnull_pair) == 112, "prb_fnull_pair: no padding");
+#endif
+typedef struct prb_fnullset prb_fnullset;
+int prb_fnullset_create(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, prb_fnullset **out);
+int prb_fnullset_begin(prb_ctx *ctx, prb_fnullset *fn, const int32_t *owner, const int32_t *decoy, int32_t ndq);
+int prb_search_page_fnull(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_fnullset *fn);
+int prb_fnullset_add_hits(prb_ctx *ctx, prb_fnullset *fn, int32_t page, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,
+                          int64_t npairs);
+int prb_fnullset_end(prb_ctx *ctx, prb_fnullset *fn);
+int prb_fnullset_finish(prb_ctx *ctx, prb_fnullset *fn);
+int64_t prb_fnullset_size(const prb_fnullset *fn);
+const prb_fnull_pair *prb_fnullset_records(const prb_fnullset *fn);
+void prb_fnullset_decoy_counts(const prb_fnullset *fn, int64_t counts[3]);
+void prb_fnullset_free(prb_fnullset *fn);
+/* The lines of `ris -t -A FILE -F N` for one batch: the line of prb_write_feature_lines for every record, in the records'
+ * order, with the null columns of prb_write_gnull_lines behind it:
+ *   ,<decoys>,<null_hits>,<null_le>,<null_min, or NA when null_hits == 0>,<(null_le + 1) / (decoys + 1)>
+ * Arguments and results as prb_write_feature_lines. */
+int prb_write_fnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                          const prb_fnull_pair *recs, int64_t nrecs, const char *const *feat_names, const int32_t *feat_start,
+                          const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
 
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered

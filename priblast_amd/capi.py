@@ -94,6 +94,12 @@ assert GNULL_DTYPE.itemsize == 120
 FEATURE_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("feature", "<i4"), ("inside", "<i8")])
 assert FEATURE_DTYPE.itemsize == 80
 
+# prb_fnull_pair: the embedded prb_feature_pair's fields (the kept record), then the decoys per query and the null counters
+# of the feature (`ris -t -A FILE -F N`)
+FNULL_DTYPE = np.dtype(FEATURE_DTYPE.descr + [("decoys", "<i4"), ("pad", "<i4"), ("null_hits", "<i8"), ("null_le", "<i8"),
+                                              ("null_min", "<f8")])
+assert FNULL_DTYPE.itemsize == 112
+
 # prb_eval_score: a real hit's place among its query's real hits and among the pooled hits of its decoys (`ris -k N -E M`)
 EVAL_DTYPE = np.dtype([("decoys", "<i4"), ("reserved", "<i4"), ("null_le", "<i8"), ("rank", "<i8"), ("q_num", "<u4"), ("q_den", "<u4")])
 assert EVAL_DTYPE.itemsize == 32
@@ -281,6 +287,19 @@ SYMBOLS = {
     "prb_featset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_featset_unassigned": (c_i64, [ctypes.c_void_p]),
     "prb_featset_free": (None, [ctypes.c_void_p]),
+    "prb_fnullset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_fnullset_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32]),
+    "prb_search_page_fnull": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
+    "prb_fnullset_add_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64]),
+    "prb_fnullset_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_fnullset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_fnullset_size": (c_i64, [ctypes.c_void_p]),
+    "prb_fnullset_records": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_fnullset_decoy_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_fnullset_free": (None, [ctypes.c_void_p]),
+    "prb_write_fnull_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                             P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, ctypes.c_int, P(c_i64),
+                                             P(c_i64)]),
     "prb_write_feature_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                                P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, ctypes.c_int, P(c_i64),
                                                P(c_i64)]),
@@ -1111,6 +1130,83 @@ class GNullSet(_Table):
         return tuple(c)
 
 
+class FNullSet(_Table):
+    """prb_fnullset: per kept (query, feature) record of a feature table, how the query's decoys fare against the feature.
+    Made from a FeatSet with every page merged, which it finishes (feature_records(fs) are then its records); the decoys come
+    in batches between begin() and end().  Close it before its annotation."""
+    PREFIX = "fnullset"
+
+    def __init__(self, ctx, fs, ndecoys):
+        h = ctypes.c_void_p()
+        _check(lib().prb_fnullset_create(ctx.h, fs.h, ndecoys, ctypes.byref(h)))
+        self.h, self.ctx, self.db = h, ctx, fs.annot.db
+
+    def begin(self, owner, decoy):
+        """prb_fnullset_begin: opens the batch of the decoys decoy[k] of the real queries owner[k]"""
+        owner, decoy = np.ascontiguousarray(owner, np.int32), np.ascontiguousarray(decoy, np.int32)
+        assert len(owner) == len(decoy)
+        _check(lib().prb_fnullset_begin(self.ctx.h, self.h, owner.ctypes.data if len(owner) else None,
+                                        decoy.ctypes.data if len(owner) else None, len(owner)))
+
+    def merge(self, dqb, page, opts=None):
+        """prb_search_page_fnull: the open batch's decoys dqb against `page`"""
+        o = opts or default_opts()
+        _check(lib().prb_search_page_fnull(self.ctx.h, dqb.h, self.db.h, page, ctypes.byref(o), self.h))
+
+    def add_hits(self, page, hits, bp):
+        """prb_fnullset_add_hits: a list of final hits of the open batch's decoys against `page` (HIT_DTYPE records ascending
+        by `query`, their place in the batch, with the int32 [n, 2] pairs their bp_offset / bp_count index)"""
+        hits = np.ascontiguousarray(hits, HIT_DTYPE)
+        bp = np.ascontiguousarray(bp, np.int32)
+        _check(lib().prb_fnullset_add_hits(self.ctx.h, self.h, page, hits.ctypes.data if len(hits) else None, len(hits),
+                                           bp.ctypes.data if bp.size else None, bp.size // 2))
+
+    def end(self):
+        """prb_fnullset_end: the open batch counted and closed"""
+        _check(lib().prb_fnullset_end(self.ctx.h, self.h))
+
+    def finish(self):
+        """prb_fnullset_finish -> structured array FNULL_DTYPE (a copy), in the feature table's order"""
+        return self._finish("records", FNULL_DTYPE)
+
+    def counts(self):
+        """the stage counts of the decoy searches"""
+        c = (c_i64 * 3)()
+        lib().prb_fnullset_decoy_counts(self.h, c)
+        return tuple(c)
+
+
+def feature_records(fs):
+    """prb_featset_records of a finished feature table (an FNullSet finishes the one it is made from) -> FEATURE_DTYPE (a copy)"""
+    return _records(lib().prb_featset_records(fs.h), lib().prb_featset_size(fs.h), FEATURE_DTYPE)
+
+
+def search_fnull(ctx, qb, seqs, db, annot, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None):
+    """The feature null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its
+    file) against db under the annotation -> structured array FNULL_DTYPE, in the order of FeatSet.finish().  mask: every
+    decoy batch is searched under a pair mask that allows each decoy the targets of its owner's kept records only (the same
+    records either way).  decoy_batch: decoys per batch (all at once by default); pages: their order."""
+    o = opts or default_opts()
+    pages = list(range(db.npages)) if pages is None else list(pages)
+    with FeatSet(ctx, qb, annot) as fs:
+        for p in pages:
+            fs.merge(db, p, o)
+        with FNullSet(ctx, fs, ndecoys) as fn:
+            kept = feature_records(fs)
+
+            def targets(q):
+                mine = kept[kept["query"] == q]
+                return mine["page"].astype(np.int32), mine["db_id"].astype(np.int32)
+
+            with contextlib.closing(_decoy_batches(ctx, seqs, db, ndecoys, seed, file_pos0, o, decoy_batch, targets if mask else None)) as batches:
+                for dqb, own, dec, od in batches:
+                    fn.begin(own, dec)
+                    for p in pages:
+                        fn.merge(dqb, p, od)
+                    fn.end()
+            return fn.finish()
+
+
 class EvalSet(_Table):
     """prb_evalset: the energy keys of one batch's final hits and of its decoys', pooled per query over the whole database,
     and per real hit its rank, the decoy hits at or below it and the pair of its FDR q-value.  The real batch is searched
@@ -1395,6 +1491,16 @@ def write_grouprank_lines(db, qnames, qlen_unmasked, recs, group_names, group_si
     gsz = np.ascontiguousarray(group_sizes, np.int32)
     return _write(lib().prb_write_grouprank_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
                   gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
+
+
+def write_fnull_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start, feat_end, id0=0, fd=-1):
+    """Lines of `ris -t -A FILE -F N` for one batch: recs as FNullSet.finish returns them; feat_names / feat_start / feat_end
+    indexed by their `feature`"""
+    recs = np.ascontiguousarray(recs, FNULL_DTYPE)
+    names = (ctypes.c_char_p * max(len(feat_names), 1))(*[n.encode() for n in feat_names])
+    fs, fe = np.ascontiguousarray(feat_start, np.int32), np.ascontiguousarray(feat_end, np.int32)
+    return _write(lib().prb_write_fnull_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), names,
+                  fs.ctypes.data, fe.ctypes.data, len(feat_names), id0, fd)
 
 
 def write_gnull_lines(db, qnames, qlen_unmasked, recs, group_names, group_sizes, id0=0, fd=-1):

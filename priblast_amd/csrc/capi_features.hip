@@ -45,6 +45,64 @@ FeatWork work_of(const prb_featset *fs) {
 
 } // namespace
 
+// prb_featset_add_hits / prb_fnullset_add_hits: the caller's list against page g and a batch of nq queries, on the host -
+// a refused call leaves the table as it was -, as columns
+int prb::check_hit_list(const std::string &fn, const prb_annot::Page &g, int32_t nq, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,
+                        int64_t npairs, HitColumns &c) {
+  const int32_t nseq = (int32_t)g.slo.size();
+  try {
+    c.query.resize((size_t)nhits);
+    c.db_id.resize((size_t)nhits);
+    c.e_tot.resize((size_t)nhits);
+    c.e_acc.resize((size_t)nhits);
+    c.e_hyb.resize((size_t)nhits);
+    c.ends.resize((size_t)nhits * 4);
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  for (int64_t i = 0; i < nhits; i++) {
+    const prb_hit &x = hits[i];
+    if (x.query < 0 || x.query >= nq || (i && x.query < hits[i - 1].query) || x.db_id < 0 || x.db_id >= nseq || x.bp_count < 1 ||
+        x.bp_offset < 0 || x.bp_offset + x.bp_count > npairs)
+      return refuse(fn, "hit record " + std::to_string(i) + " is inconsistent");
+    const int32_t *first = basepairs + 2 * x.bp_offset, *last = basepairs + 2 * (x.bp_offset + x.bp_count - 1);
+    const int64_t lo = std::min(first[1], last[1]), hi = std::max(first[1], last[1]);
+    const int64_t s0 = g.slo[(size_t)x.db_id];
+    if (lo < s0 || hi >= s0 + g.slen[(size_t)x.db_id])
+      return refuse(fn, "the span of hit record " + std::to_string(i) + " leaves its sequence", PRB_ERR_STATE);
+    c.query[(size_t)i] = x.query;
+    c.db_id[(size_t)i] = x.db_id;
+    c.e_tot[(size_t)i] = x.e_tot;
+    c.e_acc[(size_t)i] = x.e_acc;
+    c.e_hyb[(size_t)i] = x.e_hyb;
+    c.ends[4 * (size_t)i] = first[0], c.ends[4 * (size_t)i + 1] = first[1], c.ends[4 * (size_t)i + 2] = last[0], c.ends[4 * (size_t)i + 3] = last[1];
+  }
+  return PRB_OK;
+}
+// ... to the device (the current one), in the table's six buffers: query, db_id, e_tot, e_acc, e_hyb, ends
+int prb::upload_hit_list(prb_ctx *ctx, const HitColumns &c, DevBuf *const bufs[6], FeatHits *h) {
+  const size_t N = c.query.size();
+  const void *src[6] = {c.query.data(), c.db_id.data(), c.e_tot.data(), c.e_acc.data(), c.e_hyb.data(), c.ends.data()};
+  const size_t bytes[6] = {N * 4, N * 4, N * 8, N * 8, N * 8, N * 16};
+  for (int k = 0; k < 6; k++)
+    if (int rc = bufs[k]->ensure(bytes[k])) return rc;
+  for (int k = 0; k < 6; k++) PRB_HIP(hipMemcpyAsync(bufs[k]->p, src[k], bytes[k], hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the vectors go)
+  *h = FeatHits{(int64_t)N,           bufs[0]->as<int32_t>(), bufs[1]->as<int32_t>(), bufs[2]->as<double>(), bufs[3]->as<double>(),
+                bufs[4]->as<double>(), bufs[5]->as<int32_t>()};
+  return PRB_OK;
+}
+// ... and its runs of equal (query, db_id): head flags and the selection of the runs' first hits, two launches
+int prb::hit_list_runs(prb_ctx *ctx, const FeatHits &h, DevBuf &head, DevBuf &start, const uint32_t **start_out, int64_t *npairs) {
+  int rc;
+  SearchWs &ws = ws_of(ctx);
+  if ((rc = ws.count.ensure(16)) || (rc = head.ensure((size_t)h.n)) || (rc = start.ensure((size_t)h.n * 4))) return rc;
+  PRB_HIP(launch_pair_heads(h.query, h.db_id, h.n, head.as<uint8_t>(), ctx->stream));
+  if ((rc = select_flagged(ctx, ws, nullptr, head.as<uint8_t>(), start.as<uint32_t>(), (size_t)h.n, npairs))) return rc;
+  *start_out = start.as<uint32_t>();
+  return PRB_OK;
+}
+
 // prb_search_page_features (per sub-batch) and prb_featset_add_hits: the list's items folded and the ones with a hit
 // appended to the block, in a bracket of the "feature" timer.  start == nullptr: the runs of the list - head flags and
 // their selection - are made here first.
@@ -60,10 +118,7 @@ static int merge_feature_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const
   if ((rc = ctx->time_begin())) return rc;
   int64_t launches = 0;
   if (!start) {
-    if ((rc = fs->head.ensure((size_t)h.n)) || (rc = fs->start.ensure((size_t)h.n * 4))) return rc;
-    PRB_HIP(launch_pair_heads(h.query, h.db_id, h.n, fs->head.as<uint8_t>(), ctx->stream));
-    if ((rc = select_flagged(ctx, ws, nullptr, fs->head.as<uint8_t>(), fs->start.as<uint32_t>(), (size_t)h.n, &npairs))) return rc;
-    start = fs->start.as<uint32_t>();
+    if ((rc = hit_list_runs(ctx, h, fs->head, fs->start, &start, &npairs))) return rc;
     launches += 2;
   }
   if (npairs <= 0 || npairs > h.n) return refuse(fn, std::to_string(npairs) + " pair runs for " + std::to_string(h.n) + " hits", PRB_ERR_STATE);
@@ -118,6 +173,61 @@ static int merge_feature_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const
 int prb_featset::take(const SubBatch &b) {
   return merge_feature_hits(ctx, this, b.page, FeatHits{b.nfin, b.F.query, b.F.db_id, b.F.e_tot, b.F.e_acc, b.F.e_hyb, b.ends}, b.pair_start, b.npairs);
 }
+
+// prb_featset_finish proper, for `fn`: the record counts of the (page, query) cells scanned by query, then page, the
+// records gathered in that order, one copy.  keep != nullptr (prb_fnullset_create): before the table's device memory is
+// released, the gathered records - still on the device - go to keep_feature_records (capi_fnull.hip).
+int prb::finish_featset(const char *fn, prb_ctx *ctx, prb_featset *fs, prb_fnullset *keep) {
+  if (int rc = finish_guard(fn, "feature", ctx, fs)) return rc;
+  if (fs->finished) return PRB_OK; // (the records are on the host already)
+  if (fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
+  fs->recs.clear();
+  PRB_HIP(hipSetDevice(ctx->device));
+  const int64_t C = fs->cells();
+  if (C > 0 && fs->nrec > 0) {
+    int rc;
+    const int32_t npages = (int32_t)fs->merged.size();
+    if ((rc = fs->tmp.ensure(((size_t)C + 1) * 8)) || (rc = fs->ioff.ensure(((size_t)C + 1) * 8)) ||
+        (rc = fs->out.ensure((size_t)fs->nrec * sizeof(prb_feature_pair))))
+      return rc;
+    try {
+      fs->recs.resize((size_t)fs->nrec);
+    } catch (const std::exception &e) {
+      return refuse(fn, e.what(), PRB_ERR_NOMEM);
+    }
+    if ((rc = ctx->time_begin())) return rc;
+    void *b = fs->table.p;
+    PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
+    PRB_HIP(launch_feat_cell_counts(fs->first_of(b), fs->end_of(b), npages, fs->nq, fs->tmp.as<int64_t>(), ctx->stream));
+    if ((rc = with_temp(fs->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &bytes) {
+           return rocprim::exclusive_scan(t, bytes, fs->tmp.as<int64_t>(), fs->ioff.as<int64_t>(), (int64_t)0, (size_t)C + 1, rocprim::plus<int64_t>(),
+                                          ctx->stream);
+         })))
+      return rc;
+    int64_t total = 0;
+    PRB_HIP(hipMemcpyAsync(&total, fs->ioff.as<int64_t>() + C, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    if (total != fs->nrec) {
+      fs->recs.clear();
+      return refuse(fn, "bad record count " + std::to_string(total) + " (the table holds " + std::to_string(fs->nrec) + ")", PRB_ERR_STATE);
+    }
+    PRB_HIP(launch_feat_gather(fs->recs_of(b), fs->nrec, fs->first_of(b), fs->ioff.as<int64_t>(), npages, fs->nq, total, fs->out.p,
+                               fs->badflag.as<uint32_t>(), ctx->stream));
+    PRB_HIP(hipMemcpyAsync(fs->recs.data(), fs->out.p, (size_t)total * sizeof(prb_feature_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->time_end(ModeTimer::kFeature, 3))) return rc; // (synchronises: the copy is over)
+    if ((rc = fetch_bad(ctx, fs))) return rc;
+    if (fs->bad) {
+      fs->recs.clear();
+      return refuse(fn, "a record lies outside the feature table", PRB_ERR_STATE);
+    }
+  }
+  if (keep) // (the gathered records are still on the device)
+    if (int rc = keep_feature_records(ctx, keep, fs, fs->out.p, (int64_t)fs->recs.size())) return rc;
+  fs->finished = true;
+  fs->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
 
 extern "C" {
 
@@ -256,56 +366,17 @@ int prb_featset_add_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const prb_
   if (page < 0 || (size_t)page >= fs->merged.size())
     return refuse(fn, "page " + std::to_string(page) + " out of range (the database has " + std::to_string(fs->merged.size()) + ")");
   if (fs->merged[(size_t)page]) return refuse(fn, "page " + std::to_string(page) + " is already merged into this feature table");
-  const prb_annot::Page &g = fs->annot->pages[(size_t)page];
-  const int32_t nseq = (int32_t)g.slo.size();
-  std::vector<int32_t> query, db_id, ends;
-  std::vector<double> e_tot, e_acc, e_hyb;
-  try {
-    query.resize((size_t)nhits);
-    db_id.resize((size_t)nhits);
-    e_tot.resize((size_t)nhits);
-    e_acc.resize((size_t)nhits);
-    e_hyb.resize((size_t)nhits);
-    ends.resize((size_t)nhits * 4);
-  } catch (const std::exception &e) {
-    return refuse(fn, e.what(), PRB_ERR_NOMEM);
-  }
-  for (int64_t i = 0; i < nhits; i++) {
-    const prb_hit &x = hits[i];
-    if (x.query < 0 || x.query >= fs->nq || (i && x.query < hits[i - 1].query) || x.db_id < 0 || x.db_id >= nseq || x.bp_count < 1 ||
-        x.bp_offset < 0 || x.bp_offset + x.bp_count > npairs)
-      return refuse(fn, "hit record " + std::to_string(i) + " is inconsistent");
-    const int32_t *first = basepairs + 2 * x.bp_offset, *last = basepairs + 2 * (x.bp_offset + x.bp_count - 1);
-    const int64_t lo = std::min(first[1], last[1]), hi = std::max(first[1], last[1]);
-    const int64_t s0 = g.slo[(size_t)x.db_id];
-    if (lo < s0 || hi >= s0 + g.slen[(size_t)x.db_id])
-      return refuse(fn, "the span of hit record " + std::to_string(i) + " leaves its sequence", PRB_ERR_STATE);
-    query[(size_t)i] = x.query;
-    db_id[(size_t)i] = x.db_id;
-    e_tot[(size_t)i] = x.e_tot;
-    e_acc[(size_t)i] = x.e_acc;
-    e_hyb[(size_t)i] = x.e_hyb;
-    ends[4 * (size_t)i] = first[0], ends[4 * (size_t)i + 1] = first[1], ends[4 * (size_t)i + 2] = last[0], ends[4 * (size_t)i + 3] = last[1];
-  }
+  HitColumns cols;
+  if (int rc = check_hit_list(fn, fs->annot->pages[(size_t)page], fs->nq, hits, nhits, basepairs, npairs, cols)) return rc;
   DeviceScope restore;
   PRB_HIP(hipSetDevice(ctx->device));
   fs->merged[(size_t)page] = 1;
   if (!nhits) return PRB_OK;
   fs->broken = true; // (until the merge is whole)
   int rc;
-  const size_t N = (size_t)nhits;
-  if ((rc = fs->h_query.ensure(N * 4)) || (rc = fs->h_db_id.ensure(N * 4)) || (rc = fs->h_e_tot.ensure(N * 8)) || (rc = fs->h_e_acc.ensure(N * 8)) ||
-      (rc = fs->h_e_hyb.ensure(N * 8)) || (rc = fs->h_ends.ensure(N * 16)))
-    return rc;
-  PRB_HIP(hipMemcpyAsync(fs->h_query.p, query.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(fs->h_db_id.p, db_id.data(), N * 4, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(fs->h_e_tot.p, e_tot.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(fs->h_e_acc.p, e_acc.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(fs->h_e_hyb.p, e_hyb.data(), N * 8, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipMemcpyAsync(fs->h_ends.p, ends.data(), N * 16, hipMemcpyHostToDevice, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the vectors go)
-  const FeatHits h{nhits,           fs->h_query.as<int32_t>(), fs->h_db_id.as<int32_t>(), fs->h_e_tot.as<double>(), fs->h_e_acc.as<double>(),
-                   fs->h_e_hyb.as<double>(), fs->h_ends.as<int32_t>()};
+  FeatHits h;
+  DevBuf *const bufs[6] = {&fs->h_query, &fs->h_db_id, &fs->h_e_tot, &fs->h_e_acc, &fs->h_e_hyb, &fs->h_ends};
+  if ((rc = upload_hit_list(ctx, cols, bufs, &h))) return rc;
   if ((rc = merge_feature_hits(ctx, fs, page, h, nullptr, 0))) return rc;
   fs->broken = false;
   return PRB_OK;
@@ -337,56 +408,7 @@ int prb_featset_merge(prb_ctx *ctx, prb_featset *dst, prb_featset *src) {
   return rc;
 }
 
-// the record counts of the (page, query) cells scanned by query, then page, the records gathered in that order, one copy
-int prb_featset_finish(prb_ctx *ctx, prb_featset *fs) {
-  const char *fn = kFinishFn;
-  if (int rc = finish_guard(fn, "feature", ctx, fs)) return rc;
-  if (fs->finished) return PRB_OK; // (the records are on the host already)
-  if (fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
-  fs->recs.clear();
-  PRB_HIP(hipSetDevice(ctx->device));
-  const int64_t C = fs->cells();
-  if (C > 0 && fs->nrec > 0) {
-    int rc;
-    const int32_t npages = (int32_t)fs->merged.size();
-    if ((rc = fs->tmp.ensure(((size_t)C + 1) * 8)) || (rc = fs->ioff.ensure(((size_t)C + 1) * 8)) ||
-        (rc = fs->out.ensure((size_t)fs->nrec * sizeof(prb_feature_pair))))
-      return rc;
-    try {
-      fs->recs.resize((size_t)fs->nrec);
-    } catch (const std::exception &e) {
-      return refuse(fn, e.what(), PRB_ERR_NOMEM);
-    }
-    if ((rc = ctx->time_begin())) return rc;
-    void *b = fs->table.p;
-    PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
-    PRB_HIP(launch_feat_cell_counts(fs->first_of(b), fs->end_of(b), npages, fs->nq, fs->tmp.as<int64_t>(), ctx->stream));
-    if ((rc = with_temp(fs->scanTmp, "rocprim::exclusive_scan", [&](void *t, size_t &bytes) {
-           return rocprim::exclusive_scan(t, bytes, fs->tmp.as<int64_t>(), fs->ioff.as<int64_t>(), (int64_t)0, (size_t)C + 1, rocprim::plus<int64_t>(),
-                                          ctx->stream);
-         })))
-      return rc;
-    int64_t total = 0;
-    PRB_HIP(hipMemcpyAsync(&total, fs->ioff.as<int64_t>() + C, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PRB_HIP(hipStreamSynchronize(ctx->stream));
-    if (total != fs->nrec) {
-      fs->recs.clear();
-      return refuse(fn, "bad record count " + std::to_string(total) + " (the table holds " + std::to_string(fs->nrec) + ")", PRB_ERR_STATE);
-    }
-    PRB_HIP(launch_feat_gather(fs->recs_of(b), fs->nrec, fs->first_of(b), fs->ioff.as<int64_t>(), npages, fs->nq, total, fs->out.p,
-                               fs->badflag.as<uint32_t>(), ctx->stream));
-    PRB_HIP(hipMemcpyAsync(fs->recs.data(), fs->out.p, (size_t)total * sizeof(prb_feature_pair), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = ctx->time_end(ModeTimer::kFeature, 3))) return rc; // (synchronises: the copy is over)
-    if ((rc = fetch_bad(ctx, fs))) return rc;
-    if (fs->bad) {
-      fs->recs.clear();
-      return refuse(fn, "a record lies outside the feature table", PRB_ERR_STATE);
-    }
-  }
-  fs->finished = true;
-  fs->release(); // (only the host records are needed from here on)
-  return PRB_OK;
-}
+int prb_featset_finish(prb_ctx *ctx, prb_featset *fs) { return finish_featset(kFinishFn, ctx, fs, nullptr); }
 
 int64_t prb_featset_size(const prb_featset *fs) { return fs ? (int64_t)fs->recs.size() : -1; }
 const prb_feature_pair *prb_featset_records(const prb_featset *fs) { return fs ? fs->recs.data() : nullptr; }

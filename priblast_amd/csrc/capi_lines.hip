@@ -180,6 +180,32 @@ int prb_write_feature_lines(const prb_db *db, int32_t nq, const char *const *qna
       [&](const FeatureView &v, LineSink &sink) { return format_feature_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
+int prb_write_fnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_fnull_pair *recs,
+                          int64_t n, const char *const *feat_names, const int32_t *feat_start, const int32_t *feat_end, int64_t nfeat, int64_t id0,
+                          int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<FNullView>(
+      "prb_write_fnull_lines", n >= 0 && (!n || recs) && nfeat >= 0 && (!nfeat || (feat_names && feat_start && feat_end)), db, nq, qnames,
+      qlen_unmasked, lines, bytes, fd,
+      [&](FNullView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_feature_pair &x = recs[i].f;
+          const prb_fnull_pair &y = recs[i];
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || x.feature < 0 || x.feature >= nfeat || !feat_names[x.feature] ||
+              x.inside < 0 || x.inside > x.s.hits || y.decoys < 1 || y.null_hits < 0 || y.null_hits > y.decoys || y.null_le < 0 ||
+              y.null_le > y.null_hits || (i && x.s.query < recs[i - 1].f.s.query))
+            return bad_record("prb_write_fnull_lines: record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = recs;
+        v.n = n;
+        v.feat_names = feat_names;
+        v.feat_start = feat_start;
+        v.feat_end = feat_end;
+        return (int)PRB_OK;
+      },
+      [&](const FNullView &v, LineSink &sink) { return format_fnull_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
 int prb_write_grouprank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
                               const prb_group_pair *recs, int64_t n, const char *const *group_names, const int32_t *group_sizes,
                               int32_t ngroups, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {

@@ -1,5 +1,5 @@
-// The protocol of the eleven result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip, capi_grouprank.hip, capi_gnull.hip, capi_eval.hip, capi_features.hip): what a prb_*_create starts with, what is checked before a page, a
+// The protocol of the twelve result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip, capi_grouprank.hip, capi_gnull.hip, capi_eval.hip, capi_features.hip, capi_fnull.hip): what a prb_*_create starts with, what is checked before a page, a
 // caller's list, a batch of decoys or another table is merged, the search of a page into a table, the uploads of a
 // caller's arrays, the device's `bad` flag, the merge of one table into another across contexts and devices, and what
 // every prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check

@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the eleven result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featset): whose they are, whether they can still be merged into, and the block on the device that
+// What the twelve result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featset, prb_fnullset): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -504,7 +504,7 @@ struct RunTable : TableState {
   }
 };
 
-// What the tables that take a batch's decoys keep of them (prb_nullset, prb_evalset, prb_gnullset): a bit per (query,
+// What the tables that take a batch's decoys keep of them (prb_nullset, prb_evalset, prb_gnullset, prb_fnullset): a bit per (query,
 // decoy) that is merged - a row of them per page, where the table keeps the pages apart: `bit0` = the bit of (0, 0) in
 // the row - and the batch of decoys being merged, on the device (decoys_guard, mark_decoys, upload_owners, capi_tables.hpp)
 struct DecoySet {
@@ -908,6 +908,60 @@ struct prb_featset : prb::MergeTable {
   }
   ~prb_featset() { release(); } // (also on the error paths of prb_featset_create)
 };
+
+// prb_fnullset_create .. prb_fnullset_free: the feature null table of one batch (capi_fnull.hip): the records that a
+// feature table was finished into, kept on the device with their sorted lookup keys, and their decoy counters.  Decoys
+// come in batches between prb_fnullset_begin and prb_fnullset_end; the pages of the open batch are folded into `cell`
+// sub-batch by sub-batch (merge_fnull_hits).  It owns all its device memory.  `table` = GNullCount[nkept]
+struct prb_fnullset : prb::TableState, prb::DecoySet { // (`merged`: a bit per (query, decoy) whose batch is closed, prb_fnullset_end)
+  const prb_annot *annot = nullptr;
+  int64_t nkept = 0, ncells = 0;         // records; the cells of the open batch
+  std::vector<int64_t> qoff;             // [nq + 1] the first key of every query (FNullTab::qoff)
+  bool open = false;                     // between prb_fnullset_begin and prb_fnullset_end
+  std::vector<int32_t> owner, decoy;     // the open batch
+  std::vector<uint8_t> page_merged;      // per page: merged in the open batch
+  prb::DevBuf key, rec, qoff_dev, kept, cell, doff;
+  prb::DevBuf cnt, ioff, long_list, scanTmp;             // per fold: FeatWork
+  prb::DevBuf head, start;                               // prb_fnullset_add_hits: the runs of the caller's list
+  prb::DevBuf h_query, h_db_id, h_e_tot, h_e_acc, h_e_hyb, h_ends; // ... and the list as columns
+  prb::DevBuf out;                       // prb_fnullset_finish: the records
+  std::vector<prb_fnull_pair> recs;      // prb_fnullset_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRuns; }
+  int take(const prb::SubBatch &b) override;
+  prb::FNullTab view() const {
+    const int32_t ndq = (int32_t)owner.size();
+    return prb::FNullTab{key.as<unsigned long long>(), rec.as<uint32_t>(), qoff_dev.as<int64_t>(), table.as<prb::GNullCount>(),
+                         cell.as<unsigned long long>(), own.as<int32_t>(), own.as<int32_t>() + ndq, doff.as<int64_t>(), badflag.as<uint32_t>(),
+                         nkept, ncells, annot->n, nq, ndecoys, (int32_t)annot->pages.size(), ndq};
+  }
+  void release() {
+    if (!quiesce()) return;
+    for (prb::DevBuf *b : {&table, &badflag, &own, &key, &rec, &qoff_dev, &kept, &cell, &doff, &cnt, &ioff, &long_list, &scanTmp, &head, &start,
+                           &h_query, &h_db_id, &h_e_tot, &h_e_acc, &h_e_hyb, &h_ends, &out})
+      b->release();
+  }
+  ~prb_fnullset() { release(); } // (also on the error paths of prb_fnullset_create)
+};
+
+namespace prb {
+// capi_features.hip: prb_featset_finish proper, for `fn_name`.  keep != nullptr (prb_fnullset_create): before the feature
+// table's device memory is released, the gathered records - still on the device - go to keep_feature_records
+// (capi_fnull.hip).
+int finish_featset(const char *fn_name, prb_ctx *ctx, prb_featset *fs, prb_fnullset *keep);
+int keep_feature_records(prb_ctx *ctx, prb_fnullset *fn, prb_featset *fs, const void *recs_dev, int64_t nrec);
+// capi_features.hip: what prb_featset_add_hits and prb_fnullset_add_hits do with a caller's list of final hits of one
+// page: checked on the host against the page `g` of the annotation and a batch of nq queries, as columns; the columns to
+// the device in the table's six buffers (query, db_id, e_tot, e_acc, e_hyb, ends); and the runs of equal (query, db_id)
+// of such a list - two launches, and a synchronisation for their number
+struct HitColumns {
+  std::vector<int32_t> query, db_id, ends;
+  std::vector<double> e_tot, e_acc, e_hyb;
+};
+int check_hit_list(const std::string &fn, const prb_annot::Page &g, int32_t nq, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,
+                   int64_t npairs, HitColumns &c);
+int upload_hit_list(prb_ctx *ctx, const HitColumns &c, DevBuf *const bufs[6], FeatHits *h);
+int hit_list_runs(prb_ctx *ctx, const FeatHits &h, DevBuf &head, DevBuf &start, const uint32_t **start_out, int64_t *npairs);
+} // namespace prb
 
 namespace prb {
 // capi_groups.hip: prb_groupset_finish proper, for `fn_name`.  keep != nullptr (prb_gnullset_create): before the group

@@ -800,4 +800,43 @@ hipError_t launch_feat_cell_counts(const int64_t *first, const int64_t *end, int
 hipError_t launch_feat_gather(const void *rec, int64_t nrec, const int64_t *first, const int64_t *off, int32_t npages, int32_t nq, int64_t total,
                               void *out, uint32_t *bad, hipStream_t s);
 
+// ============================================================================ fnull_kernels.hip: the feature null table
+// (prb_fnullset_*)  The kept (query, feature) records of a finished feature table, and per record how the query's decoys
+// fare against the feature.  There is no dense lookup - queries x features is too many -: key[0, nkept) = the records'
+// (query << 32 | feature), ascending, rec[j] = the record of key j, and qoff[q] = the first key of query q, so a (query,
+// feature) is found by binary search in its query's keys.  A record's counters are the group null table's (GNullCount).
+// The scratch of the OPEN batch (owner[d], decoy[d]; ndq decoys) has a cell per (decoy d, kept record of its owner):
+// cell[doff[d] + (j - qoff[owner[d]])] = the minimum energy key of decoy d over the hits that meet the feature of key j,
+// all ones: none yet.  bad: set when a hit, a run, a record or a cell lies outside the table, or the keys are not in order.
+struct FNullTab {
+  const unsigned long long *key; // [nkept]
+  const uint32_t *rec;           // [nkept]
+  const int64_t *qoff;           // [nq + 1]
+  GNullCount *cnt;               // [nkept]
+  unsigned long long *cell;      // [ncells] (more is allocated when an earlier batch was larger)
+  const int32_t *owner, *decoy;  // [ndq]
+  const int64_t *doff;           // [ndq + 1]; doff[ndq] = ncells
+  uint32_t *bad;
+  int64_t nkept, ncells, nfeat;
+  int32_t nq, ndecoys, npages, ndq;
+};
+// prb_fnullset_create: rec[0, nkept) (prb_feature_pair, on the device) copied to kept[], each with its energy key and
+// empty counters, its lookup key to key[k] and k to idx[k] (to be sorted by key); a lane per record
+hipError_t launch_fnull_keep(const void *rec, const FNullTab &t, void *kept, unsigned long long *key, uint32_t *idx, hipStream_t s);
+// ... and, the keys sorted: they ascend strictly, lie in their queries' ranges of qoff and name records of the table
+hipError_t launch_fnull_order(const FNullTab &t, hipStream_t s);
+// The items of a list of decoy hits (launch_feat_count and its scan: w.cnt, w.ioff), a lane per item: the (owner of the
+// run's decoy, feature) is looked up first - not kept: the lane is done, no hit is read -, then the minimum energy key
+// over the run's hits whose span meets the feature goes into the item's cell with one atomic minimum.  Items of runs
+// longer than kFeatLongRun are listed (w.long_list, w.nlong) for launch_fnull_items_long: a wavefront per listed item,
+// 64 hits at a time and a cross-lane minimum.
+hipError_t launch_fnull_items(const FeatHits &h, const uint32_t *start, int64_t npairs, int64_t nitems, const FeatPage &pg, const FeatWork &w,
+                              const FNullTab &t, hipStream_t s);
+hipError_t launch_fnull_items_long(const FeatHits &h, const uint32_t *start, int64_t npairs, int64_t nitems, const FeatPage &pg,
+                                   const FeatWork &w, const FNullTab &t, hipStream_t s);
+// prb_fnullset_end: every cell of the open batch that holds a key counted into its record and emptied; a lane per cell
+hipError_t launch_fnull_close(const FNullTab &t, hipStream_t s);
+// prb_fnullset_finish: out[k] (prb_fnull_pair) = kept[k] with its counters
+hipError_t launch_fnull_gather(const FNullTab &t, const void *kept, void *out, hipStream_t s);
+
 } // namespace prb

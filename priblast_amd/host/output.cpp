@@ -288,26 +288,39 @@ void format_group_piece(const Piece &pc, const GroupView &v, const std::vector<S
 }
 
 // the `-t` line of the record's s, then - in place of its newline - the feature columns
+void put_feature_line(Buf &b, int64_t id, const std::string &qname, int32_t qlen, const std::vector<SeqTable> &tabs, const prb_feature_pair &x,
+                      const char *const *feat_names, const int32_t *feat_start, const int32_t *feat_end) {
+  put_summary_line(b, id, qname, qlen, tabs[x.page], x.s);
+  b.n--; // (the newline)
+  const size_t len = std::strlen(feat_names[x.feature]);
+  char *p = b.room(len + 100);
+  char *const p0 = p;
+  *p++ = ',';
+  std::memcpy(p, feat_names[x.feature], len);
+  p += len;
+  *p++ = ',';
+  p = put_int(p, (long long)feat_start[x.feature]);
+  *p++ = '-';
+  p = put_int(p, (long long)feat_end[x.feature]);
+  *p++ = ',';
+  p = put_int(p, (long long)x.inside);
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
 void format_feature_piece(const Piece &pc, const FeatureView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++)
+    put_feature_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs, v.r[i], v.feat_names, v.feat_start, v.feat_end);
+}
+
+// the feature line, then the null columns
+void format_fnull_piece(const Piece &pc, const FNullView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
   for (int64_t i = pc.i0; i < pc.i1; i++) {
-    const prb_feature_pair &x = v.r[i];
-    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
-    b.n--; // (the newline)
-    const size_t len = std::strlen(v.feat_names[x.feature]);
-    char *p = b.room(len + 100);
-    char *const p0 = p;
-    *p++ = ',';
-    std::memcpy(p, v.feat_names[x.feature], len);
-    p += len;
-    *p++ = ',';
-    p = put_int(p, (long long)v.feat_start[x.feature]);
-    *p++ = '-';
-    p = put_int(p, (long long)v.feat_end[x.feature]);
-    *p++ = ',';
-    p = put_int(p, (long long)x.inside);
-    *p++ = '\n';
-    b.n += (size_t)(p - p0);
+    const prb_fnull_pair &x = v.r[i];
+    put_feature_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs, x.f, v.feat_names, v.feat_start, v.feat_end);
+    put_null_columns(b, x.decoys, x.null_hits, x.null_le, x.null_min);
   }
 }
 
@@ -450,6 +463,13 @@ int64_t format_feature_batch(const FeatureView &v, const std::vector<SeqTable> &
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_feature_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_fnull_batch(const FNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the feature records)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].f.s.query; },
+      [&](const Piece &pc, Buf &b) { format_fnull_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_gnull_batch(const GNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

@@ -111,6 +111,16 @@ struct FeatureView : QueryView {
   const int32_t *feat_start = nullptr, *feat_end = nullptr;
 };
 int64_t format_feature_batch(const FeatureView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+// Lines of `ris -t -A FILE -F N` (prb_fnullset_records): the line of `-t -A` for every kept record, in the records' order,
+// with the null columns of `-t -z` behind it:
+//   ... ,Feature,Start-End,Inside ,Decoys,NullHits,NullLE,NullMin,PValue
+struct FNullView : QueryView {
+  const prb_fnull_pair *r = nullptr;
+  int64_t n = 0;
+  const char *const *feat_names = nullptr;
+  const int32_t *feat_start = nullptr, *feat_end = nullptr;
+};
+int64_t format_fnull_batch(const FNullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 // Lines of `ris -t -G FILE -R N` (prb_grouprank_pairs): the same line for every record, in the records' order (by group,
 // then by rank - not grouped by query): names and qlen_unmasked are indexed by the records' s.query, an identifier.
 int64_t format_grouprank_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);

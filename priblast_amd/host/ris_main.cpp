@@ -69,15 +69,19 @@
 // hits whose span meets the feature.  The annotation is read and checked before any GPU work (load_features), uploaded
 // once per worker (prb_annot_create, open_workers), and a batch's pages are folded into its feature table on the device
 // (prb_search_page_features; with PRB_SPLIT the workers' tables merged, prb_featset_merge): only the records reach the host.
+// `ris -t -A FILE -F N` adds an empirical p-value to every `-t -A` line: the decoys of `-z`, but counted per feature - a
+// decoy's minimum over its hits that meet the feature against the feature's minimum - in a feature null table on the GPU
+// (prb_fnullset_*), the decoys searched against the targets of each query's kept records only.  `-F` needs -A and is
+// refused with what -A is refused with, and in rank mode.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A have one table (kSwitchTable) that every
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
 // close_run.  The producers (run_workers' two forms, run_ranks) drive run_batches, whose search_batch returns a
 // BatchResult - the one owner of whatever handles a mode leaves - and hand it as a BatchJob to the Writer, whose thread
 // calls write_job.  search_batch has two shapes.  Most modes: create_table, search_one_page for every page, finish_table
-// - the three steps that a team of workers shares out (Team::search).  The modes with decoys (runs_decoys: -z, -P, -E)
+// - the three steps that a team of workers shares out (Team::search).  The modes with decoys (runs_decoys: -z, -P, -E, -F)
 // have a function each that makes, fills and finishes its own tables around one loop, for_decoy_pieces: it cuts the
 // batch's decoys into pieces, shuffles them, makes each piece's query batch and hands it as a DecoyPiece to the mode's
 // body, which decides the piece's mask (mask_piece, mask_piece_by_list) and searches the pages.  Free has a deleter for
@@ -186,7 +190,7 @@ void usage() {
             "              PValue = (NullLE + 1) / (INT + 1); lines by query, then page, then target (1 <= INT <= 100000;\n"
             "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
-            "    -Z INT    with -z or -P, or with -E: the seed of the shuffles [default:1]\n"
+            "    -Z INT    with -z or -P, with -F, or with -E: the seed of the shuffles [default:1]\n"
             "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
             "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
             "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
@@ -228,6 +232,16 @@ void usage() {
             "              query, then target in database order, then the target's features by start, end and line (with\n"
             "              -u, -j, -L and the search options; -s has no effect; not with -n, -z, -k, -q, -r, -c, -b, -G, -P, -E,\n"
             "              -R, nor with WORLD_SIZE > 1; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
+            "    -F INT    with -t -A: an empirical p-value per query-feature pair from INT shuffled decoys of each query, as -z\n"
+            "              makes them: behind every -t -A line the decoys per query, how many of them have a hit whose span\n"
+            "              meets the feature (NullHits), how many of those reach the line's minimum interaction energy or below\n"
+            "              with such a hit (NullLE; a decoy counts once per feature, and in every feature its hit meets), the\n"
+            "              lowest decoy minimum (NullMin, NA without one) and PValue = (NullLE + 1) / (INT + 1); the decoys are\n"
+            "              searched against the targets of their query's lines only (1 <= INT <= 100000; with -u, -j, -L, -Z and\n"
+            "              the search options; -s has no effect; not with what -A can't be combined with, nor with\n"
+            "              WORLD_SIZE > 1; PRB_SPLIT has no effect; the output does not depend on PRB_BATCH or PRB_DEVICES;\n"
+            "              PRB_NULL_MASK=0: the decoys are searched against every target - every listed one under -L -, the\n"
+            "              output is the same)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -252,17 +266,19 @@ thread_local bool t_team_thread = false;
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
 // `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score, `-t -G -R` the N best
-// query-group pairs per group, `-t -A` a line per query-feature pair.
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures };
-// -z, -P, -E: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
-// (search_null_batch, search_gnull_batch, search_scored_batch) - and by one worker: there is no merge of two of them
-constexpr bool runs_decoys(OutputMode m) { return m == OutputMode::kNull || m == OutputMode::kGroupNull || m == OutputMode::kScored; }
+// query-group pairs per group, `-t -A` a line per query-feature pair, `-t -A -F` the same with the feature's null columns.
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures, kFeatureNull };
+// -z, -P, -E, -F: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
+// (search_null_batch, search_gnull_batch, search_scored_batch, search_fnull_batch) - and by one worker: there is no merge of two of them
+constexpr bool runs_decoys(OutputMode m) {
+  return m == OutputMode::kNull || m == OutputMode::kGroupNull || m == OutputMode::kScored || m == OutputMode::kFeatureNull;
+}
 
 // The switches that choose it, one row each: the description the messages carry, what a switch can't be combined with,
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -291,6 +307,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'R', "the N best queries per group", bit(kN) | bit(kP), kG, false},
     {'A', "one line per query-feature pair",
      bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kT, true},
+    {'F', "an empirical p-value per query-feature pair from N shuffled decoys",
+     bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kA, true},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -304,7 +322,7 @@ struct Args {
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
   int grouprank = 0;                                // -R, likewise
-  int decoys = 0;                                   // -z, -P or -E, likewise
+  int decoys = 0;                                   // -z, -P, -E or -F, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
   OutputMode mode = OutputMode::kHits;
@@ -333,6 +351,7 @@ struct Free {
   void operator()(prb_groupset *p) const { prb_groupset_free(p); }
   void operator()(prb_gnullset *p) const { prb_gnullset_free(p); }
   void operator()(prb_featset *p) const { prb_featset_free(p); }
+  void operator()(prb_fnullset *p) const { prb_fnullset_free(p); }
   void operator()(prb_evalset *p) const { prb_evalset_free(p); }
   void operator()(prb_qbatch *p) const { prb_qbatch_destroy(p); }
   void operator()(prb_pairmask *p) const { prb_pairmask_free(p); }
@@ -352,6 +371,7 @@ struct BatchResult {
   Handle<prb_groupset> groups;                 // kGroups; kGroupRank: until it is merged into the worker's table
   Handle<prb_gnullset> gnull;                  // kGroupNull
   Handle<prb_featset> features;                // kFeatures
+  Handle<prb_fnullset> fnull;                  // kFeatureNull
   std::vector<prb_eval_score> scores;          // kScored: of the records of `tophits`, in their order
 };
 
@@ -684,7 +704,7 @@ void check_switches(const Args &a) {
     for (int p = 0; p < kSwitches; p++)
       if (a.given[p] && (kSwitchTable[s].not_with & (1u << p))) die("Error: " + described(s) + " can't be combined with " + described(p));
     // (-Z goes with either switch that makes decoys)
-    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE]))) die("Error: " + described(s) + " needs " + described(need));
+    if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE] || a.given[kF]))) die("Error: " + described(s) + " needs " + described(need));
   }
   for (Switch s : {kR, kK, kN, kGR})
     if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : a.top; a.given[s] && (v < 1 || v > 1024))
@@ -693,6 +713,7 @@ void check_switches(const Args &a) {
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kP] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -P needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kE] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -E needs an integer between 1 and 100000 (this build's limit)");
+  if (a.given[kF] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -F needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kZSeed] && !a.seed_ok) die("Error: -Z needs a non-negative integer");
 }
 
@@ -701,6 +722,7 @@ OutputMode output_mode(const Args &a) {
   if (a.given[kZ]) return OutputMode::kNull;
   if (a.given[kP]) return OutputMode::kGroupNull;
   if (a.given[kGR]) return OutputMode::kGroupRank;
+  if (a.given[kF]) return OutputMode::kFeatureNull;
   if (a.given[kA]) return OutputMode::kFeatures;
   if (a.given[kG]) return OutputMode::kGroups;
   return a.given[kC] ? OutputMode::kCoverage : a.given[kR] ? OutputMode::kTargets : a.given[kK] ? OutputMode::kTopHits : a.given[kQ] ? OutputMode::kProfile : a.given[kN] ? OutputMode::kTop
@@ -711,7 +733,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -740,6 +762,7 @@ Args parse_args(int argc, char **argv) {
     case 'A': a.given[kA] = true, a.annotfile = optarg; break;
     case 'P': a.given[kP] = true, a.decoys = parse_count(optarg); break;
     case 'E': a.given[kE] = true, a.decoys = parse_count(optarg); break;
+    case 'F': a.given[kF] = true, a.decoys = parse_count(optarg); break;
     case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
@@ -1018,7 +1041,7 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
     if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
     if (r.a.mode == OutputMode::kCoverage && prb_covset_create(w.ctx, w.db, &w.coverage)) die(prb_last_error());
-    if (r.a.mode == OutputMode::kFeatures &&
+    if ((r.a.mode == OutputMode::kFeatures || r.a.mode == OutputMode::kFeatureNull) &&
         prb_annot_create(w.ctx, w.db, (int64_t)r.annot.page.size(), r.annot.page.data(), r.annot.db_id.data(), r.annot.start.data(),
                          r.annot.end.data(), &w.annot))
       die(std::string("Error: ") + prb_last_error());
@@ -1103,6 +1126,10 @@ std::string header_text(const Run &r) {
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Feature, Feature Range, "
                     "Inside\n";
+  case OutputMode::kFeatureNull:
+    return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
+                    "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Feature, Feature Range, "
+                    "Inside, Decoys, Null Hits, Null LE, Null Minimum Energy, P Value\n";
   case OutputMode::kGroupNull:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
@@ -1508,6 +1535,55 @@ BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
   return res;
 }
 
+// -t -A FILE -F N: the real batch against every page into a feature table, which is finished into a feature null table:
+// nothing comes to the host but the kept records.  Then the decoys, each piece against every page between
+// prb_fnullset_begin and prb_fnullset_end.  Unless PRB_NULL_MASK=0, a piece is searched under a pair mask that allows each
+// decoy the targets of its owner's kept records only (under -L those are listed pairs already); with PRB_NULL_MASK=0,
+// under -L, every pair listed for the owner.  A query without a record has its decoys searched against nothing, and closed.
+BatchResult search_fnull_batch(const Run &r, Worker &w, Prepared &p) {
+  BatchResult res = empty_result(r);
+  const bool masked = null_mask_wanted();
+  const size_t nq = p.ids.size();
+  prb_featset *raw = nullptr;
+  if (prb_featset_create(w.ctx, p.qb, w.annot, &raw)) die(prb_last_error());
+  Handle<prb_featset> real(raw);
+  const prb_ris_opts o = opts_with(r, p.mask);
+  for (int page = 0; page < r.npages; page++)
+    if (prb_search_page_features(w.ctx, p.qb, w.db, page, &o, real.get())) die(prb_last_error());
+  prb_fnullset *fn = nullptr;
+  if (prb_fnullset_create(w.ctx, real.get(), r.a.decoys, &fn)) die(prb_last_error());
+  res.fnull.reset(fn);
+  // per query the targets of its kept records (a target comes once per feature with a record: the mask takes it again)
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> kept(masked ? nq : 0);
+  if (masked) {
+    const prb_feature_pair *rec = prb_featset_records(real.get());
+    const int64_t n = prb_featset_size(real.get());
+    for (int64_t i = 0; i < n; i++) {
+      if (rec[i].s.query < 0 || (size_t)rec[i].s.query >= nq || rec[i].page < 0 || rec[i].page >= r.npages || rec[i].s.db_id < 0)
+        die("Error: bad record in the feature table");
+      std::vector<std::pair<int32_t, int32_t>> &k = kept[(size_t)rec[i].s.query];
+      if (k.empty() || k.back() != std::make_pair(rec[i].page, rec[i].s.db_id)) k.emplace_back(rec[i].page, rec[i].s.db_id);
+    }
+  }
+  real.reset();
+  for_decoy_pieces(r, w, p, [&](DecoyPiece &dp) {
+    if (masked)
+      mask_piece(w, dp, [&](size_t k, auto add) {
+        for (const auto &[page, db_id] : kept[(size_t)dp.owner[k]]) add(page, db_id);
+      });
+    else
+      mask_piece_by_list(r, w, dp);
+    const prb_ris_opts od = opts_with(r, dp.mask.get());
+    if (prb_fnullset_begin(w.ctx, fn, dp.owner.data(), dp.decoy.data(), (int32_t)dp.owner.size())) die(std::string("Error: ") + prb_last_error());
+    for (int page = 0; page < r.npages; page++)
+      if (prb_search_page_fnull(w.ctx, dp.qb.get(), w.db, page, &od, fn)) die(prb_last_error());
+    if (prb_fnullset_end(w.ctx, fn)) die(prb_last_error());
+  });
+  if (prb_fnullset_finish(w.ctx, fn)) die(prb_last_error());
+  release_batch(p);
+  return res;
+}
+
 // -k K -E M: the real batch against every page, once, into the top-N hit table and an evalset beside it; then its decoys
 // against every page into the evalset's decoy list.  There is no decoy mask, whatever PRB_NULL_MASK says: the null is
 // pooled over every target (under -L: over the owner's listed targets, the query's own search space).  The evalset is
@@ -1551,6 +1627,7 @@ BatchResult search_batch(const Run &r, Worker &w, Prepared &p) {
   if (r.a.mode == OutputMode::kScored) return search_scored_batch(r, w, p);
   if (r.a.mode == OutputMode::kNull) return search_null_batch(r, w, p);
   if (r.a.mode == OutputMode::kGroupNull) return search_gnull_batch(r, w, p);
+  if (r.a.mode == OutputMode::kFeatureNull) return search_fnull_batch(r, w, p);
   BatchResult res = empty_result(r);
   create_table(r, w, p.qb, res);
   for (int page = 0; page < r.npages; page++) search_one_page(r, w, p, page, res, res);
@@ -1691,6 +1768,21 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
       if (!in_range(r, v.nq, v.r[i].s, v.r[i].page) || v.r[i].feature < 0 || (size_t)v.r[i].feature >= r.annot.names.size())
         die("Error: bad record in the feature table");
     return written_or_die(prb::format_feature_batch(v, r.tabs, id, sink, threads));
+  }
+  case OutputMode::kFeatureNull: {
+    prb::FNullView v;
+    set_queries(v, job);
+    v.r = prb_fnullset_records(job.res.fnull.get());
+    v.n = prb_fnullset_size(job.res.fnull.get());
+    std::vector<const char *> fnames;
+    for (const std::string &f : r.annot.names) fnames.push_back(f.c_str());
+    v.feat_names = fnames.data();
+    v.feat_start = r.annot.start.data();
+    v.feat_end = r.annot.end.data();
+    for (int64_t i = 0; i < v.n; i++)
+      if (!in_range(r, v.nq, v.r[i].f.s, v.r[i].f.page) || v.r[i].f.feature < 0 || (size_t)v.r[i].f.feature >= r.annot.names.size())
+        die("Error: bad record in the feature null table");
+    return written_or_die(prb::format_fnull_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kGroupNull: {
     prb::GNullView v;
