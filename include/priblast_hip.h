@@ -224,7 +224,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   launches = 7 per sub-batch with final hits, or 3 - the counts, their scan and the unassigned count - when its targets
  *   have no feature, and 2 more - head flags and the selection of the runs' first hits - in front per prb_featset_add_hits
  *   with hits; prb_featset_merge: 1; prb_featset_finish: the cells' record counts, their scan and the gather, launches = 3,
- *   or none for a table without records);
+ *   or none for a table without records; prb_featset_finish_top / prb_fnullset_create_top: those 3 and the ranked cut - the
+ *   queries' chunk and kept counts, their two scans, the chunks' lists, the queries' folds and the gather of the kept
+ *   records -, launches = 9, or none for a table without records);
  * "fnull" (prb_fnullset_create: the kept records with their lookup keys, the sort of the keys and the check of their order,
  *   launches = 3, or none without records; prb_search_page_fnull / prb_fnullset_add_hits: the fold into the scratch - the
  *   items per pair, their scan, the item kernel and its long-run form; launches = 4 per sub-batch with final hits, or 2 -
@@ -1076,8 +1078,29 @@ void prb_evalset_free(prb_evalset *es);
  *   prb_featset_finish         the per-(page, query) record counts scanned by query, then page, the records gathered in
  *                              that order on the device and copied to the host in one copy; the device memory is released,
  *                              and nothing can be merged after it (a second call does nothing)
+ *   prb_featset_finish_top     prb_featset_finish - its guards and its effects -, but only each query's n best records
+ *                              leave the device, ranked there (below).  PRB_ERR_ARG unless 1 <= n <= 1024, the table
+ *                              untouched.  On a finished table: PRB_OK and nothing done if it was finished by this call
+ *                              with the same n; PRB_ERR_STATE otherwise - after prb_featset_finish, and with another n -,
+ *                              as is prb_featset_finish on a table finished by this call: a silent unranked result would
+ *                              be worse than a refusal.  prb_featset_size / _records then give the ranked records
  *   prb_featset_unassigned     the final hits merged so far that belong to no feature
  *   prb_featset_counts         the stage counts of prb_pairset_counts, summed over the searched pages
+ * THE RANKED CUT (prb_featset_finish_top, prb_fnullset_create_top; `ris -t -A FILE -N K`).  For a query q take the
+ * records that prb_featset_finish would return for q, in that order - page, then the (query, target) runs in list order,
+ * then a target's features by (start, end, index) -, and let p be a record's place in that order.  The rank key of a
+ * record is (energy_key(s.e_min), p), ascending; energy_key is the total order of doubles in which -0.0 == +0.0 that the
+ * other ranked tables use.  Ties in e_min are common - a nested feature and its outer feature share their best hit - and
+ * are decided by p, so no two records of a query have the same key.  With n given the table keeps the min(n, count)
+ * records of lowest key per query; the kept records come by query ascending, then rank, and are field for field the
+ * records of the full finish (there is no rank field: the rank is the place within the query's run).  Every quantity is
+ * a count or a comparison over a total order, so the result depends - bit for bit - neither on how the batch is cut
+ * into sub-batches and chunks (PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS), nor on the order of the pages, nor on page
+ * residency, nor on how the pages were shared between tables that were merged (prb_featset_merge).
+ * On the device the cut works on the gathered records: a query's records are one segment of them, the segments are cut
+ * into chunks of 2048 records, a workgroup per (query, chunk) orders its chunk's keys in LDS and writes the chunk's
+ * min(n, length) lowest; a workgroup per query folds its chunks' lists into the final n; a lane per kept record gathers
+ * it in (query, rank) order into a second buffer, from which the one host copy is made.
  * On the device a sub-batch's work items are (pair run, feature of its target): a count per run from the CSR, an exclusive
  * scan, and an item kernel - a lane per item, which finds its run by binary search and walks it in list order; items of
  * runs longer than 128 hits go to a wavefront each, which tests 64 hits at a time and adds the members' energies one by
@@ -1103,6 +1126,7 @@ int prb_featset_add_hits(prb_ctx *ctx, prb_featset *fs, int32_t page, const prb_
                          int64_t npairs);
 int prb_featset_merge(prb_ctx *ctx, prb_featset *dst, prb_featset *src);
 int prb_featset_finish(prb_ctx *ctx, prb_featset *fs);
+int prb_featset_finish_top(prb_ctx *ctx, prb_featset *fs, int32_t n);
 int64_t prb_featset_size(const prb_featset *fs);
 const prb_feature_pair *prb_featset_records(const prb_featset *fs);
 void prb_featset_counts(const prb_featset *fs, int64_t counts[3]);
@@ -1141,6 +1165,11 @@ int prb_write_feature_lines(const prb_db *db, int32_t nq, const char *const *qna
  *                            queries x features array is not affordable) and 32 B of key and counters per record.
  *                            PRB_ERR_STATE unless every page is merged into fs, and for a finished, broken or bad fs;
  *                            PRB_ERR_ARG unless 1 <= ndecoys <= 100000.
+ *   prb_fnullset_create_top  prb_fnullset_create over the ranked cut: fs is finished exactly as prb_featset_finish_top(fs,
+ *                            n) does, and the kept records, the lookup, the counters and every later scratch are sized
+ *                            by each query's n best records only; a decoy hit that touches only features cut away counts
+ *                            nowhere.  A kept record's counters are those of the same record in the uncut table.
+ *                            PRB_ERR_ARG also unless 1 <= n <= 1024.
  *   prb_fnullset_begin       opens a batch of ndq >= 1 decoys: owner[k] = the real query's index in the feature table's
  *                            batch, decoy[k] in [0, ndecoys); the checks of prb_gnullset_begin.  The scratch is 8 B per
  *                            (decoy of the batch, kept record of its owner), addressed through a prefix sum over the
@@ -1156,7 +1185,8 @@ int prb_write_feature_lines(const prb_db *db, int32_t nq, const char *const *qna
  *                            minimum is counted into its record, once, and emptied.
  *   prb_fnullset_finish      PRB_ERR_STATE unless every (query, decoy) is closed and no batch is open.  The records are
  *                            gathered on the device with their counters, and copied once.
- *   prb_fnullset_records     the records, in the order and number of prb_featset_records(fs)
+ *   prb_fnullset_records     the records, in the order and number of prb_featset_records(fs) (behind
+ *                            prb_fnullset_create_top: by query, then rank)
  *   prb_fnullset_decoy_counts  the stage counts of prb_pairset_counts, summed over the decoy searches
  * Every check of a call is made on the host before anything is enqueued: a refused call leaves the table as it was.  The
  * kernels check their ranges again and raise a flag; a table whose flag is raised returns PRB_ERR_STATE.  There is no
@@ -1172,6 +1202,7 @@ static_assert(sizeof(prb_fnull_pair) == 112, "prb_fnull_pair: no padding");
 #endif
 typedef struct prb_fnullset prb_fnullset;
 int prb_fnullset_create(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, prb_fnullset **out);
+int prb_fnullset_create_top(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, int32_t n, prb_fnullset **out);
 int prb_fnullset_begin(prb_ctx *ctx, prb_fnullset *fn, const int32_t *owner, const int32_t *decoy, int32_t ndq);
 int prb_search_page_fnull(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_fnullset *fn);
 int prb_fnullset_add_hits(prb_ctx *ctx, prb_fnullset *fn, int32_t page, const prb_hit *hits, int64_t nhits, const int32_t *basepairs,

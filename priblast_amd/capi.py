@@ -282,12 +282,14 @@ SYMBOLS = {
     "prb_featset_add_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64]),
     "prb_featset_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "prb_featset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featset_finish_top": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32]),
     "prb_featset_size": (c_i64, [ctypes.c_void_p]),
     "prb_featset_records": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_featset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
     "prb_featset_unassigned": (c_i64, [ctypes.c_void_p]),
     "prb_featset_free": (None, [ctypes.c_void_p]),
     "prb_fnullset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_fnullset_create_top": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, c_i32, P(ctypes.c_void_p)]),
     "prb_fnullset_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32]),
     "prb_search_page_fnull": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
     "prb_fnullset_add_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64]),
@@ -1029,6 +1031,12 @@ class FeatSet(_Table):
         """prb_featset_finish -> structured array FEATURE_DTYPE (a copy): by query, page, target and feature"""
         return self._finish("records", FEATURE_DTYPE)
 
+    def finish_top(self, n):
+        """prb_featset_finish_top -> structured array FEATURE_DTYPE (a copy): each query's n best records, ranked on the
+        device by (e_min, place in the order of finish()); by query, then rank"""
+        _check(lib().prb_featset_finish_top(self.ctx.h, self.h, n))
+        return feature_records(self)
+
     def unassigned(self):
         return lib().prb_featset_unassigned(self.h)
 
@@ -1133,12 +1141,16 @@ class GNullSet(_Table):
 class FNullSet(_Table):
     """prb_fnullset: per kept (query, feature) record of a feature table, how the query's decoys fare against the feature.
     Made from a FeatSet with every page merged, which it finishes (feature_records(fs) are then its records); the decoys come
-    in batches between begin() and end().  Close it before its annotation."""
+    in batches between begin() and end().  top: over each query's `top` best records only, as FeatSet.finish_top(top) ranks
+    them (prb_fnullset_create_top).  Close it before its annotation."""
     PREFIX = "fnullset"
 
-    def __init__(self, ctx, fs, ndecoys):
+    def __init__(self, ctx, fs, ndecoys, top=None):
         h = ctypes.c_void_p()
-        _check(lib().prb_fnullset_create(ctx.h, fs.h, ndecoys, ctypes.byref(h)))
+        if top is None:
+            _check(lib().prb_fnullset_create(ctx.h, fs.h, ndecoys, ctypes.byref(h)))
+        else:
+            _check(lib().prb_fnullset_create_top(ctx.h, fs.h, ndecoys, top, ctypes.byref(h)))
         self.h, self.ctx, self.db = h, ctx, fs.annot.db
 
     def begin(self, owner, decoy):
@@ -1181,17 +1193,19 @@ def feature_records(fs):
     return _records(lib().prb_featset_records(fs.h), lib().prb_featset_size(fs.h), FEATURE_DTYPE)
 
 
-def search_fnull(ctx, qb, seqs, db, annot, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None):
+def search_fnull(ctx, qb, seqs, db, annot, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None, top=None, with_counts=False):
     """The feature null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its
     file) against db under the annotation -> structured array FNULL_DTYPE, in the order of FeatSet.finish().  mask: every
     decoy batch is searched under a pair mask that allows each decoy the targets of its owner's kept records only (the same
-    records either way).  decoy_batch: decoys per batch (all at once by default); pages: their order."""
+    records either way).  decoy_batch: decoys per batch (all at once by default); pages: their order.  top: over each
+    query's `top` best records only, in the order of FeatSet.finish_top(top).  with_counts: -> (records, the (seed, ungapped,
+    final) counts of the decoy searches)."""
     o = opts or default_opts()
     pages = list(range(db.npages)) if pages is None else list(pages)
     with FeatSet(ctx, qb, annot) as fs:
         for p in pages:
             fs.merge(db, p, o)
-        with FNullSet(ctx, fs, ndecoys) as fn:
+        with FNullSet(ctx, fs, ndecoys, top) as fn:
             kept = feature_records(fs)
 
             def targets(q):
@@ -1204,7 +1218,8 @@ def search_fnull(ctx, qb, seqs, db, annot, ndecoys, seed=1, file_pos0=0, opts=No
                     for p in pages:
                         fn.merge(dqb, p, od)
                     fn.end()
-            return fn.finish()
+            recs = fn.finish()
+            return (recs, fn.counts()) if with_counts else recs
 
 
 class EvalSet(_Table):

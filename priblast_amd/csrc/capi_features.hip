@@ -174,27 +174,66 @@ int prb_featset::take(const SubBatch &b) {
   return merge_feature_hits(ctx, this, b.page, FeatHits{b.nfin, b.F.query, b.F.db_id, b.F.e_tot, b.F.e_acc, b.F.e_hyb, b.ends}, b.pair_start, b.npairs);
 }
 
+// the selection of prb_featset_finish_top behind the gather, in the same bracket of the "feature" timer: fs->out = the
+// gathered records, fs->ioff = the scanned cell offsets.  The counts of chunks and kept records per query, their two
+// scans, the chunks' lists, the queries' folds and the gather of the kept records: launches = 6.  *nkept = the records
+// that fs->topOut then holds, in (query, rank) order.
+static int select_top_records(const char *fn, prb_ctx *ctx, prb_featset *fs, int32_t n, int64_t total, int64_t *nkept) {
+  int rc;
+  const size_t Q = (size_t)fs->nq + 1;
+  if (total >= (int64_t)UINT32_MAX) return refuse(fn, std::to_string(total) + " records in one feature table (at most 2^32 - 2 can be ranked)", PRB_ERR_STATE);
+  if ((rc = fs->topCnt.ensure(2 * Q * 8)) || (rc = fs->topOff.ensure(2 * Q * 8)) || (rc = fs->topSel.ensure((size_t)fs->nq * (size_t)n * 4))) return rc;
+  const FtopTab t{fs->ioff.as<int64_t>(), fs->badflag.as<uint32_t>(), total, fs->nq, (int32_t)fs->merged.size(), n};
+  int64_t *nchunk = fs->topCnt.as<int64_t>(), *nkeep = nchunk + Q, *choff = fs->topOff.as<int64_t>(), *koff = choff + Q;
+  PRB_HIP(launch_ftop_counts(t, nchunk, nkeep, ctx->stream));
+  for (int k = 0; k < 2; k++)
+    if ((rc = with_temp(fs->scanTmp, "rocprim::exclusive_scan", [&](void *tmp, size_t &bytes) {
+           return rocprim::exclusive_scan(tmp, bytes, k ? nkeep : nchunk, k ? koff : choff, (int64_t)0, Q, rocprim::plus<int64_t>(), ctx->stream);
+         })))
+      return rc;
+  int64_t sums[2] = {0, 0}; // the chunks, the kept records
+  PRB_HIP(hipMemcpyAsync(&sums[0], choff + fs->nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(&sums[1], koff + fs->nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream));
+  const int64_t nchunks = sums[0];
+  if (nchunks < 1 || nchunks > total / kFtopChunk + fs->nq || sums[1] < 1 || sums[1] > total || sums[1] > (int64_t)fs->nq * n)
+    return refuse(fn, "bad counts of the ranked cut: " + std::to_string(nchunks) + " chunks, " + std::to_string(sums[1]) + " records kept of " +
+                          std::to_string(total),
+                  PRB_ERR_STATE);
+  if ((rc = fs->topKey.ensure((size_t)nchunks * (size_t)n * 8)) || (rc = fs->topPlace.ensure((size_t)nchunks * (size_t)n * 4)) ||
+      (rc = fs->topOut.ensure((size_t)sums[1] * sizeof(prb_feature_pair))))
+    return rc;
+  PRB_HIP(launch_ftop_chunks(t, fs->out.p, choff, nchunks, fs->topKey.as<unsigned long long>(), fs->topPlace.as<uint32_t>(), ctx->stream));
+  PRB_HIP(launch_ftop_merge(t, choff, nchunks, fs->topKey.as<unsigned long long>(), fs->topPlace.as<uint32_t>(), fs->topSel.as<uint32_t>(), ctx->stream));
+  PRB_HIP(launch_ftop_gather(t, fs->out.p, koff, fs->topSel.as<uint32_t>(), sums[1], fs->topOut.p, ctx->stream));
+  *nkept = sums[1];
+  return PRB_OK;
+}
+
 // prb_featset_finish proper, for `fn`: the record counts of the (page, query) cells scanned by query, then page, the
-// records gathered in that order, one copy.  keep != nullptr (prb_fnullset_create): before the table's device memory is
-// released, the gathered records - still on the device - go to keep_feature_records (capi_fnull.hip).
-int prb::finish_featset(const char *fn, prb_ctx *ctx, prb_featset *fs, prb_fnullset *keep) {
+// records gathered in that order, one copy.  n > 0 (prb_featset_finish_top, prb_fnullset_create_top): each query's n
+// best of them are selected on the device first, and only those are copied.  keep != nullptr (prb_fnullset_create[_top]):
+// before the table's device memory is released, the records that were copied - still on the device - go to
+// keep_feature_records (capi_fnull.hip).
+int prb::finish_featset(const char *fn, prb_ctx *ctx, prb_featset *fs, int32_t n, prb_fnullset *keep) {
   if (int rc = finish_guard(fn, "feature", ctx, fs)) return rc;
-  if (fs->finished) return PRB_OK; // (the records are on the host already)
+  if (fs->finished) {
+    if (fs->top_n == n) return PRB_OK; // (the records are on the host already)
+    return refuse(fn, fs->top_n ? "the feature table is finished with each query's " + std::to_string(fs->top_n) + " best records (prb_featset_finish_top)"
+                                : std::string("the feature table is finished with all its records (") + kFinishFn + ")",
+                  PRB_ERR_STATE);
+  }
   if (fs->bad) return refuse(fn, kBadHit, PRB_ERR_STATE);
   fs->recs.clear();
   PRB_HIP(hipSetDevice(ctx->device));
   const int64_t C = fs->cells();
+  const void *recs_dev = fs->out.p;
   if (C > 0 && fs->nrec > 0) {
     int rc;
     const int32_t npages = (int32_t)fs->merged.size();
     if ((rc = fs->tmp.ensure(((size_t)C + 1) * 8)) || (rc = fs->ioff.ensure(((size_t)C + 1) * 8)) ||
         (rc = fs->out.ensure((size_t)fs->nrec * sizeof(prb_feature_pair))))
       return rc;
-    try {
-      fs->recs.resize((size_t)fs->nrec);
-    } catch (const std::exception &e) {
-      return refuse(fn, e.what(), PRB_ERR_NOMEM);
-    }
     if ((rc = ctx->time_begin())) return rc;
     void *b = fs->table.p;
     PRB_HIP(hipMemsetAsync(fs->badflag.p, 0, 16, ctx->stream));
@@ -213,17 +252,29 @@ int prb::finish_featset(const char *fn, prb_ctx *ctx, prb_featset *fs, prb_fnull
     }
     PRB_HIP(launch_feat_gather(fs->recs_of(b), fs->nrec, fs->first_of(b), fs->ioff.as<int64_t>(), npages, fs->nq, total, fs->out.p,
                                fs->badflag.as<uint32_t>(), ctx->stream));
-    PRB_HIP(hipMemcpyAsync(fs->recs.data(), fs->out.p, (size_t)total * sizeof(prb_feature_pair), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = ctx->time_end(ModeTimer::kFeature, 3))) return rc; // (synchronises: the copy is over)
+    recs_dev = fs->out.p;
+    int64_t ncopy = total;
+    if (n) {
+      if ((rc = select_top_records(fn, ctx, fs, n, total, &ncopy))) return rc;
+      recs_dev = fs->topOut.p;
+    }
+    try {
+      fs->recs.resize((size_t)ncopy);
+    } catch (const std::exception &e) {
+      return refuse(fn, e.what(), PRB_ERR_NOMEM);
+    }
+    PRB_HIP(hipMemcpyAsync(fs->recs.data(), recs_dev, (size_t)ncopy * sizeof(prb_feature_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->time_end(ModeTimer::kFeature, n ? 9 : 3))) return rc; // (synchronises: the copy is over)
     if ((rc = fetch_bad(ctx, fs))) return rc;
     if (fs->bad) {
       fs->recs.clear();
       return refuse(fn, "a record lies outside the feature table", PRB_ERR_STATE);
     }
   }
-  if (keep) // (the gathered records are still on the device)
-    if (int rc = keep_feature_records(ctx, keep, fs, fs->out.p, (int64_t)fs->recs.size())) return rc;
+  if (keep) // (the copied records are still on the device)
+    if (int rc = keep_feature_records(ctx, keep, fs, recs_dev, (int64_t)fs->recs.size())) return rc;
   fs->finished = true;
+  fs->top_n = n;
   fs->release(); // (only the host records are needed from here on)
   return PRB_OK;
 }
@@ -408,7 +459,12 @@ int prb_featset_merge(prb_ctx *ctx, prb_featset *dst, prb_featset *src) {
   return rc;
 }
 
-int prb_featset_finish(prb_ctx *ctx, prb_featset *fs) { return finish_featset(kFinishFn, ctx, fs, nullptr); }
+int prb_featset_finish(prb_ctx *ctx, prb_featset *fs) { return finish_featset(kFinishFn, ctx, fs, 0, nullptr); }
+int prb_featset_finish_top(prb_ctx *ctx, prb_featset *fs, int32_t n) {
+  const char *fn = "prb_featset_finish_top";
+  if (const std::string why = bad_n(n); !why.empty()) return refuse(fn, why);
+  return finish_featset(fn, ctx, fs, n, nullptr);
+}
 
 int64_t prb_featset_size(const prb_featset *fs) { return fs ? (int64_t)fs->recs.size() : -1; }
 const prb_feature_pair *prb_featset_records(const prb_featset *fs) { return fs ? fs->recs.data() : nullptr; }

@@ -134,17 +134,16 @@ int prb::keep_feature_records(prb_ctx *ctx, prb_fnullset *t, prb_featset *fs, co
   return PRB_OK;
 }
 
-extern "C" {
-
-int prb_fnullset_create(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, prb_fnullset **out) {
-  const char *fn = "prb_fnullset_create";
+// prb_fnullset_create (n = 0) and prb_fnullset_create_top (n > 0: over each query's n best records, as
+// prb_featset_finish_top ranks them - the kept records, the lookup and every scratch are sized by those alone)
+static int create_fnullset(const char *fn, prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, int32_t n, prb_fnullset **out) {
   std::unique_ptr<prb_fnullset> t;
   if (int rc = new_table(fn, ctx && fs, out, t,
                          ndecoys < 1 || ndecoys > 100000 ? "need 1 <= ndecoys <= 100000 (got " + std::to_string(ndecoys) + ")" : ""))
     return rc;
   if (int rc = finish_guard(fn, "feature", ctx, fs)) return rc;
   if (fs->bad) return refuse(fn, "a hit merged into the feature table named a query or a sequence outside it, or its span left its sequence", PRB_ERR_STATE);
-  if (fs->finished) return refuse(fn, "the feature table is finished already (prb_featset_finish)", PRB_ERR_STATE);
+  if (fs->finished) return refuse(fn, "the feature table is finished already (prb_featset_finish, prb_featset_finish_top)", PRB_ERR_STATE);
   if (!fs->db) return refuse(fn, "no page is merged into the feature table: the real batch against every page comes first", PRB_ERR_STATE);
   for (size_t p = 0; p < fs->merged.size(); p++)
     if (!fs->merged[p])
@@ -162,9 +161,23 @@ int prb_fnullset_create(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, prb_fnul
   t->chain = fs->chain;
   t->ctx = ctx; // (from here on the destructor has a device and a stream to release under)
   t->db = fs->db;
-  if (int rc = finish_featset(fn, ctx, fs, t.get())) return rc;
+  if (int rc = finish_featset(fn, ctx, fs, n, t.get())) return rc;
   *out = t.release();
   return PRB_OK;
+}
+
+extern "C" {
+
+int prb_fnullset_create(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, prb_fnullset **out) {
+  return create_fnullset("prb_fnullset_create", ctx, fs, ndecoys, 0, out);
+}
+int prb_fnullset_create_top(prb_ctx *ctx, prb_featset *fs, int32_t ndecoys, int32_t n, prb_fnullset **out) {
+  const char *fn = "prb_fnullset_create_top";
+  if (const std::string why = bad_n(n); !why.empty()) {
+    if (out) *out = nullptr;
+    return refuse(fn, why);
+  }
+  return create_fnullset(fn, ctx, fs, ndecoys, n, out);
 }
 
 int prb_fnullset_begin(prb_ctx *ctx, prb_fnullset *t, const int32_t *owner, const int32_t *decoy, int32_t ndq) {

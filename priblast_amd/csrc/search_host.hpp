@@ -891,6 +891,8 @@ struct prb_featset : prb::MergeTable {
   prb::DevBuf head, start;                                          // prb_featset_add_hits: the runs of the caller's list
   prb::DevBuf h_query, h_db_id, h_e_tot, h_e_acc, h_e_hyb, h_ends;  // ... and the list as columns
   prb::DevBuf out;                                                  // prb_featset_finish: the records in order
+  prb::DevBuf topCnt, topOff, topKey, topPlace, topSel, topOut;     // prb_featset_finish_top: the counts and their scans, the chunks' lists, the ranked places and records
+  int32_t top_n = 0;                                                // ... the n it was finished with (0: a plain finish)
   std::vector<prb_feature_pair> recs;                               // prb_featset_finish
   prb::TableFeed feed() const override { return prb::TableFeed::kPairRuns; }
   int take(const prb::SubBatch &b) override;
@@ -903,7 +905,7 @@ struct prb_featset : prb::MergeTable {
   void release() {
     if (!quiesce()) return;
     for (prb::DevBuf *b : {&table, &badflag, &cnt, &ioff, &tmp, &flag, &long_list, &sel, &scanTmp, &count, &head, &start, &h_query, &h_db_id,
-                           &h_e_tot, &h_e_acc, &h_e_hyb, &h_ends, &out})
+                           &h_e_tot, &h_e_acc, &h_e_hyb, &h_ends, &out, &topCnt, &topOff, &topKey, &topPlace, &topSel, &topOut})
       b->release();
   }
   ~prb_featset() { release(); } // (also on the error paths of prb_featset_create)
@@ -944,10 +946,11 @@ struct prb_fnullset : prb::TableState, prb::DecoySet { // (`merged`: a bit per (
 };
 
 namespace prb {
-// capi_features.hip: prb_featset_finish proper, for `fn_name`.  keep != nullptr (prb_fnullset_create): before the feature
-// table's device memory is released, the gathered records - still on the device - go to keep_feature_records
-// (capi_fnull.hip).
-int finish_featset(const char *fn_name, prb_ctx *ctx, prb_featset *fs, prb_fnullset *keep);
+// capi_features.hip: prb_featset_finish proper, for `fn_name`; n > 0 (prb_featset_finish_top, prb_fnullset_create_top):
+// each query's n best records only, ranked on the device.  keep != nullptr (prb_fnullset_create[_top]): before the
+// feature table's device memory is released, the records that the host gets - still on the device, the ranked ones with
+// n > 0 - go to keep_feature_records (capi_fnull.hip).
+int finish_featset(const char *fn_name, prb_ctx *ctx, prb_featset *fs, int32_t n, prb_fnullset *keep);
 int keep_feature_records(prb_ctx *ctx, prb_fnullset *fn, prb_featset *fs, const void *recs_dev, int64_t nrec);
 // capi_features.hip: what prb_featset_add_hits and prb_fnullset_add_hits do with a caller's list of final hits of one
 // page: checked on the host against the page `g` of the annotation and a batch of nq queries, as columns; the columns to

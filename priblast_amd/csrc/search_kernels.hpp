@@ -800,6 +800,30 @@ hipError_t launch_feat_cell_counts(const int64_t *first, const int64_t *end, int
 hipError_t launch_feat_gather(const void *rec, int64_t nrec, const int64_t *first, const int64_t *off, int32_t npages, int32_t nq, int64_t total,
                               void *out, uint32_t *bad, hipStream_t s);
 
+// ---- featuretop_kernels.hip: each query's n best records (prb_featset_finish_top, prb_fnullset_create_top) ----
+// The gathered records of launch_feat_gather and their scanned cell offsets: query q's records are the segment
+// [ioff[q * npages], ioff[(q + 1) * npages]) of rec[0, total); the rank key of a record is (energy_key(s.e_min), its
+// place in the segment), ascending.  bad: raised where a segment, a chunk, a place or a rank lies outside the table.
+struct FtopTab {
+  const int64_t *ioff; // [nq * npages + 1]
+  uint32_t *bad;
+  int64_t total;
+  int32_t nq, npages, n;
+};
+inline constexpr int kFtopChunk = 2048; // records per (query, chunk) work item: a power of two, at least 2 * kTopMaxN
+// nchunk[q] = the chunks of query q's segment, nkeep[q] = min(n, its length); [nq] of both = 0 (for their scans)
+hipError_t launch_ftop_counts(const FtopTab &t, int64_t *nchunk, int64_t *nkeep, hipStream_t s);
+// choff = the scan of nchunk: a workgroup per chunk w (of the query q with choff[q] <= w < choff[q + 1]) orders the
+// chunk's keys in LDS and writes its min(n, length) lowest to pe / pp [w * n + r] (energy key, place)
+hipError_t launch_ftop_chunks(const FtopTab &t, const void *rec, const int64_t *choff, int64_t nchunks, unsigned long long *pe, uint32_t *pp,
+                              hipStream_t s);
+// a workgroup per query folds its chunks' lists: top[q * n + r] = the place of query q's record of rank r < nkeep[q]
+hipError_t launch_ftop_merge(const FtopTab &t, const int64_t *choff, int64_t nchunks, const unsigned long long *pe, const uint32_t *pp,
+                             uint32_t *top, hipStream_t s);
+// koff = the scan of nkeep: out[o] (prb_feature_pair) = the record of rank o - koff[q] of query q, a lane per record
+hipError_t launch_ftop_gather(const FtopTab &t, const void *rec, const int64_t *koff, const uint32_t *top, int64_t nkept, void *out,
+                              hipStream_t s);
+
 // ============================================================================ fnull_kernels.hip: the feature null table
 // (prb_fnullset_*)  The kept (query, feature) records of a finished feature table, and per record how the query's decoys
 // fare against the feature.  There is no dense lookup - queries x features is too many -: key[0, nkept) = the records'

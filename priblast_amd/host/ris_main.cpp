@@ -73,8 +73,13 @@
 // decoy's minimum over its hits that meet the feature against the feature's minimum - in a feature null table on the GPU
 // (prb_fnullset_*), the decoys searched against the targets of each query's kept records only.  `-F` needs -A and is
 // refused with what -A is refused with, and in rank mode.
+// `ris -t -A FILE -N K` keeps each query's K records of lowest minimum energy (ties in -t -A order), best first: the cut
+// is made on the device when the batch's feature table is finished (prb_featset_finish_top), so only K records per query
+// reach the host, and the lines are lines of the `-t -A` run.  With -F the feature null table is made over the cut
+// (prb_fnullset_create_top): its lookup and scratch hold the kept records only, and a query's decoys are searched against
+// the targets of its K kept records only.  `-N` needs -A; everything else is refused through -A.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F have one table (kSwitchTable) that every
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
@@ -242,6 +247,12 @@ void usage() {
             "              WORLD_SIZE > 1; PRB_SPLIT has no effect; the output does not depend on PRB_BATCH or PRB_DEVICES;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target - every listed one under -L -, the\n"
             "              output is the same)\n"
+            "    -N INT    with -t -A: only the INT lines of lowest minimum interaction energy per query, best first (ties in\n"
+            "              -t -A order), chosen on the GPU before the records leave it; the lines are lines of the run without\n"
+            "              -N.  With -F the decoys are searched against the targets of each query's INT kept lines only, and\n"
+            "              the null columns of a kept line are those of the run without -N (1 <= INT <= 1024; with -F, -u, -j,\n"
+            "              -L, -Z and the search options; not with what -A can't be combined with, nor with WORLD_SIZE > 1;\n"
+            "              the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -266,7 +277,8 @@ thread_local bool t_team_thread = false;
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
 // `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score, `-t -G -R` the N best
-// query-group pairs per group, `-t -A` a line per query-feature pair, `-t -A -F` the same with the feature's null columns.
+// query-group pairs per group, `-t -A` a line per query-feature pair, `-t -A -F` the same with the feature's null columns
+// (`-N K` chooses no mode of its own: kFeatures and kFeatureNull then finish their table with each query's K best records).
 enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures, kFeatureNull };
 // -z, -P, -E, -F: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
 // (search_null_batch, search_gnull_batch, search_scored_batch, search_fnull_batch) - and by one worker: there is no merge of two of them
@@ -278,7 +290,7 @@ constexpr bool runs_decoys(OutputMode m) {
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -309,6 +321,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
      bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kT, true},
     {'F', "an empirical p-value per query-feature pair from N shuffled decoys",
      bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kA, true},
+    // (what -A can't be combined with, and one process per GPU, are refused through -A's row, in its words)
+    {'N', "the N best features per query", 0, kA, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -322,6 +336,7 @@ struct Args {
   bool given[kSwitches] = {};
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
   int grouprank = 0;                                // -R, likewise
+  int feattop = 0;                                  // -N, likewise
   int decoys = 0;                                   // -z, -P, -E or -F, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
@@ -706,8 +721,8 @@ void check_switches(const Args &a) {
     // (-Z goes with either switch that makes decoys)
     if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE] || a.given[kF]))) die("Error: " + described(s) + " needs " + described(need));
   }
-  for (Switch s : {kR, kK, kN, kGR})
-    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : a.top; a.given[s] && (v < 1 || v > 1024))
+  for (Switch s : {kR, kK, kN, kGR, kFN})
+    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : s == kFN ? a.feattop : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
@@ -733,7 +748,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -764,6 +779,7 @@ Args parse_args(int argc, char **argv) {
     case 'E': a.given[kE] = true, a.decoys = parse_count(optarg); break;
     case 'F': a.given[kF] = true, a.decoys = parse_count(optarg); break;
     case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
+    case 'N': a.given[kFN] = true, a.feattop = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -1331,7 +1347,8 @@ void finish_table(const Run &r, Worker &w, const Prepared &p, BatchResult &mine,
   case OutputMode::kFeatures:
     for (BatchResult *o : others)
       if (prb_featset_merge(w.ctx, mine.features.get(), o->features.get())) die(prb_last_error());
-    if (prb_featset_finish(w.ctx, mine.features.get())) die(prb_last_error());
+    if (r.a.given[kFN] ? prb_featset_finish_top(w.ctx, mine.features.get(), r.a.feattop) : prb_featset_finish(w.ctx, mine.features.get()))
+      die(prb_last_error());
     break;
   case OutputMode::kGroupRank: // (a group's members may lie on any page: only the batch's whole group table is ranked)
     for (BatchResult *o : others)
@@ -1540,6 +1557,8 @@ BatchResult search_gnull_batch(const Run &r, Worker &w, Prepared &p) {
 // prb_fnullset_begin and prb_fnullset_end.  Unless PRB_NULL_MASK=0, a piece is searched under a pair mask that allows each
 // decoy the targets of its owner's kept records only (under -L those are listed pairs already); with PRB_NULL_MASK=0,
 // under -L, every pair listed for the owner.  A query without a record has its decoys searched against nothing, and closed.
+// With -N K the feature null table is made over each query's K best records (prb_fnullset_create_top), which are then all
+// that "kept" means here: the mask allows a decoy the targets of those K records only.
 BatchResult search_fnull_batch(const Run &r, Worker &w, Prepared &p) {
   BatchResult res = empty_result(r);
   const bool masked = null_mask_wanted();
@@ -1551,7 +1570,8 @@ BatchResult search_fnull_batch(const Run &r, Worker &w, Prepared &p) {
   for (int page = 0; page < r.npages; page++)
     if (prb_search_page_features(w.ctx, p.qb, w.db, page, &o, real.get())) die(prb_last_error());
   prb_fnullset *fn = nullptr;
-  if (prb_fnullset_create(w.ctx, real.get(), r.a.decoys, &fn)) die(prb_last_error());
+  if (r.a.given[kFN] ? prb_fnullset_create_top(w.ctx, real.get(), r.a.decoys, r.a.feattop, &fn) : prb_fnullset_create(w.ctx, real.get(), r.a.decoys, &fn))
+    die(prb_last_error());
   res.fnull.reset(fn);
   // per query the targets of its kept records (a target comes once per feature with a record: the mask takes it again)
   std::vector<std::vector<std::pair<int32_t, int32_t>>> kept(masked ? nq : 0);
