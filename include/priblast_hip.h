@@ -233,6 +233,9 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   the counts and their scan - when its targets have no feature, and 2 more - head flags and the selection of the runs'
  *   first hits - in front per prb_fnullset_add_hits with hits; prb_fnullset_end: the close, 1, or none for a batch without
  *   cells; prb_fnullset_finish: the gather, 1, or none without records);
+ * "featrank" (prb_featrank_add_featset: the records of the feature table merged into the feature ranking table - sort
+ *   keys, the stable sort by feature, rank keys and heads, the selection of the heads, the merge; launches = 5, or none when
+ *   the feature table holds no record; prb_featrank_add_records: 5, or none for n = 0; prb_featrank_merge: 1);
  * host wall-clock pseudo stages: "host_dfs" (background seed DFS), "host_dfs_wait",
  * "host_search_range", "host_cands", "host_drain_tail", "host_download" (the synchronous copy of
  * the hits of last_stage 1 / 2). */
@@ -1114,6 +1117,14 @@ typedef struct prb_feature_pair {
 #ifdef __cplusplus
 static_assert(sizeof(prb_feature_pair) == 80, "prb_feature_pair: no padding");
 #endif
+/* a record of the feature ranking table (prb_featrank_*, below): f.s.query holds the query's identifier */
+typedef struct prb_featrank_pair {
+  prb_feature_pair f;
+  int32_t rank, reserved; /* the rank within the feature, from 0; always 0 */
+} prb_featrank_pair;
+#ifdef __cplusplus
+static_assert(sizeof(prb_featrank_pair) == 88, "prb_featrank_pair: no padding");
+#endif
 typedef struct prb_annot prb_annot;
 typedef struct prb_featset prb_featset;
 int prb_annot_create(prb_ctx *ctx, const prb_db *db, int64_t n, const int32_t *page, const int32_t *db_id, const int32_t *start,
@@ -1220,6 +1231,78 @@ void prb_fnullset_free(prb_fnullset *fn);
 int prb_write_fnull_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
                           const prb_fnull_pair *recs, int64_t nrecs, const char *const *feat_names, const int32_t *feat_start,
                           const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
+
+/* ---- the N best queries per feature (`ris -t -A FILE -B N`): a feature ranking table on the device ----
+ * A feature table lives for one batch, and prb_featset_finish_top ranks features per query.  A feature ranking table
+ * holds, for every feature i of the annotation, the N records of lowest s.e_min among all the (query, feature) records
+ * merged into it over a whole run (fewer when the feature has fewer).  A record is a prb_featrank_pair: f = the
+ * prb_feature_pair exactly as prb_featset_finish returns it, but `f.s.query` holds a caller-given identifier, int32 >= 0,
+ * as in prb_search_page_targets (the command line: the 0-based position in the input FASTA); `rank` = the rank within
+ * the feature, `reserved` = 0.  Records of a feature are ranked by s.e_min ascending, compared as doubles (-0.0 == +0.0;
+ * the stored record keeps the bits it came with); equal values are ordered by the identifier ascending.  A feature lies
+ * in one page and a (query, target) run in one sub-batch (above), so a (query, feature) has at most one record, no two
+ * keys of a feature's list are equal, and the finished table depends - bit for bit - neither on how the queries are cut
+ * into batches or sub-batches, nor on the order of the batches, nor on which context (worker) took what.
+ *   prb_featrank_create       an empty table for the annotation (1 <= n <= 1024 and an annotation of at least one feature,
+ *                             else PRB_ERR_ARG).  The table is dense: n slots of 88 B and n keys of 16 B per feature,
+ *                             plus a fill count per feature, in HBM; PRB_ERR_NOMEM when that cannot be allocated.  The
+ *                             annotation must outlive the table
+ *   prb_featrank_add_featset  every record of the UNFINISHED feature table fs merged into the table, on the device:
+ *                             nothing is copied to the host, and fs is left untouched - it can still be finished or
+ *                             merged.  query_ids[q] = the identifier of query q of fs's batch.  Refused, the table
+ *                             untouched: fs or the table made with another context, an fs made with another annotation
+ *                             (the handles may differ where the annotations are equal), an identifier below 0, given
+ *                             twice in the call or already merged into the table, distinct_sites or chain_sites other
+ *                             than those the table holds (PRB_ERR_ARG); an fs that is finished, broken or bad, and an fs
+ *                             that has NOT had every page of its database merged - every identifier is merged exactly
+ *                             once, so half a batch cannot be ranked - (PRB_ERR_STATE).  A complete fs without records
+ *                             marks its identifiers and launches nothing.  The stage counts and the unassigned hits of
+ *                             fs are added to the table's
+ *   prb_featrank_add_records  the same merge for a caller's records in host memory whose f.s.query holds the identifier
+ *                             already (tests; callers with a fold of their own); rank and reserved are ignored.
+ *                             PRB_ERR_ARG, table untouched: a feature outside the annotation, an identifier below 0, an
+ *                             (identifier, feature) given twice in the call, an identifier merged by an earlier call -
+ *                             every identifier of a call is marked as merged, so all the records of one identifier come
+ *                             in one call.  n = 0 does nothing
+ *   prb_featrank_merge        two unfinished tables into one, on the device, under the contract of prb_targetset_merge:
+ *                             src may live on another device; both have the same n and the same number of features,
+ *                             hold the same distinct_sites and chain_sites unless one is empty, and no identifier is
+ *                             merged into both: anything else returns PRB_ERR_ARG and leaves both tables as they were.
+ *                             dst then holds - bit for bit - the table of all that was merged into either, and the sums
+ *                             of their stage counts and unassigned hits; src is left empty but valid
+ *   prb_featrank_finish       the filled slots compacted on the device (a scan over the fills, a gather in rank order)
+ *                             and copied to the host in one copy; the device memory is released.  prb_featrank_records
+ *                             then returns the records by feature index ascending, then rank; `rank` counts from 0
+ *                             within the feature.  Nothing can be merged after it (a second call does nothing)
+ *   prb_featrank_counts       the stage counts of prb_featset_counts, summed over the feature tables merged
+ *   prb_featrank_unassigned   the unassigned hits of prb_featset_unassigned, summed likewise
+ * A merge does work in proportion to the feature table's records: their features as sort keys, a stable sort by feature,
+ * the rank keys (the monotone 64-bit key of e_min, the identifier) and the heads of the features' runs, and a wavefront
+ * per run that merges it into the feature's ranked list in LDS - the lists, the merge and the gather of the per-target
+ * table.  No floating-point atomics, and nothing depends on the order in which threads arrive.  On the device every kernel
+ * checks feature, query and identifier against the tables' ranges again; a violation raises the table's `bad` flag and
+ * writes nothing, and this and every later call on the table returns PRB_ERR_STATE.  A merge that fails part way leaves
+ * the table unusable.  Stage timer "featrank": prb_featrank_add_featset (launches = 5: sort keys, sort, rank keys and
+ * heads, selection of the heads, merge; none when fs holds no record), prb_featrank_add_records (5; none for n = 0),
+ * prb_featrank_merge (1); the launches booked to "feature" are those of the feature table's own calls, as ever. */
+typedef struct prb_featrank prb_featrank;
+int prb_featrank_create(prb_ctx *ctx, const prb_annot *an, int32_t n, prb_featrank **out);
+int prb_featrank_add_featset(prb_ctx *ctx, prb_featrank *fr, const prb_featset *fs, const int32_t *query_ids);
+int prb_featrank_add_records(prb_ctx *ctx, prb_featrank *fr, const prb_featrank_pair *recs, int64_t n);
+int prb_featrank_merge(prb_ctx *ctx, prb_featrank *dst, prb_featrank *src);
+int prb_featrank_finish(prb_ctx *ctx, prb_featrank *fr);
+int64_t prb_featrank_size(const prb_featrank *fr);
+const prb_featrank_pair *prb_featrank_records(const prb_featrank *fr);
+void prb_featrank_counts(const prb_featrank *fr, int64_t counts[3]);
+int64_t prb_featrank_unassigned(const prb_featrank *fr);
+void prb_featrank_free(prb_featrank *fr);
+/* The lines of `ris -t -A FILE -B N`: recs[0, nrecs) as prb_featrank_records returns them (by feature, then rank), one
+ * line each in that order, numbered from id0 on; every line is the prb_write_feature_lines line of its record's f.
+ * qnames and qlen_unmasked are indexed by the query's identifier (nq_total of them: every f.s.query lies below it); the
+ * other arguments and the results as prb_write_feature_lines. */
+int prb_write_featrank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                             const prb_featrank_pair *recs, int64_t nrecs, const char *const *feat_names, const int32_t *feat_start,
+                             const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *nlines, int64_t *nbytes);
 
 /* ---- output: SaveMyResults (rna_interaction_search.cpp:322-369) ----
  * The result lines of one batch of queries, grouped query by query and page by page and numbered

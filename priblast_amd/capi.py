@@ -100,6 +100,11 @@ FNULL_DTYPE = np.dtype(FEATURE_DTYPE.descr + [("decoys", "<i4"), ("pad", "<i4"),
                                               ("null_min", "<f8")])
 assert FNULL_DTYPE.itemsize == 112
 
+# prb_featrank_pair: the embedded prb_feature_pair's fields with `query` = the query's identifier, then the rank within the
+# feature (`ris -t -A FILE -B N`)
+FEATRANK_DTYPE = np.dtype(FEATURE_DTYPE.descr + [("rank", "<i4"), ("reserved", "<i4")])
+assert FEATRANK_DTYPE.itemsize == 88
+
 # prb_eval_score: a real hit's place among its query's real hits and among the pooled hits of its decoys (`ris -k N -E M`)
 EVAL_DTYPE = np.dtype([("decoys", "<i4"), ("reserved", "<i4"), ("null_le", "<i8"), ("rank", "<i8"), ("q_num", "<u4"), ("q_den", "<u4")])
 assert EVAL_DTYPE.itemsize == 32
@@ -305,6 +310,19 @@ SYMBOLS = {
     "prb_write_feature_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                                P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, ctypes.c_int, P(c_i64),
                                                P(c_i64)]),
+    "prb_featrank_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
+    "prb_featrank_add_featset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featrank_add_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64]),
+    "prb_featrank_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featrank_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_featrank_size": (c_i64, [ctypes.c_void_p]),
+    "prb_featrank_records": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_featrank_counts": (None, [ctypes.c_void_p, P(c_i64)]),
+    "prb_featrank_unassigned": (c_i64, [ctypes.c_void_p]),
+    "prb_featrank_free": (None, [ctypes.c_void_p]),
+    "prb_write_featrank_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                                P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, ctypes.c_int, P(c_i64),
+                                                P(c_i64)]),
     "prb_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "prb_comm_create": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_char_p, P(ctypes.c_void_p)]),
     "prb_comm_destroy": (None, [ctypes.c_void_p]),
@@ -1094,6 +1112,57 @@ def search_grouprank(ctx, db, group_of_page, ngroups, n, batches, opts=None, pag
     return (recs, counts) if with_counts else recs
 
 
+class FeatRank(_Table):
+    """prb_featrank: the N best queries per feature of an Annotation, in a table on the device that any number of batches
+    is merged into - each as its complete, unfinished FeatSet, or as FEATRANK_DTYPE records -; every batch names its queries
+    by identifiers of the caller's.  Close it before its annotation and its context."""
+    PREFIX = "featrank"
+
+    def __init__(self, ctx, annot, n):
+        h = ctypes.c_void_p()
+        _check(lib().prb_featrank_create(ctx.h, annot.h, n, ctypes.byref(h)))
+        self.h, self.ctx, self.annot = h, ctx, annot
+
+    def add_featset(self, fs, ids):
+        """prb_featrank_add_featset: every record of the unfinished FeatSet `fs` (every page merged), on the device;
+        ids[q] = the identifier of query q of its batch.  fs is left as it was"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        assert len(ids) == len(fs.qb.lens)
+        _check(lib().prb_featrank_add_featset(self.ctx.h, self.h, fs.h, ids.ctypes.data))
+
+    def add_records(self, recs):
+        """prb_featrank_add_records: a caller's FEATRANK_DTYPE records whose `query` is the identifier already"""
+        recs = np.ascontiguousarray(recs, FEATRANK_DTYPE)
+        _check(lib().prb_featrank_add_records(self.ctx.h, self.h, recs.ctypes.data if len(recs) else None, len(recs)))
+
+    def merge(self, other):
+        """prb_featrank_merge: the unfinished table `other` (over other identifiers; of any context) merged into this
+        one on the device; `other` is left empty"""
+        self.absorb(other)
+
+    def finish(self):
+        """prb_featrank_finish -> structured array FEATRANK_DTYPE (a copy), by feature, then rank"""
+        return self._finish("records", FEATRANK_DTYPE)
+
+    def unassigned(self):
+        return lib().prb_featrank_unassigned(self.h)
+
+
+def search_featrank(ctx, db, annot, n, batches, opts=None, pages=None, with_counts=False):
+    """The n (query, feature) records of lowest e_min per feature over batches = [(QBatch, ids)], every batch against
+    every page (in this order, if given) into a feature table of its own, which is merged into the ranking on the device
+    and dropped -> (structured array FEATRANK_DTYPE, by feature and rank; unassigned hits).  with_counts: -> (records,
+    unassigned, (seed, ungapped, final) counts summed over the batches)."""
+    with FeatRank(ctx, annot, n) as fr:
+        for qb, ids in batches:
+            with FeatSet(ctx, qb, annot) as fs:
+                for p in range(db.npages) if pages is None else pages:
+                    fs.merge(db, p, opts)
+                fr.add_featset(fs, ids)
+        recs, un, counts = fr.finish(), fr.unassigned(), fr.counts()
+    return (recs, un, counts) if with_counts else (recs, un)
+
+
 class GNullSet(_Table):
     """prb_gnullset: per kept (query, group) record of a group table, how the query's decoys fare against the group's
     members.  Made from a GroupSet with every page merged, which it finishes (gs.records() are then its records); the decoys
@@ -1506,6 +1575,16 @@ def write_grouprank_lines(db, qnames, qlen_unmasked, recs, group_names, group_si
     gsz = np.ascontiguousarray(group_sizes, np.int32)
     return _write(lib().prb_write_grouprank_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), gn,
                   gsz.ctypes.data if len(gsz) else None, len(group_names), id0, fd)
+
+
+def write_featrank_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start, feat_end, id0=0, fd=-1):
+    """Lines of `ris -t -A FILE -B N`: recs as FeatRank.finish returns them; qnames / qlen_unmasked indexed by query
+    identifier, feat_names / feat_start / feat_end by feature.  -> (lines, bytes) written to fd (-1: formatted and counted only)."""
+    recs = np.ascontiguousarray(recs, FEATRANK_DTYPE)
+    names = (ctypes.c_char_p * max(len(feat_names), 1))(*[n.encode() for n in feat_names])
+    fs, fe = np.ascontiguousarray(feat_start, np.int32), np.ascontiguousarray(feat_end, np.int32)
+    return _write(lib().prb_write_featrank_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), names,
+                  fs.ctypes.data, fe.ctypes.data, len(feat_names), id0, fd)
 
 
 def write_fnull_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start, feat_end, id0=0, fd=-1):

@@ -30,31 +30,6 @@ int table_guard(const char *fn, const prb_ctx *ctx, const prb_grouprank *t) {
   return PRB_OK;
 }
 
-// ncand candidates grouped by group and merged into the table (inside the caller's bracket of the "grouprank" timer):
-// groups(key, val) writes their sort keys, runs(keyS, valS, rkey, head) - behind the stable sort - their rank keys and
-// the heads of the groups' runs, merge(runs) merges every run into its group's list; 5 launches
-template <class Groups, class Runs, class Merge>
-int merge_group_candidates(prb_ctx *ctx, SearchWs &w, prb_grouprank *t, int64_t ncand, Groups groups, Runs runs, Merge merge) {
-  int rc;
-  const size_t NC = (size_t)ncand;
-  if ((rc = t->key.ensure(NC * 4)) || (rc = t->keyS.ensure(NC * 4)) || (rc = t->val.ensure(NC * 4)) || (rc = t->valS.ensure(NC * 4)) ||
-      (rc = t->rkey.ensure(NC * sizeof(TargetKey))) || (rc = t->head.ensure(NC)) || (rc = t->start.ensure(NC * 4)))
-    return rc;
-  PRB_HIP(groups(t->key.as<uint32_t>(), t->val.as<uint32_t>()));
-  if ((rc = sort_target_keys(ctx->stream, t->sortTmp, t->key.as<uint32_t>(), t->keyS.as<uint32_t>(), t->val.as<uint32_t>(), t->valS.as<uint32_t>(), NC,
-                             (unsigned)bits_for(std::max(t->ngroups - 1, 1)))))
-    return rc;
-  PRB_HIP(runs(t->keyS.as<uint32_t>(), t->valS.as<uint32_t>(), t->rkey.as<TargetKey>(), t->head.as<uint8_t>()));
-  int64_t nruns = 0;
-  if ((rc = select_flagged(ctx, w, nullptr, t->head.as<uint8_t>(), t->start.as<uint32_t>(), NC, &nruns))) return rc;
-  if (nruns <= 0 || nruns > ncand || nruns > t->ngroups) {
-    set_error("group ranking table: " + std::to_string(nruns) + " groups for " + std::to_string(ncand) + " candidates");
-    return PRB_ERR_STATE;
-  }
-  PRB_HIP(merge(GroupRankRuns{t->rkey.as<TargetKey>(), t->keyS.as<uint32_t>(), t->start.as<uint32_t>(), nruns, ncand}));
-  return PRB_OK;
-}
-
 // behind a merge: the device's flag
 int bad_guard(const char *fn, prb_ctx *ctx, prb_grouprank *t) {
   if (int rc = fetch_bad(ctx, t)) return rc;
@@ -126,8 +101,8 @@ int prb_grouprank_add_groupset(prb_ctx *ctx, prb_grouprank *t, const prb_groupse
   if ((rc = select_flagged(ctx, w, nullptr, t->occ.as<uint8_t>(), t->sel.as<uint32_t>(), (size_t)S, &ncand))) return rc;
   if (ncand < 0 || ncand > S || ncand > INT32_MAX) return refuse(fn, "bad candidate count " + std::to_string(ncand), PRB_ERR_STATE);
   if (ncand) {
-    if ((rc = merge_group_candidates(
-             ctx, w, t, ncand,
+    if ((rc = merge_ranked_candidates(
+             ctx, w, t, kWhat, "groups", t->ngroups, ncand,
              [&](uint32_t *key, uint32_t *val) { return launch_grouprank_slot_groups(tab, t->sel.as<uint32_t>(), ncand, key, val, bad, ctx->stream); },
              [&](const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head) {
                return launch_grouprank_slot_runs(tab, ids, ncand, key, val, rkey, head, bad, ctx->stream);
@@ -186,8 +161,8 @@ int prb_grouprank_add_records(prb_ctx *ctx, prb_grouprank *t, const prb_group_pa
   PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's array may go)
   uint32_t *bad = t->badflag.as<uint32_t>();
   if ((rc = ctx->time_begin())) return rc;
-  if ((rc = merge_group_candidates(
-           ctx, w, t, n, [&](uint32_t *key, uint32_t *val) { return launch_grouprank_record_groups(t->h_rec.p, n, t->ngroups, key, val, bad, ctx->stream); },
+  if ((rc = merge_ranked_candidates(
+           ctx, w, t, kWhat, "groups", t->ngroups, n, [&](uint32_t *key, uint32_t *val) { return launch_grouprank_record_groups(t->h_rec.p, n, t->ngroups, key, val, bad, ctx->stream); },
            [&](const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head) {
              return launch_grouprank_record_runs(t->h_rec.p, n, t->ngroups, key, val, rkey, head, bad, ctx->stream);
            },

@@ -206,6 +206,30 @@ int prb_write_fnull_lines(const prb_db *db, int32_t nq, const char *const *qname
       [&](const FNullView &v, LineSink &sink) { return format_fnull_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
+int prb_write_featrank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
+                             const prb_featrank_pair *recs, int64_t n, const char *const *feat_names, const int32_t *feat_start,
+                             const int32_t *feat_end, int64_t nfeat, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<FeatRankView>(
+      "prb_write_featrank_lines", n >= 0 && (!n || recs) && nfeat >= 0 && (!nfeat || (feat_names && feat_start && feat_end)), db, nq_total,
+      qnames, qlen_unmasked, lines, bytes, fd,
+      [&](FeatRankView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_feature_pair &x = recs[i].f;
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq_total || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || x.feature < 0 || x.feature >= nfeat || !feat_names[x.feature] ||
+              x.inside < 0 || x.inside > x.s.hits)
+            return bad_record("prb_write_featrank_lines: record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = recs;
+        v.n = n;
+        v.feat_names = feat_names;
+        v.feat_start = feat_start;
+        v.feat_end = feat_end;
+        return (int)PRB_OK;
+      },
+      [&](const FeatRankView &v, LineSink &sink) { return format_featrank_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
 int prb_write_grouprank_lines(const prb_db *db, int32_t nq_total, const char *const *qnames, const int32_t *qlen_unmasked,
                               const prb_group_pair *recs, int64_t n, const char *const *group_names, const int32_t *group_sizes,
                               int32_t ngroups, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {

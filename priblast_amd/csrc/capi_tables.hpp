@@ -1,5 +1,5 @@
-// The protocol of the twelve result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
-// capi_groups.hip, capi_grouprank.hip, capi_gnull.hip, capi_eval.hip, capi_features.hip, capi_fnull.hip): what a prb_*_create starts with, what is checked before a page, a
+// The protocol of the thirteen result tables, each step once (capi_top.hip, capi_targets.hip, capi_spans.hip, capi_null.hip,
+// capi_groups.hip, capi_grouprank.hip, capi_gnull.hip, capi_eval.hip, capi_features.hip, capi_fnull.hip, capi_featrank.hip): what a prb_*_create starts with, what is checked before a page, a
 // caller's list, a batch of decoys or another table is merged, the search of a page into a table, the uploads of a
 // caller's arrays, the device's `bad` flag, the merge of one table into another across contexts and devices, and what
 // every prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check
@@ -60,7 +60,7 @@ inline int finish_guard(const char *fn_name, const char *what, const prb_ctx *ct
   return PRB_OK;
 }
 
-// ---- prb_targetset_finish / prb_grouprank_finish: the ranked lists of a run table (rank_kernels.hpp) to the host
+// ---- prb_targetset_finish / prb_grouprank_finish / prb_featrank_finish: the ranked lists of a run table (rank_kernels.hpp) to the host
 // fill[0, nlists] (the last one 0) scanned, the filled slots - at most `entries` - gathered by list and rank on the
 // device by gather(off, total, out), and copied to `recs` in one copy
 template <class Rec, class Gather>
@@ -296,6 +296,34 @@ inline int upload_owners(prb_ctx *ctx, DecoySet *t, const int32_t *owner, const 
   PRB_HIP(hipMemcpyAsync(t->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
   PRB_HIP(hipMemcpyAsync(t->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
+  return PRB_OK;
+}
+
+// ---- prb_grouprank_add_* / prb_featrank_add_*: a merge's candidates into the ranked lists of a run table
+// ncand candidates grouped by list - `lists`: "groups", "features"; nlists of them - and merged into the table `t` of
+// noun `what` (inside the caller's bracket of the table's timer): groups(key, val) writes their sort keys, runs(keyS,
+// valS, rkey, head) - behind the stable sort - their rank keys and the heads of the lists' runs, merge(runs) merges every
+// run into its list; 5 launches.  The table has the buffers key, keyS, val, valS, rkey, head, start and sortTmp.
+template <class T, class Groups, class Runs, class Merge>
+int merge_ranked_candidates(prb_ctx *ctx, SearchWs &w, T *t, const char *what, const char *lists, int32_t nlists, int64_t ncand, Groups groups,
+                            Runs runs, Merge merge) {
+  int rc;
+  const size_t NC = (size_t)ncand;
+  if ((rc = t->key.ensure(NC * 4)) || (rc = t->keyS.ensure(NC * 4)) || (rc = t->val.ensure(NC * 4)) || (rc = t->valS.ensure(NC * 4)) ||
+      (rc = t->rkey.ensure(NC * sizeof(TargetKey))) || (rc = t->head.ensure(NC)) || (rc = t->start.ensure(NC * 4)))
+    return rc;
+  PRB_HIP(groups(t->key.template as<uint32_t>(), t->val.template as<uint32_t>()));
+  if ((rc = sort_target_keys(ctx->stream, t->sortTmp, t->key.template as<uint32_t>(), t->keyS.template as<uint32_t>(),
+                             t->val.template as<uint32_t>(), t->valS.template as<uint32_t>(), NC, (unsigned)bits_for(std::max(nlists - 1, 1)))))
+    return rc;
+  PRB_HIP(runs(t->keyS.template as<uint32_t>(), t->valS.template as<uint32_t>(), t->rkey.template as<TargetKey>(), t->head.template as<uint8_t>()));
+  int64_t nruns = 0;
+  if ((rc = select_flagged(ctx, w, nullptr, t->head.template as<uint8_t>(), t->start.template as<uint32_t>(), NC, &nruns))) return rc;
+  if (nruns <= 0 || nruns > ncand || nruns > nlists) {
+    set_error(std::string(what) + " table: " + std::to_string(nruns) + " " + lists + " for " + std::to_string(ncand) + " candidates");
+    return PRB_ERR_STATE;
+  }
+  PRB_HIP(merge(GroupRankRuns{t->rkey.template as<TargetKey>(), t->keyS.template as<uint32_t>(), t->start.template as<uint32_t>(), nruns, ncand}));
   return PRB_OK;
 }
 

@@ -447,8 +447,8 @@ struct SubBatch {
   const int32_t *fresh_bp = nullptr;
 };
 
-// What the twelve result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
-// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featset, prb_fnullset): whose they are, whether they can still be merged into, and the block on the device that
+// What the thirteen result tables have in common (prb_topset, prb_tophits, prb_profset, prb_targetset, prb_covset,
+// prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featset, prb_fnullset, prb_featrank): whose they are, whether they can still be merged into, and the block on the device that
 // the merges work on.  What every prb_*_merge and prb_*_finish checks (capi_tables.hpp), and what a page search hands
 // its sub-batches to: the table says which feed it takes, and takes it - in a bracket of its own stage timer, in its
 // own file; nothing leaves the device.
@@ -466,7 +466,7 @@ struct TableState {
   int64_t counts[3] = {0, 0, 0};
   DevBuf table;                // the table proper, one block (every table says what it holds)
   bool bad = false;            // the device's `bad` flag, as the last call left it (fetch_bad, capi_tables.hpp) - of the
-  DevBuf badflag;              // tables that keep one of their own: prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset
+  DevBuf badflag;              // tables that keep one of their own: prb_nullset, prb_groupset, prb_grouprank, prb_gnullset, prb_evalset, prb_featrank
   // What their release() starts with - nothing of such a table is released while work on it may still be queued on its
   // context's stream: false = there is no context yet, and so nothing to release
   bool quiesce() const {
@@ -486,7 +486,7 @@ struct MergeTable : TableState {
 };
 
 // The tables that live for a whole run and are keyed by the database's targets (page, db_id) (prb_targetset, prb_covset)
-// or by its groups (prb_grouprank: one "page", its "targets" the groups): such a table takes any number of batches, so
+// or by its groups or features (prb_grouprank, prb_featrank: one "page", its "targets" the groups / the features): such a table takes any number of batches, so
 // it keeps a bit per (page, query identifier)
 struct RunTable : TableState {
   std::vector<int64_t> tbase;                 // [npages + 1] the first target of every page; back() = the targets
@@ -751,7 +751,7 @@ struct prb_groupset : prb::MergeTable {
 
 // prb_grouprank_create .. prb_grouprank_free: the group ranking table of a run (capi_grouprank.hip): per group its n best
 // queries over as many batches as the caller likes, fed from each batch's complete group table or from a caller's
-// records (merge_group_candidates) - never by a search itself.  A run table with one "page": `merged` keeps a bit per
+// records (merge_ranked_candidates, capi_tables.hpp) - never by a search itself.  A run table with one "page": `merged` keeps a bit per
 // query identifier, tbase = {0, ngroups}.  It owns all its device memory.
 // The block: TargetKey[G * n], prb_group_pair[G * n], int32_t fill[G + 1] (the last one 0)
 struct prb_grouprank : prb::RunTable {
@@ -943,6 +943,37 @@ struct prb_fnullset : prb::TableState, prb::DecoySet { // (`merged`: a bit per (
       b->release();
   }
   ~prb_fnullset() { release(); } // (also on the error paths of prb_fnullset_create)
+};
+
+// prb_featrank_create .. prb_featrank_free: the feature ranking table of a run (capi_featrank.hip): per feature of the
+// annotation its n best queries over as many batches as the caller likes, fed from each batch's complete feature table or
+// from a caller's records (merge_ranked_candidates, capi_tables.hpp) - never by a search itself.  A run table with one
+// "page": `merged` keeps a bit per query identifier, tbase = {0, nfeat}.  It owns all its device memory.
+// The block: TargetKey[F * n], prb_featrank_pair[F * n], int32_t fill[F + 1] (the last one 0)
+struct prb_featrank : prb::RunTable {
+  const prb_annot *annot = nullptr;
+  int32_t n = 0, nfeat = 0;
+  int64_t unassigned = 0;                                       // summed over the feature tables merged
+  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per merge: the candidates in feature order
+  prb::DevBuf h_rec;                                            // prb_featrank_add_records: the caller's records
+  std::vector<prb_featrank_pair> recs;                          // prb_featrank_finish
+  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+  int take(const prb::SubBatch &) override { return PRB_ERR_STATE; } // (no search feeds it)
+  size_t entries() const { return (size_t)nfeat * (size_t)n; }
+  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_featrank_pair)) + ((size_t)nfeat + 1) * sizeof(int32_t); }
+  // the three arrays of a block at b (the table's own, or a copy of another table's)
+  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
+  prb_featrank_pair *slots_of(void *b) const {
+    return reinterpret_cast<prb_featrank_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey));
+  }
+  int32_t *fill_of(void *b) const {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_featrank_pair)));
+  }
+  void release() {
+    if (!quiesce()) return;
+    for (prb::DevBuf *b : {&table, &badflag, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp, &h_rec}) b->release();
+  }
+  ~prb_featrank() { release(); } // (also on the error paths of prb_featrank_create)
 };
 
 namespace prb {

@@ -824,6 +824,44 @@ hipError_t launch_ftop_merge(const FtopTab &t, const int64_t *choff, int64_t nch
 hipError_t launch_ftop_gather(const FtopTab &t, const void *rec, const int64_t *koff, const uint32_t *top, int64_t nkept, void *out,
                               hipStream_t s);
 
+// ============================================================================ featrank_kernels.hip: feature ranking table
+// (prb_featrank_*)  Per feature of the annotation n ranked keys (TargetKey: `id` = the query's identifier), n payload
+// slots (prb_featrank_pair) and a fill count, the lists of rank_kernels.hpp as the per-target table keeps them.  The
+// candidates of one merge come from a batch's unfinished feature table - the records rec[0, nrec) (prb_feature_pair) of
+// its block, named by their place; ids[q] = the identifier of query q of its nq - or from a caller's records
+// (prb_featrank_pair, f.s.query = the identifier).  bad: set when a candidate names a feature, a query or an identifier
+// outside its table; such a candidate is skipped and nothing is written for it.
+struct FeatRankFeed {
+  const void *rec; // [nrec]
+  int64_t nrec;
+  const int32_t *ids; // [nq]
+  int32_t nq, nfeat;
+};
+// key[c] = the feature of candidate c, val[c] = its place / its index: what the stable sort by feature takes
+hipError_t launch_featrank_table_features(const FeatRankFeed &t, uint32_t *key, uint32_t *val, uint32_t *bad, hipStream_t s);
+hipError_t launch_featrank_record_features(const void *rec, int64_t nrec, int32_t nfeat, uint32_t *key, uint32_t *val, uint32_t *bad,
+                                           hipStream_t s);
+// behind that sort (key, val sorted): rkey[i] = (the energy key of candidate val[i], its identifier, val[i]), head[i] = 1
+// where key changes (and for i = 0): the first candidate of every feature's run
+hipError_t launch_featrank_table_runs(const FeatRankFeed &t, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head,
+                                      uint32_t *bad, hipStream_t s);
+hipError_t launch_featrank_record_runs(const void *rec, int64_t nrec, int32_t nfeat, const uint32_t *key, const uint32_t *val, TargetKey *rkey,
+                                       uint8_t *head, uint32_t *bad, hipStream_t s);
+// the runs of rkey (GroupRankRuns: run r is feature group_of[start[r]]) merged into the table, a wavefront per run; no
+// (identifier, feature) may be in the table yet
+hipError_t launch_featrank_table_merge(const FeatRankFeed &t, const GroupRankRuns &r, int32_t n, TargetKey *keys, void *slots, int32_t *fill,
+                                       hipStream_t s);
+hipError_t launch_featrank_record_merge(const void *rec, int64_t nrec, const GroupRankRuns &r, int32_t nfeat, int32_t n, TargetKey *keys,
+                                        void *slots, int32_t *fill, hipStream_t s);
+// prb_featrank_merge: per feature, the table's and src's ranked entries merged under the table's order, the first n kept,
+// in the table (src is only read); a wavefront per feature
+hipError_t launch_featrank_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
+                                int64_t nfeat, int32_t n, hipStream_t s);
+// prb_featrank_finish: out[0, total) = the filled slots by feature, then rank (`rank` set); off = the exclusive scan of
+// fill over nfeat + 1 values
+hipError_t launch_featrank_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t nfeat, int32_t n, int64_t total,
+                                  void *out, hipStream_t s);
+
 // ============================================================================ fnull_kernels.hip: the feature null table
 // (prb_fnullset_*)  The kept (query, feature) records of a finished feature table, and per record how the query's decoys
 // fare against the feature.  There is no dense lookup - queries x features is too many -: key[0, nkept) = the records'

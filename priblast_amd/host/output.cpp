@@ -331,6 +331,13 @@ void format_grouprank_piece(const Piece &pc, const GroupView &v, const std::vect
     put_group_line(b, id++, v.names[v.r[i].s.query], v.qlen_unmasked[v.r[i].s.query], tabs, v.r[i], v.group_names, v.group_sizes);
 }
 
+// the feature line of records that are not grouped by query: f.s.query is the query's identifier
+void format_featrank_piece(const Piece &pc, const FeatRankView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++)
+    put_feature_line(b, id++, v.names[v.r[i].f.s.query], v.qlen_unmasked[v.r[i].f.s.query], tabs, v.r[i].f, v.feat_names, v.feat_start, v.feat_end);
+}
+
 // the group line, then the null columns
 void format_gnull_piece(const Piece &pc, const GNullView &v, const std::vector<SeqTable> &tabs, Buf &b) {
   int64_t id = pc.id;
@@ -491,6 +498,13 @@ int64_t format_grouprank_batch(const GroupView &v, const std::vector<SeqTable> &
   std::vector<Piece> pieces;
   for (int64_t i = 0; i < v.n; i += kPieceLines) pieces.push_back(Piece{0, 0, i, std::min(v.n, i + kPieceLines), id0 + i});
   return write_pieces(pieces, [&](const Piece &pc, Buf &b) { format_grouprank_piece(pc, v, tabs, b); }, sink, threads) ? id0 + v.n : -1;
+}
+
+int64_t format_featrank_batch(const FeatRankView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (as the per-target records: in output order, not grouped by query)
+  std::vector<Piece> pieces;
+  for (int64_t i = 0; i < v.n; i += kPieceLines) pieces.push_back(Piece{0, 0, i, std::min(v.n, i + kPieceLines), id0 + i});
+  return write_pieces(pieces, [&](const Piece &pc, Buf &b) { format_featrank_piece(pc, v, tabs, b); }, sink, threads) ? id0 + v.n : -1;
 }
 
 int64_t format_region_batch(const RegionView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

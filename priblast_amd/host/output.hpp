@@ -125,6 +125,16 @@ int64_t format_fnull_batch(const FNullView &v, const std::vector<SeqTable> &tabs
 // then by rank - not grouped by query): names and qlen_unmasked are indexed by the records' s.query, an identifier.
 int64_t format_grouprank_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
+// Lines of `ris -t -A FILE -B N` (prb_featrank_records): the `-t -A` line of every record's f, in the records' order (by
+// feature, then by rank - not grouped by query): names and qlen_unmasked are indexed by the records' f.s.query, an identifier.
+struct FeatRankView : QueryView {
+  const prb_featrank_pair *r = nullptr;
+  int64_t n = 0;
+  const char *const *feat_names = nullptr;
+  const int32_t *feat_start = nullptr, *feat_end = nullptr;
+};
+int64_t format_featrank_batch(const FeatRankView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+
 // Lines of `ris -t -G FILE -P N` (prb_gnullset_pairs): the line of `-t -G` for every kept record, in the records' order,
 // with the null columns of `-t -z` behind it:
 //   ... ,Group,Members,GroupSize,GroupHits ,Decoys,NullHits,NullLE,NullMin,PValue

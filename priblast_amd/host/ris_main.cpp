@@ -78,8 +78,15 @@
 // reach the host, and the lines are lines of the `-t -A` run.  With -F the feature null table is made over the cut
 // (prb_fnullset_create_top): its lookup and scratch hold the kept records only, and a query's decoys are searched against
 // the targets of its K kept records only.  `-N` needs -A; everything else is refused through -A.
+// `ris -t -A FILE -B N` is `-R` at the level of the features: the `-t -A` lines of each FEATURE's N queries of lowest
+// minimum energy over all the queries of the run.  A batch is searched page by page into its feature table as for `-t -A`
+// (with PRB_SPLIT the workers' tables merged), and that table - complete, never finished, never copied to the host - is
+// merged on the device into the feature ranking table that the worker owns for the whole run (prb_featrank_add_featset,
+// under the queries' input positions); at the end the first worker merges the others' into its own (prb_featrank_merge),
+// and only N records per feature reach the host, written by feature - in the order load_features numbers them - and rank.
+// `-B` needs -A and is refused with -F and -N; everything else is refused through -A.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N have one table (kSwitchTable) that every
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N -B have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
@@ -236,7 +243,8 @@ void usage() {
             "              and behind it the feature's name, its start-end and the hits that lie wholly inside it; lines by\n"
             "              query, then target in database order, then the target's features by start, end and line (with\n"
             "              -u, -j, -L and the search options; -s has no effect; not with -n, -z, -k, -q, -r, -c, -b, -G, -P, -E,\n"
-            "              -R, nor with WORLD_SIZE > 1; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
+            "              -R, nor with WORLD_SIZE > 1; the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT;\n"
+            "              the best queries per feature: -B)\n"
             "    -F INT    with -t -A: an empirical p-value per query-feature pair from INT shuffled decoys of each query, as -z\n"
             "              makes them: behind every -t -A line the decoys per query, how many of them have a hit whose span\n"
             "              meets the feature (NullHits), how many of those reach the line's minimum interaction energy or below\n"
@@ -253,6 +261,14 @@ void usage() {
             "              the null columns of a kept line are those of the run without -N (1 <= INT <= 1024; with -F, -u, -j,\n"
             "              -L, -Z and the search options; not with what -A can't be combined with, nor with WORLD_SIZE > 1;\n"
             "              the output does not depend on PRB_BATCH, PRB_DEVICES or PRB_SPLIT)\n"
+            "    -B INT    with -t -A: the -t -A lines of only the INT queries of lowest minimum interaction energy per feature\n"
+            "              over all the queries, written at the end of the run by feature, then rank (ties by the query's place\n"
+            "              in the input file).  The features are numbered in the order of the annotation file's lines; a line\n"
+            "              whose target name several database sequences carry is one feature of each, in database order.  A\n"
+            "              feature that no query touches writes nothing (1 <= INT <= 1024; with -u, -j, -L and the search\n"
+            "              options; -s has no effect; not with -F, -N, nor with what -A can't be combined with; with one process\n"
+            "              per GPU, WORLD_SIZE > 1, it is not implemented; the output does not depend on PRB_BATCH,\n"
+            "              PRB_DEVICES or PRB_SPLIT)\n"
             "\n"
             "  Environment: PRB_DEVICES=0,1,..  GPUs (workers) of this process;  PRB_BATCH=N  queries per batch [default 2048];\n"
             "               PRB_SPLIT=auto|queries|pages  what the workers share out: whole batches of queries, or the pages of\n"
@@ -277,9 +293,10 @@ thread_local bool t_team_thread = false;
 // `-t -n` the N best pairs per query, `-q` a line per covered query position, `-k` the N best hits per query, `-r` the
 // N best pairs per target, `-c` the regions of each target that enough queries cover, `-t -G` a line per query-group pair,
 // `-t -G -P` the same with the group's null columns, `-k -E` the `-k` lines with each hit's score, `-t -G -R` the N best
-// query-group pairs per group, `-t -A` a line per query-feature pair, `-t -A -F` the same with the feature's null columns
+// query-group pairs per group, `-t -A` a line per query-feature pair, `-t -A -F` the same with the feature's null columns,
+// `-t -A -B` the N best query-feature pairs per feature
 // (`-N K` chooses no mode of its own: kFeatures and kFeatureNull then finish their table with each query's K best records).
-enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures, kFeatureNull };
+enum class OutputMode { kHits, kSummary, kTop, kProfile, kTopHits, kTargets, kCoverage, kNull, kGroups, kGroupNull, kScored, kGroupRank, kFeatures, kFeatureNull, kFeatureRank };
 // -z, -P, -E, -F: a batch is searched with its decoys behind it, into tables that the mode's own function makes and finishes
 // (search_null_batch, search_gnull_batch, search_scored_batch, search_fnull_batch) - and by one worker: there is no merge of two of them
 constexpr bool runs_decoys(OutputMode m) {
@@ -290,7 +307,7 @@ constexpr bool runs_decoys(OutputMode m) {
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kFB, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -323,6 +340,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
      bit(kN) | bit(kQ) | bit(kK) | bit(kB) | bit(kR) | bit(kC) | bit(kZ) | bit(kG) | bit(kP) | bit(kE) | bit(kGR), kA, true},
     // (what -A can't be combined with, and one process per GPU, are refused through -A's row, in its words)
     {'N', "the N best features per query", 0, kA, false},
+    // (likewise)
+    {'B', "the N best queries per feature", bit(kF) | bit(kFN), kA, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -337,6 +356,7 @@ struct Args {
   int top = 0, tophits = 0, targets = 0, depth = 0; // the values of -n, -k, -r and -c (-1: not a count)
   int grouprank = 0;                                // -R, likewise
   int feattop = 0;                                  // -N, likewise
+  int featrank = 0;                                 // -B, likewise
   int decoys = 0;                                   // -z, -P, -E or -F, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
@@ -352,7 +372,8 @@ struct Worker {
   prb_covset *coverage = nullptr;                     // -c: this worker's table, for the whole run
   prb_grouprank *grouprank = nullptr;                 // -R: this worker's table, for the whole run
   prb_annot *annot = nullptr;                         // -A: the annotation on this worker's device, for the whole run
-  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c, -R: (input position, unmasked length) of the queries it prepared
+  prb_featrank *featrank = nullptr;                   // -B: this worker's table, for the whole run
+  std::vector<std::pair<int32_t, int32_t>> target_qlen; // -r, -c, -R, -B: (input position, unmasked length) of the queries it prepared
 };
 
 // The one place where what a search returned is freed.
@@ -385,7 +406,7 @@ struct BatchResult {
   Handle<prb_nullset> null;                    // kNull
   Handle<prb_groupset> groups;                 // kGroups; kGroupRank: until it is merged into the worker's table
   Handle<prb_gnullset> gnull;                  // kGroupNull
-  Handle<prb_featset> features;                // kFeatures
+  Handle<prb_featset> features;                // kFeatures; kFeatureRank: until it is merged into the worker's table
   Handle<prb_fnullset> fnull;                  // kFeatureNull
   std::vector<prb_eval_score> scores;          // kScored: of the records of `tophits`, in their order
 };
@@ -721,8 +742,8 @@ void check_switches(const Args &a) {
     // (-Z goes with either switch that makes decoys)
     if (const int need = kSwitchTable[s].needs; need >= 0 && !a.given[need] && !(s == kZSeed && (a.given[kP] || a.given[kE] || a.given[kF]))) die("Error: " + described(s) + " needs " + described(need));
   }
-  for (Switch s : {kR, kK, kN, kGR, kFN})
-    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : s == kFN ? a.feattop : a.top; a.given[s] && (v < 1 || v > 1024))
+  for (Switch s : {kR, kK, kN, kGR, kFN, kFB})
+    if (const int v = s == kR ? a.targets : s == kK ? a.tophits : s == kGR ? a.grouprank : s == kFN ? a.feattop : s == kFB ? a.featrank : a.top; a.given[s] && (v < 1 || v > 1024))
       die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and 1024 (this build's limit)");
   if (a.given[kC] && (a.depth < 1 || a.depth > 1000000)) die("Error: -c needs an integer between 1 and 1000000 (this build's limit)");
   if (a.given[kZ] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -z needs an integer between 1 and 100000 (this build's limit)");
@@ -737,6 +758,7 @@ OutputMode output_mode(const Args &a) {
   if (a.given[kZ]) return OutputMode::kNull;
   if (a.given[kP]) return OutputMode::kGroupNull;
   if (a.given[kGR]) return OutputMode::kGroupRank;
+  if (a.given[kFB]) return OutputMode::kFeatureRank;
   if (a.given[kF]) return OutputMode::kFeatureNull;
   if (a.given[kA]) return OutputMode::kFeatures;
   if (a.given[kG]) return OutputMode::kGroups;
@@ -748,7 +770,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:B:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -780,6 +802,7 @@ Args parse_args(int argc, char **argv) {
     case 'F': a.given[kF] = true, a.decoys = parse_count(optarg); break;
     case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
     case 'N': a.given[kFN] = true, a.feattop = parse_count(optarg); break;
+    case 'B': a.given[kFB] = true, a.featrank = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -965,6 +988,7 @@ void load_features(Run &r) {
       an.names.push_back(f[3]);
     }
   }
+  if (r.a.given[kFB] && an.names.empty()) die("Error: annotation file " + r.a.annotfile + " has no feature: " + described(kFB) + " needs one");
 }
 
 // -L: the mask of a prepared batch's queries (input positions `ids`)
@@ -1057,12 +1081,16 @@ void open_workers(Run &r, const std::vector<int> &devices) {
     if (prb_db_open(w.ctx, r.a.db.c_str(), &w.db)) die(prb_last_error());
     if (r.a.mode == OutputMode::kTargets && prb_targetset_create(w.ctx, w.db, r.a.targets, &w.targets)) die(prb_last_error());
     if (r.a.mode == OutputMode::kCoverage && prb_covset_create(w.ctx, w.db, &w.coverage)) die(prb_last_error());
-    if ((r.a.mode == OutputMode::kFeatures || r.a.mode == OutputMode::kFeatureNull) &&
+    if ((r.a.mode == OutputMode::kFeatures || r.a.mode == OutputMode::kFeatureNull || r.a.mode == OutputMode::kFeatureRank) &&
         prb_annot_create(w.ctx, w.db, (int64_t)r.annot.page.size(), r.annot.page.data(), r.annot.db_id.data(), r.annot.start.data(),
                          r.annot.end.data(), &w.annot))
       die(std::string("Error: ") + prb_last_error());
     if (r.a.mode == OutputMode::kGroupRank && prb_grouprank_create(w.ctx, (int32_t)r.groups.names.size(), r.a.grouprank, &w.grouprank))
       die(prb_last_error());
+    if (r.a.mode == OutputMode::kFeatureRank) {
+      if (const int rc = prb_featrank_create(w.ctx, w.annot, r.a.featrank, &w.featrank))
+        die(rc == PRB_ERR_NOMEM ? std::string("Error: ") + prb_last_error() + "; lower -B" : std::string(prb_last_error()));
+    }
   }
 }
 
@@ -1139,6 +1167,7 @@ std::string header_text(const Run &r) {
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Group, Members, Group Size, "
                     "Group Hits\n";
   case OutputMode::kFeatures:
+  case OutputMode::kFeatureRank:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Feature, Feature Range, "
                     "Inside\n";
@@ -1282,7 +1311,8 @@ void create_table(const Run &r, Worker &w, prb_qbatch *qb, BatchResult &res) {
     res.tophits.reset(t);
     break;
   }
-  case OutputMode::kFeatures: {
+  case OutputMode::kFeatures:
+  case OutputMode::kFeatureRank: { // (-B: the batch's feature table, merged into the worker's)
     prb_featset *t = nullptr;
     rc = prb_featset_create(w.ctx, qb, w.annot, &t);
     res.features.reset(t);
@@ -1307,7 +1337,8 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   case OutputMode::kTop: rc = kTopOps.search(w.ctx, qb, w.db, page, &o, mine.top.get()); break;
   case OutputMode::kProfile: rc = kProfOps.search(w.ctx, qb, w.db, page, &o, mine.prof.get()); break;
   case OutputMode::kTopHits: rc = kTopHitsOps.search(w.ctx, qb, w.db, page, &o, mine.tophits.get()); break;
-  case OutputMode::kFeatures: rc = prb_search_page_features(w.ctx, qb, w.db, page, &o, mine.features.get()); break;
+  case OutputMode::kFeatures:
+  case OutputMode::kFeatureRank: rc = prb_search_page_features(w.ctx, qb, w.db, page, &o, mine.features.get()); break;
   case OutputMode::kGroups:
   case OutputMode::kGroupRank: rc = prb_search_page_groups(w.ctx, qb, w.db, page, &o, mine.groups.get()); break;
   case OutputMode::kSummary: {
@@ -1327,8 +1358,8 @@ void search_one_page(const Run &r, Worker &w, const Prepared &p, int page, Batch
   if (rc) die(prb_last_error());
 }
 
-// the table of `mine` - with the tables of `others` merged into it first - to the host: one copy of its records; -R: into
-// the worker's table of the run under the input positions of the batch `p`, on the device, and dropped
+// the table of `mine` - with the tables of `others` merged into it first - to the host: one copy of its records; -R, -B:
+// into the worker's table of the run under the input positions of the batch `p`, on the device, and dropped
 void finish_table(const Run &r, Worker &w, const Prepared &p, BatchResult &mine, const std::vector<BatchResult *> &others = {}) {
   auto run = [&](auto ops, auto member) {
     for (BatchResult *o : others)
@@ -1356,6 +1387,12 @@ void finish_table(const Run &r, Worker &w, const Prepared &p, BatchResult &mine,
     if (prb_grouprank_add_groupset(w.ctx, w.grouprank, mine.groups.get(), p.ids.data())) die(prb_last_error());
     mine.groups.reset();
     break;
+  case OutputMode::kFeatureRank: // (every identifier is merged once: only the batch's whole feature table is ranked)
+    for (BatchResult *o : others)
+      if (prb_featset_merge(w.ctx, mine.features.get(), o->features.get())) die(prb_last_error());
+    if (prb_featrank_add_featset(w.ctx, w.featrank, mine.features.get(), p.ids.data())) die(prb_last_error());
+    mine.features.reset();
+    break;
   default: break; // (no table of the batch's own to finish: create_table)
   }
 }
@@ -1369,9 +1406,11 @@ BatchResult empty_result(const Run &r) {
   return res;
 }
 
-// -r, -c, -R: the lines are written at the end of the run, with every query's unmasked length by its place in the input
+// -r, -c, -R, -B: the lines are written at the end of the run, with every query's unmasked length by its place in the input
 void note_target_queries(const Run &r, Worker &w, const Prepared &p) {
-  if (r.a.mode != OutputMode::kTargets && r.a.mode != OutputMode::kCoverage && r.a.mode != OutputMode::kGroupRank) return;
+  if (r.a.mode != OutputMode::kTargets && r.a.mode != OutputMode::kCoverage && r.a.mode != OutputMode::kGroupRank &&
+      r.a.mode != OutputMode::kFeatureRank)
+    return;
   for (size_t q = 0; q < p.ids.size(); q++) w.target_qlen.emplace_back(p.ids[q], p.qlen_unmasked[q]);
 }
 
@@ -1817,6 +1856,7 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
   }
   case OutputMode::kTargets:
   case OutputMode::kGroupRank:
+  case OutputMode::kFeatureRank:
   case OutputMode::kCoverage: return id; // (nothing but progress: the table is written at the end of the run, close_run)
   case OutputMode::kSummary: {
     prb::SummaryView v;
@@ -2259,9 +2299,39 @@ void write_grouprank(Run &r) {
   written_or_die(prb::format_grouprank_batch(v, r.tabs, 0, sink, prb::format_threads()));
 }
 
+// -B: the first worker merges the others' tables into its own on the device and finishes it; the lines by feature and
+// rank, numbered from 0
+void write_featrank(Run &r) {
+  Worker &w0 = r.workers[0];
+  std::vector<int32_t> qlen(r.seqs.size(), 0);
+  for (Worker &w : r.workers) {
+    for (const auto &[id, len] : w.target_qlen) qlen[(size_t)id] = len;
+    if (&w != &w0 && prb_featrank_merge(w0.ctx, w0.featrank, w.featrank)) die(prb_last_error());
+  }
+  if (prb_featrank_finish(w0.ctx, w0.featrank)) die(prb_last_error());
+  prb::FeatRankView v;
+  v.nq = r.names.size();
+  v.names = r.names.data();
+  v.qlen_unmasked = qlen.data();
+  v.r = prb_featrank_records(w0.featrank);
+  v.n = prb_featrank_size(w0.featrank);
+  std::vector<const char *> fnames;
+  for (const std::string &f : r.annot.names) fnames.push_back(f.c_str());
+  v.feat_names = fnames.data();
+  v.feat_start = r.annot.start.data();
+  v.feat_end = r.annot.end.data();
+  for (int64_t i = 0; i < v.n; i++)
+    if (!in_range(r, v.nq, v.r[i].f.s, v.r[i].f.page) || v.r[i].f.feature < 0 || (size_t)v.r[i].f.feature >= r.annot.names.size())
+      die("Error: bad record in the table of the best queries per feature");
+  LineSink sink;
+  sink.fd = fileno(r.out);
+  written_or_die(prb::format_featrank_batch(v, r.tabs, 0, sink, prb::format_threads()));
+}
+
 void close_run(Run &r, int64_t total_hits) {
   if (r.a.mode == OutputMode::kTargets && r.rank == 0) write_targets(r);
   if (r.a.mode == OutputMode::kGroupRank && r.rank == 0) write_grouprank(r);
+  if (r.a.mode == OutputMode::kFeatureRank && r.rank == 0) write_featrank(r);
   if (r.a.mode == OutputMode::kCoverage && r.rank == 0) write_regions(r);
   if (r.a.binary()) {
     put<int64_t>(r.out, kEnd);
@@ -2273,6 +2343,7 @@ void close_run(Run &r, int64_t total_hits) {
     prb_targetset_free(w.targets);
     prb_covset_free(w.coverage);
     prb_grouprank_free(w.grouprank);
+    prb_featrank_free(w.featrank);
     prb_annot_free(w.annot);
     prb_db_close(w.db);
     if (w.prep_ctx) prb_ctx_destroy(w.prep_ctx);
