@@ -48,6 +48,7 @@ typedef struct prb_db prb_db;         /* database pages resident in HBM */
 typedef struct prb_qbatch prb_qbatch; /* a batch of queries: enc + SA + accessibilities */
 typedef struct prb_hitset prb_hitset; /* result of prb_search_page, host side */
 typedef struct prb_pairmask prb_pairmask; /* the (query, target) pairs a search is restricted to, see below */
+typedef struct prb_nullset prb_nullset;   /* the null table of `ris -t -z N`, see below (prb_pairmask_create_live takes one) */
 
 /* `ris` options, defaults of rna_interaction_search_parameters.hpp:54-62 */
 typedef struct prb_ris_opts {
@@ -136,15 +137,31 @@ static_assert(sizeof(prb_ris_opts) == 64, "prb_ris_opts: eleven fields, allowed_
  *                         before the first search that uses the mask (afterwards PRB_ERR_STATE); an index out of range is
  *                         PRB_ERR_ARG with the entry named, and nothing of the call is applied
  *   prb_pairmask_count    the allowed pairs (-1 for NULL)
+ *   prb_pairmask_row_words   the 32-bit words of a row, (targets + 31) / 32 (-1 for NULL)
+ *   prb_pairmask_words    out[0, n) = the first n words of the mask, row by row, as a search reads them - from the device
+ *                         once the mask is used; bit (t & 31) of word t >> 5 of row q = the pair (q, target t).  For tests
+ *   prb_pairmask_create_live   the mask of a batch dqb of ndq decoys from the LIVE pairs of a null table (prb_nullset, below):
+ *                         row k holds, for every target, whether the pair (owner[k], target) of the table still takes decoys.
+ *                         It is built on the device from the table's live bytes - a wavefront per 64 targets of an owner's
+ *                         row, one coalesced byte per lane, the ballot stored as two 32-bit words, an owner's words written
+ *                         to all of its rows; bits at or beyond the number of targets are 0 - and no bit ever exists on the
+ *                         host.  The mask is born used: prb_pairmask_allow on it is PRB_ERR_STATE.  prb_pairmask_count is
+ *                         the popcount of the device words, reduced on the device.  It shows the live pairs as they are at
+ *                         the call: a later prb_nullset_retire does not change it.  PRB_ERR_ARG for an owner outside the
+ *                         table's batch or ndq != the queries of dqb; PRB_ERR_STATE for a table that is finished or broken
  * A mask belongs to the batch and the database it was made for and must be freed before either: a search tells them by
  * their handles (and the batch's size and the database's page count), so a mask that outlives its batch may be taken
  * for the mask of a later batch of equal size at the same address.  Searches of several threads (contexts) may share a
  * mask - its first use is guarded -, prb_pairmask_allow may not run beside a search or another prb_pairmask_allow.
  * Stage timer "allow": the bit test and the compaction of the one-pass form's pairs (launches = 3 per chunk: test,
- * scan, scatter), for the chunks that are not issued ahead. */
+ * scan, scatter), for the chunks that are not issued ahead; and prb_pairmask_create_live's kernel (launches = 1). */
 int prb_pairmask_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, prb_pairmask **out);
 int prb_pairmask_allow(prb_pairmask *pm, int64_t n, const int32_t *query, const int32_t *page, const int32_t *db_id);
 int64_t prb_pairmask_count(const prb_pairmask *pm);
+int64_t prb_pairmask_row_words(const prb_pairmask *pm);
+int prb_pairmask_words(const prb_pairmask *pm, uint32_t *out, int64_t n);
+int prb_pairmask_create_live(prb_ctx *ctx, prb_nullset *ns, const prb_qbatch *dqb, const int32_t *owner, int32_t ndq,
+                             prb_pairmask **out);
 void prb_pairmask_free(prb_pairmask *pm);
 
 typedef struct prb_hit {
@@ -678,15 +695,17 @@ void prb_covset_free(prb_covset *cs);
  *              (-0.0 == +0.0); a decoy without a hit counts as +infinity, that is, nowhere
  *   null_min   the smallest decoy e_min against the target (of -0.0 and +0.0 the latter is reported); +infinity when
  *              null_hits == 0.  An integer atomic minimum over the order-preserving 64-bit key of the energy
- *   decoys     N; the p-value is p = (null_le + 1) / (N + 1), computed in double on the host (prb_write_null_lines)
+ *   decoys     per pair: the decoys the pair has seen - N, or, for a pair that prb_nullset_retire retired, the `upto` of that
+ *              call; null_hits, null_le and null_min are taken over the decoys 0 .. decoys - 1 only.  The p-value is
+ *              p = (null_le + 1) / (decoys + 1), computed in double on the host (prb_write_null_lines)
  * Decoy pairs whose (owner, target) is not observed are counted nowhere.  Records come by query, then page, then db_id: an
  * order of this mode's own, not the `-t` order.  Every column is an integer sum or a minimum over a total order, so the
  * table is - bit for bit - independent of how the decoys are cut into batches and sub-batches, of the order of the pages
  * and of the decoy batches, of PRB_SEARCH_PAIRS, PRB_GAPPED_CHUNK_HITS and page residency, and of whether the decoys were
  * searched under a pair mask that allows (at least) the observed targets of their owners.
  *   prb_nullset_create        an empty table for qb and db, 1 <= ndecoys <= 100000 (else PRB_ERR_ARG): one dense slot per
- *                             (query, target of every page) of 96 B - the 64 B record, three 8 B counters, a flag - and
- *                             1 B of selection flag, in HBM; PRB_ERR_NOMEM when that cannot be allocated, PRB_ERR_ARG for
+ *                             (query, target of every page) of 96 B - the 64 B record, three 8 B counters, a flag, the
+ *                             decoys seen - and 2 B of selection and live flags, in HBM; PRB_ERR_NOMEM when that cannot be allocated, PRB_ERR_ARG for
  *                             2^32 slots or more.  The table owns all its device memory and must be freed before its
  *                             context, its batch and its database
  *   prb_search_page_observed  the search of prb_search_page_summary of the real batch against `page`, its records
@@ -704,8 +723,21 @@ void prb_covset_free(prb_covset *cs);
  *                             and decoy[nq]); n = 0 only marks the decoys as merged.  Both take the refusals of the two
  *                             search entries but for the options, and refuse (PRB_ERR_ARG) a record whose query or db_id is
  *                             out of range, whose hits are below 1, or whose (query, db_id) comes twice in the list
+ *   prb_nullset_retire        sequential Monte-Carlo p-values (Besag & Clifford 1991; `ris -t -z N -H H`): between two batches
+ *                             of decoys, one pass over the slots retires every live pair - an observed pair that has not
+ *                             retired - with null_le >= min_le: it takes no further decoy (a record that arrives for it is
+ *                             counted nowhere), and its `decoys` is `upto`, the number of decoys per query merged so far.  A
+ *                             pair retired earlier keeps its `decoys`.  live_per_query[nq] (may be NULL) = the live pairs
+ *                             left per query, counted on the device per wavefront (ballot, popcount, one atomic add per
+ *                             wavefront and query).  Checked on the host before anything is enqueued: min_le >= 1; upto is
+ *                             above that of the call before and at most ndecoys (PRB_ERR_ARG); every page is observed, and
+ *                             every (query, decoy < upto, page) of every query that had live pairs before the call is merged
+ *                             (PRB_ERR_STATE).  The caller decides what `upto` means by what it merges first: the result is
+ *                             that of the plain table with `upto` decoys, for the pairs that retire here
  *   prb_nullset_finish        PRB_ERR_STATE unless every (query, decoy, page) has been merged - a p-value never rests on
- *                             fewer decoys than it says.  The observed slots are selected on the device, their records
+ *                             fewer decoys than it says; with retired pairs, only the queries that still have live pairs
+ *                             need all N decoys: for a query without, the decoys from the `upto` on of the
+ *                             prb_nullset_retire that found it so are exempt.  The observed slots are selected on the device, their records
  *                             gathered there and copied to the host in one copy; the device memory is released.  Nothing
  *                             can be merged after it (a second call does nothing)
  *   prb_nullset_counts        the stage counts of prb_pairset_counts, summed over the observed pages;
@@ -717,17 +749,16 @@ void prb_covset_free(prb_covset *cs);
  * A table holds pages searched with one value of distinct_sites and of chain_sites (a second one is PRB_ERR_ARG).  There is
  * no prb_nullset_merge: a batch belongs to one worker.  Stage timer "null": the scatter or the fold (launches = 1 per
  * sub-batch with final hits, and per prb_nullset_observe / _add_pairs with records), and prb_nullset_finish: the selection
- * and the gather (launches = 2, or 1 when no pair is observed). */
+ * and the gather (launches = 2, or 1 when no pair is observed); prb_nullset_retire: its pass (launches = 1). */
 typedef struct prb_null_pair {
   prb_pair_summary s;   /* the observed pair */
-  int32_t page, decoys; /* the target's page; N */
+  int32_t page, decoys; /* the target's page; the decoys this pair has seen (N unless it retired) */
   int64_t null_hits, null_le;
   double null_min;
 } prb_null_pair;
 #ifdef __cplusplus
 static_assert(sizeof(prb_null_pair) == 96, "prb_null_pair: no padding");
 #endif
-typedef struct prb_nullset prb_nullset;
 int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int32_t ndecoys, prb_nullset **out);
 int prb_search_page_observed(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, prb_nullset *ns);
 int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t page, const prb_ris_opts *opts, const int32_t *owner,
@@ -735,6 +766,7 @@ int prb_search_page_decoys(prb_ctx *ctx, prb_qbatch *dqb, prb_db *db, int32_t pa
 int prb_nullset_observe(prb_ctx *ctx, prb_nullset *ns, int32_t page, const prb_pair_summary *pairs, int64_t n);
 int prb_nullset_add_pairs(prb_ctx *ctx, prb_nullset *ns, int32_t page, const int32_t *owner, const int32_t *decoy, int32_t nq,
                           const prb_pair_summary *pairs, int64_t n);
+int prb_nullset_retire(prb_ctx *ctx, prb_nullset *ns, int64_t min_le, int32_t upto, int64_t *live_per_query);
 int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns);
 int64_t prb_nullset_size(const prb_nullset *ns);
 const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns);

@@ -156,6 +156,9 @@ SYMBOLS = {
     "prb_pairmask_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p)]),
     "prb_pairmask_allow": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "prb_pairmask_count": (c_i64, [ctypes.c_void_p]),
+    "prb_pairmask_row_words": (c_i64, [ctypes.c_void_p]),
+    "prb_pairmask_words": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64]),
+    "prb_pairmask_create_live": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(ctypes.c_void_p)]),
     "prb_pairmask_free": (None, [ctypes.c_void_p]),
     "prb_hitset_size": (c_i64, [ctypes.c_void_p]),
     "prb_hitset_hits": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -224,6 +227,7 @@ SYMBOLS = {
     "prb_nullset_observe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64]),
     "prb_nullset_add_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, ctypes.c_void_p, c_i32,
                                              ctypes.c_void_p, c_i64]),
+    "prb_nullset_retire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i32, ctypes.c_void_p]),
     "prb_nullset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "prb_nullset_size": (c_i64, [ctypes.c_void_p]),
     "prb_nullset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -568,6 +572,18 @@ class PairMask:
         _check(lib().prb_pairmask_create(ctx.h, qb.h, db.h, ctypes.byref(h)))
         self.h = h
 
+    @classmethod
+    def live(cls, ctx, ns, dqb, owner):
+        """prb_pairmask_create_live: the mask of the decoy batch dqb from the live pairs of the NullSet ns, made on the
+        device; row k = the live pairs of query owner[k]"""
+        owner = np.ascontiguousarray(owner, np.int32)
+        self = cls.__new__(cls)
+        self.h = None
+        h = ctypes.c_void_p()
+        _check(lib().prb_pairmask_create_live(ctx.h, ns.h, dqb.h, owner.ctypes.data if len(owner) else None, len(owner), ctypes.byref(h)))
+        self.h = h
+        return self
+
     def allow(self, query, page, db_id):
         """arrays of equal length; query -1 = every query of the batch"""
         q, p, d = (np.ascontiguousarray(np.atleast_1d(x), np.int32) for x in (query, page, db_id))
@@ -578,6 +594,13 @@ class PairMask:
     @property
     def count(self):
         return lib().prb_pairmask_count(self.h)
+
+    def words(self, nrows):
+        """prb_pairmask_words -> uint32 [nrows, row_words]: the rows as a search reads them"""
+        rw = lib().prb_pairmask_row_words(self.h)
+        out = np.zeros((nrows, rw), np.uint32)
+        _check(lib().prb_pairmask_words(self.h, out.ctypes.data if out.size else None, out.size))
+        return out
 
     def close(self):
         if self.h:
@@ -945,6 +968,13 @@ class NullSet(_Table):
         _check(lib().prb_nullset_add_pairs(self.ctx.h, self.h, page, owner.ctypes.data if len(owner) else None,
                                            decoy.ctypes.data if len(owner) else None, len(owner),
                                            pairs.ctypes.data if len(pairs) else None, len(pairs)))
+
+    def retire(self, min_le, upto):
+        """prb_nullset_retire: the live pairs with null_le >= min_le retire with decoys = upto -> the live pairs left per
+        query (int64 array)"""
+        left = np.zeros(len(self.qb.lens), np.int64)
+        _check(lib().prb_nullset_retire(self.ctx.h, self.h, min_le, upto, left.ctypes.data if len(left) else None))
+        return left
 
     def finish(self):
         """prb_nullset_finish -> structured array NULL_DTYPE (a copy), by query, then page, then db_id"""
@@ -1458,6 +1488,51 @@ def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask
         counts = tuple(int(x) for x in counts) if mask else ns.counts()
         dcounts = ns.decoy_counts()
     return (recs, counts, dcounts) if with_counts else recs
+
+
+def search_seqnull(ctx, qb, seqs, db, ndecoys, min_le, per_round, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None,
+                   with_counts=False):
+    """The null table of search_null with sequential p-values (`ris -t -z ndecoys -H min_le -D per_round`): the decoys in
+    rounds of per_round, each round for the queries that still have live pairs and - with mask - under the mask of the live
+    pairs made on the device; at every round's end the pairs with null_le >= min_le retire.  -> NULL_DTYPE records, whose
+    `decoys` is per pair.  with_counts: -> (records, counts of the real batch, counts of the decoys, [(boundary, live pairs
+    per query)])."""
+    o = opts or default_opts()
+    rounds = []
+    with NullSet(ctx, qb, db, ndecoys) as ns:
+        for p in range(db.npages):
+            ns.observed(p, o)
+        od = RisOpts.from_buffer_copy(o)
+        queries = list(range(len(seqs)))
+        for lo in range(0, ndecoys, per_round):
+            if not queries:
+                break
+            hi = min(ndecoys, lo + per_round)
+            todo = [(q, d) for q in queries for d in range(lo, hi)]
+            step = decoy_batch or len(todo)
+            for i0 in range(0, len(todo), step):
+                part = todo[i0:i0 + step]
+                own, dec = np.array([q for q, _ in part], np.int32), np.array([d for _, d in part], np.int32)
+                dqb = QBatch(ctx, [shuffle_sequence(seqs[q], seed, file_pos0 + q, d) for q, d in part], db.repeat_flag)
+                pm = None
+                try:
+                    dqb.accessibility(db.W, db.delta)
+                    od.allowed_pairs = None
+                    if mask:
+                        pm = PairMask.live(ctx, ns, dqb, own)
+                        od.allowed_pairs = pm.h.value
+                    for p in range(db.npages):
+                        ns.decoys(dqb, p, own, dec, od)
+                finally:
+                    if pm is not None:
+                        pm.close()
+                    dqb.close()
+            left = ns.retire(min_le, hi)
+            rounds.append((hi, left))
+            queries = [q for q in queries if left[q] > 0]
+        recs = ns.finish()
+        counts, dcounts = ns.counts(), ns.decoy_counts()
+    return (recs, counts, dcounts, rounds) if with_counts else recs
 
 
 class Comm:

@@ -1,5 +1,5 @@
 // C ABI, part 10: the null table of one batch - per observed (query, target) pair, how the query's decoys fare against
-// the same target (prb_nullset_*, `ris -t -z N`).  The kernels are in null_kernels.hip.  Every check of a call is made on
+// the same target (prb_nullset_*, `ris -t -z N [-H H]`).  The kernels are in null_kernels.hip.  Every check of a call is made on
 // the host before anything is enqueued: a refused call leaves the table as it was.
 #include "capi_tables.hpp"
 
@@ -81,6 +81,8 @@ int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int
     ns->nq = qb->nq;
     ns->ndecoys = ndecoys;
     ns->merged.assign((size_t)((ns->triples() + 63) / 64), 0);
+    ns->live_q.assign((size_t)ns->nq, -1);
+    ns->needs.assign((size_t)ns->nq, ndecoys);
   } catch (const std::exception &e) {
     return refuse(fn, e.what(), PRB_ERR_NOMEM);
   }
@@ -92,8 +94,9 @@ int prb_nullset_create(prb_ctx *ctx, const prb_qbatch *qb, const prb_db *db, int
   PRB_HIP(hipSetDevice(ctx->device));
   const size_t S = (size_t)ns->slots();
   if (ns->table.ensure(std::max<size_t>(S * sizeof(NullSlot), 16)) != PRB_OK || ns->obs.ensure(std::max<size_t>(S, 16)) != PRB_OK ||
+      ns->live.ensure(std::max<size_t>(S, 16)) != PRB_OK || ns->live_dev.ensure(std::max<size_t>((size_t)ns->nq * 8, 16)) != PRB_OK ||
       ns->badflag.ensure(16) != PRB_OK || ns->tbase_dev.ensure(ns->tbase.size() * 8) != PRB_OK)
-    return refuse(fn, "can't allocate the null table (" + std::to_string((S * (sizeof(NullSlot) + 1)) >> 20) + " MB of HBM for " + std::to_string(ns->nq) +
+    return refuse(fn, "can't allocate the null table (" + std::to_string((S * (sizeof(NullSlot) + 2)) >> 20) + " MB of HBM for " + std::to_string(ns->nq) +
                           " queries x " + std::to_string(ns->targets()) + " targets)",
                   PRB_ERR_NOMEM);
   PRB_HIP(hipMemsetAsync(ns->badflag.p, 0, 16, ctx->stream));
@@ -185,9 +188,19 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
   if (int rc = finish_guard(fn, "null", ctx, ns)) return rc;
   if (ns->finished) return PRB_OK; // (the records are on the host already)
   if (ns->bad) return refuse(fn, "a record merged into this null table named a query, a sequence, an owner or a decoy outside it", PRB_ERR_STATE);
-  if (ns->nmerged != ns->triples())
-    return refuse(fn, std::to_string(ns->nmerged) + " of " + std::to_string(ns->triples()) + " (query, decoy, page) searches are merged: every decoy of every query against every page comes first",
-                  PRB_ERR_STATE);
+  if (!ns->retired_upto) {
+    if (ns->nmerged != ns->triples())
+      return refuse(fn, std::to_string(ns->nmerged) + " of " + std::to_string(ns->triples()) + " (query, decoy, page) searches are merged: every decoy of every query against every page comes first",
+                    PRB_ERR_STATE);
+  } else { // (retired pairs: a query without live pairs needs no decoy from the boundary on that found it so)
+    int64_t need = 0, have = 0;
+    for (int32_t q = 0; q < ns->nq; q++)
+      for (int32_t page = 0; page < ns->npages; page++)
+        for (int32_t d = 0; d < ns->needs[(size_t)q]; d++) need++, have += ns->merged_bit(page, q, d);
+    if (have != need)
+      return refuse(fn, std::to_string(have) + " of " + std::to_string(need) + " (query, decoy, page) searches are merged: every decoy of every query that has live pairs against every page comes first",
+                    PRB_ERR_STATE);
+  }
   ns->pairs.clear();
   PRB_HIP(hipSetDevice(ctx->device));
   const int64_t S = ns->slots();
@@ -220,6 +233,53 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
   }
   ns->finished = true;
   ns->release(); // (only the host records are needed from here on)
+  return PRB_OK;
+}
+
+// One pass over the slots (k_null_retire), the live slots left per query counted there and copied to the host
+int prb_nullset_retire(prb_ctx *ctx, prb_nullset *ns, int64_t min_le, int32_t upto, int64_t *live_per_query) {
+  const char *fn = "prb_nullset_retire";
+  if (int rc = null_guard(fn, ctx, ns, 0)) return rc;
+  if (upto <= ns->retired_upto || upto > ns->ndecoys)
+    return refuse(fn, "need " + std::to_string(ns->retired_upto) + " < upto <= " + std::to_string(ns->ndecoys) + " (got " + std::to_string(upto) +
+                          "): above that of the call before, and at most the table's decoys per query");
+  if (min_le < 1) return refuse(fn, "need min_le >= 1 (got " + std::to_string(min_le) + ")");
+  for (size_t p = 0; p < ns->observed.size(); p++)
+    if (!ns->observed[p]) return refuse(fn, "page " + std::to_string(p) + " is not observed yet (the real batch's search comes first)", PRB_ERR_STATE);
+  // (a query that has live pairs had them at every call before: its decoys below the last boundary were checked there)
+  for (int32_t q = 0; q < ns->nq; q++)
+    if (ns->live_q[(size_t)q])
+      for (int32_t page = 0; page < ns->npages; page++)
+        for (int32_t d = ns->retired_upto; d < upto; d++)
+          if (!ns->merged_bit(page, q, d))
+            return refuse(fn, "decoy " + std::to_string(d) + " of query " + std::to_string(q) + " is not merged for page " + std::to_string(page) +
+                                  ": every decoy below " + std::to_string(upto) + " of every query that has live pairs comes first",
+                          PRB_ERR_STATE);
+  DeviceScope restore;
+  PRB_HIP(hipSetDevice(ctx->device));
+  std::vector<int64_t> left;
+  try {
+    left.assign((size_t)ns->nq, 0);
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  if (ns->slots() > 0) {
+    ns->broken = true; // (until the pass is whole)
+    int rc;
+    if ((rc = ctx->time_begin())) return rc;
+    PRB_HIP(hipMemsetAsync(ns->live_dev.p, 0, (size_t)ns->nq * 8, ctx->stream));
+    PRB_HIP(launch_null_retire(ns->view(), (unsigned long long)min_le, (uint32_t)upto, ns->live_dev.as<unsigned long long>(), ctx->stream));
+    PRB_HIP(hipMemcpyAsync(left.data(), ns->live_dev.p, (size_t)ns->nq * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->time_end(ModeTimer::kNull, 1))) return rc; // (synchronises: the copy is over)
+    if ((rc = fetch_bad(ctx, ns))) return rc;
+    ns->broken = false;
+  }
+  for (int32_t q = 0; q < ns->nq; q++) {
+    if (ns->live_q[(size_t)q] && !left[(size_t)q]) ns->needs[(size_t)q] = upto;
+    ns->live_q[(size_t)q] = left[(size_t)q];
+    if (live_per_query) live_per_query[q] = left[(size_t)q];
+  }
+  ns->retired_upto = upto;
   return PRB_OK;
 }
 

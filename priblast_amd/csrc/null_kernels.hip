@@ -6,6 +6,11 @@
 // slot holds the observed pair's summary record and the counters; every counter is an integer sum or an integer
 // minimum, built with integer atomics only.  Every kernel checks its records against the table's ranges before it
 // writes: a record out of range raises `bad`, is counted nowhere and writes nothing (the next host call fails).
+//
+// Sequential p-values (`ris -t -z N -H H`): a byte per slot, `live`, says that the slot still takes decoys.  It is set
+// with `observed`; k_null_retire clears it for the slots whose null_le has reached the caller's bound, between two rounds
+// of decoys, and k_null_count leaves a slot that is not live alone.  k_null_live_mask turns the live bytes of a decoy
+// batch's owners into the rows of the pair mask that the next round is searched under.
 #include "../../include/priblast_hip.h"
 
 #include "launch.hpp"
@@ -49,6 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_null_observe(const prb_pair_summary 
   for (int k = 0; k < 8; k++) d[k] = v[k];
   t.slot[slot].observed = 1u;
   t.obs[slot] = 1;
+  t.live[slot] = 1;
 }
 
 // prb_search_page_decoys / prb_nullset_add_pairs: the pair records rec[0, nrec) of a batch of ndq decoys against one
@@ -70,8 +76,9 @@ __global__ __launch_bounds__(kBlock) void k_null_count(const prb_pair_summary *_
     atomicOr(t.bad, 1u);
     return;
   }
+  // (a decoy's pair that the real query does not have, or whose slot has retired, is counted nowhere)
+  if (!t.live[slot]) return;
   NullSlot &s = t.slot[slot];
-  if (!s.observed) return; // (a decoy's pair that the real query does not have is counted nowhere)
   const unsigned long long ek = energy_key(rec[i].e_min);
   atomicAdd(&s.null_hits, 1ull);
   if (ek <= energy_key(null_rec(s).e_min)) atomicAdd(&s.null_le, 1ull);
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_null_gather(NullTab t, const uint32_
   prb_null_pair r;
   r.s = null_rec(s);
   r.page = lo;
-  r.decoys = t.ndecoys;
+  r.decoys = s.seen ? (int32_t)s.seen : t.ndecoys;
   r.null_hits = (int64_t)s.null_hits;
   r.null_le = (int64_t)s.null_le;
   // the energy key back to its double (energy_key: negative values are stored inverted, the others with the top bit set)
@@ -117,6 +124,58 @@ __global__ __launch_bounds__(kBlock) void k_null_clear(NullTab t) {
   for (int k = 0; k < 12; k++) d[k] = make_uint2(0u, 0u);
   t.slot[i].null_min = 0xFFF0000000000000ull; // energy_key(+inf)
   t.obs[i] = 0;
+  t.live[i] = 0;
+}
+
+// prb_nullset_retire: a lane per slot.  A live slot whose null_le has reached min_le retires: live = 0, seen = upto (a
+// slot retired earlier is not live, so it keeps its seen).  The slots that stay live are counted per query: the lanes of
+// a wavefront that hold slots of one query are found by ballot, and their first lane adds the popcount - a wavefront's
+// 64 slots lie in as many queries' rows as ntargets lets them, so the loop runs once per query present.  No lane leaves
+// before the ballots.
+__global__ __launch_bounds__(kBlock) void k_null_retire(NullTab t, unsigned long long min_le, uint32_t upto, unsigned long long *live_q) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool in = i < t.nslots;
+  bool live = in && t.live[i];
+  if (live && t.slot[i].null_le >= min_le) {
+    t.live[i] = 0;
+    t.slot[i].seen = upto;
+    live = false;
+  }
+  const int32_t q = in ? (int32_t)(i / t.ntargets) : -1;
+  unsigned long long todo = __ballot(live);
+  while (todo) { // (wavefront-uniform)
+    const int lead = __ffsll((long long)todo) - 1;
+    const int32_t ql = __shfl(q, lead);
+    const unsigned long long same = __ballot(live && q == ql);
+    if (lane == lead) atomicAdd(&live_q[ql], (unsigned long long)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+// prb_pairmask_create_live: wavefront w of the grid takes the 64 targets [64 c, 64 c + 64) of owner r.uowner[u], u = w / C,
+// c = w % C, C = the 64-target chunks of a row.  A lane reads one live byte - a target at or beyond ntargets reads as 0 -,
+// the ballot is the 64 bits, and the lanes share out the owner's rows: the low word to word 2 c of each, the high word
+// to word 2 c + 1 where the row has one (row_words may be odd).  Every word of every row is written by one wavefront.
+__global__ __launch_bounds__(kBlock) void k_null_live_mask(NullTab t, LiveMaskRows r, uint32_t *__restrict__ bits, int64_t row_words,
+                                                           unsigned long long *count) {
+  const int64_t chunks = (t.ntargets + 63) >> 6;
+  const int64_t w = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (w >= (int64_t)r.nown * chunks) return; // (a whole wavefront)
+  const int32_t u = (int32_t)(w / chunks);
+  const int64_t c = w % chunks, target = c * 64 + lane;
+  const int32_t own = r.uowner[u];
+  const bool own_ok = own >= 0 && own < t.nq;
+  if (!own_ok && lane == 0) atomicOr(t.bad, 1u);
+  const bool bit = own_ok && target < t.ntargets && t.live[(int64_t)own * t.ntargets + target];
+  const unsigned long long m = __ballot(bit);
+  const int32_t row0 = r.rowoff[u], nrows = r.rowoff[u + 1] - row0;
+  for (int32_t x = lane; x < 2 * nrows; x += 64) {
+    const int64_t word = 2 * c + (x & 1);
+    if (word < row_words) bits[(int64_t)r.rows[row0 + (x >> 1)] * row_words + word] = (uint32_t)((x & 1) ? m >> 32 : m);
+  }
+  if (lane == 0 && m) atomicAdd(count, (unsigned long long)__popcll(m) * (unsigned long long)nrows);
 }
 
 } // namespace
@@ -128,6 +187,13 @@ hipError_t launch_null_observe(const void *rec, int64_t nrec, const NullTab &t, 
 hipError_t launch_null_count(const void *rec, int64_t nrec, const int32_t *owner, const int32_t *decoy, int32_t ndq, const NullTab &t,
                              const NullPage &pg, hipStream_t s) {
   return launch_1d(k_null_count, nrec, kBlock, 0, s, static_cast<const prb_pair_summary *>(rec), nrec, owner, decoy, ndq, t, pg);
+}
+hipError_t launch_null_retire(const NullTab &t, unsigned long long min_le, uint32_t upto, unsigned long long *live_q, hipStream_t s) {
+  return launch_1d(k_null_retire, t.nslots, kBlock, 0, s, t, min_le, upto, live_q);
+}
+hipError_t launch_null_live_mask(const NullTab &t, const LiveMaskRows &r, uint32_t *bits, int64_t row_words, unsigned long long *count,
+                                 hipStream_t s) {
+  return launch_1d(k_null_live_mask, (int64_t)r.nown * ((t.ntargets + 63) >> 6) * 64, kBlock, 0, s, t, r, bits, row_words, count);
 }
 hipError_t launch_null_gather(const NullTab &t, const uint32_t *idx, int64_t n, const int64_t *tbase, int32_t npages, void *out, hipStream_t s) {
   return launch_1d(k_null_gather, n, kBlock, 0, s, t, idx, n, tbase, npages, static_cast<prb_null_pair *>(out));

@@ -700,11 +700,17 @@ struct prb_covset : prb::RunTable, prb::SpanBufs {
 
 // prb_nullset_create .. prb_nullset_free: the null table of one batch against one database (capi_null.hip), merged into
 // sub-batch by sub-batch - the real batch's pairs page by page first (merge_null_observed), then the pairs of its decoys
-// (merge_null_decoys).  It owns all its device memory; `table` = NullSlot[nq * targets]
+// (merge_null_decoys).  Between two batches of decoys prb_nullset_retire may retire the decided pairs: a retired slot takes
+// no further decoys, and a query without live slots needs none.  It owns all its device memory; `table` = NullSlot[nq * targets]
 struct prb_nullset : prb::DecoyTable {
   std::vector<int64_t> tbase;        // [npages + 1] the first target of every page; back() = the targets
   std::vector<uint8_t> observed;     // per page: the real batch's search is merged
   prb::DevBuf obs, tbase_dev;        // the selection's flags, tbase on the device
+  prb::DevBuf live, live_dev;        // a byte per slot: it still takes decoys; prb_nullset_retire's counts per query
+  int32_t retired_upto = 0;          // `upto` of the last prb_nullset_retire (0: none yet)
+  std::vector<int64_t> live_q;       // [nq] the live slots of every query after that call (before the first: not known, -1)
+  std::vector<int32_t> needs;        // [nq] the decoys a query must have merged for prb_nullset_finish: ndecoys while it has
+                                     // live slots, else `upto` of the call that found it without
   prb::DevBuf h_rec;                 // prb_nullset_observe / _add_pairs: the caller's records
   prb::DevBuf sel, out;              // prb_nullset_finish: the observed slots, their records
   std::vector<prb_null_pair> pairs;  // prb_nullset_finish
@@ -713,12 +719,16 @@ struct prb_nullset : prb::DecoyTable {
   int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
   int64_t slots() const { return (int64_t)nq * targets(); }
   prb::NullTab view() const {
-    return prb::NullTab{table.as<prb::NullSlot>(), obs.as<uint8_t>(), badflag.as<uint32_t>(), slots(), targets(), nq, ndecoys};
+    return prb::NullTab{table.as<prb::NullSlot>(), obs.as<uint8_t>(), live.as<uint8_t>(), badflag.as<uint32_t>(), slots(), targets(), nq, ndecoys};
+  }
+  bool merged_bit(int32_t page, int32_t q, int32_t d) const {
+    const int64_t b = bit_of(bit0(page), q, d);
+    return (merged[(size_t)(b >> 6)] >> (b & 63)) & 1;
   }
   prb::NullPage page_view(size_t page) const { return prb::NullPage{tbase[page], (int32_t)(tbase[page + 1] - tbase[page])}; }
   void release() {
     if (!quiesce()) return;
-    for (prb::DevBuf *b : {&table, &obs, &badflag, &tbase_dev, &own, &h_rec, &sel, &out}) b->release();
+    for (prb::DevBuf *b : {&table, &obs, &live, &live_dev, &badflag, &tbase_dev, &own, &h_rec, &sel, &out}) b->release();
   }
   ~prb_nullset() { release(); } // (also on the error paths of prb_nullset_create)
 };

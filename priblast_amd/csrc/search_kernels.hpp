@@ -568,16 +568,19 @@ hipError_t launch_cov_regions(const CovTab &t, const int64_t *tbase, int32_t npa
 // q * ntargets + t, targets numbered page by page.  A slot: the observed pair's summary record, the number of decoys
 // with a hit against the target, the number of those whose e_min is not above the observed one, and the smallest decoy
 // e_min as its energy key (the key of +infinity: none).  obs[slot] = the slot's `observed` as the flag the selection of
-// prb_nullset_finish takes.  bad: set when a record names a query, a sequence, an owner or a decoy outside the table.
+// prb_nullset_finish takes.  live[slot]: the slot still takes decoys - set when it is observed, cleared when it retires
+// (launch_null_retire), which writes the number of decoys it has seen into `seen` (0: not retired).  bad: set when a
+// record names a query, a sequence, an owner or a decoy outside the table.
 struct NullSlot {
   uint64_t s[8];                                 // the observed pair's prb_pair_summary
   unsigned long long null_hits, null_le, null_min;
-  uint32_t observed, reserved;
+  uint32_t observed, seen;
 };
-static_assert(sizeof(NullSlot) == 96, "NullSlot: 64 B of record, three counters, the flag");
+static_assert(sizeof(NullSlot) == 96, "NullSlot: 64 B of record, three counters, the flag, the decoys seen");
 struct NullTab {
   NullSlot *slot;    // [nslots]
   uint8_t *obs;      // [nslots]
+  uint8_t *live;     // [nslots]
   uint32_t *bad;
   int64_t nslots, ntargets; // nslots = nq * ntargets
   int32_t nq, ndecoys;
@@ -592,9 +595,21 @@ hipError_t launch_null_clear(const NullTab &t, hipStream_t s);
 // into the slot of its (query, db_id), a lane per record; a (query, page) comes once
 hipError_t launch_null_observe(const void *rec, int64_t nrec, const NullTab &t, const NullPage &pg, hipStream_t s);
 // rec[0, nrec) = the records of a batch of ndq decoys against the page: record i is decoy decoy[query] of the real query
-// owner[query]; folded into the counters of the observed slots with integer atomics, a lane per record
+// owner[query]; folded into the counters of the live slots with integer atomics, a lane per record
 hipError_t launch_null_count(const void *rec, int64_t nrec, const int32_t *owner, const int32_t *decoy, int32_t ndq, const NullTab &t,
                              const NullPage &pg, hipStream_t s);
+// prb_nullset_retire: every live slot with null_le >= min_le retires with seen = upto, a lane per slot; live_q[nq] (zeroed
+// by the caller) += the slots of each query that stay live, one atomic per wavefront and query
+hipError_t launch_null_retire(const NullTab &t, unsigned long long min_le, uint32_t upto, unsigned long long *live_q, hipStream_t s);
+// prb_pairmask_create_live: the rows of a decoy batch's pair mask from the live bytes.  The batch's distinct owners are
+// uowner[nown]; owner u has the rows rows[rowoff[u], rowoff[u + 1]) of bits (row_words 32-bit words each).  A wavefront
+// per (owner, 64 consecutive targets); *count (zeroed by the caller) += the bits set
+struct LiveMaskRows {
+  const int32_t *uowner, *rowoff, *rows;
+  int32_t nown;
+};
+hipError_t launch_null_live_mask(const NullTab &t, const LiveMaskRows &r, uint32_t *bits, int64_t row_words, unsigned long long *count,
+                                 hipStream_t s);
 // prb_nullset_finish: out[j] (prb_null_pair) of the observed slot idx[j]; tbase[npages + 1] = the pages' first targets
 hipError_t launch_null_gather(const NullTab &t, const uint32_t *idx, int64_t n, const int64_t *tbase, int32_t npages, void *out, hipStream_t s);
 

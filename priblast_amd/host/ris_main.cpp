@@ -86,7 +86,13 @@
 // and only N records per feature reach the host, written by feature - in the order load_features numbers them - and rank.
 // `-B` needs -A and is refused with -F and -N; everything else is refused through -A.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N -B have one table (kSwitchTable) that every
+// `ris -t -z N -H H [-D R]` makes the p-values of -z sequential: the decoys are searched in rounds of R, and at every round's
+// end the null table retires, on the device, the pairs that H or more of their decoys have reached (prb_nullset_retire);
+// the next round's pieces are searched under a mask of the pairs still live, made on the device from the table
+// (prb_pairmask_create_live), and a query without live pairs gets no further decoys.  No record reaches the host between
+// rounds.  `-H` needs -z, `-D` needs -H.
+//
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N -B -H -D have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
@@ -203,6 +209,18 @@ void usage() {
             "              with -u, -j, -L and the search options; not with -n, -k, -q, -r, -c, -b; PRB_SPLIT has no effect;\n"
             "              PRB_NULL_MASK=0: the decoys are searched against every target, the output is the same)\n"
             "    -Z INT    with -z or -P, with -F, or with -E: the seed of the shuffles [default:1]\n"
+            "    -H INT    with -t -z N: sequential p-values (Besag & Clifford 1991).  The decoys 0 .. N - 1 of a query are searched\n"
+            "              in rounds of R (-D), and at the end of a round - after R, 2 R, ... and N decoys - a pair that INT or more\n"
+            "              of its decoys so far have reached (NullLE >= INT) retires: its p-value is large and known well enough.\n"
+            "              It takes no more decoys, and its line is the line of -t -z SEEN, SEEN the decoys it has seen: Decoys =\n"
+            "              SEEN, NullHits, NullLE and NullMin over the decoys 0 .. SEEN - 1, PValue = (NullLE + 1) / (SEEN + 1) -\n"
+            "              never below Besag & Clifford's INT / SEEN.  Only the pairs that are still candidates for a small p-value\n"
+            "              see all N decoys; a query whose pairs have all retired gets no further decoy.  The retiring and the\n"
+            "              mask of the live pairs that the next round is searched under are made on the GPU.  The lines and\n"
+            "              their order are those of -z; -H N -D N writes the bytes of -t -z N (1 <= INT <= N; not with -P, -F,\n"
+            "              -E; the output depends on N, INT, R and -Z only - not on PRB_BATCH, PRB_DEVICES, PRB_SPLIT or\n"
+            "              PRB_NULL_MASK=0, which searches every round against every target)\n"
+            "    -D INT    with -H: the decoys per round, R; the last round may be short [default:10; 1 <= INT <= N]\n"
             "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
             "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
             "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
@@ -307,7 +325,7 @@ constexpr bool runs_decoys(OutputMode m) {
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kFB, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kFB, kH, kHRound, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -342,6 +360,9 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     {'N', "the N best features per query", 0, kA, false},
     // (likewise)
     {'B', "the N best queries per feature", bit(kF) | bit(kFN), kA, false},
+    // (-P, -F and -E make decoys of their own and are refused with -z: -H is refused with them through its need of -z)
+    {'H', "sequential p-values: a pair takes no more decoys once H of them reach its minimum energy", 0, kZ, false},
+    {'D', "the decoys per round of the sequential p-values", 0, kH, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -358,6 +379,7 @@ struct Args {
   int feattop = 0;                                  // -N, likewise
   int featrank = 0;                                 // -B, likewise
   int decoys = 0;                                   // -z, -P, -E or -F, likewise
+  int retire_le = 0, round = 10;                    // -H and -D, likewise
   uint64_t shuffle_seed = 1;                        // -Z
   bool seed_ok = true;                              // -Z's value is a non-negative integer
   OutputMode mode = OutputMode::kHits;
@@ -751,6 +773,9 @@ void check_switches(const Args &a) {
   if (a.given[kE] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -E needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kF] && (a.decoys < 1 || a.decoys > 100000)) die("Error: -F needs an integer between 1 and 100000 (this build's limit)");
   if (a.given[kZSeed] && !a.seed_ok) die("Error: -Z needs a non-negative integer");
+  for (Switch s : {kH, kHRound})
+    if (const int v = s == kH ? a.retire_le : a.round; a.given[s] && (v < 1 || v > a.decoys))
+      die(std::string("Error: -") + kSwitchTable[s].letter + " needs an integer between 1 and the decoys per query (-z " + std::to_string(a.decoys) + ")");
 }
 
 OutputMode output_mode(const Args &a) {
@@ -770,7 +795,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:B:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:B:H:D:")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -803,6 +828,8 @@ Args parse_args(int argc, char **argv) {
     case 'R': a.given[kGR] = true, a.grouprank = parse_count(optarg); break;
     case 'N': a.given[kFN] = true, a.feattop = parse_count(optarg); break;
     case 'B': a.given[kFB] = true, a.featrank = parse_count(optarg); break;
+    case 'H': a.given[kH] = true, a.retire_le = parse_count(optarg); break;
+    case 'D': a.given[kHRound] = true, a.round = parse_count(optarg); break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -1426,8 +1453,11 @@ struct DecoyPiece {
 // in the input file and the decoy's number), made on host threads -, query by query and decoy by decoy, in pieces of at
 // most the batch size: each piece gets its suffix arrays and accessibilities, goes to the mode's `body` - which makes
 // the piece's mask, if it wants one, and searches the piece against every page -, and is let go of with its mask.
-template <class Body> void for_decoy_pieces(const Run &r, Worker &w, const Prepared &p, Body body) {
-  const size_t nd = (size_t)r.a.decoys, total = p.ids.size() * nd;
+// The general form takes the decoys [d_lo, d_hi) of the queries `queries` of the batch (ascending places in it) - one
+// round of `-H` for the queries that still have live pairs -, in the same order.
+template <class Body>
+void for_decoy_pieces(const Run &r, Worker &w, const Prepared &p, const std::vector<int32_t> &queries, int32_t d_lo, int32_t d_hi, Body body) {
+  const size_t nd = (size_t)(d_hi - d_lo), total = queries.size() * nd;
   for (size_t d0 = 0; d0 < total; d0 += r.batch) {
     const size_t m = std::min(total, d0 + r.batch) - d0;
     DecoyPiece dp;
@@ -1436,8 +1466,8 @@ template <class Body> void for_decoy_pieces(const Run &r, Worker &w, const Prepa
     dp.ids.resize(m);
     std::vector<int64_t> off(m + 1, 0);
     for (size_t k = 0; k < m; k++) {
-      dp.owner[k] = (int32_t)((d0 + k) / nd);
-      dp.decoy[k] = (int32_t)((d0 + k) % nd);
+      dp.owner[k] = queries[(d0 + k) / nd];
+      dp.decoy[k] = d_lo + (int32_t)((d0 + k) % nd);
       dp.ids[k] = p.ids[(size_t)dp.owner[k]];
       off[k + 1] = off[k] + (int64_t)r.seqs[(size_t)dp.ids[k]].size();
     }
@@ -1458,6 +1488,11 @@ template <class Body> void for_decoy_pieces(const Run &r, Worker &w, const Prepa
     if (prb_qbatch_accessibility(w.ctx, dqb, r.W, r.delta)) die(prb_last_error());
     body(dp);
   }
+}
+template <class Body> void for_decoy_pieces(const Run &r, Worker &w, const Prepared &p, Body body) {
+  std::vector<int32_t> all(p.ids.size());
+  std::iota(all.begin(), all.end(), 0);
+  for_decoy_pieces(r, w, p, all, 0, r.a.decoys, body);
 }
 
 // PRB_NULL_MASK=0: -z and -P search their decoys without a mask of the mode's own
@@ -1489,7 +1524,54 @@ void mask_piece_by_list(const Run &r, Worker &w, DecoyPiece &dp) {
 // (under -L those are listed pairs already): the real batch's records come to the host for that
 // (prb_search_page_summary) and go into the table from there (prb_nullset_observe); without the mask - none at all, also
 // under -L - they never leave the device (prb_search_page_observed).
+// -t -z N -H H [-D R]: the real batch against every page into the null table on the device (prb_search_page_observed: no
+// record comes to the host), then the decoys round by round: the decoys [b, b + R) of the queries that still have live
+// pairs, each piece - unless PRB_NULL_MASK=0 - under the mask of its owners' live pairs, which the device makes from the
+// table (prb_pairmask_create_live; under -L live pairs are listed pairs already); at the round's end the pairs with
+// NullLE >= H retire (prb_nullset_retire), and a query left without live pairs gets no further decoys - no shuffle, no
+// suffix array, no accessibility.  One line on stderr says how many pairs were live after each round.
+BatchResult search_seqnull_batch(const Run &r, Worker &w, Prepared &p) {
+  BatchResult res = empty_result(r);
+  const bool masked = null_mask_wanted();
+  const size_t nq = p.ids.size();
+  const int32_t N = r.a.decoys;
+  prb_nullset *ns = nullptr;
+  if (prb_nullset_create(w.ctx, p.qb, w.db, N, &ns)) die(prb_last_error());
+  res.null.reset(ns);
+  const prb_ris_opts o = opts_with(r, p.mask);
+  for (int page = 0; page < r.npages; page++)
+    if (prb_search_page_observed(w.ctx, p.qb, w.db, page, &o, ns)) die(prb_last_error());
+  std::vector<int32_t> queries(nq);
+  std::iota(queries.begin(), queries.end(), 0);
+  std::vector<int64_t> live(nq, 0);
+  std::string after;
+  for (int32_t lo = 0, hi; lo < N && !queries.empty(); lo = hi) {
+    hi = std::min(N, lo + r.a.round);
+    for_decoy_pieces(r, w, p, queries, lo, hi, [&](DecoyPiece &dp) {
+      if (masked) {
+        prb_pairmask *m = nullptr;
+        const int rc = prb_pairmask_create_live(w.ctx, ns, dp.qb.get(), dp.owner.data(), (int32_t)dp.owner.size(), &m);
+        dp.mask.reset(m);
+        if (rc) die(std::string("Error: ") + prb_last_error());
+      }
+      const prb_ris_opts od = opts_with(r, dp.mask.get());
+      for (int page = 0; page < r.npages; page++)
+        if (prb_search_page_decoys(w.ctx, dp.qb.get(), w.db, page, &od, dp.owner.data(), dp.decoy.data(), ns)) die(prb_last_error());
+    });
+    if (prb_nullset_retire(w.ctx, ns, r.a.retire_le, hi, live.data())) die(prb_last_error());
+    queries.clear();
+    for (size_t q = 0; q < nq; q++)
+      if (live[q] > 0) queries.push_back((int32_t)q);
+    after += (after.empty() ? "" : ", ") + std::to_string(hi) + ": " + std::to_string(std::accumulate(live.begin(), live.end(), (int64_t)0));
+  }
+  std::fprintf(stderr, "sequential null: %zu queries, live pairs after decoy %s; queries without live pairs: %zu\n", nq, after.c_str(), nq - queries.size());
+  if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
+  release_batch(p);
+  return res;
+}
+
 BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
+  if (r.a.given[kH]) return search_seqnull_batch(r, w, p);
   BatchResult res = empty_result(r);
   const bool masked = null_mask_wanted();
   const size_t nq = p.ids.size();
