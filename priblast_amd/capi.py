@@ -1099,11 +1099,30 @@ def search_features(ctx, qb, db, annot, opts=None, pages=None, with_counts=False
     return (recs, un, counts) if with_counts else (recs, un)
 
 
-class GroupRank(_Table):
+class _RankTable(_Table):
+    """A ranking table of a run on the device: records of DTYPE, which prb_<PREFIX>_<RECORDS> points to once it is finished."""
+    DTYPE = RECORDS = None
+
+    def add_records(self, recs):
+        """prb_<PREFIX>_add_records: a caller's DTYPE records whose `query` is the identifier already"""
+        recs = np.ascontiguousarray(recs, self.DTYPE)
+        _check(self._fn("add_records")(self.ctx.h, self.h, recs.ctypes.data if len(recs) else None, len(recs)))
+
+    def merge(self, other):
+        """prb_<PREFIX>_merge: the unfinished table `other` (over other identifiers; of any context) merged into this
+        one on the device; `other` is left empty"""
+        self.absorb(other)
+
+    def finish(self):
+        """prb_<PREFIX>_finish -> structured array DTYPE (a copy), by list - group, feature -, then rank"""
+        return self._finish(self.RECORDS, self.DTYPE)
+
+
+class GroupRank(_RankTable):
     """prb_grouprank: the N best queries per group of database sequences, in a table on the device that any number of
     batches is merged into - each as its complete, unfinished GroupSet, or as GROUP_DTYPE records -; every batch names its
     queries by identifiers of the caller's.  Close it before its context."""
-    PREFIX = "grouprank"
+    PREFIX, DTYPE, RECORDS = "grouprank", GROUP_DTYPE, "pairs"
 
     def __init__(self, ctx, ngroups, n):
         h = ctypes.c_void_p()
@@ -1116,15 +1135,6 @@ class GroupRank(_Table):
         ids = np.ascontiguousarray(ids, np.int32)
         assert len(ids) == len(gs.qb.lens)
         _check(lib().prb_grouprank_add_groupset(self.ctx.h, self.h, gs.h, ids.ctypes.data))
-
-    def add_records(self, recs):
-        """prb_grouprank_add_records: a caller's GROUP_DTYPE records whose s.query is the identifier already"""
-        recs = np.ascontiguousarray(recs, GROUP_DTYPE)
-        _check(lib().prb_grouprank_add_records(self.ctx.h, self.h, recs.ctypes.data if len(recs) else None, len(recs)))
-
-    def finish(self):
-        """prb_grouprank_finish -> structured array GROUP_DTYPE (a copy), by group, then rank"""
-        return self._finish("pairs", GROUP_DTYPE)
 
 
 def search_grouprank(ctx, db, group_of_page, ngroups, n, batches, opts=None, pages=None, with_counts=False):
@@ -1142,11 +1152,11 @@ def search_grouprank(ctx, db, group_of_page, ngroups, n, batches, opts=None, pag
     return (recs, counts) if with_counts else recs
 
 
-class FeatRank(_Table):
+class FeatRank(_RankTable):
     """prb_featrank: the N best queries per feature of an Annotation, in a table on the device that any number of batches
     is merged into - each as its complete, unfinished FeatSet, or as FEATRANK_DTYPE records -; every batch names its queries
     by identifiers of the caller's.  Close it before its annotation and its context."""
-    PREFIX = "featrank"
+    PREFIX, DTYPE, RECORDS = "featrank", FEATRANK_DTYPE, "records"
 
     def __init__(self, ctx, annot, n):
         h = ctypes.c_void_p()
@@ -1159,20 +1169,6 @@ class FeatRank(_Table):
         ids = np.ascontiguousarray(ids, np.int32)
         assert len(ids) == len(fs.qb.lens)
         _check(lib().prb_featrank_add_featset(self.ctx.h, self.h, fs.h, ids.ctypes.data))
-
-    def add_records(self, recs):
-        """prb_featrank_add_records: a caller's FEATRANK_DTYPE records whose `query` is the identifier already"""
-        recs = np.ascontiguousarray(recs, FEATRANK_DTYPE)
-        _check(lib().prb_featrank_add_records(self.ctx.h, self.h, recs.ctypes.data if len(recs) else None, len(recs)))
-
-    def merge(self, other):
-        """prb_featrank_merge: the unfinished table `other` (over other identifiers; of any context) merged into this
-        one on the device; `other` is left empty"""
-        self.absorb(other)
-
-    def finish(self):
-        """prb_featrank_finish -> structured array FEATRANK_DTYPE (a copy), by feature, then rank"""
-        return self._finish("records", FEATRANK_DTYPE)
 
     def unassigned(self):
         return lib().prb_featrank_unassigned(self.h)

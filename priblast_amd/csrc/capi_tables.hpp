@@ -4,7 +4,8 @@
 // caller's arrays, the device's `bad` flag, the merge of one table into another across contexts and devices, and what
 // every prb_*_finish starts with.  `fn_name` is the entry point and `what` the table's noun in the messages.  Every check
 // comes before a table is touched: a refused call leaves it as it was.  The per-table files keep what is theirs alone:
-// their own state checks, their kernels' launches and their create and finish.
+// their own state checks, their kernels' launches and their create and finish.  What the three ranked run tables share
+// beyond this - their merges and their finish - is in capi_ranked.hpp.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -57,38 +58,6 @@ inline std::string bad_n(int32_t n) {
 inline int finish_guard(const char *fn_name, const char *what, const prb_ctx *ctx, const TableState *t) {
   if (!ctx || !t || t->ctx != ctx) return refuse(fn_name, "bad argument (the table belongs to another context)");
   if (t->broken) return refuse(fn_name, std::string("an earlier merge into this ") + what + " table failed", PRB_ERR_STATE);
-  return PRB_OK;
-}
-
-// ---- prb_targetset_finish / prb_grouprank_finish / prb_featrank_finish: the ranked lists of a run table (rank_kernels.hpp) to the host
-// fill[0, nlists] (the last one 0) scanned, the filled slots - at most `entries` - gathered by list and rank on the
-// device by gather(off, total, out), and copied to `recs` in one copy
-template <class Rec, class Gather>
-int finish_ranked(const char *fn_name, prb_ctx *ctx, const int32_t *fill, int64_t nlists, size_t entries, std::vector<Rec> &recs, Gather gather) {
-  recs.clear();
-  if (nlists <= 0) return PRB_OK;
-  int rc;
-  ScratchBuf off, out, tmp;
-  if ((rc = off.ensure(((size_t)nlists + 1) * 8))) return rc;
-  auto fills = rocprim::make_transform_iterator(fill, ToI64());
-  if ((rc = with_temp(tmp, "rocprim::exclusive_scan", [&](void *t, size_t &b) {
-         return rocprim::exclusive_scan(t, b, fills, off.as<int64_t>(), (int64_t)0, (size_t)nlists + 1, rocprim::plus<int64_t>(), ctx->stream);
-       })))
-    return rc;
-  int64_t total = 0;
-  PRB_HIP(hipMemcpyAsync(&total, off.as<int64_t>() + nlists, 8, hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
-  if (total < 0 || (uint64_t)total > (uint64_t)entries) return refuse(fn_name, "bad record count " + std::to_string(total), PRB_ERR_STATE);
-  if (!total) return PRB_OK;
-  try {
-    recs.resize((size_t)total);
-  } catch (const std::exception &e) {
-    return refuse(fn_name, e.what(), PRB_ERR_NOMEM);
-  }
-  if ((rc = out.ensure((size_t)total * sizeof(Rec)))) return rc;
-  PRB_HIP(gather(off.as<int64_t>(), total, out.p));
-  PRB_HIP(hipMemcpyAsync(recs.data(), out.p, (size_t)total * sizeof(Rec), hipMemcpyDeviceToHost, ctx->stream));
-  PRB_HIP(hipStreamSynchronize(ctx->stream));
   return PRB_OK;
 }
 
@@ -296,34 +265,6 @@ inline int upload_owners(prb_ctx *ctx, DecoySet *t, const int32_t *owner, const 
   PRB_HIP(hipMemcpyAsync(t->own.p, owner, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
   PRB_HIP(hipMemcpyAsync(t->own.as<int32_t>() + ndq, decoy, (size_t)ndq * 4, hipMemcpyHostToDevice, ctx->stream));
   PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory: the caller's arrays may go)
-  return PRB_OK;
-}
-
-// ---- prb_grouprank_add_* / prb_featrank_add_*: a merge's candidates into the ranked lists of a run table
-// ncand candidates grouped by list - `lists`: "groups", "features"; nlists of them - and merged into the table `t` of
-// noun `what` (inside the caller's bracket of the table's timer): groups(key, val) writes their sort keys, runs(keyS,
-// valS, rkey, head) - behind the stable sort - their rank keys and the heads of the lists' runs, merge(runs) merges every
-// run into its list; 5 launches.  The table has the buffers key, keyS, val, valS, rkey, head, start and sortTmp.
-template <class T, class Groups, class Runs, class Merge>
-int merge_ranked_candidates(prb_ctx *ctx, SearchWs &w, T *t, const char *what, const char *lists, int32_t nlists, int64_t ncand, Groups groups,
-                            Runs runs, Merge merge) {
-  int rc;
-  const size_t NC = (size_t)ncand;
-  if ((rc = t->key.ensure(NC * 4)) || (rc = t->keyS.ensure(NC * 4)) || (rc = t->val.ensure(NC * 4)) || (rc = t->valS.ensure(NC * 4)) ||
-      (rc = t->rkey.ensure(NC * sizeof(TargetKey))) || (rc = t->head.ensure(NC)) || (rc = t->start.ensure(NC * 4)))
-    return rc;
-  PRB_HIP(groups(t->key.template as<uint32_t>(), t->val.template as<uint32_t>()));
-  if ((rc = sort_target_keys(ctx->stream, t->sortTmp, t->key.template as<uint32_t>(), t->keyS.template as<uint32_t>(),
-                             t->val.template as<uint32_t>(), t->valS.template as<uint32_t>(), NC, (unsigned)bits_for(std::max(nlists - 1, 1)))))
-    return rc;
-  PRB_HIP(runs(t->keyS.template as<uint32_t>(), t->valS.template as<uint32_t>(), t->rkey.template as<TargetKey>(), t->head.template as<uint8_t>()));
-  int64_t nruns = 0;
-  if ((rc = select_flagged(ctx, w, nullptr, t->head.template as<uint8_t>(), t->start.template as<uint32_t>(), NC, &nruns))) return rc;
-  if (nruns <= 0 || nruns > ncand || nruns > nlists) {
-    set_error(std::string(what) + " table: " + std::to_string(nruns) + " " + lists + " for " + std::to_string(ncand) + " candidates");
-    return PRB_ERR_STATE;
-  }
-  PRB_HIP(merge(GroupRankRuns{t->rkey.template as<TargetKey>(), t->keyS.template as<uint32_t>(), t->start.template as<uint32_t>(), nruns, ncand}));
   return PRB_OK;
 }
 

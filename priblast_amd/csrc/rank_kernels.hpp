@@ -1,15 +1,22 @@
-// The ranked top-N lists of the run tables on gfx950, shared by the per-target table (target_kernels.hip: each database
-// sequence's N best queries) and the group ranking table (grouprank_kernels.hip: each group's N best queries): the
-// order, the merge of a run of candidates into a list, the merge of two tables and the gather of the finish.  Each unit
-// wraps the bodies below in kernels of its own and says what a payload is and where a newcomer's comes from.
+// The ranked top-N lists of the run tables on gfx950 - the per-target table (each database sequence's N best queries),
+// the group ranking table (each group's) and the feature ranking table (each annotated feature's): the order, the merge
+// of a run of candidates into a list, the merge of two tables and the gather of the finish.  ranked_kernels.hip wraps
+// the bodies below in one kernel template each and says what the payloads are and where a newcomer's comes from.
 //
-// A list t (a target, a group) owns n ranked keys keys[t * n ..), n payload slots slots[t * n ..) and fill[t].  A key is
-// (energy key, query id, payload slot); the keys in use are keys[t * n, t * n + fill[t]) in rank order, and the slots
-// they name are - as a set - 0 .. fill[t] - 1.  Payloads never move: a newcomer takes a slot that was never used, or the
-// slot of an entry that the same merge pushed out, and the finish gathers in rank order.
+// A list t (a target, a group, a feature) owns n ranked keys keys[t * n ..), n payload slots slots[t * n ..) and
+// fill[t].  A key is (energy key, query id, payload slot); the keys in use are keys[t * n, t * n + fill[t]) in rank
+// order, and the slots they name are - as a set - 0 .. fill[t] - 1.  Payloads never move: a newcomer takes a slot that
+// was never used, or the slot of an entry that the same merge pushed out, and the finish gathers in rank order.
 //
-// A Source of newcomers has  uint32_t limit()  - a candidate key's `at` lies below it, else the candidate is skipped -
-// and  void put(Payload *to, const TargetKey &c)  - the payload of candidate c into a slot.
+// A Source of newcomers names its candidates by a 32-bit `at` (all ones: none).  It has
+//   uint32_t limit()                                 a candidate key's `at` lies below it, else the candidate is skipped
+//   int64_t first()                                  the list of the table that the source's list 0 is
+//   void put(Payload *to, const TargetKey &c)        the payload of candidate c into a slot
+// and, for the kernels that group a merge's candidates by list (the per-target table has two of its own instead),
+//   bool locate(int64_t c, uint32_t *list, uint32_t *at)   the list and the name of the c-th candidate; false: it names
+//                                                          a list outside the table
+//   bool key(uint32_t at, TargetKey *k)              the rank key of the candidate named `at`; false: it names a query
+//                                                    or an identifier outside the table
 #pragma once
 #include <algorithm>
 
@@ -71,8 +78,8 @@ template <class Payload> __device__ __forceinline__ void copy_payload(Payload *t
 
 // ---- the merge of a run of candidates into its list ----
 // One wavefront per run [start[run], start[run + 1]) of rkey, blockDim.x / 64 runs per workgroup; no workgroup barrier
-// anywhere.  Run `run` belongs to list list_of[start[run]] (below nlists) + lbase.  Fast path: the list is full and no
-// key of the run beats its last kept key - the wavefront has read the run's 16-byte keys and one key of the table.  Else
+// anywhere.  Run `run` belongs to list src.first() + list_of[start[run]] (below nlists).  Fast path: the list is full and
+// no key of the run beats its last kept key - the wavefront has read the run's 16-byte keys and one key of the table.  Else
 // the list's keys go to LDS (S, n entries) and the run is streamed 64 keys a step: those that beat the threshold are
 // appended to C by ballot and ordered (a bitonic network over the lanes); either list's entries find their new places by
 // rank - own index plus the other list's keys below it -, S moving in rounds of 64 from the top down (an entry only
@@ -82,7 +89,7 @@ template <class Payload> __device__ __forceinline__ void copy_payload(Payload *t
 // slot on, so the steps' writes are kept in order by a fence.
 template <class Payload, class Source>
 __device__ __forceinline__ void merge_runs(TargetKey *lds, const Source &src, const TargetKey *__restrict__ rkey, const uint32_t *__restrict__ list_of,
-                                           const uint32_t *__restrict__ start, int64_t nruns, int64_t nrec, int64_t lbase, int32_t nlists, int32_t n,
+                                           const uint32_t *__restrict__ start, int64_t nruns, int64_t nrec, int32_t nlists, int32_t n,
                                            TargetKey *__restrict__ keys, Payload *__restrict__ slots, int32_t *__restrict__ fill) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t run = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
@@ -92,7 +99,7 @@ __device__ __forceinline__ void merge_runs(TargetKey *lds, const Source &src, co
   if (a >= b || b > nrec) return;
   const uint32_t list = list_of[a];
   if (list >= (uint32_t)nlists) return;
-  const int64_t t = lbase + list;
+  const int64_t t = src.first() + list;
   TargetKey *const tk = keys + t * n;
   Payload *const ts = slots + t * n;
   int cnt = min(max(fill[t], 0), n);

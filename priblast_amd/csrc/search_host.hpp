@@ -1,5 +1,5 @@
 // What the host units of the search share (capi_pages.hip, capi_search.hip, capi_gapped.hip, capi_top.hip,
-// capi_targets.hip, capi_spans.hip, capi_lines.hip): the objects behind the C ABI's handles, the workspace of the search stages, and the
+// capi_targets.hip, capi_grouprank.hip, capi_featrank.hip, capi_spans.hip, capi_lines.hip): the objects behind the C ABI's handles, the workspace of the search stages, and the
 // rocPRIM idioms they all use.
 #pragma once
 #include <atomic>
@@ -546,6 +546,40 @@ template <class Slot> struct TopTable : MergeTable {
   size_t bytes() const { return slots_bytes() + (size_t)nq * sizeof(int32_t); }
   int32_t *fill() const { return reinterpret_cast<int32_t *>(table.template as<char>() + slots_bytes()); }
 };
+
+// What the three ranked run tables have in common (prb_targetset, prb_grouprank, prb_featrank; capi_ranked.hpp): per
+// list - a target, a group, a feature: L = targets() of them - its n best queries as the ranked lists of rank_kernels.hpp,
+// merged into for as many batches as the caller likes, and the sort buffers of those merges.  It owns all its device memory.
+// The block: TargetKey[L * n], Payload[L * n], int32_t fill[L + 1] (the last one 0)
+template <class P> struct RankedTable : RunTable {
+  using Payload = P;
+  int32_t n = 0;
+  DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per merge: the candidates in list order
+  DevBuf h_rec;                                            // prb_*_add_records: the caller's records
+  std::vector<Payload> recs;                               // prb_*_finish
+  TableFeed feed() const override { return TableFeed::kPairRecords; }
+  int take(const SubBatch &) override { return PRB_ERR_STATE; } // (no search feeds it, unless the table says otherwise)
+  size_t entries() const { return (size_t)targets() * (size_t)n; }
+  size_t bytes() const { return entries() * (sizeof(TargetKey) + sizeof(Payload)) + ((size_t)targets() + 1) * sizeof(int32_t); }
+  // the three arrays of a block at b (the table's own, or a copy of another table's)
+  TargetKey *keys_of(void *b) const { return static_cast<TargetKey *>(b); }
+  Payload *slots_of(void *b) const { return reinterpret_cast<Payload *>(static_cast<char *>(b) + entries() * sizeof(TargetKey)); }
+  int32_t *fill_of(void *b) const { return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(TargetKey) + sizeof(Payload))); }
+  RankedLists lists_of(void *b) const { return RankedLists{keys_of(b), slots_of(b), fill_of(b), targets(), n}; }
+  // every key, payload slot and fill count of the table back to "nothing", on its own device and stream
+  int clear() {
+    PRB_HIP(hipSetDevice(ctx->device));
+    PRB_HIP(hipMemsetAsync(table.p, 0, bytes(), ctx->stream));
+    PRB_HIP(hipStreamSynchronize(ctx->stream));
+    return PRB_OK;
+  }
+  void release(std::initializer_list<DevBuf *> own = {}) { // (`own`: what the table has beside)
+    if (!quiesce()) return;
+    for (DevBuf *b : {&table, &badflag, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp, &h_rec}) b->release();
+    for (DevBuf *b : own) b->release();
+  }
+  ~RankedTable() { release(); } // (also on the error paths of prb_*_create)
+};
 } // namespace prb
 
 // prb_topset_create .. prb_topset_free: the top-N table of one batch, merged into page by page (launch_top_merge)
@@ -623,29 +657,10 @@ struct prb_profset : prb::MergeTable, prb::SpanBufs {
 };
 
 // prb_targetset_create .. prb_targetset_free: the per-target table of one database, merged into sub-batch by sub-batch
-// (merge_targets, capi_targets.hip) for as many batches as the caller likes, and the sort buffers of those merges.
-// The block: TargetKey[T * n], prb_target_pair[T * n], int32_t fill[T + 1] (the last one 0)
-struct prb_targetset : prb::RunTable {
-  int32_t n = 0;
-  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per sub-batch: the records in target order
-  std::vector<prb_target_pair> pairs;         // prb_targetset_finish
-  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
+// (prb_targetset::take, capi_targets.hip) for as many batches as the caller likes: a ranked table whose lists are the
+// database's targets, page by page
+struct prb_targetset : prb::RankedTable<prb_target_pair> {
   int take(const prb::SubBatch &b) override;
-  size_t entries() const { return (size_t)targets() * (size_t)n; }
-  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)) + ((size_t)targets() + 1) * sizeof(int32_t); }
-  // the three arrays of a block at b (the table's own, or a copy of another table's)
-  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
-  prb_target_pair *slots_of(void *b) const { return reinterpret_cast<prb_target_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
-  int32_t *fill_of(void *b) const {
-    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_target_pair)));
-  }
-  void release() {
-    for (prb::DevBuf *b : {&table, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp}) b->release();
-  }
-  ~prb_targetset() { // (also on the error paths of prb_targetset_create)
-    if (table.p || ids.p || key.p) (void)hipSetDevice(ctx->device);
-    release();
-  }
 };
 
 // prb_covset_create .. prb_covset_free: the per-position coverage table of one database, merged into sub-batch by
@@ -761,30 +776,13 @@ struct prb_groupset : prb::MergeTable {
 
 // prb_grouprank_create .. prb_grouprank_free: the group ranking table of a run (capi_grouprank.hip): per group its n best
 // queries over as many batches as the caller likes, fed from each batch's complete group table or from a caller's
-// records (merge_ranked_candidates, capi_tables.hpp) - never by a search itself.  A run table with one "page": `merged` keeps a bit per
-// query identifier, tbase = {0, ngroups}.  It owns all its device memory.
-// The block: TargetKey[G * n], prb_group_pair[G * n], int32_t fill[G + 1] (the last one 0)
-struct prb_grouprank : prb::RunTable {
-  int32_t n = 0, ngroups = 0;
-  prb::DevBuf occ, sel;                                         // per merge: the group table's occupied slots
-  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // ... and the candidates in group order
-  prb::DevBuf h_rec;                                            // prb_grouprank_add_records: the caller's records
-  std::vector<prb_group_pair> pairs;                            // prb_grouprank_finish
-  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
-  int take(const prb::SubBatch &) override { return PRB_ERR_STATE; } // (no search feeds it)
-  size_t entries() const { return (size_t)ngroups * (size_t)n; }
-  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_group_pair)) + ((size_t)ngroups + 1) * sizeof(int32_t); }
-  // the three arrays of a block at b (the table's own, or a copy of another table's)
-  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
-  prb_group_pair *slots_of(void *b) const { return reinterpret_cast<prb_group_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey)); }
-  int32_t *fill_of(void *b) const {
-    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_group_pair)));
-  }
-  void release() {
-    if (!quiesce()) return;
-    for (prb::DevBuf *b : {&table, &badflag, &ids, &occ, &sel, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp, &h_rec}) b->release();
-  }
-  ~prb_grouprank() { release(); } // (also on the error paths of prb_grouprank_create)
+// records (merge_ranked_candidates, capi_ranked.hpp) - never by a search itself.  A ranked table with one "page": `merged`
+// keeps a bit per query identifier, tbase = {0, ngroups}.
+struct prb_grouprank : prb::RankedTable<prb_group_pair> {
+  int32_t ngroups = 0;
+  prb::DevBuf occ, sel; // per merge: the group table's occupied slots
+  void release() { RankedTable::release({&occ, &sel}); }
+  ~prb_grouprank() { release(); }
 };
 
 // prb_gnullset_create .. prb_gnullset_free: the group null table of one batch (capi_gnull.hip): the records that a group
@@ -957,33 +955,17 @@ struct prb_fnullset : prb::TableState, prb::DecoySet { // (`merged`: a bit per (
 
 // prb_featrank_create .. prb_featrank_free: the feature ranking table of a run (capi_featrank.hip): per feature of the
 // annotation its n best queries over as many batches as the caller likes, fed from each batch's complete feature table or
-// from a caller's records (merge_ranked_candidates, capi_tables.hpp) - never by a search itself.  A run table with one
-// "page": `merged` keeps a bit per query identifier, tbase = {0, nfeat}.  It owns all its device memory.
-// The block: TargetKey[F * n], prb_featrank_pair[F * n], int32_t fill[F + 1] (the last one 0)
-struct prb_featrank : prb::RunTable {
+// from a caller's records (merge_ranked_candidates, capi_ranked.hpp) - never by a search itself.  A ranked table with one
+// "page": `merged` keeps a bit per query identifier, tbase = {0, nfeat}.
+struct prb_featrank : prb::RankedTable<prb_featrank_pair> {
   const prb_annot *annot = nullptr;
-  int32_t n = 0, nfeat = 0;
-  int64_t unassigned = 0;                                       // summed over the feature tables merged
-  prb::DevBuf key, keyS, val, valS, rkey, head, start, sortTmp; // per merge: the candidates in feature order
-  prb::DevBuf h_rec;                                            // prb_featrank_add_records: the caller's records
-  std::vector<prb_featrank_pair> recs;                          // prb_featrank_finish
-  prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
-  int take(const prb::SubBatch &) override { return PRB_ERR_STATE; } // (no search feeds it)
-  size_t entries() const { return (size_t)nfeat * (size_t)n; }
-  size_t bytes() const { return entries() * (sizeof(prb::TargetKey) + sizeof(prb_featrank_pair)) + ((size_t)nfeat + 1) * sizeof(int32_t); }
-  // the three arrays of a block at b (the table's own, or a copy of another table's)
-  prb::TargetKey *keys_of(void *b) const { return static_cast<prb::TargetKey *>(b); }
-  prb_featrank_pair *slots_of(void *b) const {
-    return reinterpret_cast<prb_featrank_pair *>(static_cast<char *>(b) + entries() * sizeof(prb::TargetKey));
+  int32_t nfeat = 0;
+  int64_t unassigned = 0; // summed over the feature tables merged
+  int clear() {
+    if (int rc = RankedTable::clear()) return rc;
+    unassigned = 0;
+    return PRB_OK;
   }
-  int32_t *fill_of(void *b) const {
-    return reinterpret_cast<int32_t *>(static_cast<char *>(b) + entries() * (sizeof(prb::TargetKey) + sizeof(prb_featrank_pair)));
-  }
-  void release() {
-    if (!quiesce()) return;
-    for (prb::DevBuf *b : {&table, &badflag, &ids, &key, &keyS, &val, &valS, &rkey, &head, &start, &sortTmp, &h_rec}) b->release();
-  }
-  ~prb_featrank() { release(); } // (also on the error paths of prb_featrank_create)
 };
 
 namespace prb {
@@ -1040,7 +1022,7 @@ int check_search_args(const char *fn, const prb_ctx *ctx, const prb_qbatch *qb, 
 int search_page(prb_ctx *ctx, prb_qbatch *qb, prb_db *db, int32_t page, const prb_ris_opts *opts, int32_t last_stage,
                 SearchMode mode, prb_hitset **out, TableState *table = nullptr);
 // capi_search.hip: the two radix sorts of the tables' merges - by the low `bits` bits of 32-bit keys, through `tmp`
-// (capi_targets.hip), and rocPRIM's two calls for 64-bit keys (capi_spans.hip).  Every radix sort of the search is
+// (the ranked run tables, capi_ranked.hpp), and rocPRIM's two calls for 64-bit keys (capi_spans.hip).  Every radix sort of the search is
 // instantiated in that one unit: the register count and the code the compiler gives a rocPRIM sort kernel depend on
 // which other sorts the unit instantiates.  With these two in the tables' units, five kernels came out otherwise: the
 // block sort of (u32, u32), the block sort of (u64, u32) in both its `const *` and plain-pointer forms (52 VGPRs against

@@ -442,35 +442,6 @@ hipError_t launch_top_join(void *tab, int32_t *fill, const void *src, const int3
 hipError_t launch_tophits_join(void *tab, int32_t *fill, const void *src, const int32_t *src_fill, int32_t nq, int32_t n, int64_t shift,
                                hipStream_t s);
 
-// ============================================================================ target_kernels.hip: per-target table
-// (prb_search_page_targets)  A target = (page, db_id), numbered page by page; per target n ranked keys, n payload slots
-// (prb_target_pair) and a fill count.  A key: the order-preserving image of e_min, the query's identifier, and `at` - in
-// the table the payload slot of the entry (payloads never move), in a sub-batch's run the record's index.
-struct alignas(16) TargetKey {
-  uint64_t e;
-  uint32_t id, at;
-};
-// rec[0, nrec) = launch_pair_fold's records of a sub-batch: `query` (index in the batch, < nq) becomes ids[query];
-// key[i] = db_id, val[i] = i - what the stable sort by target takes
-hipError_t launch_target_ids(void *rec, int64_t nrec, const int32_t *ids, int32_t nq, uint32_t *key, uint32_t *val, hipStream_t s);
-// behind that sort (key, val sorted): rkey[i] = the rank key of record val[i] (`at` = val[i]), head[i] = 1 where key
-// changes (and for i = 0): the first record of every target's run
-hipError_t launch_target_runs(const void *rec, int64_t nrec, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head,
-                              hipStream_t s);
-// the runs [start[r], start[r + 1]) (the last one up to nrec) of rkey - run r is target tbase + db_of[start[r]] of
-// `page` (nseq sequences) - merged into the table, a wavefront per run; no (query id, page) may be in the table yet
-hipError_t launch_target_merge(const void *rec, const TargetKey *rkey, const uint32_t *db_of, const uint32_t *start, int64_t nruns,
-                               int64_t nrec, int32_t page, int64_t tbase, int32_t nseq, int32_t n, TargetKey *keys, void *slots, int32_t *fill,
-                               hipStream_t s);
-// prb_targetset_merge: per target, the table's and src's ranked entries merged under the table's order, the first n kept,
-// in the table (src is only read); a wavefront per target
-hipError_t launch_target_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
-                              int64_t ntargets, int32_t n, hipStream_t s);
-// prb_targetset_finish: out[0, total) = the filled slots by target, then rank (`rank` set); off = the exclusive scan of
-// fill over ntargets + 1 values
-hipError_t launch_target_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t ntargets, int32_t n, int64_t total,
-                                void *out, hipStream_t s);
-
 // ============================================================================ profile_kernels.hip: per-position profile
 // (prb_search_page_profile)
 // The table of one batch in HBM.  Query q owns the slots [off[q], off[q + 1]) = its len + 1 positions (the last one
@@ -653,43 +624,6 @@ hipError_t launch_group_select(const GroupTab &t, const uint32_t *occ, int64_t n
 // ... out[j] (prb_group_pair) of the slot idx[j] (top == nullptr, rank 0), or of the slot top[idx[j]] with rank idx[j] % n
 hipError_t launch_group_gather(const GroupTab &t, const uint32_t *idx, int64_t nrec, const uint32_t *top, int32_t n, void *out, hipStream_t s);
 
-// ============================================================================ grouprank_kernels.hip: group ranking table
-// (prb_grouprank_*)  Per group n ranked keys (TargetKey: `id` = the query's identifier), n payload slots (prb_group_pair)
-// and a fill count, the lists of rank_kernels.hpp as the per-target table keeps them.  The candidates of one merge come
-// from a batch's group table - its occupied slots cand[0, ncand), ascending; ids[q] = the identifier of query q - or
-// from a caller's records (prb_group_pair, s.query = the identifier).  bad: set when a candidate names a slot, a group, a
-// query or an identifier outside its table; such a candidate is skipped.
-// key[c] = the group of candidate c, val[c] = its slot / its index: what the stable sort by group takes
-hipError_t launch_grouprank_slot_groups(const GroupTab &t, const uint32_t *cand, int64_t ncand, uint32_t *key, uint32_t *val, uint32_t *bad,
-                                        hipStream_t s);
-hipError_t launch_grouprank_record_groups(const void *rec, int64_t nrec, int32_t ngroups, uint32_t *key, uint32_t *val, uint32_t *bad,
-                                          hipStream_t s);
-// behind that sort (key, val sorted): rkey[i] = (the energy key of candidate val[i], its identifier, val[i]), head[i] = 1
-// where key changes (and for i = 0): the first candidate of every group's run
-hipError_t launch_grouprank_slot_runs(const GroupTab &t, const int32_t *ids, int64_t ncand, const uint32_t *key, const uint32_t *val,
-                                      TargetKey *rkey, uint8_t *head, uint32_t *bad, hipStream_t s);
-hipError_t launch_grouprank_record_runs(const void *rec, int64_t nrec, int32_t ngroups, const uint32_t *key, const uint32_t *val, TargetKey *rkey,
-                                        uint8_t *head, uint32_t *bad, hipStream_t s);
-// the runs [start[r], start[r + 1]) (the last one up to ncand) of rkey - run r is group group_of[start[r]] - merged into
-// the table, a wavefront per run; no (identifier, group) may be in the table yet
-struct GroupRankRuns {
-  const TargetKey *rkey;
-  const uint32_t *group_of, *start;
-  int64_t nruns, ncand;
-};
-hipError_t launch_grouprank_slot_merge(const GroupTab &t, const int32_t *ids, const GroupRankRuns &r, int32_t n, TargetKey *keys, void *slots,
-                                       int32_t *fill, hipStream_t s);
-hipError_t launch_grouprank_record_merge(const void *rec, int64_t nrec, const GroupRankRuns &r, int32_t ngroups, int32_t n, TargetKey *keys,
-                                         void *slots, int32_t *fill, hipStream_t s);
-// prb_grouprank_merge: per group, the table's and src's ranked entries merged under the table's order, the first n kept,
-// in the table (src is only read); a wavefront per group
-hipError_t launch_grouprank_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
-                                 int64_t ngroups, int32_t n, hipStream_t s);
-// prb_grouprank_finish: out[0, total) = the filled slots by group, then rank (`rank` set); off = the exclusive scan of
-// fill over ngroups + 1 values
-hipError_t launch_grouprank_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t ngroups, int32_t n, int64_t total,
-                                   void *out, hipStream_t s);
-
 // ============================================================================ gnull_kernels.hip: the group null table
 // (prb_gnullset_*)  The kept (query, group) records of a finished group table, and per record how the query's decoys
 // fare against the group.  lookup[q * ngroups + g] = the record of (q, g), all ones: not kept.  A record's counters: the
@@ -839,43 +773,84 @@ hipError_t launch_ftop_merge(const FtopTab &t, const int64_t *choff, int64_t nch
 hipError_t launch_ftop_gather(const FtopTab &t, const void *rec, const int64_t *koff, const uint32_t *top, int64_t nkept, void *out,
                               hipStream_t s);
 
-// ============================================================================ featrank_kernels.hip: feature ranking table
-// (prb_featrank_*)  Per feature of the annotation n ranked keys (TargetKey: `id` = the query's identifier), n payload
-// slots (prb_featrank_pair) and a fill count, the lists of rank_kernels.hpp as the per-target table keeps them.  The
-// candidates of one merge come from a batch's unfinished feature table - the records rec[0, nrec) (prb_feature_pair) of
-// its block, named by their place; ids[q] = the identifier of query q of its nq - or from a caller's records
-// (prb_featrank_pair, f.s.query = the identifier).  bad: set when a candidate names a feature, a query or an identifier
+// ============================================================================ ranked_kernels.hip: the ranked run tables
+// (prb_search_page_targets, prb_grouprank_*, prb_featrank_*)  Per list - a target (page, db_id), numbered page by page;
+// a group; a feature of the annotation - n ranked keys, n payload slots and a fill count, the lists of rank_kernels.hpp.
+// A key: the order-preserving image of e_min, the query's identifier, and `at` - in the table the payload slot of the
+// entry (payloads never move), in a merge's run the candidate's name at its source.  The payloads: prb_target_pair,
+// prb_group_pair, prb_featrank_pair.
+struct alignas(16) TargetKey {
+  uint64_t e;
+  uint32_t id, at;
+};
+// the three arrays of a table's block (or of a copy of another table's): nlists lists of n slots, fill[nlists + 1]
+struct RankedLists {
+  TargetKey *keys;
+  void *slots;
+  int32_t *fill;
+  int64_t nlists;
+  int32_t n;
+};
+// The candidates of one merge, by their source.  bad: set when a candidate names a slot, a list, a query or an identifier
 // outside its table; such a candidate is skipped and nothing is written for it.
-struct FeatRankFeed {
+// ... launch_pair_fold's records (prb_pair_summary) of a sub-batch against `page` (nseq sequences, the lists tbase ..):
+// `query` (index in the batch, < nq) becomes ids[query] in place; there is nothing to refuse, and no flag
+struct PairFeed {
+  void *rec; // [nrec]
+  int64_t nrec;
+  const int32_t *ids; // [nq]
+  int32_t nq, page, nseq;
+  int64_t tbase;
+};
+// ... the occupied slots cand[0, ncand), ascending, of a batch's group table; ids[q] = the identifier of query q
+struct GroupSlotFeed {
+  GroupTab t;
+  const uint32_t *cand; // [ncand]
+  int64_t ncand;
+  const int32_t *ids; // [t.nq]
+  uint32_t *bad;
+};
+// ... the records rec[0, nrec) (prb_feature_pair) of a batch's unfinished feature table, named by their place in its
+// block; ids[q] = the identifier of query q of its nq
+struct FeatTableFeed {
   const void *rec; // [nrec]
   int64_t nrec;
   const int32_t *ids; // [nq]
   int32_t nq, nfeat;
+  uint32_t *bad;
 };
-// key[c] = the feature of candidate c, val[c] = its place / its index: what the stable sort by feature takes
-hipError_t launch_featrank_table_features(const FeatRankFeed &t, uint32_t *key, uint32_t *val, uint32_t *bad, hipStream_t s);
-hipError_t launch_featrank_record_features(const void *rec, int64_t nrec, int32_t nfeat, uint32_t *key, uint32_t *val, uint32_t *bad,
-                                           hipStream_t s);
+// ... a caller's records (Payload = prb_group_pair, prb_featrank_pair: their query is the identifier already, their
+// group / feature lies below nlists), named by their index
+template <class Payload> struct RecordFeed {
+  const void *rec; // [nrec]
+  int64_t nrec;
+  int32_t nlists;
+  uint32_t *bad;
+};
+// key[c] = the list of candidate c, val[c] = its name at its source: what the stable sort by list takes
+template <class Feed> hipError_t launch_ranked_lists(const Feed &f, uint32_t *key, uint32_t *val, hipStream_t s);
 // behind that sort (key, val sorted): rkey[i] = (the energy key of candidate val[i], its identifier, val[i]), head[i] = 1
-// where key changes (and for i = 0): the first candidate of every feature's run
-hipError_t launch_featrank_table_runs(const FeatRankFeed &t, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head,
-                                      uint32_t *bad, hipStream_t s);
-hipError_t launch_featrank_record_runs(const void *rec, int64_t nrec, int32_t nfeat, const uint32_t *key, const uint32_t *val, TargetKey *rkey,
-                                       uint8_t *head, uint32_t *bad, hipStream_t s);
-// the runs of rkey (GroupRankRuns: run r is feature group_of[start[r]]) merged into the table, a wavefront per run; no
-// (identifier, feature) may be in the table yet
-hipError_t launch_featrank_table_merge(const FeatRankFeed &t, const GroupRankRuns &r, int32_t n, TargetKey *keys, void *slots, int32_t *fill,
-                                       hipStream_t s);
-hipError_t launch_featrank_record_merge(const void *rec, int64_t nrec, const GroupRankRuns &r, int32_t nfeat, int32_t n, TargetKey *keys,
-                                        void *slots, int32_t *fill, hipStream_t s);
-// prb_featrank_merge: per feature, the table's and src's ranked entries merged under the table's order, the first n kept,
-// in the table (src is only read); a wavefront per feature
-hipError_t launch_featrank_join(TargetKey *keys, void *slots, int32_t *fill, const TargetKey *skeys, const void *sslots, const int32_t *sfill,
-                                int64_t nfeat, int32_t n, hipStream_t s);
-// prb_featrank_finish: out[0, total) = the filled slots by feature, then rank (`rank` set); off = the exclusive scan of
-// fill over nfeat + 1 values
-hipError_t launch_featrank_gather(const TargetKey *keys, const void *slots, const int64_t *off, int64_t nfeat, int32_t n, int64_t total,
-                                  void *out, hipStream_t s);
+// where key changes (and for i = 0): the first candidate of every list's run
+template <class Feed>
+hipError_t launch_ranked_runs(const Feed &f, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head, hipStream_t s);
+// the runs [start[r], start[r + 1]) (the last one up to ncand) of rkey - run r is list list_of[start[r]] of the feed -
+// merged into the table, a wavefront per run; no (identifier, list) - of the feed's page - may be in the table yet
+struct RankedRuns {
+  const TargetKey *rkey;
+  const uint32_t *list_of, *start;
+  int64_t nruns, ncand;
+};
+template <class Feed> hipError_t launch_ranked_merge(const Feed &f, const RankedRuns &r, const RankedLists &l, hipStream_t s);
+// (the per-target table's candidates are grouped by two kernels of its own)
+template <> hipError_t launch_ranked_lists(const PairFeed &f, uint32_t *key, uint32_t *val, hipStream_t s);
+template <>
+hipError_t launch_ranked_runs(const PairFeed &f, const uint32_t *key, const uint32_t *val, TargetKey *rkey, uint8_t *head, hipStream_t s);
+// prb_*_merge: per list, the table's and src's (same shape) ranked entries merged under the table's order, the first n
+// kept, in the table (src is only read); a wavefront per list
+template <class Payload> hipError_t launch_ranked_join(const RankedLists &l, const RankedLists &src, hipStream_t s);
+// prb_*_finish: out[0, total) = the filled slots by list, then rank (`rank` set); off = the exclusive scan of fill over
+// nlists + 1 values
+template <class Payload> hipError_t launch_ranked_gather(const RankedLists &l, const int64_t *off, int64_t total, void *out, hipStream_t s);
 
 // ============================================================================ fnull_kernels.hip: the feature null table
 // (prb_fnullset_*)  The kept (query, feature) records of a finished feature table, and per record how the query's decoys

@@ -8,8 +8,10 @@ would run (taken from `make --dry-run --always-make`), `-c` replaced by `--cuda-
 is cut into functions; what depends only on a function's position in its file - the function index in local
 labels such as .LBB<n>_<m> - is normalised away.  For every kernel of OLD_TREE the report says whether NEW_TREE
 has a kernel of the same symbol name, in whichever file, with the same instruction stream and the same
-.amdhsa_ descriptor (registers, LDS, scratch and the rest).  Device functions that were not inlined are
-compared the same way.  Exit status 1 on any difference or missing symbol.  Needs hipcc, no GPU.
+.amdhsa_ descriptor (registers, LDS, scratch and the rest).  A kernel whose symbol is gone counts as "renamed" when
+a kernel that only NEW_TREE has is the same instruction stream and descriptor; the pair is printed, old name to new.
+Device functions that were not inlined are compared like the kernels.  Exit status 1 on any difference or missing
+symbol.  Needs hipcc, no GPU.
 """
 import argparse
 import concurrent.futures
@@ -137,9 +139,23 @@ def main():
     names = demangle(sorted(set(old) | set(new)))
     files = lambda variants: ",".join(sorted(variants)) if variants else "-"
     is_kernel = lambda variants: any(desc is not None for _, desc in variants.values())
+    # a kernel that only NEW_TREE has, by what it is - its versions with its own symbol (a directive may name it) taken
+    # out -: the code of an old kernel under another name
+    nameless = lambda sym, variants: frozenset((tuple(line.replace(sym, "@") for line in c), d) for c, d in variants.values())
+    only_new = {}
+    for s in sorted(set(new) - set(old), key=lambda s: names[s]):
+        if is_kernel(new[s]):
+            only_new.setdefault(nameless(s, new[s]), []).append(s)
     bad = 0
+    renamed = set()
     for sym in sorted(old, key=lambda s: (files(old[s]), names[s])):
         o, n = old[sym], new.get(sym, {})
+        if not n and is_kernel(o) and nameless(sym, o) in only_new:
+            same = only_new[nameless(sym, o)]  # (several of one code: each taken once, while they last)
+            to = same.pop(0) if len(same) > 1 else same[0]
+            renamed.add(to)
+            print(f"{'renamed':10s} {'kernel':8s} {files(o)} -> {files(new[to])}: {names[sym]} -> {names[to]}")
+            continue
         if not n:
             verdict = "MISSING"
         else:  # the same versions of the code (one, unless the copies of a library's kernel differ between files)
@@ -155,12 +171,12 @@ def main():
                 for tag, variants in (("old", o), ("new", n)):
                     for name, (c, d) in sorted(variants.items()):
                         print(f"           {tag} {name}: {len(c)} lines, {figures(d)}")
-    added = sorted(set(new) - set(old))
+    added = sorted(set(new) - set(old) - renamed)
     for sym in added:
         print(f"{'new':10s} {'kernel' if is_kernel(new[sym]) else 'function':8s} - -> {files(new[sym])}: {names[sym]}")
     kernels = sum(1 for s in old if is_kernel(old[s]))
-    print(f"{kernels} kernels and {len(old) - kernels} device functions of {a.old_tree}: {len(old) - bad} identical in {a.new_tree}, "
-          f"{bad} different or missing; {len(added)} only in {a.new_tree}")
+    print(f"{kernels} kernels and {len(old) - kernels} device functions of {a.old_tree}: {len(old) - bad - len(renamed)} identical in {a.new_tree}, "
+          f"{len(renamed)} renamed, {bad} different or missing; {len(added)} only in {a.new_tree}")
     return 1 if bad else 0
 
 
