@@ -225,6 +225,8 @@ int prb_ctx_synchronize(prb_ctx *ctx);
  *   region kernel, launches = 4, or 3 when there is no region; prb_covset_merge: 1);
  * "null" (prb_search_page_observed / _decoys, prb_nullset_observe / _add_pairs: the scatter or the fold into the null
  *   table, launches = 1 per sub-batch with final hits; prb_nullset_finish: the selection and the gather, launches = 2);
+ * "fdr" (prb_nullset_finish_fdr: the key pass, launches = 1, then the sort, the rank pass, the step-up pass and the scatter,
+ *   launches = 4; nothing without observed pairs);
  * "group" (prb_search_page_groups / prb_groupset_add_pairs: the fold into the group table, launches = 3 per sub-batch with
  *   final hits; prb_groupset_merge: 1; prb_groupset_finish: the flags, the selections and the gather, launches = 2 to 5);
  * "grouprank" (prb_grouprank_add_groupset: the group table's occupied slots merged into the group ranking table - flags,
@@ -773,6 +775,53 @@ const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns);
 void prb_nullset_counts(const prb_nullset *ns, int64_t counts[3]);
 void prb_nullset_decoy_counts(const prb_nullset *ns, int64_t counts[3]);
 void prb_nullset_free(prb_nullset *ns);
+
+/* ---- a Benjamini-Hochberg q-value per pair of the null table (`ris -t -z N -Q`), ranked on the device ----
+ * A query is searched against every target, so the p-values of a null table are read many at a time: which pairs survive
+ * that many tests?  Sequential Monte-Carlo p-values (prb_nullset_retire) followed by the step-up procedure is the form the
+ * false-discovery-rate correction was worked out for (Besag & Clifford 1991; Benjamini & Hochberg 1995).  All in integers:
+ * take one query q.  Its observed pairs are a with num_a = null_le_a + 1 and den_a = decoys_a + 1 (decoys_a: N, or the
+ * `upto` at which the pair retired); the p-value is the exact rational p_a = num_a / den_a.  tests_q is the number of
+ * hypotheses of q - the targets it was searched against; an unobserved target has p = 1 and takes part through tests_q
+ * only.
+ *   rank_a    the observed pairs b of q with p_b <= p_a, a itself among them; equal rationals share it (1/2 and 2/4)
+ *   FDR_a     tests_q * num_a / (den_a * rank_a)
+ *   QValue_a  min(1, the minimum of FDR_b over the observed pairs b of q with p_b >= p_a), kept as the minimising pair's
+ *             triple (q_num, q_den, q_rank) = (num_g, den_g, rank_g): among equal fractions the g of lowest rank, among
+ *             those - which share their p - the one of lowest den.  A minimum above 1 is the triple (0, 0, 0).
+ * A host prints 1 for (0, 0, 0) and else (double)(tests * q_num) / (double)((uint64_t)q_den * q_rank): both operands are
+ * exact in double, so one division rounds it (prb_write_null_fdr_lines).  No float decides an order: p-values are ordered
+ * by the 41-bit key (num << 40) / den, which is exact for denominators up to 100001, FDR fractions by cross-multiplication
+ * in 64 bits (DESIGN.md has both arguments).  Every figure is a count over a total order or a minimum under one, so they
+ * are - bit for bit - independent of everything the null table's records are independent of, and of the order in which
+ * the sort leaves equal keys.
+ *   prb_nullset_finish_fdr  prb_nullset_finish - every check and every refusal of it, the same records in the same order,
+ *                           byte for byte - with the figures beside them.  tests[nq] = tests_q per query, or NULL: every
+ *                           target of the database.  PRB_ERR_ARG, checked on the host before anything is enqueued, when a
+ *                           tests[q] is below 1 or 2^31 or more, when the database has 2^30 targets or more (the cross
+ *                           products would leave 64 bits) or the batch more than 2^23 queries (the sort key would).  The
+ *                           observed pairs per query are known on the device only: they are counted there by the key
+ *                           pass, behind the selection, and a tests[q] below its query's count is PRB_ERR_ARG before the
+ *                           ranking is enqueued.  A call refused with PRB_ERR_ARG leaves the table as it was - unfinished,
+ *                           to be finished by either entry.  A slot whose null_le exceeds its decoys (decoys beyond `upto`
+ *                           were merged before prb_nullset_retire) has no p-value: it raises the table's `bad` flag
+ *                           (PRB_ERR_STATE, the table is unusable, nothing is written; so is a table whose counts and selection disagree).  After a plain prb_nullset_finish the call does nothing,
+ *                           like a second finish
+ *   prb_nullset_fdr         the figures, parallel to prb_nullset_pairs; NULL after a plain finish
+ *   prb_fdr_chunk           the entries of a query's sorted segment that the step-up pass scans at a time (tests place
+ *                           segments across its multiples)
+ * Stage timer "fdr": the key pass (launches = 1), then the sort by (query, p-key), the rank pass, the step-up pass and the
+ * scatter (launches = 4); nothing for a table without observed pairs.  The selection and the gather stay under "null". */
+typedef struct prb_null_fdr {
+  int64_t tests;                       /* tests_q of the pair's query */
+  uint32_t rank, q_rank, q_num, q_den; /* rank_a; the triple of QValue_a */
+} prb_null_fdr;
+#ifdef __cplusplus
+static_assert(sizeof(prb_null_fdr) == 24, "prb_null_fdr: no padding");
+#endif
+int prb_nullset_finish_fdr(prb_ctx *ctx, prb_nullset *ns, const int64_t *tests);
+const prb_null_fdr *prb_nullset_fdr(const prb_nullset *ns);
+int32_t prb_fdr_chunk(void);
 
 /* ---- one record per (query, group of targets) (`ris -t -G FILE`): a group table on the device ----
  * A transcriptome lists isoforms that share most of their exons, so a strong interaction comes back once per isoform.  A
@@ -1392,6 +1441,15 @@ int prb_write_region_lines(const prb_db *db, int32_t nq_total, const char *const
  * printed as %.6g. */
 int prb_write_null_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_null_pair *recs,
                          int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes);
+/* The lines of `ris -t -z N -Q` for one batch: the lines of prb_write_null_lines for recs[0, n), and behind each one the
+ * figures of fdr[0, n) (prb_nullset_fdr, parallel to recs):
+ *   ,Tests,Rank,QValue
+ * QValue = 1 for the triple (0, 0, 0), else (Tests * q_num) / (q_den * q_rank): two exact doubles, one division, printed
+ * as %.6g like PValue.  PRB_ERR_ARG for a figure with tests or rank below 1, or whose triple is neither (0, 0, 0) nor
+ * three positive numbers. */
+int prb_write_null_fdr_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked,
+                             const prb_null_pair *recs, const prb_null_fdr *fdr, int64_t n, int64_t id0, int fd, int64_t *lines,
+                             int64_t *bytes);
 
 /* ---- multi-GPU: one process per GPU, the final hit gather over RCCL (xGMI) ----
  * Replaces MergeOutput's MPI token ring (rna_interaction_search.cpp:426-487) and, with the caller

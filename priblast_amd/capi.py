@@ -77,6 +77,9 @@ assert REGION_DTYPE.itemsize == 72
 NULL_DTYPE = np.dtype(PAIR_DTYPE.descr + [("page", "<i4"), ("decoys", "<i4"), ("null_hits", "<i8"), ("null_le", "<i8"),
                                           ("null_min", "<f8")])
 assert NULL_DTYPE.itemsize == 96
+# prb_null_fdr (priblast_hip.h): the Benjamini-Hochberg figures of one record of NULL_DTYPE
+FDR_DTYPE = np.dtype([("tests", "<i8"), ("rank", "<u4"), ("q_rank", "<u4"), ("q_num", "<u4"), ("q_den", "<u4")])
+assert FDR_DTYPE.itemsize == 24
 
 # prb_group_pair: the embedded prb_pair_summary's fields (the group's best member pair), then that pair's page, the group,
 # the members with a hit, the rank within the query and the members' hits (`ris -t -G FILE`)
@@ -229,6 +232,9 @@ SYMBOLS = {
                                              ctypes.c_void_p, c_i64]),
     "prb_nullset_retire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i32, ctypes.c_void_p]),
     "prb_nullset_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_nullset_finish_fdr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "prb_nullset_fdr": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "prb_fdr_chunk": (c_i32, []),
     "prb_nullset_size": (c_i64, [ctypes.c_void_p]),
     "prb_nullset_pairs": (ctypes.c_void_p, [ctypes.c_void_p]),
     "prb_nullset_counts": (None, [ctypes.c_void_p, P(c_i64)]),
@@ -236,6 +242,8 @@ SYMBOLS = {
     "prb_nullset_free": (None, [ctypes.c_void_p]),
     "prb_write_null_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                             c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
+    "prb_write_null_fdr_lines": (ctypes.c_int, [ctypes.c_void_p, c_i32, P(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                c_i64, c_i64, ctypes.c_int, P(c_i64), P(c_i64)]),
     "prb_groupset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_void_p), c_i32, P(ctypes.c_void_p)]),
     "prb_search_page_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32, P(RisOpts), ctypes.c_void_p]),
     "prb_groupset_add_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i32, ctypes.c_void_p, c_i64]),
@@ -980,6 +988,16 @@ class NullSet(_Table):
         """prb_nullset_finish -> structured array NULL_DTYPE (a copy), by query, then page, then db_id"""
         return self._finish("pairs", NULL_DTYPE)
 
+    def finish_fdr(self, tests=None):
+        """prb_nullset_finish_fdr -> (NULL_DTYPE records as finish() returns them, FDR_DTYPE figures parallel to them); tests =
+        the hypotheses per query (None: every target of the database)"""
+        t = None if tests is None else np.ascontiguousarray(tests, np.int64)
+        assert t is None or len(t) == len(self.qb.lens)
+        _check(lib().prb_nullset_finish_fdr(self.ctx.h, self.h, None if t is None or not len(t) else t.ctypes.data))
+        n = lib().prb_nullset_size(self.h)
+        figs = lib().prb_nullset_fdr(self.h)  # (NULL: the table was finished without them)
+        return _records(lib().prb_nullset_pairs(self.h), n, NULL_DTYPE), _records(figs, n if figs else 0, FDR_DTYPE)
+
     def decoy_counts(self):
         c = (c_i64 * 3)()
         lib().prb_nullset_decoy_counts(self.h, c)
@@ -1452,12 +1470,13 @@ def _decoy_batches(ctx, seqs, db, ndecoys, seed, file_pos0, opts, decoy_batch, t
 
 
 def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask=True, decoy_batch=None, pages=None,
-                with_counts=False):
+                with_counts=False, fdr=False):
     """The null table of the batch qb (of the sequences seqs, the first of which stands at place file_pos0 of its file)
     against db with ndecoys decoys per query -> structured array NULL_DTYPE, by query, then page, then db_id.  mask: every
     decoy batch is searched under a pair mask that allows its owners' observed targets only (the same records either way).
     decoy_batch: decoys per batch (all at once by default); pages: their order.  with_counts: -> (records, counts of the
-    real batch's searches, counts of the decoys')."""
+    real batch's searches, counts of the decoys').  fdr: the records are (records, FDR_DTYPE figures), finished with the
+    q-values over every target of the database (NullSet.finish_fdr)."""
     o = opts or default_opts()
     pages = list(range(db.npages)) if pages is None else list(pages)
     with NullSet(ctx, qb, db, ndecoys) as ns:
@@ -1480,7 +1499,7 @@ def search_null(ctx, qb, seqs, db, ndecoys, seed=1, file_pos0=0, opts=None, mask
             for dqb, own, dec, od in batches:
                 for p in pages:
                     ns.decoys(dqb, p, own, dec, od)
-        recs = ns.finish()
+        recs = ns.finish_fdr() if fdr else ns.finish()
         counts = tuple(int(x) for x in counts) if mask else ns.counts()
         dcounts = ns.decoy_counts()
     return (recs, counts, dcounts) if with_counts else recs
@@ -1656,6 +1675,14 @@ def write_featrank_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start
     fs, fe = np.ascontiguousarray(feat_start, np.int32), np.ascontiguousarray(feat_end, np.int32)
     return _write(lib().prb_write_featrank_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None, len(recs), names,
                   fs.ctypes.data, fe.ctypes.data, len(feat_names), id0, fd)
+
+
+def write_null_fdr_lines(db, qnames, qlen_unmasked, recs, fdr, id0=0, fd=-1):
+    """Lines of `ris -t -z N -Q` for one batch: recs and fdr as NullSet.finish_fdr returns them -> (lines, bytes)"""
+    recs, fdr = np.ascontiguousarray(recs, NULL_DTYPE), np.ascontiguousarray(fdr, FDR_DTYPE)
+    assert len(recs) == len(fdr)
+    return _write(lib().prb_write_null_fdr_lines, db, qnames, qlen_unmasked, recs.ctypes.data if len(recs) else None,
+                  fdr.ctypes.data if len(recs) else None, len(recs), id0, fd)
 
 
 def write_fnull_lines(db, qnames, qlen_unmasked, recs, feat_names, feat_start, feat_end, id0=0, fd=-1):

@@ -133,6 +133,29 @@ int prb_write_null_lines(const prb_db *db, int32_t nq, const char *const *qnames
       [&](const NullView &v, LineSink &sink) { return format_null_batch(v, db->tabs, id0, sink, format_threads()); });
 }
 
+int prb_write_null_fdr_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_null_pair *recs,
+                             const prb_null_fdr *fdr, int64_t n, int64_t id0, int fd, int64_t *lines, int64_t *bytes) {
+  return write_lines<NullFdrView>(
+      "prb_write_null_fdr_lines", n >= 0 && (!n || (recs && fdr)), db, nq, qnames, qlen_unmasked, lines, bytes, fd,
+      [&](NullFdrView &v) {
+        for (int64_t i = 0; i < n; i++) {
+          const prb_null_pair &x = recs[i];
+          const prb_null_fdr &f = fdr[i];
+          const bool capped = !f.q_num && !f.q_den && !f.q_rank, triple = f.q_num && f.q_den && f.q_rank;
+          if (x.page < 0 || x.page >= (int32_t)db->pages.size() || x.s.query < 0 || x.s.query >= nq || x.s.db_id < 0 ||
+              x.s.db_id >= db->pages[(size_t)x.page].nseq || x.s.hits < 1 || x.decoys < 1 || x.null_hits < 0 || x.null_hits > x.decoys ||
+              x.null_le < 0 || x.null_le > x.null_hits || (i && x.s.query < recs[i - 1].s.query) || f.tests < 1 || f.tests >= (int64_t)1 << 31 ||
+              f.rank < 1 || !(capped || triple))
+            return bad_record("prb_write_null_fdr_lines: record " + std::to_string(i) + " is inconsistent");
+        }
+        v.r = recs;
+        v.f = fdr;
+        v.n = n;
+        return (int)PRB_OK;
+      },
+      [&](const NullFdrView &v, LineSink &sink) { return format_null_fdr_batch(v, db->tabs, id0, sink, format_threads()); });
+}
+
 int prb_write_group_lines(const prb_db *db, int32_t nq, const char *const *qnames, const int32_t *qlen_unmasked, const prb_group_pair *recs,
                           int64_t n, const char *const *group_names, const int32_t *group_sizes, int32_t ngroups, int64_t id0, int fd,
                           int64_t *lines, int64_t *bytes) {

@@ -182,9 +182,73 @@ int prb_nullset_add_pairs(prb_ctx *ctx, prb_nullset *ns, int32_t page, const int
   return PRB_OK;
 }
 
-// the observed slots selected on the device, their records gathered there and copied once
-int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
-  const char *fn = kFinishFn;
+// prb_nullset_finish_fdr, between the selection and the gather: the figures of the nsel selected slots ns->sel into
+// ns->fdr_out, in the selection's order.  Two brackets of the "fdr" timer: the key pass, which also counts the observed
+// pairs per query - the host checks `tests` against the counts and turns them into the segments' bounds -, then the sort
+// by (query, p-key) - capi_search.hip's (search_host.hpp: no sort is instantiated here) -, the rank pass, the step-up pass
+// and the scatter.  A refusal of `tests` leaves the table as it was.
+static int rank_fdr(const char *fn, prb_ctx *ctx, prb_nullset *ns, int64_t nsel, const int64_t *tests) {
+  const size_t n = (size_t)nsel, NQ = (size_t)ns->nq;
+  int rc;
+  ScratchBuf keyA, keyB, valA, valB, frac, ent, qv, cnt, off, tests_dev, tmp;
+  if ((rc = keyA.ensure(n * 8)) || (rc = keyB.ensure(n * 8)) || (rc = valA.ensure(n * 4)) || (rc = valB.ensure(n * 4)) || (rc = frac.ensure(n * 8)) ||
+      (rc = ent.ensure(n * 16)) || (rc = qv.ensure(n * 16)) || (rc = cnt.ensure(NQ * 4)) || (rc = off.ensure((NQ + 1) * 8)) ||
+      (rc = tests_dev.ensure(NQ * 8)) || (rc = ns->fdr_out.ensure(n * sizeof(prb_null_fdr))))
+    return rc;
+  const int bits = kFdrKeyBits + bits_for(std::max(0, ns->nq - 1));
+  auto sort_keys = [&](void *t, size_t &b) {
+    return sort_span_keys(t, b, keyA.as<uint64_t>(), keyB.as<uint64_t>(), valA.as<uint32_t>(), valB.as<uint32_t>(), n, bits, ctx->stream);
+  };
+  size_t tmp_bytes = 0;
+  PRB_HIP(sort_keys(nullptr, tmp_bytes));
+  if ((rc = tmp.ensure(std::max<size_t>(tmp_bytes, 16)))) return rc;
+  std::vector<uint32_t> c;
+  std::vector<int64_t> o, tq;
+  try {
+    c.assign(NQ, 0);
+    o.assign(NQ + 1, 0);
+    tq.assign(NQ, ns->targets());
+  } catch (const std::exception &e) {
+    return refuse(fn, e.what(), PRB_ERR_NOMEM);
+  }
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(hipMemsetAsync(cnt.p, 0, NQ * 4, ctx->stream));
+  PRB_HIP(launch_fdr_keys(ns->view(), ns->sel.as<uint32_t>(), nsel, keyA.as<unsigned long long>(), valA.as<uint32_t>(), frac.as<uint2>(),
+                          cnt.as<uint32_t>(), ctx->stream));
+  PRB_HIP(hipMemcpyAsync(c.data(), cnt.p, NQ * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = ctx->time_end(ModeTimer::kFdr, 1))) return rc; // (synchronises: the copy is over)
+  if ((rc = fetch_bad(ctx, ns))) return rc;
+  if (ns->bad) return refuse(fn, "a selected slot lies outside the null table, or its null_le exceeds the decoys it has seen", PRB_ERR_STATE);
+  for (size_t q = 0; q < NQ; q++) {
+    if (tests) tq[q] = tests[q];
+    if ((int64_t)c[q] > tq[q])
+      return refuse(fn, "tests[" + std::to_string(q) + "] = " + std::to_string(tq[q]) + " is below the " + std::to_string(c[q]) +
+                            " observed pairs of query " + std::to_string(q));
+    o[q + 1] = o[q] + (int64_t)c[q];
+  }
+  if (o[NQ] != nsel) { // (the device's counts and its selection disagree: the table is not to be trusted)
+    ns->broken = true;
+    return refuse(fn, "the queries' segments hold " + std::to_string(o[NQ]) + " pairs, the selection " + std::to_string(nsel), PRB_ERR_STATE);
+  }
+  PRB_HIP(hipMemcpyAsync(off.p, o.data(), (NQ + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipMemcpyAsync(tests_dev.p, tq.data(), NQ * 8, hipMemcpyHostToDevice, ctx->stream));
+  PRB_HIP(hipStreamSynchronize(ctx->stream)); // (pageable memory)
+  const FdrTab f{keyB.as<unsigned long long>(), valB.as<uint32_t>(), off.as<int64_t>(), tests_dev.as<int64_t>(), frac.as<uint2>(),
+                 ent.as<uint4>(),               qv.as<uint4>(),      ns->badflag.as<uint32_t>(), nsel, ns->nq};
+  if ((rc = ctx->time_begin())) return rc;
+  PRB_HIP(sort_keys(tmp.p, tmp_bytes));
+  PRB_HIP(launch_fdr_rank(f, ctx->stream));
+  PRB_HIP(launch_fdr_stepup(f, ctx->stream));
+  PRB_HIP(launch_fdr_scatter(f, ns->fdr_out.p, ctx->stream));
+  if ((rc = ctx->time_end(ModeTimer::kFdr, 4))) return rc; // (synchronises: the scratch is read no more)
+  if ((rc = fetch_bad(ctx, ns))) return rc;
+  if (ns->bad) return refuse(fn, "an index of the ranking lies outside its list", PRB_ERR_STATE);
+  return PRB_OK;
+}
+
+// the observed slots selected on the device, their records gathered there and copied once; with_fdr: their figures
+// ranked between the two (rank_fdr) and copied beside them
+static int finish_null(const char *fn, prb_ctx *ctx, prb_nullset *ns, bool with_fdr, const int64_t *tests) {
   if (int rc = finish_guard(fn, "null", ctx, ns)) return rc;
   if (ns->finished) return PRB_OK; // (the records are on the host already)
   if (ns->bad) return refuse(fn, "a record merged into this null table named a query, a sequence, an owner or a decoy outside it", PRB_ERR_STATE);
@@ -201,7 +265,16 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
       return refuse(fn, std::to_string(have) + " of " + std::to_string(need) + " (query, decoy, page) searches are merged: every decoy of every query that has live pairs against every page comes first",
                     PRB_ERR_STATE);
   }
+  if (with_fdr) {
+    if (ns->targets() >= (int64_t)1 << 30)
+      return refuse(fn, "the database has " + std::to_string(ns->targets()) + " targets (fewer than 2^30 for the q-values: their cross products stay within 64 bits)");
+    if (ns->nq > 1 << 23) return refuse(fn, "the batch has " + std::to_string(ns->nq) + " queries (at most 2^23 for the q-values: the sort key holds the query above 41 bits)");
+    for (int32_t q = 0; tests && q < ns->nq; q++)
+      if (tests[q] < 1 || tests[q] >= (int64_t)1 << 31)
+        return refuse(fn, "need 1 <= tests[q] < 2^31 (tests[" + std::to_string(q) + "] = " + std::to_string(tests[q]) + ")");
+  }
   ns->pairs.clear();
+  ns->fdr.clear();
   PRB_HIP(hipSetDevice(ctx->device));
   const int64_t S = ns->slots();
   if (S > 0) {
@@ -212,10 +285,18 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
     int64_t nsel = 0;
     if ((rc = select_flagged(ctx, w, nullptr, ns->obs.as<uint8_t>(), ns->sel.as<uint32_t>(), (size_t)S, &nsel))) return rc;
     if (nsel < 0 || nsel > S) return refuse(fn, "bad record count " + std::to_string(nsel), PRB_ERR_STATE);
+    const bool ranked = with_fdr && nsel > 0;
+    if (ranked) { // (the selection's share of the "null" timer; the gather's follows the ranking)
+      if ((rc = ctx->time_end(ModeTimer::kNull, 1))) return rc;
+      if ((rc = rank_fdr(fn, ctx, ns, nsel, tests))) return rc;
+      if ((rc = ctx->time_begin())) return rc;
+    }
     if (nsel) {
       try {
         ns->pairs.resize((size_t)nsel);
+        if (ranked) ns->fdr.resize((size_t)nsel);
       } catch (const std::exception &e) {
+        ns->pairs.clear();
         return refuse(fn, e.what(), PRB_ERR_NOMEM);
       }
       const size_t bytes = (size_t)nsel * sizeof(prb_null_pair);
@@ -223,18 +304,23 @@ int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) {
       PRB_HIP(launch_null_gather(ns->view(), ns->sel.as<uint32_t>(), nsel, ns->tbase_dev.as<int64_t>(), (int32_t)ns->observed.size(), ns->out.p,
                                  ctx->stream));
       PRB_HIP(hipMemcpyAsync(ns->pairs.data(), ns->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      if (ranked) PRB_HIP(hipMemcpyAsync(ns->fdr.data(), ns->fdr_out.p, (size_t)nsel * sizeof(prb_null_fdr), hipMemcpyDeviceToHost, ctx->stream));
     }
-    if ((rc = ctx->time_end(ModeTimer::kNull, nsel ? 2 : 1))) return rc; // (synchronises: the copy is over)
+    if ((rc = ctx->time_end(ModeTimer::kNull, ranked ? 1 : nsel ? 2 : 1))) return rc; // (synchronises: the copy is over)
     if ((rc = fetch_bad(ctx, ns))) return rc;
     if (ns->bad) {
       ns->pairs.clear();
+      ns->fdr.clear();
       return refuse(fn, "a selected slot lies outside the null table", PRB_ERR_STATE);
     }
   }
   ns->finished = true;
+  ns->has_fdr = with_fdr;
   ns->release(); // (only the host records are needed from here on)
   return PRB_OK;
 }
+int prb_nullset_finish(prb_ctx *ctx, prb_nullset *ns) { return finish_null(kFinishFn, ctx, ns, false, nullptr); }
+int prb_nullset_finish_fdr(prb_ctx *ctx, prb_nullset *ns, const int64_t *tests) { return finish_null("prb_nullset_finish_fdr", ctx, ns, true, tests); }
 
 // One pass over the slots (k_null_retire), the live slots left per query counted there and copied to the host
 int prb_nullset_retire(prb_ctx *ctx, prb_nullset *ns, int64_t min_le, int32_t upto, int64_t *live_per_query) {
@@ -285,6 +371,8 @@ int prb_nullset_retire(prb_ctx *ctx, prb_nullset *ns, int64_t min_le, int32_t up
 
 int64_t prb_nullset_size(const prb_nullset *ns) { return ns ? (int64_t)ns->pairs.size() : -1; }
 const prb_null_pair *prb_nullset_pairs(const prb_nullset *ns) { return ns ? ns->pairs.data() : nullptr; }
+const prb_null_fdr *prb_nullset_fdr(const prb_nullset *ns) { return ns && ns->has_fdr ? ns->fdr.data() : nullptr; }
+int32_t prb_fdr_chunk(void) { return kFdrChunk; }
 void prb_nullset_counts(const prb_nullset *ns, int64_t counts[3]) {
   for (int i = 0; i < 3; i++) counts[i] = ns ? ns->counts[i] : 0;
 }

@@ -37,11 +37,11 @@ struct StageTimer {
 
 // The stages outside the full-output search (prb_ctx::mode_timers): one row each, the value and - in the same order -
 // the name that prb_ctx_stage_ms answers to
-enum class ModeTimer { kSummary, kTop, kProfile, kTopHits, kTargets, kDistinct, kChain, kAllow, kCoverage, kNull, kGroup, kGnull, kEval, kGroupRank, kFeature, kFnull, kFeatRank, kCount };
+enum class ModeTimer { kSummary, kTop, kProfile, kTopHits, kTargets, kDistinct, kChain, kAllow, kCoverage, kNull, kGroup, kGnull, kEval, kGroupRank, kFeature, kFnull, kFeatRank, kFdr, kCount };
 inline constexpr const char *kModeTimerName[(int)ModeTimer::kCount] = {"summary", "top",   "profile",  "tophits", "targets", "distinct",
                                                                        "chain",   "allow", "coverage", "null",    "group",   "gnull",
                                                                        "eval",    "grouprank", "feature", "fnull",
-                                                                       "featrank"};
+                                                                       "featrank", "fdr"};
 
 } // namespace prb
 

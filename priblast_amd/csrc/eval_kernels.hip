@@ -11,6 +11,7 @@
 #include "launch.hpp"
 #include "search_device.hpp"
 #include "search_kernels.hpp"
+#include "stepup_device.hpp"
 
 namespace prb {
 
@@ -78,23 +79,6 @@ __global__ __launch_bounds__(kBlock) void k_eval_count(const uint32_t *__restric
   atomicAdd(&cnt[q], 1u);
 }
 
-// the first place in key[a, b) whose key is above k (b when there is none)
-__device__ __forceinline__ int64_t eval_upper(const unsigned long long *__restrict__ key, int64_t a, int64_t b, unsigned long long k) {
-  while (a < b) {
-    const int64_t m = (a + b) >> 1;
-    if (key[m] <= k) a = m + 1;
-    else b = m;
-  }
-  return a;
-}
-
-// the bounds [*s0, *s1) of query q's segment in a list of n entries, or false when they are not an order within the list
-__device__ __forceinline__ bool eval_segment(const int64_t *__restrict__ off, int32_t q, int64_t n, int64_t *s0, int64_t *s1) {
-  *s0 = off[q];
-  *s1 = off[q + 1];
-  return *s0 >= 0 && *s0 <= *s1 && *s1 <= n;
-}
-
 // k_eval_rank: a lane per real entry i.  Its query is the segment that i lies in; its rank the upper bound of its key in
 // that segment - so equal keys share it -, its null_le the upper bound in the same query's decoy segment.
 __global__ __launch_bounds__(kBlock) void k_eval_rank(EvalTab t) {
@@ -107,13 +91,13 @@ __global__ __launch_bounds__(kBlock) void k_eval_rank(EvalTab t) {
     else hi = m;
   }
   int64_t r0, r1, d0, d1;
-  if (!eval_segment(t.roff, lo, t.nreal, &r0, &r1) || i < r0 || i >= r1 || !eval_segment(t.doff, lo, t.ndecoy, &d0, &d1)) {
+  if (!segment_bounds(t.roff, lo, t.nreal, &r0, &r1) || i < r0 || i >= r1 || !segment_bounds(t.doff, lo, t.ndecoy, &d0, &d1)) {
     atomicOr(t.bad, 1u);
     return;
   }
   const unsigned long long k = t.rkey[i];
-  t.rank[i] = (uint32_t)(eval_upper(t.rkey, i + 1, r1, k) - r0);
-  t.null_le[i] = (uint32_t)(eval_upper(t.dkey, d0, d1, k) - d0);
+  t.rank[i] = (uint32_t)(sorted_upper(t.rkey, i + 1, r1, k) - r0);
+  t.null_le[i] = (uint32_t)(sorted_upper(t.dkey, d0, d1, k) - d0);
 }
 
 // A fraction x / y of the suffix minimum: null_le / rank of one real entry (rank >= 1), or "none" = (all ones) / 0, which
@@ -124,16 +108,14 @@ __device__ __forceinline__ bool eval_le(uint2 a, uint2 b) { return (uint64_t)a.x
 __device__ __forceinline__ uint2 eval_min(uint2 above, uint2 below) { return eval_le(below, above) ? below : above; }
 
 // k_eval_qmin: the workgroup of query blockIdx.x walks the query's segment from its end in chunks of kEvalChunk.  Thread
-// t of a chunk has the entry t places below the chunk's top, so an inclusive scan in thread order is a suffix minimum in
-// key order: __shfl_up within the wavefront, the wavefronts' totals through LDS, and `carry` = the minimum over all the
-// chunks above, which every thread keeps in registers.
+// t of a chunk has the entry t places below the chunk's top; the chunk's suffix minimum and the carry over the chunks
+// above are chunk_suffix_min's (stepup_device.hpp).
 __global__ __launch_bounds__(kEvalChunk) void k_eval_qmin(EvalTab t) {
   constexpr int kWaves = kEvalChunk / 64;
   __shared__ uint2 wave_total[kWaves];
   const int32_t q = (int32_t)blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int64_t lo, hi;
-  if (!eval_segment(t.roff, q, t.nreal, &lo, &hi)) { // (the same for every thread)
+  if (!segment_bounds(t.roff, q, t.nreal, &lo, &hi)) { // (the same for every thread)
     if (threadIdx.x == 0) atomicOr(t.bad, 1u);
     return;
   }
@@ -142,27 +124,13 @@ __global__ __launch_bounds__(kEvalChunk) void k_eval_qmin(EvalTab t) {
     const int64_t p = top - 1 - (int64_t)threadIdx.x;
     const bool live = p >= lo;
     uint2 v = live ? make_uint2(t.null_le[p], t.rank[p]) : make_uint2(kEvalNoneNum, 0u);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint2 above = make_uint2(__shfl_up(v.x, d), __shfl_up(v.y, d));
-      if (lane >= d) v = eval_min(above, v);
-    }
-    if (lane == 63) wave_total[wave] = v;
-    __syncthreads();
-    uint2 pre = carry; // everything above this wavefront's entries
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) {
-      if (w == wave) v = eval_min(pre, v);
-      pre = eval_min(pre, wave_total[w]);
-    }
-    carry = pre; // ... and above the next chunk's
+    v = chunk_suffix_min<kWaves>(v, carry, wave_total, [](uint2 above, uint2 below) { return eval_min(above, below); });
     if (live) {
       // min(1, v): a minimum above 1 is stored as ndecoys / (ndecoys * 1)
       if ((uint64_t)v.x > (uint64_t)t.ndecoys * v.y) v = make_uint2((uint32_t)t.ndecoys, 1u);
       t.qnum[p] = v.x;
       t.qden[p] = v.y;
     }
-    __syncthreads(); // (wave_total is written again)
   }
 }
 
@@ -174,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_eval_lookup(EvalTab t, const int32_t
   prb_eval_score r{};
   const int32_t q = query[i];
   int64_t s0, s1;
-  if (q < 0 || q >= t.nq || !eval_segment(t.roff, q, t.nreal, &s0, &s1)) {
+  if (q < 0 || q >= t.nq || !segment_bounds(t.roff, q, t.nreal, &s0, &s1)) {
     atomicOr(t.bad, 1u);
     out[i] = r;
     return;

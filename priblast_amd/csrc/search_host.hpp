@@ -728,7 +728,10 @@ struct prb_nullset : prb::DecoyTable {
                                      // live slots, else `upto` of the call that found it without
   prb::DevBuf h_rec;                 // prb_nullset_observe / _add_pairs: the caller's records
   prb::DevBuf sel, out;              // prb_nullset_finish: the observed slots, their records
+  prb::DevBuf fdr_out;               // prb_nullset_finish_fdr: their figures
   std::vector<prb_null_pair> pairs;  // prb_nullset_finish
+  std::vector<prb_null_fdr> fdr;     // prb_nullset_finish_fdr: parallel to pairs
+  bool has_fdr = false;              // ... finished it
   prb::TableFeed feed() const override { return prb::TableFeed::kPairRecords; }
   int take(const prb::SubBatch &b) override;
   int64_t targets() const { return tbase.empty() ? 0 : tbase.back(); }
@@ -743,7 +746,7 @@ struct prb_nullset : prb::DecoyTable {
   prb::NullPage page_view(size_t page) const { return prb::NullPage{tbase[page], (int32_t)(tbase[page + 1] - tbase[page])}; }
   void release() {
     if (!quiesce()) return;
-    for (prb::DevBuf *b : {&table, &obs, &live, &live_dev, &badflag, &tbase_dev, &own, &h_rec, &sel, &out}) b->release();
+    for (prb::DevBuf *b : {&table, &obs, &live, &live_dev, &badflag, &tbase_dev, &own, &h_rec, &sel, &out, &fdr_out}) b->release();
   }
   ~prb_nullset() { release(); } // (also on the error paths of prb_nullset_create)
 };

@@ -584,6 +584,42 @@ hipError_t launch_null_live_mask(const NullTab &t, const LiveMaskRows &r, uint32
 // prb_nullset_finish: out[j] (prb_null_pair) of the observed slot idx[j]; tbase[npages + 1] = the pages' first targets
 hipError_t launch_null_gather(const NullTab &t, const uint32_t *idx, int64_t n, const int64_t *tbase, int32_t npages, void *out, hipStream_t s);
 
+// ============================================================================ fdr_kernels.hip: q-values of the null table
+// (prb_nullset_finish_fdr)  Per observed pair of a null table the Benjamini-Hochberg figures of include/priblast_hip.h,
+// all in integers.  The n observed slots sel[0, n) ascend, so place j of sel is record j of the finish.  A pair's p-value
+// is num / den = (null_le + 1) / (decoys + 1); its sort key (query << kFdrKeyBits) | ((num << 40) / den) orders the pairs
+// of a query exactly as their p-values and makes equal p-values collide.  After the sort: key / place [n] in
+// (query, p-value) order, off[nq + 1] the queries' segments, and per sorted entry ent = (num, den, rank, first) - rank =
+// the end of its run of equal keys, first = the run's start, both counted from the segment's start - and qv = the
+// triple (q_num, q_den, q_rank, 0) of the suffix minimum from the entry on.  bad (the null table's): a slot, a place, a
+// query or a segment lies outside its range, or a slot holds a p-value above 1.
+inline constexpr int kFdrKeyBits = 41;  // p-keys lie in [0, 2^40]
+inline constexpr int kFdrChunk = 256;   // the entries of a segment that the workgroup of launch_fdr_stepup scans at a time
+inline constexpr uint32_t kFdrMaxDen = 100001; // ndecoys + 1 at most: with ranks below 2^30 the cross products stay below 2^64
+struct FdrTab {
+  const unsigned long long *key; // [n] sorted
+  const uint32_t *place;         // [n] sorted
+  const int64_t *off;            // [nq + 1]
+  const int64_t *tests;          // [nq]
+  const uint2 *frac;             // [n] by place: (num, den)
+  uint4 *ent, *qv;               // [n] sorted
+  uint32_t *bad;
+  int64_t n;
+  int32_t nq;
+};
+// the key pass, a lane per place j: key[j], place[j] = j, frac[j], and cnt[query] (zeroed by the caller) += 1, one atomic
+// per wavefront and query
+hipError_t launch_fdr_keys(const NullTab &t, const uint32_t *sel, int64_t n, unsigned long long *key, uint32_t *place, uint2 *frac,
+                           uint32_t *cnt, hipStream_t s);
+// behind the sort, a lane per sorted entry: its segment from its key, the ends of its run by bisection, ent
+hipError_t launch_fdr_rank(const FdrTab &f, hipStream_t s);
+// the suffix minimum of tests * num / (den * rank) within every query's segment, from the highest p-value down, compared
+// by cross-multiplication in 64 bits with ties to the lower rank, then the lower den; a workgroup per query walking its
+// segment in chunks of kFdrChunk (chunk_suffix_min, stepup_device.hpp); a minimum above 1 is stored as (0, 0, 0)
+hipError_t launch_fdr_stepup(const FdrTab &f, hipStream_t s);
+// out[place] (prb_null_fdr) = the query's tests, the entry's rank and the triple at the start of its run, a lane per entry
+hipError_t launch_fdr_scatter(const FdrTab &f, void *out, hipStream_t s);
+
 // ============================================================================ group_kernels.hip: the group table
 // (prb_groupset_*)  The table of one batch against one database in HBM: a slot per (query q, group g), slot
 // q * ngroups + g.  A slot: the best member pair's summary record, the 128-bit key it won with - the energy key of its

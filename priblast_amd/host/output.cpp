@@ -263,6 +263,33 @@ void format_null_piece(const Piece &pc, const NullView &v, const std::vector<Seq
   }
 }
 
+// in place of a line's newline: the Benjamini-Hochberg columns and the newline
+void put_fdr_columns(Buf &b, const prb_null_fdr &x) {
+  b.n--; // (the newline)
+  char *p = b.room(120);
+  char *const p0 = p;
+  for (long long f : {(long long)x.tests, (long long)x.rank}) {
+    *p++ = ',';
+    p = put_int(p, f);
+  }
+  *p++ = ',';
+  // (both operands are integers below 2^53: one rounding, the division's)
+  p = put_g(p, x.q_den == 0 ? 1.0 : (double)((uint64_t)x.tests * x.q_num) / (double)((uint64_t)x.q_den * x.q_rank));
+  *p++ = '\n';
+  b.n += (size_t)(p - p0);
+}
+
+// the `-z` line, then the Benjamini-Hochberg columns
+void format_null_fdr_piece(const Piece &pc, const NullFdrView &v, const std::vector<SeqTable> &tabs, Buf &b) {
+  int64_t id = pc.id;
+  for (int64_t i = pc.i0; i < pc.i1; i++) {
+    const prb_null_pair &x = v.r[i];
+    put_summary_line(b, id++, v.names[pc.q], v.qlen_unmasked[pc.q], tabs[x.page], x.s);
+    put_null_columns(b, x.decoys, x.null_hits, x.null_le, x.null_min);
+    put_fdr_columns(b, v.f[i]);
+  }
+}
+
 // the `-t` line of the group's best member x, then - in place of its newline - the group columns
 void put_group_line(Buf &b, int64_t id, const std::string &qname, int32_t qlen, const std::vector<SeqTable> &tabs, const prb_group_pair &x,
                     const char *const *group_names, const int32_t *group_sizes) {
@@ -456,6 +483,13 @@ int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, 
   return format_records(
       v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
       [&](const Piece &pc, Buf &b) { format_null_piece(pc, v, tabs, b); }, id0, sink, threads);
+}
+
+int64_t format_null_fdr_batch(const NullFdrView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {
+  // (one "page", as for the null records)
+  return format_records(
+      v.nq, 1, [&](size_t) { return v.n; }, [&](size_t, int64_t i) { return v.r[i].s.query; },
+      [&](const Piece &pc, Buf &b) { format_null_fdr_piece(pc, v, tabs, b); }, id0, sink, threads);
 }
 
 int64_t format_group_batch(const GroupView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads) {

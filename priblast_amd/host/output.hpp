@@ -88,6 +88,16 @@ struct NullView : QueryView {
   int64_t n = 0;
 };
 int64_t format_null_batch(const NullView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
+// Lines of `ris -t -z N -Q` (prb_nullset_pairs with prb_nullset_fdr beside them): the `-z` line of every record, and
+// behind it the Benjamini-Hochberg figures of its pair:
+//   ... ,Decoys,NullHits,NullLE,NullMin,PValue ,Tests,Rank,QValue
+// Tests = the hypotheses of the query, Rank = the query's pairs whose p-value is not above the line's, QValue = 1 for the
+// triple (0, 0, 0), else (Tests * q_num) / (q_den * q_rank) - two integers that are exact in double, one division -, six
+// significant digits like PValue.
+struct NullFdrView : NullView {
+  const prb_null_fdr *f = nullptr; // [n], parallel to r
+};
+int64_t format_null_fdr_batch(const NullFdrView &v, const std::vector<SeqTable> &tabs, int64_t id0, LineSink &sink, int threads);
 
 // Lines of `ris -t -G FILE` (prb_groupset_pairs): the `-t` line of every group's best member with the group columns behind
 // it, in the records' order (by query, then group or rank), numbered from id0 on:

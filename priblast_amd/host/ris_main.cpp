@@ -92,7 +92,13 @@
 // (prb_pairmask_create_live), and a query without live pairs gets no further decoys.  No record reaches the host between
 // rounds.  `-H` needs -z, `-D` needs -H.
 //
-// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N -B -H -D have one table (kSwitchTable) that every
+// `ris -t -z N -Q [-H H [-D R]]` puts a Benjamini-Hochberg q-value behind every -z line: the null table is finished with
+// prb_nullset_finish_fdr, which ranks each query's p-values on the device as exact fractions and takes the step-up
+// minimum there (finish_null_table); the records and their order are those of the run without -Q, and three columns
+// follow them: Tests - the targets the query was searched against, under -L the distinct targets listed for it -,
+// Rank and QValue.  `-Q` takes no argument and needs -z.
+//
+// How the file is laid out.  The switches -t -n -q -k -b -u -j -r -c -z -Z -G -P -E -R -A -F -N -B -H -D -Q have one table (kSwitchTable) that every
 // refusal is generated from, and decide one OutputMode.  ris_main is a sequence of steps over one Run: parse_args (then
 // load_pairlist, load_groups and load_features, which read the files of -L, -G and -A), rank_setup, open_workers, join_ranks (the
 // Rendezvous), read_seq_tables, open_output (header_text), plan_batches, then run_workers or run_ranks (the Gatherer), and
@@ -221,6 +227,14 @@ void usage() {
             "              -E; the output depends on N, INT, R and -Z only - not on PRB_BATCH, PRB_DEVICES, PRB_SPLIT or\n"
             "              PRB_NULL_MASK=0, which searches every round against every target)\n"
             "    -D INT    with -H: the decoys per round, R; the last round may be short [default:10; 1 <= INT <= N]\n"
+            "    -Q        with -t -z N: a Benjamini-Hochberg q-value per query-target pair, ranked on the GPU.  A query is tested\n"
+            "              against every target it is searched against - Tests of them: the targets of the database, under -L\n"
+            "              the targets listed for the query; a target without a hit has p = 1.  Behind every -z line Tests, Rank =\n"
+            "              the query's lines whose PValue is not above the line's (as exact fractions: 1/2 and 2/4 are equal), and\n"
+            "              QValue = the lowest Tests * PValue / Rank over the query's lines of this PValue or above, at most 1.\n"
+            "              With -H the q-values are over the sequential p-values (Besag-Clifford stopping, then Benjamini-\n"
+            "              Hochberg).  The lines and their order are those of the run without -Q (with -H, -D, -Z, -u, -j, -L;\n"
+            "              not with -P, -F, -E; the output does not depend on PRB_BATCH, PRB_DEVICES, PRB_SPLIT or PRB_NULL_MASK)\n"
             "    -G STR    with -t: one line per query-group pair, folded on the GPU.  The file STR names the groups (genes, say):\n"
             "              one target per line, target name, a tab, group name; empty lines and lines that begin with # are\n"
             "              skipped; a target the file does not list is a group of its own, named like the target.  Every line\n"
@@ -325,7 +339,7 @@ constexpr bool runs_decoys(OutputMode m) {
 // what it needs, and whether it is refused with one process per GPU (the gather carries hit records only).  The refusals
 // are generated from this table (check_switches, check_rank_mode) and keep their precedence: the rows from the last to the
 // first, a row's partners from the first to the last.
-enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kFB, kH, kHRound, kSwitches };
+enum Switch { kT, kN, kQ, kK, kB, kU, kJ, kR, kC, kZ, kZSeed, kG, kP, kE, kGR, kA, kF, kFN, kFB, kH, kHRound, kQValue, kSwitches };
 constexpr unsigned bit(Switch s) { return 1u << s; }
 struct SwitchRow {
   char letter;
@@ -363,6 +377,8 @@ constexpr SwitchRow kSwitchTable[kSwitches] = {
     // (-P, -F and -E make decoys of their own and are refused with -z: -H is refused with them through its need of -z)
     {'H', "sequential p-values: a pair takes no more decoys once H of them reach its minimum energy", 0, kZ, false},
     {'D', "the decoys per round of the sequential p-values", 0, kH, false},
+    // (likewise: -P, -F and -E are refused with -Q through its need of -z)
+    {'Q', "a Benjamini-Hochberg q-value per pair of the null table", 0, kZ, false},
 };
 std::string described(int s) { return std::string("-") + kSwitchTable[s].letter + " (" + kSwitchTable[s].what + ")"; }
 
@@ -795,7 +811,7 @@ Args parse_args(int argc, char **argv) {
   Args a;
   prb_ris_opts_default(&a.o);
   int c;
-  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:B:H:D:")) != -1) {
+  while ((c = getopt(argc, argv, "i:o:d:l:e:y:x:f:g:s:m:p:a:btn:qk:ujr:c:L:z:Z:G:P:E:R:A:F:N:B:H:D:Q")) != -1) {
     switch (c) {
     case 'i': a.in = optarg; break;
     case 'o': a.out = optarg; break;
@@ -830,6 +846,7 @@ Args parse_args(int argc, char **argv) {
     case 'B': a.given[kFB] = true, a.featrank = parse_count(optarg); break;
     case 'H': a.given[kH] = true, a.retire_le = parse_count(optarg); break;
     case 'D': a.given[kHRound] = true, a.round = parse_count(optarg); break;
+    case 'Q': a.given[kQValue] = true; break;
     case 'Z': {
       char *end = nullptr;
       errno = 0;
@@ -1209,7 +1226,7 @@ std::string header_text(const Run &r) {
   case OutputMode::kNull:
     return header + "Id,Query name, Query Length, Target name, Target Length, Hits, Minimum Interaction Energy, "
                     "Sum of Interaction Energies, Accessibility Energy, Hybridization Energy, BasePair, Decoys, Null Hits, Null LE, "
-                    "Null Minimum Energy, P Value\n";
+                    "Null Minimum Energy, P Value" + (a.given[kQValue] ? ", Tests, Rank, Q Value\n" : "\n");
   case OutputMode::kScored:
     return header + "Id,Query name, Query Length, Target name, Target Length, Accessibility Energy, Hybridization Energy, "
                     "Interaction Energy, BasePair, Decoys, Null LE, Rank, E Value, Q Value\n";
@@ -1519,6 +1536,29 @@ void mask_piece_by_list(const Run &r, Worker &w, DecoyPiece &dp) {
   if (r.a.have_pairlist) dp.mask.reset(batch_mask(r, w.ctx, dp.qb.get(), w.db, dp.ids));
 }
 
+// The null table finished: as it is, or - with -Q - with the Benjamini-Hochberg figures of its pairs ranked on the device
+// (prb_nullset_finish_fdr).  A query's tests are the targets it was searched against: every target of the database, or
+// under -L the distinct targets that the list names for it or for every query - the list's own count, on the host already
+// (a query without any has no pair either: 1).
+void finish_null_table(const Run &r, Worker &w, const Prepared &p, prb_nullset *ns) {
+  if (!r.a.given[kQValue]) {
+    if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
+    return;
+  }
+  std::vector<int64_t> tests;
+  if (p.mask) {
+    tests.assign(p.ids.size(), 0);
+    for (size_t q = 0; q < tests.size(); q++) {
+      std::vector<int64_t> listed = r.list.every;
+      const std::vector<int64_t> &own = r.list.of_query[(size_t)p.ids[q]];
+      listed.insert(listed.end(), own.begin(), own.end());
+      std::sort(listed.begin(), listed.end());
+      tests[q] = std::max<int64_t>(std::unique(listed.begin(), listed.end()) - listed.begin(), 1);
+    }
+  }
+  if (prb_nullset_finish_fdr(w.ctx, ns, p.mask ? tests.data() : nullptr)) die(prb_last_error());
+}
+
 // -t -z N: the real batch against every page into a null table of its own, then its decoys against every page.  Unless
 // PRB_NULL_MASK=0, a piece is searched under a pair mask that allows each decoy the observed targets of its owner only
 // (under -L those are listed pairs already): the real batch's records come to the host for that
@@ -1565,7 +1605,7 @@ BatchResult search_seqnull_batch(const Run &r, Worker &w, Prepared &p) {
     after += (after.empty() ? "" : ", ") + std::to_string(hi) + ": " + std::to_string(std::accumulate(live.begin(), live.end(), (int64_t)0));
   }
   std::fprintf(stderr, "sequential null: %zu queries, live pairs after decoy %s; queries without live pairs: %zu\n", nq, after.c_str(), nq - queries.size());
-  if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
+  finish_null_table(r, w, p, ns);
   release_batch(p);
   return res;
 }
@@ -1605,7 +1645,7 @@ BatchResult search_null_batch(const Run &r, Worker &w, Prepared &p) {
     for (int page = 0; page < r.npages; page++)
       if (prb_search_page_decoys(w.ctx, dp.qb.get(), w.db, page, &od, dp.owner.data(), dp.decoy.data(), ns)) die(prb_last_error());
   });
-  if (prb_nullset_finish(w.ctx, ns)) die(prb_last_error());
+  finish_null_table(r, w, p, ns);
   release_batch(p);
   return res;
 }
@@ -1882,6 +1922,12 @@ int64_t write_job(const Run &r, BatchJob job, int64_t id, LineSink &sink) {
     v.n = prb_nullset_size(job.res.null.get());
     for (int64_t i = 0; i < v.n; i++)
       if (!in_range(r, v.nq, v.r[i].s, v.r[i].page)) die("Error: bad record in the null table");
+    if (const prb_null_fdr *f = prb_nullset_fdr(job.res.null.get())) { // (-Q)
+      prb::NullFdrView vf;
+      static_cast<prb::NullView &>(vf) = v;
+      vf.f = f;
+      return written_or_die(prb::format_null_fdr_batch(vf, r.tabs, id, sink, threads));
+    }
     return written_or_die(prb::format_null_batch(v, r.tabs, id, sink, threads));
   }
   case OutputMode::kGroups: {
